@@ -17,9 +17,14 @@ crashes at import.  ``python -m torch.distributed.run`` is only the launcher (it
 WORLD_SIZE / MASTER_*); barrier, max-over-ranks and handing the RCCL unique id to the ranks go through
 ``tbmodels_amd.rendezvous.FileGroup`` (single node).  The eigenvalue all-gather is RCCL.
 
-Rank 0 prints ONE JSON line with the contract fields plus ``roofline`` (the H(k) MFMA kernel, timed
-with HIP events on the library's stream) and ``cpu_baseline`` (the oracle = port of the reference's
-NumPy/SciPy algorithm, timed on this box's host cores on a bounded sample).
+A plain run sets up, warms up, times the steps and prints ONE JSON line (rank 0) with the contract fields
+(``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``) and the run's configuration.
+``--dump-outputs DIR`` then also writes the eigenvalues of the last timed step as ``DIR/eigenvalues.npy`` (float64;
+a fixed, seeded sample of rows above 64 MB; ``--construct-only``: H(k) as ``hamiltonian_real.npy`` and
+``hamiltonian_imag.npy``).  Everything else the line used to carry runs only with ``--full``:
+``roofline`` (the H(k) MFMA kernel, timed with HIP events on the library's stream), ``cpu_baseline`` (the oracle =
+port of the reference's NumPy/SciPy algorithm, timed on the host's cores on a bounded sample), the host-buffer
+and one-k legs, the other BASELINE configs, the strong-scaling leg and the parity checks against the oracle.
 """
 
 import argparse
@@ -68,7 +73,15 @@ def parse_args():
     ap.add_argument("--dry-ranks", action="store_true",
                     help="no GPU: every rank walks the control flow of a --gpus N run with tools/standin_lib.py in place of libtbk "
                          "and a tiny model (CPU test of the exact launch command; the numbers mean nothing)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg of the line: CPU baselines, roofline and stage times, "
+                         "host-buffer and one-k calls, the other configs, the strong-scaling leg, the checks against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def build_model_arrays(cfg_name, n_r_override=0):
@@ -98,6 +111,42 @@ def stage(lib, device, arrays):
                                             _lib.ptr(arrays["r_ptr"]), _lib.ptr(arrays["row"]), _lib.ptr(arrays["col"]),
                                             _lib.ptr(np.ascontiguousarray(arrays["val"])), ctypes.byref(handle)))
     return handle
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20231015
+
+
+def dump_row_sample(n_rows, row_bytes):
+    """Rows to dump: None (all of them) when they fit in DUMP_LIMIT_BYTES, else a sorted sample of as many as fit, drawn
+    with a fixed seed -- the same rows for the same shape in every run and every build."""
+    keep = max(1, DUMP_LIMIT_BYTES // row_bytes)
+    if n_rows <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=keep, replace=False))
+
+
+def dump_outputs(lib, device, directory, d_out, n_rows, row_shape, complex_rows=False):
+    """`n_rows` rows of shape `row_shape` (float64, or complex128 with `complex_rows`) at device pointer `d_out` -> .npy
+    files in `directory`: eigenvalues.npy, or hamiltonian_real.npy + hamiltonian_imag.npy for complex rows."""
+    os.makedirs(directory, exist_ok=True)
+    dtype = np.complex128 if complex_rows else np.float64
+    row_bytes = int(np.prod(row_shape)) * np.dtype(dtype).itemsize
+    rows = dump_row_sample(n_rows, row_bytes)
+    if rows is None or n_rows * row_bytes <= (4 << 30):  # (small rows: one copy, then the sample on the host)
+        host = np.empty((n_rows,) + tuple(row_shape), dtype=dtype)
+        _lib.check(lib.tbk_memcpy_d2h(device, _lib.ptr(host), d_out, host.nbytes))
+        if rows is not None:
+            host = host[rows]
+    else:
+        host = np.empty((len(rows),) + tuple(row_shape), dtype=dtype)
+        for i, row in enumerate(rows):
+            _lib.check(lib.tbk_memcpy_d2h(device, _lib.ptr(host[i]), ctypes.c_void_p(d_out.value + int(row) * row_bytes), row_bytes))
+    if complex_rows:
+        np.save(os.path.join(directory, "hamiltonian_real.npy"), np.ascontiguousarray(host.real))
+        np.save(os.path.join(directory, "hamiltonian_imag.npy"), np.ascontiguousarray(host.imag))
+    else:
+        np.save(os.path.join(directory, "eigenvalues.npy"), host)
 
 
 def measured_traffic(kernel, k_per_launch):
@@ -829,9 +878,10 @@ def main():
     cpu_all_rows = None
     cpu_all_other = {}
     per_proc_all = {"cfg1": 64, "cfg2": 256, "cfg3": 24, "cfg4": 256, "cfg5": 2}  # ~5-10 s each
-    run_others = (world == 1 and args.config == "cfg2" and not args.construct_only and not args.nk and not args.nr
+    # (without --full: none of the legs after the clock, only the timed steps and the contract fields)
+    run_others = (args.full and world == 1 and args.config == "cfg2" and not args.construct_only and not args.nk and not args.nr
                   and not args.dry_ranks and os.environ.get("TBK_BENCH_SKIP_CONFIGS") != "1")
-    if rank == 0 and world == 1 and args.cpu_sample != 0 and not args.construct_only and not args.dry_ranks:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample != 0 and not args.construct_only and not args.dry_ranks:
         cpu_all, cpu_all_rows = cpu_baseline_all_cores(arrays, k_slab, per_proc_all[args.config])
         if run_others and os.environ.get("TBK_BENCH_CPU_LIGHT") != "1":
             # all-core row of the sparse config too; it forks, so it runs here, before the GPU is touched
@@ -961,10 +1011,11 @@ def main():
     barrier()
     if not args.construct_only:
         _lib.check(lib.tbk_eigenval_check(model))
-    _lib.check(lib.tbk_model_set_option(model, _lib.TBK_OPT_TIMING, 1))
     ms = (ctypes.c_double * _lib.TBK_T_COUNT)()
     launches = (ctypes.c_int64 * _lib.TBK_T_COUNT)()
-    _lib.check(lib.tbk_get_timing(model, ms, launches, 1))
+    if args.full:  # HIP events around every stage of the timed steps: the roofline entries and stage_ms_per_step
+        _lib.check(lib.tbk_model_set_option(model, _lib.TBK_OPT_TIMING, 1))
+        _lib.check(lib.tbk_get_timing(model, ms, launches, 1))
 
     barrier()
     t0 = time.perf_counter()
@@ -976,13 +1027,24 @@ def main():
         elapsed = group.allreduce_max(elapsed)
     if not args.construct_only:
         _lib.check(lib.tbk_eigenval_check(model))
-    _lib.check(lib.tbk_get_timing(model, ms, launches, 1))
+    if args.full:
+        _lib.check(lib.tbk_get_timing(model, ms, launches, 1))
     stage_ms = {name: ms[i] for i, name in enumerate(_lib.STAGE_NAMES)}
     stage_n = {name: launches[i] for i, name in enumerate(_lib.STAGE_NAMES)}
 
-    # --- after the clock: per-rank split of one step (N > 1), and the host-buffer API leg (N = 1) ---------------
+    # --- the outputs of the last timed step: what a caller of the timed path receives ----------------------------------
+    if args.dump_outputs and rank == 0:
+        last = (step_no[0] - 1) & 1
+        if args.construct_only:
+            dump_outputs(lib, device, args.dump_outputs, d_h, nk_gpu, (n_orb, n_orb), complex_rows=True)
+        elif comm is not None:  # every rank receives the all-gathered eigenvalues of all slabs
+            dump_outputs(lib, device, args.dump_outputs, d_gather_pair[last], world * nk_gpu, (n_orb,))
+        else:
+            dump_outputs(lib, device, args.dump_outputs, d_e_pair[last], nk_gpu, (n_orb,))
+
+    # --- after the clock (--full): per-rank split of one step (N > 1), and the host-buffer API leg (N = 1) ----------
     per_rank = None
-    if world > 1 and comm is not None and not args.construct_only:
+    if args.full and world > 1 and comm is not None and not args.construct_only:
         split = np.zeros(2)
         barrier()
         t1 = time.perf_counter()
@@ -999,7 +1061,7 @@ def main():
                     "allgather_ms": [round(float(p[1]), 3) for p in parts],
                     "note": "one step, not overlapped: eigenval on the rank's slab, then the RCCL all-gather alone"}
     host_api = None
-    if world == 1 and rank == 0 and not args.construct_only and not args.dry_ranks and os.environ.get("TBK_BENCH_SKIP_HOSTAPI") != "1":
+    if args.full and world == 1 and rank == 0 and not args.construct_only and not args.dry_ranks and os.environ.get("TBK_BENCH_SKIP_HOSTAPI") != "1":
         # SURVEY 8(d) "Evidence": wall-clock through the drop-in surface -- host k in, host eigenvalues out (H2D of k,
         # all kernels, the non-finite check, D2H), i.e. tbk_eigenval, what Model.eigenval_array calls; plus the
         # reference's return type (a Python list of row arrays, _tb_model.py:1148-1150)
@@ -1023,7 +1085,7 @@ def main():
         }
         _lib.check(lib.tbk_get_timing(model, None, None, 1))  # drop the stage events of these two extra calls
     construct = None
-    if world == 1 and rank == 0 and not args.construct_only and not args.dry_ranks and os.environ.get("TBK_BENCH_SKIP_HOSTAPI") != "1":
+    if args.full and world == 1 and rank == 0 and not args.construct_only and not args.dry_ranks and os.environ.get("TBK_BENCH_SKIP_HOSTAPI") != "1":
         # SURVEY 8(d) "Metric": k-points/s for H(k) construction alone, the result resident in HBM (tbk_hamilton_device, the
         # FULL matrix of Model.hamilton); and hard part 5: the batch hamilton() wall-clock through HOST buffers, PCIe-bound
         nk_c = min(nk_gpu, max(1, int(12e9 // (n_orb * n_orb * 16))))  # at most 12 GB of H
@@ -1058,12 +1120,12 @@ def main():
         del h_host
         _lib.check(lib.tbk_get_timing(model, None, None, 1))
     peak_measured = None
-    if rank == 0 and arrays["kind"] == "dense" and os.environ.get("TBK_BENCH_SKIP_PEAK") != "1":
+    if args.full and rank == 0 and arrays["kind"] == "dense" and os.environ.get("TBK_BENCH_SKIP_PEAK") != "1":
         tf = ctypes.c_double(0.0)
         _lib.check(lib.tbk_mfma_f64_peak(device, ctypes.byref(tf)))  # ~1 s: a bare v_mfma_f64_16x16x4_f64 loop
         peak_measured = round(tf.value, 2)
 
-    # --- correctness checks on rank 0 (after the clock stopped) ----------------------------------
+    # --- correctness checks on rank 0 (after the clock stopped; --full) --------------------------
     # (i) the first k-points of the slab against the oracle (with the CPU baseline below);
     # (ii) sum_i E_i(k) = tr H(k) = sum_R 2 Re(e^{2 pi i k.R} tr hop[R]) on rows drawn from the whole
     #      slab, so every k chunk of the pipeline is covered (host work independent of the GPU path)
@@ -1071,7 +1133,7 @@ def main():
     trace_err = None
     moment_err = None
     parity_all = None
-    if not args.construct_only and rank == 0:
+    if args.full and not args.construct_only and rank == 0:
         d_e = d_e_pair[(step_no[0] - 1) & 1]  # the buffer of the last step
         _lib.check(lib.tbk_memcpy_d2h(device, _lib.ptr(eig_head), d_e, eig_head.nbytes))
         eig_all = np.empty((nk_gpu, n_orb))
@@ -1089,6 +1151,34 @@ def main():
     if rank == 0:
         total_k = world * nk_gpu * args.steps
         value = total_k / elapsed
+        result = {
+            "metric": "k-points/sec (H(k)+eig) at N_orb=%d, N_R=%d" % (n_orb, n_r) if not args.construct_only
+                      else "k-points/sec (H(k) construction only) at N_orb=%d, N_R=%d" % (n_orb, n_r),
+            "value": round(value, 1),
+            "unit": "k-points/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "strong" if args.config == "cfg4" and not args.nk else "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic" if not args.dry_ranks else "synthetic; DRY RUN on the CPU (tools/standin_lib.py in place of libtbk, a 5-orbital model): launch mechanics only, the numbers mean nothing",
+            "config": {
+                "workload": "%s: %s N_orb=%d N_R=%d, %d %s k-points per GPU, eigenval (H(k)+eig)"
+                            % (args.config, arrays["kind"], n_orb, n_r, nk_gpu,
+                               "grid" if args.config in ("cfg1", "cfg4") else "random"),
+                "kpoints_per_gpu": nk_gpu,
+                "sharding": "contiguous k slabs, hoppings replicated, all-gather of eigenvalue slabs" if world > 1
+                            else "single GPU",
+                "collective": collective,
+                "rccl_ranks": rccl_ranks,
+                "eigensolver": args.eigensolver,
+            },
+            "rccl_ranks": rccl_ranks,
+        }
+    if rank == 0 and args.full:
         roofline = hk_roofline_entry(arrays, n_orb, n_r, dim, stage_ms, stage_n, nk_gpu * args.steps, args.config,
                                      construct_only=args.construct_only, peak_measured=peak_measured,
                                      with_traffic=(args.config == "cfg2" and not args.nr))
@@ -1136,39 +1226,14 @@ def main():
             for name in ("cfg1", "cfg3", "cfg5"):
                 entry_all, rows_all = cpu_all_other.get(name, (None, None))
                 other[name] = run_other_config(lib, device, name, cpu_all=entry_all, cpu_all_rows=rows_all)
-        result = {
-            "metric": "k-points/sec (H(k)+eig) at N_orb=%d, N_R=%d" % (n_orb, n_r) if not args.construct_only
-                      else "k-points/sec (H(k) construction only) at N_orb=%d, N_R=%d" % (n_orb, n_r),
-            "value": round(value, 1),
+        result.update({
             # the same call on HOST buffers (H2D of k and D2H of the eigenvalues inside: SURVEY 8(d) "Evidence"); N = 1 only
             "value_host_buffers": host_api["value"] if host_api else None,
-            "unit": "k-points/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "strong" if args.config == "cfg4" and not args.nk else "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic" if not args.dry_ranks else "synthetic; DRY RUN on the CPU (tools/standin_lib.py in place of libtbk, a 5-orbital model): launch mechanics only, the numbers mean nothing",
-            "config": {
-                "workload": "%s: %s N_orb=%d N_R=%d, %d %s k-points per GPU, eigenval (H(k)+eig)"
-                            % (args.config, arrays["kind"], n_orb, n_r, nk_gpu,
-                               "grid" if args.config in ("cfg1", "cfg4") else "random"),
-                "kpoints_per_gpu": nk_gpu,
-                "sharding": "contiguous k slabs, hoppings replicated, all-gather of eigenvalue slabs" if world > 1
-                            else "single GPU",
-                "collective": collective,
-                "rccl_ranks": rccl_ranks,
-                "eigensolver": args.eigensolver,
-            },
             "roofline": roofline,
             "eig_roofline": eig_roofline,
             "cpu_baseline": cpu,
             "cpu_baseline_all_cores": cpu_all,
             "host_api": host_api,
-            "rccl_ranks": rccl_ranks,
             "per_rank": per_rank,
             "configs": other,
             "stage_ms_per_step": {k: round(v / args.steps, 3) for k, v in stage_ms.items()},
@@ -1179,7 +1244,7 @@ def main():
             "max_second_moment_err": moment_err,
             "construct_only": construct,
             "strong_scaling": None,
-        }
+        })
     # --- after everything else: BASELINE config 4, the one STRONG-scaling config -- the 100^3 mesh of the staged model in
     # `world` contiguous slabs, every rank's slab evaluated into its rows of the full result with the RCCL all-gather of
     # finished row blocks pipelined behind the k chunks (tbk_eigenval_device_gather), the gather INSIDE the timing.  Every
@@ -1187,14 +1252,15 @@ def main():
     # at this point: if the leg fails or does not come back (a rank lost in a collective), the line is printed WITHOUT it
     # -- with the error under configs.cfg4 -- instead of being lost with the process.
     strong_failed = False
-    if comm is not None and args.config == "cfg2" and not args.construct_only and not args.nr \
+    if args.full and comm is not None and args.config == "cfg2" and not args.construct_only and not args.nr \
             and ((os.environ.get("TBK_BENCH_SKIP_CONFIGS") != "1" and not args.nk) or os.environ.get("TBK_BENCH_STRONG") == "1"):
         strong_failed = guarded_strong_leg(
             result, world, float(os.environ.get("TBK_BENCH_STRONG_TIMEOUT", "240")),
             lambda: strong_scaling_leg(lib, device, model, comm, group, world, rank, n_orb, arrays,
                                        mesh=int(os.environ.get("TBK_BENCH_STRONG_MESH", "100"))))
     if rank == 0 and result is not None:
-        result["summary"] = make_summary(result)  # LAST key: what survives in a record that keeps the end of the line
+        if args.full:
+            result["summary"] = make_summary(result)  # LAST key: what survives in a record that keeps the end of the line
         print(json.dumps(result), flush=True)
     if strong_failed:  # the main line stands and says "strong_scaling": "failed"; the exit status below reports it too
         sys.stderr.write("[bench] the cfg4 strong-scaling leg failed on rank %d: see configs in the JSON line\n" % rank)

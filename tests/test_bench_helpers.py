@@ -229,7 +229,7 @@ def test_summary_is_compact_and_carries_every_config():
 
 def test_the_scaling_drivers_command_runs_dry_on_eight_cpu_ranks():
     """The exact command the SCALE driver runs on an 8-GPU node -- ``python -m torch.distributed.run --nnodes=1 --nproc-per-node 8
-    --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 --steps K --warmup W`` -- with ``--dry-ranks`` appended: eight rank
+    --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 --steps K --warmup W`` -- with ``--dry-ranks --full`` appended: eight rank
     processes walk main()'s whole control flow on the CPU (rendezvous from the launcher's environment, the communicator, the
     step loop with the overlapped gather, the per-rank split, the cfg4 strong-scaling leg, ONE JSON line from rank 0) with
     tools/standin_lib.py in place of libtbk.  No scaling curve has ever been measured (no multi-GPU node in six rounds): this
@@ -242,7 +242,8 @@ def test_the_scaling_drivers_command_runs_dry_on_eight_cpu_ranks():
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--dry-ranks"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--dry-ranks",
+           "--full"]
     run = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, check=False)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [line for line in run.stdout.splitlines() if line.startswith("{")]
@@ -257,3 +258,48 @@ def test_the_scaling_drivers_command_runs_dry_on_eight_cpu_ranks():
     assert leg["max_abs_err_vs_oracle"] <= 1e-12 and record["max_abs_err_vs_oracle"] <= 1e-12
     assert list(record)[-1] == "summary" and abs(record["summary"]["cfg4"]["v"] - leg["value"]) <= 1e-5 * leg["value"]
     assert record["value"] > 0 and record["unit"] == "k-points/s" and record["value_host_buffers"] is None
+
+
+def test_dump_row_sample_is_fixed_and_within_the_limit():
+    import bench
+
+    assert bench.dump_row_sample(1000, 64 * 8) is None  # 512 KB: every row
+    rows = bench.dump_row_sample(10 ** 6, 64 * 8)
+    assert len(rows) * 64 * 8 <= bench.DUMP_LIMIT_BYTES and len(rows) == bench.DUMP_LIMIT_BYTES // (64 * 8)
+    assert np.all(np.diff(rows) > 0) and rows[-1] < 10 ** 6
+    assert np.array_equal(rows, bench.dump_row_sample(10 ** 6, 64 * 8))  # the same rows in every run
+
+
+def test_a_plain_dry_run_prints_the_contract_fields_and_dumps_the_last_step(tmp_path):
+    """``bench.py --gpus 2 --steps 2 --warmup 1 --dump-outputs DIR`` without ``--full``, on two CPU ranks (``--dry-ranks``): one
+    JSON line with the contract fields and none of the legs after the clock; DIR/eigenvalues.npy holds the all-gathered
+    eigenvalues of the last step, in the order of the global k list."""
+    import json
+    import socket
+    import subprocess
+
+    from oracle import tbk_oracle as oracle
+    from tbmodels_amd import synthetic
+
+    with socket.socket() as sock:
+        sock.bind(("127.0.0.1", 0))
+        port = sock.getsockname()[1]
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dry-ranks",
+           "--dump-outputs", str(out)]
+    run = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, check=False)
+    assert run.returncode == 0, run.stderr[-3000:]
+    lines = [line for line in run.stdout.splitlines() if line.startswith("{")]
+    assert len(lines) == 1, run.stdout[-2000:]
+    record = json.loads(lines[0])
+    assert record["unit"] == "k-points/s" and record["higher_is_better"] is True and record["dtype"] == "f64"
+    assert record["value"] > 0 and record["ms_per_step"] > 0 and record["steps"] == 2 and record["n_gpus"] == 2
+    assert "metric" in record
+    for key in ("roofline", "cpu_baseline", "host_api", "configs", "per_rank", "max_abs_err_vs_oracle", "strong_scaling", "summary"):
+        assert key not in record, key
+    eig = np.load(out / "eigenvalues.npy")
+    assert eig.dtype == np.float64 and eig.shape == (2 * 96, 5)
+    r_vec, hop, _ = synthetic.dense_model_arrays(5, 12, synthetic.MODEL_SEED + 77)  # bench.py's dry-run model
+    ref = np.array(oracle.eigenval(r_vec, hop, synthetic.random_kpoints(2 * 96)))
+    assert np.abs(eig - ref).max() <= 1e-12

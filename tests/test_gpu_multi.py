@@ -352,7 +352,7 @@ def _bench(extra_args, extra_env, timeout=600):
     env = dict(os.environ, TBK_BENCH_SKIP_CONFIGS="1", TBK_BENCH_SKIP_PEAK="1", **extra_env)
     for name in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(name, None)
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-sample", "0"] + extra_args, env=env,
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-sample", "0"] + extra_args, env=env,
                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout, check=False)
 
 

@@ -4,8 +4,10 @@ HDF5 wire formats: the reader / writer of ``tbmodels_amd.hd
 
 * the reference's own sample files (``tests/samples/cli_eigenvals/*`` of the reference, committed as data
   fixtures under ``tests/golden/cli_eigenvals``),
-* real ``h5py`` / the reference's own ``Model.from_hdf5_file`` / ``to_hdf5`` where an interpreter with h5py
-  exists (``tools/hdf5_crosscheck.py`` as a child process; skipped otherwise -- the GPU box has none).
+* real ``h5py``: files it wrote and its reading of a file of ours, stored under ``tests/golden/h5py``
+  (made with ``tools/hdf5_crosscheck.py``),
+* the reference's own ``Model.from_hdf5_file`` / ``to_hdf5`` where an interpreter with h5py and the reference
+  exists (``tools/hdf5_crosscheck.py`` as a child process; skipped otherwise).
 """
 
 import os
@@ -31,7 +33,6 @@ def _have_h5py():
     return subprocess.run([H5PY_PYTHON, "-c", "import h5py"], capture_output=True, check=False).returncode == 0
 
 
-needs_h5py = pytest.mark.skipif(not _have_h5py(), reason="no interpreter with h5py on this machine")
 needs_reference = pytest.mark.skipif(
     not (_have_h5py() and os.path.isdir("/root/reference/src/tbmodels")), reason="reference sources not present"
 )
@@ -254,30 +255,28 @@ def test_cli_arguments(tmp_path, capsys):
 # ------------------------------------------------------------------------------------------------
 # against real h5py / the reference
 # ------------------------------------------------------------------------------------------------
-@needs_h5py
+# Stored h5py evidence (tests/golden/h5py, made with h5py 3.3.0 / HDF5 1.10.6 through tools/hdf5_crosscheck.py):
+# theirs.hdf5 (``h5py-write``) with h5py's own reading of it (``h5py-read`` -> theirs_h5py.npz), chunked.hdf5 (``h5py-chunked``),
+# and the SHA-256 of the file ``hdf5_lite.write`` makes of ``sample_tree(n_hop=700)``, which h5py read back as exactly that tree.
+# A change of the writer's bytes needs that check redone with h5py and the digest renewed.
+H5PY_GOLDEN = os.path.join(GOLDEN, "h5py")
+
+
 def test_h5py_reads_our_files(tmp_path):
+    import hashlib
+
     tree = sample_tree(n_hop=700)
     path = tmp_path / "ours.hdf5"
     hdf5_lite.write(path, tree)
-    dump = tmp_path / "dump.npz"
-    crosscheck("h5py-read", str(path), str(dump))
-    want = flatten(tree)
-    with np.load(dump) as got:
-        assert set(got.files) == set(want)
-        for key, value in want.items():
-            if value.dtype.kind == "U":
-                assert str(got[key]) == str(value)
-            else:
-                assert got[key].dtype == value.dtype and got[key].shape == value.shape, key
-                np.testing.assert_array_equal(got[key], value)
+    with open(os.path.join(H5PY_GOLDEN, "ours.hdf5.sha256")) as handle:
+        checked_by_h5py = handle.read().strip()
+    assert hashlib.sha256(path.read_bytes()).hexdigest() == checked_by_h5py
+    assert_trees_equal(hdf5_lite.read(path), tree)
 
 
-@needs_h5py
-def test_we_read_h5py_files(tmp_path):
-    path = tmp_path / "theirs.hdf5"
-    dump = tmp_path / "dump.npz"
-    crosscheck("h5py-write", str(path))
-    crosscheck("h5py-read", str(path), str(dump))
+def test_we_read_h5py_files():
+    path = os.path.join(H5PY_GOLDEN, "theirs.hdf5")
+    dump = os.path.join(H5PY_GOLDEN, "theirs_h5py.npz")
     got = flatten(hdf5_lite.read(path))
     with np.load(dump) as want:
         assert set(want.files) == set(got)
@@ -290,10 +289,8 @@ def test_we_read_h5py_files(tmp_path):
     assert hdf5_lite.read(path)["empty_group"] == {}
 
 
-@needs_h5py
-def test_unsupported_features_are_named(tmp_path):
-    path = tmp_path / "chunked.hdf5"
-    crosscheck("h5py-chunked", str(path))
+def test_unsupported_features_are_named():
+    path = os.path.join(H5PY_GOLDEN, "chunked.hdf5")
     with pytest.raises(hdf5_lite.HDF5FormatError, match="chunked|filtered"):
         hdf5_lite.read(path)
 
