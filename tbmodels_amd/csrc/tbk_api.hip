@@ -27,11 +27,7 @@ void tbk_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* tbk_last_error(void) { return g_err; }
-#ifdef TBK_EXPERIMENTS
-extern "C" const char* tbk_version(void) { return "tbk 0.1 (gfx950) +experiments"; }  // (`make EXPERIMENTS=1`: tbk_exp_env reads the environment)
-#else
 extern "C" const char* tbk_version(void) { return "tbk 0.1 (gfx950)"; }
-#endif
 
 extern "C" int tbk_device_count(int* count) {
     TBK_ARG(count != nullptr, "count is NULL");
@@ -182,15 +178,7 @@ static int create_common(int device, int dim, int n_orb, int64_t n_r, const int3
         if (rc != TBK_OK) return fail(rc);      \
     } while (0)
 
-    {
-        // TBK_MAIN_PRIORITY=1 (measurements): the main stream -- the H(k) kernels -- at the highest priority
-        static const bool main_hi = tbk_exp_env("TBK_MAIN_PRIORITY") != nullptr && atoi(tbk_exp_env("TBK_MAIN_PRIORITY")) != 0;
-        int lo = 0, hi = 0;
-        if (main_hi && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess)
-            TBK_TRY(TBK_HIP(hipStreamCreateWithPriority(&m->stream, hipStreamNonBlocking, hi)));
-        else
-            TBK_TRY(TBK_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking)));
-    }
+    TBK_TRY(TBK_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking)));
     TBK_TRY(TBK_HIP(hipStreamCreateWithFlags(&m->stream_eig, hipStreamNonBlocking)));
     TBK_TRY(TBK_HIP(hipStreamCreateWithFlags(&m->stream_ql, hipStreamNonBlocking)));
     // (stream_xl / ev_xl: created by launch_band_xl when a batch above 1024 orbitals first goes in groups)
@@ -210,8 +198,7 @@ static int create_common(int device, int dim, int n_orb, int64_t n_r, const int3
     // one H(k) (up to 1024 orbitals: 16 MiB) with its k-point and positions, or a few hundred eigenvalue rows
     m->h_stage_bytes = std::max<size_t>(size_t(320) << 10,
                                         n_orb <= 1024 ? (size_t)n_orb * n_orb * 16 + (size_t)n_orb * dim * 8 + (size_t(64) << 10) : 0);
-    static const int stage_mode = tbk_exp_env("TBK_STAGE_MODE") ? atoi(tbk_exp_env("TBK_STAGE_MODE")) : 1;  // 0 off, 1 non-coherent, 2 coherent
-    if (stage_mode == 0 || hipHostMalloc(&m->h_stage, m->h_stage_bytes, stage_mode == 1 ? hipHostMallocNonCoherent : hipHostMallocDefault) != hipSuccess) {
+    if (hipHostMalloc(&m->h_stage, m->h_stage_bytes, hipHostMallocNonCoherent) != hipSuccess) {
         (void)hipGetLastError();
         m->h_stage = nullptr;  // no pinned memory: every call takes the pageable path
         m->h_stage_bytes = 0;
@@ -387,7 +374,7 @@ extern "C" void tbk_model_destroy(tbk_model* m) {
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     DevBuf* bufs[] = {&m->ws_phase, &m->ws_H, &m->ws_E,   &m->ws_E2,
-                      &m->ws_info,  &m->ws_k, &m->ws_pos, &m->ws_out, &m->ws_out2, &m->ws_flag, &m->ws_orb, &m->ws_part, &m->ws_kfold, &m->ws_kline, &m->ws_band, &m->ws_bandmat[0], &m->ws_bandmat[1], &m->ws_H2, &m->ws_split, &m->ws_xl, &m->ws_posraw};
+                      &m->ws_info,  &m->ws_k, &m->ws_pos, &m->ws_out, &m->ws_out2, &m->ws_flag, &m->ws_orb, &m->ws_part, &m->ws_kfold, &m->ws_kline, &m->ws_band, &m->ws_bandmat[0], &m->ws_bandmat[1], &m->ws_H2, &m->ws_xl, &m->ws_posraw};
     for (DevBuf* b : bufs) b->release();
     tbk_fold_release(m);
     delete m;
@@ -533,11 +520,12 @@ extern "C" int tbk_hamilton_device(tbk_model* m, const double* d_k, int64_t nk, 
 // is a serial chain of ~n^2 rotations (1.6 ms at n = 64 however few matrices there are) that only pays when tens of
 // thousands of matrices share it and it can hide under the next chunk's reduction; bisection spends a wave per
 // matrix (VALU work ~ n per matrix) and got ~1.7x faster with the secant steps of tbk_eig_stream.hip.  Measured
-// crossover (tools/bench_crossover.py, ms per call, QL vs bisection): n = 64, N_R = 4096: 49152 k-points 57.29 vs
+// crossover (ms per call, QL vs bisection): n = 64, N_R = 4096: 49152 k-points 57.29 vs
 // 56.84, 57344: 66.71 vs 66.82, 100000: 114.4 vs 115.5; n = 48, N_R = 512: 30000: 5.94 vs 5.79, 40000: 7.55 vs 7.81;
 // n = 32, N_R = 256: 16384: 1.45 vs 1.42, 24576: 1.84 vs 1.87.  (The rule was 640 n in round 1 and 384 n between the
-// free-running QL and the faster bisection.)  TBK_SMALL_CALL_PER_ORBITAL overrides the factor (measurements only).
+// free-running QL and the faster bisection.)
 constexpr int64_t TBK_SMALL_CALL = 4096;
+constexpr int64_t TBK_SMALL_CALL_PER_ORBITAL = 768;
 // (Up to 12 orbitals the QL chain used to be the shorter one -- 61 us at n = 8 -- until small matrices got the idle
 // lanes of their wave for multisection: 1000 silicon k-points 59 -> 20 us, so small calls bisect at every size now.)
 
@@ -632,8 +620,7 @@ static int eigenval_wave_pipeline(tbk_model* m, const double* d_k, int64_t nk, d
     const int64_t n_chunks = (int64_t)sched.size();
     const int64_t max_chunk = *std::max_element(sched.begin(), sched.end());
     // a property of the call, not of its chunking: TBK_OPT_K_CHUNK must not change the results
-    static const int64_t per_orbital = tbk_exp_env("TBK_SMALL_CALL_PER_ORBITAL") ? atoll(tbk_exp_env("TBK_SMALL_CALL_PER_ORBITAL")) : 768;
-    const bool small_call = nk <= std::max<int64_t>(TBK_SMALL_CALL, per_orbital * (int64_t)m->n_orb);
+    const bool small_call = nk <= std::max<int64_t>(TBK_SMALL_CALL, TBK_SMALL_CALL_PER_ORBITAL * (int64_t)m->n_orb);
     TBK_CHECK(m->ws_H.reserve((size_t)max_chunk * nn2 * sizeof(double)));
     for (int b = 0; b < (n_chunks > 1 ? 2 : 1); ++b)
         TBK_CHECK(debuf[b]->reserve((size_t)max_chunk * n * 2 * sizeof(double)));
@@ -643,28 +630,15 @@ static int eigenval_wave_pipeline(tbk_model* m, const double* d_k, int64_t nk, d
     // of chunk c - 2.  (Not for the direct contraction, which fills the chip and shares the FP64 pipe: see above.)
     // Round 4, MEASURED AND LEFT OFF (DESIGN_LOG.md R4.15): the same for the direct H(k) of the two-stage sizes (from 185
     // orbitals) -- that reduction is a chain of short phases which leaves the matrix pipe idle four fifths of the time, and
-    // the sparse H(k) is an HBM-write kernel.  Default: one after the other (the round-3 order); TBK_H_OVERLAP_BIG=1 turns
-    // the overlap (and the 84 KiB hk_lds_floor below) on for measurements.
-    static const bool overlap_on = tbk_exp_env("TBK_H_OVERLAP") == nullptr || atoi(tbk_exp_env("TBK_H_OVERLAP")) != 0;
-    static const bool overlap_big = tbk_exp_env("TBK_H_OVERLAP_BIG") != nullptr && atoi(tbk_exp_env("TBK_H_OVERLAP_BIG")) != 0;
-    const bool h_overlap = n_chunks > 2 && overlap_on &&
-                           ((builder != nullptr && tbk_eig_small_supported(m->n_orb)) ||
-                            (overlap_big && builder == nullptr && !tbk_eig_small_supported(m->n_orb) && tbk_eig_two_stage(m)));
+    // the sparse H(k) is an HBM-write kernel.  There: one after the other (the round-3 order).
+    const bool h_overlap = n_chunks > 2 && builder != nullptr && tbk_eig_small_supported(m->n_orb);
     double* d_Hbuf[2] = {d_H, d_H};
-    struct LdsFloor {  // (reset on every way out)
-        tbk_model* m;
-        ~LdsFloor() { m->hk_lds_floor = 0; }
-    } lds_floor_guard{m};
-    if (h_overlap && builder == nullptr) {
-        static const int floor_kib = tbk_exp_env("TBK_H_OVERLAP_LDS") ? atoi(tbk_exp_env("TBK_H_OVERLAP_LDS")) : 84;
-        m->hk_lds_floor = (size_t)floor_kib * 1024;
-    }
     if (h_overlap) {
         TBK_CHECK(m->ws_H2.reserve((size_t)max_chunk * nn2 * sizeof(double)));
         d_Hbuf[1] = m->ws_H2.as<double>();
     }
-    // two-stage reduction in two launches (TBK_BAND_FUSE=0): stage two of a chunk goes to the tridiagonal stream; fused
-    // (default) it is part of the reduction kernel and this flag stays off
+    // two-stage reduction in two launches (above 256 orbitals): stage two of a chunk goes to the tridiagonal stream; fused
+    // (up to 256) it is part of the reduction kernel and this flag stays off
     const bool two_stage = !tbk_eig_small_supported(m->n_orb) && tbk_eig_two_stage(m) && n_chunks > 1 && !tbk_band_fused(m->n_orb);
     if (two_stage) {
         TBK_CHECK(m->ws_band.reserve((size_t)max_chunk * tbk_band_scratch_per_matrix(m->n_orb)));
@@ -718,12 +692,9 @@ static int eigenval_wave_pipeline(tbk_model* m, const double* d_k, int64_t nk, d
         TBK_HIP(hipEventRecord(m->ev_tri[b], m->stream_eig));
 
         if (c >= 1) {  // tridiagonal stage of the previous chunk, alongside this chunk's reduction
-            // TBK_CHASE_EARLY=1 (measurements): ... alongside this chunk's H(k) already -- it starts as soon as its own
-            // reduction is done
-            static const bool early = tbk_exp_env("TBK_CHASE_EARLY") && atoi(tbk_exp_env("TBK_CHASE_EARLY")) != 0;
-            if (!(early && two_stage)) TBK_HIP(hipStreamWaitEvent(m->stream_ql, m->ev_hk[b], 0));
+            TBK_HIP(hipStreamWaitEvent(m->stream_ql, m->ev_hk[b], 0));
             // (d, e) of the previous chunk: implied by ev_hk unless H(c) was built beside that reduction
-            if (h_overlap || (early && two_stage)) TBK_HIP(hipStreamWaitEvent(m->stream_ql, m->ev_tri[b ^ 1], 0));
+            if (h_overlap) TBK_HIP(hipStreamWaitEvent(m->stream_ql, m->ev_tri[b ^ 1], 0));
             TBK_CHECK(launch_tridiag_eigenvalues(m, m->stream_ql, debuf[b ^ 1]->as<double>(), prev_nkc,
                                                  d_E + (size_t)prev_c0 * n, false, small_call,
                                                  two_stage ? m->ws_bandmat[b ^ 1].ptr : nullptr));
@@ -1157,8 +1128,8 @@ extern "C" int tbk_hamilton(tbk_model* m, const double* k, int64_t nk, int conve
             // across PCIe: 1.69 -> 1.81 ms), so a bigger H still takes the copy; downloading it in two or four pieces, each
             // copied on to the caller's array while the next crosses PCIe, was measured and is within the noise of the
             // 1.3 - 1.4 ms kernel in front of it (1586 / 1661 / 1704 and 1568 / 1613 / 1563 us for 1 / 2 / 4 pieces).
-            static const size_t direct_max = tbk_exp_env("TBK_ZERO_COPY_MAX") ? (size_t)atoll(tbk_exp_env("TBK_ZERO_COPY_MAX")) : (size_t(1) << 20);
-            const bool direct = h_bytes <= direct_max;
+            constexpr size_t ZERO_COPY_MAX = size_t(1) << 20;
+            const bool direct = h_bytes <= ZERO_COPY_MAX;
             double* d_out = direct ? reinterpret_cast<double*>(st + h_off) : m->ws_out.as<double>();
             const int rc_inline = tbk_hamilton_device(m, m->ws_k.as<double>(), nk, convention, d_pos, d_out);
             m->h_k_inline = nullptr;
@@ -1166,8 +1137,7 @@ extern "C" int tbk_hamilton(tbk_model* m, const double* k, int64_t nk, int conve
             TBK_CHECK(rc_inline);
             if (!direct) TBK_HIP(hipMemcpyAsync(st + h_off, m->ws_out.ptr, h_bytes, hipMemcpyDeviceToHost, m->stream));
             TBK_CHECK(wait_main_stream(m));
-            static const bool no_copy = tbk_exp_env("TBK_ABLATE_NO_HOSTCOPY") != nullptr;  // (timing only: what the host copy costs)
-            if (!no_copy) std::memcpy(H_out, st + h_off, h_bytes);
+            std::memcpy(H_out, st + h_off, h_bytes);
             return TBK_OK;
         }
     }

@@ -35,10 +35,7 @@ __device__ unsigned long long tbk_band_clock[32];
 #endif
 
 // Non-temporal tile loads / stores (so that the streaming tiles do not push the re-read [V | W] blocks out of L2) were
-// measured: 4.51 -> 4.78 us per matrix at 256 orbitals, 31.5 -> 31.0 at 512 -- nothing either way; off.
-#ifndef TBK_TILE_NT
-#define TBK_TILE_NT 0
-#endif
+// measured: 4.51 -> 4.78 us per matrix at 256 orbitals, 31.5 -> 31.0 at 512 -- nothing either way; not used.
 
 // Ablation switches for tools/band_ablate.sh (TIMING ONLY: each makes the results wrong; never defined in the library build).
 // They price the levers of the tile pass before anything is built on them (round 4):
@@ -56,12 +53,9 @@ constexpr int TS = 16;   // MFMA tile edge
 // MATRIX pipe: the rows go through a wave-private LDS plane into operand order ([Re | Im] as 16 real columns, 16 MFMAs per 64
 // rows), the waves' 16 x 16 partial products meet ONCE, and the panel QR takes ALL its reflectors from that one Gram matrix
 // (tools/two_stage_model.py: panel_qr_gram).  Before: one round of vector products, 64-bit DPP wave sums and
-// a workgroup barrier PER REFLECTOR (8 per panel) plus two more for T and W.  TBK_PANEL_GRAM=0 builds the round-4 form (A/B).
+// a workgroup barrier PER REFLECTOR (8 per panel) plus two more for T and W.
 // One row per thread only (up to 256 orbitals, and every call of a few matrices): with two rows per thread the recurrence's
 // tracked block beside both rows did not fit the register file (60 - 340 B of scratch in every arrangement tried).
-#ifndef TBK_PANEL_GRAM
-#define TBK_PANEL_GRAM 1
-#endif
 constexpr int GP = 17;   // pitch (doubles) of a wave's transposition plane [64 rows][16 values]
 // a column whose remaining norm^2 (a difference of Gram sums) has cancelled below this fraction of its full norm^2 ends the
 // round: the rows apply the reflectors found so far and a fresh Gram matrix is formed (errors ~ eps sqrt(1 / fraction))
@@ -71,7 +65,7 @@ constexpr double GRAM_THRESH = 1.0 / 64.0;
 // transposition planes, which live there while X and V are dead
 __host__ __device__ inline size_t band_xv_bytes(int npad, bool vn_lds, int nw, int rows) {
     const size_t xv = (size_t)npad * PB * 16 * (vn_lds ? 2 : 1);
-    const size_t planes = (TBK_PANEL_GRAM && rows == 1) ? (size_t)nw * 64 * GP * 8 : 0;
+    const size_t planes = rows == 1 ? (size_t)nw * 64 * GP * 8 : 0;
     return xv > planes ? xv : planes;
 }
 
@@ -304,29 +298,9 @@ __device__ __forceinline__ size_t vw_index(int row, int c) {
     return ((size_t)(row >> 4) * 4 + (c >> 2)) * 64 + (size_t)(c & 3) * 16 + (row & 15);
 }
 
-// workgroups that share the tile pass of ONE matrix in the launch chain: enough that a wave owns one block (two at 1024
-// orbitals), at most eight
-__host__ __device__ inline int tbk_band_split_members(int n, int nw) {
-    const int nbk = (n + TS - 1) / TS;
-    const int want = (nbk + nw - 1) / nw;
-    return want < 1 ? 1 : (want > 8 ? 8 : want);
-}
-
 struct Frag {  // a 16 x 16 complex operand block in A/B-operand layout: lane l holds [l % 16][l / 16 + 4 s], s = 0..3
     double re[4], im[4];
 };
-#ifdef TBK_EXPERIMENTS
-// The band's way out of the matrix for the launch chain: band[i][dd] = H[i][i + dd], dd = 0..8 (what the tail of the one-launch
-// kernel does).
-__global__ void __launch_bounds__(256) band_extract_kernel(const double* __restrict__ Hall, int n, d2* __restrict__ band_all, size_t band_stride) {
-    const double* H = Hall + (size_t)blockIdx.x * n * n * 2;
-    d2* band = band_all + (size_t)blockIdx.x * band_stride;
-    for (int idx = threadIdx.x; idx < n * (PB + 1); idx += 256) {
-        const int i = idx / (PB + 1), dd = idx - i * (PB + 1);
-        band[idx] = (i + dd < n) ? *reinterpret_cast<const d2*>(H + ((size_t)i * n + i + dd) * 2) : (d2){0.0, 0.0};
-    }
-}
-#endif
 
 }  // namespace
 
@@ -335,7 +309,6 @@ constexpr int BAND_ONE_WG_MAXN = 1024;    // one workgroup per matrix: two rows 
 constexpr int BAND_LDS_CHASE_MAXN = 512;  // above: the chase keeps its 16 diagonals in global memory
 bool tbk_band_is_xl(int n);               // the sizes that ALWAYS take the launch chain of band_xl_* (above 1024 orbitals; TBK_BAND_XL_FROM)
 int tbk_band_chase_pitch(int n);          // pitch of a working diagonal of the second stage
-bool tbk_band_chase_global_forced(int n);
 bool tbk_band_chase_small_window(const tbk_model* m, int n, int64_t nk);
 // tbk_eig_band_chase.hip: stage two of nk matrices on stream s, no stage timer (the callers hold one)
 int tbk_band_launch_chase(tbk_model* m, hipStream_t s, const void* d_band, int64_t nk, double* d_D, double* d_E);

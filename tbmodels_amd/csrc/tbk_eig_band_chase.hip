@@ -44,8 +44,8 @@ band_chase4g_kernel(d2* __restrict__ band_all, size_t band_stride, int n, int np
 // tools/two_stage_model.py: stage2_window is this scheme with an occupancy tag per window column (every access finds ITS
 // column, a column only enters a free cell; tests/test_two_stage_model.py).  Same arithmetic per sweep as chase4_body: the same bits.
 // NW waves = 4 NW sweep slots; CW window columns (>= 15 * 4 NW + 18: what the slots can hold in flight), CWP = pitch of a diagonal
-// (= 9 mod 16: bank-conflict free, as in the plain LDS form).  <8, 512, 521>: above 512 orbitals.  <4, 272, 281> (TBK_CHASE_WINDOW_SMALL,
-// measurements): 257 - 512 orbitals in 78 KiB instead of the 133 KiB of the plain LDS form.
+// (= 9 mod 16: bank-conflict free, as in the plain LDS form).  <8, 512, 521>: above 512 orbitals.  <4, 272, 281> (calls of more
+// matrices than the chip has CUs, tbk_band_chase_small_window): 257 - 768 orbitals in 78 KiB (the plain LDS form takes 133 KiB at 512).
 template <int NW, int CW, int CWP>
 __global__ void __launch_bounds__(NW * 64)
 band_chase4w_kernel(d2* __restrict__ band_all, size_t band_stride, int n, int np, double* __restrict__ D, double* __restrict__ E) {
@@ -401,13 +401,13 @@ int tbk_band_launch_chase(tbk_model* m, hipStream_t s, const void* d_band, int64
 #else
     const bool win_force = false;
 #endif
-    if (n > BAND_LDS_CHASE_MAXN || tbk_band_chase_global_forced(n) || small_window || win_force) {
+    if (n > BAND_LDS_CHASE_MAXN || small_window || win_force) {
         const int np = tbk_band_chase_pitch(n);
         // The working diagonals in a cyclic LDS window in front of the global buffer (band_chase4w_kernel; the same bits as the
         // global-memory form below).  One workgroup per CU (158 KiB of LDS) and still ahead at every call size: whole eigenval of
         // 2048 k-points 44.7 -> 41.0 us per k-point at 520 orbitals, 110.6 -> 99.6 at 768, 245.5 -> 216.1 at 1024; one k-point 15.2 ->
         // 13.0 ms at 1024, 32.1 -> 27.2 at 1536, 53.7 -> 44.4 at 2048.
-        if (window_env && !tbk_band_chase_global_forced(n)) {
+        if (window_env) {
             d2* d_b = static_cast<d2*>(const_cast<void*>(d_band));
             const size_t stride = tbk_band_bytes_per_matrix(n) / sizeof(d2);
             if (small_window && !win_force) {
@@ -426,25 +426,17 @@ int tbk_band_launch_chase(tbk_model* m, hipStream_t s, const void* d_band, int64
             return TBK_OK;
         }
         // 32 sweeps in flight, two steps apart, from 512 orbitals on (a sweep is n / 8 >= 64 steps long); 16 below
-        static const int env_nwg = tbk_exp_env("TBK_CHASE_NW") ? atoi(tbk_exp_env("TBK_CHASE_NW")) : 0;
-        // (TBK_CHASE_NW=12, round 5: twelve waves = 48 sweeps in flight for calls of a few matrices -- measured: one-k eigenval
-        // 13.88 -> 14.09 ms at 768 orbitals, 24.90 -> 25.17 at 1024, the same bits: the ticks' global-memory round trips, not the
-        // 32 slots, bound it.  Eight stay.)
-        const int nwg = env_nwg ? env_nwg : (n <= 256 ? 4 : 8);
+        // (round 5: twelve waves = 48 sweeps in flight for calls of a few matrices -- measured: one-k eigenval 13.88 -> 14.09 ms
+        // at 768 orbitals, 24.90 -> 25.17 at 1024, the same bits: the ticks' global-memory round trips, not the 32 slots, bound
+        // it.  Eight stay.)
+        const int nwg = n <= 256 ? 4 : 8;
         const size_t ldsg = (size_t)nwg * 64 * 16 + (size_t)n * sizeof(int) + 16;
         d2* d_b = static_cast<d2*>(const_cast<void*>(d_band));
         const size_t stride = tbk_band_bytes_per_matrix(n) / sizeof(d2);
         if (nwg <= 4)
             hipLaunchKernelGGL(band_chase4g_kernel<4>, dim3((unsigned)nk), dim3(256), ldsg, s, d_b, stride, n, np, 2, d_D, d_E);
-#ifdef TBK_EXPERIMENTS
-        else if (nwg <= 8)
-            hipLaunchKernelGGL(band_chase4g_kernel<8>, dim3((unsigned)nk), dim3(512), ldsg, s, d_b, stride, n, np, 2, d_D, d_E);
-        else
-            hipLaunchKernelGGL(band_chase4g_kernel<12>, dim3((unsigned)nk), dim3(768), ldsg, s, d_b, stride, n, np, 2, d_D, d_E);
-#else
         else
             hipLaunchKernelGGL(band_chase4g_kernel<8>, dim3((unsigned)nk), dim3(512), ldsg, s, d_b, stride, n, np, 2, d_D, d_E);
-#endif
         TBK_HIP(hipGetLastError());
         return TBK_OK;
     }
@@ -452,12 +444,10 @@ int tbk_band_launch_chase(tbk_model* m, hipStream_t s, const void* d_band, int64
         const int np = tbk_band_chase_pitch(n);
         // Consecutive sweeps run `stagger` chase steps apart: 2 is the closest that keeps the steps of one tick on
         // disjoint cells (tools/two_stage_model.py: check_pipeline).  Waves per workgroup: enough sweeps in flight to
-        // fill that pipeline (a sweep is ~n / 8 steps long).  TBK_CHASE_NW / TBK_CHASE_STAGGER: measurements only.
-        static const int env_nw = tbk_exp_env("TBK_CHASE_NW") ? atoi(tbk_exp_env("TBK_CHASE_NW")) : 0;
-        static const int env_stagger = tbk_exp_env("TBK_CHASE_STAGGER") ? atoi(tbk_exp_env("TBK_CHASE_STAGGER")) : 0;
-        const int stagger = env_stagger >= 2 ? env_stagger : 2;
+        // fill that pipeline (a sweep is ~n / 8 steps long).
+        const int stagger = 2;
         // four sweeps per wave: a sweep is ~n / 8 steps long and sweeps start two ticks apart
-        const int nw4 = env_nw ? env_nw : (n <= 128 ? 2 : n <= 256 ? 4 : 8);
+        const int nw4 = n <= 128 ? 2 : n <= 256 ? 4 : 8;
         const size_t lds4 = (size_t)16 * np * 16 + (size_t)nw4 * 64 * 16 + (size_t)n * sizeof(int) + 16;
         static std::atomic<bool> raised4[3][TBK_MAX_DEVICES] = {};
 #define TBK_CHASE4(NWV, SLOT)                                                                                             \

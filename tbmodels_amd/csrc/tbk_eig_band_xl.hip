@@ -21,8 +21,7 @@ namespace {
 //                           (one owner per block of X, complete in registers: no partner sums, no LDS for X, any number of
 //                           rows) and writes the stored orientation to the NEW buffer.  Every tile is read twice and written
 //                           once per panel.
-// (band_xl_update_kernel + band_xl_product_kernel: the same as two sweeps on ONE buffer -- the first form, TBK_BAND_XL_SWEEPS=2,
-// and the last pending update of the chain; band_xl_sweep4_kernel + band_xl_xsum_kernel: every tile read once, measured, off.)
+//   band_xl_update_kernel   the last pending update of the chain, in place.
 // Stream order is the only synchronisation between them; a batch goes in two groups of matrices on two streams.  Same
 // arithmetic as the kernels above (tools/two_stage_model.py: panel_qr_gram, stage1_band); the global-memory chase and the
 // bisection follow.
@@ -448,104 +447,12 @@ band_xl_update_kernel(double* __restrict__ Hall, int n, const d2* __restrict__ V
     }
 }
 
-// X_I = sum_J tile(I, J) Vn_J over J = i0 .. nbk - 1 for the block row I = i0 + blockIdx.x: the tiles right of the diagonal
-// as stored, those left of it as the transposed stored ones, the diagonal tile completed from its upper part.  The waves
-// take every NW-th tile and add their partial blocks in wave order.
-template <int NT>
-__global__ void __launch_bounds__(NT, 2)
-band_xl_product_kernel(const double* __restrict__ Hall, int n, const d2* __restrict__ VNall, d2* __restrict__ XYall, int i0) {
-    constexpr int NW = NT / 64;
-    __shared__ double sTr[NW * 16 * 17];
-    __shared__ double sRed[NW * 4 * 64];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int nbk = (n + TS - 1) / TS, npad = nbk * TS;
-    const size_t mat = blockIdx.y;
-    const double* H = Hall + mat * (size_t)n * n * 2;
-    const double* VNd = reinterpret_cast<const double*>(VNall + mat * (size_t)npad * PB);
-    double* XYd = reinterpret_cast<double*>(XYall + mat * (size_t)npad * PB);
-    const int I = i0 + (int)blockIdx.x;
-    const int lrow = lane & 15, lq = lane >> 4;
-    const int lane_x = lq * 16 + 2 * (lrow & 7) + (lrow >> 3);
-    const double lane_sgn = (lrow < 8) ? -1.0 : 1.0;
-    double* tr = sTr + wave * (16 * 17);
-    d4 own1 = (d4){0.0, 0.0, 0.0, 0.0}, own2 = own1;
-    for (int J = i0 + wave; J < nbk; J += NW) {
-        const int Ir = min(I, J), Jc = max(I, J);
-        const bool interior = (Ir + 1) * TS <= n && (Jc + 1) * TS <= n;
-        const unsigned gc = (unsigned)min(Jc * TS + lrow, n - 1);
-        d4 tre, tim;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const unsigned gr = (unsigned)min(Ir * TS + lq + 4 * r, n - 1);
-            const d2 v2 = *reinterpret_cast<const d2*>(reinterpret_cast<const char*>(H) + (size_t)gr * (size_t)n * 16 + (size_t)gc * 16);
-            const bool inside = interior || (Ir * TS + lq + 4 * r < n && Jc * TS + lrow < n);
-            tre[r] = inside ? v2[0] : 0.0;
-            tim[r] = inside ? v2[1] : 0.0;
-        }
-        double pb[4];
-#pragma unroll
-        for (int sg = 0; sg < 4; ++sg) pb[sg] = (VNd + (size_t)J * (TS * 16) + lane_x)[sg * 64];
-        if (J >= I) {
-            // the own block is the row block of the stored tile: the operand is the transposed copy [lrow][lq + 4 sg]
-            double ttre[4], ttim[4];
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int r = 0; r < 4; ++r) tr[(lq + 4 * r) * 17 + lrow] = tre[r];
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int sg = 0; sg < 4; ++sg) ttre[sg] = tr[lrow * 17 + lq + 4 * sg];
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int r = 0; r < 4; ++r) tr[(lq + 4 * r) * 17 + lrow] = tim[r];
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int sg = 0; sg < 4; ++sg) ttim[sg] = tr[lrow * 17 + lq + 4 * sg];
-            asm volatile("" ::: "memory");
-            if (J == I) {  // Hermitian tile of which only the upper part is valid
-#pragma unroll
-                for (int sg = 0; sg < 4; ++sg) {
-                    const bool upper = lrow <= lq + 4 * sg;
-                    const double ar = upper ? ttre[sg] : tre[sg];
-                    const double ai = upper ? ttim[sg] : -tim[sg];
-                    own1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, pb[sg], own1, 0, 0, 0);
-                    own2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, pb[sg], own2, 0, 0, 0);
-                }
-            } else {
-#pragma unroll
-                for (int sg = 0; sg < 4; ++sg) {
-                    own1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ttre[sg], pb[sg], own1, 0, 0, 0);
-                    own2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ttim[sg], pb[sg], own2, 0, 0, 0);
-                }
-            }
-        } else {
-            // the own block is the column block: X_I += tile^H Vn_J, the stored tile is the operand as it is (conjugated)
-#pragma unroll
-            for (int sg = 0; sg < 4; ++sg) {
-                own1 = __builtin_amdgcn_mfma_f64_16x16x4f64(tre[sg], pb[sg], own1, 0, 0, 0);
-                own2 = __builtin_amdgcn_mfma_f64_16x16x4f64(tim[sg], pb[sg], own2, 0, 0, 1);  // conj
-            }
-        }
-    }
-    // lane (row lq + 4 r, c = lrow): Re X[row][c] (c < 8) or Im X[row][c - 8]; the waves' partial blocks in wave order
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sRed[(wave * 4 + r) * 64 + lane] = fma(dpp_mov<0x128>(own2[r]), lane_sgn, own1[r]);
-    lds_fence();
-    __syncthreads();
-    for (int r = wave; r < 4; r += NW) {
-        double tot = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) tot += sRed[(w * 4 + r) * 64 + lane];
-        (XYd + (size_t)I * (TS * 16) + lane_x)[r * 64] = tot;
-    }
-}
-
-// ONE sweep per panel (default): the workgroup of block row I walks ALL tiles of that row -- those left of the diagonal as the
+// ONE sweep per panel: the workgroup of block row I walks ALL tiles of that row -- those left of the diagonal as the
 // transposed stored ones -- reads every tile from the OLD matrix buffer, applies the pending rank-16 update in registers
 // (either orientation: the row block's [V | W] is the A operand), adds tile Vn_J to its block of X, and writes the updated
 // tile to the NEW buffer when it is the stored orientation (J >= I).  Nobody reads what this launch writes, so there is no
-// order to keep: every tile crosses HBM three times per panel (read twice, written once) instead of four with the two sweeps
-// above, and a panel is two launches instead of three.  The buffers change roles from panel to panel; finished rows never
+// order to keep: every tile crosses HBM three times per panel (read twice, written once) instead of four with an update sweep
+// and a product sweep on one buffer, and a panel is two launches instead of three.  The buffers change roles from panel to panel; finished rows never
 // enter them (band_xl_serial_kernel writes those to the compact band).
 template <int NT>
 __global__ void __launch_bounds__(NT, 2)
@@ -687,176 +594,6 @@ band_xl_sweep_kernel(const double* __restrict__ Hsrc_all, double* __restrict__ H
     }
 }
 
-// The sweep of a BATCH (launch_band_xl: enough matrices to fill the chip): every tile crosses HBM TWICE per panel -- read once,
-// written once -- instead of three times.  A workgroup takes FOUR block rows (wave w: row I = i0 + 4 blockIdx.x + w) and walks the
-// block columns J together; a wave reads only the stored orientation tile(I, J), J >= I, updates it, writes it to the new buffer
-// and forms BOTH products from it: X_I += tile Vn_J in its registers (as above) and the part tile^H Vn_I of X_J, which the four
-// waves add up through LDS (one barrier per block column) and leave as this workgroup's partial of X_J in P[blockIdx.x][J].
-// band_xl_xsum_kernel then adds the partials to X in a fixed order (workgroup 0, 1, ...): the same sums on every run.  (PMC, 64
-// matrices of 1536 orbitals: the one-row sweep above reads 1.27 x the two reads of every tile its walk asks for and writes 1 x --
-// 276 GB per call against 155 GB of read-once + write-once; a walk that pairs the two reads of a tile in time -- block row I at
-// step t visits (t - I) mod m -- was slower, 1.248 -> 1.366 ms per k-point: the partner's operand blocks are then different for
-// every workgroup of a matrix.  One-row workgroups stay for calls of a few matrices: four times as many, a quarter as long.)
-template <int NT>
-__global__ void __launch_bounds__(NT, 2)
-band_xl_sweep4_kernel(const double* __restrict__ Hsrc_all, double* __restrict__ Hdst_all, int n, const d2* __restrict__ VWall,
-                      const d2* __restrict__ VNall, d2* __restrict__ XYall, double* __restrict__ Pall, size_t p_stride, int i0,
-                      int with_update) {
-    constexpr int NW = NT / 64;
-    static_assert(NW == 4, "four block rows per workgroup, one per wave; the partial sums are four registers per lane");
-    __shared__ double sTr[NW * 16 * 17];
-    __shared__ double sRed[2 * NW * 4 * 64];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int nbk = (n + TS - 1) / TS, npad = nbk * TS;
-    const size_t mat = blockIdx.y;
-    const double* Hs = Hsrc_all + mat * (size_t)n * n * 2;
-    double* Hd = Hdst_all + mat * (size_t)n * n * 2;
-    const d2* VW = VWall + mat * (size_t)nbk * 256;
-    const double* VNd = reinterpret_cast<const double*>(VNall + mat * (size_t)npad * PB);
-    double* XYd = reinterpret_cast<double*>(XYall + mat * (size_t)npad * PB);
-    double* Pd = Pall + mat * p_stride + (size_t)blockIdx.x * nbk * 256;  // this workgroup's partials: [block column][16 rows][8 complex]
-    const int I0 = i0 + NW * (int)blockIdx.x;
-    const int I = I0 + wave;
-    const bool row_ok = I < nbk;  // (uniform per wave)
-    const int Ic = min(I, nbk - 1);
-    const int lrow = lane & 15, lq = lane >> 4;
-    const int lane_x = lq * 16 + 2 * (lrow & 7) + (lrow >> 3);
-    const double lane_sgn = (lrow < 8) ? -1.0 : 1.0;
-    double* tr = sTr + wave * (16 * 17);
-    Frag own;
-    double pbi[4];
-#pragma unroll
-    for (int sg = 0; sg < 4; ++sg) {
-        const d2 v2 = with_update ? VW[((size_t)Ic * 4 + sg) * 64 + lane] : (d2){0.0, 0.0};
-        own.re[sg] = v2[0];
-        own.im[sg] = v2[1];
-        pbi[sg] = (VNd + (size_t)Ic * (TS * 16) + lane_x)[sg * 64];
-    }
-    d4 own1 = (d4){0.0, 0.0, 0.0, 0.0}, own2 = own1;
-    // what a step needs from memory: fetched ONE STEP AHEAD (the tile of step J + 1 is on its way while step J computes -- with
-    // three or fewer waves per SIMD nothing else covers the latency of HBM)
-    struct StepIn {
-        d4 tre, tim;
-        double pb[4];
-        Frag par;
-    };
-    auto fetch = [&](int J, StepIn& in) {
-        const bool interior = (I + 1) * TS <= n && (J + 1) * TS <= n;
-        const unsigned gc = (unsigned)min(J * TS + lrow, n - 1);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const unsigned gr = (unsigned)min(I * TS + lq + 4 * r, n - 1);
-            const d2 v2 = *reinterpret_cast<const d2*>(reinterpret_cast<const char*>(Hs) + (size_t)gr * (size_t)n * 16 + (size_t)gc * 16);
-            const bool inside = interior || (I * TS + lq + 4 * r < n && J * TS + lrow < n);
-            in.tre[r] = inside ? v2[0] : 0.0;
-            in.tim[r] = inside ? v2[1] : 0.0;
-        }
-#pragma unroll
-        for (int sg = 0; sg < 4; ++sg) in.pb[sg] = (VNd + (size_t)J * (TS * 16) + lane_x)[sg * 64];
-        if (with_update) {
-#pragma unroll
-            for (int sg = 0; sg < 4; ++sg) {
-                const d2 v2 = VW[((size_t)J * 4 + sg) * 64 + lane];
-                in.par.re[sg] = v2[0];
-                in.par.im[sg] = v2[1];
-            }
-        }
-    };
-    auto step = [&](int J, StepIn& cur, StepIn& nxt) {
-        const int buf = (J - I0) & 1;
-        if (row_ok && J + 1 >= I && J + 1 < nbk) fetch(J + 1, nxt);  // (uniform per wave)
-        d4 t1 = (d4){0.0, 0.0, 0.0, 0.0}, t2 = t1;
-        if (row_ok && J >= I) {  // (uniform per wave)
-            const bool interior = (I + 1) * TS <= n && (J + 1) * TS <= n;
-            d4 tre = cur.tre, tim = cur.tim;
-            if (with_update) {  // tile(I, J) -= [V | W]_I ([W | V]_J)^H
-#pragma unroll
-                for (int sg = 0; sg < 4; ++sg) {
-                    const int sb = (sg + 2) & 3;
-                    tre = __builtin_amdgcn_mfma_f64_16x16x4f64(own.re[sg], cur.par.re[sb], tre, 0, 0, 1);
-                    tre = __builtin_amdgcn_mfma_f64_16x16x4f64(own.im[sg], cur.par.im[sb], tre, 0, 0, 1);
-                    tim = __builtin_amdgcn_mfma_f64_16x16x4f64(own.im[sg], cur.par.re[sb], tim, 0, 0, 1);
-                    tim = __builtin_amdgcn_mfma_f64_16x16x4f64(own.re[sg], cur.par.im[sb], tim, 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int gr = I * TS + lq + 4 * r;
-                if (interior || (gr < n && J * TS + lrow < n))
-                    *reinterpret_cast<d2*>(reinterpret_cast<char*>(Hd) + (size_t)gr * (size_t)n * 16 + (size_t)(J * TS + lrow) * 16) = (d2){tre[r], tim[r]};
-            }
-            double ttre[4], ttim[4];
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int r = 0; r < 4; ++r) tr[(lq + 4 * r) * 17 + lrow] = tre[r];
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int sg = 0; sg < 4; ++sg) ttre[sg] = tr[lrow * 17 + lq + 4 * sg];
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int r = 0; r < 4; ++r) tr[(lq + 4 * r) * 17 + lrow] = tim[r];
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int sg = 0; sg < 4; ++sg) ttim[sg] = tr[lrow * 17 + lq + 4 * sg];
-            asm volatile("" ::: "memory");
-            if (J == I) {
-#pragma unroll
-                for (int sg = 0; sg < 4; ++sg) {
-                    const bool upper = lrow <= lq + 4 * sg;
-                    const double ar = upper ? ttre[sg] : tre[sg];
-                    const double ai = upper ? ttim[sg] : -tim[sg];
-                    own1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, cur.pb[sg], own1, 0, 0, 0);
-                    own2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, cur.pb[sg], own2, 0, 0, 0);
-                }
-            } else {
-#pragma unroll
-                for (int sg = 0; sg < 4; ++sg) {
-                    own1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ttre[sg], cur.pb[sg], own1, 0, 0, 0);
-                    own2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ttim[sg], cur.pb[sg], own2, 0, 0, 0);
-                    // ... and this tile's part of X_J: tile^H Vn_I (the registers as they were loaded ARE the transposed operand)
-                    t1 = __builtin_amdgcn_mfma_f64_16x16x4f64(tre[sg], pbi[sg], t1, 0, 0, 0);
-                    t2 = __builtin_amdgcn_mfma_f64_16x16x4f64(tim[sg], pbi[sg], t2, 0, 0, 1);  // conj
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sRed[((buf * NW + wave) * 4 + r) * 64 + lane] = fma(dpp_mov<0x128>(t2[r]), lane_sgn, t1[r]);
-        lds_fence();
-        __syncthreads();  // (one per block column: a wave that runs ahead writes the OTHER area, and cannot pass the next barrier alone)
-        {
-            double tot = 0.0;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) tot += sRed[((buf * NW + w) * 4 + wave) * 64 + lane];
-            (Pd + (size_t)J * 256 + lane_x)[wave * 64] = tot;
-        }
-    };
-    StepIn in_a, in_b;
-    if (row_ok && I0 >= I) fetch(I0, in_a);  // (wave 0; the others fetch their first tile in the step before it)
-    for (int J = I0; J < nbk; J += 2) {
-        step(J, in_a, in_b);
-        if (J + 1 < nbk) step(J + 1, in_b, in_a);
-    }
-    if (row_ok) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) (XYd + (size_t)I * (TS * 16) + lane_x)[r * 64] = fma(dpp_mov<0x128>(own2[r]), lane_sgn, own1[r]);
-    }
-}
-
-// X_J += the partials of the workgroups 0 .. (J - i0) / 4 of band_xl_sweep4_kernel, in that order (grid: block columns x matrices)
-__global__ void __launch_bounds__(256)
-band_xl_xsum_kernel(d2* __restrict__ XYall, const double* __restrict__ Pall, size_t p_stride, int n, int i0) {
-    const int nbk = (n + TS - 1) / TS, npad = nbk * TS;
-    const size_t mat = blockIdx.y;
-    const int J = i0 + (int)blockIdx.x;
-    double* X = reinterpret_cast<double*>(XYall + mat * (size_t)npad * PB) + (size_t)J * 256 + threadIdx.x;
-    const double* P = Pall + mat * p_stride + (size_t)J * 256 + threadIdx.x;
-    double acc = *X;
-    const int last = (J - i0) / 4;
-    for (int g = 0; g <= last; ++g) acc += P[(size_t)g * nbk * 256];
-    *X = acc;
-}
-
 // the band rows from row0 on out of a matrix buffer (the one-sweep chain: the rows behind the last panel), and the whole band back
 // INTO the caller's matrix buffer (tbk_tridiagonal_reduce hands that buffer out as the work copy of the reduction)
 __global__ void __launch_bounds__(256) band_extract_from_kernel(const double* __restrict__ Hall, int n, d2* __restrict__ band_all, size_t band_stride, int row0) {
@@ -882,18 +619,7 @@ __global__ void __launch_bounds__(256) band_deposit_kernel(double* __restrict__ 
 // launchers
 // ------------------------------------------------------------------------------------------------
 // the second matrix buffer of the chain (ws_xl), per matrix of a chunk: only the sizes that ALWAYS take the chain count for the chunk size
-// (+ the partial sums of band_xl_sweep4_kernel: [workgroups = block rows / 4][block columns][16 x 8 complex])
-static size_t xl_partial_doubles(int n) {
-    const size_t nbk = (size_t)((n + TS - 1) / TS);
-    return (nbk + 3) / 4 * nbk * 256;
-}
-static bool xl_sweep4() {
-    static const bool on = tbk_exp_env("TBK_BAND_XL_SWEEP4") && atoi(tbk_exp_env("TBK_BAND_XL_SWEEP4")) != 0;
-    return on;
-}
-size_t tbk_band_xl_buffer_per_matrix(int n) {
-    return tbk_band_is_xl(n) ? (size_t)n * n * sizeof(d2) + (xl_sweep4() ? xl_partial_doubles(n) * sizeof(double) : 0) : 0;
-}
+size_t tbk_band_xl_buffer_per_matrix(int n) { return tbk_band_is_xl(n) ? (size_t)n * n * sizeof(d2) : 0; }
 bool tbk_band_split(const tbk_model* m, int64_t nk);
 // The chain's second matrix buffer for calls / chunks of up to max_nk matrices, reserved where the callers reserve ws_band and
 // ws_bandmat -- in front of the pipeline, not inside a launch (a grow there is a free + malloc, i.e. a device synchronisation
@@ -902,14 +628,13 @@ bool tbk_band_split(const tbk_model* m, int64_t nk);
 int tbk_band_xl_reserve(tbk_model* m, int64_t max_nk) {
     const int n = m->n_orb;
     if (!(tbk_band_is_xl(n) || tbk_band_split(m, max_nk))) return TBK_OK;
-    return m->ws_xl.reserve((size_t)max_nk * ((size_t)n * n * sizeof(d2) + (xl_sweep4() ? xl_partial_doubles(n) * sizeof(double) : 0)));
+    return m->ws_xl.reserve((size_t)max_nk * n * n * sizeof(d2));
 }
 // The first stage above 1024 orbitals: three launches per panel (serial phases / update sweep / product sweep), one more update
 // sweep for the last pending update, then the band's way out.
 static int xl_groups(int n, int64_t nk) {
-    // TBK_BAND_XL_GROUPS=g (1 - 4; measurements): default 2
-    static const int groups_env = tbk_exp_env("TBK_BAND_XL_GROUPS") ? std::min(4, std::max(1, atoi(tbk_exp_env("TBK_BAND_XL_GROUPS")))) : 2;
-    return (tbk_band_is_xl(n) && nk >= 4 * groups_env) ? groups_env : 1;
+    constexpr int XL_GROUPS = 2;  // (1 - 4 were measured)
+    return (tbk_band_is_xl(n) && nk >= 4 * XL_GROUPS) ? XL_GROUPS : 1;
 }
 bool tbk_band_xl_grouped(int n, int64_t nk) { return xl_groups(n, nk) > 1; }
 
@@ -926,50 +651,18 @@ int tbk_band_launch_xl(tbk_model* m, hipStream_t s, double* d_H, int n, int64_t 
     int p_end = 0;  // first panel without a trailing matrix behind it
     while (n - PB * (p_end + 1) >= 2) ++p_end;
     constexpr int NTS = 512, NTP = 256;
-    // TBK_BAND_XL_SWEEPS=2 (measurements): the update sweep and the product sweep as two launches on ONE matrix buffer (the first
-    // form of the chain: every tile crosses HBM four times per panel)
-    static const bool two_sweeps = tbk_exp_env("TBK_BAND_XL_SWEEPS") && atoi(tbk_exp_env("TBK_BAND_XL_SWEEPS")) == 2;
-#ifdef TBK_EXPERIMENTS
-    if (two_sweeps) {
-        for (int p = 0; p <= p_end; ++p) {
-            hipLaunchKernelGGL((band_xl_serial_kernel<NTS, false>), dim3((unsigned)nk), dim3(NTS), 0, s, d_H, n, d_VW, d_VN, d_XY, d_T, p,
-                               (d2*)nullptr, (size_t)0);
-            if (p == p_end) break;
-            const int i0 = PB * (p + 1) / TS, na = nbk - i0;
-            if (p > 0)
-                hipLaunchKernelGGL((band_xl_update_kernel<NTP>), dim3((unsigned)na, (unsigned)nk), dim3(NTP), 0, s, d_H, n, d_VW, i0);
-            hipLaunchKernelGGL((band_xl_product_kernel<NTP>), dim3((unsigned)na, (unsigned)nk), dim3(NTP), 0, s, d_H, n, d_VN, d_XY, i0);
-        }
-        if (p_end > 0) {  // the last pending update (no look-ahead consumed any of its rows)
-            const int i0 = PB * p_end / TS;
-            hipLaunchKernelGGL((band_xl_update_kernel<NTP>), dim3((unsigned)(nbk - i0), (unsigned)nk), dim3(NTP), 0, s, d_H, n, d_VW, i0);
-        }
-        hipLaunchKernelGGL(band_extract_kernel, dim3((unsigned)nk), dim3(256), 0, s, d_H, n, d_band, stride);
-        TBK_HIP(hipGetLastError());
-        return TBK_OK;
-    }
-#else
-    (void)two_sweeps;
-#endif
     // One sweep per panel between two matrix buffers (the caller's and ws_xl) that change roles; the finished rows go to the band
     // as the serial phases produce them, the rows behind the last panel come out of the buffer the last update leaves them in,
     // and the band is put back into the caller's buffer (the work copy tbk_tridiagonal_reduce hands out).
-    // TBK_BAND_XL_SWEEP4=1 (measurements): band_xl_sweep4_kernel -- every tile read once, four block rows per workgroup -- for every
-    // call of the process.  Built in round 5 and not faster (DESIGN_LOG.md R5.12: 64 / 256 matrices of 1536 orbitals 1.256 -> 1.288 /
-    // 0.940 -> 0.893 ms per k-point, of 2048 orbitals 2.585 -> 2.637 / 2.195 -> 2.214): the one-row sweep stays.
-    const bool sweep4 = xl_sweep4();
-    const size_t p_stride = xl_partial_doubles(n);
-    TBK_CHECK(m->ws_xl.reserve((size_t)nk * n * n * 2 * sizeof(double) + (sweep4 ? (size_t)nk * p_stride * sizeof(double) : 0)));
+    // (a read-once sweep of four block rows per workgroup was built in round 5 and not faster, DESIGN_LOG.md R5.12: 64 / 256
+    // matrices of 1536 orbitals 1.256 -> 1.288 / 0.940 -> 0.893 ms per k-point, of 2048 orbitals 2.585 -> 2.637 / 2.195 -> 2.214)
+    TBK_CHECK(m->ws_xl.reserve((size_t)nk * n * n * 2 * sizeof(double)));
     double* buf[2] = {d_H, m->ws_xl.as<double>()};
-    double* d_P = m->ws_xl.as<double>() + (size_t)nk * n * n * 2;  // (partial sums of the read-once sweep: experiments build)
-    (void)d_P;
-    // up to 1024 orbitals (calls of a few matrices): the panel's rows in LDS (TBK_BAND_XL_YLDS=0: in global memory, as above 1024)
-    static const bool y_lds_env = !(tbk_exp_env("TBK_BAND_XL_YLDS") && atoi(tbk_exp_env("TBK_BAND_XL_YLDS")) == 0);
-    const bool y_lds = y_lds_env && n <= BAND_ONE_WG_MAXN;
+    // up to 1024 orbitals (calls of a few matrices): the panel's rows in LDS (above 1024: in global memory)
+    const bool y_lds = n <= BAND_ONE_WG_MAXN;
     const size_t y_bytes = (size_t)npad * PB * sizeof(d2);
-    // up to 256 orbitals the rows fill four waves only: a workgroup of four (TBK_BAND_XL_SERIAL4=0: eight, measurements) meets faster
-    static const bool serial4_env = !(tbk_exp_env("TBK_BAND_XL_SERIAL4") && atoi(tbk_exp_env("TBK_BAND_XL_SERIAL4")) == 0);
-    const bool four_waves = serial4_env && y_lds && n <= 256;
+    // up to 256 orbitals the rows fill four waves only: a workgroup of four (instead of eight) meets faster
+    const bool four_waves = y_lds && n <= 256;
     if (y_lds) {
         static std::atomic<bool> raised[TBK_MAX_DEVICES] = {};
         TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&band_xl_serial_kernel<NTS, true>), 132 * 1024, raised));
@@ -981,8 +674,6 @@ int tbk_band_launch_xl(tbk_model* m, hipStream_t s, double* d_H, int n, int64_t 
     // stage is one workgroup per matrix for 2 n ticks -- one group's chains run under the other groups' sweeps.  Per matrix nothing
     // changes (same launches, same order, same bits).
     const int groups = xl_groups(n, nk);
-    // TBK_BAND_XL_WALK=1 (measurements): the pairing walk of band_xl_sweep_kernel
-    static const int walk_flag = (tbk_exp_env("TBK_BAND_XL_WALK") && atoi(tbk_exp_env("TBK_BAND_XL_WALK")) != 0) ? 2 : 0;
     auto chain = [&](hipStream_t st, int64_t k0, int64_t nkg) {
         double* b[2] = {buf[0] + (size_t)k0 * n * n * 2, buf[1] + (size_t)k0 * n * n * 2};
         d2* vw = d_VW + (size_t)k0 * nbk * 256;
@@ -1004,18 +695,9 @@ int tbk_band_launch_xl(tbk_model* m, hipStream_t s, double* d_H, int n, int64_t 
                                    stride);
             if (p == p_end) break;
             const int i0 = PB * (p + 1) / TS, na = nbk - i0;
-#ifdef TBK_EXPERIMENTS
-            if (sweep4) {
-                hipLaunchKernelGGL((band_xl_sweep4_kernel<NTP>), dim3((unsigned)((na + 3) / 4), (unsigned)nkg), dim3(NTP), 0, st, b[cur], b[cur ^ 1],
-                                   n, vw, vn, xy, d_P + (size_t)k0 * p_stride, p_stride, i0, p > 0 ? 1 : 0);
-                hipLaunchKernelGGL(band_xl_xsum_kernel, dim3((unsigned)na, (unsigned)nkg), dim3(256), 0, st, xy, d_P + (size_t)k0 * p_stride,
-                                   p_stride, n, i0);
-            } else
-#endif
-            {
-                hipLaunchKernelGGL((band_xl_sweep_kernel<NTP>), dim3((unsigned)na, (unsigned)nkg), dim3(NTP), 0, st, b[cur], b[cur ^ 1], n, vw, vn,
-                                   xy, i0, (p > 0 ? 1 : 0) | walk_flag);
-            }
+            // (flags bit 0: apply the pending update; bit 1, the pairing walk, was measured slower and stays off)
+            hipLaunchKernelGGL((band_xl_sweep_kernel<NTP>), dim3((unsigned)na, (unsigned)nkg), dim3(NTP), 0, st, b[cur], b[cur ^ 1], n, vw, vn, xy,
+                               i0, p > 0 ? 1 : 0);
             cur ^= 1;
         }
         if (p_end > 0) {  // the last pending update, in place (nobody reads tiles in this launch)

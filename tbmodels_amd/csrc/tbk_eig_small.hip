@@ -1019,32 +1019,29 @@ static int launch_tridiag_33_64(hipStream_t s, double* d_H, int n, int64_t nk, d
     // columns per lane = padded size / 4: a 40-orbital matrix in the 64-row instantiation does 16 column
     // updates per lane and step where 10 are enough (n = 48: 8.0 -> 7.2 ms per 65536 matrices)
     // Round 3: the four-wave kernel only does the first n - 32 steps; the trailing 32 x 32 block goes through the
-    // head of the matrix' own storage to the packed kernel (two matrices per wave).  TBK_SMALL_SPLIT=0: one kernel.
+    // head of the matrix' own storage to the packed kernel (two matrices per wave).
     // Calls of a few matrices (all of them resident at once: what counts is one matrix' latency, not issue slots) keep the
     // whole reduction in ONE launch of the four-wave kernel: a single 64 x 64 matrix 99 -> 78 us.  By the size of the CALL,
     // not of this chunk: TBK_OPT_K_CHUNK must not change results, and the forms differ in the last bit.
-    static const bool split_env = !(tbk_exp_env("TBK_SMALL_SPLIT") && atoi(tbk_exp_env("TBK_SMALL_SPLIT")) == 0);
-    const bool split_on = split_env && std::max(call_nk, nk) > 512;
+    const bool split_on = std::max(call_nk, nk) > 512;
     const int n_steps = split_on ? n - 32 : n - 1;
-    // TWO waves per matrix at every size when the kernel only does the first n - 32 steps (round 3; TBK_SMALL_NW2=0:
-    // four): those are the steps with the most FMAs per reduction / barrier / scalar chain, and halving the copies of
-    // that overhead buys more than the lower occupancy costs (178 registers at 64 rows: two waves per SIMD) -- cfg2
-    // 951 -> 963 k, cfg4 8.84 -> 9.26 M k-points/s.  For the WHOLE reduction it was a wash (4.07 vs 4.14 ms, round 2).
-    static const bool two_env = !(tbk_exp_env("TBK_SMALL_NW2") && atoi(tbk_exp_env("TBK_SMALL_NW2")) == 0);
-    const bool two_waves = split_on && two_env;
+    // TWO waves per matrix at every size when the kernel only does the first n - 32 steps (round 3): those are the steps
+    // with the most FMAs per reduction / barrier / scalar chain, and halving the copies of that overhead buys more than the
+    // lower occupancy costs (178 registers at 64 rows: two waves per SIMD) -- cfg2 951 -> 963 k, cfg4 8.84 -> 9.26 M
+    // k-points/s.  For the WHOLE reduction it was a wash (4.07 vs 4.14 ms, round 2).
 #define TBK_T4(NRV, NWV) \
     hipLaunchKernelGGL((herm_tridiag4_kernel<NRV, NWV>), grid, dim3(NWV * 64), 0, s, d_H, n, d_D, d_Eo, n_steps, h_stride, ldd, off)
     if (n <= 40 && split_on)
         TBK_T4(40, 2);
-    else if (n <= 48 && two_waves)
+    else if (n <= 48 && split_on)
         TBK_T4(48, 2);
     else if (n <= 48)
         TBK_T4(48, 4);
-    else if (n <= 56 && two_waves)
+    else if (n <= 56 && split_on)
         TBK_T4(56, 2);
     else if (n <= 56)
         TBK_T4(56, 4);
-    else if (two_waves)
+    else if (split_on)
         TBK_T4(64, 2);
     else
         TBK_T4(64, 4);

@@ -812,13 +812,12 @@ int tbk_launch_tridiag_stream(tbk_model* m, hipStream_t s, double* d_H, int64_t 
     // (tools/bench_sizes.py): four waves and a panel of 4 up to 128 orbitals (n = 80: 1.08 us per matrix against
     // 1.42 with eight waves and a panel of 8); above that panel / workgroup variants are within 2 % of each other
     // Round 3: the kernel stops after the first n - 64 steps and the register-resident kernels finish the trailing 64 x 64
-    // block (tbk_launch_tridiag_tail64); TBK_STREAM_SPLIT=0: the whole reduction here (measurements).
-    static const bool split_on = !(tbk_exp_env("TBK_STREAM_SPLIT") && atoi(tbk_exp_env("TBK_STREAM_SPLIT")) == 0);
+    // block (tbk_launch_tridiag_tail64).
     // above 128 orbitals: this kernel goes down to the trailing 128 x 128 block, the eight-wave register kernel to
     // 64 x 64 (TBK_REG128=0: this kernel down to 64)
-    const bool via128 = split_on && n > 128 && tbk_eig_reg128_supported(128);
-    const int n_steps = via128 ? n - 128 : split_on ? n - 64 : n - 1;
-    if (split_on && tbk_eig_reg128_supported(n))  // round 3: 65 .. 128 orbitals never leave the registers
+    const bool via128 = n > 128 && tbk_eig_reg128_supported(128);
+    const int n_steps = via128 ? n - 128 : n - 64;
+    if (tbk_eig_reg128_supported(n))  // round 3: 65 .. 128 orbitals never leave the registers
         TBK_CHECK(tbk_launch_tridiag_reg128(s, d_H, n, nk, d_D, d_Eo, (int64_t)n * n * 2, n, 0));
     else if (n <= 128)
         TBK_HIP((launch_stream<2, 4, 256>(s, (unsigned)nk, d_H, n, d_D, d_Eo, n_steps)));
@@ -831,7 +830,7 @@ int tbk_launch_tridiag_stream(tbk_model* m, hipStream_t s, double* d_H, int64_t 
     else
         TBK_HIP((launch_stream<8, 4, 512>(s, (unsigned)nk, d_H, n, d_D, d_Eo, n_steps)));
     if (via128) TBK_CHECK(tbk_launch_tridiag_reg128(s, d_H, 128, nk, d_D, d_Eo, (int64_t)n * n * 2, n, n - 128));
-    if (split_on) TBK_CHECK(tbk_launch_tridiag_tail64(s, d_H, nk, d_D, d_Eo, n, m->call_nk));
+    TBK_CHECK(tbk_launch_tridiag_tail64(s, d_H, nk, d_D, d_Eo, n, m->call_nk));
     return TBK_OK;
 }
 
@@ -849,7 +848,6 @@ int tbk_launch_bisect(tbk_model* m, hipStream_t s, const double* d_de, int64_t n
     const int64_t call_nk = std::max(m->call_nk, nk);
     int lpe = call_nk <= 32 ? 16 : call_nk <= 512 ? 4 : 1;
     unsigned threads, parts = 1;
-    static const int lpe_env = tbk_exp_env("TBK_BISECT_LPE") ? atoi(tbk_exp_env("TBK_BISECT_LPE")) : 0;  // (measurements: 1, 4 or 16 above 64 orbitals)
     if (n > 64) {
         // Above 64 orbitals (round 5): 16 or 4 lanes per eigenvalue at every size, over as many workgroups as that takes (until
         // round 4 the lanes had to fit ONE workgroup: 4 at 256 orbitals, 2 at 512 -- 31 sweeps where one lane with its secant steps
@@ -860,7 +858,6 @@ int tbk_launch_bisect(tbk_model* m, hipStream_t s, const double* d_de, int64_t n
         const int64_t eigenvalues = call_nk * (int64_t)n;
         if (lpe == 16 && eigenvalues * 16 > (int64_t(1) << 17)) lpe = 4;
         if (lpe == 4 && eigenvalues * 4 > (int64_t(1) << 18)) lpe = 1;
-        if (lpe_env == 1 || lpe_env == 4 || lpe_env == 16) lpe = lpe_env;
         if (lpe > 1) {
             threads = (unsigned)std::min(1024, n_pad);  // (the shared first round: one sweep per thread up to 1024 orbitals)
             const unsigned per = threads / (unsigned)lpe;  // eigenvalues per workgroup (>= the kernel's m_per = ceil(n / parts))

@@ -665,22 +665,12 @@ hipError_t launch_gemv(tbk_model* m, const HkArgs& a, size_t lds, hipStream_t s)
 // stops mattering (no difference measured at 16.5 vs 15.98 rounds: the chip is power-limited there).
 constexpr int TAIL_MAX_ROUNDS = 12;
 
-static int tail_split_rounds() {
-    static const int rounds = [] {
-        const char* v = tbk_exp_env("TBK_HK_TAIL_SPLIT");  // measurements only: "0" switches it off, N sets the limit
-        return v ? atoi(v) : TAIL_MAX_ROUNDS;
-    }();
-    return rounds;
-}
-
 // `a.splits` >= 1 with a.P / a.p_rows set by the caller when > 1; `grid` blocks of the tile walk.
 template <int MODE, int CONV>
 int launch(tbk_model* m, const HkArgs& a0, int grid) {
     hipStream_t s = m->stream;
-    // 73,728 B: above the 64 KiB default cap.  m->hk_lds_floor (the pipeline of the two-stage sizes, when H(k) of the next chunk
-    // runs beside a reduction): ask for more than half a CU's LDS, so that ONE contraction workgroup shares a CU with one
-    // reduction workgroup instead of two of a kind
-    const size_t lds = std::max<size_t>(2 * STAGE_DOUBLES * sizeof(double), m->hk_lds_floor);
+    // 73,728 B: above the 64 KiB default cap
+    const size_t lds = 2 * STAGE_DOUBLES * sizeof(double);
     static std::atomic<bool> raised[TBK_MAX_DEVICES] = {};
     static std::atomic<bool> raised_split[TBK_MAX_DEVICES] = {};
     TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&hk_dense_kernel<MODE, CONV, false>), 160 * 1024, raised));
@@ -693,7 +683,7 @@ int launch(tbk_model* m, const HkArgs& a0, int grid) {
     const int full = units / slots * slots, tail = units - full;
     const int unit_stages = (n_stage + a.splits - 1) / a.splits;
     int sub = 1;
-    if (full > 0 && tail > 0 && units < tail_split_rounds() * slots && unit_stages >= 8) {
+    if (full > 0 && tail > 0 && units < TAIL_MAX_ROUNDS * slots && unit_stages >= 8) {
         // Time of u equal workgroups in rounds of two per CU: one alone on its CU runs at 1.06 ms per tile against
         // 1.97 ms for each of two sharing it, so up to n_cu workgroups cost 0.54.  Sub-splitting the tail s ways
         // costs rounds(tail * s) / s plus the partial tiles (~90 ns per tile and sub-split) and three launches.
@@ -830,7 +820,6 @@ int tbk_launch_hk_dense(tbk_model* m, const double* d_A, int64_t nk, int64_t nk_
     int grid;
     if (a.mt_count >= 32) {  // below that a plain round-robin over the XCDs balances better
         a.xcd_rows = 4;
-        if (const char* v = tbk_exp_env("TBK_HK_XCD_ROWS")) a.xcd_rows = std::max(1, atoi(v));  // measurements only
         const int max_rows = (a.mt_count + 7) / 8;
         grid = max_rows * a.nt_count * 8;
     } else {

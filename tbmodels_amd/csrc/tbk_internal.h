@@ -66,18 +66,11 @@ void tbk_set_error(const char* fmt, ...);
     } while (0)
 
 // ------------------------------------------------------------------------------------------------
-// Environment switches.  The DEFAULT library reads only the switches a test uses as an independent cross-check of the product
-// path (plain getenv in the sources: TBK_BAND, TBK_BAND_SPLIT, TBK_BAND_XL, TBK_BAND_XL_FROM, TBK_CHASE_WINDOW, TBK_REG128,
-// TBK_REG128_NW2, TBK_GATHER_BLOCK_ROWS -- the table in DESIGN.md section 6).  Every measurement switch of a variant that was
-// built, measured and dropped goes through tbk_exp_env(), which is a constant NULL unless the library is built with
-// `make EXPERIMENTS=1` (-DTBK_EXPERIMENTS): a user cannot flip a product-path branch by accident, and the dead branches
-// fold away at compile time.
+// Environment switches.  The library reads only the switches a test uses as an independent cross-check of the product path
+// (TBK_BAND, TBK_BAND_SPLIT, TBK_BAND_XL, TBK_BAND_XL_FROM, TBK_CHASE_WINDOW, TBK_REG128, TBK_REG128_NW2,
+// TBK_GATHER_BLOCK_ROWS -- the table in DESIGN.md section 6).  Variants that were built, measured and dropped are not in the
+// sources; their measurements are in DESIGN_LOG.md and their code in the git history.
 // ------------------------------------------------------------------------------------------------
-#ifdef TBK_EXPERIMENTS
-inline const char* tbk_exp_env(const char* name) { return getenv(name); }
-#else
-inline const char* tbk_exp_env(const char*) { return nullptr; }
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // dynamic LDS above the 64 KiB default: hipFuncSetAttribute acts on the CURRENT device's copy of the
@@ -238,13 +231,11 @@ struct tbk_model {
     const double* d_pos_inline = nullptr;  // raw positions [n_orb][dim] on the device for the call in progress, else NULL
     std::vector<double> pos_cache;         // host copy of what ws_posraw holds
     DevBuf ws_posraw;
-    DevBuf ws_split;  // calls of a few matrices: T and the members' partial X between the launches of the first stage
     DevBuf ws_xl;     // the launch chain of band_xl_*: the second matrix buffer (the sweep of a panel reads one, writes the other)
     // Set for the duration of one eigenvalue call by tbk_eigenval_device_gather (tbk_comm.hip): the chunk pipeline calls it
     // whenever the eigenvalues of rows [c0, c0 + nkc) of the call have been enqueued, with an event recorded behind
     // them -- the all-gather of finished rows leaves on the communicator's stream while later chunks compute.
     std::function<int(int64_t c0, int64_t nkc, hipEvent_t done)> chunk_done;
-    size_t hk_lds_floor = 0;  // dynamic LDS the dense contraction asks for at least (0: what it needs)
     std::vector<EventPair> events;
     double t_ms[TBK_T_COUNT] = {0, 0, 0, 0};
     int64_t t_n[TBK_T_COUNT] = {0, 0, 0, 0};

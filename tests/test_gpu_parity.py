@@ -766,53 +766,6 @@ np.savez(out, d=d, e=e, h=h[:3])
     assert _lib is not None
 
 
-def test_the_read_once_sweep_above_1024_orbitals_stays_correct():
-    """``TBK_BAND_XL_SWEEP4=1`` (a measurement switch of the EXPERIMENTS build of the library, `libtbk_experiments.so` -- the default
-    library does not read it; read once per process, hence the child process): the panels' sweeps run four
-    block rows per workgroup, every tile is read once and the transposed products are added up through partial sums
-    (csrc/tbk_eig_band_xl.hip, band_xl_sweep4_kernel + band_xl_xsum_kernel; DESIGN_LOG.md R5.12: built, not faster, off by default).
-    Same function as the one-row sweep: the spectra are those of the matrices (scipy's eigvalsh at _tb_model.py:1149), two runs
-    give the same bits (the partial sums are added in a fixed order)."""
-    import os
-    import subprocess
-    import sys
-
-    from tbmodels_amd import _lib
-
-    if not os.path.exists(_lib.EXPERIMENTS_LIB_PATH):
-        pytest.skip("the read-once sweep is a dropped variant: only in the experiments build (make -C tbmodels_amd/csrc EXPERIMENTS=1)")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = """
-import numpy as np, scipy.linalg as la
-from tbmodels_amd import _lib
-lib = _lib.lib()
-assert b"+experiments" in lib.tbk_version()
-n, nk = 1040, 9
-rng = np.random.default_rng(78)
-m = rng.standard_normal((nk, n, n)) + 1j * rng.standard_normal((nk, n, n))
-h = np.ascontiguousarray((m + m.conj().transpose(0, 2, 1)) / 2)
-h[5] *= 1e-25
-h[6] = np.diag(np.diagonal(h[6]).real)
-out = []
-for rep in range(2):
-    d, e = np.empty((nk, n)), np.empty((nk, n))
-    _lib.check(lib.tbk_tridiagonal_reduce(0, n, nk, _lib.ptr(h), _lib.TBK_REDUCE_AUTO, _lib.ptr(d), _lib.ptr(e), None))
-    out.append((d, e))
-assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
-d, e = out[0]
-assert np.isfinite(d).all() and np.isfinite(e).all()
-for i in (0, 5, 6, 8):
-    ref = np.linalg.eigvalsh(h[i])
-    got = la.eigvalsh_tridiagonal(d[i], e[i, :-1])
-    assert np.abs(got - ref).max() <= 1e-13 * n * np.abs(ref).max(), i
-print("ok")
-"""
-    env = dict(os.environ, TBK_BAND_XL_SWEEP4="1", TBK_LIBTBK=_lib.EXPERIMENTS_LIB_PATH,
-               PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    run = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600, cwd=root)
-    assert run.returncode == 0 and run.stdout.strip().endswith("ok"), run.stderr[-2000:]
-
-
 def test_a_batch_above_1024_orbitals_in_groups_equals_its_matrices_one_at_a_time():
     """Above 1024 orbitals a batch goes in groups of matrices on streams of their own (csrc/tbk_eig_band_xl.hip, tbk_band_launch_xl:
     one group's serial phases and second stage under the other groups' sweeps).  Per matrix nothing may change: (d, e) and the
@@ -1001,7 +954,7 @@ def test_launch_chain_above_1024_orbitals_equals_the_model_at_small_sizes(n):
 @pytest.mark.parametrize("n_orb", [200, 300, 520])
 def test_launch_chain_of_small_calls_agrees_with_the_one_launch_kernel(n_orb):
     """Calls of a few matrices take the first stage of the two-stage reduction as a chain of launches (every tile pass on
-    several CUs, csrc/tbk_eig_band.hip PHASE 1 / 2); TBK_BAND_SPLIT=0 (read once per process) keeps the one-launch kernels:
+    several CUs, csrc/tbk_eig_band_xl.hip); TBK_BAND_SPLIT=0 (read once per process) keeps the one-launch kernels:
     the same eigenvalues to rounding, both within 1e-10 of the oracle; the chain is deterministic."""
     import os
     import subprocess

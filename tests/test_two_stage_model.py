@@ -105,7 +105,7 @@ def _band_eig_error(h, panel_qr):
 
 @pytest.mark.parametrize("n", [40, 97])
 def test_gram_panel_qr_is_as_accurate_as_the_sequential_one_and_restarts_where_it_must(n):
-    """Round 5 (csrc/tbk_eig_band.hip, TBK_PANEL_GRAM): all reflectors of a panel from ONE Gram matrix.  The remaining norm
+    """Round 5 (csrc/tbk_eig_band.hip, GRAM / GRAM2): all reflectors of a panel from ONE Gram matrix.  The remaining norm
     of a column is a difference of Gram sums; a column where it has cancelled below 1/64 of the full norm ends the round and a
     fresh Gram matrix is formed (model.panel_qr_gram).  Random matrices never need a second round; the structured matrices of
     tests/test_gpu_parity.py::test_eigensolver_structured_matrices that make columns (nearly) dependent -- graded, rank one,

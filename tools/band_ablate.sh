@@ -1,7 +1,8 @@
 #!/bin/bash
 # What the levers of the two-stage reduction's tile pass are worth, measured before anything is built on them
 # (DESIGN.md 5.5, round 4).  Builds tools/band_time with the TIMING-ONLY ablation switches of csrc/tbk_eig_band.hip --
-# results of those binaries are wrong by construction -- and runs them at 256 / 512 orbitals.
+# results of those binaries are wrong by construction -- and runs them at 256 / 512 orbitals (at 256 the time includes the second
+# stage, which runs fused behind the first).
 #   here:        bash tools/band_ablate.sh build
 #   GPU box:     bash tools/band_ablate.sh run > gpurun_out/ablate.txt
 cd "$(dirname "$0")/.."
@@ -19,7 +20,7 @@ if [ "$1" = build ]; then
 else
   for name in "${NAMES[@]}"; do
     echo "== $name"
-    TBK_BAND_FUSE=0 tools/exp/band_$name 256 8192 | tail -1
+    tools/exp/band_$name 256 8192 | tail -1
     tools/exp/band_$name 512 4096 | tail -1
   done
 fi

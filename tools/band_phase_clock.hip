@@ -6,7 +6,6 @@
 #include <cstdlib>
 #include <vector>
 
-#define TBK_EXPERIMENTS 1  // (this driver flips the measurement switches: tbk_exp_env reads the environment)
 #include "../tbmodels_amd/csrc/tbk_eig_band.hip"
 #include "../tbmodels_amd/csrc/tbk_eig_band_chase.hip"
 #include "../tbmodels_amd/csrc/tbk_eig_band_xl.hip"

@@ -10,7 +10,7 @@ make -s -C $C -j8 > /dev/null
 while [ $# -ge 3 ]; do
   name=$1; file=$2; defs=$3; shift 3
   ( /opt/rocm/bin/hipcc $FLAGS $defs -c $C/$file -o tools/exp/${name}_${file%.hip}.o 2>/dev/null &&
-    objs=$(ls $C/*.o | grep -v "\.exp\.o" | grep -v "/${file%.hip}.o") &&
+    objs=$(ls $C/*.o | grep -v "/${file%.hip}.o") &&
     /opt/rocm/bin/hipcc --offload-arch=gfx950 $objs tools/exp/${name}_${file%.hip}.o $LD -o tools/exp/libtbk_$name.so 2>/dev/null && echo built $name ) &
 done
 wait

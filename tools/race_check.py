@@ -4,7 +4,7 @@
     python tools/race_check.py <n> <nk> <reps>                 the reduction alone (tbk_tridiagonal_reduce) on random matrices
     python tools/race_check.py --model <n> <n_r> <nk> <reps>   the whole path (H(k) + reduction + bisection) through Model.eigenval_array
 
-Environment (read once per process): TBK_BAND_FUSE, TBK_BAND.  The second form found the one-in-250 000 race of round 3 (a wave
+Environment (read once per process): TBK_BAND.  The second form found the one-in-250 000 race of round 3 (a wave
 overwriting partial sums another wave was still adding up, csrc/tbk_eig_band.hip)."""
 import os
 import sys
@@ -34,8 +34,7 @@ def reduction_alone(n, nk, reps):
                 i = bad[0]
                 print("rep %d: %d matrices differ; first %d, max |dd| %.2e |de| %.2e" % (
                     rep, len(bad), i, np.abs(d[i] - first[0][i]).max(), np.abs(e[i] - first[1][i]).max()))
-    print("n=%d nk=%d reps=%d env FUSE=%s BAND=%s: %d differing matrices" % (
-        n, nk, reps, os.environ.get("TBK_BAND_FUSE"), os.environ.get("TBK_BAND"), bad_total))
+    print("n=%d nk=%d reps=%d env BAND=%s: %d differing matrices" % (n, nk, reps, os.environ.get("TBK_BAND"), bad_total))
 
 
 def whole_path(n, n_r, nk, reps):
@@ -58,7 +57,7 @@ def whole_path(n, n_r, nk, reps):
                 rep, len(bad), i, np.abs(again[i] - first[i]).max(), np.flatnonzero(again[i] != first[i])[:8]))
         if rep % 8 == 0 and not np.array_equal(model.hamilton(k[:256]), ham0):
             print("rep %d: hamilton differs" % rep)
-    print("n=%d n_r=%d nk=%d reps=%d FUSE=%s: %d differing rows" % (n, n_r, nk, reps, os.environ.get("TBK_BAND_FUSE"), bad_total))
+    print("n=%d n_r=%d nk=%d reps=%d: %d differing rows" % (n, n_r, nk, reps, bad_total))
 
 
 if __name__ == "__main__":

@@ -67,7 +67,7 @@ GRAM_STATS = {"rounds": 0, "panels": 0, "columns": 0}
 
 def panel_qr_gram(y, thresh=None):
     """
-    The panel QR of csrc/tbk_eig_band.hip with TBK_PANEL_GRAM (round 5): ALL reflectors of a round from ONE Gram matrix
+    The panel QR of csrc/tbk_eig_band.hip (round 5): ALL reflectors of a round from ONE Gram matrix
     G = P^H P of the panel's rows (formed on the matrix pipe, one meeting of the workgroup) and the explicitly tracked top
     rows -- the inner products every later reflector needs follow from G, which the reflectors leave invariant, minus the
     finished rows R[i]:  g_c[t] = G[c][t] - sum_{i<c} conj(R[i][c]) R[i][t].  Every wave runs the 8-step recurrence on
