@@ -135,8 +135,9 @@ static int require_device(int device) {
 }
 
 // everything both model kinds share: stream, rocBLAS handle, lattice vectors, packed-element map
+// (pair_diagonal: the slot map of dense tight-binding models, two diagonal elements per slot -- tbk_internal.h)
 static int create_common(int device, int dim, int n_orb, int64_t n_r, const int32_t* R,
-                         int64_t k_rows_per_r, tbk_model** out) {
+                         int64_t k_rows_per_r, bool pair_diagonal, tbk_model** out) {
     TBK_ARG(out != nullptr, "out is NULL");
     *out = nullptr;
     TBK_ARG(dim >= 1 && dim <= TBK_MAX_DIM, "dim must be in [1, 8]");
@@ -161,7 +162,7 @@ static int create_common(int device, int dim, int n_orb, int64_t n_r, const int3
     // K rows are padded to whole LDS stages (TBK_BK); padding rows carry zero hoppings
     m->k2 = round_up(n_r * k_rows_per_r, TBK_BK);
     m->n_r_pad = m->k2 / k_rows_per_r;
-    m->ncol = (int)((int64_t)n_orb * (n_orb + 1) / 2);
+    m->ncol = (int)(pair_diagonal ? (int64_t)n_orb * (n_orb - 1) / 2 + (n_orb + 1) / 2 : (int64_t)n_orb * (n_orb + 1) / 2);
     m->ncol_pad = (int)round_up(m->ncol, TBK_BNP);
 
     int rc = TBK_OK;
@@ -204,12 +205,19 @@ static int create_common(int device, int dim, int n_orb, int64_t n_r, const int3
         m->h_stage_bytes = 0;
     }
 
-    // packed upper-triangle map, row-major over (i <= j): consecutive e -> consecutive j
+    // packed upper-triangle map, row-major over (i <= j): consecutive e -> consecutive j.  With pair_diagonal, row i
+    // starts with the slot of the diagonal pair (i, i + 1) when i is even (a single (i, i) for the last row of an odd
+    // n_orb, whose Im plane is then 0 by construction) and holds no diagonal slot when i is odd.
     {
         std::vector<int32_t> colmap((size_t)m->ncol_pad, -1);
         size_t e = 0;
-        for (int i = 0; i < n_orb; ++i)
-            for (int j = i; j < n_orb; ++j) colmap[e++] = (int32_t)((i << 16) | j);
+        for (int i = 0; i < n_orb; ++i) {
+            if (!pair_diagonal)
+                colmap[e++] = (int32_t)((i << 16) | i);
+            else if (i % 2 == 0)
+                colmap[e++] = i + 1 < n_orb ? (int32_t)((i << 16) | TBK_SLOT_PAIR | (i + 1)) : (int32_t)((i << 16) | i);
+            for (int j = i + 1; j < n_orb; ++j) colmap[e++] = (int32_t)((i << 16) | j);
+        }
         TBK_TRY(TBK_HIP(hipMalloc((void**)&m->d_colmap, colmap.size() * sizeof(int32_t))));
         TBK_TRY(TBK_HIP(hipMemcpy(m->d_colmap, colmap.data(), colmap.size() * sizeof(int32_t),
                                   hipMemcpyHostToDevice)));
@@ -238,7 +246,7 @@ extern "C" int tbk_model_create_dense(int device, int dim, int n_orb, int64_t n_
     *out = nullptr;
     TBK_ARG(n_r == 0 || hop != nullptr, "hop is NULL");
     tbk_model* m = nullptr;
-    TBK_CHECK(create_common(device, dim, n_orb, n_r, R, 2, &m));
+    TBK_CHECK(create_common(device, dim, n_orb, n_r, R, 2, true, &m));
     m->sparse = false;
     int rc = TBK_OK;
     double* d_raw = nullptr;
@@ -278,7 +286,7 @@ extern "C" int tbk_model_create_csr(int device, int dim, int n_orb, int64_t n_r,
                 "row/col index out of range");
 
     tbk_model* m = nullptr;
-    TBK_CHECK(create_common(device, dim, n_orb, n_r, R, 2, &m));
+    TBK_CHECK(create_common(device, dim, n_orb, n_r, R, 2, false, &m));
     m->sparse = true;
 
     // transpose "per lattice vector, which elements" into "per packed element, which lattice
@@ -1246,7 +1254,7 @@ extern "C" int tbk_tridiagonal_reduce(int device, int n_orb, int64_t nk, const d
     if (nk == 0) return TBK_OK;
     TBK_ARG(H && d && e, "H / d / e is NULL");
     tbk_model* m = nullptr;
-    TBK_CHECK(create_common(device, 1, n_orb, 0, nullptr, 2, &m));
+    TBK_CHECK(create_common(device, 1, n_orb, 0, nullptr, 2, false, &m));
     const size_t n = (size_t)n_orb, mat_bytes = n * n * 2 * sizeof(double);
     int rc = [&]() -> int {
         TBK_LOCK(m);
@@ -1295,7 +1303,7 @@ extern "C" int tbk_reduce_standalone(int device, int n_orb, int64_t nk, int reps
     TBK_ARG(n_orb >= 1 && (n_orb <= 64 || tbk_eig_stream_supported(n_orb)), "n_orb must be in [1, 4096]");
     for (int q = 0; q < 3; ++q) us_per_matrix[q] = 0.0;
     tbk_model* m = nullptr;
-    TBK_CHECK(create_common(device, 1, n_orb, 0, nullptr, 2, &m));
+    TBK_CHECK(create_common(device, 1, n_orb, 0, nullptr, 2, false, &m));
     const size_t n = (size_t)n_orb, mat_bytes = n * n * 2 * sizeof(double);
     DevBuf pristine;
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -1360,7 +1368,7 @@ extern "C" int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, con
     TBK_ARG(n_p == 0 || (powers && coeffs), "powers / coeffs is NULL");
     for (int64_t t = 0; t < n_p * dim; ++t) TBK_ARG(powers[t] >= 0, "negative power");
     tbk_model* m = nullptr;
-    TBK_CHECK(create_common(device, dim, n_orb, n_p, nullptr, 1, &m));
+    TBK_CHECK(create_common(device, dim, n_orb, n_p, nullptr, 1, false, &m));
     m->kdotp = true;
     double* d_raw = nullptr;
     const size_t raw_bytes = (size_t)n_p * n_orb * n_orb * 2 * sizeof(double);

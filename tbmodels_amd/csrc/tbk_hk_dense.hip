@@ -5,8 +5,9 @@
 //
 //     A   [k2][nk_pad]                 cos/sin rows from tbk_phase.hip (k contiguous)
 //     Bt  [k2][ncol_pad/16][2][16]     symmetrised hoppings from tbk_stage.hip
-//     e = packed upper-triangle element (i <= j);  output scattered to H[k][i][j] (and, in FULL
-//     mode, the conjugate to H[k][j][i]) -- the `H += H^H` of :1123 is already inside Bt.
+//     e = packed slot: an upper-triangle element (i <= j), or two diagonal elements (TBK_SLOT_PAIR);
+//     output scattered to H[k][i][j] (and, in FULL mode, the conjugate to H[k][j][i]) by store_slot --
+//     the `H += H^H` of :1123 is already inside Bt.
 //
 // Machine mapping (gfx950):
 //   * v_mfma_f64_16x16x4_f64: 16 k-points x 16 columns x 4 K rows per instruction, one f64 of A and
@@ -124,6 +125,21 @@ __device__ __forceinline__ void store_element(const HkArgs& a, int64_t kq, int o
     double* hk = a.H + (size_t)kq * a.n_orb * a.n_orb * 2;
     *reinterpret_cast<d2*>(hk + ((size_t)oi * a.n_orb + oj) * 2) = (d2){re, im};
     if (MODE == HK_FULL && oi != oj) *reinterpret_cast<d2*>(hk + ((size_t)oj * a.n_orb + oi) * 2) = (d2){re, -im};
+}
+
+// One finished packed slot (tbk_internal.h): an element, or the pair of diagonal elements (Re H[i][i], Re H[j][j]) whose
+// Im parts are exactly 0 -- in both conventions, the convention-1 phase being 1 on the diagonal.  P / P2 and the partial
+// sums of every path hold the slot's two planes as they are; only this store decodes them.
+template <int MODE, int CONV>
+__device__ __forceinline__ void store_slot(const HkArgs& a, int64_t kq, int32_t slot, double v0, double v1) {
+    const int oi = slot >> 16, oj = slot & 0x7fff;
+    if (slot & TBK_SLOT_PAIR) {
+        double* hk = a.H + (size_t)kq * a.n_orb * a.n_orb * 2;
+        *reinterpret_cast<d2*>(hk + ((size_t)oi * a.n_orb + oi) * 2) = (d2){v0, 0.0};
+        *reinterpret_cast<d2*>(hk + ((size_t)oj * a.n_orb + oj) * 2) = (d2){v1, 0.0};
+        return;
+    }
+    store_element<MODE, CONV>(a, kq, oi, oj, v0, v1);
 }
 
 __device__ __forceinline__ bool tile_of_block(const HkArgs& a, int b, int& mt, int& nt) {
@@ -317,7 +333,6 @@ __global__ void __launch_bounds__(256, 2) hk_dense_kernel(const HkArgs a) {
         const int e = (int)n0 + (wn * 2 + j) * 16 + l15;
         const int32_t ij = a.colmap[e];
         if (ij < 0) continue;
-        const int oi = ij >> 16, oj = ij & 0xffff;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -333,7 +348,7 @@ __global__ void __launch_bounds__(256, 2) hk_dense_kernel(const HkArgs a) {
                             : a.P + (((size_t)split_y * a.p_rows + kq) * a.ncol_pad + e) * 2;
                     *reinterpret_cast<d2*>(part) = (d2){acc[i][j][0][r], acc[i][j][1][r]};
                 } else {
-                    store_element<MODE, CONV>(a, kq, oi, oj, acc[i][j][0][r], acc[i][j][1][r]);
+                    store_slot<MODE, CONV>(a, kq, ij, acc[i][j][0][r], acc[i][j][1][r]);
                 }
             }
         }
@@ -368,7 +383,14 @@ __global__ void __launch_bounds__(256) hk_gemv_kernel(const HkArgs a, int strip_
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nblk = a.ncol_pad >> 6;
-    const int task = (int)blockIdx.x * 4 + wave;
+    // XCD x (block b runs on XCD b % 8) takes a contiguous range of workgroups, i.e. whole rows of Bt.  In dispatch order,
+    // with nblk a multiple of 32 (the pair-slot layout at 64, 128, 512 orbitals) every workgroup of an XCD reads the same
+    // 4 KiB column stripe of every 32 KiB row: one-k hamilton at the headline shape took 76 us that way, 66 us this way
+    // (67 us with the 33 blocks of the one-slot-per-element layout in dispatch order).  The sums are the same either way.
+    const int b = (int)blockIdx.x, n_wg = (int)gridDim.x;
+    const int xcd = b & 7, per_xcd = n_wg >> 3, extra = n_wg & 7;
+    const int wg = xcd * per_xcd + min(xcd, extra) + (b >> 3);
+    const int task = wg * 4 + wave;
     const int sl = task / nblk, cb = task - sl * nblk;
     if (sl >= a.splits) return;  // (whole waves: nothing below synchronises the workgroup)
     const int64_t n_pairs = a.k2 >> 1;  // slices are cut between lattice vectors: a (cos, sin) pair of rows stays together
@@ -528,7 +550,7 @@ __global__ void __launch_bounds__(256) hk_tiny_kernel(const HkArgs a, int strip_
         sum[0] += part[w * 64 + lane][0];
         sum[1] += part[w * 64 + lane][1];
     }
-    store_element<MODE, CONV>(a, 0, ij >> 16, ij & 0xffff, sum[0], sum[1]);
+    store_slot<MODE, CONV>(a, 0, ij, sum[0], sum[1]);
 }
 
 // split-K finish: one thread per (k-point, packed element) adds the partial tiles in split order and stores the
@@ -547,7 +569,7 @@ __global__ void __launch_bounds__(256) hk_finish_kernel(const HkArgs a) {
         re += v[0];
         im += v[1];
     }
-    store_element<MODE, CONV>(a, kq, ij >> 16, ij & 0xffff, re, im);
+    store_slot<MODE, CONV>(a, kq, ij, re, im);
 }
 
 // The same for many splits and few k-points (the matrix-vector path: ~100 K slices, one k-point): 16 threads per
@@ -583,7 +605,7 @@ __global__ void __launch_bounds__(256) hk_finish_wide_kernel(const HkArgs a) {
         if (ij < 0) return;
         const double sr = (part[0][el][0] + part[1][el][0]) + (part[2][el][0] + part[3][el][0]);
         const double si = (part[0][el][1] + part[1][el][1]) + (part[2][el][1] + part[3][el][1]);
-        store_element<MODE, CONV>(a, kq, ij >> 16, ij & 0xffff, sr, si);
+        store_slot<MODE, CONV>(a, kq, ij, sr, si);
     }
 }
 
@@ -612,7 +634,7 @@ __global__ void __launch_bounds__(256) hk_finish_tiles_kernel(const HkArgs a) {
         if (a.splits > 1)
             *reinterpret_cast<d2*>(a.P + (((size_t)split_y * a.p_rows + kq) * a.ncol_pad + e) * 2) = (d2){re, im};
         else
-            store_element<MODE, CONV>(a, kq, ij >> 16, ij & 0xffff, re, im);
+            store_slot<MODE, CONV>(a, kq, ij, re, im);
     }
 }
 

@@ -24,6 +24,12 @@ constexpr int TBK_BK = 16;       // depth of one LDS stage in real K rows (= 8 l
 constexpr int TBK_CT = 16;       // packed elements per MFMA column tile
 constexpr int TBK_MAX_DIM = 8;   // lattice dimension limit of the phase kernel
 
+// Packed slots of the dense operand (d_colmap): (i << 16) | j for the element H[i][j], i <= j, one real column per plane
+// (Re, Im); -1 for padding.  Tight-binding models put TWO diagonal elements in one slot, (i << 16) | TBK_SLOT_PAIR | j:
+// plane 0 is Re H[i][i], plane 1 Re H[j][j] (their Im parts are 0 by construction and not contracted), so N orbitals
+// take N (N - 1) / 2 + ceil(N / 2) = ceil(N^2 / 2) slots instead of N (N + 1) / 2.  j < 32768: bit 15 is free.
+constexpr int32_t TBK_SLOT_PAIR = 0x8000;
+
 // ------------------------------------------------------------------------------------------------
 // error plumbing
 // ------------------------------------------------------------------------------------------------
@@ -155,10 +161,11 @@ struct tbk_model {
     // --- common staging ---
     int64_t n_r_pad = 0;   // n_r rounded up so that 2 * n_r_pad is a multiple of TBK_BK
     int64_t k2 = 0;        // real K rows of the contraction: 2 * n_r_pad (cos, sin per lattice vector)
-    int ncol = 0;          // n_orb (n_orb + 1) / 2 packed upper-triangle elements
+    int ncol = 0;          // packed slots: ceil(n_orb^2 / 2) for dense tight-binding models (diagonal pairs),
+                           // n_orb (n_orb + 1) / 2 upper-triangle elements for CSR and k.p models
     int ncol_pad = 0;      // rounded up to TBK_BNP
     int32_t* d_R = nullptr;       // [n_r_pad][dim] lattice vectors (padding rows are zero)
-    int32_t* d_colmap = nullptr;  // [ncol_pad]  (i << 16) | j, or -1 for padding
+    int32_t* d_colmap = nullptr;  // [ncol_pad]  (i << 16) | j, (i << 16) | TBK_SLOT_PAIR | j, or -1 for padding
     int32_t* d_powers = nullptr;  // k.p only: [n_r][dim] monomial exponents
 
     // --- dense: symmetrised hop planes, tile-interleaved  Bt[K2][ncol_pad / 16][2][16] ---

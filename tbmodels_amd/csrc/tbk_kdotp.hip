@@ -6,7 +6,8 @@
 // the derivative flavour of the Fourier sum: the same staged operand Bt (tbk_stage.hip), the phase of ONE
 // k-point, and a monomial weight R^p per lattice vector.  C_p is Hermitian, so only the packed upper
 // triangle is accumulated and the lower one is written as its conjugate.  The work is n_p * N(N+1)/2 * N_R
-// complex multiply-adds (20 * 2080 * 4096 at order 3 of the headline model): one thread per (element, p).
+// complex multiply-adds (20 * 2080 * 4096 at order 3 of the headline model): one thread per (packed slot, p), i.e.
+// per element, or per two diagonal elements of a TBK_SLOT_PAIR slot.
 
 #include <algorithm>
 
@@ -38,7 +39,8 @@ kdotp_coeff_kernel(const double* __restrict__ Bt, const int32_t* __restrict__ co
     const int p = blockIdx.y;
     if (e >= ncol) return;
     const int32_t ij = colmap[e];
-    const int oi = ij >> 16, oj = ij & 0xffff;
+    const int oi = ij >> 16, oj = ij & 0x7fff;
+    const bool pair = (ij & TBK_SLOT_PAIR) != 0;
     int pw[TBK_MAX_DIM];
     int deg = 0;
     for (int d = 0; d < dim; ++d) {
@@ -48,7 +50,7 @@ kdotp_coeff_kernel(const double* __restrict__ Bt, const int32_t* __restrict__ co
     const double sgn = (deg & 1) ? -1.0 : 1.0;
     const size_t tiles = ncol_pad / TBK_CT;
     const size_t col = ((size_t)(e / TBK_CT) * 2) * TBK_CT + e % TBK_CT;
-    double xr = 0.0, xi = 0.0;
+    double xr = 0.0, xi = 0.0, yr = 0.0, yi = 0.0;  // (y: H[j][j] of a pair slot)
     for (int64_t r = 0; r < n_r; ++r) {
         double mono = 1.0;
         for (int d = 0; d < dim; ++d) {
@@ -58,20 +60,34 @@ kdotp_coeff_kernel(const double* __restrict__ Bt, const int32_t* __restrict__ co
         if (mono == 0.0) continue;
         const double* row_c = Bt + (size_t)(2 * r) * tiles * 2 * TBK_CT + col;      // cos row
         const double* row_s = Bt + (size_t)(2 * r + 1) * tiles * 2 * TBK_CT + col;  // sin row
-        // staged planes: cos row = (hr + gr, hi - gi), sin row = (-(hi + gi), hr - gr);  h = hop[i][j], g = hop[j][i]
-        const double s_re = row_c[0], d_im = row_c[TBK_CT], ms_im = row_s[0], d_re = row_s[TBK_CT];
-        const double hr = 0.5 * (s_re + d_re), gr = 0.5 * (s_re - d_re);
-        const double hi = 0.5 * (d_im - ms_im), gi = 0.5 * (-ms_im - d_im);
         const double c = ph[2 * r], s = ph[2 * r + 1];
-        // ph h + sgn conj(ph) conj(g)
-        const double tr = (c * hr - s * hi) + sgn * (c * gr - s * gi);
-        const double ti = (c * hi + s * hr) - sgn * (c * gi + s * gr);
-        xr = fma(mono, tr, xr);
-        xi = fma(mono, ti, xi);
+        // staged planes: cos row = (hr + gr, hi - gi), sin row = (-(hi + gi), hr - gr);  h = hop[i][j], g = hop[j][i].  On the
+        // diagonal hi - gi = hr - gr = 0: a pair slot leaves those planes out (cos row (2 hr_ii, 2 hr_jj), sin row
+        // (-2 hi_ii, -2 hi_jj)) and each of its elements is the single-element case with them 0
+        auto term = [&](double s_re, double d_im, double ms_im, double d_re, double& ar, double& ai) {
+            const double hr = 0.5 * (s_re + d_re), gr = 0.5 * (s_re - d_re);
+            const double hi = 0.5 * (d_im - ms_im), gi = 0.5 * (-ms_im - d_im);
+            // ph h + sgn conj(ph) conj(g)
+            const double tr = (c * hr - s * hi) + sgn * (c * gr - s * gi);
+            const double ti = (c * hi + s * hr) - sgn * (c * gi + s * gr);
+            ar = fma(mono, tr, ar);
+            ai = fma(mono, ti, ai);
+        };
+        if (pair) {
+            term(row_c[0], 0.0, row_s[0], 0.0, xr, xi);
+            term(row_c[TBK_CT], 0.0, row_s[TBK_CT], 0.0, yr, yi);
+        } else {
+            term(row_c[0], row_c[TBK_CT], row_s[0], row_s[TBK_CT], xr, xi);
+        }
     }
     const double fr = prefactor[2 * p], fi = prefactor[2 * p + 1];
-    const double cr = fr * xr - fi * xi, ci = fr * xi + fi * xr;
     double* cp = out + (size_t)p * n_orb * n_orb * 2;
+    const double cr = fr * xr - fi * xi, ci = fr * xi + fi * xr;
+    if (pair) {
+        *reinterpret_cast<d2*>(cp + ((size_t)oi * n_orb + oi) * 2) = (d2){cr, ci};
+        *reinterpret_cast<d2*>(cp + ((size_t)oj * n_orb + oj) * 2) = (d2){fr * yr - fi * yi, fr * yi + fi * yr};
+        return;
+    }
     *reinterpret_cast<d2*>(cp + ((size_t)oi * n_orb + oj) * 2) = (d2){cr, ci};
     if (oi != oj) *reinterpret_cast<d2*>(cp + ((size_t)oj * n_orb + oi) * 2) = (d2){cr, -ci};
 }

@@ -15,9 +15,15 @@
 // columns) and removes the transpose-add pass.  Diagonal elements get Im == 0 exactly, as in the
 // reference.
 //
+// Their Re columns are all that is contracted for diagonal elements: a dense model puts two of them in one slot
+// (TBK_SLOT_PAIR, tbk_internal.h), cos row (2 hr_ii | 2 hr_jj), sin row (-2 hi_ii | -2 hi_jj) -- the very values the
+// single-element slot holds in its Re plane, so each column's arithmetic is unchanged.  At N_orb = 64 that is 2048
+// slots (32 element tiles) instead of 2080 padded to 2112 (33 tiles).  k.p models keep one slot per element (the Im
+// of their diagonal is the caller's).
+//
 // Layout written here ("tile-interleaved", so one workgroup row segment is contiguous):
 //
-//     Bt[kk][e / 16][plane][e % 16]      plane 0 = Re column, 1 = Im column; f64
+//     Bt[kk][e / 16][plane][e % 16]      plane 0 = Re column, 1 = Im column (pair slot: Re of H[j][j]); f64
 //
 // Padding rows (r >= n_r) and padding elements (e >= ncol) are zero.
 
@@ -33,13 +39,22 @@ stage_dense_kernel(const double* __restrict__ hop, const int32_t* __restrict__ c
     if (e >= ncol_pad || r >= n_r) return;
     const int32_t ij = colmap[e];
     if (ij < 0) return;
-    const int i = ij >> 16, j = ij & 0xffff;
+    const int i = ij >> 16, j = ij & 0x7fff;
     const double* blk = hop + (size_t)r * n_orb * n_orb * 2;
-    const double hr = blk[((size_t)i * n_orb + j) * 2], hi = blk[((size_t)i * n_orb + j) * 2 + 1];
-    const double gr = blk[((size_t)j * n_orb + i) * 2], gi = blk[((size_t)j * n_orb + i) * 2 + 1];
     const size_t tiles = ncol_pad / TBK_CT;
     const size_t base0 = (((size_t)(2 * r) * tiles + e / TBK_CT) * 2) * TBK_CT + e % TBK_CT;
     const size_t base1 = (((size_t)(2 * r + 1) * tiles + e / TBK_CT) * 2) * TBK_CT + e % TBK_CT;
+    if (ij & TBK_SLOT_PAIR) {  // H[i][i] in plane 0, H[j][j] in plane 1
+        const double hr = blk[((size_t)i * n_orb + i) * 2], hi = blk[((size_t)i * n_orb + i) * 2 + 1];
+        const double gr = blk[((size_t)j * n_orb + j) * 2], gi = blk[((size_t)j * n_orb + j) * 2 + 1];
+        Bt[base0] = hr + hr;
+        Bt[base0 + TBK_CT] = gr + gr;
+        Bt[base1] = -(hi + hi);
+        Bt[base1 + TBK_CT] = -(gi + gi);
+        return;
+    }
+    const double hr = blk[((size_t)i * n_orb + j) * 2], hi = blk[((size_t)i * n_orb + j) * 2 + 1];
+    const double gr = blk[((size_t)j * n_orb + i) * 2], gi = blk[((size_t)j * n_orb + i) * 2 + 1];
     Bt[base0] = hr + gr;              // cos row, Re column
     Bt[base0 + TBK_CT] = hi - gi;     // cos row, Im column
     Bt[base1] = -(hi + gi);           // sin row, Re column
