@@ -159,11 +159,14 @@ static int create_common(int device, int dim, int n_orb, int64_t n_r, const int3
     m->dim = dim;
     m->n_orb = n_orb;
     m->n_r = n_r;
-    // K rows are padded to whole LDS stages (TBK_BK); padding rows carry zero hoppings
-    m->k2 = round_up(n_r * k_rows_per_r, TBK_BK);
+    // K rows are padded to whole LDS stages (TBK_BK); padding rows carry zero hoppings.  Dense tight-binding models large enough
+    // for the Strassen path (tbk_internal.h) pad to whole stages in each HALF of K and to whole element tiles in each half of
+    // the slots (padding slots keep colmap -1)
+    const bool strassen = pair_diagonal && k_rows_per_r == 2 && tbk_strassen_model(false, false, n_r);
+    m->k2 = round_up(n_r * k_rows_per_r, strassen ? 2 * TBK_BK : TBK_BK);
     m->n_r_pad = m->k2 / k_rows_per_r;
     m->ncol = (int)(pair_diagonal ? (int64_t)n_orb * (n_orb - 1) / 2 + (n_orb + 1) / 2 : (int64_t)n_orb * (n_orb + 1) / 2);
-    m->ncol_pad = (int)round_up(m->ncol, TBK_BNP);
+    m->ncol_pad = (int)round_up(m->ncol, strassen ? 2 * TBK_BNP : TBK_BNP);
 
     int rc = TBK_OK;
     auto fail = [&](int code) {
@@ -257,6 +260,7 @@ extern "C" int tbk_model_create_dense(int device, int dim, int n_orb, int64_t n_
             TBK_HIP(hipMemcpyAsync(d_raw, hop, raw_bytes, hipMemcpyHostToDevice, m->stream));
         }
         TBK_CHECK(tbk_stage_dense(m, d_raw));
+        TBK_CHECK(tbk_stage_strassen(m));
         TBK_HIP(hipStreamSynchronize(m->stream));
         return TBK_OK;
     }();
@@ -378,7 +382,7 @@ extern "C" void tbk_model_destroy(tbk_model* m) {
     if (m->h_stage) (void)hipHostFree(m->h_stage);
     for (hipStream_t st : streams)
         if (st) (void)hipStreamDestroy(st);
-    void* ptrs[] = {m->d_R, m->d_colmap, m->d_B, m->d_cptr, m->d_rec_r, m->d_rec_v, m->d_powers, m->d_sptr, m->d_srec_r, m->d_srec_v};
+    void* ptrs[] = {m->d_R, m->d_colmap, m->d_B, m->d_Bs, m->d_cptr, m->d_rec_r, m->d_rec_v, m->d_powers, m->d_sptr, m->d_srec_r, m->d_srec_v};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     DevBuf* bufs[] = {&m->ws_phase, &m->ws_H, &m->ws_E,   &m->ws_E2,
@@ -405,6 +409,9 @@ extern "C" int tbk_model_set_option(tbk_model* m, int option, int64_t value) {
             return TBK_OK;
         case TBK_OPT_FOLD:
             m->fold_enabled = value != 0;
+            return TBK_OK;
+        case TBK_OPT_STRASSEN:
+            m->strassen = value != 0;
             return TBK_OK;
         default:
             tbk_set_error("unknown option %d", option);
@@ -438,7 +445,7 @@ static int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
     // (what this handle's grow-only chunk workspaces hold already is as good as free: counted out, the second call of a model
     // chose a smaller chunk than the first -- cfg3: one chunk in the warm-up, two from then on)
     free_b += m->ws_H.bytes + m->ws_H2.bytes + m->ws_phase.bytes + m->ws_band.bytes + m->ws_bandmat[0].bytes + m->ws_bandmat[1].bytes +
-              m->ws_E.bytes + m->ws_xl.bytes;
+              m->ws_E.bytes + m->ws_xl.bytes + m->ws_part.bytes;
     // above 64 orbitals a chunk is a few thousand matrices: every kernel of the eigensolver ends on a partly filled
     // round of workgroups, and 2 - 3 times longer chunks were worth 3 - 4 % (cfg3 3846 -> 12500 matrices per chunk,
     // cfg5 1250 -> 5000)
@@ -458,6 +465,14 @@ static int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
     int64_t cap = mid ? 131072 : 32768;
     if (n < 64) cap *= std::min<int64_t>(32, (64 / n) * (64 / n));
     chunk = std::max<int64_t>(TBK_BM, std::min<int64_t>(chunk, cap));
+    if (tbk_hk_strassen(m, std::min(chunk, nk))) {
+        // a Strassen chunk also holds its phase rows 7/4 times (As[7][K2 / 2][Mh]) and the seven half-size products
+        // P[7][Mh][ncol_pad / 2] (re, im): that must fit the quarter of the free memory -- else a shorter chunk (classical
+        // below TBK_STRASSEN_MIN_NK k-points)
+        const int64_t per_k_s = per_k + m->k2 * 8 * 3 / 4 + (int64_t)m->ncol_pad * 16 * 7 / 4;
+        const int64_t fit = (int64_t)(free_b / 4) / per_k_s / TBK_BM * TBK_BM;
+        chunk = std::max<int64_t>(TBK_BM, std::min(chunk, fit));
+    }
     if (m->k_chunk > 0) chunk = round_up(m->k_chunk, TBK_BM);
     else if (chunk >= 4096) chunk = chunk / 4096 * 4096;  // 32 k tiles: equal shares for the 8 XCDs
     return std::min(chunk, round_up(nk, TBK_BM));
@@ -467,6 +482,7 @@ static int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
 static inline int64_t phase_ld(int64_t nk) { return round_up(nk, TBK_BM); }
 
 static int fill_rows(tbk_model* m, const double* d_k, int64_t nk, int64_t nk_pad, double* d_A) {
+    if (tbk_hk_strassen(m, nk)) return tbk_launch_phase_strassen(m, d_k, nk, d_A);  // the seven blocks of its left operands
     if (m->kdotp)
         return tbk_launch_monomials(m->stream, m->d_powers, m->dim, m->n_r, m->k2, d_k, nk, nk_pad, d_A);
     return tbk_launch_phase(m, d_k, nk, nk_pad, d_A);
@@ -494,7 +510,7 @@ extern "C" int tbk_hamilton_device(tbk_model* m, const double* d_k, int64_t nk, 
     for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
         const int64_t nkc = std::min(chunk, nk - c0);
         const int64_t nk_pad = phase_ld(nkc);
-        TBK_CHECK(m->ws_phase.reserve((size_t)std::max<int64_t>(m->k2, 1) * nk_pad * sizeof(double)));
+        TBK_CHECK(m->ws_phase.reserve((size_t)tbk_phase_doubles(m, nkc, nk_pad) * sizeof(double)));
         double* d_A = m->ws_phase.as<double>();
         const double* kc = d_k + c0 * m->dim;
         const bool own_rows = tbk_hk_inline_phases(m, nkc);  // a few k-points: the H(k) kernel makes its phase rows
@@ -606,7 +622,7 @@ static int eigenval_wave_pipeline(tbk_model* m, const double* d_k, int64_t nk, d
     const auto prepare_rows = [&](int64_t c0, int64_t nkc) -> int {
         if (tbk_hk_inline_phases(m, nkc)) return TBK_OK;
         const int64_t nk_pad = phase_ld(nkc);
-        TBK_CHECK(m->ws_phase.reserve((size_t)std::max<int64_t>(m->k2, 1) * nk_pad * sizeof(double)));
+        TBK_CHECK(m->ws_phase.reserve((size_t)tbk_phase_doubles(m, nkc, nk_pad) * sizeof(double)));
         TBK_CHECK(fill_rows(m, d_k + c0 * m->dim, nkc, nk_pad, m->ws_phase.as<double>()));
         rows_ready_for = c0;
         return TBK_OK;
@@ -761,7 +777,7 @@ static int eigenval_folded(tbk_model* m, const double* d_k, const double* h_k, i
     // [lo, hi) of one run, `m` folded for that run: phase rows + contraction of the (dim - 1)-dimensional model
     auto piece_plane = [&](int64_t lo, int64_t hi, double* d_Hp) -> int {
         const int64_t len = hi - lo, nk_pad = phase_ld(len);
-        TBK_CHECK(m->ws_phase.reserve((size_t)std::max<int64_t>(m->k2, 1) * nk_pad * sizeof(double)));
+        TBK_CHECK(m->ws_phase.reserve((size_t)tbk_phase_doubles(m, len, nk_pad) * sizeof(double)));
         TBK_CHECK(fill_rows(m, d_k2 + lo * (dim - 1), len, nk_pad, m->ws_phase.as<double>()));
         return build_h(m, m->ws_phase.as<double>(), len, nk_pad, HK_TRI, 2, d_k2 + lo * (dim - 1), nullptr, d_Hp);
     };
@@ -986,7 +1002,7 @@ static int eigenval_device_solve(tbk_model* m, const double* d_k, const double* 
     for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
         const int64_t nkc = std::min(chunk, nk - c0);
         const int64_t nk_pad = phase_ld(nkc);
-        TBK_CHECK(m->ws_phase.reserve((size_t)std::max<int64_t>(m->k2, 1) * nk_pad * sizeof(double)));
+        TBK_CHECK(m->ws_phase.reserve((size_t)tbk_phase_doubles(m, nkc, nk_pad) * sizeof(double)));
         TBK_CHECK(m->ws_H.reserve((size_t)nkc * nn2 * sizeof(double)));
         double* d_A = m->ws_phase.as<double>();
         double* d_H = m->ws_H.as<double>();

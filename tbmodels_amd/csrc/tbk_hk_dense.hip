@@ -72,6 +72,11 @@ struct HkArgs {
     int splits;
     int unit_grid;
     int64_t p_rows;  // k rows per split in P
+    // Strassen launches (launch_strassen below): split y is product p of the seven of one Strassen level instead of a K
+    // range -- its operands start at A + p * a_prod_stride and Bt + p * b_prod_stride, it walks the whole (half) K of the
+    // launch, and the epilogue parks every element of its tile, padding slots included, for hk_strassen_finish_kernel
+    int products;
+    int64_t a_prod_stride, b_prod_stride;
     // "lines" launches (second-level fold, tbk_fold.hip): k tile t is one mesh line -- its own operand at
     // Bt + t * b_tile_stride, the SAME phase rows for every line (a_tile_stride = 0), rows_per_tile k-points of output
     int64_t a_tile_stride;  // TBK_BM in ordinary launches
@@ -205,8 +210,13 @@ __global__ void __launch_bounds__(256, 2) hk_dense_kernel(const HkArgs a) {
 #pragma unroll
             for (int p = 0; p < 2; ++p) acc[i][j][p] = (d4){0.0, 0.0, 0.0, 0.0};
 
+    const double* opA = a.A;
+    const double* opB = a.Bt;
     int s_begin = 0, n_stage = (int)(a.k2 / TBK_BK);
-    if (SPLIT) {
+    if (SPLIT && a.products) {
+        opA += split_y * a.a_prod_stride;
+        opB += split_y * a.b_prod_stride;
+    } else if (SPLIT) {
         const int per = (n_stage + a.splits - 1) / a.splits;
         s_begin = min(split_y * per, n_stage);
         n_stage = min(s_begin + per, n_stage);
@@ -231,8 +241,8 @@ __global__ void __launch_bounds__(256, 2) hk_dense_kernel(const HkArgs a) {
     const uint32_t lane_bytes = (uint32_t)lane * 16u;
     const int64_t ldgA = a.nk_pad * (int64_t)sizeof(double);                   // bytes per K row
     const int64_t ldgB = (int64_t)a.ncol_pad * 2 * (int64_t)sizeof(double);
-    const char* rowA = reinterpret_cast<const char*>(a.A + (int64_t)mt_idx * a.a_tile_stride) + ((int64_t)s_begin * TBK_BK + wave) * ldgA;
-    const char* rowB = reinterpret_cast<const char*>(a.Bt + (int64_t)mt_idx * a.b_tile_stride + n0 * 2) + ((int64_t)s_begin * TBK_BK + wave) * ldgB;
+    const char* rowA = reinterpret_cast<const char*>(opA + (int64_t)mt_idx * a.a_tile_stride) + ((int64_t)s_begin * TBK_BK + wave) * ldgA;
+    const char* rowB = reinterpret_cast<const char*>(opB + (int64_t)mt_idx * a.b_tile_stride + n0 * 2) + ((int64_t)s_begin * TBK_BK + wave) * ldgB;
     auto issue_stage = [&](auto bufc) {  // the stage rowA / rowB point at -> buffer bufc; advances them by one stage
         constexpr int buf = decltype(bufc)::value;
         double* sA = smem + buf * STAGE_DOUBLES + wave * LDA;
@@ -332,7 +342,7 @@ __global__ void __launch_bounds__(256, 2) hk_dense_kernel(const HkArgs a) {
     for (int j = 0; j < 2; ++j) {
         const int e = (int)n0 + (wn * 2 + j) * 16 + l15;
         const int32_t ij = a.colmap[e];
-        if (ij < 0) continue;
+        if (ij < 0 && !(SPLIT && a.products)) continue;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -572,6 +582,36 @@ __global__ void __launch_bounds__(256) hk_finish_kernel(const HkArgs a) {
     store_slot<MODE, CONV>(a, kq, ij, re, im);
 }
 
+// Strassen combine: one thread per (k' < Mh, e' < ncol_pad / 2) of the half-size grid loads the seven products M1 .. M7 of
+// its element, P[p][k'][e'] (re, im), and finishes the four quadrants in the order of DESIGN.md section 3:
+//     C11 = M1 + M4 - M5 + M7 -> (k', e')            C12 = M3 + M5 -> (k', e' + ncol_pad / 2)
+//     C21 = M2 + M4 -> (k' + Mh, e')                 C22 = M1 - M2 + M3 + M6 -> (k' + Mh, e' + ncol_pad / 2)
+// Padding k-points (>= nk) and padding slots (colmap < 0) are not stored.  `a` is the caller's (nk, ncol_pad of the model).
+template <int MODE, int CONV>
+__global__ void __launch_bounds__(256) hk_strassen_finish_kernel(const HkArgs a, int64_t mh) {
+    const int half = a.ncol_pad / 2;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int e = (int)(idx % half);
+    const int64_t kq = idx / half;
+    if (kq >= mh) return;
+    const size_t blk = (size_t)mh * half;
+    const d2* mp = reinterpret_cast<const d2*>(a.P) + (size_t)kq * half + e;
+    const d2 m1 = mp[0], m2 = mp[blk], m3 = mp[2 * blk], m4 = mp[3 * blk], m5 = mp[4 * blk], m6 = mp[5 * blk], m7 = mp[6 * blk];
+    const d2 c11 = ((m1 + m4) - m5) + m7;
+    const d2 c12 = m3 + m5;
+    const d2 c21 = m2 + m4;
+    const d2 c22 = ((m1 - m2) + m3) + m6;
+    const int32_t ij0 = a.colmap[e], ij1 = a.colmap[e + half];
+    if (kq < a.nk) {
+        if (ij0 >= 0) store_slot<MODE, CONV>(a, kq, ij0, c11[0], c11[1]);
+        if (ij1 >= 0) store_slot<MODE, CONV>(a, kq, ij1, c12[0], c12[1]);
+    }
+    if (kq + mh < a.nk) {
+        if (ij0 >= 0) store_slot<MODE, CONV>(a, kq + mh, ij0, c21[0], c21[1]);
+        if (ij1 >= 0) store_slot<MODE, CONV>(a, kq + mh, ij1, c22[0], c22[1]);
+    }
+}
+
 // The same for many splits and few k-points (the matrix-vector path: ~100 K slices, one k-point): 16 threads per
 // element, thread j adds splits j, j + 16, ... and the 16 partial sums are combined in a fixed tree -- the one-thread
 // loop was a chain of ~100 dependent loads, 31 us of a 117 us single-k hamilton() call.
@@ -754,6 +794,53 @@ int launch(tbk_model* m, const HkArgs& a0, int grid) {
     return TBK_OK;
 }
 
+// One Strassen level: the seven half-size products as the units of ONE launch -- unit u = product
+// u / grid, block u % grid of the XCD-aware walk over the Mh x ncol_pad / 2 grid -- each parking its tiles in P[p], then the
+// combine.  The operands were made by phase_rows_strassen_kernel (a.A = As[7][K2 / 2][Mh]) and stage_strassen_kernel
+// (m->d_Bs); the K loop is the classical one over K2 / 2 rows.  Products do not depend on MODE / CONV: one instantiation.
+template <int MODE, int CONV>
+int launch_strassen(tbk_model* m, const HkArgs& a0) {
+    hipStream_t s = m->stream;
+    const size_t lds = 2 * STAGE_DOUBLES * sizeof(double);
+    static std::atomic<bool> raised[TBK_MAX_DEVICES] = {};
+    TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&hk_dense_kernel<HK_TRI, 2, true>), 160 * 1024, raised));
+    const int64_t mh = tbk_strassen_mh(a0.nk);
+    const int half = a0.ncol_pad / 2;
+    HkArgs a = a0;
+    a.Bt = m->d_Bs;
+    a.k2 = m->k2 / 2;
+    a.nk = mh;
+    a.nk_pad = mh;
+    a.ncol_pad = half;
+    a.mt_count = (int)(mh / TBK_BM);
+    a.nt_count = half / TBK_BNP;
+    int grid;
+    if (a.mt_count >= 32) {
+        a.xcd_rows = 4;
+        grid = ((a.mt_count + 7) / 8) * a.nt_count * 8;
+    } else {
+        a.xcd_rows = 0;
+        grid = a.mt_count * a.nt_count;
+    }
+    a.products = 1;
+    a.splits = 7;
+    a.unit_grid = grid;
+    a.p_rows = mh;
+    a.a_prod_stride = a.k2 * mh;
+    a.b_prod_stride = a.k2 * half * 2;
+    TBK_CHECK(m->ws_part.reserve((size_t)7 * mh * half * 2 * sizeof(double)));
+    a.P = m->ws_part.as<double>();
+    hipLaunchKernelGGL((hk_dense_kernel<HK_TRI, 2, true>), dim3(7 * grid), dim3(256), lds, s, a);
+    TBK_HIP(hipGetLastError());
+    HkArgs f = a0;
+    f.P = a.P;
+    const int64_t threads = mh * half;
+    hipLaunchKernelGGL((hk_strassen_finish_kernel<MODE, CONV>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, f, mh);
+    TBK_HIP(hipGetLastError());
+    m->counters[TBK_CNT_STRASSEN_LAUNCHES] += 1;
+    return TBK_OK;
+}
+
 // K slices of the matrix-vector path: (blocks of 64 packed elements) x (K slices) independent waves, four to a workgroup.
 // The kernel is bound by the bytes a CU pulls, so the workgroups must come out EVEN over the CUs: an operand of up to ~1.5 MB
 // per workgroup slot goes in ONE round of at most two workgroups per CU (`*lds_out` = half a CU's LDS keeps a third one away);
@@ -798,6 +885,22 @@ void gemv_plan(const tbk_model* m, int64_t nk, int* slices_out, size_t* lds_out)
 }
 
 }  // namespace
+
+// The Strassen path (launch_strassen): a dense tight-binding model padded and staged for it, with its own operand (not a
+// folded one), TBK_OPT_STRASSEN on, and a chunk of at least TBK_STRASSEN_MIN_NK k-points that takes neither the matrix-vector
+// path nor split-K.  Whether a chunk takes it is a function of (model, nk) only, so the phase rows made for a chunk
+// (tbk_api.hip fill_rows) and its contraction agree.
+bool tbk_hk_strassen(const tbk_model* m, int64_t nk) {
+    if (!m->strassen || m->d_Bs == nullptr || m->d_B != m->bs_src || m->sparse || m->kdotp) return false;
+    if (m->n_r_pad < TBK_STRASSEN_MIN_NR || nk < TBK_STRASSEN_MIN_NK || tbk_hk_gemv_path(m, nk)) return false;
+    const int64_t tiles = (nk + TBK_BM - 1) / TBK_BM * (m->ncol_pad / TBK_BNP);
+    return tiles >= 2 * m->n_cu;  // (fewer: the split-K launches below)
+}
+
+int64_t tbk_phase_doubles(const tbk_model* m, int64_t nk, int64_t nk_pad) {
+    if (tbk_hk_strassen(m, nk)) return 7 * (m->k2 / 2) * tbk_strassen_mh(nk);
+    return std::max<int64_t>(m->k2, 1) * nk_pad;
+}
 
 // True when tbk_launch_hk_dense will take the matrix-vector path AND can make its phase rows itself: the caller then
 // skips tbk_launch_phase and passes d_A = nullptr.
@@ -851,6 +954,8 @@ int tbk_launch_hk_dense(tbk_model* m, const double* d_A, int64_t nk, int64_t nk_
     a.P = nullptr;
     a.splits = 1;
     a.p_rows = 0;
+    a.products = 0;
+    a.a_prod_stride = a.b_prod_stride = 0;
     a.a_tile_stride = TBK_BM;
     a.b_tile_stride = 0;
     a.rows_per_tile = TBK_BM;
@@ -900,6 +1005,17 @@ int tbk_launch_hk_dense(tbk_model* m, const double* d_A, int64_t nk, int64_t nk_
             TBK_HIP((launch_gemv<HK_FULL, 1>(m, a, lds, m->stream)));
         } else {
             TBK_HIP((launch_gemv<HK_FULL, 2>(m, a, lds, m->stream)));
+        }
+        return TBK_OK;
+    }
+    if (d_A != nullptr && tbk_hk_strassen(m, nk)) {
+        StageTimer t(m, TBK_T_HK);
+        if (mode == HK_TRI) {
+            TBK_CHECK((launch_strassen<HK_TRI, 2>(m, a)));
+        } else if (convention == 1) {
+            TBK_CHECK((launch_strassen<HK_FULL, 1>(m, a)));
+        } else {
+            TBK_CHECK((launch_strassen<HK_FULL, 2>(m, a)));
         }
         return TBK_OK;
     }
@@ -961,6 +1077,8 @@ int tbk_launch_hk_dense_lines(tbk_model* m, const double* d_A, int64_t n_lines, 
     a.P = nullptr;
     a.splits = 1;
     a.p_rows = 0;
+    a.products = 0;
+    a.a_prod_stride = a.b_prod_stride = 0;
     a.a_tile_stride = 0;
     a.b_tile_stride = b_stride;
     a.rows_per_tile = line_len;

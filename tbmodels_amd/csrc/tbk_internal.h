@@ -170,6 +170,10 @@ struct tbk_model {
 
     // --- dense: symmetrised hop planes, tile-interleaved  Bt[K2][ncol_pad / 16][2][16] ---
     double* d_B = nullptr;
+    // --- dense, n_r_pad >= TBK_STRASSEN_MIN_NR: the seven right operands of one Strassen level, Bs[7][K2 / 2][ncol_pad / 2 / 16][2][16]
+    // (tbk_stage.hip), built from the staged d_B; bs_src is that d_B (a folded operand swapped in by tbk_fold_enter has none)
+    double* d_Bs = nullptr;
+    const double* bs_src = nullptr;
 
     // --- sparse: per packed element, the list of lattice vectors that touch it ---
     int64_t nnz_rec = 0;
@@ -191,7 +195,8 @@ struct tbk_model {
     std::vector<int32_t> h_R;  // host copy of the lattice vectors [n_r][dim]
     tbk_fold_plan_t fold[TBK_MAX_DIM];
     bool fold_enabled = true;
-    int64_t counters[TBK_CNT_COUNT] = {0, 0, 0, 0};  // tbk_model_counter
+    bool strassen = true;  // TBK_OPT_STRASSEN
+    int64_t counters[TBK_CNT_COUNT] = {0, 0, 0, 0, 0};  // tbk_model_counter
 
     // --- options ---
     int eigensolver = TBK_EIG_AUTO;
@@ -271,7 +276,19 @@ struct StageTimer {
 // ------------------------------------------------------------------------------------------------
 enum HkMode { HK_TRI = 0, HK_FULL = 1 };
 
+// One Strassen level in the dense H(k) contraction (tbk_hk_dense.hip).  Models with at least
+// TBK_STRASSEN_MIN_NR padded lattice vectors are padded for it (n_r_pad a multiple of 16, ncol_pad of 128) and get the
+// operand blocks d_Bs; k chunks of at least TBK_STRASSEN_MIN_NK k-points on the direct MFMA path then take it.
+constexpr int64_t TBK_STRASSEN_MIN_NR = 1024;
+constexpr int64_t TBK_STRASSEN_MIN_NK = 8192;
+inline bool tbk_strassen_model(bool sparse, bool kdotp, int64_t n_r) { return !sparse && !kdotp && n_r >= TBK_STRASSEN_MIN_NR; }
+bool tbk_hk_strassen(const tbk_model* m, int64_t nk);  // tbk_hk_dense.hip: this chunk of nk k-points takes the Strassen path
+inline int64_t tbk_strassen_mh(int64_t nk) { return (((nk + 1) / 2) + TBK_BM - 1) / TBK_BM * TBK_BM; }  // k rows per half
+// doubles of the phase rows of a chunk of nk k-points (padded to nk_pad): the seven blocks As[7][K2 / 2][Mh], or A[K2][nk_pad]
+int64_t tbk_phase_doubles(const tbk_model* m, int64_t nk, int64_t nk_pad);
+
 // tbk_phase.hip
+int tbk_launch_phase_strassen(tbk_model* m, const double* d_k, int64_t nk, double* d_As);
 int tbk_launch_phase(tbk_model* m, const double* d_k, int64_t nk, int64_t nk_pad, double* d_A);
 int tbk_launch_orbital_phases(tbk_model* m, const double* d_k, const double* d_pos, int64_t nk, double* d_orb);
 int tbk_launch_monomials(hipStream_t s, const int32_t* d_powers, int dim, int64_t n_p,
@@ -281,6 +298,7 @@ int tbk_launch_monomials(hipStream_t s, const int32_t* d_powers, int dim, int64_
 // tbk_stage.hip
 int tbk_stage_dense(tbk_model* m, const double* d_hop_raw);
 int tbk_stage_kdotp(tbk_model* m, const double* d_coeff_raw);
+int tbk_stage_strassen(tbk_model* m);
 
 // tbk_hk_dense.hip
 int tbk_launch_hk_dense(tbk_model* m, const double* d_A, int64_t nk, int64_t nk_pad, int mode,

@@ -36,6 +36,47 @@ phase_rows_kernel(const double* __restrict__ k, const int32_t* __restrict__ R, i
     A[(2 * r + 1) * nk_pad + kidx] = s;
 }
 
+// The left operands of one Strassen level (tbk_hk_dense.hip).  P = A^T split into halves: k-points
+// [0, Mh) | [Mh, 2 Mh), lattice vectors [0, n_r_pad / 2) | the rest; P_ab is k-half a x K-half b.  One thread per
+// (k' < Mh, r' < n_r_pad / 2) forms the four quadrant phases with the arithmetic of phase_rows_kernel (k-points past nk and
+// padding lattice vectors get cos = sin = 0) and writes the seven blocks As[7][K2 / 2][Mh], k contiguous:
+//
+//     As[0] = P11 + P22   As[1] = P21 + P22   As[2] = P11   As[3] = P22   As[4] = P11 + P12   As[5] = P21 - P11   As[6] = P12 - P22
+__global__ void __launch_bounds__(256)
+phase_rows_strassen_kernel(const double* __restrict__ k, const int32_t* __restrict__ R, int dim, int64_t nk, int64_t mh,
+                           int64_t n_r, int64_t rh, double* __restrict__ As) {
+    const int64_t kq = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t r = blockIdx.y;
+    if (kq >= mh) return;
+    double c[2][2], s[2][2];  // [k half][K half]
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int64_t kidx = kq + a * mh, rr = r + b * rh;
+            c[a][b] = 0.0;
+            s[a][b] = 0.0;
+            if (kidx < nk && rr < n_r) {
+                double dot = 0.0;
+                for (int d = 0; d < dim; ++d) dot = fma(k[kidx * dim + d], (double)R[rr * dim + d], dot);
+                sincospi(2.0 * dot, &s[a][b], &c[a][b]);
+            }
+        }
+    const size_t blk = (size_t)2 * rh * mh;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {  // cos row 2r', sin row 2r' + 1
+        const double(&v)[2][2] = t == 0 ? c : s;
+        double* row = As + (size_t)(2 * r + t) * mh + kq;
+        row[0 * blk] = v[0][0] + v[1][1];
+        row[1 * blk] = v[1][0] + v[1][1];
+        row[2 * blk] = v[0][0];
+        row[3 * blk] = v[1][1];
+        row[4 * blk] = v[0][0] + v[0][1];
+        row[5 * blk] = v[1][0] - v[0][0];
+        row[6 * blk] = v[0][1] - v[1][1];
+    }
+}
+
 // k.p monomials (kdotp.py:71-78): A[p][k] = prod_d k_d^powers[p][d]
 __global__ void __launch_bounds__(256)
 monomial_rows_kernel(const double* __restrict__ k, const int32_t* __restrict__ powers, int dim,
@@ -91,6 +132,15 @@ int tbk_launch_phase(tbk_model* m, const double* d_k, int64_t nk, int64_t nk_pad
     dim3 grid((unsigned)((nk_pad + 255) / 256), (unsigned)m->n_r_pad);
     hipLaunchKernelGGL(phase_rows_kernel, grid, dim3(256), 0, m->stream, d_k, m->d_R, m->dim, nk,
                        nk_pad, m->n_r, d_A);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+int tbk_launch_phase_strassen(tbk_model* m, const double* d_k, int64_t nk, double* d_As) {
+    const int64_t mh = tbk_strassen_mh(nk), rh = m->n_r_pad / 2;
+    StageTimer t(m, TBK_T_PHASE);
+    dim3 grid((unsigned)((mh + 255) / 256), (unsigned)rh);
+    hipLaunchKernelGGL(phase_rows_strassen_kernel, grid, dim3(256), 0, m->stream, d_k, m->d_R, m->dim, nk, mh, m->n_r, rh, d_As);
     TBK_HIP(hipGetLastError());
     return TBK_OK;
 }

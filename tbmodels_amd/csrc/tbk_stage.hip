@@ -78,7 +78,50 @@ stage_kdotp_kernel(const double* __restrict__ coeff, const int32_t* __restrict__
     Bt[base + TBK_CT] = blk[((size_t)i * n_orb + j) * 2 + 1];
 }
 
+// One Strassen level (tbk_hk_dense.hip): the right operand of product p is a sum of the quadrants
+// B_bc = Bt[b-th half of K][c-th half of the slots] -- in the tile-interleaved layout a slot half is one contiguous half of
+// every K row, so each block is an ordinary operand of ncol_pad / 2 slots:
+//
+//     Bs[0] = B11 + B22   Bs[1] = B11   Bs[2] = B12 - B22   Bs[3] = B21 - B11   Bs[4] = B22   Bs[5] = B11 + B12   Bs[6] = B21 + B22
+//
+// One thread per (K row of the half, double of the half row).
+__global__ void __launch_bounds__(256)
+stage_strassen_kernel(const double* __restrict__ Bt, int64_t kh, int ncol_pad, double* __restrict__ Bs) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;  // < ncol_pad: a half row holds ncol_pad / 2 slots x 2 planes
+    const int64_t kk = blockIdx.y;
+    if (j >= ncol_pad) return;
+    const size_t row = (size_t)2 * ncol_pad;
+    const double b11 = Bt[kk * row + j], b12 = Bt[kk * row + ncol_pad + j];
+    const double b21 = Bt[(kk + kh) * row + j], b22 = Bt[(kk + kh) * row + ncol_pad + j];
+    const size_t blk = (size_t)kh * ncol_pad, o = kk * (size_t)ncol_pad + j;
+    Bs[0 * blk + o] = b11 + b22;
+    Bs[1 * blk + o] = b11;
+    Bs[2 * blk + o] = b12 - b22;
+    Bs[3 * blk + o] = b21 - b11;
+    Bs[4 * blk + o] = b22;
+    Bs[5 * blk + o] = b11 + b12;
+    Bs[6 * blk + o] = b21 + b22;
+}
+
 }  // namespace
+
+// The Strassen operand blocks of a dense model padded for them (tbk_api.hip create_common).  7/4 of Bt; a model whose blocks
+// would take more than a quarter of the free HBM keeps the classical path only (d_Bs stays NULL).
+int tbk_stage_strassen(tbk_model* m) {
+    if (!tbk_strassen_model(m->sparse, m->kdotp, m->n_r) || m->d_B == nullptr) return TBK_OK;
+    const int64_t kh = m->k2 / 2;
+    if (kh % TBK_BK != 0 || m->ncol_pad % (2 * TBK_BNP) != 0 || kh > 65535) return TBK_OK;
+    const size_t bytes = (size_t)7 * kh * m->ncol_pad * sizeof(double);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4) return TBK_OK;
+    TBK_HIP(hipMalloc((void**)&m->d_Bs, bytes));
+    m->staged_bytes += (int64_t)bytes;
+    m->bs_src = m->d_B;
+    dim3 grid((m->ncol_pad + 255) / 256, (unsigned)kh);
+    hipLaunchKernelGGL(stage_strassen_kernel, grid, dim3(256), 0, m->stream, m->d_B, kh, m->ncol_pad, m->d_Bs);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
 
 int tbk_stage_dense(tbk_model* m, const double* d_hop_raw) {
     const size_t bytes = (size_t)m->k2 * m->ncol_pad * 2 * sizeof(double);
