@@ -78,7 +78,7 @@ enum {
     TBK_OPT_FOLD = 4,        /* 0: never fold k lists with long runs of one shared component (grids) into
                               *    lower-dimensional models (default 1; dense models, eigenval only)          */
     TBK_OPT_STRASSEN = 5     /* 0: dense H(k) of long k chunks as the classical product instead of one Strassen
-                              *    level (default 1; csrc/tbk_hk_dense.hip tbk_hk_strassen)                    */
+                              *    level (default 1; csrc/tbk_hk_dense.hip tbk_hk_plan)                        */
 };
 
 /* ---- library / device ------------------------------------------------------------------ */

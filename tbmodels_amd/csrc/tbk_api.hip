@@ -465,7 +465,7 @@ static int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
     int64_t cap = mid ? 131072 : 32768;
     if (n < 64) cap *= std::min<int64_t>(32, (64 / n) * (64 / n));
     chunk = std::max<int64_t>(TBK_BM, std::min<int64_t>(chunk, cap));
-    if (tbk_hk_strassen(m, std::min(chunk, nk))) {
+    if (tbk_hk_plan(m, std::min(chunk, nk), false).path == HK_PATH_STRASSEN) {
         // a Strassen chunk also holds its phase rows 7/4 times (As[7][K2 / 2][Mh]) and the seven half-size products
         // P[7][Mh][ncol_pad / 2] (re, im): that must fit the quarter of the free memory -- else a shorter chunk (classical
         // below TBK_STRASSEN_MIN_NK k-points)
@@ -478,21 +478,24 @@ static int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
     return std::min(chunk, round_up(nk, TBK_BM));
 }
 
-// leading dimension (in k-points) of the phase-row matrix A[K][ld]: whole k tiles
-static inline int64_t phase_ld(int64_t nk) { return round_up(nk, TBK_BM); }
-
-static int fill_rows(tbk_model* m, const double* d_k, int64_t nk, int64_t nk_pad, double* d_A) {
-    if (tbk_hk_strassen(m, nk)) return tbk_launch_phase_strassen(m, d_k, nk, d_A);  // the seven blocks of its left operands
-    if (m->kdotp)
-        return tbk_launch_monomials(m->stream, m->d_powers, m->dim, m->n_r, m->k2, d_k, nk, nk_pad, d_A);
-    return tbk_launch_phase(m, d_k, nk, nk_pad, d_A);
+// The phase rows of a chunk of plan.nk k-points for its plan, in ws_phase (reserved also when the H(k) kernel makes them).
+static int fill_rows(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_k) {
+    TBK_CHECK(m->ws_phase.reserve((size_t)plan.row_doubles * sizeof(double)));
+    double* d_A = m->ws_phase.as<double>();
+    if (plan.rows == HK_ROWS_NONE) return TBK_OK;
+    if (plan.rows == HK_ROWS_STRASSEN) return tbk_launch_phase_strassen(m, d_k, plan.nk, d_A);  // the seven blocks of its left operands
+    if (plan.rows == HK_ROWS_MONOMIAL)
+        return tbk_launch_monomials(m->stream, m->d_powers, m->dim, m->n_r, m->k2, d_k, plan.nk, plan.nk_pad, d_A);
+    return tbk_launch_phase(m, d_k, plan.nk, plan.nk_pad, d_A);
 }
 
-static int build_h(tbk_model* m, const double* d_A, int64_t nk, int64_t nk_pad, int mode,
-                   int convention, const double* d_k, const double* d_pos, double* d_H) {
-    if (m->sparse)
-        return tbk_launch_hk_csr(m, d_A, nk, nk_pad, mode, convention, d_k, d_pos, d_H);
-    return tbk_launch_hk_dense(m, d_A, nk, nk_pad, mode, convention, d_k, d_pos, d_H);
+// H(k) of the chunk whose rows fill_rows made for the same plan
+static int build_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, const double* d_k, const double* d_pos,
+                   double* d_H) {
+    const double* d_A = plan.rows == HK_ROWS_NONE ? nullptr : m->ws_phase.as<double>();
+    if (plan.path == HK_PATH_CSR)
+        return tbk_launch_hk_csr(m, d_A, plan.nk, plan.nk_pad, mode, convention, d_k, d_pos, d_H);
+    return tbk_launch_hk_dense(m, plan, d_A, mode, convention, d_k, d_pos, d_H);
 }
 
 extern "C" int tbk_hamilton_device(tbk_model* m, const double* d_k, int64_t nk, int convention,
@@ -509,22 +512,19 @@ extern "C" int tbk_hamilton_device(tbk_model* m, const double* d_k, int64_t nk, 
     const size_t nn2 = (size_t)m->n_orb * m->n_orb * 2;
     for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
         const int64_t nkc = std::min(chunk, nk - c0);
-        const int64_t nk_pad = phase_ld(nkc);
-        TBK_CHECK(m->ws_phase.reserve((size_t)tbk_phase_doubles(m, nkc, nk_pad) * sizeof(double)));
-        double* d_A = m->ws_phase.as<double>();
+        const tbk_hk_plan_t plan = tbk_hk_plan(m, nkc, false);
         const double* kc = d_k + c0 * m->dim;
-        const bool own_rows = tbk_hk_inline_phases(m, nkc);  // a few k-points: the H(k) kernel makes its phase rows
-        if (!own_rows) TBK_CHECK(fill_rows(m, kc, nkc, nk_pad, d_A));
+        TBK_CHECK(fill_rows(m, plan, kc));
         const double* d_orb = nullptr;
         // (one-k host call on the matrix-vector path: the H(k) kernel forms the phases of its one k-point itself from the
         // raw positions -- no orbital_phase_kernel launch)
-        const bool inline_orb = m->h_k_inline != nullptr && m->d_pos_inline != nullptr && nk == 1 && own_rows;
+        const bool inline_orb = m->h_k_inline != nullptr && m->d_pos_inline != nullptr && nk == 1 && plan.rows == HK_ROWS_NONE;
         if (convention == 1 && !inline_orb) {
             TBK_CHECK(m->ws_orb.reserve((size_t)nkc * m->n_orb * 2 * sizeof(double)));
             TBK_CHECK(tbk_launch_orbital_phases(m, kc, d_pos, nkc, m->ws_orb.as<double>()));
             d_orb = m->ws_orb.as<double>();
         }
-        TBK_CHECK(build_h(m, own_rows ? nullptr : d_A, nkc, nk_pad, HK_FULL, convention, kc, d_orb, d_H + (size_t)c0 * nn2));
+        TBK_CHECK(build_h(m, plan, HK_FULL, convention, kc, d_orb, d_H + (size_t)c0 * nn2));
     }
     return TBK_OK;
 }
@@ -618,21 +618,17 @@ static int eigenval_wave_pipeline(tbk_model* m, const double* d_k, int64_t nk, d
     // row buffer (stream order), not the eigensolver to be done with H -- so they are enqueued BEFORE the main stream
     // waits for the previous chunk's reduction and run under it (an HBM-write kernel beside a VALU-bound one: 1.5 ms
     // per 100 k k-points at the headline shape).
-    int64_t rows_ready_for = -1;  // c0 of the chunk whose phase rows are in ws_phase
+    int64_t rows_ready_for = -1;  // c0 of the chunk whose phase rows are in ws_phase, made for rows_plan
+    tbk_hk_plan_t rows_plan;
     const auto prepare_rows = [&](int64_t c0, int64_t nkc) -> int {
-        if (tbk_hk_inline_phases(m, nkc)) return TBK_OK;
-        const int64_t nk_pad = phase_ld(nkc);
-        TBK_CHECK(m->ws_phase.reserve((size_t)tbk_phase_doubles(m, nkc, nk_pad) * sizeof(double)));
-        TBK_CHECK(fill_rows(m, d_k + c0 * m->dim, nkc, nk_pad, m->ws_phase.as<double>()));
+        rows_plan = tbk_hk_plan(m, nkc, false);
+        if (rows_plan.rows != HK_ROWS_NONE) TBK_CHECK(fill_rows(m, rows_plan, d_k + c0 * m->dim));
         rows_ready_for = c0;
         return TBK_OK;
     };
     const HBuilder direct = [&](int64_t c0, int64_t nkc, double* d_H) -> int {
-        const int64_t nk_pad = phase_ld(nkc);
-        const double* kc = d_k + c0 * m->dim;
-        if (tbk_hk_inline_phases(m, nkc)) return build_h(m, nullptr, nkc, nk_pad, HK_TRI, 2, kc, nullptr, d_H);
         if (rows_ready_for != c0) TBK_CHECK(prepare_rows(c0, nkc));
-        return build_h(m, m->ws_phase.as<double>(), nkc, nk_pad, HK_TRI, 2, kc, nullptr, d_H);
+        return build_h(m, rows_plan, HK_TRI, 2, d_k + c0 * m->dim, nullptr, d_H);
     };
     const HBuilder& build = builder ? *builder : direct;
     const int64_t chunk = choose_chunk(m, nk, true);
@@ -776,10 +772,9 @@ static int eigenval_folded(tbk_model* m, const double* d_k, const double* h_k, i
 
     // [lo, hi) of one run, `m` folded for that run: phase rows + contraction of the (dim - 1)-dimensional model
     auto piece_plane = [&](int64_t lo, int64_t hi, double* d_Hp) -> int {
-        const int64_t len = hi - lo, nk_pad = phase_ld(len);
-        TBK_CHECK(m->ws_phase.reserve((size_t)tbk_phase_doubles(m, len, nk_pad) * sizeof(double)));
-        TBK_CHECK(fill_rows(m, d_k2 + lo * (dim - 1), len, nk_pad, m->ws_phase.as<double>()));
-        return build_h(m, m->ws_phase.as<double>(), len, nk_pad, HK_TRI, 2, d_k2 + lo * (dim - 1), nullptr, d_Hp);
+        const tbk_hk_plan_t plan = tbk_hk_plan(m, hi - lo, true);
+        TBK_CHECK(fill_rows(m, plan, d_k2 + lo * (dim - 1)));
+        return build_h(m, plan, HK_TRI, 2, d_k2 + lo * (dim - 1), nullptr, d_Hp);
     };
 
     // Second level (meshes): inside a plane the k-points come in LINES -- equal-length sub-runs of one more shared
@@ -848,8 +843,7 @@ static int eigenval_folded(tbk_model* m, const double* d_k, const double* h_k, i
         TBK_CHECK(tbk_fold_enter(m, plan2, 0, saved2));
         int rc = m->ws_kline.reserve((size_t)li.L * std::max(dim1 - 1, 1) * sizeof(double));
         if (rc == TBK_OK) rc = tbk_fold_drop_component(m, d_k2 + a0 * dim1, dim1, li.e2, li.L, m->ws_kline.as<double>());
-        if (rc == TBK_OK) rc = m->ws_phase.reserve((size_t)std::max<int64_t>(m->k2, 1) * TBK_BM * sizeof(double));
-        if (rc == TBK_OK) rc = fill_rows(m, m->ws_kline.as<double>(), li.L, TBK_BM, m->ws_phase.as<double>());
+        if (rc == TBK_OK) rc = fill_rows(m, tbk_hk_plan(m, li.L, true), m->ws_kline.as<double>());  // (one k tile of rows)
         if (rc == TBK_OK)
             rc = tbk_launch_hk_dense_lines(m, m->ws_phase.as<double>(), n, (int)li.L, plan2.k2 * row_len, d_Hp);
         tbk_fold_leave(m, saved2);
@@ -1001,14 +995,12 @@ static int eigenval_device_solve(tbk_model* m, const double* d_k, const double* 
     m->counters[TBK_CNT_LIBRARY_CALLS] += 1;
     for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
         const int64_t nkc = std::min(chunk, nk - c0);
-        const int64_t nk_pad = phase_ld(nkc);
-        TBK_CHECK(m->ws_phase.reserve((size_t)tbk_phase_doubles(m, nkc, nk_pad) * sizeof(double)));
-        TBK_CHECK(m->ws_H.reserve((size_t)nkc * nn2 * sizeof(double)));
-        double* d_A = m->ws_phase.as<double>();
-        double* d_H = m->ws_H.as<double>();
+        const tbk_hk_plan_t plan = tbk_hk_plan(m, nkc, true);
         const double* kc = d_k + c0 * m->dim;
-        TBK_CHECK(fill_rows(m, kc, nkc, nk_pad, d_A));
-        TBK_CHECK(build_h(m, d_A, nkc, nk_pad, HK_TRI, 2, kc, nullptr, d_H));
+        TBK_CHECK(fill_rows(m, plan, kc));
+        TBK_CHECK(m->ws_H.reserve((size_t)nkc * nn2 * sizeof(double)));
+        double* d_H = m->ws_H.as<double>();
+        TBK_CHECK(build_h(m, plan, HK_TRI, 2, kc, nullptr, d_H));
         TBK_CHECK(tbk_eig_batched(m, d_H, nkc, d_E + (size_t)c0 * m->n_orb));
     }
     return TBK_OK;
@@ -1120,7 +1112,7 @@ extern "C" int tbk_hamilton(tbk_model* m, const double* k, int64_t nk, int conve
             TBK_CHECK(m->ws_out.reserve(h_bytes));
             // ONE k-point of a dense model (the Z2Pack call shape): k goes into the kernel arguments and the positions of
             // convention 1 stay on the device from call to call -- two uploads and one launch less per call
-            const bool inline_k = nk == 1 && !m->sparse && !m->kdotp && tbk_hk_inline_phases(m, 1);
+            const bool inline_k = nk == 1 && tbk_hk_plan(m, 1, false).rows == HK_ROWS_NONE;
             const double* d_pos = nullptr;
             if (inline_k) {
                 if (convention == 1) {
@@ -1227,7 +1219,7 @@ extern "C" int tbk_eigenval(tbk_model* m, const double* k, int64_t nk, double* E
         // (one k-point of a dense model on the matrix-vector path: k travels in the kernel arguments, see tbk_hamilton --
         // only the chunk pipeline reads it from there: the rocSOLVER branch fills its phase rows from ws_k, which a call
         // that skipped the upload would leave stale)
-        const bool inline_k = nk == 1 && !m->sparse && !m->kdotp && eigenval_own_solvers(m) && tbk_hk_inline_phases(m, 1);
+        const bool inline_k = nk == 1 && eigenval_own_solvers(m) && tbk_hk_plan(m, 1, false).rows == HK_ROWS_NONE;
         if (inline_k) {
             m->h_k_inline = k;
         } else {

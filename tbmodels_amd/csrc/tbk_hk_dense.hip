@@ -48,54 +48,54 @@ constexpr int STAGE_DOUBLES = TBK_BK * (LDA + LDB);
 static_assert(TBK_BM == 128 && TBK_BNP == 64 && TBK_BK == 16, "wave decomposition is written for 128x64x16");
 
 struct HkArgs {
-    const double* A;
-    const double* Bt;
-    const int32_t* colmap;
-    const double* kpts;  // [nk][dim]: read by the matrix-vector kernel when it makes its own phase rows (A == nullptr)
-    const int32_t* R;    // [n_r_pad][dim] lattice vectors, same use
-    int64_t n_r;
-    const double* pos;   // convention 1 only: orbital phase table e[k][p] = exp(2 pi i k.pos_p), [nk][n_orb][2]
-    double* H;
-    int64_t k2;
-    int64_t nk;
-    int64_t nk_pad;
-    int ncol_pad;
-    int n_orb;
-    int dim;
-    int mt_count;  // k tiles
-    int nt_count;  // element tiles
-    int xcd_rows;  // 0: plain order; > 0: k tiles per XCD super-row
+    const double* A = nullptr;
+    const double* Bt = nullptr;
+    const int32_t* colmap = nullptr;
+    const double* kpts = nullptr;  // [nk][dim]: read by the matrix-vector kernel when it makes its own phase rows (A == nullptr)
+    const int32_t* R = nullptr;    // [n_r_pad][dim] lattice vectors, same use
+    int64_t n_r = 0;
+    const double* pos = nullptr;   // convention 1 only: orbital phase table e[k][p] = exp(2 pi i k.pos_p), [nk][n_orb][2]
+    double* H = nullptr;
+    int64_t k2 = 0;
+    int64_t nk = 0;
+    int64_t nk_pad = 0;
+    int ncol_pad = 0;
+    int n_orb = 0;
+    int dim = 0;
+    int mt_count = 0;  // k tiles
+    int nt_count = 0;  // element tiles
+    int xcd_rows = 0;  // 0: plain order; > 0: k tiles per XCD super-row
     // split-K (small k batches): the launch covers `splits * unit_grid` units, unit u = split y = u / unit_grid of
     // block b = u % unit_grid of the tile walk; a unit owns a contiguous range of K stages and stores its partial tile
     // to P[y][k][e] (re, im) instead of scattering it; hk_finish_kernel adds the partials in fixed order
-    double* P;
-    int splits;
-    int unit_grid;
-    int64_t p_rows;  // k rows per split in P
+    double* P = nullptr;
+    int splits = 1;
+    int unit_grid = 1;
+    int64_t p_rows = 0;  // k rows per split in P
     // Strassen launches (launch_strassen below): split y is product p of the seven of one Strassen level instead of a K
     // range -- its operands start at A + p * a_prod_stride and Bt + p * b_prod_stride, it walks the whole (half) K of the
     // launch, and the epilogue parks every element of its tile, padding slots included, for hk_strassen_finish_kernel
-    int products;
-    int64_t a_prod_stride, b_prod_stride;
+    int products = 0;
+    int64_t a_prod_stride = 0, b_prod_stride = 0;
     // "lines" launches (second-level fold, tbk_fold.hip): k tile t is one mesh line -- its own operand at
     // Bt + t * b_tile_stride, the SAME phase rows for every line (a_tile_stride = 0), rows_per_tile k-points of output
-    int64_t a_tile_stride;  // TBK_BM in ordinary launches
-    int64_t b_tile_stride;  // 0 in ordinary launches
-    int rows_per_tile;      // TBK_BM in ordinary launches
+    int64_t a_tile_stride = TBK_BM;
+    int64_t b_tile_stride = 0;
+    int rows_per_tile = TBK_BM;
     // "tail" launches: the units of the last, partly filled round of a launch are split along K once more (launch()
     // below): this launch covers units block_offset + blockIdx.x, blockIdx.y < sub_splits takes a part of the unit's
     // stage range, and the partial tile goes to the compact P2[blockIdx.y][blockIdx.x][128][64] (re, im);
     // hk_finish_tiles_kernel adds them in order into H (splits == 1) or into the unit's P[y] (splits > 1)
-    int block_offset;
-    int p_tiles;  // > 0: a tail launch of that many units
-    int sub_splits;
-    double* P2;
+    int block_offset = 0;
+    int p_tiles = 0;  // > 0: a tail launch of that many units
+    int sub_splits = 1;
+    double* P2 = nullptr;
     // one-k host calls (round 4; Z2Pack evaluates ONE k-point per call, _tb_model.py:1103-1108): the k-point travels in the
     // kernel arguments instead of through an upload the kernels would have to wait for, and the convention-1 phases of the one
     // k-point are formed where they are used from the raw orbital positions (no orbital_phase_kernel launch in front)
-    double k_val[TBK_MAX_DIM];
-    int k_inline;
-    const double* pos_raw;  // [n_orb][dim], with k_inline and convention 1
+    double k_val[TBK_MAX_DIM] = {};
+    int k_inline = 0;
+    const double* pos_raw = nullptr;  // [n_orb][dim], with k_inline and convention 1
 };
 
 __device__ __forceinline__ double hk_kcomp(const HkArgs& a, int64_t kq, int d) { return a.k_inline ? a.k_val[d] : a.kpts[kq * a.dim + d]; }
@@ -794,6 +794,44 @@ int launch(tbk_model* m, const HkArgs& a0, int grid) {
     return TBK_OK;
 }
 
+// The arguments every launch shares: the model's operand (a.nt_count element tiles of it) and the output.
+HkArgs hk_args(const tbk_model* m, const double* d_A, int64_t nk, int64_t nk_pad, double* d_H) {
+    HkArgs a;
+    a.A = d_A;
+    a.Bt = m->d_B;
+    a.colmap = m->d_colmap;
+    a.R = m->d_R;
+    a.n_r = m->n_r;
+    a.H = d_H;
+    a.k2 = m->k2;
+    a.nk = nk;
+    a.nk_pad = nk_pad;
+    a.ncol_pad = m->ncol_pad;
+    a.n_orb = m->n_orb;
+    a.dim = m->dim;
+    a.nt_count = m->ncol_pad / TBK_BNP;
+    return a;
+}
+
+// The tile walk over mt_count k tiles and a.nt_count element tiles: XCD-aware (tile_of_block) from 32 k tiles -- below
+// that a plain round-robin over the XCDs balances better.  Returns the blocks of the walk.
+int tile_grid(HkArgs& a, int mt_count) {
+    a.mt_count = mt_count;
+    a.xcd_rows = mt_count >= 32 ? 4 : 0;
+    return mt_count >= 32 ? (mt_count + 7) / 8 * a.nt_count * 8 : mt_count * a.nt_count;
+}
+
+// The instantiation a launch takes: the upper triangle (the eigenvalue path, convention 2) or the full matrix in convention
+// 1 or 2, handed to `launch` as two std::integral_constant.  The return types are deduced, so both this and `launch` are
+// instantiated where by_mode is called: the kernel templates are first used in source order, which their code depends on.
+template <class F>
+auto by_mode(int mode, int convention, F&& launch) {
+    using std::integral_constant;
+    if (mode == HK_TRI) return launch(integral_constant<int, HK_TRI>(), integral_constant<int, 2>());
+    if (convention == 1) return launch(integral_constant<int, HK_FULL>(), integral_constant<int, 1>());
+    return launch(integral_constant<int, HK_FULL>(), integral_constant<int, 2>());
+}
+
 // One Strassen level: the seven half-size products as the units of ONE launch -- unit u = product
 // u / grid, block u % grid of the XCD-aware walk over the Mh x ncol_pad / 2 grid -- each parking its tiles in P[p], then the
 // combine.  The operands were made by phase_rows_strassen_kernel (a.A = As[7][K2 / 2][Mh]) and stage_strassen_kernel
@@ -806,22 +844,12 @@ int launch_strassen(tbk_model* m, const HkArgs& a0) {
     TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&hk_dense_kernel<HK_TRI, 2, true>), 160 * 1024, raised));
     const int64_t mh = tbk_strassen_mh(a0.nk);
     const int half = a0.ncol_pad / 2;
-    HkArgs a = a0;
+    HkArgs a = hk_args(m, a0.A, mh, mh, a0.H);
     a.Bt = m->d_Bs;
     a.k2 = m->k2 / 2;
-    a.nk = mh;
-    a.nk_pad = mh;
     a.ncol_pad = half;
-    a.mt_count = (int)(mh / TBK_BM);
     a.nt_count = half / TBK_BNP;
-    int grid;
-    if (a.mt_count >= 32) {
-        a.xcd_rows = 4;
-        grid = ((a.mt_count + 7) / 8) * a.nt_count * 8;
-    } else {
-        a.xcd_rows = 0;
-        grid = a.mt_count * a.nt_count;
-    }
+    const int grid = tile_grid(a, (int)(mh / TBK_BM));
     a.products = 1;
     a.splits = 7;
     a.unit_grid = grid;
@@ -886,167 +914,111 @@ void gemv_plan(const tbk_model* m, int64_t nk, int* slices_out, size_t* lds_out)
 
 }  // namespace
 
-// The Strassen path (launch_strassen): a dense tight-binding model padded and staged for it, with its own operand (not a
-// folded one), TBK_OPT_STRASSEN on, and a chunk of at least TBK_STRASSEN_MIN_NK k-points that takes neither the matrix-vector
-// path nor split-K.  Whether a chunk takes it is a function of (model, nk) only, so the phase rows made for a chunk
-// (tbk_api.hip fill_rows) and its contraction agree.
-bool tbk_hk_strassen(const tbk_model* m, int64_t nk) {
-    if (!m->strassen || m->d_Bs == nullptr || m->d_B != m->bs_src || m->sparse || m->kdotp) return false;
-    if (m->n_r_pad < TBK_STRASSEN_MIN_NR || nk < TBK_STRASSEN_MIN_NK || tbk_hk_gemv_path(m, nk)) return false;
-    const int64_t tiles = (nk + TBK_BM - 1) / TBK_BM * (m->ncol_pad / TBK_BNP);
-    return tiles >= 2 * m->n_cu;  // (fewer: the split-K launches below)
-}
-
-int64_t tbk_phase_doubles(const tbk_model* m, int64_t nk, int64_t nk_pad) {
-    if (tbk_hk_strassen(m, nk)) return 7 * (m->k2 / 2) * tbk_strassen_mh(nk);
-    return std::max<int64_t>(m->k2, 1) * nk_pad;
-}
-
-// True when tbk_launch_hk_dense will take the matrix-vector path AND can make its phase rows itself: the caller then
-// skips tbk_launch_phase and passes d_A = nullptr.
-bool tbk_hk_inline_phases(const tbk_model* m, int64_t nk) {
-    if (!tbk_hk_gemv_path(m, nk) || m->kdotp || m->d_R == nullptr) return false;
-    // the phase rows of a wave's slice for its (up to 32) k-points must fit its strip of the workgroup's LDS
-    int slices;
-    size_t lds;
-    gemv_plan(m, nk, &slices, &lds);
-    return gemv_strip_rows(m, slices) * gemv_nkv(nk) <= (int64_t)(lds / 32);
-}
-
-// The matrix-vector path: up to 32 k-points of any model, and up to 4096 k-points (in groups of 32) of a SMALL model --
-// at most 22 orbitals and fewer than 128 lattice vectors, i.e. a handful of MFMA tiles walking a dozen K stages one
-// load latency at a time (the 1000-point silicon grid: 31 us in the tile kernel, ~10 us here).
-bool tbk_hk_gemv_path(const tbk_model* m, int64_t nk) {
-    if (nk < 1 || m->k2 <= 0 || m->sparse) return false;
-    if (nk <= 32) return true;
-    return nk <= 4096 && m->ncol_pad <= 256 && m->k2 < 16 * TBK_BK;
-}
-
-int tbk_launch_hk_dense(tbk_model* m, const double* d_A, int64_t nk, int64_t nk_pad, int mode,
-                        int convention, const double* d_k, const double* d_pos, double* d_H) {
-    if (nk == 0) return TBK_OK;
-    HkArgs a;
-    a.A = d_A;
-    a.Bt = m->d_B;
-    a.colmap = m->d_colmap;
-    a.kpts = d_k;
-    a.R = m->d_R;
-    a.n_r = m->n_r;
-    a.pos = d_pos;
-    a.H = d_H;
-    a.k2 = m->k2;
-    a.nk = nk;
-    a.nk_pad = nk_pad;
-    a.ncol_pad = m->ncol_pad;
-    a.n_orb = m->n_orb;
-    a.dim = m->dim;
-    a.mt_count = (int)((nk + TBK_BM - 1) / TBK_BM);  // nk_pad is only the row stride of A
-    a.nt_count = m->ncol_pad / TBK_BNP;
-    int grid;
-    if (a.mt_count >= 32) {  // below that a plain round-robin over the XCDs balances better
-        a.xcd_rows = 4;
-        const int max_rows = (a.mt_count + 7) / 8;
-        grid = max_rows * a.nt_count * 8;
-    } else {
-        a.xcd_rows = 0;
-        grid = a.mt_count * a.nt_count;
+// ---- the path of a chunk ------------------------------------------------------------------------------------------------
+//
+// * CSR: sparse models.
+// * The matrix-vector path (GEMV): up to 32 k-points of any model, and up to 4096 k-points (in groups of 32) of a SMALL model --
+//   at most 22 orbitals and fewer than 128 lattice vectors, i.e. a handful of MFMA tiles walking a dozen K stages one load
+//   latency at a time (the 1000-point silicon grid: 31 us in the tile kernel, ~10 us here).  Its kernel makes the phase rows
+//   itself (HK_ROWS_NONE: the caller skips them and passes d_A = nullptr) unless the caller makes them, the model is k.p, or
+//   the rows of a wave's slice for its (up to 32) k-points do not fit its strip of the workgroup's LDS.
+// * TINY: one k-point of a small model whose rows the kernel makes -- the whole H(k) in ONE launch (hk_tiny_kernel, <= 36 KiB
+//   of LDS).
+// * STRASSEN (launch_strassen): a dense tight-binding model padded and staged for it, with its own operand (not a folded
+//   one), TBK_OPT_STRASSEN on, and a chunk of at least TBK_STRASSEN_MIN_NK k-points that takes neither the matrix-vector path
+//   nor split-K.  Its rows are the seven blocks As[7][K2 / 2][Mh].
+// * TILES: the MFMA tiles.  Small k batches: a workgroup's K loop is a serial chain (1.06 ms at N_R = 4096 whatever the
+//   batch), and fewer tiles than workgroup slots leave CUs idle -- split K into ~1280 units (block x split) so that the
+//   launch fills the chip for two to three rounds; launch() cuts the ragged last round once more.  Partial tiles go to a
+//   workspace, hk_finish_kernel adds them in fixed order.  Measured at N_orb = 64, N_R = 4096: one k-point 1056 -> 163 us
+//   (before the matrix-vector path), 1000 k-points 2137 -> 1264 us.  (Just enough splits for ONE full round plus a
+//   sub-split tail was slower up to 500 k-points: three more launches on a 0.2 ms kernel.)
+tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, int64_t nk, bool caller_rows) {
+    tbk_hk_plan_t p;
+    p.nk = nk;
+    p.nk_pad = (nk + TBK_BM - 1) / TBK_BM * TBK_BM;
+    p.rows = m->kdotp ? HK_ROWS_MONOMIAL : HK_ROWS_PHASE;
+    p.row_doubles = std::max<int64_t>(m->k2, 1) * p.nk_pad;
+    if (m->sparse) {
+        p.path = HK_PATH_CSR;
+        return p;
     }
-    a.P = nullptr;
-    a.splits = 1;
-    a.p_rows = 0;
-    a.products = 0;
-    a.a_prod_stride = a.b_prod_stride = 0;
-    a.a_tile_stride = TBK_BM;
-    a.b_tile_stride = 0;
-    a.rows_per_tile = TBK_BM;
-    a.block_offset = 0;
-    a.p_tiles = 0;
-    a.sub_splits = 1;
-    a.P2 = nullptr;
-    a.unit_grid = 1;
-    a.k_inline = 0;
-    a.pos_raw = nullptr;
-    for (int d = 0; d < TBK_MAX_DIM; ++d) a.k_val[d] = 0.0;
-    if (tbk_hk_gemv_path(m, nk)) {
-        int slices;
-        size_t lds;
-        gemv_plan(m, nk, &slices, &lds);
-        const size_t per_split = (size_t)nk * a.ncol_pad * 2 * sizeof(double);
-        if (m->h_k_inline != nullptr && nk == 1 && d_A == nullptr && tbk_hk_inline_phases(m, 1)) {
-            a.k_inline = 1;  // (tbk_hamilton / tbk_eigenval on host buffers, one k-point: no upload of k)
-            for (int d = 0; d < m->dim; ++d) a.k_val[d] = m->h_k_inline[d];
-            a.pos_raw = m->d_pos_inline;  // convention 1: the raw positions (tbk_hamilton keeps them on the device)
-        }
-        TBK_ARG(d_A != nullptr || (tbk_hk_inline_phases(m, nk) && (d_k != nullptr || a.k_inline)), "phase rows missing");
-        TBK_ARG(convention != 1 || mode == HK_TRI || d_pos != nullptr || (a.k_inline && a.pos_raw != nullptr), "convention 1 needs the orbital phases");
-        if (nk == 1 && d_A == nullptr && a.ncol_pad <= 256 && m->k2 <= 4096) {  // (<= 36 KiB of LDS)
-            // one k-point of a small model: the whole H(k) in ONE launch (hk_tiny_kernel)
-            const int strip = (int)(((m->k2 / 2 + 3) / 4 * 2 + 15) / 16 * 16);  // rows of the longest quarter, whole trips of the loop
-            const size_t lds_tiny = ((size_t)4 * strip + 4 * 64 * 2) * sizeof(double);
-            const dim3 grid_tiny((unsigned)(a.ncol_pad / 64));
-            StageTimer t(m, TBK_T_HK);
-            if (mode == HK_TRI)
-                hipLaunchKernelGGL((hk_tiny_kernel<HK_TRI, 2>), grid_tiny, dim3(256), lds_tiny, m->stream, a, strip);
-            else if (convention == 1)
-                hipLaunchKernelGGL((hk_tiny_kernel<HK_FULL, 1>), grid_tiny, dim3(256), lds_tiny, m->stream, a, strip);
-            else
-                hipLaunchKernelGGL((hk_tiny_kernel<HK_FULL, 2>), grid_tiny, dim3(256), lds_tiny, m->stream, a, strip);
+    if (nk >= 1 && m->k2 > 0 && (nk <= 32 || (nk <= 4096 && m->ncol_pad <= 256 && m->k2 < 16 * TBK_BK))) {
+        gemv_plan(m, nk, &p.splits, &p.lds);
+        if (!caller_rows && !m->kdotp && m->d_R != nullptr && gemv_strip_rows(m, p.splits) * gemv_nkv(nk) <= (int64_t)(p.lds / 32))
+            p.rows = HK_ROWS_NONE;
+        const bool tiny = p.rows == HK_ROWS_NONE && nk == 1 && m->ncol_pad <= 256 && m->k2 <= 4096;
+        p.path = tiny ? HK_PATH_TINY : HK_PATH_GEMV;
+        return p;
+    }
+    const int64_t tiles = (nk + TBK_BM - 1) / TBK_BM * (m->ncol_pad / TBK_BNP);
+    if (m->strassen && m->d_Bs != nullptr && m->d_B == m->bs_src && !m->kdotp && m->n_r_pad >= TBK_STRASSEN_MIN_NR &&
+        nk >= TBK_STRASSEN_MIN_NK && tiles >= 2 * m->n_cu) {
+        p.path = HK_PATH_STRASSEN;
+        p.rows = HK_ROWS_STRASSEN;
+        p.row_doubles = 7 * (m->k2 / 2) * tbk_strassen_mh(nk);
+        return p;
+    }
+    p.path = HK_PATH_TILES;
+    const int n_stage = (int)(m->k2 / TBK_BK);
+    if (tiles < 2 * m->n_cu && n_stage >= 16) {
+        int64_t splits = std::min<int64_t>((1280 + tiles / 2) / tiles, n_stage / 4);
+        const size_t per_split = (size_t)p.nk_pad * m->ncol_pad * 2 * sizeof(double);
+        splits = std::min<int64_t>(splits, (int64_t)((size_t(512) << 20) / per_split));
+        if (splits > 1) p.splits = (int)splits;
+    }
+    return p;
+}
+
+int tbk_launch_hk_dense(tbk_model* m, const tbk_hk_plan_t& p, const double* d_A, int mode, int convention,
+                        const double* d_k, const double* d_pos, double* d_H) {
+    if (p.nk == 0) return TBK_OK;
+    TBK_ARG(p.path != HK_PATH_CSR, "sparse models take tbk_launch_hk_csr");
+    HkArgs a = hk_args(m, d_A, p.nk, p.nk_pad, d_H);
+    a.kpts = d_k;
+    a.pos = d_pos;
+    const int grid = tile_grid(a, (int)((p.nk + TBK_BM - 1) / TBK_BM));  // (nk_pad is only the row stride of A)
+    if (m->h_k_inline != nullptr && p.nk == 1 && p.rows == HK_ROWS_NONE) {
+        a.k_inline = 1;  // (tbk_hamilton / tbk_eigenval on host buffers, one k-point: no upload of k)
+        for (int d = 0; d < m->dim; ++d) a.k_val[d] = m->h_k_inline[d];
+        a.pos_raw = m->d_pos_inline;  // convention 1: the raw positions (tbk_hamilton keeps them on the device)
+    }
+    TBK_ARG(p.rows == HK_ROWS_NONE ? d_k != nullptr || a.k_inline : d_A != nullptr, "phase rows missing");
+    TBK_ARG(convention != 1 || mode == HK_TRI || d_pos != nullptr || (a.k_inline && a.pos_raw != nullptr), "convention 1 needs the orbital phases");
+    if (p.path == HK_PATH_TINY) {
+        const int strip = (int)(((m->k2 / 2 + 3) / 4 * 2 + 15) / 16 * 16);  // rows of the longest quarter, whole trips of the loop
+        const size_t lds = ((size_t)4 * strip + 4 * 64 * 2) * sizeof(double);
+        StageTimer t(m, TBK_T_HK);
+        return by_mode(mode, convention, [&](auto md, auto cv) {
+            hipLaunchKernelGGL((hk_tiny_kernel<md, cv>), dim3((unsigned)(a.ncol_pad / 64)), dim3(256), lds, m->stream, a, strip);
             TBK_HIP(hipGetLastError());
             return TBK_OK;
-        }
-        TBK_CHECK(m->ws_part.reserve(per_split * slices));
+        });
+    }
+    if (p.path == HK_PATH_GEMV) {
+        TBK_CHECK(m->ws_part.reserve((size_t)p.nk * a.ncol_pad * 2 * sizeof(double) * p.splits));
         a.P = m->ws_part.as<double>();
-        a.splits = slices;
-        a.p_rows = nk;
+        a.splits = p.splits;
+        a.p_rows = p.nk;
         StageTimer t(m, TBK_T_HK);
-        if (mode == HK_TRI) {
-            TBK_HIP((launch_gemv<HK_TRI, 2>(m, a, lds, m->stream)));
-        } else if (convention == 1) {
-            TBK_HIP((launch_gemv<HK_FULL, 1>(m, a, lds, m->stream)));
-        } else {
-            TBK_HIP((launch_gemv<HK_FULL, 2>(m, a, lds, m->stream)));
-        }
-        return TBK_OK;
+        return by_mode(mode, convention, [&](auto md, auto cv) {
+            TBK_HIP((launch_gemv<md, cv>(m, a, p.lds, m->stream)));
+            return TBK_OK;
+        });
     }
-    if (d_A != nullptr && tbk_hk_strassen(m, nk)) {
+    if (p.path == HK_PATH_STRASSEN) {
         StageTimer t(m, TBK_T_HK);
-        if (mode == HK_TRI) {
-            TBK_CHECK((launch_strassen<HK_TRI, 2>(m, a)));
-        } else if (convention == 1) {
-            TBK_CHECK((launch_strassen<HK_FULL, 1>(m, a)));
-        } else {
-            TBK_CHECK((launch_strassen<HK_FULL, 2>(m, a)));
-        }
-        return TBK_OK;
+        return by_mode(mode, convention, [&](auto md, auto cv) { return launch_strassen<md, cv>(m, a); });
     }
-    // Small k batches: a workgroup's K loop is a serial chain (1.06 ms at N_R = 4096 whatever the batch), and fewer
-    // tiles than workgroup slots leave CUs idle -- split K into ~1280 units (block x split) so that the launch fills
-    // the chip for two to three rounds; launch() cuts the ragged last round once more.  Partial tiles go to a
-    // workspace, hk_finish_kernel adds them in fixed order.  Measured at N_orb = 64, N_R = 4096: one k-point
-    // 1056 -> 163 us (before the matrix-vector path), 1000 k-points 2137 -> 1264 us.  (Just enough splits for ONE
-    // full round plus a sub-split tail was slower up to 500 k-points: three more launches on a 0.2 ms kernel.)
-    const int n_stage = (int)(m->k2 / TBK_BK);
-    const int tiles = a.mt_count * a.nt_count;
-    if (tiles < 2 * m->n_cu && n_stage >= 16) {
-        int splits = std::min((1280 + tiles / 2) / tiles, n_stage / 4);
-        const size_t per_split = (size_t)nk_pad * a.ncol_pad * 2 * sizeof(double);
-        splits = (int)std::min<size_t>((size_t)splits, (size_t(512) << 20) / per_split);
-        if (splits > 1) {
-            TBK_CHECK(m->ws_part.reserve(per_split * splits));
-            a.P = m->ws_part.as<double>();
-            a.splits = splits;
-            a.p_rows = nk_pad;
-        }
+    if (p.splits > 1) {
+        const size_t per_split = (size_t)p.nk_pad * a.ncol_pad * 2 * sizeof(double);
+        TBK_CHECK(m->ws_part.reserve(per_split * p.splits));
+        a.P = m->ws_part.as<double>();
+        a.splits = p.splits;
+        a.p_rows = p.nk_pad;
     }
     StageTimer t(m, TBK_T_HK);
-    if (mode == HK_TRI) {
-        TBK_CHECK((launch<HK_TRI, 2>(m, a, grid)));
-    } else if (convention == 1) {
-        TBK_CHECK((launch<HK_FULL, 1>(m, a, grid)));
-    } else {
-        TBK_CHECK((launch<HK_FULL, 2>(m, a, grid)));
-    }
-    return TBK_OK;
+    return by_mode(mode, convention, [&](auto md, auto cv) { return launch<md, cv>(m, a, grid); });
 }
 
 // H(k) of n_lines mesh lines of line_len (<= 128) k-points each in ONE launch: line t uses the operand at
@@ -1057,45 +1029,11 @@ int tbk_launch_hk_dense_lines(tbk_model* m, const double* d_A, int64_t n_lines, 
                               double* d_H) {
     if (n_lines == 0) return TBK_OK;
     TBK_ARG(line_len >= 1 && line_len <= TBK_BM, "a mesh line must fit one k tile");
-    HkArgs a;
-    a.A = d_A;
-    a.Bt = m->d_B;
-    a.colmap = m->d_colmap;
-    a.kpts = nullptr;
-    a.R = m->d_R;
-    a.n_r = m->n_r;
-    a.pos = nullptr;
-    a.H = d_H;
-    a.k2 = m->k2;
-    a.nk = n_lines * line_len;
-    a.nk_pad = TBK_BM;
-    a.ncol_pad = m->ncol_pad;
-    a.n_orb = m->n_orb;
-    a.dim = m->dim;
-    a.mt_count = (int)n_lines;
-    a.nt_count = m->ncol_pad / TBK_BNP;
-    a.P = nullptr;
-    a.splits = 1;
-    a.p_rows = 0;
-    a.products = 0;
-    a.a_prod_stride = a.b_prod_stride = 0;
+    HkArgs a = hk_args(m, d_A, n_lines * line_len, TBK_BM, d_H);
     a.a_tile_stride = 0;
     a.b_tile_stride = b_stride;
     a.rows_per_tile = line_len;
-    a.block_offset = 0;
-    a.p_tiles = 0;
-    a.sub_splits = 1;
-    a.P2 = nullptr;
-    a.unit_grid = 1;
-    int grid;
-    if (a.mt_count >= 32) {
-        a.xcd_rows = 4;
-        grid = ((a.mt_count + 7) / 8) * a.nt_count * 8;
-    } else {
-        a.xcd_rows = 0;
-        grid = a.mt_count * a.nt_count;
-    }
+    const int grid = tile_grid(a, (int)n_lines);
     StageTimer t(m, TBK_T_HK);
-    TBK_CHECK((launch<HK_TRI, 2>(m, a, grid)));
-    return TBK_OK;
+    return launch<HK_TRI, 2>(m, a, grid);
 }

@@ -278,14 +278,40 @@ enum HkMode { HK_TRI = 0, HK_FULL = 1 };
 
 // One Strassen level in the dense H(k) contraction (tbk_hk_dense.hip).  Models with at least
 // TBK_STRASSEN_MIN_NR padded lattice vectors are padded for it (n_r_pad a multiple of 16, ncol_pad of 128) and get the
-// operand blocks d_Bs; k chunks of at least TBK_STRASSEN_MIN_NK k-points on the direct MFMA path then take it.
+// operand blocks d_Bs; k chunks of at least TBK_STRASSEN_MIN_NK k-points on the direct MFMA path then take it (tbk_hk_plan).
 constexpr int64_t TBK_STRASSEN_MIN_NR = 1024;
 constexpr int64_t TBK_STRASSEN_MIN_NK = 8192;
 inline bool tbk_strassen_model(bool sparse, bool kdotp, int64_t n_r) { return !sparse && !kdotp && n_r >= TBK_STRASSEN_MIN_NR; }
-bool tbk_hk_strassen(const tbk_model* m, int64_t nk);  // tbk_hk_dense.hip: this chunk of nk k-points takes the Strassen path
 inline int64_t tbk_strassen_mh(int64_t nk) { return (((nk + 1) / 2) + TBK_BM - 1) / TBK_BM * TBK_BM; }  // k rows per half
-// doubles of the phase rows of a chunk of nk k-points (padded to nk_pad): the seven blocks As[7][K2 / 2][Mh], or A[K2][nk_pad]
-int64_t tbk_phase_doubles(const tbk_model* m, int64_t nk, int64_t nk_pad);
+
+// How the H(k) of one chunk of k-points is computed: the contraction path and the rows it reads.  tbk_hk_plan
+// (tbk_hk_dense.hip) is the only place that chooses them; the phase rows of a chunk (tbk_api.hip fill_rows) and its
+// contraction (build_h) are made from the same plan.
+enum HkPath {
+    HK_PATH_CSR,       // sparse models (tbk_hk_csr.hip)
+    HK_PATH_TINY,      // one k-point of a small model in one launch (hk_tiny_kernel)
+    HK_PATH_GEMV,      // the matrix-vector kernel (hk_gemv_kernel), `splits` K slices
+    HK_PATH_STRASSEN,  // one Strassen level on the MFMA tiles (launch_strassen)
+    HK_PATH_TILES,     // the MFMA tiles, split along K `splits` ways (1: not split)
+};
+enum HkRows {
+    HK_ROWS_NONE,      // the H(k) kernel makes them from k (d_A = NULL)
+    HK_ROWS_PHASE,     // A[K2][nk_pad] cos / sin rows
+    HK_ROWS_MONOMIAL,  // A[K2][nk_pad] k.p monomials
+    HK_ROWS_STRASSEN,  // the seven blocks As[7][K2 / 2][Mh]
+};
+struct tbk_hk_plan_t {
+    HkPath path = HK_PATH_TILES;
+    HkRows rows = HK_ROWS_PHASE;
+    int64_t nk = 0;
+    int64_t nk_pad = 0;       // the row stride of A: whole k tiles
+    int64_t row_doubles = 0;  // ws_phase for the rows (reserved for HK_ROWS_NONE as well)
+    int splits = 1;           // GEMV: K slices; TILES: K splits
+    size_t lds = 0;           // GEMV: dynamic LDS per workgroup
+};
+// A function of the model as it stands (a folded operand swapped in by tbk_fold_enter included) and nk.  caller_rows: the
+// caller makes the phase rows whatever the path (never HK_ROWS_NONE).
+tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, int64_t nk, bool caller_rows);
 
 // tbk_phase.hip
 int tbk_launch_phase_strassen(tbk_model* m, const double* d_k, int64_t nk, double* d_As);
@@ -300,9 +326,9 @@ int tbk_stage_dense(tbk_model* m, const double* d_hop_raw);
 int tbk_stage_kdotp(tbk_model* m, const double* d_coeff_raw);
 int tbk_stage_strassen(tbk_model* m);
 
-// tbk_hk_dense.hip
-int tbk_launch_hk_dense(tbk_model* m, const double* d_A, int64_t nk, int64_t nk_pad, int mode,
-                        int convention, const double* d_k, const double* d_pos, double* d_H);
+// tbk_hk_dense.hip: the H(k) of plan.nk k-points along plan.path (not HK_PATH_CSR); d_A holds the plan's rows
+int tbk_launch_hk_dense(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_A, int mode, int convention,
+                        const double* d_k, const double* d_pos, double* d_H);
 
 int tbk_launch_hk_dense_lines(tbk_model* m, const double* d_A, int64_t n_lines, int line_len, int64_t b_stride, double* d_H);
 
@@ -323,8 +349,6 @@ int tbk_eig_batched(tbk_model* m, double* d_H, int64_t nk, double* d_E);    // f
 bool tbk_eig_stream_supported(int n);
 // method: TBK_REDUCE_AUTO (what eigenval takes), _ONE_STAGE, _TWO_STAGE (tbk.h)
 int tbk_launch_tridiag_stream(tbk_model* m, hipStream_t s, double* d_H, int64_t nk, double* d_de, int method = 0);
-bool tbk_hk_inline_phases(const tbk_model* m, int64_t nk);  // tbk_hk_dense.hip
-bool tbk_hk_gemv_path(const tbk_model* m, int64_t nk);
 int tbk_launch_bisect(tbk_model* m, hipStream_t s, const double* d_de, int64_t nk, double* d_E);
 size_t tbk_eig_scratch_per_k(const tbk_model* m);
 int tbk_band_xl_reserve(tbk_model* m, int64_t max_nk);  // tbk_eig_band.hip: ws_xl for chunks of up to max_nk matrices

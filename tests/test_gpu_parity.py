@@ -208,7 +208,7 @@ def test_matrix_vector_path_over_shapes(n_orb):
     """The matrix-vector kernel of round 6 cuts its work into (blocks of 64 packed elements) x (slices of whole lattice vectors)
     per WAVE, the slices ragged (K rows / slices is no whole number), one round of two workgroups per CU or many rounds, the
     phase rows in a wave-private LDS strip or -- strip too short -- handed in (`csrc/tbk_hk_dense.hip`: gemv_plan,
-    tbk_hk_inline_phases).  Every combination of 13 orbital counts (1 .. 300: one block of 64 elements .. 706 blocks, with and
+    tbk_hk_plan).  Every combination of 13 orbital counts (1 .. 300: one block of 64 elements .. 706 blocks, with and
     without padding), 8 lattice-vector counts (1 .. 1500: one slice of 16 rows .. hundreds) and 7 batch sizes (every
     instantiation, full and ragged) against the oracle: H(k) in both conventions, and the eigenvalues
     (`_tb_model.py:1109-1128`, `:1147-1150`)."""
@@ -1224,7 +1224,7 @@ def test_block_diagonal_spectra_symmetric_about_zero(n):
 @pytest.mark.parametrize("n_k", [33, 64, 65, 1000, 4096, 4097])
 def test_small_model_batches_take_the_grouped_matrix_vector_path(silicon, n_k):
     """Small models (<= 22 orbitals, < 128 lattice vectors) evaluate up to 4096 k-points in groups of 32 with the
-    matrix-vector kernel (tbk_hk_gemv_path); 4097 k-points are back on the MFMA tiles.  Both conventions, both H modes."""
+    matrix-vector kernel (tbk_hk_plan); 4097 k-points are back on the MFMA tiles.  Both conventions, both H modes."""
     model = tbmodels_amd.Model.from_packed(silicon["R"], silicon["hop"], pos=silicon["pos"])
     k = syn.random_kpoints(n_k, seed=n_k) * 2.0 - 0.7
     sub = np.unique(np.concatenate([np.arange(0, n_k, max(1, n_k // 37)), [n_k - 1, n_k - 2, 31, 32]]))
