@@ -119,6 +119,17 @@ int tbk_hamilton(tbk_model* m, const double* k, int64_t nk, int convention, cons
 /* Ascending eigenvalues of H(k) (convention 2) for nk k-points. */
 int tbk_eigenval(tbk_model* m, const double* k, int64_t nk, double* E_out);
 
+/* Eigenvalues AND eigenvectors of H(k) in `convention` (1 or 2; pos as for tbk_hamilton; Model.eigh):
+ *   E  double [nk][n_orb]             ascending eigenvalues per k
+ *   U  double [nk][n_orb][n_orb][2]   U[k][i][j] = component i of the unit eigenvector of E[k][j] (columns, as in
+ *                                     scipy.linalg.eigh); the columns of every U[k] are orthonormal
+ * The phase of every column, and the basis inside a degenerate eigenspace, are unspecified (as in LAPACK).
+ * n_orb <= 64 (TBK_EIG_AUTO / _WAVE): parallel cyclic Jacobi in LDS (csrc/tbk_eigh.hip), whose result for one matrix does not
+ * depend on the call shape; above 64 orbitals or with TBK_EIG_ROCSOLVER: rocsolver_zheev_strided_batched
+ * (TBK_CNT_LIBRARY_CALLS); TBK_EIG_WAVE above 64 orbitals is TBK_ERR_ARGUMENT.  Non-finite H(k) -> TBK_ERR_NOT_FINITE
+ * (NaN rows in E and U), no convergence -> TBK_ERR_NO_CONVERGENCE.  The solver's time is charged to TBK_T_EIG. */
+int tbk_eigh(tbk_model* m, const double* k, int64_t nk, int convention, const double* pos, double* E_out, double* U_out);
+
 /* ---- the hot path on several devices from ONE process (host buffers) ----------------------
  * handles[0..n_handles) are staged copies of the SAME model, normally one per device (several on one device are
  * allowed).  The k list is cut into contiguous slabs of ceil(nk / n_handles) rows (handle i takes slab i; the last
@@ -130,11 +141,17 @@ int tbk_eigenval(tbk_model* m, const double* k, int64_t nk, double* E_out);
 int tbk_eigenval_multi(tbk_model* const* handles, int n_handles, const double* k, int64_t nk, double* E_out);
 int tbk_hamilton_multi(tbk_model* const* handles, int n_handles, const double* k, int64_t nk, int convention,
                        const double* pos, double* H_out);
+int tbk_eigh_multi(tbk_model* const* handles, int n_handles, const double* k, int64_t nk, int convention,
+                   const double* pos, double* E_out, double* U_out);
 
 /* ---- the hot path, device buffers (bench, sharded runs, device-side consumers) ----------- */
 int tbk_hamilton_device(tbk_model* m, const double* d_k, int64_t nk, int convention,
                         const double* d_pos, double* d_H);
 int tbk_eigenval_device(tbk_model* m, const double* d_k, int64_t nk, double* d_E);
+/* tbk_eigh on device buffers: H(k) of every chunk is built straight into its rows of d_U and overwritten there by its
+ * eigenvectors (no N^2 workspace).  Enqueued only: the non-finite / convergence flags are reported by tbk_eigenval_check. */
+int tbk_eigh_device(tbk_model* m, const double* d_k, int64_t nk, int convention, const double* d_pos, double* d_E,
+                    double* d_U);
 /* The same for a caller that still holds the host array it uploaded: h_k == the contents of d_k (or NULL).
  * Device-resident lists are never read back -- that would synchronise -- so long runs of one shared k component
  * (uniform meshes in meshgrid order, stacks of planes; TBK_OPT_FOLD) are only recognised through h_k: the run
@@ -171,10 +188,12 @@ int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, const int32_t*
 void tbk_kdotp_destroy(tbk_kdotp* m);
 int tbk_kdotp_hamilton(tbk_kdotp* m, const double* k, int64_t nk, double* H_out);
 int tbk_kdotp_eigenval(tbk_kdotp* m, const double* k, int64_t nk, double* E_out);
+int tbk_kdotp_eigh(tbk_kdotp* m, const double* k, int64_t nk, double* E_out, double* U_out);  /* tbk_eigh, convention 2 */
 /* The same on several devices from one process: staged copies of ONE k.p model, contiguous k slabs, one host thread
  * per non-empty slab -- tbk_eigenval_multi / tbk_hamilton_multi for kdotp.py:51-100. */
 int tbk_kdotp_eigenval_multi(tbk_kdotp* const* handles, int n_handles, const double* k, int64_t nk, double* E_out);
 int tbk_kdotp_hamilton_multi(tbk_kdotp* const* handles, int n_handles, const double* k, int64_t nk, double* H_out);
+int tbk_kdotp_eigh_multi(tbk_kdotp* const* handles, int n_handles, const double* k, int64_t nk, double* E_out, double* U_out);
 
 /* Model.construct_kdotp (_tb_model.py:942-982): Taylor coefficients of H(k) around k0 for n_p power
  * tuples.  powers: int32 [n_p][dim]; prefactor: double [n_p][2] = (2 pi i)^{|p|} / prod p_d! as (re, im);
@@ -191,7 +210,7 @@ int tbk_device_mem_info(int device, int64_t* free_bytes, int64_t* total_bytes);
 
 /* ---- timing: HIP events around every kernel of the path, on the stream it is launched on -------
  * stages: PHASE phase rows; HK the H(k) contraction; EIG reduction to tridiagonal form (or the whole
- * rocSOLVER call); QL the tridiagonal stage (QL + sort, or bisection).  Stages of different k chunks may overlap. */
+ * rocSOLVER call, and the eigenvector solver of tbk_eigh); QL the tridiagonal stage (QL + sort, or bisection).  Stages of different k chunks may overlap. */
 enum { TBK_T_PHASE = 0, TBK_T_HK = 1, TBK_T_EIG = 2, TBK_T_QL = 3, TBK_T_COUNT = 4 };
 /* ms[i] = summed duration of stage i, launches[i] = number of timed launches; reset = 1 clears. */
 int tbk_get_timing(tbk_model* m, double* ms, int64_t* launches, int reset);

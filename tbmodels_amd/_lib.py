@@ -54,6 +54,9 @@ SIGNATURES = {
     "tbk_eigenval": (_c_int, [_vp, _vp, _c_i64, _vp]),
     "tbk_eigenval_multi": (_c_int, [_vp, _c_int, _vp, _c_i64, _vp]),
     "tbk_hamilton_multi": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_int, _vp, _vp]),
+    "tbk_eigh": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp, _vp, _vp]),
+    "tbk_eigh_multi": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_int, _vp, _vp, _vp]),
+    "tbk_eigh_device": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp, _vp, _vp]),
     "tbk_hamilton_device": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp, _vp]),
     "tbk_eigenval_device": (_c_int, [_vp, _vp, _c_i64, _vp]),
     "tbk_eigenval_device_hint": (_c_int, [_vp, _vp, _vp, _c_i64, _vp]),
@@ -68,6 +71,8 @@ SIGNATURES = {
     "tbk_kdotp_eigenval": (_c_int, [_vp, _vp, _c_i64, _vp]),
     "tbk_kdotp_eigenval_multi": (_c_int, [_vp, _c_int, _vp, _c_i64, _vp]),
     "tbk_kdotp_hamilton_multi": (_c_int, [_vp, _c_int, _vp, _c_i64, _vp]),
+    "tbk_kdotp_eigh": (_c_int, [_vp, _vp, _c_i64, _vp, _vp]),
+    "tbk_kdotp_eigh_multi": (_c_int, [_vp, _c_int, _vp, _c_i64, _vp, _vp]),
     "tbk_kdotp_coefficients": (_c_int, [_vp, _vp, _c_i64, _vp, _vp, _vp]),
     "tbk_device_malloc": (_c_int, [_c_int, _c_i64, _pp]),
     "tbk_device_free": (_c_int, [_c_int, _vp]),

@@ -746,6 +746,34 @@ class Model:
             _lib.check(_lib.lib().tbk_eigenval_multi(handles, n_handles, _lib.ptr(k_array), n_k, _lib.ptr(out)))
         return out[0] if single else out
 
+    def eigh(self, k, convention=2):
+        """
+        Eigenvalues and eigenvectors of ``hamilton(k, convention)``: ``(E, U)`` with ``E (N,)`` float64 and ``U (N, N)``
+        complex128 for one k-point, ``E (NK, N)`` and ``U (NK, N, N)`` for a list of k-points (arrays, not lists).
+        ``E`` is ascending and ``U[..., :, j]`` is a unit eigenvector for ``E[..., j]``, as in ``scipy.linalg.eigh``; the
+        columns of ``U`` are orthonormal.  The phase of every column is unspecified, as in LAPACK, and so is the basis
+        chosen inside a degenerate eigenspace.  Not in the reference (``_tb_model.py`` has only ``eigenval``).
+        """
+        if convention not in [1, 2]:
+            raise ValueError(
+                "Invalid value '{}' for 'convention': must be either '1' or '2'".format(convention)
+            )
+        if np.shape(k) == (0,):  # an empty list of k-points
+            k = np.zeros((0, self.dim))
+        k_array, single = self._k_array(k)
+        n_k = k_array.shape[0]
+        eig = _outbuf.empty((n_k, self.size), np.float64)
+        vec = _outbuf.empty((n_k, self.size, self.size), np.complex128)
+        pos = np.ascontiguousarray(self.pos, dtype=np.float64) if convention == 1 else None
+        with self._call_lock:
+            # NaN / Inf in k or in the hoppings: TBK_ERR_NOT_FINITE -> ValueError; no convergence -> LinAlgError
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_eigh_multi(handles, n_handles, _lib.ptr(k_array), n_k, int(convention), _lib.ptr(pos),
+                                          _lib.ptr(eig), _lib.ptr(vec))
+            )
+        return (eig[0], vec[0]) if single else (eig, vec)
+
     def construct_kdotp(self, k, order):
         """
         k.p model around the k-point ``k``: the Taylor expansion of H(k) (convention 2) up to total power

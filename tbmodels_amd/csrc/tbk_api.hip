@@ -434,7 +434,7 @@ extern "C" int tbk_model_info(const tbk_model* m, int* device, int* dim, int* n_
 // ------------------------------------------------------------------------------------------------
 // the chunked pipeline
 // ------------------------------------------------------------------------------------------------
-static int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
+int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
     // (a call of up to one k tile is one chunk whatever the memory: no hipMemGetInfo -- a driver query -- on the one-k path)
     if (nk <= TBK_BM) return TBK_BM;
     const int64_t n = m->n_orb;
@@ -479,7 +479,7 @@ static int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
 }
 
 // The phase rows of a chunk of plan.nk k-points for its plan, in ws_phase (reserved also when the H(k) kernel makes them).
-static int fill_rows(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_k) {
+int fill_rows(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_k) {
     TBK_CHECK(m->ws_phase.reserve((size_t)plan.row_doubles * sizeof(double)));
     double* d_A = m->ws_phase.as<double>();
     if (plan.rows == HK_ROWS_NONE) return TBK_OK;
@@ -490,7 +490,7 @@ static int fill_rows(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_k)
 }
 
 // H(k) of the chunk whose rows fill_rows made for the same plan
-static int build_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, const double* d_k, const double* d_pos,
+int build_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, const double* d_k, const double* d_pos,
                    double* d_H) {
     const double* d_A = plan.rows == HK_ROWS_NONE ? nullptr : m->ws_phase.as<double>();
     if (plan.path == HK_PATH_CSR)

@@ -313,6 +313,12 @@ struct tbk_hk_plan_t {
 // caller makes the phase rows whatever the path (never HK_ROWS_NONE).
 tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, int64_t nk, bool caller_rows);
 
+// tbk_api.hip: the chunk pipeline's pieces -- k-points per chunk (with_eig: room for the eigensolver's buffers too), the
+// phase rows of a chunk for its plan (in ws_phase), and H(k) of that chunk from those rows (tbk_eigh.hip uses them as well)
+int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig);
+int fill_rows(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_k);
+int build_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, const double* d_k, const double* d_pos, double* d_H);
+
 // tbk_phase.hip
 int tbk_launch_phase_strassen(tbk_model* m, const double* d_k, int64_t nk, double* d_As);
 int tbk_launch_phase(tbk_model* m, const double* d_k, int64_t nk, int64_t nk_pad, double* d_A);
@@ -344,6 +350,9 @@ void tbk_csr_schedule(int ncol, int kt, const std::vector<int64_t>& cptr, const 
 
 // tbk_eig.hip
 int tbk_eig_batched(tbk_model* m, double* d_H, int64_t nk, double* d_E);    // full rocSOLVER zheevd
+
+// tbk_eigh.hip: the checks of the eigh entry points that need no model (convention, pos, nk)
+int tbk_eigh_check_arguments(int64_t nk, int convention, const double* pos);
 
 // tbk_eig_stream.hip
 bool tbk_eig_stream_supported(int n);

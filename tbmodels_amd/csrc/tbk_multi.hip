@@ -99,6 +99,20 @@ extern "C" int tbk_hamilton_multi(tbk_model* const* handles, int n_handles, cons
     });
 }
 
+extern "C" int tbk_eigh_multi(tbk_model* const* handles, int n_handles, const double* k, int64_t nk, int convention,
+                              const double* pos, double* E_out, double* U_out) {
+    TBK_CHECK(tbk_eigh_check_arguments(nk, convention, pos));
+    TBK_CHECK(check_handles(handles, n_handles));
+    if (nk == 0) return TBK_OK;
+    TBK_ARG(k && E_out && U_out, "k / E / U is NULL");
+    const int dim = handles[0]->dim, n_orb = handles[0]->n_orb;
+    const int64_t nn2 = (int64_t)n_orb * n_orb * 2;
+    if (n_handles == 1) return tbk_eigh(handles[0], k, nk, convention, pos, E_out, U_out);
+    return run_slabs(n_handles, nk, [&](int i, int64_t lo, int64_t count) {
+        return tbk_eigh(handles[i], k + lo * dim, count, convention, pos, E_out + lo * n_orb, U_out + lo * nn2);
+    });
+}
+
 // k.p models on several devices (kdotp.py:51-100 has the same two methods as Model): the same slabs, through the k.p
 // entry points of every staged copy
 extern "C" int tbk_kdotp_eigenval_multi(tbk_kdotp* const* handles, int n_handles, const double* k, int64_t nk, double* E_out) {
@@ -119,4 +133,16 @@ extern "C" int tbk_kdotp_hamilton_multi(tbk_kdotp* const* handles, int n_handles
         cores[(size_t)i] = handles[i]->core;
     }
     return tbk_hamilton_multi(cores.data(), n_handles, k, nk, 2, nullptr, H_out);
+}
+
+extern "C" int tbk_kdotp_eigh_multi(tbk_kdotp* const* handles, int n_handles, const double* k, int64_t nk, double* E_out,
+                                    double* U_out) {
+    TBK_CHECK(tbk_eigh_check_arguments(nk, 2, nullptr));
+    TBK_ARG(handles != nullptr && n_handles >= 1, "no handles");
+    std::vector<tbk_model*> cores((size_t)n_handles);
+    for (int i = 0; i < n_handles; ++i) {
+        TBK_ARG(handles[i] != nullptr && handles[i]->core != nullptr, "a handle is NULL");
+        cores[(size_t)i] = handles[i]->core;
+    }
+    return tbk_eigh_multi(cores.data(), n_handles, k, nk, 2, nullptr, E_out, U_out);
 }

@@ -210,6 +210,20 @@ class KdotpModel:
             _lib.check(_lib.lib().tbk_kdotp_eigenval_multi(handles, n_handles, _lib.ptr(k_array), k_array.shape[0], _lib.ptr(out)))
         return out[0] if single else out
 
+    def eigh(self, k):
+        """Eigenvalues and eigenvectors at one k-point or a list of k-points: ``(E, U)`` as in ``Model.eigh``."""
+        dim, size = self._shape()
+        if np.shape(k) == (0,):  # an empty list of k-points
+            k = np.zeros((0, dim))
+        k_array, single = self._k_array(k)
+        eig = _outbuf.empty((k_array.shape[0], size), np.float64)
+        vec = _outbuf.empty((k_array.shape[0], size, size), np.complex128)
+        with self._call_lock:
+            handles, n_handles = self._handle_array()
+            _lib.check(_lib.lib().tbk_kdotp_eigh_multi(handles, n_handles, _lib.ptr(k_array), k_array.shape[0], _lib.ptr(eig),
+                                                       _lib.ptr(vec)))
+        return (eig[0], vec[0]) if single else (eig, vec)
+
     # ------------------------------------------------------------------ HDF5 (``tbmodels.kdotp_model``)
     def to_hdf5(self):
         """
