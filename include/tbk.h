@@ -77,8 +77,11 @@ enum {
     TBK_OPT_TIMING = 3,      /* 1: bracket every kernel with HIP events (tbk_get_timing)   */
     TBK_OPT_FOLD = 4,        /* 0: never fold k lists with long runs of one shared component (grids) into
                               *    lower-dimensional models (default 1; dense models, eigenval only)          */
-    TBK_OPT_STRASSEN = 5     /* 0: dense H(k) of long k chunks as the classical product instead of one Strassen
-                              *    level (default 1; csrc/tbk_hk_dense.hip tbk_hk_plan)                        */
+    TBK_OPT_STRASSEN = 5,    /* 0: dense H(k) of long k chunks as the classical product instead of Strassen's
+                              *    (default 1; csrc/tbk_hk_dense.hip tbk_hk_plan)                              */
+    TBK_OPT_STRASSEN_LEVELS = 6 /* 1 or 2 (default 2): the deepest recursion a chunk may take while TBK_OPT_STRASSEN
+                              *    is on -- two levels need longer chunks than one (tbk_hk_plan); anything else is
+                              *    TBK_ERR_ARGUMENT                                                            */
 };
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -106,8 +109,9 @@ int tbk_model_info(const tbk_model* m, int* device, int* dim, int* n_orb, int64_
 /* Event counters of a handle since its creation (which path the eigenvalue calls took). */
 enum { TBK_CNT_EIGENVAL_CALLS = 0, TBK_CNT_FOLDED_CALLS = 1, TBK_CNT_FOLDED_KPOINTS = 2,
        TBK_CNT_LIBRARY_CALLS = 3, /* eigenvalue calls handed to rocSOLVER (on request, or above the own kernels' range) */
-       TBK_CNT_STRASSEN_LAUNCHES = 4, /* dense H(k) launches of a k chunk that took the Strassen product */
-       TBK_CNT_COUNT = 5 };
+       TBK_CNT_STRASSEN_LAUNCHES = 4, /* dense H(k) launches of a k chunk that took the Strassen product, either depth */
+       TBK_CNT_STRASSEN2_LAUNCHES = 5, /* ... those of them that took two levels */
+       TBK_CNT_COUNT = 6 };
 int tbk_model_counter(tbk_model* m, int counter, int64_t* value);
 
 /* ---- the hot path, host buffers (what Model.hamilton / Model.eigenval call) -------------- */

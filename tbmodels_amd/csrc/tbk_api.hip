@@ -382,7 +382,7 @@ extern "C" void tbk_model_destroy(tbk_model* m) {
     if (m->h_stage) (void)hipHostFree(m->h_stage);
     for (hipStream_t st : streams)
         if (st) (void)hipStreamDestroy(st);
-    void* ptrs[] = {m->d_R, m->d_colmap, m->d_B, m->d_Bs, m->d_cptr, m->d_rec_r, m->d_rec_v, m->d_powers, m->d_sptr, m->d_srec_r, m->d_srec_v};
+    void* ptrs[] = {m->d_R, m->d_colmap, m->d_B, m->d_Bs, m->d_Bs2, m->d_cptr, m->d_rec_r, m->d_rec_v, m->d_powers, m->d_sptr, m->d_srec_r, m->d_srec_v};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     DevBuf* bufs[] = {&m->ws_phase, &m->ws_H, &m->ws_E,   &m->ws_E2,
@@ -412,6 +412,10 @@ extern "C" int tbk_model_set_option(tbk_model* m, int option, int64_t value) {
             return TBK_OK;
         case TBK_OPT_STRASSEN:
             m->strassen = value != 0;
+            return TBK_OK;
+        case TBK_OPT_STRASSEN_LEVELS:
+            TBK_ARG(value == 1 || value == 2, "Strassen levels must be 1 or 2");
+            m->strassen_levels = (int)value;
             return TBK_OK;
         default:
             tbk_set_error("unknown option %d", option);
@@ -465,7 +469,26 @@ int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
     int64_t cap = mid ? 131072 : 32768;
     if (n < 64) cap *= std::min<int64_t>(32, (64 / n) * (64 / n));
     chunk = std::max<int64_t>(TBK_BM, std::min<int64_t>(chunk, cap));
-    if (tbk_hk_plan(m, std::min(chunk, nk), false).path == HK_PATH_STRASSEN) {
+    tbk_hk_plan_t plan = tbk_hk_plan(m, std::min(chunk, nk), false);
+    if (plan.path == HK_PATH_STRASSEN2) {
+        // The first two-level chunk of a model builds the operand blocks of the second level (fill_rows): decided here, where
+        // the memory is counted -- blocks above a quarter of the free memory are skipped, and the model stays on one level.
+        // Such a chunk holds its phase rows 49/16 times (As2[49][K2 / 4][Mq]) and the 49 quarter-size products
+        // P[49][Mq][ncol_pad / 4]; a chunk that does not fit gets shorter, and below TBK_STRASSEN2_MIN_NK it takes one level
+        size_t free2 = free_b;
+        if (m->d_Bs2 == nullptr) {
+            const size_t blocks = tbk_strassen2_bytes(m);
+            if (blocks > free_b / 4) m->bs2_skipped = true;
+            else free2 -= blocks;
+        }
+        if (!m->bs2_skipped) {
+            const int64_t per_k_s = per_k + m->k2 * 8 * 33 / 16 + (int64_t)m->ncol_pad * 16 * 49 / 16;
+            const int64_t fit = (int64_t)(free2 / 4) / per_k_s / TBK_BM * TBK_BM;
+            chunk = std::max<int64_t>(TBK_BM, std::min(chunk, fit));
+        }
+        plan = tbk_hk_plan(m, std::min(chunk, nk), false);
+    }
+    if (plan.path == HK_PATH_STRASSEN) {
         // a Strassen chunk also holds its phase rows 7/4 times (As[7][K2 / 2][Mh]) and the seven half-size products
         // P[7][Mh][ncol_pad / 2] (re, im): that must fit the quarter of the free memory -- else a shorter chunk (classical
         // below TBK_STRASSEN_MIN_NK k-points)
@@ -484,6 +507,10 @@ int fill_rows(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_k) {
     double* d_A = m->ws_phase.as<double>();
     if (plan.rows == HK_ROWS_NONE) return TBK_OK;
     if (plan.rows == HK_ROWS_STRASSEN) return tbk_launch_phase_strassen(m, d_k, plan.nk, d_A);  // the seven blocks of its left operands
+    if (plan.rows == HK_ROWS_STRASSEN2) {
+        TBK_CHECK(tbk_stage_strassen2(m));  // the right operands of the second level, on the model's first two-level chunk
+        return tbk_launch_phase_strassen2(m, d_k, plan.nk, d_A);  // the 49 blocks of its left operands
+    }
     if (plan.rows == HK_ROWS_MONOMIAL)
         return tbk_launch_monomials(m->stream, m->d_powers, m->dim, m->n_r, m->k2, d_k, plan.nk, plan.nk_pad, d_A);
     return tbk_launch_phase(m, d_k, plan.nk, plan.nk_pad, d_A);

@@ -72,7 +72,7 @@ struct HkArgs {
     int splits = 1;
     int unit_grid = 1;
     int64_t p_rows = 0;  // k rows per split in P
-    // Strassen launches (launch_strassen below): split y is product p of the seven of one Strassen level instead of a K
+    // Strassen launches (launch_strassen, launch_strassen2 below): split y is product p of the 7 of one level or the 49 of two instead of a K
     // range -- its operands start at A + p * a_prod_stride and Bt + p * b_prod_stride, it walks the whole (half) K of the
     // launch, and the epilogue parks every element of its tile, padding slots included, for hk_strassen_finish_kernel
     int products = 0;
@@ -612,6 +612,55 @@ __global__ void __launch_bounds__(256) hk_strassen_finish_kernel(const HkArgs a,
     }
 }
 
+// Two levels: one thread per (k' < Mq, e' < ncol_pad / 4) of the quarter-size grid walks the outer products p1 = 1 .. 7.  The seven
+// loads P[7 (p1 - 1) + p2 - 1][k'][e'] finish the four quadrants of M_p1 with the expressions above, and each quadrant goes into
+// the outer C11, C12, C21, C22 of the same expressions -- visited in the natural order of p1 that is the association
+// ((M1 + M4) - M5) + M7, M3 + M5, M2 + M4, ((M1 - M2) + M3) + M6 of the nested form, bit for bit, with 16 x 2 accumulators instead
+// of 49 x 2 live values.  Output quarter 2 a1 + a2 of the k-points, 2 c1 + c2 of the slots (half a1 / c1 of the outer split).
+// Loads are 16 B per thread, contiguous along e'.
+template <int MODE, int CONV>
+__global__ void __launch_bounds__(256) hk_strassen2_finish_kernel(const HkArgs a, int64_t mq) {
+    const int quarter = a.ncol_pad / 4;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int e = (int)(idx % quarter);
+    const int64_t kq = idx / quarter;
+    if (kq >= mq) return;
+    const size_t blk = (size_t)mq * quarter;
+    const d2* mp = reinterpret_cast<const d2*>(a.P) + (size_t)kq * quarter + e;
+    d2 c[2][2][2][2];  // [a1][c1][a2][c2]
+#pragma unroll
+    for (int p1 = 0; p1 < 7; ++p1) {
+        const d2* q = mp + (size_t)(7 * p1) * blk;
+        const d2 m1 = q[0], m2 = q[blk], m3 = q[2 * blk], m4 = q[3 * blk], m5 = q[4 * blk], m6 = q[5 * blk], m7 = q[6 * blk];
+        const d2 in[2][2] = {{((m1 + m4) - m5) + m7, m3 + m5}, {m2 + m4, ((m1 - m2) + m3) + m6}};
+#pragma unroll
+        for (int a2 = 0; a2 < 2; ++a2)
+#pragma unroll
+            for (int c2 = 0; c2 < 2; ++c2) {
+                const d2 v = in[a2][c2];
+                if (p1 == 0) c[0][0][a2][c2] = v, c[1][1][a2][c2] = v;
+                if (p1 == 1) c[1][0][a2][c2] = v, c[1][1][a2][c2] -= v;
+                if (p1 == 2) c[0][1][a2][c2] = v, c[1][1][a2][c2] += v;
+                if (p1 == 3) c[0][0][a2][c2] += v, c[1][0][a2][c2] += v;
+                if (p1 == 4) c[0][0][a2][c2] -= v, c[0][1][a2][c2] += v;
+                if (p1 == 5) c[1][1][a2][c2] += v;
+                if (p1 == 6) c[0][0][a2][c2] += v;
+            }
+    }
+#pragma unroll
+    for (int cq = 0; cq < 4; ++cq) {
+        const int32_t ij = a.colmap[e + cq * quarter];
+        if (ij < 0) continue;
+#pragma unroll
+        for (int aq = 0; aq < 4; ++aq) {
+            const int64_t kout = kq + aq * mq;
+            if (kout >= a.nk) continue;
+            const d2 v = c[aq >> 1][cq >> 1][aq & 1][cq & 1];
+            store_slot<MODE, CONV>(a, kout, ij, v[0], v[1]);
+        }
+    }
+}
+
 // The same for many splits and few k-points (the matrix-vector path: ~100 K slices, one k-point): 16 threads per
 // element, thread j adds splits j, j + 16, ... and the 16 partial sums are combined in a fixed tree -- the one-thread
 // loop was a chain of ~100 dependent loads, 31 us of a 117 us single-k hamilton() call.
@@ -869,6 +918,43 @@ int launch_strassen(tbk_model* m, const HkArgs& a0) {
     return TBK_OK;
 }
 
+// Two levels: the 49 quarter-size products as the units of one launch, as above -- operands from phase_rows_strassen2_kernel
+// (a.A = As2[49][K2 / 4][Mq]) and tbk_stage_strassen2 (m->d_Bs2), the K loop over K2 / 4 rows.
+template <int MODE, int CONV>
+int launch_strassen2(tbk_model* m, const HkArgs& a0) {
+    hipStream_t s = m->stream;
+    const size_t lds = 2 * STAGE_DOUBLES * sizeof(double);
+    static std::atomic<bool> raised[TBK_MAX_DEVICES] = {};
+    TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&hk_dense_kernel<HK_TRI, 2, true>), 160 * 1024, raised));
+    TBK_ARG(m->d_Bs2 != nullptr, "the operand blocks of the second Strassen level are missing");
+    const int64_t mq = tbk_strassen_mq(a0.nk);
+    const int quarter = a0.ncol_pad / 4;
+    HkArgs a = hk_args(m, a0.A, mq, mq, a0.H);
+    a.Bt = m->d_Bs2;
+    a.k2 = m->k2 / 4;
+    a.ncol_pad = quarter;
+    a.nt_count = quarter / TBK_BNP;
+    const int grid = tile_grid(a, (int)(mq / TBK_BM));
+    a.products = 1;
+    a.splits = 49;
+    a.unit_grid = grid;
+    a.p_rows = mq;
+    a.a_prod_stride = a.k2 * mq;
+    a.b_prod_stride = a.k2 * quarter * 2;
+    TBK_CHECK(m->ws_part.reserve((size_t)49 * mq * quarter * 2 * sizeof(double)));
+    a.P = m->ws_part.as<double>();
+    hipLaunchKernelGGL((hk_dense_kernel<HK_TRI, 2, true>), dim3(49 * grid), dim3(256), lds, s, a);
+    TBK_HIP(hipGetLastError());
+    HkArgs f = a0;
+    f.P = a.P;
+    const int64_t threads = mq * quarter;
+    hipLaunchKernelGGL((hk_strassen2_finish_kernel<MODE, CONV>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, f, mq);
+    TBK_HIP(hipGetLastError());
+    m->counters[TBK_CNT_STRASSEN_LAUNCHES] += 1;
+    m->counters[TBK_CNT_STRASSEN2_LAUNCHES] += 1;
+    return TBK_OK;
+}
+
 // K slices of the matrix-vector path: (blocks of 64 packed elements) x (K slices) independent waves, four to a workgroup.
 // The kernel is bound by the bytes a CU pulls, so the workgroups must come out EVEN over the CUs: an operand of up to ~1.5 MB
 // per workgroup slot goes in ONE round of at most two workgroups per CU (`*lds_out` = half a CU's LDS keeps a third one away);
@@ -927,6 +1013,9 @@ void gemv_plan(const tbk_model* m, int64_t nk, int* slices_out, size_t* lds_out)
 // * STRASSEN (launch_strassen): a dense tight-binding model padded and staged for it, with its own operand (not a folded
 //   one), TBK_OPT_STRASSEN on, and a chunk of at least TBK_STRASSEN_MIN_NK k-points that takes neither the matrix-vector path
 //   nor split-K.  Its rows are the seven blocks As[7][K2 / 2][Mh].
+// * STRASSEN2 (launch_strassen2): the same and TBK_OPT_STRASSEN_LEVELS = 2, whole K stages and element tiles in every quarter
+//   of the model's padding, a chunk of at least TBK_STRASSEN2_MIN_NK k-points, and the blocks of the second level built or still
+//   to be tried (tbk_api.hip choose_chunk).  Its rows are the 49 blocks As2[49][K2 / 4][Mq].
 // * TILES: the MFMA tiles.  Small k batches: a workgroup's K loop is a serial chain (1.06 ms at N_R = 4096 whatever the
 //   batch), and fewer tiles than workgroup slots leave CUs idle -- split K into ~1280 units (block x split) so that the
 //   launch fills the chip for two to three rounds; launch() cuts the ragged last round once more.  Partial tiles go to a
@@ -954,6 +1043,13 @@ tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, int64_t nk, bool caller_rows) {
     const int64_t tiles = (nk + TBK_BM - 1) / TBK_BM * (m->ncol_pad / TBK_BNP);
     if (m->strassen && m->d_Bs != nullptr && m->d_B == m->bs_src && !m->kdotp && m->n_r_pad >= TBK_STRASSEN_MIN_NR &&
         nk >= TBK_STRASSEN_MIN_NK && tiles >= 2 * m->n_cu) {
+        if (m->strassen_levels >= 2 && !m->bs2_skipped && nk >= TBK_STRASSEN2_MIN_NK && m->k2 % (4 * TBK_BK) == 0 &&
+            m->ncol_pad % (4 * TBK_BNP) == 0) {
+            p.path = HK_PATH_STRASSEN2;
+            p.rows = HK_ROWS_STRASSEN2;
+            p.row_doubles = 49 * (m->k2 / 4) * tbk_strassen_mq(nk);
+            return p;
+        }
         p.path = HK_PATH_STRASSEN;
         p.rows = HK_ROWS_STRASSEN;
         p.row_doubles = 7 * (m->k2 / 2) * tbk_strassen_mh(nk);
@@ -1009,6 +1105,10 @@ int tbk_launch_hk_dense(tbk_model* m, const tbk_hk_plan_t& p, const double* d_A,
     if (p.path == HK_PATH_STRASSEN) {
         StageTimer t(m, TBK_T_HK);
         return by_mode(mode, convention, [&](auto md, auto cv) { return launch_strassen<md, cv>(m, a); });
+    }
+    if (p.path == HK_PATH_STRASSEN2) {
+        StageTimer t(m, TBK_T_HK);
+        return by_mode(mode, convention, [&](auto md, auto cv) { return launch_strassen2<md, cv>(m, a); });
     }
     if (p.splits > 1) {
         const size_t per_split = (size_t)p.nk_pad * a.ncol_pad * 2 * sizeof(double);

@@ -174,6 +174,11 @@ struct tbk_model {
     // (tbk_stage.hip), built from the staged d_B; bs_src is that d_B (a folded operand swapped in by tbk_fold_enter has none)
     double* d_Bs = nullptr;
     const double* bs_src = nullptr;
+    // --- the 49 right operands of two Strassen levels, Bs2[49][K2 / 4][ncol_pad / 4 / 16][2][16]: the table applied to each block
+    // of d_Bs (valid while d_Bs is).  Built by the first call whose chunks take two levels (tbk_stage_strassen2); bs2_skipped:
+    // they did not fit a quarter of the free memory then, and the model stays on one level
+    double* d_Bs2 = nullptr;
+    bool bs2_skipped = false;
 
     // --- sparse: per packed element, the list of lattice vectors that touch it ---
     int64_t nnz_rec = 0;
@@ -196,7 +201,8 @@ struct tbk_model {
     tbk_fold_plan_t fold[TBK_MAX_DIM];
     bool fold_enabled = true;
     bool strassen = true;  // TBK_OPT_STRASSEN
-    int64_t counters[TBK_CNT_COUNT] = {0, 0, 0, 0, 0};  // tbk_model_counter
+    int strassen_levels = 2;  // TBK_OPT_STRASSEN_LEVELS
+    int64_t counters[TBK_CNT_COUNT] = {0, 0, 0, 0, 0, 0};  // tbk_model_counter
 
     // --- options ---
     int eigensolver = TBK_EIG_AUTO;
@@ -280,9 +286,15 @@ enum HkMode { HK_TRI = 0, HK_FULL = 1 };
 // TBK_STRASSEN_MIN_NR padded lattice vectors are padded for it (n_r_pad a multiple of 16, ncol_pad of 128) and get the
 // operand blocks d_Bs; k chunks of at least TBK_STRASSEN_MIN_NK k-points on the direct MFMA path then take it (tbk_hk_plan).
 constexpr int64_t TBK_STRASSEN_MIN_NR = 1024;
-constexpr int64_t TBK_STRASSEN_MIN_NK = 8192;
+constexpr int64_t TBK_STRASSEN_MIN_NK = 4096;
 inline bool tbk_strassen_model(bool sparse, bool kdotp, int64_t n_r) { return !sparse && !kdotp && n_r >= TBK_STRASSEN_MIN_NR; }
 inline int64_t tbk_strassen_mh(int64_t nk) { return (((nk + 1) / 2) + TBK_BM - 1) / TBK_BM * TBK_BM; }  // k rows per half
+// Two levels: the table applied to each of its seven products, 49 products of quarter size.  For models whose padding gives
+// whole K stages and whole element tiles in every QUARTER (k2 a multiple of 4 TBK_BK, ncol_pad of 4 TBK_BNP -- no model is padded
+// further for it) and chunks of at least TBK_STRASSEN2_MIN_NK k-points; shorter chunks keep one level.  Both thresholds are the
+// lower ends of the measured ranges (DESIGN_LOG.md R8.2): the deeper path won at every length tried.
+constexpr int64_t TBK_STRASSEN2_MIN_NK = 8192;
+inline int64_t tbk_strassen_mq(int64_t nk) { return (((nk + 3) / 4) + TBK_BM - 1) / TBK_BM * TBK_BM; }  // k rows per quarter
 
 // How the H(k) of one chunk of k-points is computed: the contraction path and the rows it reads.  tbk_hk_plan
 // (tbk_hk_dense.hip) is the only place that chooses them; the phase rows of a chunk (tbk_api.hip fill_rows) and its
@@ -292,6 +304,7 @@ enum HkPath {
     HK_PATH_TINY,      // one k-point of a small model in one launch (hk_tiny_kernel)
     HK_PATH_GEMV,      // the matrix-vector kernel (hk_gemv_kernel), `splits` K slices
     HK_PATH_STRASSEN,  // one Strassen level on the MFMA tiles (launch_strassen)
+    HK_PATH_STRASSEN2, // two Strassen levels (launch_strassen2)
     HK_PATH_TILES,     // the MFMA tiles, split along K `splits` ways (1: not split)
 };
 enum HkRows {
@@ -299,6 +312,7 @@ enum HkRows {
     HK_ROWS_PHASE,     // A[K2][nk_pad] cos / sin rows
     HK_ROWS_MONOMIAL,  // A[K2][nk_pad] k.p monomials
     HK_ROWS_STRASSEN,  // the seven blocks As[7][K2 / 2][Mh]
+    HK_ROWS_STRASSEN2, // the 49 blocks As2[49][K2 / 4][Mq]
 };
 struct tbk_hk_plan_t {
     HkPath path = HK_PATH_TILES;
@@ -321,6 +335,7 @@ int build_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, c
 
 // tbk_phase.hip
 int tbk_launch_phase_strassen(tbk_model* m, const double* d_k, int64_t nk, double* d_As);
+int tbk_launch_phase_strassen2(tbk_model* m, const double* d_k, int64_t nk, double* d_As2);
 int tbk_launch_phase(tbk_model* m, const double* d_k, int64_t nk, int64_t nk_pad, double* d_A);
 int tbk_launch_orbital_phases(tbk_model* m, const double* d_k, const double* d_pos, int64_t nk, double* d_orb);
 int tbk_launch_monomials(hipStream_t s, const int32_t* d_powers, int dim, int64_t n_p,
@@ -331,6 +346,8 @@ int tbk_launch_monomials(hipStream_t s, const int32_t* d_powers, int dim, int64_
 int tbk_stage_dense(tbk_model* m, const double* d_hop_raw);
 int tbk_stage_kdotp(tbk_model* m, const double* d_coeff_raw);
 int tbk_stage_strassen(tbk_model* m);
+size_t tbk_strassen2_bytes(const tbk_model* m);
+int tbk_stage_strassen2(tbk_model* m);  // builds d_Bs2 from d_Bs if it is missing
 
 // tbk_hk_dense.hip: the H(k) of plan.nk k-points along plan.path (not HK_PATH_CSR); d_A holds the plan's rows
 int tbk_launch_hk_dense(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_A, int mode, int convention,

@@ -36,6 +36,17 @@ phase_rows_kernel(const double* __restrict__ k, const int32_t* __restrict__ R, i
     A[(2 * r + 1) * nk_pad + kidx] = s;
 }
 
+// The table of the left operands of one Strassen level (below), applied to quadrants v[k half][K half]
+__device__ __forceinline__ void strassen_left(const double (&v)[2][2], double (&out)[7]) {
+    out[0] = v[0][0] + v[1][1];
+    out[1] = v[1][0] + v[1][1];
+    out[2] = v[0][0];
+    out[3] = v[1][1];
+    out[4] = v[0][0] + v[0][1];
+    out[5] = v[1][0] - v[0][0];
+    out[6] = v[0][1] - v[1][1];
+}
+
 // The left operands of one Strassen level (tbk_hk_dense.hip).  P = A^T split into halves: k-points
 // [0, Mh) | [Mh, 2 Mh), lattice vectors [0, n_r_pad / 2) | the rest; P_ab is k-half a x K-half b.  One thread per
 // (k' < Mh, r' < n_r_pad / 2) forms the four quadrant phases with the arithmetic of phase_rows_kernel (k-points past nk and
@@ -65,15 +76,59 @@ phase_rows_strassen_kernel(const double* __restrict__ k, const int32_t* __restri
     const size_t blk = (size_t)2 * rh * mh;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {  // cos row 2r', sin row 2r' + 1
-        const double(&v)[2][2] = t == 0 ? c : s;
         double* row = As + (size_t)(2 * r + t) * mh + kq;
-        row[0 * blk] = v[0][0] + v[1][1];
-        row[1 * blk] = v[1][0] + v[1][1];
-        row[2 * blk] = v[0][0];
-        row[3 * blk] = v[1][1];
-        row[4 * blk] = v[0][0] + v[0][1];
-        row[5 * blk] = v[1][0] - v[0][0];
-        row[6 * blk] = v[0][1] - v[1][1];
+        double out[7];
+        strassen_left(t == 0 ? c : s, out);
+#pragma unroll
+        for (int p = 0; p < 7; ++p) row[p * blk] = out[p];
+    }
+}
+
+// Two levels: the table applied to each of its seven operands.  k-points and lattice vectors in QUARTERS (quarter 2 a1 + a2:
+// half a1 of the outer split, half a2 of the inner one); one thread per (k' < Mq, r' < n_r_pad / 4) forms the 16 quadrant phases
+// (padding k-points and lattice vectors: cos = sin = 0), the seven outer operands quadrant by quadrant, and of each the seven
+// inner ones: As2[7 p1 + p2][K2 / 4][Mq], k contiguous -- 98 coalesced row segments per wave.  HBM-write bound.
+__global__ void __launch_bounds__(256)
+phase_rows_strassen2_kernel(const double* __restrict__ k, const int32_t* __restrict__ R, int dim, int64_t nk, int64_t mq,
+                            int64_t n_r, int64_t rq, double* __restrict__ As2) {
+    const int64_t kq = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t r = blockIdx.y;
+    if (kq >= mq) return;
+    double cs[2][4][4];  // [cos | sin][k quarter][K quarter]
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int64_t kidx = kq + a * mq, rr = r + b * rq;
+            double c = 0.0, s = 0.0;
+            if (kidx < nk && rr < n_r) {
+                double dot = 0.0;
+                for (int d = 0; d < dim; ++d) dot = fma(k[kidx * dim + d], (double)R[rr * dim + d], dot);
+                sincospi(2.0 * dot, &s, &c);
+            }
+            cs[0][a][b] = c;
+            cs[1][a][b] = s;
+        }
+    const size_t blk = (size_t)2 * rq * mq;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {  // cos row 2r', sin row 2r' + 1
+        double* row = As2 + (size_t)(2 * r + t) * mq + kq;
+        double outer[2][2][7];  // [inner k half][inner K half][p1]
+#pragma unroll
+        for (int a2 = 0; a2 < 2; ++a2)
+#pragma unroll
+            for (int b2 = 0; b2 < 2; ++b2) {
+                const double v[2][2] = {{cs[t][a2][b2], cs[t][a2][2 + b2]}, {cs[t][2 + a2][b2], cs[t][2 + a2][2 + b2]}};
+                strassen_left(v, outer[a2][b2]);
+            }
+#pragma unroll
+        for (int p1 = 0; p1 < 7; ++p1) {
+            const double v[2][2] = {{outer[0][0][p1], outer[0][1][p1]}, {outer[1][0][p1], outer[1][1][p1]}};
+            double inner[7];
+            strassen_left(v, inner);
+#pragma unroll
+            for (int p2 = 0; p2 < 7; ++p2) row[(size_t)(7 * p1 + p2) * blk] = inner[p2];
+        }
     }
 }
 
@@ -141,6 +196,15 @@ int tbk_launch_phase_strassen(tbk_model* m, const double* d_k, int64_t nk, doubl
     StageTimer t(m, TBK_T_PHASE);
     dim3 grid((unsigned)((mh + 255) / 256), (unsigned)rh);
     hipLaunchKernelGGL(phase_rows_strassen_kernel, grid, dim3(256), 0, m->stream, d_k, m->d_R, m->dim, nk, mh, m->n_r, rh, d_As);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+int tbk_launch_phase_strassen2(tbk_model* m, const double* d_k, int64_t nk, double* d_As2) {
+    const int64_t mq = tbk_strassen_mq(nk), rq = m->n_r_pad / 4;
+    StageTimer t(m, TBK_T_PHASE);
+    dim3 grid((unsigned)((mq + 255) / 256), (unsigned)rq);
+    hipLaunchKernelGGL(phase_rows_strassen2_kernel, grid, dim3(256), 0, m->stream, d_k, m->d_R, m->dim, nk, mq, m->n_r, rq, d_As2);
     TBK_HIP(hipGetLastError());
     return TBK_OK;
 }

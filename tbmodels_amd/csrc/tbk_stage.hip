@@ -123,6 +123,29 @@ int tbk_stage_strassen(tbk_model* m) {
     return TBK_OK;
 }
 
+// The blocks of the second level: Bs2[7 p1 + p2] is the table applied to the quadrants of Bs[p1] -- K halves of K2 / 4 rows, slot
+// halves of ncol_pad / 4 slots, contiguous in every row like the halves of Bt -- i.e. stage_strassen_kernel on each of the seven
+// blocks: the inner table applied to the outer table's operands, every sum in a fixed order.  49/16 of Bt, not built with the
+// model: most models never run a chunk long enough to read them (choose_chunk decides, fill_rows calls this).
+size_t tbk_strassen2_bytes(const tbk_model* m) { return (size_t)49 * (m->k2 / 4) * (m->ncol_pad / 2) * sizeof(double); }
+
+int tbk_stage_strassen2(tbk_model* m) {
+    if (m->d_Bs2 != nullptr) return TBK_OK;
+    TBK_ARG(m->d_Bs != nullptr && m->k2 % (4 * TBK_BK) == 0 && m->ncol_pad % (4 * TBK_BNP) == 0, "model is not staged for two Strassen levels");
+    const int64_t kq = m->k2 / 4;
+    const int half = m->ncol_pad / 2;
+    const size_t bytes = tbk_strassen2_bytes(m);
+    TBK_HIP(hipMalloc((void**)&m->d_Bs2, bytes));
+    m->staged_bytes += (int64_t)bytes;
+    const size_t blk1 = (size_t)2 * kq * m->ncol_pad, blk2 = (size_t)kq * half;  // doubles per block of Bs, of Bs2
+    for (int p1 = 0; p1 < 7; ++p1) {
+        dim3 grid((half + 255) / 256, (unsigned)kq);
+        hipLaunchKernelGGL(stage_strassen_kernel, grid, dim3(256), 0, m->stream, m->d_Bs + p1 * blk1, kq, half, m->d_Bs2 + 7 * p1 * blk2);
+        TBK_HIP(hipGetLastError());
+    }
+    return TBK_OK;
+}
+
 int tbk_stage_dense(tbk_model* m, const double* d_hop_raw) {
     const size_t bytes = (size_t)m->k2 * m->ncol_pad * 2 * sizeof(double);
     if (bytes == 0) return TBK_OK;
