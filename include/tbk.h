@@ -65,7 +65,7 @@ typedef enum tbk_status {
  * bisection on Sturm counts otherwise (n_orb > 64, calls of <= max(4096, 768 n_orb) k-points, and the last
  * chunk of a call).  Both are backward stable; they agree to rounding, so eigenvalues are reproducible run to
  * run but depend on the batch size at the 1e-13 level.  The same holds for the reduction above 128 orbitals: calls of
- * a few matrices take wider kernels / a chain of launches (tbk_eig_band.hip: tbk_band_split, `wide`) whose partial sums
+ * a few matrices take wider kernels / a chain of launches (tbk_eig_plan.hip: the plan's `chain`, `wide`) whose partial sums
  * differ from the one-workgroup kernels' in the last bit.  Bitwise reproducibility is therefore a property of a CALL SHAPE:
  * the same k list on the same number of devices / ranks (tbk_eigenval_multi and ShardedEigenval cut it into
  * ceil(nk / n) slabs, and every slab chooses its kernels by ITS size) gives the same bits every time; the same list on a

@@ -1,6 +1,8 @@
 // tbk_api.hip -- the C ABI of include/tbk.h: staging, the chunked k pipeline, host/device entry
-// points.  Kernels live in tbk_phase.hip / tbk_stage.hip / tbk_hk_dense.hip / tbk_hk_csr.hip /
-// tbk_eig.hip; this file only owns memory, streams and ordering.
+// points.  Kernels live in tbk_phase.hip / tbk_stage.hip / tbk_hk_dense.hip / tbk_hk_csr.hip, the
+// eigensolver's in tbk_eig_small.hip / tbk_eig_stream.hip / tbk_eig_band*.hip (tbk_eig.hip: the rocSOLVER
+// path), and which of them a call takes is tbk_eig_plan's (tbk_eig_plan.hip); this file only owns memory,
+// streams and ordering.
 
 #include <algorithm>
 #include <cmath>
@@ -556,9 +558,8 @@ extern "C" int tbk_hamilton_device(tbk_model* m, const double* d_k, int64_t nk, 
     return TBK_OK;
 }
 
-// Eigenvalues with the hand-written solvers (register-resident reduction for n_orb <= 64, blocked streaming
-// reduction up to 512), software-pipelined over k chunks on
-// three streams:   main: phase(c) -> H(c)      eig: tridiag(c)      ql: QL(c - 1)
+// Eigenvalues with the hand-written solvers (the reduction family of the call's tbk_eig_plan), software-pipelined over k
+// chunks on three streams:   main: phase(c) -> H(c)      eig: tridiag(c)      ql: QL(c - 1)
 //
 //     | H(c) | tridiag(c) || QL(c-1) | H(c+1) | tridiag(c+1) || QL(c) | ...
 //
@@ -566,27 +567,16 @@ extern "C" int tbk_hamilton_device(tbk_model* m, const double* d_k, int64_t nk, 
 // it only displaces its workgroups.  The two eigensolver kernels are complementary -- the reduction is
 // VALU-bound with 14 KiB of LDS per workgroup, the QL is a latency-bound serial chain with 64 KiB per
 // workgroup and almost no issue pressure -- so QL(c-1) runs in the shadow of tridiag(c).
-// tridiagonal stage on the QL stream: lane-per-matrix QL up to 64 orbitals, bisection above
-// Calls of at most max(4096, 768 n) k-points take the bisection kernel for every chunk: the lane-per-matrix QL
-// is a serial chain of ~n^2 rotations (1.6 ms at n = 64 however few matrices there are) that only pays when tens of
-// thousands of matrices share it and it can hide under the next chunk's reduction; bisection spends a wave per
-// matrix (VALU work ~ n per matrix) and got ~1.7x faster with the secant steps of tbk_eig_stream.hip.  Measured
-// crossover (ms per call, QL vs bisection): n = 64, N_R = 4096: 49152 k-points 57.29 vs
-// 56.84, 57344: 66.71 vs 66.82, 100000: 114.4 vs 115.5; n = 48, N_R = 512: 30000: 5.94 vs 5.79, 40000: 7.55 vs 7.81;
-// n = 32, N_R = 256: 16384: 1.45 vs 1.42, 24576: 1.84 vs 1.87.  (The rule was 640 n in round 1 and 384 n between the
-// free-running QL and the faster bisection.)
-constexpr int64_t TBK_SMALL_CALL = 4096;
-constexpr int64_t TBK_SMALL_CALL_PER_ORBITAL = 768;
-// (Up to 12 orbitals the QL chain used to be the shorter one -- 61 us at n = 8 -- until small matrices got the idle
-// lanes of their wave for multisection: 1000 silicon k-points 59 -> 20 us, so small calls bisect at every size now.)
-
-static int launch_tridiag_eigenvalues(tbk_model* m, hipStream_t s, double* d_de, int64_t nk, double* d_E,
-                                      bool beside_ql = false, bool small_call = false, const void* d_band = nullptr) {
+// tridiagonal stage on the QL stream: lane-per-matrix QL or bisection, as the plan says.  Per launch, not in the plan:
+// `beside_ql` (tbk_launch_ql), `bisect_anyway` (the last chunk of a pipeline has no reduction to hide a QL chain behind), and
+// d_band (the second stage of this chunk runs here first)
+static int launch_tridiag_eigenvalues(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, double* d_de, int64_t nk, double* d_E,
+                                      bool beside_ql = false, bool bisect_anyway = false, const void* d_band = nullptr) {
     // two-stage reduction: the second stage (band -> tridiagonal) of this chunk runs here, in front of its bisection --
     // on the tridiagonal stream, i.e. next to the first stage of the following chunk
-    if (d_band) TBK_CHECK(tbk_launch_band_chase(m, s, d_band, nk, d_de));
-    if (tbk_eig_small_supported(m->n_orb) && !small_call) return tbk_launch_ql(m, s, d_de, nk, d_E, beside_ql);
-    return tbk_launch_bisect(m, s, d_de, nk, d_E);
+    if (d_band) TBK_CHECK(tbk_launch_band_chase(m, plan, s, d_band, nk, d_de));
+    if (!plan.bisect && !bisect_anyway) return tbk_launch_ql(m, s, d_de, nk, d_E, beside_ql);
+    return tbk_launch_bisect(m, plan, s, d_de, nk, d_E);
 }
 
 // k chunks of the pipeline.  The lane-per-matrix QL is a latency chain (~3 ms however few matrices it
@@ -639,8 +629,8 @@ static std::vector<int64_t> run_schedule(const std::vector<int64_t>& runs, int64
     return out;
 }
 
-static int eigenval_wave_pipeline(tbk_model* m, const double* d_k, int64_t nk, double* d_E, const HBuilder* builder = nullptr,
-                                  const std::vector<int64_t>* runs = nullptr) {
+static int eigenval_wave_pipeline(tbk_model* m, const tbk_eig_plan_t& plan, const double* d_k, int64_t nk, double* d_E,
+                                  const HBuilder* builder = nullptr, const std::vector<int64_t>* runs = nullptr) {
     // The direct builder in two halves: the phase rows of a chunk only need the previous contraction to be done with the
     // row buffer (stream order), not the eigensolver to be done with H -- so they are enqueued BEFORE the main stream
     // waits for the previous chunk's reduction and run under it (an HBM-write kernel beside a VALU-bound one: 1.5 ms
@@ -666,8 +656,6 @@ static int eigenval_wave_pipeline(tbk_model* m, const double* d_k, int64_t nk, d
         (runs != nullptr && m->k_chunk == 0 && nk > chunk) ? run_schedule(*runs, chunk) : chunk_schedule(m, nk, chunk);
     const int64_t n_chunks = (int64_t)sched.size();
     const int64_t max_chunk = *std::max_element(sched.begin(), sched.end());
-    // a property of the call, not of its chunking: TBK_OPT_K_CHUNK must not change the results
-    const bool small_call = nk <= std::max<int64_t>(TBK_SMALL_CALL, TBK_SMALL_CALL_PER_ORBITAL * (int64_t)m->n_orb);
     TBK_CHECK(m->ws_H.reserve((size_t)max_chunk * nn2 * sizeof(double)));
     for (int b = 0; b < (n_chunks > 1 ? 2 : 1); ++b)
         TBK_CHECK(debuf[b]->reserve((size_t)max_chunk * n * 2 * sizeof(double)));
@@ -678,30 +666,24 @@ static int eigenval_wave_pipeline(tbk_model* m, const double* d_k, int64_t nk, d
     // Round 4, MEASURED AND LEFT OFF (DESIGN_LOG.md R4.15): the same for the direct H(k) of the two-stage sizes (from 185
     // orbitals) -- that reduction is a chain of short phases which leaves the matrix pipe idle four fifths of the time, and
     // the sparse H(k) is an HBM-write kernel.  There: one after the other (the round-3 order).
-    const bool h_overlap = n_chunks > 2 && builder != nullptr && tbk_eig_small_supported(m->n_orb);
+    const bool h_overlap = n_chunks > 2 && builder != nullptr && plan.family == EIG_REGISTER;
     double* d_Hbuf[2] = {d_H, d_H};
     if (h_overlap) {
         TBK_CHECK(m->ws_H2.reserve((size_t)max_chunk * nn2 * sizeof(double)));
         d_Hbuf[1] = m->ws_H2.as<double>();
     }
     // two-stage reduction in two launches (above 256 orbitals): stage two of a chunk goes to the tridiagonal stream; fused
-    // (up to 256) it is part of the reduction kernel and this flag stays off
-    const bool two_stage = !tbk_eig_small_supported(m->n_orb) && tbk_eig_two_stage(m) && n_chunks > 1 && !tbk_band_fused(m->n_orb);
-    if (two_stage) {
-        TBK_CHECK(m->ws_band.reserve((size_t)max_chunk * tbk_band_scratch_per_matrix(m->n_orb)));
-        for (int b = 0; b < 2; ++b) TBK_CHECK(m->ws_bandmat[b].reserve((size_t)max_chunk * tbk_band_bytes_per_matrix(m->n_orb)));
-        TBK_CHECK(tbk_band_xl_reserve(m, max_chunk));
-    }
+    // (up to 256) it is part of the reduction kernel and this flag stays off.  (Of the launch, not of the plan: one chunk has
+    // no following chunk to run beside.)
+    const bool two_stage = plan.family == EIG_TWO_STAGE && !plan.fused && n_chunks > 1;
+    TBK_CHECK(tbk_eig_reserve(m, plan, max_chunk, n_chunks > 1 ? 2 : 1));
     if (n_chunks == 1) {
         // one chunk has nothing to overlap: everything in order on the main stream, no cross-stream events (they
         // cost more than the kernels of a single-k call)
         double* d_de = debuf[0]->as<double>();
         TBK_CHECK(build(0, nk, d_H));
-        if (tbk_eig_small_supported(m->n_orb))
-            TBK_CHECK(tbk_launch_tridiag(m, m->stream, d_H, nk, d_de));
-        else
-            TBK_CHECK(tbk_launch_tridiag_stream(m, m->stream, d_H, nk, d_de));
-        TBK_CHECK(launch_tridiag_eigenvalues(m, m->stream, d_de, nk, d_E, false, small_call));
+        TBK_CHECK(tbk_eig_reduce(m, plan, m->stream, d_H, nk, d_de));
+        TBK_CHECK(launch_tridiag_eigenvalues(m, plan, m->stream, d_de, nk, d_E));
         if (m->chunk_done) {
             TBK_HIP(hipEventRecord(m->ev_ql[0], m->stream));
             TBK_CHECK(m->chunk_done(0, nk, m->ev_ql[0]));
@@ -730,20 +712,15 @@ static int eigenval_wave_pipeline(tbk_model* m, const double* d_k, int64_t nk, d
 
         TBK_HIP(hipStreamWaitEvent(m->stream_eig, m->ev_hk[b], 0));
         if (c >= 2 && h_overlap) TBK_HIP(hipStreamWaitEvent(m->stream_eig, m->ev_ql[b], 0));
-        if (tbk_eig_small_supported(m->n_orb))
-            TBK_CHECK(tbk_launch_tridiag(m, m->stream_eig, d_H, nkc, d_de));
-        else if (two_stage)
-            TBK_CHECK(tbk_launch_band_reduce(m, m->stream_eig, d_H, nkc, m->ws_band.ptr, m->ws_bandmat[b].ptr));
-        else
-            TBK_CHECK(tbk_launch_tridiag_stream(m, m->stream_eig, d_H, nkc, d_de));
+        TBK_CHECK(tbk_eig_reduce(m, plan, m->stream_eig, d_H, nkc, d_de, two_stage ? m->ws_bandmat[b].ptr : nullptr));
         TBK_HIP(hipEventRecord(m->ev_tri[b], m->stream_eig));
 
         if (c >= 1) {  // tridiagonal stage of the previous chunk, alongside this chunk's reduction
             TBK_HIP(hipStreamWaitEvent(m->stream_ql, m->ev_hk[b], 0));
             // (d, e) of the previous chunk: implied by ev_hk unless H(c) was built beside that reduction
             if (h_overlap) TBK_HIP(hipStreamWaitEvent(m->stream_ql, m->ev_tri[b ^ 1], 0));
-            TBK_CHECK(launch_tridiag_eigenvalues(m, m->stream_ql, debuf[b ^ 1]->as<double>(), prev_nkc,
-                                                 d_E + (size_t)prev_c0 * n, false, small_call,
+            TBK_CHECK(launch_tridiag_eigenvalues(m, plan, m->stream_ql, debuf[b ^ 1]->as<double>(), prev_nkc,
+                                                 d_E + (size_t)prev_c0 * n, false, false,
                                                  two_stage ? m->ws_bandmat[b ^ 1].ptr : nullptr));
             TBK_HIP(hipEventRecord(m->ev_ql[b ^ 1], m->stream_ql));
             if (m->chunk_done) TBK_CHECK(m->chunk_done(prev_c0, prev_nkc, m->ev_ql[b ^ 1]));
@@ -756,9 +733,8 @@ static int eigenval_wave_pipeline(tbk_model* m, const double* d_k, int64_t nk, d
        // Nothing is left to hide a 2.7 ms QL chain behind: the (short) last chunk takes the bisection kernel,
        // a wave per matrix for ~0.1 ms (measured: 2.6 ms off the 100k step).
         const int b = (int)((n_chunks - 1) & 1);
-        TBK_CHECK(launch_tridiag_eigenvalues(m, m->stream_eig, debuf[b]->as<double>(), prev_nkc,
-                                             d_E + (size_t)prev_c0 * n, n_chunks > 1,
-                                             small_call || n_chunks > 1, two_stage ? m->ws_bandmat[b].ptr : nullptr));
+        TBK_CHECK(launch_tridiag_eigenvalues(m, plan, m->stream_eig, debuf[b]->as<double>(), prev_nkc,
+                                             d_E + (size_t)prev_c0 * n, true, true, two_stage ? m->ws_bandmat[b].ptr : nullptr));
         TBK_HIP(hipEventRecord(m->ev_ql[b], m->stream_eig));
         if (m->chunk_done) TBK_CHECK(m->chunk_done(prev_c0, prev_nkc, m->ev_ql[b]));
     }
@@ -771,7 +747,8 @@ static int eigenval_wave_pipeline(tbk_model* m, const double* d_k, int64_t nk, d
 // k lists with long runs of one shared component (grids in meshgrid order, stacks of planes): every run is
 // evaluated on the model folded along that component (tbk_fold.hip).  Returns TBK_OK with *done = false when the
 // list does not qualify.
-static int eigenval_folded(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, double* d_E, bool* done) {
+static int eigenval_folded(tbk_model* m, const tbk_eig_plan_t& eig_plan, const double* d_k, const double* h_k, int64_t nk, double* d_E,
+                           bool* done) {
     *done = false;
     if (!m->fold_enabled || m->sparse || m->kdotp || m->dim < 2 || m->n_r < 64 || nk < 1024) return TBK_OK;
     // Device-resident lists are never read back (include/tbk.h: the device entry points enqueue and return): the run
@@ -877,11 +854,6 @@ static int eigenval_folded(tbk_model* m, const double* d_k, const double* h_k, i
         return rc;
     };
 
-    // Second level (meshes): inside a plane the k-points come in LINES -- equal-length sub-runs of one more shared
-    // component whose remaining coordinates repeat from line to line.  Every line is a (dim - 2)-dimensional model
-    // (13 instead of 313 lattice vectors at the headline shape); all lines of the piece go through ONE launch with
-    // per-line operands and shared phase rows (tbk_launch_hk_dense_lines).  Ragged ends of the piece, and anything
-    // that does not have this structure, take piece_plane.
     auto piece = [&](int64_t lo, int64_t hi, double* d_Hp) -> int {
         const LineInfo li = analyse(lo, hi);
         if (!li.ok) return piece_plane(lo, hi, d_Hp);
@@ -979,57 +951,10 @@ static int eigenval_folded(tbk_model* m, const double* d_k, const double* h_k, i
         }
         return TBK_OK;
     };
-    TBK_CHECK(eigenval_wave_pipeline(m, d_k, nk, d_E, &folded, &runs));
+    TBK_CHECK(eigenval_wave_pipeline(m, eig_plan, d_k, nk, d_E, &folded, &runs));
     m->counters[TBK_CNT_FOLDED_CALLS] += 1;
     m->counters[TBK_CNT_FOLDED_KPOINTS] += nk;
     *done = true;
-    return TBK_OK;
-}
-
-// the call takes the library's own reduction kernels (the chunk pipeline), not rocSOLVER
-static bool eigenval_own_solvers(const tbk_model* m) {
-    return m->eigensolver != TBK_EIG_ROCSOLVER &&
-           (tbk_eig_small_supported(m->n_orb) || (m->eigensolver == TBK_EIG_AUTO && tbk_eig_stream_supported(m->n_orb)));
-}
-
-static int eigenval_device_solve(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, double* d_E) {
-    TBK_ARG(m != nullptr, "model is NULL");
-    TBK_LOCK(m);
-    TBK_ARG(nk >= 0, "nk < 0");
-    if (nk == 0) return TBK_OK;
-    TBK_ARG(d_k && d_E, "k / E is NULL");
-    TBK_HIP(hipSetDevice(m->device));
-    m->call_nk = nk;
-    m->counters[TBK_CNT_EIGENVAL_CALLS] += 1;
-    if (m->eigensolver == TBK_EIG_WAVE && !tbk_eig_small_supported(m->n_orb)) {
-        tbk_set_error("TBK_EIG_WAVE handles n_orb <= 64 only (n_orb = %d)", m->n_orb);
-        return TBK_ERR_ARGUMENT;
-    }
-    if (eigenval_own_solvers(m)) {
-        bool done = false;
-        TBK_CHECK(eigenval_folded(m, d_k, h_k, nk, d_E, &done));
-        if (done) return TBK_OK;
-        return eigenval_wave_pipeline(m, d_k, nk, d_E);
-    }
-
-    int64_t chunk = choose_chunk(m, nk, true);
-    const size_t nn2 = (size_t)m->n_orb * m->n_orb * 2;
-    // rocsolver_zheevd_strided_batched faulted (memory access fault inside the library) on 2048 matrices of 768 / 1024
-    // orbitals -- 1.2e9 / 2.1e9 complex elements in one call -- and ran 2048 x 640 (8.4e8): calls are kept below 2^29
-    // elements
-    chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t(1) << 29) / std::max<int64_t>(1, (int64_t)m->n_orb * m->n_orb)));
-    // rocSOLVER path: TBK_EIG_ROCSOLVER, or n_orb above the own solvers' range
-    m->counters[TBK_CNT_LIBRARY_CALLS] += 1;
-    for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
-        const int64_t nkc = std::min(chunk, nk - c0);
-        const tbk_hk_plan_t plan = tbk_hk_plan(m, nkc, true);
-        const double* kc = d_k + c0 * m->dim;
-        TBK_CHECK(fill_rows(m, plan, kc));
-        TBK_CHECK(m->ws_H.reserve((size_t)nkc * nn2 * sizeof(double)));
-        double* d_H = m->ws_H.as<double>();
-        TBK_CHECK(build_h(m, plan, HK_TRI, 2, kc, nullptr, d_H));
-        TBK_CHECK(tbk_eig_batched(m, d_H, nkc, d_E + (size_t)c0 * m->n_orb));
-    }
     return TBK_OK;
 }
 
@@ -1043,12 +968,44 @@ __global__ void __launch_bounds__(256) flag_nonfinite_kernel(const double* __res
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicAdd(flag, 1);
 }
 
-static int eigenval_device_impl(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, double* d_E) {
-    TBK_CHECK(eigenval_device_solve(m, d_k, h_k, nk, d_E));
-    // the wave solvers raise the flag themselves (QL and bisection see every non-finite (d, e) and answer NaN);
-    // rocSOLVER's eigenvalues get the pass over the output
-    const bool own_solvers = m != nullptr && eigenval_own_solvers(m);
-    if (nk > 0 && m != nullptr && !own_solvers) {
+// plan: tbk_eig_plan of this call, made once by the entry point; everything below reads it
+static int eigenval_device_impl(tbk_model* m, const tbk_eig_plan_t& plan, const double* d_k, const double* h_k, int64_t nk, double* d_E) {
+    TBK_ARG(m != nullptr, "model is NULL");
+    TBK_LOCK(m);
+    TBK_ARG(nk >= 0, "nk < 0");
+    if (nk == 0) return TBK_OK;
+    TBK_ARG(d_k && d_E, "k / E is NULL");
+    TBK_HIP(hipSetDevice(m->device));
+    m->counters[TBK_CNT_EIGENVAL_CALLS] += 1;
+    TBK_CHECK(tbk_eig_check_option(m));
+    // the library's own reduction kernels (the chunk pipeline), not rocSOLVER.  They raise the flag themselves (QL and
+    // bisection see every non-finite (d, e) and answer NaN); rocSOLVER's eigenvalues get the pass over the output
+    if (plan.own()) {
+        bool done = false;
+        TBK_CHECK(eigenval_folded(m, plan, d_k, h_k, nk, d_E, &done));
+        if (done) return TBK_OK;
+        return eigenval_wave_pipeline(m, plan, d_k, nk, d_E);
+    }
+
+    int64_t chunk = choose_chunk(m, nk, true);
+    const size_t nn2 = (size_t)m->n_orb * m->n_orb * 2;
+    // rocsolver_zheevd_strided_batched faulted (memory access fault inside the library) on 2048 matrices of 768 / 1024
+    // orbitals -- 1.2e9 / 2.1e9 complex elements in one call -- and ran 2048 x 640 (8.4e8): calls are kept below 2^29
+    // elements
+    chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t(1) << 29) / std::max<int64_t>(1, (int64_t)m->n_orb * m->n_orb)));
+    // rocSOLVER path: TBK_EIG_ROCSOLVER, or n_orb above the own solvers' range
+    m->counters[TBK_CNT_LIBRARY_CALLS] += 1;
+    for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
+        const int64_t nkc = std::min(chunk, nk - c0);
+        const tbk_hk_plan_t hk = tbk_hk_plan(m, nkc, true);
+        const double* kc = d_k + c0 * m->dim;
+        TBK_CHECK(fill_rows(m, hk, kc));
+        TBK_CHECK(m->ws_H.reserve((size_t)nkc * nn2 * sizeof(double)));
+        double* d_H = m->ws_H.as<double>();
+        TBK_CHECK(build_h(m, hk, HK_TRI, 2, kc, nullptr, d_H));
+        TBK_CHECK(tbk_eig_batched(m, d_H, nkc, d_E + (size_t)c0 * m->n_orb));
+    }
+    {
         const int64_t total = nk * m->n_orb;
         const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 8 * 1024);
         hipLaunchKernelGGL(flag_nonfinite_kernel, dim3(blocks), dim3(256), 0, m->stream, d_E, total, m->ws_flag.as<int>() + 1);
@@ -1057,12 +1014,14 @@ static int eigenval_device_impl(tbk_model* m, const double* d_k, const double* h
     return TBK_OK;
 }
 
-extern "C" int tbk_eigenval_device(tbk_model* m, const double* d_k, int64_t nk, double* d_E) {
-    return eigenval_device_impl(m, d_k, nullptr, nk, d_E);
+extern "C" int tbk_eigenval_device_hint(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, double* d_E) {
+    TBK_ARG(m != nullptr, "model is NULL");
+    TBK_LOCK(m);
+    return eigenval_device_impl(m, tbk_eig_plan(m->n_orb, m->eigensolver, nk), d_k, h_k, nk, d_E);
 }
 
-extern "C" int tbk_eigenval_device_hint(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, double* d_E) {
-    return eigenval_device_impl(m, d_k, h_k, nk, d_E);
+extern "C" int tbk_eigenval_device(tbk_model* m, const double* d_k, int64_t nk, double* d_E) {
+    return tbk_eigenval_device_hint(m, d_k, nullptr, nk, d_E);
 }
 
 extern "C" int tbk_model_counter(tbk_model* m, int counter, int64_t* value) {
@@ -1235,6 +1194,7 @@ extern "C" int tbk_eigenval(tbk_model* m, const double* k, int64_t nk, double* E
     if (nk == 0) return TBK_OK;
     TBK_ARG(k && E_out, "k / E is NULL");
     TBK_HIP(hipSetDevice(m->device));
+    const tbk_eig_plan_t plan = tbk_eig_plan(m->n_orb, m->eigensolver, nk);
     const size_t k_bytes = (size_t)nk * m->dim * sizeof(double), e_bytes = (size_t)nk * m->n_orb * sizeof(double);
     TBK_CHECK(m->ws_k.reserve(k_bytes));
     TBK_CHECK(m->ws_out.reserve(e_bytes));
@@ -1246,7 +1206,7 @@ extern "C" int tbk_eigenval(tbk_model* m, const double* k, int64_t nk, double* E
         // (one k-point of a dense model on the matrix-vector path: k travels in the kernel arguments, see tbk_hamilton --
         // only the chunk pipeline reads it from there: the rocSOLVER branch fills its phase rows from ws_k, which a call
         // that skipped the upload would leave stale)
-        const bool inline_k = nk == 1 && eigenval_own_solvers(m) && tbk_hk_plan(m, 1, false).rows == HK_ROWS_NONE;
+        const bool inline_k = nk == 1 && plan.own() && tbk_hk_plan(m, 1, false).rows == HK_ROWS_NONE;
         if (inline_k) {
             m->h_k_inline = k;
         } else {
@@ -1254,7 +1214,7 @@ extern "C" int tbk_eigenval(tbk_model* m, const double* k, int64_t nk, double* E
             TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, st, k_bytes, hipMemcpyHostToDevice, m->stream));
         }
         // (the eigenvalues stored straight into the pinned buffer, like H in tbk_hamilton: measured, no gain -- 180.2 vs 180.0 us)
-        const int rc_inline = eigenval_device_impl(m, m->ws_k.as<double>(), k, nk, m->ws_out.as<double>());
+        const int rc_inline = eigenval_device_impl(m, plan, m->ws_k.as<double>(), k, nk, m->ws_out.as<double>());
         m->h_k_inline = nullptr;
         TBK_CHECK(rc_inline);
         {
@@ -1270,7 +1230,7 @@ extern "C" int tbk_eigenval(tbk_model* m, const double* k, int64_t nk, double* E
         return TBK_OK;
     }
     TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, k, k_bytes, hipMemcpyHostToDevice, m->stream));
-    TBK_CHECK(eigenval_device_impl(m, m->ws_k.as<double>(), k, nk, m->ws_out.as<double>()));
+    TBK_CHECK(eigenval_device_impl(m, plan, m->ws_k.as<double>(), k, nk, m->ws_out.as<double>()));
     TBK_HIP(hipMemcpyAsync(E_out, m->ws_out.ptr, e_bytes, hipMemcpyDeviceToHost, m->stream));
     return tbk_eigenval_check(m);  // synchronises
 }
@@ -1281,7 +1241,7 @@ extern "C" int tbk_eigenval(tbk_model* m, const double* k, int64_t nk, double* E
 extern "C" int tbk_tridiagonal_reduce(int device, int n_orb, int64_t nk, const double* H, int method, double* d, double* e,
                                       double* H_reduced) {
     TBK_ARG(nk >= 0, "nk < 0");
-    TBK_ARG(n_orb >= 1 && (n_orb <= 64 || tbk_eig_stream_supported(n_orb)),
+    TBK_ARG(n_orb >= 1 && (n_orb <= 64 || tbk_eig_band_supported(n_orb)),
             "n_orb must be in [1, 4096] (larger matrices go through rocSOLVER as a whole)");
     TBK_ARG(method >= TBK_REDUCE_AUTO && method <= TBK_REDUCE_TWO_STAGE, "unknown reduction method");
     TBK_ARG(method != TBK_REDUCE_TWO_STAGE || tbk_eig_band_supported(n_orb), "the two-stage reduction handles 64 < n_orb <= 4096");
@@ -1293,14 +1253,12 @@ extern "C" int tbk_tridiagonal_reduce(int device, int n_orb, int64_t nk, const d
     const size_t n = (size_t)n_orb, mat_bytes = n * n * 2 * sizeof(double);
     int rc = [&]() -> int {
         TBK_LOCK(m);
-        m->call_nk = nk;
+        const tbk_eig_plan_t plan = tbk_eig_plan(n_orb, m->eigensolver, nk, method);
         TBK_CHECK(m->ws_H.reserve((size_t)nk * mat_bytes));
         TBK_CHECK(m->ws_E.reserve((size_t)nk * n * 2 * sizeof(double)));
+        TBK_CHECK(tbk_eig_reserve(m, plan, nk, 1));
         TBK_HIP(hipMemcpyAsync(m->ws_H.ptr, H, (size_t)nk * mat_bytes, hipMemcpyHostToDevice, m->stream));
-        if (tbk_eig_small_supported(n_orb))
-            TBK_CHECK(tbk_launch_tridiag(m, m->stream, m->ws_H.as<double>(), nk, m->ws_E.as<double>()));
-        else
-            TBK_CHECK(tbk_launch_tridiag_stream(m, m->stream, m->ws_H.as<double>(), nk, m->ws_E.as<double>(), method));
+        TBK_CHECK(tbk_eig_reduce(m, plan, m->stream, m->ws_H.as<double>(), nk, m->ws_E.as<double>()));
         TBK_HIP(hipMemcpyAsync(d, m->ws_E.ptr, (size_t)nk * n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
         TBK_HIP(hipMemcpyAsync(e, m->ws_E.as<double>() + (size_t)nk * n, (size_t)nk * n * sizeof(double), hipMemcpyDeviceToHost,
                                m->stream));
@@ -1335,7 +1293,7 @@ __global__ void __launch_bounds__(256) random_hermitian_kernel(double* __restric
 extern "C" int tbk_reduce_standalone(int device, int n_orb, int64_t nk, int reps, double* us_per_matrix) {
     TBK_ARG(us_per_matrix != nullptr, "us_per_matrix is NULL");
     TBK_ARG(nk >= 1 && reps >= 1, "nk / reps < 1");
-    TBK_ARG(n_orb >= 1 && (n_orb <= 64 || tbk_eig_stream_supported(n_orb)), "n_orb must be in [1, 4096]");
+    TBK_ARG(n_orb >= 1 && (n_orb <= 64 || tbk_eig_band_supported(n_orb)), "n_orb must be in [1, 4096]");
     for (int q = 0; q < 3; ++q) us_per_matrix[q] = 0.0;
     tbk_model* m = nullptr;
     TBK_CHECK(create_common(device, 1, n_orb, 0, nullptr, 2, false, &m));
@@ -1344,7 +1302,7 @@ extern "C" int tbk_reduce_standalone(int device, int n_orb, int64_t nk, int reps
     hipEvent_t ev[2] = {nullptr, nullptr};
     int rc = [&]() -> int {
         TBK_LOCK(m);
-        m->call_nk = nk;
+        const tbk_eig_plan_t plan = tbk_eig_plan(n_orb, m->eigensolver, nk);
         TBK_CHECK(pristine.reserve((size_t)nk * mat_bytes));
         TBK_CHECK(m->ws_H.reserve((size_t)nk * mat_bytes));
         TBK_CHECK(m->ws_E.reserve((size_t)nk * n * 2 * sizeof(double)));
@@ -1352,11 +1310,10 @@ extern "C" int tbk_reduce_standalone(int device, int n_orb, int64_t nk, int reps
         TBK_HIP(hipEventCreate(&ev[1]));
         hipLaunchKernelGGL(random_hermitian_kernel, dim3(4096), dim3(256), 0, m->stream, pristine.as<double>(), n_orb, nk);
         TBK_HIP(hipGetLastError());
-        const bool band = !tbk_eig_small_supported(n_orb) && tbk_eig_two_stage(m);
-        if (band) {
-            TBK_CHECK(m->ws_band.reserve((size_t)nk * tbk_band_scratch_per_matrix(n_orb)));
-            TBK_CHECK(m->ws_bandmat[0].reserve((size_t)nk * tbk_band_bytes_per_matrix(n_orb)));
-        }
+        const bool band = plan.family == EIG_TWO_STAGE;
+        TBK_CHECK(tbk_eig_reserve(m, plan, nk, 1));
+        // (the stages run apart below at every two-stage size, a band buffer between them also where the plan fuses them)
+        TBK_CHECK(m->ws_bandmat[0].reserve((size_t)nk * plan.band_stride));
         // what: 0 = the reduction as the pipeline runs it, 1 = first stage alone, 2 = second stage alone (two-stage sizes only).
         // The second stage has no input of its own: every repetition of `what == 2` chases the band the LAST repetition of
         // `what == 1` left in ws_bandmat[0] (the chase reads it and writes only (d, e): the same work every time).
@@ -1367,14 +1324,11 @@ extern "C" int tbk_reduce_standalone(int device, int n_orb, int64_t nk, int reps
                     TBK_HIP(hipMemcpyAsync(m->ws_H.ptr, pristine.ptr, (size_t)nk * mat_bytes, hipMemcpyDeviceToDevice, m->stream));
                 TBK_HIP(hipEventRecord(ev[0], m->stream));
                 if (what == 0) {
-                    if (tbk_eig_small_supported(n_orb))
-                        TBK_CHECK(tbk_launch_tridiag(m, m->stream, m->ws_H.as<double>(), nk, m->ws_E.as<double>()));
-                    else
-                        TBK_CHECK(tbk_launch_tridiag_stream(m, m->stream, m->ws_H.as<double>(), nk, m->ws_E.as<double>(), TBK_REDUCE_AUTO));
+                    TBK_CHECK(tbk_eig_reduce(m, plan, m->stream, m->ws_H.as<double>(), nk, m->ws_E.as<double>()));
                 } else if (what == 1) {
-                    TBK_CHECK(tbk_launch_band_reduce(m, m->stream, m->ws_H.as<double>(), nk, m->ws_band.ptr, m->ws_bandmat[0].ptr));
+                    TBK_CHECK(tbk_launch_band_reduce(m, plan, m->stream, m->ws_H.as<double>(), nk, m->ws_band.ptr, m->ws_bandmat[0].ptr));
                 } else {
-                    TBK_CHECK(tbk_launch_band_chase(m, m->stream, m->ws_bandmat[0].ptr, nk, m->ws_E.as<double>()));
+                    TBK_CHECK(tbk_launch_band_chase(m, plan, m->stream, m->ws_bandmat[0].ptr, nk, m->ws_E.as<double>()));
                 }
                 TBK_HIP(hipEventRecord(ev[1], m->stream));
                 TBK_HIP(hipEventSynchronize(ev[1]));

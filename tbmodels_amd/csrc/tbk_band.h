@@ -1,11 +1,11 @@
 // tbk_band.h -- what the three translation units of the two-stage reduction share (round 6: tbk_eig_band.hip was one file of
 // 3700 lines / 31 kernels):
-//   tbk_eig_band.hip        stage 1 in one workgroup per matrix (band_reduce_kernel), the size policy, tbk_launch_band_reduce
+//   tbk_eig_band.hip        stage 1 in one workgroup per matrix (band_reduce_kernel), the buffer sizes, tbk_launch_band_reduce
 //   tbk_eig_band_chase.hip  stage 2 as kernels of its own (band_chase4 / 4g / 4w), tbk_launch_band_chase
 //   tbk_eig_band_xl.hip     stage 1 as a chain of launches (band_xl_*: above 1024 orbitals, and calls of a few matrices)
 //   tbk_band_chase.h        the body of stage 2 (chase4_body): inlined into the fused stage-1 kernel and into the stage-2 kernels
-// Device helpers live in an anonymous namespace (every unit compiles its own copy); the host-side policy functions are defined
-// once, in tbk_eig_band.hip.
+// Device helpers live in an anonymous namespace (every unit compiles its own copy); which kernels a call takes is decided by
+// tbk_eig_plan (tbk_eig_plan.hip), the launchers here read the plan.
 #pragma once
 
 #include <algorithm>
@@ -43,7 +43,7 @@ __device__ unsigned long long tbk_band_clock[32];
 //   TBK_ABLATE_BARRIER   no workgroup barrier per step of the pass
 //   TBK_ABLATE_STORES    the updated tiles are never stored (an upper bound for ANY scheme that defers the update)
 //   TBK_ABLATE_WIN_IO    band_chase4w_kernel without the global loads / stores of the columns that enter and leave the window
-//   TBK_ABLATE_WIN_FORCE the 32-slot window kernel from 257 orbitals on at every call size (against the plain LDS form at 512)
+//   TBK_ABLATE_WIN_FORCE the 32-slot window kernel from 257 orbitals on at every call size (against the plain LDS form at 512; tbk_eig_plan.hip)
 //   TBK_ABLATE_STORES_ALT  ... stored on every second panel only: what "the rank-16 update every second panel" saves in
 //                        stores, before any of its costs (a K = 32 update, the corrections of the products)
 constexpr int PB = 8;    // panel height = band half-width
@@ -304,13 +304,9 @@ struct Frag {  // a 16 x 16 complex operand block in A/B-operand layout: lane l 
 
 }  // namespace
 
-// ---- host side: sizes and policy (defined in tbk_eig_band.hip) ---------------------------------------------------------------------
-constexpr int BAND_ONE_WG_MAXN = 1024;    // one workgroup per matrix: two rows per thread of 512 threads, X (8 complex per row) is 128 KiB of LDS
-constexpr int BAND_LDS_CHASE_MAXN = 512;  // above: the chase keeps its 16 diagonals in global memory
-bool tbk_band_is_xl(int n);               // the sizes that ALWAYS take the launch chain of band_xl_* (above 1024 orbitals; TBK_BAND_XL_FROM)
+// ---- host side (the policy is tbk_eig_plan's, tbk_internal.h) ------------------------------------------------------------------------
 int tbk_band_chase_pitch(int n);          // pitch of a working diagonal of the second stage
-bool tbk_band_chase_small_window(const tbk_model* m, int n, int64_t nk);
 // tbk_eig_band_chase.hip: stage two of nk matrices on stream s, no stage timer (the callers hold one)
-int tbk_band_launch_chase(tbk_model* m, hipStream_t s, const void* d_band, int64_t nk, double* d_D, double* d_E);
+int tbk_band_launch_chase(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, const void* d_band, int64_t nk, double* d_D, double* d_E);
 // tbk_eig_band_xl.hip: the first stage as a chain of launches; d_de != NULL: the second stage of every group behind it
-int tbk_band_launch_xl(tbk_model* m, hipStream_t s, double* d_H, int n, int64_t nk, void* d_scratch, void* d_band, double* d_de = nullptr);
+int tbk_band_launch_xl(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int64_t nk, void* d_scratch, void* d_band, double* d_de = nullptr);

@@ -1068,19 +1068,10 @@ band_reduce_kernel(double* __restrict__ Hall, int n, d2* __restrict__ VWall, d2*
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
-// sizes, policy, launchers
-// ------------------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------------------
-// launchers
+// buffer sizes, launchers
 // ------------------------------------------------------------------------------------------------
 // per matrix: the pending [V | W] rows in fragment order (16 complex per row) + the next panel's V (8 complex per row; used
 // when it does not live in LDS)
-// the sizes that take the launch chain of band_xl_*: above 1024 orbitals (TBK_BAND_XL_FROM=n: above n -- tests run the chain
-// at sizes the NumPy model is quick at, and A/B it against the one-workgroup kernels)
-bool tbk_band_is_xl(int n) {
-    static const int from = getenv("TBK_BAND_XL_FROM") ? atoi(getenv("TBK_BAND_XL_FROM")) : 1024;
-    return n > from;
-}
 // (+ for the launch chain of band_xl_*: X / the panel's rows [npad][8] and T of the panel)
 size_t tbk_band_scratch_per_matrix(int n) {
     const size_t nbk = (size_t)((n + TS - 1) / TS);
@@ -1096,100 +1087,26 @@ int tbk_band_chase_pitch(int n) {
     return np;
 }
 
-bool tbk_band_fused(int n);
-// above: every panel as three launches with nothing per row in registers or LDS (band_xl_*).  The limit is what has been
-// validated (tests/test_gpu_parity.py: 1030 / 1536 / 2048 / 2050 / 3000 / 4096); nothing in the kernels depends on it.  TBK_BAND_XL=0: rocSOLVER above
-// 1024 orbitals, as until round 4 (measurements).
-static int band_maxn() {
-    static const bool xl = !(getenv("TBK_BAND_XL") && atoi(getenv("TBK_BAND_XL")) == 0);
-    return xl ? 4096 : BAND_ONE_WG_MAXN;
-}
-#define BAND_MAXN band_maxn()
-// 257 - 768 orbitals, calls of more matrices than the chip has CUs: the windowed kernel with 16 sweep slots and 272 columns -- 78 KiB
-// of LDS instead of the 133 KiB of the plain LDS form at 512 orbitals, so two of its workgroups share a CU, or one sits beside a
-// first-stage workgroup of the next chunk (76 KiB).  A matrix takes more and slower ticks (1293 x ~2.2 us instead of 1088 x 1.55 at
-// 512 orbitals), the chip holds twice as many: cfg5 16.04 -> 16.63 k k-points/s, whole eigenval of 2048 k-points 12.93 -> 11.74 us per
-// k-point at 320 orbitals, 18.82 -> 17.66 at 384, 34.57 -> 33.64 at 512; the same bits.
-bool tbk_band_chase_small_window(const tbk_model* m, int n, int64_t nk) {
-    // Up to 768 orbitals: above 512 against the 32-slot window -- whole eigenval of 2048 k-points 41.1 -> 39.1 us per k-point
-    // at 520 orbitals, 64.8 -> 62.9 at 640, 100.1 -> 97.4 at 768, 206.2 -> 215.6 at 1000.
-    constexpr int SMALL_WINDOW_MAXN = 768;
-    return n > 256 && n <= SMALL_WINDOW_MAXN && !tbk_band_fused(n) && std::max<int64_t>(m->call_nk, nk) > 256;
-}
-// does a matrix' band buffer carry the 16 working diagonals behind the compact band (by the size alone: any call may need them)
-static bool chase_has_buffer(int n) { return n > BAND_LDS_CHASE_MAXN || (n > 256 && !tbk_band_fused(n)); }
-
-// The kernels handle 64 < n <= 512; the two-stage path is TAKEN from 189 orbitals on (129 until round 3): up to 128 the one-stage kernel of
-// tbk_eig_stream.hip (four waves per matrix, rows of two 64-column chunks) is faster -- 0.65 vs 0.84 us per matrix at 65
-// orbitals, 1.73 vs 2.14 at 128; from 129 on the one-stage rows grow a third chunk and the order flips (3.8 vs 3.3 us at 160).
-// Both stages in ONE kernel (the workgroup goes straight on to the bulge chasing of its matrix, in the same LDS) or in
-// two launches with the second one on the tridiagonal stream next to the following chunk's first stage.  Per matrix
-// the two cost the same -- a workgroup's critical path is the sum of its phases either way -- and in the chunk pipeline
-// fused is 1 % ahead at 256 orbitals (cfg3 134.1 vs 132.3 k k-points/s), 4 % behind at 512 (cfg5 13.5 vs 14.0 k: one
-// workgroup per CU there, and the separate launch fills the gaps of the next chunk's first stage).
-bool tbk_band_fused(int n) {
-    if (tbk_band_is_xl(n)) return false;  // (the launch chain ends in the band's way out; the second stage is a launch of its own)
-    return n <= 256;
+// the compact band between the stages (9 complex per row) and, above 256 orbitals (the plan's chase_buffer), the second
+// stage's 16 working diagonals behind it
+size_t tbk_band_bytes_per_matrix(int n, bool chase_buffer) {
+    return ((size_t)n * (PB + 1) + (chase_buffer ? (size_t)16 * tbk_band_chase_pitch(n) : 0)) * sizeof(d2);
 }
 
-bool tbk_eig_band_supported(int n) { return n > 64 && n <= BAND_MAXN; }
-bool tbk_eig_band_preferred(int n) {
-    // (round 3: the one-stage kernel hands its last 128 steps to the register-resident kernels -- eight waves per matrix
-    // from 128 to 64, tbk_eig_small.hip -- which moved the crossover up: 1.34 vs 2.37 us per matrix at 130 orbitals, 1.96 vs
-    // 2.57 at 144, 2.56 vs 3.02 at 160; reduction stage of 4096 matrices 12.2 vs 12.7 ms at 176, 13.4 vs 13.9 at 184,
-    // 14.9 vs 14.4 at 192.  Round 4, after the trims of both stages, whole eigenval per k-point, one-stage vs two-stage:
-    // 2.85 vs 3.16 us at 168, 3.36 vs 3.34 at 176, 3.70 vs 3.70 at 184, 3.88 vs 3.78 at 188 -- 177 .. 192 orbitals pad to
-    // the same twelve blocks of 16, so the two-stage path takes over where the one-stage time reaches that: from 185)
-    constexpr int BAND_FROM = 185;
-    return n >= BAND_FROM && n <= BAND_MAXN;
-}
-
-// the compact band between the stages (9 complex per row) and, above 512 orbitals, the second stage's 16 working
-// diagonals behind it
-size_t tbk_band_bytes_per_matrix(int n) {
-    return ((size_t)n * (PB + 1) + (chase_has_buffer(n) ? (size_t)16 * tbk_band_chase_pitch(n) : 0)) * sizeof(d2);
-}
-
-// Calls of a few matrices (Z2Pack-style lines and single k-points, _tb_model.py:1103-1108; band-structure paths of a few dozen
-// points): the first stage as a chain of launches, so that every tile pass runs on several CUs per matrix instead of one.  By
-// the size of the CALL (TBK_OPT_K_CHUNK must not change a result: the partial sums differ from one workgroup's in the last
-// bit).  TBK_BAND_SPLIT=0: off (an independent reference path for the tests).
-bool tbk_band_split(const tbk_model* m, int64_t nk) {
-    static const bool on = !(getenv("TBK_BAND_SPLIT") && atoi(getenv("TBK_BAND_SPLIT")) == 0);
-    const int n = m->n_orb;
-    if (!on || n <= 128 || n > BAND_ONE_WG_MAXN || tbk_band_is_xl(n)) return false;
-    // as long as every member workgroup of every matrix finds a CU of its own: n_cu / members matrices (on 256 CUs: 64 up to
-    // 512 orbitals, 32 at 1024).  Measured (one k-point per call, reduction stage): 256 orbitals 2.11 -> 2.04 ms, 384: 4.62 -> 3.80, 512: 8.31 ->
-    // 6.01, 1024: 49.0 -> 24.4
-    // (up to 256 orbitals the serial launches dominate and 64 matrices in one launch are as fast: 2.49 vs 2.40 ms -- 8 there)
-    // Round 5: the chain these calls take is the one of band_xl_* (three launches per panel, sweeps on a workgroup per block row =
-    // every CU for ONE matrix; round 4's chain had two launches per panel and 4 - 8 member workgroups per matrix).  One-k
-    // eigenval, round-4 chain -> band_xl chain: 2.05 -> 1.94 ms at 256 orbitals, 3.99 -> 3.50 at 384, 6.05 -> 5.03 at 512, 13.98
-    // -> 10.28 at 768, 24.35 -> 16.84 at 1024; 64 matrices: 2.23 -> 2.31 / 4.39 -> 4.43 / 6.80 -> 7.16 / 22.5 -> 17.6 / 46.3 ->
-    // 35.1; 64 matrices of 512 orbitals in ONE launch of the eight-wave kernel: 8.09 ms -- so calls of up to 8 matrices up to 256
-    // orbitals, 64 up to 512, 96 above.
-    const int64_t limit = n <= 256 ? 8 : n <= 512 ? 64 : 96;
-    return std::max<int64_t>(m->call_nk, nk) <= limit;
-}
-
-
-// Stage one: the upper triangle of every d_H matrix is overwritten; d_vw: scratch of tbk_band_scratch_per_matrix(n)
-// bytes per matrix; d_band receives the band, tbk_band_bytes_per_matrix(n) bytes per matrix.
-int tbk_launch_band_reduce(tbk_model* m, hipStream_t s, double* d_H, int64_t nk, void* d_vw, void* d_band, double* d_de_fused) {
-    const int n = m->n_orb;
+// Stage one: the upper triangle of every d_H matrix is overwritten; d_vw: scratch of plan.ws_band bytes per matrix; d_band
+// receives the band, plan.band_stride bytes per matrix.
+int tbk_launch_band_reduce(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int64_t nk, void* d_vw, void* d_band,
+                           double* d_de_fused) {
+    const int n = plan.n;
     if (nk == 0) return TBK_OK;
     StageTimer t(m, TBK_T_EIG, s);
-    if (tbk_band_is_xl(n)) return tbk_band_launch_xl(m, s, d_H, n, nk, static_cast<d2*>(d_vw), static_cast<d2*>(d_band), d_de_fused);
+    if (plan.chain) return tbk_band_launch_xl(m, plan, s, d_H, nk, d_vw, d_band, d_de_fused);
     const int nbk = (n + TS - 1) / TS, npad = nbk * TS;
     // up to 256 orbitals a row per thread, V and X in LDS; above, TWO rows per thread and V in global memory, so that two
     // workgroups still fit a CU (76 KiB each at 512 orbitals) -- with 512 threads / V in LDS only one did and nothing
     // overlapped its serial phases (31.7 instead of 29.7 us per 512 x 512 matrix; that instantiation is gone)
     const bool vn_lds = n <= 256;
-    // Calls of a few matrices (one k-point per call is what Z2Pack-style callers do, _tb_model.py:1103-1108): every matrix has
-    // a CU to itself anyway, so it gets EIGHT waves and one row per thread -- twice the waves on the tile pass, half the
-    // rows per thread in the thread-per-row phases.  By the size of the CALL (TBK_OPT_K_CHUNK must not change a result:
-    // the partial sums of eight waves differ from those of four in the last bit).
-    const bool wide = n <= 512 && std::max<int64_t>(m->call_nk, nk) <= 128;
+    const bool wide = plan.wide;  // eight waves and one row per thread: twice the waves on the tile pass, half the rows per thread in the thread-per-row phases
     const int nw = (n > 512 || wide) ? 8 : 4;
     const int rows_per_thread = (n > 512 || (n > 256 && !wide)) ? 2 : 1;  // (the instantiation chosen below)
     size_t lds = band_xv_bytes(npad, vn_lds, nw, rows_per_thread) + (size_t)(nw * 16 * 17 + nw * 64 + 64) * 8 + (16 + 64 + 64 + 8 + 2) * 16;
@@ -1203,14 +1120,12 @@ int tbk_launch_band_reduce(tbk_model* m, hipStream_t s, double* d_H, int64_t nk,
     }
     d2* d_VW = static_cast<d2*>(d_vw);
     d2* d_VN = d_VW + (size_t)nk * nbk * 256;
-    if (d_de_fused == nullptr && tbk_band_split(m, nk))
-        return tbk_band_launch_xl(m, s, d_H, n, nk, static_cast<d2*>(d_vw), static_cast<d2*>(d_band));
     static std::atomic<bool> raised[5][TBK_MAX_DEVICES] = {};
 #define TBK_REDUCE(NTV, ROWSV, VNL, SLOT)                                                                                       \
     do {                                                                                                                        \
         TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&band_reduce_kernel<NTV, ROWSV, VNL>), 160 * 1024, raised[SLOT])); \
         hipLaunchKernelGGL((band_reduce_kernel<NTV, ROWSV, VNL>), dim3((unsigned)nk), dim3(NTV), lds, s, d_H, n, d_VW, d_VN,      \
-                           static_cast<d2*>(d_band), tbk_band_bytes_per_matrix(n) / sizeof(d2), np, 2, d_D, d_E);               \
+                           static_cast<d2*>(d_band), plan.band_stride / sizeof(d2), np, 2, d_D, d_E);                          \
     } while (0)
     if (wide && vn_lds)
         TBK_REDUCE(512, 1, true, 3);

@@ -45,7 +45,7 @@ band_chase4g_kernel(d2* __restrict__ band_all, size_t band_stride, int n, int np
 // column, a column only enters a free cell; tests/test_two_stage_model.py).  Same arithmetic per sweep as chase4_body: the same bits.
 // NW waves = 4 NW sweep slots; CW window columns (>= 15 * 4 NW + 18: what the slots can hold in flight), CWP = pitch of a diagonal
 // (= 9 mod 16: bank-conflict free, as in the plain LDS form).  <8, 512, 521>: above 512 orbitals.  <4, 272, 281> (calls of more
-// matrices than the chip has CUs, tbk_band_chase_small_window): 257 - 768 orbitals in 78 KiB (the plain LDS form takes 133 KiB at 512).
+// matrices than the chip has CUs, EIG_CHASE_WINDOW16): 257 - 768 orbitals in 78 KiB (the plain LDS form takes 133 KiB at 512).
 template <int NW, int CW, int CWP>
 __global__ void __launch_bounds__(NW * 64)
 band_chase4w_kernel(d2* __restrict__ band_all, size_t band_stride, int n, int np, double* __restrict__ D, double* __restrict__ E) {
@@ -390,38 +390,30 @@ band_chase4w_kernel(d2* __restrict__ band_all, size_t band_stride, int n, int np
 
 }  // namespace
 
-// Stage two: d_band -> d_de = d[nk][n] followed by e[nk][n]
-int tbk_band_launch_chase(tbk_model* m, hipStream_t s, const void* d_band, int64_t nk, double* d_D, double* d_E) {
-    const int n = m->n_orb;
-    // TBK_CHASE_WINDOW=0 (measurements): no windowed kernel -- above 512 orbitals the global-memory form, the plain LDS form below
-    static const bool window_env = !(getenv("TBK_CHASE_WINDOW") && atoi(getenv("TBK_CHASE_WINDOW")) == 0);
-    const bool small_window = window_env && tbk_band_chase_small_window(m, n, nk);
-#ifdef TBK_ABLATE_WIN_FORCE  // (timing: the 32-slot window from 257 orbitals on, at every call size)
-    const bool win_force = n > 256 && !tbk_band_fused(n);
-#else
-    const bool win_force = false;
-#endif
-    if (n > BAND_LDS_CHASE_MAXN || small_window || win_force) {
+// Stage two: d_band -> d_de = d[nk][n] followed by e[nk][n], in the plan's chase kernel
+int tbk_band_launch_chase(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, const void* d_band, int64_t nk, double* d_D, double* d_E) {
+    const int n = plan.n;
+    if (plan.chase != EIG_CHASE_LDS) {
         const int np = tbk_band_chase_pitch(n);
         // The working diagonals in a cyclic LDS window in front of the global buffer (band_chase4w_kernel; the same bits as the
         // global-memory form below).  One workgroup per CU (158 KiB of LDS) and still ahead at every call size: whole eigenval of
         // 2048 k-points 44.7 -> 41.0 us per k-point at 520 orbitals, 110.6 -> 99.6 at 768, 245.5 -> 216.1 at 1024; one k-point 15.2 ->
         // 13.0 ms at 1024, 32.1 -> 27.2 at 1536, 53.7 -> 44.4 at 2048.
-        if (window_env) {
+        if (plan.chase != EIG_CHASE_GLOBAL) {
             d2* d_b = static_cast<d2*>(const_cast<void*>(d_band));
-            const size_t stride = tbk_band_bytes_per_matrix(n) / sizeof(d2);
-            if (small_window && !win_force) {
-                const size_t ldsw = (size_t)16 * 281 * 16 + (size_t)4 * 64 * 16 + (size_t)n * sizeof(int) + 16;
-                static std::atomic<bool> raised_s[TBK_MAX_DEVICES] = {};
-                TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&band_chase4w_kernel<4, 272, 281>), 160 * 1024, raised_s));
-                hipLaunchKernelGGL((band_chase4w_kernel<4, 272, 281>), dim3((unsigned)nk), dim3(256), ldsw, s, d_b, stride, n, np, d_D, d_E);
-                TBK_HIP(hipGetLastError());
-                return TBK_OK;
-            }
-            const size_t ldsw = (size_t)16 * 521 * 16 + (size_t)8 * 64 * 16 + (size_t)n * sizeof(int) + 16;
-            static std::atomic<bool> raised_w[TBK_MAX_DEVICES] = {};
-            TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&band_chase4w_kernel<8, 512, 521>), 160 * 1024, raised_w));
-            hipLaunchKernelGGL((band_chase4w_kernel<8, 512, 521>), dim3((unsigned)nk), dim3(512), ldsw, s, d_b, stride, n, np, d_D, d_E);
+            const size_t stride = plan.band_stride / sizeof(d2);
+            static std::atomic<bool> raised_w[2][TBK_MAX_DEVICES] = {};
+#define TBK_CHASE4W(NWV, CWV, CWPV, SLOT)                                                                                              \
+    do {                                                                                                                               \
+        const size_t ldsw = (size_t)16 * CWPV * 16 + (size_t)NWV * 64 * 16 + (size_t)n * sizeof(int) + 16;                             \
+        TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&band_chase4w_kernel<NWV, CWV, CWPV>), 160 * 1024, raised_w[SLOT])); \
+        hipLaunchKernelGGL((band_chase4w_kernel<NWV, CWV, CWPV>), dim3((unsigned)nk), dim3(NWV * 64), ldsw, s, d_b, stride, n, np, d_D, d_E); \
+    } while (0)
+            if (plan.chase == EIG_CHASE_WINDOW16)
+                TBK_CHASE4W(4, 272, 281, 0);
+            else
+                TBK_CHASE4W(8, 512, 521, 1);
+#undef TBK_CHASE4W
             TBK_HIP(hipGetLastError());
             return TBK_OK;
         }
@@ -432,7 +424,7 @@ int tbk_band_launch_chase(tbk_model* m, hipStream_t s, const void* d_band, int64
         const int nwg = n <= 256 ? 4 : 8;
         const size_t ldsg = (size_t)nwg * 64 * 16 + (size_t)n * sizeof(int) + 16;
         d2* d_b = static_cast<d2*>(const_cast<void*>(d_band));
-        const size_t stride = tbk_band_bytes_per_matrix(n) / sizeof(d2);
+        const size_t stride = plan.band_stride / sizeof(d2);
         if (nwg <= 4)
             hipLaunchKernelGGL(band_chase4g_kernel<4>, dim3((unsigned)nk), dim3(256), ldsg, s, d_b, stride, n, np, 2, d_D, d_E);
         else
@@ -453,7 +445,7 @@ int tbk_band_launch_chase(tbk_model* m, hipStream_t s, const void* d_band, int64
 #define TBK_CHASE4(NWV, SLOT)                                                                                             \
     do {                                                                                                                  \
         TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&band_chase4_kernel<NWV>), 160 * 1024, raised4[SLOT]));   \
-        hipLaunchKernelGGL(band_chase4_kernel<NWV>, dim3((unsigned)nk), dim3(NWV * 64), lds4, s, static_cast<const d2*>(d_band), tbk_band_bytes_per_matrix(n) / sizeof(d2), n, np, stagger, d_D, d_E); \
+        hipLaunchKernelGGL(band_chase4_kernel<NWV>, dim3((unsigned)nk), dim3(NWV * 64), lds4, s, static_cast<const d2*>(d_band), plan.band_stride / sizeof(d2), n, np, stagger, d_D, d_E); \
     } while (0)
         if (nw4 <= 2)
             TBK_CHASE4(2, 0);
@@ -467,8 +459,8 @@ int tbk_band_launch_chase(tbk_model* m, hipStream_t s, const void* d_band, int64
     return TBK_OK;
 }
 
-int tbk_launch_band_chase(tbk_model* m, hipStream_t s, const void* d_band, int64_t nk, double* d_de) {
+int tbk_launch_band_chase(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, const void* d_band, int64_t nk, double* d_de) {
     if (nk == 0) return TBK_OK;
     StageTimer t(m, TBK_T_EIG, s);
-    return tbk_band_launch_chase(m, s, d_band, nk, d_de, d_de + (size_t)nk * m->n_orb);
+    return tbk_band_launch_chase(m, plan, s, d_band, nk, d_de, d_de + (size_t)nk * plan.n);
 }

@@ -618,28 +618,15 @@ __global__ void __launch_bounds__(256) band_deposit_kernel(double* __restrict__ 
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-// the second matrix buffer of the chain (ws_xl), per matrix of a chunk: only the sizes that ALWAYS take the chain count for the chunk size
-size_t tbk_band_xl_buffer_per_matrix(int n) { return tbk_band_is_xl(n) ? (size_t)n * n * sizeof(d2) : 0; }
-bool tbk_band_split(const tbk_model* m, int64_t nk);
-// The chain's second matrix buffer for calls / chunks of up to max_nk matrices, reserved where the callers reserve ws_band and
-// ws_bandmat -- in front of the pipeline, not inside a launch (a grow there is a free + malloc, i.e. a device synchronisation
-// between the chunks of a call whose later chunk is the larger one).  Calls of a few matrices take the chain at
-// every size (tbk_band_split): up to 96 matrices x 16 n^2 bytes, 1.6 GB at 1024 orbitals.
-int tbk_band_xl_reserve(tbk_model* m, int64_t max_nk) {
-    const int n = m->n_orb;
-    if (!(tbk_band_is_xl(n) || tbk_band_split(m, max_nk))) return TBK_OK;
-    return m->ws_xl.reserve((size_t)max_nk * n * n * sizeof(d2));
-}
 // The first stage above 1024 orbitals: three launches per panel (serial phases / update sweep / product sweep), one more update
 // sweep for the last pending update, then the band's way out.
-static int xl_groups(int n, int64_t nk) {
-    constexpr int XL_GROUPS = 2;  // (1 - 4 were measured)
-    return (tbk_band_is_xl(n) && nk >= 4 * XL_GROUPS) ? XL_GROUPS : 1;
-}
-bool tbk_band_xl_grouped(int n, int64_t nk) { return xl_groups(n, nk) > 1; }
-
+// The chain's second matrix buffer (ws_xl, plan.ws_xl bytes per matrix) is reserved where the callers reserve ws_band and
+// ws_bandmat (tbk_eig_reserve) -- in front of the pipeline, not inside a launch (a grow there is a free + malloc, i.e. a device
+// synchronisation between the chunks of a call whose later chunk is the larger one).  Calls of a few matrices take the
+// chain at every size: up to 96 matrices x 16 n^2 bytes, 1.6 GB at 1024 orbitals.
 // d_de != NULL: the second stage of every group runs behind its first stage on the group's stream and (d, e) are written there
-int tbk_band_launch_xl(tbk_model* m, hipStream_t s, double* d_H, int n, int64_t nk, void* d_scratch_v, void* d_band_v, double* d_de) {
+int tbk_band_launch_xl(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int64_t nk, void* d_scratch_v, void* d_band_v, double* d_de) {
+    const int n = plan.n;
     d2* d_scratch = static_cast<d2*>(d_scratch_v);
     d2* d_band = static_cast<d2*>(d_band_v);
     const int nbk = (n + TS - 1) / TS, npad = nbk * TS;
@@ -647,7 +634,7 @@ int tbk_band_launch_xl(tbk_model* m, hipStream_t s, double* d_H, int n, int64_t 
     d2* d_VN = d_VW + (size_t)nk * nbk * 256;
     d2* d_XY = d_VN + (size_t)nk * npad * PB;
     d2* d_T = d_XY + (size_t)nk * npad * PB;
-    const size_t stride = tbk_band_bytes_per_matrix(n) / sizeof(d2);
+    const size_t stride = plan.band_stride / sizeof(d2);
     int p_end = 0;  // first panel without a trailing matrix behind it
     while (n - PB * (p_end + 1) >= 2) ++p_end;
     constexpr int NTS = 512, NTP = 256;
@@ -656,7 +643,10 @@ int tbk_band_launch_xl(tbk_model* m, hipStream_t s, double* d_H, int n, int64_t 
     // and the band is put back into the caller's buffer (the work copy tbk_tridiagonal_reduce hands out).
     // (a read-once sweep of four block rows per workgroup was built in round 5 and not faster, DESIGN_LOG.md R5.12: 64 / 256
     // matrices of 1536 orbitals 1.256 -> 1.288 / 0.940 -> 0.893 ms per k-point, of 2048 orbitals 2.585 -> 2.637 / 2.195 -> 2.214)
-    TBK_CHECK(m->ws_xl.reserve((size_t)nk * n * n * 2 * sizeof(double)));
+    if (m->ws_xl.bytes < (size_t)nk * plan.ws_xl) {
+        tbk_set_error("the launch chain's second matrix buffer was not reserved for %lld matrices", (long long)nk);
+        return TBK_ERR_DEVICE;
+    }
     double* buf[2] = {d_H, m->ws_xl.as<double>()};
     // up to 1024 orbitals (calls of a few matrices): the panel's rows in LDS (above 1024: in global memory)
     const bool y_lds = n <= BAND_ONE_WG_MAXN;
@@ -673,7 +663,7 @@ int tbk_band_launch_xl(tbk_model* m, hipStream_t s, double* d_H, int n, int64_t 
     // workgroup per matrix (a latency chain on a quarter of the CUs at 64 matrices) while the sweep is bound by HBM, and the second
     // stage is one workgroup per matrix for 2 n ticks -- one group's chains run under the other groups' sweeps.  Per matrix nothing
     // changes (same launches, same order, same bits).
-    const int groups = xl_groups(n, nk);
+    const int groups = tbk_eig_xl_groups(plan, nk);
     auto chain = [&](hipStream_t st, int64_t k0, int64_t nkg) {
         double* b[2] = {buf[0] + (size_t)k0 * n * n * 2, buf[1] + (size_t)k0 * n * n * 2};
         d2* vw = d_VW + (size_t)k0 * nbk * 256;
@@ -706,7 +696,7 @@ int tbk_band_launch_xl(tbk_model* m, hipStream_t s, double* d_H, int n, int64_t 
         }
         hipLaunchKernelGGL(band_extract_from_kernel, dim3((unsigned)nkg), dim3(256), 0, st, b[cur], n, bd, stride, PB * p_end);
         hipLaunchKernelGGL(band_deposit_kernel, dim3((unsigned)nkg), dim3(256), 0, st, b[0], n, bd, stride);
-        if (d_de) return tbk_band_launch_chase(m, st, bd, nkg, d_de + (size_t)k0 * n, d_de + (size_t)(nk + k0) * n);
+        if (d_de) return tbk_band_launch_chase(m, plan, st, bd, nkg, d_de + (size_t)k0 * n, d_de + (size_t)(nk + k0) * n);
         return (int)TBK_OK;
     };
     if (groups == 1) {

@@ -1007,23 +1007,18 @@ tridiag_ql_kernel(const double* __restrict__ D, const double* __restrict__ E, in
 
 }  // namespace
 
-bool tbk_eig_small_supported(int n) { return n >= 1 && n <= 64; }
-
 // d_de holds the tridiagonal of every matrix: d[nk][n] followed by e[nk][n]
 // The register-resident reduction of nk n x n matrices (32 < n <= 64) that sit h_stride doubles apart in d_H; (d, e) of
 // matrix m to d_D / d_E + m * ldd + off.  Two launches: the first n - 32 steps (four or two waves per matrix), then the
 // trailing 32 x 32 blocks two per wave.
 static int launch_tridiag_33_64(hipStream_t s, double* d_H, int n, int64_t nk, double* d_D, double* d_Eo, int64_t h_stride, int ldd, int off,
-                                int64_t call_nk) {
+                                bool split_on) {
     const dim3 grid((unsigned)nk), block(64);
     // columns per lane = padded size / 4: a 40-orbital matrix in the 64-row instantiation does 16 column
     // updates per lane and step where 10 are enough (n = 48: 8.0 -> 7.2 ms per 65536 matrices)
     // Round 3: the four-wave kernel only does the first n - 32 steps; the trailing 32 x 32 block goes through the
     // head of the matrix' own storage to the packed kernel (two matrices per wave).
-    // Calls of a few matrices (all of them resident at once: what counts is one matrix' latency, not issue slots) keep the
-    // whole reduction in ONE launch of the four-wave kernel: a single 64 x 64 matrix 99 -> 78 us.  By the size of the CALL,
-    // not of this chunk: TBK_OPT_K_CHUNK must not change results, and the forms differ in the last bit.
-    const bool split_on = std::max(call_nk, nk) > 512;
+    // Calls of a few matrices keep the whole reduction in ONE launch of the four-wave kernel (the plan's split_on is off).
     const int n_steps = split_on ? n - 32 : n - 1;
     // TWO waves per matrix at every size when the kernel only does the first n - 32 steps (round 3): those are the steps
     // with the most FMAs per reduction / barrier / scalar chain, and halving the copies of that overhead buys more than the
@@ -1057,24 +1052,20 @@ static int launch_tridiag_33_64(hipStream_t s, double* d_H, int n, int64_t nk, d
 
 // The tail of the streaming reduction (tbk_eig_stream.hip): the trailing 64 x 64 blocks it left at the head of the
 // n_full x n_full matrices, (d, e)[n_full - 64 ...] of every matrix.  No stage timer: the caller holds one.
-int tbk_launch_tridiag_tail64(hipStream_t s, double* d_H, int64_t nk, double* d_D, double* d_E, int n_full, int64_t call_nk) {
-    return launch_tridiag_33_64(s, d_H, 64, nk, d_D, d_E, (int64_t)n_full * n_full * 2, n_full, n_full - 64, call_nk);
+int tbk_launch_tridiag_tail64(const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int64_t nk, double* d_D, double* d_E, int n_full) {
+    return launch_tridiag_33_64(s, d_H, 64, nk, d_D, d_E, (int64_t)n_full * n_full * 2, n_full, n_full - 64, plan.split_on);
 }
 
 // The first n - 64 Householder steps of nk n x n matrices, 64 < n <= 128, in the eight-wave register kernel; the trailing
 // 64 x 64 blocks are left at the head of every matrix' storage for tbk_launch_tridiag_tail64.  (d, e)[0 .. n - 65] of
 // matrix m to d_D / d_E + m * ldd + off.
-bool tbk_eig_reg128_supported(int n) {
-    static const bool on = !(getenv("TBK_REG128") && atoi(getenv("TBK_REG128")) == 0);  // measurements: 0 = streaming kernel
-    return on && n > 64 && n <= 128;
-}
-int tbk_launch_tridiag_reg128(hipStream_t s, double* d_H, int n, int64_t nk, double* d_D, double* d_E, int64_t h_stride, int ldd, int off) {
+int tbk_launch_tridiag_reg128(const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int n, int64_t nk, double* d_D, double* d_E, int64_t h_stride, int ldd, int off) {
     const dim3 grid((unsigned)nk);
 #define TBK_T8(NCV, NWV) \
     hipLaunchKernelGGL((herm_tridiag8_kernel<NCV, NWV>), grid, dim3(NWV * 128), 0, s, d_H, n, d_D, d_E, n - 64, h_stride, ldd, off)
     // up to 96 orbitals FOUR waves per matrix (two column residues: 48 complex per lane, ~250 registers): two matrices
     // per CU, so that one's barriers and scalar chains run under the other's FMAs (TBK_REG128_NW2=0: eight waves)
-    static const bool nw2 = !(getenv("TBK_REG128_NW2") && atoi(getenv("TBK_REG128_NW2")) == 0);
+    const bool nw2 = plan.reg128_nw2;
     if (n <= 80 && nw2)
         TBK_T8(80, 2);
     else if (n <= 80)
@@ -1093,15 +1084,15 @@ int tbk_launch_tridiag_reg128(hipStream_t s, double* d_H, int n, int64_t nk, dou
 }
 
 // d_de holds the tridiagonal of every matrix: d[nk][n] followed by e[nk][n]
-int tbk_launch_tridiag(tbk_model* m, hipStream_t s, double* d_H, int64_t nk, double* d_de) {
-    const int n = m->n_orb;
+int tbk_launch_tridiag(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int64_t nk, double* d_de) {
+    const int n = plan.n;
     if (nk == 0) return TBK_OK;
     double* d_D = d_de;
     double* d_Eo = d_de + (size_t)nk * n;
     StageTimer t(m, TBK_T_EIG, s);
     const dim3 block(64);
     const int64_t packed = (int64_t)n * n * 2;
-    if (n > 32) return launch_tridiag_33_64(s, d_H, n, nk, d_D, d_Eo, packed, n, 0, m->call_nk);
+    if (n > 32) return launch_tridiag_33_64(s, d_H, n, nk, d_D, d_Eo, packed, n, 0, plan.split_on);
     if (n <= 8)
         hipLaunchKernelGGL(herm_tridiag_packed_kernel<8>, dim3((unsigned)((nk + 7) / 8)), block, 0, s, d_H, n, nk, d_D, d_Eo, packed, n, 0);
     else if (n <= 16)

@@ -99,8 +99,6 @@ __device__ __forceinline__ void wg_sync() {
     __syncthreads();
 }
 
-constexpr int ST_MAXN = 512;
-
 // Phase clock for tools/stream_phase_clock.hip (compiled out of the library): cycles per phase of a Householder
 // step, accumulated by thread 0 of workgroup 0.
 #ifdef TBK_PHASE_CLOCK
@@ -773,37 +771,14 @@ hipError_t launch_stream(hipStream_t s, unsigned nk, double* d_H, int n, double*
 
 }  // namespace
 
-// sizes the own solvers of this file and of tbk_eig_band.hip cover between them: the one-stage kernel here up to 512
-// orbitals, the two-stage reduction up to band_maxn() = 4096 (round 5: the launch chain of band_xl_* above 1024; with
-// TBK_BAND_XL=0 the range ends at 1024 again); rocSOLVER above
-bool tbk_eig_stream_supported(int n) { return n > 64 && (n <= ST_MAXN || tbk_eig_band_supported(n)); }
-
-// two-stage reduction (tbk_eig_band.hip) unless TBK_BAND=0 asks for the one-stage kernel of this file
-bool tbk_eig_two_stage(const tbk_model* m) {
-    static const bool band = [] {
-        const char* v = getenv("TBK_BAND");
-        return v == nullptr || atoi(v) != 0;
-    }();
-    if (m->n_orb > ST_MAXN) return tbk_eig_band_supported(m->n_orb);  // above 512 orbitals there is no one-stage kernel
-    return band && tbk_eig_band_preferred(m->n_orb);
-}
-
-// d_de: d[nk][n] followed by e[nk][n]; d_H (upper triangle of the row-major H) is overwritten
-int tbk_launch_tridiag_stream(tbk_model* m, hipStream_t s, double* d_H, int64_t nk, double* d_de, int method) {
-    const int n = m->n_orb;
+// The one-stage reduction (plans of the EIG_ONE_STAGE family).  d_de: d[nk][n] followed by e[nk][n]; d_H (upper triangle of
+// the row-major H) is overwritten
+int tbk_launch_tridiag_stream(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int64_t nk, double* d_de) {
+    const int n = plan.n;
     if (nk == 0) return TBK_OK;
-    if (n > ST_MAXN && method == TBK_REDUCE_ONE_STAGE) {
+    if (n > ST_MAXN) {
         tbk_set_error("the one-stage reduction handles n_orb <= %d (n_orb = %d)", ST_MAXN, n);
         return TBK_ERR_ARGUMENT;
-    }
-    if (method == TBK_REDUCE_TWO_STAGE || (method == TBK_REDUCE_AUTO && tbk_eig_two_stage(m))) {  // both stages in order on this stream (single-chunk calls, tbk_tridiagonal_reduce)
-        TBK_CHECK(m->ws_band.reserve((size_t)nk * tbk_band_scratch_per_matrix(n)));
-        TBK_CHECK(tbk_band_xl_reserve(m, nk));
-        if (tbk_band_fused(n) && !tbk_band_split(m, nk)) return tbk_launch_band_reduce(m, s, d_H, nk, m->ws_band.ptr, nullptr, d_de);
-        TBK_CHECK(m->ws_bandmat[0].reserve((size_t)nk * tbk_band_bytes_per_matrix(n)));
-        if (tbk_band_xl_grouped(n, nk)) return tbk_launch_band_reduce(m, s, d_H, nk, m->ws_band.ptr, m->ws_bandmat[0].ptr, d_de);
-        TBK_CHECK(tbk_launch_band_reduce(m, s, d_H, nk, m->ws_band.ptr, m->ws_bandmat[0].ptr));
-        return tbk_launch_band_chase(m, s, m->ws_bandmat[0].ptr, nk, d_de);
     }
     double* d_D = d_de;
     double* d_Eo = d_de + (size_t)nk * n;
@@ -815,10 +790,10 @@ int tbk_launch_tridiag_stream(tbk_model* m, hipStream_t s, double* d_H, int64_t 
     // block (tbk_launch_tridiag_tail64).
     // above 128 orbitals: this kernel goes down to the trailing 128 x 128 block, the eight-wave register kernel to
     // 64 x 64 (TBK_REG128=0: this kernel down to 64)
-    const bool via128 = n > 128 && tbk_eig_reg128_supported(128);
+    const bool via128 = plan.via128;
     const int n_steps = via128 ? n - 128 : n - 64;
-    if (tbk_eig_reg128_supported(n))  // round 3: 65 .. 128 orbitals never leave the registers
-        TBK_CHECK(tbk_launch_tridiag_reg128(s, d_H, n, nk, d_D, d_Eo, (int64_t)n * n * 2, n, 0));
+    if (plan.reg128)  // round 3: 65 .. 128 orbitals never leave the registers
+        TBK_CHECK(tbk_launch_tridiag_reg128(plan, s, d_H, n, nk, d_D, d_Eo, (int64_t)n * n * 2, n, 0));
     else if (n <= 128)
         TBK_HIP((launch_stream<2, 4, 256>(s, (unsigned)nk, d_H, n, d_D, d_Eo, n_steps)));
     else if (n <= 192)
@@ -829,35 +804,23 @@ int tbk_launch_tridiag_stream(tbk_model* m, hipStream_t s, double* d_H, int64_t 
         TBK_HIP((launch_stream<6, 4, 512>(s, (unsigned)nk, d_H, n, d_D, d_Eo, n_steps)));
     else
         TBK_HIP((launch_stream<8, 4, 512>(s, (unsigned)nk, d_H, n, d_D, d_Eo, n_steps)));
-    if (via128) TBK_CHECK(tbk_launch_tridiag_reg128(s, d_H, 128, nk, d_D, d_Eo, (int64_t)n * n * 2, n, n - 128));
-    TBK_CHECK(tbk_launch_tridiag_tail64(s, d_H, nk, d_D, d_Eo, n, m->call_nk));
+    if (via128) TBK_CHECK(tbk_launch_tridiag_reg128(plan, s, d_H, 128, nk, d_D, d_Eo, (int64_t)n * n * 2, n, n - 128));
+    TBK_CHECK(tbk_launch_tridiag_tail64(plan, s, d_H, nk, d_D, d_Eo, n));
     return TBK_OK;
 }
 
 // eigenvalues of the tridiagonals d_de = (d[nk][n], e[nk][n]) -> d_E[nk][n], ascending
-int tbk_launch_bisect(tbk_model* m, hipStream_t s, const double* d_de, int64_t nk, double* d_E) {
-    const int n = m->n_orb;
+int tbk_launch_bisect(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, const double* d_de, int64_t nk, double* d_E) {
+    const int n = plan.n;
     if (nk == 0) return TBK_OK;
     StageTimer t(m, TBK_T_QL, s);
     const int n_pad = (n + 63) / 64 * 64;
     const size_t lds = 2 * (size_t)n_pad * sizeof(double) + (size_t)n_pad * sizeof(int);  // (d, e^2) + the shared round's counts
     const double* d_e = d_de + (size_t)nk * n;
-    // a few matrices cannot fill the chip with one lane per eigenvalue: spend lanes on shorter chains instead.  By the
-    // size of the CALL, not of this chunk: TBK_OPT_K_CHUNK must not change results, and the variants differ in the
-    // last bit.  Small matrices get the lanes their first wave would leave idle anyway (8 orbitals: 8 per eigenvalue).
-    const int64_t call_nk = std::max(m->call_nk, nk);
-    int lpe = call_nk <= 32 ? 16 : call_nk <= 512 ? 4 : 1;
+    // lanes per eigenvalue: the plan's (by the size of the call); the workgroups that takes are worked out here
+    const int lpe = plan.bisect_lanes;
     unsigned threads, parts = 1;
     if (n > 64) {
-        // Above 64 orbitals (round 5): 16 or 4 lanes per eigenvalue at every size, over as many workgroups as that takes (until
-        // round 4 the lanes had to fit ONE workgroup: 4 at 256 orbitals, 2 at 512 -- 31 sweeps where one lane with its secant steps
-        // needs ~20 --, 1 above), while the call stays a few waves per CU: the sweeps are latency chains and idle lanes are free,
-        // busy ones are not.  Measured (tools/bench_single_k.py, us of this stage, 1 / 4 / 16 lanes): one k-point at 256 orbitals
-        // 188 / 160 / 114, at 512 414 / 370 / 244, at 1024 1348 / 1118 / 772; 64 k-points at 512 orbitals 462 / 404 / 800, at 1024
-        // 1410 / 1300 / 3230, at 1536 1.8 / 3.5 ms / --.
-        const int64_t eigenvalues = call_nk * (int64_t)n;
-        if (lpe == 16 && eigenvalues * 16 > (int64_t(1) << 17)) lpe = 4;
-        if (lpe == 4 && eigenvalues * 4 > (int64_t(1) << 18)) lpe = 1;
         if (lpe > 1) {
             threads = (unsigned)std::min(1024, n_pad);  // (the shared first round: one sweep per thread up to 1024 orbitals)
             const unsigned per = threads / (unsigned)lpe;  // eigenvalues per workgroup (>= the kernel's m_per = ceil(n / parts))
@@ -871,8 +834,6 @@ int tbk_launch_bisect(tbk_model* m, hipStream_t s, const double* d_de, int64_t n
             }
         }
     } else {
-        while (lpe < 16 && n * lpe * 2 <= 64) lpe *= 2;
-        while (lpe > 1 && n * lpe > 1024) lpe /= 2;
         threads = (unsigned)((n * lpe + 63) / 64 * 64);
         // a few matrices with several lanes per eigenvalue: up to four workgroups per matrix (each still loads all of (d, e),
         // so at least n threads), their waves on different CUs

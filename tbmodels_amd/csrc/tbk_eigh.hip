@@ -365,12 +365,10 @@ extern "C" int tbk_eigh_device(tbk_model* m, const double* d_k, int64_t nk, int 
     TBK_LOCK(m);
     if (nk == 0 || m->n_orb == 0) return TBK_OK;
     TBK_ARG(d_k && d_E && d_U, "k / E / U is NULL");
-    if (m->eigensolver == TBK_EIG_WAVE && !tbk_eig_small_supported(m->n_orb)) {
-        tbk_set_error("TBK_EIG_WAVE handles n_orb <= 64 only (n_orb = %d)", m->n_orb);
-        return TBK_ERR_ARGUMENT;
-    }
+    TBK_CHECK(tbk_eig_check_option(m));
     TBK_HIP(hipSetDevice(m->device));
-    const bool own = m->eigensolver != TBK_EIG_ROCSOLVER && tbk_eig_small_supported(m->n_orb);
+    // eigenvectors: the Jacobi kernel where eigenval takes the register-resident family, rocSOLVER everywhere else
+    const bool own = tbk_eig_plan(m->n_orb, m->eigensolver, nk).family == EIG_REGISTER;
     int64_t chunk = choose_chunk(m, nk, true);
     const size_t n = (size_t)m->n_orb, nn2 = n * n * 2;
     if (!own) {

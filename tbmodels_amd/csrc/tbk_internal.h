@@ -74,9 +74,16 @@ void tbk_set_error(const char* fmt, ...);
 // ------------------------------------------------------------------------------------------------
 // Environment switches.  The library reads only the switches a test uses as an independent cross-check of the product path
 // (TBK_BAND, TBK_BAND_SPLIT, TBK_BAND_XL, TBK_BAND_XL_FROM, TBK_CHASE_WINDOW, TBK_REG128, TBK_REG128_NW2,
-// TBK_GATHER_BLOCK_ROWS -- the table in DESIGN.md section 6).  Variants that were built, measured and dropped are not in the
-// sources; their measurements are in DESIGN_LOG.md and their code in the git history.
+// TBK_GATHER_BLOCK_ROWS -- the table in DESIGN.md section 6).  The seven eigensolver switches are read once per process by
+// tbk_eig_env (tbk_eig_plan.hip) and consulted by tbk_eig_plan alone; TBK_GATHER_BLOCK_ROWS is read in tbk_comm.hip.  Variants
+// that were built, measured and dropped are not in the sources; their measurements are in DESIGN_LOG.md and their code in the
+// git history.
 // ------------------------------------------------------------------------------------------------
+struct tbk_eig_env_t {  // TBK_BAND, _BAND_SPLIT, _BAND_XL, _CHASE_WINDOW, _REG128, _REG128_NW2 (0: off), TBK_BAND_XL_FROM=n
+    bool band = true, band_split = true, band_xl = true, chase_window = true, reg128 = true, reg128_nw2 = true;
+    int band_xl_from = 1024;
+};
+const tbk_eig_env_t& tbk_eig_env();
 
 // ------------------------------------------------------------------------------------------------
 // dynamic LDS above the 64 KiB default: hipFuncSetAttribute acts on the CURRENT device's copy of the
@@ -150,7 +157,6 @@ struct tbk_model {
     // (ctypes drops the GIL for the duration of a call).  Recursive: the host-buffer calls go through the device ones.
     std::recursive_mutex mu;
     int device = 0;
-    int64_t call_nk = 0;  // k-points of the eigenvalue call in progress: choices that must not depend on the chunking
     int n_cu = 256;  // compute units of the device (workgroup slots per round = 2 * n_cu for the H(k) kernel)
     int dim = 0;
     int n_orb = 0;
@@ -371,37 +377,80 @@ int tbk_eig_batched(tbk_model* m, double* d_H, int64_t nk, double* d_E);    // f
 // tbk_eigh.hip: the checks of the eigh entry points that need no model (convention, pos, nk)
 int tbk_eigh_check_arguments(int64_t nk, int convention, const double* pos);
 
-// tbk_eig_stream.hip
-bool tbk_eig_stream_supported(int n);
-// method: TBK_REDUCE_AUTO (what eigenval takes), _ONE_STAGE, _TWO_STAGE (tbk.h)
-int tbk_launch_tridiag_stream(tbk_model* m, hipStream_t s, double* d_H, int64_t nk, double* d_de, int method = 0);
-int tbk_launch_bisect(tbk_model* m, hipStream_t s, const double* d_de, int64_t nk, double* d_E);
+// ------------------------------------------------------------------------------------------------
+// The eigensolver's plan (tbk_eig_plan.hip).  How the matrices of one eigenvalue CALL are reduced and solved: tbk_eig_plan is
+// the only place that chooses, the entry points make the plan once and every launcher picks its instantiation from its fields.
+// A function of the orbital count, the model's `eigensolver` option, the k-points of the call, the requested method (tbk.h:
+// TBK_REDUCE_AUTO is what eigenval takes) and the environment switches, of nothing else.  Of the CALL, never of a chunk: several
+// of the variants differ in the last bit, and TBK_OPT_K_CHUNK must not change a result (tests/test_gpu_parity.py).
+// ------------------------------------------------------------------------------------------------
+constexpr int ST_MAXN = 512;              // the one-stage streaming kernel (tbk_eig_stream.hip): 64 < n <= 512
+constexpr int BAND_ONE_WG_MAXN = 1024;    // one workgroup per matrix: two rows per thread of 512 threads, X (8 complex per row) is 128 KiB of LDS
+constexpr int BAND_LDS_CHASE_MAXN = 512;  // above: the chase keeps its 16 diagonals in global memory
+// own kernels or not: rocSOLVER (TBK_EIG_ROCSOLVER, or a size / method they do not cover), register-resident (n <= 64,
+// tbk_eig_small.hip), one-stage streaming (tbk_eig_stream.hip), two-stage dense -> band -> tridiagonal (tbk_eig_band*.hip)
+enum EigFamily { EIG_ROCSOLVER, EIG_REGISTER, EIG_ONE_STAGE, EIG_TWO_STAGE };
+// the second stage's 16 working diagonals: in LDS (band_chase4_kernel), in a cyclic LDS window of 272 columns / 16 sweep slots or
+// of 512 columns / 32 slots (band_chase4w_kernel), in global memory (band_chase4g_kernel)
+enum EigChase { EIG_CHASE_LDS, EIG_CHASE_WINDOW16, EIG_CHASE_WINDOW32, EIG_CHASE_GLOBAL };
+struct tbk_eig_plan_t {
+    int n = 0;                   // orbitals
+    int64_t call_nk = 0;         // k-points of the call
+    EigFamily family = EIG_ROCSOLVER;
+    bool split_on = false;       // register kernels (also the 64 x 64 tail of one-stage): the trailing 32 x 32 block as a second launch
+    bool reg128 = false;         // one-stage, 65 - 128 orbitals: the 128-row register kernel instead of the streaming one
+    bool via128 = false;         // one-stage above 128: the streaming kernel hands over at the trailing 128 x 128 block (else 64 x 64)
+    bool reg128_nw2 = false;     // the 128-row register kernel on four waves up to 96 rows (else eight at every size)
+    bool chain = false;          // first stage: the launch chain of band_xl_* (else one workgroup per matrix)
+    bool chain_by_size = false;  // ... at every call size (above TBK_BAND_XL_FROM orbitals): batches go in groups, tbk_eig_xl_groups
+    bool wide = false;           // one workgroup per matrix: its eight-wave, row-per-thread form
+    bool fused = false;          // second stage: inside the first-stage kernel (else a launch of its own)
+    EigChase chase = EIG_CHASE_LDS;
+    bool chase_buffer = false;   // a matrix' band buffer carries the 16 working diagonals behind the compact band
+    bool bisect = false;         // tridiagonal stage: bisection (else the lane-per-matrix QL)
+    int bisect_lanes = 1;        // lanes per eigenvalue of the bisection kernel
+    // bytes per matrix of the workspaces (0: the path does not use them); band_stride: bytes between the matrices of a band buffer
+    size_t band_stride = 0, ws_band = 0, ws_bandmat = 0, ws_xl = 0;
+    bool own() const { return family != EIG_ROCSOLVER; }
+};
+tbk_eig_plan_t tbk_eig_plan(int n_orb, int eigensolver, int64_t call_nk, int method = TBK_REDUCE_AUTO);
+int tbk_eig_check_option(const tbk_model* m);  // TBK_EIG_WAVE is the register-resident kernels: an error above 64 orbitals
+// the range checks of the argument validation: 1 .. 64; 65 .. 4096 (1024 with TBK_BAND_XL=0: the two-stage kernels cover all of it)
+bool tbk_eig_small_supported(int n);
+bool tbk_eig_band_supported(int n);
+// What depends on one LAUNCH, not on the call, takes the plan and keeps the chunk length out of it: the groups a launch of nk
+// matrices above TBK_BAND_XL_FROM orbitals goes in (per matrix the same launches in the same order, the same bits).  The others
+// are arguments in tbk_api.hip: `beside_ql`, "the last chunk of a pipeline bisects", and tbk_eig_reduce's d_band (the second
+// stage of a chunk goes to the tridiagonal stream: that needs a following chunk).
+int tbk_eig_xl_groups(const tbk_eig_plan_t& plan, int64_t nk);
 size_t tbk_eig_scratch_per_k(const tbk_model* m);
-int tbk_band_xl_reserve(tbk_model* m, int64_t max_nk);  // tbk_eig_band.hip: ws_xl for chunks of up to max_nk matrices
+// ws_band / ws_xl for launches of up to max_nk matrices and `bandmats` of the ws_bandmat (one per chunk in flight), from the
+// plan's byte counts.  In front of the pipeline, never inside a launch (tbk_eig_band_xl.hip)
+int tbk_eig_reserve(tbk_model* m, const tbk_eig_plan_t& plan, int64_t max_nk, int bandmats);
+// Reduce nk matrices on stream s per the plan: d_H (upper triangle of the row-major H) is overwritten, d_de receives d[nk][n]
+// followed by e[nk][n].  d_band != NULL (two-stage, second stage a launch of its own): the first stage alone, the band goes
+// there and the caller runs tbk_launch_band_chase; else both stages in order on s.
+int tbk_eig_reduce(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int64_t nk, double* d_de, void* d_band = nullptr);
+
+// tbk_eig_stream.hip: the one-stage reduction (64 < n <= 512) and the bisection
+int tbk_launch_tridiag_stream(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int64_t nk, double* d_de);
+int tbk_launch_bisect(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, const double* d_de, int64_t nk, double* d_E);
 
 // tbk_eig_band.hip: two-stage reduction (dense -> band on the matrix pipe, band -> tridiagonal in LDS)
-bool tbk_eig_band_supported(int n);
-bool tbk_eig_band_preferred(int n);
 size_t tbk_band_scratch_per_matrix(int n);
-size_t tbk_band_bytes_per_matrix(int n);
-size_t tbk_band_xl_buffer_per_matrix(int n);  // the second matrix buffer of the launch chain above 1024 orbitals
-bool tbk_eig_two_stage(const tbk_model* m);  // the band path applies to this model (64 < n_orb <= band_maxn() = 4096 -- 1024 with TBK_BAND_XL=0 --, not TBK_BAND=0)
-// d_de_fused != NULL: every workgroup runs the second stage for its matrix too and writes (d, e); d_band is not used
-int tbk_launch_band_reduce(tbk_model* m, hipStream_t s, double* d_H, int64_t nk, void* d_vw, void* d_band,
+size_t tbk_band_bytes_per_matrix(int n, bool chase_buffer);
+// d_de_fused != NULL: every workgroup runs the second stage for its matrix too and writes (d, e); d_band is not used.  (A plan
+// on the launch chain: the second stage of every group behind its first stage; d_band is used.)
+int tbk_launch_band_reduce(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int64_t nk, void* d_vw, void* d_band,
                            double* d_de_fused = nullptr);
-bool tbk_band_fused(int n);  // both stages in one kernel (<= 256 orbitals) or two launches, the second one overlappable
-// calls of a few matrices: the first stage as a chain of launches, every tile pass on several CUs (never fused with stage two)
-bool tbk_band_split(const tbk_model* m, int64_t nk);
-bool tbk_band_xl_grouped(int n, int64_t nk);  // above 1024 orbitals, a batch: tbk_launch_band_reduce(..., d_band, d_de) runs both stages group by group
-int tbk_launch_band_chase(tbk_model* m, hipStream_t s, const void* d_band, int64_t nk, double* d_de);
+int tbk_launch_band_chase(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, const void* d_band, int64_t nk, double* d_de);
 
 // tbk_eig_small.hip
-bool tbk_eig_small_supported(int n);
 // (above 32 orbitals the head of every matrix in d_H is overwritten with its trailing 32 x 32 block: H is consumed)
-int tbk_launch_tridiag(tbk_model* m, hipStream_t s, double* d_H, int64_t nk, double* d_de);
-bool tbk_eig_reg128_supported(int n);  // 64 < n <= 128: the eight-wave register kernel does the first n - 64 steps
-int tbk_launch_tridiag_reg128(hipStream_t s, double* d_H, int n, int64_t nk, double* d_D, double* d_E, int64_t h_stride, int ldd, int off);
-int tbk_launch_tridiag_tail64(hipStream_t s, double* d_H, int64_t nk, double* d_D, double* d_E, int n_full, int64_t call_nk);  // tbk_eig_stream.hip hands over here
+int tbk_launch_tridiag(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int64_t nk, double* d_de);
+// 64 < n <= 128: the eight-wave register kernel does the first n - 64 steps
+int tbk_launch_tridiag_reg128(const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int n, int64_t nk, double* d_D, double* d_E, int64_t h_stride, int ldd, int off);
+int tbk_launch_tridiag_tail64(const tbk_eig_plan_t& plan, hipStream_t s, double* d_H, int64_t nk, double* d_D, double* d_E, int n_full);  // tbk_eig_stream.hip hands over here
 // `beside_ql`: this launch shares the chip with another QL launch (the tail of the chunk pipeline): use
 // half-size workgroups (32 KiB of LDS) that fit next to two resident 64 KiB ones.
 int tbk_launch_ql(tbk_model* m, hipStream_t s, const double* d_de, int64_t nk, double* d_E, bool beside_ql = false);

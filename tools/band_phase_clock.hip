@@ -9,6 +9,11 @@
 #include "../tbmodels_amd/csrc/tbk_eig_band.hip"
 #include "../tbmodels_amd/csrc/tbk_eig_band_chase.hip"
 #include "../tbmodels_amd/csrc/tbk_eig_band_xl.hip"
+#include "../tbmodels_amd/csrc/tbk_eig_plan.hip"
+
+// (tbk_eig_reduce names the launchers of every family; this driver builds the two-stage ones only)
+int tbk_launch_tridiag(tbk_model*, const tbk_eig_plan_t&, hipStream_t, double*, int64_t, double*) { return TBK_ERR_ARGUMENT; }
+int tbk_launch_tridiag_stream(tbk_model*, const tbk_eig_plan_t&, hipStream_t, double*, int64_t, double*) { return TBK_ERR_ARGUMENT; }
 
 void tbk_set_error(const char*, ...) {}
 int DevBuf::reserve(size_t) { return 0; }
@@ -29,8 +34,13 @@ int main(int argc, char** argv) {
     hipMalloc(&d_H0, (size_t)nk * n * n * 16);
     hipMalloc(&d_H, (size_t)nk * n * n * 16);
     hipMalloc(&d_de, (size_t)nk * n * 16);
-    hipMalloc(&d_vw, (size_t)nk * tbk_band_scratch_per_matrix(n));
-    hipMalloc(&d_band, (size_t)nk * tbk_band_bytes_per_matrix(n));
+    const tbk_eig_plan_t plan = tbk_eig_plan(n, TBK_EIG_AUTO, nk, TBK_REDUCE_TWO_STAGE);
+    if (plan.family != EIG_TWO_STAGE || plan.chain) {
+        printf("n=%d: not a size of the one-workgroup two-stage kernels\n", n);
+        return 1;
+    }
+    hipMalloc(&d_vw, (size_t)nk * plan.ws_band);
+    hipMalloc(&d_band, (size_t)nk * plan.band_stride);
     for (int k = 0; k < nk; ++k) hipMemcpy(d_H0 + (size_t)k * n * n * 2, h.data(), h.size() * 8, hipMemcpyHostToDevice);
     tbk_model m;
     m.n_orb = n;
@@ -45,11 +55,11 @@ int main(int argc, char** argv) {
         hipEventCreate(&b);
         hipDeviceSynchronize();
         hipEventRecord(a, nullptr);
-        if (tbk_band_fused(n)) {
-            tbk_launch_band_reduce(&m, nullptr, d_H, nk, d_vw, nullptr, d_de);
+        if (plan.fused) {
+            tbk_launch_band_reduce(&m, plan, nullptr, d_H, nk, d_vw, nullptr, d_de);
         } else {
-            tbk_launch_band_reduce(&m, nullptr, d_H, nk, d_vw, d_band);
-            tbk_launch_band_chase(&m, nullptr, d_band, nk, d_de);
+            tbk_launch_band_reduce(&m, plan, nullptr, d_H, nk, d_vw, d_band);
+            tbk_launch_band_chase(&m, plan, nullptr, d_band, nk, d_de);
         }
         hipEventRecord(b, nullptr);
         hipDeviceSynchronize();

@@ -1,18 +1,14 @@
 // Cycles per phase of one Householder step of herm_tridiag_stream_kernel, measured on workgroup 0 while the whole
 // grid runs (so the memory system is loaded as in production).  Build + run on the GPU box:
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -DTBK_PHASE_CLOCK -Iinclude -Itbmodels_amd/csrc \
-//         tools/stream_phase_clock.hip -o /tmp/spc -lrocblas && /tmp/spc 80 36864
+//         tools/stream_phase_clock.hip -o /tmp/spc -Ltbmodels_amd -ltbk -Wl,-rpath,$PWD/tbmodels_amd -lrocblas && /tmp/spc 80 36864
+// (the plan and the register kernels the streaming kernel hands over to come from the built library; TBK_REG128=0 keeps
+// sizes up to 128 orbitals on the streaming kernel)
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "../tbmodels_amd/csrc/tbk_eig_stream.hip"
-
-void tbk_set_error(const char*, ...) {}
-int DevBuf::reserve(size_t) { return 0; }
-void DevBuf::release() {}
-StageTimer::StageTimer(tbk_model* m_, int, hipStream_t s) : m(m_), on(false), stream(s) {}
-StageTimer::~StageTimer() {}
 
 int main(int argc, char** argv) {
     const int n = argc > 1 ? atoi(argv[1]) : 80;
@@ -28,6 +24,11 @@ int main(int argc, char** argv) {
     for (int k = 0; k < nk; ++k) hipMemcpy(d_H + (size_t)k * n * n * 2, h.data(), h.size() * 8, hipMemcpyHostToDevice);
     tbk_model m;
     m.n_orb = n;
+    const tbk_eig_plan_t plan = tbk_eig_plan(n, TBK_EIG_AUTO, nk, TBK_REDUCE_ONE_STAGE);
+    if (plan.family != EIG_ONE_STAGE) {
+        printf("n=%d: not a size of the one-stage kernel\n", n);
+        return 1;
+    }
     unsigned long long zero[16] = {0};
     for (int rep = 0; rep < 2; ++rep) {
         hipMemcpyToSymbol(HIP_SYMBOL(tbk_phase_clock), zero, sizeof(zero));
@@ -35,7 +36,7 @@ int main(int argc, char** argv) {
         hipEventCreate(&a);
         hipEventCreate(&b);
         hipEventRecord(a, nullptr);
-        tbk_launch_tridiag_stream(&m, nullptr, d_H, nk, d_de);
+        tbk_launch_tridiag_stream(&m, plan, nullptr, d_H, nk, d_de);
         hipEventRecord(b, nullptr);
         hipDeviceSynchronize();
         float ms = 0;
