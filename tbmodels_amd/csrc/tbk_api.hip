@@ -1,8 +1,9 @@
 // tbk_api.hip -- the C ABI of include/tbk.h: staging, the chunked k pipeline, host/device entry
 // points.  Kernels live in tbk_phase.hip / tbk_stage.hip / tbk_hk_dense.hip / tbk_hk_csr.hip, the
 // eigensolver's in tbk_eig_small.hip / tbk_eig_stream.hip / tbk_eig_band*.hip (tbk_eig.hip: the rocSOLVER
-// path), and which of them a call takes is tbk_eig_plan's (tbk_eig_plan.hip); this file only owns memory,
-// streams and ordering.
+// path), and which of them a call takes is tbk_eig_plan's (tbk_eig_plan.hip); a k list that folds is driven by
+// tbk_folded_call (tbk_fold.hip), which hands the pipeline here its H(k) builder.  This file only owns memory, streams
+// and ordering.
 
 #include <algorithm>
 #include <cmath>
@@ -471,7 +472,7 @@ int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
     int64_t cap = mid ? 131072 : 32768;
     if (n < 64) cap *= std::min<int64_t>(32, (64 / n) * (64 / n));
     chunk = std::max<int64_t>(TBK_BM, std::min<int64_t>(chunk, cap));
-    tbk_hk_plan_t plan = tbk_hk_plan(m, std::min(chunk, nk), false);
+    tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), std::min(chunk, nk), false);
     if (plan.path == HK_PATH_STRASSEN2) {
         // The first two-level chunk of a model builds the operand blocks of the second level (fill_rows): decided here, where
         // the memory is counted -- blocks above a quarter of the free memory are skipped, and the model stays on one level.
@@ -488,7 +489,7 @@ int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
             const int64_t fit = (int64_t)(free2 / 4) / per_k_s / TBK_BM * TBK_BM;
             chunk = std::max<int64_t>(TBK_BM, std::min(chunk, fit));
         }
-        plan = tbk_hk_plan(m, std::min(chunk, nk), false);
+        plan = tbk_hk_plan(m, tbk_staged_operand(m), std::min(chunk, nk), false);
     }
     if (plan.path == HK_PATH_STRASSEN) {
         // a Strassen chunk also holds its phase rows 7/4 times (As[7][K2 / 2][Mh]) and the seven half-size products
@@ -503,19 +504,19 @@ int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
     return std::min(chunk, round_up(nk, TBK_BM));
 }
 
-// The phase rows of a chunk of plan.nk k-points for its plan, in ws_phase (reserved also when the H(k) kernel makes them).
+// The phase rows of a chunk of plan.nk k-points for its plan (the lattice of plan.op), in ws_phase (reserved also when the H(k) kernel makes them).
 int fill_rows(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_k) {
     TBK_CHECK(m->ws_phase.reserve((size_t)plan.row_doubles * sizeof(double)));
     double* d_A = m->ws_phase.as<double>();
     if (plan.rows == HK_ROWS_NONE) return TBK_OK;
-    if (plan.rows == HK_ROWS_STRASSEN) return tbk_launch_phase_strassen(m, d_k, plan.nk, d_A);  // the seven blocks of its left operands
+    if (plan.rows == HK_ROWS_STRASSEN) return tbk_launch_phase_strassen(m, plan.op, d_k, plan.nk, d_A);  // the seven blocks of its left operands
     if (plan.rows == HK_ROWS_STRASSEN2) {
         TBK_CHECK(tbk_stage_strassen2(m));  // the right operands of the second level, on the model's first two-level chunk
-        return tbk_launch_phase_strassen2(m, d_k, plan.nk, d_A);  // the 49 blocks of its left operands
+        return tbk_launch_phase_strassen2(m, plan.op, d_k, plan.nk, d_A);  // the 49 blocks of its left operands
     }
     if (plan.rows == HK_ROWS_MONOMIAL)
-        return tbk_launch_monomials(m->stream, m->d_powers, m->dim, m->n_r, m->k2, d_k, plan.nk, plan.nk_pad, d_A);
-    return tbk_launch_phase(m, d_k, plan.nk, plan.nk_pad, d_A);
+        return tbk_launch_monomials(m->stream, m->d_powers, plan.op.dim, plan.op.n_r, plan.op.k2, d_k, plan.nk, plan.nk_pad, d_A);
+    return tbk_launch_phase(m, plan.op, d_k, plan.nk, plan.nk_pad, d_A);
 }
 
 // H(k) of the chunk whose rows fill_rows made for the same plan
@@ -541,7 +542,7 @@ extern "C" int tbk_hamilton_device(tbk_model* m, const double* d_k, int64_t nk, 
     const size_t nn2 = (size_t)m->n_orb * m->n_orb * 2;
     for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
         const int64_t nkc = std::min(chunk, nk - c0);
-        const tbk_hk_plan_t plan = tbk_hk_plan(m, nkc, false);
+        const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), nkc, false);
         const double* kc = d_k + c0 * m->dim;
         TBK_CHECK(fill_rows(m, plan, kc));
         const double* d_orb = nullptr;
@@ -607,28 +608,6 @@ static std::vector<int64_t> chunk_schedule(tbk_model* m, int64_t nk, int64_t chu
 // Fills H for k-points [c0, c0 + nkc) of the call (phase rows + contraction on the main stream).
 using HBuilder = std::function<int(int64_t c0, int64_t nkc, double* d_H)>;
 
-// Chunks of a folded call: whole runs (mesh planes) packed up to the chunk size -- every run a chunk cuts costs a second
-// fold pass, ragged mesh lines and a handful of small launches on both sides of the cut (the 100^3 mesh in chunks of 30 000
-// = three planes instead of 32 768: 150.8 -> 143.6 ms).  Runs longer than a chunk are cut into chunk-sized pieces.
-static std::vector<int64_t> run_schedule(const std::vector<int64_t>& runs, int64_t chunk) {
-    std::vector<int64_t> out;
-    int64_t cur = 0;
-    for (size_t r = 0; r + 1 < runs.size(); ++r) {
-        int64_t len = runs[r + 1] - runs[r];
-        if (cur > 0 && cur + len > chunk) {
-            out.push_back(cur);
-            cur = 0;
-        }
-        while (len > chunk) {
-            out.push_back(chunk);
-            len -= chunk;
-        }
-        cur += len;
-    }
-    if (cur > 0) out.push_back(cur);
-    return out;
-}
-
 static int eigenval_wave_pipeline(tbk_model* m, const tbk_eig_plan_t& plan, const double* d_k, int64_t nk, double* d_E,
                                   const HBuilder* builder = nullptr, const std::vector<int64_t>* runs = nullptr) {
     // The direct builder in two halves: the phase rows of a chunk only need the previous contraction to be done with the
@@ -638,7 +617,7 @@ static int eigenval_wave_pipeline(tbk_model* m, const tbk_eig_plan_t& plan, cons
     int64_t rows_ready_for = -1;  // c0 of the chunk whose phase rows are in ws_phase, made for rows_plan
     tbk_hk_plan_t rows_plan;
     const auto prepare_rows = [&](int64_t c0, int64_t nkc) -> int {
-        rows_plan = tbk_hk_plan(m, nkc, false);
+        rows_plan = tbk_hk_plan(m, tbk_staged_operand(m), nkc, false);
         if (rows_plan.rows != HK_ROWS_NONE) TBK_CHECK(fill_rows(m, rows_plan, d_k + c0 * m->dim));
         rows_ready_for = c0;
         return TBK_OK;
@@ -744,214 +723,16 @@ static int eigenval_wave_pipeline(tbk_model* m, const tbk_eig_plan_t& plan, cons
     return TBK_OK;
 }
 
-// k lists with long runs of one shared component (grids in meshgrid order, stacks of planes): every run is
-// evaluated on the model folded along that component (tbk_fold.hip).  Returns TBK_OK with *done = false when the
-// list does not qualify.
+// k lists with long runs of one shared component (grids in meshgrid order, stacks of planes): the pipeline above with the
+// H(k) builder of tbk_folded_call (tbk_fold.hip).  Returns TBK_OK with *done = false when the list does not qualify.
 static int eigenval_folded(tbk_model* m, const tbk_eig_plan_t& eig_plan, const double* d_k, const double* h_k, int64_t nk, double* d_E,
                            bool* done) {
     *done = false;
-    if (!m->fold_enabled || m->sparse || m->kdotp || m->dim < 2 || m->n_r < 64 || nk < 1024) return TBK_OK;
-    // Device-resident lists are never read back (include/tbk.h: the device entry points enqueue and return): the run
-    // structure comes from the caller's host copy of the list (tbk_eigenval / tbk_eigenval_device_hint) or not at all.
-    if (h_k == nullptr) return TBK_OK;
-    std::vector<int64_t> runs;
-    const int f = tbk_fold_choose(m, h_k, nk, runs);
-    if (f < 0) return TBK_OK;
-    const int dim = m->dim;
-    TBK_CHECK(m->ws_kfold.reserve((size_t)nk * (dim - 1) * sizeof(double)));
-    double* d_k2 = m->ws_kfold.as<double>();
-    TBK_CHECK(tbk_fold_drop_component(m, d_k, dim, f, nk, d_k2));
-    const size_t nn2 = (size_t)m->n_orb * m->n_orb * 2;
-    // the chunk pipeline (schedule, overlap of the tridiagonal stage) runs over the whole list; only the H(k) of a
-    // chunk is assembled run by run, each piece on the model folded for its run.
-    // Runs are folded a group at a time (one pass over Bt for up to 16 of them); `group_lo` is the first run of the
-    // group whose operands are in the plan's buffer.
-    const int64_t n_runs = (int64_t)runs.size() - 1;
-    const int group = tbk_fold_group_size();
-    int64_t group_lo = -1;
-    tbk_fold_plan_t& plan1 = m->fold[f];
-    std::vector<int> reduced;  // original component of every reduced one
-    for (int d = 0; d < dim; ++d)
-        if (d != f) reduced.push_back(d);
-
-    // [lo, hi) of one run, `m` folded for that run: phase rows + contraction of the (dim - 1)-dimensional model
-    auto piece_plane = [&](int64_t lo, int64_t hi, double* d_Hp) -> int {
-        const tbk_hk_plan_t plan = tbk_hk_plan(m, hi - lo, true);
-        TBK_CHECK(fill_rows(m, plan, d_k2 + lo * (dim - 1)));
-        return build_h(m, plan, HK_TRI, 2, d_k2 + lo * (dim - 1), nullptr, d_Hp);
-    };
-
-    // Second level (meshes): inside a plane the k-points come in LINES -- equal-length sub-runs of one more shared
-    // component whose remaining coordinates repeat from line to line.  Every line is a (dim - 2)-dimensional model
-    // (13 instead of 313 lattice vectors at the headline shape); all lines of the piece go through ONE launch with
-    // per-line operands and shared phase rows (tbk_launch_hk_dense_lines).  Ragged ends of the piece, and anything
-    // that does not have this structure, take piece_plane.
-    struct LineInfo {
-        bool ok = false;     // the piece has a body of whole mesh lines
-        int e2 = -1;         // reduced component shared along a line
-        int64_t L = 0;       // points per line
-        int64_t body = 0;    // first point of the body
-        int64_t n_lines = 0;
-    };
-    const int dim1 = dim - 1;
-    const int line_cap = 512;  // lines per batch (operands: cap x k2'' x row)
-    auto same_line = [&](int64_t a0, int64_t b0, int64_t L, int e2) {  // equal remaining coordinates along two lines
-        for (int64_t t = 0; t < L; ++t)
-            for (int e = 0; e < dim1; ++e)
-                if (e != e2 && h_k[(a0 + t) * dim + reduced[e]] != h_k[(b0 + t) * dim + reduced[e]]) return false;
-        return true;
-    };
-    auto analyse = [&](int64_t lo, int64_t hi) -> LineInfo {
-        LineInfo li;
-        if (dim1 < 2 || hi - lo < 512) return li;
-        // the reduced component with the longest sub-runs
-        int e2 = -1;
-        int64_t best_changes = hi - lo;
-        for (int e = 0; e < dim1; ++e) {
-            int64_t changes = 0;
-            for (int64_t i = lo + 1; i < hi; ++i) changes += h_k[i * dim + reduced[e]] != h_k[(i - 1) * dim + reduced[e]];
-            if (changes < best_changes) {
-                best_changes = changes;
-                e2 = e;
-            }
-        }
-        if (e2 < 0 || best_changes < 4) return li;
-        const int c2 = reduced[e2];
-        std::vector<int64_t> sb(1, lo);  // sub-run starts
-        for (int64_t i = lo + 1; i < hi; ++i)
-            if (h_k[i * dim + c2] != h_k[(i - 1) * dim + c2]) sb.push_back(i);
-        sb.push_back(hi);
-        const size_t n_sub = sb.size() - 1;
-        if (n_sub < 6) return li;
-        const int64_t L = sb[2] - sb[1];  // an interior line
-        if (L < 8 || L > TBK_BM) return li;
-        // body: the longest prefix of interior sub-runs (from the second one) that are lines like the first of them
-        size_t first = (sb[1] - sb[0] == L && same_line(sb[0], sb[1], L, e2)) ? 0 : 1, last = first;
-        while (last < n_sub && sb[last + 1] - sb[last] == L && same_line(sb[first], sb[last], L, e2)) ++last;
-        li.n_lines = (int64_t)(last - first);
-        if (li.n_lines < 4) return li;
-        li.ok = true;
-        li.e2 = e2;
-        li.L = L;
-        li.body = sb[first];
-        return li;
-    };
-    // lines a0, a0 + L, ... (n of them) of the CURRENT first-level model -> slots slot0 ... of the second-level plan
-    auto fold_body = [&](tbk_fold_plan_t& plan2, const LineInfo& li, int64_t a0, int64_t n, int slot0) -> int {
-        return tbk_fold_lines(m, plan2, d_k2 + a0 * dim1 + li.e2, li.L * dim1, (int)n, slot0);
-    };
-    // one launch for n lines whose operands are in slots 0 .. n - 1 (shared phase rows: the lines have equal coordinates)
-    auto contract_lines = [&](tbk_fold_plan_t& plan2, const LineInfo& li, int64_t a0, int64_t n, double* d_Hp) -> int {
-        const int64_t row_len = (int64_t)m->ncol_pad * 2;
-        tbk_fold_saved_t saved2;
-        TBK_CHECK(tbk_fold_enter(m, plan2, 0, saved2));
-        int rc = m->ws_kline.reserve((size_t)li.L * std::max(dim1 - 1, 1) * sizeof(double));
-        if (rc == TBK_OK) rc = tbk_fold_drop_component(m, d_k2 + a0 * dim1, dim1, li.e2, li.L, m->ws_kline.as<double>());
-        if (rc == TBK_OK) rc = fill_rows(m, tbk_hk_plan(m, li.L, true), m->ws_kline.as<double>());  // (one k tile of rows)
-        if (rc == TBK_OK)
-            rc = tbk_launch_hk_dense_lines(m, m->ws_phase.as<double>(), n, (int)li.L, plan2.k2 * row_len, d_Hp);
-        tbk_fold_leave(m, saved2);
-        return rc;
-    };
-
-    auto piece = [&](int64_t lo, int64_t hi, double* d_Hp) -> int {
-        const LineInfo li = analyse(lo, hi);
-        if (!li.ok) return piece_plane(lo, hi, d_Hp);
-        tbk_fold_plan_t* plan2 = nullptr;
-        TBK_CHECK(tbk_fold_subplan(m, plan1, li.e2, line_cap, &plan2));
-        if (!plan2 || plan2->n_rho * 3 > plan1.n_rho) return piece_plane(lo, hi, d_Hp);
-
-        if (li.body > lo) TBK_CHECK(piece_plane(lo, li.body, d_Hp));  // ragged head
-        for (int64_t l0 = 0; l0 < li.n_lines; l0 += line_cap) {
-            const int64_t nl = std::min<int64_t>(line_cap, li.n_lines - l0);
-            const int64_t a0 = li.body + l0 * li.L;
-            // (the lines' shared-component values are read on the device: first point of every line)
-            TBK_CHECK(fold_body(*plan2, li, a0, nl, 0));
-            TBK_CHECK(contract_lines(*plan2, li, a0, nl, d_Hp + (size_t)(a0 - lo) * nn2));
-        }
-        const int64_t body_end = li.body + li.n_lines * li.L;
-        if (body_end < hi) TBK_CHECK(piece_plane(body_end, hi, d_Hp + (size_t)(body_end - lo) * nn2));  // ragged tail
-        return TBK_OK;
-    };
-
-    // first-level model of run r in place (its group folded if it is not in the plan's buffer)
-    auto enter_run = [&](size_t r, tbk_fold_saved_t& saved) -> int {
-        if (group_lo < 0 || (int64_t)r < group_lo || (int64_t)r >= group_lo + group) {
-            group_lo = (int64_t)r;
-            const int n_g = (int)std::min<int64_t>(group, n_runs - group_lo);
-            double kf[64];
-            for (int g = 0; g < n_g; ++g) kf[g] = h_k[runs[(size_t)(group_lo + g)] * dim + f];
-            TBK_CHECK(tbk_fold_group(m, plan1, kf, n_g, 0));
-        }
-        return tbk_fold_enter(m, plan1, (int)((int64_t)r - group_lo), saved);
-    };
-    // A chunk of WHOLE runs that are nothing but equal mesh lines (the planes of a mesh: run_schedule cuts chunks at
-    // run boundaries): the lines of all its planes are folded plane by plane into consecutive slots -- light launches
-    // that get through beside the previous chunk's reduction -- and contracted by ONE launch, instead of one contraction
-    // (which cannot start before the reduction has left the chip) and four light launches behind it per plane.
-    auto batched = [&](int64_t c0, int64_t nkc, double* d_H, bool* done) -> int {
-        *done = false;
-        const size_t r0 = (size_t)(std::upper_bound(runs.begin(), runs.end(), c0) - runs.begin()) - 1;
-        if (runs[r0] != c0) return TBK_OK;
-        size_t r1 = r0;
-        while (r1 + 1 < runs.size() && runs[r1 + 1] <= c0 + nkc) ++r1;
-        if (r1 - r0 < 2 || runs[r1] != c0 + nkc) return TBK_OK;  // fewer than two whole runs, or a cut run
-        const LineInfo li0 = analyse(runs[r0], runs[r0 + 1]);
-        if (!li0.ok || li0.body != runs[r0] || li0.body + li0.n_lines * li0.L != runs[r0 + 1]) return TBK_OK;
-        int64_t total = li0.n_lines;
-        for (size_t r = r0 + 1; r < r1; ++r) {
-            const LineInfo li = analyse(runs[r], runs[r + 1]);
-            if (!li.ok || li.e2 != li0.e2 || li.L != li0.L || li.body != runs[r] ||
-                li.body + li.n_lines * li.L != runs[r + 1] || !same_line(runs[r0], runs[r], li0.L, li0.e2))
-                return TBK_OK;
-            total += li.n_lines;
-        }
-        if (total > line_cap) return TBK_OK;
-        tbk_fold_plan_t* plan2 = nullptr;
-        TBK_CHECK(tbk_fold_subplan(m, plan1, li0.e2, line_cap, &plan2));
-        if (!plan2 || plan2->n_rho * 3 > plan1.n_rho) return TBK_OK;
-        int slot = 0;
-        for (size_t r = r0; r < r1; ++r) {
-            tbk_fold_saved_t saved;
-            TBK_CHECK(enter_run(r, saved));
-            const int64_t n = (runs[r + 1] - runs[r]) / li0.L;
-            const int rc = fold_body(*plan2, li0, runs[r], n, slot);
-            tbk_fold_leave(m, saved);
-            TBK_CHECK(rc);
-            slot += (int)n;
-        }
-        {
-            // the second-level plan sits on top of a first-level model: any run of the chunk will do for the shapes (the
-            // last one is in the buffer whatever groups the chunk straddles)
-            tbk_fold_saved_t saved;
-            TBK_CHECK(enter_run(r1 - 1, saved));
-            const int rc = contract_lines(*plan2, li0, c0, total, d_H);
-            tbk_fold_leave(m, saved);
-            TBK_CHECK(rc);
-        }
-        *done = true;
-        return TBK_OK;
-    };
-
-    const HBuilder folded = [&](int64_t c0, int64_t nkc, double* d_H) -> int {
-        {
-            bool done = false;
-            TBK_CHECK(batched(c0, nkc, d_H, &done));
-            if (done) return TBK_OK;
-        }
-        size_t r = (size_t)(std::upper_bound(runs.begin(), runs.end(), c0) - runs.begin()) - 1;
-        for (int64_t lo = c0; lo < c0 + nkc; ++r) {
-            const int64_t hi = std::min(runs[r + 1], c0 + nkc);
-            tbk_fold_saved_t saved;
-            TBK_CHECK(enter_run(r, saved));
-            const int rc = piece(lo, hi, d_H + (size_t)(lo - c0) * nn2);
-            tbk_fold_leave(m, saved);
-            TBK_CHECK(rc);
-            lo = hi;
-        }
-        return TBK_OK;
-    };
-    TBK_CHECK(eigenval_wave_pipeline(m, eig_plan, d_k, nk, d_E, &folded, &runs));
+    tbk_folded_call call(m, d_k, h_k, nk);
+    if (!call.folds()) return TBK_OK;
+    TBK_CHECK(call.begin());
+    const HBuilder folded = [&call](int64_t c0, int64_t nkc, double* d_H) { return call.build(c0, nkc, d_H); };
+    TBK_CHECK(eigenval_wave_pipeline(m, eig_plan, d_k, nk, d_E, &folded, &call.runs));
     m->counters[TBK_CNT_FOLDED_CALLS] += 1;
     m->counters[TBK_CNT_FOLDED_KPOINTS] += nk;
     *done = true;
@@ -997,7 +778,7 @@ static int eigenval_device_impl(tbk_model* m, const tbk_eig_plan_t& plan, const 
     m->counters[TBK_CNT_LIBRARY_CALLS] += 1;
     for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
         const int64_t nkc = std::min(chunk, nk - c0);
-        const tbk_hk_plan_t hk = tbk_hk_plan(m, nkc, true);
+        const tbk_hk_plan_t hk = tbk_hk_plan(m, tbk_staged_operand(m), nkc, true);
         const double* kc = d_k + c0 * m->dim;
         TBK_CHECK(fill_rows(m, hk, kc));
         TBK_CHECK(m->ws_H.reserve((size_t)nkc * nn2 * sizeof(double)));
@@ -1098,7 +879,7 @@ extern "C" int tbk_hamilton(tbk_model* m, const double* k, int64_t nk, int conve
             TBK_CHECK(m->ws_out.reserve(h_bytes));
             // ONE k-point of a dense model (the Z2Pack call shape): k goes into the kernel arguments and the positions of
             // convention 1 stay on the device from call to call -- two uploads and one launch less per call
-            const bool inline_k = nk == 1 && tbk_hk_plan(m, 1, false).rows == HK_ROWS_NONE;
+            const bool inline_k = nk == 1 && tbk_hk_plan(m, tbk_staged_operand(m), 1, false).rows == HK_ROWS_NONE;
             const double* d_pos = nullptr;
             if (inline_k) {
                 if (convention == 1) {
@@ -1206,7 +987,7 @@ extern "C" int tbk_eigenval(tbk_model* m, const double* k, int64_t nk, double* E
         // (one k-point of a dense model on the matrix-vector path: k travels in the kernel arguments, see tbk_hamilton --
         // only the chunk pipeline reads it from there: the rocSOLVER branch fills its phase rows from ws_k, which a call
         // that skipped the upload would leave stale)
-        const bool inline_k = nk == 1 && plan.own() && tbk_hk_plan(m, 1, false).rows == HK_ROWS_NONE;
+        const bool inline_k = nk == 1 && plan.own() && tbk_hk_plan(m, tbk_staged_operand(m), 1, false).rows == HK_ROWS_NONE;
         if (inline_k) {
             m->h_k_inline = k;
         } else {

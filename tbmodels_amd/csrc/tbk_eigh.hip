@@ -378,7 +378,7 @@ extern "C" int tbk_eigh_device(tbk_model* m, const double* d_k, int64_t nk, int 
     }
     for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
         const int64_t nkc = std::min(chunk, nk - c0);
-        const tbk_hk_plan_t plan = tbk_hk_plan(m, nkc, false);
+        const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), nkc, false);
         const double* kc = d_k + c0 * m->dim;
         double* Uc = d_U + (size_t)c0 * nn2;
         double* Ec = d_E + (size_t)c0 * n;

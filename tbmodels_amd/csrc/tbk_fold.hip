@@ -15,13 +15,16 @@
 // 4096 half-space vectors for the synthetic headline model (|R_i| <= 12) -- 13x less work for the H(k) contraction,
 // with every kernel of the path unchanged (phase rows, MFMA contraction, eigensolvers all run on the folded model).
 //
-// The fold acts on the STAGED operand Bt (two real rows P_r, Q_r per lattice vector: H = sum_r c_r P_r + s_r Q_r,
-// tbk_stage.hip).  With theta = alpha + sigma beta' (alpha = 2 pi k_f R_f, beta' the phase of the canonical
+// The fold acts on an operand Bt (two real rows P_r, Q_r per lattice vector: H = sum_r c_r P_r + s_r Q_r, tbk_stage.hip) --
+// a tbk_operand_t: the staged one, or, for the mesh lines inside a plane, a folded one.  With theta = alpha + sigma beta' (alpha = 2 pi k_f R_f, beta' the phase of the canonical
 // (dim-1)-vector rho', sigma = -1 where R's remaining components had to be negated to make them canonical):
 //
 //     P'_rho += cos(alpha) P_r + sin(alpha) Q_r          Q'_rho += sigma (-sin(alpha) P_r + cos(alpha) Q_r)
 //
 // One pass over Bt per run (272 MB at the headline shape: 55 us) against a contraction 13x shorter.
+//
+// Kernels and plans first, then the host analysis of a k list (no model, no device), then the driver of one folded
+// eigenvalue call (tbk_folded_call), whose build() the chunk pipeline of tbk_api.hip runs.
 
 #include <algorithm>
 #include <cstring>
@@ -178,6 +181,7 @@ static int build_plan(tbk_fold_plan_t& plan, const int32_t* R, int64_t n_r, int 
     plan.k2 = (plan.n_rho * 2 + TBK_BK - 1) / TBK_BK * TBK_BK;
     plan.n_rho_pad = plan.k2 / 2;
     plan.capacity = capacity;
+    plan.row_len = (int64_t)ncol_pad * 2;
     std::vector<int64_t> lptr((size_t)plan.n_rho_pad + 1, 0);
     std::vector<int32_t> lrec;
     for (int64_t i = 0; i < plan.n_rho_pad; ++i) {
@@ -186,12 +190,11 @@ static int build_plan(tbk_fold_plan_t& plan, const int32_t* R, int64_t n_r, int 
     }
     std::vector<int32_t> r2((size_t)plan.n_rho_pad * std::max(dim - 1, 1), 0);
     std::copy(plan.h_R2.begin(), plan.h_R2.end(), r2.begin());
-    const size_t row_len = (size_t)ncol_pad * 2;
     TBK_HIP(hipMalloc((void**)&plan.d_R2, std::max<size_t>(r2.size(), 1) * sizeof(int32_t)));
     TBK_HIP(hipMalloc((void**)&plan.d_lptr, lptr.size() * sizeof(int64_t)));
     TBK_HIP(hipMalloc((void**)&plan.d_lrec, std::max<size_t>(lrec.size(), 1) * sizeof(int32_t)));
     TBK_HIP(hipMalloc((void**)&plan.d_rcomp, std::max<size_t>(rcomp.size(), 1) * sizeof(int32_t)));
-    TBK_HIP(hipMalloc((void**)&plan.d_B2, (size_t)capacity * plan.k2 * row_len * sizeof(double)));
+    TBK_HIP(hipMalloc((void**)&plan.d_B2, (size_t)capacity * plan.k2 * plan.row_len * sizeof(double)));
     plan.table_entries = n_r * FOLD_GROUP;
     TBK_HIP(hipMalloc((void**)&plan.d_table, std::max<size_t>((size_t)plan.table_entries * 2, 1) * sizeof(double)));
     TBK_HIP(hipMemcpy(plan.d_R2, r2.data(), r2.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -202,13 +205,13 @@ static int build_plan(tbk_fold_plan_t& plan, const int32_t* R, int64_t n_r, int 
     return TBK_OK;
 }
 
-int tbk_fold_plan(tbk_model* m, int f) {
+static int tbk_fold_plan(tbk_model* m, int f) {
     return build_plan(m->fold[f], m->h_R.data(), m->n_r, m->dim, f, m->ncol_pad, FOLD_GROUP);
 }
 
 // Second-level plan: folds the lattice `parent` produced along its component f2 (mesh lines inside a mesh plane);
 // room for `capacity` operands (one per line of a plane piece).
-int tbk_fold_subplan(tbk_model* m, tbk_fold_plan_t& parent, int f2, int capacity, tbk_fold_plan_t** out) {
+static int tbk_fold_subplan(tbk_model* m, tbk_fold_plan_t& parent, int f2, int capacity, tbk_fold_plan_t** out) {
     *out = nullptr;
     const int dim2 = parent.dim - 1;
     if (dim2 < 2 || f2 < 0 || f2 >= dim2) return TBK_OK;
@@ -243,11 +246,11 @@ void tbk_fold_release(tbk_model* m) {
 // Average run length from which folding pays: a run costs one pass over Bt (60 us at the headline shape) plus
 // three small launches, the direct contraction ~1 us per k-point.  Measured on meshes of the headline model:
 // 14^3 (runs of 196) 4.4 -> 2.4 ms, 20^3 11.4 -> 5.0 ms, 30^3 38 -> 13.6 ms, 50^3 159 -> 49 ms.
-int64_t tbk_fold_min_run() { return 128; }
+static int64_t tbk_fold_min_run() { return 128; }
 
 // Which component (if any) is worth folding for this k list: the one with the fewest runs of equal consecutive
 // values, if its runs average >= tbk_fold_min_run() k-points and the folded lattice is at least 3x smaller.  -1: none.
-int tbk_fold_choose(tbk_model* m, const double* h_k, int64_t nk, std::vector<int64_t>& run_starts) {
+static int tbk_fold_choose(tbk_model* m, const double* h_k, int64_t nk, std::vector<int64_t>& run_starts) {
     run_starts.clear();
     if (!m->fold_enabled || m->sparse || m->kdotp || m->dim < 2 || m->n_r < 64 || nk < 1024 || m->h_R.empty()) return -1;
     int best = -1;
@@ -271,17 +274,91 @@ int tbk_fold_choose(tbk_model* m, const double* h_k, int64_t nk, std::vector<int
     return best;
 }
 
-int tbk_fold_group_size() { return FOLD_GROUP; }
+// Chunks of a folded call: whole runs (mesh planes) packed up to the chunk size -- every run a chunk cuts costs a second
+// fold pass, ragged mesh lines and a handful of small launches on both sides of the cut (the 100^3 mesh in chunks of 30 000
+// = three planes instead of 32 768: 150.8 -> 143.6 ms).  Runs longer than a chunk are cut into chunk-sized pieces.
+std::vector<int64_t> run_schedule(const std::vector<int64_t>& runs, int64_t chunk) {
+    std::vector<int64_t> out;
+    int64_t cur = 0;
+    for (size_t r = 0; r + 1 < runs.size(); ++r) {
+        int64_t len = runs[r + 1] - runs[r];
+        if (cur > 0 && cur + len > chunk) {
+            out.push_back(cur);
+            cur = 0;
+        }
+        while (len > chunk) {
+            out.push_back(chunk);
+            len -= chunk;
+        }
+        cur += len;
+    }
+    if (cur > 0) out.push_back(cur);
+    return out;
+}
 
-// Folds the CURRENT operand of `m` (m->d_B: the staged one, or a first-level folded one) for the n_g (<= FOLD_GROUP)
-// shared-component values h_kf[] in one pass, into slots slot0 .. slot0 + n_g - 1 of the plan's buffer (main stream).
-int tbk_fold_group(tbk_model* m, tbk_fold_plan_t& plan, const double* h_kf, int n_g, int slot0) {
-    const int64_t row_len = (int64_t)m->ncol_pad * 2;
-    double* out = plan.d_B2 + (size_t)slot0 * plan.k2 * row_len;
+// Second level (meshes): inside a plane the k-points come in LINES -- equal-length sub-runs of one more shared
+// component whose remaining coordinates repeat from line to line.  Every line is a (dim - 2)-dimensional model
+// (13 instead of 313 lattice vectors at the headline shape); all lines of the piece go through ONE launch with
+// per-line operands and shared phase rows (tbk_launch_hk_dense_lines).  Ragged ends of the piece, and anything
+// that does not have this structure, take piece_plane.  The two functions that find the lines read the list of the call,
+// h_k[.][dim]; reduced[e] is the original component of reduced component e of a run.
+
+// equal remaining coordinates along the lines of L points that start at a0 and b0 (e2: the component shared along a line)
+static bool same_line(const double* h_k, int dim, const std::vector<int>& reduced, int64_t a0, int64_t b0, int64_t L, int e2) {
+    const int dim1 = (int)reduced.size();
+    for (int64_t t = 0; t < L; ++t)
+        for (int e = 0; e < dim1; ++e)
+            if (e != e2 && h_k[(a0 + t) * dim + reduced[e]] != h_k[(b0 + t) * dim + reduced[e]]) return false;
+    return true;
+}
+
+// the mesh lines of the piece [lo, hi) of one run
+static LineInfo analyse(const double* h_k, int dim, const std::vector<int>& reduced, int64_t lo, int64_t hi) {
+    const int dim1 = (int)reduced.size();
+    LineInfo li;
+    if (dim1 < 2 || hi - lo < 512) return li;
+    // the reduced component with the longest sub-runs
+    int e2 = -1;
+    int64_t best_changes = hi - lo;
+    for (int e = 0; e < dim1; ++e) {
+        int64_t changes = 0;
+        for (int64_t i = lo + 1; i < hi; ++i) changes += h_k[i * dim + reduced[e]] != h_k[(i - 1) * dim + reduced[e]];
+        if (changes < best_changes) {
+            best_changes = changes;
+            e2 = e;
+        }
+    }
+    if (e2 < 0 || best_changes < 4) return li;
+    const int c2 = reduced[e2];
+    std::vector<int64_t> sb(1, lo);  // sub-run starts
+    for (int64_t i = lo + 1; i < hi; ++i)
+        if (h_k[i * dim + c2] != h_k[(i - 1) * dim + c2]) sb.push_back(i);
+    sb.push_back(hi);
+    const size_t n_sub = sb.size() - 1;
+    if (n_sub < 6) return li;
+    const int64_t L = sb[2] - sb[1];  // an interior line
+    if (L < 8 || L > TBK_BM) return li;
+    // body: the longest prefix of interior sub-runs (from the second one) that are lines like the first of them
+    size_t first = (sb[1] - sb[0] == L && same_line(h_k, dim, reduced, sb[0], sb[1], L, e2)) ? 0 : 1, last = first;
+    while (last < n_sub && sb[last + 1] - sb[last] == L && same_line(h_k, dim, reduced, sb[first], sb[last], L, e2)) ++last;
+    li.n_lines = (int64_t)(last - first);
+    if (li.n_lines < 4) return li;
+    li.ok = true;
+    li.e2 = e2;
+    li.L = L;
+    li.body = sb[first];
+    return li;
+}
+
+// Folds the operand `from` (the staged one, or a first-level folded one) for the n_g (<= FOLD_GROUP) shared-component
+// values h_kf[] in one pass, into slots slot0 .. slot0 + n_g - 1 of the plan's buffer (main stream).
+static int tbk_fold_group(tbk_model* m, const tbk_operand_t& from, tbk_fold_plan_t& plan, const double* h_kf, int n_g, int slot0) {
+    const int64_t row_len = plan.row_len;
+    double* out = plan.slot(slot0);
     StageTimer t(m, TBK_T_PHASE);
     if (n_g == 1) {
         dim3 grid((unsigned)((row_len + 255) / 256), (unsigned)plan.n_rho_pad);
-        hipLaunchKernelGGL(fold_rows_kernel, grid, dim3(256), 0, m->stream, m->d_B, row_len, plan.d_lptr, plan.d_lrec,
+        hipLaunchKernelGGL(fold_rows_kernel, grid, dim3(256), 0, m->stream, from.d_B, row_len, plan.d_lptr, plan.d_lrec,
                            plan.d_rcomp, h_kf[0], out);
         TBK_HIP(hipGetLastError());
         return TBK_OK;
@@ -293,16 +370,18 @@ int tbk_fold_group(tbk_model* m, tbk_fold_plan_t& plan, const double* h_kf, int 
                        plan.n_r, values, n_g, plan.d_table);
     TBK_HIP(hipGetLastError());
     dim3 grid((unsigned)((row_len + 255) / 256), (unsigned)plan.n_rho_pad);
-    hipLaunchKernelGGL(fold_rows_group_kernel, grid, dim3(256), 0, m->stream, m->d_B, row_len, plan.d_lptr, plan.d_lrec,
+    hipLaunchKernelGGL(fold_rows_group_kernel, grid, dim3(256), 0, m->stream, from.d_B, row_len, plan.d_lptr, plan.d_lrec,
                        plan.d_table, n_g, plan.k2 * row_len, out);
     TBK_HIP(hipGetLastError());
     return TBK_OK;
 }
 
-// All n_lines lines of a mesh plane piece in one go: their shared-component values are read on the device
-// (d_kf[line * stride]); slots slot0 .. slot0 + n_lines - 1 of the plan's buffer (slot0 + n_lines <= plan.capacity).
-int tbk_fold_lines(tbk_model* m, tbk_fold_plan_t& plan, const double* d_kf, int64_t stride, int n_lines, int slot0) {
-    const int64_t row_len = (int64_t)m->ncol_pad * 2;
+// All n_lines lines of a mesh plane piece in one go, folded from the operand `from` of their plane: their shared-component
+// values are read on the device (d_kf[line * stride]); slots slot0 .. slot0 + n_lines - 1 of the plan's buffer
+// (slot0 + n_lines <= plan.capacity).
+static int tbk_fold_lines(tbk_model* m, const tbk_operand_t& from, tbk_fold_plan_t& plan, const double* d_kf, int64_t stride, int n_lines,
+                          int slot0) {
+    const int64_t row_len = plan.row_len;
     StageTimer t(m, TBK_T_PHASE);
     if ((size_t)plan.table_entries < (size_t)plan.n_r * n_lines) {
         if (plan.d_table) TBK_HIP(hipFree(plan.d_table));
@@ -315,43 +394,150 @@ int tbk_fold_lines(tbk_model* m, tbk_fold_plan_t& plan, const double* d_kf, int6
                        plan.d_rcomp, plan.n_r, d_kf, stride, n_lines, plan.d_table);
     TBK_HIP(hipGetLastError());
     dim3 grid((unsigned)((row_len + 255) / 256), (unsigned)plan.n_rho_pad, (unsigned)((n_lines + FOLD_GROUP - 1) / FOLD_GROUP));
-    hipLaunchKernelGGL(fold_rows_group_kernel, grid, dim3(256), 0, m->stream, m->d_B, row_len, plan.d_lptr, plan.d_lrec,
-                       plan.d_table, n_lines, plan.k2 * row_len, plan.d_B2 + (size_t)slot0 * plan.k2 * row_len);
+    hipLaunchKernelGGL(fold_rows_group_kernel, grid, dim3(256), 0, m->stream, from.d_B, row_len, plan.d_lptr, plan.d_lrec,
+                       plan.d_table, n_lines, plan.k2 * row_len, plan.slot(slot0));
     TBK_HIP(hipGetLastError());
     return TBK_OK;
 }
 
-// Turns `m` into the model folded by `plan`, with the operand in `slot` of the plan's buffer; the caller evaluates and
-// calls tbk_fold_leave.  Nests (a second-level plan on top of a first-level one).
-int tbk_fold_enter(tbk_model* m, tbk_fold_plan_t& plan, int slot, tbk_fold_saved_t& saved) {
-    const int64_t row_len = (int64_t)m->ncol_pad * 2;
-    saved.dim = m->dim;
-    saved.n_r = m->n_r;
-    saved.n_r_pad = m->n_r_pad;
-    saved.k2 = m->k2;
-    saved.d_R = m->d_R;
-    saved.d_B = m->d_B;
-    m->dim = saved.dim - 1;
-    m->n_r = plan.n_rho;
-    m->n_r_pad = plan.n_rho_pad;
-    m->k2 = plan.k2;
-    m->d_R = plan.d_R2;
-    m->d_B = plan.d_B2 + (size_t)slot * plan.k2 * row_len;
-    return TBK_OK;
-}
-
-void tbk_fold_leave(tbk_model* m, const tbk_fold_saved_t& saved) {
-    m->dim = saved.dim;
-    m->n_r = saved.n_r;
-    m->n_r_pad = saved.n_r_pad;
-    m->k2 = saved.k2;
-    m->d_R = saved.d_R;
-    m->d_B = saved.d_B;
-}
-
-int tbk_fold_drop_component(tbk_model* m, const double* d_k, int dim, int f, int64_t nk, double* d_k2) {
+static int tbk_fold_drop_component(tbk_model* m, const double* d_k, int dim, int f, int64_t nk, double* d_k2) {
     hipLaunchKernelGGL(drop_component_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, m->stream, d_k, dim, f, nk,
                        d_k2);
     TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the folded eigenvalue call
+// ------------------------------------------------------------------------------------------------
+constexpr int LINE_CAP = 512;  // lines per batch (operands: cap x k2'' x row)
+
+tbk_folded_call::tbk_folded_call(tbk_model* m_, const double* d_k_, const double* h_k_, int64_t nk_)
+    : m(m_), d_k(d_k_), h_k(h_k_), nk(nk_) {
+    if (h_k == nullptr) return;
+    f = tbk_fold_choose(m, h_k, nk, runs);
+    if (f < 0) return;
+    dim = m->dim;
+    dim1 = dim - 1;
+    nn2 = (size_t)m->n_orb * m->n_orb * 2;
+    plan1 = &m->fold[f];
+    for (int d = 0; d < dim; ++d)
+        if (d != f) reduced.push_back(d);
+}
+
+int tbk_folded_call::begin() {
+    TBK_CHECK(m->ws_kfold.reserve((size_t)nk * dim1 * sizeof(double)));
+    d_k2 = m->ws_kfold.as<double>();
+    return tbk_fold_drop_component(m, d_k, dim, f, nk, d_k2);
+}
+
+// The first-level operand of run r.  Runs are folded a group at a time (one pass over Bt for up to FOLD_GROUP of them): the
+// group of r is folded if its operands are not in the plan's buffer.
+int tbk_folded_call::run_operand(size_t r, tbk_operand_t* op) {
+    if (group_lo < 0 || (int64_t)r < group_lo || (int64_t)r >= group_lo + FOLD_GROUP) {
+        group_lo = (int64_t)r;
+        const int n_g = (int)std::min<int64_t>(FOLD_GROUP, (int64_t)runs.size() - 1 - group_lo);
+        double kf[FOLD_GROUP];
+        for (int g = 0; g < n_g; ++g) kf[g] = h_k[runs[(size_t)(group_lo + g)] * dim + f];
+        TBK_CHECK(tbk_fold_group(m, tbk_staged_operand(m), *plan1, kf, n_g, 0));
+    }
+    *op = plan1->operand((int)((int64_t)r - group_lo));
+    return TBK_OK;
+}
+
+// [lo, hi) of one run with the operand `op` folded for that run: phase rows + contraction of the (dim - 1)-dimensional model
+int tbk_folded_call::piece_plane(const tbk_operand_t& op, int64_t lo, int64_t hi, double* d_Hp) {
+    const tbk_hk_plan_t plan = tbk_hk_plan(m, op, hi - lo, true);
+    TBK_CHECK(fill_rows(m, plan, d_k2 + lo * dim1));
+    return build_h(m, plan, HK_TRI, 2, d_k2 + lo * dim1, nullptr, d_Hp);
+}
+
+// lines a0, a0 + L, ... (n of them) of the first-level operand `from` -> slots slot0 ... of the second-level plan
+// (the lines' shared-component values are read on the device: first point of every line)
+int tbk_folded_call::fold_body(const tbk_operand_t& from, tbk_fold_plan_t& plan2, const LineInfo& li, int64_t a0, int64_t n, int slot0) {
+    return tbk_fold_lines(m, from, plan2, d_k2 + a0 * dim1 + li.e2, li.L * dim1, (int)n, slot0);
+}
+
+// one launch for n lines whose operands are in slots 0 .. n - 1 (shared phase rows: the lines have equal coordinates)
+int tbk_folded_call::contract_lines(tbk_fold_plan_t& plan2, const LineInfo& li, int64_t a0, int64_t n, double* d_Hp) {
+    const tbk_operand_t op2 = plan2.operand(0);
+    TBK_CHECK(m->ws_kline.reserve((size_t)li.L * std::max(dim1 - 1, 1) * sizeof(double)));
+    TBK_CHECK(tbk_fold_drop_component(m, d_k2 + a0 * dim1, dim1, li.e2, li.L, m->ws_kline.as<double>()));
+    TBK_CHECK(fill_rows(m, tbk_hk_plan(m, op2, li.L, true), m->ws_kline.as<double>()));  // (one k tile of rows)
+    return tbk_launch_hk_dense_lines(m, op2, m->ws_phase.as<double>(), n, (int)li.L, plan2.k2 * plan2.row_len, d_Hp);
+}
+
+int tbk_folded_call::piece(const tbk_operand_t& op, int64_t lo, int64_t hi, double* d_Hp) {
+    const LineInfo li = analyse(h_k, dim, reduced, lo, hi);
+    if (!li.ok) return piece_plane(op, lo, hi, d_Hp);
+    tbk_fold_plan_t* plan2 = nullptr;
+    TBK_CHECK(tbk_fold_subplan(m, *plan1, li.e2, LINE_CAP, &plan2));
+    if (!plan2 || plan2->n_rho * 3 > plan1->n_rho) return piece_plane(op, lo, hi, d_Hp);
+
+    if (li.body > lo) TBK_CHECK(piece_plane(op, lo, li.body, d_Hp));  // ragged head
+    for (int64_t l0 = 0; l0 < li.n_lines; l0 += LINE_CAP) {
+        const int64_t nl = std::min<int64_t>(LINE_CAP, li.n_lines - l0);
+        const int64_t a0 = li.body + l0 * li.L;
+        TBK_CHECK(fold_body(op, *plan2, li, a0, nl, 0));
+        TBK_CHECK(contract_lines(*plan2, li, a0, nl, d_Hp + (size_t)(a0 - lo) * nn2));
+    }
+    const int64_t body_end = li.body + li.n_lines * li.L;
+    if (body_end < hi) TBK_CHECK(piece_plane(op, body_end, hi, d_Hp + (size_t)(body_end - lo) * nn2));  // ragged tail
+    return TBK_OK;
+}
+
+// A chunk of WHOLE runs that are nothing but equal mesh lines (the planes of a mesh: run_schedule cuts chunks at
+// run boundaries): the lines of all its planes are folded plane by plane into consecutive slots -- light launches
+// that get through beside the previous chunk's reduction -- and contracted by ONE launch, instead of one contraction
+// (which cannot start before the reduction has left the chip) and four light launches behind it per plane.
+int tbk_folded_call::batched(int64_t c0, int64_t nkc, double* d_H, bool* done) {
+    *done = false;
+    const size_t r0 = (size_t)(std::upper_bound(runs.begin(), runs.end(), c0) - runs.begin()) - 1;
+    if (runs[r0] != c0) return TBK_OK;
+    size_t r1 = r0;
+    while (r1 + 1 < runs.size() && runs[r1 + 1] <= c0 + nkc) ++r1;
+    if (r1 - r0 < 2 || runs[r1] != c0 + nkc) return TBK_OK;  // fewer than two whole runs, or a cut run
+    const LineInfo li0 = analyse(h_k, dim, reduced, runs[r0], runs[r0 + 1]);
+    if (!li0.ok || li0.body != runs[r0] || li0.body + li0.n_lines * li0.L != runs[r0 + 1]) return TBK_OK;
+    int64_t total = li0.n_lines;
+    for (size_t r = r0 + 1; r < r1; ++r) {
+        const LineInfo li = analyse(h_k, dim, reduced, runs[r], runs[r + 1]);
+        if (!li.ok || li.e2 != li0.e2 || li.L != li0.L || li.body != runs[r] || li.body + li.n_lines * li.L != runs[r + 1] ||
+            !same_line(h_k, dim, reduced, runs[r0], runs[r], li0.L, li0.e2))
+            return TBK_OK;
+        total += li.n_lines;
+    }
+    if (total > LINE_CAP) return TBK_OK;
+    tbk_fold_plan_t* plan2 = nullptr;
+    TBK_CHECK(tbk_fold_subplan(m, *plan1, li0.e2, LINE_CAP, &plan2));
+    if (!plan2 || plan2->n_rho * 3 > plan1->n_rho) return TBK_OK;
+    int slot = 0;
+    for (size_t r = r0; r < r1; ++r) {
+        tbk_operand_t op;
+        TBK_CHECK(run_operand(r, &op));
+        const int64_t n = (runs[r + 1] - runs[r]) / li0.L;
+        TBK_CHECK(fold_body(op, *plan2, li0, runs[r], n, slot));
+        slot += (int)n;
+    }
+    TBK_CHECK(contract_lines(*plan2, li0, c0, total, d_H));
+    *done = true;
+    return TBK_OK;
+}
+
+// Only the H(k) of a chunk is assembled run by run, each piece with the operand folded for its run.
+int tbk_folded_call::build(int64_t c0, int64_t nkc, double* d_H) {
+    {
+        bool done = false;
+        TBK_CHECK(batched(c0, nkc, d_H, &done));
+        if (done) return TBK_OK;
+    }
+    size_t r = (size_t)(std::upper_bound(runs.begin(), runs.end(), c0) - runs.begin()) - 1;
+    for (int64_t lo = c0; lo < c0 + nkc; ++r) {
+        const int64_t hi = std::min(runs[r + 1], c0 + nkc);
+        tbk_operand_t op;
+        TBK_CHECK(run_operand(r, &op));
+        TBK_CHECK(piece(op, lo, hi, d_H + (size_t)(lo - c0) * nn2));
+        lo = hi;
+    }
     return TBK_OK;
 }

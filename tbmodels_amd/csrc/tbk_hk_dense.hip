@@ -843,21 +843,21 @@ int launch(tbk_model* m, const HkArgs& a0, int grid) {
     return TBK_OK;
 }
 
-// The arguments every launch shares: the model's operand (a.nt_count element tiles of it) and the output.
-HkArgs hk_args(const tbk_model* m, const double* d_A, int64_t nk, int64_t nk_pad, double* d_H) {
+// The arguments every launch shares: the operand (a.nt_count element tiles of it) and the output.
+HkArgs hk_args(const tbk_model* m, const tbk_operand_t& op, const double* d_A, int64_t nk, int64_t nk_pad, double* d_H) {
     HkArgs a;
     a.A = d_A;
-    a.Bt = m->d_B;
+    a.Bt = op.d_B;
     a.colmap = m->d_colmap;
-    a.R = m->d_R;
-    a.n_r = m->n_r;
+    a.R = op.d_R;
+    a.n_r = op.n_r;
     a.H = d_H;
-    a.k2 = m->k2;
+    a.k2 = op.k2;
     a.nk = nk;
     a.nk_pad = nk_pad;
     a.ncol_pad = m->ncol_pad;
     a.n_orb = m->n_orb;
-    a.dim = m->dim;
+    a.dim = op.dim;
     a.nt_count = m->ncol_pad / TBK_BNP;
     return a;
 }
@@ -886,16 +886,16 @@ auto by_mode(int mode, int convention, F&& launch) {
 // combine.  The operands were made by phase_rows_strassen_kernel (a.A = As[7][K2 / 2][Mh]) and stage_strassen_kernel
 // (m->d_Bs); the K loop is the classical one over K2 / 2 rows.  Products do not depend on MODE / CONV: one instantiation.
 template <int MODE, int CONV>
-int launch_strassen(tbk_model* m, const HkArgs& a0) {
+int launch_strassen(tbk_model* m, const tbk_operand_t& op, const HkArgs& a0) {
     hipStream_t s = m->stream;
     const size_t lds = 2 * STAGE_DOUBLES * sizeof(double);
     static std::atomic<bool> raised[TBK_MAX_DEVICES] = {};
     TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&hk_dense_kernel<HK_TRI, 2, true>), 160 * 1024, raised));
     const int64_t mh = tbk_strassen_mh(a0.nk);
     const int half = a0.ncol_pad / 2;
-    HkArgs a = hk_args(m, a0.A, mh, mh, a0.H);
+    HkArgs a = hk_args(m, op, a0.A, mh, mh, a0.H);
     a.Bt = m->d_Bs;
-    a.k2 = m->k2 / 2;
+    a.k2 = op.k2 / 2;
     a.ncol_pad = half;
     a.nt_count = half / TBK_BNP;
     const int grid = tile_grid(a, (int)(mh / TBK_BM));
@@ -921,7 +921,7 @@ int launch_strassen(tbk_model* m, const HkArgs& a0) {
 // Two levels: the 49 quarter-size products as the units of one launch, as above -- operands from phase_rows_strassen2_kernel
 // (a.A = As2[49][K2 / 4][Mq]) and tbk_stage_strassen2 (m->d_Bs2), the K loop over K2 / 4 rows.
 template <int MODE, int CONV>
-int launch_strassen2(tbk_model* m, const HkArgs& a0) {
+int launch_strassen2(tbk_model* m, const tbk_operand_t& op, const HkArgs& a0) {
     hipStream_t s = m->stream;
     const size_t lds = 2 * STAGE_DOUBLES * sizeof(double);
     static std::atomic<bool> raised[TBK_MAX_DEVICES] = {};
@@ -929,9 +929,9 @@ int launch_strassen2(tbk_model* m, const HkArgs& a0) {
     TBK_ARG(m->d_Bs2 != nullptr, "the operand blocks of the second Strassen level are missing");
     const int64_t mq = tbk_strassen_mq(a0.nk);
     const int quarter = a0.ncol_pad / 4;
-    HkArgs a = hk_args(m, a0.A, mq, mq, a0.H);
+    HkArgs a = hk_args(m, op, a0.A, mq, mq, a0.H);
     a.Bt = m->d_Bs2;
-    a.k2 = m->k2 / 4;
+    a.k2 = op.k2 / 4;
     a.ncol_pad = quarter;
     a.nt_count = quarter / TBK_BNP;
     const int grid = tile_grid(a, (int)(mq / TBK_BM));
@@ -965,24 +965,24 @@ int gemv_nkv(int64_t nk) {  // the kernel instantiation's k-points per wave
     while (nkv < std::min<int64_t>(nk, 32)) nkv *= 2;
     return nkv;
 }
-int64_t gemv_strip_rows(const tbk_model* m, int64_t slices) {  // rows of the longest slice, rounded up to whole trips of the loop
-    const int64_t n_pairs = m->k2 / 2;
+int64_t gemv_strip_rows(int64_t k2, int64_t slices) {  // rows of the longest slice, rounded up to whole trips of the loop
+    const int64_t n_pairs = k2 / 2;
     return (2 * ((n_pairs + slices - 1) / slices) + 15) / 16 * 16;
 }
 
-void gemv_plan(const tbk_model* m, int64_t nk, int* slices_out, size_t* lds_out) {
+void gemv_plan(const tbk_model* m, int64_t k2, int64_t nk, int* slices_out, size_t* lds_out) {
     const int nblk = m->ncol_pad / 64;
-    const int64_t n_pairs = m->k2 / 2;
+    const int64_t n_pairs = k2 / 2;
     const size_t per_split = (size_t)nk * m->ncol_pad * 2 * sizeof(double);
     const int64_t cap = std::max<int64_t>(1, (int64_t)((size_t(256) << 20) / per_split));
     // (one-k hamilton at N_orb = 64, N_R = 4096 with 1 / 2 / 3 / 4 / 5 workgroups per CU: 69.4 / 65.2 / 66.5 / 67.9 / 69.2 us)
     const int64_t wave_slots = (int64_t)m->n_cu * 8;  // two workgroups per CU
     int64_t slices = wave_slots / nblk;               // one round: nblk * slices <= slots
     size_t lds = 80 * 1024;
-    const int64_t rows_one_round = slices > 0 ? (m->k2 + slices - 1) / slices : m->k2 + 1;
+    const int64_t rows_one_round = slices > 0 ? (k2 + slices - 1) / slices : k2 + 1;
     if (slices < 1 || nblk * slices * 10 < wave_slots * 9 || rows_one_round > 384 || slices > cap) {
         // many rounds: workgroups of ~1 MB, at least eight per CU while a slice keeps 16 rows
-        slices = std::max<int64_t>(m->k2 / 256, std::min<int64_t>(((int64_t)m->n_cu * 32 + nblk - 1) / nblk, n_pairs / 8));
+        slices = std::max<int64_t>(k2 / 256, std::min<int64_t>(((int64_t)m->n_cu * 32 + nblk - 1) / nblk, n_pairs / 8));
         slices = std::max<int64_t>(1, std::min(cap, slices));
         lds = 16 * 1024;
     }
@@ -991,7 +991,7 @@ void gemv_plan(const tbk_model* m, int64_t nk, int* slices_out, size_t* lds_out)
     if (lds < 64 * 1024) {
         // no occupancy limiter: as much LDS as the phase strips of four waves take (up to 64 KiB), so that e.g. groups of 32
         // k-points of a small model still make their own rows (the 1000-point silicon mesh: no phase_rows_kernel launch)
-        const size_t need = (size_t)4 * gemv_strip_rows(m, slices) * gemv_nkv(nk) * sizeof(double);
+        const size_t need = (size_t)4 * gemv_strip_rows(k2, slices) * gemv_nkv(nk) * sizeof(double);
         if (need <= size_t(64) * 1024) lds = std::max(lds, need);
     }
     *slices_out = (int)slices;
@@ -1010,8 +1010,8 @@ void gemv_plan(const tbk_model* m, int64_t nk, int* slices_out, size_t* lds_out)
 //   the rows of a wave's slice for its (up to 32) k-points do not fit its strip of the workgroup's LDS.
 // * TINY: one k-point of a small model whose rows the kernel makes -- the whole H(k) in ONE launch (hk_tiny_kernel, <= 36 KiB
 //   of LDS).
-// * STRASSEN (launch_strassen): a dense tight-binding model padded and staged for it, with its own operand (not a folded
-//   one), TBK_OPT_STRASSEN on, and a chunk of at least TBK_STRASSEN_MIN_NK k-points that takes neither the matrix-vector path
+// * STRASSEN (launch_strassen): a dense tight-binding model padded and staged for it, the staged operand (a folded one has
+//   no blocks), TBK_OPT_STRASSEN on, and a chunk of at least TBK_STRASSEN_MIN_NK k-points that takes neither the matrix-vector path
 //   nor split-K.  Its rows are the seven blocks As[7][K2 / 2][Mh].
 // * STRASSEN2 (launch_strassen2): the same and TBK_OPT_STRASSEN_LEVELS = 2, whole K stages and element tiles in every quarter
 //   of the model's padding, a chunk of at least TBK_STRASSEN2_MIN_NK k-points, and the blocks of the second level built or still
@@ -1022,41 +1022,42 @@ void gemv_plan(const tbk_model* m, int64_t nk, int* slices_out, size_t* lds_out)
 //   workspace, hk_finish_kernel adds them in fixed order.  Measured at N_orb = 64, N_R = 4096: one k-point 1056 -> 163 us
 //   (before the matrix-vector path), 1000 k-points 2137 -> 1264 us.  (Just enough splits for ONE full round plus a
 //   sub-split tail was slower up to 500 k-points: three more launches on a 0.2 ms kernel.)
-tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, int64_t nk, bool caller_rows) {
+tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, const tbk_operand_t& op, int64_t nk, bool caller_rows) {
     tbk_hk_plan_t p;
+    p.op = op;
     p.nk = nk;
     p.nk_pad = (nk + TBK_BM - 1) / TBK_BM * TBK_BM;
     p.rows = m->kdotp ? HK_ROWS_MONOMIAL : HK_ROWS_PHASE;
-    p.row_doubles = std::max<int64_t>(m->k2, 1) * p.nk_pad;
+    p.row_doubles = std::max<int64_t>(op.k2, 1) * p.nk_pad;
     if (m->sparse) {
         p.path = HK_PATH_CSR;
         return p;
     }
-    if (nk >= 1 && m->k2 > 0 && (nk <= 32 || (nk <= 4096 && m->ncol_pad <= 256 && m->k2 < 16 * TBK_BK))) {
-        gemv_plan(m, nk, &p.splits, &p.lds);
-        if (!caller_rows && !m->kdotp && m->d_R != nullptr && gemv_strip_rows(m, p.splits) * gemv_nkv(nk) <= (int64_t)(p.lds / 32))
+    if (nk >= 1 && op.k2 > 0 && (nk <= 32 || (nk <= 4096 && m->ncol_pad <= 256 && op.k2 < 16 * TBK_BK))) {
+        gemv_plan(m, op.k2, nk, &p.splits, &p.lds);
+        if (!caller_rows && !m->kdotp && op.d_R != nullptr && gemv_strip_rows(op.k2, p.splits) * gemv_nkv(nk) <= (int64_t)(p.lds / 32))
             p.rows = HK_ROWS_NONE;
-        const bool tiny = p.rows == HK_ROWS_NONE && nk == 1 && m->ncol_pad <= 256 && m->k2 <= 4096;
+        const bool tiny = p.rows == HK_ROWS_NONE && nk == 1 && m->ncol_pad <= 256 && op.k2 <= 4096;
         p.path = tiny ? HK_PATH_TINY : HK_PATH_GEMV;
         return p;
     }
     const int64_t tiles = (nk + TBK_BM - 1) / TBK_BM * (m->ncol_pad / TBK_BNP);
-    if (m->strassen && m->d_Bs != nullptr && m->d_B == m->bs_src && !m->kdotp && m->n_r_pad >= TBK_STRASSEN_MIN_NR &&
+    if (m->strassen && m->d_Bs != nullptr && op.d_B == m->d_B && !m->kdotp && op.n_r_pad >= TBK_STRASSEN_MIN_NR &&
         nk >= TBK_STRASSEN_MIN_NK && tiles >= 2 * m->n_cu) {
-        if (m->strassen_levels >= 2 && !m->bs2_skipped && nk >= TBK_STRASSEN2_MIN_NK && m->k2 % (4 * TBK_BK) == 0 &&
+        if (m->strassen_levels >= 2 && !m->bs2_skipped && nk >= TBK_STRASSEN2_MIN_NK && op.k2 % (4 * TBK_BK) == 0 &&
             m->ncol_pad % (4 * TBK_BNP) == 0) {
             p.path = HK_PATH_STRASSEN2;
             p.rows = HK_ROWS_STRASSEN2;
-            p.row_doubles = 49 * (m->k2 / 4) * tbk_strassen_mq(nk);
+            p.row_doubles = 49 * (op.k2 / 4) * tbk_strassen_mq(nk);
             return p;
         }
         p.path = HK_PATH_STRASSEN;
         p.rows = HK_ROWS_STRASSEN;
-        p.row_doubles = 7 * (m->k2 / 2) * tbk_strassen_mh(nk);
+        p.row_doubles = 7 * (op.k2 / 2) * tbk_strassen_mh(nk);
         return p;
     }
     p.path = HK_PATH_TILES;
-    const int n_stage = (int)(m->k2 / TBK_BK);
+    const int n_stage = (int)(op.k2 / TBK_BK);
     if (tiles < 2 * m->n_cu && n_stage >= 16) {
         int64_t splits = std::min<int64_t>((1280 + tiles / 2) / tiles, n_stage / 4);
         const size_t per_split = (size_t)p.nk_pad * m->ncol_pad * 2 * sizeof(double);
@@ -1070,19 +1071,19 @@ int tbk_launch_hk_dense(tbk_model* m, const tbk_hk_plan_t& p, const double* d_A,
                         const double* d_k, const double* d_pos, double* d_H) {
     if (p.nk == 0) return TBK_OK;
     TBK_ARG(p.path != HK_PATH_CSR, "sparse models take tbk_launch_hk_csr");
-    HkArgs a = hk_args(m, d_A, p.nk, p.nk_pad, d_H);
+    HkArgs a = hk_args(m, p.op, d_A, p.nk, p.nk_pad, d_H);
     a.kpts = d_k;
     a.pos = d_pos;
     const int grid = tile_grid(a, (int)((p.nk + TBK_BM - 1) / TBK_BM));  // (nk_pad is only the row stride of A)
     if (m->h_k_inline != nullptr && p.nk == 1 && p.rows == HK_ROWS_NONE) {
         a.k_inline = 1;  // (tbk_hamilton / tbk_eigenval on host buffers, one k-point: no upload of k)
-        for (int d = 0; d < m->dim; ++d) a.k_val[d] = m->h_k_inline[d];
+        for (int d = 0; d < p.op.dim; ++d) a.k_val[d] = m->h_k_inline[d];
         a.pos_raw = m->d_pos_inline;  // convention 1: the raw positions (tbk_hamilton keeps them on the device)
     }
     TBK_ARG(p.rows == HK_ROWS_NONE ? d_k != nullptr || a.k_inline : d_A != nullptr, "phase rows missing");
     TBK_ARG(convention != 1 || mode == HK_TRI || d_pos != nullptr || (a.k_inline && a.pos_raw != nullptr), "convention 1 needs the orbital phases");
     if (p.path == HK_PATH_TINY) {
-        const int strip = (int)(((m->k2 / 2 + 3) / 4 * 2 + 15) / 16 * 16);  // rows of the longest quarter, whole trips of the loop
+        const int strip = (int)(((p.op.k2 / 2 + 3) / 4 * 2 + 15) / 16 * 16);  // rows of the longest quarter, whole trips of the loop
         const size_t lds = ((size_t)4 * strip + 4 * 64 * 2) * sizeof(double);
         StageTimer t(m, TBK_T_HK);
         return by_mode(mode, convention, [&](auto md, auto cv) {
@@ -1104,11 +1105,11 @@ int tbk_launch_hk_dense(tbk_model* m, const tbk_hk_plan_t& p, const double* d_A,
     }
     if (p.path == HK_PATH_STRASSEN) {
         StageTimer t(m, TBK_T_HK);
-        return by_mode(mode, convention, [&](auto md, auto cv) { return launch_strassen<md, cv>(m, a); });
+        return by_mode(mode, convention, [&](auto md, auto cv) { return launch_strassen<md, cv>(m, p.op, a); });
     }
     if (p.path == HK_PATH_STRASSEN2) {
         StageTimer t(m, TBK_T_HK);
-        return by_mode(mode, convention, [&](auto md, auto cv) { return launch_strassen2<md, cv>(m, a); });
+        return by_mode(mode, convention, [&](auto md, auto cv) { return launch_strassen2<md, cv>(m, p.op, a); });
     }
     if (p.splits > 1) {
         const size_t per_split = (size_t)p.nk_pad * a.ncol_pad * 2 * sizeof(double);
@@ -1122,14 +1123,14 @@ int tbk_launch_hk_dense(tbk_model* m, const tbk_hk_plan_t& p, const double* d_A,
 }
 
 // H(k) of n_lines mesh lines of line_len (<= 128) k-points each in ONE launch: line t uses the operand at
-// m->d_B + t * b_stride (a second-level folded model per line) and all lines share the phase rows d_A[K][128]
+// op.d_B + t * b_stride (a second-level folded model per line) and all lines share the phase rows d_A[K][128]
 // (the k-points of a line differ only in the remaining component, which is the same sequence on every line).
 // TRI mode, convention 2 (the eigenvalue path).
-int tbk_launch_hk_dense_lines(tbk_model* m, const double* d_A, int64_t n_lines, int line_len, int64_t b_stride,
-                              double* d_H) {
+int tbk_launch_hk_dense_lines(tbk_model* m, const tbk_operand_t& op, const double* d_A, int64_t n_lines, int line_len,
+                              int64_t b_stride, double* d_H) {
     if (n_lines == 0) return TBK_OK;
     TBK_ARG(line_len >= 1 && line_len <= TBK_BM, "a mesh line must fit one k tile");
-    HkArgs a = hk_args(m, d_A, n_lines * line_len, TBK_BM, d_H);
+    HkArgs a = hk_args(m, op, d_A, n_lines * line_len, TBK_BM, d_H);
     a.a_tile_stride = 0;
     a.b_tile_stride = b_stride;
     a.rows_per_tile = line_len;

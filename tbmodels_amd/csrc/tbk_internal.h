@@ -123,6 +123,17 @@ struct EventPair {
 };
 
 // ------------------------------------------------------------------------------------------------
+// The right-hand side of one H(k) contraction: a lattice and the operand rows staged for it.  The staged operand of a
+// model (tbk_staged_operand, below) or a folded one (tbk_fold_plan_t::operand); tbk_hk_plan stores the one its chunk takes.
+// ------------------------------------------------------------------------------------------------
+struct tbk_operand_t {
+    int dim = 0;
+    int64_t n_r = 0, n_r_pad = 0, k2 = 0;
+    const int32_t* d_R = nullptr;   // [n_r_pad][dim], NULL for k.p
+    const double* d_B = nullptr;    // Bt[k2][ncol_pad / 16][2][16]
+};
+
+// ------------------------------------------------------------------------------------------------
 // folding along one k component (tbk_fold.hip)
 // ------------------------------------------------------------------------------------------------
 struct tbk_fold_plan_t {
@@ -130,23 +141,20 @@ struct tbk_fold_plan_t {
     int dim = 0;                 // dimension of the lattice this plan folds (the folded one has dim - 1)
     int64_t n_r = 0;             // its lattice vectors
     int64_t n_rho = 0, n_rho_pad = 0, k2 = 0;  // folded lattice vectors; K rows of the folded operand
+    int64_t row_len = 0;         // doubles per operand row: ncol_pad * 2
     int capacity = 0;            // folded operands that fit d_B2
     std::vector<int32_t> h_R2;   // host copy of the folded lattice [n_rho][dim - 1] (second-level plans are built on it)
     int32_t* d_R2 = nullptr;     // [n_rho_pad][dim - 1]
     int64_t* d_lptr = nullptr;   // [n_rho_pad + 1] lists of contributing lattice vectors
     int32_t* d_lrec = nullptr;   // r | (negated ? 1 << 31 : 0)
     int32_t* d_rcomp = nullptr;  // [n_r] the folded component of every lattice vector
-    double* d_B2 = nullptr;      // [capacity][k2][ncol_pad * 2] folded operands
+    double* d_B2 = nullptr;      // [capacity][k2][row_len] folded operands
     double* d_table = nullptr;   // [n_r][slots][2] (cos, sin) of the shared-component phases
     int64_t table_entries = 0;   // its capacity in (r, slot) pairs
     tbk_fold_plan_t* sub = nullptr;  // [dim - 1] second-level plans (mesh lines inside a mesh plane), built on demand
-};
-
-struct tbk_fold_saved_t {
-    int dim;
-    int64_t n_r, n_r_pad, k2;
-    int32_t* d_R;
-    double* d_B;
+    double* slot(int s) const { return d_B2 + (size_t)s * k2 * row_len; }
+    // the folded model whose operand rows are in slot s
+    tbk_operand_t operand(int s) const { return {dim - 1, n_rho, n_rho_pad, k2, d_R2, slot(s)}; }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -158,6 +166,8 @@ struct tbk_model {
     std::recursive_mutex mu;
     int device = 0;
     int n_cu = 256;  // compute units of the device (workgroup slots per round = 2 * n_cu for the H(k) kernel)
+    // dim, n_r, n_r_pad, k2, d_R, d_B are the staged operand: written by creation and staging (tbk_api.hip create_common,
+    // tbk_stage.hip), read-only from then on
     int dim = 0;
     int n_orb = 0;
     int64_t n_r = 0;
@@ -177,9 +187,8 @@ struct tbk_model {
     // --- dense: symmetrised hop planes, tile-interleaved  Bt[K2][ncol_pad / 16][2][16] ---
     double* d_B = nullptr;
     // --- dense, n_r_pad >= TBK_STRASSEN_MIN_NR: the seven right operands of one Strassen level, Bs[7][K2 / 2][ncol_pad / 2 / 16][2][16]
-    // (tbk_stage.hip), built from the staged d_B; bs_src is that d_B (a folded operand swapped in by tbk_fold_enter has none)
+    // (tbk_stage.hip), built from the staged d_B and valid for that operand alone (a folded one has none)
     double* d_Bs = nullptr;
-    const double* bs_src = nullptr;
     // --- the 49 right operands of two Strassen levels, Bs2[49][K2 / 4][ncol_pad / 4 / 16][2][16]: the table applied to each block
     // of d_Bs (valid while d_Bs is).  Built by the first call whose chunks take two levels (tbk_stage_strassen2); bs2_skipped:
     // they did not fit a quarter of the free memory then, and the model stays on one level
@@ -265,6 +274,9 @@ struct tbk_model {
     int64_t t_n[TBK_T_COUNT] = {0, 0, 0, 0};
 };
 
+// the operand the model was staged with
+inline tbk_operand_t tbk_staged_operand(const tbk_model* m) { return {m->dim, m->n_r, m->n_r_pad, m->k2, m->d_R, m->d_B}; }
+
 struct tbk_kdotp {
     tbk_model* core = nullptr;  // the dense pipeline with monomial rows in place of phase rows
 };
@@ -321,6 +333,7 @@ enum HkRows {
     HK_ROWS_STRASSEN2, // the 49 blocks As2[49][K2 / 4][Mq]
 };
 struct tbk_hk_plan_t {
+    tbk_operand_t op;         // what the chunk is contracted with: its rows and its contraction are both made for it
     HkPath path = HK_PATH_TILES;
     HkRows rows = HK_ROWS_PHASE;
     int64_t nk = 0;
@@ -329,9 +342,9 @@ struct tbk_hk_plan_t {
     int splits = 1;           // GEMV: K slices; TILES: K splits
     size_t lds = 0;           // GEMV: dynamic LDS per workgroup
 };
-// A function of the model as it stands (a folded operand swapped in by tbk_fold_enter included) and nk.  caller_rows: the
-// caller makes the phase rows whatever the path (never HK_ROWS_NONE).
-tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, int64_t nk, bool caller_rows);
+// A function of the model's options and packed columns, the operand (the staged one, or a folded one: only the staged one
+// has Strassen blocks) and nk.  caller_rows: the caller makes the phase rows whatever the path (never HK_ROWS_NONE).
+tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, const tbk_operand_t& op, int64_t nk, bool caller_rows);
 
 // tbk_api.hip: the chunk pipeline's pieces -- k-points per chunk (with_eig: room for the eigensolver's buffers too), the
 // phase rows of a chunk for its plan (in ws_phase), and H(k) of that chunk from those rows (tbk_eigh.hip uses them as well)
@@ -340,9 +353,9 @@ int fill_rows(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_k);
 int build_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, const double* d_k, const double* d_pos, double* d_H);
 
 // tbk_phase.hip
-int tbk_launch_phase_strassen(tbk_model* m, const double* d_k, int64_t nk, double* d_As);
-int tbk_launch_phase_strassen2(tbk_model* m, const double* d_k, int64_t nk, double* d_As2);
-int tbk_launch_phase(tbk_model* m, const double* d_k, int64_t nk, int64_t nk_pad, double* d_A);
+int tbk_launch_phase_strassen(tbk_model* m, const tbk_operand_t& op, const double* d_k, int64_t nk, double* d_As);
+int tbk_launch_phase_strassen2(tbk_model* m, const tbk_operand_t& op, const double* d_k, int64_t nk, double* d_As2);
+int tbk_launch_phase(tbk_model* m, const tbk_operand_t& op, const double* d_k, int64_t nk, int64_t nk_pad, double* d_A);
 int tbk_launch_orbital_phases(tbk_model* m, const double* d_k, const double* d_pos, int64_t nk, double* d_orb);
 int tbk_launch_monomials(hipStream_t s, const int32_t* d_powers, int dim, int64_t n_p,
                          int64_t n_p_pad, const double* d_k, int64_t nk, int64_t nk_pad,
@@ -355,11 +368,13 @@ int tbk_stage_strassen(tbk_model* m);
 size_t tbk_strassen2_bytes(const tbk_model* m);
 int tbk_stage_strassen2(tbk_model* m);  // builds d_Bs2 from d_Bs if it is missing
 
-// tbk_hk_dense.hip: the H(k) of plan.nk k-points along plan.path (not HK_PATH_CSR); d_A holds the plan's rows
+// tbk_hk_dense.hip: the H(k) of plan.nk k-points with plan.op along plan.path (not HK_PATH_CSR); d_A holds the plan's rows
 int tbk_launch_hk_dense(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_A, int mode, int convention,
                         const double* d_k, const double* d_pos, double* d_H);
 
-int tbk_launch_hk_dense_lines(tbk_model* m, const double* d_A, int64_t n_lines, int line_len, int64_t b_stride, double* d_H);
+// ... and of n_lines mesh lines in one launch: line t takes the operand b_stride doubles behind that of line t - 1 (op: line 0)
+int tbk_launch_hk_dense_lines(tbk_model* m, const tbk_operand_t& op, const double* d_A, int64_t n_lines, int line_len, int64_t b_stride,
+                              double* d_H);
 
 // tbk_hk_csr.hip
 int tbk_launch_hk_csr(tbk_model* m, const double* d_A, int64_t nk, int64_t nk_pad, int mode,
@@ -456,16 +471,52 @@ int tbk_launch_tridiag_tail64(const tbk_eig_plan_t& plan, hipStream_t s, double*
 int tbk_launch_ql(tbk_model* m, hipStream_t s, const double* d_de, int64_t nk, double* d_E, bool beside_ql = false);
 
 // tbk_fold.hip
-int tbk_fold_choose(tbk_model* m, const double* h_k, int64_t nk, std::vector<int64_t>& run_starts);
-int tbk_fold_group_size();
-int tbk_fold_group(tbk_model* m, tbk_fold_plan_t& plan, const double* h_kf, int n_g, int slot0);
-int tbk_fold_lines(tbk_model* m, tbk_fold_plan_t& plan, const double* d_kf, int64_t stride, int n_lines, int slot0 = 0);
-int tbk_fold_enter(tbk_model* m, tbk_fold_plan_t& plan, int slot, tbk_fold_saved_t& saved);
-void tbk_fold_leave(tbk_model* m, const tbk_fold_saved_t& saved);
-int tbk_fold_drop_component(tbk_model* m, const double* d_k, int dim, int f, int64_t nk, double* d_k2);
-int tbk_fold_subplan(tbk_model* m, tbk_fold_plan_t& parent, int f2, int capacity, tbk_fold_plan_t** out);
+// Chunks of a folded call: whole runs (mesh planes) packed up to the chunk size
+std::vector<int64_t> run_schedule(const std::vector<int64_t>& runs, int64_t chunk);
+
+// The mesh lines of a piece [lo, hi) of one run (tbk_fold.hip: analyse)
+struct LineInfo {
+    bool ok = false;     // the piece has a body of whole mesh lines
+    int e2 = -1;         // reduced component shared along a line
+    int64_t L = 0;       // points per line
+    int64_t body = 0;    // first point of the body
+    int64_t n_lines = 0;
+};
+
+// One eigenvalue call on a k list with long runs of one shared component (grids in meshgrid order, stacks of planes): every
+// run is evaluated with the operand folded along that component.  The chunk pipeline (tbk_api.hip) runs over the whole list
+// and calls build() for the H(k) of every chunk, which is assembled run by run.
+struct tbk_folded_call {
+    // h_k: the caller's host copy of the list, or NULL.  Device-resident lists are never read back (include/tbk.h: the device
+    // entry points enqueue and return): the run structure comes from that copy (tbk_eigenval / tbk_eigenval_device_hint) or
+    // not at all.
+    tbk_folded_call(tbk_model* m, const double* d_k, const double* h_k, int64_t nk);
+    bool folds() const { return f >= 0; }  // else the call takes the direct path
+    std::vector<int64_t> runs;             // first k-point of every run, and nk
+    int begin();                           // the k-points without the folded component (main stream), in front of the first build()
+    int build(int64_t c0, int64_t nkc, double* d_H);  // H of k-points [c0, c0 + nkc) of the call (main stream)
+
+private:
+    int run_operand(size_t r, tbk_operand_t* op);
+    int piece_plane(const tbk_operand_t& op, int64_t lo, int64_t hi, double* d_Hp);
+    int fold_body(const tbk_operand_t& from, tbk_fold_plan_t& plan2, const LineInfo& li, int64_t a0, int64_t n, int slot0);
+    int contract_lines(tbk_fold_plan_t& plan2, const LineInfo& li, int64_t a0, int64_t n, double* d_Hp);
+    int piece(const tbk_operand_t& op, int64_t lo, int64_t hi, double* d_Hp);
+    int batched(int64_t c0, int64_t nkc, double* d_H, bool* done);
+
+    tbk_model* m;
+    const double* d_k;
+    const double* h_k;
+    int64_t nk;
+    int f = -1;                       // the folded component (-1: the list does not fold)
+    int dim = 0, dim1 = 0;            // of the model, of a folded run
+    size_t nn2 = 0;                   // doubles per H(k)
+    tbk_fold_plan_t* plan1 = nullptr; // folds the staged operand along f
+    std::vector<int> reduced;         // original component of every reduced one
+    int64_t group_lo = -1;            // first run of the group whose operands are in plan1's buffer
+    double* d_k2 = nullptr;           // [nk][dim1] the k-points without component f (ws_kfold)
+};
 void tbk_fold_release(tbk_model* m);
-int64_t tbk_fold_min_run();
 
 // tbk_peak.hip
 int tbk_run_mfma_f64_peak(double* tflops);

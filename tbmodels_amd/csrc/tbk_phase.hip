@@ -181,30 +181,30 @@ int tbk_launch_orbital_phases(tbk_model* m, const double* d_k, const double* d_p
     return TBK_OK;
 }
 
-int tbk_launch_phase(tbk_model* m, const double* d_k, int64_t nk, int64_t nk_pad, double* d_A) {
-    if (m->n_r_pad == 0 || nk_pad == 0) return TBK_OK;
+int tbk_launch_phase(tbk_model* m, const tbk_operand_t& op, const double* d_k, int64_t nk, int64_t nk_pad, double* d_A) {
+    if (op.n_r_pad == 0 || nk_pad == 0) return TBK_OK;
     StageTimer t(m, TBK_T_PHASE);
-    dim3 grid((unsigned)((nk_pad + 255) / 256), (unsigned)m->n_r_pad);
-    hipLaunchKernelGGL(phase_rows_kernel, grid, dim3(256), 0, m->stream, d_k, m->d_R, m->dim, nk,
-                       nk_pad, m->n_r, d_A);
+    dim3 grid((unsigned)((nk_pad + 255) / 256), (unsigned)op.n_r_pad);
+    hipLaunchKernelGGL(phase_rows_kernel, grid, dim3(256), 0, m->stream, d_k, op.d_R, op.dim, nk,
+                       nk_pad, op.n_r, d_A);
     TBK_HIP(hipGetLastError());
     return TBK_OK;
 }
 
-int tbk_launch_phase_strassen(tbk_model* m, const double* d_k, int64_t nk, double* d_As) {
-    const int64_t mh = tbk_strassen_mh(nk), rh = m->n_r_pad / 2;
+int tbk_launch_phase_strassen(tbk_model* m, const tbk_operand_t& op, const double* d_k, int64_t nk, double* d_As) {
+    const int64_t mh = tbk_strassen_mh(nk), rh = op.n_r_pad / 2;
     StageTimer t(m, TBK_T_PHASE);
     dim3 grid((unsigned)((mh + 255) / 256), (unsigned)rh);
-    hipLaunchKernelGGL(phase_rows_strassen_kernel, grid, dim3(256), 0, m->stream, d_k, m->d_R, m->dim, nk, mh, m->n_r, rh, d_As);
+    hipLaunchKernelGGL(phase_rows_strassen_kernel, grid, dim3(256), 0, m->stream, d_k, op.d_R, op.dim, nk, mh, op.n_r, rh, d_As);
     TBK_HIP(hipGetLastError());
     return TBK_OK;
 }
 
-int tbk_launch_phase_strassen2(tbk_model* m, const double* d_k, int64_t nk, double* d_As2) {
-    const int64_t mq = tbk_strassen_mq(nk), rq = m->n_r_pad / 4;
+int tbk_launch_phase_strassen2(tbk_model* m, const tbk_operand_t& op, const double* d_k, int64_t nk, double* d_As2) {
+    const int64_t mq = tbk_strassen_mq(nk), rq = op.n_r_pad / 4;
     StageTimer t(m, TBK_T_PHASE);
     dim3 grid((unsigned)((mq + 255) / 256), (unsigned)rq);
-    hipLaunchKernelGGL(phase_rows_strassen2_kernel, grid, dim3(256), 0, m->stream, d_k, m->d_R, m->dim, nk, mq, m->n_r, rq, d_As2);
+    hipLaunchKernelGGL(phase_rows_strassen2_kernel, grid, dim3(256), 0, m->stream, d_k, op.d_R, op.dim, nk, mq, op.n_r, rq, d_As2);
     TBK_HIP(hipGetLastError());
     return TBK_OK;
 }

@@ -116,7 +116,6 @@ int tbk_stage_strassen(tbk_model* m) {
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4) return TBK_OK;
     TBK_HIP(hipMalloc((void**)&m->d_Bs, bytes));
     m->staged_bytes += (int64_t)bytes;
-    m->bs_src = m->d_B;
     dim3 grid((m->ncol_pad + 255) / 256, (unsigned)kh);
     hipLaunchKernelGGL(stage_strassen_kernel, grid, dim3(256), 0, m->stream, m->d_B, kh, m->ncol_pad, m->d_Bs);
     TBK_HIP(hipGetLastError());
