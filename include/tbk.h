@@ -186,6 +186,37 @@ int tbk_tridiagonal_reduce(int device, int n_orb, int64_t nk, const double* H, i
  * `eig_roofline.standalone`): the in-pipeline stage time shares the FP64 pipe with the next chunk's H(k). */
 int tbk_reduce_standalone(int device, int n_orb, int64_t nk, int reps, double* us_per_matrix);
 
+/* ---- density of states of a uniform k mesh: the linear tetrahedron method (not in the reference) ---------------------------
+ * mesh   int32 [dim]   a Gamma-centred, periodic mesh: k = (i_1 / n_1, ..., i_dim / n_dim) in np.meshgrid(indexing="ij") order
+ * the energy grid is E_j = e_min + j e_step, j = 0 .. n_e - 1  (2 <= n_e <= 2^20, e_step > 0)
+ * nos    double [n_e]  nos[j] = states per unit cell with energy <= E_j, from linear interpolation of every band inside the six
+ *                      tetrahedra that share the main diagonal of a mesh cell (dim = 3; its two triangles in dim = 2).  The density
+ *                      of states is its difference quotient; nos[n_e - 1] == n_orb when the grid ends above the spectrum.
+ * Only dim in {2, 3}.  The kernel (csrc/tbk_dos.hip) accumulates in 64-bit fixed point with a resolution of 2^-40 per simplex
+ * (|error| <= 4.5e-13 n_orb) and sums in integers, so for given eigenvalues nos does not depend on the order in which the
+ * device runs its waves: the same call gives the same bits, as for the eigenvalues above.
+ * Argument errors (TBK_ERR_ARGUMENT): dim not in {2, 3}, a mesh entry < 1, 2^31 mesh points or more, n_e outside [2, 2^20],
+ * e_step <= 0 or not finite, e_min not finite, a NULL pointer, a k.p handle.  Host buffers; synchronous. */
+
+/* The kernel alone on eigenvalues the caller brings: E[NK][n_orb] in mesh order, every row ascending (what tbk_tridiagonal_reduce is
+ * to the eigensolver: for tests, and for callers that have their own eigenvalues). */
+int tbk_dos_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double e_min, double e_step,
+                             int64_t n_e, double* nos_out);
+/* The whole call: the mesh's k list is made on the host and evaluated through the path of tbk_eigenval_device_hint (dense models
+ * fold, CSR models work unchanged), the eigenvalues of the whole mesh stay in device memory (NK n_orb doubles; TBK_ERR_MEMORY
+ * when they do not fit), the kernel runs on them and n_e doubles come back.  Non-finite eigenvalues and no convergence are
+ * reported as by tbk_eigenval, in front of the kernel. */
+int tbk_dos(tbk_model* m, const int32_t* mesh, double e_min, double e_step, int64_t n_e, double* nos_out);
+/* On several devices from one process (handles as for tbk_eigenval_multi): handle i takes a contiguous slab of ceil(n_1 / n_handles)
+ * cells along axis 0 and evaluates its planes plus the one periodic neighbour plane it needs; the host adds the handles' shares in
+ * handle order; handles whose slab is empty are skipped.  n_handles == 1 is tbk_dos.  The internal eigenvalue calls have another
+ * shape than on one device, so the result agrees with tbk_dos to rounding (1e-13 level), not bitwise. */
+int tbk_dos_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, double e_min, double e_step, int64_t n_e,
+                  double* nos_out);
+/* While TBK_OPT_TIMING is on: ms = summed HIP-event time of the density-of-states kernels of this handle's tbk_dos calls (the
+ * eigenvalue stages are in tbk_get_timing, whose array length is fixed), calls = how many; reset = 1 clears. */
+int tbk_dos_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
 /* ---- k.p models (kdotp.py:51-100): H(k) = sum_p prod_d k_d^powers[p][d] * coeffs[p] ------- */
 int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, const int32_t* powers,
                      const double* coeffs, tbk_kdotp** out);

@@ -66,6 +66,10 @@ SIGNATURES = {
     "tbk_synchronize": (_c_int, [_vp]),
     "tbk_tridiagonal_reduce": (_c_int, [_c_int, _c_int, _c_i64, _vp, _c_int, _vp, _vp, _vp]),
     "tbk_reduce_standalone": (_c_int, [_c_int, _c_int, _c_i64, _c_int, ctypes.POINTER(ctypes.c_double)]),
+    "tbk_dos_from_eigenvalues": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, ctypes.c_double, ctypes.c_double, _c_i64, _vp]),
+    "tbk_dos": (_c_int, [_vp, _vp, ctypes.c_double, ctypes.c_double, _c_i64, _vp]),
+    "tbk_dos_multi": (_c_int, [_vp, _c_int, _vp, ctypes.c_double, ctypes.c_double, _c_i64, _vp]),
+    "tbk_dos_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
     "tbk_kdotp_create": (_c_int, [_c_int, _c_int, _c_int, _c_i64, _vp, _vp, _pp]),
     "tbk_kdotp_destroy": (None, [_vp]),
     "tbk_kdotp_hamilton": (_c_int, [_vp, _vp, _c_i64, _vp]),

@@ -33,7 +33,10 @@ try:  # fast content hash for the staging fingerprint; zlib is the fallback
 except ImportError:  # pragma: no cover
     _xxhash = None
 
-__all__ = ("Model",)
+__all__ = ("Model", "DensityOfStates")
+
+#: what ``Model.dos`` returns: the energy grid (NE,), the number of states at its points (NE,), their difference quotient (NE - 1,)
+DensityOfStates = co.namedtuple("DensityOfStates", ("energies", "nos", "dos"))
 
 
 def _devices_from_env():
@@ -773,6 +776,62 @@ class Model:
                                           _lib.ptr(eig), _lib.ptr(vec))
             )
         return (eig[0], vec[0]) if single else (eig, vec)
+
+    def dos(self, mesh, energies):
+        """
+        Number of states and density of states from a uniform k mesh by the linear tetrahedron method, computed on the GPU
+        from eigenvalues that never leave it.  Not in the reference (``_tb_model.py`` has no density of states).
+
+        ``mesh`` is a sequence of ``dim`` positive integers ``(n_1, ..., n_dim)``: the Gamma-centred, periodic mesh
+        ``k = (i_1 / n_1, ..., i_dim / n_dim)``.  ``energies`` is a 1-D ascending, uniformly spaced grid of at least two points
+        (``max|diff - mean diff| <= 1e-9 mean diff``).  Returns the named tuple ``(energies, nos, dos)``: ``nos[j]`` (shape
+        ``(NE,)``) is the number of states per unit cell with energy ``<= energies[j]``, ``dos = np.diff(nos) / step`` (shape
+        ``(NE - 1,)``) belongs to the bin midpoints.  ``nos`` is bounded and exact in its state count for flat bands
+        (``nos[-1] == size`` when the grid ends above the spectrum); the pointwise g(E) is not computed.
+
+        Decomposition: band ``b`` (the b-th ascending eigenvalue at every mesh point) is interpolated linearly inside simplices.
+        In three dimensions every mesh cell is cut into the 6 tetrahedra that share its main diagonal -- corners
+        ``0, e_a, e_a + e_b, e_a + e_b + e_c`` for every order ``(a, b, c)`` of the axes, weight ``1 / (6 NK)`` each; in two
+        dimensions into the 2 triangles ``0, e_a, e_a + e_b``, weight ``1 / (2 NK)``.  One-dimensional models raise
+        ``ValueError``.  With several ``devices`` every device takes a slab of the mesh along its first axis.
+        """
+        if self.dim not in (2, 3):
+            raise ValueError("dos needs a 2- or 3-dimensional model, this one has dimension {}".format(self.dim))
+        try:
+            mesh_list = list(mesh)
+        except TypeError:
+            raise ValueError("mesh must be a sequence of {} positive integers".format(self.dim)) from None
+        if len(mesh_list) != self.dim:
+            raise ValueError("mesh has {} entries but the model has dimension {}".format(len(mesh_list), self.dim))
+        for entry in mesh_list:
+            if isinstance(entry, (bool, np.bool_)) or not isinstance(entry, (int, np.integer)):
+                raise ValueError("mesh entries must be integers, got {!r}".format(entry))
+            if entry < 1:
+                raise ValueError("mesh entries must be positive, got {!r}".format(entry))
+        mesh_array = np.array(mesh_list, dtype=np.int64)
+        if int(np.prod(mesh_array, dtype=object)) >= 2 ** 31:
+            raise ValueError("the mesh has 2^31 points or more")
+        mesh_array = np.ascontiguousarray(mesh_array, dtype=np.int32)
+        grid = np.array(energies, dtype=np.float64)
+        if grid.ndim != 1 or grid.shape[0] < 2:
+            raise ValueError("energies must be a 1-D array of at least two points")
+        if not np.all(np.isfinite(grid)):
+            raise ValueError("energies must be finite")
+        steps = np.diff(grid)
+        step = float((grid[-1] - grid[0]) / (grid.shape[0] - 1))  # the mean step
+        if not step > 0 or np.any(steps <= 0):
+            raise ValueError("energies must be ascending")
+        if np.abs(steps - step).max() > 1e-9 * step:
+            raise ValueError("energies must be uniformly spaced")
+        nos = np.empty(grid.shape[0], dtype=np.float64)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigenval
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_dos_multi(handles, n_handles, _lib.ptr(mesh_array), float(grid[0]), step, grid.shape[0],
+                                         _lib.ptr(nos))
+            )
+        return DensityOfStates(grid, nos, np.diff(nos) / step)
 
     def construct_kdotp(self, k, order):
         """

@@ -1,0 +1,444 @@
+// tbk_dos.hip -- the number of states nos(E) of a uniform, periodic k mesh by the linear tetrahedron method (dim = 3; triangles in
+// dim = 2), from eigenvalues that are already in device memory.  Not in the reference (it has no density of states at all);
+// DESIGN.md section 10 has the formulas, the layout and the measurements.
+//
+//   E[NK][n_orb]   ascending eigenvalues per mesh point, mesh order = np.meshgrid(..., indexing="ij") (last axis fastest)
+//   nos[j]         = 1 / (S NK) * sum over (cell, band, simplex) of n_T(E_j),   S = 6 tetrahedra (2 triangles) per cell
+//
+// A work item is one (cell, band) pair, band fastest: a wave reads 64 consecutive doubles of a row of E per corner.  Per simplex
+// the corners are sorted, j_lo = first j with E_j >= e1 and j_hi = first j with E_j >= e_top are found from one multiply (the
+// grid is uniform) and settled by the comparison itself, n_T(E_j) is added for j_lo <= j < j_hi only, and the "1" that every
+// bin from j_hi upwards would receive is ONE integer count at j_hi: the prefix sum over the counts comes last and is exact.
+//
+// Reproducibility (include/tbk.h: the same call gives the same bits).  Floating-point atomics add in arrival order, in LDS
+// as in global memory, so there are none here: n_T in [0, 1] is accumulated in 64-bit FIXED POINT (integer adds commute), every
+// workgroup stores its bins with plain stores into its own row of a [n_workgroups][NE] buffer, and a second kernel sums the rows
+// in integers as well.  The result does not depend on the order in which waves run, nor on the number of workgroups.
+//
+// Bound (measured): VALU issue -- the bin loop of a simplex runs for the longest range among a wave's lanes and every
+// bin costs one or two FP64 divisions; LDS adds are 1 in 55 instructions and the corner loads ~95 GB/s out of L2.
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "tbk_internal.h"
+
+namespace {
+
+constexpr int DOS_THREADS = 256;
+constexpr int DOS_TILE = 4096;  // energy bins per LDS tile: 4096 * (8 + 4) bytes = 48 KiB; longer grids take gridDim.y tiles
+// Fixed point: a contribution n_T in [0, 1] is stored as round(n_T * 2^40), i.e. with an error of at most 2^-41 each.  A bin of
+// nos sums at most S NK n_orb of them and is divided by S NK: |error| <= n_orb * 2^-41 = 4.5e-13 n_orb in the worst case
+// (every contribution off by half a unit in the same direction), a twentieth of the 1e-11 n_orb the kernel is tested to.
+// Overflow: a workgroup takes at most DOS_MAX_ITEMS (cell, band) pairs, so one of its bins receives at most
+// 6 * 2^20 contributions of at most 2^40: 6 * 2^60 < 2^64.
+constexpr int DOS_FRAC_BITS = 40;
+constexpr int64_t DOS_MAX_ITEMS = int64_t(1) << 20;
+// the second kernel splits every workgroup's 64-bit bin into its high 44 and low 20 bits and sums each in 64 bits: exact up to
+// 2^20 workgroups (the launcher never takes more than that)
+constexpr int DOS_SPLIT_BITS = 20;
+constexpr int64_t DOS_MAX_NE = int64_t(1) << 20;  // documented limit of the energy grid (tbk.h)
+
+struct DosGeom {
+    int n0_cells;   // cells along axis 0 this launch covers
+    int n0_planes;  // planes of axis 0 in E: n0_cells + 1 for a slab (its periodic neighbour plane is the last), n0_cells for a whole mesh
+    int n1, n2;     // the other axes (n2 = 1 in two dimensions)
+    int n_orb;
+    int64_t items;         // n0_cells * n1 * n2 * n_orb
+    int64_t items_per_wg;  // contiguous items per workgroup, <= DOS_MAX_ITEMS
+};
+
+__device__ __forceinline__ double dos_grid(double e_min, double e_step, int j) {
+    // two roundings, never an FMA: the same number as NumPy's e_min + j * e_step
+    return __dadd_rn(e_min, __dmul_rn((double)j, e_step));
+}
+
+// first j in [0, n_e] with E_j >= e (n_e: none).  The multiply gives a guess, the comparisons decide.  NaN -> 0, no iteration.
+__device__ __forceinline__ int dos_first_at_or_above(double e, double e_min, double e_step, double inv_step, int n_e) {
+    double t = ceil((e - e_min) * inv_step);
+    t = fmin(fmax(t, 0.0), (double)n_e);
+    int j = (int)t;
+    while (j > 0 && dos_grid(e_min, e_step, j - 1) >= e) --j;
+    while (j < n_e && dos_grid(e_min, e_step, j) < e) ++j;
+    return j;
+}
+
+__device__ __forceinline__ void dos_sort2(double& a, double& b) {
+    const double lo = fmin(a, b), hi = fmax(a, b);
+    a = lo;
+    b = hi;
+}
+
+struct DosWindow {
+    double e_min, e_step, inv_step;
+    int n_e;
+    int tile_lo, tile_n;  // this workgroup's bins
+};
+
+__device__ __forceinline__ void dos_add(unsigned long long* part, int bin, double frac) {
+    frac = fmin(fmax(frac, 0.0), 1.0);
+    atomicAdd(&part[bin], (unsigned long long)__double2ll_rn(frac * (double)(1ull << DOS_FRAC_BITS)));
+}
+
+// one tetrahedron: DESIGN 10.1 (the ranges are half-open as written there; the comparisons select the branch, so a branch with
+// a zero denominator is empty and never evaluated)
+__device__ __forceinline__ void dos_tetrahedron(double e1, double e2, double e3, double e4, const DosWindow& w, unsigned long long* part,
+                                                unsigned* step) {
+    dos_sort2(e1, e2);
+    dos_sort2(e3, e4);
+    dos_sort2(e1, e3);
+    dos_sort2(e2, e4);
+    dos_sort2(e2, e3);
+    const int j_lo = dos_first_at_or_above(e1, w.e_min, w.e_step, w.inv_step, w.n_e);
+    const int j_hi = dos_first_at_or_above(e4, w.e_min, w.e_step, w.inv_step, w.n_e);
+    if (j_hi >= w.tile_lo && j_hi < w.tile_lo + w.tile_n) atomicAdd(&step[j_hi - w.tile_lo], 1u);
+    const int lo = max(j_lo, w.tile_lo), hi = min(j_hi, w.tile_lo + w.tile_n);
+    const double e21 = e2 - e1, e31 = e3 - e1, e41 = e4 - e1, e32 = e3 - e2, e42 = e4 - e2, e43 = e4 - e3;
+    for (int j = lo; j < hi; ++j) {
+        const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e4 here
+        double n;
+        if (E < e2) {
+            const double x = E - e1;
+            n = x * x * x / (e21 * e31 * e41);
+        } else if (E < e3) {
+            const double x = E - e2;
+            n = (e21 * e21 + 3.0 * e21 * x + 3.0 * x * x - (e31 + e42) / (e32 * e42) * (x * x * x)) / (e31 * e41);
+        } else {
+            const double x = e4 - E;
+            n = 1.0 - x * x * x / (e41 * e42 * e43);
+        }
+        dos_add(part, j - w.tile_lo, n);
+    }
+}
+
+__device__ __forceinline__ void dos_triangle(double e1, double e2, double e3, const DosWindow& w, unsigned long long* part, unsigned* step) {
+    dos_sort2(e1, e2);
+    dos_sort2(e2, e3);
+    dos_sort2(e1, e2);
+    const int j_lo = dos_first_at_or_above(e1, w.e_min, w.e_step, w.inv_step, w.n_e);
+    const int j_hi = dos_first_at_or_above(e3, w.e_min, w.e_step, w.inv_step, w.n_e);
+    if (j_hi >= w.tile_lo && j_hi < w.tile_lo + w.tile_n) atomicAdd(&step[j_hi - w.tile_lo], 1u);
+    const int lo = max(j_lo, w.tile_lo), hi = min(j_hi, w.tile_lo + w.tile_n);
+    const double e21 = e2 - e1, e31 = e3 - e1, e32 = e3 - e2;
+    for (int j = lo; j < hi; ++j) {
+        const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e3 here
+        double n;
+        if (E < e2) {
+            const double x = E - e1;
+            n = x * x / (e21 * e31);
+        } else {
+            const double x = e3 - E;
+            n = 1.0 - x * x / (e31 * e32);
+        }
+        dos_add(part, j - w.tile_lo, n);
+    }
+}
+
+// grid: (workgroups, energy tiles).  part_g / step_g: [gridDim.x][n_e]; every element is written by exactly one workgroup.
+template <int DIM>
+__global__ void __launch_bounds__(DOS_THREADS) dos_accumulate_kernel(const double* __restrict__ E, DosGeom g, double e_min, double e_step,
+                                                                     double inv_step, int n_e, unsigned long long* __restrict__ part_g,
+                                                                     unsigned* __restrict__ step_g) {
+    extern __shared__ unsigned long long dos_lds[];
+    DosWindow w;
+    w.e_min = e_min;
+    w.e_step = e_step;
+    w.inv_step = inv_step;
+    w.n_e = n_e;
+    w.tile_lo = (int)blockIdx.y * DOS_TILE;
+    w.tile_n = min(DOS_TILE, n_e - w.tile_lo);
+    unsigned long long* part = dos_lds;                                 // [tile_n]
+    unsigned* step = reinterpret_cast<unsigned*>(dos_lds + w.tile_n);  // [tile_n]
+    const int tid = (int)threadIdx.x;
+    for (int t = tid; t < w.tile_n; t += DOS_THREADS) {
+        part[t] = 0ull;
+        step[t] = 0u;
+    }
+    __syncthreads();
+
+    const int64_t first = (int64_t)blockIdx.x * g.items_per_wg;
+    const int64_t last = min(first + g.items_per_wg, g.items);
+    for (int64_t it = first + tid; it < last; it += DOS_THREADS) {
+        const int64_t cell64 = it / g.n_orb;
+        const int band = (int)(it - cell64 * g.n_orb);
+        int c = (int)cell64;  // NK < 2^31 (checked by the launcher)
+        const int i2 = c % g.n2;
+        c /= g.n2;
+        const int i1 = c % g.n1;
+        const int i0 = c / g.n1;  // < n0_cells
+        const int j0 = i0 + 1 == g.n0_planes ? 0 : i0 + 1;
+        const int j1 = i1 + 1 == g.n1 ? 0 : i1 + 1;
+        const int j2 = i2 + 1 == g.n2 ? 0 : i2 + 1;
+        auto at = [&](int a0, int a1, int a2) -> double {
+            const int64_t k = ((int64_t)a0 * g.n1 + a1) * g.n2 + a2;
+            return E[k * g.n_orb + band];
+        };
+        if (DIM == 3) {
+            // corner c_xyz: x, y, z = step along axis 0, 1, 2
+            const double c000 = at(i0, i1, i2), c100 = at(j0, i1, i2), c010 = at(i0, j1, i2), c110 = at(j0, j1, i2);
+            const double c001 = at(i0, i1, j2), c101 = at(j0, i1, j2), c011 = at(i0, j1, j2), c111 = at(j0, j1, j2);
+            // the six orders (a, b, c) of the axes: corners 0, e_a, e_a + e_b, e_a + e_b + e_c
+            dos_tetrahedron(c000, c100, c110, c111, w, part, step);  // (0, 1, 2)
+            dos_tetrahedron(c000, c100, c101, c111, w, part, step);  // (0, 2, 1)
+            dos_tetrahedron(c000, c010, c110, c111, w, part, step);  // (1, 0, 2)
+            dos_tetrahedron(c000, c010, c011, c111, w, part, step);  // (1, 2, 0)
+            dos_tetrahedron(c000, c001, c101, c111, w, part, step);  // (2, 0, 1)
+            dos_tetrahedron(c000, c001, c011, c111, w, part, step);  // (2, 1, 0)
+        } else {
+            const double c00 = at(i0, i1, 0), c10 = at(j0, i1, 0), c01 = at(i0, j1, 0), c11 = at(j0, j1, 0);
+            dos_triangle(c00, c10, c11, w, part, step);  // (0, 1)
+            dos_triangle(c00, c01, c11, w, part, step);  // (1, 0)
+        }
+    }
+    __syncthreads();
+    const int64_t row = (int64_t)blockIdx.x * n_e + w.tile_lo;
+    for (int t = tid; t < w.tile_n; t += DOS_THREADS) {
+        part_g[row + t] = part[t];
+        step_g[row + t] = step[t];
+    }
+}
+
+// one thread per bin: the workgroups' rows in index order, in integers (high and low part of every 64-bit bin apart, so that
+// neither sum overflows)
+__global__ void __launch_bounds__(DOS_THREADS) dos_reduce_kernel(const unsigned long long* __restrict__ part_g, const unsigned* __restrict__ step_g,
+                                                                 int n_wg, int n_e, double* __restrict__ frac, long long* __restrict__ count) {
+    const int j = (int)blockIdx.x * DOS_THREADS + (int)threadIdx.x;
+    if (j >= n_e) return;
+    unsigned long long hi = 0, lo = 0;
+    long long c = 0;
+    for (int wg = 0; wg < n_wg; ++wg) {
+        const unsigned long long p = part_g[(int64_t)wg * n_e + j];
+        hi += p >> DOS_SPLIT_BITS;
+        lo += p & ((1ull << DOS_SPLIT_BITS) - 1);
+        c += (long long)step_g[(int64_t)wg * n_e + j];
+    }
+    frac[j] = (double)hi * (1.0 / (double)(1ull << (DOS_FRAC_BITS - DOS_SPLIT_BITS))) + (double)lo * (1.0 / (double)(1ull << DOS_FRAC_BITS));
+    count[j] = c;
+}
+
+// one workgroup: nos[j] = (frac[j] + sum_{i <= j} count[i]) / denom.  Every thread owns a contiguous segment of the grid.
+__global__ void __launch_bounds__(DOS_THREADS) dos_scan_kernel(const double* __restrict__ frac, const long long* __restrict__ count, int n_e,
+                                                               double denom, double* __restrict__ nos) {
+    __shared__ long long total[DOS_THREADS];
+    const int tid = (int)threadIdx.x;
+    const int seg = (n_e + DOS_THREADS - 1) / DOS_THREADS;
+    const int lo = min(n_e, tid * seg), hi = min(n_e, lo + seg);
+    long long sum = 0;
+    for (int j = lo; j < hi; ++j) sum += count[j];
+    total[tid] = sum;
+    __syncthreads();
+    long long run = 0;
+    for (int t = 0; t < tid; ++t) run += total[t];
+    for (int j = lo; j < hi; ++j) {
+        run += count[j];
+        nos[j] = (frac[j] + (double)run) / denom;
+    }
+}
+
+struct DosLaunch {
+    DosGeom g;
+    int n_wg = 0, n_tiles = 0, n_e = 0;
+    size_t off_step = 0, off_frac = 0, off_count = 0, ws_bytes = 0;
+};
+
+size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+
+// dim in {2, 3}; cells0 cells along axis 0 out of planes0 planes held in E (planes0 == cells0: the axis wraps onto itself)
+int dos_plan(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb, int64_t n_e, DosLaunch* out) {
+    DosLaunch L;
+    L.g.n0_cells = (int)cells0;
+    L.g.n0_planes = (int)planes0;
+    L.g.n1 = mesh[1];
+    L.g.n2 = dim == 3 ? mesh[2] : 1;
+    L.g.n_orb = n_orb;
+    L.g.items = cells0 * L.g.n1 * L.g.n2 * n_orb;
+    L.n_e = (int)n_e;
+    L.n_tiles = (int)((n_e + DOS_TILE - 1) / DOS_TILE);
+    // workgroups: enough to fill the chip, no more rows than 2^24 bins of partials, never more than DOS_MAX_ITEMS items each
+    const int64_t by_memory = std::max<int64_t>(1, (int64_t(1) << 24) / n_e);
+    int64_t n_wg = std::min<int64_t>((L.g.items + DOS_THREADS - 1) / DOS_THREADS, std::min<int64_t>(1024, by_memory));
+    n_wg = std::max<int64_t>(n_wg, (L.g.items + DOS_MAX_ITEMS - 1) / DOS_MAX_ITEMS);
+    TBK_ARG(n_wg <= (int64_t(1) << DOS_SPLIT_BITS), "mesh x orbitals too large for one density-of-states call");
+    L.g.items_per_wg = (L.g.items + n_wg - 1) / n_wg;
+    L.n_wg = (int)((L.g.items + L.g.items_per_wg - 1) / L.g.items_per_wg);
+    const size_t bins = (size_t)L.n_wg * (size_t)n_e;
+    L.off_step = align256(bins * sizeof(unsigned long long));
+    L.off_frac = L.off_step + align256(bins * sizeof(unsigned));
+    L.off_count = L.off_frac + align256((size_t)n_e * sizeof(double));
+    L.ws_bytes = L.off_count + align256((size_t)n_e * sizeof(long long));
+    *out = L;
+    return TBK_OK;
+}
+
+// enqueue: E -> nos on stream s (d_ws: L.ws_bytes).  denom = S * NK of the WHOLE mesh.
+int dos_launch(hipStream_t s, int dim, const DosLaunch& L, const double* d_E, double e_min, double e_step, double denom, void* d_ws,
+               double* d_nos) {
+    char* ws = static_cast<char*>(d_ws);
+    auto* part_g = reinterpret_cast<unsigned long long*>(ws);
+    auto* step_g = reinterpret_cast<unsigned*>(ws + L.off_step);
+    auto* frac = reinterpret_cast<double*>(ws + L.off_frac);
+    auto* count = reinterpret_cast<long long*>(ws + L.off_count);
+    const size_t lds = (size_t)std::min<int64_t>(L.n_e, DOS_TILE) * (sizeof(unsigned long long) + sizeof(unsigned));
+    const dim3 grid((unsigned)L.n_wg, (unsigned)L.n_tiles);
+    if (dim == 3)
+        hipLaunchKernelGGL(dos_accumulate_kernel<3>, grid, dim3(DOS_THREADS), lds, s, d_E, L.g, e_min, e_step, 1.0 / e_step, L.n_e, part_g, step_g);
+    else
+        hipLaunchKernelGGL(dos_accumulate_kernel<2>, grid, dim3(DOS_THREADS), lds, s, d_E, L.g, e_min, e_step, 1.0 / e_step, L.n_e, part_g, step_g);
+    TBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(dos_reduce_kernel, dim3((unsigned)((L.n_e + DOS_THREADS - 1) / DOS_THREADS)), dim3(DOS_THREADS), 0, s, part_g, step_g,
+                       L.n_wg, L.n_e, frac, count);
+    TBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(dos_scan_kernel, dim3(1), dim3(DOS_THREADS), 0, s, frac, count, L.n_e, denom, d_nos);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// the checks every entry point shares; *nk_total = points of the whole mesh
+int dos_check(int dim, const int32_t* mesh, double e_step, int64_t n_e, const double* nos_out, int64_t* nk_total) {
+    TBK_ARG(dim == 2 || dim == 3, "the density of states needs a 2- or 3-dimensional mesh");
+    TBK_ARG(mesh != nullptr && nos_out != nullptr, "mesh / nos is NULL");
+    int64_t nk = 1;
+    for (int d = 0; d < dim; ++d) {
+        TBK_ARG(mesh[d] >= 1, "a mesh entry is < 1");
+        nk *= mesh[d];
+        TBK_ARG(nk < (int64_t(1) << 31), "the mesh has 2^31 points or more");
+    }
+    TBK_ARG(n_e >= 2, "the energy grid needs at least two points");
+    TBK_ARG(n_e <= DOS_MAX_NE, "the energy grid has more than 2^20 points");
+    TBK_ARG(std::isfinite(e_step) && e_step > 0.0, "the energy step must be positive and finite");
+    *nk_total = nk;
+    return TBK_OK;
+}
+
+}  // namespace
+
+extern "C" int tbk_dos_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double e_min, double e_step,
+                                        int64_t n_e, double* nos_out) {
+    int64_t nk = 0;
+    TBK_CHECK(dos_check(dim, mesh, e_step, n_e, nos_out, &nk));
+    TBK_ARG(E != nullptr, "E is NULL");
+    TBK_ARG(n_orb >= 1, "n_orb < 1");
+    TBK_ARG(std::isfinite(e_min), "e_min is not finite");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
+        (void)hipGetLastError();
+        tbk_set_error("no HIP device visible: libtbk has no CPU path");
+        return TBK_ERR_DEVICE;
+    }
+    TBK_ARG(device >= 0 && device < n_dev, "device out of range");
+    TBK_HIP(hipSetDevice(device));
+    DosLaunch L;
+    TBK_CHECK(dos_plan(dim, mesh, mesh[0], mesh[0], n_orb, n_e, &L));
+    const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double);
+    DevBuf d_E, d_ws, d_nos;
+    const int rc = [&]() -> int {
+        TBK_CHECK(d_E.reserve(e_bytes));
+        TBK_CHECK(d_ws.reserve(L.ws_bytes));
+        TBK_CHECK(d_nos.reserve((size_t)n_e * sizeof(double)));
+        TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
+        TBK_CHECK(dos_launch(nullptr, dim, L, d_E.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk, d_ws.ptr, d_nos.as<double>()));
+        TBK_HIP(hipMemcpy(nos_out, d_nos.ptr, (size_t)n_e * sizeof(double), hipMemcpyDeviceToHost));
+        return TBK_OK;
+    }();
+    d_E.release();
+    d_ws.release();
+    d_nos.release();
+    return rc;
+}
+
+// Cells [p_lo, p_lo + p_count) along axis 0 of the mesh on one handle: the eigenvalues of those planes and of the one periodic
+// neighbour plane the last cells need (none when the slab is the whole axis) stay in HBM; nos_out receives this slab's share of
+// nos, already divided by S * NK of the whole mesh.
+int tbk_dos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_count, double e_min, double e_step, int64_t n_e, double* nos_out) {
+    TBK_ARG(m != nullptr, "model is NULL");
+    TBK_LOCK(m);
+    TBK_ARG(!m->kdotp, "a k.p model has no Brillouin zone");
+    int64_t nk_total = 0;
+    TBK_CHECK(dos_check(m->dim, mesh, e_step, n_e, nos_out, &nk_total));
+    TBK_ARG(std::isfinite(e_min), "e_min is not finite");
+    const int dim = m->dim, n_orb = m->n_orb;
+    const int64_t n0 = mesh[0];
+    TBK_ARG(p_lo >= 0 && p_count >= 1 && p_lo + p_count <= n0, "slab outside the mesh");
+    TBK_HIP(hipSetDevice(m->device));
+    const int64_t planes = p_count == n0 ? n0 : p_count + 1;
+    const int64_t plane_pts = nk_total / n0, nk = planes * plane_pts;
+    DosLaunch L;
+    TBK_CHECK(dos_plan(dim, mesh, p_count, planes, n_orb, n_e, &L));
+
+    // the k list of the slab, in mesh order (the order tbk_fold.hip recognises): k_d = i_d / n_d
+    std::vector<double> h_k;
+    try {
+        h_k.resize((size_t)nk * dim);
+    } catch (...) {
+        tbk_set_error("cannot allocate the k list of the mesh");
+        return TBK_ERR_MEMORY;
+    }
+    {
+        const int n1 = mesh[1], n2 = dim == 3 ? mesh[2] : 1;
+        size_t q = 0;
+        for (int64_t p = 0; p < planes; ++p) {
+            const double k0 = (double)((p_lo + p) % n0) / (double)n0;
+            for (int i1 = 0; i1 < n1; ++i1) {
+                const double k1 = (double)i1 / (double)n1;
+                for (int i2 = 0; i2 < n2; ++i2) {
+                    h_k[q++] = k0;
+                    h_k[q++] = k1;
+                    if (dim == 3) h_k[q++] = (double)i2 / (double)n2;
+                }
+            }
+        }
+    }
+    const size_t k_bytes = h_k.size() * sizeof(double);
+    TBK_CHECK(m->ws_k.reserve(k_bytes));
+    TBK_CHECK(m->ws_out.reserve((size_t)nk * n_orb * sizeof(double)));
+    TBK_CHECK(m->ws_dos.reserve(L.ws_bytes + align256((size_t)n_e * sizeof(double))));
+    TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, h_k.data(), k_bytes, hipMemcpyHostToDevice, m->stream));
+    // the existing pipeline with the host list as the fold hint: dense models fold, CSR models take their own path
+    TBK_CHECK(tbk_eigenval_device_hint(m, m->ws_k.as<double>(), h_k.data(), nk, m->ws_out.as<double>()));
+    TBK_CHECK(tbk_eigenval_check(m));  // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigenval
+
+    double* d_nos = reinterpret_cast<double*>(static_cast<char*>(m->ws_dos.ptr) + L.ws_bytes);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timed = m->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    if (timed) (void)hipEventRecord(ev[0], m->stream);
+    int rc = dos_launch(m->stream, dim, L, m->ws_out.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk_total, m->ws_dos.ptr, d_nos);
+    if (timed) (void)hipEventRecord(ev[1], m->stream);
+    if (rc == TBK_OK) {
+        rc = [&]() -> int {
+            TBK_HIP(hipMemcpyAsync(nos_out, d_nos, (size_t)n_e * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+            TBK_HIP(hipStreamSynchronize(m->stream));
+            return TBK_OK;
+        }();
+    }
+    if (timed && rc == TBK_OK) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) {
+            m->dos_ms += (double)ms;
+            m->dos_calls += 1;
+        }
+    }
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
+extern "C" int tbk_dos(tbk_model* m, const int32_t* mesh, double e_min, double e_step, int64_t n_e, double* nos_out) {
+    TBK_ARG(m != nullptr, "model is NULL");
+    TBK_ARG(mesh != nullptr, "mesh / nos is NULL");
+    TBK_ARG(m->dim == 2 || m->dim == 3, "the density of states needs a 2- or 3-dimensional mesh");
+    TBK_ARG(mesh[0] >= 1, "a mesh entry is < 1");
+    return tbk_dos_slab(m, mesh, 0, mesh[0], e_min, e_step, n_e, nos_out);
+}
+
+extern "C" int tbk_dos_timing(tbk_model* m, double* ms, int64_t* calls, int reset) {
+    TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr, "model / ms / calls is NULL");
+    TBK_LOCK(m);
+    *ms = m->dos_ms;
+    *calls = m->dos_calls;
+    if (reset) {
+        m->dos_ms = 0.0;
+        m->dos_calls = 0;
+    }
+    return TBK_OK;
+}

@@ -265,6 +265,7 @@ struct tbk_model {
     std::vector<double> pos_cache;         // host copy of what ws_posraw holds
     DevBuf ws_posraw;
     DevBuf ws_xl;     // the launch chain of band_xl_*: the second matrix buffer (the sweep of a panel reads one, writes the other)
+    DevBuf ws_dos;    // tbk_dos: the workgroups' fixed-point bins [n_wg][NE], the combined bins and nos (tbk_dos.hip)
     // Set for the duration of one eigenvalue call by tbk_eigenval_device_gather (tbk_comm.hip): the chunk pipeline calls it
     // whenever the eigenvalues of rows [c0, c0 + nkc) of the call have been enqueued, with an event recorded behind
     // them -- the all-gather of finished rows leaves on the communicator's stream while later chunks compute.
@@ -272,6 +273,8 @@ struct tbk_model {
     std::vector<EventPair> events;
     double t_ms[TBK_T_COUNT] = {0, 0, 0, 0};
     int64_t t_n[TBK_T_COUNT] = {0, 0, 0, 0};
+    double dos_ms = 0.0;    // tbk_dos_timing: summed HIP-event time of the density-of-states kernels while `timing` is on
+    int64_t dos_calls = 0;  // ... and the calls it was summed over
 };
 
 // the operand the model was staged with
@@ -517,6 +520,10 @@ private:
     double* d_k2 = nullptr;           // [nk][dim1] the k-points without component f (ws_kfold)
 };
 void tbk_fold_release(tbk_model* m);
+
+// tbk_dos.hip: the share of cells [p_lo, p_lo + p_count) along axis 0 of a mesh in nos (tbk_dos is the whole axis; tbk_dos_multi
+// gives every handle one slab)
+int tbk_dos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_count, double e_min, double e_step, int64_t n_e, double* nos_out);
 
 // tbk_peak.hip
 int tbk_run_mfma_f64_peak(double* tflops);

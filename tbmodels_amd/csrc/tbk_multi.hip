@@ -113,6 +113,37 @@ extern "C" int tbk_eigh_multi(tbk_model* const* handles, int n_handles, const do
     });
 }
 
+// The density of states of a mesh on several devices (tbk_dos.hip): handle i takes a contiguous slab of ceil(n_1 / n) cells along
+// axis 0 and evaluates the planes of that slab plus the one periodic neighbour plane its last cells need.  Every handle returns
+// its share of nos; the host adds the shares in handle order (slabs that hold no cells are skipped).
+extern "C" int tbk_dos_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, double e_min, double e_step, int64_t n_e,
+                             double* nos_out) {
+    TBK_CHECK(check_handles(handles, n_handles));
+    TBK_ARG(mesh != nullptr && nos_out != nullptr, "mesh / nos is NULL");
+    if (n_handles == 1) return tbk_dos(handles[0], mesh, e_min, e_step, n_e, nos_out);
+    TBK_ARG(handles[0]->dim == 2 || handles[0]->dim == 3, "the density of states needs a 2- or 3-dimensional mesh");
+    TBK_ARG(mesh[0] >= 1, "a mesh entry is < 1");
+    TBK_ARG(n_e >= 2 && n_e <= (int64_t(1) << 20), "the energy grid needs 2 to 2^20 points");
+    const int64_t n0 = mesh[0], per = (n0 + n_handles - 1) / n_handles;
+    const int busy = (int)((n0 + per - 1) / per);
+    std::vector<double> share;
+    try {
+        share.assign((size_t)busy * (size_t)n_e, 0.0);
+    } catch (...) {
+        tbk_set_error("cannot allocate the per-handle results");
+        return TBK_ERR_MEMORY;
+    }
+    TBK_CHECK(run_slabs(n_handles, n0, [&](int i, int64_t lo, int64_t count) {
+        return tbk_dos_slab(handles[i], mesh, lo, count, e_min, e_step, n_e, share.data() + (size_t)i * (size_t)n_e);
+    }));
+    for (int64_t j = 0; j < n_e; ++j) {
+        double sum = share[(size_t)j];
+        for (int i = 1; i < busy; ++i) sum += share[(size_t)i * (size_t)n_e + (size_t)j];
+        nos_out[j] = sum;
+    }
+    return TBK_OK;
+}
+
 // k.p models on several devices (kdotp.py:51-100 has the same two methods as Model): the same slabs, through the k.p
 // entry points of every staged copy
 extern "C" int tbk_kdotp_eigenval_multi(tbk_kdotp* const* handles, int n_handles, const double* k, int64_t nk, double* E_out) {
