@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """
-Band structure along a k path, a k.p expansion beside it, and a density of states from a uniform mesh -- the
+Band structure along a k path, a k.p expansion beside it, and a (projected) density of states from a uniform mesh -- the
 pattern of the reference's `examples/kdotp/run.py` (single-k calls in a loop) plus the batched calls this package
 is built for.  Runs on the silicon model of the reference's test-suite (tests/golden/cli_eigenvals); needs a GPU.
 
@@ -59,6 +59,19 @@ def main():
     peak = np.argmax(result.dos)
     print("tetrahedron DOS on the same mesh in %.1f ms: %.6f states below %.3f, peak %.3f states per energy unit at %.3f"
           % (dt * 1e3, result.nos[-1], energies[-1], result.dos[peak], mid[peak]))
+
+    # 4. the orbital character of that spectrum: s and p orbitals (the model's sp3 basis, s first on both atoms).  Eigenvectors
+    # are reduced to four weights per (k, band) where they are produced; 4 x 401 numbers come back
+    if model.size == 8:
+        groups = {"s": [0, 4], "p": [1, 2, 3, 5, 6, 7]}
+        model.pdos((n, n, n), energies[:2], list(groups.values()))  # warm up
+        t0 = time.perf_counter()
+        projected = model.pdos((n, n, n), energies, list(groups.values()))
+        dt = time.perf_counter() - t0
+        print("projected DOS on the same mesh in %.1f ms; s + p against the total: %.1e" % (dt * 1e3, np.abs(projected.nos.sum(axis=0) - result.nos).max()))
+        for name, nos, dos in zip(groups, projected.nos, projected.dos):
+            peak = np.argmax(dos)
+            print("  %s: %.4f states in all, peak %.3f states per energy unit at %.3f" % (name, nos[-1], dos[peak], mid[peak]))
 
 if __name__ == "__main__":
     main()

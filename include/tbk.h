@@ -217,6 +217,49 @@ int tbk_dos_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh,
  * eigenvalue stages are in tbk_get_timing, whose array length is fixed), calls = how many; reset = 1 clears. */
 int tbk_dos_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
+/* ---- orbital-projected density of states of a uniform k mesh (not in the reference) ------------------------------------------
+ * The linear tetrahedron method with matrix elements: state (k, b) carries the weight A_g(k, b) = sum_{i in group g} |U[k][i][b]|^2
+ * (U: the eigenvectors of tbk_eigh, convention 2), and A_g is interpolated linearly inside the simplices of tbk_dos like the band
+ * energy (Bloechl's corner weights; csrc/tbk_pdos.hip).  mesh, the energy grid and the simplices are those of
+ * tbk_dos.
+ *   groups  n_groups in [1, TBK_PDOS_MAX_GROUPS]; group g = group_orbitals[group_offsets[g] .. group_offsets[g + 1]): int32 indices
+ *           in [0, n_orb), at least one per group, none twice inside a group (group_offsets[0] == 0; an orbital may sit in several
+ *           groups or in none)
+ *   nos     double [n_groups][n_e]  nos[g][j] = states per unit cell with energy <= E_j weighted by A_g; over groups that partition
+ *           the orbitals the rows add up to the nos of tbk_dos
+ * Inside a degenerate eigenspace the split of A_g over the bands depends on the basis tbk_eigh returns; its sum over the cluster
+ * does not, and nos moves by no more than the method's own discretisation error.
+ * The kernels accumulate in 64-bit fixed point (2^-40 per contribution, |error| <= 9.1e-13 n_orb) and sum in integers: for given
+ * (E, W) the same call gives the same bits.  Energy grids are tiled by 4096 / GT points per workgroup, GT = n_groups rounded up to
+ * a power of two.
+ * Argument errors (TBK_ERR_ARGUMENT): those of tbk_dos, n_groups outside [1, TBK_PDOS_MAX_GROUPS], an empty group, an index outside
+ * [0, n_orb), a repeat inside a group, a NULL pointer, a k.p handle, more than 2^42 (simplex, band) pairs.  Host buffers;
+ * synchronous. */
+enum { TBK_PDOS_MAX_GROUPS = 16 };
+
+/* The accumulate stage alone on an eigensystem the caller brings: E[NK][n_orb] in mesh order, every row ascending, and the weights
+ * W[NK][n_groups][n_orb] in [0, 1] (what tbk_dos_from_eigenvalues is to tbk_dos: for tests, and for callers with their own
+ * weights -- spin, layer or any other diagonal observable). */
+int tbk_pdos_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, int n_groups, const double* E, const double* W,
+                              double e_min, double e_step, int64_t n_e, double* nos_out);
+/* The whole call: the mesh's k list is made on the host and walked in chunks of at most TBK_OPT_K_CHUNK k-points (0: chosen from
+ * free device memory; chunks need not be whole mesh planes); per chunk tbk_eigh_device fills a chunk-sized eigenvector workspace
+ * and one kernel reduces it to the chunk's rows of W.  E and W of the whole mesh stay in device memory (NK n_orb (1 + n_groups)
+ * doubles; TBK_ERR_MEMORY when they, or the eigenvectors of one chunk, do not fit); all eigenvectors are never held.  Non-finite
+ * eigenvalues and no convergence are reported as by tbk_eigh, in front of the accumulate kernels.  The eigenvector solver is the one
+ * tbk_eigh takes (Jacobi up to 64 orbitals, whose result for a matrix does not depend on the chunk; rocSOLVER above). */
+int tbk_pdos(tbk_model* m, const int32_t* mesh, const int32_t* group_offsets, const int32_t* group_orbitals, int n_groups,
+             double e_min, double e_step, int64_t n_e, double* nos_out);
+/* On several devices from one process: the slabs of tbk_dos_multi (handle i: ceil(n_1 / n_handles) cells along axis 0 plus the
+ * periodic neighbour plane), the host adds the handles' shares in handle order, empty slabs are skipped.  n_handles == 1 is
+ * tbk_pdos. */
+int tbk_pdos_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, const int32_t* group_offsets,
+                   const int32_t* group_orbitals, int n_groups, double e_min, double e_step, int64_t n_e, double* nos_out);
+/* While TBK_OPT_TIMING is on: ms[3] = summed HIP-event time of this handle's tbk_pdos calls in the weights kernel (all chunks), the
+ * accumulate kernel, and the reduction + prefix sum; calls = how many; reset = 1 clears.  (The eigenvector stages are in
+ * tbk_get_timing.) */
+int tbk_pdos_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
 /* ---- k.p models (kdotp.py:51-100): H(k) = sum_p prod_d k_d^powers[p][d] * coeffs[p] ------- */
 int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, const int32_t* powers,
                      const double* coeffs, tbk_kdotp** out);

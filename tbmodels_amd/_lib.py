@@ -31,6 +31,7 @@ TBK_CNT_EIGENVAL_CALLS, TBK_CNT_FOLDED_CALLS, TBK_CNT_FOLDED_KPOINTS, TBK_CNT_LI
 TBK_CNT_STRASSEN2_LAUNCHES = 5
 TBK_T_PHASE, TBK_T_HK, TBK_T_EIG, TBK_T_QL, TBK_T_COUNT = 0, 1, 2, 3, 4
 STAGE_NAMES = ("phase", "hk", "eig", "ql")
+TBK_PDOS_MAX_GROUPS = 16
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -70,6 +71,10 @@ SIGNATURES = {
     "tbk_dos": (_c_int, [_vp, _vp, ctypes.c_double, ctypes.c_double, _c_i64, _vp]),
     "tbk_dos_multi": (_c_int, [_vp, _c_int, _vp, ctypes.c_double, ctypes.c_double, _c_i64, _vp]),
     "tbk_dos_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
+    "tbk_pdos_from_eigensystem": (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp, ctypes.c_double, ctypes.c_double, _c_i64, _vp]),
+    "tbk_pdos": (_c_int, [_vp, _vp, _vp, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp]),
+    "tbk_pdos_multi": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp]),
+    "tbk_pdos_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
     "tbk_kdotp_create": (_c_int, [_c_int, _c_int, _c_int, _c_i64, _vp, _vp, _pp]),
     "tbk_kdotp_destroy": (None, [_vp]),
     "tbk_kdotp_hamilton": (_c_int, [_vp, _vp, _c_i64, _vp]),

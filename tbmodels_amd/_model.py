@@ -33,10 +33,11 @@ try:  # fast content hash for the staging fingerprint; zlib is the fallback
 except ImportError:  # pragma: no cover
     _xxhash = None
 
-__all__ = ("Model", "DensityOfStates")
+__all__ = ("Model", "DensityOfStates", "ProjectedDensityOfStates")
 
 #: what ``Model.dos`` returns: the energy grid (NE,), the number of states at its points (NE,), their difference quotient (NE - 1,)
 DensityOfStates = co.namedtuple("DensityOfStates", ("energies", "nos", "dos"))
+ProjectedDensityOfStates = co.namedtuple("ProjectedDensityOfStates", ("energies", "nos", "dos"))
 
 
 def _devices_from_env():
@@ -777,24 +778,8 @@ class Model:
             )
         return (eig[0], vec[0]) if single else (eig, vec)
 
-    def dos(self, mesh, energies):
-        """
-        Number of states and density of states from a uniform k mesh by the linear tetrahedron method, computed on the GPU
-        from eigenvalues that never leave it.  Not in the reference (``_tb_model.py`` has no density of states).
-
-        ``mesh`` is a sequence of ``dim`` positive integers ``(n_1, ..., n_dim)``: the Gamma-centred, periodic mesh
-        ``k = (i_1 / n_1, ..., i_dim / n_dim)``.  ``energies`` is a 1-D ascending, uniformly spaced grid of at least two points
-        (``max|diff - mean diff| <= 1e-9 mean diff``).  Returns the named tuple ``(energies, nos, dos)``: ``nos[j]`` (shape
-        ``(NE,)``) is the number of states per unit cell with energy ``<= energies[j]``, ``dos = np.diff(nos) / step`` (shape
-        ``(NE - 1,)``) belongs to the bin midpoints.  ``nos`` is bounded and exact in its state count for flat bands
-        (``nos[-1] == size`` when the grid ends above the spectrum); the pointwise g(E) is not computed.
-
-        Decomposition: band ``b`` (the b-th ascending eigenvalue at every mesh point) is interpolated linearly inside simplices.
-        In three dimensions every mesh cell is cut into the 6 tetrahedra that share its main diagonal -- corners
-        ``0, e_a, e_a + e_b, e_a + e_b + e_c`` for every order ``(a, b, c)`` of the axes, weight ``1 / (6 NK)`` each; in two
-        dimensions into the 2 triangles ``0, e_a, e_a + e_b``, weight ``1 / (2 NK)``.  One-dimensional models raise
-        ``ValueError``.  With several ``devices`` every device takes a slab of the mesh along its first axis.
-        """
+    def _dos_arguments(self, mesh, energies):
+        """The checks ``dos`` and ``pdos`` share: ``(mesh int32 (dim,), grid float64 (NE,), mean step)`` or ``ValueError``."""
         if self.dim not in (2, 3):
             raise ValueError("dos needs a 2- or 3-dimensional model, this one has dimension {}".format(self.dim))
         try:
@@ -823,6 +808,27 @@ class Model:
             raise ValueError("energies must be ascending")
         if np.abs(steps - step).max() > 1e-9 * step:
             raise ValueError("energies must be uniformly spaced")
+        return mesh_array, grid, step
+
+    def dos(self, mesh, energies):
+        """
+        Number of states and density of states from a uniform k mesh by the linear tetrahedron method, computed on the GPU
+        from eigenvalues that never leave it.  Not in the reference (``_tb_model.py`` has no density of states).
+
+        ``mesh`` is a sequence of ``dim`` positive integers ``(n_1, ..., n_dim)``: the Gamma-centred, periodic mesh
+        ``k = (i_1 / n_1, ..., i_dim / n_dim)``.  ``energies`` is a 1-D ascending, uniformly spaced grid of at least two points
+        (``max|diff - mean diff| <= 1e-9 mean diff``).  Returns the named tuple ``(energies, nos, dos)``: ``nos[j]`` (shape
+        ``(NE,)``) is the number of states per unit cell with energy ``<= energies[j]``, ``dos = np.diff(nos) / step`` (shape
+        ``(NE - 1,)``) belongs to the bin midpoints.  ``nos`` is bounded and exact in its state count for flat bands
+        (``nos[-1] == size`` when the grid ends above the spectrum); the pointwise g(E) is not computed.
+
+        Decomposition: band ``b`` (the b-th ascending eigenvalue at every mesh point) is interpolated linearly inside simplices.
+        In three dimensions every mesh cell is cut into the 6 tetrahedra that share its main diagonal -- corners
+        ``0, e_a, e_a + e_b, e_a + e_b + e_c`` for every order ``(a, b, c)`` of the axes, weight ``1 / (6 NK)`` each; in two
+        dimensions into the 2 triangles ``0, e_a, e_a + e_b``, weight ``1 / (2 NK)``.  One-dimensional models raise
+        ``ValueError``.  With several ``devices`` every device takes a slab of the mesh along its first axis.
+        """
+        mesh_array, grid, step = self._dos_arguments(mesh, energies)
         nos = np.empty(grid.shape[0], dtype=np.float64)
         with self._call_lock:
             # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigenval
@@ -832,6 +838,61 @@ class Model:
                                          _lib.ptr(nos))
             )
         return DensityOfStates(grid, nos, np.diff(nos) / step)
+
+    def pdos(self, mesh, energies, projections):
+        """
+        Orbital-projected number of states and density of states from a uniform k mesh by the linear tetrahedron method, computed
+        on the GPU from eigenvalues and eigenvectors that never leave it.  Not in the reference (``_tb_model.py`` has neither a
+        density of states nor eigenvectors).
+
+        ``mesh`` and ``energies`` are those of :meth:`dos`, with the same checks.  ``projections`` is a non-empty sequence of G
+        groups (at most ``TBK_PDOS_MAX_GROUPS`` = 16), each a non-empty sequence of orbital indices in ``[0, size)`` without repeats
+        inside the group; an orbital may appear in several groups or in none.  Returns the named tuple ``(energies, nos, dos)``:
+        ``nos[g, j]`` (shape ``(G, NE)``) is the number of states per unit cell with energy ``<= energies[j]``, every state
+        ``(k, b)`` weighted by ``A_g(k, b) = sum_{i in g} |U[k][i][b]|^2`` with ``U`` the eigenvectors of ``eigh(k, convention=2)``;
+        ``dos = np.diff(nos, axis=1) / step`` (shape ``(G, NE - 1)``) belongs to the bin midpoints.  Over groups that partition
+        the orbitals ``nos.sum(axis=0)`` is the ``nos`` of :meth:`dos`.
+
+        Inside a degenerate eigenspace the split of ``A_g`` over the bands depends on the basis, which is unspecified (see
+        :meth:`eigh`); the sum of ``A_g`` over the degenerate cluster does not.  The effect on ``nos`` is of the order of the
+        method's own discretisation error.
+
+        Decomposition: the simplices of :meth:`dos` -- in three dimensions the 6 tetrahedra that share the main diagonal of every
+        mesh cell (corners ``0, e_a, e_a + e_b, e_a + e_b + e_c`` for every order of the axes), in two dimensions the 2 triangles
+        ``0, e_a, e_a + e_b`` -- inside which both the band energy and ``A_g`` are interpolated linearly between the corners
+        (Bloechl's corner weights).  One-dimensional models raise ``ValueError``.  With several ``devices`` every device takes a
+        slab of the mesh along its first axis.
+        """
+        mesh_array, grid, step = self._dos_arguments(mesh, energies)
+        try:
+            groups = [list(group) for group in projections]
+        except TypeError:
+            raise ValueError("projections must be a sequence of sequences of orbital indices") from None
+        if not groups:
+            raise ValueError("projections must hold at least one group")
+        if len(groups) > _lib.TBK_PDOS_MAX_GROUPS:
+            raise ValueError("projections has {} groups, at most {} are supported".format(len(groups), _lib.TBK_PDOS_MAX_GROUPS))
+        for group in groups:
+            if not group:
+                raise ValueError("a projection group is empty")
+            for index in group:
+                if isinstance(index, (bool, np.bool_)) or not isinstance(index, (int, np.integer)):
+                    raise ValueError("orbital indices must be integers, got {!r}".format(index))
+                if not 0 <= index < self.size:
+                    raise ValueError("orbital index {!r} is outside [0, {})".format(index, self.size))
+            if len(set(int(index) for index in group)) != len(group):
+                raise ValueError("an orbital repeats inside the projection group {!r}".format(group))
+        offsets = np.ascontiguousarray(np.cumsum([0] + [len(group) for group in groups]), dtype=np.int32)
+        orbitals = np.ascontiguousarray(np.concatenate(groups), dtype=np.int32)
+        nos = np.empty((len(groups), grid.shape[0]), dtype=np.float64)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_pdos_multi(handles, n_handles, _lib.ptr(mesh_array), _lib.ptr(offsets), _lib.ptr(orbitals), len(groups),
+                                          float(grid[0]), step, grid.shape[0], _lib.ptr(nos))
+            )
+        return ProjectedDensityOfStates(grid, nos, np.diff(nos, axis=1) / step)
 
     def construct_kdotp(self, k, order):
         """

@@ -22,47 +22,18 @@
 #include <cmath>
 #include <vector>
 
-#include "tbk_internal.h"
+#include "tbk_dos_common.h"
 
 namespace {
 
 constexpr int DOS_THREADS = 256;
 constexpr int DOS_TILE = 4096;  // energy bins per LDS tile: 4096 * (8 + 4) bytes = 48 KiB; longer grids take gridDim.y tiles
-// Fixed point: a contribution n_T in [0, 1] is stored as round(n_T * 2^40), i.e. with an error of at most 2^-41 each.  A bin of
-// nos sums at most S NK n_orb of them and is divided by S NK: |error| <= n_orb * 2^-41 = 4.5e-13 n_orb in the worst case
-// (every contribution off by half a unit in the same direction), a twentieth of the 1e-11 n_orb the kernel is tested to.
+// Fixed point (tbk_dos_common.h): a contribution n_T in [0, 1] is stored as round(n_T * 2^40), i.e. with an error of at most 2^-41
+// each.  A bin of nos sums at most S NK n_orb of them and is divided by S NK: |error| <= n_orb * 2^-41 = 4.5e-13 n_orb in the worst
+// case (every contribution off by half a unit in the same direction), a twentieth of the 1e-11 n_orb the kernel is tested to.
 // Overflow: a workgroup takes at most DOS_MAX_ITEMS (cell, band) pairs, so one of its bins receives at most
 // 6 * 2^20 contributions of at most 2^40: 6 * 2^60 < 2^64.
-constexpr int DOS_FRAC_BITS = 40;
-constexpr int64_t DOS_MAX_ITEMS = int64_t(1) << 20;
-// the second kernel splits every workgroup's 64-bit bin into its high 44 and low 20 bits and sums each in 64 bits: exact up to
-// 2^20 workgroups (the launcher never takes more than that)
-constexpr int DOS_SPLIT_BITS = 20;
-constexpr int64_t DOS_MAX_NE = int64_t(1) << 20;  // documented limit of the energy grid (tbk.h)
-
-struct DosGeom {
-    int n0_cells;   // cells along axis 0 this launch covers
-    int n0_planes;  // planes of axis 0 in E: n0_cells + 1 for a slab (its periodic neighbour plane is the last), n0_cells for a whole mesh
-    int n1, n2;     // the other axes (n2 = 1 in two dimensions)
-    int n_orb;
-    int64_t items;         // n0_cells * n1 * n2 * n_orb
-    int64_t items_per_wg;  // contiguous items per workgroup, <= DOS_MAX_ITEMS
-};
-
-__device__ __forceinline__ double dos_grid(double e_min, double e_step, int j) {
-    // two roundings, never an FMA: the same number as NumPy's e_min + j * e_step
-    return __dadd_rn(e_min, __dmul_rn((double)j, e_step));
-}
-
-// first j in [0, n_e] with E_j >= e (n_e: none).  The multiply gives a guess, the comparisons decide.  NaN -> 0, no iteration.
-__device__ __forceinline__ int dos_first_at_or_above(double e, double e_min, double e_step, double inv_step, int n_e) {
-    double t = ceil((e - e_min) * inv_step);
-    t = fmin(fmax(t, 0.0), (double)n_e);
-    int j = (int)t;
-    while (j > 0 && dos_grid(e_min, e_step, j - 1) >= e) --j;
-    while (j < n_e && dos_grid(e_min, e_step, j) < e) ++j;
-    return j;
-}
+// The grid, the search on it, DosGeom and DosWindow are shared with tbk_pdos.hip: tbk_dos_common.h.
 
 __device__ __forceinline__ void dos_sort2(double& a, double& b) {
     const double lo = fmin(a, b), hi = fmax(a, b);
@@ -70,15 +41,8 @@ __device__ __forceinline__ void dos_sort2(double& a, double& b) {
     b = hi;
 }
 
-struct DosWindow {
-    double e_min, e_step, inv_step;
-    int n_e;
-    int tile_lo, tile_n;  // this workgroup's bins
-};
-
 __device__ __forceinline__ void dos_add(unsigned long long* part, int bin, double frac) {
-    frac = fmin(fmax(frac, 0.0), 1.0);
-    atomicAdd(&part[bin], (unsigned long long)__double2ll_rn(frac * (double)(1ull << DOS_FRAC_BITS)));
+    atomicAdd(&part[bin], dos_fixed(frac));
 }
 
 // one tetrahedron: DESIGN 10.1 (the ranges are half-open as written there; the comparisons select the branch, so a branch with
@@ -242,8 +206,6 @@ struct DosLaunch {
     size_t off_step = 0, off_frac = 0, off_count = 0, ws_bytes = 0;
 };
 
-size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 // dim in {2, 3}; cells0 cells along axis 0 out of planes0 planes held in E (planes0 == cells0: the axis wraps onto itself)
 int dos_plan(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb, int64_t n_e, DosLaunch* out) {
     DosLaunch L;
@@ -263,10 +225,10 @@ int dos_plan(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int 
     L.g.items_per_wg = (L.g.items + n_wg - 1) / n_wg;
     L.n_wg = (int)((L.g.items + L.g.items_per_wg - 1) / L.g.items_per_wg);
     const size_t bins = (size_t)L.n_wg * (size_t)n_e;
-    L.off_step = align256(bins * sizeof(unsigned long long));
-    L.off_frac = L.off_step + align256(bins * sizeof(unsigned));
-    L.off_count = L.off_frac + align256((size_t)n_e * sizeof(double));
-    L.ws_bytes = L.off_count + align256((size_t)n_e * sizeof(long long));
+    L.off_step = dos_align256(bins * sizeof(unsigned long long));
+    L.off_frac = L.off_step + dos_align256(bins * sizeof(unsigned));
+    L.off_count = L.off_frac + dos_align256((size_t)n_e * sizeof(double));
+    L.ws_bytes = L.off_count + dos_align256((size_t)n_e * sizeof(long long));
     *out = L;
     return TBK_OK;
 }
@@ -294,8 +256,10 @@ int dos_launch(hipStream_t s, int dim, const DosLaunch& L, const double* d_E, do
     return TBK_OK;
 }
 
+}  // namespace
+
 // the checks every entry point shares; *nk_total = points of the whole mesh
-int dos_check(int dim, const int32_t* mesh, double e_step, int64_t n_e, const double* nos_out, int64_t* nk_total) {
+int tbk_dos_check(int dim, const int32_t* mesh, double e_step, int64_t n_e, const void* nos_out, int64_t* nk_total) {
     TBK_ARG(dim == 2 || dim == 3, "the density of states needs a 2- or 3-dimensional mesh");
     TBK_ARG(mesh != nullptr && nos_out != nullptr, "mesh / nos is NULL");
     int64_t nk = 1;
@@ -311,12 +275,35 @@ int dos_check(int dim, const int32_t* mesh, double e_step, int64_t n_e, const do
     return TBK_OK;
 }
 
-}  // namespace
+// the k list of `planes` planes of axis 0 from plane p_lo on, in mesh order (the order tbk_fold.hip recognises): k_d = i_d / n_d
+int tbk_dos_mesh_klist(int dim, const int32_t* mesh, int64_t p_lo, int64_t planes, std::vector<double>* h_k) {
+    const int64_t n0 = mesh[0];
+    const int n1 = mesh[1], n2 = dim == 3 ? mesh[2] : 1;
+    try {
+        h_k->resize((size_t)(planes * n1 * n2) * dim);
+    } catch (...) {
+        tbk_set_error("cannot allocate the k list of the mesh");
+        return TBK_ERR_MEMORY;
+    }
+    size_t q = 0;
+    for (int64_t p = 0; p < planes; ++p) {
+        const double k0 = (double)((p_lo + p) % n0) / (double)n0;
+        for (int i1 = 0; i1 < n1; ++i1) {
+            const double k1 = (double)i1 / (double)n1;
+            for (int i2 = 0; i2 < n2; ++i2) {
+                (*h_k)[q++] = k0;
+                (*h_k)[q++] = k1;
+                if (dim == 3) (*h_k)[q++] = (double)i2 / (double)n2;
+            }
+        }
+    }
+    return TBK_OK;
+}
 
 extern "C" int tbk_dos_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double e_min, double e_step,
                                         int64_t n_e, double* nos_out) {
     int64_t nk = 0;
-    TBK_CHECK(dos_check(dim, mesh, e_step, n_e, nos_out, &nk));
+    TBK_CHECK(tbk_dos_check(dim, mesh, e_step, n_e, nos_out, &nk));
     TBK_ARG(E != nullptr, "E is NULL");
     TBK_ARG(n_orb >= 1, "n_orb < 1");
     TBK_ARG(std::isfinite(e_min), "e_min is not finite");
@@ -355,7 +342,7 @@ int tbk_dos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_coun
     TBK_LOCK(m);
     TBK_ARG(!m->kdotp, "a k.p model has no Brillouin zone");
     int64_t nk_total = 0;
-    TBK_CHECK(dos_check(m->dim, mesh, e_step, n_e, nos_out, &nk_total));
+    TBK_CHECK(tbk_dos_check(m->dim, mesh, e_step, n_e, nos_out, &nk_total));
     TBK_ARG(std::isfinite(e_min), "e_min is not finite");
     const int dim = m->dim, n_orb = m->n_orb;
     const int64_t n0 = mesh[0];
@@ -366,33 +353,12 @@ int tbk_dos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_coun
     DosLaunch L;
     TBK_CHECK(dos_plan(dim, mesh, p_count, planes, n_orb, n_e, &L));
 
-    // the k list of the slab, in mesh order (the order tbk_fold.hip recognises): k_d = i_d / n_d
     std::vector<double> h_k;
-    try {
-        h_k.resize((size_t)nk * dim);
-    } catch (...) {
-        tbk_set_error("cannot allocate the k list of the mesh");
-        return TBK_ERR_MEMORY;
-    }
-    {
-        const int n1 = mesh[1], n2 = dim == 3 ? mesh[2] : 1;
-        size_t q = 0;
-        for (int64_t p = 0; p < planes; ++p) {
-            const double k0 = (double)((p_lo + p) % n0) / (double)n0;
-            for (int i1 = 0; i1 < n1; ++i1) {
-                const double k1 = (double)i1 / (double)n1;
-                for (int i2 = 0; i2 < n2; ++i2) {
-                    h_k[q++] = k0;
-                    h_k[q++] = k1;
-                    if (dim == 3) h_k[q++] = (double)i2 / (double)n2;
-                }
-            }
-        }
-    }
+    TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, p_lo, planes, &h_k));
     const size_t k_bytes = h_k.size() * sizeof(double);
     TBK_CHECK(m->ws_k.reserve(k_bytes));
     TBK_CHECK(m->ws_out.reserve((size_t)nk * n_orb * sizeof(double)));
-    TBK_CHECK(m->ws_dos.reserve(L.ws_bytes + align256((size_t)n_e * sizeof(double))));
+    TBK_CHECK(m->ws_dos.reserve(L.ws_bytes + dos_align256((size_t)n_e * sizeof(double))));
     TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, h_k.data(), k_bytes, hipMemcpyHostToDevice, m->stream));
     // the existing pipeline with the host list as the fold hint: dense models fold, CSR models take their own path
     TBK_CHECK(tbk_eigenval_device_hint(m, m->ws_k.as<double>(), h_k.data(), nk, m->ws_out.as<double>()));

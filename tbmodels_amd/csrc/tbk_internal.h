@@ -265,7 +265,10 @@ struct tbk_model {
     std::vector<double> pos_cache;         // host copy of what ws_posraw holds
     DevBuf ws_posraw;
     DevBuf ws_xl;     // the launch chain of band_xl_*: the second matrix buffer (the sweep of a panel reads one, writes the other)
-    DevBuf ws_dos;    // tbk_dos: the workgroups' fixed-point bins [n_wg][NE], the combined bins and nos (tbk_dos.hip)
+    DevBuf ws_dos;    // tbk_dos / tbk_pdos: the workgroups' fixed-point bins [n_wg][NE], the combined bins and nos (tbk_dos.hip, tbk_pdos.hip)
+    DevBuf ws_pdos_u;    // tbk_pdos: the eigenvectors of one k chunk [chunk][n_orb][n_orb] complex
+    DevBuf ws_pdos_w;    // ... the weights of the whole slab W[NK][G][n_orb]
+    DevBuf ws_pdos_grp;  // ... the groups: offsets [G + 1] and, 256-byte aligned behind them, the orbital list
     // Set for the duration of one eigenvalue call by tbk_eigenval_device_gather (tbk_comm.hip): the chunk pipeline calls it
     // whenever the eigenvalues of rows [c0, c0 + nkc) of the call have been enqueued, with an event recorded behind
     // them -- the all-gather of finished rows leaves on the communicator's stream while later chunks compute.
@@ -275,6 +278,8 @@ struct tbk_model {
     int64_t t_n[TBK_T_COUNT] = {0, 0, 0, 0};
     double dos_ms = 0.0;    // tbk_dos_timing: summed HIP-event time of the density-of-states kernels while `timing` is on
     int64_t dos_calls = 0;  // ... and the calls it was summed over
+    double pdos_ms[3] = {0.0, 0.0, 0.0};  // tbk_pdos_timing: the same for the weights kernel, the accumulate kernel, reduction + scan
+    int64_t pdos_calls = 0;
 };
 
 // the operand the model was staged with
@@ -524,6 +529,11 @@ void tbk_fold_release(tbk_model* m);
 // tbk_dos.hip: the share of cells [p_lo, p_lo + p_count) along axis 0 of a mesh in nos (tbk_dos is the whole axis; tbk_dos_multi
 // gives every handle one slab)
 int tbk_dos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_count, double e_min, double e_step, int64_t n_e, double* nos_out);
+
+// tbk_pdos.hip: the same for the projected number of states (nos_out[n_groups][n_e]), and the check of the groups
+int tbk_pdos_check_groups(int n_orb, const int32_t* group_offsets, const int32_t* group_orbitals, int n_groups);
+int tbk_pdos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_count, const int32_t* group_offsets, const int32_t* group_orbitals,
+                  int n_groups, double e_min, double e_step, int64_t n_e, double* nos_out);
 
 // tbk_peak.hip
 int tbk_run_mfma_f64_peak(double* tflops);

@@ -144,6 +144,39 @@ extern "C" int tbk_dos_multi(tbk_model* const* handles, int n_handles, const int
     return TBK_OK;
 }
 
+// The projected number of states on several devices (tbk_pdos.hip): the slabs of tbk_dos_multi, every handle returning its share of
+// nos[n_groups][n_e]; the host adds the shares in handle order.
+extern "C" int tbk_pdos_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, const int32_t* group_offsets,
+                              const int32_t* group_orbitals, int n_groups, double e_min, double e_step, int64_t n_e, double* nos_out) {
+    TBK_CHECK(check_handles(handles, n_handles));
+    TBK_ARG(mesh != nullptr && nos_out != nullptr, "mesh / nos is NULL");
+    if (n_handles == 1) return tbk_pdos(handles[0], mesh, group_offsets, group_orbitals, n_groups, e_min, e_step, n_e, nos_out);
+    TBK_ARG(handles[0]->dim == 2 || handles[0]->dim == 3, "the density of states needs a 2- or 3-dimensional mesh");
+    TBK_ARG(mesh[0] >= 1, "a mesh entry is < 1");
+    TBK_ARG(n_e >= 2 && n_e <= (int64_t(1) << 20), "the energy grid needs 2 to 2^20 points");
+    TBK_CHECK(tbk_pdos_check_groups(handles[0]->n_orb, group_offsets, group_orbitals, n_groups));
+    const int64_t n0 = mesh[0], per = (n0 + n_handles - 1) / n_handles;
+    const int busy = (int)((n0 + per - 1) / per);
+    const size_t n_out = (size_t)n_groups * (size_t)n_e;
+    std::vector<double> share;
+    try {
+        share.assign((size_t)busy * n_out, 0.0);
+    } catch (...) {
+        tbk_set_error("cannot allocate the per-handle results");
+        return TBK_ERR_MEMORY;
+    }
+    TBK_CHECK(run_slabs(n_handles, n0, [&](int i, int64_t lo, int64_t count) {
+        return tbk_pdos_slab(handles[i], mesh, lo, count, group_offsets, group_orbitals, n_groups, e_min, e_step, n_e,
+                             share.data() + (size_t)i * n_out);
+    }));
+    for (size_t j = 0; j < n_out; ++j) {
+        double sum = share[j];
+        for (int i = 1; i < busy; ++i) sum += share[(size_t)i * n_out + j];
+        nos_out[j] = sum;
+    }
+    return TBK_OK;
+}
+
 // k.p models on several devices (kdotp.py:51-100 has the same two methods as Model): the same slabs, through the k.p
 // entry points of every staged copy
 extern "C" int tbk_kdotp_eigenval_multi(tbk_kdotp* const* handles, int n_handles, const double* k, int64_t nk, double* E_out) {

@@ -1,0 +1,585 @@
+// tbk_pdos.hip -- the orbital-projected number of states nos_g(E) of a uniform, periodic k mesh by the linear tetrahedron method
+// with matrix elements (Bloechl's corner weights; triangles in dim = 2).  Not in the reference; DESIGN.md section 11 has the
+// formulas, the layout and the measurements, tools/pdos_model.py is the NumPy statement the tests compare with.
+//
+//   U[nk][n][n][2]    eigenvectors of one k chunk, U[k][i][b] = component i of band b (tbk_eigh_device, convention 2)
+//   W[NK][G][n_orb]   A_g(k, b) = sum_{i in g} |U[k][i][b]|^2 in [0, 1]             (pdos_weights_kernel, per chunk)
+//   E[NK][n_orb]      ascending eigenvalues per mesh point, mesh order (last axis fastest)
+//   nos[g][j]         = 1 / (S NK) * sum over (cell, band, simplex) of sum_c w_c(E_j) A_g at corner c   (pdos_accumulate_kernel)
+//
+// The accumulate kernel has the structure of dos_accumulate_kernel (tbk_dos.hip): a work item is one (cell, band) pair, band
+// fastest; per simplex the corners are sorted by energy -- adjacent exchanges on a strict comparison, so ties keep corner order,
+// and every corner's G weights travel with its energy -- the bins j_lo <= j < j_hi receive sum_c w_c(E_j) A_g,c, the corner
+// weights of a (simplex, bin) being computed ONCE and applied to all groups, and the constant every bin from j_hi upwards would
+// receive -- the mean of A over the corners, no longer the integer 1 -- is rounded once to fixed point and added at j_hi into a
+// per-group step accumulator whose prefix sum comes last.
+//
+// Reproducibility: as in tbk_dos.hip there are no floating-point atomics.  Contributions in [0, 1] are accumulated in 64-bit
+// fixed point (2^-40), every workgroup stores its bins into its own row of a [n_workgroups][G][NE] buffer, the rows are summed
+// and the steps prefix-summed in integers: for given E and W the bits of nos depend neither on wave order nor workgroup count.
+// Error: a bin of nos_g sums at most S NK n_orb rounded contributions AND at most S NK n_orb rounded steps, each off by at most
+// 2^-41, and is divided by S NK: |error| <= 2 n_orb 2^-41 = 9.1e-13 n_orb.
+//
+// Overflow.  A workgroup takes at most DOS_MAX_ITEMS = 2^20 items, so one of its bins (fraction or step) receives at most
+// 6 * 2^20 values of at most 2^40: 6 * 2^60 < 2^64.  The reduction splits every workgroup's bin into its high 44 (< 6 * 2^40) and
+// low 20 bits and sums each over at most 2^20 workgroups: < 2^63 and < 2^40.  The prefix sum of the steps would overflow 64 bits
+// (up to S NK n_orb terms of 2^40), so it runs on the two halves apart: the high halves of ALL steps sum to at most
+// S NK n_orb * 2^20 and the low halves to at most 2^20 bins * 2^40; the launcher refuses S NK n_orb > 2^42 (far beyond what fits
+// device memory: NK n_orb (1 + G) doubles), so both stay below 2^63.
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "tbk_dos_common.h"
+
+namespace {
+
+constexpr int PDOS_THREADS = 256;
+// (group, energy) bins of a workgroup's LDS: a 64-bit fraction and a 64-bit step each = 64 KiB.  The energy tile is
+// PDOS_LDS_BINS / GT points for GT = n_groups rounded up to a power of two (the kernel's instantiation): 4096, 2048, ... 256
+constexpr int PDOS_LDS_BINS = 4096;
+constexpr int64_t PDOS_MAX_TERMS = int64_t(1) << 42;  // S NK n_orb (the overflow bound above)
+
+int pdos_group_tile(int n_groups) {
+    int gt = 1;
+    while (gt < n_groups) gt *= 2;
+    return gt;
+}
+
+// ---- eigenvectors -> weights -------------------------------------------------------------------------------------------------
+// One thread per (k, band), band fastest: a wave reads 64 consecutive complex numbers of a row of U[k] per orbital.  The groups
+// are walked in order, the orbitals of a group in list order; one launch serves all groups, so an element of U comes from HBM
+// once (an orbital that sits in several groups is re-read from L2 by the workgroup that just fetched it).
+__global__ void __launch_bounds__(PDOS_THREADS) pdos_weights_kernel(const double2* __restrict__ U, int n, int64_t nk, int n_groups,
+                                                                    const int32_t* __restrict__ offsets, const int32_t* __restrict__ orbitals,
+                                                                    double* __restrict__ W) {
+    const int64_t t = (int64_t)blockIdx.x * PDOS_THREADS + threadIdx.x;
+    if (t >= nk * n) return;
+    const int64_t k = t / n;
+    const int b = (int)(t - k * n);
+    const double2* Uk = U + (size_t)k * n * n + b;
+    double* Wk = W + (size_t)k * n_groups * n + b;
+    for (int g = 0; g < n_groups; ++g) {
+        double acc = 0.0;
+        for (int e = offsets[g]; e < offsets[g + 1]; ++e) {
+            const double2 u = Uk[(size_t)orbitals[e] * n];
+            acc += u.x * u.x + u.y * u.y;
+        }
+        Wk[(size_t)g * n] = acc;
+    }
+}
+
+// ---- accumulate --------------------------------------------------------------------------------------------------------------
+template <int GT, int NC, int A, int B>
+__device__ __forceinline__ void pdos_exchange(double (&e)[NC], double (&a)[GT][NC]) {
+    const bool sw = e[B] < e[A];  // strict: equal energies keep their order
+    const double lo = sw ? e[B] : e[A], hi = sw ? e[A] : e[B];
+    e[A] = lo;
+    e[B] = hi;
+#pragma unroll
+    for (int g = 0; g < GT; ++g) {
+        const double x = sw ? a[g][B] : a[g][A], y = sw ? a[g][A] : a[g][B];
+        a[g][A] = x;
+        a[g][B] = y;
+    }
+}
+
+// One simplex of NC corners (4: tetrahedron, 3: triangle) whose mesh points are kc[]: DESIGN 11.1.  part / step: [n_groups][tile_n].
+// The ranges are half-open and the comparisons select the branch, so a reciprocal of a zero difference (inf) is never used.
+template <int GT, int NC>
+__device__ __forceinline__ void pdos_simplex(const double (&e_in)[NC], const int64_t (&kc)[NC], int band, const double* __restrict__ W,
+                                             int n_groups, int n_orb, const DosWindow& w, unsigned long long* part, unsigned long long* step) {
+    double e[NC], a[GT][NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) e[c] = e_in[c];
+#pragma unroll
+    for (int g = 0; g < GT; ++g)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) a[g][c] = g < n_groups ? W[((size_t)kc[c] * n_groups + g) * n_orb + band] : 0.0;
+    // a stable sorting network: adjacent exchanges only
+    pdos_exchange<GT, NC, 0, 1>(e, a);
+    pdos_exchange<GT, NC, 1, 2>(e, a);
+    if (NC == 4) pdos_exchange<GT, NC, NC - 2, NC - 1>(e, a);
+    pdos_exchange<GT, NC, 0, 1>(e, a);
+    if (NC == 4) {
+        pdos_exchange<GT, NC, 1, 2>(e, a);
+        pdos_exchange<GT, NC, 0, 1>(e, a);
+    }
+    const int j_lo = dos_first_at_or_above(e[0], w.e_min, w.e_step, w.inv_step, w.n_e);
+    const int j_hi = dos_first_at_or_above(e[NC - 1], w.e_min, w.e_step, w.inv_step, w.n_e);
+    if (j_hi >= w.tile_lo && j_hi < w.tile_lo + w.tile_n) {
+#pragma unroll
+        for (int g = 0; g < GT; ++g)
+            if (g < n_groups) {
+                // the mean over the corners, rounded once (exactly 1 for unit weights)
+                const double mean = NC == 4 ? 0.25 * (((a[g][0] + a[g][1]) + a[g][2]) + a[g][NC - 1]) : ((a[g][0] + a[g][1]) + a[g][2]) / 3.0;
+                atomicAdd(&step[g * w.tile_n + (j_hi - w.tile_lo)], dos_fixed(mean));
+            }
+    }
+    const int lo = max(j_lo, w.tile_lo), hi = min(j_hi, w.tile_lo + w.tile_n);
+    if (lo >= hi) return;
+    if (NC == 4) {
+        const double e1 = e[0], e2 = e[1], e3 = e[2], e4 = e[NC - 1];
+        const double r21 = 1.0 / (e2 - e1), r31 = 1.0 / (e3 - e1), r41 = 1.0 / (e4 - e1), r32 = 1.0 / (e3 - e2), r42 = 1.0 / (e4 - e2),
+                     r43 = 1.0 / (e4 - e3);
+        for (int j = lo; j < hi; ++j) {
+            const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e4 here
+            double w1, w2, w3, w4;
+            if (E < e2) {
+                const double x = E - e1;
+                const double C = 0.25 * (x * x * x) * (r21 * r31 * r41);
+                w1 = C * (4.0 - x * (r21 + r31 + r41));
+                w2 = C * x * r21;
+                w3 = C * x * r31;
+                w4 = C * x * r41;
+            } else if (E < e3) {
+                const double x1 = E - e1, x2 = E - e2, y3 = e3 - E, y4 = e4 - E;
+                const double C1 = 0.25 * (x1 * x1) * (r41 * r31);
+                const double C2 = 0.25 * (x1 * x2 * y3) * (r41 * r32 * r31);
+                const double C3 = 0.25 * (x2 * x2 * y4) * (r42 * r32 * r41);
+                const double C12 = C1 + C2, C23 = C2 + C3, C123 = C12 + C3;
+                w1 = C1 + C12 * y3 * r31 + C123 * y4 * r41;
+                w2 = C123 + C23 * y3 * r32 + C3 * y4 * r42;
+                w3 = C12 * x1 * r31 + C23 * x2 * r32;
+                w4 = C123 * x1 * r41 + C3 * x2 * r42;
+            } else {
+                const double y = e4 - E;
+                const double C = 0.25 * (y * y * y) * (r41 * r42 * r43);
+                w1 = 0.25 - C * y * r41;
+                w2 = 0.25 - C * y * r42;
+                w3 = 0.25 - C * y * r43;
+                w4 = 0.25 - C * (4.0 - y * (r41 + r42 + r43));
+            }
+#pragma unroll
+            for (int g = 0; g < GT; ++g)
+                if (g < n_groups)
+                    atomicAdd(&part[g * w.tile_n + (j - w.tile_lo)], dos_fixed(w1 * a[g][0] + w2 * a[g][1] + w3 * a[g][2] + w4 * a[g][NC - 1]));
+        }
+    } else {
+        const double e1 = e[0], e2 = e[1], e3 = e[2];
+        const double r21 = 1.0 / (e2 - e1), r31 = 1.0 / (e3 - e1), r32 = 1.0 / (e3 - e2);
+        const double third = 1.0 / 3.0;
+        for (int j = lo; j < hi; ++j) {
+            const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e3 here
+            double w1, w2, w3;
+            if (E < e2) {
+                const double x = E - e1;
+                const double C = third * (x * x) * (r21 * r31);
+                w1 = C * (3.0 - x * (r21 + r31));
+                w2 = C * x * r21;
+                w3 = C * x * r31;
+            } else {
+                const double y = e3 - E;
+                const double C = third * (y * y) * (r31 * r32);
+                w1 = third - C * y * r31;
+                w2 = third - C * y * r32;
+                w3 = third - C * (3.0 - y * (r31 + r32));
+            }
+#pragma unroll
+            for (int g = 0; g < GT; ++g)
+                if (g < n_groups) atomicAdd(&part[g * w.tile_n + (j - w.tile_lo)], dos_fixed(w1 * a[g][0] + w2 * a[g][1] + w3 * a[g][2]));
+        }
+    }
+}
+
+// grid: (workgroups, energy tiles).  part_g / step_g: [gridDim.x][n_groups][n_e]; every element is written by exactly one workgroup.
+template <int DIM, int GT>
+__global__ void __launch_bounds__(PDOS_THREADS)
+    pdos_accumulate_kernel(const double* __restrict__ E, const double* __restrict__ W, DosGeom g, int n_groups, double e_min, double e_step,
+                           double inv_step, int n_e, unsigned long long* __restrict__ part_g, unsigned long long* __restrict__ step_g) {
+    extern __shared__ unsigned long long pdos_lds[];
+    constexpr int TILE = PDOS_LDS_BINS / GT;
+    DosWindow w;
+    w.e_min = e_min;
+    w.e_step = e_step;
+    w.inv_step = inv_step;
+    w.n_e = n_e;
+    w.tile_lo = (int)blockIdx.y * TILE;
+    w.tile_n = min(TILE, n_e - w.tile_lo);
+    const int bins = n_groups * w.tile_n;  // <= PDOS_LDS_BINS
+    unsigned long long* part = pdos_lds;   // [n_groups][tile_n]
+    unsigned long long* step = pdos_lds + bins;
+    const int tid = (int)threadIdx.x;
+    for (int t = tid; t < 2 * bins; t += PDOS_THREADS) pdos_lds[t] = 0ull;
+    __syncthreads();
+
+    const int64_t first = (int64_t)blockIdx.x * g.items_per_wg;
+    const int64_t last = min(first + g.items_per_wg, g.items);
+    for (int64_t it = first + tid; it < last; it += PDOS_THREADS) {
+        const int64_t cell64 = it / g.n_orb;
+        const int band = (int)(it - cell64 * g.n_orb);
+        int c = (int)cell64;  // NK < 2^31 (checked by the launcher)
+        const int i2 = c % g.n2;
+        c /= g.n2;
+        const int i1 = c % g.n1;
+        const int i0 = c / g.n1;  // < n0_cells
+        const int j0 = i0 + 1 == g.n0_planes ? 0 : i0 + 1;
+        const int j1 = i1 + 1 == g.n1 ? 0 : i1 + 1;
+        const int j2 = i2 + 1 == g.n2 ? 0 : i2 + 1;
+        auto at = [&](int a0, int a1, int a2) -> int64_t { return ((int64_t)a0 * g.n1 + a1) * g.n2 + a2; };
+        auto energy = [&](int64_t k) -> double { return E[k * g.n_orb + band]; };
+        if (DIM == 3) {
+            // corner k_xyz: x, y, z = step along axis 0, 1, 2
+            const int64_t k000 = at(i0, i1, i2), k100 = at(j0, i1, i2), k010 = at(i0, j1, i2), k110 = at(j0, j1, i2);
+            const int64_t k001 = at(i0, i1, j2), k101 = at(j0, i1, j2), k011 = at(i0, j1, j2), k111 = at(j0, j1, j2);
+            const double c000 = energy(k000), c100 = energy(k100), c010 = energy(k010), c110 = energy(k110);
+            const double c001 = energy(k001), c101 = energy(k101), c011 = energy(k011), c111 = energy(k111);
+            // the six orders (a, b, c) of the axes: corners 0, e_a, e_a + e_b, e_a + e_b + e_c -- the list of tbk_dos.hip
+            const double e012[4] = {c000, c100, c110, c111}, e021[4] = {c000, c100, c101, c111}, e102[4] = {c000, c010, c110, c111};
+            const double e120[4] = {c000, c010, c011, c111}, e201[4] = {c000, c001, c101, c111}, e210[4] = {c000, c001, c011, c111};
+            const int64_t k012[4] = {k000, k100, k110, k111}, k021[4] = {k000, k100, k101, k111}, k102[4] = {k000, k010, k110, k111};
+            const int64_t k120[4] = {k000, k010, k011, k111}, k201[4] = {k000, k001, k101, k111}, k210[4] = {k000, k001, k011, k111};
+            pdos_simplex<GT, 4>(e012, k012, band, W, n_groups, g.n_orb, w, part, step);
+            pdos_simplex<GT, 4>(e021, k021, band, W, n_groups, g.n_orb, w, part, step);
+            pdos_simplex<GT, 4>(e102, k102, band, W, n_groups, g.n_orb, w, part, step);
+            pdos_simplex<GT, 4>(e120, k120, band, W, n_groups, g.n_orb, w, part, step);
+            pdos_simplex<GT, 4>(e201, k201, band, W, n_groups, g.n_orb, w, part, step);
+            pdos_simplex<GT, 4>(e210, k210, band, W, n_groups, g.n_orb, w, part, step);
+        } else {
+            const int64_t k00 = at(i0, i1, 0), k10 = at(j0, i1, 0), k01 = at(i0, j1, 0), k11 = at(j0, j1, 0);
+            const double c00 = energy(k00), c10 = energy(k10), c01 = energy(k01), c11 = energy(k11);
+            const double e01[3] = {c00, c10, c11}, e10[3] = {c00, c01, c11};
+            const int64_t k01_[3] = {k00, k10, k11}, k10_[3] = {k00, k01, k11};
+            pdos_simplex<GT, 3>(e01, k01_, band, W, n_groups, g.n_orb, w, part, step);  // (0, 1)
+            pdos_simplex<GT, 3>(e10, k10_, band, W, n_groups, g.n_orb, w, part, step);  // (1, 0)
+        }
+    }
+    __syncthreads();
+    const int64_t row = (int64_t)blockIdx.x * n_groups * n_e;
+    for (int t = tid; t < bins; t += PDOS_THREADS) {
+        const int grp = t / w.tile_n, j = t - grp * w.tile_n;
+        const int64_t at_g = row + (int64_t)grp * n_e + w.tile_lo + j;
+        part_g[at_g] = part[t];
+        step_g[at_g] = step[t];
+    }
+}
+
+// one thread per (group, bin): the workgroups' rows in index order, in integers, the high and low part of every 64-bit bin apart.
+// sums: [4][n_groups * n_e] = fraction high / low, step high / low
+__global__ void __launch_bounds__(PDOS_THREADS)
+    pdos_reduce_kernel(const unsigned long long* __restrict__ part_g, const unsigned long long* __restrict__ step_g, int n_wg, int64_t n_bins,
+                       unsigned long long* __restrict__ sums) {
+    const int64_t j = (int64_t)blockIdx.x * PDOS_THREADS + threadIdx.x;
+    if (j >= n_bins) return;
+    const unsigned long long mask = (1ull << DOS_SPLIT_BITS) - 1;
+    unsigned long long p_hi = 0, p_lo = 0, s_hi = 0, s_lo = 0;
+    for (int wg = 0; wg < n_wg; ++wg) {
+        const unsigned long long p = part_g[(int64_t)wg * n_bins + j], s = step_g[(int64_t)wg * n_bins + j];
+        p_hi += p >> DOS_SPLIT_BITS;
+        p_lo += p & mask;
+        s_hi += s >> DOS_SPLIT_BITS;
+        s_lo += s & mask;
+    }
+    sums[j] = p_hi;
+    sums[n_bins + j] = p_lo;
+    sums[2 * n_bins + j] = s_hi;
+    sums[3 * n_bins + j] = s_lo;
+}
+
+// one workgroup per group: nos[g][j] = (fraction[j] + sum_{i <= j} step[i]) / denom, the prefix sum on the two halves apart (in
+// integers: see Overflow above).  Every thread owns a contiguous segment of the grid.
+__global__ void __launch_bounds__(PDOS_THREADS) pdos_scan_kernel(const unsigned long long* __restrict__ sums, int n_e, int64_t n_bins, double denom,
+                                                                 double* __restrict__ nos) {
+    __shared__ unsigned long long total_hi[PDOS_THREADS], total_lo[PDOS_THREADS];
+    const int tid = (int)threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * n_e;
+    const unsigned long long* p_hi = sums + base;
+    const unsigned long long* p_lo = sums + n_bins + base;
+    const unsigned long long* s_hi = sums + 2 * n_bins + base;
+    const unsigned long long* s_lo = sums + 3 * n_bins + base;
+    const int seg = (n_e + PDOS_THREADS - 1) / PDOS_THREADS;
+    const int lo = min(n_e, tid * seg), hi = min(n_e, lo + seg);
+    unsigned long long sum_hi = 0, sum_lo = 0;
+    for (int j = lo; j < hi; ++j) {
+        sum_hi += s_hi[j];
+        sum_lo += s_lo[j];
+    }
+    total_hi[tid] = sum_hi;
+    total_lo[tid] = sum_lo;
+    __syncthreads();
+    unsigned long long run_hi = 0, run_lo = 0;
+    for (int t = 0; t < tid; ++t) {
+        run_hi += total_hi[t];
+        run_lo += total_lo[t];
+    }
+    const unsigned long long mask = (1ull << DOS_SPLIT_BITS) - 1;
+    for (int j = lo; j < hi; ++j) {
+        run_hi += s_hi[j];
+        run_lo += s_lo[j];
+        unsigned long long all_lo = run_lo + p_lo[j];
+        const unsigned long long all_hi = run_hi + p_hi[j] + (all_lo >> DOS_SPLIT_BITS);
+        all_lo &= mask;
+        const double value = (double)all_hi * (1.0 / (double)(1ull << (DOS_FRAC_BITS - DOS_SPLIT_BITS))) + (double)all_lo * (1.0 / (double)(1ull << DOS_FRAC_BITS));
+        nos[base + j] = value / denom;
+    }
+}
+
+struct PdosLaunch {
+    DosGeom g;
+    int n_groups = 0, group_tile = 1, n_wg = 0, n_tiles = 0, n_e = 0;
+    size_t off_step = 0, off_sums = 0, ws_bytes = 0;
+};
+
+// dim in {2, 3}; cells0 cells along axis 0 out of planes0 planes held in E and W
+int pdos_plan(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb, int n_groups, int64_t n_e, PdosLaunch* out) {
+    PdosLaunch L;
+    L.g.n0_cells = (int)cells0;
+    L.g.n0_planes = (int)planes0;
+    L.g.n1 = mesh[1];
+    L.g.n2 = dim == 3 ? mesh[2] : 1;
+    L.g.n_orb = n_orb;
+    L.g.items = cells0 * L.g.n1 * L.g.n2 * n_orb;
+    TBK_ARG(L.g.items * (dim == 3 ? 6 : 2) <= PDOS_MAX_TERMS, "mesh x orbitals too large for one projected density-of-states call");
+    L.n_groups = n_groups;
+    L.group_tile = pdos_group_tile(n_groups);
+    L.n_e = (int)n_e;
+    const int tile = PDOS_LDS_BINS / L.group_tile;
+    L.n_tiles = (int)((n_e + tile - 1) / tile);
+    // workgroups: enough to fill the chip, no more rows than 2^24 bins of partials, never more than DOS_MAX_ITEMS items each
+    const int64_t by_memory = std::max<int64_t>(1, (int64_t(1) << 24) / (n_e * n_groups));
+    int64_t n_wg = std::min<int64_t>((L.g.items + PDOS_THREADS - 1) / PDOS_THREADS, std::min<int64_t>(1024, by_memory));
+    n_wg = std::max<int64_t>(n_wg, (L.g.items + DOS_MAX_ITEMS - 1) / DOS_MAX_ITEMS);
+    TBK_ARG(n_wg <= (int64_t(1) << DOS_SPLIT_BITS), "mesh x orbitals too large for one projected density-of-states call");
+    L.g.items_per_wg = (L.g.items + n_wg - 1) / n_wg;
+    L.n_wg = (int)((L.g.items + L.g.items_per_wg - 1) / L.g.items_per_wg);
+    const size_t bins = (size_t)n_groups * (size_t)n_e;
+    L.off_step = dos_align256((size_t)L.n_wg * bins * sizeof(unsigned long long));
+    L.off_sums = 2 * L.off_step;
+    L.ws_bytes = L.off_sums + dos_align256(4 * bins * sizeof(unsigned long long));
+    *out = L;
+    return TBK_OK;
+}
+
+template <int DIM>
+void pdos_launch_accumulate(hipStream_t s, const PdosLaunch& L, const double* d_E, const double* d_W, double e_min, double e_step,
+                            unsigned long long* part_g, unsigned long long* step_g) {
+    const int tile = PDOS_LDS_BINS / L.group_tile;
+    const size_t lds = (size_t)L.n_groups * (size_t)std::min<int64_t>(L.n_e, tile) * 2 * sizeof(unsigned long long);
+    const dim3 grid((unsigned)L.n_wg, (unsigned)L.n_tiles);
+#define PDOS_CASE(GT)                                                                                                                     \
+    case GT:                                                                                                                              \
+        hipLaunchKernelGGL((pdos_accumulate_kernel<DIM, GT>), grid, dim3(PDOS_THREADS), lds, s, d_E, d_W, L.g, L.n_groups, e_min, e_step, \
+                           1.0 / e_step, L.n_e, part_g, step_g);                                                                          \
+        break;
+    switch (L.group_tile) {
+        PDOS_CASE(1)
+        PDOS_CASE(2)
+        PDOS_CASE(4)
+        PDOS_CASE(8)
+        PDOS_CASE(16)
+    }
+#undef PDOS_CASE
+}
+
+// enqueue: (E, W) -> nos[G][n_e] on stream s (d_ws: L.ws_bytes).  denom = S * NK of the WHOLE mesh.  ev (or NULL): three events,
+// in front of the accumulate kernel, behind it, behind the scan
+int pdos_launch(hipStream_t s, int dim, const PdosLaunch& L, const double* d_E, const double* d_W, double e_min, double e_step, double denom,
+                void* d_ws, double* d_nos, hipEvent_t* ev) {
+    static_assert(TBK_PDOS_MAX_GROUPS == 16, "pdos_launch_accumulate instantiates group tiles up to 16");
+    char* ws = static_cast<char*>(d_ws);
+    auto* part_g = reinterpret_cast<unsigned long long*>(ws);
+    auto* step_g = reinterpret_cast<unsigned long long*>(ws + L.off_step);
+    auto* sums = reinterpret_cast<unsigned long long*>(ws + L.off_sums);
+    const int64_t n_bins = (int64_t)L.n_groups * L.n_e;
+    if (ev) (void)hipEventRecord(ev[0], s);
+    if (dim == 3)
+        pdos_launch_accumulate<3>(s, L, d_E, d_W, e_min, e_step, part_g, step_g);
+    else
+        pdos_launch_accumulate<2>(s, L, d_E, d_W, e_min, e_step, part_g, step_g);
+    TBK_HIP(hipGetLastError());
+    if (ev) (void)hipEventRecord(ev[1], s);
+    hipLaunchKernelGGL(pdos_reduce_kernel, dim3((unsigned)((n_bins + PDOS_THREADS - 1) / PDOS_THREADS)), dim3(PDOS_THREADS), 0, s, part_g, step_g,
+                       L.n_wg, n_bins, sums);
+    TBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pdos_scan_kernel, dim3((unsigned)L.n_groups), dim3(PDOS_THREADS), 0, s, sums, L.n_e, n_bins, denom, d_nos);
+    TBK_HIP(hipGetLastError());
+    if (ev) (void)hipEventRecord(ev[2], s);
+    return TBK_OK;
+}
+
+struct EventSet {  // HIP events of one timed call, destroyed with it
+    std::vector<hipEvent_t> ev;
+    bool make(size_t count) {
+        for (size_t i = 0; i < count; ++i) {
+            hipEvent_t e = nullptr;
+            if (hipEventCreate(&e) != hipSuccess) return false;
+            ev.push_back(e);
+        }
+        return true;
+    }
+    ~EventSet() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+};
+
+}  // namespace
+
+// The groups as the C ABI takes them: group g = group_orbitals[group_offsets[g] .. group_offsets[g + 1])
+int tbk_pdos_check_groups(int n_orb, const int32_t* group_offsets, const int32_t* group_orbitals, int n_groups) {
+    TBK_ARG(group_offsets != nullptr && group_orbitals != nullptr, "group_offsets / group_orbitals is NULL");
+    TBK_ARG(n_groups >= 1, "no projection groups");
+    TBK_ARG(n_groups <= TBK_PDOS_MAX_GROUPS, "more than TBK_PDOS_MAX_GROUPS projection groups");
+    TBK_ARG(group_offsets[0] == 0, "group_offsets[0] must be 0");
+    std::vector<char> seen((size_t)std::max(n_orb, 0));
+    for (int g = 0; g < n_groups; ++g) {
+        TBK_ARG(group_offsets[g + 1] > group_offsets[g], "a projection group is empty");
+        TBK_ARG(group_offsets[g + 1] - group_offsets[g] <= n_orb, "an orbital repeats inside a projection group");
+        std::fill(seen.begin(), seen.end(), 0);
+        for (int32_t e = group_offsets[g]; e < group_offsets[g + 1]; ++e) {
+            const int32_t i = group_orbitals[e];
+            TBK_ARG(i >= 0 && i < n_orb, "an orbital index of a projection group is out of range");
+            TBK_ARG(!seen[(size_t)i], "an orbital repeats inside a projection group");
+            seen[(size_t)i] = 1;
+        }
+    }
+    return TBK_OK;
+}
+
+extern "C" int tbk_pdos_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, int n_groups, const double* E, const double* W,
+                                         double e_min, double e_step, int64_t n_e, double* nos_out) {
+    int64_t nk = 0;
+    TBK_CHECK(tbk_dos_check(dim, mesh, e_step, n_e, nos_out, &nk));
+    TBK_ARG(E != nullptr && W != nullptr, "E / W is NULL");
+    TBK_ARG(n_orb >= 1, "n_orb < 1");
+    TBK_ARG(n_groups >= 1 && n_groups <= TBK_PDOS_MAX_GROUPS, "n_groups outside [1, TBK_PDOS_MAX_GROUPS]");
+    TBK_ARG(std::isfinite(e_min), "e_min is not finite");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
+        (void)hipGetLastError();
+        tbk_set_error("no HIP device visible: libtbk has no CPU path");
+        return TBK_ERR_DEVICE;
+    }
+    TBK_ARG(device >= 0 && device < n_dev, "device out of range");
+    TBK_HIP(hipSetDevice(device));
+    PdosLaunch L;
+    TBK_CHECK(pdos_plan(dim, mesh, mesh[0], mesh[0], n_orb, n_groups, n_e, &L));
+    const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double), w_bytes = e_bytes * (size_t)n_groups;
+    const size_t nos_bytes = (size_t)n_groups * (size_t)n_e * sizeof(double);
+    DevBuf d_E, d_W, d_ws, d_nos;
+    const int rc = [&]() -> int {
+        TBK_CHECK(d_E.reserve(e_bytes));
+        TBK_CHECK(d_W.reserve(w_bytes));
+        TBK_CHECK(d_ws.reserve(L.ws_bytes));
+        TBK_CHECK(d_nos.reserve(nos_bytes));
+        TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
+        TBK_HIP(hipMemcpy(d_W.ptr, W, w_bytes, hipMemcpyHostToDevice));
+        TBK_CHECK(pdos_launch(nullptr, dim, L, d_E.as<double>(), d_W.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk, d_ws.ptr,
+                              d_nos.as<double>(), nullptr));
+        TBK_HIP(hipMemcpy(nos_out, d_nos.ptr, nos_bytes, hipMemcpyDeviceToHost));
+        return TBK_OK;
+    }();
+    d_E.release();
+    d_W.release();
+    d_ws.release();
+    d_nos.release();
+    return rc;
+}
+
+// Cells [p_lo, p_lo + p_count) along axis 0 of the mesh on one handle: E and W of those planes and of the one periodic neighbour
+// plane the last cells need stay in HBM (NK n_orb (1 + G) doubles); the eigenvectors exist one k chunk at a time.  nos_out[G][n_e]
+// receives this slab's share, already divided by S * NK of the whole mesh.
+int tbk_pdos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_count, const int32_t* group_offsets, const int32_t* group_orbitals,
+                  int n_groups, double e_min, double e_step, int64_t n_e, double* nos_out) {
+    TBK_ARG(m != nullptr, "model is NULL");
+    TBK_LOCK(m);
+    TBK_ARG(!m->kdotp, "a k.p model has no Brillouin zone");
+    int64_t nk_total = 0;
+    TBK_CHECK(tbk_dos_check(m->dim, mesh, e_step, n_e, nos_out, &nk_total));
+    TBK_ARG(std::isfinite(e_min), "e_min is not finite");
+    TBK_CHECK(tbk_pdos_check_groups(m->n_orb, group_offsets, group_orbitals, n_groups));
+    const int dim = m->dim, n_orb = m->n_orb;
+    const int64_t n0 = mesh[0];
+    TBK_ARG(p_lo >= 0 && p_count >= 1 && p_lo + p_count <= n0, "slab outside the mesh");
+    TBK_CHECK(tbk_eig_check_option(m));
+    TBK_HIP(hipSetDevice(m->device));
+    const int64_t planes = p_count == n0 ? n0 : p_count + 1;
+    const int64_t plane_pts = nk_total / n0, nk = planes * plane_pts;
+    PdosLaunch L;
+    TBK_CHECK(pdos_plan(dim, mesh, p_count, planes, n_orb, n_groups, n_e, &L));
+
+    std::vector<double> h_k;
+    TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, p_lo, planes, &h_k));
+    const size_t k_bytes = h_k.size() * sizeof(double);
+    const size_t off_bytes = dos_align256((size_t)(n_groups + 1) * sizeof(int32_t)), orb_bytes = (size_t)group_offsets[n_groups] * sizeof(int32_t);
+    const size_t nos_bytes = (size_t)n_groups * (size_t)n_e * sizeof(double);
+    // what stays for the whole call first, so that the chunk is chosen from what is left
+    TBK_CHECK(m->ws_k.reserve(k_bytes));
+    TBK_CHECK(m->ws_out.reserve((size_t)nk * n_orb * sizeof(double)));
+    TBK_CHECK(m->ws_pdos_w.reserve((size_t)nk * n_groups * n_orb * sizeof(double)));
+    TBK_CHECK(m->ws_pdos_grp.reserve(off_bytes + orb_bytes));
+    TBK_CHECK(m->ws_dos.reserve(L.ws_bytes + dos_align256(nos_bytes)));
+    // k-points per chunk: TBK_OPT_K_CHUNK as given (chunks need not be whole planes nor whole k tiles), else what the eigenvector
+    // call itself would take from the free memory -- its U chunk, chunk * n_orb^2 * 16 bytes, is the large term there
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : choose_chunk(m, nk, true)));
+    TBK_CHECK(m->ws_pdos_u.reserve((size_t)chunk * n_orb * n_orb * 2 * sizeof(double)));
+    const auto* d_off = m->ws_pdos_grp.as<int32_t>();
+    const auto* d_orb = reinterpret_cast<const int32_t*>(static_cast<const char*>(m->ws_pdos_grp.ptr) + off_bytes);
+    TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, h_k.data(), k_bytes, hipMemcpyHostToDevice, m->stream));
+    TBK_HIP(hipMemcpyAsync(m->ws_pdos_grp.ptr, group_offsets, (size_t)(n_groups + 1) * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+    TBK_HIP(hipMemcpyAsync(m->ws_pdos_grp.as<char>() + off_bytes, group_orbitals, orb_bytes, hipMemcpyHostToDevice, m->stream));
+
+    const int64_t n_chunks = (nk + chunk - 1) / chunk;
+    EventSet events;
+    const bool timed = m->timing && events.make(2 * (size_t)n_chunks + 3);
+    double* d_E = m->ws_out.as<double>();
+    double* d_W = m->ws_pdos_w.as<double>();
+    double* d_U = m->ws_pdos_u.as<double>();
+    for (int64_t c = 0; c < n_chunks; ++c) {
+        const int64_t c0 = c * chunk, nkc = std::min(chunk, nk - c0);
+        TBK_CHECK(tbk_eigh_device(m, m->ws_k.as<double>() + c0 * dim, nkc, 2, nullptr, d_E + c0 * n_orb, d_U));
+        if (timed) (void)hipEventRecord(events.ev[2 * (size_t)c], m->stream);
+        const int64_t threads = nkc * n_orb;
+        hipLaunchKernelGGL(pdos_weights_kernel, dim3((unsigned)((threads + PDOS_THREADS - 1) / PDOS_THREADS)), dim3(PDOS_THREADS), 0, m->stream,
+                           reinterpret_cast<const double2*>(d_U), n_orb, nkc, n_groups, d_off, d_orb, d_W + (size_t)c0 * n_groups * n_orb);
+        TBK_HIP(hipGetLastError());
+        if (timed) (void)hipEventRecord(events.ev[2 * (size_t)c + 1], m->stream);
+    }
+    TBK_CHECK(tbk_eigenval_check(m));  // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigh
+
+    double* d_nos = reinterpret_cast<double*>(static_cast<char*>(m->ws_dos.ptr) + L.ws_bytes);
+    TBK_CHECK(pdos_launch(m->stream, dim, L, d_E, d_W, e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk_total, m->ws_dos.ptr, d_nos,
+                          timed ? events.ev.data() + 2 * (size_t)n_chunks : nullptr));
+    TBK_HIP(hipMemcpyAsync(nos_out, d_nos, nos_bytes, hipMemcpyDeviceToHost, m->stream));
+    TBK_HIP(hipStreamSynchronize(m->stream));
+    if (timed) {
+        double ms[3] = {0.0, 0.0, 0.0};
+        bool ok = true;
+        float t = 0.f;
+        for (int64_t c = 0; c < n_chunks && ok; ++c) {
+            ok = hipEventElapsedTime(&t, events.ev[2 * (size_t)c], events.ev[2 * (size_t)c + 1]) == hipSuccess;
+            ms[0] += (double)t;
+        }
+        for (int i = 0; i < 2 && ok; ++i) {
+            ok = hipEventElapsedTime(&t, events.ev[2 * (size_t)n_chunks + i], events.ev[2 * (size_t)n_chunks + i + 1]) == hipSuccess;
+            ms[1 + i] = (double)t;
+        }
+        if (ok) {
+            for (int i = 0; i < 3; ++i) m->pdos_ms[i] += ms[i];
+            m->pdos_calls += 1;
+        }
+    }
+    return TBK_OK;
+}
+
+extern "C" int tbk_pdos(tbk_model* m, const int32_t* mesh, const int32_t* group_offsets, const int32_t* group_orbitals, int n_groups, double e_min,
+                        double e_step, int64_t n_e, double* nos_out) {
+    TBK_ARG(m != nullptr, "model is NULL");
+    TBK_ARG(mesh != nullptr, "mesh / nos is NULL");
+    TBK_ARG(m->dim == 2 || m->dim == 3, "the density of states needs a 2- or 3-dimensional mesh");
+    TBK_ARG(mesh[0] >= 1, "a mesh entry is < 1");
+    return tbk_pdos_slab(m, mesh, 0, mesh[0], group_offsets, group_orbitals, n_groups, e_min, e_step, n_e, nos_out);
+}
+
+extern "C" int tbk_pdos_timing(tbk_model* m, double* ms, int64_t* calls, int reset) {
+    TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr, "model / ms / calls is NULL");
+    TBK_LOCK(m);
+    for (int i = 0; i < 3; ++i) ms[i] = m->pdos_ms[i];
+    *calls = m->pdos_calls;
+    if (reset) {
+        for (int i = 0; i < 3; ++i) m->pdos_ms[i] = 0.0;
+        m->pdos_calls = 0;
+    }
+    return TBK_OK;
+}
