@@ -195,6 +195,8 @@ int tbk_reduce_standalone(int device, int n_orb, int64_t nk, int reps, double* u
  * Only dim in {2, 3}.  The kernel (csrc/tbk_dos.hip) accumulates in 64-bit fixed point with a resolution of 2^-40 per simplex
  * (|error| <= 4.5e-13 n_orb) and sums in integers, so for given eigenvalues nos does not depend on the order in which the
  * device runs its waves: the same call gives the same bits, as for the eigenvalues above.
+ * Range: the kernels (this one and tbk_pdos) work on energies multiplied by 2^54, so that a corner gap down to the smallest
+ * subnormal has a finite reciprocal; eigenvalues and grid points must stay below 2^969 in magnitude (not checked).
  * Argument errors (TBK_ERR_ARGUMENT): dim not in {2, 3}, a mesh entry < 1, 2^31 mesh points or more, n_e outside [2, 2^20],
  * e_step <= 0 or not finite, e_min not finite, a NULL pointer, a k.p handle.  Host buffers; synchronous. */
 

@@ -15,8 +15,8 @@
 // workgroup stores its bins with plain stores into its own row of a [n_workgroups][NE] buffer, and a second kernel sums the rows
 // in integers as well.  The result does not depend on the order in which waves run, nor on the number of workgroups.
 //
-// Bound (measured): VALU issue -- the bin loop of a simplex runs for the longest range among a wave's lanes and every
-// bin costs one or two FP64 divisions; LDS adds are 1 in 55 instructions and the corner loads ~95 GB/s out of L2.
+// Bound (measured): VALU issue -- the bin loop of a simplex runs for the longest range among a wave's lanes; the
+// reciprocals of the corner gaps are taken once per simplex, so a bin costs FP64 multiplies and adds, no division.
 
 #include <algorithm>
 #include <cmath>
@@ -46,7 +46,7 @@ __device__ __forceinline__ void dos_add(unsigned long long* part, int bin, doubl
 }
 
 // one tetrahedron: DESIGN 10.1 (the ranges are half-open as written there; the comparisons select the branch, so a branch with
-// a zero denominator is empty and never evaluated)
+// a zero gap is empty and never evaluated; every ratio in [0, 1] is formed on its own, tbk_dos_common.h)
 __device__ __forceinline__ void dos_tetrahedron(double e1, double e2, double e3, double e4, const DosWindow& w, unsigned long long* part,
                                                 unsigned* step) {
     dos_sort2(e1, e2);
@@ -58,19 +58,25 @@ __device__ __forceinline__ void dos_tetrahedron(double e1, double e2, double e3,
     const int j_hi = dos_first_at_or_above(e4, w.e_min, w.e_step, w.inv_step, w.n_e);
     if (j_hi >= w.tile_lo && j_hi < w.tile_lo + w.tile_n) atomicAdd(&step[j_hi - w.tile_lo], 1u);
     const int lo = max(j_lo, w.tile_lo), hi = min(j_hi, w.tile_lo + w.tile_n);
-    const double e21 = e2 - e1, e31 = e3 - e1, e41 = e4 - e1, e32 = e3 - e2, e42 = e4 - e2, e43 = e4 - e3;
+    if (lo >= hi) return;
+    // reciprocals of the scaled gaps, once per simplex (tbk_dos_common.h): the bin loop has no division
+    const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE, s4 = e4 * DOS_GAP_SCALE;
+    const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r41 = 1.0 / (s4 - s1), r32 = 1.0 / (s3 - s2), r42 = 1.0 / (s4 - s2),
+                 r43 = 1.0 / (s4 - s3);
     for (int j = lo; j < hi; ++j) {
         const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e4 here
+        const double Es = E * DOS_GAP_SCALE;
         double n;
         if (E < e2) {
-            const double x = E - e1;
-            n = x * x * x / (e21 * e31 * e41);
+            const double x = Es - s1;
+            n = (x * r21) * (x * r31) * (x * r41);
         } else if (E < e3) {
-            const double x = E - e2;
-            n = (e21 * e21 + 3.0 * e21 * x + 3.0 * x * x - (e31 + e42) / (e32 * e42) * (x * x * x)) / (e31 * e41);
+            const double x1 = Es - s1, x2 = Es - s2, y3 = s3 - Es, y4 = s4 - Es;
+            const double q32 = x2 * r32;
+            n = (x1 * r41) * (x1 * r31 + q32 * (y3 * r31)) + (x2 * r42) * q32 * (y4 * r41);
         } else {
-            const double x = e4 - E;
-            n = 1.0 - x * x * x / (e41 * e42 * e43);
+            const double y = s4 - Es;
+            n = 1.0 - (y * r41) * (y * r42) * (y * r43);
         }
         dos_add(part, j - w.tile_lo, n);
     }
@@ -84,16 +90,19 @@ __device__ __forceinline__ void dos_triangle(double e1, double e2, double e3, co
     const int j_hi = dos_first_at_or_above(e3, w.e_min, w.e_step, w.inv_step, w.n_e);
     if (j_hi >= w.tile_lo && j_hi < w.tile_lo + w.tile_n) atomicAdd(&step[j_hi - w.tile_lo], 1u);
     const int lo = max(j_lo, w.tile_lo), hi = min(j_hi, w.tile_lo + w.tile_n);
-    const double e21 = e2 - e1, e31 = e3 - e1, e32 = e3 - e2;
+    if (lo >= hi) return;
+    const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE;
+    const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r32 = 1.0 / (s3 - s2);
     for (int j = lo; j < hi; ++j) {
         const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e3 here
+        const double Es = E * DOS_GAP_SCALE;
         double n;
         if (E < e2) {
-            const double x = E - e1;
-            n = x * x / (e21 * e31);
+            const double x = Es - s1;
+            n = (x * r21) * (x * r31);
         } else {
-            const double x = e3 - E;
-            n = 1.0 - x * x / (e31 * e32);
+            const double y = s3 - Es;
+            n = 1.0 - (y * r31) * (y * r32);
         }
         dos_add(part, j - w.tile_lo, n);
     }

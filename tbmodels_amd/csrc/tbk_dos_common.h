@@ -49,6 +49,17 @@ __device__ __forceinline__ unsigned long long dos_fixed(double x) {
     return (unsigned long long)__double2ll_rn(x * (double)(1ull << DOS_FRAC_BITS));
 }
 
+// Branch arithmetic.  Every branch of the tetrahedron formulas is a polynomial in ratios x / gap in [0, 1], x a
+// distance of E from a corner and gap the corner difference that contains it, and the kernels form every ratio on its own as
+// x * (1 / gap): a product of three small distances can then not underflow to 0 against a product of reciprocals that overflowed.
+// What is left is a gap whose own reciprocal overflows -- below about 2^-1024, deep in the subnormal range, which starts under
+// 2^-1022 -- where x = 0 would give 0 * inf; so
+// the corner energies and E are multiplied by DOS_GAP_SCALE first.  That is exact (a power of two), the ratios do not change, and
+// the smallest positive gap, 2^-1074, becomes 2^-1020 with a finite reciprocal.  Only the reciprocal of a ZERO gap is inf, and a
+// branch that is selected has none (the comparisons are made on the unscaled numbers).  Energies above 2^969 would overflow
+// (include/tbk.h states the limit).
+constexpr double DOS_GAP_SCALE = 0x1p54;
+
 inline size_t dos_align256(size_t x) { return (x + 255) / 256 * 256; }
 
 // tbk_dos.hip: the checks every density-of-states entry point shares (*nk_total = points of the whole mesh), and the k list of

@@ -87,7 +87,8 @@ __device__ __forceinline__ void pdos_exchange(double (&e)[NC], double (&a)[GT][N
 }
 
 // One simplex of NC corners (4: tetrahedron, 3: triangle) whose mesh points are kc[]: DESIGN 11.1.  part / step: [n_groups][tile_n].
-// The ranges are half-open and the comparisons select the branch, so a reciprocal of a zero difference (inf) is never used.
+// The ranges are half-open and the comparisons select the branch, so a reciprocal of a zero difference (inf) is never used; every
+// ratio in [0, 1] is formed on its own from scaled energies (tbk_dos_common.h), so a selected branch has no 0 * inf.
 template <int GT, int NC>
 __device__ __forceinline__ void pdos_simplex(const double (&e_in)[NC], const int64_t (&kc)[NC], int band, const double* __restrict__ W,
                                              int n_groups, int n_orb, const DosWindow& w, unsigned long long* part, unsigned long long* step) {
@@ -122,35 +123,42 @@ __device__ __forceinline__ void pdos_simplex(const double (&e_in)[NC], const int
     if (lo >= hi) return;
     if (NC == 4) {
         const double e1 = e[0], e2 = e[1], e3 = e[2], e4 = e[NC - 1];
-        const double r21 = 1.0 / (e2 - e1), r31 = 1.0 / (e3 - e1), r41 = 1.0 / (e4 - e1), r32 = 1.0 / (e3 - e2), r42 = 1.0 / (e4 - e2),
-                     r43 = 1.0 / (e4 - e3);
+        const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE, s4 = e4 * DOS_GAP_SCALE;
+        const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r41 = 1.0 / (s4 - s1), r32 = 1.0 / (s3 - s2), r42 = 1.0 / (s4 - s2),
+                     r43 = 1.0 / (s4 - s3);
         for (int j = lo; j < hi; ++j) {
             const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e4 here
+            const double Es = E * DOS_GAP_SCALE;
             double w1, w2, w3, w4;
             if (E < e2) {
-                const double x = E - e1;
-                const double C = 0.25 * (x * x * x) * (r21 * r31 * r41);
-                w1 = C * (4.0 - x * (r21 + r31 + r41));
-                w2 = C * x * r21;
-                w3 = C * x * r31;
-                w4 = C * x * r41;
+                const double x = Es - s1;
+                const double q21 = x * r21, q31 = x * r31, q41 = x * r41;
+                const double C = 0.25 * q21 * q31 * q41;
+                w1 = C * (4.0 - (q21 + q31 + q41));
+                w2 = C * q21;
+                w3 = C * q31;
+                w4 = C * q41;
             } else if (E < e3) {
-                const double x1 = E - e1, x2 = E - e2, y3 = e3 - E, y4 = e4 - E;
-                const double C1 = 0.25 * (x1 * x1) * (r41 * r31);
-                const double C2 = 0.25 * (x1 * x2 * y3) * (r41 * r32 * r31);
-                const double C3 = 0.25 * (x2 * x2 * y4) * (r42 * r32 * r41);
+                const double x1 = Es - s1, x2 = Es - s2, y3 = s3 - Es, y4 = s4 - Es;
+                const double p31 = x1 * r31, p41 = x1 * r41, p32 = x2 * r32, p42 = x2 * r42;  // from below
+                const double m31 = y3 * r31, m32 = y3 * r32, m41 = y4 * r41, m42 = y4 * r42;  // from above
+                const double T = 0.25 * p41;
+                const double C1 = T * p31;
+                const double C2 = T * p32 * m31;
+                const double C3 = 0.25 * p42 * p32 * m41;
                 const double C12 = C1 + C2, C23 = C2 + C3, C123 = C12 + C3;
-                w1 = C1 + C12 * y3 * r31 + C123 * y4 * r41;
-                w2 = C123 + C23 * y3 * r32 + C3 * y4 * r42;
-                w3 = C12 * x1 * r31 + C23 * x2 * r32;
-                w4 = C123 * x1 * r41 + C3 * x2 * r42;
+                w1 = C1 + C12 * m31 + C123 * m41;
+                w2 = C123 + C23 * m32 + C3 * m42;
+                w3 = C12 * p31 + C23 * p32;
+                w4 = C123 * p41 + C3 * p42;
             } else {
-                const double y = e4 - E;
-                const double C = 0.25 * (y * y * y) * (r41 * r42 * r43);
-                w1 = 0.25 - C * y * r41;
-                w2 = 0.25 - C * y * r42;
-                w3 = 0.25 - C * y * r43;
-                w4 = 0.25 - C * (4.0 - y * (r41 + r42 + r43));
+                const double y = s4 - Es;
+                const double q41 = y * r41, q42 = y * r42, q43 = y * r43;
+                const double C = 0.25 * q41 * q42 * q43;
+                w1 = 0.25 - C * q41;
+                w2 = 0.25 - C * q42;
+                w3 = 0.25 - C * q43;
+                w4 = 0.25 - C * (4.0 - (q41 + q42 + q43));
             }
 #pragma unroll
             for (int g = 0; g < GT; ++g)
@@ -159,23 +167,27 @@ __device__ __forceinline__ void pdos_simplex(const double (&e_in)[NC], const int
         }
     } else {
         const double e1 = e[0], e2 = e[1], e3 = e[2];
-        const double r21 = 1.0 / (e2 - e1), r31 = 1.0 / (e3 - e1), r32 = 1.0 / (e3 - e2);
+        const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE;
+        const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r32 = 1.0 / (s3 - s2);
         const double third = 1.0 / 3.0;
         for (int j = lo; j < hi; ++j) {
             const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e3 here
+            const double Es = E * DOS_GAP_SCALE;
             double w1, w2, w3;
             if (E < e2) {
-                const double x = E - e1;
-                const double C = third * (x * x) * (r21 * r31);
-                w1 = C * (3.0 - x * (r21 + r31));
-                w2 = C * x * r21;
-                w3 = C * x * r31;
+                const double x = Es - s1;
+                const double q21 = x * r21, q31 = x * r31;
+                const double C = third * q21 * q31;
+                w1 = C * (3.0 - (q21 + q31));
+                w2 = C * q21;
+                w3 = C * q31;
             } else {
-                const double y = e3 - E;
-                const double C = third * (y * y) * (r31 * r32);
-                w1 = third - C * y * r31;
-                w2 = third - C * y * r32;
-                w3 = third - C * (3.0 - y * (r31 + r32));
+                const double y = s3 - Es;
+                const double q31 = y * r31, q32 = y * r32;
+                const double C = third * q31 * q32;
+                w1 = third - C * q31;
+                w2 = third - C * q32;
+                w3 = third - C * (3.0 - (q31 + q32));
             }
 #pragma unroll
             for (int g = 0; g < GT; ++g)

@@ -1,5 +1,5 @@
 """
-Model.dos measurements (DESIGN.md section 10.5): prints one table.
+Model.dos measurements (DESIGN.md section 10.4): prints one table.
 
 At the BASELINE config-4 shape (64 orbitals, 4096 lattice vectors, the 100^3 mesh) and for the silicon model on a 60^3 mesh:
 

@@ -25,7 +25,9 @@ def simplex_fraction(corners, energies):
     Filled fraction n_T(E) of simplices whose corner energies are ``corners[..., :]`` (3 corners: triangle, 4: tetrahedron) for
     every E of the 1-D array ``energies``: shape ``corners.shape[:-1] + (len(energies),)``.  The ranges are half-open as in
     DESIGN 10.1, the comparisons select the branch, and a branch is evaluated only where it was selected (so a zero denominator
-    is never divided by; a fully degenerate simplex is a clean step at its energy).
+    is never divided by; a fully degenerate simplex is a clean step at its energy).  Every branch is a polynomial in ratios
+    (E - e_i) / (e_j - e_i) or (e_j - E) / (e_j - e_i) that lie in [0, 1] and are formed one by one: no product of differences can
+    underflow to 0 against an overflowing product of reciprocals, however small a gap is.
     """
     corners = np.sort(np.asarray(corners, dtype=float), axis=-1)
     energies = np.asarray(energies, dtype=float)
@@ -41,24 +43,24 @@ def simplex_fraction(corners, energies):
     if n_c == 4:
         e1, e2, e3, e4 = e
         sel = (en >= e1) & (en < e2)
-        a1, a2, a3, a4, x = e1[sel], e2[sel], e3[sel], e4[sel], en[sel]
-        out[sel] = (x - a1) ** 3 / ((a2 - a1) * (a3 - a1) * (a4 - a1))
+        a1, a2, a3, a4, x = e1[sel], e2[sel], e3[sel], e4[sel], en[sel] - e1[sel]
+        out[sel] = (x / (a2 - a1)) * (x / (a3 - a1)) * (x / (a4 - a1))
         sel = (en >= e2) & (en < e3)
         a1, a2, a3, a4, x = e1[sel], e2[sel], e3[sel], e4[sel], en[sel]
-        e21, e31, e41, e32, e42 = a2 - a1, a3 - a1, a4 - a1, a3 - a2, a4 - a2
-        d = x - a2
-        out[sel] = (e21 * e21 + 3.0 * e21 * d + 3.0 * d * d - (e31 + e42) / (e32 * e42) * (d * d * d)) / (e31 * e41)
+        x1, x2, y3, y4 = x - a1, x - a2, a3 - x, a4 - x
+        q41, q32 = x1 / (a4 - a1), x2 / (a3 - a2)
+        out[sel] = q41 * (x1 / (a3 - a1) + q32 * (y3 / (a3 - a1))) + (x2 / (a4 - a2)) * q32 * (y4 / (a4 - a1))
         sel = (en >= e3) & (en < e4)
-        a1, a2, a3, a4, x = e1[sel], e2[sel], e3[sel], e4[sel], en[sel]
-        out[sel] = 1.0 - (a4 - x) ** 3 / ((a4 - a1) * (a4 - a2) * (a4 - a3))
+        a1, a2, a3, a4, y = e1[sel], e2[sel], e3[sel], e4[sel], e4[sel] - en[sel]
+        out[sel] = 1.0 - (y / (a4 - a1)) * (y / (a4 - a2)) * (y / (a4 - a3))
     else:
         e1, e2, e3 = e
         sel = (en >= e1) & (en < e2)
-        a1, a2, a3, x = e1[sel], e2[sel], e3[sel], en[sel]
-        out[sel] = (x - a1) ** 2 / ((a2 - a1) * (a3 - a1))
+        a1, a2, a3, x = e1[sel], e2[sel], e3[sel], en[sel] - e1[sel]
+        out[sel] = (x / (a2 - a1)) * (x / (a3 - a1))
         sel = (en >= e2) & (en < e3)
-        a1, a2, a3, x = e1[sel], e2[sel], e3[sel], en[sel]
-        out[sel] = 1.0 - (a3 - x) ** 2 / ((a3 - a1) * (a3 - a2))
+        a1, a2, a3, y = e1[sel], e2[sel], e3[sel], e3[sel] - en[sel]
+        out[sel] = 1.0 - (y / (a3 - a1)) * (y / (a3 - a2))
     return out
 
 

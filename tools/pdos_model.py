@@ -26,7 +26,8 @@ def corner_weights(e_sorted, energies):
     4: tetrahedron) for every E of the 1-D array ``energies``: shape ``e_sorted.shape[:-1] + (len(energies), n_corners)``.
     w_c(E) = int_T theta(E - eps) lambda_c / |T| for the linear interpolant eps = sum_c lambda_c e_c; sum_c w_c = n_T(E).  The
     ranges are half-open, the comparisons select the branch and a branch is evaluated only where it was selected, so a zero
-    denominator is never divided by.
+    denominator is never divided by.  As in dos_model every branch is built from ratios in [0, 1] that are formed one by one, so
+    a gap too small for its reciprocal (a subnormal one) never meets a zero: there is no 0 * inf and no 0 / 0 in a selected branch.
     """
     corners = np.asarray(e_sorted, dtype=float)
     energies = np.asarray(energies, dtype=float)
@@ -43,46 +44,46 @@ def corner_weights(e_sorted, energies):
     if n_c == 4:
         e1, e2, e3, e4 = e
         sel = (en >= e1) & (en < e2)
-        a1, a2, a3, a4, en_s = e1[sel], e2[sel], e3[sel], e4[sel], en[sel]
-        e21, e31, e41 = a2 - a1, a3 - a1, a4 - a1
-        x = en_s - a1
-        c = x ** 3 / (4.0 * e21 * e31 * e41)
-        out[sel] = np.stack([c * (4.0 - x * (1.0 / e21 + 1.0 / e31 + 1.0 / e41)), c * x / e21, c * x / e31, c * x / e41], axis=-1)
+        a1, a2, a3, a4, x = e1[sel], e2[sel], e3[sel], e4[sel], en[sel] - e1[sel]
+        q21, q31, q41 = x / (a2 - a1), x / (a3 - a1), x / (a4 - a1)
+        c = 0.25 * q21 * q31 * q41
+        out[sel] = np.stack([c * (4.0 - (q21 + q31 + q41)), c * q21, c * q31, c * q41], axis=-1)
         sel = (en >= e2) & (en < e3)
         a1, a2, a3, a4, en_s = e1[sel], e2[sel], e3[sel], e4[sel], en[sel]
         e31, e41, e32, e42 = a3 - a1, a4 - a1, a3 - a2, a4 - a2
         x1, x2, y3, y4 = en_s - a1, en_s - a2, a3 - en_s, a4 - en_s
-        c1 = x1 * x1 / (4.0 * e41 * e31)
-        c2 = x1 * x2 * y3 / (4.0 * e41 * e32 * e31)
-        c3 = x2 * x2 * y4 / (4.0 * e42 * e32 * e41)
+        p31, p41, p32, p42 = x1 / e31, x1 / e41, x2 / e32, x2 / e42  # from below
+        m31, m32, m41, m42 = y3 / e31, y3 / e32, y4 / e41, y4 / e42  # from above
+        t = 0.25 * p41
+        c1 = t * p31
+        c2 = t * p32 * m31
+        c3 = 0.25 * p42 * p32 * m41
+        c12, c23 = c1 + c2, c2 + c3
+        c123 = c12 + c3
         out[sel] = np.stack([
-            c1 + (c1 + c2) * y3 / e31 + (c1 + c2 + c3) * y4 / e41,
-            c1 + c2 + c3 + (c2 + c3) * y3 / e32 + c3 * y4 / e42,
-            (c1 + c2) * x1 / e31 + (c2 + c3) * x2 / e32,
-            (c1 + c2 + c3) * x1 / e41 + c3 * x2 / e42,
+            c1 + c12 * m31 + c123 * m41,
+            c123 + c23 * m32 + c3 * m42,
+            c12 * p31 + c23 * p32,
+            c123 * p41 + c3 * p42,
         ], axis=-1)
         sel = (en >= e3) & (en < e4)
-        a1, a2, a3, a4, en_s = e1[sel], e2[sel], e3[sel], e4[sel], en[sel]
-        e41, e42, e43 = a4 - a1, a4 - a2, a4 - a3
-        y = a4 - en_s
-        c = y ** 3 / (4.0 * e41 * e42 * e43)
-        out[sel] = np.stack([0.25 - c * y / e41, 0.25 - c * y / e42, 0.25 - c * y / e43,
-                             0.25 - c * (4.0 - y * (1.0 / e41 + 1.0 / e42 + 1.0 / e43))], axis=-1)
+        a1, a2, a3, a4, y = e1[sel], e2[sel], e3[sel], e4[sel], e4[sel] - en[sel]
+        q41, q42, q43 = y / (a4 - a1), y / (a4 - a2), y / (a4 - a3)
+        c = 0.25 * q41 * q42 * q43
+        out[sel] = np.stack([0.25 - c * q41, 0.25 - c * q42, 0.25 - c * q43, 0.25 - c * (4.0 - (q41 + q42 + q43))], axis=-1)
     else:
         e1, e2, e3 = e
         third = 1.0 / 3.0
         sel = (en >= e1) & (en < e2)
-        a1, a2, a3, en_s = e1[sel], e2[sel], e3[sel], en[sel]
-        e21, e31 = a2 - a1, a3 - a1
-        x = en_s - a1
-        c = x * x / (3.0 * e21 * e31)
-        out[sel] = np.stack([c * (3.0 - x * (1.0 / e21 + 1.0 / e31)), c * x / e21, c * x / e31], axis=-1)
+        a1, a2, a3, x = e1[sel], e2[sel], e3[sel], en[sel] - e1[sel]
+        q21, q31 = x / (a2 - a1), x / (a3 - a1)
+        c = third * q21 * q31
+        out[sel] = np.stack([c * (3.0 - (q21 + q31)), c * q21, c * q31], axis=-1)
         sel = (en >= e2) & (en < e3)
-        a1, a2, a3, en_s = e1[sel], e2[sel], e3[sel], en[sel]
-        e31, e32 = a3 - a1, a3 - a2
-        y = a3 - en_s
-        c = y * y / (3.0 * e31 * e32)
-        out[sel] = np.stack([third - c * y / e31, third - c * y / e32, third - c * (3.0 - y * (1.0 / e31 + 1.0 / e32))], axis=-1)
+        a1, a2, a3, y = e1[sel], e2[sel], e3[sel], e3[sel] - en[sel]
+        q31, q32 = y / (a3 - a1), y / (a3 - a2)
+        c = third * q31 * q32
+        out[sel] = np.stack([third - c * q31, third - c * q32, third - c * (3.0 - (q31 + q32))], axis=-1)
     return out
 
 
