@@ -60,6 +60,17 @@ def main():
     print("tetrahedron DOS on the same mesh in %.1f ms: %.6f states below %.3f, peak %.3f states per energy unit at %.3f"
           % (dt * 1e3, result.nos[-1], energies[-1], result.dos[peak], mid[peak]))
 
+    # the Fermi level of the same mesh at half filling (one state per band and cell, no spin factor) and the gap, if there is one:
+    # a search on doubles with the eigenvalues on the GPU, four numbers come back
+    t0 = time.perf_counter()
+    level = model.fermi_level((n, n, n), model.size / 2)
+    dt = time.perf_counter() - t0
+    if level.lower < level.upper:
+        print("Fermi level at half filling in %.1f ms: mu = %.6f in the gap [%.6f, %.6f] of %.6f"
+              % (dt * 1e3, level.mu, level.lower, level.upper, level.upper - level.lower))
+    else:
+        print("Fermi level at half filling in %.1f ms: mu = %.12f (no gap on this mesh), %.12f states below it" % (dt * 1e3, level.mu, level.nos))
+
     # 4. the orbital character of that spectrum: s and p orbitals (the model's sp3 basis, s first on both atoms).  Eigenvectors
     # are reduced to four weights per (k, band) where they are produced; 4 x 401 numbers come back
     if model.size == 8:

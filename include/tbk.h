@@ -262,6 +262,59 @@ int tbk_pdos_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh
  * tbk_get_timing.) */
 int tbk_pdos_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
+/* ---- band edges and the Fermi level of a uniform k mesh (not in the reference) ---------------------------------------------------
+ * mesh, the simplices and the filled fraction n_T(E) of a simplex are those of tbk_dos; N(E) = 1 / (S NK) sum n_T(E) counts states
+ * without a spin factor (csrc/tbk_fermi.hip).  There is no energy grid: the kernel evaluates N at up to 16
+ * arbitrary energies per launch, in registers, and produces per energy the integer
+ *     Q(E) = sum over (cell, band, simplex) of round(n_T(E) 2^40) [e1 <= E < e_top]  +  2^40 * (simplices with e_top <= E),
+ * independent of wave order, of the workgroup count and of the other energies of the launch; N(E) = Q(E) / (2^40 S NK), rounded
+ * twice (|N - exact| <= 4.5e-13 n_orb from the fixed point).
+ *   band edges   emin[b] = min over the mesh points of E[k][b], emax[b] = max: doubles of the eigenvalue array, no arithmetic
+ *   Fermi level  for n_electrons = n in (0, n_orb), target t = n S NK 2^40:
+ *     gap case   n is an integer m and emax[m - 1] < emin[m]: lower = emax[m - 1], upper = emin[m], mu = lower + (upper - lower) / 2,
+ *                N(mu) = m; no kernel pass.  (Fixed point cannot find a band edge: 1 - (y / gap)^3 rounds to 1 at 2^-40 once
+ *                y / gap < 1e-4.)
+ *     otherwise  mu = lower = upper = the double hi of a bracket lo < hi of NEIGHBOURING doubles with Q(lo) < t <= Q(hi), found
+ *                from lo = nextafter(emin[0], -inf), hi = emax[n_orb - 1] in passes of 15 probes that are equidistant in the
+ *                ordered-integer image of the doubles (a bracket around zero first takes one pass at 0 and lo, hi times 2^-256 j,
+ *                j = 1 .. 7): at most 16 passes whatever the scale, and a scaling of all energies by a power of two moves the
+ *                probes with it.  N(mu) is the kernel's value at hi.
+ *     Q against t  exactly, in integers: Q is kept as (whole, rem) with Q = whole 2^40 + rem, rem < 2^40 -- whole = count + the
+ *                fraction words' carry -- and t is replaced by the integer ceil(t) in the same form (Q is an integer, so
+ *                Q >= t <=> Q >= ceil(t)); Q >= t <=> whole > t.whole or (whole == t.whole and rem >= t.rem).  S NK n_orb 2^40 does
+ *                not fit 64 bits; no product of the two words is formed.  Several handles: the pairs are added, with carry.
+ *     flat band  across a band that is constant over the mesh N jumps; for n inside the jump mu is the energy of the jump and
+ *                N(mu) the value above it.  Not an error.
+ * Range: as for tbk_dos, eigenvalues and probe energies must stay below 2^969 in magnitude (not checked).
+ * Argument errors (TBK_ERR_ARGUMENT): dim not in {2, 3}, a mesh entry < 1, 2^31 mesh points or more, n_electrons not finite or
+ * outside (0, n_orb), a probe energy that is not finite, n_p < 1, a NULL pointer, a k.p handle, a handle given twice.  Host buffers;
+ * synchronous. */
+
+/* The probe kernel alone on eigenvalues the caller brings (E[NK][n_orb] in mesh order, every row ascending): nos_out[j] = N(energies[j])
+ * for n_p >= 1 finite energies in any order, walked 16 per launch.  The value at an energy does not depend on the others. */
+int tbk_nos_at_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* energies,
+                                int64_t n_p, double* nos_out);
+/* emin_out / emax_out: double [n_orb] */
+int tbk_band_edges_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double* emin_out,
+                                    double* emax_out);
+/* out: double [4] = mu, lower, upper, N(mu); passes_out (may be NULL): the kernel passes of the search, 0 in the gap case */
+int tbk_fermi_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double n_electrons, double* out,
+                               int32_t* passes_out);
+/* The whole call: the mesh is evaluated as in tbk_dos (fold hint, tbk_eigenval_check in front of the kernels), and its eigenvalues
+ * stay in device memory across all passes. */
+int tbk_band_edges(tbk_model* m, const int32_t* mesh, double* emin_out, double* emax_out);
+int tbk_fermi(tbk_model* m, const int32_t* mesh, double n_electrons, double* out);
+/* On several devices from one process: the slabs of tbk_dos_multi.  Every handle keeps its slab's eigenvalues and probes them in
+ * every pass (its periodic neighbour plane is read by its last cells and left out of its band edges); the host adds the handles'
+ * integer pairs and takes the min / max of their edges, so for given eigenvalues the handle count changes no bit -- the
+ * eigenvalues themselves differ at rounding level between handle counts, as for tbk_dos_multi.  The calling thread holds every
+ * handle for the whole call and drives them all: the handles must be distinct. */
+int tbk_band_edges_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, double* emin_out, double* emax_out);
+int tbk_fermi_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, double n_electrons, double* out);
+/* calls = this handle's tbk_fermi / tbk_band_edges calls, passes = the kernel passes of its searches, ms = the summed HIP-event time
+ * of its probe and band-edge kernels in the calls made while TBK_OPT_TIMING was on; reset = 1 clears. */
+int tbk_fermi_timing(tbk_model* m, double* ms, int64_t* calls, int64_t* passes, int reset);
+
 /* ---- k.p models (kdotp.py:51-100): H(k) = sum_p prod_d k_d^powers[p][d] * coeffs[p] ------- */
 int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, const int32_t* powers,
                      const double* coeffs, tbk_kdotp** out);

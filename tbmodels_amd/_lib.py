@@ -75,6 +75,14 @@ SIGNATURES = {
     "tbk_pdos": (_c_int, [_vp, _vp, _vp, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp]),
     "tbk_pdos_multi": (_c_int, [_vp, _c_int, _vp, _vp, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp]),
     "tbk_pdos_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
+    "tbk_nos_at_from_eigenvalues": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, _vp, _c_i64, _vp]),
+    "tbk_band_edges_from_eigenvalues": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, _vp, _vp]),
+    "tbk_fermi_from_eigenvalues": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, ctypes.c_double, _vp, ctypes.POINTER(ctypes.c_int32)]),
+    "tbk_band_edges": (_c_int, [_vp, _vp, _vp, _vp]),
+    "tbk_fermi": (_c_int, [_vp, _vp, ctypes.c_double, _vp]),
+    "tbk_band_edges_multi": (_c_int, [_vp, _c_int, _vp, _vp, _vp]),
+    "tbk_fermi_multi": (_c_int, [_vp, _c_int, _vp, ctypes.c_double, _vp]),
+    "tbk_fermi_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _c_int]),
     "tbk_kdotp_create": (_c_int, [_c_int, _c_int, _c_int, _c_i64, _vp, _vp, _pp]),
     "tbk_kdotp_destroy": (None, [_vp]),
     "tbk_kdotp_hamilton": (_c_int, [_vp, _vp, _c_i64, _vp]),

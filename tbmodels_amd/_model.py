@@ -33,11 +33,15 @@ try:  # fast content hash for the staging fingerprint; zlib is the fallback
 except ImportError:  # pragma: no cover
     _xxhash = None
 
-__all__ = ("Model", "DensityOfStates", "ProjectedDensityOfStates")
+__all__ = ("Model", "DensityOfStates", "ProjectedDensityOfStates", "BandEdges", "FermiLevel")
 
 #: what ``Model.dos`` returns: the energy grid (NE,), the number of states at its points (NE,), their difference quotient (NE - 1,)
 DensityOfStates = co.namedtuple("DensityOfStates", ("energies", "nos", "dos"))
 ProjectedDensityOfStates = co.namedtuple("ProjectedDensityOfStates", ("energies", "nos", "dos"))
+#: what ``Model.band_edges`` returns: per band the minimum and the maximum over the mesh, (size,) each
+BandEdges = co.namedtuple("BandEdges", ("emin", "emax"))
+#: what ``Model.fermi_level`` returns: floats; ``lower < upper`` exactly when the mesh has a gap at the filling asked for
+FermiLevel = co.namedtuple("FermiLevel", ("mu", "lower", "upper", "nos"))
 
 
 def _devices_from_env():
@@ -778,10 +782,10 @@ class Model:
             )
         return (eig[0], vec[0]) if single else (eig, vec)
 
-    def _dos_arguments(self, mesh, energies):
-        """The checks ``dos`` and ``pdos`` share: ``(mesh int32 (dim,), grid float64 (NE,), mean step)`` or ``ValueError``."""
+    def _mesh_argument(self, mesh, what="dos"):
+        """The mesh check ``dos``, ``pdos``, ``band_edges`` and ``fermi_level`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
         if self.dim not in (2, 3):
-            raise ValueError("dos needs a 2- or 3-dimensional model, this one has dimension {}".format(self.dim))
+            raise ValueError("{} needs a 2- or 3-dimensional model, this one has dimension {}".format(what, self.dim))
         try:
             mesh_list = list(mesh)
         except TypeError:
@@ -796,7 +800,11 @@ class Model:
         mesh_array = np.array(mesh_list, dtype=np.int64)
         if int(np.prod(mesh_array, dtype=object)) >= 2 ** 31:
             raise ValueError("the mesh has 2^31 points or more")
-        mesh_array = np.ascontiguousarray(mesh_array, dtype=np.int32)
+        return np.ascontiguousarray(mesh_array, dtype=np.int32)
+
+    def _dos_arguments(self, mesh, energies):
+        """The checks ``dos`` and ``pdos`` share: ``(mesh int32 (dim,), grid float64 (NE,), mean step)`` or ``ValueError``."""
+        mesh_array = self._mesh_argument(mesh)
         grid = np.array(energies, dtype=np.float64)
         if grid.ndim != 1 or grid.shape[0] < 2:
             raise ValueError("energies must be a 1-D array of at least two points")
@@ -893,6 +901,52 @@ class Model:
                                           float(grid[0]), step, grid.shape[0], _lib.ptr(nos))
             )
         return ProjectedDensityOfStates(grid, nos, np.diff(nos, axis=1) / step)
+
+    def band_edges(self, mesh):
+        """
+        Minimum and maximum of every band over a uniform k mesh, computed on the GPU from eigenvalues that never leave it.  Not in
+        the reference.  ``mesh`` is that of :meth:`dos`.  Returns the named tuple ``(emin, emax)`` of two ``(size,)`` arrays:
+        ``emin[b]`` / ``emax[b]`` is the smallest / largest b-th ascending eigenvalue among the mesh points -- band widths, and for
+        ``m`` filled bands the valence-band top ``emax[m - 1]``, the conduction-band bottom ``emin[m]`` and the gap of the mesh.
+        """
+        mesh_array = self._mesh_argument(mesh, "band_edges")
+        emin = np.empty(self.size, dtype=np.float64)
+        emax = np.empty(self.size, dtype=np.float64)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigenval
+            handles, n_handles = self._handle_array()
+            _lib.check(_lib.lib().tbk_band_edges_multi(handles, n_handles, _lib.ptr(mesh_array), _lib.ptr(emin), _lib.ptr(emax)))
+        return BandEdges(emin, emax)
+
+    def fermi_level(self, mesh, n_electrons):
+        """
+        The Fermi level of a uniform k mesh for ``n_electrons`` states per unit cell by the linear tetrahedron method, found on the
+        GPU from eigenvalues that never leave it.  Not in the reference.
+
+        ``mesh`` and the simplices are those of :meth:`dos`, and states are counted as its ``nos`` counts them (no spin factor):
+        ``n_electrons`` is a real number inside ``(0, size)``.  Returns the named tuple ``(mu, lower, upper, nos)`` of floats.
+
+        * ``n_electrons`` is an integer ``m`` and the mesh has a gap above band ``m - 1``: ``lower`` is the top of that band,
+          ``upper`` the bottom of the next (the values of :meth:`band_edges`), ``mu`` their midpoint and ``nos == m``.
+        * Otherwise ``mu == lower == upper`` is the smallest double at which the number of states reaches ``n_electrons``, found by
+          a search on doubles (no energy grid is involved), and ``nos`` is the number of states there.  Across a band that is
+          constant over the mesh the number of states jumps: for ``n_electrons`` inside the jump ``mu`` is that band's energy.
+
+        ``lower < upper`` exactly when the result came from the gap.  With several ``devices`` every device keeps the eigenvalues
+        of a slab of the mesh along its first axis.
+        """
+        mesh_array = self._mesh_argument(mesh, "fermi_level")
+        if isinstance(n_electrons, (bool, np.bool_)) or not isinstance(n_electrons, (int, float, np.integer, np.floating)):
+            raise ValueError("n_electrons must be a real number, got {!r}".format(n_electrons))
+        count = float(n_electrons)
+        if not np.isfinite(count) or not 0.0 < count < self.size:
+            raise ValueError("n_electrons must lie inside (0, {}), got {!r}".format(self.size, n_electrons))
+        out = np.empty(4, dtype=np.float64)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigenval
+            handles, n_handles = self._handle_array()
+            _lib.check(_lib.lib().tbk_fermi_multi(handles, n_handles, _lib.ptr(mesh_array), count, _lib.ptr(out)))
+        return FermiLevel(float(out[0]), float(out[1]), float(out[2]), float(out[3]))
 
     def construct_kdotp(self, k, order):
         """

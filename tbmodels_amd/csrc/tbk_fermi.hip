@@ -1,0 +1,748 @@
+// tbk_fermi.hip -- the number of states N(E) of a uniform, periodic k mesh at a handful of ARBITRARY energies, the per-band minimum
+// and maximum over the mesh, and the Fermi level for n electrons per cell: a search on doubles that refines a bracket with the
+// first kernel until it is one double wide.  Not in the reference; DESIGN.md section 12 has the quantities, the comparison rule
+// and the measurements, tools/fermi_model.py is the exact statement the tests compare with.
+//
+//   E[NK][n_orb]    ascending eigenvalues per mesh point, mesh order (last axis fastest): what tbk_dos.hip reads
+//   N(E_m)          = Q(E_m) / (2^40 S NK),  Q(E) = sum over (cell, band, simplex) of round(n_T(E) 2^40) for e1 <= E < e_top
+//                                                   + 2^40 * (number of simplices with e_top <= E)
+//
+// nos_probe_kernel has the work partition and the corner loads of dos_accumulate_kernel (tbk_dos.hip): a work item is one
+// (cell, band) pair, band fastest, a wave reads 64 consecutive doubles per corner.  There is no energy grid, no search on one and no
+// LDS bins: the up to 16 probe energies are kernel arguments, and every thread keeps one 64-bit fixed-point sum and one count per
+// probe in registers (every loop over the probes is unrolled; no accumulator is indexed dynamically).  Per simplex the corners are
+// sorted, count[m] += (E_m >= e_top), and n_T is evaluated for the probes with e1 <= E_m < e_top only; the six reciprocals of the
+// scaled corner gaps are taken once per simplex and only if some probe of the wave's lanes needs them.  The branch arithmetic is
+// that of dos_tetrahedron / dos_triangle, expression for expression.
+//
+// Reproducibility.  No floating-point sum crosses a thread: the wave adds its lanes' integers with shuffles, the workgroup adds its
+// waves' with integer LDS atomics, every workgroup stores its row [16] with plain stores, and a second kernel sums the rows, the
+// high 44 and low 20 bits of every 64-bit sum apart (dos_reduce_kernel's split).  Per probe the result is the exact integer triple
+// (count, high, low): independent of wave order, of the workgroup count and of which other probes shared the launch.
+// Overflow: the bound of tbk_dos.hip -- a workgroup takes at most DOS_MAX_ITEMS items, so one of its sums is below 6 * 2^60.
+//
+// band_edges_kernel: min / max per band over the mesh rows.  Both are order independent, so fmin / fmax partials per workgroup and
+// a second step give the same bits whatever the launch shape.
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "tbk_dos_common.h"
+
+namespace {
+
+constexpr int FERMI_THREADS = 256;
+constexpr int FERMI_PROBES = 16;      // probe energies per launch
+constexpr int FERMI_SEARCH_M = 15;    // probes per pass of the search: 16 sub-intervals, 4 bits of the ordered image per pass
+constexpr int FERMI_EDGE_WG = 256;    // row workgroups of the band-edge kernel, at most
+
+struct FermiProbes {
+    double e[FERMI_PROBES];
+};
+
+__device__ __forceinline__ void fermi_sort2(double& a, double& b) {
+    const double lo = fmin(a, b), hi = fmax(a, b);
+    a = lo;
+    b = hi;
+}
+
+// one tetrahedron at every probe (half-open ranges, the comparisons on the unscaled numbers select the branch, every
+// ratio in [0, 1] is formed on its own from energies scaled by DOS_GAP_SCALE: tbk_dos_common.h)
+__device__ __forceinline__ void fermi_tetrahedron(double e1, double e2, double e3, double e4, const FermiProbes& p,
+                                                  unsigned long long (&frac)[FERMI_PROBES], unsigned (&count)[FERMI_PROBES]) {
+    fermi_sort2(e1, e2);
+    fermi_sort2(e3, e4);
+    fermi_sort2(e1, e3);
+    fermi_sort2(e2, e4);
+    fermi_sort2(e2, e3);
+    bool inside = false;
+#pragma unroll
+    for (int m = 0; m < FERMI_PROBES; ++m) {
+        count[m] += p.e[m] >= e4 ? 1u : 0u;
+        inside = inside || (p.e[m] >= e1 && p.e[m] < e4);
+    }
+    if (!inside) return;
+    const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE, s4 = e4 * DOS_GAP_SCALE;
+    const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r41 = 1.0 / (s4 - s1), r32 = 1.0 / (s3 - s2), r42 = 1.0 / (s4 - s2),
+                 r43 = 1.0 / (s4 - s3);
+#pragma unroll
+    for (int m = 0; m < FERMI_PROBES; ++m) {
+        const double E = p.e[m];
+        if (E >= e1 && E < e4) {
+            const double Es = E * DOS_GAP_SCALE;
+            double n;
+            if (E < e2) {
+                const double x = Es - s1;
+                n = (x * r21) * (x * r31) * (x * r41);
+            } else if (E < e3) {
+                const double x1 = Es - s1, x2 = Es - s2, y3 = s3 - Es, y4 = s4 - Es;
+                const double q32 = x2 * r32;
+                n = (x1 * r41) * (x1 * r31 + q32 * (y3 * r31)) + (x2 * r42) * q32 * (y4 * r41);
+            } else {
+                const double y = s4 - Es;
+                n = 1.0 - (y * r41) * (y * r42) * (y * r43);
+            }
+            frac[m] += dos_fixed(n);
+        }
+    }
+}
+
+__device__ __forceinline__ void fermi_triangle(double e1, double e2, double e3, const FermiProbes& p, unsigned long long (&frac)[FERMI_PROBES],
+                                               unsigned (&count)[FERMI_PROBES]) {
+    fermi_sort2(e1, e2);
+    fermi_sort2(e2, e3);
+    fermi_sort2(e1, e2);
+    bool inside = false;
+#pragma unroll
+    for (int m = 0; m < FERMI_PROBES; ++m) {
+        count[m] += p.e[m] >= e3 ? 1u : 0u;
+        inside = inside || (p.e[m] >= e1 && p.e[m] < e3);
+    }
+    if (!inside) return;
+    const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE;
+    const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r32 = 1.0 / (s3 - s2);
+#pragma unroll
+    for (int m = 0; m < FERMI_PROBES; ++m) {
+        const double E = p.e[m];
+        if (E >= e1 && E < e3) {
+            const double Es = E * DOS_GAP_SCALE;
+            double n;
+            if (E < e2) {
+                const double x = Es - s1;
+                n = (x * r21) * (x * r31);
+            } else {
+                const double y = s3 - Es;
+                n = 1.0 - (y * r31) * (y * r32);
+            }
+            frac[m] += dos_fixed(n);
+        }
+    }
+}
+
+// grid: workgroups.  part_g / count_g: [gridDim.x][FERMI_PROBES]; every element is written by exactly one workgroup.  Probe slots
+// the caller does not use repeat its last energy.
+template <int DIM>
+__global__ void __launch_bounds__(FERMI_THREADS) nos_probe_kernel(const double* __restrict__ E, DosGeom g, FermiProbes p,
+                                                                  unsigned long long* __restrict__ part_g, unsigned* __restrict__ count_g) {
+    __shared__ unsigned long long wg_frac[FERMI_PROBES];
+    __shared__ unsigned wg_count[FERMI_PROBES];
+    const int tid = (int)threadIdx.x;
+    if (tid < FERMI_PROBES) {
+        wg_frac[tid] = 0ull;
+        wg_count[tid] = 0u;
+    }
+    __syncthreads();
+    unsigned long long frac[FERMI_PROBES];
+    unsigned count[FERMI_PROBES];
+#pragma unroll
+    for (int m = 0; m < FERMI_PROBES; ++m) {
+        frac[m] = 0ull;
+        count[m] = 0u;
+    }
+
+    const int64_t first = (int64_t)blockIdx.x * g.items_per_wg;
+    const int64_t last = min(first + g.items_per_wg, g.items);
+    for (int64_t it = first + tid; it < last; it += FERMI_THREADS) {
+        const int64_t cell64 = it / g.n_orb;
+        const int band = (int)(it - cell64 * g.n_orb);
+        int c = (int)cell64;  // NK < 2^31 (checked by the launcher)
+        const int i2 = c % g.n2;
+        c /= g.n2;
+        const int i1 = c % g.n1;
+        const int i0 = c / g.n1;  // < n0_cells
+        const int j0 = i0 + 1 == g.n0_planes ? 0 : i0 + 1;
+        const int j1 = i1 + 1 == g.n1 ? 0 : i1 + 1;
+        const int j2 = i2 + 1 == g.n2 ? 0 : i2 + 1;
+        auto at = [&](int a0, int a1, int a2) -> double {
+            const int64_t k = ((int64_t)a0 * g.n1 + a1) * g.n2 + a2;
+            return E[k * g.n_orb + band];
+        };
+        if (DIM == 3) {
+            // corner c_xyz: x, y, z = step along axis 0, 1, 2
+            const double c000 = at(i0, i1, i2), c100 = at(j0, i1, i2), c010 = at(i0, j1, i2), c110 = at(j0, j1, i2);
+            const double c001 = at(i0, i1, j2), c101 = at(j0, i1, j2), c011 = at(i0, j1, j2), c111 = at(j0, j1, j2);
+            // the six orders (a, b, c) of the axes: corners 0, e_a, e_a + e_b, e_a + e_b + e_c -- the list of tbk_dos.hip.  A loop
+            // that is not unrolled, so that the probe code exists once: the two middle corners are selected by a uniform index
+#pragma unroll 1
+            for (int s = 0; s < 6; ++s) {
+                const double ca = s < 2 ? c100 : s < 4 ? c010 : c001;
+                const double cb = s == 0 || s == 2 ? c110 : s == 1 || s == 4 ? c101 : c011;
+                fermi_tetrahedron(c000, ca, cb, c111, p, frac, count);
+            }
+        } else {
+            const double c00 = at(i0, i1, 0), c10 = at(j0, i1, 0), c01 = at(i0, j1, 0), c11 = at(j0, j1, 0);
+#pragma unroll 1
+            for (int s = 0; s < 2; ++s) fermi_triangle(c00, s == 0 ? c10 : c01, c11, p, frac, count);
+        }
+    }
+    // the workgroup's sums, in integers: across the wave with shuffles, across the waves with LDS integer atomics
+#pragma unroll
+    for (int m = 0; m < FERMI_PROBES; ++m) {
+        unsigned long long f = frac[m];
+        unsigned n = count[m];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            f += __shfl_xor(f, off);
+            n += __shfl_xor(n, off);
+        }
+        if ((tid & 63) == 0) {
+            atomicAdd(&wg_frac[m], f);
+            atomicAdd(&wg_count[m], n);
+        }
+    }
+    __syncthreads();
+    if (tid < FERMI_PROBES) {
+        part_g[(int64_t)blockIdx.x * FERMI_PROBES + tid] = wg_frac[tid];
+        count_g[(int64_t)blockIdx.x * FERMI_PROBES + tid] = wg_count[tid];
+    }
+}
+
+// one workgroup: 16 row lanes per probe walk the workgroups' rows, the high and low part of every 64-bit sum apart (neither sum
+// overflows up to 2^20 rows), and meet in integer LDS atomics.  sums[m] = {count, high, low}
+__global__ void __launch_bounds__(FERMI_THREADS) nos_probe_reduce_kernel(const unsigned long long* __restrict__ part_g,
+                                                                         const unsigned* __restrict__ count_g, int n_wg,
+                                                                         unsigned long long* __restrict__ sums) {
+    __shared__ unsigned long long total[FERMI_PROBES * 3];
+    const int tid = (int)threadIdx.x;
+    if (tid < FERMI_PROBES * 3) total[tid] = 0ull;
+    __syncthreads();
+    const int m = tid % FERMI_PROBES;
+    unsigned long long hi = 0, lo = 0, c = 0;
+    for (int wg = tid / FERMI_PROBES; wg < n_wg; wg += FERMI_THREADS / FERMI_PROBES) {
+        const unsigned long long v = part_g[(int64_t)wg * FERMI_PROBES + m];
+        hi += v >> DOS_SPLIT_BITS;
+        lo += v & ((1ull << DOS_SPLIT_BITS) - 1);
+        c += (unsigned long long)count_g[(int64_t)wg * FERMI_PROBES + m];
+    }
+    atomicAdd(&total[m * 3 + 0], c);
+    atomicAdd(&total[m * 3 + 1], hi);
+    atomicAdd(&total[m * 3 + 2], lo);
+    __syncthreads();
+    if (tid < FERMI_PROBES * 3) sums[tid] = total[tid];
+}
+
+// Per-band minimum and maximum over `rows` rows of E[rows][n_orb].  Up to 256 orbitals a workgroup reads 256 / n_orb whole rows per
+// step (contiguous doubles; a thread keeps its band), above that grid.y walks the bands in blocks of 256.  grid.x workgroups share
+// the rows; pmin / pmax: [gridDim.x][n_orb].
+__global__ void __launch_bounds__(FERMI_THREADS) band_edges_kernel(const double* __restrict__ E, int64_t rows, int n_orb,
+                                                                   double* __restrict__ pmin, double* __restrict__ pmax) {
+    __shared__ double s_min[FERMI_THREADS], s_max[FERMI_THREADS];
+    const int tid = (int)threadIdx.x;
+    const int per_step = n_orb <= FERMI_THREADS ? FERMI_THREADS / n_orb : 1;  // rows per step
+    const int width = n_orb <= FERMI_THREADS ? n_orb : min(FERMI_THREADS, n_orb - (int)blockIdx.y * FERMI_THREADS);
+    const int lane_row = tid / width, lane_band = tid - lane_row * width;
+    const int band = (int)blockIdx.y * FERMI_THREADS + lane_band;
+    double lo = INFINITY, hi = -INFINITY;
+    if (lane_row < per_step) {
+        for (int64_t r = (int64_t)blockIdx.x * per_step + lane_row; r < rows; r += (int64_t)gridDim.x * per_step) {
+            const double e = E[r * n_orb + band];
+            lo = fmin(lo, e);
+            hi = fmax(hi, e);
+        }
+    }
+    s_min[tid] = lo;
+    s_max[tid] = hi;
+    __syncthreads();
+    if (tid < width) {
+        for (int q = 1; q < per_step; ++q) {
+            lo = fmin(lo, s_min[q * width + tid]);
+            hi = fmax(hi, s_max[q * width + tid]);
+        }
+        pmin[(int64_t)blockIdx.x * n_orb + band] = lo;
+        pmax[(int64_t)blockIdx.x * n_orb + band] = hi;
+    }
+}
+
+// one thread per band over the workgroups' partials
+__global__ void __launch_bounds__(FERMI_THREADS) band_edges_reduce_kernel(const double* __restrict__ pmin, const double* __restrict__ pmax, int n_wg,
+                                                                          int n_orb, double* __restrict__ emin, double* __restrict__ emax) {
+    const int band = (int)blockIdx.x * FERMI_THREADS + (int)threadIdx.x;
+    if (band >= n_orb) return;
+    double lo = INFINITY, hi = -INFINITY;
+    for (int wg = 0; wg < n_wg; ++wg) {
+        lo = fmin(lo, pmin[(int64_t)wg * n_orb + band]);
+        hi = fmax(hi, pmax[(int64_t)wg * n_orb + band]);
+    }
+    emin[band] = lo;
+    emax[band] = hi;
+}
+
+// ---- host: one slab of the mesh on one device ----------------------------------------------------------------------------------
+struct FermiLaunch {
+    DosGeom g;
+    int n_wg = 0, edge_wg = 0;
+    int64_t rows = 0;  // mesh rows of this slab's own cells (without the periodic neighbour plane)
+    size_t off_count = 0, off_sums = 0, off_pmin = 0, off_pmax = 0, off_emin = 0, off_emax = 0, ws_bytes = 0;
+};
+
+// dim in {2, 3}; cells0 cells along axis 0 out of planes0 planes held in E -- the partition of dos_plan (tbk_dos.hip)
+int fermi_plan(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb, FermiLaunch* out) {
+    FermiLaunch L;
+    L.g.n0_cells = (int)cells0;
+    L.g.n0_planes = (int)planes0;
+    L.g.n1 = mesh[1];
+    L.g.n2 = dim == 3 ? mesh[2] : 1;
+    L.g.n_orb = n_orb;
+    L.rows = cells0 * L.g.n1 * L.g.n2;
+    L.g.items = L.rows * n_orb;
+    int64_t n_wg = std::min<int64_t>((L.g.items + FERMI_THREADS - 1) / FERMI_THREADS, 1024);
+    n_wg = std::max<int64_t>(n_wg, (L.g.items + DOS_MAX_ITEMS - 1) / DOS_MAX_ITEMS);
+    TBK_ARG(n_wg <= (int64_t(1) << DOS_SPLIT_BITS), "mesh x orbitals too large for one Fermi-level call");
+    L.g.items_per_wg = (L.g.items + n_wg - 1) / n_wg;
+    L.n_wg = (int)((L.g.items + L.g.items_per_wg - 1) / L.g.items_per_wg);
+    const int per_step = n_orb <= FERMI_THREADS ? FERMI_THREADS / n_orb : 1;
+    L.edge_wg = (int)std::min<int64_t>(FERMI_EDGE_WG, (L.rows + per_step - 1) / per_step);
+    L.off_count = dos_align256((size_t)L.n_wg * FERMI_PROBES * sizeof(unsigned long long));
+    L.off_sums = L.off_count + dos_align256((size_t)L.n_wg * FERMI_PROBES * sizeof(unsigned));
+    L.off_pmin = L.off_sums + dos_align256((size_t)FERMI_PROBES * 3 * sizeof(unsigned long long));
+    const size_t partial = dos_align256((size_t)L.edge_wg * (size_t)n_orb * sizeof(double)), edge = dos_align256((size_t)n_orb * sizeof(double));
+    L.off_pmax = L.off_pmin + partial;
+    L.off_emin = L.off_pmax + partial;
+    L.off_emax = L.off_emin + edge;
+    L.ws_bytes = L.off_emax + edge;
+    *out = L;
+    return TBK_OK;
+}
+
+// Q(E) of include/tbk.h as (whole, rem): Q = whole * 2^40 + rem, rem < 2^40.  Sums of them are exact.
+struct FermiCount {
+    unsigned long long whole = 0, rem = 0;
+    void add(const FermiCount& o) {
+        rem += o.rem;
+        whole += o.whole + (rem >> DOS_FRAC_BITS);
+        rem &= (1ull << DOS_FRAC_BITS) - 1;
+    }
+    bool at_least(const FermiCount& t) const { return whole > t.whole || (whole == t.whole && rem >= t.rem); }
+};
+
+FermiCount fermi_count(const unsigned long long* triple) {  // {count, high, low} of nos_probe_reduce_kernel
+    const unsigned long long mask = (1ull << DOS_SPLIT_BITS) - 1;
+    FermiCount q;
+    q.rem = ((triple[1] & mask) << DOS_SPLIT_BITS) + triple[2];  // < 2^41
+    q.whole = triple[0] + (triple[1] >> DOS_SPLIT_BITS) + (q.rem >> DOS_FRAC_BITS);
+    q.rem &= (1ull << DOS_FRAC_BITS) - 1;
+    return q;
+}
+
+// N = Q / (2^40 simplices): the 86-bit integer is rounded to double once, the division once more
+double fermi_nos(const FermiCount& q, int64_t simplices) {
+    const unsigned __int128 v = ((unsigned __int128)q.whole << DOS_FRAC_BITS) + q.rem;
+    return std::ldexp((double)v, -DOS_FRAC_BITS) / (double)simplices;
+}
+
+// the smallest integer >= n_electrons * simplices * 2^40 (n_electrons > 0 finite, simplices < 2^34): Q >= t  <=>  Q >= ceil(t)
+FermiCount fermi_target(double n_electrons, int64_t simplices) {
+    int exp2 = 0;
+    const double mant = std::frexp(n_electrons, &exp2);  // n = mant * 2^exp2, mant in [0.5, 1)
+    const unsigned __int128 prod = (unsigned __int128)(unsigned long long)std::ldexp(mant, 53) * (unsigned __int128)(unsigned long long)simplices;
+    const int shift = exp2 - 53 + DOS_FRAC_BITS;  // t = prod * 2^shift, prod < 2^87
+    unsigned __int128 t;
+    if (shift >= 0)
+        t = prod << shift;  // n < n_orb <= 2^12: t < 2^86
+    else if (-shift >= 127)
+        t = 1;
+    else
+        t = (prod >> -shift) + ((prod & (((unsigned __int128)1 << -shift) - 1)) != 0 ? 1 : 0);
+    FermiCount q;
+    q.whole = (unsigned long long)(t >> DOS_FRAC_BITS);
+    q.rem = (unsigned long long)(t & (((unsigned __int128)1 << DOS_FRAC_BITS) - 1));
+    return q;
+}
+
+struct FermiSlab {
+    tbk_model* m = nullptr;  // NULL: eigenvalues the caller brought
+    int device = 0, dim = 0;
+    hipStream_t stream = nullptr;
+    FermiLaunch L;
+    const double* d_E = nullptr;
+    char* d_ws = nullptr;
+    std::vector<double> h_k;  // the mesh's k list until the eigenvalues are checked
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool timed = false;
+    double ms = 0.0;
+    unsigned long long h_sums[FERMI_PROBES * 3];
+
+    void start() {
+        if (timed) (void)hipEventRecord(ev[0], stream);
+    }
+    void stop() {
+        if (timed) (void)hipEventRecord(ev[1], stream);
+    }
+    void collect_time() {  // after a synchronisation of the stream
+        float t = 0.f;
+        if (timed && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) ms += (double)t;
+    }
+};
+
+// enqueue: N at n probes (1 .. 16) of this slab's cells -> h_sums, behind the stream
+int fermi_probe_enqueue(FermiSlab& s, const double* energies, int n) {
+    FermiProbes p;
+    for (int m = 0; m < FERMI_PROBES; ++m) p.e[m] = energies[std::min(m, n - 1)];
+    TBK_HIP(hipSetDevice(s.device));
+    auto* part_g = reinterpret_cast<unsigned long long*>(s.d_ws);
+    auto* count_g = reinterpret_cast<unsigned*>(s.d_ws + s.L.off_count);
+    auto* sums = reinterpret_cast<unsigned long long*>(s.d_ws + s.L.off_sums);
+    s.start();
+    if (s.dim == 3)
+        hipLaunchKernelGGL(nos_probe_kernel<3>, dim3((unsigned)s.L.n_wg), dim3(FERMI_THREADS), 0, s.stream, s.d_E, s.L.g, p, part_g, count_g);
+    else
+        hipLaunchKernelGGL(nos_probe_kernel<2>, dim3((unsigned)s.L.n_wg), dim3(FERMI_THREADS), 0, s.stream, s.d_E, s.L.g, p, part_g, count_g);
+    TBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(nos_probe_reduce_kernel, dim3(1), dim3(FERMI_THREADS), 0, s.stream, part_g, count_g, s.L.n_wg, sums);
+    TBK_HIP(hipGetLastError());
+    s.stop();
+    TBK_HIP(hipMemcpyAsync(s.h_sums, sums, sizeof(s.h_sums), hipMemcpyDeviceToHost, s.stream));
+    return TBK_OK;
+}
+
+// Q at n probes over all slabs: every slab's kernels are enqueued first, then every stream is waited for; the host adds the integers
+int fermi_probe(std::vector<FermiSlab>& slabs, const double* energies, int n, FermiCount* q) {
+    for (FermiSlab& s : slabs) TBK_CHECK(fermi_probe_enqueue(s, energies, n));
+    for (int m = 0; m < n; ++m) q[m] = FermiCount();
+    for (FermiSlab& s : slabs) {
+        TBK_HIP(hipSetDevice(s.device));
+        TBK_HIP(hipStreamSynchronize(s.stream));
+        s.collect_time();
+        for (int m = 0; m < n; ++m) q[m].add(fermi_count(s.h_sums + 3 * m));
+    }
+    return TBK_OK;
+}
+
+// emin / emax [n_orb] over all slabs
+int fermi_edges(std::vector<FermiSlab>& slabs, int n_orb, double* emin, double* emax) {
+    std::vector<double> share((size_t)slabs.size() * 2 * (size_t)n_orb);
+    for (size_t i = 0; i < slabs.size(); ++i) {
+        FermiSlab& s = slabs[i];
+        TBK_HIP(hipSetDevice(s.device));
+        auto* pmin = reinterpret_cast<double*>(s.d_ws + s.L.off_pmin);
+        auto* pmax = reinterpret_cast<double*>(s.d_ws + s.L.off_pmax);
+        auto* d_min = reinterpret_cast<double*>(s.d_ws + s.L.off_emin);
+        auto* d_max = reinterpret_cast<double*>(s.d_ws + s.L.off_emax);
+        const dim3 grid((unsigned)s.L.edge_wg, (unsigned)((n_orb + FERMI_THREADS - 1) / FERMI_THREADS));
+        s.start();
+        hipLaunchKernelGGL(band_edges_kernel, grid, dim3(FERMI_THREADS), 0, s.stream, s.d_E, s.L.rows, n_orb, pmin, pmax);
+        TBK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(band_edges_reduce_kernel, dim3(grid.y), dim3(FERMI_THREADS), 0, s.stream, pmin, pmax, s.L.edge_wg, n_orb, d_min, d_max);
+        TBK_HIP(hipGetLastError());
+        s.stop();
+        double* h = share.data() + i * 2 * (size_t)n_orb;
+        TBK_HIP(hipMemcpyAsync(h, d_min, (size_t)n_orb * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+        TBK_HIP(hipMemcpyAsync(h + n_orb, d_max, (size_t)n_orb * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+    }
+    for (size_t i = 0; i < slabs.size(); ++i) {
+        FermiSlab& s = slabs[i];
+        TBK_HIP(hipSetDevice(s.device));
+        TBK_HIP(hipStreamSynchronize(s.stream));
+        s.collect_time();
+        const double* h = share.data() + i * 2 * (size_t)n_orb;
+        for (int b = 0; b < n_orb; ++b) {
+            emin[b] = i == 0 ? h[b] : std::fmin(emin[b], h[b]);
+            emax[b] = i == 0 ? h[n_orb + b] : std::fmax(emax[b], h[n_orb + b]);
+        }
+    }
+    return TBK_OK;
+}
+
+// ---- the search on doubles -------------------------------------------------------------------------------------------------------
+// the ordered-integer image of the doubles: x < y  <=>  key(x) < key(y) (-0.0 is the double in front of +0.0)
+unsigned long long fermi_key(double x) {
+    unsigned long long b;
+    std::memcpy(&b, &x, sizeof(b));
+    return (b >> 63) ? ~b : b | (1ull << 63);
+}
+double fermi_unkey(unsigned long long k) {
+    const unsigned long long b = (k >> 63) ? k & ~(1ull << 63) : ~k;
+    double x;
+    std::memcpy(&x, &b, sizeof(x));
+    return x;
+}
+
+// mu, lower, upper, N(mu) for n_electrons in (0, n_orb) (include/tbk.h); simplices = S * NK of the whole mesh
+int fermi_search(std::vector<FermiSlab>& slabs, int n_orb, int64_t simplices, double n_electrons, double* out, int* passes_out) {
+    std::vector<double> emin((size_t)n_orb), emax((size_t)n_orb);
+    TBK_CHECK(fermi_edges(slabs, n_orb, emin.data(), emax.data()));
+    *passes_out = 0;
+    // the gap case: the doubles of the eigenvalue array, no search (fixed point cannot see the band edge: DESIGN 12.3)
+    if (n_electrons == std::floor(n_electrons)) {
+        const int m = (int)n_electrons;  // 1 .. n_orb - 1
+        if (emax[(size_t)m - 1] < emin[(size_t)m]) {
+            const double lower = emax[(size_t)m - 1], upper = emin[(size_t)m];
+            out[0] = lower + (upper - lower) / 2;
+            out[1] = lower;
+            out[2] = upper;
+            out[3] = (double)m;  // every simplex of the bands below is full, none of those above has begun: the kernel's N, exactly
+            return TBK_OK;
+        }
+    }
+    const FermiCount target = fermi_target(n_electrons, simplices);
+    double lo = std::nextafter(emin[0], -INFINITY), hi = emax[(size_t)n_orb - 1];  // Q(lo) = 0 < t <= Q(hi) = n_orb S NK 2^40
+    TBK_ARG(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "the eigenvalues are not finite");
+    FermiCount q_hi;
+    q_hi.whole = (unsigned long long)n_orb * (unsigned long long)simplices;
+    double probes[FERMI_PROBES];
+    FermiCount q[FERMI_PROBES];
+    bool first = true;
+    while (fermi_key(hi) - fermi_key(lo) > 1) {
+        int n = 0;
+        if (first && lo < 0.0 && hi > 0.0) {
+            // A bracket around zero: the image of the negative doubles runs against that of the positive ones, so equidistant
+            // points in it would not follow a scaling of the energies.  One pass of points that do: 0 and lo, hi times 2^-256 j.
+            // Every sub-interval is then at most 256 binades = 2^60 doubles long (points that underflow to zero are left out; the
+            // interval next to zero then ends below 2^-818 and is shorter still): 15 more passes.
+            for (int j = 1; j <= 7; ++j) {
+                const double x = std::ldexp(lo, -256 * j);
+                if (x < 0.0 && x > lo) probes[n++] = x;
+            }
+            probes[n++] = 0.0;
+            for (int j = 7; j >= 1; --j) {
+                const double x = std::ldexp(hi, -256 * j);
+                if (x > 0.0 && x < hi) probes[n++] = x;
+            }
+        } else {
+            const unsigned long long k_lo = fermi_key(lo), gap = fermi_key(hi) - k_lo;
+            n = (int)std::min<unsigned long long>(FERMI_SEARCH_M, gap - 1);
+            for (int j = 1; j <= n; ++j)
+                probes[j - 1] = fermi_unkey(k_lo + (unsigned long long)(((unsigned __int128)gap * (unsigned)j) / (unsigned)(n + 1)));
+        }
+        first = false;
+        TBK_CHECK(fermi_probe(slabs, probes, n, q));
+        *passes_out += 1;
+        int j = 0;
+        while (j < n && !q[j].at_least(target)) ++j;  // the first probe with Q >= t
+        if (j > 0) lo = probes[j - 1];
+        if (j < n) {
+            hi = probes[j];
+            q_hi = q[j];
+        }
+        if (lo == 0.0 && hi > 0.0) lo = 0.0;                      // +0.0: the double in front of the positive ones
+        if (hi == 0.0 && lo < 0.0) hi = -0.0;                     // -0.0: the double behind the negative ones
+        TBK_ARG(*passes_out <= 64, "the Fermi-level search does not end (N(E) is not a number?)");
+    }
+    const double mu = hi == 0.0 ? 0.0 : hi;
+    out[0] = out[1] = out[2] = mu;
+    out[3] = fermi_nos(q_hi, simplices);
+    return TBK_OK;
+}
+
+int fermi_check_device(int device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
+        (void)hipGetLastError();
+        tbk_set_error("no HIP device visible: libtbk has no CPU path");
+        return TBK_ERR_DEVICE;
+    }
+    TBK_ARG(device >= 0 && device < n_dev, "device out of range");
+    TBK_HIP(hipSetDevice(device));
+    return TBK_OK;
+}
+
+// the mesh checks of tbk_dos_check that apply (there is no energy grid)
+int fermi_check_mesh(int dim, const int32_t* mesh, int64_t* nk_total) {
+    TBK_ARG(dim == 2 || dim == 3, "the density of states needs a 2- or 3-dimensional mesh");
+    TBK_ARG(mesh != nullptr, "mesh is NULL");
+    int64_t nk = 1;
+    for (int d = 0; d < dim; ++d) {
+        TBK_ARG(mesh[d] >= 1, "a mesh entry is < 1");
+        nk *= mesh[d];
+        TBK_ARG(nk < (int64_t(1) << 31), "the mesh has 2^31 points or more");
+    }
+    *nk_total = nk;
+    return TBK_OK;
+}
+
+int fermi_check_electrons(double n_electrons, int n_orb) {
+    TBK_ARG(std::isfinite(n_electrons) && n_electrons > 0.0 && n_electrons < (double)n_orb, "n_electrons must lie inside (0, n_orb)");
+    return TBK_OK;
+}
+
+// eigenvalues the caller brought, on one device: the slab is the whole mesh
+struct FermiOwned {
+    DevBuf d_E, d_ws;
+    std::vector<FermiSlab> slabs;
+    ~FermiOwned() {
+        d_E.release();
+        d_ws.release();
+    }
+    int make(int device, int dim, const int32_t* mesh, int n_orb, const double* E, int64_t nk) {
+        FermiSlab s;
+        s.device = device;
+        s.dim = dim;
+        TBK_CHECK(fermi_plan(dim, mesh, mesh[0], mesh[0], n_orb, &s.L));
+        const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double);
+        TBK_CHECK(d_E.reserve(e_bytes));
+        TBK_CHECK(d_ws.reserve(s.L.ws_bytes));
+        TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
+        s.d_E = d_E.as<double>();
+        s.d_ws = d_ws.as<char>();
+        slabs.push_back(s);
+        return TBK_OK;
+    }
+};
+
+// The mesh on staged handles: handle i takes the slab of tbk_dos_multi.  The caller's thread holds every handle's lock for the
+// whole call (the eigenvalues stay in the handles' ws_out across all passes), taken in address order; the eigenvalue calls are
+// enqueued handle after handle and checked afterwards, the probes of a pass likewise.
+struct FermiStaged {
+    std::vector<std::unique_lock<std::recursive_mutex>> locks;
+    std::vector<FermiSlab> slabs;
+    int64_t simplices = 0;
+    ~FermiStaged() {
+        for (FermiSlab& s : slabs)
+            for (hipEvent_t e : s.ev)
+                if (e) (void)hipEventDestroy(e);
+    }
+    int make(tbk_model* const* handles, int n_handles, const int32_t* mesh) {
+        TBK_ARG(handles != nullptr && n_handles >= 1, "no handles");
+        for (int i = 0; i < n_handles; ++i) {
+            TBK_ARG(handles[i] != nullptr, "a handle is NULL");
+            TBK_ARG(handles[i]->dim == handles[0]->dim && handles[i]->n_orb == handles[0]->n_orb, "handles of different models (dim / n_orb differ)");
+        }
+        std::vector<tbk_model*> order(handles, handles + n_handles);
+        std::sort(order.begin(), order.end());
+        order.erase(std::unique(order.begin(), order.end()), order.end());
+        TBK_ARG((int)order.size() == n_handles, "a handle appears twice");
+        for (tbk_model* m : order) locks.emplace_back(m->mu);
+        tbk_model* m0 = handles[0];
+        TBK_ARG(!m0->kdotp, "a k.p model has no Brillouin zone");
+        int64_t nk_total = 0;
+        TBK_CHECK(fermi_check_mesh(m0->dim, mesh, &nk_total));
+        const int dim = m0->dim, n_orb = m0->n_orb;
+        simplices = (int64_t)(dim == 3 ? 6 : 2) * nk_total;
+        const int64_t n0 = mesh[0], per = (n0 + n_handles - 1) / n_handles, plane_pts = nk_total / n0;
+        slabs.reserve((size_t)n_handles);
+        for (int i = 0; i < n_handles; ++i) {
+            const int64_t p_lo = std::min<int64_t>(n0, (int64_t)i * per), p_count = std::min<int64_t>(n0, p_lo + per) - p_lo;
+            if (p_count <= 0) break;  // handles whose slab is empty are skipped
+            tbk_model* m = handles[i];
+            TBK_ARG(!m->kdotp, "a k.p model has no Brillouin zone");
+            slabs.emplace_back();
+            FermiSlab& s = slabs.back();
+            s.m = m;
+            s.device = m->device;
+            s.dim = dim;
+            s.stream = m->stream;
+            TBK_HIP(hipSetDevice(m->device));
+            const int64_t planes = p_count == n0 ? n0 : p_count + 1, nk = planes * plane_pts;
+            TBK_CHECK(fermi_plan(dim, mesh, p_count, planes, n_orb, &s.L));
+            TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, p_lo, planes, &s.h_k));
+            const size_t k_bytes = s.h_k.size() * sizeof(double);
+            TBK_CHECK(m->ws_k.reserve(k_bytes));
+            TBK_CHECK(m->ws_out.reserve((size_t)nk * n_orb * sizeof(double)));
+            TBK_CHECK(m->ws_dos.reserve(s.L.ws_bytes));
+            TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, s.h_k.data(), k_bytes, hipMemcpyHostToDevice, m->stream));
+            // the existing pipeline with the host list as the fold hint, as in tbk_dos_slab
+            TBK_CHECK(tbk_eigenval_device_hint(m, m->ws_k.as<double>(), s.h_k.data(), nk, m->ws_out.as<double>()));
+            s.d_E = m->ws_out.as<double>();
+            s.d_ws = m->ws_dos.as<char>();
+            s.timed = m->timing && hipEventCreate(&s.ev[0]) == hipSuccess && hipEventCreate(&s.ev[1]) == hipSuccess;
+        }
+        // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigenval: the first failing slab's
+        for (FermiSlab& s : slabs) {
+            TBK_CHECK(tbk_eigenval_check(s.m));
+            std::vector<double>().swap(s.h_k);
+        }
+        return TBK_OK;
+    }
+    void book(int passes, bool searched) {
+        for (FermiSlab& s : slabs) {
+            s.m->fermi_ms += s.ms;
+            s.m->fermi_calls += 1;
+            if (searched) s.m->fermi_passes += passes;
+        }
+    }
+};
+
+}  // namespace
+
+extern "C" int tbk_nos_at_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* energies,
+                                           int64_t n_p, double* nos_out) {
+    int64_t nk = 0;
+    TBK_CHECK(fermi_check_mesh(dim, mesh, &nk));
+    TBK_ARG(E != nullptr && energies != nullptr && nos_out != nullptr, "E / energies / nos is NULL");
+    TBK_ARG(n_orb >= 1, "n_orb < 1");
+    TBK_ARG(n_p >= 1, "no probe energies");
+    for (int64_t j = 0; j < n_p; ++j) TBK_ARG(std::isfinite(energies[j]), "a probe energy is not finite");
+    TBK_CHECK(fermi_check_device(device));
+    FermiOwned own;
+    TBK_CHECK(own.make(device, dim, mesh, n_orb, E, nk));
+    const int64_t simplices = (int64_t)(dim == 3 ? 6 : 2) * nk;
+    FermiCount q[FERMI_PROBES];
+    for (int64_t j0 = 0; j0 < n_p; j0 += FERMI_PROBES) {
+        const int n = (int)std::min<int64_t>(FERMI_PROBES, n_p - j0);
+        TBK_CHECK(fermi_probe(own.slabs, energies + j0, n, q));
+        for (int m = 0; m < n; ++m) nos_out[j0 + m] = fermi_nos(q[m], simplices);
+    }
+    return TBK_OK;
+}
+
+extern "C" int tbk_band_edges_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double* emin_out,
+                                               double* emax_out) {
+    int64_t nk = 0;
+    TBK_CHECK(fermi_check_mesh(dim, mesh, &nk));
+    TBK_ARG(E != nullptr && emin_out != nullptr && emax_out != nullptr, "E / emin / emax is NULL");
+    TBK_ARG(n_orb >= 1, "n_orb < 1");
+    TBK_CHECK(fermi_check_device(device));
+    FermiOwned own;
+    TBK_CHECK(own.make(device, dim, mesh, n_orb, E, nk));
+    return fermi_edges(own.slabs, n_orb, emin_out, emax_out);
+}
+
+extern "C" int tbk_fermi_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double n_electrons, double* out,
+                                          int32_t* passes_out) {
+    int64_t nk = 0;
+    TBK_CHECK(fermi_check_mesh(dim, mesh, &nk));
+    TBK_ARG(E != nullptr && out != nullptr, "E / out is NULL");
+    TBK_ARG(n_orb >= 1, "n_orb < 1");
+    TBK_CHECK(fermi_check_electrons(n_electrons, n_orb));
+    TBK_CHECK(fermi_check_device(device));
+    FermiOwned own;
+    TBK_CHECK(own.make(device, dim, mesh, n_orb, E, nk));
+    int passes = 0;
+    TBK_CHECK(fermi_search(own.slabs, n_orb, (int64_t)(dim == 3 ? 6 : 2) * nk, n_electrons, out, &passes));
+    if (passes_out) *passes_out = passes;
+    return TBK_OK;
+}
+
+extern "C" int tbk_band_edges_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, double* emin_out, double* emax_out) {
+    TBK_ARG(emin_out != nullptr && emax_out != nullptr, "emin / emax is NULL");
+    FermiStaged staged;
+    TBK_CHECK(staged.make(handles, n_handles, mesh));
+    TBK_CHECK(fermi_edges(staged.slabs, handles[0]->n_orb, emin_out, emax_out));
+    staged.book(0, false);
+    return TBK_OK;
+}
+
+extern "C" int tbk_band_edges(tbk_model* m, const int32_t* mesh, double* emin_out, double* emax_out) {
+    return tbk_band_edges_multi(&m, 1, mesh, emin_out, emax_out);
+}
+
+extern "C" int tbk_fermi_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, double n_electrons, double* out) {
+    TBK_ARG(out != nullptr, "out is NULL");
+    TBK_ARG(handles != nullptr && n_handles >= 1 && handles[0] != nullptr, "no handles");
+    TBK_CHECK(fermi_check_electrons(n_electrons, handles[0]->n_orb));
+    FermiStaged staged;
+    TBK_CHECK(staged.make(handles, n_handles, mesh));
+    int passes = 0;
+    TBK_CHECK(fermi_search(staged.slabs, handles[0]->n_orb, staged.simplices, n_electrons, out, &passes));
+    staged.book(passes, true);
+    return TBK_OK;
+}
+
+extern "C" int tbk_fermi(tbk_model* m, const int32_t* mesh, double n_electrons, double* out) { return tbk_fermi_multi(&m, 1, mesh, n_electrons, out); }
+
+extern "C" int tbk_fermi_timing(tbk_model* m, double* ms, int64_t* calls, int64_t* passes, int reset) {
+    TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr && passes != nullptr, "model / ms / calls / passes is NULL");
+    TBK_LOCK(m);
+    *ms = m->fermi_ms;
+    *calls = m->fermi_calls;
+    *passes = m->fermi_passes;
+    if (reset) {
+        m->fermi_ms = 0.0;
+        m->fermi_calls = 0;
+        m->fermi_passes = 0;
+    }
+    return TBK_OK;
+}

@@ -265,7 +265,7 @@ struct tbk_model {
     std::vector<double> pos_cache;         // host copy of what ws_posraw holds
     DevBuf ws_posraw;
     DevBuf ws_xl;     // the launch chain of band_xl_*: the second matrix buffer (the sweep of a panel reads one, writes the other)
-    DevBuf ws_dos;    // tbk_dos / tbk_pdos: the workgroups' fixed-point bins [n_wg][NE], the combined bins and nos (tbk_dos.hip, tbk_pdos.hip)
+    DevBuf ws_dos;    // tbk_dos / tbk_pdos: the workgroups' fixed-point bins [n_wg][NE], the combined bins and nos (tbk_dos.hip, tbk_pdos.hip); tbk_fermi: its rows and partials
     DevBuf ws_pdos_u;    // tbk_pdos: the eigenvectors of one k chunk [chunk][n_orb][n_orb] complex
     DevBuf ws_pdos_w;    // ... the weights of the whole slab W[NK][G][n_orb]
     DevBuf ws_pdos_grp;  // ... the groups: offsets [G + 1] and, 256-byte aligned behind them, the orbital list
@@ -280,6 +280,9 @@ struct tbk_model {
     int64_t dos_calls = 0;  // ... and the calls it was summed over
     double pdos_ms[3] = {0.0, 0.0, 0.0};  // tbk_pdos_timing: the same for the weights kernel, the accumulate kernel, reduction + scan
     int64_t pdos_calls = 0;
+    double fermi_ms = 0.0;     // tbk_fermi_timing: summed HIP-event time of the probe and band-edge kernels while `timing` is on
+    int64_t fermi_calls = 0;   // ... the tbk_fermi / tbk_band_edges calls of this handle
+    int64_t fermi_passes = 0;  // ... and the passes of its Fermi-level searches (counted whether `timing` is on or not)
 };
 
 // the operand the model was staged with
