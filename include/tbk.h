@@ -315,6 +315,50 @@ int tbk_fermi_multi(tbk_model* const* handles, int n_handles, const int32_t* mes
  * of its probe and band-edge kernels in the calls made while TBK_OPT_TIMING was on; reset = 1 clears. */
 int tbk_fermi_timing(tbk_model* m, double* ms, int64_t* calls, int64_t* passes, int reset);
 
+/* ---- tetrahedron integration weights and occupations of a uniform k mesh (not in the reference) -----------------------------------
+ * mesh, the simplices, the half-open ranges and the stable sort are those of tbk_dos / tbk_pdos (csrc/tbk_occ.hip, DESIGN.md
+ * section 13).  At one energy mu every state (k, b) of the mesh gets the weight
+ *     w[k][b] = 1 / (S NK) * sum over the simplices T that contain mesh point k of Bloechl's corner weight of k in T,
+ * 24 tetrahedra over 15 mesh points in three dimensions, 6 triangles over 7 in two, added in one fixed order and divided once:
+ * sum_{k, b} w = N(mu), 0 <= NK w <= 1, w = 0 exactly below the spectrum and the double nearest 1 / NK above it.  Any
+ * Brillouin-zone integral over the occupied states is then sum_{k, b} w[k][b] A[k][b]; three of them are computed here:
+ *     f[b]  = sum_k w[k][b]                          band occupations in [0, 1] (fixed point 2^-40: exactly 1 for a full band)
+ *     eb[b] = sum_k w[k][b] E[k][b]                  band energies (doubles, in an order fixed by the mesh and n_orb)
+ *     q[i]  = sum_k sum_b w[k][b] |U[k][i][b]|^2     orbital occupations, U of tbk_eigh, convention 2 (fixed point: for given
+ *                                                    (w, U) the same bits for every chunk size; |error| <= 2^-41 per orbital)
+ * sum_i q[i] = sum_b f[b] = N(mu).  Inside a degenerate eigenspace the split of q over the bands depends on the basis the
+ * eigensolver returns (the caveat of tbk_pdos); the sum over the degenerate cluster does not.
+ * Argument errors (TBK_ERR_ARGUMENT), before any device is touched: dim not in {2, 3}, a mesh entry < 1, 2^31 mesh points or more,
+ * an energy that is not finite, mode not in {0, 1}, mode 1 with n_electrons not finite or outside (0, n_orb), k_chunk < 0, a NULL
+ * pointer, a k.p handle, a handle given twice.  Host buffers; synchronous. */
+
+/* The kernels alone on an eigensystem the caller brings: E[NK][n_orb] in mesh order, rows ascending; U[NK][n_orb][n_orb][2] with
+ * U[k][i][b] = component i of band b.  w_out: double [NK][n_orb].  U is walked in chunks of k_chunk mesh points (0: all at once);
+ * q_out, f_out, eb_out: double [n_orb]. */
+int tbk_tetra_weights_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double energy, double* w_out);
+int tbk_occupations_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double energy,
+                                     int64_t k_chunk, double* q_out, double* f_out, double* eb_out);
+/* The whole call: the mesh is evaluated through the eigenvalue path as in tbk_fermi (fold hint, tbk_eigenval_check in front of the
+ * kernels), so tbk_tetra_weights, tbk_fermi and tbk_occupations see the same eigenvalues.  tbk_tetra_weights is the one call of the
+ * family that returns NK n_orb doubles.  tbk_occupations: mode 0, value = the energy mu, mu_out = (mu, mu, mu, N(mu)) with N from the
+ * probe kernel of tbk_fermi; mode 1, value = n_electrons, mu_out = the four numbers of tbk_fermi, whose search runs on the resident
+ * eigenvalues.  The weights stay in device memory; the k list is walked in chunks of at most TBK_OPT_K_CHUNK points (0: what
+ * tbk_eigh_device would choose), per chunk tbk_eigh_device fills a chunk-sized eigenvector workspace that one kernel contracts
+ * with the chunk's weights.  Memory: 2 NK n_orb doubles and the eigenvectors of one chunk (TBK_ERR_MEMORY otherwise). */
+int tbk_tetra_weights(tbk_model* m, const int32_t* mesh, double energy, double* w_out);
+int tbk_occupations(tbk_model* m, const int32_t* mesh, int mode, double value, double* mu_out, double* q_out, double* f_out,
+                    double* eb_out);
+/* On several devices from one process: the slabs of tbk_dos_multi.  A handle keeps its slab's eigenvalues and the periodic
+ * neighbour plane on BOTH sides, and writes weights for its own planes only; the host concatenates w, adds the integer words of f
+ * and q exactly and adds eb in handle order.  The calling thread holds every handle for the whole call: the handles must be
+ * distinct. */
+int tbk_tetra_weights_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, double energy, double* w_out);
+int tbk_occupations_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double* mu_out,
+                          double* q_out, double* f_out, double* eb_out);
+/* ms[3] = the summed HIP-event time of the weights kernel, the band sums, and the contraction + its reduction in this handle's calls
+ * made while TBK_OPT_TIMING was on; calls = how many calls; reset = 1 clears.  (The eigensolver stages are in tbk_get_timing.) */
+int tbk_occ_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
 /* ---- k.p models (kdotp.py:51-100): H(k) = sum_p prod_d k_d^powers[p][d] * coeffs[p] ------- */
 int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, const int32_t* powers,
                      const double* coeffs, tbk_kdotp** out);

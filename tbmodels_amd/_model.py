@@ -33,7 +33,7 @@ try:  # fast content hash for the staging fingerprint; zlib is the fallback
 except ImportError:  # pragma: no cover
     _xxhash = None
 
-__all__ = ("Model", "DensityOfStates", "ProjectedDensityOfStates", "BandEdges", "FermiLevel")
+__all__ = ("Model", "DensityOfStates", "ProjectedDensityOfStates", "BandEdges", "FermiLevel", "Occupations")
 
 #: what ``Model.dos`` returns: the energy grid (NE,), the number of states at its points (NE,), their difference quotient (NE - 1,)
 DensityOfStates = co.namedtuple("DensityOfStates", ("energies", "nos", "dos"))
@@ -42,6 +42,7 @@ ProjectedDensityOfStates = co.namedtuple("ProjectedDensityOfStates", ("energies"
 BandEdges = co.namedtuple("BandEdges", ("emin", "emax"))
 #: what ``Model.fermi_level`` returns: floats; ``lower < upper`` exactly when the mesh has a gap at the filling asked for
 FermiLevel = co.namedtuple("FermiLevel", ("mu", "lower", "upper", "nos"))
+Occupations = co.namedtuple("Occupations", ("mu", "orbital_occ", "band_occ", "band_energy"))
 
 
 def _devices_from_env():
@@ -783,7 +784,7 @@ class Model:
         return (eig[0], vec[0]) if single else (eig, vec)
 
     def _mesh_argument(self, mesh, what="dos"):
-        """The mesh check ``dos``, ``pdos``, ``band_edges`` and ``fermi_level`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
+        """The mesh check ``dos``, ``pdos``, ``band_edges``, ``fermi_level``, ``tetra_weights`` and ``occupations`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
         if self.dim not in (2, 3):
             raise ValueError("{} needs a 2- or 3-dimensional model, this one has dimension {}".format(what, self.dim))
         try:
@@ -947,6 +948,84 @@ class Model:
             handles, n_handles = self._handle_array()
             _lib.check(_lib.lib().tbk_fermi_multi(handles, n_handles, _lib.ptr(mesh_array), count, _lib.ptr(out)))
         return FermiLevel(float(out[0]), float(out[1]), float(out[2]), float(out[3]))
+
+    def tetra_weights(self, mesh, energy):
+        """
+        The tetrahedron integration weight of every state of a uniform k mesh at ``energy``, computed on the GPU from eigenvalues
+        that never leave it.  Not in the reference.
+
+        ``mesh`` and the simplices are those of :meth:`dos`; ``energy`` is a finite real number.  Returns an array ``w`` of shape
+        ``mesh + (size,)``: ``w[i_1, ..., i_dim, b]`` is Bloechl's corner weight of the mesh point in every simplex that contains
+        it (24 tetrahedra in three dimensions, 6 triangles in two), summed and divided by their number per cell times ``NK``.
+        Any Brillouin-zone integral over the states below ``energy`` is ``(w * A).sum()`` for ``A`` of the same shape;
+        ``w.sum()`` is the ``nos`` of :meth:`dos` at ``energy``, ``0 <= NK w <= 1``, ``w`` is exactly 0 below the spectrum and
+        exactly the double nearest ``1 / NK`` above it.  For given eigenvalues the result is reproducible bit for bit.
+
+        This is the one call of the family that returns ``NK * size`` doubles; :meth:`occupations` keeps the weights on the GPU.
+        One-dimensional models raise ``ValueError``.  With several ``devices`` every device takes a slab of the mesh along its
+        first axis.
+        """
+        mesh_array = self._mesh_argument(mesh, "tetra_weights")
+        value = self._energy_argument(energy)
+        out = np.empty(tuple(int(n) for n in mesh_array) + (self.size,), dtype=np.float64)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigenval
+            handles, n_handles = self._handle_array()
+            _lib.check(_lib.lib().tbk_tetra_weights_multi(handles, n_handles, _lib.ptr(mesh_array), value, _lib.ptr(out)))
+        return out
+
+    @staticmethod
+    def _energy_argument(energy):
+        if isinstance(energy, (bool, np.bool_)) or not isinstance(energy, (int, float, np.integer, np.floating)):
+            raise ValueError("energy must be a real number, got {!r}".format(energy))
+        value = float(energy)
+        if not np.isfinite(value):
+            raise ValueError("energy must be finite, got {!r}".format(energy))
+        return value
+
+    def occupations(self, mesh, *, energy=None, n_electrons=None):
+        """
+        Orbital occupations, band occupations and band energies of a uniform k mesh by the linear tetrahedron method, computed on
+        the GPU from eigenvalues, eigenvectors and integration weights that never leave it.  Not in the reference.
+
+        ``mesh`` is that of :meth:`dos`.  Exactly one of ``energy`` (the chemical potential, a finite real number) and
+        ``n_electrons`` (a real number inside ``(0, size)``: the chemical potential is that of :meth:`fermi_level`, bit for bit) is
+        given, else ``ValueError``.  Returns the named tuple ``(mu, orbital_occ, band_occ, band_energy)``:
+
+        * ``mu`` is the :class:`FermiLevel` tuple ``(mu, lower, upper, nos)`` -- for ``energy`` all three are ``energy`` and ``nos``
+          is the number of states there;
+        * ``orbital_occ[i] = sum_k sum_b w[k][b] |U[k][i][b]|^2`` with ``w`` of :meth:`tetra_weights` at ``mu.mu`` and ``U`` the
+          eigenvectors of ``eigh(k, convention=2)``: the charge on orbital ``i`` (no spin factor);
+        * ``band_occ[b] = sum_k w[k][b]`` in ``[0, 1]``, exactly 1 for a full band and exactly 0 for an empty one;
+        * ``band_energy[b] = sum_k w[k][b] E[k][b]``; ``band_energy.sum()`` is the band energy per unit cell.
+
+        ``orbital_occ.sum() == band_occ.sum() == mu.nos`` up to ``size * 2^-40``.  Inside a degenerate eigenspace the split of a
+        state's weight over the orbitals depends on the basis, which is unspecified (see :meth:`eigh`); the sum over the degenerate
+        cluster does not, so filled clusters (an insulator's valence bands) give a basis-independent ``orbital_occ``.
+        One-dimensional models raise ``ValueError``.  With several ``devices`` every device takes a slab of the mesh along its
+        first axis.
+        """
+        mesh_array = self._mesh_argument(mesh, "occupations")
+        if (energy is None) == (n_electrons is None):
+            raise ValueError("occupations takes exactly one of energy and n_electrons")
+        if energy is not None:
+            mode, value = 0, self._energy_argument(energy)
+        else:
+            if isinstance(n_electrons, (bool, np.bool_)) or not isinstance(n_electrons, (int, float, np.integer, np.floating)):
+                raise ValueError("n_electrons must be a real number, got {!r}".format(n_electrons))
+            mode, value = 1, float(n_electrons)
+            if not np.isfinite(value) or not 0.0 < value < self.size:
+                raise ValueError("n_electrons must lie inside (0, {}), got {!r}".format(self.size, n_electrons))
+        mu = np.empty(4, dtype=np.float64)
+        orbital, band, energy_out = (np.empty(self.size, dtype=np.float64) for _ in range(3))
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_occupations_multi(handles, n_handles, _lib.ptr(mesh_array), mode, value, _lib.ptr(mu), _lib.ptr(orbital),
+                                                 _lib.ptr(band), _lib.ptr(energy_out))
+            )
+        return Occupations(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), orbital, band, energy_out)
 
     def construct_kdotp(self, k, order):
         """

@@ -657,6 +657,36 @@ struct FermiStaged {
 
 }  // namespace
 
+int tbk_fermi_check_electrons(double n_electrons, int n_orb) { return fermi_check_electrons(n_electrons, n_orb); }
+
+int tbk_fermi_resident(const tbk_fermi_slab_t* slabs, int n_slabs, int dim, const int32_t* mesh, int n_orb, int mode, double value, double* out4) {
+    int64_t nk_total = 0;
+    TBK_CHECK(fermi_check_mesh(dim, mesh, &nk_total));
+    std::vector<FermiSlab> v((size_t)n_slabs);
+    for (int i = 0; i < n_slabs; ++i) {
+        FermiSlab& s = v[(size_t)i];
+        s.m = slabs[i].m;
+        s.device = s.m->device;
+        s.dim = dim;
+        s.stream = s.m->stream;
+        TBK_CHECK(fermi_plan(dim, mesh, slabs[i].cells0, slabs[i].planes0, n_orb, &s.L));
+        TBK_HIP(hipSetDevice(s.device));
+        TBK_CHECK(s.m->ws_dos.reserve(s.L.ws_bytes));
+        s.d_E = slabs[i].d_E;
+        s.d_ws = s.m->ws_dos.as<char>();
+    }
+    const int64_t simplices = (int64_t)(dim == 3 ? 6 : 2) * nk_total;
+    if (mode == 1) {
+        int passes = 0;
+        return fermi_search(v, n_orb, simplices, value, out4, &passes);
+    }
+    FermiCount q[FERMI_PROBES];
+    TBK_CHECK(fermi_probe(v, &value, 1, q));
+    out4[0] = out4[1] = out4[2] = value;
+    out4[3] = fermi_nos(q[0], simplices);
+    return TBK_OK;
+}
+
 extern "C" int tbk_nos_at_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* energies,
                                            int64_t n_p, double* nos_out) {
     int64_t nk = 0;

@@ -269,6 +269,9 @@ struct tbk_model {
     DevBuf ws_pdos_u;    // tbk_pdos: the eigenvectors of one k chunk [chunk][n_orb][n_orb] complex
     DevBuf ws_pdos_w;    // ... the weights of the whole slab W[NK][G][n_orb]
     DevBuf ws_pdos_grp;  // ... the groups: offsets [G + 1] and, 256-byte aligned behind them, the orbital list
+    DevBuf ws_occ_w;     // tbk_tetra_weights / tbk_occupations: the point weights of the slab's own mesh points w[rows][n_orb] (tbk_occ.hip)
+    DevBuf ws_occ;       // ... the block partials of the band sums, the workgroups' rows of the contraction and the combined words
+                         // (the eigenvectors of one k chunk go through ws_pdos_u, the Fermi search through ws_dos)
     // Set for the duration of one eigenvalue call by tbk_eigenval_device_gather (tbk_comm.hip): the chunk pipeline calls it
     // whenever the eigenvalues of rows [c0, c0 + nkc) of the call have been enqueued, with an event recorded behind
     // them -- the all-gather of finished rows leaves on the communicator's stream while later chunks compute.
@@ -283,6 +286,8 @@ struct tbk_model {
     double fermi_ms = 0.0;     // tbk_fermi_timing: summed HIP-event time of the probe and band-edge kernels while `timing` is on
     int64_t fermi_calls = 0;   // ... the tbk_fermi / tbk_band_edges calls of this handle
     int64_t fermi_passes = 0;  // ... and the passes of its Fermi-level searches (counted whether `timing` is on or not)
+    double occ_ms[3] = {0.0, 0.0, 0.0};  // tbk_occ_timing: the weights kernel, the band sums, the contraction + its reduction
+    int64_t occ_calls = 0;
 };
 
 // the operand the model was staged with
@@ -537,6 +542,18 @@ int tbk_dos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_coun
 int tbk_pdos_check_groups(int n_orb, const int32_t* group_offsets, const int32_t* group_orbitals, int n_groups);
 int tbk_pdos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_count, const int32_t* group_offsets, const int32_t* group_orbitals,
                   int n_groups, double e_min, double e_step, int64_t n_e, double* nos_out);
+
+// tbk_fermi.hip: the Fermi search (mode 1, value = n_electrons: mu, lower, upper, N(mu) of tbk_fermi) or N at one energy (mode 0,
+// value = the energy: mu = lower = upper = value) on eigenvalues that are resident on the handles -- slab i holds planes0 planes of
+// axis 0 at d_E, its own cells0 cells first (the layout of tbk_fermi_multi).  The caller holds the handles' locks and has checked
+// the eigenvalues; the probe rows go through every handle's ws_dos.  tbk_occupations (tbk_occ.hip) finds its mu here.
+struct tbk_fermi_slab_t {
+    tbk_model* m;
+    const double* d_E;
+    int64_t cells0, planes0;
+};
+int tbk_fermi_resident(const tbk_fermi_slab_t* slabs, int n_slabs, int dim, const int32_t* mesh, int n_orb, int mode, double value, double* out4);
+int tbk_fermi_check_electrons(double n_electrons, int n_orb);
 
 // tbk_peak.hip
 int tbk_run_mfma_f64_peak(double* tflops);

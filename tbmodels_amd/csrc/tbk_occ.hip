@@ -1,0 +1,796 @@
+// tbk_occ.hip -- the tetrahedron integration weight of every state (k, b) of a uniform, periodic k mesh at one energy mu, and what a
+// user integrates with it: band occupations, band energies and the charge on every orbital.  Not in the reference; DESIGN.md
+// section 13 has the quantities, the summation orders and the measurements, tools/occ_model.py is the statement the tests compare with.
+//
+//   E[planes][n1][n2][n_orb]  ascending eigenvalues per mesh point, mesh order (last axis fastest): what tbk_dos.hip reads
+//   w[k][b]   = (sum over the simplices T that contain mesh point k of Bloechl's corner weight w_c(T, b; mu) of k in T) / (S NK)
+//   f[b]      = sum_k w[k][b]                       eb[b] = sum_k w[k][b] E[k][b]
+//   q[i]      = sum_k sum_b w[k][b] |U[k][i][b]|^2  (U[nk][n][n][2] of tbk_eigh_device, convention 2)
+//
+// tetra_weights_kernel is a GATHER: the work item is one (mesh point, band) pair, band fastest, so a wave reads 64 consecutive
+// doubles of a row of E per neighbour.  Mesh point v is corner p of the simplex with axis order sigma of the cell at
+// v - (e_sigma1 + ... + e_sigmap): in three dimensions 6 orders x 4 positions = 24 tetrahedra over v and the 14 offsets in
+// {-1, 0, 1}^3 whose non-zero components share a sign, in two dimensions 2 x 3 = 6 triangles over 7 points.  The item loads those 15
+// (7) energies once, walks the simplices in the order s = 4 sigma + p (3 sigma + p), sigma in the order of tbk_dos.hip's list
+// (012, 021, 102, 120, 201, 210; 01, 10), by two nested loops that are NOT unrolled -- the corners are selected by uniform indices, so
+// the branch code exists once -- and adds the own corner's weight of every simplex to ONE double in that order.  Per simplex: the
+// stable sort of tbk_pdos.hip (adjacent exchanges on a strict comparison, corners in simplex order) carrying the rank of the own
+// corner; 0 or the full weight from two comparisons unless e1 <= mu < e_top; else the reciprocals of the DOS_GAP_SCALE-scaled gaps
+// and the corner weights of pdos_simplex, expression for expression.  A full tetrahedron gives 1/4 to every corner, so above the
+// spectrum the sum is 24 / 4 = 6 exactly and w = 6 / (6 NK) is the double nearest 1 / NK.  A triangle's corner weights are carried
+// TIMES THREE (a full corner is 1, not the inexact 1/3) and the divisor is 3 S NK = 6 NK: the same property.  One division, one
+// plain store per item: no atomics, no LDS, no scratch; for given E and mu the bits of w depend on nothing else.
+//
+// Every axis goes through the same modular neighbour index (i - 1 and i + 1 modulo the planes held): an axis of one point is its
+// own neighbour on both sides, an axis of two has one neighbour on both sides.  A slab of a mesh shared among handles holds the
+// periodic neighbour plane on BOTH sides of its own planes (off0 = 1): the modular index then never wraps along axis 0.
+//
+// occ_band_kernel: f in the 64-bit fixed point of DESIGN 10.3 -- a term is round(NK w 2^40) -- and eb in doubles in a fixed order:
+// the own mesh points are cut into blocks of 256 consecutive points; inside a block the lane of band b with row slot r (of
+// 256 / n_orb slots; one above 256 orbitals) adds the points r, r + slots, ... in index order, the slots are added in index order,
+// and occ_band_reduce_kernel adds the blocks in index order.  So eb depends on (slab, n_orb) alone and f on nothing but w.
+//
+// occ_contract_kernel: one wave per (k, i) row of U, lanes along b (16-byte loads, coalesced; w[k][.] alongside).  A lane adds its
+// bands b = lane, lane + 64, ... in order, the lanes meet in an xor butterfly (32, 16, ..., 1: commutative, every lane holds the same
+// bits), P = NK * sum in [0, 1] is rounded ONCE to fixed point and added, in integers, to the workgroup's LDS accumulator of orbital
+// i; the workgroup then adds its accumulators to its own row of a [n_workgroups][n_orb] buffer that persists across the k chunks of a
+// call.  Which workgroup takes a k-point is a function of the point's index in the slab (kpw consecutive points each, at most 2^20:
+// a row's sums stay below 2^60), not of the chunk.  occ_reduce_kernel sums the rows, high 44 and low 20 bits apart.  For given
+// (w, U) the bits of q depend neither on the chunk size nor on the workgroup count; |error| <= 2^-41 per orbital.
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "tbk_dos_common.h"
+
+namespace {
+
+constexpr int OCC_THREADS = 256;
+constexpr int OCC_BLOCK = 256;             // mesh points per block of the band sums
+constexpr int64_t OCC_MAX_WG = 4096;       // rows of the contraction buffer, at most (more only for the 2^20 bound)
+constexpr int64_t OCC_MAX_GRID = 1 << 20;  // workgroups of the weights kernel, at most (the items are strided over them)
+
+struct OccGeom {
+    int n0_own;     // planes of axis 0 this launch writes weights for
+    int n0_planes;  // planes of axis 0 in E
+    int off0;       // the first own plane in E: 0 for a whole mesh, 1 for a slab with its two neighbour planes
+    int n1, n2;     // the other axes (n2 = 1 in two dimensions)
+    int n_orb;
+    int64_t items;  // n0_own * n1 * n2 * n_orb
+};
+
+__device__ __forceinline__ int occ_prev(int i, int n) { return i == 0 ? n - 1 : i - 1; }
+__device__ __forceinline__ int occ_next(int i, int n) { return i + 1 == n ? 0 : i + 1; }
+
+// one adjacent exchange of the stable sort; r follows the own corner
+template <int A, int B>
+__device__ __forceinline__ void occ_exchange(double& a, double& b, int& r) {
+    const bool sw = b < a;  // strict: equal energies keep their order
+    const double lo = sw ? b : a, hi = sw ? a : b;
+    a = lo;
+    b = hi;
+    r = sw ? (r == A ? B : r == B ? A : r) : r;
+}
+
+// Bloechl's weight of corner `own` (0 .. 3, in simplex order) of one tetrahedron at mu: in [0, 1/4].  The branches are those of
+// pdos_simplex (tbk_pdos.hip): half-open ranges, the comparisons on the unscaled numbers select, every ratio is formed on its own.
+__device__ __forceinline__ double occ_tetrahedron(double e1, double e2, double e3, double e4, int own, double mu) {
+    int r = own;
+    occ_exchange<0, 1>(e1, e2, r);
+    occ_exchange<1, 2>(e2, e3, r);
+    occ_exchange<2, 3>(e3, e4, r);
+    occ_exchange<0, 1>(e1, e2, r);
+    occ_exchange<1, 2>(e2, e3, r);
+    occ_exchange<0, 1>(e1, e2, r);
+    if (mu < e1) return 0.0;
+    if (mu >= e4) return 0.25;
+    const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE, s4 = e4 * DOS_GAP_SCALE;
+    const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r41 = 1.0 / (s4 - s1), r32 = 1.0 / (s3 - s2), r42 = 1.0 / (s4 - s2),
+                 r43 = 1.0 / (s4 - s3);
+    const double Es = mu * DOS_GAP_SCALE;
+    double w1, w2, w3, w4;
+    if (mu < e2) {
+        const double x = Es - s1;
+        const double q21 = x * r21, q31 = x * r31, q41 = x * r41;
+        const double C = 0.25 * q21 * q31 * q41;
+        w1 = C * (4.0 - (q21 + q31 + q41));
+        w2 = C * q21;
+        w3 = C * q31;
+        w4 = C * q41;
+    } else if (mu < e3) {
+        const double x1 = Es - s1, x2 = Es - s2, y3 = s3 - Es, y4 = s4 - Es;
+        const double p31 = x1 * r31, p41 = x1 * r41, p32 = x2 * r32, p42 = x2 * r42;  // from below
+        const double m31 = y3 * r31, m32 = y3 * r32, m41 = y4 * r41, m42 = y4 * r42;  // from above
+        const double T = 0.25 * p41;
+        const double C1 = T * p31;
+        const double C2 = T * p32 * m31;
+        const double C3 = 0.25 * p42 * p32 * m41;
+        const double C12 = C1 + C2, C23 = C2 + C3, C123 = C12 + C3;
+        w1 = C1 + C12 * m31 + C123 * m41;
+        w2 = C123 + C23 * m32 + C3 * m42;
+        w3 = C12 * p31 + C23 * p32;
+        w4 = C123 * p41 + C3 * p42;
+    } else {
+        const double y = s4 - Es;
+        const double q41 = y * r41, q42 = y * r42, q43 = y * r43;
+        const double C = 0.25 * q41 * q42 * q43;
+        w1 = 0.25 - C * q41;
+        w2 = 0.25 - C * q42;
+        w3 = 0.25 - C * q43;
+        w4 = 0.25 - C * (4.0 - (q41 + q42 + q43));
+    }
+    const double w = r == 0 ? w1 : r == 1 ? w2 : r == 2 ? w3 : w4;
+    return fmin(fmax(w, 0.0), 0.25);  // (NaN -> 0)
+}
+
+// THREE TIMES the weight of corner `own` (0 .. 2) of one triangle at mu: in [0, 1], exactly 1 for a full triangle
+__device__ __forceinline__ double occ_triangle(double e1, double e2, double e3, int own, double mu) {
+    int r = own;
+    occ_exchange<0, 1>(e1, e2, r);
+    occ_exchange<1, 2>(e2, e3, r);
+    occ_exchange<0, 1>(e1, e2, r);
+    if (mu < e1) return 0.0;
+    if (mu >= e3) return 1.0;
+    const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE;
+    const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r32 = 1.0 / (s3 - s2);
+    const double Es = mu * DOS_GAP_SCALE;
+    double w1, w2, w3;
+    if (mu < e2) {
+        const double x = Es - s1;
+        const double q21 = x * r21, q31 = x * r31;
+        const double C = q21 * q31;
+        w1 = C * (3.0 - (q21 + q31));
+        w2 = C * q21;
+        w3 = C * q31;
+    } else {
+        const double y = s3 - Es;
+        const double q31 = y * r31, q32 = y * r32;
+        const double C = q31 * q32;
+        w1 = 1.0 - C * q31;
+        w2 = 1.0 - C * q32;
+        w3 = 1.0 - C * (3.0 - (q31 + q32));
+    }
+    const double w = r == 0 ? w1 : r == 1 ? w2 : w3;
+    return fmin(fmax(w, 0.0), 1.0);
+}
+
+__device__ __forceinline__ double occ_pick(int i, double x, double y, double z) { return i == 0 ? x : i == 1 ? y : z; }
+
+// w[own point][n_orb] = acc / denom, denom = 24 NK / 4 = 6 NK in both dimensions (see the head of the file)
+template <int DIM>
+__global__ void __launch_bounds__(OCC_THREADS) tetra_weights_kernel(const double* __restrict__ E, OccGeom g, double mu, double denom,
+                                                                    double* __restrict__ w) {
+    for (int64_t it = (int64_t)blockIdx.x * OCC_THREADS + threadIdx.x; it < g.items; it += (int64_t)gridDim.x * OCC_THREADS) {
+        const int64_t pt = it / g.n_orb;
+        const int band = (int)(it - pt * g.n_orb);
+        int c = (int)pt;  // NK < 2^31 (checked by the launcher)
+        const int i2 = c % g.n2;
+        c /= g.n2;
+        const int i1 = c % g.n1;
+        const int i0 = c / g.n1 + g.off0;
+        const int m0 = occ_prev(i0, g.n0_planes), p0 = occ_next(i0, g.n0_planes);
+        const int m1 = occ_prev(i1, g.n1), p1 = occ_next(i1, g.n1);
+        auto at = [&](int a0, int a1, int a2) -> double {
+            const int64_t k = ((int64_t)a0 * g.n1 + a1) * g.n2 + a2;
+            return E[k * g.n_orb + band];
+        };
+        double acc = 0.0;
+        if (DIM == 3) {
+            const int m2 = occ_prev(i2, g.n2), p2 = occ_next(i2, g.n2);
+            // v, and the neighbours at +x, +y, +z, +x+y, ... (x, y, z = a step along axis 0, 1, 2) and at the negated offsets
+            const double v = at(i0, i1, i2);
+            const double px = at(p0, i1, i2), py = at(i0, p1, i2), pz = at(i0, i1, p2);
+            const double pxy = at(p0, p1, i2), pxz = at(p0, i1, p2), pyz = at(i0, p1, p2), pxyz = at(p0, p1, p2);
+            const double mx = at(m0, i1, i2), my = at(i0, m1, i2), mz = at(i0, i1, m2);
+            const double mxy = at(m0, m1, i2), mxz = at(m0, i1, m2), myz = at(i0, m1, m2), mxyz = at(m0, m1, m2);
+#pragma unroll 1
+            for (int o = 0; o < 6; ++o) {
+                // the order (a, b, c) of the axes: 012, 021, 102, 120, 201, 210
+                const int a = o >> 1;
+                const int b = o == 0 || o == 5 ? 1 : o == 1 || o == 3 ? 2 : 0;
+                const int cc = 3 - a - b;
+                const double pa = occ_pick(a, px, py, pz), pb = occ_pick(b, px, py, pz), pc = occ_pick(cc, px, py, pz);
+                const double pab = occ_pick(cc, pyz, pxz, pxy), pbc = occ_pick(a, pyz, pxz, pxy);  // a pair is the complement of an axis
+                const double ma = occ_pick(a, mx, my, mz), mb = occ_pick(b, mx, my, mz), mc = occ_pick(cc, mx, my, mz);
+                const double mab = occ_pick(cc, myz, mxz, mxy), mbc = occ_pick(a, myz, mxz, mxy);
+#pragma unroll 1
+                for (int p = 0; p < 4; ++p) {
+                    // the cell at v - (e_a + ... ): corners 0, e_a, e_a + e_b, e_a + e_b + e_c of it; v is corner p
+                    const double c0 = p == 0 ? v : p == 1 ? ma : p == 2 ? mab : mxyz;
+                    const double c1 = p == 0 ? pa : p == 1 ? v : p == 2 ? mb : mbc;
+                    const double c2 = p == 0 ? pab : p == 1 ? pb : p == 2 ? v : mc;
+                    const double c3 = p == 0 ? pxyz : p == 1 ? pbc : p == 2 ? pc : v;
+                    acc += occ_tetrahedron(c0, c1, c2, c3, p, mu);
+                }
+            }
+        } else {
+            const double v = at(i0, i1, 0);
+            const double px = at(p0, i1, 0), py = at(i0, p1, 0), pxy = at(p0, p1, 0);
+            const double mx = at(m0, i1, 0), my = at(i0, m1, 0), mxy = at(m0, m1, 0);
+#pragma unroll 1
+            for (int o = 0; o < 2; ++o) {
+                const double pa = o == 0 ? px : py, pb = o == 0 ? py : px;
+                const double ma = o == 0 ? mx : my, mb = o == 0 ? my : mx;
+#pragma unroll 1
+                for (int p = 0; p < 3; ++p) {
+                    const double c0 = p == 0 ? v : p == 1 ? ma : mxy;
+                    const double c1 = p == 0 ? pa : p == 1 ? v : mb;
+                    const double c2 = p == 0 ? pxy : p == 1 ? pb : v;
+                    acc += occ_triangle(c0, c1, c2, p, mu);
+                }
+            }
+        }
+        w[it] = acc / denom;
+    }
+}
+
+// grid: (blocks of OCC_BLOCK own mesh points, blocks of 256 bands above 256 orbitals).  part_f / part_eb: [gridDim.x][n_orb]
+__global__ void __launch_bounds__(OCC_THREADS) occ_band_kernel(const double* __restrict__ w, const double* __restrict__ E, int64_t rows, int n_orb,
+                                                               double nk_total, unsigned long long* __restrict__ part_f,
+                                                               double* __restrict__ part_eb) {
+    __shared__ double s_eb[OCC_THREADS];
+    __shared__ unsigned long long s_f[OCC_THREADS];
+    const int tid = (int)threadIdx.x;
+    const int slots = n_orb <= OCC_THREADS ? OCC_THREADS / n_orb : 1;
+    const int width = n_orb <= OCC_THREADS ? n_orb : min(OCC_THREADS, n_orb - (int)blockIdx.y * OCC_THREADS);
+    const int slot = tid / width, lane_band = tid - slot * width;
+    const int band = (int)blockIdx.y * OCC_THREADS + lane_band;
+    const int64_t r0 = (int64_t)blockIdx.x * OCC_BLOCK, r1 = min(r0 + OCC_BLOCK, rows);
+    double eb = 0.0;
+    unsigned long long f = 0ull;
+    if (slot < slots) {
+        for (int64_t r = r0 + slot; r < r1; r += slots) {
+            const double x = w[r * n_orb + band];
+            eb += x * E[r * n_orb + band];
+            f += dos_fixed(x * nk_total);
+        }
+    }
+    s_eb[tid] = eb;
+    s_f[tid] = f;
+    __syncthreads();
+    if (tid < width) {
+        for (int q = 1; q < slots; ++q) {
+            eb += s_eb[q * width + tid];
+            f += s_f[q * width + tid];
+        }
+        part_eb[(int64_t)blockIdx.x * n_orb + band] = eb;
+        part_f[(int64_t)blockIdx.x * n_orb + band] = f;
+    }
+}
+
+// one thread per band over the blocks in index order.  sums: f high [n_orb], f low [n_orb]; eb [n_orb]
+__global__ void __launch_bounds__(OCC_THREADS) occ_band_reduce_kernel(const unsigned long long* __restrict__ part_f, const double* __restrict__ part_eb,
+                                                                      int64_t n_blocks, int n_orb, unsigned long long* __restrict__ sums,
+                                                                      double* __restrict__ eb_out) {
+    const int band = (int)blockIdx.x * OCC_THREADS + (int)threadIdx.x;
+    if (band >= n_orb) return;
+    const unsigned long long mask = (1ull << DOS_SPLIT_BITS) - 1;
+    unsigned long long hi = 0, lo = 0;
+    double eb = 0.0;
+    for (int64_t blk = 0; blk < n_blocks; ++blk) {
+        const unsigned long long v = part_f[blk * n_orb + band];
+        hi += v >> DOS_SPLIT_BITS;
+        lo += v & mask;
+        eb += part_eb[blk * n_orb + band];
+    }
+    sums[band] = hi;
+    sums[n_orb + band] = lo;
+    eb_out[band] = eb;
+}
+
+// U: the eigenvectors of the k-points [c0, c0 + nkc) of the slab's own points, w_chunk their rows of w.  Workgroup blockIdx.x + wg_lo
+// owns the points [wg kpw, (wg + 1) kpw) of the slab and takes those of them the chunk holds.  Dynamic LDS: n u64
+__global__ void __launch_bounds__(OCC_THREADS) occ_contract_kernel(const double2* __restrict__ U, const double* __restrict__ w_chunk, int n,
+                                                                   int64_t c0, int64_t nkc, int64_t kpw, int64_t wg_lo, double nk_total,
+                                                                   unsigned long long* __restrict__ buf) {
+    extern __shared__ unsigned long long occ_acc[];
+    const int tid = (int)threadIdx.x;
+    const int64_t wg = wg_lo + blockIdx.x;
+    const int64_t k_lo = max(c0, wg * kpw), k_hi = min(c0 + nkc, (wg + 1) * kpw);
+    if (k_lo >= k_hi) return;  // (uniform)
+    for (int i = tid; i < n; i += OCC_THREADS) occ_acc[i] = 0ull;
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63;
+    const int64_t n_rows = (k_hi - k_lo) * n;
+    for (int64_t row = wave; row < n_rows; row += OCC_THREADS / 64) {
+        const int64_t kk = row / n;
+        const int i = (int)(row - kk * n);
+        const int64_t k = k_lo - c0 + kk;  // inside the chunk
+        const double2* u = U + ((size_t)k * n + i) * n;
+        const double* wk = w_chunk + (size_t)k * n;
+        double s = 0.0;
+        for (int b = lane; b < n; b += 64) {
+            const double2 z = u[b];
+            const double a = z.x * z.x + z.y * z.y;
+            s += wk[b] * a;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        if (lane == 0) atomicAdd(&occ_acc[i], dos_fixed(s * nk_total));
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += OCC_THREADS) buf[wg * n + i] += occ_acc[i];  // this workgroup's own row
+}
+
+// one thread per orbital over the workgroups' rows.  sums: high [n], low [n]
+__global__ void __launch_bounds__(OCC_THREADS) occ_reduce_kernel(const unsigned long long* __restrict__ buf, int64_t n_wg, int n,
+                                                                 unsigned long long* __restrict__ sums) {
+    const int i = (int)blockIdx.x * OCC_THREADS + (int)threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long mask = (1ull << DOS_SPLIT_BITS) - 1;
+    unsigned long long hi = 0, lo = 0;
+    for (int64_t wg = 0; wg < n_wg; ++wg) {
+        const unsigned long long v = buf[wg * n + i];
+        hi += v >> DOS_SPLIT_BITS;
+        lo += v & mask;
+    }
+    sums[i] = hi;
+    sums[n + i] = lo;
+}
+
+// ---- host: one slab of the mesh on one device ----------------------------------------------------------------------------------
+struct OccPlan {
+    OccGeom g;
+    int dim = 0;
+    int64_t rows = 0;      // own mesh points
+    int64_t n_blocks = 0;  // of the band sums
+    int64_t kpw = 1, n_wg = 1;
+    int w_grid = 1;
+    // the workspace: part_f, part_eb [n_blocks][n]; buf [n_wg][n]; then what goes to the host in one copy: f high / low [2][n],
+    // q high / low [2][n] (u64), eb [n] (double)
+    size_t off_part_eb = 0, off_buf = 0, off_host = 0, host_bytes = 0, ws_bytes = 0;
+};
+
+// cells0 own planes along axis 0 out of planes0 planes in E, the first own one at off0
+int occ_plan(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int off0, int n_orb, OccPlan* out) {
+    OccPlan L;
+    L.dim = dim;
+    L.g.n0_own = (int)cells0;
+    L.g.n0_planes = (int)planes0;
+    L.g.off0 = off0;
+    L.g.n1 = mesh[1];
+    L.g.n2 = dim == 3 ? mesh[2] : 1;
+    L.g.n_orb = n_orb;
+    L.rows = cells0 * L.g.n1 * L.g.n2;
+    L.g.items = L.rows * n_orb;
+    L.w_grid = (int)std::min<int64_t>((L.g.items + OCC_THREADS - 1) / OCC_THREADS, OCC_MAX_GRID);
+    L.n_blocks = (L.rows + OCC_BLOCK - 1) / OCC_BLOCK;
+    // rows of the contraction buffer: at most 32 MiB of them, never more than 2^20 k-points each
+    int64_t n_wg = std::min<int64_t>(L.rows, std::min<int64_t>(OCC_MAX_WG, std::max<int64_t>(1, (int64_t(1) << 22) / n_orb)));
+    n_wg = std::max<int64_t>(n_wg, (L.rows + DOS_MAX_ITEMS - 1) / DOS_MAX_ITEMS);
+    L.kpw = (L.rows + n_wg - 1) / n_wg;
+    L.n_wg = (L.rows + L.kpw - 1) / L.kpw;
+    const size_t n = (size_t)n_orb;
+    L.off_part_eb = dos_align256((size_t)L.n_blocks * n * sizeof(unsigned long long));
+    L.off_buf = L.off_part_eb + dos_align256((size_t)L.n_blocks * n * sizeof(double));
+    L.off_host = L.off_buf + dos_align256((size_t)L.n_wg * n * sizeof(unsigned long long));
+    L.host_bytes = 5 * n * sizeof(double);
+    L.ws_bytes = L.off_host + dos_align256(L.host_bytes);
+    *out = L;
+    return TBK_OK;
+}
+
+int occ_launch_weights(hipStream_t s, const OccPlan& L, const double* d_E, double mu, double nk_total, double* d_w) {
+    const double denom = 6.0 * nk_total;
+    if (L.dim == 3)
+        hipLaunchKernelGGL(tetra_weights_kernel<3>, dim3((unsigned)L.w_grid), dim3(OCC_THREADS), 0, s, d_E, L.g, mu, denom, d_w);
+    else
+        hipLaunchKernelGGL(tetra_weights_kernel<2>, dim3((unsigned)L.w_grid), dim3(OCC_THREADS), 0, s, d_E, L.g, mu, denom, d_w);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// d_E_own: the rows of E of the own mesh points
+int occ_launch_band(hipStream_t s, const OccPlan& L, const double* d_w, const double* d_E_own, double nk_total, char* ws) {
+    const int n = L.g.n_orb;
+    auto* part_f = reinterpret_cast<unsigned long long*>(ws);
+    auto* part_eb = reinterpret_cast<double*>(ws + L.off_part_eb);
+    auto* sums = reinterpret_cast<unsigned long long*>(ws + L.off_host);
+    auto* eb = reinterpret_cast<double*>(ws + L.off_host) + 4 * (size_t)n;
+    const dim3 grid((unsigned)L.n_blocks, (unsigned)((n + OCC_THREADS - 1) / OCC_THREADS));
+    hipLaunchKernelGGL(occ_band_kernel, grid, dim3(OCC_THREADS), 0, s, d_w, d_E_own, L.rows, n, nk_total, part_f, part_eb);
+    TBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(occ_band_reduce_kernel, dim3(grid.y), dim3(OCC_THREADS), 0, s, part_f, part_eb, L.n_blocks, n, sums, eb);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+int occ_clear_buf(hipStream_t s, const OccPlan& L, char* ws) {
+    TBK_HIP(hipMemsetAsync(ws + L.off_buf, 0, (size_t)L.n_wg * (size_t)L.g.n_orb * sizeof(unsigned long long), s));
+    return TBK_OK;
+}
+
+// the own points [c0, c0 + nkc) of the slab: d_U their eigenvectors, d_w the slab's weights
+int occ_launch_contract(hipStream_t s, const OccPlan& L, const double* d_U, const double* d_w, int64_t c0, int64_t nkc, double nk_total, char* ws) {
+    const int n = L.g.n_orb;
+    const int64_t wg_lo = c0 / L.kpw, wg_hi = (c0 + nkc - 1) / L.kpw;
+    hipLaunchKernelGGL(occ_contract_kernel, dim3((unsigned)(wg_hi - wg_lo + 1)), dim3(OCC_THREADS), (size_t)n * sizeof(unsigned long long), s,
+                       reinterpret_cast<const double2*>(d_U), d_w + (size_t)c0 * n, n, c0, nkc, L.kpw, wg_lo, nk_total,
+                       reinterpret_cast<unsigned long long*>(ws + L.off_buf));
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+int occ_launch_reduce(hipStream_t s, const OccPlan& L, char* ws) {
+    const int n = L.g.n_orb;
+    hipLaunchKernelGGL(occ_reduce_kernel, dim3((unsigned)((n + OCC_THREADS - 1) / OCC_THREADS)), dim3(OCC_THREADS), 0, s,
+                       reinterpret_cast<const unsigned long long*>(ws + L.off_buf), L.n_wg, n,
+                       reinterpret_cast<unsigned long long*>(ws + L.off_host) + 2 * (size_t)n);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// the integer words of f and q and the doubles of eb, summed over the slabs on the host: the words exactly (128 bits), eb in slab order
+struct OccTotals {
+    std::vector<unsigned __int128> f, q;
+    std::vector<double> eb;
+    explicit OccTotals(int n) : f((size_t)n, 0), q((size_t)n, 0), eb((size_t)n, 0.0) {}
+    void add(const std::vector<double>& host, int n, bool first) {  // one slab's off_host block
+        std::vector<unsigned long long> words(4 * (size_t)n);
+        std::memcpy(words.data(), host.data(), words.size() * sizeof(unsigned long long));
+        for (int i = 0; i < n; ++i) {
+            f[(size_t)i] += ((unsigned __int128)words[i] << DOS_SPLIT_BITS) + words[n + i];
+            q[(size_t)i] += ((unsigned __int128)words[2 * n + i] << DOS_SPLIT_BITS) + words[3 * n + i];
+            eb[(size_t)i] = first ? host[4 * (size_t)n + i] : eb[(size_t)i] + host[4 * (size_t)n + i];
+        }
+    }
+    // x = words / (2^40 NK): the integer is rounded to double once, the division once more
+    void finish(int n, double nk_total, double* q_out, double* f_out, double* eb_out) const {
+        for (int i = 0; i < n; ++i) {
+            f_out[i] = std::ldexp((double)f[(size_t)i], -DOS_FRAC_BITS) / nk_total;
+            q_out[i] = std::ldexp((double)q[(size_t)i], -DOS_FRAC_BITS) / nk_total;
+            eb_out[i] = eb[(size_t)i];
+        }
+    }
+};
+
+int occ_check_device(int device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
+        (void)hipGetLastError();
+        tbk_set_error("no HIP device visible: libtbk has no CPU path");
+        return TBK_ERR_DEVICE;
+    }
+    TBK_ARG(device >= 0 && device < n_dev, "device out of range");
+    TBK_HIP(hipSetDevice(device));
+    return TBK_OK;
+}
+
+int occ_check_mesh(int dim, const int32_t* mesh, int64_t* nk_total) {
+    TBK_ARG(dim == 2 || dim == 3, "the tetrahedron weights need a 2- or 3-dimensional mesh");
+    TBK_ARG(mesh != nullptr, "mesh is NULL");
+    int64_t nk = 1;
+    for (int d = 0; d < dim; ++d) {
+        TBK_ARG(mesh[d] >= 1, "a mesh entry is < 1");
+        nk *= mesh[d];
+        TBK_ARG(nk < (int64_t(1) << 31), "the mesh has 2^31 points or more");
+    }
+    *nk_total = nk;
+    return TBK_OK;
+}
+
+struct OccBufs {  // device memory of the entry points that bring their own eigensystem
+    DevBuf d_E, d_w, d_ws, d_U;
+    ~OccBufs() {
+        d_E.release();
+        d_w.release();
+        d_ws.release();
+        d_U.release();
+    }
+};
+
+// ---- the mesh on staged handles ------------------------------------------------------------------------------------------------
+struct OccEvents {  // (start, stop, stage) of one timed call on one handle, destroyed with it
+    struct Pair {
+        hipEvent_t a, b;
+        int stage;
+    };
+    std::vector<Pair> pairs;
+    bool on = false;
+    hipStream_t stream = nullptr;
+    void start(int stage) {
+        if (!on) return;
+        Pair p{nullptr, nullptr, stage};
+        if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) {
+            if (p.a) (void)hipEventDestroy(p.a);
+            on = false;
+            return;
+        }
+        (void)hipEventRecord(p.a, stream);
+        pairs.push_back(p);
+    }
+    void stop() {
+        if (on && !pairs.empty()) (void)hipEventRecord(pairs.back().b, stream);
+    }
+    void collect(double* ms) {  // after a synchronisation of the stream
+        for (const Pair& p : pairs) {
+            float t = 0.f;
+            if (on && hipEventElapsedTime(&t, p.a, p.b) == hipSuccess) ms[p.stage] += (double)t;
+        }
+    }
+    ~OccEvents() {
+        for (const Pair& p : pairs) {
+            (void)hipEventDestroy(p.a);
+            (void)hipEventDestroy(p.b);
+        }
+    }
+};
+
+struct OccSlab {
+    tbk_model* m = nullptr;
+    int64_t p_lo = 0, p_count = 0, planes = 0;
+    int off0 = 0;
+    OccPlan L;
+    const double* d_E = nullptr;  // planes planes
+    std::vector<double> h_k;
+    std::vector<double> host;  // the off_host block
+    OccEvents ev;
+};
+
+// Handle i takes the slab of tbk_dos_multi.  Its eigenvalues: the planes [p_lo, p_lo + p_count] come from ONE call of the
+// eigenvalue path on the k list tbk_fermi_multi gives it (the same call, so the same bits: mu is tbk_fermi's), the neighbour plane
+// p_lo - 1 from a second call, in front of them in ws_out.  A handle that holds the whole axis needs neither neighbour.
+struct OccStaged {
+    std::vector<std::unique_lock<std::recursive_mutex>> locks;
+    std::vector<OccSlab> slabs;
+    int dim = 0, n_orb = 0;
+    int64_t nk_total = 0, plane_pts = 0;
+
+    int check(tbk_model* const* handles, int n_handles, const int32_t* mesh) {
+        TBK_ARG(handles != nullptr && n_handles >= 1, "no handles");
+        for (int i = 0; i < n_handles; ++i) {
+            TBK_ARG(handles[i] != nullptr, "a handle is NULL");
+            TBK_ARG(handles[i]->dim == handles[0]->dim && handles[i]->n_orb == handles[0]->n_orb, "handles of different models (dim / n_orb differ)");
+            TBK_ARG(!handles[i]->kdotp, "a k.p model has no Brillouin zone");
+        }
+        std::vector<tbk_model*> order(handles, handles + n_handles);
+        std::sort(order.begin(), order.end());
+        order.erase(std::unique(order.begin(), order.end()), order.end());
+        TBK_ARG((int)order.size() == n_handles, "a handle appears twice");
+        dim = handles[0]->dim;
+        n_orb = handles[0]->n_orb;
+        TBK_CHECK(occ_check_mesh(dim, mesh, &nk_total));
+        plane_pts = nk_total / mesh[0];
+        for (tbk_model* m : order) locks.emplace_back(m->mu);
+        return TBK_OK;
+    }
+
+    // after check(): the eigenvalues of every slab, checked
+    int make(tbk_model* const* handles, int n_handles, const int32_t* mesh) {
+        const int64_t n0 = mesh[0], per = (n0 + n_handles - 1) / n_handles;
+        slabs.reserve((size_t)n_handles);
+        for (int i = 0; i < n_handles; ++i) {
+            const int64_t p_lo = std::min<int64_t>(n0, (int64_t)i * per), p_count = std::min<int64_t>(n0, p_lo + per) - p_lo;
+            if (p_count <= 0) break;  // handles whose slab is empty are skipped
+            tbk_model* m = handles[i];
+            slabs.emplace_back();
+            OccSlab& s = slabs.back();
+            s.m = m;
+            s.p_lo = p_lo;
+            s.p_count = p_count;
+            s.off0 = p_count == n0 ? 0 : 1;
+            const int64_t main_planes = p_count == n0 ? n0 : p_count + 1;
+            s.planes = main_planes + s.off0;
+            TBK_CHECK(tbk_eig_check_option(m));
+            TBK_HIP(hipSetDevice(m->device));
+            TBK_CHECK(occ_plan(dim, mesh, p_count, s.planes, s.off0, n_orb, &s.L));
+            // the k list: the neighbour plane below first, then the main planes
+            std::vector<double> below;
+            if (s.off0) TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, (p_lo - 1 + n0) % n0, 1, &below));
+            TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, p_lo, main_planes, &s.h_k));
+            try {
+                s.h_k.insert(s.h_k.begin(), below.begin(), below.end());
+            } catch (...) {
+                tbk_set_error("cannot allocate the k list of the mesh");
+                return TBK_ERR_MEMORY;
+            }
+            const size_t k_bytes = s.h_k.size() * sizeof(double);
+            const int64_t nk = s.planes * plane_pts;
+            TBK_CHECK(m->ws_k.reserve(k_bytes));
+            TBK_CHECK(m->ws_out.reserve((size_t)nk * n_orb * sizeof(double)));
+            TBK_CHECK(m->ws_occ_w.reserve((size_t)s.L.rows * n_orb * sizeof(double)));
+            TBK_CHECK(m->ws_occ.reserve(s.L.ws_bytes));
+            TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, s.h_k.data(), k_bytes, hipMemcpyHostToDevice, m->stream));
+            const int64_t head = (int64_t)s.off0 * plane_pts;  // points in front of the main planes
+            // the existing pipeline with the host list as the fold hint, as in tbk_dos_slab
+            TBK_CHECK(tbk_eigenval_device_hint(m, m->ws_k.as<double>() + head * dim, s.h_k.data() + head * dim, main_planes * plane_pts,
+                                               m->ws_out.as<double>() + head * n_orb));
+            if (s.off0) TBK_CHECK(tbk_eigenval_device_hint(m, m->ws_k.as<double>(), s.h_k.data(), plane_pts, m->ws_out.as<double>()));
+            s.d_E = m->ws_out.as<double>();
+            s.ev.on = m->timing;
+            s.ev.stream = m->stream;
+        }
+        // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigenval: the first failing slab's
+        for (OccSlab& s : slabs) TBK_CHECK(tbk_eigenval_check(s.m));
+        return TBK_OK;
+    }
+
+    // mode 1: the Fermi search of tbk_fermi on the resident eigenvalues; mode 0: N(value) from the probe kernel
+    int find_mu(const int32_t* mesh, int mode, double value, double* mu_out) {
+        std::vector<tbk_fermi_slab_t> f;
+        for (OccSlab& s : slabs)
+            f.push_back({s.m, s.d_E + (size_t)s.off0 * plane_pts * n_orb, s.p_count, s.p_count == mesh[0] ? s.p_count : s.p_count + 1});
+        return tbk_fermi_resident(f.data(), (int)f.size(), dim, mesh, n_orb, mode, value, mu_out);
+    }
+
+    int weights(double mu, double* w_out) {
+        for (OccSlab& s : slabs) {
+            TBK_HIP(hipSetDevice(s.m->device));
+            s.ev.start(0);
+            TBK_CHECK(occ_launch_weights(s.m->stream, s.L, s.d_E, mu, (double)nk_total, s.m->ws_occ_w.as<double>()));
+            s.ev.stop();
+            if (w_out)
+                TBK_HIP(hipMemcpyAsync(w_out + (size_t)s.p_lo * plane_pts * n_orb, s.m->ws_occ_w.ptr, (size_t)s.L.rows * n_orb * sizeof(double),
+                                       hipMemcpyDeviceToHost, s.m->stream));
+        }
+        return TBK_OK;
+    }
+
+    // f, eb and q of every slab (the weights are in ws_occ_w), left in s.host
+    int sums() {
+        for (OccSlab& s : slabs) {
+            tbk_model* m = s.m;
+            TBK_HIP(hipSetDevice(m->device));
+            char* ws = m->ws_occ.as<char>();
+            const double* d_w = m->ws_occ_w.as<double>();
+            const double* d_E_own = s.d_E + (size_t)s.off0 * plane_pts * n_orb;
+            s.ev.start(1);
+            TBK_CHECK(occ_launch_band(m->stream, s.L, d_w, d_E_own, (double)nk_total, ws));
+            s.ev.stop();
+            TBK_CHECK(occ_clear_buf(m->stream, s.L, ws));
+            // k-points per chunk: TBK_OPT_K_CHUNK as given, else what the eigenvector call itself would take from the free memory;
+            // the chunk's eigenvalues (not used: the weights come from the eigenvalue path) go behind its eigenvectors
+            const int64_t nk = s.L.rows;
+            const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : choose_chunk(m, nk, true)));
+            const size_t u_doubles = (size_t)chunk * n_orb * n_orb * 2;
+            TBK_CHECK(m->ws_pdos_u.reserve((u_doubles + (size_t)chunk * n_orb) * sizeof(double)));
+            double* d_U = m->ws_pdos_u.as<double>();
+            const double* d_k_own = m->ws_k.as<double>() + (size_t)s.off0 * plane_pts * dim;
+            for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
+                const int64_t nkc = std::min(chunk, nk - c0);
+                TBK_CHECK(tbk_eigh_device(m, d_k_own + c0 * dim, nkc, 2, nullptr, d_U + u_doubles, d_U));
+                s.ev.start(2);
+                TBK_CHECK(occ_launch_contract(m->stream, s.L, d_U, d_w, c0, nkc, (double)nk_total, ws));
+                s.ev.stop();
+            }
+            s.ev.start(2);
+            TBK_CHECK(occ_launch_reduce(m->stream, s.L, ws));
+            s.ev.stop();
+            try {
+                s.host.resize(5 * (size_t)n_orb);
+            } catch (...) {
+                tbk_set_error("cannot allocate the per-handle results");
+                return TBK_ERR_MEMORY;
+            }
+            TBK_HIP(hipMemcpyAsync(s.host.data(), ws + s.L.off_host, s.L.host_bytes, hipMemcpyDeviceToHost, m->stream));
+        }
+        return TBK_OK;
+    }
+
+    // synchronises every handle (the eigenvector flags are reported as by tbk_eigh) and books the kernel times
+    int finish() {
+        for (OccSlab& s : slabs) TBK_CHECK(tbk_eigenval_check(s.m));
+        for (OccSlab& s : slabs) {
+            TBK_HIP(hipSetDevice(s.m->device));
+            TBK_HIP(hipStreamSynchronize(s.m->stream));
+            s.ev.collect(s.m->occ_ms);
+            s.m->occ_calls += 1;
+        }
+        return TBK_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" int tbk_tetra_weights_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double energy, double* w_out) {
+    int64_t nk = 0;
+    TBK_CHECK(occ_check_mesh(dim, mesh, &nk));
+    TBK_ARG(E != nullptr && w_out != nullptr, "E / w is NULL");
+    TBK_ARG(n_orb >= 1, "n_orb < 1");
+    TBK_ARG(std::isfinite(energy), "the energy is not finite");
+    TBK_CHECK(occ_check_device(device));
+    OccPlan L;
+    TBK_CHECK(occ_plan(dim, mesh, mesh[0], mesh[0], 0, n_orb, &L));
+    const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double);
+    OccBufs b;
+    TBK_CHECK(b.d_E.reserve(e_bytes));
+    TBK_CHECK(b.d_w.reserve(e_bytes));
+    TBK_HIP(hipMemcpy(b.d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
+    TBK_CHECK(occ_launch_weights(nullptr, L, b.d_E.as<double>(), energy, (double)nk, b.d_w.as<double>()));
+    TBK_HIP(hipMemcpy(w_out, b.d_w.ptr, e_bytes, hipMemcpyDeviceToHost));
+    return TBK_OK;
+}
+
+extern "C" int tbk_occupations_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double energy,
+                                                int64_t k_chunk, double* q_out, double* f_out, double* eb_out) {
+    int64_t nk = 0;
+    TBK_CHECK(occ_check_mesh(dim, mesh, &nk));
+    TBK_ARG(E != nullptr && U != nullptr, "E / U is NULL");
+    TBK_ARG(q_out != nullptr && f_out != nullptr && eb_out != nullptr, "q / f / eb is NULL");
+    TBK_ARG(n_orb >= 1, "n_orb < 1");
+    TBK_ARG(std::isfinite(energy), "the energy is not finite");
+    TBK_ARG(k_chunk >= 0, "k_chunk < 0");
+    TBK_CHECK(occ_check_device(device));
+    OccPlan L;
+    TBK_CHECK(occ_plan(dim, mesh, mesh[0], mesh[0], 0, n_orb, &L));
+    const int64_t chunk = k_chunk == 0 ? nk : std::min(k_chunk, nk);
+    const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double), u_per_k = (size_t)n_orb * (size_t)n_orb * 2;
+    OccBufs b;
+    TBK_CHECK(b.d_E.reserve(e_bytes));
+    TBK_CHECK(b.d_w.reserve(e_bytes));
+    TBK_CHECK(b.d_ws.reserve(L.ws_bytes));
+    TBK_CHECK(b.d_U.reserve((size_t)chunk * u_per_k * sizeof(double)));
+    char* ws = b.d_ws.as<char>();
+    TBK_HIP(hipMemcpy(b.d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
+    TBK_CHECK(occ_launch_weights(nullptr, L, b.d_E.as<double>(), energy, (double)nk, b.d_w.as<double>()));
+    TBK_CHECK(occ_launch_band(nullptr, L, b.d_w.as<double>(), b.d_E.as<double>(), (double)nk, ws));
+    TBK_CHECK(occ_clear_buf(nullptr, L, ws));
+    for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
+        const int64_t nkc = std::min(chunk, nk - c0);
+        TBK_HIP(hipMemcpy(b.d_U.ptr, U + (size_t)c0 * u_per_k, (size_t)nkc * u_per_k * sizeof(double), hipMemcpyHostToDevice));
+        TBK_CHECK(occ_launch_contract(nullptr, L, b.d_U.as<double>(), b.d_w.as<double>(), c0, nkc, (double)nk, ws));
+    }
+    TBK_CHECK(occ_launch_reduce(nullptr, L, ws));
+    std::vector<double> host(5 * (size_t)n_orb);
+    TBK_HIP(hipMemcpy(host.data(), ws + L.off_host, L.host_bytes, hipMemcpyDeviceToHost));
+    OccTotals totals(n_orb);
+    totals.add(host, n_orb, true);
+    totals.finish(n_orb, (double)nk, q_out, f_out, eb_out);
+    return TBK_OK;
+}
+
+extern "C" int tbk_tetra_weights_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, double energy, double* w_out) {
+    TBK_ARG(w_out != nullptr, "w is NULL");
+    TBK_ARG(std::isfinite(energy), "the energy is not finite");
+    OccStaged staged;
+    TBK_CHECK(staged.check(handles, n_handles, mesh));
+    TBK_CHECK(staged.make(handles, n_handles, mesh));
+    TBK_CHECK(staged.weights(energy, w_out));
+    return staged.finish();
+}
+
+extern "C" int tbk_tetra_weights(tbk_model* m, const int32_t* mesh, double energy, double* w_out) {
+    return tbk_tetra_weights_multi(&m, 1, mesh, energy, w_out);
+}
+
+extern "C" int tbk_occupations_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double* mu_out,
+                                     double* q_out, double* f_out, double* eb_out) {
+    TBK_ARG(mu_out != nullptr && q_out != nullptr && f_out != nullptr && eb_out != nullptr, "mu / q / f / eb is NULL");
+    TBK_ARG(mode == 0 || mode == 1, "mode must be 0 (value = energy) or 1 (value = n_electrons)");
+    TBK_ARG(handles != nullptr && n_handles >= 1 && handles[0] != nullptr, "no handles");
+    if (mode == 1)
+        TBK_CHECK(tbk_fermi_check_electrons(value, handles[0]->n_orb));
+    else
+        TBK_ARG(std::isfinite(value), "the energy is not finite");
+    OccStaged staged;
+    TBK_CHECK(staged.check(handles, n_handles, mesh));
+    TBK_CHECK(staged.make(handles, n_handles, mesh));
+    TBK_CHECK(staged.find_mu(mesh, mode, value, mu_out));
+    TBK_CHECK(staged.weights(mu_out[0], nullptr));
+    TBK_CHECK(staged.sums());
+    TBK_CHECK(staged.finish());
+    OccTotals totals(staged.n_orb);
+    for (size_t i = 0; i < staged.slabs.size(); ++i) totals.add(staged.slabs[i].host, staged.n_orb, i == 0);
+    totals.finish(staged.n_orb, (double)staged.nk_total, q_out, f_out, eb_out);
+    return TBK_OK;
+}
+
+extern "C" int tbk_occupations(tbk_model* m, const int32_t* mesh, int mode, double value, double* mu_out, double* q_out, double* f_out,
+                               double* eb_out) {
+    return tbk_occupations_multi(&m, 1, mesh, mode, value, mu_out, q_out, f_out, eb_out);
+}
+
+extern "C" int tbk_occ_timing(tbk_model* m, double* ms, int64_t* calls, int reset) {
+    TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr, "model / ms / calls is NULL");
+    TBK_LOCK(m);
+    for (int i = 0; i < 3; ++i) ms[i] = m->occ_ms[i];
+    *calls = m->occ_calls;
+    if (reset) {
+        for (int i = 0; i < 3; ++i) m->occ_ms[i] = 0.0;
+        m->occ_calls = 0;
+    }
+    return TBK_OK;
+}
