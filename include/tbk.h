@@ -162,6 +162,11 @@ int tbk_eigh_device(tbk_model* m, const double* d_k, int64_t nk, int convention,
  * STRUCTURE and the shared-component values are taken from h_k, everything else from d_k.  tbk_eigenval_device is
  * this call with h_k = NULL (never folds); tbk_eigenval (host buffers) always has the list. */
 int tbk_eigenval_device_hint(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, double* d_E);
+/* The k chunks a tbk_eigenval_device call of nk k-points on this model would run as now (TBK_OPT_K_CHUNK, the free device
+ * memory and the contraction path of the last chunk enter; folded calls cut whole runs instead): *n_chunks of them, the first
+ * min(*n_chunks, capacity) lengths in lengths[].  Read-only, enqueues nothing; TBK_ERR_ARGUMENT for models whose eigenvalue
+ * calls go to rocSOLVER. */
+int tbk_eigenval_schedule(tbk_model* m, int64_t nk, int64_t* lengths, int capacity, int* n_chunks);
 /* Check the info flags of the eigenvalue calls since the last check (synchronises). */
 int tbk_eigenval_check(tbk_model* m);
 int tbk_synchronize(tbk_model* m);

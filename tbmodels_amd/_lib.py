@@ -63,6 +63,7 @@ SIGNATURES = {
     "tbk_eigenval_device": (_c_int, [_vp, _vp, _c_i64, _vp]),
     "tbk_eigenval_device_hint": (_c_int, [_vp, _vp, _vp, _c_i64, _vp]),
     "tbk_model_counter": (_c_int, [_vp, _c_int, ctypes.POINTER(_c_i64)]),
+    "tbk_eigenval_schedule": (_c_int, [_vp, _c_i64, ctypes.POINTER(_c_i64), _c_int, ctypes.POINTER(_c_int)]),
     "tbk_eigenval_check": (_c_int, [_vp]),
     "tbk_synchronize": (_c_int, [_vp]),
     "tbk_tridiagonal_reduce": (_c_int, [_c_int, _c_int, _c_i64, _vp, _c_int, _vp, _vp, _vp]),

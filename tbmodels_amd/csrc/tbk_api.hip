@@ -584,15 +584,32 @@ static int launch_tridiag_eigenvalues(tbk_model* m, const tbk_eig_plan_t& plan, 
 // gets), and the QL of the last chunk has nothing to hide behind: the schedule therefore ends on a short
 // chunk (one XCD round of k tiles plus the ragged remainder) whose reduction is brief, and that chunk's QL
 // runs next to the QL of the chunk before it.  All other chunks are multiples of 4096 k-points.
-static std::vector<int64_t> chunk_schedule(tbk_model* m, int64_t nk, int64_t chunk) {
+//
+// The short chunk is one unit longer (two units plus the remainder) where that moves it from a slower contraction path onto
+// two Strassen levels: tbk_hk_plan is asked for both lengths, its thresholds are not repeated here.  Models whose chunks never
+// take two levels, and the folded builder (`direct` false), keep one unit plus the remainder.  Measured at the headline shape
+// (64 orbitals, 4096 lattice vectors, 100 000 k-points; tools/sweep_strassen.py, contraction + rows of one chunk, ms):
+//     one level, 5792 k-points     5.219 + 0.110        two levels, 28672    21.264 + 1.085
+//     two levels, 9888             7.591 + 0.324        two levels, 32768    24.194 + 1.263
+// 32768 + 32768 + 28672 + 5792 is 78.59 ms, 32768 + 28672 + 28672 + 9888 is 78.07: the last chunk pays 2.59 ms for the
+// 4096 k-points that cost a long chunk 3.11 (0.76 us per k-point).  The reduction and bisection of the longer last chunk
+// are exposed as before; only the bisection's share grows (~0.05 ms).  `python bench.py`, old and new rule alternating, five
+// runs each: 86.49 -> 85.72 ms per step (medians; 86.43 - 86.89 and 85.29 - 85.76).
+static std::vector<int64_t> chunk_schedule(tbk_model* m, int64_t nk, int64_t chunk, bool direct) {
     std::vector<int64_t> out;
     const int64_t unit = 4096;
     if (!tbk_eig_small_supported(m->n_orb) || m->k_chunk > 0 || chunk < 2 * unit || nk < 3 * unit) {
         for (int64_t c0 = 0; c0 < nk; c0 += chunk) out.push_back(std::min(chunk, nk - c0));
         return out;
     }
-    const int64_t last = unit + nk % unit;  // in [4096, 8192)
-    int64_t rest = nk - last;               // a multiple of 4096
+    int64_t last = unit + nk % unit;  // in [4096, 8192)
+    if (direct && last + unit <= chunk) {
+        const tbk_operand_t op = tbk_staged_operand(m);
+        const HkPath shorter = tbk_hk_plan(m, op, last, false).path;
+        if (tbk_hk_plan(m, op, last + unit, false).path == HK_PATH_STRASSEN2 && (shorter == HK_PATH_STRASSEN || shorter == HK_PATH_TILES))
+            last += unit;  // in [8192, 12288)
+    }
+    int64_t rest = nk - last;  // a multiple of 4096
     const int64_t n_big = (rest + chunk - 1) / chunk;
     for (int64_t i = 0; i < n_big; ++i) {
         // as even as whole units allow, larger chunks first
@@ -632,7 +649,7 @@ static int eigenval_wave_pipeline(tbk_model* m, const tbk_eig_plan_t& plan, cons
     const size_t nn2 = n * n * 2;
     DevBuf* debuf[2] = {&m->ws_E, &m->ws_E2};
     const std::vector<int64_t> sched =
-        (runs != nullptr && m->k_chunk == 0 && nk > chunk) ? run_schedule(*runs, chunk) : chunk_schedule(m, nk, chunk);
+        (runs != nullptr && m->k_chunk == 0 && nk > chunk) ? run_schedule(*runs, chunk) : chunk_schedule(m, nk, chunk, builder == nullptr);
     const int64_t n_chunks = (int64_t)sched.size();
     const int64_t max_chunk = *std::max_element(sched.begin(), sched.end());
     TBK_CHECK(m->ws_H.reserve((size_t)max_chunk * nn2 * sizeof(double)));
@@ -803,6 +820,19 @@ extern "C" int tbk_eigenval_device_hint(tbk_model* m, const double* d_k, const d
 
 extern "C" int tbk_eigenval_device(tbk_model* m, const double* d_k, int64_t nk, double* d_E) {
     return tbk_eigenval_device_hint(m, d_k, nullptr, nk, d_E);
+}
+
+extern "C" int tbk_eigenval_schedule(tbk_model* m, int64_t nk, int64_t* lengths, int capacity, int* n_chunks) {
+    TBK_ARG(m != nullptr && n_chunks != nullptr, "model / n_chunks is NULL");
+    TBK_ARG(nk >= 1, "nk < 1");
+    TBK_ARG(capacity >= 0 && (lengths != nullptr || capacity == 0), "lengths is NULL");
+    TBK_LOCK(m);
+    TBK_ARG(tbk_eig_plan(m->n_orb, m->eigensolver, nk).own(), "the eigenvalue calls of this model go to rocSOLVER, not through the chunk pipeline");
+    TBK_HIP(hipSetDevice(m->device));
+    const std::vector<int64_t> sched = chunk_schedule(m, nk, choose_chunk(m, nk, true), true);
+    *n_chunks = (int)sched.size();
+    for (size_t i = 0; i < sched.size() && (int)i < capacity; ++i) lengths[i] = sched[i];
+    return TBK_OK;
 }
 
 extern "C" int tbk_model_counter(tbk_model* m, int counter, int64_t* value) {
