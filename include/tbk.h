@@ -79,9 +79,12 @@ enum {
                               *    lower-dimensional models (default 1; dense models, eigenval only)          */
     TBK_OPT_STRASSEN = 5,    /* 0: dense H(k) of long k chunks as the classical product instead of Strassen's
                               *    (default 1; csrc/tbk_hk_dense.hip tbk_hk_plan)                              */
-    TBK_OPT_STRASSEN_LEVELS = 6 /* 1 or 2 (default 2): the deepest recursion a chunk may take while TBK_OPT_STRASSEN
+    TBK_OPT_STRASSEN_LEVELS = 6, /* 1 or 2 (default 2): the deepest recursion a chunk may take while TBK_OPT_STRASSEN
                               *    is on -- two levels need longer chunks than one (tbk_hk_plan); anything else is
                               *    TBK_ERR_ARGUMENT                                                            */
+    TBK_OPT_STRASSEN_COMBINE = 7 /* 1 (default): the combine of a two-level chunk of the eigenvalue path in two passes,
+                              *    the first beside the last products (launch_strassen2); 0: the single kernel behind
+                              *    them.  Same bits either way                                                 */
 };
 
 /* ---- library / device ------------------------------------------------------------------ */
@@ -111,7 +114,8 @@ enum { TBK_CNT_EIGENVAL_CALLS = 0, TBK_CNT_FOLDED_CALLS = 1, TBK_CNT_FOLDED_KPOI
        TBK_CNT_LIBRARY_CALLS = 3, /* eigenvalue calls handed to rocSOLVER (on request, or above the own kernels' range) */
        TBK_CNT_STRASSEN_LAUNCHES = 4, /* dense H(k) launches of a k chunk that took the Strassen product, either depth */
        TBK_CNT_STRASSEN2_LAUNCHES = 5, /* ... those of them that took two levels */
-       TBK_CNT_COUNT = 6 };
+       TBK_CNT_STRASSEN2_SPLIT = 6, /* ... those of them whose combine ran in two passes (TBK_OPT_STRASSEN_COMBINE) */
+       TBK_CNT_COUNT = 7 };
 int tbk_model_counter(tbk_model* m, int counter, int64_t* value);
 
 /* ---- the hot path, host buffers (what Model.hamilton / Model.eigenval call) -------------- */

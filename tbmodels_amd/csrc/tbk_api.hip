@@ -194,6 +194,7 @@ static int create_common(int device, int dim, int n_orb, int64_t n_r, const int3
         TBK_TRY(TBK_HIP(hipEventCreateWithFlags(&m->ev_tri[b], hipEventDisableTiming)));
         TBK_TRY(TBK_HIP(hipEventCreateWithFlags(&m->ev_ql[b], hipEventDisableTiming)));
         TBK_TRY(TBK_HIP(hipEventCreateWithFlags(&m->ev_out[b], hipEventDisableTiming)));
+        TBK_TRY(TBK_HIP(hipEventCreateWithFlags(&m->ev_s2[b], hipEventDisableTiming)));
         // (release to system scope: results of small calls are read by the CPU from non-coherent pinned memory right
         // behind hipEventSynchronize on this event -- with a default event that visibility is the runtime's choice)
         if (b == 0) TBK_TRY(TBK_HIP(hipEventCreateWithFlags(&m->ev_sync, hipEventDisableTiming | hipEventReleaseToSystem)));
@@ -375,6 +376,7 @@ extern "C" void tbk_model_destroy(tbk_model* m) {
         if (m->ev_tri[b]) (void)hipEventDestroy(m->ev_tri[b]);
         if (m->ev_ql[b]) (void)hipEventDestroy(m->ev_ql[b]);
         if (m->ev_out[b]) (void)hipEventDestroy(m->ev_out[b]);
+        if (m->ev_s2[b]) (void)hipEventDestroy(m->ev_s2[b]);
         if (b == 0 && m->ev_sync) (void)hipEventDestroy(m->ev_sync);
     }
     for (auto& ev : m->events) {
@@ -389,7 +391,7 @@ extern "C" void tbk_model_destroy(tbk_model* m) {
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     DevBuf* bufs[] = {&m->ws_phase, &m->ws_H, &m->ws_E,   &m->ws_E2,
-                      &m->ws_info,  &m->ws_k, &m->ws_pos, &m->ws_out, &m->ws_out2, &m->ws_flag, &m->ws_orb, &m->ws_part, &m->ws_kfold, &m->ws_kline, &m->ws_band, &m->ws_bandmat[0], &m->ws_bandmat[1], &m->ws_H2, &m->ws_xl, &m->ws_posraw, &m->ws_dos, &m->ws_pdos_u, &m->ws_pdos_w, &m->ws_pdos_grp, &m->ws_occ_w, &m->ws_occ};
+                      &m->ws_info,  &m->ws_k, &m->ws_pos, &m->ws_out, &m->ws_out2, &m->ws_flag, &m->ws_orb, &m->ws_part, &m->ws_c11, &m->ws_kfold, &m->ws_kline, &m->ws_band, &m->ws_bandmat[0], &m->ws_bandmat[1], &m->ws_H2, &m->ws_xl, &m->ws_posraw, &m->ws_dos, &m->ws_pdos_u, &m->ws_pdos_w, &m->ws_pdos_grp, &m->ws_occ_w, &m->ws_occ};
     for (DevBuf* b : bufs) b->release();
     tbk_fold_release(m);
     delete m;
@@ -419,6 +421,10 @@ extern "C" int tbk_model_set_option(tbk_model* m, int option, int64_t value) {
         case TBK_OPT_STRASSEN_LEVELS:
             TBK_ARG(value == 1 || value == 2, "Strassen levels must be 1 or 2");
             m->strassen_levels = (int)value;
+            return TBK_OK;
+        case TBK_OPT_STRASSEN_COMBINE:
+            TBK_ARG(value == 0 || value == 1, "the Strassen combine is 0 (one kernel) or 1 (two passes)");
+            m->strassen_combine_split = value != 0;
             return TBK_OK;
         default:
             tbk_set_error("unknown option %d", option);
@@ -452,7 +458,7 @@ int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
     // (what this handle's grow-only chunk workspaces hold already is as good as free: counted out, the second call of a model
     // chose a smaller chunk than the first -- cfg3: one chunk in the warm-up, two from then on)
     free_b += m->ws_H.bytes + m->ws_H2.bytes + m->ws_phase.bytes + m->ws_band.bytes + m->ws_bandmat[0].bytes + m->ws_bandmat[1].bytes +
-              m->ws_E.bytes + m->ws_xl.bytes + m->ws_part.bytes;
+              m->ws_E.bytes + m->ws_xl.bytes + m->ws_part.bytes + m->ws_c11.bytes;
     // above 64 orbitals a chunk is a few thousand matrices: every kernel of the eigensolver ends on a partly filled
     // round of workgroups, and 2 - 3 times longer chunks were worth 3 - 4 % (cfg3 3846 -> 12500 matrices per chunk,
     // cfg5 1250 -> 5000)
@@ -477,7 +483,8 @@ int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
         // The first two-level chunk of a model builds the operand blocks of the second level (fill_rows): decided here, where
         // the memory is counted -- blocks above a quarter of the free memory are skipped, and the model stays on one level.
         // Such a chunk holds its phase rows 49/16 times (As2[49][K2 / 4][Mq]) and the 49 quarter-size products
-        // P[49][Mq][ncol_pad / 4]; a chunk that does not fit gets shorter, and below TBK_STRASSEN2_MIN_NK it takes one level
+        // P[49][Mq][ncol_pad / 4], and with the two-pass combine of the eigenvalue path the four partial C11 quarters
+        // [4][Mq][ncol_pad / 4] between the passes; a chunk that does not fit gets shorter, and below TBK_STRASSEN2_MIN_NK it takes one level
         size_t free2 = free_b;
         if (m->d_Bs2 == nullptr) {
             const size_t blocks = tbk_strassen2_bytes(m);
@@ -485,7 +492,7 @@ int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig) {
             else free2 -= blocks;
         }
         if (!m->bs2_skipped) {
-            const int64_t per_k_s = per_k + m->k2 * 8 * 33 / 16 + (int64_t)m->ncol_pad * 16 * 49 / 16;
+            const int64_t per_k_s = per_k + m->k2 * 8 * 33 / 16 + (int64_t)m->ncol_pad * 16 * 49 / 16 + (with_eig && m->strassen_combine_split ? (int64_t)m->ncol_pad * 16 * 4 / 16 : 0);
             const int64_t fit = (int64_t)(free2 / 4) / per_k_s / TBK_BM * TBK_BM;
             chunk = std::max<int64_t>(TBK_BM, std::min(chunk, fit));
         }
@@ -674,8 +681,10 @@ static int eigenval_wave_pipeline(tbk_model* m, const tbk_eig_plan_t& plan, cons
     const bool two_stage = plan.family == EIG_TWO_STAGE && !plan.fused && n_chunks > 1;
     TBK_CHECK(tbk_eig_reserve(m, plan, max_chunk, n_chunks > 1 ? 2 : 1));
     if (n_chunks == 1) {
-        // one chunk has nothing to overlap: everything in order on the main stream, no cross-stream events (they
-        // cost more than the kernels of a single-k call)
+        // one chunk has nothing to overlap: everything in order on the main stream, and the pipeline adds no cross-stream
+        // events (they cost more than the kernels of a single-k call).  A chunk long enough for two Strassen levels (from
+        // TBK_STRASSEN2_MIN_NK k-points, ~7 ms of products) does cross to stream_eig and back inside launch_strassen2, for the
+        // first pass of its combine; H is complete on the main stream when build() returns either way.
         double* d_de = debuf[0]->as<double>();
         TBK_CHECK(build(0, nk, d_H));
         TBK_CHECK(tbk_eig_reduce(m, plan, m->stream, d_H, nk, d_de));

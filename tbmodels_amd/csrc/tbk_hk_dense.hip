@@ -618,6 +618,67 @@ __global__ void __launch_bounds__(256) hk_strassen_finish_kernel(const HkArgs a,
 // ((M1 + M4) - M5) + M7, M3 + M5, M2 + M4, ((M1 - M2) + M3) + M6 of the nested form, bit for bit, with 16 x 2 accumulators instead
 // of 49 x 2 live values.  Output quarter 2 a1 + a2 of the k-points, 2 c1 + c2 of the slots (half a1 / c1 of the outer split).
 // Loads are 16 B per thread, contiguous along e'.
+//
+// The four inner quadrants of outer product p1 (0-based) from its seven blocks q[0], q[blk], ..., q[6 blk]:
+__device__ __forceinline__ void strassen2_inner(const d2* q, size_t blk, d2 (&in)[2][2]) {
+    const d2 m1 = q[0], m2 = q[blk], m3 = q[2 * blk], m4 = q[3 * blk], m5 = q[4 * blk], m6 = q[5 * blk], m7 = q[6 * blk];
+    in[0][0] = ((m1 + m4) - m5) + m7;
+    in[0][1] = m3 + m5;
+    in[1][0] = m2 + m4;
+    in[1][1] = ((m1 - m2) + m3) + m6;
+}
+// ... and their step of the outer table, c[a1][c1][a2][c2]; the steps are taken in the order p1 = 0 .. 6
+template <int P1>
+__device__ __forceinline__ void strassen2_outer(d2 (&c)[2][2][2][2], const d2 (&in)[2][2]) {
+#pragma unroll
+    for (int a2 = 0; a2 < 2; ++a2)
+#pragma unroll
+        for (int c2 = 0; c2 < 2; ++c2) {
+            const d2 v = in[a2][c2];
+            if (P1 == 0) c[0][0][a2][c2] = v, c[1][1][a2][c2] = v;
+            if (P1 == 1) c[1][0][a2][c2] = v, c[1][1][a2][c2] -= v;
+            if (P1 == 2) c[0][1][a2][c2] = v, c[1][1][a2][c2] += v;
+            if (P1 == 3) c[0][0][a2][c2] += v, c[1][0][a2][c2] += v;
+            if (P1 == 4) c[0][0][a2][c2] -= v, c[0][1][a2][c2] += v;
+            if (P1 == 5) c[1][1][a2][c2] += v;
+            if (P1 == 6) c[0][0][a2][c2] += v;
+        }
+}
+// One step.  PINNED, for the kernel that has to fit a register budget: the sums the step touched are made opaque behind it
+// and a scheduling fence follows.  Left alone the compiler sinks the additions into the conditional stores at the kernel's end
+// and keeps the loaded products alive until then (the 219 - 232 registers of the single kernel), and hoists the loads of later
+// steps above earlier ones.
+__device__ __forceinline__ void strassen2_pin(d2& v) {
+    double x = v[0], y = v[1];
+    asm volatile("" : "+v"(x), "+v"(y));
+    v = (d2){x, y};
+}
+template <int P1, bool PINNED = false>
+__device__ __forceinline__ void strassen2_step(const d2* mp, size_t blk, d2 (&c)[2][2][2][2]) {
+    d2 in[2][2];
+    strassen2_inner(mp + (size_t)(7 * P1) * blk, blk, in);
+    strassen2_outer<P1>(c, in);
+    if constexpr (PINNED) {
+#pragma unroll
+        for (int a2 = 0; a2 < 2; ++a2)
+#pragma unroll
+            for (int c2 = 0; c2 < 2; ++c2) {
+                if (P1 == 0 || P1 == 3 || P1 == 4 || P1 == 6) strassen2_pin(c[0][0][a2][c2]);
+                if (P1 == 2 || P1 == 4) strassen2_pin(c[0][1][a2][c2]);
+                if (P1 == 1 || P1 == 3) strassen2_pin(c[1][0][a2][c2]);
+                if (P1 == 0 || P1 == 1 || P1 == 2 || P1 == 5) strassen2_pin(c[1][1][a2][c2]);
+            }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+template <int P1, int P1_END>
+__device__ __forceinline__ void strassen2_walk(const d2* mp, size_t blk, d2 (&c)[2][2][2][2]) {
+    if constexpr (P1 < P1_END) {
+        strassen2_step<P1>(mp, blk, c);
+        strassen2_walk<P1 + 1, P1_END>(mp, blk, c);
+    }
+}
+
 template <int MODE, int CONV>
 __global__ void __launch_bounds__(256) hk_strassen2_finish_kernel(const HkArgs a, int64_t mq) {
     const int quarter = a.ncol_pad / 4;
@@ -628,25 +689,7 @@ __global__ void __launch_bounds__(256) hk_strassen2_finish_kernel(const HkArgs a
     const size_t blk = (size_t)mq * quarter;
     const d2* mp = reinterpret_cast<const d2*>(a.P) + (size_t)kq * quarter + e;
     d2 c[2][2][2][2];  // [a1][c1][a2][c2]
-#pragma unroll
-    for (int p1 = 0; p1 < 7; ++p1) {
-        const d2* q = mp + (size_t)(7 * p1) * blk;
-        const d2 m1 = q[0], m2 = q[blk], m3 = q[2 * blk], m4 = q[3 * blk], m5 = q[4 * blk], m6 = q[5 * blk], m7 = q[6 * blk];
-        const d2 in[2][2] = {{((m1 + m4) - m5) + m7, m3 + m5}, {m2 + m4, ((m1 - m2) + m3) + m6}};
-#pragma unroll
-        for (int a2 = 0; a2 < 2; ++a2)
-#pragma unroll
-            for (int c2 = 0; c2 < 2; ++c2) {
-                const d2 v = in[a2][c2];
-                if (p1 == 0) c[0][0][a2][c2] = v, c[1][1][a2][c2] = v;
-                if (p1 == 1) c[1][0][a2][c2] = v, c[1][1][a2][c2] -= v;
-                if (p1 == 2) c[0][1][a2][c2] = v, c[1][1][a2][c2] += v;
-                if (p1 == 3) c[0][0][a2][c2] += v, c[1][0][a2][c2] += v;
-                if (p1 == 4) c[0][0][a2][c2] -= v, c[0][1][a2][c2] += v;
-                if (p1 == 5) c[1][1][a2][c2] += v;
-                if (p1 == 6) c[0][0][a2][c2] += v;
-            }
-    }
+    strassen2_walk<0, 7>(mp, blk, c);
 #pragma unroll
     for (int cq = 0; cq < 4; ++cq) {
         const int32_t ij = a.colmap[e + cq * quarter];
@@ -656,6 +699,84 @@ __global__ void __launch_bounds__(256) hk_strassen2_finish_kernel(const HkArgs a
             const int64_t kout = kq + aq * mq;
             if (kout >= a.nk) continue;
             const d2 v = c[aq >> 1][cq >> 1][aq & 1][cq & 1];
+            store_slot<MODE, CONV>(a, kout, ij, v[0], v[1]);
+        }
+    }
+}
+
+// The same combine in two passes (the eigenvalue path; launch_strassen2).  M7 of the outer table (p1 = 6) enters C11 alone, as
+// the last term of ((M1 + M4) - M5) + M7: after p1 = 0 .. 5 the outer C12, C21 and C22 are final and C11 lacks one addition.
+// The first pass therefore needs only the products below 42 and runs while the last seven are computed; the closing pass adds
+// the quadrants of M7.  Every sum keeps its order, so the two passes store the bits of the single kernel.
+//
+// First pass: p1 = 0 .. 5, the twelve finished quarter blocks to H, the four partial C11 quarters as they are (plane 0,
+// plane 1) to part[2 a2 + c2][k'][e'].  It has to be resident BESIDE two workgroups of hk_dense_kernel per CU: no LDS, and at
+// most 112 registers -- those hold 196 each, allocated in eights as 2 x 200 of a SIMD's 512.  (The attribute counts halves
+// of the unified file on this target: 56 caps the kernel at 112.)  Sixteen sums and seven loads in flight do not fit that, so
+// the steps go in the order 0, 1, 3, 2, 4, 5 and a quadrant leaves as soon as it is final: C21 = M2 + M4 behind step 3, before
+// C12 = M3 + M5 begins with step 2 -- twelve sums live at most.  The order of the terms WITHIN every sum is that of the single
+// kernel (C11: 0, 3, 4; C12: 2, 4; C21: 1, 3; C22: 0, 1, 2, 5), which is all the bits depend on.
+template <int MODE, int CONV>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56)))
+hk_strassen2_first_kernel(const HkArgs a, int64_t mq, d2* __restrict__ part) {
+    const int quarter = a.ncol_pad / 4;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int e = (int)(idx % quarter);
+    const int64_t kq = idx / quarter;
+    if (kq >= mq) return;
+    const size_t blk = (size_t)mq * quarter;
+    const d2* mp = reinterpret_cast<const d2*>(a.P) + (size_t)kq * quarter + e;
+    d2 c[2][2][2][2];  // [a1][c1][a2][c2]
+    const auto store_quadrant = [&](auto a1c, auto c1c) {  // the four quarter blocks of outer quadrant (a1, c1)
+        constexpr int a1 = decltype(a1c)::value, c1 = decltype(c1c)::value;
+#pragma unroll
+        for (int c2 = 0; c2 < 2; ++c2) {
+            const int32_t ij = a.colmap[e + (2 * c1 + c2) * quarter];
+            if (ij < 0) continue;
+#pragma unroll
+            for (int a2 = 0; a2 < 2; ++a2) {
+                const int64_t kout = kq + (2 * a1 + a2) * mq;
+                if (kout < a.nk) store_slot<MODE, CONV>(a, kout, ij, c[a1][c1][a2][c2][0], c[a1][c1][a2][c2][1]);
+            }
+        }
+    };
+    using i0 = std::integral_constant<int, 0>;
+    using i1 = std::integral_constant<int, 1>;
+    strassen2_step<0, true>(mp, blk, c);
+    strassen2_step<1, true>(mp, blk, c);
+    strassen2_step<3, true>(mp, blk, c);
+    store_quadrant(i1{}, i0{});
+    strassen2_step<2, true>(mp, blk, c);
+    strassen2_step<4, true>(mp, blk, c);
+    store_quadrant(i0{}, i1{});
+#pragma unroll
+    for (int a2 = 0; a2 < 2; ++a2)
+#pragma unroll
+        for (int c2 = 0; c2 < 2; ++c2) part[(size_t)(2 * a2 + c2) * blk + (size_t)kq * quarter + e] = c[0][0][a2][c2];
+    strassen2_step<5, true>(mp, blk, c);
+    store_quadrant(i1{}, i1{});
+}
+
+// Closing pass: the seven blocks of p1 = 6 and the parked partial sums -> the four quarter blocks of C11.
+template <int MODE, int CONV>
+__global__ void __launch_bounds__(256) hk_strassen2_close_kernel(const HkArgs a, int64_t mq, const d2* __restrict__ part) {
+    const int quarter = a.ncol_pad / 4;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int e = (int)(idx % quarter);
+    const int64_t kq = idx / quarter;
+    if (kq >= mq) return;
+    const size_t blk = (size_t)mq * quarter;
+    d2 in[2][2];
+    strassen2_inner(reinterpret_cast<const d2*>(a.P) + (size_t)kq * quarter + e + (size_t)(7 * 6) * blk, blk, in);
+#pragma unroll
+    for (int c2 = 0; c2 < 2; ++c2) {
+        const int32_t ij = a.colmap[e + c2 * quarter];
+        if (ij < 0) continue;
+#pragma unroll
+        for (int a2 = 0; a2 < 2; ++a2) {
+            const int64_t kout = kq + a2 * mq;
+            if (kout >= a.nk) continue;
+            const d2 v = part[(size_t)(2 * a2 + c2) * blk + (size_t)kq * quarter + e] + in[a2][c2];
             store_slot<MODE, CONV>(a, kout, ij, v[0], v[1]);
         }
     }
@@ -943,15 +1064,49 @@ int launch_strassen2(tbk_model* m, const tbk_operand_t& op, const HkArgs& a0) {
     a.b_prod_stride = a.k2 * quarter * 2;
     TBK_CHECK(m->ws_part.reserve((size_t)49 * mq * quarter * 2 * sizeof(double)));
     a.P = m->ws_part.as<double>();
-    hipLaunchKernelGGL((hk_dense_kernel<HK_TRI, 2, true>), dim3(49 * grid), dim3(256), lds, s, a);
-    TBK_HIP(hipGetLastError());
     HkArgs f = a0;
     f.P = a.P;
     const int64_t threads = mq * quarter;
-    hipLaunchKernelGGL((hk_strassen2_finish_kernel<MODE, CONV>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, f, mq);
-    TBK_HIP(hipGetLastError());
+    const dim3 f_grid((unsigned)((threads + 255) / 256));
     m->counters[TBK_CNT_STRASSEN_LAUNCHES] += 1;
     m->counters[TBK_CNT_STRASSEN2_LAUNCHES] += 1;
+    // The eigenvalue path combines in two passes (TBK_OPT_STRASSEN_COMBINE).  The products go as two launches of one unit range:
+    // [0, n_a) holds every unit of the products below 42 in whole rounds of workgroup slots, the rest keeps the ragged end of
+    // the single launch.  The first pass waits for the first launch on the reduction's stream -- idle while a chunk's products
+    // run, the previous reduction having been waited for before H(c) may be written -- and runs beside the second; the closing
+    // pass follows both on the main stream, so whoever waits for H waits for the same stream as before.  n_a must be a
+    // multiple of 8 for the second launch's blocks to fall on the XCDs of their units (tile_of_block); where it is not, or
+    // where rounding leaves the second launch nothing, the chunk takes the single launch and the single combine.
+    // (HK_FULL stays whole: the rotation of convention 1 in store_element does not commute with a split sum.)
+    const int64_t n_units = (int64_t)49 * grid;
+    if constexpr (MODE == HK_TRI && CONV == 2) {
+      const int slots = 2 * m->n_cu;
+      const int64_t n_a = ((int64_t)42 * grid + slots - 1) / slots * slots;
+      if (m->strassen_combine_split && n_a < n_units && n_a % 8 == 0) {
+        TBK_CHECK(m->ws_c11.reserve((size_t)4 * mq * quarter * 2 * sizeof(double)));
+        d2* part = m->ws_c11.as<d2>();
+        hipLaunchKernelGGL((hk_dense_kernel<HK_TRI, 2, true>), dim3((unsigned)n_a), dim3(256), lds, s, a);
+        TBK_HIP(hipGetLastError());
+        TBK_HIP(hipEventRecord(m->ev_s2[0], s));
+        HkArgs b = a;
+        b.block_offset = (int)n_a;
+        hipLaunchKernelGGL((hk_dense_kernel<HK_TRI, 2, true>), dim3((unsigned)(n_units - n_a)), dim3(256), lds, s, b);
+        TBK_HIP(hipGetLastError());
+        TBK_HIP(hipStreamWaitEvent(m->stream_eig, m->ev_s2[0], 0));
+        hipLaunchKernelGGL((hk_strassen2_first_kernel<MODE, CONV>), f_grid, dim3(256), 0, m->stream_eig, f, mq, part);
+        TBK_HIP(hipGetLastError());
+        TBK_HIP(hipEventRecord(m->ev_s2[1], m->stream_eig));
+        TBK_HIP(hipStreamWaitEvent(s, m->ev_s2[1], 0));
+        hipLaunchKernelGGL((hk_strassen2_close_kernel<MODE, CONV>), f_grid, dim3(256), 0, s, f, mq, part);
+        TBK_HIP(hipGetLastError());
+        m->counters[TBK_CNT_STRASSEN2_SPLIT] += 1;
+        return TBK_OK;
+      }
+    }
+    hipLaunchKernelGGL((hk_dense_kernel<HK_TRI, 2, true>), dim3((unsigned)n_units), dim3(256), lds, s, a);
+    TBK_HIP(hipGetLastError());
+    hipLaunchKernelGGL((hk_strassen2_finish_kernel<MODE, CONV>), f_grid, dim3(256), 0, s, f, mq);
+    TBK_HIP(hipGetLastError());
     return TBK_OK;
 }
 

@@ -217,7 +217,8 @@ struct tbk_model {
     bool fold_enabled = true;
     bool strassen = true;  // TBK_OPT_STRASSEN
     int strassen_levels = 2;  // TBK_OPT_STRASSEN_LEVELS
-    int64_t counters[TBK_CNT_COUNT] = {0, 0, 0, 0, 0, 0};  // tbk_model_counter
+    bool strassen_combine_split = true;  // TBK_OPT_STRASSEN_COMBINE
+    int64_t counters[TBK_CNT_COUNT] = {0, 0, 0, 0, 0, 0, 0};  // tbk_model_counter
 
     // --- options ---
     int eigensolver = TBK_EIG_AUTO;
@@ -234,6 +235,7 @@ struct tbk_model {
     hipEvent_t ev_tri[2] = {nullptr, nullptr};  // H[buf] consumed, (d, e)[buf] written
     hipEvent_t ev_out[2] = {nullptr, nullptr};  // tbk_hamilton: chunk in ws_out / ws_out2 computed
     hipEvent_t ev_ql[2] = {nullptr, nullptr};   // (d, e)[buf] consumed, eigenvalues written
+    hipEvent_t ev_s2[2] = {nullptr, nullptr};   // two-pass Strassen combine (launch_strassen2): the first product launch done, the first pass done
     hipEvent_t ev_sync = nullptr;               // host waits on the main stream go through this event (tbk_api.hip)
     rocblas_handle blas = nullptr;
     DevBuf ws_phase;  // [K2][nk_pad] cos/sin rows
@@ -254,6 +256,7 @@ struct tbk_model {
     void* h_stage = nullptr;
     size_t h_stage_bytes = 0;
     DevBuf ws_part;   // split-K partial tiles of the dense H(k) kernel (small k batches)
+    DevBuf ws_c11;    // two-pass Strassen combine: the four partial C11 quarters between its passes, [4][Mq][ncol_pad / 4] (re, im)
     DevBuf ws_kfold;  // k-points of a folded run without the folded component
     DevBuf ws_kline;  // one mesh line without both folded components (second-level fold)
     DevBuf ws_band;   // two-stage reduction: pending [V | W] panel of every matrix of a chunk
