@@ -22,89 +22,35 @@
 #include <cmath>
 #include <vector>
 
-#include "tbk_dos_common.h"
+#include "tbk_tetra.h"
 
 namespace {
 
 constexpr int DOS_THREADS = 256;
 constexpr int DOS_TILE = 4096;  // energy bins per LDS tile: 4096 * (8 + 4) bytes = 48 KiB; longer grids take gridDim.y tiles
-// Fixed point (tbk_dos_common.h): a contribution n_T in [0, 1] is stored as round(n_T * 2^40), i.e. with an error of at most 2^-41
+// Fixed point (tbk_tetra.h): a contribution n_T in [0, 1] is stored as round(n_T * 2^40), i.e. with an error of at most 2^-41
 // each.  A bin of nos sums at most S NK n_orb of them and is divided by S NK: |error| <= n_orb * 2^-41 = 4.5e-13 n_orb in the worst
 // case (every contribution off by half a unit in the same direction), a twentieth of the 1e-11 n_orb the kernel is tested to.
 // Overflow: a workgroup takes at most DOS_MAX_ITEMS (cell, band) pairs, so one of its bins receives at most
 // 6 * 2^20 contributions of at most 2^40: 6 * 2^60 < 2^64.
-// The grid, the search on it, DosGeom and DosWindow are shared with tbk_pdos.hip: tbk_dos_common.h.
 
-__device__ __forceinline__ void dos_sort2(double& a, double& b) {
-    const double lo = fmin(a, b), hi = fmax(a, b);
-    a = lo;
-    b = hi;
-}
-
-__device__ __forceinline__ void dos_add(unsigned long long* part, int bin, double frac) {
-    atomicAdd(&part[bin], dos_fixed(frac));
-}
-
-// one tetrahedron: DESIGN 10.1 (the ranges are half-open as written there; the comparisons select the branch, so a branch with
-// a zero gap is empty and never evaluated; every ratio in [0, 1] is formed on its own, tbk_dos_common.h)
-__device__ __forceinline__ void dos_tetrahedron(double e1, double e2, double e3, double e4, const DosWindow& w, unsigned long long* part,
-                                                unsigned* step) {
-    dos_sort2(e1, e2);
-    dos_sort2(e3, e4);
-    dos_sort2(e1, e3);
-    dos_sort2(e2, e4);
-    dos_sort2(e2, e3);
-    const int j_lo = dos_first_at_or_above(e1, w.e_min, w.e_step, w.inv_step, w.n_e);
-    const int j_hi = dos_first_at_or_above(e4, w.e_min, w.e_step, w.inv_step, w.n_e);
+// one simplex of NC corners: DESIGN 10.1.  n_T and the reciprocals behind it are TetraGaps' (tbk_tetra.h), taken once per simplex
+// and only if the window holds one of its bins: the bin loop has no division
+template <int NC>
+__device__ __forceinline__ void dos_simplex(const double (&corners)[NC], const DosWindow& w, unsigned long long* part, unsigned* step) {
+    double e[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) e[c] = corners[c];
+    tetra_sort(e);
+    const int j_lo = dos_first_at_or_above(e[0], w.e_min, w.e_step, w.inv_step, w.n_e);
+    const int j_hi = dos_first_at_or_above(e[NC - 1], w.e_min, w.e_step, w.inv_step, w.n_e);
     if (j_hi >= w.tile_lo && j_hi < w.tile_lo + w.tile_n) atomicAdd(&step[j_hi - w.tile_lo], 1u);
     const int lo = max(j_lo, w.tile_lo), hi = min(j_hi, w.tile_lo + w.tile_n);
     if (lo >= hi) return;
-    // reciprocals of the scaled gaps, once per simplex (tbk_dos_common.h): the bin loop has no division
-    const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE, s4 = e4 * DOS_GAP_SCALE;
-    const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r41 = 1.0 / (s4 - s1), r32 = 1.0 / (s3 - s2), r42 = 1.0 / (s4 - s2),
-                 r43 = 1.0 / (s4 - s3);
+    const TetraGaps<NC> gaps(e);
     for (int j = lo; j < hi; ++j) {
-        const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e4 here
-        const double Es = E * DOS_GAP_SCALE;
-        double n;
-        if (E < e2) {
-            const double x = Es - s1;
-            n = (x * r21) * (x * r31) * (x * r41);
-        } else if (E < e3) {
-            const double x1 = Es - s1, x2 = Es - s2, y3 = s3 - Es, y4 = s4 - Es;
-            const double q32 = x2 * r32;
-            n = (x1 * r41) * (x1 * r31 + q32 * (y3 * r31)) + (x2 * r42) * q32 * (y4 * r41);
-        } else {
-            const double y = s4 - Es;
-            n = 1.0 - (y * r41) * (y * r42) * (y * r43);
-        }
-        dos_add(part, j - w.tile_lo, n);
-    }
-}
-
-__device__ __forceinline__ void dos_triangle(double e1, double e2, double e3, const DosWindow& w, unsigned long long* part, unsigned* step) {
-    dos_sort2(e1, e2);
-    dos_sort2(e2, e3);
-    dos_sort2(e1, e2);
-    const int j_lo = dos_first_at_or_above(e1, w.e_min, w.e_step, w.inv_step, w.n_e);
-    const int j_hi = dos_first_at_or_above(e3, w.e_min, w.e_step, w.inv_step, w.n_e);
-    if (j_hi >= w.tile_lo && j_hi < w.tile_lo + w.tile_n) atomicAdd(&step[j_hi - w.tile_lo], 1u);
-    const int lo = max(j_lo, w.tile_lo), hi = min(j_hi, w.tile_lo + w.tile_n);
-    if (lo >= hi) return;
-    const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE;
-    const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r32 = 1.0 / (s3 - s2);
-    for (int j = lo; j < hi; ++j) {
-        const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e3 here
-        const double Es = E * DOS_GAP_SCALE;
-        double n;
-        if (E < e2) {
-            const double x = Es - s1;
-            n = (x * r21) * (x * r31);
-        } else {
-            const double y = s3 - Es;
-            n = 1.0 - (y * r31) * (y * r32);
-        }
-        dos_add(part, j - w.tile_lo, n);
+        const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e_top here
+        atomicAdd(&part[j - w.tile_lo], dos_fixed(gaps.fraction(E)));
     }
 }
 
@@ -133,35 +79,24 @@ __global__ void __launch_bounds__(DOS_THREADS) dos_accumulate_kernel(const doubl
     const int64_t first = (int64_t)blockIdx.x * g.items_per_wg;
     const int64_t last = min(first + g.items_per_wg, g.items);
     for (int64_t it = first + tid; it < last; it += DOS_THREADS) {
-        const int64_t cell64 = it / g.n_orb;
-        const int band = (int)(it - cell64 * g.n_orb);
-        int c = (int)cell64;  // NK < 2^31 (checked by the launcher)
-        const int i2 = c % g.n2;
-        c /= g.n2;
-        const int i1 = c % g.n1;
-        const int i0 = c / g.n1;  // < n0_cells
-        const int j0 = i0 + 1 == g.n0_planes ? 0 : i0 + 1;
-        const int j1 = i1 + 1 == g.n1 ? 0 : i1 + 1;
-        const int j2 = i2 + 1 == g.n2 ? 0 : i2 + 1;
-        auto at = [&](int a0, int a1, int a2) -> double {
-            const int64_t k = ((int64_t)a0 * g.n1 + a1) * g.n2 + a2;
-            return E[k * g.n_orb + band];
-        };
+        const TetraItem t = tetra_item(g, it);
+        const int i0 = t.i0, i1 = t.i1, i2 = t.i2, j0 = t.j0, j1 = t.j1, j2 = t.j2;
+        auto at = [&](int a0, int a1, int a2) -> double { return E[tetra_row(g, a0, a1, a2) * g.n_orb + t.band]; };
         if (DIM == 3) {
             // corner c_xyz: x, y, z = step along axis 0, 1, 2
             const double c000 = at(i0, i1, i2), c100 = at(j0, i1, i2), c010 = at(i0, j1, i2), c110 = at(j0, j1, i2);
             const double c001 = at(i0, i1, j2), c101 = at(j0, i1, j2), c011 = at(i0, j1, j2), c111 = at(j0, j1, j2);
             // the six orders (a, b, c) of the axes: corners 0, e_a, e_a + e_b, e_a + e_b + e_c
-            dos_tetrahedron(c000, c100, c110, c111, w, part, step);  // (0, 1, 2)
-            dos_tetrahedron(c000, c100, c101, c111, w, part, step);  // (0, 2, 1)
-            dos_tetrahedron(c000, c010, c110, c111, w, part, step);  // (1, 0, 2)
-            dos_tetrahedron(c000, c010, c011, c111, w, part, step);  // (1, 2, 0)
-            dos_tetrahedron(c000, c001, c101, c111, w, part, step);  // (2, 0, 1)
-            dos_tetrahedron(c000, c001, c011, c111, w, part, step);  // (2, 1, 0)
+            dos_simplex<4>({c000, c100, c110, c111}, w, part, step);  // (0, 1, 2)
+            dos_simplex<4>({c000, c100, c101, c111}, w, part, step);  // (0, 2, 1)
+            dos_simplex<4>({c000, c010, c110, c111}, w, part, step);  // (1, 0, 2)
+            dos_simplex<4>({c000, c010, c011, c111}, w, part, step);  // (1, 2, 0)
+            dos_simplex<4>({c000, c001, c101, c111}, w, part, step);  // (2, 0, 1)
+            dos_simplex<4>({c000, c001, c011, c111}, w, part, step);  // (2, 1, 0)
         } else {
             const double c00 = at(i0, i1, 0), c10 = at(j0, i1, 0), c01 = at(i0, j1, 0), c11 = at(j0, j1, 0);
-            dos_triangle(c00, c10, c11, w, part, step);  // (0, 1)
-            dos_triangle(c00, c01, c11, w, part, step);  // (1, 0)
+            dos_simplex<3>({c00, c10, c11}, w, part, step);  // (0, 1)
+            dos_simplex<3>({c00, c01, c11}, w, part, step);  // (1, 0)
         }
     }
     __syncthreads();
@@ -178,15 +113,13 @@ __global__ void __launch_bounds__(DOS_THREADS) dos_reduce_kernel(const unsigned 
                                                                  int n_wg, int n_e, double* __restrict__ frac, long long* __restrict__ count) {
     const int j = (int)blockIdx.x * DOS_THREADS + (int)threadIdx.x;
     if (j >= n_e) return;
-    unsigned long long hi = 0, lo = 0;
+    DosWords sum;
     long long c = 0;
     for (int wg = 0; wg < n_wg; ++wg) {
-        const unsigned long long p = part_g[(int64_t)wg * n_e + j];
-        hi += p >> DOS_SPLIT_BITS;
-        lo += p & ((1ull << DOS_SPLIT_BITS) - 1);
+        sum.add(part_g[(int64_t)wg * n_e + j]);
         c += (long long)step_g[(int64_t)wg * n_e + j];
     }
-    frac[j] = (double)hi * (1.0 / (double)(1ull << (DOS_FRAC_BITS - DOS_SPLIT_BITS))) + (double)lo * (1.0 / (double)(1ull << DOS_FRAC_BITS));
+    frac[j] = sum.value();
     count[j] = c;
 }
 
@@ -218,21 +151,13 @@ struct DosLaunch {
 // dim in {2, 3}; cells0 cells along axis 0 out of planes0 planes held in E (planes0 == cells0: the axis wraps onto itself)
 int dos_plan(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb, int64_t n_e, DosLaunch* out) {
     DosLaunch L;
-    L.g.n0_cells = (int)cells0;
-    L.g.n0_planes = (int)planes0;
-    L.g.n1 = mesh[1];
-    L.g.n2 = dim == 3 ? mesh[2] : 1;
-    L.g.n_orb = n_orb;
-    L.g.items = cells0 * L.g.n1 * L.g.n2 * n_orb;
+    L.g = tetra_geom(dim, mesh, cells0, planes0, n_orb);
     L.n_e = (int)n_e;
     L.n_tiles = (int)((n_e + DOS_TILE - 1) / DOS_TILE);
-    // workgroups: enough to fill the chip, no more rows than 2^24 bins of partials, never more than DOS_MAX_ITEMS items each
+    // no more rows than 2^24 bins of partials
     const int64_t by_memory = std::max<int64_t>(1, (int64_t(1) << 24) / n_e);
-    int64_t n_wg = std::min<int64_t>((L.g.items + DOS_THREADS - 1) / DOS_THREADS, std::min<int64_t>(1024, by_memory));
-    n_wg = std::max<int64_t>(n_wg, (L.g.items + DOS_MAX_ITEMS - 1) / DOS_MAX_ITEMS);
-    TBK_ARG(n_wg <= (int64_t(1) << DOS_SPLIT_BITS), "mesh x orbitals too large for one density-of-states call");
-    L.g.items_per_wg = (L.g.items + n_wg - 1) / n_wg;
-    L.n_wg = (int)((L.g.items + L.g.items_per_wg - 1) / L.g.items_per_wg);
+    TBK_CHECK(tetra_partition(L.g.items, DOS_THREADS, std::min<int64_t>(1024, by_memory), "mesh x orbitals too large for one density-of-states call",
+                              &L.g.items_per_wg, &L.n_wg));
     const size_t bins = (size_t)L.n_wg * (size_t)n_e;
     L.off_step = dos_align256(bins * sizeof(unsigned long long));
     L.off_frac = L.off_step + dos_align256(bins * sizeof(unsigned));
@@ -267,20 +192,79 @@ int dos_launch(hipStream_t s, int dim, const DosLaunch& L, const double* d_E, do
 
 }  // namespace
 
-// the checks every entry point shares; *nk_total = points of the whole mesh
-int tbk_dos_check(int dim, const int32_t* mesh, double e_step, int64_t n_e, const void* nos_out, int64_t* nk_total) {
-    TBK_ARG(dim == 2 || dim == 3, "the density of states needs a 2- or 3-dimensional mesh");
-    TBK_ARG(mesh != nullptr && nos_out != nullptr, "mesh / nos is NULL");
+// ---- what the four tetrahedron files share on the host (tbk_tetra.h) ---------------------------------------------------------------
+int tetra_check_mesh(int dim, const int32_t* mesh, const char* what, int64_t* nk_total) {
+    TBK_ARG(dim == 2 || dim == 3, what);
+    TBK_ARG(mesh != nullptr, "mesh is NULL");
     int64_t nk = 1;
     for (int d = 0; d < dim; ++d) {
         TBK_ARG(mesh[d] >= 1, "a mesh entry is < 1");
         nk *= mesh[d];
         TBK_ARG(nk < (int64_t(1) << 31), "the mesh has 2^31 points or more");
     }
+    *nk_total = nk;
+    return TBK_OK;
+}
+
+int tbk_dos_check(int dim, const int32_t* mesh, double e_step, int64_t n_e, const void* nos_out, int64_t* nk_total) {
+    if (dim == 2 || dim == 3) TBK_ARG(mesh != nullptr && nos_out != nullptr, "mesh / nos is NULL");  // (a wrong dim is reported first)
+    TBK_CHECK(tetra_check_mesh(dim, mesh, "the density of states needs a 2- or 3-dimensional mesh", nk_total));
     TBK_ARG(n_e >= 2, "the energy grid needs at least two points");
     TBK_ARG(n_e <= DOS_MAX_NE, "the energy grid has more than 2^20 points");
     TBK_ARG(std::isfinite(e_step) && e_step > 0.0, "the energy step must be positive and finite");
-    *nk_total = nk;
+    return TBK_OK;
+}
+
+int tetra_check_device(int device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
+        (void)hipGetLastError();
+        tbk_set_error("no HIP device visible: libtbk has no CPU path");
+        return TBK_ERR_DEVICE;
+    }
+    TBK_ARG(device >= 0 && device < n_dev, "device out of range");
+    TBK_HIP(hipSetDevice(device));
+    return TBK_OK;
+}
+
+DosGeom tetra_geom(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb) {
+    DosGeom g;
+    g.n0_cells = (int)cells0;
+    g.n0_planes = (int)planes0;
+    g.n1 = mesh[1];
+    g.n2 = dim == 3 ? mesh[2] : 1;
+    g.n_orb = n_orb;
+    g.items = cells0 * g.n1 * g.n2 * n_orb;
+    g.items_per_wg = 0;
+    return g;
+}
+
+int tetra_partition(int64_t items, int threads, int64_t cap, const char* what, int64_t* items_per_wg, int* n_wg_out) {
+    int64_t n_wg = std::min<int64_t>((items + threads - 1) / threads, cap);
+    n_wg = std::max<int64_t>(n_wg, (items + DOS_MAX_ITEMS - 1) / DOS_MAX_ITEMS);
+    TBK_ARG(n_wg <= (int64_t(1) << DOS_SPLIT_BITS), what);
+    *items_per_wg = (items + n_wg - 1) / n_wg;
+    *n_wg_out = (int)((items + *items_per_wg - 1) / *items_per_wg);
+    return TBK_OK;
+}
+
+int TetraHandles::open(tbk_model* const* handles, int n_handles, const int32_t* mesh, const char* what) {
+    TBK_ARG(handles != nullptr && n_handles >= 1, "no handles");
+    for (int i = 0; i < n_handles; ++i) {
+        TBK_ARG(handles[i] != nullptr, "a handle is NULL");
+        TBK_ARG(handles[i]->dim == handles[0]->dim && handles[i]->n_orb == handles[0]->n_orb, "handles of different models (dim / n_orb differ)");
+        TBK_ARG(!handles[i]->kdotp, "a k.p model has no Brillouin zone");
+    }
+    std::vector<tbk_model*> order(handles, handles + n_handles);
+    std::sort(order.begin(), order.end());
+    order.erase(std::unique(order.begin(), order.end()), order.end());
+    TBK_ARG((int)order.size() == n_handles, "a handle appears twice");
+    dim = handles[0]->dim;
+    n_orb = handles[0]->n_orb;
+    TBK_CHECK(tetra_check_mesh(dim, mesh, what, &nk_total));
+    plane_pts = nk_total / mesh[0];
+    cut = TetraSlabs(mesh[0], n_handles);
+    for (tbk_model* m : order) locks.emplace_back(m->mu);
     return TBK_OK;
 }
 
@@ -316,14 +300,7 @@ extern "C" int tbk_dos_from_eigenvalues(int device, int dim, const int32_t* mesh
     TBK_ARG(E != nullptr, "E is NULL");
     TBK_ARG(n_orb >= 1, "n_orb < 1");
     TBK_ARG(std::isfinite(e_min), "e_min is not finite");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-        (void)hipGetLastError();
-        tbk_set_error("no HIP device visible: libtbk has no CPU path");
-        return TBK_ERR_DEVICE;
-    }
-    TBK_ARG(device >= 0 && device < n_dev, "device out of range");
-    TBK_HIP(hipSetDevice(device));
+    TBK_CHECK(tetra_check_device(device));
     DosLaunch L;
     TBK_CHECK(dos_plan(dim, mesh, mesh[0], mesh[0], n_orb, n_e, &L));
     const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double);

@@ -12,12 +12,12 @@
 // LDS bins: the up to 16 probe energies are kernel arguments, and every thread keeps one 64-bit fixed-point sum and one count per
 // probe in registers (every loop over the probes is unrolled; no accumulator is indexed dynamically).  Per simplex the corners are
 // sorted, count[m] += (E_m >= e_top), and n_T is evaluated for the probes with e1 <= E_m < e_top only; the six reciprocals of the
-// scaled corner gaps are taken once per simplex and only if some probe of the wave's lanes needs them.  The branch arithmetic is
-// that of dos_tetrahedron / dos_triangle, expression for expression.
+// scaled corner gaps are taken once per simplex and only if some probe of the wave's lanes needs them.  The sort and n_T are
+// those of dos_simplex: tetra_sort and TetraGaps::fraction (tbk_tetra.h).
 //
 // Reproducibility.  No floating-point sum crosses a thread: the wave adds its lanes' integers with shuffles, the workgroup adds its
 // waves' with integer LDS atomics, every workgroup stores its row [16] with plain stores, and a second kernel sums the rows, the
-// high 44 and low 20 bits of every 64-bit sum apart (dos_reduce_kernel's split).  Per probe the result is the exact integer triple
+// high 44 and low 20 bits of every 64-bit sum apart (DosWords, tbk_tetra.h).  Per probe the result is the exact integer triple
 // (count, high, low): independent of wave order, of the workgroup count and of which other probes shared the launch.
 // Overflow: the bound of tbk_dos.hip -- a workgroup takes at most DOS_MAX_ITEMS items, so one of its sums is below 6 * 2^60.
 //
@@ -27,10 +27,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
-#include "tbk_dos_common.h"
+#include "tbk_tetra.h"
 
 namespace {
 
@@ -43,82 +42,26 @@ struct FermiProbes {
     double e[FERMI_PROBES];
 };
 
-__device__ __forceinline__ void fermi_sort2(double& a, double& b) {
-    const double lo = fmin(a, b), hi = fmax(a, b);
-    a = lo;
-    b = hi;
-}
-
-// one tetrahedron at every probe (half-open ranges, the comparisons on the unscaled numbers select the branch, every
-// ratio in [0, 1] is formed on its own from energies scaled by DOS_GAP_SCALE: tbk_dos_common.h)
-__device__ __forceinline__ void fermi_tetrahedron(double e1, double e2, double e3, double e4, const FermiProbes& p,
-                                                  unsigned long long (&frac)[FERMI_PROBES], unsigned (&count)[FERMI_PROBES]) {
-    fermi_sort2(e1, e2);
-    fermi_sort2(e3, e4);
-    fermi_sort2(e1, e3);
-    fermi_sort2(e2, e4);
-    fermi_sort2(e2, e3);
+// one simplex of NC corners at every probe: count[m] += (E_m >= e_top), frac[m] += n_T(E_m) for e1 <= E_m < e_top
+template <int NC>
+__device__ __forceinline__ void fermi_simplex(const double (&corners)[NC], const FermiProbes& p, unsigned long long (&frac)[FERMI_PROBES],
+                                              unsigned (&count)[FERMI_PROBES]) {
+    double e[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) e[c] = corners[c];
+    tetra_sort(e);
     bool inside = false;
 #pragma unroll
     for (int m = 0; m < FERMI_PROBES; ++m) {
-        count[m] += p.e[m] >= e4 ? 1u : 0u;
-        inside = inside || (p.e[m] >= e1 && p.e[m] < e4);
+        count[m] += p.e[m] >= e[NC - 1] ? 1u : 0u;
+        inside = inside || (p.e[m] >= e[0] && p.e[m] < e[NC - 1]);
     }
     if (!inside) return;
-    const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE, s4 = e4 * DOS_GAP_SCALE;
-    const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r41 = 1.0 / (s4 - s1), r32 = 1.0 / (s3 - s2), r42 = 1.0 / (s4 - s2),
-                 r43 = 1.0 / (s4 - s3);
+    const TetraGaps<NC> gaps(e);
 #pragma unroll
     for (int m = 0; m < FERMI_PROBES; ++m) {
         const double E = p.e[m];
-        if (E >= e1 && E < e4) {
-            const double Es = E * DOS_GAP_SCALE;
-            double n;
-            if (E < e2) {
-                const double x = Es - s1;
-                n = (x * r21) * (x * r31) * (x * r41);
-            } else if (E < e3) {
-                const double x1 = Es - s1, x2 = Es - s2, y3 = s3 - Es, y4 = s4 - Es;
-                const double q32 = x2 * r32;
-                n = (x1 * r41) * (x1 * r31 + q32 * (y3 * r31)) + (x2 * r42) * q32 * (y4 * r41);
-            } else {
-                const double y = s4 - Es;
-                n = 1.0 - (y * r41) * (y * r42) * (y * r43);
-            }
-            frac[m] += dos_fixed(n);
-        }
-    }
-}
-
-__device__ __forceinline__ void fermi_triangle(double e1, double e2, double e3, const FermiProbes& p, unsigned long long (&frac)[FERMI_PROBES],
-                                               unsigned (&count)[FERMI_PROBES]) {
-    fermi_sort2(e1, e2);
-    fermi_sort2(e2, e3);
-    fermi_sort2(e1, e2);
-    bool inside = false;
-#pragma unroll
-    for (int m = 0; m < FERMI_PROBES; ++m) {
-        count[m] += p.e[m] >= e3 ? 1u : 0u;
-        inside = inside || (p.e[m] >= e1 && p.e[m] < e3);
-    }
-    if (!inside) return;
-    const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE;
-    const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r32 = 1.0 / (s3 - s2);
-#pragma unroll
-    for (int m = 0; m < FERMI_PROBES; ++m) {
-        const double E = p.e[m];
-        if (E >= e1 && E < e3) {
-            const double Es = E * DOS_GAP_SCALE;
-            double n;
-            if (E < e2) {
-                const double x = Es - s1;
-                n = (x * r21) * (x * r31);
-            } else {
-                const double y = s3 - Es;
-                n = 1.0 - (y * r31) * (y * r32);
-            }
-            frac[m] += dos_fixed(n);
-        }
+        if (E >= e[0] && E < e[NC - 1]) frac[m] += dos_fixed(gaps.fraction(E));
     }
 }
 
@@ -146,20 +89,9 @@ __global__ void __launch_bounds__(FERMI_THREADS) nos_probe_kernel(const double* 
     const int64_t first = (int64_t)blockIdx.x * g.items_per_wg;
     const int64_t last = min(first + g.items_per_wg, g.items);
     for (int64_t it = first + tid; it < last; it += FERMI_THREADS) {
-        const int64_t cell64 = it / g.n_orb;
-        const int band = (int)(it - cell64 * g.n_orb);
-        int c = (int)cell64;  // NK < 2^31 (checked by the launcher)
-        const int i2 = c % g.n2;
-        c /= g.n2;
-        const int i1 = c % g.n1;
-        const int i0 = c / g.n1;  // < n0_cells
-        const int j0 = i0 + 1 == g.n0_planes ? 0 : i0 + 1;
-        const int j1 = i1 + 1 == g.n1 ? 0 : i1 + 1;
-        const int j2 = i2 + 1 == g.n2 ? 0 : i2 + 1;
-        auto at = [&](int a0, int a1, int a2) -> double {
-            const int64_t k = ((int64_t)a0 * g.n1 + a1) * g.n2 + a2;
-            return E[k * g.n_orb + band];
-        };
+        const TetraItem t = tetra_item(g, it);
+        const int i0 = t.i0, i1 = t.i1, i2 = t.i2, j0 = t.j0, j1 = t.j1, j2 = t.j2;
+        auto at = [&](int a0, int a1, int a2) -> double { return E[tetra_row(g, a0, a1, a2) * g.n_orb + t.band]; };
         if (DIM == 3) {
             // corner c_xyz: x, y, z = step along axis 0, 1, 2
             const double c000 = at(i0, i1, i2), c100 = at(j0, i1, i2), c010 = at(i0, j1, i2), c110 = at(j0, j1, i2);
@@ -170,12 +102,12 @@ __global__ void __launch_bounds__(FERMI_THREADS) nos_probe_kernel(const double* 
             for (int s = 0; s < 6; ++s) {
                 const double ca = s < 2 ? c100 : s < 4 ? c010 : c001;
                 const double cb = s == 0 || s == 2 ? c110 : s == 1 || s == 4 ? c101 : c011;
-                fermi_tetrahedron(c000, ca, cb, c111, p, frac, count);
+                fermi_simplex<4>({c000, ca, cb, c111}, p, frac, count);
             }
         } else {
             const double c00 = at(i0, i1, 0), c10 = at(j0, i1, 0), c01 = at(i0, j1, 0), c11 = at(j0, j1, 0);
 #pragma unroll 1
-            for (int s = 0; s < 2; ++s) fermi_triangle(c00, s == 0 ? c10 : c01, c11, p, frac, count);
+            for (int s = 0; s < 2; ++s) fermi_simplex<3>({c00, s == 0 ? c10 : c01, c11}, p, frac, count);
         }
     }
     // the workgroup's sums, in integers: across the wave with shuffles, across the waves with LDS integer atomics
@@ -210,16 +142,15 @@ __global__ void __launch_bounds__(FERMI_THREADS) nos_probe_reduce_kernel(const u
     if (tid < FERMI_PROBES * 3) total[tid] = 0ull;
     __syncthreads();
     const int m = tid % FERMI_PROBES;
-    unsigned long long hi = 0, lo = 0, c = 0;
+    DosWords sum;
+    unsigned long long c = 0;
     for (int wg = tid / FERMI_PROBES; wg < n_wg; wg += FERMI_THREADS / FERMI_PROBES) {
-        const unsigned long long v = part_g[(int64_t)wg * FERMI_PROBES + m];
-        hi += v >> DOS_SPLIT_BITS;
-        lo += v & ((1ull << DOS_SPLIT_BITS) - 1);
+        sum.add(part_g[(int64_t)wg * FERMI_PROBES + m]);
         c += (unsigned long long)count_g[(int64_t)wg * FERMI_PROBES + m];
     }
     atomicAdd(&total[m * 3 + 0], c);
-    atomicAdd(&total[m * 3 + 1], hi);
-    atomicAdd(&total[m * 3 + 2], lo);
+    atomicAdd(&total[m * 3 + 1], sum.hi);
+    atomicAdd(&total[m * 3 + 2], sum.lo);
     __syncthreads();
     if (tid < FERMI_PROBES * 3) sums[tid] = total[tid];
 }
@@ -278,21 +209,12 @@ struct FermiLaunch {
     size_t off_count = 0, off_sums = 0, off_pmin = 0, off_pmax = 0, off_emin = 0, off_emax = 0, ws_bytes = 0;
 };
 
-// dim in {2, 3}; cells0 cells along axis 0 out of planes0 planes held in E -- the partition of dos_plan (tbk_dos.hip)
+// dim in {2, 3}; cells0 cells along axis 0 out of planes0 planes held in E
 int fermi_plan(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb, FermiLaunch* out) {
     FermiLaunch L;
-    L.g.n0_cells = (int)cells0;
-    L.g.n0_planes = (int)planes0;
-    L.g.n1 = mesh[1];
-    L.g.n2 = dim == 3 ? mesh[2] : 1;
-    L.g.n_orb = n_orb;
-    L.rows = cells0 * L.g.n1 * L.g.n2;
-    L.g.items = L.rows * n_orb;
-    int64_t n_wg = std::min<int64_t>((L.g.items + FERMI_THREADS - 1) / FERMI_THREADS, 1024);
-    n_wg = std::max<int64_t>(n_wg, (L.g.items + DOS_MAX_ITEMS - 1) / DOS_MAX_ITEMS);
-    TBK_ARG(n_wg <= (int64_t(1) << DOS_SPLIT_BITS), "mesh x orbitals too large for one Fermi-level call");
-    L.g.items_per_wg = (L.g.items + n_wg - 1) / n_wg;
-    L.n_wg = (int)((L.g.items + L.g.items_per_wg - 1) / L.g.items_per_wg);
+    L.g = tetra_geom(dim, mesh, cells0, planes0, n_orb);
+    L.rows = L.g.items / n_orb;
+    TBK_CHECK(tetra_partition(L.g.items, FERMI_THREADS, 1024, "mesh x orbitals too large for one Fermi-level call", &L.g.items_per_wg, &L.n_wg));
     const int per_step = n_orb <= FERMI_THREADS ? FERMI_THREADS / n_orb : 1;
     L.edge_wg = (int)std::min<int64_t>(FERMI_EDGE_WG, (L.rows + per_step - 1) / per_step);
     L.off_count = dos_align256((size_t)L.n_wg * FERMI_PROBES * sizeof(unsigned long long));
@@ -319,18 +241,19 @@ struct FermiCount {
 };
 
 FermiCount fermi_count(const unsigned long long* triple) {  // {count, high, low} of nos_probe_reduce_kernel
-    const unsigned long long mask = (1ull << DOS_SPLIT_BITS) - 1;
+    DosWords sum;
+    sum.hi = triple[1];
+    sum.lo = triple[2];
+    const unsigned __int128 v = sum.whole();
     FermiCount q;
-    q.rem = ((triple[1] & mask) << DOS_SPLIT_BITS) + triple[2];  // < 2^41
-    q.whole = triple[0] + (triple[1] >> DOS_SPLIT_BITS) + (q.rem >> DOS_FRAC_BITS);
-    q.rem &= (1ull << DOS_FRAC_BITS) - 1;
+    q.whole = triple[0] + (unsigned long long)(v >> DOS_FRAC_BITS);
+    q.rem = (unsigned long long)(v & (((unsigned __int128)1 << DOS_FRAC_BITS) - 1));
     return q;
 }
 
 // N = Q / (2^40 simplices): the 86-bit integer is rounded to double once, the division once more
 double fermi_nos(const FermiCount& q, int64_t simplices) {
-    const unsigned __int128 v = ((unsigned __int128)q.whole << DOS_FRAC_BITS) + q.rem;
-    return std::ldexp((double)v, -DOS_FRAC_BITS) / (double)simplices;
+    return DosWords::to_double(((unsigned __int128)q.whole << DOS_FRAC_BITS) + q.rem) / (double)simplices;
 }
 
 // the smallest integer >= n_electrons * simplices * 2^40 (n_electrons > 0 finite, simplices < 2^34): Q >= t  <=>  Q >= ceil(t)
@@ -527,31 +450,7 @@ int fermi_search(std::vector<FermiSlab>& slabs, int n_orb, int64_t simplices, do
     return TBK_OK;
 }
 
-int fermi_check_device(int device) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-        (void)hipGetLastError();
-        tbk_set_error("no HIP device visible: libtbk has no CPU path");
-        return TBK_ERR_DEVICE;
-    }
-    TBK_ARG(device >= 0 && device < n_dev, "device out of range");
-    TBK_HIP(hipSetDevice(device));
-    return TBK_OK;
-}
-
-// the mesh checks of tbk_dos_check that apply (there is no energy grid)
-int fermi_check_mesh(int dim, const int32_t* mesh, int64_t* nk_total) {
-    TBK_ARG(dim == 2 || dim == 3, "the density of states needs a 2- or 3-dimensional mesh");
-    TBK_ARG(mesh != nullptr, "mesh is NULL");
-    int64_t nk = 1;
-    for (int d = 0; d < dim; ++d) {
-        TBK_ARG(mesh[d] >= 1, "a mesh entry is < 1");
-        nk *= mesh[d];
-        TBK_ARG(nk < (int64_t(1) << 31), "the mesh has 2^31 points or more");
-    }
-    *nk_total = nk;
-    return TBK_OK;
-}
+const char* const FERMI_MESH = "the density of states needs a 2- or 3-dimensional mesh";
 
 int fermi_check_electrons(double n_electrons, int n_orb) {
     TBK_ARG(std::isfinite(n_electrons) && n_electrons > 0.0 && n_electrons < (double)n_orb, "n_electrons must lie inside (0, n_orb)");
@@ -585,8 +484,7 @@ struct FermiOwned {
 // The mesh on staged handles: handle i takes the slab of tbk_dos_multi.  The caller's thread holds every handle's lock for the
 // whole call (the eigenvalues stay in the handles' ws_out across all passes), taken in address order; the eigenvalue calls are
 // enqueued handle after handle and checked afterwards, the probes of a pass likewise.
-struct FermiStaged {
-    std::vector<std::unique_lock<std::recursive_mutex>> locks;
+struct FermiStaged : TetraHandles {
     std::vector<FermiSlab> slabs;
     int64_t simplices = 0;
     ~FermiStaged() {
@@ -595,29 +493,13 @@ struct FermiStaged {
                 if (e) (void)hipEventDestroy(e);
     }
     int make(tbk_model* const* handles, int n_handles, const int32_t* mesh) {
-        TBK_ARG(handles != nullptr && n_handles >= 1, "no handles");
-        for (int i = 0; i < n_handles; ++i) {
-            TBK_ARG(handles[i] != nullptr, "a handle is NULL");
-            TBK_ARG(handles[i]->dim == handles[0]->dim && handles[i]->n_orb == handles[0]->n_orb, "handles of different models (dim / n_orb differ)");
-        }
-        std::vector<tbk_model*> order(handles, handles + n_handles);
-        std::sort(order.begin(), order.end());
-        order.erase(std::unique(order.begin(), order.end()), order.end());
-        TBK_ARG((int)order.size() == n_handles, "a handle appears twice");
-        for (tbk_model* m : order) locks.emplace_back(m->mu);
-        tbk_model* m0 = handles[0];
-        TBK_ARG(!m0->kdotp, "a k.p model has no Brillouin zone");
-        int64_t nk_total = 0;
-        TBK_CHECK(fermi_check_mesh(m0->dim, mesh, &nk_total));
-        const int dim = m0->dim, n_orb = m0->n_orb;
+        TBK_CHECK(open(handles, n_handles, mesh, FERMI_MESH));
         simplices = (int64_t)(dim == 3 ? 6 : 2) * nk_total;
-        const int64_t n0 = mesh[0], per = (n0 + n_handles - 1) / n_handles, plane_pts = nk_total / n0;
-        slabs.reserve((size_t)n_handles);
-        for (int i = 0; i < n_handles; ++i) {
-            const int64_t p_lo = std::min<int64_t>(n0, (int64_t)i * per), p_count = std::min<int64_t>(n0, p_lo + per) - p_lo;
-            if (p_count <= 0) break;  // handles whose slab is empty are skipped
+        const int64_t n0 = mesh[0];
+        slabs.reserve((size_t)cut.busy());
+        for (int i = 0; i < cut.busy(); ++i) {  // handles whose slab is empty are skipped
+            const int64_t p_lo = cut.lo(i), p_count = cut.count(i);
             tbk_model* m = handles[i];
-            TBK_ARG(!m->kdotp, "a k.p model has no Brillouin zone");
             slabs.emplace_back();
             FermiSlab& s = slabs.back();
             s.m = m;
@@ -661,7 +543,7 @@ int tbk_fermi_check_electrons(double n_electrons, int n_orb) { return fermi_chec
 
 int tbk_fermi_resident(const tbk_fermi_slab_t* slabs, int n_slabs, int dim, const int32_t* mesh, int n_orb, int mode, double value, double* out4) {
     int64_t nk_total = 0;
-    TBK_CHECK(fermi_check_mesh(dim, mesh, &nk_total));
+    TBK_CHECK(tetra_check_mesh(dim, mesh, FERMI_MESH, &nk_total));
     std::vector<FermiSlab> v((size_t)n_slabs);
     for (int i = 0; i < n_slabs; ++i) {
         FermiSlab& s = v[(size_t)i];
@@ -690,12 +572,12 @@ int tbk_fermi_resident(const tbk_fermi_slab_t* slabs, int n_slabs, int dim, cons
 extern "C" int tbk_nos_at_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* energies,
                                            int64_t n_p, double* nos_out) {
     int64_t nk = 0;
-    TBK_CHECK(fermi_check_mesh(dim, mesh, &nk));
+    TBK_CHECK(tetra_check_mesh(dim, mesh, FERMI_MESH, &nk));
     TBK_ARG(E != nullptr && energies != nullptr && nos_out != nullptr, "E / energies / nos is NULL");
     TBK_ARG(n_orb >= 1, "n_orb < 1");
     TBK_ARG(n_p >= 1, "no probe energies");
     for (int64_t j = 0; j < n_p; ++j) TBK_ARG(std::isfinite(energies[j]), "a probe energy is not finite");
-    TBK_CHECK(fermi_check_device(device));
+    TBK_CHECK(tetra_check_device(device));
     FermiOwned own;
     TBK_CHECK(own.make(device, dim, mesh, n_orb, E, nk));
     const int64_t simplices = (int64_t)(dim == 3 ? 6 : 2) * nk;
@@ -711,10 +593,10 @@ extern "C" int tbk_nos_at_from_eigenvalues(int device, int dim, const int32_t* m
 extern "C" int tbk_band_edges_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double* emin_out,
                                                double* emax_out) {
     int64_t nk = 0;
-    TBK_CHECK(fermi_check_mesh(dim, mesh, &nk));
+    TBK_CHECK(tetra_check_mesh(dim, mesh, FERMI_MESH, &nk));
     TBK_ARG(E != nullptr && emin_out != nullptr && emax_out != nullptr, "E / emin / emax is NULL");
     TBK_ARG(n_orb >= 1, "n_orb < 1");
-    TBK_CHECK(fermi_check_device(device));
+    TBK_CHECK(tetra_check_device(device));
     FermiOwned own;
     TBK_CHECK(own.make(device, dim, mesh, n_orb, E, nk));
     return fermi_edges(own.slabs, n_orb, emin_out, emax_out);
@@ -723,11 +605,11 @@ extern "C" int tbk_band_edges_from_eigenvalues(int device, int dim, const int32_
 extern "C" int tbk_fermi_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double n_electrons, double* out,
                                           int32_t* passes_out) {
     int64_t nk = 0;
-    TBK_CHECK(fermi_check_mesh(dim, mesh, &nk));
+    TBK_CHECK(tetra_check_mesh(dim, mesh, FERMI_MESH, &nk));
     TBK_ARG(E != nullptr && out != nullptr, "E / out is NULL");
     TBK_ARG(n_orb >= 1, "n_orb < 1");
     TBK_CHECK(fermi_check_electrons(n_electrons, n_orb));
-    TBK_CHECK(fermi_check_device(device));
+    TBK_CHECK(tetra_check_device(device));
     FermiOwned own;
     TBK_CHECK(own.make(device, dim, mesh, n_orb, E, nk));
     int passes = 0;

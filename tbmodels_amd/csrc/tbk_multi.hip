@@ -15,7 +15,7 @@
 #include <thread>
 #include <vector>
 
-#include "tbk_internal.h"
+#include "tbk_tetra.h"
 
 namespace {
 
@@ -26,15 +26,13 @@ struct SlabResult {
 
 template <class Call>
 int run_slabs(int n, int64_t nk, Call&& call) {  // call(i, lo, count): slab i on handle i
-    const int64_t per = (nk + n - 1) / n;
+    const TetraSlabs cut(nk, n);
     // slabs that hold k-points: a one-k call under TBK_DEVICES=0..7 has ONE, and must not pay seven thread starts
-    const int busy = (int)std::min<int64_t>(n, (nk + per - 1) / std::max<int64_t>(per, 1));
+    const int busy = cut.busy();
     if (busy <= 1) return call(0, 0, nk);
     std::vector<SlabResult> results((size_t)busy);
     auto work = [&](int i) {
-        const int64_t lo = std::min<int64_t>(nk, (int64_t)i * per), hi = std::min<int64_t>(nk, lo + per);
-        if (hi <= lo) return;
-        const int status = call(i, lo, hi - lo);
+        const int status = call(i, cut.lo(i), cut.count(i));
         results[(size_t)i].status = status;
         if (status != TBK_OK) results[(size_t)i].message = tbk_last_error();  // this thread's message
     };
@@ -124,8 +122,8 @@ extern "C" int tbk_dos_multi(tbk_model* const* handles, int n_handles, const int
     TBK_ARG(handles[0]->dim == 2 || handles[0]->dim == 3, "the density of states needs a 2- or 3-dimensional mesh");
     TBK_ARG(mesh[0] >= 1, "a mesh entry is < 1");
     TBK_ARG(n_e >= 2 && n_e <= (int64_t(1) << 20), "the energy grid needs 2 to 2^20 points");
-    const int64_t n0 = mesh[0], per = (n0 + n_handles - 1) / n_handles;
-    const int busy = (int)((n0 + per - 1) / per);
+    const int64_t n0 = mesh[0];
+    const int busy = TetraSlabs(n0, n_handles).busy();
     std::vector<double> share;
     try {
         share.assign((size_t)busy * (size_t)n_e, 0.0);
@@ -155,8 +153,8 @@ extern "C" int tbk_pdos_multi(tbk_model* const* handles, int n_handles, const in
     TBK_ARG(mesh[0] >= 1, "a mesh entry is < 1");
     TBK_ARG(n_e >= 2 && n_e <= (int64_t(1) << 20), "the energy grid needs 2 to 2^20 points");
     TBK_CHECK(tbk_pdos_check_groups(handles[0]->n_orb, group_offsets, group_orbitals, n_groups));
-    const int64_t n0 = mesh[0], per = (n0 + n_handles - 1) / n_handles;
-    const int busy = (int)((n0 + per - 1) / per);
+    const int64_t n0 = mesh[0];
+    const int busy = TetraSlabs(n0, n_handles).busy();
     const size_t n_out = (size_t)n_groups * (size_t)n_e;
     std::vector<double> share;
     try {

@@ -14,9 +14,9 @@
 // (7) energies once, walks the simplices in the order s = 4 sigma + p (3 sigma + p), sigma in the order of tbk_dos.hip's list
 // (012, 021, 102, 120, 201, 210; 01, 10), by two nested loops that are NOT unrolled -- the corners are selected by uniform indices, so
 // the branch code exists once -- and adds the own corner's weight of every simplex to ONE double in that order.  Per simplex: the
-// stable sort of tbk_pdos.hip (adjacent exchanges on a strict comparison, corners in simplex order) carrying the rank of the own
+// stable sort of tbk_tetra.h (adjacent exchanges on a strict comparison, corners in simplex order) carrying the rank of the own
 // corner; 0 or the full weight from two comparisons unless e1 <= mu < e_top; else the reciprocals of the DOS_GAP_SCALE-scaled gaps
-// and the corner weights of pdos_simplex, expression for expression.  A full tetrahedron gives 1/4 to every corner, so above the
+// and the corner weights that pdos_simplex takes as well: TetraGaps::corner_weights.  A full tetrahedron gives 1/4 to every corner, so above the
 // spectrum the sum is 24 / 4 = 6 exactly and w = 6 / (6 NK) is the double nearest 1 / NK.  A triangle's corner weights are carried
 // TIMES THREE (a full corner is 1, not the inexact 1/3) and the divisor is 3 S NK = 6 NK: the same property.  One division, one
 // plain store per item: no atomics, no LDS, no scratch; for given E and mu the bits of w depend on nothing else.
@@ -41,10 +41,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
-#include "tbk_dos_common.h"
+#include "tbk_tetra.h"
 
 namespace {
 
@@ -65,96 +64,36 @@ struct OccGeom {
 __device__ __forceinline__ int occ_prev(int i, int n) { return i == 0 ? n - 1 : i - 1; }
 __device__ __forceinline__ int occ_next(int i, int n) { return i + 1 == n ? 0 : i + 1; }
 
-// one adjacent exchange of the stable sort; r follows the own corner
-template <int A, int B>
-__device__ __forceinline__ void occ_exchange(double& a, double& b, int& r) {
-    const bool sw = b < a;  // strict: equal energies keep their order
-    const double lo = sw ? b : a, hi = sw ? a : b;
-    a = lo;
-    b = hi;
-    r = sw ? (r == A ? B : r == B ? A : r) : r;
-}
-
-// Bloechl's weight of corner `own` (0 .. 3, in simplex order) of one tetrahedron at mu: in [0, 1/4].  The branches are those of
-// pdos_simplex (tbk_pdos.hip): half-open ranges, the comparisons on the unscaled numbers select, every ratio is formed on its own.
-__device__ __forceinline__ double occ_tetrahedron(double e1, double e2, double e3, double e4, int own, double mu) {
-    int r = own;
-    occ_exchange<0, 1>(e1, e2, r);
-    occ_exchange<1, 2>(e2, e3, r);
-    occ_exchange<2, 3>(e3, e4, r);
-    occ_exchange<0, 1>(e1, e2, r);
-    occ_exchange<1, 2>(e2, e3, r);
-    occ_exchange<0, 1>(e1, e2, r);
-    if (mu < e1) return 0.0;
-    if (mu >= e4) return 0.25;
-    const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE, s4 = e4 * DOS_GAP_SCALE;
-    const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r41 = 1.0 / (s4 - s1), r32 = 1.0 / (s3 - s2), r42 = 1.0 / (s4 - s2),
-                 r43 = 1.0 / (s4 - s3);
-    const double Es = mu * DOS_GAP_SCALE;
-    double w1, w2, w3, w4;
-    if (mu < e2) {
-        const double x = Es - s1;
-        const double q21 = x * r21, q31 = x * r31, q41 = x * r41;
-        const double C = 0.25 * q21 * q31 * q41;
-        w1 = C * (4.0 - (q21 + q31 + q41));
-        w2 = C * q21;
-        w3 = C * q31;
-        w4 = C * q41;
-    } else if (mu < e3) {
-        const double x1 = Es - s1, x2 = Es - s2, y3 = s3 - Es, y4 = s4 - Es;
-        const double p31 = x1 * r31, p41 = x1 * r41, p32 = x2 * r32, p42 = x2 * r42;  // from below
-        const double m31 = y3 * r31, m32 = y3 * r32, m41 = y4 * r41, m42 = y4 * r42;  // from above
-        const double T = 0.25 * p41;
-        const double C1 = T * p31;
-        const double C2 = T * p32 * m31;
-        const double C3 = 0.25 * p42 * p32 * m41;
-        const double C12 = C1 + C2, C23 = C2 + C3, C123 = C12 + C3;
-        w1 = C1 + C12 * m31 + C123 * m41;
-        w2 = C123 + C23 * m32 + C3 * m42;
-        w3 = C12 * p31 + C23 * p32;
-        w4 = C123 * p41 + C3 * p42;
-    } else {
-        const double y = s4 - Es;
-        const double q41 = y * r41, q42 = y * r42, q43 = y * r43;
-        const double C = 0.25 * q41 * q42 * q43;
-        w1 = 0.25 - C * q41;
-        w2 = 0.25 - C * q42;
-        w3 = 0.25 - C * q43;
-        w4 = 0.25 - C * (4.0 - (q41 + q42 + q43));
+// the payload of the stable sort (tbk_tetra.h): the rank of the own corner
+struct OccRank {
+    int r;
+    template <int A, int B>
+    __device__ __forceinline__ void follow(bool sw) {
+        r = sw ? (r == A ? B : r == B ? A : r) : r;
     }
-    const double w = r == 0 ? w1 : r == 1 ? w2 : r == 2 ? w3 : w4;
-    return fmin(fmax(w, 0.0), 0.25);  // (NaN -> 0)
-}
+};
 
-// THREE TIMES the weight of corner `own` (0 .. 2) of one triangle at mu: in [0, 1], exactly 1 for a full triangle
-__device__ __forceinline__ double occ_triangle(double e1, double e2, double e3, int own, double mu) {
-    int r = own;
-    occ_exchange<0, 1>(e1, e2, r);
-    occ_exchange<1, 2>(e2, e3, r);
-    occ_exchange<0, 1>(e1, e2, r);
-    if (mu < e1) return 0.0;
-    if (mu >= e3) return 1.0;
-    const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE;
-    const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r32 = 1.0 / (s3 - s2);
-    const double Es = mu * DOS_GAP_SCALE;
-    double w1, w2, w3;
-    if (mu < e2) {
-        const double x = Es - s1;
-        const double q21 = x * r21, q31 = x * r31;
-        const double C = q21 * q31;
-        w1 = C * (3.0 - (q21 + q31));
-        w2 = C * q21;
-        w3 = C * q31;
-    } else {
-        const double y = s3 - Es;
-        const double q31 = y * r31, q32 = y * r32;
-        const double C = q31 * q32;
-        w1 = 1.0 - C * q31;
-        w2 = 1.0 - C * q32;
-        w3 = 1.0 - C * (3.0 - (q31 + q32));
-    }
-    const double w = r == 0 ? w1 : r == 1 ? w2 : w3;
-    return fmin(fmax(w, 0.0), 1.0);
+// Bloechl's weight of corner `own` (0 .. NC - 1, in simplex order) of one simplex at mu.  A tetrahedron's is in [0, 1/4]; a
+// triangle's is carried TIMES THREE: in [0, 1], exactly 1 for a full triangle.
+template <int NC>
+__device__ __forceinline__ double occ_simplex(const double (&corners)[NC], int own, double mu) {
+    constexpr double full = NC == 4 ? 0.25 : 1.0;
+    double e[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) e[c] = corners[c];
+    OccRank rank{own};
+    tetra_stable_sort(e, rank);
+    if (mu < e[0]) return 0.0;
+    if (mu >= e[NC - 1]) return full;
+    const TetraGaps<NC> gaps(e);
+    double wc[NC];
+    if constexpr (NC == 4)
+        gaps.corner_weights(mu, wc);
+    else
+        gaps.template corner_weights<1>(mu, wc);
+    const int r = rank.r;
+    const double w = r == 0 ? wc[0] : r == 1 ? wc[1] : NC == 3 || r == 2 ? wc[2] : wc[NC - 1];
+    return fmin(fmax(w, 0.0), full);  // (NaN -> 0)
 }
 
 __device__ __forceinline__ double occ_pick(int i, double x, double y, double z) { return i == 0 ? x : i == 1 ? y : z; }
@@ -203,7 +142,7 @@ __global__ void __launch_bounds__(OCC_THREADS) tetra_weights_kernel(const double
                     const double c1 = p == 0 ? pa : p == 1 ? v : p == 2 ? mb : mbc;
                     const double c2 = p == 0 ? pab : p == 1 ? pb : p == 2 ? v : mc;
                     const double c3 = p == 0 ? pxyz : p == 1 ? pbc : p == 2 ? pc : v;
-                    acc += occ_tetrahedron(c0, c1, c2, c3, p, mu);
+                    acc += occ_simplex<4>({c0, c1, c2, c3}, p, mu);
                 }
             }
         } else {
@@ -219,7 +158,7 @@ __global__ void __launch_bounds__(OCC_THREADS) tetra_weights_kernel(const double
                     const double c0 = p == 0 ? v : p == 1 ? ma : mxy;
                     const double c1 = p == 0 ? pa : p == 1 ? v : mb;
                     const double c2 = p == 0 ? pxy : p == 1 ? pb : v;
-                    acc += occ_triangle(c0, c1, c2, p, mu);
+                    acc += occ_simplex<3>({c0, c1, c2}, p, mu);
                 }
             }
         }
@@ -267,17 +206,14 @@ __global__ void __launch_bounds__(OCC_THREADS) occ_band_reduce_kernel(const unsi
                                                                       double* __restrict__ eb_out) {
     const int band = (int)blockIdx.x * OCC_THREADS + (int)threadIdx.x;
     if (band >= n_orb) return;
-    const unsigned long long mask = (1ull << DOS_SPLIT_BITS) - 1;
-    unsigned long long hi = 0, lo = 0;
+    DosWords f;
     double eb = 0.0;
     for (int64_t blk = 0; blk < n_blocks; ++blk) {
-        const unsigned long long v = part_f[blk * n_orb + band];
-        hi += v >> DOS_SPLIT_BITS;
-        lo += v & mask;
+        f.add(part_f[blk * n_orb + band]);
         eb += part_eb[blk * n_orb + band];
     }
-    sums[band] = hi;
-    sums[n_orb + band] = lo;
+    sums[band] = f.hi;
+    sums[n_orb + band] = f.lo;
     eb_out[band] = eb;
 }
 
@@ -320,15 +256,10 @@ __global__ void __launch_bounds__(OCC_THREADS) occ_reduce_kernel(const unsigned 
                                                                  unsigned long long* __restrict__ sums) {
     const int i = (int)blockIdx.x * OCC_THREADS + (int)threadIdx.x;
     if (i >= n) return;
-    const unsigned long long mask = (1ull << DOS_SPLIT_BITS) - 1;
-    unsigned long long hi = 0, lo = 0;
-    for (int64_t wg = 0; wg < n_wg; ++wg) {
-        const unsigned long long v = buf[wg * n + i];
-        hi += v >> DOS_SPLIT_BITS;
-        lo += v & mask;
-    }
-    sums[i] = hi;
-    sums[n + i] = lo;
+    DosWords q;
+    for (int64_t wg = 0; wg < n_wg; ++wg) q.add(buf[wg * n + i]);
+    sums[i] = q.hi;
+    sums[n + i] = q.lo;
 }
 
 // ---- host: one slab of the mesh on one device ----------------------------------------------------------------------------------
@@ -432,45 +363,25 @@ struct OccTotals {
         std::vector<unsigned long long> words(4 * (size_t)n);
         std::memcpy(words.data(), host.data(), words.size() * sizeof(unsigned long long));
         for (int i = 0; i < n; ++i) {
-            f[(size_t)i] += ((unsigned __int128)words[i] << DOS_SPLIT_BITS) + words[n + i];
-            q[(size_t)i] += ((unsigned __int128)words[2 * n + i] << DOS_SPLIT_BITS) + words[3 * n + i];
+            DosWords fw, qw;
+            fw.hi = words[i], fw.lo = words[n + i];
+            qw.hi = words[2 * n + i], qw.lo = words[3 * n + i];
+            f[(size_t)i] += fw.whole();
+            q[(size_t)i] += qw.whole();
             eb[(size_t)i] = first ? host[4 * (size_t)n + i] : eb[(size_t)i] + host[4 * (size_t)n + i];
         }
     }
     // x = words / (2^40 NK): the integer is rounded to double once, the division once more
     void finish(int n, double nk_total, double* q_out, double* f_out, double* eb_out) const {
         for (int i = 0; i < n; ++i) {
-            f_out[i] = std::ldexp((double)f[(size_t)i], -DOS_FRAC_BITS) / nk_total;
-            q_out[i] = std::ldexp((double)q[(size_t)i], -DOS_FRAC_BITS) / nk_total;
+            f_out[i] = DosWords::to_double(f[(size_t)i]) / nk_total;
+            q_out[i] = DosWords::to_double(q[(size_t)i]) / nk_total;
             eb_out[i] = eb[(size_t)i];
         }
     }
 };
 
-int occ_check_device(int device) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-        (void)hipGetLastError();
-        tbk_set_error("no HIP device visible: libtbk has no CPU path");
-        return TBK_ERR_DEVICE;
-    }
-    TBK_ARG(device >= 0 && device < n_dev, "device out of range");
-    TBK_HIP(hipSetDevice(device));
-    return TBK_OK;
-}
-
-int occ_check_mesh(int dim, const int32_t* mesh, int64_t* nk_total) {
-    TBK_ARG(dim == 2 || dim == 3, "the tetrahedron weights need a 2- or 3-dimensional mesh");
-    TBK_ARG(mesh != nullptr, "mesh is NULL");
-    int64_t nk = 1;
-    for (int d = 0; d < dim; ++d) {
-        TBK_ARG(mesh[d] >= 1, "a mesh entry is < 1");
-        nk *= mesh[d];
-        TBK_ARG(nk < (int64_t(1) << 31), "the mesh has 2^31 points or more");
-    }
-    *nk_total = nk;
-    return TBK_OK;
-}
+const char* const OCC_MESH = "the tetrahedron weights need a 2- or 3-dimensional mesh";
 
 struct OccBufs {  // device memory of the entry points that bring their own eigensystem
     DevBuf d_E, d_w, d_ws, d_U;
@@ -533,38 +444,16 @@ struct OccSlab {
 // Handle i takes the slab of tbk_dos_multi.  Its eigenvalues: the planes [p_lo, p_lo + p_count] come from ONE call of the
 // eigenvalue path on the k list tbk_fermi_multi gives it (the same call, so the same bits: mu is tbk_fermi's), the neighbour plane
 // p_lo - 1 from a second call, in front of them in ws_out.  A handle that holds the whole axis needs neither neighbour.
-struct OccStaged {
-    std::vector<std::unique_lock<std::recursive_mutex>> locks;
+struct OccStaged : TetraHandles {
     std::vector<OccSlab> slabs;
-    int dim = 0, n_orb = 0;
-    int64_t nk_total = 0, plane_pts = 0;
 
-    int check(tbk_model* const* handles, int n_handles, const int32_t* mesh) {
-        TBK_ARG(handles != nullptr && n_handles >= 1, "no handles");
-        for (int i = 0; i < n_handles; ++i) {
-            TBK_ARG(handles[i] != nullptr, "a handle is NULL");
-            TBK_ARG(handles[i]->dim == handles[0]->dim && handles[i]->n_orb == handles[0]->n_orb, "handles of different models (dim / n_orb differ)");
-            TBK_ARG(!handles[i]->kdotp, "a k.p model has no Brillouin zone");
-        }
-        std::vector<tbk_model*> order(handles, handles + n_handles);
-        std::sort(order.begin(), order.end());
-        order.erase(std::unique(order.begin(), order.end()), order.end());
-        TBK_ARG((int)order.size() == n_handles, "a handle appears twice");
-        dim = handles[0]->dim;
-        n_orb = handles[0]->n_orb;
-        TBK_CHECK(occ_check_mesh(dim, mesh, &nk_total));
-        plane_pts = nk_total / mesh[0];
-        for (tbk_model* m : order) locks.emplace_back(m->mu);
-        return TBK_OK;
-    }
-
-    // after check(): the eigenvalues of every slab, checked
+    // the handles and the mesh, checked and locked; then the eigenvalues of every slab, checked
     int make(tbk_model* const* handles, int n_handles, const int32_t* mesh) {
-        const int64_t n0 = mesh[0], per = (n0 + n_handles - 1) / n_handles;
-        slabs.reserve((size_t)n_handles);
-        for (int i = 0; i < n_handles; ++i) {
-            const int64_t p_lo = std::min<int64_t>(n0, (int64_t)i * per), p_count = std::min<int64_t>(n0, p_lo + per) - p_lo;
-            if (p_count <= 0) break;  // handles whose slab is empty are skipped
+        TBK_CHECK(open(handles, n_handles, mesh, OCC_MESH));
+        const int64_t n0 = mesh[0];
+        slabs.reserve((size_t)cut.busy());
+        for (int i = 0; i < cut.busy(); ++i) {  // handles whose slab is empty are skipped
+            const int64_t p_lo = cut.lo(i), p_count = cut.count(i);
             tbk_model* m = handles[i];
             slabs.emplace_back();
             OccSlab& s = slabs.back();
@@ -687,11 +576,11 @@ struct OccStaged {
 
 extern "C" int tbk_tetra_weights_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double energy, double* w_out) {
     int64_t nk = 0;
-    TBK_CHECK(occ_check_mesh(dim, mesh, &nk));
+    TBK_CHECK(tetra_check_mesh(dim, mesh, OCC_MESH, &nk));
     TBK_ARG(E != nullptr && w_out != nullptr, "E / w is NULL");
     TBK_ARG(n_orb >= 1, "n_orb < 1");
     TBK_ARG(std::isfinite(energy), "the energy is not finite");
-    TBK_CHECK(occ_check_device(device));
+    TBK_CHECK(tetra_check_device(device));
     OccPlan L;
     TBK_CHECK(occ_plan(dim, mesh, mesh[0], mesh[0], 0, n_orb, &L));
     const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double);
@@ -707,13 +596,13 @@ extern "C" int tbk_tetra_weights_from_eigenvalues(int device, int dim, const int
 extern "C" int tbk_occupations_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double energy,
                                                 int64_t k_chunk, double* q_out, double* f_out, double* eb_out) {
     int64_t nk = 0;
-    TBK_CHECK(occ_check_mesh(dim, mesh, &nk));
+    TBK_CHECK(tetra_check_mesh(dim, mesh, OCC_MESH, &nk));
     TBK_ARG(E != nullptr && U != nullptr, "E / U is NULL");
     TBK_ARG(q_out != nullptr && f_out != nullptr && eb_out != nullptr, "q / f / eb is NULL");
     TBK_ARG(n_orb >= 1, "n_orb < 1");
     TBK_ARG(std::isfinite(energy), "the energy is not finite");
     TBK_ARG(k_chunk >= 0, "k_chunk < 0");
-    TBK_CHECK(occ_check_device(device));
+    TBK_CHECK(tetra_check_device(device));
     OccPlan L;
     TBK_CHECK(occ_plan(dim, mesh, mesh[0], mesh[0], 0, n_orb, &L));
     const int64_t chunk = k_chunk == 0 ? nk : std::min(k_chunk, nk);
@@ -746,7 +635,6 @@ extern "C" int tbk_tetra_weights_multi(tbk_model* const* handles, int n_handles,
     TBK_ARG(w_out != nullptr, "w is NULL");
     TBK_ARG(std::isfinite(energy), "the energy is not finite");
     OccStaged staged;
-    TBK_CHECK(staged.check(handles, n_handles, mesh));
     TBK_CHECK(staged.make(handles, n_handles, mesh));
     TBK_CHECK(staged.weights(energy, w_out));
     return staged.finish();
@@ -766,7 +654,6 @@ extern "C" int tbk_occupations_multi(tbk_model* const* handles, int n_handles, c
     else
         TBK_ARG(std::isfinite(value), "the energy is not finite");
     OccStaged staged;
-    TBK_CHECK(staged.check(handles, n_handles, mesh));
     TBK_CHECK(staged.make(handles, n_handles, mesh));
     TBK_CHECK(staged.find_mu(mesh, mode, value, mu_out));
     TBK_CHECK(staged.weights(mu_out[0], nullptr));

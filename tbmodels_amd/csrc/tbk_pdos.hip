@@ -32,7 +32,7 @@
 #include <cstring>
 #include <vector>
 
-#include "tbk_dos_common.h"
+#include "tbk_tetra.h"
 
 namespace {
 
@@ -72,23 +72,23 @@ __global__ void __launch_bounds__(PDOS_THREADS) pdos_weights_kernel(const double
 }
 
 // ---- accumulate --------------------------------------------------------------------------------------------------------------
-template <int GT, int NC, int A, int B>
-__device__ __forceinline__ void pdos_exchange(double (&e)[NC], double (&a)[GT][NC]) {
-    const bool sw = e[B] < e[A];  // strict: equal energies keep their order
-    const double lo = sw ? e[B] : e[A], hi = sw ? e[A] : e[B];
-    e[A] = lo;
-    e[B] = hi;
+// the payload of the stable sort (tbk_tetra.h): every corner's GT weights travel with its energy
+template <int GT, int NC>
+struct PdosColumns {
+    double (&a)[GT][NC];
+    template <int A, int B>
+    __device__ __forceinline__ void follow(bool sw) {
 #pragma unroll
-    for (int g = 0; g < GT; ++g) {
-        const double x = sw ? a[g][B] : a[g][A], y = sw ? a[g][A] : a[g][B];
-        a[g][A] = x;
-        a[g][B] = y;
+        for (int g = 0; g < GT; ++g) {
+            const double x = sw ? a[g][B] : a[g][A], y = sw ? a[g][A] : a[g][B];
+            a[g][A] = x;
+            a[g][B] = y;
+        }
     }
-}
+};
 
 // One simplex of NC corners (4: tetrahedron, 3: triangle) whose mesh points are kc[]: DESIGN 11.1.  part / step: [n_groups][tile_n].
-// The ranges are half-open and the comparisons select the branch, so a reciprocal of a zero difference (inf) is never used; every
-// ratio in [0, 1] is formed on its own from scaled energies (tbk_dos_common.h), so a selected branch has no 0 * inf.
+// The corner weights of a bin are TetraGaps' (tbk_tetra.h), computed once and applied to all groups.
 template <int GT, int NC>
 __device__ __forceinline__ void pdos_simplex(const double (&e_in)[NC], const int64_t (&kc)[NC], int band, const double* __restrict__ W,
                                              int n_groups, int n_orb, const DosWindow& w, unsigned long long* part, unsigned long long* step) {
@@ -99,15 +99,8 @@ __device__ __forceinline__ void pdos_simplex(const double (&e_in)[NC], const int
     for (int g = 0; g < GT; ++g)
 #pragma unroll
         for (int c = 0; c < NC; ++c) a[g][c] = g < n_groups ? W[((size_t)kc[c] * n_groups + g) * n_orb + band] : 0.0;
-    // a stable sorting network: adjacent exchanges only
-    pdos_exchange<GT, NC, 0, 1>(e, a);
-    pdos_exchange<GT, NC, 1, 2>(e, a);
-    if (NC == 4) pdos_exchange<GT, NC, NC - 2, NC - 1>(e, a);
-    pdos_exchange<GT, NC, 0, 1>(e, a);
-    if (NC == 4) {
-        pdos_exchange<GT, NC, 1, 2>(e, a);
-        pdos_exchange<GT, NC, 0, 1>(e, a);
-    }
+    PdosColumns<GT, NC> columns{a};
+    tetra_stable_sort(e, columns);
     const int j_lo = dos_first_at_or_above(e[0], w.e_min, w.e_step, w.inv_step, w.n_e);
     const int j_hi = dos_first_at_or_above(e[NC - 1], w.e_min, w.e_step, w.inv_step, w.n_e);
     if (j_hi >= w.tile_lo && j_hi < w.tile_lo + w.tile_n) {
@@ -121,78 +114,18 @@ __device__ __forceinline__ void pdos_simplex(const double (&e_in)[NC], const int
     }
     const int lo = max(j_lo, w.tile_lo), hi = min(j_hi, w.tile_lo + w.tile_n);
     if (lo >= hi) return;
-    if (NC == 4) {
-        const double e1 = e[0], e2 = e[1], e3 = e[2], e4 = e[NC - 1];
-        const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE, s4 = e4 * DOS_GAP_SCALE;
-        const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r41 = 1.0 / (s4 - s1), r32 = 1.0 / (s3 - s2), r42 = 1.0 / (s4 - s2),
-                     r43 = 1.0 / (s4 - s3);
-        for (int j = lo; j < hi; ++j) {
-            const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e4 here
-            const double Es = E * DOS_GAP_SCALE;
-            double w1, w2, w3, w4;
-            if (E < e2) {
-                const double x = Es - s1;
-                const double q21 = x * r21, q31 = x * r31, q41 = x * r41;
-                const double C = 0.25 * q21 * q31 * q41;
-                w1 = C * (4.0 - (q21 + q31 + q41));
-                w2 = C * q21;
-                w3 = C * q31;
-                w4 = C * q41;
-            } else if (E < e3) {
-                const double x1 = Es - s1, x2 = Es - s2, y3 = s3 - Es, y4 = s4 - Es;
-                const double p31 = x1 * r31, p41 = x1 * r41, p32 = x2 * r32, p42 = x2 * r42;  // from below
-                const double m31 = y3 * r31, m32 = y3 * r32, m41 = y4 * r41, m42 = y4 * r42;  // from above
-                const double T = 0.25 * p41;
-                const double C1 = T * p31;
-                const double C2 = T * p32 * m31;
-                const double C3 = 0.25 * p42 * p32 * m41;
-                const double C12 = C1 + C2, C23 = C2 + C3, C123 = C12 + C3;
-                w1 = C1 + C12 * m31 + C123 * m41;
-                w2 = C123 + C23 * m32 + C3 * m42;
-                w3 = C12 * p31 + C23 * p32;
-                w4 = C123 * p41 + C3 * p42;
-            } else {
-                const double y = s4 - Es;
-                const double q41 = y * r41, q42 = y * r42, q43 = y * r43;
-                const double C = 0.25 * q41 * q42 * q43;
-                w1 = 0.25 - C * q41;
-                w2 = 0.25 - C * q42;
-                w3 = 0.25 - C * q43;
-                w4 = 0.25 - C * (4.0 - (q41 + q42 + q43));
-            }
+    const TetraGaps<NC> gaps(e);
+    for (int j = lo; j < hi; ++j) {
+        const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e_top here
+        double wc[NC];
+        gaps.corner_weights(E, wc);
 #pragma unroll
-            for (int g = 0; g < GT; ++g)
-                if (g < n_groups)
-                    atomicAdd(&part[g * w.tile_n + (j - w.tile_lo)], dos_fixed(w1 * a[g][0] + w2 * a[g][1] + w3 * a[g][2] + w4 * a[g][NC - 1]));
-        }
-    } else {
-        const double e1 = e[0], e2 = e[1], e3 = e[2];
-        const double s1 = e1 * DOS_GAP_SCALE, s2 = e2 * DOS_GAP_SCALE, s3 = e3 * DOS_GAP_SCALE;
-        const double r21 = 1.0 / (s2 - s1), r31 = 1.0 / (s3 - s1), r32 = 1.0 / (s3 - s2);
-        const double third = 1.0 / 3.0;
-        for (int j = lo; j < hi; ++j) {
-            const double E = dos_grid(w.e_min, w.e_step, j);  // e1 <= E < e3 here
-            const double Es = E * DOS_GAP_SCALE;
-            double w1, w2, w3;
-            if (E < e2) {
-                const double x = Es - s1;
-                const double q21 = x * r21, q31 = x * r31;
-                const double C = third * q21 * q31;
-                w1 = C * (3.0 - (q21 + q31));
-                w2 = C * q21;
-                w3 = C * q31;
-            } else {
-                const double y = s3 - Es;
-                const double q31 = y * r31, q32 = y * r32;
-                const double C = third * q31 * q32;
-                w1 = third - C * q31;
-                w2 = third - C * q32;
-                w3 = third - C * (3.0 - (q31 + q32));
+        for (int g = 0; g < GT; ++g)
+            if (g < n_groups) {
+                double sum = wc[0] * a[g][0] + wc[1] * a[g][1] + wc[2] * a[g][2];
+                if constexpr (NC == 4) sum = sum + wc[3] * a[g][3];
+                atomicAdd(&part[g * w.tile_n + (j - w.tile_lo)], dos_fixed(sum));
             }
-#pragma unroll
-            for (int g = 0; g < GT; ++g)
-                if (g < n_groups) atomicAdd(&part[g * w.tile_n + (j - w.tile_lo)], dos_fixed(w1 * a[g][0] + w2 * a[g][1] + w3 * a[g][2]));
-        }
     }
 }
 
@@ -220,17 +153,9 @@ __global__ void __launch_bounds__(PDOS_THREADS)
     const int64_t first = (int64_t)blockIdx.x * g.items_per_wg;
     const int64_t last = min(first + g.items_per_wg, g.items);
     for (int64_t it = first + tid; it < last; it += PDOS_THREADS) {
-        const int64_t cell64 = it / g.n_orb;
-        const int band = (int)(it - cell64 * g.n_orb);
-        int c = (int)cell64;  // NK < 2^31 (checked by the launcher)
-        const int i2 = c % g.n2;
-        c /= g.n2;
-        const int i1 = c % g.n1;
-        const int i0 = c / g.n1;  // < n0_cells
-        const int j0 = i0 + 1 == g.n0_planes ? 0 : i0 + 1;
-        const int j1 = i1 + 1 == g.n1 ? 0 : i1 + 1;
-        const int j2 = i2 + 1 == g.n2 ? 0 : i2 + 1;
-        auto at = [&](int a0, int a1, int a2) -> int64_t { return ((int64_t)a0 * g.n1 + a1) * g.n2 + a2; };
+        const TetraItem t = tetra_item(g, it);
+        const int band = t.band, i0 = t.i0, i1 = t.i1, i2 = t.i2, j0 = t.j0, j1 = t.j1, j2 = t.j2;
+        auto at = [&](int a0, int a1, int a2) -> int64_t { return tetra_row(g, a0, a1, a2); };
         auto energy = [&](int64_t k) -> double { return E[k * g.n_orb + band]; };
         if (DIM == 3) {
             // corner k_xyz: x, y, z = step along axis 0, 1, 2
@@ -275,19 +200,15 @@ __global__ void __launch_bounds__(PDOS_THREADS)
                        unsigned long long* __restrict__ sums) {
     const int64_t j = (int64_t)blockIdx.x * PDOS_THREADS + threadIdx.x;
     if (j >= n_bins) return;
-    const unsigned long long mask = (1ull << DOS_SPLIT_BITS) - 1;
-    unsigned long long p_hi = 0, p_lo = 0, s_hi = 0, s_lo = 0;
+    DosWords p, s;
     for (int wg = 0; wg < n_wg; ++wg) {
-        const unsigned long long p = part_g[(int64_t)wg * n_bins + j], s = step_g[(int64_t)wg * n_bins + j];
-        p_hi += p >> DOS_SPLIT_BITS;
-        p_lo += p & mask;
-        s_hi += s >> DOS_SPLIT_BITS;
-        s_lo += s & mask;
+        p.add(part_g[(int64_t)wg * n_bins + j]);
+        s.add(step_g[(int64_t)wg * n_bins + j]);
     }
-    sums[j] = p_hi;
-    sums[n_bins + j] = p_lo;
-    sums[2 * n_bins + j] = s_hi;
-    sums[3 * n_bins + j] = s_lo;
+    sums[j] = p.hi;
+    sums[n_bins + j] = p.lo;
+    sums[2 * n_bins + j] = s.hi;
+    sums[3 * n_bins + j] = s.lo;
 }
 
 // one workgroup per group: nos[g][j] = (fraction[j] + sum_{i <= j} step[i]) / denom, the prefix sum on the two halves apart (in
@@ -316,15 +237,13 @@ __global__ void __launch_bounds__(PDOS_THREADS) pdos_scan_kernel(const unsigned 
         run_hi += total_hi[t];
         run_lo += total_lo[t];
     }
-    const unsigned long long mask = (1ull << DOS_SPLIT_BITS) - 1;
     for (int j = lo; j < hi; ++j) {
         run_hi += s_hi[j];
         run_lo += s_lo[j];
-        unsigned long long all_lo = run_lo + p_lo[j];
-        const unsigned long long all_hi = run_hi + p_hi[j] + (all_lo >> DOS_SPLIT_BITS);
-        all_lo &= mask;
-        const double value = (double)all_hi * (1.0 / (double)(1ull << (DOS_FRAC_BITS - DOS_SPLIT_BITS))) + (double)all_lo * (1.0 / (double)(1ull << DOS_FRAC_BITS));
-        nos[base + j] = value / denom;
+        DosWords all;  // the low halves carry into the high ones first: the sum of up to 2^20 of them has more than 20 bits
+        all.add(run_lo + p_lo[j]);
+        all.hi += run_hi + p_hi[j];
+        nos[base + j] = all.value() / denom;
     }
 }
 
@@ -337,25 +256,17 @@ struct PdosLaunch {
 // dim in {2, 3}; cells0 cells along axis 0 out of planes0 planes held in E and W
 int pdos_plan(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb, int n_groups, int64_t n_e, PdosLaunch* out) {
     PdosLaunch L;
-    L.g.n0_cells = (int)cells0;
-    L.g.n0_planes = (int)planes0;
-    L.g.n1 = mesh[1];
-    L.g.n2 = dim == 3 ? mesh[2] : 1;
-    L.g.n_orb = n_orb;
-    L.g.items = cells0 * L.g.n1 * L.g.n2 * n_orb;
+    L.g = tetra_geom(dim, mesh, cells0, planes0, n_orb);
     TBK_ARG(L.g.items * (dim == 3 ? 6 : 2) <= PDOS_MAX_TERMS, "mesh x orbitals too large for one projected density-of-states call");
     L.n_groups = n_groups;
     L.group_tile = pdos_group_tile(n_groups);
     L.n_e = (int)n_e;
     const int tile = PDOS_LDS_BINS / L.group_tile;
     L.n_tiles = (int)((n_e + tile - 1) / tile);
-    // workgroups: enough to fill the chip, no more rows than 2^24 bins of partials, never more than DOS_MAX_ITEMS items each
+    // no more rows than 2^24 bins of partials
     const int64_t by_memory = std::max<int64_t>(1, (int64_t(1) << 24) / (n_e * n_groups));
-    int64_t n_wg = std::min<int64_t>((L.g.items + PDOS_THREADS - 1) / PDOS_THREADS, std::min<int64_t>(1024, by_memory));
-    n_wg = std::max<int64_t>(n_wg, (L.g.items + DOS_MAX_ITEMS - 1) / DOS_MAX_ITEMS);
-    TBK_ARG(n_wg <= (int64_t(1) << DOS_SPLIT_BITS), "mesh x orbitals too large for one projected density-of-states call");
-    L.g.items_per_wg = (L.g.items + n_wg - 1) / n_wg;
-    L.n_wg = (int)((L.g.items + L.g.items_per_wg - 1) / L.g.items_per_wg);
+    TBK_CHECK(tetra_partition(L.g.items, PDOS_THREADS, std::min<int64_t>(1024, by_memory),
+                              "mesh x orbitals too large for one projected density-of-states call", &L.g.items_per_wg, &L.n_wg));
     const size_t bins = (size_t)n_groups * (size_t)n_e;
     L.off_step = dos_align256((size_t)L.n_wg * bins * sizeof(unsigned long long));
     L.off_sums = 2 * L.off_step;
@@ -457,14 +368,7 @@ extern "C" int tbk_pdos_from_eigensystem(int device, int dim, const int32_t* mes
     TBK_ARG(n_orb >= 1, "n_orb < 1");
     TBK_ARG(n_groups >= 1 && n_groups <= TBK_PDOS_MAX_GROUPS, "n_groups outside [1, TBK_PDOS_MAX_GROUPS]");
     TBK_ARG(std::isfinite(e_min), "e_min is not finite");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) {
-        (void)hipGetLastError();
-        tbk_set_error("no HIP device visible: libtbk has no CPU path");
-        return TBK_ERR_DEVICE;
-    }
-    TBK_ARG(device >= 0 && device < n_dev, "device out of range");
-    TBK_HIP(hipSetDevice(device));
+    TBK_CHECK(tetra_check_device(device));
     PdosLaunch L;
     TBK_CHECK(pdos_plan(dim, mesh, mesh[0], mesh[0], n_orb, n_groups, n_e, &L));
     const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double), w_bytes = e_bytes * (size_t)n_groups;

@@ -23,7 +23,7 @@ import numpy as np
 import dos_model
 import tetra_exact
 
-GAP_SCALE = 2.0 ** 54  # DOS_GAP_SCALE of csrc/tbk_dos_common.h
+GAP_SCALE = 2.0 ** 54  # DOS_GAP_SCALE of csrc/tbk_tetra.h
 
 
 def gather_table(dim):
