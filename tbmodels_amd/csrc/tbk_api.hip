@@ -49,17 +49,46 @@ extern "C" int tbk_device_count(int* count) {
 // ------------------------------------------------------------------------------------------------
 int DevBuf::reserve(size_t want) {
     if (want <= bytes) return TBK_OK;
-    release();
+    bytes = 0;
     const size_t rounded = (want + (size_t(1) << 20) - 1) & ~((size_t(1) << 20) - 1);
-    TBK_HIP(hipMalloc(&ptr, rounded));
+    TBK_HIP(hipMalloc(ptr.put(), rounded));
     bytes = rounded;
     return TBK_OK;
 }
 
-void DevBuf::release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    bytes = 0;
+void SpanRecorder::start(int stage) {
+    if (!on) return;
+    EventSpan span;
+    span.stage = stage;
+    if (hipEventCreate(span.start.put()) != hipSuccess || hipEventCreate(span.stop.put()) != hipSuccess) {
+        (void)hipGetLastError();
+        on = false;
+        return;
+    }
+    (void)hipEventRecord(span.start, stream);
+    spans.push_back(std::move(span));
+}
+
+void SpanRecorder::stop() {
+    if (on && !spans.empty()) (void)hipEventRecord(spans.back().stop, stream);
+}
+
+void SpanRecorder::collect(double* ms) {
+    std::vector<float> t(spans.size(), 0.f);
+    for (size_t i = 0; i < spans.size() && on; ++i)
+        if (hipEventElapsedTime(&t[i], spans[i].start, spans[i].stop) != hipSuccess) on = false;
+    for (size_t i = 0; i < spans.size() && on; ++i) ms[spans[i].stage] += (double)t[i];
+    spans.clear();
+}
+
+int tbk_timed_read(tbk_model* m, TimedFamily family, int stages, double* ms, int64_t* calls, int64_t* passes, int reset) {
+    TBK_LOCK(m);
+    TimedSums& row = m->timed[family];
+    for (int i = 0; i < stages; ++i) ms[i] = row.ms[i];
+    *calls = row.calls;
+    if (passes) *passes = row.passes;
+    if (reset) row = TimedSums();
+    return TBK_OK;
 }
 
 // roctx ranges (rocprofv3 --marker-trace labels the timeline with them): the tools library is looked up at run time,
@@ -103,7 +132,7 @@ StageTimer::StageTimer(tbk_model* m_, int stage, hipStream_t s)
     : m(m_), on(m_->timing), stream(s ? s : m_->stream) {
     ev.stage = stage;
     if (on) {
-        if (hipEventCreate(&ev.start) != hipSuccess || hipEventCreate(&ev.stop) != hipSuccess) {
+        if (hipEventCreate(ev.start.put()) != hipSuccess || hipEventCreate(ev.stop.put()) != hipSuccess) {
             on = false;
             return;
         }
@@ -116,7 +145,7 @@ StageTimer::~StageTimer() {
     if (on) {
         (void)hipEventRecord(ev.stop, stream);
         tbk_range_pop();
-        m->events.push_back(ev);
+        m->events.push_back(std::move(ev));
     }
 }
 
@@ -137,19 +166,24 @@ static int require_device(int device) {
     return TBK_OK;
 }
 
+// a handle under construction: destroyed on every early return, released into *out on success
+struct ModelDestroy {
+    void operator()(tbk_model* m) const { tbk_model_destroy(m); }
+};
+using ModelGuard = std::unique_ptr<tbk_model, ModelDestroy>;
+
 // everything both model kinds share: stream, rocBLAS handle, lattice vectors, packed-element map
 // (pair_diagonal: the slot map of dense tight-binding models, two diagonal elements per slot -- tbk_internal.h)
 static int create_common(int device, int dim, int n_orb, int64_t n_r, const int32_t* R,
-                         int64_t k_rows_per_r, bool pair_diagonal, tbk_model** out) {
-    TBK_ARG(out != nullptr, "out is NULL");
-    *out = nullptr;
+                         int64_t k_rows_per_r, bool pair_diagonal, ModelGuard* out) {
     TBK_ARG(dim >= 1 && dim <= TBK_MAX_DIM, "dim must be in [1, 8]");
     TBK_ARG(n_orb >= 1 && n_orb <= 32768, "n_orb must be in [1, 32768]");
     TBK_ARG(n_r >= 0 && n_r < (int64_t(1) << 28), "n_r out of range");
     TBK_ARG(n_r == 0 || R != nullptr || k_rows_per_r == 1, "R is NULL");  // k.p rows carry no R
     TBK_CHECK(require_device(device));
 
-    tbk_model* m = new (std::nothrow) tbk_model();
+    ModelGuard guard(new (std::nothrow) tbk_model());
+    tbk_model* m = guard.get();
     if (!m) {
         tbk_set_error("out of host memory");
         return TBK_ERR_MEMORY;
@@ -171,44 +205,30 @@ static int create_common(int device, int dim, int n_orb, int64_t n_r, const int3
     m->ncol = (int)(pair_diagonal ? (int64_t)n_orb * (n_orb - 1) / 2 + (n_orb + 1) / 2 : (int64_t)n_orb * (n_orb + 1) / 2);
     m->ncol_pad = (int)round_up(m->ncol, strassen ? 2 * TBK_BNP : TBK_BNP);
 
-    int rc = TBK_OK;
-    auto fail = [&](int code) {
-        tbk_model_destroy(m);
-        return code;
-    };
-#define TBK_TRY(expr)                           \
-    do {                                        \
-        rc = [&]() -> int {                     \
-            expr;                               \
-            return TBK_OK;                      \
-        }();                                    \
-        if (rc != TBK_OK) return fail(rc);      \
-    } while (0)
-
-    TBK_TRY(TBK_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking)));
-    TBK_TRY(TBK_HIP(hipStreamCreateWithFlags(&m->stream_eig, hipStreamNonBlocking)));
-    TBK_TRY(TBK_HIP(hipStreamCreateWithFlags(&m->stream_ql, hipStreamNonBlocking)));
+    TBK_HIP(hipStreamCreateWithFlags(m->stream.put(), hipStreamNonBlocking));
+    TBK_HIP(hipStreamCreateWithFlags(m->stream_eig.put(), hipStreamNonBlocking));
+    TBK_HIP(hipStreamCreateWithFlags(m->stream_ql.put(), hipStreamNonBlocking));
     // (stream_xl / ev_xl: created by launch_band_xl when a batch above 1024 orbitals first goes in groups)
     for (int b = 0; b < 2; ++b) {
-        TBK_TRY(TBK_HIP(hipEventCreateWithFlags(&m->ev_hk[b], hipEventDisableTiming)));
-        TBK_TRY(TBK_HIP(hipEventCreateWithFlags(&m->ev_tri[b], hipEventDisableTiming)));
-        TBK_TRY(TBK_HIP(hipEventCreateWithFlags(&m->ev_ql[b], hipEventDisableTiming)));
-        TBK_TRY(TBK_HIP(hipEventCreateWithFlags(&m->ev_out[b], hipEventDisableTiming)));
-        TBK_TRY(TBK_HIP(hipEventCreateWithFlags(&m->ev_s2[b], hipEventDisableTiming)));
+        TBK_HIP(hipEventCreateWithFlags(m->ev_hk[b].put(), hipEventDisableTiming));
+        TBK_HIP(hipEventCreateWithFlags(m->ev_tri[b].put(), hipEventDisableTiming));
+        TBK_HIP(hipEventCreateWithFlags(m->ev_ql[b].put(), hipEventDisableTiming));
+        TBK_HIP(hipEventCreateWithFlags(m->ev_out[b].put(), hipEventDisableTiming));
+        TBK_HIP(hipEventCreateWithFlags(m->ev_s2[b].put(), hipEventDisableTiming));
         // (release to system scope: results of small calls are read by the CPU from non-coherent pinned memory right
         // behind hipEventSynchronize on this event -- with a default event that visibility is the runtime's choice)
-        if (b == 0) TBK_TRY(TBK_HIP(hipEventCreateWithFlags(&m->ev_sync, hipEventDisableTiming | hipEventReleaseToSystem)));
+        if (b == 0) TBK_HIP(hipEventCreateWithFlags(m->ev_sync.put(), hipEventDisableTiming | hipEventReleaseToSystem));
     }
-    TBK_TRY(TBK_ROCBLAS(rocblas_create_handle(&m->blas)));
-    TBK_TRY(TBK_ROCBLAS(rocblas_set_stream(m->blas, m->stream)));
-    TBK_TRY(TBK_CHECK(m->ws_flag.reserve(2 * sizeof(int))));
-    TBK_TRY(TBK_HIP(hipMemsetAsync(m->ws_flag.ptr, 0, 2 * sizeof(int), m->stream)));
+    TBK_ROCBLAS(rocblas_create_handle(m->blas.put()));
+    TBK_ROCBLAS(rocblas_set_stream(m->blas, m->stream));
+    TBK_CHECK(m->ws_flag.reserve(2 * sizeof(int)));
+    TBK_HIP(hipMemsetAsync(m->ws_flag.ptr, 0, 2 * sizeof(int), m->stream));
     // one H(k) (up to 1024 orbitals: 16 MiB) with its k-point and positions, or a few hundred eigenvalue rows
     m->h_stage_bytes = std::max<size_t>(size_t(320) << 10,
                                         n_orb <= 1024 ? (size_t)n_orb * n_orb * 16 + (size_t)n_orb * dim * 8 + (size_t(64) << 10) : 0);
-    if (hipHostMalloc(&m->h_stage, m->h_stage_bytes, hipHostMallocNonCoherent) != hipSuccess) {
+    if (hipHostMalloc(m->h_stage.put(), m->h_stage_bytes, hipHostMallocNonCoherent) != hipSuccess) {
         (void)hipGetLastError();
-        m->h_stage = nullptr;  // no pinned memory: every call takes the pageable path
+        m->h_stage.h = nullptr;  // no pinned memory: every call takes the pageable path
         m->h_stage_bytes = 0;
     }
 
@@ -225,22 +245,19 @@ static int create_common(int device, int dim, int n_orb, int64_t n_r, const int3
                 colmap[e++] = i + 1 < n_orb ? (int32_t)((i << 16) | TBK_SLOT_PAIR | (i + 1)) : (int32_t)((i << 16) | i);
             for (int j = i + 1; j < n_orb; ++j) colmap[e++] = (int32_t)((i << 16) | j);
         }
-        TBK_TRY(TBK_HIP(hipMalloc((void**)&m->d_colmap, colmap.size() * sizeof(int32_t))));
-        TBK_TRY(TBK_HIP(hipMemcpy(m->d_colmap, colmap.data(), colmap.size() * sizeof(int32_t),
-                                  hipMemcpyHostToDevice)));
+        TBK_HIP(hipMalloc(m->d_colmap.put(), colmap.size() * sizeof(int32_t)));
+        TBK_HIP(hipMemcpy(m->d_colmap, colmap.data(), colmap.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         m->staged_bytes += (int64_t)(colmap.size() * sizeof(int32_t));
     }
     if (n_r > 0 && R != nullptr && k_rows_per_r == 2) m->h_R.assign(R, R + (size_t)n_r * dim);
     if (m->n_r_pad > 0 && R != nullptr) {
         std::vector<int32_t> r_pad((size_t)m->n_r_pad * dim, 0);
         std::memcpy(r_pad.data(), R, (size_t)n_r * dim * sizeof(int32_t));
-        TBK_TRY(TBK_HIP(hipMalloc((void**)&m->d_R, r_pad.size() * sizeof(int32_t))));
-        TBK_TRY(TBK_HIP(hipMemcpy(m->d_R, r_pad.data(), r_pad.size() * sizeof(int32_t),
-                                  hipMemcpyHostToDevice)));
+        TBK_HIP(hipMalloc(m->d_R.put(), r_pad.size() * sizeof(int32_t)));
+        TBK_HIP(hipMemcpy(m->d_R, r_pad.data(), r_pad.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         m->staged_bytes += (int64_t)(r_pad.size() * sizeof(int32_t));
     }
-#undef TBK_TRY
-    *out = m;
+    *out = std::move(guard);
     return TBK_OK;
 }
 
@@ -252,28 +269,20 @@ extern "C" int tbk_model_create_dense(int device, int dim, int n_orb, int64_t n_
     TBK_ARG(out != nullptr, "out is NULL");
     *out = nullptr;
     TBK_ARG(n_r == 0 || hop != nullptr, "hop is NULL");
-    tbk_model* m = nullptr;
-    TBK_CHECK(create_common(device, dim, n_orb, n_r, R, 2, true, &m));
+    ModelGuard guard;
+    TBK_CHECK(create_common(device, dim, n_orb, n_r, R, 2, true, &guard));
+    tbk_model* m = guard.get();
     m->sparse = false;
-    int rc = TBK_OK;
-    double* d_raw = nullptr;
+    DevPtr<double> d_raw;
     const size_t raw_bytes = (size_t)n_r * n_orb * n_orb * 2 * sizeof(double);
-    rc = [&]() -> int {
-        if (raw_bytes) {
-            TBK_HIP(hipMalloc((void**)&d_raw, raw_bytes));
-            TBK_HIP(hipMemcpyAsync(d_raw, hop, raw_bytes, hipMemcpyHostToDevice, m->stream));
-        }
-        TBK_CHECK(tbk_stage_dense(m, d_raw));
-        TBK_CHECK(tbk_stage_strassen(m));
-        TBK_HIP(hipStreamSynchronize(m->stream));
-        return TBK_OK;
-    }();
-    if (d_raw) (void)hipFree(d_raw);
-    if (rc != TBK_OK) {
-        tbk_model_destroy(m);
-        return rc;
+    if (raw_bytes) {
+        TBK_HIP(hipMalloc(d_raw.put(), raw_bytes));
+        TBK_HIP(hipMemcpyAsync(d_raw, hop, raw_bytes, hipMemcpyHostToDevice, m->stream));
     }
-    *out = m;
+    TBK_CHECK(tbk_stage_dense(m, d_raw));
+    TBK_CHECK(tbk_stage_strassen(m));
+    TBK_HIP(hipStreamSynchronize(m->stream));
+    *out = guard.release();
     return TBK_OK;
 }
 
@@ -293,8 +302,9 @@ extern "C" int tbk_model_create_csr(int device, int dim, int n_orb, int64_t n_r,
         TBK_ARG(row[t] >= 0 && row[t] < n_orb && col[t] >= 0 && col[t] < n_orb,
                 "row/col index out of range");
 
-    tbk_model* m = nullptr;
-    TBK_CHECK(create_common(device, dim, n_orb, n_r, R, 2, false, &m));
+    ModelGuard guard;
+    TBK_CHECK(create_common(device, dim, n_orb, n_r, R, 2, false, &guard));
+    tbk_model* m = guard.get();
     m->sparse = true;
 
     // transpose "per lattice vector, which elements" into "per packed element, which lattice
@@ -324,76 +334,46 @@ extern "C" int tbk_model_create_csr(int device, int dim, int n_orb, int64_t n_r,
             }
     }
     m->nnz_rec = nnz;
-    int rc = [&]() -> int {
-        TBK_HIP(hipMalloc((void**)&m->d_cptr, cptr.size() * sizeof(int64_t)));
-        TBK_HIP(hipMemcpy(m->d_cptr, cptr.data(), cptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        m->staged_bytes += (int64_t)(cptr.size() * sizeof(int64_t));
-        if (nnz > 0) {
-            TBK_HIP(hipMalloc((void**)&m->d_rec_r, (size_t)nnz * sizeof(int32_t)));
-            TBK_HIP(hipMalloc((void**)&m->d_rec_v, (size_t)nnz * 2 * sizeof(double)));
-            TBK_HIP(hipMemcpy(m->d_rec_r, rec_r.data(), (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
-            TBK_HIP(hipMemcpy(m->d_rec_v, rec_v.data(), (size_t)nnz * 2 * sizeof(double), hipMemcpyHostToDevice));
-            m->staged_bytes += nnz * (int64_t)(sizeof(int32_t) + 2 * sizeof(double));
-            const int kt = tbk_csr_tile_kpoints(n_r);
-            if (kt > 0) {
-                std::vector<int64_t> sptr;
-                std::vector<int32_t> srec_r;
-                std::vector<double> srec_v;
-                tbk_csr_schedule(m->ncol, kt, cptr, rec_r, rec_v, sptr, srec_r, srec_v);
-                m->sched_steps = sptr.back();
-                auto upload = [&](void** dst, const void* src, size_t bytes) -> int {
-                    TBK_HIP(hipMalloc(dst, std::max<size_t>(bytes, 8)));
-                    if (bytes) TBK_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-                    m->staged_bytes += (int64_t)bytes;
-                    return TBK_OK;
-                };
-                TBK_CHECK(upload((void**)&m->d_sptr, sptr.data(), sptr.size() * sizeof(int64_t)));
-                TBK_CHECK(upload((void**)&m->d_srec_r, srec_r.data(), srec_r.size() * sizeof(int32_t)));
-                TBK_CHECK(upload((void**)&m->d_srec_v, srec_v.data(), srec_v.size() * sizeof(double)));
-                m->sched_kt = kt;
-            }
+    TBK_HIP(hipMalloc(m->d_cptr.put(), cptr.size() * sizeof(int64_t)));
+    TBK_HIP(hipMemcpy(m->d_cptr, cptr.data(), cptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    m->staged_bytes += (int64_t)(cptr.size() * sizeof(int64_t));
+    if (nnz > 0) {
+        TBK_HIP(hipMalloc(m->d_rec_r.put(), (size_t)nnz * sizeof(int32_t)));
+        TBK_HIP(hipMalloc(m->d_rec_v.put(), (size_t)nnz * 2 * sizeof(double)));
+        TBK_HIP(hipMemcpy(m->d_rec_r, rec_r.data(), (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+        TBK_HIP(hipMemcpy(m->d_rec_v, rec_v.data(), (size_t)nnz * 2 * sizeof(double), hipMemcpyHostToDevice));
+        m->staged_bytes += nnz * (int64_t)(sizeof(int32_t) + 2 * sizeof(double));
+        const int kt = tbk_csr_tile_kpoints(n_r);
+        if (kt > 0) {
+            std::vector<int64_t> sptr;
+            std::vector<int32_t> srec_r;
+            std::vector<double> srec_v;
+            tbk_csr_schedule(m->ncol, kt, cptr, rec_r, rec_v, sptr, srec_r, srec_v);
+            m->sched_steps = sptr.back();
+            auto upload = [&](auto& dst, const void* src, size_t bytes) -> int {
+                TBK_HIP(hipMalloc(dst.put(), std::max<size_t>(bytes, 8)));
+                if (bytes) TBK_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+                m->staged_bytes += (int64_t)bytes;
+                return TBK_OK;
+            };
+            TBK_CHECK(upload(m->d_sptr, sptr.data(), sptr.size() * sizeof(int64_t)));
+            TBK_CHECK(upload(m->d_srec_r, srec_r.data(), srec_r.size() * sizeof(int32_t)));
+            TBK_CHECK(upload(m->d_srec_v, srec_v.data(), srec_v.size() * sizeof(double)));
+            m->sched_kt = kt;
         }
-        return TBK_OK;
-    }();
-    if (rc != TBK_OK) {
-        tbk_model_destroy(m);
-        return rc;
     }
-    *out = m;
+    *out = guard.release();
     return TBK_OK;
 }
 
+// The members free themselves (tbk_internal.h: the owning types, destroyed last member first); what is left here is what has to
+// hold while they go: the handle's device is current, and nothing is still running on its streams.
 extern "C" void tbk_model_destroy(tbk_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
-    hipStream_t streams[] = {m->stream, m->stream_eig, m->stream_ql, m->stream_xl[0], m->stream_xl[1], m->stream_xl[2]};
+    const hipStream_t streams[] = {m->stream, m->stream_eig, m->stream_ql, m->stream_xl[0], m->stream_xl[1], m->stream_xl[2]};
     for (hipStream_t st : streams)
         if (st) (void)hipStreamSynchronize(st);
-    for (hipEvent_t e : m->ev_xl)
-        if (e) (void)hipEventDestroy(e);
-    for (int b = 0; b < 2; ++b) {
-        if (m->ev_hk[b]) (void)hipEventDestroy(m->ev_hk[b]);
-        if (m->ev_tri[b]) (void)hipEventDestroy(m->ev_tri[b]);
-        if (m->ev_ql[b]) (void)hipEventDestroy(m->ev_ql[b]);
-        if (m->ev_out[b]) (void)hipEventDestroy(m->ev_out[b]);
-        if (m->ev_s2[b]) (void)hipEventDestroy(m->ev_s2[b]);
-        if (b == 0 && m->ev_sync) (void)hipEventDestroy(m->ev_sync);
-    }
-    for (auto& ev : m->events) {
-        (void)hipEventDestroy(ev.start);
-        (void)hipEventDestroy(ev.stop);
-    }
-    if (m->blas) (void)rocblas_destroy_handle(m->blas);
-    if (m->h_stage) (void)hipHostFree(m->h_stage);
-    for (hipStream_t st : streams)
-        if (st) (void)hipStreamDestroy(st);
-    void* ptrs[] = {m->d_R, m->d_colmap, m->d_B, m->d_Bs, m->d_Bs2, m->d_cptr, m->d_rec_r, m->d_rec_v, m->d_powers, m->d_sptr, m->d_srec_r, m->d_srec_v};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    DevBuf* bufs[] = {&m->ws_phase, &m->ws_H, &m->ws_E,   &m->ws_E2,
-                      &m->ws_info,  &m->ws_k, &m->ws_pos, &m->ws_out, &m->ws_out2, &m->ws_flag, &m->ws_orb, &m->ws_part, &m->ws_c11, &m->ws_kfold, &m->ws_kline, &m->ws_band, &m->ws_bandmat[0], &m->ws_bandmat[1], &m->ws_H2, &m->ws_xl, &m->ws_posraw, &m->ws_dos, &m->ws_pdos_u, &m->ws_pdos_w, &m->ws_pdos_grp, &m->ws_occ_w, &m->ws_occ};
-    for (DevBuf* b : bufs) b->release();
-    tbk_fold_release(m);
     delete m;
 }
 
@@ -913,7 +893,7 @@ extern "C" int tbk_hamilton(tbk_model* m, const double* k, int64_t nk, int conve
             // small result (one k-point: 64 KiB of H at 64 orbitals): [k | pos | H] through the pinned buffer.  The chunked
             // download below -- a blocking copy into pageable memory -- takes 290 us per call for results of 25 - 64 KiB
             // in a loop of one-k calls (tools/trace_single_k.py), this path 50 - 95 us whatever the size
-            char* st = static_cast<char*>(m->h_stage);
+            char* st = static_cast<char*>(m->h_stage.h);
             TBK_CHECK(m->ws_k.reserve(k_bytes));
             TBK_CHECK(m->ws_out.reserve(h_bytes));
             // ONE k-point of a dense model (the Z2Pack call shape): k goes into the kernel arguments and the positions of
@@ -1021,7 +1001,7 @@ extern "C" int tbk_eigenval(tbk_model* m, const double* k, int64_t nk, double* E
     const size_t e_off = (k_bytes + 63) / 64 * 64;
     if (m->h_stage != nullptr && e_off + e_bytes + 16 <= m->h_stage_bytes) {
         // small call: [k | E | flags] through the pinned buffer, everything enqueued, one synchronisation
-        char* st = static_cast<char*>(m->h_stage);
+        char* st = static_cast<char*>(m->h_stage.h);
         int* flag = reinterpret_cast<int*>(st + e_off + e_bytes);
         // (one k-point of a dense model on the matrix-vector path: k travels in the kernel arguments, see tbk_hamilton --
         // only the chunk pipeline reads it from there: the rocSOLVER branch fills its phase rows from ws_k, which a call
@@ -1068,27 +1048,24 @@ extern "C" int tbk_tridiagonal_reduce(int device, int n_orb, int64_t nk, const d
     TBK_ARG(method != TBK_REDUCE_ONE_STAGE || n_orb <= 512, "the one-stage reduction handles n_orb <= 512");
     if (nk == 0) return TBK_OK;
     TBK_ARG(H && d && e, "H / d / e is NULL");
-    tbk_model* m = nullptr;
-    TBK_CHECK(create_common(device, 1, n_orb, 0, nullptr, 2, false, &m));
+    ModelGuard guard;  // (declared in front of the lock: destroyed behind it)
+    TBK_CHECK(create_common(device, 1, n_orb, 0, nullptr, 2, false, &guard));
+    tbk_model* m = guard.get();
     const size_t n = (size_t)n_orb, mat_bytes = n * n * 2 * sizeof(double);
-    int rc = [&]() -> int {
-        TBK_LOCK(m);
-        const tbk_eig_plan_t plan = tbk_eig_plan(n_orb, m->eigensolver, nk, method);
-        TBK_CHECK(m->ws_H.reserve((size_t)nk * mat_bytes));
-        TBK_CHECK(m->ws_E.reserve((size_t)nk * n * 2 * sizeof(double)));
-        TBK_CHECK(tbk_eig_reserve(m, plan, nk, 1));
-        TBK_HIP(hipMemcpyAsync(m->ws_H.ptr, H, (size_t)nk * mat_bytes, hipMemcpyHostToDevice, m->stream));
-        TBK_CHECK(tbk_eig_reduce(m, plan, m->stream, m->ws_H.as<double>(), nk, m->ws_E.as<double>()));
-        TBK_HIP(hipMemcpyAsync(d, m->ws_E.ptr, (size_t)nk * n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-        TBK_HIP(hipMemcpyAsync(e, m->ws_E.as<double>() + (size_t)nk * n, (size_t)nk * n * sizeof(double), hipMemcpyDeviceToHost,
-                               m->stream));
-        if (H_reduced)
-            TBK_HIP(hipMemcpyAsync(H_reduced, m->ws_H.ptr, (size_t)nk * mat_bytes, hipMemcpyDeviceToHost, m->stream));
-        TBK_HIP(hipStreamSynchronize(m->stream));
-        return TBK_OK;
-    }();
-    tbk_model_destroy(m);
-    return rc;
+    TBK_LOCK(m);
+    const tbk_eig_plan_t plan = tbk_eig_plan(n_orb, m->eigensolver, nk, method);
+    TBK_CHECK(m->ws_H.reserve((size_t)nk * mat_bytes));
+    TBK_CHECK(m->ws_E.reserve((size_t)nk * n * 2 * sizeof(double)));
+    TBK_CHECK(tbk_eig_reserve(m, plan, nk, 1));
+    TBK_HIP(hipMemcpyAsync(m->ws_H.ptr, H, (size_t)nk * mat_bytes, hipMemcpyHostToDevice, m->stream));
+    TBK_CHECK(tbk_eig_reduce(m, plan, m->stream, m->ws_H.as<double>(), nk, m->ws_E.as<double>()));
+    TBK_HIP(hipMemcpyAsync(d, m->ws_E.ptr, (size_t)nk * n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    TBK_HIP(hipMemcpyAsync(e, m->ws_E.as<double>() + (size_t)nk * n, (size_t)nk * n * sizeof(double), hipMemcpyDeviceToHost,
+                           m->stream));
+    if (H_reduced)
+        TBK_HIP(hipMemcpyAsync(H_reduced, m->ws_H.ptr, (size_t)nk * mat_bytes, hipMemcpyDeviceToHost, m->stream));
+    TBK_HIP(hipStreamSynchronize(m->stream));
+    return TBK_OK;
 }
 
 // The reduction stage ALONE on the chip, timed with HIP events: what `eig_roofline.standalone` of bench.py quotes beside the
@@ -1115,56 +1092,50 @@ extern "C" int tbk_reduce_standalone(int device, int n_orb, int64_t nk, int reps
     TBK_ARG(nk >= 1 && reps >= 1, "nk / reps < 1");
     TBK_ARG(n_orb >= 1 && (n_orb <= 64 || tbk_eig_band_supported(n_orb)), "n_orb must be in [1, 4096]");
     for (int q = 0; q < 3; ++q) us_per_matrix[q] = 0.0;
-    tbk_model* m = nullptr;
-    TBK_CHECK(create_common(device, 1, n_orb, 0, nullptr, 2, false, &m));
+    ModelGuard guard;  // (declared in front of the lock: destroyed behind it)
+    TBK_CHECK(create_common(device, 1, n_orb, 0, nullptr, 2, false, &guard));
+    tbk_model* m = guard.get();
     const size_t n = (size_t)n_orb, mat_bytes = n * n * 2 * sizeof(double);
     DevBuf pristine;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int rc = [&]() -> int {
-        TBK_LOCK(m);
-        const tbk_eig_plan_t plan = tbk_eig_plan(n_orb, m->eigensolver, nk);
-        TBK_CHECK(pristine.reserve((size_t)nk * mat_bytes));
-        TBK_CHECK(m->ws_H.reserve((size_t)nk * mat_bytes));
-        TBK_CHECK(m->ws_E.reserve((size_t)nk * n * 2 * sizeof(double)));
-        TBK_HIP(hipEventCreate(&ev[0]));
-        TBK_HIP(hipEventCreate(&ev[1]));
-        hipLaunchKernelGGL(random_hermitian_kernel, dim3(4096), dim3(256), 0, m->stream, pristine.as<double>(), n_orb, nk);
-        TBK_HIP(hipGetLastError());
-        const bool band = plan.family == EIG_TWO_STAGE;
-        TBK_CHECK(tbk_eig_reserve(m, plan, nk, 1));
-        // (the stages run apart below at every two-stage size, a band buffer between them also where the plan fuses them)
-        TBK_CHECK(m->ws_bandmat[0].reserve((size_t)nk * plan.band_stride));
-        // what: 0 = the reduction as the pipeline runs it, 1 = first stage alone, 2 = second stage alone (two-stage sizes only).
-        // The second stage has no input of its own: every repetition of `what == 2` chases the band the LAST repetition of
-        // `what == 1` left in ws_bandmat[0] (the chase reads it and writes only (d, e): the same work every time).
-        for (int what = 0; what < (band ? 3 : 1); ++what) {
-            float sum = 0.0f;
-            for (int r = 0; r <= reps; ++r) {  // (repetition 0 warms up)
-                if (what != 2)
-                    TBK_HIP(hipMemcpyAsync(m->ws_H.ptr, pristine.ptr, (size_t)nk * mat_bytes, hipMemcpyDeviceToDevice, m->stream));
-                TBK_HIP(hipEventRecord(ev[0], m->stream));
-                if (what == 0) {
-                    TBK_CHECK(tbk_eig_reduce(m, plan, m->stream, m->ws_H.as<double>(), nk, m->ws_E.as<double>()));
-                } else if (what == 1) {
-                    TBK_CHECK(tbk_launch_band_reduce(m, plan, m->stream, m->ws_H.as<double>(), nk, m->ws_band.ptr, m->ws_bandmat[0].ptr));
-                } else {
-                    TBK_CHECK(tbk_launch_band_chase(m, plan, m->stream, m->ws_bandmat[0].ptr, nk, m->ws_E.as<double>()));
-                }
-                TBK_HIP(hipEventRecord(ev[1], m->stream));
-                TBK_HIP(hipEventSynchronize(ev[1]));
-                float ms = 0.0f;
-                TBK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-                if (r > 0) sum += ms;
+    Event ev[2];
+    TBK_LOCK(m);
+    const tbk_eig_plan_t plan = tbk_eig_plan(n_orb, m->eigensolver, nk);
+    TBK_CHECK(pristine.reserve((size_t)nk * mat_bytes));
+    TBK_CHECK(m->ws_H.reserve((size_t)nk * mat_bytes));
+    TBK_CHECK(m->ws_E.reserve((size_t)nk * n * 2 * sizeof(double)));
+    TBK_HIP(hipEventCreate(ev[0].put()));
+    TBK_HIP(hipEventCreate(ev[1].put()));
+    hipLaunchKernelGGL(random_hermitian_kernel, dim3(4096), dim3(256), 0, m->stream, pristine.as<double>(), n_orb, nk);
+    TBK_HIP(hipGetLastError());
+    const bool band = plan.family == EIG_TWO_STAGE;
+    TBK_CHECK(tbk_eig_reserve(m, plan, nk, 1));
+    // (the stages run apart below at every two-stage size, a band buffer between them also where the plan fuses them)
+    TBK_CHECK(m->ws_bandmat[0].reserve((size_t)nk * plan.band_stride));
+    // what: 0 = the reduction as the pipeline runs it, 1 = first stage alone, 2 = second stage alone (two-stage sizes only).
+    // The second stage has no input of its own: every repetition of `what == 2` chases the band the LAST repetition of
+    // `what == 1` left in ws_bandmat[0] (the chase reads it and writes only (d, e): the same work every time).
+    for (int what = 0; what < (band ? 3 : 1); ++what) {
+        float sum = 0.0f;
+        for (int r = 0; r <= reps; ++r) {  // (repetition 0 warms up)
+            if (what != 2)
+                TBK_HIP(hipMemcpyAsync(m->ws_H.ptr, pristine.ptr, (size_t)nk * mat_bytes, hipMemcpyDeviceToDevice, m->stream));
+            TBK_HIP(hipEventRecord(ev[0], m->stream));
+            if (what == 0) {
+                TBK_CHECK(tbk_eig_reduce(m, plan, m->stream, m->ws_H.as<double>(), nk, m->ws_E.as<double>()));
+            } else if (what == 1) {
+                TBK_CHECK(tbk_launch_band_reduce(m, plan, m->stream, m->ws_H.as<double>(), nk, m->ws_band.ptr, m->ws_bandmat[0].ptr));
+            } else {
+                TBK_CHECK(tbk_launch_band_chase(m, plan, m->stream, m->ws_bandmat[0].ptr, nk, m->ws_E.as<double>()));
             }
-            us_per_matrix[what] = (double)sum / reps * 1e3 / (double)nk;
+            TBK_HIP(hipEventRecord(ev[1], m->stream));
+            TBK_HIP(hipEventSynchronize(ev[1]));
+            float ms = 0.0f;
+            TBK_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            if (r > 0) sum += ms;
         }
-        return TBK_OK;
-    }();
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-    pristine.release();
-    tbk_model_destroy(m);
-    return rc;
+        us_per_matrix[what] = (double)sum / reps * 1e3 / (double)nk;
+    }
+    return TBK_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1176,34 +1147,26 @@ extern "C" int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, con
     *out = nullptr;
     TBK_ARG(n_p == 0 || (powers && coeffs), "powers / coeffs is NULL");
     for (int64_t t = 0; t < n_p * dim; ++t) TBK_ARG(powers[t] >= 0, "negative power");
-    tbk_model* m = nullptr;
-    TBK_CHECK(create_common(device, dim, n_orb, n_p, nullptr, 1, false, &m));
+    ModelGuard guard;
+    TBK_CHECK(create_common(device, dim, n_orb, n_p, nullptr, 1, false, &guard));
+    tbk_model* m = guard.get();
     m->kdotp = true;
-    double* d_raw = nullptr;
+    DevPtr<double> d_raw;
     const size_t raw_bytes = (size_t)n_p * n_orb * n_orb * 2 * sizeof(double);
-    int rc = [&]() -> int {
-        if (n_p > 0) {
-            TBK_HIP(hipMalloc((void**)&m->d_powers, (size_t)n_p * dim * sizeof(int32_t)));
-            TBK_HIP(hipMemcpy(m->d_powers, powers, (size_t)n_p * dim * sizeof(int32_t), hipMemcpyHostToDevice));
-            TBK_HIP(hipMalloc((void**)&d_raw, raw_bytes));
-            TBK_HIP(hipMemcpyAsync(d_raw, coeffs, raw_bytes, hipMemcpyHostToDevice, m->stream));
-        }
-        TBK_CHECK(tbk_stage_kdotp(m, d_raw));
-        TBK_HIP(hipStreamSynchronize(m->stream));
-        return TBK_OK;
-    }();
-    if (d_raw) (void)hipFree(d_raw);
-    if (rc != TBK_OK) {
-        tbk_model_destroy(m);
-        return rc;
+    if (n_p > 0) {
+        TBK_HIP(hipMalloc(m->d_powers.put(), (size_t)n_p * dim * sizeof(int32_t)));
+        TBK_HIP(hipMemcpy(m->d_powers, powers, (size_t)n_p * dim * sizeof(int32_t), hipMemcpyHostToDevice));
+        TBK_HIP(hipMalloc(d_raw.put(), raw_bytes));
+        TBK_HIP(hipMemcpyAsync(d_raw, coeffs, raw_bytes, hipMemcpyHostToDevice, m->stream));
     }
+    TBK_CHECK(tbk_stage_kdotp(m, d_raw));
+    TBK_HIP(hipStreamSynchronize(m->stream));
     tbk_kdotp* kp = new (std::nothrow) tbk_kdotp();
     if (!kp) {
-        tbk_model_destroy(m);
         tbk_set_error("out of host memory");
         return TBK_ERR_MEMORY;
     }
-    kp->core = m;
+    kp->core = guard.release();
     *out = kp;
     return TBK_OK;
 }
@@ -1277,14 +1240,12 @@ extern "C" int tbk_get_timing(tbk_model* m, double* ms, int64_t* launches, int r
     TBK_HIP(hipStreamSynchronize(m->stream));
     TBK_HIP(hipStreamSynchronize(m->stream_eig));
     TBK_HIP(hipStreamSynchronize(m->stream_ql));
-    for (auto& ev : m->events) {
+    for (const EventSpan& ev : m->events) {
         float t = 0.f;
         if (hipEventElapsedTime(&t, ev.start, ev.stop) == hipSuccess) {
             m->t_ms[ev.stage] += (double)t;
             m->t_n[ev.stage] += 1;
         }
-        (void)hipEventDestroy(ev.start);
-        (void)hipEventDestroy(ev.stop);
     }
     m->events.clear();
     for (int i = 0; i < TBK_T_COUNT; ++i) {

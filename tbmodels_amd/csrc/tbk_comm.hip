@@ -20,14 +20,14 @@ struct tbk_comm {
     int world = 1;
     int rank = 0;
     ncclComm_t comm = nullptr;
-    hipStream_t stream = nullptr;  // collectives that overlap the next batch's kernels run here
-    hipEvent_t ready = nullptr;    // "the send buffer is complete" on the model's stream
-    hipEvent_t done[2] = {nullptr, nullptr};  // gather of buffer slot 0 / 1 finished
+    Stream stream;  // collectives that overlap the next batch's kernels run here
+    Event ready;    // "the send buffer is complete" on the model's stream
+    Event done[2];  // gather of buffer slot 0 / 1 finished
     // chunk-pipelined gather of one call (tbk_eigenval_device_gather)
-    double* d_stage = nullptr;      // [world][block rows * n_orb] landing area of one block's all-gather
+    DevPtr<double> d_stage;   // [world][block rows * n_orb] landing area of one block's all-gather
     size_t stage_bytes = 0;
-    double* d_status = nullptr;     // [1 + world] this rank's status word, then everybody's
-    hipEvent_t tail = nullptr;      // "the main stream has everything of the call behind it"
+    DevPtr<double> d_status;  // [1 + world] this rank's status word, then everybody's
+    Event tail;               // "the main stream has everything of the call behind it"
 };
 
 #define TBK_NCCL(expr)                                                                           \
@@ -71,12 +71,12 @@ extern "C" int tbk_comm_create(int device, int world_size, int rank, const void*
         delete c;
         return TBK_ERR_DEVICE;
     }
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ready, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->done[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->done[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->tail, hipEventDisableTiming) != hipSuccess ||
-        hipMalloc((void**)&c->d_status, (size_t)(1 + world_size) * sizeof(double)) != hipSuccess) {
+    if (hipStreamCreateWithFlags(c->stream.put(), hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(c->ready.put(), hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(c->done[0].put(), hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(c->done[1].put(), hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(c->tail.put(), hipEventDisableTiming) != hipSuccess ||
+        hipMalloc(c->d_status.put(), (size_t)(1 + world_size) * sizeof(double)) != hipSuccess) {
         tbk_set_error("cannot create the communicator's stream / event");
         tbk_comm_destroy(c);
         return TBK_ERR_DEVICE;
@@ -90,14 +90,7 @@ extern "C" void tbk_comm_destroy(tbk_comm* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) (void)ncclCommDestroy(c->comm);
-    if (c->ready) (void)hipEventDestroy(c->ready);
-    for (hipEvent_t e : c->done)
-        if (e) (void)hipEventDestroy(e);
-    if (c->tail) (void)hipEventDestroy(c->tail);
-    if (c->d_stage) (void)hipFree(c->d_stage);
-    if (c->d_status) (void)hipFree(c->d_status);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // events and buffers, then the stream (tbk_internal.h: the owning types)
 }
 
 extern "C" int tbk_comm_allgather_f64(tbk_comm* c, tbk_model* m, const double* d_send, double* d_recv,
@@ -240,10 +233,8 @@ extern "C" int tbk_comm_prepare_gather(tbk_comm* c, int n_orb, int64_t per) {
     if (want > c->stage_bytes) {
         // (a gather of an earlier call may still read the old area: it is released behind the communicator's stream)
         TBK_HIP(hipStreamSynchronize(c->stream));
-        if (c->d_stage) TBK_HIP(hipFree(c->d_stage));
-        c->d_stage = nullptr;
         c->stage_bytes = 0;
-        TBK_HIP(hipMalloc((void**)&c->d_stage, want));
+        TBK_HIP(hipMalloc(c->d_stage.put(), want));
         c->stage_bytes = want;
     }
     return TBK_OK;

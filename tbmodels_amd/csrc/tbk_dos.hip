@@ -293,6 +293,31 @@ int tbk_dos_mesh_klist(int dim, const int32_t* mesh, int64_t p_lo, int64_t plane
     return TBK_OK;
 }
 
+int tbk_mesh_eigenvalues(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t planes, bool below, std::vector<double>* h_k) {
+    const int dim = m->dim, n_orb = m->n_orb;
+    const int64_t n0 = mesh[0], plane_pts = (int64_t)mesh[1] * (dim == 3 ? mesh[2] : 1);
+    TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, p_lo, planes, h_k));
+    if (below) {
+        std::vector<double> head;
+        TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, (p_lo - 1 + n0) % n0, 1, &head));
+        try {
+            h_k->insert(h_k->begin(), head.begin(), head.end());
+        } catch (...) {
+            tbk_set_error("cannot allocate the k list of the mesh");
+            return TBK_ERR_MEMORY;
+        }
+    }
+    const int64_t head_pts = below ? plane_pts : 0, nk = planes * plane_pts;
+    const size_t k_bytes = h_k->size() * sizeof(double);
+    TBK_CHECK(m->ws_k.reserve(k_bytes));
+    TBK_CHECK(m->ws_out.reserve((size_t)(head_pts + nk) * n_orb * sizeof(double)));
+    TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, h_k->data(), k_bytes, hipMemcpyHostToDevice, m->stream));
+    TBK_CHECK(tbk_eigenval_device_hint(m, m->ws_k.as<double>() + head_pts * dim, h_k->data() + head_pts * dim, nk,
+                                       m->ws_out.as<double>() + head_pts * n_orb));
+    if (below) TBK_CHECK(tbk_eigenval_device_hint(m, m->ws_k.as<double>(), h_k->data(), plane_pts, m->ws_out.as<double>()));
+    return TBK_OK;
+}
+
 extern "C" int tbk_dos_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double e_min, double e_step,
                                         int64_t n_e, double* nos_out) {
     int64_t nk = 0;
@@ -305,19 +330,13 @@ extern "C" int tbk_dos_from_eigenvalues(int device, int dim, const int32_t* mesh
     TBK_CHECK(dos_plan(dim, mesh, mesh[0], mesh[0], n_orb, n_e, &L));
     const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double);
     DevBuf d_E, d_ws, d_nos;
-    const int rc = [&]() -> int {
-        TBK_CHECK(d_E.reserve(e_bytes));
-        TBK_CHECK(d_ws.reserve(L.ws_bytes));
-        TBK_CHECK(d_nos.reserve((size_t)n_e * sizeof(double)));
-        TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
-        TBK_CHECK(dos_launch(nullptr, dim, L, d_E.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk, d_ws.ptr, d_nos.as<double>()));
-        TBK_HIP(hipMemcpy(nos_out, d_nos.ptr, (size_t)n_e * sizeof(double), hipMemcpyDeviceToHost));
-        return TBK_OK;
-    }();
-    d_E.release();
-    d_ws.release();
-    d_nos.release();
-    return rc;
+    TBK_CHECK(d_E.reserve(e_bytes));
+    TBK_CHECK(d_ws.reserve(L.ws_bytes));
+    TBK_CHECK(d_nos.reserve((size_t)n_e * sizeof(double)));
+    TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
+    TBK_CHECK(dos_launch(nullptr, dim, L, d_E.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk, d_ws.ptr, d_nos.as<double>()));
+    TBK_HIP(hipMemcpy(nos_out, d_nos.ptr, (size_t)n_e * sizeof(double), hipMemcpyDeviceToHost));
+    return TBK_OK;
 }
 
 // Cells [p_lo, p_lo + p_count) along axis 0 of the mesh on one handle: the eigenvalues of those planes and of the one periodic
@@ -335,44 +354,25 @@ int tbk_dos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_coun
     TBK_ARG(p_lo >= 0 && p_count >= 1 && p_lo + p_count <= n0, "slab outside the mesh");
     TBK_HIP(hipSetDevice(m->device));
     const int64_t planes = p_count == n0 ? n0 : p_count + 1;
-    const int64_t plane_pts = nk_total / n0, nk = planes * plane_pts;
     DosLaunch L;
     TBK_CHECK(dos_plan(dim, mesh, p_count, planes, n_orb, n_e, &L));
 
-    std::vector<double> h_k;
-    TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, p_lo, planes, &h_k));
-    const size_t k_bytes = h_k.size() * sizeof(double);
-    TBK_CHECK(m->ws_k.reserve(k_bytes));
-    TBK_CHECK(m->ws_out.reserve((size_t)nk * n_orb * sizeof(double)));
     TBK_CHECK(m->ws_dos.reserve(L.ws_bytes + dos_align256((size_t)n_e * sizeof(double))));
-    TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, h_k.data(), k_bytes, hipMemcpyHostToDevice, m->stream));
-    // the existing pipeline with the host list as the fold hint: dense models fold, CSR models take their own path
-    TBK_CHECK(tbk_eigenval_device_hint(m, m->ws_k.as<double>(), h_k.data(), nk, m->ws_out.as<double>()));
+    std::vector<double> h_k;
+    TBK_CHECK(tbk_mesh_eigenvalues(m, mesh, p_lo, planes, false, &h_k));
     TBK_CHECK(tbk_eigenval_check(m));  // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigenval
 
-    double* d_nos = reinterpret_cast<double*>(static_cast<char*>(m->ws_dos.ptr) + L.ws_bytes);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timed = m->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-    if (timed) (void)hipEventRecord(ev[0], m->stream);
-    int rc = dos_launch(m->stream, dim, L, m->ws_out.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk_total, m->ws_dos.ptr, d_nos);
-    if (timed) (void)hipEventRecord(ev[1], m->stream);
-    if (rc == TBK_OK) {
-        rc = [&]() -> int {
-            TBK_HIP(hipMemcpyAsync(nos_out, d_nos, (size_t)n_e * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-            TBK_HIP(hipStreamSynchronize(m->stream));
-            return TBK_OK;
-        }();
-    }
-    if (timed && rc == TBK_OK) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) {
-            m->dos_ms += (double)ms;
-            m->dos_calls += 1;
-        }
-    }
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    return rc;
+    double* d_nos = reinterpret_cast<double*>(m->ws_dos.as<char>() + L.ws_bytes);
+    SpanRecorder timer(m->timing, m->stream);
+    timer.start();
+    TBK_CHECK(dos_launch(m->stream, dim, L, m->ws_out.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk_total, m->ws_dos.ptr, d_nos));
+    timer.stop();
+    TBK_HIP(hipMemcpyAsync(nos_out, d_nos, (size_t)n_e * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    TBK_HIP(hipStreamSynchronize(m->stream));
+    TimedSums& sums = m->timed[TIMED_DOS];
+    timer.collect(sums.ms);
+    if (timer.on) sums.calls += 1;
+    return TBK_OK;
 }
 
 extern "C" int tbk_dos(tbk_model* m, const int32_t* mesh, double e_min, double e_step, int64_t n_e, double* nos_out) {
@@ -385,12 +385,5 @@ extern "C" int tbk_dos(tbk_model* m, const int32_t* mesh, double e_min, double e
 
 extern "C" int tbk_dos_timing(tbk_model* m, double* ms, int64_t* calls, int reset) {
     TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr, "model / ms / calls is NULL");
-    TBK_LOCK(m);
-    *ms = m->dos_ms;
-    *calls = m->dos_calls;
-    if (reset) {
-        m->dos_ms = 0.0;
-        m->dos_calls = 0;
-    }
-    return TBK_OK;
+    return tbk_timed_read(m, TIMED_DOS, 1, ms, calls, nullptr, reset);
 }

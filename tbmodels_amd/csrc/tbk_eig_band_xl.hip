@@ -705,9 +705,9 @@ int tbk_band_launch_xl(tbk_model* m, const tbk_eig_plan_t& plan, hipStream_t s, 
         // the side streams and their events exist from the first batch that uses them (not for every model: the temporary
         // models of tbk_tridiagonal_reduce / tbk_reduce_standalone and every small model never get here)
         for (int g = 1; g < groups; ++g)
-            if (m->stream_xl[g - 1] == nullptr) TBK_HIP(hipStreamCreateWithFlags(&m->stream_xl[g - 1], hipStreamNonBlocking));
+            if (m->stream_xl[g - 1] == nullptr) TBK_HIP(hipStreamCreateWithFlags(m->stream_xl[g - 1].put(), hipStreamNonBlocking));
         for (int g = 0; g < groups; ++g)
-            if (m->ev_xl[g] == nullptr) TBK_HIP(hipEventCreateWithFlags(&m->ev_xl[g], hipEventDisableTiming));
+            if (m->ev_xl[g] == nullptr) TBK_HIP(hipEventCreateWithFlags(m->ev_xl[g].put(), hipEventDisableTiming));
         TBK_HIP(hipEventRecord(m->ev_xl[0], s));
         const int64_t per = (nk + groups - 1) / groups;
         for (int g = 1; g < groups; ++g) TBK_HIP(hipStreamWaitEvent(m->stream_xl[g - 1], m->ev_xl[0], 0));

@@ -416,7 +416,7 @@ extern "C" int tbk_eigh(tbk_model* m, const double* k, int64_t nk, int conventio
     }
     const bool staged_in = m->h_stage != nullptr && k_bytes + p_bytes <= m->h_stage_bytes;
     if (staged_in) {
-        char* st = static_cast<char*>(m->h_stage);
+        char* st = static_cast<char*>(m->h_stage.h);
         std::memcpy(st, k, k_bytes);
         if (p_bytes) std::memcpy(st + k_bytes, pos, p_bytes);
         TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, st, k_bytes, hipMemcpyHostToDevice, m->stream));
@@ -435,7 +435,7 @@ extern "C" int tbk_eigh(tbk_model* m, const double* k, int64_t nk, int conventio
                                   m->ws_out.as<double>()));
         // (a small result comes down through the pinned buffer -- after the upload has left it: same stream)
         if (staged_in && nkc == nk && u_bytes + e_bytes <= m->h_stage_bytes) {
-            char* st = static_cast<char*>(m->h_stage);
+            char* st = static_cast<char*>(m->h_stage.h);
             TBK_HIP(hipMemcpyAsync(st, m->ws_out.ptr, u_bytes, hipMemcpyDeviceToHost, m->stream));
             TBK_HIP(hipMemcpyAsync(st + u_bytes, m->ws_out2.ptr, e_bytes, hipMemcpyDeviceToHost, m->stream));
             TBK_CHECK(tbk_eigenval_check(m));  // synchronises

@@ -283,21 +283,9 @@ struct FermiSlab {
     const double* d_E = nullptr;
     char* d_ws = nullptr;
     std::vector<double> h_k;  // the mesh's k list until the eigenvalues are checked
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool timed = false;
-    double ms = 0.0;
+    SpanRecorder timer;       // off unless the slab is a staged handle's with TBK_OPT_TIMING on
+    double ms = 0.0;          // the kernels of every pass of the call
     unsigned long long h_sums[FERMI_PROBES * 3];
-
-    void start() {
-        if (timed) (void)hipEventRecord(ev[0], stream);
-    }
-    void stop() {
-        if (timed) (void)hipEventRecord(ev[1], stream);
-    }
-    void collect_time() {  // after a synchronisation of the stream
-        float t = 0.f;
-        if (timed && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) ms += (double)t;
-    }
 };
 
 // enqueue: N at n probes (1 .. 16) of this slab's cells -> h_sums, behind the stream
@@ -308,7 +296,7 @@ int fermi_probe_enqueue(FermiSlab& s, const double* energies, int n) {
     auto* part_g = reinterpret_cast<unsigned long long*>(s.d_ws);
     auto* count_g = reinterpret_cast<unsigned*>(s.d_ws + s.L.off_count);
     auto* sums = reinterpret_cast<unsigned long long*>(s.d_ws + s.L.off_sums);
-    s.start();
+    s.timer.start();
     if (s.dim == 3)
         hipLaunchKernelGGL(nos_probe_kernel<3>, dim3((unsigned)s.L.n_wg), dim3(FERMI_THREADS), 0, s.stream, s.d_E, s.L.g, p, part_g, count_g);
     else
@@ -316,7 +304,7 @@ int fermi_probe_enqueue(FermiSlab& s, const double* energies, int n) {
     TBK_HIP(hipGetLastError());
     hipLaunchKernelGGL(nos_probe_reduce_kernel, dim3(1), dim3(FERMI_THREADS), 0, s.stream, part_g, count_g, s.L.n_wg, sums);
     TBK_HIP(hipGetLastError());
-    s.stop();
+    s.timer.stop();
     TBK_HIP(hipMemcpyAsync(s.h_sums, sums, sizeof(s.h_sums), hipMemcpyDeviceToHost, s.stream));
     return TBK_OK;
 }
@@ -328,7 +316,7 @@ int fermi_probe(std::vector<FermiSlab>& slabs, const double* energies, int n, Fe
     for (FermiSlab& s : slabs) {
         TBK_HIP(hipSetDevice(s.device));
         TBK_HIP(hipStreamSynchronize(s.stream));
-        s.collect_time();
+        s.timer.collect(&s.ms);
         for (int m = 0; m < n; ++m) q[m].add(fermi_count(s.h_sums + 3 * m));
     }
     return TBK_OK;
@@ -345,12 +333,12 @@ int fermi_edges(std::vector<FermiSlab>& slabs, int n_orb, double* emin, double* 
         auto* d_min = reinterpret_cast<double*>(s.d_ws + s.L.off_emin);
         auto* d_max = reinterpret_cast<double*>(s.d_ws + s.L.off_emax);
         const dim3 grid((unsigned)s.L.edge_wg, (unsigned)((n_orb + FERMI_THREADS - 1) / FERMI_THREADS));
-        s.start();
+        s.timer.start();
         hipLaunchKernelGGL(band_edges_kernel, grid, dim3(FERMI_THREADS), 0, s.stream, s.d_E, s.L.rows, n_orb, pmin, pmax);
         TBK_HIP(hipGetLastError());
         hipLaunchKernelGGL(band_edges_reduce_kernel, dim3(grid.y), dim3(FERMI_THREADS), 0, s.stream, pmin, pmax, s.L.edge_wg, n_orb, d_min, d_max);
         TBK_HIP(hipGetLastError());
-        s.stop();
+        s.timer.stop();
         double* h = share.data() + i * 2 * (size_t)n_orb;
         TBK_HIP(hipMemcpyAsync(h, d_min, (size_t)n_orb * sizeof(double), hipMemcpyDeviceToHost, s.stream));
         TBK_HIP(hipMemcpyAsync(h + n_orb, d_max, (size_t)n_orb * sizeof(double), hipMemcpyDeviceToHost, s.stream));
@@ -359,7 +347,7 @@ int fermi_edges(std::vector<FermiSlab>& slabs, int n_orb, double* emin, double* 
         FermiSlab& s = slabs[i];
         TBK_HIP(hipSetDevice(s.device));
         TBK_HIP(hipStreamSynchronize(s.stream));
-        s.collect_time();
+        s.timer.collect(&s.ms);
         const double* h = share.data() + i * 2 * (size_t)n_orb;
         for (int b = 0; b < n_orb; ++b) {
             emin[b] = i == 0 ? h[b] : std::fmin(emin[b], h[b]);
@@ -461,12 +449,9 @@ int fermi_check_electrons(double n_electrons, int n_orb) {
 struct FermiOwned {
     DevBuf d_E, d_ws;
     std::vector<FermiSlab> slabs;
-    ~FermiOwned() {
-        d_E.release();
-        d_ws.release();
-    }
     int make(int device, int dim, const int32_t* mesh, int n_orb, const double* E, int64_t nk) {
-        FermiSlab s;
+        slabs.emplace_back();
+        FermiSlab& s = slabs.back();
         s.device = device;
         s.dim = dim;
         TBK_CHECK(fermi_plan(dim, mesh, mesh[0], mesh[0], n_orb, &s.L));
@@ -476,7 +461,6 @@ struct FermiOwned {
         TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
         s.d_E = d_E.as<double>();
         s.d_ws = d_ws.as<char>();
-        slabs.push_back(s);
         return TBK_OK;
     }
 };
@@ -487,11 +471,6 @@ struct FermiOwned {
 struct FermiStaged : TetraHandles {
     std::vector<FermiSlab> slabs;
     int64_t simplices = 0;
-    ~FermiStaged() {
-        for (FermiSlab& s : slabs)
-            for (hipEvent_t e : s.ev)
-                if (e) (void)hipEventDestroy(e);
-    }
     int make(tbk_model* const* handles, int n_handles, const int32_t* mesh) {
         TBK_CHECK(open(handles, n_handles, mesh, FERMI_MESH));
         simplices = (int64_t)(dim == 3 ? 6 : 2) * nk_total;
@@ -507,19 +486,13 @@ struct FermiStaged : TetraHandles {
             s.dim = dim;
             s.stream = m->stream;
             TBK_HIP(hipSetDevice(m->device));
-            const int64_t planes = p_count == n0 ? n0 : p_count + 1, nk = planes * plane_pts;
+            const int64_t planes = p_count == n0 ? n0 : p_count + 1;
             TBK_CHECK(fermi_plan(dim, mesh, p_count, planes, n_orb, &s.L));
-            TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, p_lo, planes, &s.h_k));
-            const size_t k_bytes = s.h_k.size() * sizeof(double);
-            TBK_CHECK(m->ws_k.reserve(k_bytes));
-            TBK_CHECK(m->ws_out.reserve((size_t)nk * n_orb * sizeof(double)));
             TBK_CHECK(m->ws_dos.reserve(s.L.ws_bytes));
-            TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, s.h_k.data(), k_bytes, hipMemcpyHostToDevice, m->stream));
-            // the existing pipeline with the host list as the fold hint, as in tbk_dos_slab
-            TBK_CHECK(tbk_eigenval_device_hint(m, m->ws_k.as<double>(), s.h_k.data(), nk, m->ws_out.as<double>()));
+            TBK_CHECK(tbk_mesh_eigenvalues(m, mesh, p_lo, planes, false, &s.h_k));
             s.d_E = m->ws_out.as<double>();
             s.d_ws = m->ws_dos.as<char>();
-            s.timed = m->timing && hipEventCreate(&s.ev[0]) == hipSuccess && hipEventCreate(&s.ev[1]) == hipSuccess;
+            s.timer = SpanRecorder(m->timing, m->stream);
         }
         // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigenval: the first failing slab's
         for (FermiSlab& s : slabs) {
@@ -530,9 +503,10 @@ struct FermiStaged : TetraHandles {
     }
     void book(int passes, bool searched) {
         for (FermiSlab& s : slabs) {
-            s.m->fermi_ms += s.ms;
-            s.m->fermi_calls += 1;
-            if (searched) s.m->fermi_passes += passes;
+            TimedSums& sums = s.m->timed[TIMED_FERMI];
+            if (s.timer.on) sums.ms[0] += s.ms;
+            sums.calls += 1;
+            if (searched) sums.passes += passes;
         }
     }
 };
@@ -647,14 +621,5 @@ extern "C" int tbk_fermi(tbk_model* m, const int32_t* mesh, double n_electrons, 
 
 extern "C" int tbk_fermi_timing(tbk_model* m, double* ms, int64_t* calls, int64_t* passes, int reset) {
     TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr && passes != nullptr, "model / ms / calls / passes is NULL");
-    TBK_LOCK(m);
-    *ms = m->fermi_ms;
-    *calls = m->fermi_calls;
-    *passes = m->fermi_passes;
-    if (reset) {
-        m->fermi_ms = 0.0;
-        m->fermi_calls = 0;
-        m->fermi_passes = 0;
-    }
-    return TBK_OK;
+    return tbk_timed_read(m, TIMED_FERMI, 1, ms, calls, passes, reset);
 }

@@ -190,13 +190,13 @@ static int build_plan(tbk_fold_plan_t& plan, const int32_t* R, int64_t n_r, int 
     }
     std::vector<int32_t> r2((size_t)plan.n_rho_pad * std::max(dim - 1, 1), 0);
     std::copy(plan.h_R2.begin(), plan.h_R2.end(), r2.begin());
-    TBK_HIP(hipMalloc((void**)&plan.d_R2, std::max<size_t>(r2.size(), 1) * sizeof(int32_t)));
-    TBK_HIP(hipMalloc((void**)&plan.d_lptr, lptr.size() * sizeof(int64_t)));
-    TBK_HIP(hipMalloc((void**)&plan.d_lrec, std::max<size_t>(lrec.size(), 1) * sizeof(int32_t)));
-    TBK_HIP(hipMalloc((void**)&plan.d_rcomp, std::max<size_t>(rcomp.size(), 1) * sizeof(int32_t)));
-    TBK_HIP(hipMalloc((void**)&plan.d_B2, (size_t)capacity * plan.k2 * plan.row_len * sizeof(double)));
+    TBK_HIP(hipMalloc(plan.d_R2.put(), std::max<size_t>(r2.size(), 1) * sizeof(int32_t)));
+    TBK_HIP(hipMalloc(plan.d_lptr.put(), lptr.size() * sizeof(int64_t)));
+    TBK_HIP(hipMalloc(plan.d_lrec.put(), std::max<size_t>(lrec.size(), 1) * sizeof(int32_t)));
+    TBK_HIP(hipMalloc(plan.d_rcomp.put(), std::max<size_t>(rcomp.size(), 1) * sizeof(int32_t)));
+    TBK_HIP(hipMalloc(plan.d_B2.put(), (size_t)capacity * plan.k2 * plan.row_len * sizeof(double)));
     plan.table_entries = n_r * FOLD_GROUP;
-    TBK_HIP(hipMalloc((void**)&plan.d_table, std::max<size_t>((size_t)plan.table_entries * 2, 1) * sizeof(double)));
+    TBK_HIP(hipMalloc(plan.d_table.put(), std::max<size_t>((size_t)plan.table_entries * 2, 1) * sizeof(double)));
     TBK_HIP(hipMemcpy(plan.d_R2, r2.data(), r2.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     TBK_HIP(hipMemcpy(plan.d_lptr, lptr.data(), lptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     TBK_HIP(hipMemcpy(plan.d_lrec, lrec.data(), lrec.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -215,32 +215,12 @@ static int tbk_fold_subplan(tbk_model* m, tbk_fold_plan_t& parent, int f2, int c
     *out = nullptr;
     const int dim2 = parent.dim - 1;
     if (dim2 < 2 || f2 < 0 || f2 >= dim2) return TBK_OK;
-    if (!parent.sub) parent.sub = new tbk_fold_plan_t[TBK_MAX_DIM];
+    if (!parent.sub) parent.sub.reset(new tbk_fold_plan_t[TBK_MAX_DIM]);
     tbk_fold_plan_t& plan = parent.sub[f2];
-    if (plan.built && plan.capacity < capacity) {  // a longer piece than any before: rebuild with more room
-        void* ptrs[] = {plan.d_R2, plan.d_lptr, plan.d_lrec, plan.d_rcomp, plan.d_B2, plan.d_table};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        plan = tbk_fold_plan_t();
-    }
+    if (plan.built && plan.capacity < capacity) plan = tbk_fold_plan_t();  // a longer piece than any before: rebuild with more room
     TBK_CHECK(build_plan(plan, parent.h_R2.data(), parent.n_rho, dim2, f2, m->ncol_pad, capacity));
     *out = &plan;
     return TBK_OK;
-}
-
-static void release_plan(tbk_fold_plan_t& plan) {
-    if (plan.sub) {
-        for (int i = 0; i < TBK_MAX_DIM; ++i) release_plan(plan.sub[i]);
-        delete[] plan.sub;
-    }
-    void* ptrs[] = {plan.d_R2, plan.d_lptr, plan.d_lrec, plan.d_rcomp, plan.d_B2, plan.d_table};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    plan = tbk_fold_plan_t();
-}
-
-void tbk_fold_release(tbk_model* m) {
-    for (tbk_fold_plan_t& plan : m->fold) release_plan(plan);
 }
 
 // Average run length from which folding pays: a run costs one pass over Bt (60 us at the headline shape) plus
@@ -384,10 +364,9 @@ static int tbk_fold_lines(tbk_model* m, const tbk_operand_t& from, tbk_fold_plan
     const int64_t row_len = plan.row_len;
     StageTimer t(m, TBK_T_PHASE);
     if ((size_t)plan.table_entries < (size_t)plan.n_r * n_lines) {
-        if (plan.d_table) TBK_HIP(hipFree(plan.d_table));
-        plan.d_table = nullptr;
+        plan.d_table.reset();
         plan.table_entries = plan.n_r * (int64_t)std::max(n_lines, plan.capacity);
-        TBK_HIP(hipMalloc((void**)&plan.d_table, std::max<size_t>((size_t)plan.table_entries * 2, 1) * sizeof(double)));
+        TBK_HIP(hipMalloc(plan.d_table.put(), std::max<size_t>((size_t)plan.table_entries * 2, 1) * sizeof(double)));
     }
     const int64_t entries = plan.n_r * n_lines;
     hipLaunchKernelGGL(fold_table_dev_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, m->stream,

@@ -9,8 +9,10 @@
 #include <cstdint>
 #include <cstdio>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "tbk.h"
@@ -104,22 +106,84 @@ inline hipError_t tbk_raise_lds_limit(const void* kernel, int bytes, tbk_flag_ro
 }
 
 // ------------------------------------------------------------------------------------------------
-// a grow-only device buffer
+// Owners of GPU resources.  Move-only; each converts to its raw handle or pointer, so launches, copies and
+// hipStreamWaitEvent / hipEventRecord take them as they take the raw ones.  put(): the address a create call fills (what
+// the owner held before is let go first).  Members are destroyed with the struct that holds them: nothing else frees.
 // ------------------------------------------------------------------------------------------------
+template <class H, auto Destroy>
+struct Owned {
+    H h = nullptr;
+    Owned() = default;
+    Owned(Owned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    Owned& operator=(Owned&& o) noexcept {
+        if (this != &o) {
+            reset();
+            h = o.h;
+            o.h = nullptr;
+        }
+        return *this;
+    }
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    ~Owned() { reset(); }
+    void reset() {
+        if (h) (void)Destroy(h);
+        h = nullptr;
+    }
+    H* put() {
+        reset();
+        return &h;
+    }
+    operator H() const { return h; }
+};
+template <class T>
+using DevPtr = Owned<T*, hipFree>;  // device memory of hipMalloc
+using PinnedPtr = Owned<void*, hipHostFree>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+
+// a grow-only device buffer
 struct DevBuf {
-    void* ptr = nullptr;
+    DevPtr<void> ptr;
     size_t bytes = 0;
     int reserve(size_t want);  // keeps contents only if no reallocation happens
-    void release();
     template <class T>
     T* as() const {
-        return static_cast<T*>(ptr);
+        return static_cast<T*>(ptr.h);
     }
 };
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value,
+              "a DevBuf owns its memory: it moves, it is never copied");
 
-struct EventPair {
-    hipEvent_t start, stop;
-    int stage;
+// ------------------------------------------------------------------------------------------------
+// HIP-event timing.  One span: the kernels between a start and a stop event on one stream, booked on `stage`.
+// ------------------------------------------------------------------------------------------------
+struct EventSpan {
+    Event start, stop;
+    int stage = 0;
+};
+
+// The spans of one call on one stream.  start / stop do nothing when timing is off; collect, after the stream has been
+// synchronised, adds every span to ms[stage] and drops the spans.  An event that cannot be created or read switches the
+// recorder off for good (`on` tells): the call goes on untimed and what it had recorded is not added.
+struct SpanRecorder {
+    hipStream_t stream = nullptr;
+    bool on = false;
+    std::vector<EventSpan> spans;
+    SpanRecorder() = default;
+    SpanRecorder(bool timing, hipStream_t s) : stream(s), on(timing) {}
+    void start(int stage = 0);
+    void stop();
+    void collect(double* ms);
+};
+
+// The sums the mesh calls book their kernel times on, one row per family (tbk_dos_timing, tbk_pdos_timing, tbk_fermi_timing,
+// tbk_occ_timing: what each counts differs and is listed in DESIGN.md section 10)
+enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_COUNT };
+struct TimedSums {
+    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one)
+    int64_t calls = 0;
+    int64_t passes = 0;  // fermi: the passes of its searches
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -144,14 +208,14 @@ struct tbk_fold_plan_t {
     int64_t row_len = 0;         // doubles per operand row: ncol_pad * 2
     int capacity = 0;            // folded operands that fit d_B2
     std::vector<int32_t> h_R2;   // host copy of the folded lattice [n_rho][dim - 1] (second-level plans are built on it)
-    int32_t* d_R2 = nullptr;     // [n_rho_pad][dim - 1]
-    int64_t* d_lptr = nullptr;   // [n_rho_pad + 1] lists of contributing lattice vectors
-    int32_t* d_lrec = nullptr;   // r | (negated ? 1 << 31 : 0)
-    int32_t* d_rcomp = nullptr;  // [n_r] the folded component of every lattice vector
-    double* d_B2 = nullptr;      // [capacity][k2][row_len] folded operands
-    double* d_table = nullptr;   // [n_r][slots][2] (cos, sin) of the shared-component phases
+    DevPtr<int32_t> d_R2;        // [n_rho_pad][dim - 1]
+    DevPtr<int64_t> d_lptr;      // [n_rho_pad + 1] lists of contributing lattice vectors
+    DevPtr<int32_t> d_lrec;      // r | (negated ? 1 << 31 : 0)
+    DevPtr<int32_t> d_rcomp;     // [n_r] the folded component of every lattice vector
+    DevPtr<double> d_B2;         // [capacity][k2][row_len] folded operands
+    DevPtr<double> d_table;      // [n_r][slots][2] (cos, sin) of the shared-component phases
     int64_t table_entries = 0;   // its capacity in (r, slot) pairs
-    tbk_fold_plan_t* sub = nullptr;  // [dim - 1] second-level plans (mesh lines inside a mesh plane), built on demand
+    std::unique_ptr<tbk_fold_plan_t[]> sub;  // [dim - 1] second-level plans (mesh lines inside a mesh plane), built on demand
     double* slot(int s) const { return d_B2 + (size_t)s * k2 * row_len; }
     // the folded model whose operand rows are in slot s
     tbk_operand_t operand(int s) const { return {dim - 1, n_rho, n_rho_pad, k2, d_R2, slot(s)}; }
@@ -180,34 +244,34 @@ struct tbk_model {
     int ncol = 0;          // packed slots: ceil(n_orb^2 / 2) for dense tight-binding models (diagonal pairs),
                            // n_orb (n_orb + 1) / 2 upper-triangle elements for CSR and k.p models
     int ncol_pad = 0;      // rounded up to TBK_BNP
-    int32_t* d_R = nullptr;       // [n_r_pad][dim] lattice vectors (padding rows are zero)
-    int32_t* d_colmap = nullptr;  // [ncol_pad]  (i << 16) | j, (i << 16) | TBK_SLOT_PAIR | j, or -1 for padding
-    int32_t* d_powers = nullptr;  // k.p only: [n_r][dim] monomial exponents
+    DevPtr<int32_t> d_R;       // [n_r_pad][dim] lattice vectors (padding rows are zero)
+    DevPtr<int32_t> d_colmap;  // [ncol_pad]  (i << 16) | j, (i << 16) | TBK_SLOT_PAIR | j, or -1 for padding
+    DevPtr<int32_t> d_powers;  // k.p only: [n_r][dim] monomial exponents
 
     // --- dense: symmetrised hop planes, tile-interleaved  Bt[K2][ncol_pad / 16][2][16] ---
-    double* d_B = nullptr;
+    DevPtr<double> d_B;
     // --- dense, n_r_pad >= TBK_STRASSEN_MIN_NR: the seven right operands of one Strassen level, Bs[7][K2 / 2][ncol_pad / 2 / 16][2][16]
     // (tbk_stage.hip), built from the staged d_B and valid for that operand alone (a folded one has none)
-    double* d_Bs = nullptr;
+    DevPtr<double> d_Bs;
     // --- the 49 right operands of two Strassen levels, Bs2[49][K2 / 4][ncol_pad / 4 / 16][2][16]: the table applied to each block
     // of d_Bs (valid while d_Bs is).  Built by the first call whose chunks take two levels (tbk_stage_strassen2); bs2_skipped:
     // they did not fit a quarter of the free memory then, and the model stays on one level
-    double* d_Bs2 = nullptr;
+    DevPtr<double> d_Bs2;
     bool bs2_skipped = false;
 
     // --- sparse: per packed element, the list of lattice vectors that touch it ---
     int64_t nnz_rec = 0;
-    int64_t* d_cptr = nullptr;   // [ncol + 1]
-    int32_t* d_rec_r = nullptr;  // [nnz_rec]  (kind << 28) | r   kind: 0 direct, 1 transposed, 2 diagonal
-    double* d_rec_v = nullptr;   // [nnz_rec][2]
+    DevPtr<int64_t> d_cptr;   // [ncol + 1]
+    DevPtr<int32_t> d_rec_r;  // [nnz_rec]  (kind << 28) | r   kind: 0 direct, 1 transposed, 2 diagonal
+    DevPtr<double> d_rec_v;   // [nnz_rec][2]
     // the same records in the order the LDS kernel walks them: per 64 packed elements ("wave round") a number of steps,
     // every step one record (or none) per lane, arranged so that the 16 lanes the LDS serves together read 16 different
     // 16-byte slots of its 256-byte row (tbk_hk_csr.hip: tbk_csr_schedule)
     int sched_kt = 0;             // k-points per phase tile the schedule was built for (0: no schedule)
     int64_t sched_steps = 0;
-    int64_t* d_sptr = nullptr;    // [ceil(ncol / 64) + 1] first step of every wave round
-    int32_t* d_srec_r = nullptr;  // [sched_steps][64]  (sign code << 30) | byte offset of the phase row, 0x80000000: no record
-    double* d_srec_v = nullptr;   // [sched_steps][64][2]
+    DevPtr<int64_t> d_sptr;    // [ceil(ncol / 64) + 1] first step of every wave round
+    DevPtr<int32_t> d_srec_r;  // [sched_steps][64]  (sign code << 30) | byte offset of the phase row, 0x80000000: no record
+    DevPtr<double> d_srec_v;   // [sched_steps][64][2]
 
     int64_t staged_bytes = 0;
 
@@ -226,18 +290,20 @@ struct tbk_model {
     bool timing = false;
 
     // --- runtime ---
-    hipStream_t stream = nullptr;      // phase rows, H(k), rocSOLVER, collectives
-    hipStream_t stream_eig = nullptr;  // wave eigensolver: reduction to tridiagonal form
-    hipStream_t stream_ql = nullptr;   // wave eigensolver: tridiagonal QL (latency-bound, overlaps the rest)
-    hipStream_t stream_xl[3] = {nullptr, nullptr, nullptr};  // band_xl_* above 1024 orbitals: the other groups of a batch (tbk_eig_band.hip)
-    hipEvent_t ev_xl[4] = {nullptr, nullptr, nullptr, nullptr};  // fork, and one join per extra group
-    hipEvent_t ev_hk[2] = {nullptr, nullptr};   // H[buf] written
-    hipEvent_t ev_tri[2] = {nullptr, nullptr};  // H[buf] consumed, (d, e)[buf] written
-    hipEvent_t ev_out[2] = {nullptr, nullptr};  // tbk_hamilton: chunk in ws_out / ws_out2 computed
-    hipEvent_t ev_ql[2] = {nullptr, nullptr};   // (d, e)[buf] consumed, eigenvalues written
-    hipEvent_t ev_s2[2] = {nullptr, nullptr};   // two-pass Strassen combine (launch_strassen2): the first product launch done, the first pass done
-    hipEvent_t ev_sync = nullptr;               // host waits on the main stream go through this event (tbk_api.hip)
-    rocblas_handle blas = nullptr;
+    // (members are destroyed last to first: the streams are declared in front of everything that is used on them, and the
+    // rocBLAS handle, behind them, goes before the stream it was set to; tbk_model_destroy synchronises the streams first)
+    Stream stream;      // phase rows, H(k), rocSOLVER, collectives
+    Stream stream_eig;  // wave eigensolver: reduction to tridiagonal form
+    Stream stream_ql;   // wave eigensolver: tridiagonal QL (latency-bound, overlaps the rest)
+    Stream stream_xl[3];  // band_xl_* above 1024 orbitals: the other groups of a batch (tbk_eig_band.hip)
+    Event ev_xl[4];     // fork, and one join per extra group
+    Event ev_hk[2];     // H[buf] written
+    Event ev_tri[2];    // H[buf] consumed, (d, e)[buf] written
+    Event ev_out[2];    // tbk_hamilton: chunk in ws_out / ws_out2 computed
+    Event ev_ql[2];     // (d, e)[buf] consumed, eigenvalues written
+    Event ev_s2[2];     // two-pass Strassen combine (launch_strassen2): the first product launch done, the first pass done
+    Event ev_sync;      // host waits on the main stream go through this event (tbk_api.hip)
+    Owned<rocblas_handle, rocblas_destroy_handle> blas;
     DevBuf ws_phase;  // [K2][nk_pad] cos/sin rows
     DevBuf ws_H;      // [chunk][n_orb][n_orb] complex
     DevBuf ws_H2;     // second H buffer: folded H(k) of a chunk is built beside the previous chunk's reduction
@@ -253,7 +319,7 @@ struct tbk_model {
     // small host-buffer calls (one k-point per call is what Z2Pack-style callers do): k, the result and the flags cross
     // PCIe through this PINNED buffer -- asynchronous DMA copies enqueued back to back and ONE synchronisation, where
     // three copies from / to pageable memory each cost a host-side staging round trip (~20 us apiece)
-    void* h_stage = nullptr;
+    PinnedPtr h_stage;
     size_t h_stage_bytes = 0;
     DevBuf ws_part;   // split-K partial tiles of the dense H(k) kernel (small k batches)
     DevBuf ws_c11;    // two-pass Strassen combine: the four partial C11 quarters between its passes, [4][Mq][ncol_pad / 4] (re, im)
@@ -279,18 +345,10 @@ struct tbk_model {
     // whenever the eigenvalues of rows [c0, c0 + nkc) of the call have been enqueued, with an event recorded behind
     // them -- the all-gather of finished rows leaves on the communicator's stream while later chunks compute.
     std::function<int(int64_t c0, int64_t nkc, hipEvent_t done)> chunk_done;
-    std::vector<EventPair> events;
+    std::vector<EventSpan> events;  // StageTimer's spans, read by tbk_get_timing (no synchronisation on the pipeline's path)
     double t_ms[TBK_T_COUNT] = {0, 0, 0, 0};
     int64_t t_n[TBK_T_COUNT] = {0, 0, 0, 0};
-    double dos_ms = 0.0;    // tbk_dos_timing: summed HIP-event time of the density-of-states kernels while `timing` is on
-    int64_t dos_calls = 0;  // ... and the calls it was summed over
-    double pdos_ms[3] = {0.0, 0.0, 0.0};  // tbk_pdos_timing: the same for the weights kernel, the accumulate kernel, reduction + scan
-    int64_t pdos_calls = 0;
-    double fermi_ms = 0.0;     // tbk_fermi_timing: summed HIP-event time of the probe and band-edge kernels while `timing` is on
-    int64_t fermi_calls = 0;   // ... the tbk_fermi / tbk_band_edges calls of this handle
-    int64_t fermi_passes = 0;  // ... and the passes of its Fermi-level searches (counted whether `timing` is on or not)
-    double occ_ms[3] = {0.0, 0.0, 0.0};  // tbk_occ_timing: the weights kernel, the band sums, the contraction + its reduction
-    int64_t occ_calls = 0;
+    TimedSums timed[TIMED_COUNT];
 };
 
 // the operand the model was staged with
@@ -300,6 +358,10 @@ struct tbk_kdotp {
     tbk_model* core = nullptr;  // the dense pipeline with monomial rows in place of phase rows
 };
 
+// what a tbk_*_timing getter does behind its argument checks: the family's row (its first `stages` times; passes may be NULL),
+// read and, if asked, reset under the handle's lock
+int tbk_timed_read(tbk_model* m, TimedFamily family, int stages, double* ms, int64_t* calls, int64_t* passes, int reset);
+
 // roctx range around a stage (no-ops unless a roctx library can be loaded); tbk_api.hip
 void tbk_range_push(const char* name);
 void tbk_range_pop();
@@ -307,7 +369,7 @@ void tbk_range_pop();
 // timing scope helper: records a start/stop pair on the model stream when timing is on
 struct StageTimer {
     tbk_model* m;
-    EventPair ev;
+    EventSpan ev;
     bool on;
     hipStream_t stream;
     StageTimer(tbk_model* m_, int stage, hipStream_t s = nullptr);
@@ -535,7 +597,6 @@ private:
     int64_t group_lo = -1;            // first run of the group whose operands are in plan1's buffer
     double* d_k2 = nullptr;           // [nk][dim1] the k-points without component f (ws_kfold)
 };
-void tbk_fold_release(tbk_model* m);
 
 // tbk_dos.hip: the share of cells [p_lo, p_lo + p_count) along axis 0 of a mesh in nos (tbk_dos is the whole axis; tbk_dos_multi
 // gives every handle one slab)

@@ -383,53 +383,7 @@ struct OccTotals {
 
 const char* const OCC_MESH = "the tetrahedron weights need a 2- or 3-dimensional mesh";
 
-struct OccBufs {  // device memory of the entry points that bring their own eigensystem
-    DevBuf d_E, d_w, d_ws, d_U;
-    ~OccBufs() {
-        d_E.release();
-        d_w.release();
-        d_ws.release();
-        d_U.release();
-    }
-};
-
 // ---- the mesh on staged handles ------------------------------------------------------------------------------------------------
-struct OccEvents {  // (start, stop, stage) of one timed call on one handle, destroyed with it
-    struct Pair {
-        hipEvent_t a, b;
-        int stage;
-    };
-    std::vector<Pair> pairs;
-    bool on = false;
-    hipStream_t stream = nullptr;
-    void start(int stage) {
-        if (!on) return;
-        Pair p{nullptr, nullptr, stage};
-        if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) {
-            if (p.a) (void)hipEventDestroy(p.a);
-            on = false;
-            return;
-        }
-        (void)hipEventRecord(p.a, stream);
-        pairs.push_back(p);
-    }
-    void stop() {
-        if (on && !pairs.empty()) (void)hipEventRecord(pairs.back().b, stream);
-    }
-    void collect(double* ms) {  // after a synchronisation of the stream
-        for (const Pair& p : pairs) {
-            float t = 0.f;
-            if (on && hipEventElapsedTime(&t, p.a, p.b) == hipSuccess) ms[p.stage] += (double)t;
-        }
-    }
-    ~OccEvents() {
-        for (const Pair& p : pairs) {
-            (void)hipEventDestroy(p.a);
-            (void)hipEventDestroy(p.b);
-        }
-    }
-};
-
 struct OccSlab {
     tbk_model* m = nullptr;
     int64_t p_lo = 0, p_count = 0, planes = 0;
@@ -438,7 +392,7 @@ struct OccSlab {
     const double* d_E = nullptr;  // planes planes
     std::vector<double> h_k;
     std::vector<double> host;  // the off_host block
-    OccEvents ev;
+    SpanRecorder ev;  // stages: 0 the weights kernel, 1 the band sums, 2 the contraction + its reduction
 };
 
 // Handle i takes the slab of tbk_dos_multi.  Its eigenvalues: the planes [p_lo, p_lo + p_count] come from ONE call of the
@@ -466,31 +420,12 @@ struct OccStaged : TetraHandles {
             TBK_CHECK(tbk_eig_check_option(m));
             TBK_HIP(hipSetDevice(m->device));
             TBK_CHECK(occ_plan(dim, mesh, p_count, s.planes, s.off0, n_orb, &s.L));
-            // the k list: the neighbour plane below first, then the main planes
-            std::vector<double> below;
-            if (s.off0) TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, (p_lo - 1 + n0) % n0, 1, &below));
-            TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, p_lo, main_planes, &s.h_k));
-            try {
-                s.h_k.insert(s.h_k.begin(), below.begin(), below.end());
-            } catch (...) {
-                tbk_set_error("cannot allocate the k list of the mesh");
-                return TBK_ERR_MEMORY;
-            }
-            const size_t k_bytes = s.h_k.size() * sizeof(double);
-            const int64_t nk = s.planes * plane_pts;
-            TBK_CHECK(m->ws_k.reserve(k_bytes));
-            TBK_CHECK(m->ws_out.reserve((size_t)nk * n_orb * sizeof(double)));
             TBK_CHECK(m->ws_occ_w.reserve((size_t)s.L.rows * n_orb * sizeof(double)));
             TBK_CHECK(m->ws_occ.reserve(s.L.ws_bytes));
-            TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, s.h_k.data(), k_bytes, hipMemcpyHostToDevice, m->stream));
-            const int64_t head = (int64_t)s.off0 * plane_pts;  // points in front of the main planes
-            // the existing pipeline with the host list as the fold hint, as in tbk_dos_slab
-            TBK_CHECK(tbk_eigenval_device_hint(m, m->ws_k.as<double>() + head * dim, s.h_k.data() + head * dim, main_planes * plane_pts,
-                                               m->ws_out.as<double>() + head * n_orb));
-            if (s.off0) TBK_CHECK(tbk_eigenval_device_hint(m, m->ws_k.as<double>(), s.h_k.data(), plane_pts, m->ws_out.as<double>()));
+            // the neighbour plane below in front of the main planes
+            TBK_CHECK(tbk_mesh_eigenvalues(m, mesh, p_lo, main_planes, s.off0 != 0, &s.h_k));
             s.d_E = m->ws_out.as<double>();
-            s.ev.on = m->timing;
-            s.ev.stream = m->stream;
+            s.ev = SpanRecorder(m->timing, m->stream);
         }
         // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigenval: the first failing slab's
         for (OccSlab& s : slabs) TBK_CHECK(tbk_eigenval_check(s.m));
@@ -565,8 +500,8 @@ struct OccStaged : TetraHandles {
         for (OccSlab& s : slabs) {
             TBK_HIP(hipSetDevice(s.m->device));
             TBK_HIP(hipStreamSynchronize(s.m->stream));
-            s.ev.collect(s.m->occ_ms);
-            s.m->occ_calls += 1;
+            s.ev.collect(s.m->timed[TIMED_OCC].ms);
+            s.m->timed[TIMED_OCC].calls += 1;
         }
         return TBK_OK;
     }
@@ -584,12 +519,12 @@ extern "C" int tbk_tetra_weights_from_eigenvalues(int device, int dim, const int
     OccPlan L;
     TBK_CHECK(occ_plan(dim, mesh, mesh[0], mesh[0], 0, n_orb, &L));
     const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double);
-    OccBufs b;
-    TBK_CHECK(b.d_E.reserve(e_bytes));
-    TBK_CHECK(b.d_w.reserve(e_bytes));
-    TBK_HIP(hipMemcpy(b.d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
-    TBK_CHECK(occ_launch_weights(nullptr, L, b.d_E.as<double>(), energy, (double)nk, b.d_w.as<double>()));
-    TBK_HIP(hipMemcpy(w_out, b.d_w.ptr, e_bytes, hipMemcpyDeviceToHost));
+    DevBuf d_E, d_w;
+    TBK_CHECK(d_E.reserve(e_bytes));
+    TBK_CHECK(d_w.reserve(e_bytes));
+    TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
+    TBK_CHECK(occ_launch_weights(nullptr, L, d_E.as<double>(), energy, (double)nk, d_w.as<double>()));
+    TBK_HIP(hipMemcpy(w_out, d_w.ptr, e_bytes, hipMemcpyDeviceToHost));
     return TBK_OK;
 }
 
@@ -607,20 +542,20 @@ extern "C" int tbk_occupations_from_eigensystem(int device, int dim, const int32
     TBK_CHECK(occ_plan(dim, mesh, mesh[0], mesh[0], 0, n_orb, &L));
     const int64_t chunk = k_chunk == 0 ? nk : std::min(k_chunk, nk);
     const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double), u_per_k = (size_t)n_orb * (size_t)n_orb * 2;
-    OccBufs b;
-    TBK_CHECK(b.d_E.reserve(e_bytes));
-    TBK_CHECK(b.d_w.reserve(e_bytes));
-    TBK_CHECK(b.d_ws.reserve(L.ws_bytes));
-    TBK_CHECK(b.d_U.reserve((size_t)chunk * u_per_k * sizeof(double)));
-    char* ws = b.d_ws.as<char>();
-    TBK_HIP(hipMemcpy(b.d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
-    TBK_CHECK(occ_launch_weights(nullptr, L, b.d_E.as<double>(), energy, (double)nk, b.d_w.as<double>()));
-    TBK_CHECK(occ_launch_band(nullptr, L, b.d_w.as<double>(), b.d_E.as<double>(), (double)nk, ws));
+    DevBuf d_E, d_w, d_ws, d_U;
+    TBK_CHECK(d_E.reserve(e_bytes));
+    TBK_CHECK(d_w.reserve(e_bytes));
+    TBK_CHECK(d_ws.reserve(L.ws_bytes));
+    TBK_CHECK(d_U.reserve((size_t)chunk * u_per_k * sizeof(double)));
+    char* ws = d_ws.as<char>();
+    TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
+    TBK_CHECK(occ_launch_weights(nullptr, L, d_E.as<double>(), energy, (double)nk, d_w.as<double>()));
+    TBK_CHECK(occ_launch_band(nullptr, L, d_w.as<double>(), d_E.as<double>(), (double)nk, ws));
     TBK_CHECK(occ_clear_buf(nullptr, L, ws));
     for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
         const int64_t nkc = std::min(chunk, nk - c0);
-        TBK_HIP(hipMemcpy(b.d_U.ptr, U + (size_t)c0 * u_per_k, (size_t)nkc * u_per_k * sizeof(double), hipMemcpyHostToDevice));
-        TBK_CHECK(occ_launch_contract(nullptr, L, b.d_U.as<double>(), b.d_w.as<double>(), c0, nkc, (double)nk, ws));
+        TBK_HIP(hipMemcpy(d_U.ptr, U + (size_t)c0 * u_per_k, (size_t)nkc * u_per_k * sizeof(double), hipMemcpyHostToDevice));
+        TBK_CHECK(occ_launch_contract(nullptr, L, d_U.as<double>(), d_w.as<double>(), c0, nkc, (double)nk, ws));
     }
     TBK_CHECK(occ_launch_reduce(nullptr, L, ws));
     std::vector<double> host(5 * (size_t)n_orb);
@@ -672,12 +607,5 @@ extern "C" int tbk_occupations(tbk_model* m, const int32_t* mesh, int mode, doub
 
 extern "C" int tbk_occ_timing(tbk_model* m, double* ms, int64_t* calls, int reset) {
     TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr, "model / ms / calls is NULL");
-    TBK_LOCK(m);
-    for (int i = 0; i < 3; ++i) ms[i] = m->occ_ms[i];
-    *calls = m->occ_calls;
-    if (reset) {
-        for (int i = 0; i < 3; ++i) m->occ_ms[i] = 0.0;
-        m->occ_calls = 0;
-    }
-    return TBK_OK;
+    return tbk_timed_read(m, TIMED_OCC, 3, ms, calls, nullptr, reset);
 }

@@ -299,43 +299,29 @@ void pdos_launch_accumulate(hipStream_t s, const PdosLaunch& L, const double* d_
 // enqueue: (E, W) -> nos[G][n_e] on stream s (d_ws: L.ws_bytes).  denom = S * NK of the WHOLE mesh.  ev (or NULL): three events,
 // in front of the accumulate kernel, behind it, behind the scan
 int pdos_launch(hipStream_t s, int dim, const PdosLaunch& L, const double* d_E, const double* d_W, double e_min, double e_step, double denom,
-                void* d_ws, double* d_nos, hipEvent_t* ev) {
+                void* d_ws, double* d_nos, SpanRecorder& timer) {
     static_assert(TBK_PDOS_MAX_GROUPS == 16, "pdos_launch_accumulate instantiates group tiles up to 16");
     char* ws = static_cast<char*>(d_ws);
     auto* part_g = reinterpret_cast<unsigned long long*>(ws);
     auto* step_g = reinterpret_cast<unsigned long long*>(ws + L.off_step);
     auto* sums = reinterpret_cast<unsigned long long*>(ws + L.off_sums);
     const int64_t n_bins = (int64_t)L.n_groups * L.n_e;
-    if (ev) (void)hipEventRecord(ev[0], s);
+    timer.start(1);
     if (dim == 3)
         pdos_launch_accumulate<3>(s, L, d_E, d_W, e_min, e_step, part_g, step_g);
     else
         pdos_launch_accumulate<2>(s, L, d_E, d_W, e_min, e_step, part_g, step_g);
     TBK_HIP(hipGetLastError());
-    if (ev) (void)hipEventRecord(ev[1], s);
+    timer.stop();
+    timer.start(2);
     hipLaunchKernelGGL(pdos_reduce_kernel, dim3((unsigned)((n_bins + PDOS_THREADS - 1) / PDOS_THREADS)), dim3(PDOS_THREADS), 0, s, part_g, step_g,
                        L.n_wg, n_bins, sums);
     TBK_HIP(hipGetLastError());
     hipLaunchKernelGGL(pdos_scan_kernel, dim3((unsigned)L.n_groups), dim3(PDOS_THREADS), 0, s, sums, L.n_e, n_bins, denom, d_nos);
     TBK_HIP(hipGetLastError());
-    if (ev) (void)hipEventRecord(ev[2], s);
+    timer.stop();
     return TBK_OK;
 }
-
-struct EventSet {  // HIP events of one timed call, destroyed with it
-    std::vector<hipEvent_t> ev;
-    bool make(size_t count) {
-        for (size_t i = 0; i < count; ++i) {
-            hipEvent_t e = nullptr;
-            if (hipEventCreate(&e) != hipSuccess) return false;
-            ev.push_back(e);
-        }
-        return true;
-    }
-    ~EventSet() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-};
 
 }  // namespace
 
@@ -374,23 +360,17 @@ extern "C" int tbk_pdos_from_eigensystem(int device, int dim, const int32_t* mes
     const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double), w_bytes = e_bytes * (size_t)n_groups;
     const size_t nos_bytes = (size_t)n_groups * (size_t)n_e * sizeof(double);
     DevBuf d_E, d_W, d_ws, d_nos;
-    const int rc = [&]() -> int {
-        TBK_CHECK(d_E.reserve(e_bytes));
-        TBK_CHECK(d_W.reserve(w_bytes));
-        TBK_CHECK(d_ws.reserve(L.ws_bytes));
-        TBK_CHECK(d_nos.reserve(nos_bytes));
-        TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
-        TBK_HIP(hipMemcpy(d_W.ptr, W, w_bytes, hipMemcpyHostToDevice));
-        TBK_CHECK(pdos_launch(nullptr, dim, L, d_E.as<double>(), d_W.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk, d_ws.ptr,
-                              d_nos.as<double>(), nullptr));
-        TBK_HIP(hipMemcpy(nos_out, d_nos.ptr, nos_bytes, hipMemcpyDeviceToHost));
-        return TBK_OK;
-    }();
-    d_E.release();
-    d_W.release();
-    d_ws.release();
-    d_nos.release();
-    return rc;
+    TBK_CHECK(d_E.reserve(e_bytes));
+    TBK_CHECK(d_W.reserve(w_bytes));
+    TBK_CHECK(d_ws.reserve(L.ws_bytes));
+    TBK_CHECK(d_nos.reserve(nos_bytes));
+    TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
+    TBK_HIP(hipMemcpy(d_W.ptr, W, w_bytes, hipMemcpyHostToDevice));
+    SpanRecorder untimed;
+    TBK_CHECK(pdos_launch(nullptr, dim, L, d_E.as<double>(), d_W.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk, d_ws.ptr,
+                          d_nos.as<double>(), untimed));
+    TBK_HIP(hipMemcpy(nos_out, d_nos.ptr, nos_bytes, hipMemcpyDeviceToHost));
+    return TBK_OK;
 }
 
 // Cells [p_lo, p_lo + p_count) along axis 0 of the mesh on one handle: E and W of those planes and of the one periodic neighbour
@@ -431,51 +411,35 @@ int tbk_pdos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_cou
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : choose_chunk(m, nk, true)));
     TBK_CHECK(m->ws_pdos_u.reserve((size_t)chunk * n_orb * n_orb * 2 * sizeof(double)));
     const auto* d_off = m->ws_pdos_grp.as<int32_t>();
-    const auto* d_orb = reinterpret_cast<const int32_t*>(static_cast<const char*>(m->ws_pdos_grp.ptr) + off_bytes);
+    const auto* d_orb = reinterpret_cast<const int32_t*>(m->ws_pdos_grp.as<char>() + off_bytes);
     TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, h_k.data(), k_bytes, hipMemcpyHostToDevice, m->stream));
     TBK_HIP(hipMemcpyAsync(m->ws_pdos_grp.ptr, group_offsets, (size_t)(n_groups + 1) * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
     TBK_HIP(hipMemcpyAsync(m->ws_pdos_grp.as<char>() + off_bytes, group_orbitals, orb_bytes, hipMemcpyHostToDevice, m->stream));
 
     const int64_t n_chunks = (nk + chunk - 1) / chunk;
-    EventSet events;
-    const bool timed = m->timing && events.make(2 * (size_t)n_chunks + 3);
+    SpanRecorder timer(m->timing, m->stream);  // stages: 0 the weights kernel, 1 the accumulate kernel, 2 reduction + scan
     double* d_E = m->ws_out.as<double>();
     double* d_W = m->ws_pdos_w.as<double>();
     double* d_U = m->ws_pdos_u.as<double>();
     for (int64_t c = 0; c < n_chunks; ++c) {
         const int64_t c0 = c * chunk, nkc = std::min(chunk, nk - c0);
         TBK_CHECK(tbk_eigh_device(m, m->ws_k.as<double>() + c0 * dim, nkc, 2, nullptr, d_E + c0 * n_orb, d_U));
-        if (timed) (void)hipEventRecord(events.ev[2 * (size_t)c], m->stream);
+        timer.start(0);
         const int64_t threads = nkc * n_orb;
         hipLaunchKernelGGL(pdos_weights_kernel, dim3((unsigned)((threads + PDOS_THREADS - 1) / PDOS_THREADS)), dim3(PDOS_THREADS), 0, m->stream,
                            reinterpret_cast<const double2*>(d_U), n_orb, nkc, n_groups, d_off, d_orb, d_W + (size_t)c0 * n_groups * n_orb);
         TBK_HIP(hipGetLastError());
-        if (timed) (void)hipEventRecord(events.ev[2 * (size_t)c + 1], m->stream);
+        timer.stop();
     }
     TBK_CHECK(tbk_eigenval_check(m));  // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigh
 
-    double* d_nos = reinterpret_cast<double*>(static_cast<char*>(m->ws_dos.ptr) + L.ws_bytes);
-    TBK_CHECK(pdos_launch(m->stream, dim, L, d_E, d_W, e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk_total, m->ws_dos.ptr, d_nos,
-                          timed ? events.ev.data() + 2 * (size_t)n_chunks : nullptr));
+    double* d_nos = reinterpret_cast<double*>(m->ws_dos.as<char>() + L.ws_bytes);
+    TBK_CHECK(pdos_launch(m->stream, dim, L, d_E, d_W, e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk_total, m->ws_dos.ptr, d_nos, timer));
     TBK_HIP(hipMemcpyAsync(nos_out, d_nos, nos_bytes, hipMemcpyDeviceToHost, m->stream));
     TBK_HIP(hipStreamSynchronize(m->stream));
-    if (timed) {
-        double ms[3] = {0.0, 0.0, 0.0};
-        bool ok = true;
-        float t = 0.f;
-        for (int64_t c = 0; c < n_chunks && ok; ++c) {
-            ok = hipEventElapsedTime(&t, events.ev[2 * (size_t)c], events.ev[2 * (size_t)c + 1]) == hipSuccess;
-            ms[0] += (double)t;
-        }
-        for (int i = 0; i < 2 && ok; ++i) {
-            ok = hipEventElapsedTime(&t, events.ev[2 * (size_t)n_chunks + i], events.ev[2 * (size_t)n_chunks + i + 1]) == hipSuccess;
-            ms[1 + i] = (double)t;
-        }
-        if (ok) {
-            for (int i = 0; i < 3; ++i) m->pdos_ms[i] += ms[i];
-            m->pdos_calls += 1;
-        }
-    }
+    TimedSums& sums = m->timed[TIMED_PDOS];
+    timer.collect(sums.ms);
+    if (timer.on) sums.calls += 1;
     return TBK_OK;
 }
 
@@ -490,12 +454,5 @@ extern "C" int tbk_pdos(tbk_model* m, const int32_t* mesh, const int32_t* group_
 
 extern "C" int tbk_pdos_timing(tbk_model* m, double* ms, int64_t* calls, int reset) {
     TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr, "model / ms / calls is NULL");
-    TBK_LOCK(m);
-    for (int i = 0; i < 3; ++i) ms[i] = m->pdos_ms[i];
-    *calls = m->pdos_calls;
-    if (reset) {
-        for (int i = 0; i < 3; ++i) m->pdos_ms[i] = 0.0;
-        m->pdos_calls = 0;
-    }
-    return TBK_OK;
+    return tbk_timed_read(m, TIMED_PDOS, 3, ms, calls, nullptr, reset);
 }

@@ -50,11 +50,11 @@ int tbk_run_mfma_f64_peak(double* tflops) {
     TBK_HIP(hipGetDevice(&dev));
     TBK_HIP(hipGetDeviceProperties(&prop, dev));
     const int iters = 100000;  // ~20 ms per launch: long enough for the clock to settle
-    double* d_out = nullptr;
-    TBK_HIP(hipMalloc((void**)&d_out, (size_t)prop.multiProcessorCount * 4 * 256 * sizeof(double)));
-    hipEvent_t e0, e1;
-    TBK_HIP(hipEventCreate(&e0));
-    TBK_HIP(hipEventCreate(&e1));
+    DevPtr<double> d_out;
+    TBK_HIP(hipMalloc(d_out.put(), (size_t)prop.multiProcessorCount * 4 * 256 * sizeof(double)));
+    Event e0, e1;
+    TBK_HIP(hipEventCreate(e0.put()));
+    TBK_HIP(hipEventCreate(e1.put()));
     double best = 0.0;
     // waves per SIMD x {non-trivial operands, all-zero operands}: the chip clocks to its power budget, so
     // the sustained rate depends on both (MI355X_MICROARCH.md, DVFS give-back)
@@ -77,9 +77,6 @@ int tbk_run_mfma_f64_peak(double* tflops) {
             if (!zero && best_cfg > best) best = best_cfg;
         }
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(d_out);
     *tflops = best;
     return TBK_OK;
 }

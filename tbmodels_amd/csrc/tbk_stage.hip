@@ -114,7 +114,7 @@ int tbk_stage_strassen(tbk_model* m) {
     const size_t bytes = (size_t)7 * kh * m->ncol_pad * sizeof(double);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes > free_b / 4) return TBK_OK;
-    TBK_HIP(hipMalloc((void**)&m->d_Bs, bytes));
+    TBK_HIP(hipMalloc(m->d_Bs.put(), bytes));
     m->staged_bytes += (int64_t)bytes;
     dim3 grid((m->ncol_pad + 255) / 256, (unsigned)kh);
     hipLaunchKernelGGL(stage_strassen_kernel, grid, dim3(256), 0, m->stream, m->d_B, kh, m->ncol_pad, m->d_Bs);
@@ -134,7 +134,7 @@ int tbk_stage_strassen2(tbk_model* m) {
     const int64_t kq = m->k2 / 4;
     const int half = m->ncol_pad / 2;
     const size_t bytes = tbk_strassen2_bytes(m);
-    TBK_HIP(hipMalloc((void**)&m->d_Bs2, bytes));
+    TBK_HIP(hipMalloc(m->d_Bs2.put(), bytes));
     m->staged_bytes += (int64_t)bytes;
     const size_t blk1 = (size_t)2 * kq * m->ncol_pad, blk2 = (size_t)kq * half;  // doubles per block of Bs, of Bs2
     for (int p1 = 0; p1 < 7; ++p1) {
@@ -148,7 +148,7 @@ int tbk_stage_strassen2(tbk_model* m) {
 int tbk_stage_dense(tbk_model* m, const double* d_hop_raw) {
     const size_t bytes = (size_t)m->k2 * m->ncol_pad * 2 * sizeof(double);
     if (bytes == 0) return TBK_OK;
-    TBK_HIP(hipMalloc((void**)&m->d_B, bytes));
+    TBK_HIP(hipMalloc(m->d_B.put(), bytes));
     m->staged_bytes += (int64_t)bytes;
     TBK_HIP(hipMemsetAsync(m->d_B, 0, bytes, m->stream));
     if (m->n_r > 0) {
@@ -164,7 +164,7 @@ int tbk_stage_dense(tbk_model* m, const double* d_hop_raw) {
 int tbk_stage_kdotp(tbk_model* m, const double* d_coeff_raw) {
     const size_t bytes = (size_t)m->k2 * m->ncol_pad * 2 * sizeof(double);
     if (bytes == 0) return TBK_OK;
-    TBK_HIP(hipMalloc((void**)&m->d_B, bytes));
+    TBK_HIP(hipMalloc(m->d_B.put(), bytes));
     m->staged_bytes += (int64_t)bytes;
     TBK_HIP(hipMemsetAsync(m->d_B, 0, bytes, m->stream));
     if (m->n_r > 0) {

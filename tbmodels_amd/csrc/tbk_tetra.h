@@ -316,6 +316,12 @@ DosGeom tetra_geom(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0
 int tetra_partition(int64_t items, int threads, int64_t cap, const char* what, int64_t* items_per_wg, int* n_wg);
 // the k list of `planes` planes of axis 0 from plane p_lo on (periodic), in mesh order: k_d = i_d / n_d
 int tbk_dos_mesh_klist(int dim, const int32_t* mesh, int64_t p_lo, int64_t planes, std::vector<double>* h_k);
+// The eigenvalues of those planes on a staged handle, enqueued on its stream: the k list goes through ws_k, the eigenvalues stay in
+// ws_out (the eigenvalue path with the host list as the fold hint: dense models fold, CSR models take their own path).  below: the
+// periodic neighbour plane p_lo - 1 too, from a second call, in front of the others in h_k, ws_k and ws_out.  The caller has made
+// the handle's device current and reserved its family's workspaces (the eigenvalue call chooses its chunk from what is left), keeps
+// h_k until it has called tbk_eigenval_check, and calls that: callers with several handles enqueue all of them first.
+int tbk_mesh_eigenvalues(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t planes, bool below, std::vector<double>* h_k);
 
 // n0 rows (planes of axis 0, or k-points) on n handles: handle i takes the ceil(n0 / n) from lo(i) on, the last handles possibly none
 struct TetraSlabs {

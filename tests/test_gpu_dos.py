@@ -204,6 +204,35 @@ def test_two_handles_agree_with_one(silicon_model, mesh):
     assert err <= 1e-12 * model.size
 
 
+def _dos_timing(handle, reset=0):
+    ms, calls = ctypes.c_double(-1.0), ctypes.c_int64(-1)
+    _lib.check(_lib.lib().tbk_dos_timing(handle, ctypes.byref(ms), ctypes.byref(calls), reset))
+    return ms.value, calls.value
+
+
+def test_timing_getter_counts_the_timed_calls_only():
+    g = load_golden("silicon")
+    model = tbmodels_amd.Model.from_packed(g["R"], g["hop"], pos=g["pos"], uc=g["uc"])
+    grid = np.linspace(-8.0, 14.0, 257)
+    model.dos((4, 4, 4), grid)  # TBK_OPT_TIMING is off: neither time nor a call is booked
+    assert _dos_timing(model._staged()) == (0.0, 0)
+    model.set_option(_lib.TBK_OPT_TIMING, 1)
+    model.dos((4, 4, 4), grid)
+    model.dos((4, 4, 4), grid)
+    ms, calls = _dos_timing(model._staged(), reset=1)
+    print("two timed calls: %.3f ms of kernels" % ms)
+    assert calls == 2 and ms > 0.0
+    assert _dos_timing(model._staged()) == (0.0, 0)  # the read above reset the sums
+    twin = pickle.loads(pickle.dumps(model))
+    twin.devices = [0, 0]
+    twin.set_option(_lib.TBK_OPT_TIMING, 1)
+    twin.dos((4, 4, 4), grid)  # one slab per handle
+    assert len(twin._handles) == 2
+    for handle in twin._staged_all():
+        ms, calls = _dos_timing(handle)
+        assert calls == 1 and ms > 0.0
+
+
 # ---- 5. errors ------------------------------------------------------------------------------------------------------------------
 def test_argument_errors_need_no_device(silicon_model, monkeypatch):
     model, _ = silicon_model

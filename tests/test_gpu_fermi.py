@@ -308,6 +308,15 @@ def test_model_methods_against_the_model_of_the_same_mesh():
     print("gap cases met: %d" % gaps)
 
 
+def test_untimed_calls_are_counted_without_time():
+    g = load_golden("silicon")
+    model = tbmodels_amd.Model.from_packed(g["R"], g["hop"], pos=g["pos"], uc=g["uc"])
+    model.fermi_level((4, 4, 4), 4.5)  # TBK_OPT_TIMING is off
+    ms, calls, passes = ctypes.c_double(-1.0), ctypes.c_int64(-1), ctypes.c_int64(-1)
+    _lib.check(_lib.lib().tbk_fermi_timing(model._staged(), ctypes.byref(ms), ctypes.byref(calls), ctypes.byref(passes), 0))
+    assert calls.value == 1 and passes.value >= 1 and ms.value == 0.0
+
+
 # ---- 10. arguments --------------------------------------------------------------------------------------------------------------------------------------
 def test_python_argument_errors_need_no_device(monkeypatch):
     g = load_golden("silicon")

@@ -243,6 +243,15 @@ def test_model_methods_against_the_model_of_the_same_mesh():
     assert gaps == 1  # silicon at n = 4
 
 
+def test_untimed_calls_are_counted_without_time():
+    g = load_golden("silicon")
+    model = tbmodels_amd.Model.from_packed(g["R"], g["hop"], pos=g["pos"], uc=g["uc"])
+    model.occupations((4, 4, 4), n_electrons=4.5)  # TBK_OPT_TIMING is off
+    ms, calls = (ctypes.c_double * 3)(-1.0, -1.0, -1.0), ctypes.c_int64(-1)
+    _lib.check(_lib.lib().tbk_occ_timing(model._staged(), ms, ctypes.byref(calls), 0))
+    assert calls.value == 1 and list(ms) == [0.0, 0.0, 0.0]
+
+
 # ---- 4. arguments -----------------------------------------------------------------------------------------------------------------------------
 def test_python_argument_errors_need_no_device(monkeypatch):
     g = load_golden("silicon")

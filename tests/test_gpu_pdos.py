@@ -241,6 +241,35 @@ def test_two_handles_agree_with_one(silicon_model, mesh):
     assert err <= 1e-12 * silicon_model.size
 
 
+def _pdos_timing(handle, reset=0):
+    ms, calls = (ctypes.c_double * 3)(-1.0, -1.0, -1.0), ctypes.c_int64(-1)
+    _lib.check(_lib.lib().tbk_pdos_timing(handle, ms, ctypes.byref(calls), reset))
+    return list(ms), calls.value
+
+
+def test_timing_getter_counts_the_timed_calls_only():
+    g = load_golden("silicon")
+    model = tbmodels_amd.Model.from_packed(g["R"], g["hop"], pos=g["pos"], uc=g["uc"])
+    grid, groups = np.linspace(-8.0, 14.0, 257), [[0, 4], [3, 1, 2], [5, 6, 7]]
+    model.pdos((4, 4, 4), grid, groups)  # TBK_OPT_TIMING is off: neither time nor a call is booked
+    assert _pdos_timing(model._staged()) == ([0.0, 0.0, 0.0], 0)
+    model.set_option(_lib.TBK_OPT_TIMING, 1)
+    model.pdos((4, 4, 4), grid, groups)
+    model.pdos((4, 4, 4), grid, groups)
+    ms, calls = _pdos_timing(model._staged(), reset=1)
+    print("two timed calls: %.3f / %.3f / %.3f ms of kernels" % tuple(ms))
+    assert calls == 2 and min(ms) > 0.0
+    assert _pdos_timing(model._staged()) == ([0.0, 0.0, 0.0], 0)  # the read above reset the sums
+    twin = pickle.loads(pickle.dumps(model))
+    twin.devices = [0, 0]
+    twin.set_option(_lib.TBK_OPT_TIMING, 1)
+    twin.pdos((4, 4, 4), grid, groups)  # one slab per handle
+    assert len(twin._handles) == 2
+    for handle in twin._staged_all():
+        ms, calls = _pdos_timing(handle)
+        assert calls == 1 and min(ms) > 0.0
+
+
 # ---- 7. errors ---------------------------------------------------------------------------------------------------------------------
 def test_argument_errors_need_no_device(silicon_model, monkeypatch):
     grid = np.linspace(-1.0, 1.0, 11)
