@@ -94,6 +94,28 @@ def main():
               % (dt * 1e3, occ.mu.mu, " ".join("%.4f" % x for x in occ.orbital_occ), occ.orbital_occ.sum()))
         print("  band occupations %s, band energy %.6f per cell" % (" ".join("%g" % x for x in occ.band_occ), occ.band_energy.sum()))
 
+        # 6. the density matrix of those four bands at the model's own hopping vectors: the bond order between the first orbitals
+        # of the two atoms across the nearest-neighbour bond, and the band energy again, now as a sum over bonds --
+        # 2 Re sum_R sum_ij conj(rho(R)_ij) hop[R]_ij for the stored half of the hoppings; NR x 8 x 8 complex numbers come back
+        model.density_matrix((n, n, n), n_electrons=4)  # warm up
+        t0 = time.perf_counter()
+        dm = model.density_matrix((n, n, n), n_electrons=4)
+        dt = time.perf_counter() - t0
+        _, hop = model.packed_hop()
+        bonds = 2.0 * np.real(np.conj(dm.rho) * hop).sum(axis=(1, 2))
+        # rho(R)[i][j] joins orbital i of the home cell and orbital j of cell R; the stored half holds R or -R, and
+        # rho(-R) = rho(R)^H.  The nearest image of orbital 4 as seen from orbital 0, by the Cartesian length of pos[4] + R - pos[0]:
+        pos = np.asarray(model.pos, dtype=float)
+        cell = np.eye(model.dim) if model.uc is None else np.asarray(model.uc, dtype=float)
+        signed = np.concatenate([dm.R, -dm.R])
+        nearest = int(np.argmin(np.linalg.norm((pos[4] + signed - pos[0]) @ cell, axis=1)))
+        index, flipped = nearest % len(dm.R), nearest >= len(dm.R)
+        order = np.conj(dm.rho[index][4, 0]) if flipped else dm.rho[index][0, 4]
+        print("density matrix at %d lattice vectors in %.1f ms: nearest-neighbour bond order between orbitals 0 and 4 %.4f at R = %s"
+              % (len(dm.R), dt * 1e3, order.real, tuple(int(x) for x in signed[nearest])))
+        print("  band energy from the bonds %.6f per cell (occupations: %.6f), largest single vector %.6f"
+              % (bonds.sum(), occ.band_energy.sum(), bonds[np.argmax(np.abs(bonds))]))
+
 
 if __name__ == "__main__":
     main()

@@ -368,6 +368,45 @@ int tbk_occupations_multi(tbk_model* const* handles, int n_handles, const int32_
  * made while TBK_OPT_TIMING was on; calls = how many calls; reset = 1 clears.  (The eigensolver stages are in tbk_get_timing.) */
 int tbk_occ_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
+/* ---- the real-space density matrix of a uniform k mesh (not in the reference) --------------------------------------------------
+ * Mesh, simplices, the weights w[k][b] at mu and the eigenvectors U[k][i][b] (convention 2) are those of tbk_occupations
+ * (csrc/tbk_dm.hip).  With the mesh points k = (i_1 / n_1, ..., i_dim / n_dim):
+ *     P(k)[i][j]   = sum_b w[k][b] U[k][i][b] conj(U[k][j][b])                         Hermitian, trace = sum_b w[k][b]
+ *     rho(R)[i][j] = sum_k exp(-2 pi i sum_d ((i_d R_d) mod n_d) / n_d) P(k)[i][j]     for every requested integer vector R
+ * The argument of the phase is reduced in integers: every (i_d R_d) mod n_d is taken in 64-bit arithmetic with a non-negative
+ * result, the numerators are brought to the common denominator NK = prod n_d and reduced modulo NK, and cos / sin are taken of
+ * that fraction; rho(R + n_d e_d) has the bits of rho(R).  rho(-R) = rho(R)^H, diag rho(0) = the q of tbk_occupations, tr rho(0) =
+ * N(mu); with the stored half of the hoppings sum_b eb[b] = 2 Re sum_R sum_ij conj(rho(R)[i][j]) hop[R][i][j].  Every element is
+ * a sum of NK n_orb terms whose moduli add up to at most 1: |error| <= 4 (NK n_orb + 32) 2^-53.  Repeated calls with the same
+ * arguments, chunk size and handles give the same bits; another chunk size regroups the sums (inside the bound).  The split of a
+ * degenerate cluster's weight over its bands depends on the basis the eigensolver returns (the caveat of tbk_occupations); rho of a
+ * cluster filled as a whole does not.
+ * R: int64 [n_r][dim], duplicates allowed; rho_out: double [n_r][n_orb][n_orb][2].  Argument errors (TBK_ERR_ARGUMENT), before any
+ * device is touched: those of tbk_occupations, n_r < 1 or above 1048560, more than 16320 orbitals, a NULL pointer.  rho, its partial
+ * sums (at most 256 MiB beyond rho itself) and the buffers of one k chunk must fit (TBK_ERR_MEMORY otherwise).  Host buffers;
+ * synchronous. */
+
+/* The kernels alone on an eigensystem the caller brings (E, U, k_chunk as for tbk_occupations_from_eigensystem). */
+int tbk_density_matrix_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double energy,
+                                        int64_t k_chunk, int64_t n_r, const int64_t* R, double* rho_out);
+/* The whole call: eigenvalues, mu (mode, value, mu_out as for tbk_occupations: mode 1 gives tbk_fermi's numbers bit for bit) and the
+ * weights as in tbk_occupations; then the k list is walked in chunks of at most TBK_OPT_K_CHUNK points (0: half of what
+ * tbk_eigh_device would choose, the projectors of a chunk take the other half), per chunk tbk_eigh_device, the chunk's phase table,
+ * its projectors and their contraction into the resident rho. */
+int tbk_density_matrix(tbk_model* m, const int32_t* mesh, int mode, double value, int64_t n_r, const int64_t* R, double* mu_out,
+                       double* rho_out);
+/* On several devices from one process: the slabs of tbk_dos_multi.  Every handle contracts the mesh points of its own planes, the host
+ * adds the handles' partial rho in handle order.  The handles must be distinct. */
+int tbk_density_matrix_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, int64_t n_r,
+                             const int64_t* R, double* mu_out, double* rho_out);
+/* How the contraction over k of a slab of `rows` mesh points is cut: out[0] = n_r rounded up to the tile of 16, out[1] = the k slices
+ * (one partial rho each, added in index order; 1: none), out[2] = mesh points per slice.  A function of its arguments alone. */
+int tbk_dm_plan(int64_t rows, int n_orb, int64_t n_r, int64_t* out);
+/* ms[3] = the summed HIP-event time of the phase tables, the projectors, and the contraction + the sum of its slices in this handle's
+ * calls made while TBK_OPT_TIMING was on; calls = how many calls; reset = 1 clears.  (The eigensolver stages are in tbk_get_timing; the
+ * weights kernel, a stage of tbk_occ_timing, is not timed in these calls.) */
+int tbk_dm_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
 /* ---- k.p models (kdotp.py:51-100): H(k) = sum_p prod_d k_d^powers[p][d] * coeffs[p] ------- */
 int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, const int32_t* powers,
                      const double* coeffs, tbk_kdotp** out);

@@ -93,6 +93,11 @@ SIGNATURES = {
     "tbk_tetra_weights_multi": (_c_int, [_vp, _c_int, _vp, ctypes.c_double, _vp]),
     "tbk_occupations_multi": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, _vp, _vp, _vp, _vp]),
     "tbk_occ_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
+    "tbk_density_matrix_from_eigensystem": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, _vp, ctypes.c_double, _c_i64, _c_i64, _vp, _vp]),
+    "tbk_density_matrix": (_c_int, [_vp, _vp, _c_int, ctypes.c_double, _c_i64, _vp, _vp, _vp]),
+    "tbk_density_matrix_multi": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, _c_i64, _vp, _vp, _vp]),
+    "tbk_dm_plan": (_c_int, [_c_i64, _c_int, _c_i64, ctypes.POINTER(_c_i64)]),
+    "tbk_dm_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
     "tbk_kdotp_create": (_c_int, [_c_int, _c_int, _c_int, _c_i64, _vp, _vp, _pp]),
     "tbk_kdotp_destroy": (None, [_vp]),
     "tbk_kdotp_hamilton": (_c_int, [_vp, _vp, _c_i64, _vp]),

@@ -43,6 +43,7 @@ BandEdges = co.namedtuple("BandEdges", ("emin", "emax"))
 #: what ``Model.fermi_level`` returns: floats; ``lower < upper`` exactly when the mesh has a gap at the filling asked for
 FermiLevel = co.namedtuple("FermiLevel", ("mu", "lower", "upper", "nos"))
 Occupations = co.namedtuple("Occupations", ("mu", "orbital_occ", "band_occ", "band_energy"))
+DensityMatrix = co.namedtuple("DensityMatrix", ("mu", "R", "rho"))
 
 
 def _devices_from_env():
@@ -784,7 +785,7 @@ class Model:
         return (eig[0], vec[0]) if single else (eig, vec)
 
     def _mesh_argument(self, mesh, what="dos"):
-        """The mesh check ``dos``, ``pdos``, ``band_edges``, ``fermi_level``, ``tetra_weights`` and ``occupations`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
+        """The mesh check ``dos``, ``pdos``, ``band_edges``, ``fermi_level``, ``tetra_weights``, ``occupations`` and ``density_matrix`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
         if self.dim not in (2, 3):
             raise ValueError("{} needs a 2- or 3-dimensional model, this one has dimension {}".format(what, self.dim))
         try:
@@ -1006,16 +1007,7 @@ class Model:
         first axis.
         """
         mesh_array = self._mesh_argument(mesh, "occupations")
-        if (energy is None) == (n_electrons is None):
-            raise ValueError("occupations takes exactly one of energy and n_electrons")
-        if energy is not None:
-            mode, value = 0, self._energy_argument(energy)
-        else:
-            if isinstance(n_electrons, (bool, np.bool_)) or not isinstance(n_electrons, (int, float, np.integer, np.floating)):
-                raise ValueError("n_electrons must be a real number, got {!r}".format(n_electrons))
-            mode, value = 1, float(n_electrons)
-            if not np.isfinite(value) or not 0.0 < value < self.size:
-                raise ValueError("n_electrons must lie inside (0, {}), got {!r}".format(self.size, n_electrons))
+        mode, value = self._occupation_argument("occupations", energy, n_electrons)
         mu = np.empty(4, dtype=np.float64)
         orbital, band, energy_out = (np.empty(self.size, dtype=np.float64) for _ in range(3))
         with self._call_lock:
@@ -1026,6 +1018,86 @@ class Model:
                                                  _lib.ptr(band), _lib.ptr(energy_out))
             )
         return Occupations(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), orbital, band, energy_out)
+
+    def _occupation_argument(self, what, energy, n_electrons):
+        """``(mode, value)`` of the C calls from exactly one of ``energy`` and ``n_electrons``, or ``ValueError``."""
+        if (energy is None) == (n_electrons is None):
+            raise ValueError("{} takes exactly one of energy and n_electrons".format(what))
+        if energy is not None:
+            return 0, self._energy_argument(energy)
+        if isinstance(n_electrons, (bool, np.bool_)) or not isinstance(n_electrons, (int, float, np.integer, np.floating)):
+            raise ValueError("n_electrons must be a real number, got {!r}".format(n_electrons))
+        value = float(n_electrons)
+        if not np.isfinite(value) or not 0.0 < value < self.size:
+            raise ValueError("n_electrons must lie inside (0, {}), got {!r}".format(self.size, n_electrons))
+        return 1, value
+
+    def _lattice_vectors_argument(self, R):
+        """``R int64 (NR, dim)`` from an integer array-like of that shape, one vector, or ``None`` (the stored hopping vectors)."""
+        if R is None:
+            keys = [key for key, _ in self._hop_items()]
+            if not keys:
+                raise ValueError("the model has no hoppings: give R")
+            return np.ascontiguousarray(np.array(keys, dtype=np.int64).reshape(len(keys), self.dim))
+        try:
+            array = np.asarray(R)
+        except (TypeError, ValueError):
+            raise ValueError("R must be an integer array of shape (NR, {})".format(self.dim)) from None
+        if array.dtype.kind not in "iu" or array.dtype == np.uint64:
+            raise ValueError("R must hold (64-bit signed) integers, got dtype {}".format(array.dtype))
+        if array.ndim == 1:
+            array = array.reshape(1, -1)
+        if array.ndim != 2 or array.shape[1] != self.dim or array.shape[0] < 1:
+            raise ValueError("R must have shape (NR, {}) with NR >= 1, got {}".format(self.dim, array.shape))
+        return np.ascontiguousarray(array, dtype=np.int64)
+
+    def density_matrix(self, mesh, *, energy=None, n_electrons=None, R=None):
+        """
+        The real-space one-particle density matrix ``rho(R)`` of a uniform k mesh by the linear tetrahedron method, computed on the
+        GPU from eigenvalues, eigenvectors and integration weights that never leave it.  Not in the reference.
+
+        ``mesh``, ``energy`` and ``n_electrons`` are those of :meth:`occupations`: exactly one of the last two is given, else
+        ``ValueError``.  ``R`` is an integer array-like of shape ``(NR, dim)`` or one vector; duplicates are allowed; ``None`` means
+        the model's stored hopping vectors in the order of ``self.hop``.  Returns the named tuple ``(mu, R, rho)``: ``mu`` is the
+        :class:`FermiLevel` tuple of :meth:`occupations`, ``R`` the vectors as ``int64 (NR, dim)`` and ``rho`` is
+        ``complex128 (NR, size, size)``.
+
+        Definition.  With ``w`` of :meth:`tetra_weights` at ``mu.mu``, ``U`` the eigenvectors of ``eigh(k, convention=2)`` and the
+        mesh points ``k = (i_1 / n_1, ..., i_dim / n_dim)``::
+
+            P(k)[i, j]   = sum_b w[k, b] U[k, i, b] conj(U[k, j, b])
+            rho(R)[i, j] = sum_k exp(-2 pi i k . R) P(k)[i, j]
+
+        The sign is that of the inverse of ``hamilton``: H(k) sums ``exp(+2 pi i k . R) hop[R]``.  ``k . R`` is reduced in integers
+        before any floating-point operation (every ``(i_d R_d) mod n_d``, then the common denominator ``NK``), so
+        ``rho(R + n_d e_d)`` has the bits of ``rho(R)``: the mesh cannot tell them apart.  No spin factor.
+
+        Properties.  (1) ``rho(-R) = rho(R)^H``; ``rho(0)`` is Hermitian, its diagonal is ``orbital_occ`` of :meth:`occupations`
+        and its trace ``mu.nos``.  (2) Over the dual cell of the mesh, ``sum_{R in [0, n_1) x ... x [0, n_dim)} exp(+2 pi i k' . R)
+        rho(R) = NK P(k')`` at every mesh point ``k'``.  (3) With the stored half of the hoppings (``R=None``), ``2 Re sum_R sum_ij
+        conj(rho(R)[i, j]) hop[R][i, j]`` is the band energy per cell, ``occupations(...).band_energy.sum()``.  (4) Above the
+        spectrum ``rho(R)`` is the identity for ``R = 0`` modulo the mesh and 0 otherwise; below the spectrum it is exactly 0.
+        Every element is a sum of ``NK size`` terms whose moduli add up to at most 1: the rounding error is at most
+        ``4 (NK size + 32) 2^-53``.  Repeated calls give the same bits.
+
+        Inside a degenerate eigenspace the split of a state's weight over the bands depends on the basis, which is unspecified (see
+        :meth:`eigh`); ``rho`` of a cluster that is filled as a whole (an insulator's valence bands) does not.  One-dimensional
+        models raise ``ValueError``.  With several ``devices`` every device contracts a slab of the mesh along its first axis and
+        the host adds the slabs.
+        """
+        mesh_array = self._mesh_argument(mesh, "density_matrix")
+        mode, value = self._occupation_argument("density_matrix", energy, n_electrons)
+        vectors = self._lattice_vectors_argument(R)
+        mu = np.empty(4, dtype=np.float64)
+        rho = np.empty((vectors.shape[0], self.size, self.size), dtype=np.complex128)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_density_matrix_multi(handles, n_handles, _lib.ptr(mesh_array), mode, value, vectors.shape[0],
+                                                    _lib.ptr(vectors), _lib.ptr(mu), _lib.ptr(rho))
+            )
+        return DensityMatrix(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, rho)
 
     def construct_kdotp(self, k, order):
         """

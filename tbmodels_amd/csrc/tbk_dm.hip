@@ -1,0 +1,504 @@
+// tbk_dm.hip -- the real-space one-particle density matrix of a uniform, periodic k mesh at one chemical potential.  Not in the
+// reference; DESIGN.md section 14 has the quantity, the kernels and the measurements, tools/dm_model.py is the statement the tests
+// compare with.
+//
+//   P(k)[i][j]  = sum_b w[k][b] U[k][i][b] conj(U[k][j][b])              w of tbk_occ.hip at mu, U of tbk_eigh_device (convention 2)
+//   rho(R)[i][j] = sum_k exp(-2 pi i  num(k, R) / NK) P(k)[i][j]         num = sum_d ((i_d R_d) mod n_d) (NK / n_d)  mod NK
+//
+// The phase.  Mesh point k = (i_1 / n_1, ..., i_dim / n_dim).  The host reduces every R_d to [0, n_d) first (so the 64-bit product
+// below cannot overflow; (i_d R_d) mod n_d does not change), the kernel forms t_d = (i_d (R_d mod n_d)) mod n_d in 64-bit integers,
+// brings the numerators to the common denominator NK = prod n_d < 2^31, num = (sum_d t_d NK / n_d) mod NK, and takes
+// sincospi(2 num / NK): one division of two exact integers, nothing else in floating point.  R and R + n_d e_d give the same bits.
+//
+// Three kernels per chunk of k-points (the eigenvectors come one chunk at a time), all in TABLE coordinates: the chunk holds the
+// slab's points [c0, c0 + nkc); table column j is slab point 4 (c0 / 4) + j, so groups of four columns -- one MFMA's K -- start at
+// multiples of four of the SLAB index whatever the chunk, up to three leading and three trailing columns are padding (phase 0,
+// P 0), and the fixed k slices of the Fourier kernel (multiples of four points) never cut a group.
+//
+//   dm_phase_kernel    tab[R tile][group][cos | sin][64]: the A operand of the Fourier product in the order its lanes load it --
+//                      lane (q, r) of a group holds R row 16 tile + r at column 4 group + q.  VALU work, once per chunk.
+//   dm_project_kernel  P = (U diag w) U^H as two real products on v_mfma_f64_16x16x4_f64, contraction over the bands:
+//                      Pr = wUr Ur^T + wUi Ui^T, Pi = wUi Ur^T - wUr Ui^T (the minus is the instruction's negate-A bit).  A workgroup
+//                      owns a 64 x 64 block of one P(k) (16 x 16 of four k-points up to 16 orbitals): panels of 16 bands of the
+//                      block's rows of U go through LDS once, band-major planes wUr, wUi (rows of the block) and Ur, Ui (its
+//                      columns), padded with zeros to the tile, so an operand is one ds_read_b64 per lane.  Every tile is computed
+//                      (no mirroring).  Padding columns of the table get P = 0.
+//   dm_fourier_kernel  rho_r += c Pr + s Pi, rho_i += c Pi - s Pr: one wave per output tile of 16 R-vectors x 16 complex elements of
+//                      the n^2, two accumulators, four MFMAs per group of four k-points, operands straight from global memory
+//                      (tab: 512 contiguous bytes per load; P: four 256-byte row segments as double2), sixteen MFMAs per pointer bump.
+//                      The accumulators start from and return to part[slice][R][n^2], which lives across the chunks of a call:
+//                      every element has one owner per launch, no atomics.  Few tiles (8 orbitals: 4 column tiles per 16 R): the
+//                      slab's points are cut into `slices` ranges of kps points -- a function of the slab index, not of the chunk,
+//                      as in occ_contract_kernel -- one partial rho each, and dm_reduce_kernel adds them in index order.
+//
+// For given (w, U), R, chunk size and slab the bits of rho depend on nothing else.  Another chunk size regroups the k-points of the
+// groups at the chunk boundaries: results differ within the rounding bound of DESIGN 14.
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "tbk_occ.h"
+
+namespace {
+
+typedef double dm_d4 __attribute__((ext_vector_type(4)));
+
+constexpr int DM_THREADS = 256;
+constexpr int64_t DM_TARGET_WAVES = 1024;             // Fourier tiles x slices the plan aims for (four waves on each of 256 CUs)
+constexpr int64_t DM_MIN_SLICE = 16;                  // mesh points per slice, at least
+constexpr size_t DM_PART_BUDGET = size_t(256) << 20;  // the partials of all slices together; fewer slices beyond it
+constexpr size_t DM_TAB_BUDGET = size_t(256) << 20;   // the phase table of one chunk; a shorter chunk beyond it
+constexpr int64_t DM_MAX_R = int64_t(65535) * 16;     // one grid row per 16 R-vectors
+
+struct DmMesh {
+    int dim;
+    int n[3];       // (n[2] = 1 in two dimensions)
+    int64_t nk;     // points of the whole mesh
+    int64_t first;  // mesh index of the slab's first own point
+};
+
+struct DmPlan {
+    DmMesh mesh;
+    int n = 0;                       // orbitals
+    int64_t n2 = 0, nct = 0;         // elements of one matrix, column tiles of 16 of them
+    int64_t n_r = 0, nr_pad = 0;     // R-vectors, rounded up to the tile
+    int64_t rows = 0;                // own mesh points of the slab
+    int64_t slices = 1, kps = 4;     // k slices of the Fourier kernel, mesh points per slice (a multiple of 4)
+    size_t part_bytes() const { return (size_t)slices * nr_pad * n2 * sizeof(double2); }
+    size_t rho_bytes() const { return (size_t)n_r * n2 * sizeof(double2); }
+    int64_t groups(int64_t chunk) const { return chunk / 4 + 2; }  // table groups of a chunk, at most
+    size_t tab_bytes(int64_t chunk) const { return (size_t)nr_pad * groups(chunk) * 4 * 2 * sizeof(double); }
+    size_t p_bytes(int64_t chunk) const { return (size_t)groups(chunk) * 4 * n2 * sizeof(double2); }
+};
+
+// the slices: enough of them to fill the device with tiles, none shorter than DM_MIN_SLICE points, all partials inside the budget
+void dm_plan_slices(int64_t rows, int n_orb, int64_t n_r, int64_t* nr_pad, int64_t* slices, int64_t* kps) {
+    const int64_t n2 = (int64_t)n_orb * n_orb;
+    *nr_pad = (n_r + 15) / 16 * 16;
+    const int64_t tiles = *nr_pad / 16 * ((n2 + 15) / 16);
+    const int64_t by_work = (DM_TARGET_WAVES + tiles - 1) / tiles;
+    const int64_t by_rows = rows / DM_MIN_SLICE;
+    const int64_t by_memory = (int64_t)(DM_PART_BUDGET / ((size_t)*nr_pad * n2 * sizeof(double2)));
+    const int64_t want = std::max<int64_t>(1, std::min(by_work, std::min(by_rows, by_memory)));
+    *kps = ((rows + want - 1) / want + 3) / 4 * 4;
+    *slices = std::max<int64_t>(1, (rows + *kps - 1) / *kps);
+}
+
+__global__ void __launch_bounds__(DM_THREADS) dm_phase_kernel(const int32_t* __restrict__ Rm, DmMesh g, int64_t n_r, int64_t nr_pad, int64_t c0,
+                                                              int64_t nkc, int64_t ng, double* __restrict__ tab) {
+    const int64_t t = (int64_t)blockIdx.x * DM_THREADS + threadIdx.x;
+    if (t >= nr_pad / 16 * ng * 64) return;
+    const int lane = (int)(t & 63);
+    const int64_t gg = (t >> 6) % ng, rt = (t >> 6) / ng;
+    const int64_t r = rt * 16 + (lane & 15);
+    const int64_t k = ((c0 >> 2) + gg) * 4 + (lane >> 4);  // in the slab
+    double c = 0.0, s = 0.0;
+    if (r < n_r && k >= c0 && k < c0 + nkc) {
+        int64_t pt = g.first + k, num = 0;
+#pragma unroll
+        for (int d = 2; d >= 0; --d) {  // (unrolled: the axes are named, the mesh stays in the kernel arguments)
+            if (d >= g.dim) continue;
+            const int64_t nd = g.n[d];
+            const int64_t id = pt % nd;
+            pt /= nd;
+            const int64_t td = (id * (int64_t)Rm[r * g.dim + d]) % nd;  // both factors in [0, n_d)
+            num += td * (g.nk / nd);
+        }
+        num %= g.nk;
+        sincospi((double)(2 * num) / (double)g.nk, &s, &c);
+    }
+    tab[((rt * ng + gg) * 2 + 0) * 64 + lane] = c;
+    tab[((rt * ng + gg) * 2 + 1) * 64 + lane] = s;
+}
+
+// BT tiles of 16 along each side of the workgroup's block of P: 4 (one k-point per workgroup, wave t owns tile row t) or 1 (n <= 16:
+// four k-points per workgroup, one per wave).  U, w: of the chunk.  Table column j is chunk point j - pad.
+template <int BT>
+__global__ void __launch_bounds__(DM_THREADS) dm_project_kernel(const double2* __restrict__ U, const double* __restrict__ w, int n, int64_t pad,
+                                                                int64_t nkc, double2* __restrict__ P) {
+    constexpr int RB = 16 * BT;                   // rows (and columns) of the block
+    constexpr int KPW = BT == 1 ? 4 : 1;          // k-points per workgroup
+    constexpr int TEAM = DM_THREADS / KPW;        // threads that stage one k-point's panel
+    constexpr int S = BT == 1 ? 18 : 82;          // doubles between the band rows of a plane: the 16 bands a wave stores at once land
+                                                  // in 16 different bank pairs, the four a wave reads at once (nearly) so
+    __shared__ double planes[KPW][4][16][S];      // wUr, wUi of the block's rows; Ur, Ui of its columns
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int team = BT == 1 ? wave : 0, tt = tid - team * TEAM;
+    const int nb = (n + RB - 1) / RB;
+    const int bi = (int)blockIdx.y / nb, bj = (int)blockIdx.y - bi * nb;
+    const int64_t j = (int64_t)blockIdx.x * KPW + team;  // table column
+    const int64_t k = j - pad;
+    const bool valid = k >= 0 && k < nkc;
+    const double2* Uk = U + (valid ? (size_t)k * n * n : 0);
+    const double* wk = w + (valid ? (size_t)k * n : 0);
+    double(*pl)[16][S] = planes[team];
+    const int ti = BT == 1 ? 0 : wave;  // the wave's tile row
+    const bool row_live = bi * RB + ti * 16 < n;  // (wave-uniform)
+    dm_d4 accr[BT], acci[BT];
+#pragma unroll
+    for (int tj = 0; tj < BT; ++tj) accr[tj] = acci[tj] = dm_d4{0.0, 0.0, 0.0, 0.0};
+    const int sb = tt & 15, srow0 = tt >> 4;
+    for (int b0 = 0; b0 < n; b0 += 16) {
+        __syncthreads();  // the previous panel has been read
+        const int b = b0 + sb;
+        const bool b_in = valid && b < n;
+        const double wv = b_in ? wk[b] : 0.0;
+        for (int row = srow0; row < RB; row += TEAM / 16) {
+            const int gi = bi * RB + row, gj = bj * RB + row;
+            double2 ui = make_double2(0.0, 0.0), uj = ui;
+            if (b_in && gi < n) ui = Uk[(size_t)gi * n + b];
+            if (bi == bj)
+                uj = ui;
+            else if (b_in && gj < n)
+                uj = Uk[(size_t)gj * n + b];
+            pl[0][sb][row] = wv * ui.x;
+            pl[1][sb][row] = wv * ui.y;
+            pl[2][sb][row] = uj.x;
+            pl[3][sb][row] = uj.y;
+        }
+        __syncthreads();
+        if (row_live) {
+#pragma unroll 1
+            for (int q = 0; q < 4; ++q) {  // (not unrolled: with the operands of all four steps at once the kernel takes 344 registers, 96 of them accumulation registers)
+                const int bq = 4 * q + (lane >> 4);
+                const double ar = pl[0][bq][ti * 16 + (lane & 15)], ai = pl[1][bq][ti * 16 + (lane & 15)];
+#pragma unroll
+                for (int tj = 0; tj < BT; ++tj) {
+                    if (bj * RB + tj * 16 < n) {  // (uniform)
+                        const double br = pl[2][bq][tj * 16 + (lane & 15)], bim = pl[3][bq][tj * 16 + (lane & 15)];
+                        accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, accr[tj], 0, 0, 0);
+                        accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, bim, accr[tj], 0, 0, 0);
+                        acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, acci[tj], 0, 0, 0);
+                        acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bim, acci[tj], 0, 0, 1);  // - wUr Ui^T
+                    }
+                }
+            }
+        }
+    }
+    if (!row_live) return;
+    // lane (q, c), register r: row q + 4 r, column c of the tile
+    double2* Pj = P + (size_t)j * n * n;
+#pragma unroll
+    for (int tj = 0; tj < BT; ++tj) {
+        const int gj = bj * RB + tj * 16 + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int gi = bi * RB + ti * 16 + (lane >> 4) + 4 * r;
+            if (gi < n && gj < n) Pj[(size_t)gi * n + gj] = make_double2(accr[tj][r], acci[tj][r]);
+        }
+    }
+}
+
+__device__ __forceinline__ void dm_fourier_step(double c, double s, double2 p, dm_d4& ar, dm_d4& ai) {
+    ar = __builtin_amdgcn_mfma_f64_16x16x4f64(c, p.x, ar, 0, 0, 0);
+    ar = __builtin_amdgcn_mfma_f64_16x16x4f64(s, p.y, ar, 0, 0, 0);
+    ai = __builtin_amdgcn_mfma_f64_16x16x4f64(c, p.y, ai, 0, 0, 0);
+    ai = __builtin_amdgcn_mfma_f64_16x16x4f64(s, p.x, ai, 0, 0, 1);  // - s Pr
+}
+
+// grid: (column tiles / 4, R tiles, slices the chunk touches from slice_lo on); a wave owns one tile of one slice.  The chunk's table
+// holds the absolute groups [g0, g_end) of the slab, slice s owns [s gps, (s + 1) gps).
+__global__ void __launch_bounds__(DM_THREADS) dm_fourier_kernel(const double* __restrict__ tab, const double2* __restrict__ P, int64_t n2, int64_t nct,
+                                                                int64_t nr_pad, int64_t ng, int64_t g0, int64_t g_end, int64_t gps,
+                                                                int64_t slice_lo, double2* __restrict__ part) {
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    const int64_t ct = (int64_t)blockIdx.x * 4 + wave;
+    if (ct >= nct) return;
+    const int64_t rt = blockIdx.y, sl = slice_lo + blockIdx.z;
+    const int64_t ga = max(g0, sl * gps), gb = min(g_end, (sl + 1) * gps);
+    if (ga >= gb) return;
+    const int64_t e = ct * 16 + (lane & 15);  // the lane's element of the n^2, as B column and as column of the result
+    const bool e_in = e < n2;
+    const double* pa = tab + ((rt * ng + (ga - g0)) * 2) * 64 + lane;
+    const double2* pb = P + ((ga - g0) * 4 + (lane >> 4)) * n2 + (e_in ? e : n2 - 1);
+    double2* out = part + ((sl * nr_pad + rt * 16 + (lane >> 4)) * n2 + e);  // register r: 4 r rows further
+    const int64_t out_step = 4 * n2, p_step = 4 * n2;
+    dm_d4 ar = {0.0, 0.0, 0.0, 0.0}, ai = ar;
+    if (e_in) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double2 z = out[r * out_step];
+            ar[r] = z.x;
+            ai[r] = z.y;
+        }
+    }
+    int64_t cnt = gb - ga;
+    for (; cnt >= 4; cnt -= 4) {
+        double c[4], s[4];
+        double2 p[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            c[u] = pa[u * 128];
+            s[u] = pa[u * 128 + 64];
+            p[u] = pb[u * p_step];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) dm_fourier_step(c[u], s[u], p[u], ar, ai);
+        pa += 4 * 128;
+        pb += 4 * p_step;
+    }
+    for (; cnt > 0; --cnt) {
+        dm_fourier_step(pa[0], pa[64], pb[0], ar, ai);
+        pa += 128;
+        pb += p_step;
+    }
+    if (e_in) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out[r * out_step] = make_double2(ar[r], ai[r]);
+    }
+}
+
+// rho[r][e] = the slices' partials in index order
+__global__ void __launch_bounds__(DM_THREADS) dm_reduce_kernel(const double2* __restrict__ part, int64_t slices, int64_t nr_pad, int64_t n_r, int64_t n2,
+                                                               double2* __restrict__ rho) {
+    const int64_t idx = (int64_t)blockIdx.x * DM_THREADS + threadIdx.x;
+    if (idx >= n_r * n2) return;
+    double2 acc = part[idx];  // (rows of slice 0 are those of rho)
+    for (int64_t s = 1; s < slices; ++s) {
+        const double2 z = part[s * nr_pad * n2 + idx];
+        acc.x += z.x;
+        acc.y += z.y;
+    }
+    rho[idx] = acc;
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------
+int dm_plan(int dim, const int32_t* mesh, int64_t nk_total, int64_t first_pt, int64_t rows, int n_orb, int64_t n_r, DmPlan* out) {
+    DmPlan L;
+    L.mesh.dim = dim;
+    L.mesh.n[0] = mesh[0];
+    L.mesh.n[1] = mesh[1];
+    L.mesh.n[2] = dim == 3 ? mesh[2] : 1;
+    L.mesh.nk = nk_total;
+    L.mesh.first = first_pt;
+    L.n = n_orb;
+    L.n2 = (int64_t)n_orb * n_orb;
+    L.nct = (L.n2 + 15) / 16;
+    L.n_r = n_r;
+    L.rows = rows;
+    dm_plan_slices(rows, n_orb, n_r, &L.nr_pad, &L.slices, &L.kps);
+    *out = L;
+    return TBK_OK;
+}
+
+// R[n_r][dim] reduced to [0, n_d) per axis
+int dm_reduce_R(int dim, const int32_t* mesh, int64_t n_r, const int64_t* R, std::vector<int32_t>* out) {
+    try {
+        out->resize((size_t)n_r * dim);
+    } catch (...) {
+        tbk_set_error("cannot allocate the reduced lattice vectors");
+        return TBK_ERR_MEMORY;
+    }
+    for (int64_t r = 0; r < n_r; ++r)
+        for (int d = 0; d < dim; ++d) {
+            const int64_t nd = mesh[d];
+            (*out)[(size_t)r * dim + d] = (int32_t)(((R[r * dim + d] % nd) + nd) % nd);
+        }
+    return TBK_OK;
+}
+
+// a chunk no longer than the phase table's budget allows
+int64_t dm_cap_chunk(const DmPlan& L, int64_t chunk) {
+    const int64_t by_tab = (int64_t)(DM_TAB_BUDGET / ((size_t)L.nr_pad * 2 * sizeof(double)));
+    return std::max<int64_t>(1, std::min(chunk, std::max<int64_t>(4, by_tab - 8)));
+}
+
+// The slab's points [c0, c0 + nkc): d_U their eigenvectors, d_w_chunk their rows of w.  ev (may be NULL): stages 0, 1, 2
+int dm_launch_chunk(hipStream_t s, const DmPlan& L, SpanRecorder* ev, const int32_t* d_Rm, const double* d_U, const double* d_w_chunk, int64_t c0,
+                    int64_t nkc, double* d_tab, double2* d_P, double2* d_part) {
+    const int64_t pad = c0 & 3, g0 = c0 >> 2, ng = (pad + nkc + 3) / 4, g_end = g0 + ng, gps = L.kps / 4;
+    const int64_t tab_threads = L.nr_pad / 16 * ng * 64;
+    if (ev) ev->start(0);
+    hipLaunchKernelGGL(dm_phase_kernel, dim3((unsigned)((tab_threads + DM_THREADS - 1) / DM_THREADS)), dim3(DM_THREADS), 0, s, d_Rm, L.mesh, L.n_r,
+                       L.nr_pad, c0, nkc, ng, d_tab);
+    if (ev) ev->stop();
+    TBK_HIP(hipGetLastError());
+    if (ev) ev->start(1);
+    if (L.n <= 16) {
+        hipLaunchKernelGGL(dm_project_kernel<1>, dim3((unsigned)ng, 1), dim3(DM_THREADS), 0, s, reinterpret_cast<const double2*>(d_U), d_w_chunk, L.n,
+                           pad, nkc, d_P);
+    } else {
+        const int nb = (L.n + 63) / 64;
+        hipLaunchKernelGGL(dm_project_kernel<4>, dim3((unsigned)(ng * 4), (unsigned)(nb * nb)), dim3(DM_THREADS), 0, s,
+                           reinterpret_cast<const double2*>(d_U), d_w_chunk, L.n, pad, nkc, d_P);
+    }
+    if (ev) ev->stop();
+    TBK_HIP(hipGetLastError());
+    const int64_t slice_lo = g0 / gps, slice_hi = (g_end - 1) / gps;
+    if (ev) ev->start(2);
+    hipLaunchKernelGGL(dm_fourier_kernel, dim3((unsigned)((L.nct + 3) / 4), (unsigned)(L.nr_pad / 16), (unsigned)(slice_hi - slice_lo + 1)),
+                       dim3(DM_THREADS), 0, s, d_tab, d_P, L.n2, L.nct, L.nr_pad, ng, g0, g_end, gps, slice_lo, d_part);
+    if (ev) ev->stop();
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// the result of the slab in device memory: d_part itself with one slice, else the slices summed into d_rho
+int dm_launch_reduce(hipStream_t s, const DmPlan& L, SpanRecorder* ev, const double2* d_part, double2* d_rho, const double2** result) {
+    *result = d_part;
+    if (L.slices == 1) return TBK_OK;
+    if (ev) ev->start(2);
+    hipLaunchKernelGGL(dm_reduce_kernel, dim3((unsigned)((L.n_r * L.n2 + DM_THREADS - 1) / DM_THREADS)), dim3(DM_THREADS), 0, s, d_part, L.slices,
+                       L.nr_pad, L.n_r, L.n2, d_rho);
+    if (ev) ev->stop();
+    TBK_HIP(hipGetLastError());
+    *result = d_rho;
+    return TBK_OK;
+}
+
+int dm_check_R(int64_t n_r, const int64_t* R, const double* rho_out, int n_orb) {
+    TBK_ARG(n_r >= 1, "n_r < 1");
+    TBK_ARG(R != nullptr && rho_out != nullptr, "R / rho is NULL");
+    TBK_ARG(n_r <= DM_MAX_R, "more than 1048560 lattice vectors in one call");
+    TBK_ARG(n_orb <= 16320, "more than 16320 orbitals");  // (255 x 255 blocks of the projector: one grid row each)
+    return TBK_OK;
+}
+
+// Waits for what a call has enqueued on its handles' streams when the call ends, however it ends: copies into host buffers that
+// the call owns (or the caller gets back) may be pending when an error of a later slab returns.
+struct DmDrain {
+    std::vector<OccSlab>& slabs;
+    ~DmDrain() {
+        for (OccSlab& s : slabs)
+            if (hipSetDevice(s.m->device) == hipSuccess) (void)hipStreamSynchronize(s.m->stream);
+    }
+};
+
+}  // namespace
+
+extern "C" int tbk_dm_plan(int64_t rows, int n_orb, int64_t n_r, int64_t* out) {
+    TBK_ARG(rows >= 1 && n_orb >= 1 && n_r >= 1 && out != nullptr, "rows / n_orb / n_r < 1 or out is NULL");
+    dm_plan_slices(rows, n_orb, n_r, &out[0], &out[1], &out[2]);
+    return TBK_OK;
+}
+
+extern "C" int tbk_density_matrix_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U,
+                                                   double energy, int64_t k_chunk, int64_t n_r, const int64_t* R, double* rho_out) {
+    int64_t nk = 0;
+    TBK_CHECK(tetra_check_mesh(dim, mesh, OCC_MESH, &nk));
+    TBK_ARG(E != nullptr && U != nullptr, "E / U is NULL");
+    TBK_ARG(n_orb >= 1, "n_orb < 1");
+    TBK_ARG(std::isfinite(energy), "the energy is not finite");
+    TBK_ARG(k_chunk >= 0, "k_chunk < 0");
+    TBK_CHECK(dm_check_R(n_r, R, rho_out, n_orb));
+    TBK_CHECK(tetra_check_device(device));
+    OccPlan L;
+    TBK_CHECK(occ_plan(dim, mesh, mesh[0], mesh[0], 0, n_orb, &L));
+    DmPlan D;
+    TBK_CHECK(dm_plan(dim, mesh, nk, 0, nk, n_orb, n_r, &D));
+    std::vector<int32_t> h_Rm;
+    TBK_CHECK(dm_reduce_R(dim, mesh, n_r, R, &h_Rm));
+    const int64_t chunk = dm_cap_chunk(D, k_chunk == 0 ? nk : std::min(k_chunk, nk));
+    const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double), u_per_k = (size_t)n_orb * (size_t)n_orb * 2;
+    DevBuf d_E, d_w, d_U, d_Rm, d_tab, d_P, d_part, d_rho;
+    TBK_CHECK(d_E.reserve(e_bytes));
+    TBK_CHECK(d_w.reserve(e_bytes));
+    TBK_CHECK(d_part.reserve(D.part_bytes()));
+    if (D.slices > 1) TBK_CHECK(d_rho.reserve(D.rho_bytes()));
+    TBK_CHECK(d_Rm.reserve(h_Rm.size() * sizeof(int32_t)));
+    TBK_CHECK(d_U.reserve((size_t)chunk * u_per_k * sizeof(double)));
+    TBK_CHECK(d_tab.reserve(D.tab_bytes(chunk)));
+    TBK_CHECK(d_P.reserve(D.p_bytes(chunk)));
+    TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
+    TBK_HIP(hipMemcpy(d_Rm.ptr, h_Rm.data(), h_Rm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    TBK_HIP(hipMemset(d_part.ptr, 0, D.part_bytes()));
+    TBK_CHECK(occ_launch_weights(nullptr, L, d_E.as<double>(), energy, (double)nk, d_w.as<double>()));
+    for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
+        const int64_t nkc = std::min(chunk, nk - c0);
+        TBK_HIP(hipMemcpy(d_U.ptr, U + (size_t)c0 * u_per_k, (size_t)nkc * u_per_k * sizeof(double), hipMemcpyHostToDevice));
+        TBK_CHECK(dm_launch_chunk(nullptr, D, nullptr, d_Rm.as<int32_t>(), d_U.as<double>(), d_w.as<double>() + (size_t)c0 * n_orb, c0, nkc,
+                                  d_tab.as<double>(), d_P.as<double2>(), d_part.as<double2>()));
+    }
+    const double2* d_result = nullptr;
+    TBK_CHECK(dm_launch_reduce(nullptr, D, nullptr, d_part.as<double2>(), d_rho.as<double2>(), &d_result));
+    TBK_HIP(hipMemcpy(rho_out, d_result, D.rho_bytes(), hipMemcpyDeviceToHost));
+    return TBK_OK;
+}
+
+extern "C" int tbk_density_matrix_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, int64_t n_r,
+                                        const int64_t* R, double* mu_out, double* rho_out) {
+    TBK_ARG(mu_out != nullptr, "mu is NULL");
+    TBK_ARG(mode == 0 || mode == 1, "mode must be 0 (value = energy) or 1 (value = n_electrons)");
+    TBK_ARG(handles != nullptr && n_handles >= 1 && handles[0] != nullptr, "no handles");
+    TBK_CHECK(dm_check_R(n_r, R, rho_out, handles[0]->n_orb));
+    if (mode == 1)
+        TBK_CHECK(tbk_fermi_check_electrons(value, handles[0]->n_orb));
+    else
+        TBK_ARG(std::isfinite(value), "the energy is not finite");
+    OccStaged staged;
+    TBK_CHECK(staged.make(handles, n_handles, mesh));
+    TBK_CHECK(staged.find_mu(mesh, mode, value, mu_out));
+    TBK_CHECK(staged.weights(mu_out[0], nullptr, false));  // (not one of this family's three stages: not timed)
+    const int n_orb = staged.n_orb, dim = staged.dim;
+    const size_t rho_doubles = (size_t)n_r * n_orb * n_orb * 2;
+    std::vector<int32_t> h_Rm;
+    TBK_CHECK(dm_reduce_R(dim, mesh, n_r, R, &h_Rm));
+    std::vector<std::vector<double>> partial(staged.slabs.size());  // of the slabs behind the first
+    DmDrain drain{staged.slabs};  // (declared behind the buffers: it waits before they go)
+    for (size_t i = 0; i < staged.slabs.size(); ++i) {
+        OccSlab& s = staged.slabs[i];
+        tbk_model* m = s.m;
+        TBK_HIP(hipSetDevice(m->device));
+        const int64_t nk = s.L.rows;
+        DmPlan D;
+        TBK_CHECK(dm_plan(dim, mesh, staged.nk_total, s.p_lo * staged.plane_pts, nk, n_orb, n_r, &D));
+        // rho and its partials first: the chunk is chosen from the memory they leave, and halved for the P buffer
+        TBK_CHECK(m->ws_dm_part.reserve(D.part_bytes()));
+        if (D.slices > 1) TBK_CHECK(m->ws_dm_rho.reserve(D.rho_bytes()));
+        TBK_CHECK(m->ws_dm_r.reserve(h_Rm.size() * sizeof(int32_t)));
+        const int64_t chunk = dm_cap_chunk(D, OccStaged::chunk_of(m, nk, 2));
+        const size_t u_doubles = (size_t)chunk * n_orb * n_orb * 2;
+        TBK_CHECK(m->ws_pdos_u.reserve((u_doubles + (size_t)chunk * n_orb) * sizeof(double)));
+        TBK_CHECK(m->ws_dm_tab.reserve(D.tab_bytes(chunk)));
+        TBK_CHECK(m->ws_dm_p.reserve(D.p_bytes(chunk)));
+        TBK_HIP(hipMemcpyAsync(m->ws_dm_r.ptr, h_Rm.data(), h_Rm.size() * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+        TBK_HIP(hipMemsetAsync(m->ws_dm_part.ptr, 0, D.part_bytes(), m->stream));
+        double* d_U = m->ws_pdos_u.as<double>();
+        const double* d_w = m->ws_occ_w.as<double>();
+        const double* d_k_own = m->ws_k.as<double>() + (size_t)s.off0 * staged.plane_pts * dim;
+        for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
+            const int64_t nkc = std::min(chunk, nk - c0);
+            // (the chunk's eigenvalues are not used: the weights come from the eigenvalue path)
+            TBK_CHECK(tbk_eigh_device(m, d_k_own + c0 * dim, nkc, 2, nullptr, d_U + u_doubles, d_U));
+            TBK_CHECK(dm_launch_chunk(m->stream, D, &s.ev, m->ws_dm_r.as<int32_t>(), d_U, d_w + (size_t)c0 * n_orb, c0, nkc,
+                                      m->ws_dm_tab.as<double>(), m->ws_dm_p.as<double2>(), m->ws_dm_part.as<double2>()));
+        }
+        const double2* d_result = nullptr;
+        TBK_CHECK(dm_launch_reduce(m->stream, D, &s.ev, m->ws_dm_part.as<double2>(), m->ws_dm_rho.as<double2>(), &d_result));
+        double* h_dst = rho_out;
+        if (i > 0) {
+            try {
+                partial[i].resize(rho_doubles);
+            } catch (...) {
+                tbk_set_error("cannot allocate the per-handle results");
+                return TBK_ERR_MEMORY;
+            }
+            h_dst = partial[i].data();
+        }
+        TBK_HIP(hipMemcpyAsync(h_dst, d_result, D.rho_bytes(), hipMemcpyDeviceToHost, m->stream));
+    }
+    // synchronises every handle (the eigenvector flags are reported as by tbk_eigh) and books the kernel times
+    for (OccSlab& s : staged.slabs) TBK_CHECK(tbk_eigenval_check(s.m));
+    for (size_t i = 0; i < staged.slabs.size(); ++i) {
+        tbk_model* m = staged.slabs[i].m;
+        TBK_HIP(hipSetDevice(m->device));
+        TBK_HIP(hipStreamSynchronize(m->stream));
+        staged.slabs[i].ev.collect(m->timed[TIMED_DM].ms);
+        m->timed[TIMED_DM].calls += 1;
+    }
+    for (size_t i = 1; i < staged.slabs.size(); ++i)  // in handle order
+        for (size_t x = 0; x < rho_doubles; ++x) rho_out[x] += partial[i][x];
+    return TBK_OK;
+}
+
+extern "C" int tbk_density_matrix(tbk_model* m, const int32_t* mesh, int mode, double value, int64_t n_r, const int64_t* R, double* mu_out,
+                                  double* rho_out) {
+    return tbk_density_matrix_multi(&m, 1, mesh, mode, value, n_r, R, mu_out, rho_out);
+}
+
+extern "C" int tbk_dm_timing(tbk_model* m, double* ms, int64_t* calls, int reset) {
+    TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr, "model / ms / calls is NULL");
+    return tbk_timed_read(m, TIMED_DM, 3, ms, calls, nullptr, reset);
+}

@@ -178,10 +178,10 @@ struct SpanRecorder {
 };
 
 // The sums the mesh calls book their kernel times on, one row per family (tbk_dos_timing, tbk_pdos_timing, tbk_fermi_timing,
-// tbk_occ_timing: what each counts differs and is listed in DESIGN.md section 10)
-enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_COUNT };
+// tbk_occ_timing, tbk_dm_timing: what each counts differs and is listed in DESIGN.md section 10)
+enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_COUNT };
 struct TimedSums {
-    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one)
+    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ and dm three)
     int64_t calls = 0;
     int64_t passes = 0;  // fermi: the passes of its searches
 };
@@ -341,6 +341,11 @@ struct tbk_model {
     DevBuf ws_occ_w;     // tbk_tetra_weights / tbk_occupations: the point weights of the slab's own mesh points w[rows][n_orb] (tbk_occ.hip)
     DevBuf ws_occ;       // ... the block partials of the band sums, the workgroups' rows of the contraction and the combined words
                          // (the eigenvectors of one k chunk go through ws_pdos_u, the Fermi search through ws_dos)
+    DevBuf ws_dm_r;      // tbk_density_matrix (tbk_dm.hip): the lattice vectors reduced modulo the mesh, int32 [n_r][dim]
+    DevBuf ws_dm_tab;    // ... the phase table of one k chunk, [R tiles][groups of 4 k][cos | sin][64]
+    DevBuf ws_dm_p;      // ... the projectors of one k chunk, [table columns][n_orb][n_orb] complex
+    DevBuf ws_dm_part;   // ... the k slices' partial rho [slices][n_r padded to 16][n_orb][n_orb] complex, resident across the chunks
+    DevBuf ws_dm_rho;    // ... their sum [n_r][n_orb][n_orb] complex (more than one slice)
     // Set for the duration of one eigenvalue call by tbk_eigenval_device_gather (tbk_comm.hip): the chunk pipeline calls it
     // whenever the eigenvalues of rows [c0, c0 + nkc) of the call have been enqueued, with an event recorded behind
     // them -- the all-gather of finished rows leaves on the communicator's stream while later chunks compute.

@@ -1,6 +1,8 @@
 // tbk_occ.hip -- the tetrahedron integration weight of every state (k, b) of a uniform, periodic k mesh at one energy mu, and what a
 // user integrates with it: band occupations, band energies and the charge on every orbital.  Not in the reference; DESIGN.md
 // section 13 has the quantities, the summation orders and the measurements, tools/occ_model.py is the statement the tests compare with.
+// (The plan of a slab, the launchers below and the staged call -- handles, slabs, eigenvalues, mu, weights -- are declared in tbk_occ.h:
+// tbk_dm.hip drives the same call up to the weights.)
 //
 //   E[planes][n1][n2][n_orb]  ascending eigenvalues per mesh point, mesh order (last axis fastest): what tbk_dos.hip reads
 //   w[k][b]   = (sum over the simplices T that contain mesh point k of Bloechl's corner weight w_c(T, b; mu) of k in T) / (S NK)
@@ -43,7 +45,7 @@
 #include <cstring>
 #include <vector>
 
-#include "tbk_tetra.h"
+#include "tbk_occ.h"
 
 namespace {
 
@@ -51,15 +53,6 @@ constexpr int OCC_THREADS = 256;
 constexpr int OCC_BLOCK = 256;             // mesh points per block of the band sums
 constexpr int64_t OCC_MAX_WG = 4096;       // rows of the contraction buffer, at most (more only for the 2^20 bound)
 constexpr int64_t OCC_MAX_GRID = 1 << 20;  // workgroups of the weights kernel, at most (the items are strided over them)
-
-struct OccGeom {
-    int n0_own;     // planes of axis 0 this launch writes weights for
-    int n0_planes;  // planes of axis 0 in E
-    int off0;       // the first own plane in E: 0 for a whole mesh, 1 for a slab with its two neighbour planes
-    int n1, n2;     // the other axes (n2 = 1 in two dimensions)
-    int n_orb;
-    int64_t items;  // n0_own * n1 * n2 * n_orb
-};
 
 __device__ __forceinline__ int occ_prev(int i, int n) { return i == 0 ? n - 1 : i - 1; }
 __device__ __forceinline__ int occ_next(int i, int n) { return i + 1 == n ? 0 : i + 1; }
@@ -262,19 +255,9 @@ __global__ void __launch_bounds__(OCC_THREADS) occ_reduce_kernel(const unsigned 
     sums[n + i] = q.lo;
 }
 
-// ---- host: one slab of the mesh on one device ----------------------------------------------------------------------------------
-struct OccPlan {
-    OccGeom g;
-    int dim = 0;
-    int64_t rows = 0;      // own mesh points
-    int64_t n_blocks = 0;  // of the band sums
-    int64_t kpw = 1, n_wg = 1;
-    int w_grid = 1;
-    // the workspace: part_f, part_eb [n_blocks][n]; buf [n_wg][n]; then what goes to the host in one copy: f high / low [2][n],
-    // q high / low [2][n] (u64), eb [n] (double)
-    size_t off_part_eb = 0, off_buf = 0, off_host = 0, host_bytes = 0, ws_bytes = 0;
-};
+}  // namespace
 
+// ---- host: one slab of the mesh on one device (declared in tbk_occ.h) -----------------------------------------------------------
 // cells0 own planes along axis 0 out of planes0 planes in E, the first own one at off0
 int occ_plan(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int off0, int n_orb, OccPlan* out) {
     OccPlan L;
@@ -354,6 +337,8 @@ int occ_launch_reduce(hipStream_t s, const OccPlan& L, char* ws) {
     return TBK_OK;
 }
 
+namespace {
+
 // the integer words of f and q and the doubles of eb, summed over the slabs on the host: the words exactly (128 bits), eb in slab order
 struct OccTotals {
     std::vector<unsigned __int128> f, q;
@@ -378,132 +363,6 @@ struct OccTotals {
             q_out[i] = DosWords::to_double(q[(size_t)i]) / nk_total;
             eb_out[i] = eb[(size_t)i];
         }
-    }
-};
-
-const char* const OCC_MESH = "the tetrahedron weights need a 2- or 3-dimensional mesh";
-
-// ---- the mesh on staged handles ------------------------------------------------------------------------------------------------
-struct OccSlab {
-    tbk_model* m = nullptr;
-    int64_t p_lo = 0, p_count = 0, planes = 0;
-    int off0 = 0;
-    OccPlan L;
-    const double* d_E = nullptr;  // planes planes
-    std::vector<double> h_k;
-    std::vector<double> host;  // the off_host block
-    SpanRecorder ev;  // stages: 0 the weights kernel, 1 the band sums, 2 the contraction + its reduction
-};
-
-// Handle i takes the slab of tbk_dos_multi.  Its eigenvalues: the planes [p_lo, p_lo + p_count] come from ONE call of the
-// eigenvalue path on the k list tbk_fermi_multi gives it (the same call, so the same bits: mu is tbk_fermi's), the neighbour plane
-// p_lo - 1 from a second call, in front of them in ws_out.  A handle that holds the whole axis needs neither neighbour.
-struct OccStaged : TetraHandles {
-    std::vector<OccSlab> slabs;
-
-    // the handles and the mesh, checked and locked; then the eigenvalues of every slab, checked
-    int make(tbk_model* const* handles, int n_handles, const int32_t* mesh) {
-        TBK_CHECK(open(handles, n_handles, mesh, OCC_MESH));
-        const int64_t n0 = mesh[0];
-        slabs.reserve((size_t)cut.busy());
-        for (int i = 0; i < cut.busy(); ++i) {  // handles whose slab is empty are skipped
-            const int64_t p_lo = cut.lo(i), p_count = cut.count(i);
-            tbk_model* m = handles[i];
-            slabs.emplace_back();
-            OccSlab& s = slabs.back();
-            s.m = m;
-            s.p_lo = p_lo;
-            s.p_count = p_count;
-            s.off0 = p_count == n0 ? 0 : 1;
-            const int64_t main_planes = p_count == n0 ? n0 : p_count + 1;
-            s.planes = main_planes + s.off0;
-            TBK_CHECK(tbk_eig_check_option(m));
-            TBK_HIP(hipSetDevice(m->device));
-            TBK_CHECK(occ_plan(dim, mesh, p_count, s.planes, s.off0, n_orb, &s.L));
-            TBK_CHECK(m->ws_occ_w.reserve((size_t)s.L.rows * n_orb * sizeof(double)));
-            TBK_CHECK(m->ws_occ.reserve(s.L.ws_bytes));
-            // the neighbour plane below in front of the main planes
-            TBK_CHECK(tbk_mesh_eigenvalues(m, mesh, p_lo, main_planes, s.off0 != 0, &s.h_k));
-            s.d_E = m->ws_out.as<double>();
-            s.ev = SpanRecorder(m->timing, m->stream);
-        }
-        // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigenval: the first failing slab's
-        for (OccSlab& s : slabs) TBK_CHECK(tbk_eigenval_check(s.m));
-        return TBK_OK;
-    }
-
-    // mode 1: the Fermi search of tbk_fermi on the resident eigenvalues; mode 0: N(value) from the probe kernel
-    int find_mu(const int32_t* mesh, int mode, double value, double* mu_out) {
-        std::vector<tbk_fermi_slab_t> f;
-        for (OccSlab& s : slabs)
-            f.push_back({s.m, s.d_E + (size_t)s.off0 * plane_pts * n_orb, s.p_count, s.p_count == mesh[0] ? s.p_count : s.p_count + 1});
-        return tbk_fermi_resident(f.data(), (int)f.size(), dim, mesh, n_orb, mode, value, mu_out);
-    }
-
-    int weights(double mu, double* w_out) {
-        for (OccSlab& s : slabs) {
-            TBK_HIP(hipSetDevice(s.m->device));
-            s.ev.start(0);
-            TBK_CHECK(occ_launch_weights(s.m->stream, s.L, s.d_E, mu, (double)nk_total, s.m->ws_occ_w.as<double>()));
-            s.ev.stop();
-            if (w_out)
-                TBK_HIP(hipMemcpyAsync(w_out + (size_t)s.p_lo * plane_pts * n_orb, s.m->ws_occ_w.ptr, (size_t)s.L.rows * n_orb * sizeof(double),
-                                       hipMemcpyDeviceToHost, s.m->stream));
-        }
-        return TBK_OK;
-    }
-
-    // f, eb and q of every slab (the weights are in ws_occ_w), left in s.host
-    int sums() {
-        for (OccSlab& s : slabs) {
-            tbk_model* m = s.m;
-            TBK_HIP(hipSetDevice(m->device));
-            char* ws = m->ws_occ.as<char>();
-            const double* d_w = m->ws_occ_w.as<double>();
-            const double* d_E_own = s.d_E + (size_t)s.off0 * plane_pts * n_orb;
-            s.ev.start(1);
-            TBK_CHECK(occ_launch_band(m->stream, s.L, d_w, d_E_own, (double)nk_total, ws));
-            s.ev.stop();
-            TBK_CHECK(occ_clear_buf(m->stream, s.L, ws));
-            // k-points per chunk: TBK_OPT_K_CHUNK as given, else what the eigenvector call itself would take from the free memory;
-            // the chunk's eigenvalues (not used: the weights come from the eigenvalue path) go behind its eigenvectors
-            const int64_t nk = s.L.rows;
-            const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : choose_chunk(m, nk, true)));
-            const size_t u_doubles = (size_t)chunk * n_orb * n_orb * 2;
-            TBK_CHECK(m->ws_pdos_u.reserve((u_doubles + (size_t)chunk * n_orb) * sizeof(double)));
-            double* d_U = m->ws_pdos_u.as<double>();
-            const double* d_k_own = m->ws_k.as<double>() + (size_t)s.off0 * plane_pts * dim;
-            for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
-                const int64_t nkc = std::min(chunk, nk - c0);
-                TBK_CHECK(tbk_eigh_device(m, d_k_own + c0 * dim, nkc, 2, nullptr, d_U + u_doubles, d_U));
-                s.ev.start(2);
-                TBK_CHECK(occ_launch_contract(m->stream, s.L, d_U, d_w, c0, nkc, (double)nk_total, ws));
-                s.ev.stop();
-            }
-            s.ev.start(2);
-            TBK_CHECK(occ_launch_reduce(m->stream, s.L, ws));
-            s.ev.stop();
-            try {
-                s.host.resize(5 * (size_t)n_orb);
-            } catch (...) {
-                tbk_set_error("cannot allocate the per-handle results");
-                return TBK_ERR_MEMORY;
-            }
-            TBK_HIP(hipMemcpyAsync(s.host.data(), ws + s.L.off_host, s.L.host_bytes, hipMemcpyDeviceToHost, m->stream));
-        }
-        return TBK_OK;
-    }
-
-    // synchronises every handle (the eigenvector flags are reported as by tbk_eigh) and books the kernel times
-    int finish() {
-        for (OccSlab& s : slabs) TBK_CHECK(tbk_eigenval_check(s.m));
-        for (OccSlab& s : slabs) {
-            TBK_HIP(hipSetDevice(s.m->device));
-            TBK_HIP(hipStreamSynchronize(s.m->stream));
-            s.ev.collect(s.m->timed[TIMED_OCC].ms);
-            s.m->timed[TIMED_OCC].calls += 1;
-        }
-        return TBK_OK;
     }
 };
 

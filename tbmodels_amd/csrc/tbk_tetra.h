@@ -1,5 +1,6 @@
 // tbk_tetra.h -- what the kernels that integrate over the simplices of a k mesh share: tbk_dos.hip (nos on an energy grid),
-// tbk_pdos.hip (the projected one), tbk_fermi.hip (nos at probe energies) and tbk_occ.hip (the weight of every mesh point).  Each
+// tbk_pdos.hip (the projected one), tbk_fermi.hip (nos at probe energies) and tbk_occ.hip (the weight of every mesh point; tbk_occ.h
+// carries its staged call on to tbk_dm.hip, the density matrix made from those weights).  Each
 // of these is written ONCE here: the energy grid, the search on it and a workgroup's window; the fixed-point format of a
 // contribution and the split of its 64-bit sums; the two sorts of a simplex's corners; the scaled gaps of a simplex with the
 // number-of-states fraction n_T(E) and Bloechl's corner weights; the step from a work item to its cell's corner rows; and, on the
