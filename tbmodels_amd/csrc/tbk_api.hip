@@ -3,7 +3,7 @@
 // eigensolver's in tbk_eig_small.hip / tbk_eig_stream.hip / tbk_eig_band*.hip (tbk_eig.hip: the rocSOLVER
 // path), and which of them a call takes is tbk_eig_plan's (tbk_eig_plan.hip); a k list that folds is driven by
 // tbk_folded_call (tbk_fold.hip), which hands the pipeline here its H(k) builder.  This file only owns memory, streams
-// and ordering.
+// and ordering.  What belongs to one call (tbk_one_k_t, the gather's chunk hook) travels down as arguments: the handle holds none.
 
 #include <algorithm>
 #include <cmath>
@@ -506,13 +506,38 @@ int fill_rows(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_k) {
     return tbk_launch_phase(m, plan.op, d_k, plan.nk, plan.nk_pad, d_A);
 }
 
-// H(k) of the chunk whose rows fill_rows made for the same plan
-int build_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, const double* d_k, const double* d_pos,
-                   double* d_H) {
+// H(k) of the chunk whose rows fill_rows made for the same plan: the second half of chunk_h
+static int build_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, const double* d_k, const double* d_pos_raw,
+                   const tbk_one_k_t& one_k, double* d_H) {
     const double* d_A = plan.rows == HK_ROWS_NONE ? nullptr : m->ws_phase.as<double>();
-    if (plan.path == HK_PATH_CSR)
-        return tbk_launch_hk_csr(m, d_A, plan.nk, plan.nk_pad, mode, convention, d_k, d_pos, d_H);
-    return tbk_launch_hk_dense(m, plan, d_A, mode, convention, d_k, d_pos, d_H);
+    const double* d_orb = nullptr;
+    // (a one-k host call: the H(k) kernel forms the phases of its one k-point itself from one_k's raw positions)
+    if (convention == 1 && one_k.h_k == nullptr) {
+        TBK_CHECK(m->ws_orb.reserve((size_t)plan.nk * m->n_orb * 2 * sizeof(double)));
+        TBK_CHECK(tbk_launch_orbital_phases(m, d_k, d_pos_raw, plan.nk, m->ws_orb.as<double>()));
+        d_orb = m->ws_orb.as<double>();
+    }
+    TBK_ARG(plan.path != HK_PATH_CSR || one_k.h_k == nullptr, "sparse models read k from the device");
+    if (plan.path == HK_PATH_CSR) return tbk_launch_hk_csr(m, d_A, plan.nk, plan.nk_pad, mode, convention, d_k, d_orb, d_H);
+    return tbk_launch_hk_dense(m, plan, d_A, mode, convention, d_k, d_orb, one_k, d_H);
+}
+
+int chunk_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, const double* d_k, const double* d_pos_raw,
+            const tbk_one_k_t& one_k, double* d_H) {
+    TBK_CHECK(fill_rows(m, plan, d_k));
+    return build_h(m, plan, mode, convention, d_k, d_pos_raw, one_k, d_H);
+}
+
+// FULL H(k) of nk k-points on the device, chunk by chunk (the caller holds the lock and has checked the arguments)
+static int hamilton_chunks(tbk_model* m, const double* d_k, int64_t nk, int convention, const double* d_pos, const tbk_one_k_t& one_k, double* d_H) {
+    const int64_t chunk = choose_chunk(m, nk, false);
+    const size_t nn2 = (size_t)m->n_orb * m->n_orb * 2;
+    for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
+        const int64_t nkc = std::min(chunk, nk - c0);
+        const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), nkc, false);
+        TBK_CHECK(chunk_h(m, plan, HK_FULL, convention, d_k + c0 * m->dim, d_pos, one_k, d_H + (size_t)c0 * nn2));
+    }
+    return TBK_OK;
 }
 
 extern "C" int tbk_hamilton_device(tbk_model* m, const double* d_k, int64_t nk, int convention,
@@ -525,25 +550,7 @@ extern "C" int tbk_hamilton_device(tbk_model* m, const double* d_k, int64_t nk, 
     TBK_ARG(d_k && d_H, "k / H is NULL");
     TBK_ARG(convention == 2 || d_pos != nullptr, "convention 1 needs pos");
     TBK_HIP(hipSetDevice(m->device));
-    const int64_t chunk = choose_chunk(m, nk, false);
-    const size_t nn2 = (size_t)m->n_orb * m->n_orb * 2;
-    for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
-        const int64_t nkc = std::min(chunk, nk - c0);
-        const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), nkc, false);
-        const double* kc = d_k + c0 * m->dim;
-        TBK_CHECK(fill_rows(m, plan, kc));
-        const double* d_orb = nullptr;
-        // (one-k host call on the matrix-vector path: the H(k) kernel forms the phases of its one k-point itself from the
-        // raw positions -- no orbital_phase_kernel launch)
-        const bool inline_orb = m->h_k_inline != nullptr && m->d_pos_inline != nullptr && nk == 1 && plan.rows == HK_ROWS_NONE;
-        if (convention == 1 && !inline_orb) {
-            TBK_CHECK(m->ws_orb.reserve((size_t)nkc * m->n_orb * 2 * sizeof(double)));
-            TBK_CHECK(tbk_launch_orbital_phases(m, kc, d_pos, nkc, m->ws_orb.as<double>()));
-            d_orb = m->ws_orb.as<double>();
-        }
-        TBK_CHECK(build_h(m, plan, HK_FULL, convention, kc, d_orb, d_H + (size_t)c0 * nn2));
-    }
-    return TBK_OK;
+    return hamilton_chunks(m, d_k, nk, convention, d_pos, tbk_one_k_t(), d_H);
 }
 
 // Eigenvalues with the hand-written solvers (the reduction family of the call's tbk_eig_plan), software-pipelined over k
@@ -612,8 +619,10 @@ static std::vector<int64_t> chunk_schedule(tbk_model* m, int64_t nk, int64_t chu
 // Fills H for k-points [c0, c0 + nkc) of the call (phase rows + contraction on the main stream).
 using HBuilder = std::function<int(int64_t c0, int64_t nkc, double* d_H)>;
 
+// one_k: for the direct builder (a folded call never is a one-k call).  on_chunk (NULL: none): tbk_chunk_hook_t, tbk_internal.h.
 static int eigenval_wave_pipeline(tbk_model* m, const tbk_eig_plan_t& plan, const double* d_k, int64_t nk, double* d_E,
-                                  const HBuilder* builder = nullptr, const std::vector<int64_t>* runs = nullptr) {
+                                  const tbk_one_k_t& one_k, const tbk_chunk_hook_t* on_chunk, const HBuilder* builder = nullptr,
+                                  const std::vector<int64_t>* runs = nullptr) {
     // The direct builder in two halves: the phase rows of a chunk only need the previous contraction to be done with the
     // row buffer (stream order), not the eigensolver to be done with H -- so they are enqueued BEFORE the main stream
     // waits for the previous chunk's reduction and run under it (an HBM-write kernel beside a VALU-bound one: 1.5 ms
@@ -628,7 +637,7 @@ static int eigenval_wave_pipeline(tbk_model* m, const tbk_eig_plan_t& plan, cons
     };
     const HBuilder direct = [&](int64_t c0, int64_t nkc, double* d_H) -> int {
         if (rows_ready_for != c0) TBK_CHECK(prepare_rows(c0, nkc));
-        return build_h(m, rows_plan, HK_TRI, 2, d_k + c0 * m->dim, nullptr, d_H);
+        return build_h(m, rows_plan, HK_TRI, 2, d_k + c0 * m->dim, nullptr, one_k, d_H);
     };
     const HBuilder& build = builder ? *builder : direct;
     const int64_t chunk = choose_chunk(m, nk, true);
@@ -669,9 +678,9 @@ static int eigenval_wave_pipeline(tbk_model* m, const tbk_eig_plan_t& plan, cons
         TBK_CHECK(build(0, nk, d_H));
         TBK_CHECK(tbk_eig_reduce(m, plan, m->stream, d_H, nk, d_de));
         TBK_CHECK(launch_tridiag_eigenvalues(m, plan, m->stream, d_de, nk, d_E));
-        if (m->chunk_done) {
+        if (on_chunk) {
             TBK_HIP(hipEventRecord(m->ev_ql[0], m->stream));
-            TBK_CHECK(m->chunk_done(0, nk, m->ev_ql[0]));
+            TBK_CHECK((*on_chunk)(0, nk, m->ev_ql[0]));
         }
         return TBK_OK;
     }
@@ -708,7 +717,7 @@ static int eigenval_wave_pipeline(tbk_model* m, const tbk_eig_plan_t& plan, cons
                                                  d_E + (size_t)prev_c0 * n, false, false,
                                                  two_stage ? m->ws_bandmat[b ^ 1].ptr : nullptr));
             TBK_HIP(hipEventRecord(m->ev_ql[b ^ 1], m->stream_ql));
-            if (m->chunk_done) TBK_CHECK(m->chunk_done(prev_c0, prev_nkc, m->ev_ql[b ^ 1]));
+            if (on_chunk) TBK_CHECK((*on_chunk)(prev_c0, prev_nkc, m->ev_ql[b ^ 1]));
         }
         prev_c0 = c0;
         prev_nkc = nkc;
@@ -721,7 +730,7 @@ static int eigenval_wave_pipeline(tbk_model* m, const tbk_eig_plan_t& plan, cons
         TBK_CHECK(launch_tridiag_eigenvalues(m, plan, m->stream_eig, debuf[b]->as<double>(), prev_nkc,
                                              d_E + (size_t)prev_c0 * n, true, true, two_stage ? m->ws_bandmat[b].ptr : nullptr));
         TBK_HIP(hipEventRecord(m->ev_ql[b], m->stream_eig));
-        if (m->chunk_done) TBK_CHECK(m->chunk_done(prev_c0, prev_nkc, m->ev_ql[b]));
+        if (on_chunk) TBK_CHECK((*on_chunk)(prev_c0, prev_nkc, m->ev_ql[b]));
     }
     // later work on the main stream (gather, D2H, the next call) sees the finished eigenvalues
     for (int b = 0; b < (n_chunks > 1 ? 2 : 1); ++b) TBK_HIP(hipStreamWaitEvent(m->stream, m->ev_ql[b], 0));
@@ -730,18 +739,16 @@ static int eigenval_wave_pipeline(tbk_model* m, const tbk_eig_plan_t& plan, cons
 }
 
 // k lists with long runs of one shared component (grids in meshgrid order, stacks of planes): the pipeline above with the
-// H(k) builder of tbk_folded_call (tbk_fold.hip).  Returns TBK_OK with *done = false when the list does not qualify.
+// H(k) builder of tbk_folded_call (tbk_fold.hip).  A list that does not qualify, and every one-k call, takes the direct builder.
 static int eigenval_folded(tbk_model* m, const tbk_eig_plan_t& eig_plan, const double* d_k, const double* h_k, int64_t nk, double* d_E,
-                           bool* done) {
-    *done = false;
+                           const tbk_one_k_t& one_k, const tbk_chunk_hook_t* on_chunk) {
     tbk_folded_call call(m, d_k, h_k, nk);
-    if (!call.folds()) return TBK_OK;
+    if (one_k.h_k != nullptr || !call.folds()) return eigenval_wave_pipeline(m, eig_plan, d_k, nk, d_E, one_k, on_chunk);
     TBK_CHECK(call.begin());
     const HBuilder folded = [&call](int64_t c0, int64_t nkc, double* d_H) { return call.build(c0, nkc, d_H); };
-    TBK_CHECK(eigenval_wave_pipeline(m, eig_plan, d_k, nk, d_E, &folded, &call.runs));
+    TBK_CHECK(eigenval_wave_pipeline(m, eig_plan, d_k, nk, d_E, one_k, on_chunk, &folded, &call.runs));
     m->counters[TBK_CNT_FOLDED_CALLS] += 1;
     m->counters[TBK_CNT_FOLDED_KPOINTS] += nk;
-    *done = true;
     return TBK_OK;
 }
 
@@ -755,10 +762,10 @@ __global__ void __launch_bounds__(256) flag_nonfinite_kernel(const double* __res
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicAdd(flag, 1);
 }
 
-// plan: tbk_eig_plan of this call, made once by the entry point; everything below reads it
-static int eigenval_device_impl(tbk_model* m, const tbk_eig_plan_t& plan, const double* d_k, const double* h_k, int64_t nk, double* d_E) {
-    TBK_ARG(m != nullptr, "model is NULL");
-    TBK_LOCK(m);
+// plan: tbk_eig_plan of this call, made once by the entry point (which holds the lock); everything below reads it.  h_k: the
+// caller's host copy of the list for the fold analysis, or NULL; one_k: set by tbk_eigenval alone.
+static int eigenval_device_impl(tbk_model* m, const tbk_eig_plan_t& plan, const double* d_k, const double* h_k, int64_t nk, double* d_E,
+                                const tbk_one_k_t& one_k, const tbk_chunk_hook_t* on_chunk) {
     TBK_ARG(nk >= 0, "nk < 0");
     if (nk == 0) return TBK_OK;
     TBK_ARG(d_k && d_E, "k / E is NULL");
@@ -767,12 +774,8 @@ static int eigenval_device_impl(tbk_model* m, const tbk_eig_plan_t& plan, const 
     TBK_CHECK(tbk_eig_check_option(m));
     // the library's own reduction kernels (the chunk pipeline), not rocSOLVER.  They raise the flag themselves (QL and
     // bisection see every non-finite (d, e) and answer NaN); rocSOLVER's eigenvalues get the pass over the output
-    if (plan.own()) {
-        bool done = false;
-        TBK_CHECK(eigenval_folded(m, plan, d_k, h_k, nk, d_E, &done));
-        if (done) return TBK_OK;
-        return eigenval_wave_pipeline(m, plan, d_k, nk, d_E);
-    }
+    if (plan.own()) return eigenval_folded(m, plan, d_k, h_k, nk, d_E, one_k, on_chunk);
+    TBK_ARG(one_k.h_k == nullptr, "the rocSOLVER branch fills its phase rows from k on the device");
 
     int64_t chunk = choose_chunk(m, nk, true);
     const size_t nn2 = (size_t)m->n_orb * m->n_orb * 2;
@@ -785,11 +788,9 @@ static int eigenval_device_impl(tbk_model* m, const tbk_eig_plan_t& plan, const 
     for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
         const int64_t nkc = std::min(chunk, nk - c0);
         const tbk_hk_plan_t hk = tbk_hk_plan(m, tbk_staged_operand(m), nkc, true);
-        const double* kc = d_k + c0 * m->dim;
-        TBK_CHECK(fill_rows(m, hk, kc));
         TBK_CHECK(m->ws_H.reserve((size_t)nkc * nn2 * sizeof(double)));
         double* d_H = m->ws_H.as<double>();
-        TBK_CHECK(build_h(m, hk, HK_TRI, 2, kc, nullptr, d_H));
+        TBK_CHECK(chunk_h(m, hk, HK_TRI, 2, d_k + c0 * m->dim, nullptr, tbk_one_k_t(), d_H));
         TBK_CHECK(tbk_eig_batched(m, d_H, nkc, d_E + (size_t)c0 * m->n_orb));
     }
     {
@@ -801,10 +802,14 @@ static int eigenval_device_impl(tbk_model* m, const tbk_eig_plan_t& plan, const 
     return TBK_OK;
 }
 
-extern "C" int tbk_eigenval_device_hint(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, double* d_E) {
+int tbk_eigenval_device_hooked(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, double* d_E, const tbk_chunk_hook_t* on_chunk) {
     TBK_ARG(m != nullptr, "model is NULL");
     TBK_LOCK(m);
-    return eigenval_device_impl(m, tbk_eig_plan(m->n_orb, m->eigensolver, nk), d_k, h_k, nk, d_E);
+    return eigenval_device_impl(m, tbk_eig_plan(m->n_orb, m->eigensolver, nk), d_k, h_k, nk, d_E, tbk_one_k_t(), on_chunk);
+}
+
+extern "C" int tbk_eigenval_device_hint(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, double* d_E) {
+    return tbk_eigenval_device_hooked(m, d_k, h_k, nk, d_E, nullptr);
 }
 
 extern "C" int tbk_eigenval_device(tbk_model* m, const double* d_k, int64_t nk, double* d_E) {
@@ -900,6 +905,7 @@ extern "C" int tbk_hamilton(tbk_model* m, const double* k, int64_t nk, int conve
             // convention 1 stay on the device from call to call -- two uploads and one launch less per call
             const bool inline_k = nk == 1 && tbk_hk_plan(m, tbk_staged_operand(m), 1, false).rows == HK_ROWS_NONE;
             const double* d_pos = nullptr;
+            tbk_one_k_t one_k;
             if (inline_k) {
                 if (convention == 1) {
                     const size_t n_pos = (size_t)m->n_orb * m->dim;
@@ -909,10 +915,9 @@ extern "C" int tbk_hamilton(tbk_model* m, const double* k, int64_t nk, int conve
                         TBK_HIP(hipMemcpyAsync(m->ws_posraw.ptr, st + k_bytes, p_bytes, hipMemcpyHostToDevice, m->stream));
                         m->pos_cache.assign(pos, pos + n_pos);
                     }
-                    m->d_pos_inline = m->ws_posraw.as<double>();
-                    d_pos = m->d_pos_inline;  // (non-NULL for the argument checks; the kernels read pos_raw)
+                    one_k.d_pos_raw = m->ws_posraw.as<double>();
                 }
-                m->h_k_inline = k;
+                one_k.h_k = k;
             } else {
                 std::memcpy(st, k, k_bytes);
                 TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, st, k_bytes, hipMemcpyHostToDevice, m->stream));
@@ -933,10 +938,7 @@ extern "C" int tbk_hamilton(tbk_model* m, const double* k, int64_t nk, int conve
             constexpr size_t ZERO_COPY_MAX = size_t(1) << 20;
             const bool direct = h_bytes <= ZERO_COPY_MAX;
             double* d_out = direct ? reinterpret_cast<double*>(st + h_off) : m->ws_out.as<double>();
-            const int rc_inline = tbk_hamilton_device(m, m->ws_k.as<double>(), nk, convention, d_pos, d_out);
-            m->h_k_inline = nullptr;
-            m->d_pos_inline = nullptr;
-            TBK_CHECK(rc_inline);
+            TBK_CHECK(hamilton_chunks(m, m->ws_k.as<double>(), nk, convention, d_pos, one_k, d_out));
             if (!direct) TBK_HIP(hipMemcpyAsync(st + h_off, m->ws_out.ptr, h_bytes, hipMemcpyDeviceToHost, m->stream));
             TBK_CHECK(wait_main_stream(m));
             std::memcpy(H_out, st + h_off, h_bytes);
@@ -963,7 +965,7 @@ extern "C" int tbk_hamilton(tbk_model* m, const double* k, int64_t nk, int conve
     for (int b = 0; b < (n_chunks > 1 ? 2 : 1); ++b) TBK_CHECK(obuf[b]->reserve((size_t)out_chunk * nn2 * sizeof(double)));
     auto compute = [&](int64_t c) -> int {
         const int64_t c0 = c * out_chunk, nkc = std::min(out_chunk, nk - c0);
-        TBK_CHECK(tbk_hamilton_device(m, m->ws_k.as<double>() + c0 * m->dim, nkc, convention, d_pos, obuf[c & 1]->as<double>()));
+        TBK_CHECK(hamilton_chunks(m, m->ws_k.as<double>() + c0 * m->dim, nkc, convention, d_pos, tbk_one_k_t(), obuf[c & 1]->as<double>()));
         TBK_HIP(hipEventRecord(m->ev_out[c & 1], m->stream));
         return TBK_OK;
     };
@@ -1007,16 +1009,13 @@ extern "C" int tbk_eigenval(tbk_model* m, const double* k, int64_t nk, double* E
         // only the chunk pipeline reads it from there: the rocSOLVER branch fills its phase rows from ws_k, which a call
         // that skipped the upload would leave stale)
         const bool inline_k = nk == 1 && plan.own() && tbk_hk_plan(m, tbk_staged_operand(m), 1, false).rows == HK_ROWS_NONE;
-        if (inline_k) {
-            m->h_k_inline = k;
-        } else {
+        const tbk_one_k_t one_k = {inline_k ? k : nullptr, nullptr};
+        if (!inline_k) {
             std::memcpy(st, k, k_bytes);
             TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, st, k_bytes, hipMemcpyHostToDevice, m->stream));
         }
         // (the eigenvalues stored straight into the pinned buffer, like H in tbk_hamilton: measured, no gain -- 180.2 vs 180.0 us)
-        const int rc_inline = eigenval_device_impl(m, plan, m->ws_k.as<double>(), k, nk, m->ws_out.as<double>());
-        m->h_k_inline = nullptr;
-        TBK_CHECK(rc_inline);
+        TBK_CHECK(eigenval_device_impl(m, plan, m->ws_k.as<double>(), k, nk, m->ws_out.as<double>(), one_k, nullptr));
         {
             const int64_t count = nk * m->n_orb;
             const unsigned blocks = (unsigned)std::min<int64_t>((count + 255) / 256, 64);
@@ -1030,7 +1029,7 @@ extern "C" int tbk_eigenval(tbk_model* m, const double* k, int64_t nk, double* E
         return TBK_OK;
     }
     TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, k, k_bytes, hipMemcpyHostToDevice, m->stream));
-    TBK_CHECK(eigenval_device_impl(m, plan, m->ws_k.as<double>(), k, nk, m->ws_out.as<double>()));
+    TBK_CHECK(eigenval_device_impl(m, plan, m->ws_k.as<double>(), k, nk, m->ws_out.as<double>(), tbk_one_k_t(), nullptr));
     TBK_HIP(hipMemcpyAsync(E_out, m->ws_out.ptr, e_bytes, hipMemcpyDeviceToHost, m->stream));
     return tbk_eigenval_check(m);  // synchronises
 }

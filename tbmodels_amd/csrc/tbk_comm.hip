@@ -167,7 +167,7 @@ extern "C" int tbk_comm_synchronize(tbk_comm* c) {
 // d_all is the RESULT in caller order: [world][per][n_orb], rank r's slab at row r * per.  This rank evaluates its
 // nk <= per k-points straight into its own rows; the slab is cut into blocks of B rows (B from per and n_orb alone, so
 // every rank cuts alike whatever its chunk pipeline does), and as soon as the chunk pipeline has enqueued the
-// eigenvalues of a whole block (tbk_model::chunk_done) the communicator's stream waits for that chunk's event, gathers
+// eigenvalues of a whole block (the on_chunk hook, below) the communicator's stream waits for that chunk's event, gathers
 // the block from every rank into a landing area ([rank][block], what ncclAllGather writes) and a copy kernel moves the
 // ranks' pieces to their rows of d_all -- while the next chunk computes.  Only the last block's gather is exposed.
 // Rows nk..per of a short slab are zero.  The status word (this rank's `host_status`, else what the solvers' flag words
@@ -248,7 +248,7 @@ extern "C" int tbk_eigenval_device_gather(tbk_comm* c, tbk_model* m, const doubl
     TBK_ARG(d_all != nullptr || per == 0, "result is NULL");
     TBK_ARG(d_status_all != nullptr, "status array is NULL");
     TBK_ARG(m->device == c->device, "model and communicator live on different devices");
-    TBK_LOCK(m);  // the hook below belongs to this call alone
+    TBK_LOCK(m);  // (the handle's streams and ws_flag are read below, behind the eigenvalue call)
     TBK_HIP(hipSetDevice(c->device));
     // From here on a failure of THIS rank must not end the call: the peers are entering n_blocks all-gathers and the status
     // gather, and a rank that returned early would leave them waiting.  It becomes this rank's status word instead -- the
@@ -329,13 +329,12 @@ extern "C" int tbk_eigenval_device_gather(tbk_comm* c, tbk_model* m, const doubl
     };
     int rc = TBK_OK;
     if (compute) {
-        m->chunk_done = [&](int64_t c0, int64_t nkc, hipEvent_t done) -> int {
+        const tbk_chunk_hook_t on_chunk = [&](int64_t c0, int64_t nkc, hipEvent_t done) -> int {
             // rows below c0 + nkc of this rank's slab are final once `done` has fired (chunks complete in order)
             TBK_HIP(hipStreamWaitEvent(c->stream, done, 0));
             return send_blocks(c0 + nkc);
         };
-        rc = tbk_eigenval_device_hint(m, d_k, h_k, nk, mine);
-        m->chunk_done = nullptr;
+        rc = tbk_eigenval_device_hooked(m, d_k, h_k, nk, mine, &on_chunk);
     }
     // whatever is left -- the zero rows of a short slab, paths without chunk events (rocSOLVER), a call that failed on
     // the way: the peers are waiting in the same sequence of collectives -- goes behind the main stream

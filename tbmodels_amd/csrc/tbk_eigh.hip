@@ -372,24 +372,16 @@ extern "C" int tbk_eigh_device(tbk_model* m, const double* d_k, int64_t nk, int 
     int64_t chunk = choose_chunk(m, nk, true);
     const size_t n = (size_t)m->n_orb, nn2 = n * n * 2;
     if (!own) {
-        // (tbk_api.hip eigenval_device_solve: rocsolver_zheevd_strided_batched calls stay below 2^29 elements)
+        // (tbk_api.hip eigenval_device_impl: rocsolver_zheevd_strided_batched calls stay below 2^29 elements)
         chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, (int64_t(1) << 29) / (int64_t)(n * n)));
         m->counters[TBK_CNT_LIBRARY_CALLS] += 1;
     }
     for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
         const int64_t nkc = std::min(chunk, nk - c0);
         const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), nkc, false);
-        const double* kc = d_k + c0 * m->dim;
         double* Uc = d_U + (size_t)c0 * nn2;
         double* Ec = d_E + (size_t)c0 * n;
-        TBK_CHECK(fill_rows(m, plan, kc));
-        const double* d_orb = nullptr;
-        if (convention == 1) {
-            TBK_CHECK(m->ws_orb.reserve((size_t)nkc * n * 2 * sizeof(double)));
-            TBK_CHECK(tbk_launch_orbital_phases(m, kc, d_pos, nkc, m->ws_orb.as<double>()));
-            d_orb = m->ws_orb.as<double>();
-        }
-        TBK_CHECK(build_h(m, plan, HK_FULL, convention, kc, d_orb, Uc));
+        TBK_CHECK(chunk_h(m, plan, HK_FULL, convention, d_k + c0 * m->dim, d_pos, tbk_one_k_t(), Uc));
         TBK_CHECK(own ? eigh_jacobi(m, Uc, nkc, Ec) : eigh_rocsolver(m, Uc, nkc, Ec));
     }
     return TBK_OK;

@@ -427,8 +427,7 @@ int tbk_folded_call::run_operand(size_t r, tbk_operand_t* op) {
 // [lo, hi) of one run with the operand `op` folded for that run: phase rows + contraction of the (dim - 1)-dimensional model
 int tbk_folded_call::piece_plane(const tbk_operand_t& op, int64_t lo, int64_t hi, double* d_Hp) {
     const tbk_hk_plan_t plan = tbk_hk_plan(m, op, hi - lo, true);
-    TBK_CHECK(fill_rows(m, plan, d_k2 + lo * dim1));
-    return build_h(m, plan, HK_TRI, 2, d_k2 + lo * dim1, nullptr, d_Hp);
+    return chunk_h(m, plan, HK_TRI, 2, d_k2 + lo * dim1, nullptr, tbk_one_k_t(), d_Hp);
 }
 
 // lines a0, a0 + L, ... (n of them) of the first-level operand `from` -> slots slot0 ... of the second-level plan

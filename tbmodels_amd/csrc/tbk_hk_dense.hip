@@ -1223,20 +1223,22 @@ tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, const tbk_operand_t& op, int64_t n
 }
 
 int tbk_launch_hk_dense(tbk_model* m, const tbk_hk_plan_t& p, const double* d_A, int mode, int convention,
-                        const double* d_k, const double* d_pos, double* d_H) {
+                        const double* d_k, const double* d_pos, const tbk_one_k_t& one_k, double* d_H) {
     if (p.nk == 0) return TBK_OK;
     TBK_ARG(p.path != HK_PATH_CSR, "sparse models take tbk_launch_hk_csr");
+    const bool inline_k = one_k.h_k != nullptr;
+    TBK_ARG(inline_k ? p.nk == 1 && p.rows == HK_ROWS_NONE : one_k.d_pos_raw == nullptr, "one_k is for one k-point whose rows the kernel makes");
+    TBK_ARG(p.rows == HK_ROWS_NONE ? d_k != nullptr || inline_k : d_A != nullptr, "phase rows missing");
+    TBK_ARG(convention != 1 || mode == HK_TRI || (inline_k ? one_k.d_pos_raw : d_pos) != nullptr, "convention 1 needs the orbital phases");
     HkArgs a = hk_args(m, p.op, d_A, p.nk, p.nk_pad, d_H);
     a.kpts = d_k;
     a.pos = d_pos;
     const int grid = tile_grid(a, (int)((p.nk + TBK_BM - 1) / TBK_BM));  // (nk_pad is only the row stride of A)
-    if (m->h_k_inline != nullptr && p.nk == 1 && p.rows == HK_ROWS_NONE) {
+    if (inline_k) {
         a.k_inline = 1;  // (tbk_hamilton / tbk_eigenval on host buffers, one k-point: no upload of k)
-        for (int d = 0; d < p.op.dim; ++d) a.k_val[d] = m->h_k_inline[d];
-        a.pos_raw = m->d_pos_inline;  // convention 1: the raw positions (tbk_hamilton keeps them on the device)
+        for (int d = 0; d < p.op.dim; ++d) a.k_val[d] = one_k.h_k[d];
+        a.pos_raw = one_k.d_pos_raw;  // convention 1: the raw positions (tbk_hamilton keeps them on the device)
     }
-    TBK_ARG(p.rows == HK_ROWS_NONE ? d_k != nullptr || a.k_inline : d_A != nullptr, "phase rows missing");
-    TBK_ARG(convention != 1 || mode == HK_TRI || d_pos != nullptr || (a.k_inline && a.pos_raw != nullptr), "convention 1 needs the orbital phases");
     if (p.path == HK_PATH_TINY) {
         const int strip = (int)(((p.op.k2 / 2 + 3) / 4 * 2 + 15) / 16 * 16);  // rows of the longest quarter, whole trips of the loop
         const size_t lds = ((size_t)4 * strip + 4 * 64 * 2) * sizeof(double);

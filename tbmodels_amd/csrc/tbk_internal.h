@@ -327,11 +327,8 @@ struct tbk_model {
     DevBuf ws_kline;  // one mesh line without both folded components (second-level fold)
     DevBuf ws_band;   // two-stage reduction: pending [V | W] panel of every matrix of a chunk
     DevBuf ws_bandmat[2];  // ... and the band matrices between its stages (one per chunk in flight)
-    // one-k host calls (tbk_hamilton / tbk_eigenval, nk == 1, dense): the k-point goes into the kernel arguments (no upload),
-    // the convention-1 positions stay on the device between calls (uploaded again only when their bytes change)
-    const double* h_k_inline = nullptr;    // the caller's k-point for the duration of the call, else NULL
-    const double* d_pos_inline = nullptr;  // raw positions [n_orb][dim] on the device for the call in progress, else NULL
-    std::vector<double> pos_cache;         // host copy of what ws_posraw holds
+    // one-k host calls (tbk_one_k_t): the convention-1 positions stay on the device between calls (uploaded again when their bytes change)
+    std::vector<double> pos_cache;  // host copy of what ws_posraw holds
     DevBuf ws_posraw;
     DevBuf ws_xl;     // the launch chain of band_xl_*: the second matrix buffer (the sweep of a panel reads one, writes the other)
     DevBuf ws_dos;    // tbk_dos / tbk_pdos: the workgroups' fixed-point bins [n_wg][NE], the combined bins and nos (tbk_dos.hip, tbk_pdos.hip); tbk_fermi: its rows and partials
@@ -346,10 +343,6 @@ struct tbk_model {
     DevBuf ws_dm_p;      // ... the projectors of one k chunk, [table columns][n_orb][n_orb] complex
     DevBuf ws_dm_part;   // ... the k slices' partial rho [slices][n_r padded to 16][n_orb][n_orb] complex, resident across the chunks
     DevBuf ws_dm_rho;    // ... their sum [n_r][n_orb][n_orb] complex (more than one slice)
-    // Set for the duration of one eigenvalue call by tbk_eigenval_device_gather (tbk_comm.hip): the chunk pipeline calls it
-    // whenever the eigenvalues of rows [c0, c0 + nkc) of the call have been enqueued, with an event recorded behind
-    // them -- the all-gather of finished rows leaves on the communicator's stream while later chunks compute.
-    std::function<int(int64_t c0, int64_t nkc, hipEvent_t done)> chunk_done;
     std::vector<EventSpan> events;  // StageTimer's spans, read by tbk_get_timing (no synchronisation on the pipeline's path)
     double t_ms[TBK_T_COUNT] = {0, 0, 0, 0};
     int64_t t_n[TBK_T_COUNT] = {0, 0, 0, 0};
@@ -432,11 +425,26 @@ struct tbk_hk_plan_t {
 // has Strassen blocks) and nk.  caller_rows: the caller makes the phase rows whatever the path (never HK_ROWS_NONE).
 tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, const tbk_operand_t& op, int64_t nk, bool caller_rows);
 
-// tbk_api.hip: the chunk pipeline's pieces -- k-points per chunk (with_eig: room for the eigensolver's buffers too), the
-// phase rows of a chunk for its plan (in ws_phase), and H(k) of that chunk from those rows (tbk_eigh.hip uses them as well)
+// ONE k-point on host buffers (tbk_hamilton / tbk_eigenval) whose plan is HK_ROWS_NONE: k goes into the kernel arguments (no
+// upload) and the H(k) kernel forms the convention-1 phases itself from the raw positions.  Those two entry points decide
+// and pass this down; tbk_launch_hk_dense consumes it and refuses it for any other plan.  Default-constructed: not such a call.
+struct tbk_one_k_t {
+    const double* h_k = nullptr;        // the caller's k-point [dim] on the host, read while the launch is made
+    const double* d_pos_raw = nullptr;  // convention 1: the raw positions [n_orb][dim] on the device (tbk_model::ws_posraw)
+};
+
+// tbk_api.hip: k-points per chunk (with_eig: room for the eigensolver's buffers too), and H(k) of one chunk for its plan:
+// chunk_h is fill_rows (the phase rows, in ws_phase), then, for convention 1, the chunk's orbital phases from d_pos_raw (in
+// ws_orb) unless one_k brings the k-point, then the contraction.  Only the pipeline in tbk_api.hip enqueues the rows apart.
 int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig);
 int fill_rows(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_k);
-int build_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, const double* d_k, const double* d_pos, double* d_H);
+int chunk_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, const double* d_k, const double* d_pos_raw,
+            const tbk_one_k_t& one_k, double* d_H);
+
+// tbk_api.hip: tbk_eigenval_device_hint with a hook (NULL: none).  The chunk pipeline calls it whenever the eigenvalues of rows
+// [c0, c0 + nkc) of the call have been enqueued, with an event recorded behind them (tbk_comm.hip); the rocSOLVER path never does.
+using tbk_chunk_hook_t = std::function<int(int64_t c0, int64_t nkc, hipEvent_t done)>;
+int tbk_eigenval_device_hooked(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, double* d_E, const tbk_chunk_hook_t* on_chunk);
 
 // tbk_phase.hip
 int tbk_launch_phase_strassen(tbk_model* m, const tbk_operand_t& op, const double* d_k, int64_t nk, double* d_As);
@@ -456,7 +464,7 @@ int tbk_stage_strassen2(tbk_model* m);  // builds d_Bs2 from d_Bs if it is missi
 
 // tbk_hk_dense.hip: the H(k) of plan.nk k-points with plan.op along plan.path (not HK_PATH_CSR); d_A holds the plan's rows
 int tbk_launch_hk_dense(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_A, int mode, int convention,
-                        const double* d_k, const double* d_pos, double* d_H);
+                        const double* d_k, const double* d_pos, const tbk_one_k_t& one_k, double* d_H);
 
 // ... and of n_lines mesh lines in one launch: line t takes the operand b_stride doubles behind that of line t - 1 (op: line 0)
 int tbk_launch_hk_dense_lines(tbk_model* m, const tbk_operand_t& op, const double* d_A, int64_t n_lines, int line_len, int64_t b_stride,

@@ -277,6 +277,13 @@ def test_chunk_pipelined_gather_equals_the_in_stream_gather(small_model):
         plain = model.eigenval_array(rand[:3000])
         _lib.check(lib.tbk_model_set_option(handle, _lib.TBK_OPT_K_CHUNK, 0))
         assert rc == 0 and status[0] == 0 and np.array_equal(out, plain)
+        # the gather's hook was an argument of its own call: a plain call of several chunks (three of 128 k-points) on
+        # this handle, behind all the gathers above, is bit for bit what a handle that never saw a gather computes
+        fresh = tbmodels_amd.Model.from_packed(r_vec, hop)
+        for mdl in (model, fresh):
+            _lib.check(lib.tbk_model_set_option(mdl._staged(), _lib.TBK_OPT_K_CHUNK, 128))
+        assert np.array_equal(model.eigenval_array(rand[:300]), fresh.eigenval_array(rand[:300]))
+        _lib.check(lib.tbk_model_set_option(handle, _lib.TBK_OPT_K_CHUNK, 0))
         verdict = np.full(1, -1.0)
         _lib.check(lib.tbk_comm_agree(comm, 3, _lib.ptr(verdict)))
         assert verdict[0] == 3.0

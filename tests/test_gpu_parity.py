@@ -121,6 +121,55 @@ def test_one_k_calls_take_k_in_the_kernel_arguments_and_keep_the_positions_on_th
     assert np.array_equal(h, h.conj().T) and not np.diagonal(h).imag.any()  # exactly Hermitian, real diagonal
 
 
+@pytest.mark.parametrize("n_orb,n_r", [(8, 30), (64, 200)])
+def test_a_one_k_host_call_leaves_nothing_behind_for_the_device_entry_points(n_orb, n_r):
+    """The k-point and the raw positions of a one-k host call are arguments of that call (csrc/tbk_internal.h: tbk_one_k_t):
+    ``tbk_hamilton_device`` / ``tbk_eigenval_device`` with ONE other k-point in device memory, on the same handle right
+    behind such calls, read their own k and pos -- on the one-launch path (8 orbitals) and the matrix-vector path (64)."""
+    import ctypes
+
+    from tbmodels_amd import _lib
+
+    lib = _lib.lib()
+    r_vec, hop, pos = syn.dense_model_arrays(n_orb, n_r, syn.MODEL_SEED + 500 + n_orb)
+    model = tbmodels_amd.Model.from_packed(r_vec, hop, pos=pos)
+    k = syn.random_kpoints(2, seed=n_orb + 1) * 3.0 - 1.0
+    k0, k1 = np.ascontiguousarray(k[0]), np.ascontiguousarray(k[1])
+    pos = np.ascontiguousarray(pos, dtype=np.float64)
+    ref_h1, ref_h2 = (oracle.hamilton(r_vec, hop, k1, conv, pos=pos) for conv in (1, 2))
+    _close(model.hamilton(k0, convention=1), oracle.hamilton(r_vec, hop, k0, 1, pos=pos))
+    _close(model.eigenval(k0), oracle.eigenval(r_vec, hop, k0))
+    handle, dev = model._staged(), model.device
+    h1, h2 = (np.empty((n_orb, n_orb), dtype=np.complex128) for _ in range(2))
+    eig = np.empty(n_orb)
+    ptrs = []
+    try:
+        for nbytes in (k1.nbytes, pos.nbytes, h1.nbytes, eig.nbytes):
+            p = ctypes.c_void_p()
+            _lib.check(lib.tbk_device_malloc(dev, nbytes, ctypes.byref(p)))
+            ptrs.append(p)
+        d_k1, d_pos, d_h, d_e = ptrs
+        _lib.check(lib.tbk_memcpy_h2d(dev, d_k1, _lib.ptr(k1), k1.nbytes))
+        _lib.check(lib.tbk_memcpy_h2d(dev, d_pos, _lib.ptr(pos), pos.nbytes))
+        for convention, out in ((1, h1), (2, h2)):
+            _lib.check(lib.tbk_hamilton_device(handle, d_k1, 1, convention, d_pos if convention == 1 else None, d_h))
+            _lib.check(lib.tbk_synchronize(handle))
+            _lib.check(lib.tbk_memcpy_d2h(dev, _lib.ptr(out), d_h, out.nbytes))
+        _lib.check(lib.tbk_eigenval_device(handle, d_k1, 1, d_e))
+        _lib.check(lib.tbk_eigenval_check(handle))
+        _lib.check(lib.tbk_memcpy_d2h(dev, _lib.ptr(eig), d_e, eig.nbytes))
+    finally:
+        for p in ptrs:
+            _lib.check(lib.tbk_device_free(dev, p))
+    _close(h1, ref_h1)
+    _close(h2, ref_h2)
+    _close(eig, oracle.eigenval(r_vec, hop, k1))
+    _close(h1, model.hamilton(k, convention=1)[1], 1e-13)
+    # ... and the host calls behind them take their own k again
+    _close(model.hamilton(k0, convention=1), oracle.hamilton(r_vec, hop, k0, 1, pos=pos))
+    _close(model.eigenval(k0), oracle.eigenval(r_vec, hop, k0))
+
+
 def test_scalar_k_single_point_and_empty(synthetic):
     model = tbmodels_amd.Model.from_packed(synthetic["dim1_R"], synthetic["dim1_hop"], pos=synthetic["dim1_pos"])
     k = float(synthetic["dim1_scalar_k"])
