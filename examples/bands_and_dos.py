@@ -116,6 +116,17 @@ def main():
         print("  band energy from the bonds %.6f per cell (occupations: %.6f), largest single vector %.6f"
               % (bonds.sum(), occ.band_energy.sum(), bonds[np.argmax(np.abs(bonds))]))
 
+        # 7. the bare susceptibility chi_0(q) along Gamma - X, q = (j, 0, j) / 20 in reduced coordinates (X = (1/2, 0, 1/2)), at k_B T = 0.05 with the chemical
+        # potential in the gap: one n x n overlap per (k, q) pair on the matrix pipe, one number per q comes back
+        m = 20
+        line = np.array([[j, 0, j] for j in range(m // 2 + 1)], dtype=np.int64)
+        model.susceptibility((m, m, m), line, temperature=0.05, n_electrons=4)  # warm up
+        t0 = time.perf_counter()
+        chi = model.susceptibility((m, m, m), line, temperature=0.05, n_electrons=4)
+        dt = time.perf_counter() - t0
+        print("chi_0 along Gamma - X on a %d^3 mesh at k_B T = 0.05 in %.1f ms (mu = %.6f):" % (m, dt * 1e3, chi.mu.mu))
+        print("  " + " ".join("%.4f" % x for x in chi.chi))
+
 
 if __name__ == "__main__":
     main()

@@ -407,6 +407,49 @@ int tbk_dm_plan(int64_t rows, int n_orb, int64_t n_r, int64_t* out);
  * weights kernel, a stage of tbk_occ_timing, is not timed in these calls.) */
 int tbk_dm_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
+/* ---- the bare (Lindhard) static susceptibility of a uniform k mesh (not in the reference) ----------------------------------------
+ * Mesh and mesh points k = (i_1 / n_1, ..., i_dim / n_dim) are those of tbk_occupations (dim 2 or 3); k+q is the mesh point with the
+ * indices (i_d + q_d) mod n_d.  With E, U the eigenvalues and eigenvectors of tbk_eigh (convention 2), T = k_B T > 0 in the model's
+ * energy units and the chemical potential mu (csrc/tbk_chi.hip):
+ *     M(k, q)[b][b'] = sum_i conj(U[k][i][b]) D(q)[i] U[k+q][i][b']
+ *     chi_0(q)       = -(1 / NK) sum_k sum_{b b'} F(E[k][b], E[k+q][b']) |M(k, q)[b][b']|^2
+ *     F(a, b)        = (f(a) - f(b)) / (a - b),  F(a, a) = f'(a),  f(x) = 1 / (1 + exp((x - mu) / T))
+ * D(q) = 1 for convention 2; for convention 1 D(q)[i] = exp(-2 pi i sum_d q_d pos[i][d] / n_d) with the unreduced q_d, a host table.
+ * Without matrix elements |M|^2 = 1 and no eigenvector is computed.  F is evaluated as -f(lo) (1 - f(hi)) h(y) / T with lo <= hi,
+ * y = (lo - hi) / T, h(y) = expm1(y) / y, h(0) = 1, f from exp(-|x - mu| / T) and 1 - f(x) as f(2 mu - x): no cancellation, no
+ * overflow.  No spin factor; static only.  chi_0 >= 0, chi_0(-q) = chi_0(q); for given (E, U, mu, T) the bits of chi_0(q) depend on
+ * q modulo the mesh and on D(q) alone -- not on the other vectors, their order, the batches or the number of handles -- and
+ * repeated calls give the same bits.  |error| <= tol_chi of DESIGN.md 15.4.
+ * q: int64 [n_q][dim] in mesh units, any value, duplicates allowed; chi_out: double [n_q].  The eigensystem of the WHOLE mesh stays
+ * in device memory (NK n_orb^2 complex and 3 NK n_orb doubles; TBK_ERR_MEMORY, with the bytes in the message, when it does not
+ * fit).  Argument errors (TBK_ERR_ARGUMENT), before any device is touched: those of tbk_occupations, T not finite or not positive,
+ * n_q < 1, convention not in {1, 2}, convention 1 without pos, more than 16320 orbitals, more than 2^23 mesh points, a NULL
+ * pointer.  Host buffers; synchronous. */
+
+/* The kernels alone on an eigensystem the caller brings: E [NK][n_orb], U [NK][n_orb][n_orb] complex or NULL (no matrix elements),
+ * phases: NULL or D [n_q][n_orb] complex (needs U). */
+int tbk_chi_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu, double T,
+                             int64_t n_q, const int64_t* q, const double* phases, double* chi_out);
+/* The whole call: eigenvalues and mu (mode, value, mu_out as for tbk_occupations: mode 1 gives tbk_fermi's numbers bit for bit; the
+ * finite-temperature chemical potential is not computed) through the slab route of tbk_occupations; then the handle fills the
+ * resident eigensystem of the whole mesh chunk by chunk (tbk_eigh_device, whose own eigenvalues enter F; without matrix elements
+ * the eigenvalue path), one kernel makes the Fermi tables, and the vectors go in batches of tbk_chi_plan's size through the overlap
+ * kernel and the reduction.  pos: [n_orb][dim], read for convention 1. */
+int tbk_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q,
+                       int matrix_elements, int convention, const double* pos, double* mu_out, double* chi_out);
+/* On several devices from one process: mu from the slabs of tbk_occupations_multi; then every handle holds the whole mesh's
+ * eigensystem and takes a contiguous share of the vectors (the first ceil(n_q / n_handles) to handle 0, ...). */
+int tbk_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T, int64_t n_q,
+                             const int64_t* q, int matrix_elements, int convention, const double* pos, double* mu_out, double* chi_out);
+/* How a call on nk mesh points, n_q vectors is run: out[0] = the overlap kernel's template (4: 64 x 64 blocks, 1: one tile, up to 16
+ * orbitals, 0: no matrix elements), out[1] = partial sums per (k, q) pair, out[2] = vectors per batch when the partials may take
+ * part_bytes (0: the library's budget of 256 MiB; at most 4096 vectors; 0 vectors: one does not fit), out[3] = batches. */
+int tbk_chi_plan(int64_t nk, int n_orb, int64_t n_q, int matrix_elements, int64_t part_bytes, int64_t* out);
+/* ms[3] = the summed HIP-event time of the Fermi tables, the overlaps with their epilogue (or the pair kernel), and the reduction
+ * in this handle's calls made while TBK_OPT_TIMING was on; calls = how many calls; reset = 1 clears.  (The eigensolver stages are in
+ * tbk_get_timing.) */
+int tbk_chi_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
 /* ---- k.p models (kdotp.py:51-100): H(k) = sum_p prod_d k_d^powers[p][d] * coeffs[p] ------- */
 int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, const int32_t* powers,
                      const double* coeffs, tbk_kdotp** out);

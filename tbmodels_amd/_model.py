@@ -44,6 +44,7 @@ BandEdges = co.namedtuple("BandEdges", ("emin", "emax"))
 FermiLevel = co.namedtuple("FermiLevel", ("mu", "lower", "upper", "nos"))
 Occupations = co.namedtuple("Occupations", ("mu", "orbital_occ", "band_occ", "band_energy"))
 DensityMatrix = co.namedtuple("DensityMatrix", ("mu", "R", "rho"))
+Susceptibility = co.namedtuple("Susceptibility", ("mu", "q", "chi"))
 
 
 def _devices_from_env():
@@ -785,7 +786,7 @@ class Model:
         return (eig[0], vec[0]) if single else (eig, vec)
 
     def _mesh_argument(self, mesh, what="dos"):
-        """The mesh check ``dos``, ``pdos``, ``band_edges``, ``fermi_level``, ``tetra_weights``, ``occupations`` and ``density_matrix`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
+        """The mesh check ``dos``, ``pdos``, ``band_edges``, ``fermi_level``, ``tetra_weights``, ``occupations``, ``density_matrix`` and ``susceptibility`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
         if self.dim not in (2, 3):
             raise ValueError("{} needs a 2- or 3-dimensional model, this one has dimension {}".format(what, self.dim))
         try:
@@ -1039,16 +1040,21 @@ class Model:
             if not keys:
                 raise ValueError("the model has no hoppings: give R")
             return np.ascontiguousarray(np.array(keys, dtype=np.int64).reshape(len(keys), self.dim))
+        return self._integer_vectors_argument(R, "R", "NR")
+
+    def _integer_vectors_argument(self, value, name, count):
+        """``int64 (count, dim)`` from an integer array-like of that shape or one vector, or ``ValueError`` (``R`` of
+        ``density_matrix``, ``q`` of ``susceptibility``)."""
         try:
-            array = np.asarray(R)
+            array = np.asarray(value)
         except (TypeError, ValueError):
-            raise ValueError("R must be an integer array of shape (NR, {})".format(self.dim)) from None
+            raise ValueError("{} must be an integer array of shape ({}, {})".format(name, count, self.dim)) from None
         if array.dtype.kind not in "iu" or array.dtype == np.uint64:
-            raise ValueError("R must hold (64-bit signed) integers, got dtype {}".format(array.dtype))
+            raise ValueError("{} must hold (64-bit signed) integers, got dtype {}".format(name, array.dtype))
         if array.ndim == 1:
             array = array.reshape(1, -1)
         if array.ndim != 2 or array.shape[1] != self.dim or array.shape[0] < 1:
-            raise ValueError("R must have shape (NR, {}) with NR >= 1, got {}".format(self.dim, array.shape))
+            raise ValueError("{} must have shape ({}, {}) with {} >= 1, got {}".format(name, count, self.dim, count, array.shape))
         return np.ascontiguousarray(array, dtype=np.int64)
 
     def density_matrix(self, mesh, *, energy=None, n_electrons=None, R=None):
@@ -1098,6 +1104,80 @@ class Model:
                                                     _lib.ptr(vectors), _lib.ptr(mu), _lib.ptr(rho))
             )
         return DensityMatrix(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, rho)
+
+    def susceptibility(self, mesh, q, *, temperature, energy=None, n_electrons=None, matrix_elements=True, convention=2):
+        """
+        The bare (Lindhard) static susceptibility ``chi_0(q)`` of a uniform k mesh, computed on the GPU from the eigensystem of
+        the whole mesh, which never leaves it.  Not in the reference.
+
+        ``mesh``, ``energy`` and ``n_electrons`` are those of :meth:`occupations`: exactly one of the last two is given, else
+        ``ValueError``.  ``q`` is an integer array-like of shape ``(NQ, dim)`` or one vector, in mesh units: the wavevector is
+        ``q_d / n_d``; any 64-bit integer and duplicates are allowed.  ``temperature`` is ``k_B T > 0`` in the model's energy
+        units.  Returns the named tuple ``(mu, q, chi)``: ``mu`` is the :class:`FermiLevel` tuple of :meth:`occupations`, ``q``
+        the vectors as ``int64 (NQ, dim)`` and ``chi`` is ``float64 (NQ,)``.
+
+        Definition.  With ``E, U`` of ``eigh(k, convention=2)`` at the mesh points ``k = (i_1 / n_1, ..., i_dim / n_dim)`` and
+        ``k+q`` the mesh point with the indices ``(i_d + q_d) mod n_d``::
+
+            M(k, q)[b, b'] = sum_i conj(U[k, i, b]) D(q)[i] U[k+q, i, b']
+            chi_0(q)       = -(1 / NK) sum_k sum_{b, b'} F(E[k, b], E[k+q, b']) |M(k, q)[b, b']|^2
+            F(a, b)        = (f(a) - f(b)) / (a - b),   F(a, a) = f'(a),   f(x) = 1 / (1 + exp((x - mu) / T))
+
+        ``D(q) = 1`` for ``convention=2``; for ``convention=1`` ``D(q)[i] = exp(-2 pi i sum_d q_d pos[i, d] / n_d)`` with the
+        unreduced ``q_d`` (what ``U_1 = diag(exp(-2 pi i k . pos)) U_2`` gives).  ``matrix_elements=False`` sets ``|M|^2 = 1``,
+        the constant-matrix-element Lindhard function; no eigenvector is computed then.  No spin factor; static only.
+
+        ``mu`` is ``energy`` as given or, for ``n_electrons``, the tetrahedron Fermi level of :meth:`fermi_level`, bit for bit.
+        The chemical potential of the Fermi function at ``temperature`` (which differs from it at finite ``T``) is not computed:
+        give it as ``energy`` when it matters.
+
+        ``F`` is not evaluated as the quotient, which cancels: with the pair ordered ``lo <= hi`` and ``y = (lo - hi) / T``,
+        ``F = -f(lo) (1 - f(hi)) h(y) / T`` with ``h(y) = expm1(y) / y``, ``h(0) = 1``, ``f`` from ``exp(-|x - mu| / T)`` and
+        ``1 - f(x)`` as ``f(2 mu - x)``: every factor is non-negative, nothing overflows, ``a = b`` is the same branch.
+
+        Properties.  (1) ``chi_0(q) >= 0`` and ``chi_0(-q) = chi_0(q)``, both conventions.  (2) With matrix elements
+        ``chi_0(0) = (1 / NK) sum_{k, b} f (1 - f) / T``, whatever the basis inside degenerate clusters.  (3) Without matrix
+        elements the result is a function of the eigenvalues alone.  (4) ``4 T chi_0(q) -> size`` as ``T -> inf`` (the rows of
+        ``M`` have unit norm).  (5) With ``mu`` 746 ``T`` or more below (or above) the spectrum every ``f`` (or ``1 - f``)
+        underflows and ``chi_0`` is exactly 0.  (6) For ``convention=2`` ``q + n_d e_d`` has the bits of ``q``.  (7) The bits of
+        ``chi_0(q)`` do not depend on the other entries of ``q``, on their order or on the number of ``devices``; a duplicate has
+        the bits of its original and a second call the bits of the first.
+
+        Error bound for a given eigensystem, with ``u = 2^-53`` and 2 ulps allowed for ``exp`` and ``expm1`` (DESIGN.md 15.4;
+        ``tools/chi_model.py`` ``tolerance``); without matrix elements ``[NK size^4 / 2 + 20.5 size^2] u / T``::
+
+            |error| <= [ NK size^3 / 2 + (3 size + 5) size^(3/2) + 22 size ] u / T
+
+        One-dimensional models raise ``ValueError``.  The eigenvectors of the whole mesh must fit the device (``NK size^2``
+        complex numbers), else ``MemoryError``.  With several ``devices`` every device holds the whole mesh's eigensystem and
+        takes a contiguous share of ``q``.
+        """
+        mesh_array = self._mesh_argument(mesh, "susceptibility")
+        if q is None:
+            raise ValueError("q must be an integer array of shape (NQ, {}), got None".format(self.dim))
+        vectors = self._integer_vectors_argument(q, "q", "NQ")
+        if isinstance(temperature, (bool, np.bool_)) or not isinstance(temperature, (int, float, np.integer, np.floating)):
+            raise ValueError("temperature must be a real number, got {!r}".format(temperature))
+        t_value = float(temperature)
+        if not np.isfinite(t_value) or not t_value > 0.0:
+            raise ValueError("temperature must be finite and positive, got {!r}".format(temperature))
+        mode, value = self._occupation_argument("susceptibility", energy, n_electrons)
+        if convention not in [1, 2]:
+            raise ValueError("Invalid value '{}' for 'convention': must be either '1' or '2'".format(convention))
+        if not isinstance(matrix_elements, (bool, np.bool_)):
+            raise ValueError("matrix_elements must be True or False, got {!r}".format(matrix_elements))
+        pos = np.ascontiguousarray(self.pos, dtype=np.float64) if convention == 1 else None
+        mu = np.empty(4, dtype=np.float64)
+        chi = np.empty(vectors.shape[0], dtype=np.float64)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_susceptibility_multi(handles, n_handles, _lib.ptr(mesh_array), mode, value, t_value, vectors.shape[0],
+                                                    _lib.ptr(vectors), int(bool(matrix_elements)), int(convention), _lib.ptr(pos),
+                                                    _lib.ptr(mu), _lib.ptr(chi))
+            )
+        return Susceptibility(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, chi)
 
     def construct_kdotp(self, k, order):
         """

@@ -1,0 +1,535 @@
+// tbk_chi.hip -- the bare (Lindhard) static susceptibility chi_0(q) of a uniform, periodic k mesh at one chemical potential and one
+// temperature.  Not in the reference; DESIGN.md section 15 has the quantity, the kernels, the error bound and the measurements,
+// tools/chi_model.py is the statement the tests compare with.
+//
+//   M(k, q)[b][b'] = sum_i conj(U[k][i][b]) D(q)[i] U[k+q][i][b']                U of tbk_eigh_device (convention 2), D: 1 or the
+//   chi_0(q)       = -(1 / NK) sum_k sum_{b b'} F(E[k][b], E[k+q][b']) |M|^2     orbital phases of convention 1 (a host table)
+//   F(a, b)        = (f(a) - f(b)) / (a - b) = -f(lo) (1 - f(hi)) h(y) / T       lo <= hi, y = (lo - hi) / T <= 0, h = expm1(y) / y
+//
+// k+q is the mesh point with the indices (i_d + q_d) mod n_d; the host reduces every q_d to [0, n_d) first, so q and q + n_d e_d
+// are the same arguments of the kernels.  The eigensystem of the WHOLE mesh is resident (U: NK n^2 complex), every (k, q) pair reads
+// two of its matrices.
+//
+//   chi_fermi_kernel    tab[0][k][b] = f(E), tab[1][k][b] = 1 - f(E) = f(2 mu - E), both from one exp(-|E - mu| / T): once per call.
+//   chi_overlap_kernel  M = U(k)^H D U(k+q) as four real products on v_mfma_f64_16x16x4_f64, contraction over the orbitals:
+//                       Mr = Ur^T U'r + Ui^T U'i, Mi = Ur^T U'i - Ui^T U'r (the minus is the instruction's negate-A bit).  A workgroup
+//                       owns a 64 x 64 block of one M(k, q), wave t its tile row t (16 x 16 of four k-points up to 16 orbitals, a
+//                       wave each): panels of 16 orbitals go through LDS once, orbital-major planes Ur, Ui (bands of the block's
+//                       rows, of k) and Re, Im of D U' (bands of its columns, of k+q), padded with zeros to the tile.  U[k][i][.] is
+//                       band-contiguous, so a panel row is one contiguous segment, and D is applied while staging: nothing but
+//                       ds_read_b64 and MFMA inside the loop.  M is never stored: the epilogue forms |M|^2 f(lo) (1 - f(hi)) h(y)
+//                       per accumulator element from the tables, the two eigenvalues and one expm1, masks the padding, and adds
+//                       up in a fixed order -- the lane's elements, the wave's lanes, the block's waves -- to one double in
+//                       part[q][k][block].
+//   chi_pair_kernel     the same sum with |M|^2 = 1 (no eigenvectors): a wave per (k, q), the n^2 pairs in lane-strided order.
+//   chi_reduce_kernel   chi[q] = (sum of part[q][.][.] in a fixed order) / T / NK: a workgroup per q, no atomics.
+//
+// The q list goes in batches of tbk_chi_plan's size (the memory of `part`).  For given (E, U, mu, T) the bits of chi_0(q) depend on
+// q modulo the mesh and on D(q) alone: not on the batch, the other vectors, their order or the handle that computes them.
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "tbk_occ.h"
+
+namespace {
+
+typedef double chi_d4 __attribute__((ext_vector_type(4)));
+
+constexpr int CHI_THREADS = 256;
+constexpr int64_t CHI_MAX_BATCH = 4096;                 // vectors per launch (grid z), at most
+constexpr size_t CHI_PART_BUDGET = size_t(256) << 20;   // the partials of one batch, at most
+constexpr int64_t CHI_MAX_NK = int64_t(1) << 23;          // one grid column per k-point, 256 threads each
+constexpr int CHI_MAX_ORB = 16320;                      // 255 x 255 blocks of one M: one grid row each
+
+struct ChiMesh {
+    int n[3];    // (n[2] = 1 in two dimensions)
+    int64_t nk;  // points of the mesh
+};
+
+struct ChiPlan {
+    ChiMesh mesh;
+    int n = 0;            // orbitals
+    int bt = 0;           // template of the overlap kernel: 4, 1 (up to 16 orbitals), 0: no matrix elements (chi_pair_kernel)
+    int64_t blocks = 1;   // partials per (k, q)
+    int64_t batch = 1;    // vectors per launch
+    int64_t batches = 1;
+    size_t part_bytes() const { return (size_t)batch * mesh.nk * blocks * sizeof(double); }
+};
+
+// the one place that chooses: template, partials per pair, batch size from the bytes the partials may take (0: the budget)
+void chi_plan_sizes(int64_t nk, int n_orb, int64_t n_q, bool matrix_elements, size_t mem, int* bt, int64_t* blocks, int64_t* batch,
+                    int64_t* batches) {
+    const int64_t nb = (n_orb + 63) / 64;
+    *bt = !matrix_elements ? 0 : n_orb <= 16 ? 1 : 4;
+    *blocks = *bt == 4 ? nb * nb : 1;
+    const size_t per_q = (size_t)nk * (size_t)*blocks * sizeof(double);
+    const size_t room = mem == 0 ? CHI_PART_BUDGET : mem;
+    *batch = std::max<int64_t>(0, std::min<int64_t>(std::min(n_q, CHI_MAX_BATCH), (int64_t)(room / per_q)));
+    *batches = *batch == 0 ? 0 : (n_q + *batch - 1) / *batch;
+}
+
+// the flat index of k+q (q reduced to [0, n_d) per axis, three entries)
+__device__ __forceinline__ int64_t chi_shifted(const ChiMesh& g, int64_t k, const int32_t* __restrict__ qv) {
+    const int64_t i2 = k % g.n[2], r = k / g.n[2];
+    const int64_t i1 = r % g.n[1], i0 = r / g.n[1];
+    const int64_t j0 = (i0 + qv[0]) % g.n[0], j1 = (i1 + qv[1]) % g.n[1], j2 = (i2 + qv[2]) % g.n[2];
+    return (j0 * g.n[1] + j1) * g.n[2] + j2;
+}
+
+// f(lo) (1 - f(hi)) h((lo - hi) / T) >= 0 of one pair of states: -T F
+__device__ __forceinline__ double chi_pair_weight(double ea, double fa, double ga, double eb, double fb, double gb, double inv_t) {
+    const bool a_low = ea <= eb;
+    const double lo = a_low ? ea : eb, hi = a_low ? eb : ea;
+    const double y = (lo - hi) * inv_t;
+    const double h = y < 0.0 ? expm1(y) / y : 1.0;  // (-inf: 0)
+    return (a_low ? fa : fb) * (a_low ? gb : ga) * h;
+}
+
+// all 64 lanes, the same tree whatever the values
+__device__ __forceinline__ double chi_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// f and 1 - f of one state from ONE exponential, t = exp(-|E - mu| / T): (t, 1) / (1 + t) above mu, (1, t) / (1 + t) at and below
+// it -- 1 - f(x) = f(2 mu - x) at the mirrored distance, which is -(E - mu) without a rounding
+__global__ void __launch_bounds__(CHI_THREADS) chi_fermi_kernel(const double* __restrict__ E, int64_t items, double mu, double T,
+                                                                double* __restrict__ tab) {
+    const int64_t i = (int64_t)blockIdx.x * CHI_THREADS + threadIdx.x;
+    if (i >= items) return;
+    const double d = E[i] - mu;
+    const double t = exp(-fabs(d) / T);
+    const double small = t / (1.0 + t), big = 1.0 / (1.0 + t);
+    tab[i] = d > 0.0 ? small : big;
+    tab[items + i] = d < 0.0 ? small : big;
+}
+
+// BT tiles of 16 along each side of the workgroup's block of M: 4 (one k-point per workgroup, wave t owns tile row t) or 1 (n <= 16:
+// four k-points per workgroup, one per wave).  grid: (k-points / KPW, blocks, vectors of the batch).  D: NULL or [batch][n] complex.
+template <int BT>
+__global__ void __launch_bounds__(CHI_THREADS) chi_overlap_kernel(const double2* __restrict__ U, const double* __restrict__ E,
+                                                                  const double* __restrict__ tab, ChiMesh g, int n,
+                                                                  const int32_t* __restrict__ Q, const double2* __restrict__ D, double inv_t,
+                                                                  int64_t blocks, double* __restrict__ part) {
+    constexpr int RB = 16 * BT;               // rows (and columns) of the block
+    constexpr int KPW = BT == 1 ? 4 : 1;      // k-points per workgroup
+    constexpr int TEAM = CHI_THREADS / KPW;   // threads that stage one k-point's panel
+    constexpr int S = BT == 1 ? 18 : 82;      // doubles between the orbital rows of a plane (dm_project_kernel's: the four rows a wave reads at once
+                                              // land in different bank pairs); a wave stores along a row
+    __shared__ double planes[KPW][4][16][S];  // Ur, Ui of the block's rows (k); Re, Im of D U' of its columns (k+q)
+    __shared__ double wave_part[4];
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int team = BT == 1 ? wave : 0, tt = tid - team * TEAM;
+    const int nb = (n + RB - 1) / RB;
+    const int bi = (int)blockIdx.y / nb, bj = (int)blockIdx.y - bi * nb;
+    const int64_t k = (int64_t)blockIdx.x * KPW + team;
+    const int64_t ql = blockIdx.z;
+    const bool valid = k < g.nk;
+    const int64_t kp = valid ? chi_shifted(g, k, Q + ql * 3) : 0;
+    const double2* Uk = U + (valid ? (size_t)k * n * n : 0);
+    const double2* Up = U + (size_t)kp * n * n;
+    const double2* Dq = D ? D + (size_t)ql * n : nullptr;
+    double(*pl)[16][S] = planes[team];
+    const int ti = BT == 1 ? 0 : wave;                      // the wave's tile row
+    const bool row_live = valid && bi * RB + ti * 16 < n;   // (wave-uniform)
+    chi_d4 accr[BT], acci[BT];
+#pragma unroll
+    for (int tj = 0; tj < BT; ++tj) accr[tj] = acci[tj] = chi_d4{0.0, 0.0, 0.0, 0.0};
+    const int sc = tt % RB, so0 = tt / RB;  // the band (column of the panel) and the first orbital row this thread stages
+    const int col_a = bi * RB + sc, col_b = bj * RB + sc;
+    for (int i0 = 0; i0 < n; i0 += 16) {
+        __syncthreads();  // the previous panel has been read
+#pragma unroll
+        for (int o = so0; o < 16; o += TEAM / RB) {
+            const int i = i0 + o;
+            const bool i_in = valid && i < n;
+            double2 ua = make_double2(0.0, 0.0), ub = ua;
+            if (i_in && col_a < n) ua = Uk[(size_t)i * n + col_a];
+            if (i_in && col_b < n) {
+                ub = Up[(size_t)i * n + col_b];
+                if (Dq) {
+                    const double2 d = Dq[i];
+                    ub = make_double2(d.x * ub.x - d.y * ub.y, d.x * ub.y + d.y * ub.x);
+                }
+            }
+            pl[0][o][sc] = ua.x;
+            pl[1][o][sc] = ua.y;
+            pl[2][o][sc] = ub.x;
+            pl[3][o][sc] = ub.y;
+        }
+        __syncthreads();
+        if (row_live) {
+#pragma unroll 1
+            for (int q4 = 0; q4 < 4; ++q4) {  // (not unrolled: dm_project_kernel's note on registers)
+                const int oq = 4 * q4 + (lane >> 4);
+                const double ar = pl[0][oq][ti * 16 + (lane & 15)], ai = pl[1][oq][ti * 16 + (lane & 15)];
+#pragma unroll
+                for (int tj = 0; tj < BT; ++tj) {
+                    if (bj * RB + tj * 16 < n) {  // (uniform)
+                        const double br = pl[2][oq][tj * 16 + (lane & 15)], bim = pl[3][oq][tj * 16 + (lane & 15)];
+                        accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, accr[tj], 0, 0, 0);
+                        accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, bim, accr[tj], 0, 0, 0);
+                        acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bim, acci[tj], 0, 0, 0);
+                        acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, acci[tj], 0, 0, 1);  // - Ui^T U'r
+                    }
+                }
+            }
+        }
+    }
+    // the epilogue.  lane (q, c), register r: row q + 4 r, column c of the tile
+    double sum = 0.0;
+    if (row_live) {
+        const int64_t items = g.nk * n;
+        const double* Ea = E + (size_t)k * n;
+        const double* Eb = E + (size_t)kp * n;
+        const double *fa = tab + (size_t)k * n, *ga = fa + items, *fb = tab + (size_t)kp * n, *gb = fb + items;
+        double ea[4], fav[4], gav[4];
+        bool a_in[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int b = bi * RB + ti * 16 + (lane >> 4) + 4 * r;
+            a_in[r] = b < n;
+            const int bs = a_in[r] ? b : 0;
+            ea[r] = Ea[bs];
+            fav[r] = fa[bs];
+            gav[r] = ga[bs];
+        }
+#pragma unroll
+        for (int tj = 0; tj < BT; ++tj) {
+            const int c = bj * RB + tj * 16 + (lane & 15);
+            if (bj * RB + tj * 16 < n) {  // (uniform)
+                const bool c_in = c < n;
+                const int cs = c_in ? c : 0;
+                const double eb = Eb[cs], fbv = fb[cs], gbv = gb[cs];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double m2 = accr[tj][r] * accr[tj][r] + acci[tj][r] * acci[tj][r];
+                    const double w = chi_pair_weight(ea[r], fav[r], gav[r], eb, fbv, gbv, inv_t);
+                    sum += (a_in[r] && c_in) ? w * m2 : 0.0;
+                }
+            }
+        }
+    }
+    sum = chi_wave_sum(sum);
+    if (BT == 1) {
+        if (valid && lane == 0) part[(size_t)ql * g.nk + k] = sum;
+    } else {
+        if (lane == 0) wave_part[wave] = sum;
+        __syncthreads();
+        if (tid == 0) part[((size_t)ql * g.nk + k) * blocks + blockIdx.y] = ((wave_part[0] + wave_part[1]) + wave_part[2]) + wave_part[3];
+    }
+}
+
+// |M|^2 = 1: a wave per (k, q), the n^2 pairs of states in lane-strided order.  grid: (k-points / 4, 1, vectors of the batch)
+__global__ void __launch_bounds__(CHI_THREADS) chi_pair_kernel(const double* __restrict__ E, const double* __restrict__ tab, ChiMesh g, int n,
+                                                               const int32_t* __restrict__ Q, double inv_t, double* __restrict__ part) {
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    const int64_t k = (int64_t)blockIdx.x * 4 + wave;
+    const int64_t ql = blockIdx.z;
+    const bool valid = k < g.nk;
+    double sum = 0.0;
+    if (valid) {
+        const int64_t kp = chi_shifted(g, k, Q + ql * 3);
+        const int64_t items = g.nk * n;
+        const double *Ea = E + (size_t)k * n, *Eb = E + (size_t)kp * n;
+        const double *fa = tab + (size_t)k * n, *ga = fa + items, *fb = tab + (size_t)kp * n, *gb = fb + items;
+        const int64_t pairs = (int64_t)n * n;
+        for (int64_t p = lane; p < pairs; p += 64) {
+            const int a = (int)(p / n), b = (int)(p - (int64_t)a * n);
+            sum += chi_pair_weight(Ea[a], fa[a], ga[a], Eb[b], fb[b], gb[b], inv_t);
+        }
+    }
+    sum = chi_wave_sum(sum);
+    if (valid && lane == 0) part[(size_t)ql * g.nk + k] = sum;
+}
+
+// chi[q] = (the len partials of q: thread t its contiguous piece in index order, then the threads in a fixed tree) / T / NK
+__global__ void __launch_bounds__(CHI_THREADS) chi_reduce_kernel(const double* __restrict__ part, int64_t len, double T, double nk,
+                                                                 double* __restrict__ chi) {
+    __shared__ double red[CHI_THREADS];
+    const int tid = (int)threadIdx.x;
+    const double* p = part + (size_t)blockIdx.x * len;
+    const int64_t piece = (len + CHI_THREADS - 1) / CHI_THREADS;
+    const int64_t lo = tid * piece < len ? tid * piece : len, hi = lo + piece < len ? lo + piece : len;
+    double acc = 0.0;
+    for (int64_t i = lo; i < hi; ++i) acc += p[i];
+    red[tid] = acc;
+    __syncthreads();
+    for (int s = CHI_THREADS / 2; s >= 1; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) chi[blockIdx.x] = red[0] / T / nk;
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------------
+int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, bool matrix_elements, size_t mem, ChiPlan* out) {
+    ChiPlan L;
+    L.mesh.n[0] = mesh[0];
+    L.mesh.n[1] = mesh[1];
+    L.mesh.n[2] = dim == 3 ? mesh[2] : 1;
+    L.mesh.nk = nk;
+    L.n = n_orb;
+    TBK_ARG(nk <= CHI_MAX_NK, "the susceptibility takes meshes of up to 2^23 points");
+    chi_plan_sizes(nk, n_orb, n_q, matrix_elements, mem, &L.bt, &L.blocks, &L.batch, &L.batches);
+    if (L.batch < 1) {
+        tbk_set_error("the partial sums of one susceptibility vector need %zu bytes of device memory",
+                      (size_t)nk * (size_t)L.blocks * sizeof(double));
+        return TBK_ERR_MEMORY;
+    }
+    *out = L;
+    return TBK_OK;
+}
+
+// q[n_q][dim] reduced to [0, n_d) per axis, three entries per vector
+int chi_reduce_q(int dim, const int32_t* mesh, int64_t n_q, const int64_t* q, std::vector<int32_t>* out) {
+    try {
+        out->assign((size_t)n_q * 3, 0);
+    } catch (...) {
+        tbk_set_error("cannot allocate the reduced vectors");
+        return TBK_ERR_MEMORY;
+    }
+    for (int64_t r = 0; r < n_q; ++r)
+        for (int d = 0; d < dim; ++d) {
+            const int64_t nd = mesh[d];
+            (*out)[(size_t)r * 3 + d] = (int32_t)(((q[r * dim + d] % nd) + nd) % nd);
+        }
+    return TBK_OK;
+}
+
+// D[n_q][n_orb] of convention 1: exp(-2 pi i sum_d q_d pos[i][d] / n_d), the unreduced q_d (tools/chi_model.py phase_table)
+int chi_phase_table(int dim, const int32_t* mesh, int n_orb, int64_t n_q, const int64_t* q, const double* pos, std::vector<double>* out) {
+    try {
+        out->resize((size_t)n_q * n_orb * 2);
+    } catch (...) {
+        tbk_set_error("cannot allocate the orbital phases");
+        return TBK_ERR_MEMORY;
+    }
+    const double two_pi = 6.283185307179586476925286766559;
+    for (int64_t r = 0; r < n_q; ++r)
+        for (int i = 0; i < n_orb; ++i) {
+            double angle = 0.0;
+            for (int d = 0; d < dim; ++d) angle = angle + ((double)q[r * dim + d] * pos[(size_t)i * dim + d]) / (double)mesh[d];
+            angle = -two_pi * angle;
+            (*out)[((size_t)r * n_orb + i) * 2] = std::cos(angle);
+            (*out)[((size_t)r * n_orb + i) * 2 + 1] = std::sin(angle);
+        }
+    return TBK_OK;
+}
+
+int chi_launch_fermi(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_E, double mu, double T, double* d_tab) {
+    const int64_t items = L.mesh.nk * L.n;
+    if (ev) ev->start(0);
+    hipLaunchKernelGGL(chi_fermi_kernel, dim3((unsigned)((items + CHI_THREADS - 1) / CHI_THREADS)), dim3(CHI_THREADS), 0, s, d_E, items, mu, T,
+                       d_tab);
+    if (ev) ev->stop();
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// nq vectors (at most L.batch): d_Q their reduced entries, d_D their phases (or NULL), d_chi their results
+int chi_launch_batch(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, const double* d_tab,
+                     const int32_t* d_Q, const double* d_D, int64_t nq, double T, double* d_part, double* d_chi) {
+    const double inv_t = 1.0 / T;
+    const int64_t nk = L.mesh.nk;
+    if (ev) ev->start(1);
+    if (L.bt == 0) {
+        hipLaunchKernelGGL(chi_pair_kernel, dim3((unsigned)((nk + 3) / 4), 1, (unsigned)nq), dim3(CHI_THREADS), 0, s, d_E, d_tab, L.mesh, L.n, d_Q,
+                           inv_t, d_part);
+    } else if (L.bt == 1) {
+        hipLaunchKernelGGL(chi_overlap_kernel<1>, dim3((unsigned)((nk + 3) / 4), 1, (unsigned)nq), dim3(CHI_THREADS), 0, s,
+                           reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q, reinterpret_cast<const double2*>(d_D), inv_t,
+                           L.blocks, d_part);
+    } else {
+        hipLaunchKernelGGL(chi_overlap_kernel<4>, dim3((unsigned)nk, (unsigned)L.blocks, (unsigned)nq), dim3(CHI_THREADS), 0, s,
+                           reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q, reinterpret_cast<const double2*>(d_D), inv_t,
+                           L.blocks, d_part);
+    }
+    if (ev) ev->stop();
+    TBK_HIP(hipGetLastError());
+    if (ev) ev->start(2);
+    hipLaunchKernelGGL(chi_reduce_kernel, dim3((unsigned)nq), dim3(CHI_THREADS), 0, s, d_part, nk * L.blocks, T, (double)nk, d_chi);
+    if (ev) ev->stop();
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// all batches of n_q vectors whose reduced entries (and phases) are on the device; d_chi[n_q]
+int chi_launch_all(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, double* d_tab, const int32_t* d_Q,
+                   const double* d_D, int64_t n_q, double mu, double T, double* d_part, double* d_chi) {
+    TBK_CHECK(chi_launch_fermi(s, L, ev, d_E, mu, T, d_tab));
+    for (int64_t q0 = 0; q0 < n_q; q0 += L.batch) {
+        const int64_t nq = std::min(L.batch, n_q - q0);
+        TBK_CHECK(chi_launch_batch(s, L, ev, d_U, d_E, d_tab, d_Q + q0 * 3, d_D ? d_D + (size_t)q0 * L.n * 2 : nullptr, nq, T, d_part,
+                                   d_chi + q0));
+    }
+    return TBK_OK;
+}
+
+int chi_check(double T, int64_t n_q, const int64_t* q, const double* chi_out, int n_orb) {
+    TBK_ARG(std::isfinite(T) && T > 0.0, "the temperature is not finite or not positive");
+    TBK_ARG(n_q >= 1, "n_q < 1");
+    TBK_ARG(q != nullptr && chi_out != nullptr, "q / chi is NULL");
+    TBK_ARG(n_orb >= 1 && n_orb <= CHI_MAX_ORB, "n_orb < 1 or more than 16320 orbitals");
+    return TBK_OK;
+}
+
+// a reservation whose failure names the bytes
+int chi_reserve(DevBuf& buf, size_t bytes, const char* what) {
+    const int r = buf.reserve(bytes);
+    if (r == TBK_ERR_MEMORY) tbk_set_error("the susceptibility keeps %s in device memory: %zu bytes do not fit", what, bytes);
+    return r;
+}
+
+// Waits for what a call has enqueued on its handles' streams when the call ends, however it ends (tbk_dm.hip: DmDrain).
+struct ChiDrain {
+    std::vector<tbk_model*> used;
+    ~ChiDrain() {
+        for (tbk_model* m : used)
+            if (hipSetDevice(m->device) == hipSuccess) (void)hipStreamSynchronize(m->stream);
+    }
+};
+
+}  // namespace
+
+extern "C" int tbk_chi_plan(int64_t nk, int n_orb, int64_t n_q, int matrix_elements, int64_t part_bytes, int64_t* out) {
+    TBK_ARG(nk >= 1 && n_orb >= 1 && n_orb <= CHI_MAX_ORB && n_q >= 1 && part_bytes >= 0 && out != nullptr,
+            "nk / n_orb / n_q < 1, more than 16320 orbitals, part_bytes < 0 or out is NULL");
+    int bt = 0;
+    chi_plan_sizes(nk, n_orb, n_q, matrix_elements != 0, (size_t)part_bytes, &bt, &out[1], &out[2], &out[3]);
+    out[0] = bt;
+    return TBK_OK;
+}
+
+extern "C" int tbk_chi_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu, double T,
+                                        int64_t n_q, const int64_t* q, const double* phases, double* chi_out) {
+    int64_t nk = 0;
+    TBK_CHECK(tetra_check_mesh(dim, mesh, OCC_MESH, &nk));
+    TBK_ARG(E != nullptr, "E is NULL");
+    TBK_ARG(std::isfinite(mu), "the chemical potential is not finite");
+    TBK_CHECK(chi_check(T, n_q, q, chi_out, n_orb));
+    TBK_ARG(U != nullptr || phases == nullptr, "phases without eigenvectors");
+    TBK_CHECK(tetra_check_device(device));
+    ChiPlan L;
+    TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, n_q, U != nullptr, 0, &L));
+    std::vector<int32_t> h_Q;
+    TBK_CHECK(chi_reduce_q(dim, mesh, n_q, q, &h_Q));
+    const size_t e_bytes = (size_t)nk * n_orb * sizeof(double), u_bytes = (size_t)nk * n_orb * n_orb * sizeof(double2);
+    const size_t d_bytes = (size_t)n_q * n_orb * sizeof(double2);
+    DevBuf d_E, d_U, d_tab, d_Q, d_D, d_part, d_chi;
+    TBK_CHECK(d_E.reserve(e_bytes));
+    TBK_CHECK(d_tab.reserve(2 * e_bytes));
+    if (U) TBK_CHECK(chi_reserve(d_U, u_bytes, "the eigenvectors of the whole mesh"));
+    TBK_CHECK(d_Q.reserve(h_Q.size() * sizeof(int32_t)));
+    if (phases) TBK_CHECK(d_D.reserve(d_bytes));
+    TBK_CHECK(d_part.reserve(L.part_bytes()));
+    TBK_CHECK(d_chi.reserve((size_t)n_q * sizeof(double)));
+    TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
+    if (U) TBK_HIP(hipMemcpy(d_U.ptr, U, u_bytes, hipMemcpyHostToDevice));
+    TBK_HIP(hipMemcpy(d_Q.ptr, h_Q.data(), h_Q.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (phases) TBK_HIP(hipMemcpy(d_D.ptr, phases, d_bytes, hipMemcpyHostToDevice));
+    TBK_CHECK(chi_launch_all(nullptr, L, nullptr, d_U.as<double>(), d_E.as<double>(), d_tab.as<double>(), d_Q.as<int32_t>(),
+                             phases ? d_D.as<double>() : nullptr, n_q, mu, T, d_part.as<double>(), d_chi.as<double>()));
+    TBK_HIP(hipMemcpy(chi_out, d_chi.ptr, (size_t)n_q * sizeof(double), hipMemcpyDeviceToHost));
+    return TBK_OK;
+}
+
+extern "C" int tbk_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
+                                        int64_t n_q, const int64_t* q, int matrix_elements, int convention, const double* pos, double* mu_out,
+                                        double* chi_out) {
+    TBK_ARG(mu_out != nullptr, "mu is NULL");
+    TBK_ARG(mode == 0 || mode == 1, "mode must be 0 (value = energy) or 1 (value = n_electrons)");
+    TBK_ARG(handles != nullptr && n_handles >= 1 && handles[0] != nullptr, "no handles");
+    TBK_CHECK(chi_check(T, n_q, q, chi_out, handles[0]->n_orb));
+    TBK_CHECK(tbk_eigh_check_arguments(0, convention, pos));
+    if (mode == 1)
+        TBK_CHECK(tbk_fermi_check_electrons(value, handles[0]->n_orb));
+    else
+        TBK_ARG(std::isfinite(value), "the energy is not finite");
+    // mu: the slab route of tbk_occupations as it stands
+    OccStaged staged;
+    TBK_CHECK(staged.make(handles, n_handles, mesh));
+    TBK_CHECK(staged.find_mu(mesh, mode, value, mu_out));
+    const double mu = mu_out[0];
+    const int n_orb = staged.n_orb, dim = staged.dim;
+    const int64_t nk = staged.nk_total;
+    const bool with_u = matrix_elements != 0, with_d = with_u && convention == 1;
+    std::vector<int32_t> h_Q;
+    TBK_CHECK(chi_reduce_q(dim, mesh, n_q, q, &h_Q));
+    std::vector<double> h_D, h_k;
+    if (with_d) TBK_CHECK(chi_phase_table(dim, mesh, n_orb, n_q, q, pos, &h_D));
+    TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, 0, mesh[0], &h_k));
+    // every handle holds the whole mesh's eigensystem and takes a contiguous share of the vectors
+    const TetraSlabs share(n_q, n_handles);
+    const size_t e_bytes = (size_t)nk * n_orb * sizeof(double), nn2 = (size_t)n_orb * n_orb * 2;
+    std::vector<SpanRecorder> ev((size_t)share.busy());
+    ChiDrain drain;
+    for (int i = 0; i < share.busy(); ++i) {
+        tbk_model* m = handles[i];
+        const int64_t q_lo = share.lo(i), q_n = share.count(i);
+        TBK_CHECK(tbk_eig_check_option(m));
+        TBK_HIP(hipSetDevice(m->device));
+        drain.used.push_back(m);
+        ev[(size_t)i] = SpanRecorder(m->timing, m->stream);
+        TBK_CHECK(m->ws_chi_k.reserve(h_k.size() * sizeof(double)));
+        TBK_CHECK(chi_reserve(m->ws_chi_e, 3 * e_bytes, "the eigenvalues and Fermi tables of the whole mesh"));
+        if (with_u) TBK_CHECK(chi_reserve(m->ws_chi_u, (size_t)nk * nn2 * sizeof(double), "the eigenvectors of the whole mesh"));
+        TBK_CHECK(m->ws_chi_q.reserve((size_t)q_n * (3 * sizeof(int32_t) + sizeof(double) + (with_d ? n_orb * sizeof(double2) : 0)) + 256));
+        // the batch from the memory that is left for the partials, the chunk of the eigenvector walk from what is left then
+        size_t free_b = 0, total_b = 0;
+        TBK_HIP(hipMemGetInfo(&free_b, &total_b));
+        ChiPlan L;
+        TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, q_n, with_u, std::max<size_t>(1, std::min(CHI_PART_BUDGET, std::max(m->ws_chi_part.bytes, free_b / 4))), &L));
+        TBK_CHECK(m->ws_chi_part.reserve(L.part_bytes()));
+        double* d_k = m->ws_chi_k.as<double>();
+        double* d_E = m->ws_chi_e.as<double>();
+        double* d_U = m->ws_chi_u.as<double>();
+        // ws_chi_q: the results, 256-byte aligned behind them the phases, then the reduced vectors
+        double* d_chi = m->ws_chi_q.as<double>();
+        char* behind = m->ws_chi_q.as<char>() + dos_align256((size_t)q_n * sizeof(double));
+        double* d_D = with_d ? reinterpret_cast<double*>(behind) : nullptr;
+        int32_t* d_Q = reinterpret_cast<int32_t*>(behind + (with_d ? (size_t)q_n * n_orb * sizeof(double2) : 0));
+        TBK_HIP(hipMemcpyAsync(d_k, h_k.data(), h_k.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
+        TBK_HIP(hipMemcpyAsync(d_Q, h_Q.data() + q_lo * 3, (size_t)q_n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+        if (with_d)
+            TBK_HIP(hipMemcpyAsync(d_D, h_D.data() + (size_t)q_lo * n_orb * 2, (size_t)q_n * n_orb * sizeof(double2), hipMemcpyHostToDevice,
+                                   m->stream));
+        if (with_u) {
+            // eigh's own E, so that E and U belong together
+            const int64_t chunk = OccStaged::chunk_of(m, nk);
+            for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
+                const int64_t nkc = std::min(chunk, nk - c0);
+                TBK_CHECK(tbk_eigh_device(m, d_k + c0 * dim, nkc, 2, nullptr, d_E + (size_t)c0 * n_orb, d_U + (size_t)c0 * nn2));
+            }
+        } else {
+            TBK_CHECK(tbk_eigenval_device_hint(m, d_k, h_k.data(), nk, d_E));
+        }
+        TBK_CHECK(chi_launch_all(m->stream, L, &ev[(size_t)i], d_U, d_E, d_E + (size_t)nk * n_orb, d_Q, d_D, q_n, mu, T,
+                                 m->ws_chi_part.as<double>(), d_chi));
+        TBK_HIP(hipMemcpyAsync(chi_out + q_lo, d_chi, (size_t)q_n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+    }
+    // synchronises every handle (the eigensolver's flags are reported as by tbk_eigh) and books the kernel times
+    for (tbk_model* m : drain.used) TBK_CHECK(tbk_eigenval_check(m));
+    for (size_t i = 0; i < drain.used.size(); ++i) {
+        tbk_model* m = drain.used[i];
+        TBK_HIP(hipSetDevice(m->device));
+        TBK_HIP(hipStreamSynchronize(m->stream));
+        ev[i].collect(m->timed[TIMED_CHI].ms);
+        m->timed[TIMED_CHI].calls += 1;
+    }
+    return TBK_OK;
+}
+
+extern "C" int tbk_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q,
+                                  int matrix_elements, int convention, const double* pos, double* mu_out, double* chi_out) {
+    return tbk_susceptibility_multi(&m, 1, mesh, mode, value, T, n_q, q, matrix_elements, convention, pos, mu_out, chi_out);
+}
+
+extern "C" int tbk_chi_timing(tbk_model* m, double* ms, int64_t* calls, int reset) {
+    TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr, "model / ms / calls is NULL");
+    return tbk_timed_read(m, TIMED_CHI, 3, ms, calls, nullptr, reset);
+}

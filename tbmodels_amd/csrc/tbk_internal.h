@@ -178,10 +178,10 @@ struct SpanRecorder {
 };
 
 // The sums the mesh calls book their kernel times on, one row per family (tbk_dos_timing, tbk_pdos_timing, tbk_fermi_timing,
-// tbk_occ_timing, tbk_dm_timing: what each counts differs and is listed in DESIGN.md section 10)
-enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_COUNT };
+// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing: what each counts differs and is listed in DESIGN.md section 10)
+enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_COUNT };
 struct TimedSums {
-    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ and dm three)
+    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm and chi three)
     int64_t calls = 0;
     int64_t passes = 0;  // fermi: the passes of its searches
 };
@@ -343,6 +343,11 @@ struct tbk_model {
     DevBuf ws_dm_p;      // ... the projectors of one k chunk, [table columns][n_orb][n_orb] complex
     DevBuf ws_dm_part;   // ... the k slices' partial rho [slices][n_r padded to 16][n_orb][n_orb] complex, resident across the chunks
     DevBuf ws_dm_rho;    // ... their sum [n_r][n_orb][n_orb] complex (more than one slice)
+    DevBuf ws_chi_k;     // tbk_susceptibility (tbk_chi.hip): the k list of the whole mesh [NK][dim]
+    DevBuf ws_chi_e;     // ... the resident eigenvalues of the whole mesh [NK][n_orb], behind them the Fermi tables f, 1 - f [2][NK][n_orb]
+    DevBuf ws_chi_u;     // ... the resident eigenvectors of the whole mesh [NK][n_orb][n_orb] complex (with matrix elements)
+    DevBuf ws_chi_q;     // ... this handle's vectors: chi [n_q], 256-byte aligned the phases D [n_q][n_orb] complex (convention 1), the reduced q int32 [n_q][3]
+    DevBuf ws_chi_part;  // ... the partial sums of one batch of vectors [batch][NK][blocks]
     std::vector<EventSpan> events;  // StageTimer's spans, read by tbk_get_timing (no synchronisation on the pipeline's path)
     double t_ms[TBK_T_COUNT] = {0, 0, 0, 0};
     int64_t t_n[TBK_T_COUNT] = {0, 0, 0, 0};

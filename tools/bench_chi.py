@@ -1,0 +1,111 @@
+"""
+Model.susceptibility measurements: prints one table.
+
+For the silicon model on a 32^3 mesh and a synthetic dense model of 64 orbitals and 64 lattice vectors on a 24^3 mesh, each with
+NQ = 1, 16 and 128 vectors q_j = (j, 0, 0), j = 1 .. NQ (a straight line; beyond the mesh it wraps, which costs the same), with
+matrix elements, best of --reps after a warm-up:
+
+1. wall time of Model.susceptibility;
+2. the three stages of tbk_chi_timing per call: the Fermi tables, the overlaps with their epilogue, the reduction; and the rest of
+   the call (wall time minus the stages: eigenvalues and mu by the slab route, then the eigensystem of the whole mesh);
+3. the overlap stage's executed flops, 8 n_pad^3 per (k, q) pair with n_pad = n rounded up to 16, over its time, as a fraction of
+   tbk_mfma_f64_peak of the same run;
+4. the only route to the same numbers without this call: Model.eigh of the mesh to the host and tools/chi_model.py.  Both are
+   TIMED ON THE FIRST TWO PLANES of the mesh (the model on those planes as a periodic mesh of their own, at most two vectors) AND
+   SCALED to the mesh and to NQ, and printed as such.
+
+    python tools/bench_chi.py [--reps 3] [--filling 0.3] [--temperature 0.05] [--quick]
+"""
+
+import argparse
+import ctypes
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import tbmodels_amd  # noqa: E402  pylint: disable=wrong-import-position
+from tbmodels_amd import _lib, synthetic  # noqa: E402  pylint: disable=wrong-import-position
+import chi_model  # noqa: E402  pylint: disable=wrong-import-position
+import dos_model  # noqa: E402  pylint: disable=wrong-import-position
+
+
+def _best(call, reps):
+    times = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = call()
+        times.append(time.perf_counter() - t0)
+    return min(times), out
+
+
+def measure(name, model, mesh, counts, filling, T, reps, peak_tflops):
+    lib = _lib.lib()
+    n, n_k = model.size, int(np.prod(mesh))
+    n_el = filling * n
+    n_pad = (n + 15) // 16 * 16
+    handle = model._staged()
+    ms, calls = (ctypes.c_double * 3)(), ctypes.c_int64(0)
+
+    # the host route on two planes: their eigensystem, then the model on them as a mesh of their own
+    kpts = np.ascontiguousarray(dos_model.mesh_kpoints(mesh))
+    plane = int(np.prod(mesh[1:]))
+    sub_mesh = (2,) + tuple(mesh[1:])
+    model.eigh(kpts[:plane])
+    t_eigh, (eig2, vec2) = _best(lambda: model.eigh(kpts[:2 * plane]), max(1, reps - 1))
+
+    for n_q in counts:
+        q = np.zeros((n_q, len(mesh)), dtype=np.int64)
+        q[:, 0] = np.arange(1, n_q + 1)
+        model.susceptibility(mesh, q, temperature=T, n_electrons=n_el)  # warm-up
+        t_call, result = _best(lambda: model.susceptibility(mesh, q, temperature=T, n_electrons=n_el), reps)
+        _lib.check(lib.tbk_model_set_option(handle, _lib.TBK_OPT_TIMING, 1))
+        _lib.check(lib.tbk_chi_timing(handle, ms, ctypes.byref(calls), 1))
+        for _ in range(reps):
+            model.susceptibility(mesh, q, temperature=T, n_electrons=n_el)
+        _lib.check(lib.tbk_chi_timing(handle, ms, ctypes.byref(calls), 1))
+        model.timing(reset=True)
+        _lib.check(lib.tbk_model_set_option(handle, _lib.TBK_OPT_TIMING, 0))
+        stages = [x / max(1, calls.value) for x in ms]
+        flops = 8.0 * n_pad ** 3 * n_k * n_q
+        fraction = flops / (stages[1] * 1e-3) / (peak_tflops * 1e12) if stages[1] > 0 else float("nan")
+        few = min(n_q, 2)
+        t_model, _ = _best(lambda: chi_model.susceptibility(eig2, vec2, sub_mesh, q[:few], result.mu.mu, T), max(1, reps - 1))
+        t_host = (t_eigh + t_model / few * n_q) / 2 * mesh[0]
+        print("| %s | %s | %d | %d | %.1f | %.1f | %.3f | %.3f | %.3f | %.3f | %.1f |"
+              % (name, "x".join(str(x) for x in mesh), n, n_q, t_call * 1e3, t_call * 1e3 - sum(stages), stages[0], stages[1], stages[2], fraction,
+                 t_host * 1e3))
+        print("  (%s NQ = %d: mu = %.12g, chi(q_1) = %.12g, min chi = %.6g)" % (name, n_q, result.mu.mu, result.chi[0], result.chi.min()))
+        sys.stdout.flush()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--filling", type=float, default=0.3, help="electrons per orbital")
+    ap.add_argument("--temperature", type=float, default=0.05, help="k_B T in the model's energy units")
+    ap.add_argument("--quick", action="store_true", help="small meshes and lists (a smoke run of the tool)")
+    args = ap.parse_args()
+    tf = ctypes.c_double(0.0)
+    _lib.check(_lib.lib().tbk_mfma_f64_peak(0, ctypes.byref(tf)))
+    print("FP64 MFMA peak: %.1f TFLOP/s" % tf.value)
+    print("| model | mesh | orbitals | NQ | Model.susceptibility ms | of it outside the chi kernels (eigenvalues, mu, eigensystem) ms | Fermi tables ms "
+          "| overlaps + epilogue ms | reduction ms | overlap stage / MFMA peak | today: Model.eigh to the host + tools/chi_model.py ms (two planes, "
+          "at most two vectors, scaled) |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|")
+    counts = (1, 4) if args.quick else (1, 16, 128)
+    data = np.load(os.path.join(ROOT, "tests", "golden", "silicon.npz"))
+    silicon = tbmodels_amd.Model.from_packed(data["R"], data["hop"], pos=data["pos"])
+    measure("silicon", silicon, (8,) * 3 if args.quick else (32,) * 3, counts, args.filling, args.temperature, args.reps, tf.value)
+    r_vec, hop, _ = synthetic.dense_model_arrays(64, 64, synthetic.MODEL_SEED + 2)
+    dense = tbmodels_amd.Model.from_packed(r_vec, hop)
+    measure("dense 64", dense, (6,) * 3 if args.quick else (24,) * 3, counts, args.filling, args.temperature, args.reps, tf.value)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,177 @@
+#!/usr/bin/env python3
+"""
+NumPy model of csrc/tbk_chi.hip: the bare (Lindhard) static susceptibility chi_0(q) of a uniform, periodic k mesh (DESIGN.md
+section 15).
+
+    M(k, q)[b][b'] = sum_i conj(U[k][i][b]) D(q)[i] U[k+q][i][b']
+    chi_0(q)       = -(1 / NK) sum_k sum_{b b'} F(E[k][b], E[k+q][b']) |M(k, q)[b][b']|^2
+    F(a, b)        = (f(a) - f(b)) / (a - b),   F(a, a) = f'(a),   f(x) = 1 / (1 + exp((x - mu) / T))
+
+``k+q`` is the mesh point with the indices (i_d + q_d) mod n_d, ``q`` an integer vector in mesh units (the wavevector is q_d / n_d),
+``U[k][i][b]`` component i of band b (convention 2) and ``D(q)`` the orbital phases of convention 1, ``exp(-2 pi i sum_d q_d pos[i][d]
+/ n_d)`` with the unreduced q_d, or 1.  Without matrix elements ``|M|^2 = 1``.
+
+F is never evaluated as the quotient, which cancels.  With the pair ordered lo <= hi and y = (lo - hi) / T <= 0,
+
+    F = -f(lo) (1 - f(hi)) h(y) / T,     h(y) = expm1(y) / y,  h(0) = 1
+
+f(x) from t = exp(-|x - mu| / T), 1 - f(x) as f(2 mu - x) from the same t (the mirrored distance from mu is -(x - mu)
+exactly): every factor is non-negative, nothing overflows, a = b is the same branch.
+
+`python tools/chi_model.py` prints one small case by the stable and by the naive F.  Design tooling: nothing in the product imports it.
+"""
+
+import itertools
+
+import numpy as np
+
+
+def fermi_tables(E, mu, T):
+    """(f(E), 1 - f(E)) as chi_fermi_kernel stores them per state: both from one t = exp(-|E - mu| / T), the second as f at the
+    mirrored energy 2 mu - E, whose distance from mu is -(E - mu) without a rounding."""
+    d = np.asarray(E, dtype=float) - mu
+    t = np.exp(-np.abs(d) / T)
+    small, big = t / (1.0 + t), 1.0 / (1.0 + t)
+    return np.where(d > 0.0, small, big), np.where(d < 0.0, small, big)
+
+
+def _h(y):
+    """expm1(y) / y with h(0) = 1, for y <= 0."""
+    y = np.asarray(y, dtype=float)
+    safe = np.where(y < 0.0, y, -1.0)
+    return np.where(y < 0.0, np.expm1(safe) / safe, 1.0)
+
+
+def pair_weight(a, b, fa, ga, fb, gb, T):
+    """f(lo) (1 - f(hi)) h((lo - hi) / T) >= 0 from the tables of both states: -T F(a, b)."""
+    a_low = a <= b
+    lo, hi = np.where(a_low, a, b), np.where(a_low, b, a)
+    return np.where(a_low, fa, fb) * np.where(a_low, gb, ga) * _h((lo - hi) / T)
+
+
+def pair_factor(a, b, mu, T):
+    """F(a, b) <= 0 in the stable form (broadcasts)."""
+    a, b = np.broadcast_arrays(np.asarray(a, dtype=float), np.asarray(b, dtype=float))
+    fa, ga = fermi_tables(a, mu, T)
+    fb, gb = fermi_tables(b, mu, T)
+    return -pair_weight(a, b, fa, ga, fb, gb, T) / T
+
+
+def pair_factor_naive(a, b, mu, T):
+    """The quotient as written (f' on the diagonal): for comparison where it is well conditioned."""
+    a, b = np.broadcast_arrays(np.asarray(a, dtype=float), np.asarray(b, dtype=float))
+    f = lambda x: 1.0 / (1.0 + np.exp((x - mu) / T))  # noqa: E731
+    same = a == b
+    diff = np.where(same, 1.0, a - b)
+    return np.where(same, -f(a) * (1.0 - f(a)) / T, (f(a) - f(b)) / diff)
+
+
+def mesh_indices(mesh):
+    """The index vectors of the mesh points in mesh order (last axis fastest), int64 [NK][dim]."""
+    mesh = [int(n) for n in mesh]
+    return np.array(list(itertools.product(*[range(n) for n in mesh])), dtype=np.int64).reshape(-1, len(mesh))
+
+
+def shifted_points(mesh, q):
+    """The flat index of k+q for every mesh point k, int64 [NK]."""
+    mesh = np.array([int(n) for n in mesh], dtype=np.int64)
+    q = np.mod(np.asarray(q).astype(np.int64), mesh)
+    moved = np.mod(mesh_indices(mesh) + q[None, :], mesh[None, :])
+    return np.ravel_multi_index(tuple(moved.T), tuple(int(n) for n in mesh))
+
+
+def phase_table(mesh, q, pos):
+    """D[NQ][n] of convention 1: exp(-2 pi i sum_d q_d pos[i][d] / n_d) with the unreduced q_d."""
+    mesh = np.array([float(n) for n in mesh])
+    q = np.asarray(q).astype(np.int64).reshape(-1, len(mesh))
+    angle = np.zeros((q.shape[0], np.asarray(pos).shape[0]))
+    for d in range(len(mesh)):
+        angle = angle + (q[:, d].astype(float)[:, None] * np.asarray(pos, dtype=float)[None, :, d]) / mesh[d]
+    angle = -2.0 * np.pi * angle
+    return np.cos(angle) + 1j * np.sin(angle)
+
+
+def overlaps(U, mesh, q, phases=None):
+    """M[NK][n][n] for ONE vector q: M[k][b][b'] = sum_i conj(U[k][i][b]) D[i] U[k+q][i][b'] (phases: D[n] or None)."""
+    n = np.asarray(U).shape[-1]
+    flat = np.asarray(U).reshape(-1, n, n)
+    other = flat[shifted_points(mesh, q)]
+    if phases is not None:
+        other = np.asarray(phases)[None, :, None] * other
+    return np.einsum("kib,kic->kbc", flat.conj(), other)
+
+
+def susceptibility(E, U, mesh, q, mu, T, matrix_elements=True, phases=None, factor=None):
+    """chi_0[NQ] for the integer vectors ``q`` of shape (NQ, dim).  ``E``: mesh + (n,) or (NK, n); ``U`` (not read without matrix
+    elements): mesh + (n, n) or (NK, n, n); ``phases``: None or D[NQ][n].  ``factor``: another F(a, b, mu, T) than the stable one."""
+    E = np.asarray(E, dtype=float)
+    n = E.shape[-1]
+    flat_e = E.reshape(-1, n)
+    n_k = flat_e.shape[0]
+    q = np.asarray(q)
+    if q.dtype.kind not in "iu":
+        raise ValueError("q must be integers")
+    q = q.astype(np.int64).reshape(-1, len(mesh))
+    f, g = fermi_tables(flat_e, mu, T)
+    out = np.zeros(q.shape[0])
+    for index, vector in enumerate(q):
+        to = shifted_points(mesh, vector)
+        a, b = flat_e[:, :, None], flat_e[to][:, None, :]
+        if factor is None:
+            weight = pair_weight(a, b, f[:, :, None], g[:, :, None], f[to][:, None, :], g[to][:, None, :], T)
+        else:
+            weight = -T * factor(a, b, mu, T)
+        if matrix_elements:
+            weight = weight * np.abs(overlaps(U, mesh, vector, None if phases is None else np.asarray(phases)[index])) ** 2
+        out[index] = weight.sum() / T / n_k
+    return out
+
+
+ULP_EXP = 2.0    # allowance, in ulps, for exp on one side against the exact value (the device's against NumPy's
+ULP_EXPM1 = 2.0  # was measured at most 1 ulp apart for either function over the arguments of the tests; twice that)
+
+
+def tolerance(n_k, n, T, matrix_elements=True):
+    """tol_chi of DESIGN.md 15.4: the bound on |chi - chi'| of two evaluations (the kernels, this model) of the SAME (E, U, mu, T),
+    each with IEEE double arithmetic in any order of summation and exp / expm1 within ULP_EXP / ULP_EXPM1 ulps.  With u = 2^-53,
+    per side and in units of 1 / T:  the sum of NK n^2 non-negative terms whose total is at most NK s, s = n / 4 (n^2 / 4 without
+    matrix elements: F in [-1 / (4 T), 0], the rows of |M|^2 add up to 1), divided by NK: NK n^2 s u;  the factors of a term,
+    relative: (4 ULP_EXP + ULP_EXPM1 + 15) s u;  the part of exp's argument error that grows with |E - mu| / T, absolute because
+    x exp(-x) <= 1 / e: 4 u per unit of |M|^2, 4 n u (4 n^2 u);  and |M|^2: an element of M is a sum of 2 n real products per
+    component whose moduli add up to at most 1 (and one complex multiply by D), |dM| <= (3 n + 5) u, so sum F |d(|M|^2)| <=
+    ((3 n + 5) n^(3/2) / 2 + 3 n / 4) u by sum |M| <= n^(3/2)."""
+    u = 2.0 ** -53
+    s = n / 4.0 if matrix_elements else n * n / 4.0
+    unit = n if matrix_elements else n * n
+    side = n_k * n * n * s + (4 * ULP_EXP + ULP_EXPM1 + 15) * s + 4 * unit
+    if matrix_elements:
+        side += (3 * n + 5) * n ** 1.5 / 2 + 0.75 * n
+    return 2.0 * side * u / T
+
+
+def static_limit(E, mu, T):
+    """chi_0(0) with matrix elements: (1 / NK) sum_{k b} f (1 - f) / T, from the eigenvalues alone."""
+    E = np.asarray(E, dtype=float)
+    f, g = fermi_tables(E, mu, T)
+    return float((f * g).sum() / T / (E.size // E.shape[-1]))
+
+
+def main():
+    rng = np.random.default_rng(7)
+    mesh, n, mu, T = (2, 3, 2), 5, 0.1, 0.05
+    n_k = int(np.prod(mesh))
+    hams = rng.normal(size=(n_k, n, n)) + 1j * rng.normal(size=(n_k, n, n))
+    eig, vec = np.linalg.eigh(hams + hams.conj().transpose(0, 2, 1))
+    q = np.array([[0, 0, 0], [1, 0, 0], [-1, 0, 0], [1, 2, 1], [3, 2, 1]])
+    for me in (True, False):
+        stable = susceptibility(eig, vec, mesh, q, mu, T, me)
+        naive = susceptibility(eig, vec, mesh, q, mu, T, me, factor=pair_factor_naive)
+        print("random 5-orbital model, mesh %s, mu = %g, T = %g, matrix elements: %s" % (mesh, mu, T, me))
+        for vector, s, v in zip(q, stable, naive):
+            print("    q = %-12s chi_0 = %.15f   naive F: %.15f   difference %.1e" % (tuple(int(x) for x in vector), s, v, abs(s - v)))
+    print("    chi_0(0) from the eigenvalues alone: %.15f" % static_limit(eig, mu, T))
+    print("    4 T chi_0 at T = 1e9 bandwidths: %s (n = %d)" % (4 * 1e9 * np.ptp(eig) * susceptibility(eig, vec, mesh, q[:2], mu, 1e9 * np.ptp(eig)), n))
+
+
+if __name__ == "__main__":
+    main()
