@@ -450,6 +450,46 @@ int tbk_chi_plan(int64_t nk, int n_orb, int64_t n_q, int matrix_elements, int64_
  * tbk_get_timing.) */
 int tbk_chi_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
+/* ---- the bare dynamic susceptibility chi_0(q, omega + i eta) of a uniform k mesh (not in the reference) --------------------------
+ * Mesh, k+q, q, E, U, D(q), matrix_elements, convention, mu (mode, value) and T are those of tbk_susceptibility.  With n_w real
+ * frequencies omega_j (any sign and order, duplicates allowed) and one broadening eta > 0 (csrc/tbk_chi.hip):
+ *     chi_0(q, z) = -(1 / NK) sum_k sum_{b b'} (f(E[k][b]) - f(E[k+q][b'])) / (E[k][b] - E[k+q][b'] + z) |M(k, q)[b][b']|^2,  z = omega + i eta
+ * No spin factor; the sign is the static call's: Re chi_0(q, i eta) -> chi_0(q) as eta -> 0, less the f' terms of exactly degenerate
+ * pairs, which the dynamic function does not have.  The occupation difference is evaluated as g = +-f(lo) (1 - f(hi)) (-expm1(y)),
+ * lo <= hi, y = (lo - hi) / T, from the static call's tables, + where E[k][b] <= E[k+q][b'] (no cancellation, no overflow, a zero for
+ * equal energies); per pair p = g |M|^2 and Delta = E[k][b] - E[k+q][b'] once, per frequency x = Delta + omega, r = 1 / (x^2 + eta^2),
+ * Re -= p x r, Im += p eta r, over NK.  chi_0(-q, -omega + i eta) = conj chi_0(q, omega + i eta); for given (E, U, mu, T, eta) the
+ * bits of chi_0(q, omega_j + i eta) depend on q modulo the mesh, D(q) and omega_j alone -- not on the other vectors or frequencies,
+ * their order, the batches, the frequency passes or the number of handles -- and repeated calls give the same bits.  |error| of
+ * either component <= the bound of DESIGN.md 16.4.
+ * omega: double [n_w]; chi_out: [n_q][n_w] complex (Re, Im interleaved).  Argument errors (TBK_ERR_ARGUMENT), before any device is
+ * touched: those of tbk_susceptibility, n_w < 1, more than 2^23 frequencies (one grid column of the reduction each), a NULL omega,
+ * a frequency that is not finite, eta not finite or not positive (or so small that its square underflows to 0). */
+
+/* The kernels alone on an eigensystem the caller brings (E, U, phases as for tbk_chi_from_eigensystem).  part_bytes: the bytes the
+ * partial sums may take (0: the library's budget), as in tbk_chi_dynamic_plan. */
+int tbk_chi_dynamic_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu, double T,
+                                     int64_t n_q, const int64_t* q, const double* phases, int64_t n_w, const double* omega, double eta,
+                                     int64_t part_bytes, double* chi_out);
+/* The whole call: tbk_susceptibility's driver -- the same mu, the same resident eigensystem, the same wait on every exit -- with the
+ * frequencies in device memory and the dynamic epilogue, pair kernel and reduction in place of the static ones. */
+int tbk_dynamic_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q, int64_t n_w,
+                               const double* omega, double eta, int matrix_elements, int convention, const double* pos, double* mu_out,
+                               double* chi_out);
+/* On several devices from one process: tbk_susceptibility_multi's split, a contiguous share of the vectors (with all frequencies) per
+ * handle. */
+int tbk_dynamic_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
+                                     int64_t n_q, const int64_t* q, int64_t n_w, const double* omega, double eta, int matrix_elements,
+                                     int convention, const double* pos, double* mu_out, double* chi_out);
+/* How a call on nk mesh points, n_q vectors and n_w frequencies is run: out[0], out[1] as for tbk_chi_plan; the partial sums take
+ * 16 nk out[1] bytes per (q, omega) and may take part_bytes (0: 256 MiB).  When all frequencies of one vector fit, out[4] = n_w,
+ * out[5] = 1 and out[2] = vectors per batch (at most 4096), out[3] = batches; else out[2] = 1, out[3] = n_q and the frequencies go in
+ * out[5] passes of out[4] (whole register chunks when one fits), the overlaps computed again in each.  out[2] = 0: not one (q, omega)
+ * fits.  out[6] = the frequencies per register chunk of the epilogue.  out: int64 [7]. */
+int tbk_chi_dynamic_plan(int64_t nk, int n_orb, int64_t n_q, int64_t n_w, int matrix_elements, int64_t part_bytes, int64_t* out);
+/* (Kernel times of these calls are booked into tbk_chi_timing's three stages: the Fermi tables, the overlaps with the dynamic
+ * epilogue or the dynamic pair kernel, the complex reduction; its call count includes them.) */
+
 /* ---- k.p models (kdotp.py:51-100): H(k) = sum_p prod_d k_d^powers[p][d] * coeffs[p] ------- */
 int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, const int32_t* powers,
                      const double* coeffs, tbk_kdotp** out);

@@ -45,6 +45,7 @@ FermiLevel = co.namedtuple("FermiLevel", ("mu", "lower", "upper", "nos"))
 Occupations = co.namedtuple("Occupations", ("mu", "orbital_occ", "band_occ", "band_energy"))
 DensityMatrix = co.namedtuple("DensityMatrix", ("mu", "R", "rho"))
 Susceptibility = co.namedtuple("Susceptibility", ("mu", "q", "chi"))
+DynamicSusceptibility = co.namedtuple("DynamicSusceptibility", ("mu", "q", "omega", "chi"))
 
 
 def _devices_from_env():
@@ -786,7 +787,7 @@ class Model:
         return (eig[0], vec[0]) if single else (eig, vec)
 
     def _mesh_argument(self, mesh, what="dos"):
-        """The mesh check ``dos``, ``pdos``, ``band_edges``, ``fermi_level``, ``tetra_weights``, ``occupations``, ``density_matrix`` and ``susceptibility`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
+        """The mesh check ``dos``, ``pdos``, ``band_edges``, ``fermi_level``, ``tetra_weights``, ``occupations``, ``density_matrix``, ``susceptibility`` and ``dynamic_susceptibility`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
         if self.dim not in (2, 3):
             raise ValueError("{} needs a 2- or 3-dimensional model, this one has dimension {}".format(what, self.dim))
         try:
@@ -1152,21 +1153,8 @@ class Model:
         complex numbers), else ``MemoryError``.  With several ``devices`` every device holds the whole mesh's eigensystem and
         takes a contiguous share of ``q``.
         """
-        mesh_array = self._mesh_argument(mesh, "susceptibility")
-        if q is None:
-            raise ValueError("q must be an integer array of shape (NQ, {}), got None".format(self.dim))
-        vectors = self._integer_vectors_argument(q, "q", "NQ")
-        if isinstance(temperature, (bool, np.bool_)) or not isinstance(temperature, (int, float, np.integer, np.floating)):
-            raise ValueError("temperature must be a real number, got {!r}".format(temperature))
-        t_value = float(temperature)
-        if not np.isfinite(t_value) or not t_value > 0.0:
-            raise ValueError("temperature must be finite and positive, got {!r}".format(temperature))
-        mode, value = self._occupation_argument("susceptibility", energy, n_electrons)
-        if convention not in [1, 2]:
-            raise ValueError("Invalid value '{}' for 'convention': must be either '1' or '2'".format(convention))
-        if not isinstance(matrix_elements, (bool, np.bool_)):
-            raise ValueError("matrix_elements must be True or False, got {!r}".format(matrix_elements))
-        pos = np.ascontiguousarray(self.pos, dtype=np.float64) if convention == 1 else None
+        mesh_array, vectors, t_value, mode, value, pos = self._susceptibility_arguments("susceptibility", mesh, q, temperature, energy, n_electrons,
+                                                                                        matrix_elements, convention)
         mu = np.empty(4, dtype=np.float64)
         chi = np.empty(vectors.shape[0], dtype=np.float64)
         with self._call_lock:
@@ -1178,6 +1166,113 @@ class Model:
                                                     _lib.ptr(mu), _lib.ptr(chi))
             )
         return Susceptibility(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, chi)
+
+    @staticmethod
+    def _positive_number_argument(value, name):
+        """``float`` from a finite, positive real number or ``ValueError`` (``temperature``, ``eta``)."""
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)):
+            raise ValueError("{} must be a real number, got {!r}".format(name, value))
+        number = float(value)
+        if not np.isfinite(number) or not number > 0.0:
+            raise ValueError("{} must be finite and positive, got {!r}".format(name, value))
+        return number
+
+    def _susceptibility_arguments(self, name, mesh, q, temperature, energy, n_electrons, matrix_elements, convention):
+        """The checks ``susceptibility`` and ``dynamic_susceptibility`` share, in one order and one wording: ``(mesh int32 (dim,),
+        q int64 (NQ, dim), temperature, mode, value, pos or None)`` or ``ValueError``."""
+        mesh_array = self._mesh_argument(mesh, name)
+        if q is None:
+            raise ValueError("q must be an integer array of shape (NQ, {}), got None".format(self.dim))
+        vectors = self._integer_vectors_argument(q, "q", "NQ")
+        t_value = self._positive_number_argument(temperature, "temperature")
+        mode, value = self._occupation_argument(name, energy, n_electrons)
+        if convention not in [1, 2]:
+            raise ValueError("Invalid value '{}' for 'convention': must be either '1' or '2'".format(convention))
+        if not isinstance(matrix_elements, (bool, np.bool_)):
+            raise ValueError("matrix_elements must be True or False, got {!r}".format(matrix_elements))
+        pos = np.ascontiguousarray(self.pos, dtype=np.float64) if convention == 1 else None
+        return mesh_array, vectors, t_value, mode, value, pos
+
+    def dynamic_susceptibility(self, mesh, q, omega, *, eta, temperature, energy=None, n_electrons=None, matrix_elements=True, convention=2):
+        """
+        The bare dynamic susceptibility ``chi_0(q, omega + i eta)`` of a uniform k mesh, computed on the GPU from the eigensystem
+        of the whole mesh, which never leaves it.  Not in the reference.
+
+        ``mesh``, ``q``, ``temperature``, ``energy``, ``n_electrons``, ``matrix_elements`` and ``convention`` are those of
+        :meth:`susceptibility`, with the same errors.  ``omega`` is a real array-like of shape ``(NW,)`` with ``NW >= 1`` or one
+        number: finite frequencies in the model's energy units, of any sign and order, duplicates allowed.  ``eta`` is one finite
+        broadening ``> 0``.  Returns the named tuple ``(mu, q, omega, chi)``: ``mu`` and ``q`` as for :meth:`susceptibility`,
+        ``omega`` as ``float64 (NW,)`` and ``chi`` as ``complex128 (NQ, NW)``.
+
+        Definition.  With ``E``, ``U``, ``k+q``, ``M(k, q)`` and ``f`` of :meth:`susceptibility` and ``z = omega + i eta``::
+
+            chi_0(q, z) = -(1 / NK) sum_k sum_{b, b'} (f(E[k, b]) - f(E[k+q, b'])) / (E[k, b] - E[k+q, b'] + z) |M(k, q)[b, b']|^2
+
+        No spin factor; the sign is the static call's, so ``Re chi_0(q, i eta) -> chi_0(q)`` as ``eta -> 0`` except for the ``f'``
+        terms of exactly degenerate pairs, which the dynamic function does not have.  ``mu`` is found as in
+        :meth:`susceptibility`.
+
+        The occupation difference is not formed as written: with the pair ordered ``lo <= hi`` and ``y = (lo - hi) / T``,
+        ``f(lo) - f(hi) = f(lo) (1 - f(hi)) (-expm1(y)) >= 0`` from the static call's two tables -- nothing cancels, nothing
+        overflows, equal energies give a zero -- and ``g`` is that value with the sign of the pair's order.  Per pair ``p = g |M|^2``
+        and ``Delta = E[k, b] - E[k+q, b']`` are computed once; per frequency ``x = Delta + omega``, ``r = 1 / (x^2 + eta^2)``,
+        ``Re chi -= p x r / NK``, ``Im chi += p eta r / NK``.  A frequency that hits a transition exactly (``x = 0``) is finite.
+
+        Properties, both conventions.  (1) ``chi_0(-q, -omega + i eta) = conj chi_0(q, omega + i eta)``.  (2) ``0 <= Re chi_0(q, i
+        eta) <= chi_0(q)`` of :meth:`susceptibility`: every term is the static term times ``Delta^2 / (Delta^2 + eta^2)``.  (3)
+        ``omega [Im chi_0(q, omega + i eta) + Im chi_0(-q, omega + i eta)] >= 0``: the absorptive part has one sign, pair by pair
+        (with this sign of ``chi_0``, ``Im chi_0 >= 0`` at positive frequencies where ``chi_0(-q) = chi_0(q)``).  (4) With matrix elements and ``convention=2``, ``chi_0(0, z) = 0``
+        for every ``z``: no intraband response at ``q = 0``.  (5) With ``mu`` 746 ``T`` or more below or above the spectrum every
+        entry is ``+0`` in both components.  (6) For ``convention=2`` ``q + n_d e_d`` has the bits of ``q``.  (7) The bits of
+        ``chi_0(q, omega_j + i eta)`` do not depend on the other vectors or frequencies, on their order or on the number of
+        ``devices``; duplicates have equal bits and a second call the bits of the first.
+
+        Error bound of either component for a given eigensystem, with ``u = 2^-53``, ``S = size`` (``size^2`` without matrix
+        elements), ``W`` the bandwidth and allowances of 2 for ``exp``, ``expm1`` and the quotient (DESIGN.md 16.4;
+        ``tools/chi_model.py`` ``dynamic_tolerance``); without matrix elements the last bracket is absent::
+
+            |error| <= 2 [ (NK size^2 + 34 + (2 W + |omega|) / eta) S + 2 (3 size + 5) size^(3/2) + 3 size ] u / eta
+
+        The term ``(2 W + |omega|) / eta^2`` is the rounding of ``Delta + omega`` under the slope of the Lorentzian: it is why a
+        broadening far below the level spacing of the mesh costs digits as well as meaning.
+
+        One-dimensional models raise ``ValueError``.  The eigenvectors of the whole mesh must fit the device (``NK size^2``
+        complex numbers), else ``MemoryError``.  The partial sums take ``16 NK ceil(size / 64)^2`` bytes per ``(q, omega)``; when
+        one vector's do not fit 256 MiB the frequencies go in passes and the overlaps are computed again in each.  With several
+        ``devices`` every device holds the whole mesh's eigensystem and takes a contiguous share of ``q`` with all frequencies.
+        """
+        mesh_array, vectors, t_value, mode, value, pos = self._susceptibility_arguments("dynamic_susceptibility", mesh, q, temperature, energy,
+                                                                                        n_electrons, matrix_elements, convention)
+        if omega is None or isinstance(omega, (str, bytes)):
+            raise ValueError("omega must be a real number or a real array of shape (NW,), got {!r}".format(omega))
+        try:
+            frequencies = np.asarray(omega)
+        except (TypeError, ValueError):
+            raise ValueError("omega must be a real number or a real array of shape (NW,)") from None
+        if frequencies.dtype.kind not in "iuf":
+            raise ValueError("omega must hold real numbers, got dtype {}".format(frequencies.dtype))
+        if frequencies.ndim == 0:
+            frequencies = frequencies.reshape(1)
+        if frequencies.ndim != 1 or frequencies.shape[0] < 1:
+            raise ValueError("omega must have shape (NW,) with NW >= 1, got {}".format(frequencies.shape))
+        frequencies = np.ascontiguousarray(frequencies, dtype=np.float64)
+        if not np.all(np.isfinite(frequencies)):
+            raise ValueError("omega must be finite")
+        eta_value = self._positive_number_argument(eta, "eta")
+        if not eta_value * eta_value > 0.0:
+            raise ValueError("eta must be finite and positive, got {!r} (its square underflows)".format(eta))
+        mu = np.empty(4, dtype=np.float64)
+        chi = np.empty((vectors.shape[0], frequencies.shape[0]), dtype=np.complex128)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_dynamic_susceptibility_multi(handles, n_handles, _lib.ptr(mesh_array), mode, value, t_value, vectors.shape[0],
+                                                            _lib.ptr(vectors), frequencies.shape[0], _lib.ptr(frequencies), eta_value,
+                                                            int(bool(matrix_elements)), int(convention), _lib.ptr(pos), _lib.ptr(mu),
+                                                            _lib.ptr(chi))
+            )
+        return DynamicSusceptibility(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, frequencies, chi)
 
     def construct_kdotp(self, k, order):
         """

@@ -26,6 +26,25 @@
 //
 // The q list goes in batches of tbk_chi_plan's size (the memory of `part`).  For given (E, U, mu, T) the bits of chi_0(q) depend on
 // q modulo the mesh and on D(q) alone: not on the batch, the other vectors, their order or the handle that computes them.
+//
+// The dynamic chi_0(q, omega_j + i eta) (chi_model.dynamic_susceptibility) takes the same overlaps and another
+// epilogue:
+//
+//   chi_0(q, z) = -(1 / NK) sum_k sum_{b b'} g / (Delta + z) |M|^2       g = f(E[k][b]) - f(E[k+q][b']) = +-f(lo) (1 - f(hi)) (-expm1(y)),
+//                                                                        Delta = E[k][b] - E[k+q][b'], + where E[k][b] <= E[k+q][b']
+//
+//   chi_overlap_kernel<BT, true>  keeps p = g |M|^2 and Delta of the lane's 4 BT elements in registers and walks the frequencies in
+//                       chunks of CHI_WC per-lane (Re, Im) accumulators: x = Delta + omega, r = 1 / (x^2 + eta^2), t = p r,
+//                       Re += t x, Im -= t eta, the lane's elements in register order, then the wave's lanes and the block's waves
+//                       as above: one complex partial in part[q][omega][k][block].  Every frequency of a chunk runs the same
+//                       instructions on its own accumulators (a short chunk is filled up with copies of its last frequency, which
+//                       are not stored), so the bits of one (q, omega) do not know its place in the chunk, the pass or the list.
+//   chi_pair_dyn_kernel the same with |M|^2 = 1, chi_pair_kernel's walk once per chunk.
+//   chi_reduce_dyn_kernel  chi[q][omega] = (0 - sum of part[q][omega][.][.] in chi_reduce_kernel's order) / NK per component: the
+//                       difference from +0 so that sums that are zeros of either sign give +0.
+//
+// Frequencies go in passes of tbk_chi_dynamic_plan's size when the partials of one vector for all of them do not fit; the overlaps
+// are computed again per pass.
 
 #include <algorithm>
 #include <cmath>
@@ -43,6 +62,8 @@ constexpr int64_t CHI_MAX_BATCH = 4096;                 // vectors per launch (g
 constexpr size_t CHI_PART_BUDGET = size_t(256) << 20;   // the partials of one batch, at most
 constexpr int64_t CHI_MAX_NK = int64_t(1) << 23;          // one grid column per k-point, 256 threads each
 constexpr int CHI_MAX_ORB = 16320;                      // 255 x 255 blocks of one M: one grid row each
+constexpr int CHI_WC = 8;                               // frequencies per chunk of the dynamic epilogue: 2 CHI_WC accumulators per lane
+constexpr int64_t CHI_MAX_NW = int64_t(1) << 23;          // one grid column of the dynamic reduction per frequency, 256 threads each
 
 struct ChiMesh {
     int n[3];    // (n[2] = 1 in two dimensions)
@@ -56,7 +77,20 @@ struct ChiPlan {
     int64_t blocks = 1;   // partials per (k, q)
     int64_t batch = 1;    // vectors per launch
     int64_t batches = 1;
-    size_t part_bytes() const { return (size_t)batch * mesh.nk * blocks * sizeof(double); }
+    int64_t n_w = 0;      // frequencies (0: the static call)
+    int64_t w_pass = 0;   // frequencies per launch
+    int64_t passes = 1;
+    size_t part_bytes() const {
+        return n_w == 0 ? (size_t)batch * mesh.nk * blocks * sizeof(double) : (size_t)batch * w_pass * mesh.nk * blocks * sizeof(double2);
+    }
+};
+
+// what the dynamic epilogue reads besides the static one's arguments (all zero: the static kernels)
+struct ChiDyn {
+    const double* W = nullptr;  // the frequencies of this launch [nw], device memory
+    int nw = 0;
+    double eta = 0.0;
+    double2* part = nullptr;    // [vectors of the batch][nw][NK][blocks]
 };
 
 // the one place that chooses: template, partials per pair, batch size from the bytes the partials may take (0: the budget)
@@ -68,6 +102,27 @@ void chi_plan_sizes(int64_t nk, int n_orb, int64_t n_q, bool matrix_elements, si
     const size_t per_q = (size_t)nk * (size_t)*blocks * sizeof(double);
     const size_t room = mem == 0 ? CHI_PART_BUDGET : mem;
     *batch = std::max<int64_t>(0, std::min<int64_t>(std::min(n_q, CHI_MAX_BATCH), (int64_t)(room / per_q)));
+    *batches = *batch == 0 ? 0 : (n_q + *batch - 1) / *batch;
+}
+
+// the dynamic call's: as above, with 16 NK blocks bytes per (q, omega).  All frequencies of a vector in one launch when they fit (then
+// as many vectors per batch as fit), else one vector per batch and the frequencies in passes (whole chunks of CHI_WC when one fits)
+void chi_dyn_plan_sizes(int64_t nk, int n_orb, int64_t n_q, int64_t n_w, bool matrix_elements, size_t mem, int* bt, int64_t* blocks,
+                        int64_t* batch, int64_t* batches, int64_t* w_pass, int64_t* passes) {
+    const int64_t nb = (n_orb + 63) / 64;
+    *bt = !matrix_elements ? 0 : n_orb <= 16 ? 1 : 4;
+    *blocks = *bt == 4 ? nb * nb : 1;
+    const size_t per_qw = (size_t)nk * (size_t)*blocks * sizeof(double2);
+    const size_t room = mem == 0 ? CHI_PART_BUDGET : mem;
+    const int64_t fit = (int64_t)std::min<size_t>(room / per_qw, (size_t)1 << 62);  // (q, omega) pairs whose partials fit
+    if (fit >= n_w) {
+        *w_pass = n_w;
+        *batch = std::min<int64_t>(std::min(n_q, CHI_MAX_BATCH), fit / n_w);
+    } else {
+        *w_pass = fit >= CHI_WC ? fit / CHI_WC * CHI_WC : fit;
+        *batch = fit >= 1 ? 1 : 0;
+    }
+    *passes = *w_pass == 0 ? 0 : (n_w + *w_pass - 1) / *w_pass;
     *batches = *batch == 0 ? 0 : (n_q + *batch - 1) / *batch;
 }
 
@@ -86,6 +141,23 @@ __device__ __forceinline__ double chi_pair_weight(double ea, double fa, double g
     const double y = (lo - hi) * inv_t;
     const double h = y < 0.0 ? expm1(y) / y : 1.0;  // (-inf: 0)
     return (a_low ? fa : fb) * (a_low ? gb : ga) * h;
+}
+
+// g = f(a) - f(b) of one pair of states, |g| <= 1: +-f(lo) (1 - f(hi)) (-expm1((lo - hi) / T)), + where a <= b; a zero for a == b
+__device__ __forceinline__ double chi_pair_difference(double ea, double fa, double ga, double eb, double fb, double gb, double inv_t) {
+    const bool a_low = ea <= eb;
+    const double lo = a_low ? ea : eb, hi = a_low ? eb : ea;
+    const double v = (a_low ? fa : fb) * (a_low ? gb : ga) * (-expm1((lo - hi) * inv_t));
+    return a_low ? v : -v;
+}
+
+// one pair of states at one frequency: re += t x, im -= t eta with t = p / (x^2 + eta^2), the multiply-adds fused as written
+__device__ __forceinline__ void chi_dyn_term(double p, double delta, double omega, double eta, double eta2, double& re, double& im) {
+    const double x = delta + omega;
+    const double r = 1.0 / fma(x, x, eta2);
+    const double t = p * r;
+    re = fma(t, x, re);
+    im = fma(-t, eta, im);
 }
 
 // all 64 lanes, the same tree whatever the values
@@ -110,11 +182,12 @@ __global__ void __launch_bounds__(CHI_THREADS) chi_fermi_kernel(const double* __
 
 // BT tiles of 16 along each side of the workgroup's block of M: 4 (one k-point per workgroup, wave t owns tile row t) or 1 (n <= 16:
 // four k-points per workgroup, one per wave).  grid: (k-points / KPW, blocks, vectors of the batch).  D: NULL or [batch][n] complex.
-template <int BT>
+// DYN: the dynamic epilogue (dyn, not part, is written).
+template <int BT, bool DYN>
 __global__ void __launch_bounds__(CHI_THREADS) chi_overlap_kernel(const double2* __restrict__ U, const double* __restrict__ E,
                                                                   const double* __restrict__ tab, ChiMesh g, int n,
                                                                   const int32_t* __restrict__ Q, const double2* __restrict__ D, double inv_t,
-                                                                  int64_t blocks, double* __restrict__ part) {
+                                                                  int64_t blocks, double* __restrict__ part, ChiDyn dyn) {
     constexpr int RB = 16 * BT;               // rows (and columns) of the block
     constexpr int KPW = BT == 1 ? 4 : 1;      // k-points per workgroup
     constexpr int TEAM = CHI_THREADS / KPW;   // threads that stage one k-point's panel
@@ -181,6 +254,102 @@ __global__ void __launch_bounds__(CHI_THREADS) chi_overlap_kernel(const double2*
         }
     }
     // the epilogue.  lane (q, c), register r: row q + 4 r, column c of the tile
+    if constexpr (DYN) {
+        __shared__ double wave_dyn[4][CHI_WC][2];
+        // p = g |M|^2 (0 in the padding) of the lane's elements, once for all frequencies, and the eigenvalues of their rows and columns:
+        // Delta = ea - eb is one subtraction per element and chunk, and half the registers of a stored one
+        double pw[4 * BT], ea[4], ebv[BT];
+#pragma unroll
+        for (int e = 0; e < 4 * BT; ++e) pw[e] = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ea[r] = 0.0;
+#pragma unroll
+        for (int tj = 0; tj < BT; ++tj) ebv[tj] = 0.0;
+        if (row_live) {
+            const int64_t items = g.nk * n;
+            const double* Ea = E + (size_t)k * n;
+            const double* Eb = E + (size_t)kp * n;
+            const double *fa = tab + (size_t)k * n, *ga = fa + items, *fb = tab + (size_t)kp * n, *gb = fb + items;
+            double fav[4], gav[4];
+            bool a_in[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int b = bi * RB + ti * 16 + (lane >> 4) + 4 * r;
+                a_in[r] = b < n;
+                const int bs = a_in[r] ? b : 0;
+                ea[r] = Ea[bs];
+                fav[r] = fa[bs];
+                gav[r] = ga[bs];
+            }
+#pragma unroll
+            for (int tj = 0; tj < BT; ++tj) {
+                const int c = bj * RB + tj * 16 + (lane & 15);
+                if (bj * RB + tj * 16 < n) {  // (uniform)
+                    const bool c_in = c < n;
+                    const int cs = c_in ? c : 0;
+                    const double eb = Eb[cs], fbv = fb[cs], gbv = gb[cs];
+                    ebv[tj] = eb;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const double m2 = accr[tj][r] * accr[tj][r] + acci[tj][r] * acci[tj][r];
+                        const double gd = chi_pair_difference(ea[r], fav[r], gav[r], eb, fbv, gbv, inv_t);
+                        pw[tj * 4 + r] = (a_in[r] && c_in) ? gd * m2 : 0.0;
+                    }
+                }
+            }
+        }
+        const double eta = dyn.eta, eta2 = eta * eta;
+        for (int w0 = 0; w0 < dyn.nw; w0 += CHI_WC) {
+            double om[CHI_WC], re[CHI_WC], im[CHI_WC];
+#pragma unroll
+            for (int j = 0; j < CHI_WC; ++j) {
+                om[j] = dyn.W[w0 + j < dyn.nw ? w0 + j : dyn.nw - 1];  // (uniform; beyond the list: computed, not stored)
+                re[j] = im[j] = 0.0;
+            }
+            if (row_live) {
+#pragma unroll
+                for (int tj = 0; tj < BT; ++tj) {
+                    if (bj * RB + tj * 16 < n) {  // (uniform)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const double delta = ea[r] - ebv[tj];
+#pragma unroll
+                            for (int j = 0; j < CHI_WC; ++j) chi_dyn_term(pw[tj * 4 + r], delta, om[j], eta, eta2, re[j], im[j]);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < CHI_WC; ++j) {
+                re[j] = chi_wave_sum(re[j]);
+                im[j] = chi_wave_sum(im[j]);
+            }
+            if (BT == 1) {
+                if (valid && lane == 0) {
+#pragma unroll
+                    for (int j = 0; j < CHI_WC; ++j)
+                        if (w0 + j < dyn.nw) dyn.part[((size_t)ql * dyn.nw + (w0 + j)) * g.nk + k] = make_double2(re[j], im[j]);
+                }
+            } else {
+                if (lane == 0) {
+#pragma unroll
+                    for (int j = 0; j < CHI_WC; ++j) {
+                        wave_dyn[wave][j][0] = re[j];
+                        wave_dyn[wave][j][1] = im[j];
+                    }
+                }
+                __syncthreads();
+                if (tid < 2 * CHI_WC) {
+                    const int j = tid >> 1, c = tid & 1;
+                    if (w0 + j < dyn.nw)
+                        reinterpret_cast<double*>(dyn.part)[((((size_t)ql * dyn.nw + (w0 + j)) * g.nk + k) * blocks + blockIdx.y) * 2 + c] =
+                            ((wave_dyn[0][j][c] + wave_dyn[1][j][c]) + wave_dyn[2][j][c]) + wave_dyn[3][j][c];
+                }
+                __syncthreads();  // (the next chunk writes wave_dyn)
+            }
+        }
+        return;
+    }
     double sum = 0.0;
     if (row_live) {
         const int64_t items = g.nk * n;
@@ -266,8 +435,85 @@ __global__ void __launch_bounds__(CHI_THREADS) chi_reduce_kernel(const double* _
     if (tid == 0) chi[blockIdx.x] = red[0] / T / nk;
 }
 
+// chi_pair_kernel with the dynamic terms: the walk over the n^2 pairs once per chunk of frequencies.  part: [batch][nw][NK]
+__global__ void __launch_bounds__(CHI_THREADS) chi_pair_dyn_kernel(const double* __restrict__ E, const double* __restrict__ tab, ChiMesh g, int n,
+                                                                   const int32_t* __restrict__ Q, double inv_t, ChiDyn dyn) {
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    const int64_t k = (int64_t)blockIdx.x * 4 + wave;
+    const int64_t ql = blockIdx.z;
+    const bool valid = k < g.nk;
+    const int64_t kp = valid ? chi_shifted(g, k, Q + ql * 3) : 0;
+    const int64_t items = g.nk * n;
+    const double *Ea = E + (size_t)(valid ? k : 0) * n, *Eb = E + (size_t)kp * n;
+    const double *fa = tab + (size_t)(valid ? k : 0) * n, *ga = fa + items, *fb = tab + (size_t)kp * n, *gb = fb + items;
+    const int64_t pairs = (int64_t)n * n;
+    const double eta = dyn.eta, eta2 = eta * eta;
+    for (int w0 = 0; w0 < dyn.nw; w0 += CHI_WC) {
+        double om[CHI_WC], re[CHI_WC], im[CHI_WC];
+#pragma unroll
+        for (int j = 0; j < CHI_WC; ++j) {
+            om[j] = dyn.W[w0 + j < dyn.nw ? w0 + j : dyn.nw - 1];
+            re[j] = im[j] = 0.0;
+        }
+        if (valid) {
+            for (int64_t p = lane; p < pairs; p += 64) {
+                const int a = (int)(p / n), b = (int)(p - (int64_t)a * n);
+                const double gd = chi_pair_difference(Ea[a], fa[a], ga[a], Eb[b], fb[b], gb[b], inv_t);
+                const double delta = Ea[a] - Eb[b];
+#pragma unroll
+                for (int j = 0; j < CHI_WC; ++j) chi_dyn_term(gd, delta, om[j], eta, eta2, re[j], im[j]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < CHI_WC; ++j) {
+            re[j] = chi_wave_sum(re[j]);
+            im[j] = chi_wave_sum(im[j]);
+        }
+        if (valid && lane == 0) {
+#pragma unroll
+            for (int j = 0; j < CHI_WC; ++j)
+                if (w0 + j < dyn.nw) dyn.part[((size_t)ql * dyn.nw + (w0 + j)) * g.nk + k] = make_double2(re[j], im[j]);
+        }
+    }
+}
+
+// chi[q][w_first + omega] = (0 - the len complex partials of (q, omega) in chi_reduce_kernel's order) / NK.  grid: (frequencies of the
+// pass, vectors of the batch); chi: the batch's rows of [n_q][n_w]
+__global__ void __launch_bounds__(CHI_THREADS) chi_reduce_dyn_kernel(const double2* __restrict__ part, int64_t len, double nk, int64_t n_w,
+                                                                     int64_t w_first, double2* __restrict__ chi) {
+    __shared__ double red[2][CHI_THREADS];
+    const int tid = (int)threadIdx.x;
+    const double2* p = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * len;
+    const int64_t piece = (len + CHI_THREADS - 1) / CHI_THREADS;
+    const int64_t lo = tid * piece < len ? tid * piece : len, hi = lo + piece < len ? lo + piece : len;
+    double re = 0.0, im = 0.0;
+    for (int64_t i = lo; i < hi; ++i) {
+        const double2 v = p[i];
+        re += v.x;
+        im += v.y;
+    }
+    red[0][tid] = re;
+    red[1][tid] = im;
+    __syncthreads();
+    for (int s = CHI_THREADS / 2; s >= 1; s >>= 1) {
+        if (tid < s) {
+            red[0][tid] += red[0][tid + s];
+            red[1][tid] += red[1][tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) chi[(size_t)blockIdx.y * n_w + w_first + blockIdx.x] = make_double2((0.0 - red[0][0]) / nk, (0.0 - red[1][0]) / nk);
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, bool matrix_elements, size_t mem, ChiPlan* out) {
+// the frequencies of a dynamic call (n_w = 0: the static call)
+struct ChiFreq {
+    int64_t n_w = 0;
+    const double* omega = nullptr;  // host
+    double eta = 0.0;
+};
+
+int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, int64_t n_w, bool matrix_elements, size_t mem, ChiPlan* out) {
     ChiPlan L;
     L.mesh.n[0] = mesh[0];
     L.mesh.n[1] = mesh[1];
@@ -275,10 +521,14 @@ int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, b
     L.mesh.nk = nk;
     L.n = n_orb;
     TBK_ARG(nk <= CHI_MAX_NK, "the susceptibility takes meshes of up to 2^23 points");
-    chi_plan_sizes(nk, n_orb, n_q, matrix_elements, mem, &L.bt, &L.blocks, &L.batch, &L.batches);
+    L.n_w = n_w;
+    if (n_w == 0)
+        chi_plan_sizes(nk, n_orb, n_q, matrix_elements, mem, &L.bt, &L.blocks, &L.batch, &L.batches);
+    else
+        chi_dyn_plan_sizes(nk, n_orb, n_q, n_w, matrix_elements, mem, &L.bt, &L.blocks, &L.batch, &L.batches, &L.w_pass, &L.passes);
     if (L.batch < 1) {
-        tbk_set_error("the partial sums of one susceptibility vector need %zu bytes of device memory",
-                      (size_t)nk * (size_t)L.blocks * sizeof(double));
+        tbk_set_error("the partial sums of one susceptibility vector%s need %zu bytes of device memory", n_w == 0 ? "" : " at one frequency",
+                      (size_t)nk * (size_t)L.blocks * (n_w == 0 ? sizeof(double) : sizeof(double2)));
         return TBK_ERR_MEMORY;
     }
     *out = L;
@@ -341,13 +591,13 @@ int chi_launch_batch(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const do
         hipLaunchKernelGGL(chi_pair_kernel, dim3((unsigned)((nk + 3) / 4), 1, (unsigned)nq), dim3(CHI_THREADS), 0, s, d_E, d_tab, L.mesh, L.n, d_Q,
                            inv_t, d_part);
     } else if (L.bt == 1) {
-        hipLaunchKernelGGL(chi_overlap_kernel<1>, dim3((unsigned)((nk + 3) / 4), 1, (unsigned)nq), dim3(CHI_THREADS), 0, s,
+        hipLaunchKernelGGL((chi_overlap_kernel<1, false>), dim3((unsigned)((nk + 3) / 4), 1, (unsigned)nq), dim3(CHI_THREADS), 0, s,
                            reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q, reinterpret_cast<const double2*>(d_D), inv_t,
-                           L.blocks, d_part);
+                           L.blocks, d_part, ChiDyn());
     } else {
-        hipLaunchKernelGGL(chi_overlap_kernel<4>, dim3((unsigned)nk, (unsigned)L.blocks, (unsigned)nq), dim3(CHI_THREADS), 0, s,
+        hipLaunchKernelGGL((chi_overlap_kernel<4, false>), dim3((unsigned)nk, (unsigned)L.blocks, (unsigned)nq), dim3(CHI_THREADS), 0, s,
                            reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q, reinterpret_cast<const double2*>(d_D), inv_t,
-                           L.blocks, d_part);
+                           L.blocks, d_part, ChiDyn());
     }
     if (ev) ev->stop();
     TBK_HIP(hipGetLastError());
@@ -358,12 +608,55 @@ int chi_launch_batch(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const do
     return TBK_OK;
 }
 
-// all batches of n_q vectors whose reduced entries (and phases) are on the device; d_chi[n_q]
+// the dynamic call's: nq vectors (at most L.batch), every pass of the frequencies d_W[L.n_w]; d_chi: their rows of [.][L.n_w] complex.
+// The spans are the static call's: 1 = the overlaps with the dynamic epilogue (or the pair kernel), 2 = the reduction.
+int chi_launch_dyn_batch(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, const double* d_tab,
+                         const int32_t* d_Q, const double* d_D, int64_t nq, double T, const double* d_W, double eta, double* d_part,
+                         double* d_chi) {
+    const double inv_t = 1.0 / T;
+    const int64_t nk = L.mesh.nk;
+    for (int64_t w0 = 0; w0 < L.n_w; w0 += L.w_pass) {
+        ChiDyn dyn;
+        dyn.W = d_W + w0;
+        dyn.nw = (int)std::min(L.w_pass, L.n_w - w0);
+        dyn.eta = eta;
+        dyn.part = reinterpret_cast<double2*>(d_part);
+        if (ev) ev->start(1);
+        if (L.bt == 0) {
+            hipLaunchKernelGGL(chi_pair_dyn_kernel, dim3((unsigned)((nk + 3) / 4), 1, (unsigned)nq), dim3(CHI_THREADS), 0, s, d_E, d_tab, L.mesh, L.n,
+                               d_Q, inv_t, dyn);
+        } else if (L.bt == 1) {
+            hipLaunchKernelGGL((chi_overlap_kernel<1, true>), dim3((unsigned)((nk + 3) / 4), 1, (unsigned)nq), dim3(CHI_THREADS), 0, s,
+                               reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q, reinterpret_cast<const double2*>(d_D), inv_t,
+                               L.blocks, nullptr, dyn);
+        } else {
+            hipLaunchKernelGGL((chi_overlap_kernel<4, true>), dim3((unsigned)nk, (unsigned)L.blocks, (unsigned)nq), dim3(CHI_THREADS), 0, s,
+                               reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q, reinterpret_cast<const double2*>(d_D), inv_t,
+                               L.blocks, nullptr, dyn);
+        }
+        if (ev) ev->stop();
+        TBK_HIP(hipGetLastError());
+        if (ev) ev->start(2);
+        hipLaunchKernelGGL(chi_reduce_dyn_kernel, dim3((unsigned)dyn.nw, (unsigned)nq), dim3(CHI_THREADS), 0, s, dyn.part, nk * L.blocks, (double)nk,
+                           L.n_w, w0, reinterpret_cast<double2*>(d_chi));
+        if (ev) ev->stop();
+        TBK_HIP(hipGetLastError());
+    }
+    return TBK_OK;
+}
+
+// all batches of n_q vectors whose reduced entries (and phases) are on the device; d_chi[n_q], or [n_q][L.n_w] complex with the
+// frequencies d_W of a dynamic call
 int chi_launch_all(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, double* d_tab, const int32_t* d_Q,
-                   const double* d_D, int64_t n_q, double mu, double T, double* d_part, double* d_chi) {
+                   const double* d_D, int64_t n_q, double mu, double T, const double* d_W, double eta, double* d_part, double* d_chi) {
     TBK_CHECK(chi_launch_fermi(s, L, ev, d_E, mu, T, d_tab));
     for (int64_t q0 = 0; q0 < n_q; q0 += L.batch) {
         const int64_t nq = std::min(L.batch, n_q - q0);
+        if (L.n_w > 0) {
+            TBK_CHECK(chi_launch_dyn_batch(s, L, ev, d_U, d_E, d_tab, d_Q + q0 * 3, d_D ? d_D + (size_t)q0 * L.n * 2 : nullptr, nq, T, d_W, eta,
+                                           d_part, d_chi + (size_t)q0 * L.n_w * 2));
+            continue;
+        }
         TBK_CHECK(chi_launch_batch(s, L, ev, d_U, d_E, d_tab, d_Q + q0 * 3, d_D ? d_D + (size_t)q0 * L.n * 2 : nullptr, nq, T, d_part,
                                    d_chi + q0));
     }
@@ -375,6 +668,15 @@ int chi_check(double T, int64_t n_q, const int64_t* q, const double* chi_out, in
     TBK_ARG(n_q >= 1, "n_q < 1");
     TBK_ARG(q != nullptr && chi_out != nullptr, "q / chi is NULL");
     TBK_ARG(n_orb >= 1 && n_orb <= CHI_MAX_ORB, "n_orb < 1 or more than 16320 orbitals");
+    return TBK_OK;
+}
+
+int chi_check_frequencies(int64_t n_w, const double* omega, double eta) {
+    TBK_ARG(n_w >= 1, "n_w < 1");
+    TBK_ARG(n_w <= CHI_MAX_NW, "the dynamic susceptibility takes up to 2^23 frequencies per call");
+    TBK_ARG(omega != nullptr, "omega is NULL");
+    for (int64_t j = 0; j < n_w; ++j) TBK_ARG(std::isfinite(omega[j]), "a frequency is not finite");
+    TBK_ARG(std::isfinite(eta) && eta > 0.0 && eta * eta > 0.0, "eta is not finite or not positive (or its square underflows)");
     return TBK_OK;
 }
 
@@ -405,46 +707,57 @@ extern "C" int tbk_chi_plan(int64_t nk, int n_orb, int64_t n_q, int matrix_eleme
     return TBK_OK;
 }
 
-extern "C" int tbk_chi_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu, double T,
-                                        int64_t n_q, const int64_t* q, const double* phases, double* chi_out) {
+// the kernels on a caller's eigensystem: chi_out double [n_q], or with frequencies complex [n_q][n_w]; mem: the bytes the partials may
+// take (0: the budget)
+static int chi_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu, double T,
+                         int64_t n_q, const int64_t* q, const double* phases, const ChiFreq& fr, size_t mem, double* chi_out) {
     int64_t nk = 0;
     TBK_CHECK(tetra_check_mesh(dim, mesh, OCC_MESH, &nk));
     TBK_ARG(E != nullptr, "E is NULL");
     TBK_ARG(std::isfinite(mu), "the chemical potential is not finite");
     TBK_CHECK(chi_check(T, n_q, q, chi_out, n_orb));
+    if (fr.n_w != 0) TBK_CHECK(chi_check_frequencies(fr.n_w, fr.omega, fr.eta));
     TBK_ARG(U != nullptr || phases == nullptr, "phases without eigenvectors");
     TBK_CHECK(tetra_check_device(device));
     ChiPlan L;
-    TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, n_q, U != nullptr, 0, &L));
+    TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, n_q, fr.n_w, U != nullptr, mem, &L));
+    const size_t out_bytes = (size_t)n_q * (fr.n_w == 0 ? sizeof(double) : (size_t)fr.n_w * sizeof(double2));
     std::vector<int32_t> h_Q;
     TBK_CHECK(chi_reduce_q(dim, mesh, n_q, q, &h_Q));
     const size_t e_bytes = (size_t)nk * n_orb * sizeof(double), u_bytes = (size_t)nk * n_orb * n_orb * sizeof(double2);
     const size_t d_bytes = (size_t)n_q * n_orb * sizeof(double2);
-    DevBuf d_E, d_U, d_tab, d_Q, d_D, d_part, d_chi;
+    DevBuf d_E, d_U, d_tab, d_Q, d_D, d_W, d_part, d_chi;
     TBK_CHECK(d_E.reserve(e_bytes));
     TBK_CHECK(d_tab.reserve(2 * e_bytes));
     if (U) TBK_CHECK(chi_reserve(d_U, u_bytes, "the eigenvectors of the whole mesh"));
     TBK_CHECK(d_Q.reserve(h_Q.size() * sizeof(int32_t)));
     if (phases) TBK_CHECK(d_D.reserve(d_bytes));
     TBK_CHECK(d_part.reserve(L.part_bytes()));
-    TBK_CHECK(d_chi.reserve((size_t)n_q * sizeof(double)));
+    TBK_CHECK(d_chi.reserve(out_bytes));
+    if (fr.n_w != 0) {
+        TBK_CHECK(d_W.reserve((size_t)fr.n_w * sizeof(double)));
+        TBK_HIP(hipMemcpy(d_W.ptr, fr.omega, (size_t)fr.n_w * sizeof(double), hipMemcpyHostToDevice));
+    }
     TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
     if (U) TBK_HIP(hipMemcpy(d_U.ptr, U, u_bytes, hipMemcpyHostToDevice));
     TBK_HIP(hipMemcpy(d_Q.ptr, h_Q.data(), h_Q.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     if (phases) TBK_HIP(hipMemcpy(d_D.ptr, phases, d_bytes, hipMemcpyHostToDevice));
     TBK_CHECK(chi_launch_all(nullptr, L, nullptr, d_U.as<double>(), d_E.as<double>(), d_tab.as<double>(), d_Q.as<int32_t>(),
-                             phases ? d_D.as<double>() : nullptr, n_q, mu, T, d_part.as<double>(), d_chi.as<double>()));
-    TBK_HIP(hipMemcpy(chi_out, d_chi.ptr, (size_t)n_q * sizeof(double), hipMemcpyDeviceToHost));
+                             phases ? d_D.as<double>() : nullptr, n_q, mu, T, fr.n_w != 0 ? d_W.as<double>() : nullptr, fr.eta,
+                             d_part.as<double>(), d_chi.as<double>()));
+    TBK_HIP(hipMemcpy(chi_out, d_chi.ptr, out_bytes, hipMemcpyDeviceToHost));
     return TBK_OK;
 }
 
-extern "C" int tbk_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
-                                        int64_t n_q, const int64_t* q, int matrix_elements, int convention, const double* pos, double* mu_out,
-                                        double* chi_out) {
+// the whole call, static (fr.n_w = 0, chi_out double [n_q]) or dynamic (complex [n_q][n_w])
+static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T, int64_t n_q,
+                   const int64_t* q, const ChiFreq& fr, int matrix_elements, int convention, const double* pos, double* mu_out,
+                   double* chi_out) {
     TBK_ARG(mu_out != nullptr, "mu is NULL");
     TBK_ARG(mode == 0 || mode == 1, "mode must be 0 (value = energy) or 1 (value = n_electrons)");
     TBK_ARG(handles != nullptr && n_handles >= 1 && handles[0] != nullptr, "no handles");
     TBK_CHECK(chi_check(T, n_q, q, chi_out, handles[0]->n_orb));
+    if (fr.n_w != 0) TBK_CHECK(chi_check_frequencies(fr.n_w, fr.omega, fr.eta));
     TBK_CHECK(tbk_eigh_check_arguments(0, convention, pos));
     if (mode == 1)
         TBK_CHECK(tbk_fermi_check_electrons(value, handles[0]->n_orb));
@@ -466,6 +779,8 @@ extern "C" int tbk_susceptibility_multi(tbk_model* const* handles, int n_handles
     // every handle holds the whole mesh's eigensystem and takes a contiguous share of the vectors
     const TetraSlabs share(n_q, n_handles);
     const size_t e_bytes = (size_t)nk * n_orb * sizeof(double), nn2 = (size_t)n_orb * n_orb * 2;
+    // per vector: one double, or n_w complex numbers; the frequencies follow the results
+    const size_t out_per_q = fr.n_w == 0 ? sizeof(double) : (size_t)fr.n_w * sizeof(double2), w_bytes = (size_t)fr.n_w * sizeof(double);
     std::vector<SpanRecorder> ev((size_t)share.busy());
     ChiDrain drain;
     for (int i = 0; i < share.busy(); ++i) {
@@ -478,23 +793,25 @@ extern "C" int tbk_susceptibility_multi(tbk_model* const* handles, int n_handles
         TBK_CHECK(m->ws_chi_k.reserve(h_k.size() * sizeof(double)));
         TBK_CHECK(chi_reserve(m->ws_chi_e, 3 * e_bytes, "the eigenvalues and Fermi tables of the whole mesh"));
         if (with_u) TBK_CHECK(chi_reserve(m->ws_chi_u, (size_t)nk * nn2 * sizeof(double), "the eigenvectors of the whole mesh"));
-        TBK_CHECK(m->ws_chi_q.reserve((size_t)q_n * (3 * sizeof(int32_t) + sizeof(double) + (with_d ? n_orb * sizeof(double2) : 0)) + 256));
+        TBK_CHECK(m->ws_chi_q.reserve((size_t)q_n * (3 * sizeof(int32_t) + out_per_q + (with_d ? n_orb * sizeof(double2) : 0)) + w_bytes + 256));
         // the batch from the memory that is left for the partials, the chunk of the eigenvector walk from what is left then
         size_t free_b = 0, total_b = 0;
         TBK_HIP(hipMemGetInfo(&free_b, &total_b));
         ChiPlan L;
-        TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, q_n, with_u, std::max<size_t>(1, std::min(CHI_PART_BUDGET, std::max(m->ws_chi_part.bytes, free_b / 4))), &L));
+        TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, q_n, fr.n_w, with_u, std::max<size_t>(1, std::min(CHI_PART_BUDGET, std::max(m->ws_chi_part.bytes, free_b / 4))), &L));
         TBK_CHECK(m->ws_chi_part.reserve(L.part_bytes()));
         double* d_k = m->ws_chi_k.as<double>();
         double* d_E = m->ws_chi_e.as<double>();
         double* d_U = m->ws_chi_u.as<double>();
-        // ws_chi_q: the results, 256-byte aligned behind them the phases, then the reduced vectors
+        // ws_chi_q: the results (and the frequencies of a dynamic call), 256-byte aligned behind them the phases, then the reduced vectors
         double* d_chi = m->ws_chi_q.as<double>();
-        char* behind = m->ws_chi_q.as<char>() + dos_align256((size_t)q_n * sizeof(double));
+        double* d_W = fr.n_w != 0 ? reinterpret_cast<double*>(m->ws_chi_q.as<char>() + (size_t)q_n * out_per_q) : nullptr;
+        char* behind = m->ws_chi_q.as<char>() + dos_align256((size_t)q_n * out_per_q + w_bytes);
         double* d_D = with_d ? reinterpret_cast<double*>(behind) : nullptr;
         int32_t* d_Q = reinterpret_cast<int32_t*>(behind + (with_d ? (size_t)q_n * n_orb * sizeof(double2) : 0));
         TBK_HIP(hipMemcpyAsync(d_k, h_k.data(), h_k.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
         TBK_HIP(hipMemcpyAsync(d_Q, h_Q.data() + q_lo * 3, (size_t)q_n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
+        if (d_W) TBK_HIP(hipMemcpyAsync(d_W, fr.omega, w_bytes, hipMemcpyHostToDevice, m->stream));
         if (with_d)
             TBK_HIP(hipMemcpyAsync(d_D, h_D.data() + (size_t)q_lo * n_orb * 2, (size_t)q_n * n_orb * sizeof(double2), hipMemcpyHostToDevice,
                                    m->stream));
@@ -508,9 +825,10 @@ extern "C" int tbk_susceptibility_multi(tbk_model* const* handles, int n_handles
         } else {
             TBK_CHECK(tbk_eigenval_device_hint(m, d_k, h_k.data(), nk, d_E));
         }
-        TBK_CHECK(chi_launch_all(m->stream, L, &ev[(size_t)i], d_U, d_E, d_E + (size_t)nk * n_orb, d_Q, d_D, q_n, mu, T,
+        TBK_CHECK(chi_launch_all(m->stream, L, &ev[(size_t)i], d_U, d_E, d_E + (size_t)nk * n_orb, d_Q, d_D, q_n, mu, T, d_W, fr.eta,
                                  m->ws_chi_part.as<double>(), d_chi));
-        TBK_HIP(hipMemcpyAsync(chi_out + q_lo, d_chi, (size_t)q_n * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        TBK_HIP(hipMemcpyAsync(reinterpret_cast<char*>(chi_out) + (size_t)q_lo * out_per_q, d_chi, (size_t)q_n * out_per_q, hipMemcpyDeviceToHost,
+                               m->stream));
     }
     // synchronises every handle (the eigensolver's flags are reported as by tbk_eigh) and books the kernel times
     for (tbk_model* m : drain.used) TBK_CHECK(tbk_eigenval_check(m));
@@ -522,6 +840,56 @@ extern "C" int tbk_susceptibility_multi(tbk_model* const* handles, int n_handles
         m->timed[TIMED_CHI].calls += 1;
     }
     return TBK_OK;
+}
+
+extern "C" int tbk_chi_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu, double T,
+                                        int64_t n_q, const int64_t* q, const double* phases, double* chi_out) {
+    return chi_from_eigensystem(device, dim, mesh, n_orb, E, U, mu, T, n_q, q, phases, ChiFreq(), 0, chi_out);
+}
+
+extern "C" int tbk_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
+                                        int64_t n_q, const int64_t* q, int matrix_elements, int convention, const double* pos, double* mu_out,
+                                        double* chi_out) {
+    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, ChiFreq(), matrix_elements, convention, pos, mu_out, chi_out);
+}
+
+extern "C" int tbk_chi_dynamic_plan(int64_t nk, int n_orb, int64_t n_q, int64_t n_w, int matrix_elements, int64_t part_bytes, int64_t* out) {
+    TBK_ARG(nk >= 1 && n_orb >= 1 && n_orb <= CHI_MAX_ORB && n_q >= 1 && n_w >= 1 && n_w <= CHI_MAX_NW && part_bytes >= 0 && out != nullptr,
+            "nk / n_orb / n_q / n_w < 1, more than 16320 orbitals or 2^23 frequencies, part_bytes < 0 or out is NULL");
+    int bt = 0;
+    chi_dyn_plan_sizes(nk, n_orb, n_q, n_w, matrix_elements != 0, (size_t)part_bytes, &bt, &out[1], &out[2], &out[3], &out[4], &out[5]);
+    out[0] = bt;
+    out[6] = CHI_WC;
+    return TBK_OK;
+}
+
+extern "C" int tbk_chi_dynamic_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu,
+                                                double T, int64_t n_q, const int64_t* q, const double* phases, int64_t n_w, const double* omega,
+                                                double eta, int64_t part_bytes, double* chi_out) {
+    TBK_ARG(part_bytes >= 0, "part_bytes < 0");
+    TBK_ARG(n_w >= 1, "n_w < 1");
+    ChiFreq fr;
+    fr.n_w = n_w;
+    fr.omega = omega;
+    fr.eta = eta;
+    return chi_from_eigensystem(device, dim, mesh, n_orb, E, U, mu, T, n_q, q, phases, fr, (size_t)part_bytes, chi_out);
+}
+
+extern "C" int tbk_dynamic_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
+                                                int64_t n_q, const int64_t* q, int64_t n_w, const double* omega, double eta, int matrix_elements,
+                                                int convention, const double* pos, double* mu_out, double* chi_out) {
+    TBK_ARG(n_w >= 1, "n_w < 1");
+    ChiFreq fr;
+    fr.n_w = n_w;
+    fr.omega = omega;
+    fr.eta = eta;
+    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, fr, matrix_elements, convention, pos, mu_out, chi_out);
+}
+
+extern "C" int tbk_dynamic_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q,
+                                          int64_t n_w, const double* omega, double eta, int matrix_elements, int convention, const double* pos,
+                                          double* mu_out, double* chi_out) {
+    return tbk_dynamic_susceptibility_multi(&m, 1, mesh, mode, value, T, n_q, q, n_w, omega, eta, matrix_elements, convention, pos, mu_out, chi_out);
 }
 
 extern "C" int tbk_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q,

@@ -14,7 +14,14 @@ matrix elements, best of --reps after a warm-up:
    TIMED ON THE FIRST TWO PLANES of the mesh (the model on those planes as a periodic mesh of their own, at most two vectors) AND
    SCALED to the mesh and to NQ, and printed as such.
 
-    python tools/bench_chi.py [--reps 3] [--filling 0.3] [--temperature 0.05] [--quick]
+With --omegas N[,N...] it prints the table of Model.dynamic_susceptibility instead: for every NW of the list,
+NW frequencies evenly spaced over [0, 2 bandwidths), eta = --eta, NQ = 1 and 16; the same stages (the overlap stage now holds the
+dynamic epilogue); the epilogue's share of the overlap stage as that stage's time less the static call's overlap stage for the same
+vectors, measured in the same run; its f64 VALU rate, EPILOGUE_VALU instructions per (pair of states of the padded block, frequency) over that time, as a
+fraction of --valu-peak (lane-instructions per second of the whole chip); and the host route, Model.eigh + chi_model.dynamic_susceptibility,
+timed on two planes, at most two vectors and at most four frequencies and scaled.
+
+    python tools/bench_chi.py [--reps 3] [--filling 0.3] [--temperature 0.05] [--quick] [--omegas 1,16,128 [--eta 0.05]]
 """
 
 import argparse
@@ -84,13 +91,82 @@ def measure(name, model, mesh, counts, filling, T, reps, peak_tflops):
         sys.stdout.flush()
 
 
+EPILOGUE_VALU = 16  # f64 vector instructions per (pair of states, frequency) in the built dynamic epilogue
+
+
+def measure_dynamic(name, model, mesh, counts, n_ws, filling, T, eta, reps, valu_peak):
+    lib = _lib.lib()
+    n, n_k = model.size, int(np.prod(mesh))
+    n_el = filling * n
+    n_pad = (n + 15) // 16 * 16
+    handle = model._staged()
+    ms, calls = (ctypes.c_double * 3)(), ctypes.c_int64(0)
+    kpts = np.ascontiguousarray(dos_model.mesh_kpoints(mesh))
+    plane = int(np.prod(mesh[1:]))
+    sub_mesh = (2,) + tuple(mesh[1:])
+    model.eigh(kpts[:plane])
+    t_eigh, (eig2, vec2) = _best(lambda: model.eigh(kpts[:2 * plane]), max(1, reps - 1))
+    edges = model.band_edges(mesh)
+    width = float(edges.emax.max() - edges.emin.min())
+
+    def stages_of(call):
+        call()  # warm-up
+        t_call, result = _best(call, reps)
+        _lib.check(lib.tbk_model_set_option(handle, _lib.TBK_OPT_TIMING, 1))
+        _lib.check(lib.tbk_chi_timing(handle, ms, ctypes.byref(calls), 1))
+        for _ in range(reps):
+            call()
+        _lib.check(lib.tbk_chi_timing(handle, ms, ctypes.byref(calls), 1))
+        model.timing(reset=True)
+        _lib.check(lib.tbk_model_set_option(handle, _lib.TBK_OPT_TIMING, 0))
+        return t_call, result, [x / max(1, calls.value) for x in ms]
+
+    for n_q in counts:
+        q = np.zeros((n_q, len(mesh)), dtype=np.int64)
+        q[:, 0] = np.arange(1, n_q + 1)
+        _, _, static = stages_of(lambda: model.susceptibility(mesh, q, temperature=T, n_electrons=n_el))
+        for n_w in n_ws:
+            omega = np.arange(n_w) * (2.0 * width / n_w)
+            t_call, result, stages = stages_of(lambda: model.dynamic_susceptibility(mesh, q, omega, eta=eta, temperature=T, n_electrons=n_el))
+            epilogue = stages[1] - static[1]
+            rate = EPILOGUE_VALU * float(n_pad) ** 2 * n_k * n_q * n_w / (epilogue * 1e-3) / (valu_peak * 1e9) if epilogue > 0 else float("nan")
+            few_q, few_w = min(n_q, 2), min(n_w, 4)
+            t_model, _ = _best(lambda: chi_model.dynamic_susceptibility(eig2, vec2, sub_mesh, q[:few_q], result.mu.mu, T, omega[:few_w], eta), 1)
+            t_one, _ = _best(lambda: chi_model.dynamic_susceptibility(eig2, vec2, sub_mesh, q[:few_q], result.mu.mu, T, omega[:1], eta), 1)
+            per_w = (t_model - t_one) / (few_w - 1) if few_w > 1 else 0.0
+            t_host = (t_eigh + (t_one + per_w * (n_w - 1)) / few_q * n_q) / 2 * mesh[0]
+            print("| %s | %s | %d | %d | %d | %.1f | %.1f | %.3f | %.3f | %.3f | %.3f | %.3f | %.3f | %.1f |"
+                  % (name, "x".join(str(x) for x in mesh), n, n_q, n_w, t_call * 1e3, t_call * 1e3 - sum(stages), stages[0], stages[1], stages[2], static[1],
+                     epilogue, rate, t_host * 1e3))
+            print("  (%s NQ = %d NW = %d: mu = %.12g, chi(q_1, omega_0) = %.12g%+.12gj)" % (name, n_q, n_w, result.mu.mu, result.chi[0, 0].real, result.chi[0, 0].imag))
+            sys.stdout.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--filling", type=float, default=0.3, help="electrons per orbital")
     ap.add_argument("--temperature", type=float, default=0.05, help="k_B T in the model's energy units")
     ap.add_argument("--quick", action="store_true", help="small meshes and lists (a smoke run of the tool)")
+    ap.add_argument("--omegas", type=str, default="", help="comma-separated numbers of frequencies: the table of Model.dynamic_susceptibility instead")
+    ap.add_argument("--eta", type=float, default=0.05, help="the broadening of the dynamic call")
+    ap.add_argument("--valu-peak", type=float, default=39321.6, help="f64 VALU peak in G lane-instructions per second: the data sheet's 78.6 TFLOP/s "
+                    "of vector FP64 is one fused multiply-add per lane and cycle, 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz")
     args = ap.parse_args()
+    if args.omegas:
+        n_ws = [int(x) for x in args.omegas.split(",")]
+        print("| model | mesh | orbitals | NQ | NW | Model.dynamic_susceptibility ms | of it outside the chi kernels ms | Fermi tables ms | overlaps + dynamic "
+              "epilogue ms | reduction ms | static overlap stage, same vectors ms | epilogue (difference) ms | epilogue VALU / f64 vector peak | today: "
+              "Model.eigh to the host + tools/chi_model.py ms (two planes, at most two vectors and four frequencies, scaled) |")
+        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+        counts = (1, 4) if args.quick else (1, 16)
+        data = np.load(os.path.join(ROOT, "tests", "golden", "silicon.npz"))
+        silicon = tbmodels_amd.Model.from_packed(data["R"], data["hop"], pos=data["pos"])
+        measure_dynamic("silicon", silicon, (8,) * 3 if args.quick else (32,) * 3, counts, n_ws, args.filling, args.temperature, args.eta, args.reps, args.valu_peak)
+        r_vec, hop, _ = synthetic.dense_model_arrays(64, 64, synthetic.MODEL_SEED + 2)
+        dense = tbmodels_amd.Model.from_packed(r_vec, hop)
+        measure_dynamic("dense 64", dense, (6,) * 3 if args.quick else (24,) * 3, counts, n_ws, args.filling, args.temperature, args.eta, args.reps, args.valu_peak)
+        return
     tf = ctypes.c_double(0.0)
     _lib.check(_lib.lib().tbk_mfma_f64_peak(0, ctypes.byref(tf)))
     print("FP64 MFMA peak: %.1f TFLOP/s" % tf.value)

@@ -18,6 +18,9 @@ F is never evaluated as the quotient, which cancels.  With the pair ordered lo <
 f(x) from t = exp(-|x - mu| / T), 1 - f(x) as f(2 mu - x) from the same t (the mirrored distance from mu is -(x - mu)
 exactly): every factor is non-negative, nothing overflows, a = b is the same branch.
 
+The dynamic chi_0(q, omega + i eta) of DESIGN.md section 16 is `dynamic_susceptibility`, with the occupation difference in the stable
+form of `pair_difference` and the bound `dynamic_tolerance`.
+
 `python tools/chi_model.py` prints one small case by the stable and by the naive F.  Design tooling: nothing in the product imports it.
 """
 
@@ -147,6 +150,116 @@ def tolerance(n_k, n, T, matrix_elements=True):
     if matrix_elements:
         side += (3 * n + 5) * n ** 1.5 / 2 + 0.75 * n
     return 2.0 * side * u / T
+
+
+def pair_difference(a, b, fa, ga, fb, gb, T):
+    """g = f(a) - f(b) from the tables of both states, not as the difference: with the pair ordered lo <= hi and y = (lo - hi) / T,
+    f(lo) - f(hi) = f(lo) (1 - f(hi)) (-expm1(y)) >= 0, and g carries the sign of the order (+ where a <= b).  Nothing cancels,
+    nothing overflows, and a == b gives a zero."""
+    a_low = a <= b
+    lo, hi = np.where(a_low, a, b), np.where(a_low, b, a)
+    value = np.where(a_low, fa, fb) * np.where(a_low, gb, ga) * (-np.expm1((lo - hi) / T))
+    return np.where(a_low, value, -value)
+
+
+def occupation_difference(a, b, mu, T):
+    """f(a) - f(b) in the stable form (broadcasts)."""
+    a, b = np.broadcast_arrays(np.asarray(a, dtype=float), np.asarray(b, dtype=float))
+    fa, ga = fermi_tables(a, mu, T)
+    fb, gb = fermi_tables(b, mu, T)
+    return pair_difference(a, b, fa, ga, fb, gb, T)
+
+
+def _frequencies(omega, eta):
+    omega = np.asarray(omega, dtype=float)
+    if omega.ndim == 0:
+        omega = omega.reshape(1)
+    if omega.ndim != 1 or omega.size < 1 or not np.all(np.isfinite(omega)):
+        raise ValueError("omega must be one finite number or a list of them")
+    eta = float(eta)
+    if not np.isfinite(eta) or not eta > 0.0 or not eta * eta > 0.0:
+        raise ValueError("eta must be finite and positive (and its square must not underflow)")
+    return omega, eta
+
+
+def dynamic_susceptibility(E, U, mesh, q, mu, T, omega, eta, matrix_elements=True, phases=None):
+    """chi_0(q, omega + i eta), complex [NQ][NW], of DESIGN.md section 16:
+
+        chi_0(q, z) = -(1 / NK) sum_k sum_{b b'} (f(E[k][b]) - f(E[k+q][b'])) / (E[k][b] - E[k+q][b'] + z) |M(k, q)[b][b']|^2
+
+    The arguments are those of `susceptibility`; ``omega``: real frequencies, any sign and order, or one number; ``eta > 0``.
+    Per pair of states p = g |M|^2 with g of `pair_difference` and Delta = E[k][b] - E[k+q][b'] (one rounding), per frequency
+    x = Delta + omega, r = 1 / (x^2 + eta^2), t = p r, and the sums of t x and of -(t eta) are taken away from +0 and divided by
+    NK: Re chi = (0 - sum t x) / NK, Im chi = (0 - sum -(t eta)) / NK -- so that a sum of zeros of either sign gives +0."""
+    E = np.asarray(E, dtype=float)
+    n = E.shape[-1]
+    flat_e = E.reshape(-1, n)
+    n_k = flat_e.shape[0]
+    q = np.asarray(q)
+    if q.dtype.kind not in "iu":
+        raise ValueError("q must be integers")
+    q = q.astype(np.int64).reshape(-1, len(mesh))
+    omega, eta = _frequencies(omega, eta)
+    f, g = fermi_tables(flat_e, mu, T)
+    out = np.zeros((q.shape[0], omega.size), dtype=complex)
+    for index, vector in enumerate(q):
+        to = shifted_points(mesh, vector)
+        a, b = flat_e[:, :, None], flat_e[to][:, None, :]
+        p = pair_difference(a, b, f[:, :, None], g[:, :, None], f[to][:, None, :], g[to][:, None, :], T)
+        if matrix_elements:
+            p = p * np.abs(overlaps(U, mesh, vector, None if phases is None else np.asarray(phases)[index])) ** 2
+        delta = a - b
+        for j, w in enumerate(omega):
+            x = delta + w
+            t = p * (1.0 / (x * x + eta * eta))
+            out[index, j] = complex((0.0 - (t * x).sum()) / n_k, (0.0 - (-(t * eta)).sum()) / n_k)
+    return out
+
+
+def dynamic_susceptibility_naive(E, U, mesh, q, mu, T, omega, eta, matrix_elements=True, phases=None):
+    """The formula as written, in complex arithmetic with f(a) - f(b) as the difference of two Fermi functions: for comparison
+    where that difference is well conditioned (tests/test_chi_dynamic_model.py states the condition)."""
+    E = np.asarray(E, dtype=float)
+    n = E.shape[-1]
+    flat_e = E.reshape(-1, n)
+    q = np.asarray(q).astype(np.int64).reshape(-1, len(mesh))
+    omega, eta = _frequencies(omega, eta)
+    with np.errstate(over="ignore"):
+        occ = 1.0 / (1.0 + np.exp((flat_e - mu) / T))
+    out = np.zeros((q.shape[0], omega.size), dtype=complex)
+    for index, vector in enumerate(q):
+        to = shifted_points(mesh, vector)
+        weight = (occ[:, :, None] - occ[to][:, None, :]).astype(complex)
+        if matrix_elements:
+            weight = weight * np.abs(overlaps(U, mesh, vector, None if phases is None else np.asarray(phases)[index])) ** 2
+        delta = flat_e[:, :, None] - flat_e[to][:, None, :]
+        for j, w in enumerate(omega):
+            out[index, j] = -(weight / (delta + complex(w, eta))).sum() / flat_e.shape[0]
+    return out
+
+
+ULP_DIV = 2.0  # allowance for the quotient 1 / (x^2 + eta^2), in units of u = 2^-53: a correctly rounded quotient (IEEE division, which
+#                both sides use) has 1
+
+
+def dynamic_tolerance(n_k, n, T, eta, spread, matrix_elements=True):
+    """tol of DESIGN.md 16.4: the bound on either component of chi - chi' of two evaluations (the kernels, this model) of the SAME
+    (E, U, mu, T, omega, eta), each in IEEE doubles with any order of summation, fused or unfused multiply-adds, exp / expm1 within
+    ULP_EXP / ULP_EXPM1 ulps and the quotient within ULP_DIV u.  ``spread`` = 2 bandwidth + |omega| (a number, or an array per
+    frequency: the bound is per frequency).  With u = 2^-53, |g| <= 1, |1 / (x + i eta)| <= 1 / eta, per side and in units of
+    1 / eta, S = n (n^2 without matrix elements) the most the moduli of one k-point's terms add up to:  the sum of NK n^2 terms of
+    either sign: NK n^2 S u;  the factors of a term, relative: (4 ULP_EXP + ULP_EXPM1 + ULP_DIV + 18) S u;  the unbounded part of
+    the exponential's argument error, absolute, 2 u per table entry: 4 S u;  x = fl(fl(E - E') + omega) is off by at most
+    u (2 |Delta| + |omega|) <= u spread and |d/dx 1 / (x + i eta)| <= 1 / eta^2: S spread / eta u;  |M|^2 as in 15.4 with the weight
+    |g| / eta <= 1 / eta in place of 1 / (4 T): (2 (3 n + 5) n^(3/2) + 3 n) u.  T does not enter: it is kept in the signature for
+    the callers that pass the call's arguments through."""
+    del T
+    u = 2.0 ** -53
+    big_s = float(n if matrix_elements else n * n)
+    side = n_k * n * n * big_s + (4 * ULP_EXP + ULP_EXPM1 + ULP_DIV + 18) * big_s + 4 * big_s + big_s * np.asarray(spread, dtype=float) / eta
+    if matrix_elements:
+        side = side + 2 * (3 * n + 5) * n ** 1.5 + 3 * n
+    return 2.0 * side * u / eta
 
 
 def static_limit(E, mu, T):
