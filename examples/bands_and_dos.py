@@ -138,6 +138,16 @@ def main():
         print("Im chi_0(X, omega + 0.1 i) at omega = %g ... %g on the same mesh in %.1f ms (Re chi_0(X, 0.1 i) = %.4f):" % (omega[0], omega[-1], dt * 1e3, dyn.chi[0, 0].real))
         print("  " + " ".join("%.4f" % x for x in dyn.chi[0].imag))
 
+        # 9. the orbital-resolved chi_0[i, j](q) on the same line: an 8 x 8 Hermitian matrix per q, one rank-(NK n^2) update on the matrix pipe.  Its
+        # largest eigenvalue is what a Stoner / RPA criterion reads (an instability where U times it reaches 1); the sum of its entries is chi_0(q) of step 7
+        model.orbital_susceptibility((m, m, m), line, temperature=0.05, n_electrons=4)  # warm up
+        t0 = time.perf_counter()
+        orb = model.orbital_susceptibility((m, m, m), line, temperature=0.05, n_electrons=4)
+        dt = time.perf_counter() - t0
+        print("largest eigenvalue of chi_0[i, j](q) along Gamma - X on the same mesh in %.1f ms (max |sum_ij chi_0[i, j] - chi_0| = %.1e):"
+              % (dt * 1e3, np.abs(orb.chi.sum(axis=(1, 2)) - chi.chi).max()))
+        print("  " + " ".join("%.4f" % x for x in np.linalg.eigvalsh(orb.chi)[:, -1]))
+
 
 if __name__ == "__main__":
     main()

@@ -490,6 +490,40 @@ int tbk_chi_dynamic_plan(int64_t nk, int n_orb, int64_t n_q, int64_t n_w, int ma
 /* (Kernel times of these calls are booked into tbk_chi_timing's three stages: the Fermi tables, the overlaps with the dynamic
  * epilogue or the dynamic pair kernel, the complex reduction; its call count includes them.) */
 
+/* ---- the orbital-resolved bare static susceptibility chi_0[i][j](q) of a uniform k mesh (not in the reference) -----------------
+ * Mesh, k+q, q, E, U, D(q), convention, mu (mode, value) and T are those of tbk_susceptibility; the eigenvectors are always used.
+ * With t = f(lo) (1 - f(hi)) h(y) >= 0 of tbk_susceptibility (-T F) (csrc/tbk_chi.hip):
+ *     A(k, q)[i; b, b'] = conj(U[k][i][b]) D(q)[i] U[k+q][i][b']
+ *     chi_0[i][j](q)    = (1 / (T NK)) sum_k sum_{b b'} t(E[k][b], E[k+q][b']) A[i; b, b'] conj(A[j; b, b'])
+ * No spin factor; static only; the sign is tbk_susceptibility's, whose chi_0(q) is the sum over (i, j).  chi_0(q) is Hermitian and
+ * positive semidefinite, chi_0(-q) = chi_0(q)^T.  The output is exactly Hermitian: entries with i <= j (in ascending orbital order)
+ * are computed, the others are their conjugates, the diagonal's imaginary part is +0.  m distinct orbitals are selected by
+ * orbitals (int32 [m], any order; NULL with m = n_orb: all of them): chi_out is [n_q][m][m] complex (Re, Im interleaved) in the
+ * caller's order, and every entry has the bits of the same entry of the full matrix.  For given (E, U, mu, T) the bits of an entry
+ * depend on q modulo the mesh, D(q), i and j alone.  |error| per component <= chi_model.orbital_tolerance.
+ * Argument errors (TBK_ERR_ARGUMENT), before any device is touched: those of tbk_susceptibility, m < 1 or m > n_orb, an index
+ * out of range or repeated, a NULL orbitals with m != n_orb, a NULL output. */
+/* The kernels alone on an eigensystem the caller brings (E, U, phases as for tbk_chi_from_eigensystem; U is required).  part_bytes:
+ * the bytes the partial sums may take, k_slice: the k-points per slice (0: the library's own), as in tbk_chi_orbital_plan. */
+int tbk_chi_orbital_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu, double T,
+                                     int64_t n_q, const int64_t* q, const double* phases, int m, const int32_t* orbitals, int64_t part_bytes,
+                                     int64_t k_slice, double* chi_out);
+/* The whole call: tbk_susceptibility's driver -- the same mu, the same resident eigensystem, the same wait on every exit. */
+int tbk_orbital_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q, int n_sel,
+                               const int32_t* orbitals, int convention, const double* pos, double* mu_out, double* chi_out);
+/* On several devices from one process: tbk_susceptibility_multi's split, a contiguous share of the vectors per handle. */
+int tbk_orbital_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
+                                     int64_t n_q, const int64_t* q, int m, const int32_t* orbitals, int convention, const double* pos,
+                                     double* mu_out, double* chi_out);
+/* How a call on nk mesh points, m of n_orb orbitals and n_q vectors is run: out[0] = the kernel's template (4: blocks of 64 x 64, four
+ * waves; 1: one tile, m <= 16, a wave per slice), out[1] = blocks with i <= j per vector, out[2] = k-points per slice -- k_slice, or for
+ * 0 the library's own, a function of (nk, n_orb) alone -- out[3] = slices, out[4] = vectors per batch (at most 4096; the partial sums
+ * take 16 out[3] m'^2 bytes per vector, m' = m padded to the block, and may take part_bytes, 0: 256 MiB; 0: not one vector fits,
+ * the call returns TBK_ERR_MEMORY), out[5] = batches.  out: int64 [6]. */
+int tbk_chi_orbital_plan(int64_t nk, int n_orb, int m, int64_t n_q, int64_t part_bytes, int64_t k_slice, int64_t* out);
+/* (Kernel times of these calls are booked into tbk_chi_timing's three stages: the Fermi tables, the rank-K update, the reduction of the
+ * slices; its call count includes them.) */
+
 /* ---- k.p models (kdotp.py:51-100): H(k) = sum_p prod_d k_d^powers[p][d] * coeffs[p] ------- */
 int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, const int32_t* powers,
                      const double* coeffs, tbk_kdotp** out);

@@ -46,6 +46,7 @@ Occupations = co.namedtuple("Occupations", ("mu", "orbital_occ", "band_occ", "ba
 DensityMatrix = co.namedtuple("DensityMatrix", ("mu", "R", "rho"))
 Susceptibility = co.namedtuple("Susceptibility", ("mu", "q", "chi"))
 DynamicSusceptibility = co.namedtuple("DynamicSusceptibility", ("mu", "q", "omega", "chi"))
+OrbitalSusceptibility = co.namedtuple("OrbitalSusceptibility", ("mu", "q", "orbitals", "chi"))
 
 
 def _devices_from_env():
@@ -1273,6 +1274,80 @@ class Model:
                                                             _lib.ptr(chi))
             )
         return DynamicSusceptibility(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, frequencies, chi)
+
+    def orbital_susceptibility(self, mesh, q, *, temperature, energy=None, n_electrons=None, orbitals=None, convention=2):
+        """
+        The orbital-resolved bare static susceptibility ``chi_0[i, j](q)`` of a uniform k mesh -- the response of the density on
+        orbital ``i`` to a field on orbital ``j``, what a multi-orbital RPA or a Stoner criterion per orbital starts from --
+        computed on the GPU from the eigensystem of the whole mesh, which never leaves it.  Not in the reference.
+
+        ``mesh``, ``q``, ``temperature``, ``energy``, ``n_electrons`` and ``convention`` are those of :meth:`susceptibility`, with
+        the same errors; the eigenvectors are always used.  ``orbitals`` selects ``m`` distinct orbital indices in
+        ``[0, size)``, in any order (an integer array-like of shape ``(m,)`` or one index); ``None`` means all of them in order.
+        Returns the named tuple ``(mu, q, orbitals, chi)``: ``mu`` and ``q`` as for :meth:`susceptibility`, ``orbitals`` as
+        ``int64 (m,)`` and ``chi`` as ``complex128 (NQ, m, m)`` in the order of ``orbitals``.
+
+        Definition.  With ``E``, ``U``, ``k+q``, ``D(q)`` and ``f`` of :meth:`susceptibility` and
+        ``t = f(lo) (1 - f(hi)) h(y) >= 0`` its pair weight (``-T F``)::
+
+            A(k, q)[i; b, b'] = conj(U[k, i, b]) D(q)[i] U[k+q, i, b']
+            chi_0[i, j](q)    = (1 / (T NK)) sum_k sum_{b, b'} t(E[k, b], E[k+q, b']) A[i; b, b'] conj(A[j; b, b'])
+
+        No spin factor; static only.  ``sum_i A[i; b, b'] = M(k, q)[b, b']``, so the sum of all entries is ``chi_0(q)`` of
+        :meth:`susceptibility`.
+
+        Properties.  (1) ``chi_0(q)`` is Hermitian and positive semidefinite; the output is exactly Hermitian: entries with
+        ``i <= j`` (in ascending orbital order) are computed, the others are their conjugates, and the diagonal's imaginary part is
+        ``+0``.  (2) ``sum_ij chi_0[i, j](q) = chi_0(q)``.  (3) ``chi_0(-q) = chi_0(q)^T``.  (4) ``4 T chi_0(q) -> 1`` (the unit
+        matrix) as ``T -> inf``.  (5) With ``mu`` 746 ``T`` or more outside the spectrum every entry is ``+0`` in both components.
+        (6) For ``convention=2`` ``q + n_d e_d`` has the bits of ``q``.  (7) ``chi_0`` does not depend on the phases of the
+        eigenvectors or on the basis inside degenerate clusters.  (8) The bits of ``chi_0[i, j](q)`` do not depend on the other
+        entries of ``q``, on their order or on the number of ``devices``; a second call gives the bits of the first.  (9) A
+        selection returns the bits of the same entries of the full matrix, whatever else is selected and in whatever order.
+
+        Error bound of either component of an entry for a given eigensystem, with ``u = 2^-53`` and 2 ulps allowed for ``exp`` and
+        ``expm1`` (DESIGN.md 17.5; ``tools/chi_model.py`` ``orbital_tolerance``)::
+
+            |error| <= [ NK size^2 / 2 + 27.5 ] u / T
+
+        The work is ``8 size^2 m^2`` flops per ``(k, q)`` on the FP64 matrix pipe.  One-dimensional models raise ``ValueError``.
+        The eigenvectors of the whole mesh must fit the device, else ``MemoryError``.  With several ``devices`` every device holds
+        the whole mesh's eigensystem and takes a contiguous share of ``q``.
+        """
+        mesh_array, vectors, t_value, mode, value, pos = self._susceptibility_arguments("orbital_susceptibility", mesh, q, temperature, energy,
+                                                                                        n_electrons, True, convention)
+        if orbitals is None:
+            selected = np.arange(self.size, dtype=np.int64)
+        else:
+            if isinstance(orbitals, (str, bytes)):
+                raise ValueError("orbitals must be an integer array of shape (m,), got {!r}".format(orbitals))
+            try:
+                selected = np.asarray(orbitals)
+            except (TypeError, ValueError):
+                raise ValueError("orbitals must be an integer array of shape (m,)") from None
+            if selected.dtype.kind not in "iu" or selected.dtype == np.uint64:
+                raise ValueError("orbitals must hold (64-bit signed) integers, got dtype {}".format(selected.dtype))
+            if selected.ndim == 0:
+                selected = selected.reshape(1)
+            if selected.ndim != 1 or selected.shape[0] < 1:
+                raise ValueError("orbitals must have shape (m,) with m >= 1, got {}".format(selected.shape))
+            selected = np.ascontiguousarray(selected, dtype=np.int64)
+            if selected.min() < 0 or selected.max() >= self.size:
+                raise ValueError("orbitals must lie in [0, {}), got {}".format(self.size, selected.tolist()))
+            if np.unique(selected).shape[0] != selected.shape[0]:
+                raise ValueError("orbitals must be distinct, got {}".format(selected.tolist()))
+        chosen = np.ascontiguousarray(selected, dtype=np.int32)
+        mu = np.empty(4, dtype=np.float64)
+        chi = np.empty((vectors.shape[0], chosen.shape[0], chosen.shape[0]), dtype=np.complex128)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_orbital_susceptibility_multi(handles, n_handles, _lib.ptr(mesh_array), mode, value, t_value, vectors.shape[0],
+                                                            _lib.ptr(vectors), chosen.shape[0], _lib.ptr(chosen), int(convention), _lib.ptr(pos),
+                                                            _lib.ptr(mu), _lib.ptr(chi))
+            )
+        return OrbitalSusceptibility(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, selected, chi)
 
     def construct_kdotp(self, k, order):
         """

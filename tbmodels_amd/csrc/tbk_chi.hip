@@ -45,6 +45,19 @@
 //
 // Frequencies go in passes of tbk_chi_dynamic_plan's size when the partials of one vector for all of them do not fit; the overlaps
 // are computed again per pass.
+//
+// The orbital-resolved chi_0[i][j](q) (chi_model.orbital_susceptibility) keeps the orbital indices that M sums
+// away:
+//
+//   A(k, q)[i; b, b'] = conj(U[k][i][b]) D(q)[i] U[k+q][i][b']
+//   chi_0[i][j](q)    = (1 / (T NK)) sum_k sum_{b b'} t A[i; b, b'] conj(A[j; b, b'])        t = f(lo) (1 - f(hi)) h(y) = -T F
+//
+//   chi_orbital_kernel<BT>  one Hermitian rank-K update per vector, K = (k, b, b'), on v_mfma_f64_16x16x4_f64: the operands X = t A and
+//                       Y = A are made while staging, the block of (i, j) stays in registers over a slice of k-points, one complex
+//                       partial block goes to part[q][slice][i][j].  Blocks with bi <= bj of the ascending selection only.
+//   chi_reduce_orb_kernel  the slices in index order, / T / NK, the entry and its mirror (the conjugate) at the caller's places.
+//
+// tbk_chi_orbital_plan chooses template, slice length (a function of NK and n_orb alone), slices and batch.
 
 #include <algorithm>
 #include <cmath>
@@ -505,6 +518,218 @@ __global__ void __launch_bounds__(CHI_THREADS) chi_reduce_dyn_kernel(const doubl
     if (tid == 0) chi[(size_t)blockIdx.y * n_w + w_first + blockIdx.x] = make_double2((0.0 - red[0][0]) / nk, (0.0 - red[1][0]) / nk);
 }
 
+// ---- the orbital-resolved chi_0[i][j](q) ---------------------------------------------------------------------
+// (a b) of two complex numbers, the multiply-adds fused as written: both templates of chi_orbital_kernel round alike
+__device__ __forceinline__ double2 chi_cmul(double2 a, double2 b) {
+    return make_double2(fma(a.x, b.x, -(a.y * b.y)), fma(a.x, b.y, a.y * b.x));
+}
+
+// The MFMAs of one staged panel of 16 b' on the wave's tile row ti and all BT tiles of the block: four steps of four b', the X pair
+// read once per step, per tile the Y pair and the four real products (the last with the negate bit: - Xr Yi^T).  No tile is guarded:
+// a branch around an MFMA makes its accumulator a phi of two values, which the compiler keeps in VGPRs and copies to and from the
+// AGPRs around every group of MFMAs (32 v_accvgpr moves and a drain of the pipe per four).  So the loop holds ds_read_b64 and MFMA
+// only, and a tile that is never written (padding: zeros; below the diagonal of a diagonal block) is multiplied like any other.
+template <int S, int BT>
+__device__ __forceinline__ void chi_orb_tiles(const double (*pl)[16][S], int ti, int lane, chi_d4 (&accr)[BT], chi_d4 (&acci)[BT]) {
+#pragma unroll 1
+    for (int q4 = 0; q4 < 4; ++q4) {  // (not unrolled: dm_project_kernel's note on registers)
+        const int kq = 4 * q4 + (lane >> 4);
+        const double xr = pl[0][kq][ti * 16 + (lane & 15)], xi = pl[1][kq][ti * 16 + (lane & 15)];
+#pragma unroll
+        for (int tj = 0; tj < BT; ++tj) {
+            const double yr = pl[2][kq][tj * 16 + (lane & 15)], yi = pl[3][kq][tj * 16 + (lane & 15)];
+            accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, yr, accr[tj], 0, 0, 0);
+            accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, yi, accr[tj], 0, 0, 0);
+            acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, yr, acci[tj], 0, 0, 0);
+            acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, yi, acci[tj], 0, 0, 1);  // - Xr Yi^T
+        }
+    }
+}
+
+// One Hermitian rank-K update per vector, K = (k, b, b') of a slice of k-points: chi(q) = sum X Y^H with Y = A, X = t A,
+// A[i; b, b'] = conj(U[k][i][b]) D[i] U[k+q][i][b'], t = chi_pair_weight(E[k][b], E[k+q][b']).  BT tiles of 16 along each side of the
+// workgroup's block of (i, j): 4 (one slice per workgroup, wave t owns tile row t) or 1 (m <= 16: four slices per workgroup, one per
+// wave).  grid: (slices / KPW, blocks with bi <= bj, vectors of the batch).  orb: the selected orbitals [m], ascending; rows of the
+// padding are zeros.  Every element walks K in one order in both templates: k ascending, b ascending, b' ascending in panels of 16
+// from 0, four b' per MFMA step -- and nothing else enters its bits.  The accumulators stay in registers over the whole slice; one
+// complex partial block goes to part[q][slice][mp][mp] (tiles below the diagonal or of the
+// padding are not written; <4> multiplies them all the same, see chi_orb_tiles).
+template <int BT>
+__global__ void __launch_bounds__(CHI_THREADS) chi_orbital_kernel(const double2* __restrict__ U, const double* __restrict__ E,
+                                                                  const double* __restrict__ tab, ChiMesh g, int n,
+                                                                  const int32_t* __restrict__ Q, const double2* __restrict__ D, double inv_t,
+                                                                  const int32_t* __restrict__ orb, int m, int mp, int64_t ks, int64_t slices,
+                                                                  double2* __restrict__ part) {
+    constexpr int RB = 16 * BT;               // rows (and columns) of the block
+    constexpr int KPW = BT == 1 ? 4 : 1;      // slices per workgroup
+    constexpr int TEAM = CHI_THREADS / KPW;   // threads that stage one slice's panels
+    constexpr int STEP = TEAM / 16;           // rows between the four a thread stages
+    constexpr int S = BT == 1 ? 18 : 82;      // doubles between the b' rows of a plane (dm_project_kernel's)
+    __shared__ double planes[KPW][4][16][S];  // Xr, Xi of the block's rows i; Yr, Yi of its columns j
+    __shared__ double tw[KPW][TEAM];          // t[b][b'] of TEAM b' at once: one chi_pair_weight per (k, b, b')
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int team = BT == 1 ? wave : 0, tt = tid - team * TEAM;
+    const int nb = mp / RB;
+    int bi = 0, bj = (int)blockIdx.y;
+    while (bj >= nb - bi) {
+        bj -= nb - bi;
+        ++bi;
+    }
+    bj += bi;
+    const int64_t sl = (int64_t)blockIdx.x * KPW + team;
+    const int64_t ql = blockIdx.z;
+    const bool live = sl < slices;
+    const int64_t k0 = live ? sl * ks : 0, k1 = live ? (k0 + ks < g.nk ? k0 + ks : g.nk) : 0;
+    const double2* Dq = D ? D + (size_t)ql * n : nullptr;
+    double(*pl)[16][S] = planes[team];
+    double* twt = tw[team];
+    const int ti = BT == 1 ? 0 : wave;               // the wave's tile row
+    const bool row_live = bi * RB + ti * 16 < m;     // (wave-uniform)
+    const bool diag = bi == bj;
+    chi_d4 accr[BT], acci[BT];
+#pragma unroll
+    for (int tj = 0; tj < BT; ++tj) accr[tj] = acci[tj] = chi_d4{0.0, 0.0, 0.0, 0.0};
+    // The accumulators' home is the AGPRs over all the loops below: an empty statement (no instruction) that reads them as AGPRs
+    // stands behind the loops, and in <1> another ahead of them.  Without these the compiler keeps them in VGPRs and moves them in
+    // and out around every group of MFMAs; where the statements must stand was read off the built code of each template
+    // (DESIGN.md 17.2), and the no-copy state of both loops is what to look for after a compiler change.
+    if constexpr (BT == 1) asm volatile("" : "+a"(accr[0]), "+a"(acci[0]));
+    const int sb = tt & 15, srow0 = tt >> 4;  // the b' (row of the panel) and the first orbital row this thread stages
+    int oi[4], oj[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int pi = bi * RB + srow0 + r * STEP, pj = bj * RB + srow0 + r * STEP;
+        oi[r] = pi < m ? orb[pi] : -1;
+        oj[r] = pj < m ? orb[pj] : -1;
+    }
+    const int64_t items = g.nk * n;
+    const int64_t kn = BT == 1 ? ks : k1 - k0;  // (<1>: a team past its slice keeps the barriers; <4>: one slice, its own length)
+    for (int64_t kk = 0; kk < kn; ++kk) {
+        const int64_t k = k0 + kk;
+        const bool valid = BT != 1 || k < k1;  // (uniform in the team)
+        const int64_t kp = valid ? chi_shifted(g, k, Q + ql * 3) : 0;
+        const double2* Uk = U + (valid ? (size_t)k * n * n : 0);
+        const double2* Up = U + (size_t)kp * n * n;
+        const double *Ea = E + (valid ? (size_t)k * n : 0), *Eb = E + (size_t)kp * n;
+        const double *fa = tab + (valid ? (size_t)k * n : 0), *ga = fa + items, *fb = tab + (size_t)kp * n, *gb = fb + items;
+        // <4>: the thread's entries of U[k+q] for a panel are loaded one panel ahead, under the MFMAs of the panel before (they do
+        // not depend on b: the panel behind the last of one b is the first of the next); <1> loads them where it uses them and keeps
+        // three waves per SIMD
+        double2 ui[4], uj[4];
+        auto fetch = [&](int p0) {
+            const int bp = p0 + sb;
+            const bool in = valid && bp < n;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                ui[r] = uj[r] = make_double2(0.0, 0.0);
+                if (in && oi[r] >= 0) ui[r] = Up[(size_t)oi[r] * n + bp];
+                if (!diag && in && oj[r] >= 0) uj[r] = Up[(size_t)oj[r] * n + bp];
+            }
+        };
+        if constexpr (BT != 1) fetch(0);
+        for (int b = 0; b < n; ++b) {
+            // c = conj(U[k][i][b]) D[i] of the thread's rows: one value per i and b
+            double2 ci[4], cj[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                ci[r] = cj[r] = make_double2(0.0, 0.0);
+                if (valid && oi[r] >= 0) {
+                    const double2 u = Uk[(size_t)oi[r] * n + b];
+                    ci[r] = make_double2(u.x, -u.y);
+                    if (Dq) ci[r] = chi_cmul(ci[r], Dq[oi[r]]);
+                }
+                if (!diag && valid && oj[r] >= 0) {
+                    const double2 u = Uk[(size_t)oj[r] * n + b];
+                    cj[r] = make_double2(u.x, -u.y);
+                    if (Dq) cj[r] = chi_cmul(cj[r], Dq[oj[r]]);
+                }
+            }
+            const double ea = Ea[b], fav = fa[b], gav = ga[b];
+            for (int s0 = 0; s0 < n; s0 += TEAM) {
+                {
+                    // (the panels that read the previous weights are behind their second barrier)
+                    const int bp = s0 + tt;
+                    twt[tt] = (valid && bp < n) ? chi_pair_weight(ea, fav, gav, Eb[bp], fb[bp], gb[bp], inv_t) : 0.0;
+                }
+                const int s1 = s0 + TEAM < n ? s0 + TEAM : n;
+                for (int p0 = s0; p0 < s1; p0 += 16) {
+                    __syncthreads();  // the previous panel has been read, the weights are written
+                    const int bp = p0 + sb;
+                    const bool in = valid && bp < n;
+                    const double t = twt[bp - s0];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = srow0 + r * STEP;
+                        double2 vi = make_double2(0.0, 0.0), vj = vi;
+                        if constexpr (BT == 1) {
+                            if (in && oi[r] >= 0) vi = Up[(size_t)oi[r] * n + bp];
+                            if (!diag && in && oj[r] >= 0) vj = Up[(size_t)oj[r] * n + bp];
+                        } else {
+                            vi = ui[r];
+                            vj = uj[r];
+                        }
+                        const double2 ai = chi_cmul(ci[r], vi);
+                        const double2 aj = diag ? ai : chi_cmul(cj[r], vj);
+                        pl[0][sb][row] = t * ai.x;
+                        pl[1][sb][row] = t * ai.y;
+                        pl[2][sb][row] = aj.x;
+                        pl[3][sb][row] = aj.y;
+                    }
+                    if constexpr (BT != 1) fetch(p0 + 16 < n ? p0 + 16 : 0);
+                    __syncthreads();
+                    // <4>: every wave multiplies its whole tile row in every k of the slice, so that no branch stands around the
+                    // MFMAs (chi_orb_tiles); a dead row is zeros and is not written.  <1>: a team past its slice has nothing to add
+                    if constexpr (BT == 1) {
+                        if (valid && row_live) chi_orb_tiles<S, BT>(pl, ti, lane, accr, acci);
+                    } else {
+                        chi_orb_tiles<S, BT>(pl, ti, lane, accr, acci);
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int tj = 0; tj < BT; ++tj) asm volatile("" : "+a"(accr[tj]), "+a"(acci[tj]));  // (see at the accumulators' declaration)
+    if (!live || !row_live) return;
+    // lane (q, c), register r: row q + 4 r, column c of the tile
+    double2* out = part + ((size_t)ql * slices + sl) * mp * mp;
+#pragma unroll
+    for (int tj = 0; tj < BT; ++tj) {
+        if (bj * RB + tj * 16 < m && !(diag && tj < ti)) {
+            const int gj = bj * RB + tj * 16 + (lane & 15);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int gi = bi * RB + ti * 16 + (lane >> 4) + 4 * r;
+                out[(size_t)gi * mp + gj] = make_double2(accr[tj][r], acci[tj][r]);
+            }
+        }
+    }
+}
+
+// chi[q][perm[i]][perm[j]] = (the slices of part[q][.][i][j] in index order) / T / NK and its mirror, the conjugate: one thread per
+// (q, i <= j) of the ascending list, perm its places in the caller's order.  The mirror's imaginary part is the difference from +0 and
+// the diagonal's is +0.  grid: (elements / 256, vectors of the batch)
+__global__ void __launch_bounds__(CHI_THREADS) chi_reduce_orb_kernel(const double2* __restrict__ part, int m, int mp, int64_t slices, double T,
+                                                                     double nk, const int32_t* __restrict__ perm, double2* __restrict__ chi) {
+    const int64_t e = (int64_t)blockIdx.x * CHI_THREADS + threadIdx.x;
+    if (e >= (int64_t)m * m) return;
+    const int i = (int)(e / m), j = (int)(e - (int64_t)i * m);
+    if (i > j) return;
+    const double2* p = part + (size_t)blockIdx.y * slices * mp * mp + (size_t)i * mp + j;
+    double re = 0.0, im = 0.0;
+    for (int64_t s = 0; s < slices; ++s) {
+        const double2 v = p[(size_t)s * mp * mp];
+        re += v.x;
+        im += v.y;
+    }
+    re = re / T / nk;
+    im = i == j ? 0.0 : im / T / nk;
+    double2* out = chi + (size_t)blockIdx.y * m * m;
+    const int ci = perm[i], cj = perm[j];
+    out[(size_t)ci * m + cj] = make_double2(re, im);
+    if (i != j) out[(size_t)cj * m + ci] = make_double2(re, 0.0 - im);
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 // the frequencies of a dynamic call (n_w = 0: the static call)
 struct ChiFreq {
@@ -663,6 +888,137 @@ int chi_launch_all(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const doub
     return TBK_OK;
 }
 
+// ---- the orbital-resolved call's plan, arguments and launches ----------------------------------------------------------------------
+constexpr int64_t CHI_ORB_AMORTISE = 1024;  // (b, b') pairs a slice walks at least per register-resident block
+constexpr int64_t CHI_ORB_SLICES = 1024;    // slices of one vector, about: four workgroups (or one of four slices) per compute unit
+
+struct ChiOrbPlan {
+    ChiMesh mesh;
+    int n = 0;            // orbitals
+    int m = 0;            // selected orbitals
+    int mp = 0;           // m padded to the block
+    int bt = 0;           // template of chi_orbital_kernel: 4, 1 (m <= 16)
+    int64_t blocks = 1;   // blocks with bi <= bj of one vector
+    int64_t ks = 1;       // k-points per slice
+    int64_t slices = 1;
+    int64_t batch = 1;    // vectors per launch
+    int64_t batches = 1;
+    size_t part_bytes() const { return (size_t)batch * slices * mp * mp * sizeof(double2); }
+};
+
+// the library's slice length, a function of (NK, n_orb) alone -- not of the selection, the vectors, the batch or the handles, so that
+// the bits of an element are those of any call that contains it: long enough to walk CHI_ORB_AMORTISE pairs per block held in
+// registers, short enough for about CHI_ORB_SLICES slices per vector, and long enough that four vectors' partials of the full matrix
+// fit the budget
+int64_t chi_orb_slice(int64_t nk, int n_orb) {
+    const int64_t n2 = (int64_t)n_orb * n_orb, np = ((int64_t)n_orb + 63) / 64 * 64;
+    const int64_t amortise = (CHI_ORB_AMORTISE + n2 - 1) / n2, fill = (nk + CHI_ORB_SLICES - 1) / CHI_ORB_SLICES;
+    const int64_t most = std::max<int64_t>(1, (int64_t)(CHI_PART_BUDGET / 4 / (sizeof(double2) * (size_t)np * (size_t)np)));
+    return std::min(nk, std::max(std::max(amortise, fill), (nk + most - 1) / most));
+}
+
+// the one place that chooses: template, blocks, slice length (k_slice = 0: the library's), slices, batch from the bytes the partials
+// may take (0: the budget)
+void chi_orb_plan_sizes(int64_t nk, int n_orb, int m, int64_t n_q, size_t mem, int64_t k_slice, ChiOrbPlan* L) {
+    L->n = n_orb;
+    L->m = m;
+    L->bt = m <= 16 ? 1 : 4;
+    const int rb = 16 * L->bt;
+    const int64_t nb = (m + rb - 1) / rb;
+    L->mp = (int)(nb * rb);
+    L->blocks = nb * (nb + 1) / 2;
+    L->ks = k_slice > 0 ? std::min(k_slice, nk) : chi_orb_slice(nk, n_orb);
+    L->slices = (nk + L->ks - 1) / L->ks;
+    const size_t per_q = (size_t)L->slices * L->mp * L->mp * sizeof(double2);
+    const size_t room = mem == 0 ? CHI_PART_BUDGET : mem;
+    L->batch = std::max<int64_t>(0, std::min<int64_t>(std::min(n_q, CHI_MAX_BATCH), (int64_t)(room / per_q)));
+    L->batches = L->batch == 0 ? 0 : (n_q + L->batch - 1) / L->batch;
+}
+
+int chi_orb_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int m, int64_t n_q, size_t mem, int64_t k_slice, ChiOrbPlan* out) {
+    ChiOrbPlan L;
+    L.mesh.n[0] = mesh[0];
+    L.mesh.n[1] = mesh[1];
+    L.mesh.n[2] = dim == 3 ? mesh[2] : 1;
+    L.mesh.nk = nk;
+    TBK_ARG(nk <= CHI_MAX_NK, "the susceptibility takes meshes of up to 2^23 points");
+    chi_orb_plan_sizes(nk, n_orb, m, n_q, mem, k_slice, &L);
+    if (L.batch < 1) {
+        tbk_set_error("the partial sums of one orbital-resolved susceptibility vector need %zu bytes of device memory",
+                      (size_t)L.slices * L.mp * L.mp * sizeof(double2));
+        return TBK_ERR_MEMORY;
+    }
+    *out = L;
+    return TBK_OK;
+}
+
+// the selection of an orbital-resolved call (off: the scalar calls)
+struct ChiOrb {
+    bool on = false;
+    int m = 0;
+    const int32_t* orbitals = nullptr;  // host [m] or NULL: all of them in order (m = n_orb)
+};
+
+// lists[0 .. m): the selection in ascending order; lists[m .. 2 m): the place of each in the caller's order
+int chi_orb_lists(const ChiOrb& ob, int n_orb, std::vector<int32_t>* lists) {
+    TBK_ARG(ob.m >= 1 && ob.m <= n_orb, "m < 1 or more selected orbitals than the model has");
+    TBK_ARG(ob.orbitals != nullptr || ob.m == n_orb, "orbitals is NULL and m is not n_orb");
+    try {
+        lists->assign((size_t)ob.m * 2, 0);
+    } catch (...) {
+        tbk_set_error("cannot allocate the orbital list");
+        return TBK_ERR_MEMORY;
+    }
+    for (int p = 0; p < ob.m; ++p) {
+        const int32_t o = ob.orbitals ? ob.orbitals[p] : p;
+        TBK_ARG(o >= 0 && o < n_orb, "an orbital index is out of range");
+        (*lists)[(size_t)ob.m + p] = p;
+    }
+    int32_t* perm = lists->data() + ob.m;
+    const int32_t* given = ob.orbitals;
+    std::sort(perm, perm + ob.m, [given](int32_t a, int32_t b) { return given ? given[a] < given[b] : a < b; });
+    for (int p = 0; p < ob.m; ++p) (*lists)[(size_t)p] = given ? given[perm[p]] : p;
+    for (int p = 1; p < ob.m; ++p) TBK_ARG((*lists)[(size_t)p] != (*lists)[(size_t)p - 1], "an orbital index is repeated");
+    return TBK_OK;
+}
+
+// all batches of n_q vectors; d_lists: chi_orb_lists' on the device; d_chi [n_q][m][m] complex
+int chi_orb_launch_all(hipStream_t s, const ChiOrbPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, double* d_tab,
+                       const int32_t* d_Q, const double* d_D, const int32_t* d_lists, int64_t n_q, double mu, double T, double* d_part,
+                       double* d_chi) {
+    const double inv_t = 1.0 / T;
+    const int64_t items = L.mesh.nk * L.n;
+    if (ev) ev->start(0);
+    hipLaunchKernelGGL(chi_fermi_kernel, dim3((unsigned)((items + CHI_THREADS - 1) / CHI_THREADS)), dim3(CHI_THREADS), 0, s, d_E, items, mu, T,
+                       d_tab);
+    if (ev) ev->stop();
+    TBK_HIP(hipGetLastError());
+    const int64_t elements = (int64_t)L.m * L.m;
+    for (int64_t q0 = 0; q0 < n_q; q0 += L.batch) {
+        const int64_t nq = std::min(L.batch, n_q - q0);
+        const double2* D = d_D ? reinterpret_cast<const double2*>(d_D) + (size_t)q0 * L.n : nullptr;
+        if (ev) ev->start(1);
+        if (L.bt == 1) {
+            hipLaunchKernelGGL((chi_orbital_kernel<1>), dim3((unsigned)((L.slices + 3) / 4), 1, (unsigned)nq), dim3(CHI_THREADS), 0, s,
+                               reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q + q0 * 3, D, inv_t, d_lists, L.m, L.mp, L.ks,
+                               L.slices, reinterpret_cast<double2*>(d_part));
+        } else {
+            hipLaunchKernelGGL((chi_orbital_kernel<4>), dim3((unsigned)L.slices, (unsigned)L.blocks, (unsigned)nq), dim3(CHI_THREADS), 0, s,
+                               reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q + q0 * 3, D, inv_t, d_lists, L.m, L.mp, L.ks,
+                               L.slices, reinterpret_cast<double2*>(d_part));
+        }
+        if (ev) ev->stop();
+        TBK_HIP(hipGetLastError());
+        if (ev) ev->start(2);
+        hipLaunchKernelGGL(chi_reduce_orb_kernel, dim3((unsigned)((elements + CHI_THREADS - 1) / CHI_THREADS), (unsigned)nq), dim3(CHI_THREADS), 0,
+                           s, reinterpret_cast<const double2*>(d_part), L.m, L.mp, L.slices, T, (double)L.mesh.nk, d_lists + L.m,
+                           reinterpret_cast<double2*>(d_chi) + (size_t)q0 * elements);
+        if (ev) ev->stop();
+        TBK_HIP(hipGetLastError());
+    }
+    return TBK_OK;
+}
+
 int chi_check(double T, int64_t n_q, const int64_t* q, const double* chi_out, int n_orb) {
     TBK_ARG(std::isfinite(T) && T > 0.0, "the temperature is not finite or not positive");
     TBK_ARG(n_q >= 1, "n_q < 1");
@@ -751,8 +1107,8 @@ static int chi_from_eigensystem(int device, int dim, const int32_t* mesh, int n_
 
 // the whole call, static (fr.n_w = 0, chi_out double [n_q]) or dynamic (complex [n_q][n_w])
 static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T, int64_t n_q,
-                   const int64_t* q, const ChiFreq& fr, int matrix_elements, int convention, const double* pos, double* mu_out,
-                   double* chi_out) {
+                   const int64_t* q, const ChiFreq& fr, const ChiOrb& ob, int matrix_elements, int convention, const double* pos,
+                   double* mu_out, double* chi_out) {
     TBK_ARG(mu_out != nullptr, "mu is NULL");
     TBK_ARG(mode == 0 || mode == 1, "mode must be 0 (value = energy) or 1 (value = n_electrons)");
     TBK_ARG(handles != nullptr && n_handles >= 1 && handles[0] != nullptr, "no handles");
@@ -763,6 +1119,13 @@ static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_
         TBK_CHECK(tbk_fermi_check_electrons(value, handles[0]->n_orb));
     else
         TBK_ARG(std::isfinite(value), "the energy is not finite");
+    // the orbital-resolved call's own arguments (ob.on), before any device work
+    std::vector<int32_t> h_lists;
+    if (ob.on) {
+        TBK_ARG(matrix_elements != 0, "the orbital-resolved susceptibility needs the eigenvectors");
+        TBK_CHECK(chi_orb_lists(ob, handles[0]->n_orb, &h_lists));
+    }
+    const size_t l_bytes = h_lists.size() * sizeof(int32_t);
     // mu: the slab route of tbk_occupations as it stands
     OccStaged staged;
     TBK_CHECK(staged.make(handles, n_handles, mesh));
@@ -780,7 +1143,8 @@ static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_
     const TetraSlabs share(n_q, n_handles);
     const size_t e_bytes = (size_t)nk * n_orb * sizeof(double), nn2 = (size_t)n_orb * n_orb * 2;
     // per vector: one double, or n_w complex numbers; the frequencies follow the results
-    const size_t out_per_q = fr.n_w == 0 ? sizeof(double) : (size_t)fr.n_w * sizeof(double2), w_bytes = (size_t)fr.n_w * sizeof(double);
+    const size_t out_per_q = ob.on ? (size_t)ob.m * ob.m * sizeof(double2) : fr.n_w == 0 ? sizeof(double) : (size_t)fr.n_w * sizeof(double2);
+    const size_t w_bytes = (size_t)fr.n_w * sizeof(double);
     std::vector<SpanRecorder> ev((size_t)share.busy());
     ChiDrain drain;
     for (int i = 0; i < share.busy(); ++i) {
@@ -793,13 +1157,20 @@ static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_
         TBK_CHECK(m->ws_chi_k.reserve(h_k.size() * sizeof(double)));
         TBK_CHECK(chi_reserve(m->ws_chi_e, 3 * e_bytes, "the eigenvalues and Fermi tables of the whole mesh"));
         if (with_u) TBK_CHECK(chi_reserve(m->ws_chi_u, (size_t)nk * nn2 * sizeof(double), "the eigenvectors of the whole mesh"));
-        TBK_CHECK(m->ws_chi_q.reserve((size_t)q_n * (3 * sizeof(int32_t) + out_per_q + (with_d ? n_orb * sizeof(double2) : 0)) + w_bytes + 256));
+        TBK_CHECK(m->ws_chi_q.reserve((size_t)q_n * (3 * sizeof(int32_t) + out_per_q + (with_d ? n_orb * sizeof(double2) : 0)) + w_bytes + l_bytes + 256));
         // the batch from the memory that is left for the partials, the chunk of the eigenvector walk from what is left then
         size_t free_b = 0, total_b = 0;
         TBK_HIP(hipMemGetInfo(&free_b, &total_b));
+        const size_t room = std::max<size_t>(1, std::min(CHI_PART_BUDGET, std::max(m->ws_chi_part.bytes, free_b / 4)));
         ChiPlan L;
-        TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, q_n, fr.n_w, with_u, std::max<size_t>(1, std::min(CHI_PART_BUDGET, std::max(m->ws_chi_part.bytes, free_b / 4))), &L));
-        TBK_CHECK(m->ws_chi_part.reserve(L.part_bytes()));
+        ChiOrbPlan LO;
+        if (ob.on) {
+            TBK_CHECK(chi_orb_plan(dim, mesh, nk, n_orb, ob.m, q_n, room, 0, &LO));
+            TBK_CHECK(m->ws_chi_part.reserve(LO.part_bytes()));
+        } else {
+            TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, q_n, fr.n_w, with_u, room, &L));
+            TBK_CHECK(m->ws_chi_part.reserve(L.part_bytes()));
+        }
         double* d_k = m->ws_chi_k.as<double>();
         double* d_E = m->ws_chi_e.as<double>();
         double* d_U = m->ws_chi_u.as<double>();
@@ -809,6 +1180,8 @@ static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_
         char* behind = m->ws_chi_q.as<char>() + dos_align256((size_t)q_n * out_per_q + w_bytes);
         double* d_D = with_d ? reinterpret_cast<double*>(behind) : nullptr;
         int32_t* d_Q = reinterpret_cast<int32_t*>(behind + (with_d ? (size_t)q_n * n_orb * sizeof(double2) : 0));
+        int32_t* d_lists = d_Q + (size_t)q_n * 3;  // (the orbital-resolved call's selection, behind the reduced vectors)
+        if (ob.on) TBK_HIP(hipMemcpyAsync(d_lists, h_lists.data(), l_bytes, hipMemcpyHostToDevice, m->stream));
         TBK_HIP(hipMemcpyAsync(d_k, h_k.data(), h_k.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
         TBK_HIP(hipMemcpyAsync(d_Q, h_Q.data() + q_lo * 3, (size_t)q_n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
         if (d_W) TBK_HIP(hipMemcpyAsync(d_W, fr.omega, w_bytes, hipMemcpyHostToDevice, m->stream));
@@ -825,8 +1198,12 @@ static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_
         } else {
             TBK_CHECK(tbk_eigenval_device_hint(m, d_k, h_k.data(), nk, d_E));
         }
-        TBK_CHECK(chi_launch_all(m->stream, L, &ev[(size_t)i], d_U, d_E, d_E + (size_t)nk * n_orb, d_Q, d_D, q_n, mu, T, d_W, fr.eta,
-                                 m->ws_chi_part.as<double>(), d_chi));
+        if (ob.on)
+            TBK_CHECK(chi_orb_launch_all(m->stream, LO, &ev[(size_t)i], d_U, d_E, d_E + (size_t)nk * n_orb, d_Q, d_D, d_lists, q_n, mu, T,
+                                         m->ws_chi_part.as<double>(), d_chi));
+        else
+            TBK_CHECK(chi_launch_all(m->stream, L, &ev[(size_t)i], d_U, d_E, d_E + (size_t)nk * n_orb, d_Q, d_D, q_n, mu, T, d_W, fr.eta,
+                                     m->ws_chi_part.as<double>(), d_chi));
         TBK_HIP(hipMemcpyAsync(reinterpret_cast<char*>(chi_out) + (size_t)q_lo * out_per_q, d_chi, (size_t)q_n * out_per_q, hipMemcpyDeviceToHost,
                                m->stream));
     }
@@ -850,7 +1227,7 @@ extern "C" int tbk_chi_from_eigensystem(int device, int dim, const int32_t* mesh
 extern "C" int tbk_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
                                         int64_t n_q, const int64_t* q, int matrix_elements, int convention, const double* pos, double* mu_out,
                                         double* chi_out) {
-    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, ChiFreq(), matrix_elements, convention, pos, mu_out, chi_out);
+    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, ChiFreq(), ChiOrb(), matrix_elements, convention, pos, mu_out, chi_out);
 }
 
 extern "C" int tbk_chi_dynamic_plan(int64_t nk, int n_orb, int64_t n_q, int64_t n_w, int matrix_elements, int64_t part_bytes, int64_t* out) {
@@ -883,7 +1260,7 @@ extern "C" int tbk_dynamic_susceptibility_multi(tbk_model* const* handles, int n
     fr.n_w = n_w;
     fr.omega = omega;
     fr.eta = eta;
-    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, fr, matrix_elements, convention, pos, mu_out, chi_out);
+    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, fr, ChiOrb(), matrix_elements, convention, pos, mu_out, chi_out);
 }
 
 extern "C" int tbk_dynamic_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q,
@@ -900,4 +1277,78 @@ extern "C" int tbk_susceptibility(tbk_model* m, const int32_t* mesh, int mode, d
 extern "C" int tbk_chi_timing(tbk_model* m, double* ms, int64_t* calls, int reset) {
     TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr, "model / ms / calls is NULL");
     return tbk_timed_read(m, TIMED_CHI, 3, ms, calls, nullptr, reset);
+}
+
+// ---- the orbital-resolved chi_0[i][j](q) -----------------------------------------------------------------------------------------
+extern "C" int tbk_chi_orbital_plan(int64_t nk, int n_orb, int m, int64_t n_q, int64_t part_bytes, int64_t k_slice, int64_t* out) {
+    TBK_ARG(nk >= 1 && n_orb >= 1 && n_orb <= CHI_MAX_ORB && m >= 1 && m <= n_orb && n_q >= 1 && part_bytes >= 0 && k_slice >= 0 && out != nullptr,
+            "nk / n_orb / m / n_q < 1, more than 16320 orbitals, m > n_orb, part_bytes / k_slice < 0 or out is NULL");
+    ChiOrbPlan L;
+    chi_orb_plan_sizes(nk, n_orb, m, n_q, (size_t)part_bytes, k_slice, &L);
+    out[0] = L.bt;
+    out[1] = L.blocks;
+    out[2] = L.ks;
+    out[3] = L.slices;
+    out[4] = L.batch;
+    out[5] = L.batches;
+    return TBK_OK;
+}
+
+extern "C" int tbk_chi_orbital_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu,
+                                                double T, int64_t n_q, const int64_t* q, const double* phases, int m, const int32_t* orbitals,
+                                                int64_t part_bytes, int64_t k_slice, double* chi_out) {
+    int64_t nk = 0;
+    TBK_CHECK(tetra_check_mesh(dim, mesh, OCC_MESH, &nk));
+    TBK_ARG(E != nullptr, "E is NULL");
+    TBK_ARG(std::isfinite(mu), "the chemical potential is not finite");
+    TBK_CHECK(chi_check(T, n_q, q, chi_out, n_orb));
+    TBK_ARG(U != nullptr, "U is NULL: the orbital-resolved susceptibility needs the eigenvectors");
+    TBK_ARG(part_bytes >= 0 && k_slice >= 0, "part_bytes / k_slice < 0");
+    ChiOrb ob;
+    ob.on = true;
+    ob.m = m;
+    ob.orbitals = orbitals;
+    std::vector<int32_t> h_lists;
+    TBK_CHECK(chi_orb_lists(ob, n_orb, &h_lists));
+    TBK_CHECK(tetra_check_device(device));
+    ChiOrbPlan L;
+    TBK_CHECK(chi_orb_plan(dim, mesh, nk, n_orb, m, n_q, (size_t)part_bytes, k_slice, &L));
+    const size_t out_bytes = (size_t)n_q * m * m * sizeof(double2);
+    std::vector<int32_t> h_Q;
+    TBK_CHECK(chi_reduce_q(dim, mesh, n_q, q, &h_Q));
+    const size_t e_bytes = (size_t)nk * n_orb * sizeof(double), u_bytes = (size_t)nk * n_orb * n_orb * sizeof(double2);
+    const size_t d_bytes = (size_t)n_q * n_orb * sizeof(double2), l_bytes = h_lists.size() * sizeof(int32_t);
+    DevBuf d_E, d_U, d_tab, d_Q, d_D, d_lists, d_part, d_chi;
+    TBK_CHECK(d_E.reserve(e_bytes));
+    TBK_CHECK(d_tab.reserve(2 * e_bytes));
+    TBK_CHECK(chi_reserve(d_U, u_bytes, "the eigenvectors of the whole mesh"));
+    TBK_CHECK(d_Q.reserve(h_Q.size() * sizeof(int32_t)));
+    TBK_CHECK(d_lists.reserve(l_bytes));
+    if (phases) TBK_CHECK(d_D.reserve(d_bytes));
+    TBK_CHECK(d_part.reserve(L.part_bytes()));
+    TBK_CHECK(d_chi.reserve(out_bytes));
+    TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
+    TBK_HIP(hipMemcpy(d_U.ptr, U, u_bytes, hipMemcpyHostToDevice));
+    TBK_HIP(hipMemcpy(d_Q.ptr, h_Q.data(), h_Q.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    TBK_HIP(hipMemcpy(d_lists.ptr, h_lists.data(), l_bytes, hipMemcpyHostToDevice));
+    if (phases) TBK_HIP(hipMemcpy(d_D.ptr, phases, d_bytes, hipMemcpyHostToDevice));
+    TBK_CHECK(chi_orb_launch_all(nullptr, L, nullptr, d_U.as<double>(), d_E.as<double>(), d_tab.as<double>(), d_Q.as<int32_t>(),
+                                 phases ? d_D.as<double>() : nullptr, d_lists.as<int32_t>(), n_q, mu, T, d_part.as<double>(), d_chi.as<double>()));
+    TBK_HIP(hipMemcpy(chi_out, d_chi.ptr, out_bytes, hipMemcpyDeviceToHost));
+    return TBK_OK;
+}
+
+extern "C" int tbk_orbital_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
+                                                int64_t n_q, const int64_t* q, int m, const int32_t* orbitals, int convention, const double* pos,
+                                                double* mu_out, double* chi_out) {
+    ChiOrb ob;
+    ob.on = true;
+    ob.m = m;
+    ob.orbitals = orbitals;
+    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, ChiFreq(), ob, 1, convention, pos, mu_out, chi_out);
+}
+
+extern "C" int tbk_orbital_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q,
+                                          int n_sel, const int32_t* orbitals, int convention, const double* pos, double* mu_out, double* chi_out) {
+    return tbk_orbital_susceptibility_multi(&m, 1, mesh, mode, value, T, n_q, q, n_sel, orbitals, convention, pos, mu_out, chi_out);
 }

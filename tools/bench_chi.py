@@ -21,7 +21,14 @@ vectors, measured in the same run; its f64 VALU rate, EPILOGUE_VALU instructions
 fraction of --valu-peak (lane-instructions per second of the whole chip); and the host route, Model.eigh + chi_model.dynamic_susceptibility,
 timed on two planes, at most two vectors and at most four frequencies and scaled.
 
-    python tools/bench_chi.py [--reps 3] [--filling 0.3] [--temperature 0.05] [--quick] [--omegas 1,16,128 [--eta 0.05]]
+With --orbital it prints the table of Model.orbital_susceptibility instead, NQ = 1 and 8 (--orbitals m: the
+first m orbitals only): the same stages (the overlap stage is the rank-K update), the update's flops -- 2048 n n_pad per (k, q) and
+tile of 16 x 16, n_pad = n rounded up to 16 -- over its time as a fraction of tbk_mfma_f64_peak, twice: for the tiles with i <= j of
+the selection, which are the ones written, and for all the tiles the kernel multiplies (the four-wave template multiplies whole
+64 x 64 blocks, the tiles of the padding and those below the diagonal of a diagonal block included); and the host route at one
+vector, Model.eigh + chi_model.orbital_susceptibility, timed on two planes and scaled.
+
+    python tools/bench_chi.py [--reps 3] [--filling 0.3] [--temperature 0.05] [--quick] [--omegas 1,16,128 [--eta 0.05]] [--orbital [--orbitals m]]
 """
 
 import argparse
@@ -142,6 +149,53 @@ def measure_dynamic(name, model, mesh, counts, n_ws, filling, T, eta, reps, valu
             sys.stdout.flush()
 
 
+def measure_orbital(name, model, mesh, counts, m, filling, T, reps, peak_tflops):
+    lib = _lib.lib()
+    n, n_k = model.size, int(np.prod(mesh))
+    n_el = filling * n
+    m = n if m <= 0 else min(m, n)
+    chosen = None if m == n else np.arange(m)
+    n_pad, tiles = (n + 15) // 16 * 16, (m + 15) // 16
+    handle = model._staged()
+    ms, calls, plan = (ctypes.c_double * 3)(), ctypes.c_int64(0), (ctypes.c_int64 * 6)()
+    kpts = np.ascontiguousarray(dos_model.mesh_kpoints(mesh))
+    plane = int(np.prod(mesh[1:]))
+    sub_mesh = (2,) + tuple(mesh[1:])
+    model.eigh(kpts[:plane])
+    t_eigh, (eig2, vec2) = _best(lambda: model.eigh(kpts[:2 * plane]), max(1, reps - 1))
+    for n_q in counts:
+        q = np.zeros((n_q, len(mesh)), dtype=np.int64)
+        q[:, 0] = np.arange(1, n_q + 1)
+        call = lambda: model.orbital_susceptibility(mesh, q, temperature=T, n_electrons=n_el, orbitals=chosen)  # noqa: E731
+        call()  # warm-up
+        t_call, result = _best(call, reps)
+        _lib.check(lib.tbk_model_set_option(handle, _lib.TBK_OPT_TIMING, 1))
+        _lib.check(lib.tbk_chi_timing(handle, ms, ctypes.byref(calls), 1))
+        best = None
+        for _ in range(reps):  # the stages of the call with the shortest update
+            call()
+            _lib.check(lib.tbk_chi_timing(handle, ms, ctypes.byref(calls), 1))
+            if best is None or ms[1] < best[1]:
+                best = list(ms)
+        model.timing(reset=True)
+        _lib.check(lib.tbk_model_set_option(handle, _lib.TBK_OPT_TIMING, 0))
+        _lib.check(lib.tbk_chi_orbital_plan(n_k, n, m, n_q, 0, 0, plan))
+        per_tile = 2048.0 * n * n_pad * n_k * n_q
+        issued_tiles = 16 * plan[1] if plan[0] == 4 else 1  # (plan: template, blocks, ...)
+        fraction = per_tile * (tiles * (tiles + 1) // 2) / (best[1] * 1e-3) / (peak_tflops * 1e12) if best[1] > 0 else float("nan")
+        issued = per_tile * issued_tiles / (best[1] * 1e-3) / (peak_tflops * 1e12) if best[1] > 0 else float("nan")
+        host = ""
+        if n_q == counts[0]:
+            t_model, _ = _best(lambda: chi_model.orbital_susceptibility(eig2, vec2, sub_mesh, q[:1], result.mu.mu, T, None, chosen), 1)
+            host = "%.1f" % ((t_eigh + t_model * n_q) / 2 * mesh[0] * 1e3)
+        print("| %s | %s | %d | %d | %d | %d x %d | %.1f | %.1f | %.3f | %.3f | %.3f | %.3f | %.3f | %s |"
+              % (name, "x".join(str(x) for x in mesh), n, m, n_q, plan[3], plan[2], t_call * 1e3, t_call * 1e3 - sum(best), best[0], best[1], best[2],
+                 fraction, issued, host))
+        print("  (%s NQ = %d: mu = %.12g, largest eigenvalue of chi(q_1) = %.12g, sum = %.12g)"
+              % (name, n_q, result.mu.mu, np.linalg.eigvalsh(result.chi[0]).max(), result.chi[0].sum().real))
+        sys.stdout.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -152,7 +206,25 @@ def main():
     ap.add_argument("--eta", type=float, default=0.05, help="the broadening of the dynamic call")
     ap.add_argument("--valu-peak", type=float, default=39321.6, help="f64 VALU peak in G lane-instructions per second: the data sheet's 78.6 TFLOP/s "
                     "of vector FP64 is one fused multiply-add per lane and cycle, 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz")
+    ap.add_argument("--orbital", action="store_true", help="the table of Model.orbital_susceptibility instead")
+    ap.add_argument("--orbitals", type=int, default=0, help="with --orbital: the first m orbitals only (0: all)")
     args = ap.parse_args()
+    if args.orbital:
+        tf = ctypes.c_double(0.0)
+        _lib.check(_lib.lib().tbk_mfma_f64_peak(0, ctypes.byref(tf)))
+        print("FP64 MFMA peak: %.1f TFLOP/s" % tf.value)
+        print("| model | mesh | orbitals | selected | NQ | slices x k-points | Model.orbital_susceptibility ms | of it outside the chi kernels (eigenvalues, mu, "
+              "eigensystem) ms | Fermi tables ms | rank-K update ms | reduction ms | update / MFMA peak (tiles with i <= j) | update / MFMA peak (all tiles multiplied) | today, one vector: Model.eigh "
+              "to the host + tools/chi_model.py ms (two planes, scaled) |")
+        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+        counts = (1, 2) if args.quick else (1, 8)
+        data = np.load(os.path.join(ROOT, "tests", "golden", "silicon.npz"))
+        silicon = tbmodels_amd.Model.from_packed(data["R"], data["hop"], pos=data["pos"])
+        measure_orbital("silicon", silicon, (8,) * 3 if args.quick else (32,) * 3, counts, args.orbitals, args.filling, args.temperature, args.reps, tf.value)
+        r_vec, hop, _ = synthetic.dense_model_arrays(64, 64, synthetic.MODEL_SEED + 2)
+        dense = tbmodels_amd.Model.from_packed(r_vec, hop)
+        measure_orbital("dense 64", dense, (6,) * 3 if args.quick else (24,) * 3, counts, args.orbitals, args.filling, args.temperature, args.reps, tf.value)
+        return
     if args.omegas:
         n_ws = [int(x) for x in args.omegas.split(",")]
         print("| model | mesh | orbitals | NQ | NW | Model.dynamic_susceptibility ms | of it outside the chi kernels ms | Fermi tables ms | overlaps + dynamic "

@@ -19,7 +19,8 @@ f(x) from t = exp(-|x - mu| / T), 1 - f(x) as f(2 mu - x) from the same t (the m
 exactly): every factor is non-negative, nothing overflows, a = b is the same branch.
 
 The dynamic chi_0(q, omega + i eta) of DESIGN.md section 16 is `dynamic_susceptibility`, with the occupation difference in the stable
-form of `pair_difference` and the bound `dynamic_tolerance`.
+form of `pair_difference` and the bound `dynamic_tolerance`.  The orbital-resolved chi_0[i][j](q) of section 17 is `orbital_susceptibility`
+(`orbital_susceptibility_naive`: F as the quotient), with the bound `orbital_tolerance`.
 
 `python tools/chi_model.py` prints one small case by the stable and by the naive F.  Design tooling: nothing in the product imports it.
 """
@@ -260,6 +261,102 @@ def dynamic_tolerance(n_k, n, T, eta, spread, matrix_elements=True):
     if matrix_elements:
         side = side + 2 * (3 * n + 5) * n ** 1.5 + 3 * n
     return 2.0 * side * u / eta
+
+
+def _orbital_selection(orbitals, n):
+    if orbitals is None:
+        return np.arange(n, dtype=np.int64)
+    chosen = np.asarray(orbitals)
+    if chosen.dtype.kind not in "iu" or chosen.ndim != 1 or chosen.size < 1:
+        raise ValueError("orbitals must be a list of integers")
+    chosen = chosen.astype(np.int64)
+    if chosen.min() < 0 or chosen.max() >= n or np.unique(chosen).size != chosen.size:
+        raise ValueError("orbitals must be distinct indices in [0, %d)" % n)
+    return chosen
+
+
+def orbital_amplitudes(U, mesh, q, phases=None, orbitals=None):
+    """A[NK][m][n][n] for ONE vector q: A[k][i][b][b'] = (conj(U[k][i][b]) D[i]) U[k+q][i][b'] for the selected orbitals i."""
+    n = np.asarray(U).shape[-1]
+    flat = np.asarray(U).reshape(-1, n, n)
+    chosen = _orbital_selection(orbitals, n)
+    left = flat[:, chosen, :].conj()
+    if phases is not None:
+        left = left * np.asarray(phases)[None, chosen, None]
+    return left[:, :, :, None] * flat[shifted_points(mesh, q)][:, chosen, None, :]
+
+
+def orbital_susceptibility(E, U, mesh, q, mu, T, phases=None, orbitals=None):
+    """chi_0[NQ][m][m], complex, of DESIGN.md section 17, for the integer vectors ``q`` of shape (NQ, dim):
+
+        A(k, q)[i; b, b'] = conj(U[k][i][b]) D(q)[i] U[k+q][i][b']
+        chi_0[i][j](q)    = (1 / (T NK)) sum_k sum_{b b'} t(E[k][b], E[k+q][b']) A[i; b, b'] conj(A[j; b, b'])
+
+    with t = `pair_weight` >= 0 (-T F).  ``E``, ``U``, ``phases`` as for `susceptibility`; ``orbitals``: None or m distinct indices in
+    the caller's order.  Per k-point one matrix product, (t A reshaped to (m, n^2)) A^H, so that BLAS does the n^4 part; the upper
+    triangle is kept, the lower is its conjugate and the diagonal's imaginary part is +0, as the kernels write them."""
+    E = np.asarray(E, dtype=float)
+    n = E.shape[-1]
+    flat_e = E.reshape(-1, n)
+    n_k = flat_e.shape[0]
+    q = np.asarray(q)
+    if q.dtype.kind not in "iu":
+        raise ValueError("q must be integers")
+    q = q.astype(np.int64).reshape(-1, len(mesh))
+    chosen = _orbital_selection(orbitals, n)
+    m = chosen.size
+    flat_u = np.asarray(U).reshape(-1, n, n)
+    f, g = fermi_tables(flat_e, mu, T)
+    out = np.zeros((q.shape[0], m, m), dtype=complex)
+    for index, vector in enumerate(q):
+        to = shifted_points(mesh, vector)
+        a, b = flat_e[:, :, None], flat_e[to][:, None, :]
+        weight = pair_weight(a, b, f[:, :, None], g[:, :, None], f[to][:, None, :], g[to][:, None, :], T)
+        left = flat_u[:, chosen, :].conj()
+        if phases is not None:
+            left = left * np.asarray(phases)[index][None, chosen, None]
+        total = np.zeros((m, m), dtype=complex)
+        for k in range(n_k):  # (A of one k-point at a time: m n^2 numbers)
+            y = (left[k][:, :, None] * flat_u[to[k]][chosen][:, None, :]).reshape(m, n * n)
+            total += (weight[k].reshape(1, n * n) * y) @ y.conj().T
+        total = total / T / n_k
+        upper = np.triu(total, 1)
+        out[index] = upper + upper.conj().T + np.diag(total.diagonal().real)
+    return out + (0.0 + 0.0j)  # (-0 from the conjugate of a zero becomes +0)
+
+
+def orbital_susceptibility_naive(E, U, mesh, q, mu, T, phases=None, orbitals=None):
+    """The formula with F as the quotient (`pair_factor_naive`) in one einsum: for comparison where the quotient is well conditioned."""
+    E = np.asarray(E, dtype=float)
+    n = E.shape[-1]
+    flat_e = E.reshape(-1, n)
+    q = np.asarray(q)
+    if q.dtype.kind not in "iu":
+        raise ValueError("q must be integers")
+    q = q.astype(np.int64).reshape(-1, len(mesh))
+    chosen = _orbital_selection(orbitals, n)
+    out = np.zeros((q.shape[0], chosen.size, chosen.size), dtype=complex)
+    for index, vector in enumerate(q):
+        to = shifted_points(mesh, vector)
+        factor = pair_factor_naive(flat_e[:, :, None], flat_e[to][:, None, :], mu, T)
+        amp = orbital_amplitudes(U, mesh, vector, None if phases is None else np.asarray(phases)[index], chosen)
+        out[index] = -np.einsum("kbc,kibc,kjbc->ij", factor, amp, amp.conj()) / flat_e.shape[0]
+    return out
+
+
+ROUNDINGS_AMPLITUDES = 14.0  # c_A of DESIGN.md 17.5: a term t A_i conj(A_j) holds two amplitudes, each two complex products of three
+#                              roundings per component (conj(U) D, then U'), one scale by t and one product
+
+
+def orbital_tolerance(n_k, n, T):
+    """tol of DESIGN.md 17.5: the bound on either component of one element of chi - chi' of two evaluations (the kernels, this
+    model) of the SAME (E, U, mu, T), derived as `tolerance` is.  New: sum_{b b'} |A_i| |A_j| <= 1 by Cauchy-Schwarz on the unit
+    rows of U(k) and U(k+q), so per k the moduli of an element's terms add up to at most s = 1 / 4 in units of 1 / T.  Per side:
+    the sum of NK n^2 terms, NK n^2 s u;  the factors of a term, relative, (4 ULP_EXP + ULP_EXPM1 + 15 + ROUNDINGS_AMPLITUDES) s u;
+    the unbounded part of the exponential's argument error, absolute, 4 u per unit of sum |A_i| |A_j|: 4 u."""
+    u = 2.0 ** -53
+    side = (n_k * n * n + 4 * ULP_EXP + ULP_EXPM1 + 15 + ROUNDINGS_AMPLITUDES) / 4.0 + 4.0
+    return 2.0 * side * u / T
 
 
 def static_limit(E, mu, T):
