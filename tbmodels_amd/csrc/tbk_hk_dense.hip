@@ -15,8 +15,9 @@
 //     D[row = (lane >> 4) + 4 reg][col = lane & 15].
 //   * workgroup = 4 waves = 128 k-points x 64 packed elements (128 real columns); wave (wm, wn)
 //     owns 64 k-points x 32 elements = 4 x 2 x {re, im} = 16 accumulators (128 VGPRs).
-//   * K is walked in stages of 16 rows through double-buffered LDS, filled by LDS-DMA
-//     (global_load_lds_dwordx4) issued before the MFMAs of the current stage; one barrier per stage.
+//   * K is walked in half stages of 8 rows through a ring of four LDS buffers, filled by LDS-DMA
+//     (global_load_lds_dwordx4) issued three half stages ahead and left in flight across the loop's barriers
+//     (raw s_barrier behind a counted vmcnt); one barrier per half stage.
 //     LDS rows are padded by 16 doubles so that the two K rows a 32-lane group reads with
 //     ds_read_b64 fall in different halves of the 64-bank row: conflict-free.
 //   * both operands are K-major with the fast index contiguous, so every staging load is a
@@ -43,9 +44,18 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 
 constexpr int LDA = TBK_BM + 16;       // doubles per K row of the A stage
 constexpr int LDB = 2 * TBK_BNP + 16;  // doubles per K row of the B stage
-constexpr int STAGE_DOUBLES = TBK_BK * (LDA + LDB);
+// The K loop's LDS ring: HK_RING buffers of one HALF stage (8 K rows of both operands, 18 KiB) each; the LDS-DMA of a half
+// stage is issued HK_RING - 1 half stages ahead of its first fragment read.  TBK_BK = 16 stays the padding unit of K.
+// Four buffers (72 KiB, the footprint of the two-buffer loop before it) and three (54 KiB) were both measured on the bench
+// line and tie (DESIGN_LOG.md R14.1); four is kept, which leaves what fits a CU beside two of these workgroups as it was.
+constexpr int HK_HALF = TBK_BK / 2;
+constexpr int HK_RING = 4;
+constexpr int HALF_DOUBLES = HK_HALF * (LDA + LDB);
+constexpr size_t HK_LDS_BYTES = (size_t)HK_RING * HALF_DOUBLES * sizeof(double);  // 73,728 B: above the 64 KiB default cap
 
 static_assert(TBK_BM == 128 && TBK_BNP == 64 && TBK_BK == 16, "wave decomposition is written for 128x64x16");
+static_assert(HK_RING == 3 || HK_RING == 4, "the ring's phases are written out for three or four buffers");
+static_assert(HK_LDS_BYTES <= 73728, "two workgroups per CU beside the QL kernel's and the first combine pass's footprint");
 
 struct HkArgs {
     const double* A = nullptr;
@@ -233,45 +243,50 @@ __global__ void __launch_bounds__(256, 2) hk_dense_kernel(const HkArgs a) {
     // carried per stage (64-bit pointer increments in VGPRs, v_readfirstlane for M0, ds_read base adds) cost the matrix
     // pipe ~350 of the 4096 cycles of a stage.  Now:
     //   * staging (global -> LDS, global_load_lds_dwordx4: one 1 KiB K row per wave-instruction, no staging VGPRs):
-    //     wave w copies K rows w, w + 4, w + 8, w + 12 of both operands; the row pointers are wave-uniform (SGPR pairs,
+    //     per half stage wave w copies K rows w, w + 4 of both operands; the row pointers are wave-uniform (SGPR pairs,
     //     advanced by s_add), the lane's 16 bytes are ONE loop-invariant 32-bit VGPR offset, the LDS row base goes to
     //     M0 from scalar registers;
-    //   * fragment reads: per-lane LDS base addresses of the two operands in both buffers (four loop-invariant VGPRs),
-    //     every (K step, fragment) a compile-time ds_read offset (the loop is written out for buffer 0 and 1).
+    //   * fragment reads: per-lane LDS base addresses of the two operands in every buffer (loop-invariant VGPRs),
+    //     every (K step, fragment) a compile-time ds_read offset (the loop is written out over the ring's buffers).
     const uint32_t lane_bytes = (uint32_t)lane * 16u;
     const int64_t ldgA = a.nk_pad * (int64_t)sizeof(double);                   // bytes per K row
     const int64_t ldgB = (int64_t)a.ncol_pad * 2 * (int64_t)sizeof(double);
     const char* rowA = reinterpret_cast<const char*>(opA + (int64_t)mt_idx * a.a_tile_stride) + ((int64_t)s_begin * TBK_BK + wave) * ldgA;
     const char* rowB = reinterpret_cast<const char*>(opB + (int64_t)mt_idx * a.b_tile_stride + n0 * 2) + ((int64_t)s_begin * TBK_BK + wave) * ldgB;
-    auto issue_stage = [&](auto bufc) {  // the stage rowA / rowB point at -> buffer bufc; advances them by one stage
-        constexpr int buf = decltype(bufc)::value;
-        double* sA = smem + buf * STAGE_DOUBLES + wave * LDA;
-        double* sB = smem + buf * STAGE_DOUBLES + TBK_BK * LDA + wave * LDB;
-        // (the offset is re-defined inside the block that uses it: instruction selection works per basic block and only
-        // takes the SGPR-base form of the load for `uniform pointer + zext(32-bit VGPR)` it can see whole; hoisted out
-        // of the loop the zero-extension became a VGPR pair and every load cost a 64-bit VALU add)
+    // (the lane offset is re-defined inside the basic block that uses it: instruction selection works per basic block and
+    // only takes the SGPR-base form of the load for `uniform pointer + zext(32-bit VGPR)` it can see whole; hoisted out
+    // of the loop the zero-extension became a VGPR pair and every load cost a 64-bit VALU add)
+    auto lane_off = [&]() {
         uint32_t off = lane_bytes;
         asm volatile("" : "+v"(off));
+        return off;
+    };
+    // the half stage rowA / rowB point at -> buffer bufc; advances them by one half stage.  `off`: lane_off() of the same block
+    auto issue_half = [&](auto bufc, uint32_t off) {
+        constexpr int buf = decltype(bufc)::value;
+        double* sA = smem + buf * HALF_DOUBLES + wave * LDA;
+        double* sB = smem + buf * HALF_DOUBLES + HK_HALF * LDA + wave * LDB;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < HK_HALF / 4; ++i) {
             __builtin_amdgcn_global_load_lds((gptr_t)(rowA + (int64_t)(4 * i) * ldgA + off), (lptr_t)(sA + 4 * i * LDA), 16, 0, 0);
             __builtin_amdgcn_global_load_lds((gptr_t)(rowB + (int64_t)(4 * i) * ldgB + off), (lptr_t)(sB + 4 * i * LDB), 16, 0, 0);
         }
-        rowA += TBK_BK * ldgA;
-        rowB += TBK_BK * ldgB;
+        rowA += HK_HALF * ldgA;
+        rowB += HK_HALF * ldgB;
     };
+    constexpr int GLDS_PER_HALF = 2 * (HK_HALF / 4);  // LDS-DMA instructions a wave issues per half stage
     // one opaque per-lane base per (buffer, K step, operand): the four fragments of a step are then two ds_read2_b64 with
     // immediate offsets (left to itself hipcc derives the bases of a stage from one register with a VALU add each)
     typedef __attribute__((address_space(3))) const double* lds_cptr;
-    uint32_t fragA[2][TBK_BK / 4], fragB[2][TBK_BK / 4];  // LDS byte addresses
+    uint32_t fragA[HK_RING][HK_HALF / 4], fragB[HK_RING][HK_HALF / 4];  // LDS byte addresses
     {
         const uint32_t s0 = (uint32_t)(uintptr_t)(lptr_t)smem;
 #pragma unroll
-        for (int buf = 0; buf < 2; ++buf)
+        for (int buf = 0; buf < HK_RING; ++buf)
 #pragma unroll
-            for (int ks = 0; ks < TBK_BK / 4; ++ks) {
-                fragA[buf][ks] = s0 + 8u * (uint32_t)(buf * STAGE_DOUBLES + wm * 64 + l15 + (ks * 4 + l4) * LDA);
-                fragB[buf][ks] = s0 + 8u * (uint32_t)(buf * STAGE_DOUBLES + TBK_BK * LDA + wn * 64 + l15 + (ks * 4 + l4) * LDB);
+            for (int ks = 0; ks < HK_HALF / 4; ++ks) {
+                fragA[buf][ks] = s0 + 8u * (uint32_t)(buf * HALF_DOUBLES + wm * 64 + l15 + (ks * 4 + l4) * LDA);
+                fragB[buf][ks] = s0 + 8u * (uint32_t)(buf * HALF_DOUBLES + HK_HALF * LDA + wn * 64 + l15 + (ks * 4 + l4) * LDB);
                 asm volatile("" : "+v"(fragA[buf][ks]), "+v"(fragB[buf][ks]));
             }
     }
@@ -292,50 +307,104 @@ __global__ void __launch_bounds__(256, 2) hk_dense_kernel(const HkArgs a) {
         }
         return f;
     };
-    auto mfma_step = [&](const Frags& f) {
+    // the 16 MFMAs of one K step (one per accumulator, so their order among themselves does not reach the sums): the
+    // first alone, or the other fifteen, or all of them
+    auto mfma_step = [&](const Frags& f, bool first = true, bool rest = true) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                acc[i][j][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.fa[i], f.fb[j][0], acc[i][j][0], 0, 0, 0);
-                acc[i][j][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.fa[i], f.fb[j][1], acc[i][j][1], 0, 0, 0);
-            }
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int p = 0; p < 2; ++p)
+                    if (i + j + p == 0 ? first : rest)
+                        acc[i][j][p] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.fa[i], f.fb[j][p], acc[i][j][p], 0, 0, 0);
+    };
+    // (an empty statement that reads the fragments: the compiler places its own wait for their ds_reads in front of it.  Behind an
+    // LDS-DMA it only ever waits lgkmcnt(0), so a wait it places later would also cover whatever was requested in between)
+    auto settle = [&](const Frags& f) {
+        asm volatile("" ::"v"(f.fa[0]), "v"(f.fa[1]), "v"(f.fa[2]), "v"(f.fa[3]), "v"(f.fb[0][0]), "v"(f.fb[0][1]), "v"(f.fb[1][0]), "v"(f.fb[1][1]));
     };
     using buf0 = std::integral_constant<int, 0>;
     using buf1 = std::integral_constant<int, 1>;
+    using buf2 = std::integral_constant<int, 2>;
+    using buf3 = std::integral_constant<int, 3>;
     using ks0 = std::integral_constant<int, 0>;
     using ks1 = std::integral_constant<int, 1>;
-    using ks2 = std::integral_constant<int, 2>;
-    using ks3 = std::integral_constant<int, 3>;
-    static_assert(TBK_BK == 16, "four K steps per stage are written out below");
-    // One stage: the fragments of K step ks + 1 are requested before the MFMAs of step ks; the stage barrier sits in
-    // front of the LAST step's MFMAs, and the first fragments of the NEXT stage are requested right behind it -- under
-    // those 16 MFMAs instead of in front of an idle matrix pipe.
-    auto stage = [&](auto bufc, auto nextc, Frags& cur, bool more) {
+    static_assert(HK_HALF == 8, "two K steps per half stage are written out below");
+    // The ring.  Half stage h lives in buffer h % HK_RING; its LDS-DMA is issued AHEAD = HK_RING - 1 half stages before its
+    // first fragment read and stays in flight across the barriers in between:
+    //   * the barrier is a raw s_barrier behind `s_waitcnt lgkmcnt(0)` (this wave's fragment reads are in registers) and a
+    //     COUNTED `s_waitcnt vmcnt` (this wave's rows of the NEXT half stage have landed; the `flight` younger half stages
+    //     stay outstanding).  __syncthreads() would fence with vmcnt(0) and drain the ring at every barrier;
+    //   * a buffer is read only behind the barrier that follows the wait retiring it, in every wave (RAW), and refilled
+    //     only behind the barrier that follows its last fragment read (WAR): buffer (h - 1) % HK_RING takes half stage
+    //     h + AHEAD at the head of phase h, its last read having been waited for in front of the barrier of phase h - 1.
+    constexpr int AHEAD = HK_RING - 1;
+    auto ring_barrier = [&](int flight) {
+        if (HK_RING > 3 && flight >= 2)
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GLDS_PER_HALF) : "memory");
+        else if (flight == 1)
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GLDS_PER_HALF) : "memory");
+        else
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
+    // One half stage (phase): the fragments of its second K step are requested behind the first MFMA of the first step (whose
+    // wait covers only fragments requested a K step ago); the barrier sits in front of the second step's MFMAs, and the first
+    // fragments of the NEXT half stage are requested right behind it -- under those 16 MFMAs instead of in front of an idle
+    // matrix pipe.  Scheduling fences pin that order: left alone, the compiler gathers the MFMAs of several phases behind
+    // the trip's last barrier and keeps a fourth set of fragments alive for it.
+    auto phase = [&](auto bufc, Frags& cur, uint32_t off, bool issue, int flight, bool last) {
+        constexpr int buf = decltype(bufc)::value;
+        if (issue) issue_half(std::integral_constant<int, (buf + AHEAD) % HK_RING>{}, off);
+        mfma_step(cur, true, false);
+        __builtin_amdgcn_sched_barrier(0);
         Frags f1 = read_frags(bufc, ks1{});
-        mfma_step(cur);
-        Frags f2 = read_frags(bufc, ks2{});
+        __builtin_amdgcn_sched_barrier(0);
+        mfma_step(cur, false, true);
+        if (!last) {
+            __builtin_amdgcn_sched_barrier(0);
+            settle(f1);
+            ring_barrier(flight);
+            cur = read_frags(std::integral_constant<int, (buf + 1) % HK_RING>{}, ks0{});
+            __builtin_amdgcn_sched_barrier(0);
+        }
         mfma_step(f1);
-        Frags f3 = read_frags(bufc, ks3{});
-        mfma_step(f2);
-        __syncthreads();  // the next stage has landed (vmcnt(0)) and everyone has READ this one (its last fragments are in registers)
-        if (more) cur = read_frags(nextc, ks0{});
-        mfma_step(f3);
     };
 
-    // two stages per trip (buffer 0, then 1), so that everything above is a compile-time offset; an odd stage behind it
-    const int left = n_stage - s_begin;
-    if (left > 0) issue_stage(buf0{});
-    __syncthreads();  // drains the LDS-DMA queue (vmcnt) before the barrier
-    Frags cur = read_frags(buf0{}, ks0{});
-    for (int pair = 0; pair < (left >> 1); ++pair) {
-        issue_stage(buf1{});  // lands during this stage's MFMAs
-        stage(buf0{}, buf1{}, cur, true);
-        const bool more = 2 * pair + 2 < left;
-        if (more) issue_stage(buf0{});
-        stage(buf1{}, buf0{}, cur, more);
+    // HK_RING phases per trip, so that everything above is a compile-time offset.  The steady trips issue and wait with
+    // constants; the trips behind them (and every K range shorter than the ring) decide per phase what is left to issue
+    // and how many half stages may stay in flight.  Nothing is outstanding behind the last barrier.
+    const int halves = 2 * (n_stage - s_begin);
+    if (halves > 0) {
+        {
+            const uint32_t off = lane_off();
+            issue_half(buf0{}, off);
+            issue_half(buf1{}, off);
+            if (HK_RING > 3 && halves > 2) issue_half(buf2{}, lane_off());
+        }
+        ring_barrier(min(AHEAD, halves) - 1);
+        Frags cur = read_frags(buf0{}, ks0{});
+        int h = 0;
+        for (; h + 2 * HK_RING - 2 < halves; h += HK_RING) {
+            const uint32_t off = lane_off();  // one for the trip: a single basic block
+            phase(buf0{}, cur, off, true, AHEAD - 1, false);
+            phase(buf1{}, cur, off, true, AHEAD - 1, false);
+            phase(buf2{}, cur, off, true, AHEAD - 1, false);
+            if constexpr (HK_RING > 3) phase(buf3{}, cur, off, true, AHEAD - 1, false);
+        }
+        auto tail_phase = [&](auto bufc, int hh) {
+            if (hh < halves) phase(bufc, cur, lane_off(), hh + AHEAD < halves, min(AHEAD - 1, halves - 2 - hh), hh == halves - 1);
+        };
+        for (; h < halves; h += HK_RING) {
+            tail_phase(buf0{}, h);
+            tail_phase(buf1{}, h + 1);
+            tail_phase(buf2{}, h + 2);
+            if constexpr (HK_RING > 3) tail_phase(buf3{}, h + 3);
+        }
     }
-    if (left & 1) stage(buf0{}, buf1{}, cur, false);
 
     // ---- epilogue: scatter the packed tile into H[k][i][j] (and H[k][j][i]), or park the partial tile ----
 #pragma unroll
@@ -901,8 +970,7 @@ constexpr int TAIL_MAX_ROUNDS = 12;
 template <int MODE, int CONV>
 int launch(tbk_model* m, const HkArgs& a0, int grid) {
     hipStream_t s = m->stream;
-    // 73,728 B: above the 64 KiB default cap
-    const size_t lds = 2 * STAGE_DOUBLES * sizeof(double);
+    const size_t lds = HK_LDS_BYTES;
     static std::atomic<bool> raised[TBK_MAX_DEVICES] = {};
     static std::atomic<bool> raised_split[TBK_MAX_DEVICES] = {};
     TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&hk_dense_kernel<MODE, CONV, false>), 160 * 1024, raised));
@@ -1009,7 +1077,7 @@ auto by_mode(int mode, int convention, F&& launch) {
 template <int MODE, int CONV>
 int launch_strassen(tbk_model* m, const tbk_operand_t& op, const HkArgs& a0) {
     hipStream_t s = m->stream;
-    const size_t lds = 2 * STAGE_DOUBLES * sizeof(double);
+    const size_t lds = HK_LDS_BYTES;
     static std::atomic<bool> raised[TBK_MAX_DEVICES] = {};
     TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&hk_dense_kernel<HK_TRI, 2, true>), 160 * 1024, raised));
     const int64_t mh = tbk_strassen_mh(a0.nk);
@@ -1044,7 +1112,7 @@ int launch_strassen(tbk_model* m, const tbk_operand_t& op, const HkArgs& a0) {
 template <int MODE, int CONV>
 int launch_strassen2(tbk_model* m, const tbk_operand_t& op, const HkArgs& a0) {
     hipStream_t s = m->stream;
-    const size_t lds = 2 * STAGE_DOUBLES * sizeof(double);
+    const size_t lds = HK_LDS_BYTES;
     static std::atomic<bool> raised[TBK_MAX_DEVICES] = {};
     TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(&hk_dense_kernel<HK_TRI, 2, true>), 160 * 1024, raised));
     TBK_ARG(m->d_Bs2 != nullptr, "the operand blocks of the second Strassen level are missing");
