@@ -524,6 +524,53 @@ int tbk_chi_orbital_plan(int64_t nk, int n_orb, int m, int64_t n_q, int64_t part
 /* (Kernel times of these calls are booked into tbk_chi_timing's three stages: the Fermi tables, the rank-K update, the reduction of the
  * slices; its call count includes them.) */
 
+/* ---- the lattice Berry flux and the Chern numbers of a uniform k mesh (not in the reference) -----------------------------------------
+ * The Fukui-Hatsugai-Suzuki field strength (csrc/tbk_berry.hip, DESIGN.md section 18, tools/berry_model.py).  Mesh and mesh points are
+ * those of tbk_occupations (dim 2 or 3), k+e_d is the mesh point with index (i_d + 1) mod n_d on axis d.  U is that of tbk_eigh
+ * (convention 2); D(e_d) = 1 for convention 2 and exp(-2 pi i pos[i][d] / n_d) for convention 1 (the table of tbk_susceptibility for
+ * q = e_d).  A band set is a half-open range [lo, hi) of band indices, m = hi - lo; a call takes 1 <= S <= 16 sets.  For every set,
+ * axis d and mesh point k:
+ *     M_d(k)     = U[k][:, lo:hi]^H D(e_d) U[k+e_d][:, lo:hi]                                  (m x m)
+ *     L_d(k)     = det M_d(k)      LU with partial pivoting: the pivot is the largest |Re| + |Im|, a tie goes to the lowest row
+ *     a_d(k)     = round(arg L_d(k) / (2 pi) 2^64) mod 2^64      the uint64 "angle word"; arg 0 = 0 for L = 0
+ *     F_ab(k)    = a_a(k) + a_b(k+e_a) - a_a(k+e_b) - a_b(k)     wrapping 64-bit arithmetic, read as int64; a < b
+ *     flux_ab(k) = (double)F_ab(k) 2 pi 2^-64                    in [-pi, pi]
+ *     C_ab(i_c)  = (sum over the plane's k of F_ab(k)) / 2^64    an integer: the low word of the 128-bit sum is identically 0
+ * Planes in the order (0,1), (0,2), (1,2); in two dimensions (0,1) alone.  C_ab is one integer per index i_c of the remaining axis c
+ * (one per set in two dimensions).  Only the link angles carry rounding; what follows them is integer arithmetic, so the Chern
+ * numbers are integers whatever the eigensolver's gauge.  The bits of a link depend on U(k), U(k+e_d), D, lo and hi alone -- not on the
+ * other sets, the batch or the handle.  Angle error per link <= berry_model.link_tolerance.
+ * Argument errors (TBK_ERR_ARGUMENT), before any device is touched: those of tbk_occupations' mesh, n_sets outside [1, 16], lo < 0,
+ * hi > n_orb or lo >= hi, convention not in {1, 2}, convention 1 without pos, a NULL pointer, a k.p handle, a handle given twice.
+ * Host buffers; synchronous. */
+
+/* The link kernels alone on eigenvectors the caller brings: U [NK][n_orb][n_orb] complex, ranges int32 [n_sets][2], phases NULL or
+ * D [dim][n_orb] complex; L_out complex [n_sets][dim][NK], words_out uint64 of the same shape. */
+int tbk_berry_links_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* U, int n_sets, const int32_t* ranges,
+                                     const double* phases, double* L_out, uint64_t* words_out);
+/* The plaquette kernel alone on words the caller brings: words uint64 [n_sets][dim][NK]; flux_out double [n_sets][P][NK] (P = 1 or 3
+ * planes), chern_out int64 [n_sets][sum of n_c over the planes] (n_2 + n_1 + n_0 in three dimensions, 1 in two). */
+int tbk_berry_flux_from_links(int device, int dim, const int32_t* mesh, int n_sets, const uint64_t* words, double* flux_out,
+                              int64_t* chern_out);
+/* The whole call: the handle fills the resident eigenvectors of the whole mesh chunk by chunk as tbk_susceptibility does (the same
+ * workspaces, the same routine), then the links, then the fluxes.  No chemical potential.  link_min_out: double [n_sets], the smallest
+ * |L_d(k)| of each set (small: the mesh is too coarse or the set is not isolated). */
+int tbk_berry_flux(tbk_model* m, const int32_t* mesh, int n_sets, const int32_t* ranges, int convention, const double* pos,
+                   double* flux_out, int64_t* chern_out, double* link_min_out);
+/* On several devices from one process: every handle holds the whole mesh's eigenvectors and computes the links of a contiguous share
+ * of the mesh points (the first ceil(NK / n_handles) to handle 0, ...); the host concatenates the words and handle 0 runs the plaquette
+ * kernel.  The number of handles changes no bit. */
+int tbk_berry_flux_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int n_sets, const int32_t* ranges, int convention,
+                         const double* pos, double* flux_out, int64_t* chern_out, double* link_min_out);
+/* How the links of nk mesh points are computed, per set: out[2 s] = the template (1: m <= 16, a link per wave, LU in the wave; 4:
+ * m <= 64, a link per workgroup, LU in LDS; 64: m > 64, the product kernel writes M and rocsolver_zgetrf_strided_batched factors it),
+ * out[2 s + 1] = links per launch at most (never more than the 3 nk links a set can have).  out: int64 [2 n_sets]. */
+int tbk_berry_plan(int64_t nk, int n_orb, int n_sets, const int32_t* ranges, int64_t* out);
+/* ms[3] = the summed HIP-event time of the link kernels (the products of the library path included), the library's LU with the
+ * determinant kernel, and the plaquette kernel in this handle's calls made while TBK_OPT_TIMING was on; calls = how many calls;
+ * reset = 1 clears.  (The eigensolver stages are in tbk_get_timing.) */
+int tbk_berry_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
 /* ---- k.p models (kdotp.py:51-100): H(k) = sum_p prod_d k_d^powers[p][d] * coeffs[p] ------- */
 int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, const int32_t* powers,
                      const double* coeffs, tbk_kdotp** out);

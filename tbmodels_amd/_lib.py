@@ -116,6 +116,12 @@ SIGNATURES = {
     "tbk_orbital_susceptibility_multi": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _c_int, _vp, _c_int, _vp,
                                                   _vp, _vp]),
     "tbk_chi_orbital_plan": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _c_i64, _c_i64, ctypes.POINTER(_c_i64)]),
+    "tbk_berry_links_from_eigensystem": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp]),
+    "tbk_berry_flux_from_links": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, _vp, _vp]),
+    "tbk_berry_flux": (_c_int, [_vp, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp]),
+    "tbk_berry_flux_multi": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp]),
+    "tbk_berry_plan": (_c_int, [_c_i64, _c_int, _c_int, _vp, ctypes.POINTER(_c_i64)]),
+    "tbk_berry_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
     "tbk_kdotp_create": (_c_int, [_c_int, _c_int, _c_int, _c_i64, _vp, _vp, _pp]),
     "tbk_kdotp_destroy": (None, [_vp]),
     "tbk_kdotp_hamilton": (_c_int, [_vp, _vp, _c_i64, _vp]),

@@ -47,6 +47,7 @@ DensityMatrix = co.namedtuple("DensityMatrix", ("mu", "R", "rho"))
 Susceptibility = co.namedtuple("Susceptibility", ("mu", "q", "chi"))
 DynamicSusceptibility = co.namedtuple("DynamicSusceptibility", ("mu", "q", "omega", "chi"))
 OrbitalSusceptibility = co.namedtuple("OrbitalSusceptibility", ("mu", "q", "orbitals", "chi"))
+BerryFlux = co.namedtuple("BerryFlux", ("bands", "planes", "flux", "chern", "link_min"))
 
 
 def _devices_from_env():
@@ -788,7 +789,7 @@ class Model:
         return (eig[0], vec[0]) if single else (eig, vec)
 
     def _mesh_argument(self, mesh, what="dos"):
-        """The mesh check ``dos``, ``pdos``, ``band_edges``, ``fermi_level``, ``tetra_weights``, ``occupations``, ``density_matrix``, ``susceptibility`` and ``dynamic_susceptibility`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
+        """The mesh check ``dos``, ``pdos``, ``band_edges``, ``fermi_level``, ``tetra_weights``, ``occupations``, ``density_matrix``, ``susceptibility``, ``dynamic_susceptibility`` and ``berry_flux`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
         if self.dim not in (2, 3):
             raise ValueError("{} needs a 2- or 3-dimensional model, this one has dimension {}".format(what, self.dim))
         try:
@@ -1348,6 +1349,105 @@ class Model:
                                                             _lib.ptr(mu), _lib.ptr(chi))
             )
         return OrbitalSusceptibility(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, selected, chi)
+
+    def _band_sets_argument(self, bands):
+        """``int32 (S, 2)`` half-open band ranges from an int ``n_occ`` (``[(0, n_occ)]``) or a sequence of ``(lo, hi)`` pairs, or
+        ``ValueError``."""
+        def whole(value):
+            return isinstance(value, (int, np.integer)) and not isinstance(value, (bool, np.bool_))
+
+        if whole(bands):
+            pairs = [(0, int(bands))]
+        else:
+            try:
+                pairs = [tuple(pair) for pair in bands]
+            except TypeError:
+                raise ValueError("bands must be an integer or a sequence of (lo, hi) pairs, got {!r}".format(bands)) from None
+        if not 1 <= len(pairs) <= 16:
+            raise ValueError("bands must hold 1 to 16 band sets, got {}".format(len(pairs)))
+        for pair in pairs:
+            if len(pair) != 2 or not whole(pair[0]) or not whole(pair[1]):
+                raise ValueError("a band set must be a pair of integers (lo, hi), got {!r}".format(pair))
+            if pair[0] < 0 or pair[1] > self.size or pair[0] >= pair[1]:
+                raise ValueError("a band set must satisfy 0 <= lo < hi <= {}, got {!r}".format(self.size, pair))
+        return np.ascontiguousarray(np.array(pairs, dtype=np.int32).reshape(len(pairs), 2))
+
+    def berry_flux(self, mesh, bands, *, convention=2):
+        """
+        The lattice Berry flux (the Fukui-Hatsugai-Suzuki field strength) of band sets on a uniform k mesh and their Chern numbers,
+        computed on the GPU from the eigenvectors of the whole mesh, which never leave it.  Not in the reference.
+
+        ``mesh`` is that of :meth:`occupations`.  ``bands`` is an int ``n_occ``, meaning the set ``[(0, n_occ)]``, or a sequence of 1
+        to 16 half-open ranges ``(lo, hi)`` of ascending band indices with ``0 <= lo < hi <= size``.  Returns the named tuple
+        ``(bands, planes, flux, chern, link_min)``: ``bands`` the sets as ``int32 (S, 2)``, ``planes`` the tuple of axis pairs
+        ``((0, 1),)`` in two and ``((0, 1), (0, 2), (1, 2))`` in three dimensions, ``flux`` ``float64 (S, P, *mesh)``, ``chern`` a
+        tuple of ``P`` arrays ``int64 (S, n_c)`` with ``c`` the axis the plane leaves over (``n_c = 1`` in two dimensions) and
+        ``link_min`` ``float64 (S,)``.
+
+        Definition.  With ``U`` of ``eigh(k, convention=2)`` at the mesh points ``k = (i_1 / n_1, ..., i_dim / n_dim)``, ``k+e_d`` the
+        mesh point with index ``(i_d + 1) mod n_d`` on axis ``d`` and ``m = hi - lo``::
+
+            M_d(k)     = U[k][:, lo:hi]^H D(e_d) U[k+e_d][:, lo:hi]                    (m x m)
+            L_d(k)     = det M_d(k)
+            a_d(k)     = round(arg L_d(k) / (2 pi) * 2^64) mod 2^64                    a uint64 "angle word"; arg 0 = 0 for L = 0
+            F_ab(k)    = a_a(k) + a_b(k+e_a) - a_a(k+e_b) - a_b(k)                     wrapping 64-bit arithmetic, read as int64; a < b
+            flux_ab(k) = float(F_ab(k)) * (2 pi 2^-64)                                 in [-pi, pi]
+            C_ab(i_c)  = (sum over the plane's k of F_ab(k)) / 2^64
+            link_min   = min over d and k of |L_d(k)|
+
+        ``D(e_d) = 1`` for ``convention=2``; for ``convention=1`` ``D(e_d)[i] = exp(-2 pi i pos[i, d] / n_d)``, the table of
+        :meth:`susceptibility` for ``q = e_d``.  The determinant comes from an LU factorisation with partial pivoting (the pivot is the
+        largest ``|Re| + |Im|``, a tie goes to the lowest row).  Sign: ``flux_ab ~ -Omega_ab / (n_a n_b)`` with the Berry curvature
+        ``Omega_ab = d_a A_b - d_b A_a`` of ``A_d = i tr <u| d/dk_d |u>``, so ``C_ab = -(1 / 2 pi) int Omega_ab``: the lower band of
+        the Qi-Wu-Zhang model ``sin K_x sigma_x + sin K_y sigma_y + (u + cos K_x + cos K_y) sigma_z`` has ``C = +1`` for
+        ``0 < u < 2``.
+
+        Properties.  (1) Only the link angles carry rounding: every plaquette is an exact wrapped integer sum of four words, and
+        the plaquettes of a closed plane add up to an exact multiple of ``2^64`` (the low word of the 128-bit sum is identically
+        zero), so every Chern number is an integer without rounding, whatever the phases of the eigenvectors and whatever basis the
+        eigensolver chooses inside the set.  (2) The Chern numbers do not change under a unitary mixing of the set's bands at every
+        ``k``; the fluxes move by at most four links' rounding.  (3) The full set ``(0, size)`` has ``|L| = 1``, zero Chern numbers and
+        fluxes of rounding size.  (4) Both conventions give the same Chern numbers.  (5) The bits of a set's links, fluxes and Chern
+        numbers do not depend on the other sets, on their order or on the number of ``devices``; a duplicate has the bits of its
+        original and a second call the bits of the first.
+
+        Error bound of one link angle in radians for a given eigensystem, with ``u = 2^-53`` and ``sigma_min`` the smallest singular
+        value of ``M`` (DESIGN.md 18.4; ``tools/berry_model.py`` ``link_tolerance``); a flux carries four of these::
+
+            |error| <= ((size + 8 m) m / sigma_min + 8) u
+
+        Caveats.  The Chern number is that of the lattice field: it equals the continuum one when every ``|flux| < pi`` by a margin,
+        which a finer mesh provides.  A small ``link_min`` means the mesh is too coarse or the set is not isolated from its
+        neighbours.  A set whose edge cuts a degenerate cluster (``E[k, lo - 1] = E[k, lo]`` or ``E[k, hi - 1] = E[k, hi]`` at a mesh
+        point) has ill-defined links there, since the basis inside the cluster is unspecified (see :meth:`eigh`): ``link_min`` shows
+        it.  Degeneracies inside a set do no harm.
+
+        One-dimensional models raise ``ValueError``.  The eigenvectors of the whole mesh must fit the device (``NK size^2`` complex
+        numbers), else ``MemoryError``.  With several ``devices`` every device holds the whole mesh's eigenvectors and computes the
+        links of a contiguous share of the mesh points.
+        """
+        mesh_array = self._mesh_argument(mesh, "berry_flux")
+        sets = self._band_sets_argument(bands)
+        if convention not in [1, 2]:
+            raise ValueError("Invalid value '{}' for 'convention': must be either '1' or '2'".format(convention))
+        pos = np.ascontiguousarray(self.pos, dtype=np.float64) if convention == 1 else None
+        shape = tuple(int(n) for n in mesh_array)
+        planes = ((0, 1),) if self.dim == 2 else ((0, 1), (0, 2), (1, 2))
+        counts = [1] if self.dim == 2 else [shape[2], shape[1], shape[0]]
+        n_sets = sets.shape[0]
+        flux = np.empty((n_sets, len(planes)) + shape, dtype=np.float64)
+        chern = np.empty((n_sets, sum(counts)), dtype=np.int64)
+        link_min = np.empty(n_sets, dtype=np.float64)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_berry_flux_multi(handles, n_handles, _lib.ptr(mesh_array), n_sets, _lib.ptr(sets), int(convention),
+                                                _lib.ptr(pos), _lib.ptr(flux), _lib.ptr(chern), _lib.ptr(link_min))
+            )
+        edges = np.cumsum([0] + counts)
+        return BerryFlux(sets, planes, flux, tuple(np.ascontiguousarray(chern[:, edges[p]:edges[p + 1]]) for p in range(len(planes))),
+                         link_min)
 
     def construct_kdotp(self, k, order):
         """

@@ -1054,6 +1054,23 @@ struct ChiDrain {
 
 }  // namespace
 
+int tbk_chi_fill_eigensystem(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, bool with_u, double* d_E, double* d_U) {
+    if (!with_u) return tbk_eigenval_device_hint(m, d_k, h_k, nk, d_E);
+    // eigh's own E, so that E and U belong together
+    const int dim = m->dim, n_orb = m->n_orb;
+    const size_t nn2 = (size_t)n_orb * n_orb * 2;
+    const int64_t chunk = OccStaged::chunk_of(m, nk);
+    for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
+        const int64_t nkc = std::min(chunk, nk - c0);
+        TBK_CHECK(tbk_eigh_device(m, d_k + c0 * dim, nkc, 2, nullptr, d_E + (size_t)c0 * n_orb, d_U + (size_t)c0 * nn2));
+    }
+    return TBK_OK;
+}
+
+int tbk_chi_phase_table(int dim, const int32_t* mesh, int n_orb, int64_t n_q, const int64_t* q, const double* pos, std::vector<double>* out) {
+    return chi_phase_table(dim, mesh, n_orb, n_q, q, pos, out);
+}
+
 extern "C" int tbk_chi_plan(int64_t nk, int n_orb, int64_t n_q, int matrix_elements, int64_t part_bytes, int64_t* out) {
     TBK_ARG(nk >= 1 && n_orb >= 1 && n_orb <= CHI_MAX_ORB && n_q >= 1 && part_bytes >= 0 && out != nullptr,
             "nk / n_orb / n_q < 1, more than 16320 orbitals, part_bytes < 0 or out is NULL");
@@ -1188,16 +1205,7 @@ static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_
         if (with_d)
             TBK_HIP(hipMemcpyAsync(d_D, h_D.data() + (size_t)q_lo * n_orb * 2, (size_t)q_n * n_orb * sizeof(double2), hipMemcpyHostToDevice,
                                    m->stream));
-        if (with_u) {
-            // eigh's own E, so that E and U belong together
-            const int64_t chunk = OccStaged::chunk_of(m, nk);
-            for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
-                const int64_t nkc = std::min(chunk, nk - c0);
-                TBK_CHECK(tbk_eigh_device(m, d_k + c0 * dim, nkc, 2, nullptr, d_E + (size_t)c0 * n_orb, d_U + (size_t)c0 * nn2));
-            }
-        } else {
-            TBK_CHECK(tbk_eigenval_device_hint(m, d_k, h_k.data(), nk, d_E));
-        }
+        TBK_CHECK(tbk_chi_fill_eigensystem(m, d_k, h_k.data(), nk, with_u, d_E, d_U));
         if (ob.on)
             TBK_CHECK(chi_orb_launch_all(m->stream, LO, &ev[(size_t)i], d_U, d_E, d_E + (size_t)nk * n_orb, d_Q, d_D, d_lists, q_n, mu, T,
                                          m->ws_chi_part.as<double>(), d_chi));

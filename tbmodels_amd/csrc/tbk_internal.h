@@ -178,10 +178,10 @@ struct SpanRecorder {
 };
 
 // The sums the mesh calls book their kernel times on, one row per family (tbk_dos_timing, tbk_pdos_timing, tbk_fermi_timing,
-// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing: what each counts differs and is listed in DESIGN.md section 10)
-enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_COUNT };
+// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing: what each counts differs and is listed in DESIGN.md section 10)
+enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_COUNT };
 struct TimedSums {
-    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm and chi three)
+    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi and berry three)
     int64_t calls = 0;
     int64_t passes = 0;  // fermi: the passes of its searches
 };
@@ -348,6 +348,8 @@ struct tbk_model {
     DevBuf ws_chi_u;     // ... the resident eigenvectors of the whole mesh [NK][n_orb][n_orb] complex (with matrix elements)
     DevBuf ws_chi_q;     // ... this handle's vectors: chi [n_q], 256-byte aligned the phases D [n_q][n_orb] complex (convention 1), the reduced q int32 [n_q][3]
     DevBuf ws_chi_part;  // ... the partial sums of one batch of vectors [batch][NK][blocks]
+                         // (tbk_berry_flux, tbk_berry.hip, keeps its resident eigenvectors in the same k / e / u; q: its links, words,
+                         // |L| and phases; part: the plaquette kernel's outputs, the gathered words, the library path's batch)
     std::vector<EventSpan> events;  // StageTimer's spans, read by tbk_get_timing (no synchronisation on the pipeline's path)
     double t_ms[TBK_T_COUNT] = {0, 0, 0, 0};
     int64_t t_n[TBK_T_COUNT] = {0, 0, 0, 0};

@@ -40,7 +40,14 @@ int occ_clear_buf(hipStream_t s, const OccPlan& L, char* ws);
 int occ_launch_contract(hipStream_t s, const OccPlan& L, const double* d_U, const double* d_w, int64_t c0, int64_t nkc, double nk_total, char* ws);
 int occ_launch_reduce(hipStream_t s, const OccPlan& L, char* ws);
 
-inline constexpr const char* OCC_MESH = "the tetrahedron weights need a 2- or 3-dimensional mesh";
+// ---- what the calls on the resident eigensystem of a whole mesh share (tbk_chi.hip; tbk_berry.hip calls them too) ------------------
+// The eigensystem of the nk mesh points d_k (h_k: the same list on the host) on a handle whose device is current, enqueued on its
+// stream: with_u, tbk_eigh_device chunk by chunk (its own E, so that E and U belong together), else the eigenvalue path alone.
+int tbk_chi_fill_eigensystem(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, bool with_u, double* d_E, double* d_U);
+// D[n_q][n_orb] (re, im) of convention 1: exp(-2 pi i sum_d q_d pos[i][d] / n_d), the unreduced q_d
+int tbk_chi_phase_table(int dim, const int32_t* mesh, int n_orb, int64_t n_q, const int64_t* q, const double* pos, std::vector<double>* out);
+
+inline constexpr const char* OCC_MESH ="the tetrahedron weights need a 2- or 3-dimensional mesh";
 
 // ---- the mesh on staged handles ------------------------------------------------------------------------------------------------
 struct OccSlab {
