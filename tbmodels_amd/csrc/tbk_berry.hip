@@ -37,7 +37,8 @@
 
 #include <rocsolver/rocsolver.h>
 
-#include "tbk_occ.h"
+#include "tbk_occ.h"  // OCC_MESH
+#include "tbk_resident.h"
 
 namespace {
 
@@ -506,20 +507,7 @@ int berry_check_low(const std::vector<uint64_t>& low) {
     return TBK_OK;
 }
 
-// Waits for what a call has enqueued on its handles' streams when the call ends, however it ends (tbk_dm.hip: DmDrain).
-struct BerryDrain {
-    std::vector<tbk_model*> used;
-    ~BerryDrain() {
-        for (tbk_model* m : used)
-            if (hipSetDevice(m->device) == hipSuccess) (void)hipStreamSynchronize(m->stream);
-    }
-};
-
-int berry_reserve(DevBuf& buf, size_t bytes, const char* what) {
-    const int r = buf.reserve(bytes);
-    if (r == TBK_ERR_MEMORY) tbk_set_error("the Berry flux keeps %s in device memory: %zu bytes do not fit", what, bytes);
-    return r;
-}
+constexpr const char* BERRY_FAMILY = "the Berry flux";
 
 }  // namespace
 
@@ -548,7 +536,7 @@ extern "C" int tbk_berry_links_from_eigensystem(int device, int dim, const int32
     const size_t u_bytes = (size_t)nk * n_orb * n_orb * sizeof(double2), d_bytes = (size_t)dim * n_orb * sizeof(double2);
     const size_t lib_bytes = berry_lib_bytes(sets, n_links);
     DevBuf d_U, d_D, d_lib, d_L, d_W, d_A;
-    TBK_CHECK(berry_reserve(d_U, u_bytes, "the eigenvectors of the whole mesh"));
+    TBK_CHECK(mesh_reserve(d_U, u_bytes, BERRY_FAMILY, "the eigenvectors of the whole mesh"));
     if (phases) TBK_CHECK(d_D.reserve(d_bytes));
     if (lib_bytes) TBK_CHECK(d_lib.reserve(lib_bytes));
     TBK_CHECK(d_L.reserve(items * sizeof(double2)));
@@ -605,67 +593,56 @@ extern "C" int tbk_berry_flux_multi(tbk_model* const* handles, int n_handles, co
     const BerryMesh g = berry_mesh(dim, mesh, nk);
     const int slices = berry_slices(dim, mesh), planes = dim == 3 ? 3 : 1;
     const BerryOut o(n_sets, planes, nk, slices);
-    std::vector<double> h_k, h_D;
-    TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, 0, mesh[0], &h_k));
+    // (the host buffers the enqueued copies read and write, in front of `res`: its streams wait before they go)
+    std::vector<double> h_D, h_abs, piece_a;
+    std::vector<uint64_t> h_words, piece_w, low;
+    ResidentMesh res;
+    TBK_CHECK(res.open(dim, mesh, n_orb, nk));
     if (convention == 1) {
         int64_t unit[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int d = 0; d < dim; ++d) unit[d * dim + d] = 1;
-        TBK_CHECK(tbk_chi_phase_table(dim, mesh, n_orb, dim, unit, pos, &h_D));
+        TBK_CHECK(mesh_phase_table(dim, mesh, n_orb, dim, unit, pos, &h_D));
     }
     // every handle holds the whole mesh's eigensystem and takes a contiguous share of the mesh points' links
     const TetraSlabs share(nk, n_handles);
     const bool alone = share.busy() == 1;
-    const size_t e_bytes = (size_t)nk * n_orb * sizeof(double), u_bytes = (size_t)nk * n_orb * n_orb * sizeof(double2);
     const size_t d_bytes = h_D.size() * sizeof(double);
     const size_t all_links = (size_t)n_sets * dim * nk;
-    std::vector<SpanRecorder> ev((size_t)share.busy());
     std::vector<uint64_t*> dev_words((size_t)share.busy());
     std::vector<double*> dev_abs((size_t)share.busy());
-    BerryDrain drain;
     for (int i = 0; i < share.busy(); ++i) {
         tbk_model* m = handles[i];
         const int64_t k_lo = share.lo(i), k_n = share.count(i);
         const int64_t n_links = (int64_t)dim * k_n;
         const size_t items = (size_t)n_sets * n_links;
-        TBK_CHECK(tbk_eig_check_option(m));
-        TBK_HIP(hipSetDevice(m->device));
-        drain.used.push_back(m);
-        ev[(size_t)i] = SpanRecorder(m->timing, m->stream);
-        TBK_CHECK(m->ws_chi_k.reserve(h_k.size() * sizeof(double)));
-        TBK_CHECK(berry_reserve(m->ws_chi_e, e_bytes, "the eigenvalues of the whole mesh"));
-        TBK_CHECK(berry_reserve(m->ws_chi_u, u_bytes, "the eigenvectors of the whole mesh"));
-        // ws_chi_q: this handle's links L, words, |L|, then the phases; ws_chi_part: (handle 0) the plaquette kernel's outputs and,
+        TBK_CHECK(res.stage(m, BERRY_FAMILY, (size_t)nk * n_orb * sizeof(double), "the eigenvalues of the whole mesh", true));
+        // ws_mesh_io: this handle's links L, words, |L|, then the phases; ws_mesh_work: (handle 0) the plaquette kernel's outputs and,
         // with several handles, the words and |L| of the whole mesh; behind them the library path's batch
         const size_t off_w = dos_align256(items * sizeof(double2)), off_a = off_w + dos_align256(items * sizeof(uint64_t));
         const size_t off_d = off_a + dos_align256(items * sizeof(double));
-        TBK_CHECK(m->ws_chi_q.reserve(off_d + d_bytes + 256));
+        TBK_CHECK(m->ws_mesh_io.reserve(off_d + d_bytes + 256));
         const size_t off_all = i == 0 ? dos_align256(o.bytes) : 0;
         const size_t off_lib = off_all + (i == 0 && !alone ? dos_align256(all_links * sizeof(uint64_t)) + dos_align256(all_links * sizeof(double)) : 0);
         const size_t lib_bytes = berry_lib_bytes(sets, n_links);
-        TBK_CHECK(berry_reserve(m->ws_chi_part, off_lib + lib_bytes + 256, "the workspace of the links"));
-        double* d_k = m->ws_chi_k.as<double>();
-        char* q = m->ws_chi_q.as<char>();
+        TBK_CHECK(mesh_reserve(m->ws_mesh_work, off_lib + lib_bytes + 256, BERRY_FAMILY, "the workspace of the links"));
+        char* q = m->ws_mesh_io.as<char>();
         double* d_L = reinterpret_cast<double*>(q);
         dev_words[(size_t)i] = reinterpret_cast<uint64_t*>(q + off_w);
         dev_abs[(size_t)i] = reinterpret_cast<double*>(q + off_a);
         double* d_D = convention == 1 ? reinterpret_cast<double*>(q + off_d) : nullptr;
-        TBK_HIP(hipMemcpyAsync(d_k, h_k.data(), h_k.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
+        TBK_CHECK(res.upload(m));
         if (d_D) TBK_HIP(hipMemcpyAsync(d_D, h_D.data(), d_bytes, hipMemcpyHostToDevice, m->stream));
-        TBK_CHECK(tbk_chi_fill_eigensystem(m, d_k, h_k.data(), nk, true, m->ws_chi_e.as<double>(), m->ws_chi_u.as<double>()));
-        TBK_CHECK(berry_launch_links(m->stream, m->blas, &ev[(size_t)i], g, n_orb, sets, m->ws_chi_u.as<double>(), d_D, k_lo, k_n,
-                                     m->ws_chi_part.as<char>() + off_lib, d_L, dev_words[(size_t)i], dev_abs[(size_t)i]));
+        TBK_CHECK(res.fill(m, true));
+        TBK_CHECK(berry_launch_links(m->stream, m->blas, res.ev(), g, n_orb, sets, m->ws_mesh_u.as<double>(), d_D, k_lo, k_n,
+                                     m->ws_mesh_work.as<char>() + off_lib, d_L, dev_words[(size_t)i], dev_abs[(size_t)i]));
     }
     tbk_model* m0 = handles[0];
-    char* d_out = m0->ws_chi_part.as<char>();
+    char* d_out = m0->ws_mesh_work.as<char>();
     const uint64_t* d_words = dev_words[0];
     const double* d_abs = dev_abs[0];
-    std::vector<uint64_t> h_words;
-    std::vector<double> h_abs;
     if (!alone) {
         // synchronises every handle (the eigensolver's flags are reported as by tbk_eigh); the host puts the shares side by side
-        for (tbk_model* m : drain.used) TBK_CHECK(tbk_eigenval_check(m));
-        std::vector<uint64_t> piece_w;
-        std::vector<double> piece_a;
+        TBK_CHECK(res.streams.check());
         try {
             h_words.resize(all_links);
             h_abs.resize(all_links);
@@ -695,21 +672,14 @@ extern "C" int tbk_berry_flux_multi(tbk_model* const* handles, int n_handles, co
         d_abs = all_a;
     }
     TBK_HIP(hipSetDevice(m0->device));
-    TBK_CHECK(berry_launch_flux(m0->stream, &ev[0], g, n_sets, slices, d_words, d_abs, o, d_out));
-    std::vector<uint64_t> low((size_t)n_sets * slices);
+    low.resize((size_t)n_sets * slices);
+    TBK_CHECK(berry_launch_flux(m0->stream, &res.streams.used.front().ev, g, n_sets, slices, d_words, d_abs, o, d_out));
     TBK_HIP(hipMemcpyAsync(flux_out, d_out, (size_t)n_sets * planes * nk * sizeof(double), hipMemcpyDeviceToHost, m0->stream));
     TBK_HIP(hipMemcpyAsync(chern_out, d_out + o.off_chern, low.size() * sizeof(int64_t), hipMemcpyDeviceToHost, m0->stream));
     TBK_HIP(hipMemcpyAsync(low.data(), d_out + o.off_low, low.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, m0->stream));
     TBK_HIP(hipMemcpyAsync(link_min_out, d_out + o.off_min, (size_t)n_sets * sizeof(double), hipMemcpyDeviceToHost, m0->stream));
     // synchronises every handle (the eigensolver's flags are reported as by tbk_eigh) and books the kernel times
-    for (tbk_model* m : drain.used) TBK_CHECK(tbk_eigenval_check(m));
-    for (size_t i = 0; i < drain.used.size(); ++i) {
-        tbk_model* m = drain.used[i];
-        TBK_HIP(hipSetDevice(m->device));
-        TBK_HIP(hipStreamSynchronize(m->stream));
-        ev[i].collect(m->timed[TIMED_BERRY].ms);
-        m->timed[TIMED_BERRY].calls += 1;
-    }
+    TBK_CHECK(res.streams.finish(TIMED_BERRY));
     return berry_check_low(low);
 }
 

@@ -83,19 +83,27 @@ struct ChiMesh {
     int64_t nk;  // points of the mesh
 };
 
+// the plan of a call of one of the three kinds: static (n_w = 0, m = 0), dynamic (n_w > 0), orbital-resolved (m > 0)
 struct ChiPlan {
     ChiMesh mesh;
     int n = 0;            // orbitals
-    int bt = 0;           // template of the overlap kernel: 4, 1 (up to 16 orbitals), 0: no matrix elements (chi_pair_kernel)
-    int64_t blocks = 1;   // partials per (k, q)
+    int bt = 0;           // template of the overlap kernel: 4, 1 (up to 16 orbitals), 0: no matrix elements (chi_pair_kernel);
+                          // orbital-resolved: of chi_orbital_kernel, 4, 1 (m <= 16)
+    int64_t blocks = 1;   // partials per (k, q); orbital-resolved: blocks with bi <= bj of one vector
     int64_t batch = 1;    // vectors per launch
     int64_t batches = 1;
-    int64_t n_w = 0;      // frequencies (0: the static call)
-    int64_t w_pass = 0;   // frequencies per launch
+    int64_t n_w = 0;      // dynamic: frequencies
+    int64_t w_pass = 0;   // ... per launch
     int64_t passes = 1;
-    size_t part_bytes() const {
-        return n_w == 0 ? (size_t)batch * mesh.nk * blocks * sizeof(double) : (size_t)batch * w_pass * mesh.nk * blocks * sizeof(double2);
+    int m = 0;            // orbital-resolved: selected orbitals
+    int mp = 0;           // ... padded to the block
+    int64_t ks = 1;       // ... k-points per slice
+    int64_t slices = 1;
+    // the partials of one vector (dynamic: at one frequency), and of one batch
+    size_t per_q() const {
+        return m > 0 ? (size_t)slices * mp * mp * sizeof(double2) : (size_t)mesh.nk * (size_t)blocks * (n_w == 0 ? sizeof(double) : sizeof(double2));
     }
+    size_t part_bytes() const { return (size_t)batch * (n_w == 0 ? 1 : (size_t)w_pass) * per_q(); }
 };
 
 // what the dynamic epilogue reads besides the static one's arguments (all zero: the static kernels)
@@ -738,28 +746,6 @@ struct ChiFreq {
     double eta = 0.0;
 };
 
-int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, int64_t n_w, bool matrix_elements, size_t mem, ChiPlan* out) {
-    ChiPlan L;
-    L.mesh.n[0] = mesh[0];
-    L.mesh.n[1] = mesh[1];
-    L.mesh.n[2] = dim == 3 ? mesh[2] : 1;
-    L.mesh.nk = nk;
-    L.n = n_orb;
-    TBK_ARG(nk <= CHI_MAX_NK, "the susceptibility takes meshes of up to 2^23 points");
-    L.n_w = n_w;
-    if (n_w == 0)
-        chi_plan_sizes(nk, n_orb, n_q, matrix_elements, mem, &L.bt, &L.blocks, &L.batch, &L.batches);
-    else
-        chi_dyn_plan_sizes(nk, n_orb, n_q, n_w, matrix_elements, mem, &L.bt, &L.blocks, &L.batch, &L.batches, &L.w_pass, &L.passes);
-    if (L.batch < 1) {
-        tbk_set_error("the partial sums of one susceptibility vector%s need %zu bytes of device memory", n_w == 0 ? "" : " at one frequency",
-                      (size_t)nk * (size_t)L.blocks * (n_w == 0 ? sizeof(double) : sizeof(double2)));
-        return TBK_ERR_MEMORY;
-    }
-    *out = L;
-    return TBK_OK;
-}
-
 // q[n_q][dim] reduced to [0, n_d) per axis, three entries per vector
 int chi_reduce_q(int dim, const int32_t* mesh, int64_t n_q, const int64_t* q, std::vector<int32_t>* out) {
     try {
@@ -772,26 +758,6 @@ int chi_reduce_q(int dim, const int32_t* mesh, int64_t n_q, const int64_t* q, st
         for (int d = 0; d < dim; ++d) {
             const int64_t nd = mesh[d];
             (*out)[(size_t)r * 3 + d] = (int32_t)(((q[r * dim + d] % nd) + nd) % nd);
-        }
-    return TBK_OK;
-}
-
-// D[n_q][n_orb] of convention 1: exp(-2 pi i sum_d q_d pos[i][d] / n_d), the unreduced q_d (tools/chi_model.py phase_table)
-int chi_phase_table(int dim, const int32_t* mesh, int n_orb, int64_t n_q, const int64_t* q, const double* pos, std::vector<double>* out) {
-    try {
-        out->resize((size_t)n_q * n_orb * 2);
-    } catch (...) {
-        tbk_set_error("cannot allocate the orbital phases");
-        return TBK_ERR_MEMORY;
-    }
-    const double two_pi = 6.283185307179586476925286766559;
-    for (int64_t r = 0; r < n_q; ++r)
-        for (int i = 0; i < n_orb; ++i) {
-            double angle = 0.0;
-            for (int d = 0; d < dim; ++d) angle = angle + ((double)q[r * dim + d] * pos[(size_t)i * dim + d]) / (double)mesh[d];
-            angle = -two_pi * angle;
-            (*out)[((size_t)r * n_orb + i) * 2] = std::cos(angle);
-            (*out)[((size_t)r * n_orb + i) * 2 + 1] = std::sin(angle);
         }
     return TBK_OK;
 }
@@ -870,41 +836,9 @@ int chi_launch_dyn_batch(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, cons
     return TBK_OK;
 }
 
-// all batches of n_q vectors whose reduced entries (and phases) are on the device; d_chi[n_q], or [n_q][L.n_w] complex with the
-// frequencies d_W of a dynamic call
-int chi_launch_all(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, double* d_tab, const int32_t* d_Q,
-                   const double* d_D, int64_t n_q, double mu, double T, const double* d_W, double eta, double* d_part, double* d_chi) {
-    TBK_CHECK(chi_launch_fermi(s, L, ev, d_E, mu, T, d_tab));
-    for (int64_t q0 = 0; q0 < n_q; q0 += L.batch) {
-        const int64_t nq = std::min(L.batch, n_q - q0);
-        if (L.n_w > 0) {
-            TBK_CHECK(chi_launch_dyn_batch(s, L, ev, d_U, d_E, d_tab, d_Q + q0 * 3, d_D ? d_D + (size_t)q0 * L.n * 2 : nullptr, nq, T, d_W, eta,
-                                           d_part, d_chi + (size_t)q0 * L.n_w * 2));
-            continue;
-        }
-        TBK_CHECK(chi_launch_batch(s, L, ev, d_U, d_E, d_tab, d_Q + q0 * 3, d_D ? d_D + (size_t)q0 * L.n * 2 : nullptr, nq, T, d_part,
-                                   d_chi + q0));
-    }
-    return TBK_OK;
-}
-
 // ---- the orbital-resolved call's plan, arguments and launches ----------------------------------------------------------------------
 constexpr int64_t CHI_ORB_AMORTISE = 1024;  // (b, b') pairs a slice walks at least per register-resident block
 constexpr int64_t CHI_ORB_SLICES = 1024;    // slices of one vector, about: four workgroups (or one of four slices) per compute unit
-
-struct ChiOrbPlan {
-    ChiMesh mesh;
-    int n = 0;            // orbitals
-    int m = 0;            // selected orbitals
-    int mp = 0;           // m padded to the block
-    int bt = 0;           // template of chi_orbital_kernel: 4, 1 (m <= 16)
-    int64_t blocks = 1;   // blocks with bi <= bj of one vector
-    int64_t ks = 1;       // k-points per slice
-    int64_t slices = 1;
-    int64_t batch = 1;    // vectors per launch
-    int64_t batches = 1;
-    size_t part_bytes() const { return (size_t)batch * slices * mp * mp * sizeof(double2); }
-};
 
 // the library's slice length, a function of (NK, n_orb) alone -- not of the selection, the vectors, the batch or the handles, so that
 // the bits of an element are those of any call that contains it: long enough to walk CHI_ORB_AMORTISE pairs per block held in
@@ -919,7 +853,7 @@ int64_t chi_orb_slice(int64_t nk, int n_orb) {
 
 // the one place that chooses: template, blocks, slice length (k_slice = 0: the library's), slices, batch from the bytes the partials
 // may take (0: the budget)
-void chi_orb_plan_sizes(int64_t nk, int n_orb, int m, int64_t n_q, size_t mem, int64_t k_slice, ChiOrbPlan* L) {
+void chi_orb_plan_sizes(int64_t nk, int n_orb, int m, int64_t n_q, size_t mem, int64_t k_slice, ChiPlan* L) {
     L->n = n_orb;
     L->m = m;
     L->bt = m <= 16 ? 1 : 4;
@@ -935,17 +869,30 @@ void chi_orb_plan_sizes(int64_t nk, int n_orb, int m, int64_t n_q, size_t mem, i
     L->batches = L->batch == 0 ? 0 : (n_q + L->batch - 1) / L->batch;
 }
 
-int chi_orb_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int m, int64_t n_q, size_t mem, int64_t k_slice, ChiOrbPlan* out) {
-    ChiOrbPlan L;
+// The plan of n_q vectors on a mesh of nk points: n_w frequencies (0: static), m selected orbitals (0: the scalar calls; k_slice
+// is theirs); mem: the bytes the partials may take (0: the budget)
+int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, int64_t n_w, int m, bool matrix_elements, size_t mem,
+             int64_t k_slice, ChiPlan* out) {
+    ChiPlan L;
     L.mesh.n[0] = mesh[0];
     L.mesh.n[1] = mesh[1];
     L.mesh.n[2] = dim == 3 ? mesh[2] : 1;
     L.mesh.nk = nk;
+    L.n = n_orb;
     TBK_ARG(nk <= CHI_MAX_NK, "the susceptibility takes meshes of up to 2^23 points");
-    chi_orb_plan_sizes(nk, n_orb, m, n_q, mem, k_slice, &L);
+    L.n_w = n_w;
+    if (m > 0)
+        chi_orb_plan_sizes(nk, n_orb, m, n_q, mem, k_slice, &L);
+    else if (n_w == 0)
+        chi_plan_sizes(nk, n_orb, n_q, matrix_elements, mem, &L.bt, &L.blocks, &L.batch, &L.batches);
+    else
+        chi_dyn_plan_sizes(nk, n_orb, n_q, n_w, matrix_elements, mem, &L.bt, &L.blocks, &L.batch, &L.batches, &L.w_pass, &L.passes);
     if (L.batch < 1) {
-        tbk_set_error("the partial sums of one orbital-resolved susceptibility vector need %zu bytes of device memory",
-                      (size_t)L.slices * L.mp * L.mp * sizeof(double2));
+        if (m > 0)
+            tbk_set_error("the partial sums of one orbital-resolved susceptibility vector need %zu bytes of device memory", L.per_q());
+        else
+            tbk_set_error("the partial sums of one susceptibility vector%s need %zu bytes of device memory", n_w == 0 ? "" : " at one frequency",
+                          L.per_q());
         return TBK_ERR_MEMORY;
     }
     *out = L;
@@ -960,7 +907,9 @@ struct ChiOrb {
 };
 
 // lists[0 .. m): the selection in ascending order; lists[m .. 2 m): the place of each in the caller's order
+// (a scalar call: none)
 int chi_orb_lists(const ChiOrb& ob, int n_orb, std::vector<int32_t>* lists) {
+    if (!ob.on) return TBK_OK;
     TBK_ARG(ob.m >= 1 && ob.m <= n_orb, "m < 1 or more selected orbitals than the model has");
     TBK_ARG(ob.orbitals != nullptr || ob.m == n_orb, "orbitals is NULL and m is not n_orb");
     try {
@@ -982,39 +931,50 @@ int chi_orb_lists(const ChiOrb& ob, int n_orb, std::vector<int32_t>* lists) {
     return TBK_OK;
 }
 
-// all batches of n_q vectors; d_lists: chi_orb_lists' on the device; d_chi [n_q][m][m] complex
-int chi_orb_launch_all(hipStream_t s, const ChiOrbPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, double* d_tab,
-                       const int32_t* d_Q, const double* d_D, const int32_t* d_lists, int64_t n_q, double mu, double T, double* d_part,
-                       double* d_chi) {
+// the orbital-resolved call's: nq vectors (at most L.batch); d_lists: chi_orb_lists' on the device; d_chi: their [.][m][m] complex
+int chi_launch_orb_batch(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, const double* d_tab,
+                         const int32_t* d_Q, const double* d_D, const int32_t* d_lists, int64_t nq, double T, double* d_part, double* d_chi) {
     const double inv_t = 1.0 / T;
-    const int64_t items = L.mesh.nk * L.n;
-    if (ev) ev->start(0);
-    hipLaunchKernelGGL(chi_fermi_kernel, dim3((unsigned)((items + CHI_THREADS - 1) / CHI_THREADS)), dim3(CHI_THREADS), 0, s, d_E, items, mu, T,
-                       d_tab);
+    const int64_t elements = (int64_t)L.m * L.m;
+    const double2* D = reinterpret_cast<const double2*>(d_D);
+    if (ev) ev->start(1);
+    if (L.bt == 1) {
+        hipLaunchKernelGGL((chi_orbital_kernel<1>), dim3((unsigned)((L.slices + 3) / 4), 1, (unsigned)nq), dim3(CHI_THREADS), 0, s,
+                           reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q, D, inv_t, d_lists, L.m, L.mp, L.ks, L.slices,
+                           reinterpret_cast<double2*>(d_part));
+    } else {
+        hipLaunchKernelGGL((chi_orbital_kernel<4>), dim3((unsigned)L.slices, (unsigned)L.blocks, (unsigned)nq), dim3(CHI_THREADS), 0, s,
+                           reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q, D, inv_t, d_lists, L.m, L.mp, L.ks, L.slices,
+                           reinterpret_cast<double2*>(d_part));
+    }
     if (ev) ev->stop();
     TBK_HIP(hipGetLastError());
-    const int64_t elements = (int64_t)L.m * L.m;
+    if (ev) ev->start(2);
+    hipLaunchKernelGGL(chi_reduce_orb_kernel, dim3((unsigned)((elements + CHI_THREADS - 1) / CHI_THREADS), (unsigned)nq), dim3(CHI_THREADS), 0, s,
+                       reinterpret_cast<const double2*>(d_part), L.m, L.mp, L.slices, T, (double)L.mesh.nk, d_lists + L.m,
+                       reinterpret_cast<double2*>(d_chi));
+    if (ev) ev->stop();
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// The Fermi tables once, then all batches of n_q vectors whose reduced entries (and phases) are on the device, by the plan's kind:
+// d_chi [n_q], [n_q][L.n_w] complex with the frequencies d_W of a dynamic call, or [n_q][m][m] complex with the orbital-resolved
+// call's d_lists
+int chi_launch_all(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, double* d_tab, const int32_t* d_Q,
+                   const double* d_D, const int32_t* d_lists, int64_t n_q, double mu, double T, const double* d_W, double eta, double* d_part,
+                   double* d_chi) {
+    TBK_CHECK(chi_launch_fermi(s, L, ev, d_E, mu, T, d_tab));
     for (int64_t q0 = 0; q0 < n_q; q0 += L.batch) {
         const int64_t nq = std::min(L.batch, n_q - q0);
-        const double2* D = d_D ? reinterpret_cast<const double2*>(d_D) + (size_t)q0 * L.n : nullptr;
-        if (ev) ev->start(1);
-        if (L.bt == 1) {
-            hipLaunchKernelGGL((chi_orbital_kernel<1>), dim3((unsigned)((L.slices + 3) / 4), 1, (unsigned)nq), dim3(CHI_THREADS), 0, s,
-                               reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q + q0 * 3, D, inv_t, d_lists, L.m, L.mp, L.ks,
-                               L.slices, reinterpret_cast<double2*>(d_part));
-        } else {
-            hipLaunchKernelGGL((chi_orbital_kernel<4>), dim3((unsigned)L.slices, (unsigned)L.blocks, (unsigned)nq), dim3(CHI_THREADS), 0, s,
-                               reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q + q0 * 3, D, inv_t, d_lists, L.m, L.mp, L.ks,
-                               L.slices, reinterpret_cast<double2*>(d_part));
-        }
-        if (ev) ev->stop();
-        TBK_HIP(hipGetLastError());
-        if (ev) ev->start(2);
-        hipLaunchKernelGGL(chi_reduce_orb_kernel, dim3((unsigned)((elements + CHI_THREADS - 1) / CHI_THREADS), (unsigned)nq), dim3(CHI_THREADS), 0,
-                           s, reinterpret_cast<const double2*>(d_part), L.m, L.mp, L.slices, T, (double)L.mesh.nk, d_lists + L.m,
-                           reinterpret_cast<double2*>(d_chi) + (size_t)q0 * elements);
-        if (ev) ev->stop();
-        TBK_HIP(hipGetLastError());
+        const int32_t* Q = d_Q + q0 * 3;
+        const double* D = d_D ? d_D + (size_t)q0 * L.n * 2 : nullptr;
+        if (L.m > 0)
+            TBK_CHECK(chi_launch_orb_batch(s, L, ev, d_U, d_E, d_tab, Q, D, d_lists, nq, T, d_part, d_chi + (size_t)q0 * L.m * L.m * 2));
+        else if (L.n_w > 0)
+            TBK_CHECK(chi_launch_dyn_batch(s, L, ev, d_U, d_E, d_tab, Q, D, nq, T, d_W, eta, d_part, d_chi + (size_t)q0 * L.n_w * 2));
+        else
+            TBK_CHECK(chi_launch_batch(s, L, ev, d_U, d_E, d_tab, Q, D, nq, T, d_part, d_chi + q0));
     }
     return TBK_OK;
 }
@@ -1036,40 +996,14 @@ int chi_check_frequencies(int64_t n_w, const double* omega, double eta) {
     return TBK_OK;
 }
 
-// a reservation whose failure names the bytes
-int chi_reserve(DevBuf& buf, size_t bytes, const char* what) {
-    const int r = buf.reserve(bytes);
-    if (r == TBK_ERR_MEMORY) tbk_set_error("the susceptibility keeps %s in device memory: %zu bytes do not fit", what, bytes);
-    return r;
-}
+constexpr const char* CHI_FAMILY = "the susceptibility";
 
-// Waits for what a call has enqueued on its handles' streams when the call ends, however it ends (tbk_dm.hip: DmDrain).
-struct ChiDrain {
-    std::vector<tbk_model*> used;
-    ~ChiDrain() {
-        for (tbk_model* m : used)
-            if (hipSetDevice(m->device) == hipSuccess) (void)hipStreamSynchronize(m->stream);
-    }
-};
+// the bytes of one vector's result: a double, n_w complex numbers, or the m x m complex matrix
+size_t chi_out_per_q(const ChiFreq& fr, const ChiOrb& ob) {
+    return ob.on ? (size_t)ob.m * ob.m * sizeof(double2) : fr.n_w == 0 ? sizeof(double) : (size_t)fr.n_w * sizeof(double2);
+}
 
 }  // namespace
-
-int tbk_chi_fill_eigensystem(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, bool with_u, double* d_E, double* d_U) {
-    if (!with_u) return tbk_eigenval_device_hint(m, d_k, h_k, nk, d_E);
-    // eigh's own E, so that E and U belong together
-    const int dim = m->dim, n_orb = m->n_orb;
-    const size_t nn2 = (size_t)n_orb * n_orb * 2;
-    const int64_t chunk = OccStaged::chunk_of(m, nk);
-    for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
-        const int64_t nkc = std::min(chunk, nk - c0);
-        TBK_CHECK(tbk_eigh_device(m, d_k + c0 * dim, nkc, 2, nullptr, d_E + (size_t)c0 * n_orb, d_U + (size_t)c0 * nn2));
-    }
-    return TBK_OK;
-}
-
-int tbk_chi_phase_table(int dim, const int32_t* mesh, int n_orb, int64_t n_q, const int64_t* q, const double* pos, std::vector<double>* out) {
-    return chi_phase_table(dim, mesh, n_orb, n_q, q, pos, out);
-}
 
 extern "C" int tbk_chi_plan(int64_t nk, int n_orb, int64_t n_q, int matrix_elements, int64_t part_bytes, int64_t* out) {
     TBK_ARG(nk >= 1 && n_orb >= 1 && n_orb <= CHI_MAX_ORB && n_q >= 1 && part_bytes >= 0 && out != nullptr,
@@ -1080,30 +1014,35 @@ extern "C" int tbk_chi_plan(int64_t nk, int n_orb, int64_t n_q, int matrix_eleme
     return TBK_OK;
 }
 
-// the kernels on a caller's eigensystem: chi_out double [n_q], or with frequencies complex [n_q][n_w]; mem: the bytes the partials may
-// take (0: the budget)
+// the kernels on a caller's eigensystem: chi_out double [n_q], with frequencies complex [n_q][n_w], with a selection complex
+// [n_q][m][m]; mem: the bytes the partials may take (0: the budget), k_slice: the orbital-resolved call's slice (0: the library's)
 static int chi_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu, double T,
-                         int64_t n_q, const int64_t* q, const double* phases, const ChiFreq& fr, size_t mem, double* chi_out) {
+                         int64_t n_q, const int64_t* q, const double* phases, const ChiFreq& fr, const ChiOrb& ob, size_t mem, int64_t k_slice,
+                         double* chi_out) {
     int64_t nk = 0;
     TBK_CHECK(tetra_check_mesh(dim, mesh, OCC_MESH, &nk));
     TBK_ARG(E != nullptr, "E is NULL");
     TBK_ARG(std::isfinite(mu), "the chemical potential is not finite");
     TBK_CHECK(chi_check(T, n_q, q, chi_out, n_orb));
     if (fr.n_w != 0) TBK_CHECK(chi_check_frequencies(fr.n_w, fr.omega, fr.eta));
+    TBK_ARG(U != nullptr || !ob.on, "U is NULL: the orbital-resolved susceptibility needs the eigenvectors");
     TBK_ARG(U != nullptr || phases == nullptr, "phases without eigenvectors");
+    std::vector<int32_t> h_lists;
+    TBK_CHECK(chi_orb_lists(ob, n_orb, &h_lists));
     TBK_CHECK(tetra_check_device(device));
     ChiPlan L;
-    TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, n_q, fr.n_w, U != nullptr, mem, &L));
-    const size_t out_bytes = (size_t)n_q * (fr.n_w == 0 ? sizeof(double) : (size_t)fr.n_w * sizeof(double2));
+    TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, n_q, fr.n_w, ob.m, U != nullptr, mem, k_slice, &L));
+    const size_t out_bytes = (size_t)n_q * chi_out_per_q(fr, ob);
     std::vector<int32_t> h_Q;
     TBK_CHECK(chi_reduce_q(dim, mesh, n_q, q, &h_Q));
     const size_t e_bytes = (size_t)nk * n_orb * sizeof(double), u_bytes = (size_t)nk * n_orb * n_orb * sizeof(double2);
-    const size_t d_bytes = (size_t)n_q * n_orb * sizeof(double2);
-    DevBuf d_E, d_U, d_tab, d_Q, d_D, d_W, d_part, d_chi;
+    const size_t d_bytes = (size_t)n_q * n_orb * sizeof(double2), l_bytes = h_lists.size() * sizeof(int32_t);
+    DevBuf d_E, d_U, d_tab, d_Q, d_lists, d_D, d_W, d_part, d_chi;
     TBK_CHECK(d_E.reserve(e_bytes));
     TBK_CHECK(d_tab.reserve(2 * e_bytes));
-    if (U) TBK_CHECK(chi_reserve(d_U, u_bytes, "the eigenvectors of the whole mesh"));
+    if (U) TBK_CHECK(mesh_reserve(d_U, u_bytes, CHI_FAMILY, "the eigenvectors of the whole mesh"));
     TBK_CHECK(d_Q.reserve(h_Q.size() * sizeof(int32_t)));
+    if (l_bytes) TBK_CHECK(d_lists.reserve(l_bytes));
     if (phases) TBK_CHECK(d_D.reserve(d_bytes));
     TBK_CHECK(d_part.reserve(L.part_bytes()));
     TBK_CHECK(d_chi.reserve(out_bytes));
@@ -1114,15 +1053,16 @@ static int chi_from_eigensystem(int device, int dim, const int32_t* mesh, int n_
     TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
     if (U) TBK_HIP(hipMemcpy(d_U.ptr, U, u_bytes, hipMemcpyHostToDevice));
     TBK_HIP(hipMemcpy(d_Q.ptr, h_Q.data(), h_Q.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (l_bytes) TBK_HIP(hipMemcpy(d_lists.ptr, h_lists.data(), l_bytes, hipMemcpyHostToDevice));
     if (phases) TBK_HIP(hipMemcpy(d_D.ptr, phases, d_bytes, hipMemcpyHostToDevice));
     TBK_CHECK(chi_launch_all(nullptr, L, nullptr, d_U.as<double>(), d_E.as<double>(), d_tab.as<double>(), d_Q.as<int32_t>(),
-                             phases ? d_D.as<double>() : nullptr, n_q, mu, T, fr.n_w != 0 ? d_W.as<double>() : nullptr, fr.eta,
-                             d_part.as<double>(), d_chi.as<double>()));
+                             phases ? d_D.as<double>() : nullptr, d_lists.as<int32_t>(), n_q, mu, T, fr.n_w != 0 ? d_W.as<double>() : nullptr,
+                             fr.eta, d_part.as<double>(), d_chi.as<double>()));
     TBK_HIP(hipMemcpy(chi_out, d_chi.ptr, out_bytes, hipMemcpyDeviceToHost));
     return TBK_OK;
 }
 
-// the whole call, static (fr.n_w = 0, chi_out double [n_q]) or dynamic (complex [n_q][n_w])
+// the whole call: static (fr.n_w = 0, chi_out double [n_q]), dynamic (complex [n_q][n_w]) or orbital-resolved (ob.on, complex [n_q][m][m])
 static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T, int64_t n_q,
                    const int64_t* q, const ChiFreq& fr, const ChiOrb& ob, int matrix_elements, int convention, const double* pos,
                    double* mu_out, double* chi_out) {
@@ -1136,12 +1076,10 @@ static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_
         TBK_CHECK(tbk_fermi_check_electrons(value, handles[0]->n_orb));
     else
         TBK_ARG(std::isfinite(value), "the energy is not finite");
-    // the orbital-resolved call's own arguments (ob.on), before any device work
+    // the orbital-resolved call's own arguments, before any device work
+    TBK_ARG(matrix_elements != 0 || !ob.on, "the orbital-resolved susceptibility needs the eigenvectors");
     std::vector<int32_t> h_lists;
-    if (ob.on) {
-        TBK_ARG(matrix_elements != 0, "the orbital-resolved susceptibility needs the eigenvectors");
-        TBK_CHECK(chi_orb_lists(ob, handles[0]->n_orb, &h_lists));
-    }
+    TBK_CHECK(chi_orb_lists(ob, handles[0]->n_orb, &h_lists));
     const size_t l_bytes = h_lists.size() * sizeof(int32_t);
     // mu: the slab route of tbk_occupations as it stands
     OccStaged staged;
@@ -1151,85 +1089,61 @@ static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_
     const int n_orb = staged.n_orb, dim = staged.dim;
     const int64_t nk = staged.nk_total;
     const bool with_u = matrix_elements != 0, with_d = with_u && convention == 1;
+    // (h_lists, h_Q and h_D are the sources of enqueued copies: in front of `res`, whose streams wait before they go)
     std::vector<int32_t> h_Q;
     TBK_CHECK(chi_reduce_q(dim, mesh, n_q, q, &h_Q));
-    std::vector<double> h_D, h_k;
-    if (with_d) TBK_CHECK(chi_phase_table(dim, mesh, n_orb, n_q, q, pos, &h_D));
-    TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, 0, mesh[0], &h_k));
+    std::vector<double> h_D;
+    if (with_d) TBK_CHECK(mesh_phase_table(dim, mesh, n_orb, n_q, q, pos, &h_D));
+    ResidentMesh res;
+    TBK_CHECK(res.open(dim, mesh, n_orb, nk));
     // every handle holds the whole mesh's eigensystem and takes a contiguous share of the vectors
     const TetraSlabs share(n_q, n_handles);
-    const size_t e_bytes = (size_t)nk * n_orb * sizeof(double), nn2 = (size_t)n_orb * n_orb * 2;
-    // per vector: one double, or n_w complex numbers; the frequencies follow the results
-    const size_t out_per_q = ob.on ? (size_t)ob.m * ob.m * sizeof(double2) : fr.n_w == 0 ? sizeof(double) : (size_t)fr.n_w * sizeof(double2);
+    const size_t e_bytes = (size_t)nk * n_orb * sizeof(double);
+    // the one place that knows the kind: per vector a double, n_w complex numbers or m x m of them; the frequencies follow the results,
+    // the selection the reduced vectors
+    const size_t out_per_q = chi_out_per_q(fr, ob);
     const size_t w_bytes = (size_t)fr.n_w * sizeof(double);
-    std::vector<SpanRecorder> ev((size_t)share.busy());
-    ChiDrain drain;
     for (int i = 0; i < share.busy(); ++i) {
         tbk_model* m = handles[i];
         const int64_t q_lo = share.lo(i), q_n = share.count(i);
-        TBK_CHECK(tbk_eig_check_option(m));
-        TBK_HIP(hipSetDevice(m->device));
-        drain.used.push_back(m);
-        ev[(size_t)i] = SpanRecorder(m->timing, m->stream);
-        TBK_CHECK(m->ws_chi_k.reserve(h_k.size() * sizeof(double)));
-        TBK_CHECK(chi_reserve(m->ws_chi_e, 3 * e_bytes, "the eigenvalues and Fermi tables of the whole mesh"));
-        if (with_u) TBK_CHECK(chi_reserve(m->ws_chi_u, (size_t)nk * nn2 * sizeof(double), "the eigenvectors of the whole mesh"));
-        TBK_CHECK(m->ws_chi_q.reserve((size_t)q_n * (3 * sizeof(int32_t) + out_per_q + (with_d ? n_orb * sizeof(double2) : 0)) + w_bytes + l_bytes + 256));
+        TBK_CHECK(res.stage(m, CHI_FAMILY, 3 * e_bytes, "the eigenvalues and Fermi tables of the whole mesh", with_u));
+        TBK_CHECK(m->ws_mesh_io.reserve((size_t)q_n * (3 * sizeof(int32_t) + out_per_q + (with_d ? n_orb * sizeof(double2) : 0)) + w_bytes + l_bytes + 256));
         // the batch from the memory that is left for the partials, the chunk of the eigenvector walk from what is left then
         size_t free_b = 0, total_b = 0;
         TBK_HIP(hipMemGetInfo(&free_b, &total_b));
-        const size_t room = std::max<size_t>(1, std::min(CHI_PART_BUDGET, std::max(m->ws_chi_part.bytes, free_b / 4)));
+        const size_t room = std::max<size_t>(1, std::min(CHI_PART_BUDGET, std::max(m->ws_mesh_work.bytes, free_b / 4)));
         ChiPlan L;
-        ChiOrbPlan LO;
-        if (ob.on) {
-            TBK_CHECK(chi_orb_plan(dim, mesh, nk, n_orb, ob.m, q_n, room, 0, &LO));
-            TBK_CHECK(m->ws_chi_part.reserve(LO.part_bytes()));
-        } else {
-            TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, q_n, fr.n_w, with_u, room, &L));
-            TBK_CHECK(m->ws_chi_part.reserve(L.part_bytes()));
-        }
-        double* d_k = m->ws_chi_k.as<double>();
-        double* d_E = m->ws_chi_e.as<double>();
-        double* d_U = m->ws_chi_u.as<double>();
-        // ws_chi_q: the results (and the frequencies of a dynamic call), 256-byte aligned behind them the phases, then the reduced vectors
-        double* d_chi = m->ws_chi_q.as<double>();
-        double* d_W = fr.n_w != 0 ? reinterpret_cast<double*>(m->ws_chi_q.as<char>() + (size_t)q_n * out_per_q) : nullptr;
-        char* behind = m->ws_chi_q.as<char>() + dos_align256((size_t)q_n * out_per_q + w_bytes);
+        TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, q_n, fr.n_w, ob.m, with_u, room, 0, &L));
+        TBK_CHECK(m->ws_mesh_work.reserve(L.part_bytes()));
+        double* d_E = m->ws_mesh_e.as<double>();
+        // ws_mesh_io: the results (and the frequencies of a dynamic call), 256-byte aligned behind them the phases, then the reduced
+        // vectors (and the selection of an orbital-resolved call)
+        double* d_chi = m->ws_mesh_io.as<double>();
+        double* d_W = fr.n_w != 0 ? reinterpret_cast<double*>(m->ws_mesh_io.as<char>() + (size_t)q_n * out_per_q) : nullptr;
+        char* behind = m->ws_mesh_io.as<char>() + dos_align256((size_t)q_n * out_per_q + w_bytes);
         double* d_D = with_d ? reinterpret_cast<double*>(behind) : nullptr;
         int32_t* d_Q = reinterpret_cast<int32_t*>(behind + (with_d ? (size_t)q_n * n_orb * sizeof(double2) : 0));
-        int32_t* d_lists = d_Q + (size_t)q_n * 3;  // (the orbital-resolved call's selection, behind the reduced vectors)
-        if (ob.on) TBK_HIP(hipMemcpyAsync(d_lists, h_lists.data(), l_bytes, hipMemcpyHostToDevice, m->stream));
-        TBK_HIP(hipMemcpyAsync(d_k, h_k.data(), h_k.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
+        int32_t* d_lists = d_Q + (size_t)q_n * 3;
+        if (l_bytes) TBK_HIP(hipMemcpyAsync(d_lists, h_lists.data(), l_bytes, hipMemcpyHostToDevice, m->stream));
+        TBK_CHECK(res.upload(m));
         TBK_HIP(hipMemcpyAsync(d_Q, h_Q.data() + q_lo * 3, (size_t)q_n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
         if (d_W) TBK_HIP(hipMemcpyAsync(d_W, fr.omega, w_bytes, hipMemcpyHostToDevice, m->stream));
         if (with_d)
             TBK_HIP(hipMemcpyAsync(d_D, h_D.data() + (size_t)q_lo * n_orb * 2, (size_t)q_n * n_orb * sizeof(double2), hipMemcpyHostToDevice,
                                    m->stream));
-        TBK_CHECK(tbk_chi_fill_eigensystem(m, d_k, h_k.data(), nk, with_u, d_E, d_U));
-        if (ob.on)
-            TBK_CHECK(chi_orb_launch_all(m->stream, LO, &ev[(size_t)i], d_U, d_E, d_E + (size_t)nk * n_orb, d_Q, d_D, d_lists, q_n, mu, T,
-                                         m->ws_chi_part.as<double>(), d_chi));
-        else
-            TBK_CHECK(chi_launch_all(m->stream, L, &ev[(size_t)i], d_U, d_E, d_E + (size_t)nk * n_orb, d_Q, d_D, q_n, mu, T, d_W, fr.eta,
-                                     m->ws_chi_part.as<double>(), d_chi));
+        TBK_CHECK(res.fill(m, with_u));
+        TBK_CHECK(chi_launch_all(m->stream, L, res.ev(), m->ws_mesh_u.as<double>(), d_E, d_E + (size_t)nk * n_orb, d_Q, d_D, d_lists, q_n, mu, T,
+                                 d_W, fr.eta, m->ws_mesh_work.as<double>(), d_chi));
         TBK_HIP(hipMemcpyAsync(reinterpret_cast<char*>(chi_out) + (size_t)q_lo * out_per_q, d_chi, (size_t)q_n * out_per_q, hipMemcpyDeviceToHost,
                                m->stream));
     }
     // synchronises every handle (the eigensolver's flags are reported as by tbk_eigh) and books the kernel times
-    for (tbk_model* m : drain.used) TBK_CHECK(tbk_eigenval_check(m));
-    for (size_t i = 0; i < drain.used.size(); ++i) {
-        tbk_model* m = drain.used[i];
-        TBK_HIP(hipSetDevice(m->device));
-        TBK_HIP(hipStreamSynchronize(m->stream));
-        ev[i].collect(m->timed[TIMED_CHI].ms);
-        m->timed[TIMED_CHI].calls += 1;
-    }
-    return TBK_OK;
+    return res.streams.finish(TIMED_CHI);
 }
 
 extern "C" int tbk_chi_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu, double T,
                                         int64_t n_q, const int64_t* q, const double* phases, double* chi_out) {
-    return chi_from_eigensystem(device, dim, mesh, n_orb, E, U, mu, T, n_q, q, phases, ChiFreq(), 0, chi_out);
+    return chi_from_eigensystem(device, dim, mesh, n_orb, E, U, mu, T, n_q, q, phases, ChiFreq(), ChiOrb(), 0, 0, chi_out);
 }
 
 extern "C" int tbk_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
@@ -1253,22 +1167,16 @@ extern "C" int tbk_chi_dynamic_from_eigensystem(int device, int dim, const int32
                                                 double eta, int64_t part_bytes, double* chi_out) {
     TBK_ARG(part_bytes >= 0, "part_bytes < 0");
     TBK_ARG(n_w >= 1, "n_w < 1");
-    ChiFreq fr;
-    fr.n_w = n_w;
-    fr.omega = omega;
-    fr.eta = eta;
-    return chi_from_eigensystem(device, dim, mesh, n_orb, E, U, mu, T, n_q, q, phases, fr, (size_t)part_bytes, chi_out);
+    return chi_from_eigensystem(device, dim, mesh, n_orb, E, U, mu, T, n_q, q, phases, ChiFreq{n_w, omega, eta}, ChiOrb(), (size_t)part_bytes, 0,
+                                chi_out);
 }
 
 extern "C" int tbk_dynamic_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
                                                 int64_t n_q, const int64_t* q, int64_t n_w, const double* omega, double eta, int matrix_elements,
                                                 int convention, const double* pos, double* mu_out, double* chi_out) {
     TBK_ARG(n_w >= 1, "n_w < 1");
-    ChiFreq fr;
-    fr.n_w = n_w;
-    fr.omega = omega;
-    fr.eta = eta;
-    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, fr, ChiOrb(), matrix_elements, convention, pos, mu_out, chi_out);
+    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, ChiFreq{n_w, omega, eta}, ChiOrb(), matrix_elements, convention, pos,
+                          mu_out, chi_out);
 }
 
 extern "C" int tbk_dynamic_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q,
@@ -1291,7 +1199,7 @@ extern "C" int tbk_chi_timing(tbk_model* m, double* ms, int64_t* calls, int rese
 extern "C" int tbk_chi_orbital_plan(int64_t nk, int n_orb, int m, int64_t n_q, int64_t part_bytes, int64_t k_slice, int64_t* out) {
     TBK_ARG(nk >= 1 && n_orb >= 1 && n_orb <= CHI_MAX_ORB && m >= 1 && m <= n_orb && n_q >= 1 && part_bytes >= 0 && k_slice >= 0 && out != nullptr,
             "nk / n_orb / m / n_q < 1, more than 16320 orbitals, m > n_orb, part_bytes / k_slice < 0 or out is NULL");
-    ChiOrbPlan L;
+    ChiPlan L;
     chi_orb_plan_sizes(nk, n_orb, m, n_q, (size_t)part_bytes, k_slice, &L);
     out[0] = L.bt;
     out[1] = L.blocks;
@@ -1305,55 +1213,16 @@ extern "C" int tbk_chi_orbital_plan(int64_t nk, int n_orb, int m, int64_t n_q, i
 extern "C" int tbk_chi_orbital_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu,
                                                 double T, int64_t n_q, const int64_t* q, const double* phases, int m, const int32_t* orbitals,
                                                 int64_t part_bytes, int64_t k_slice, double* chi_out) {
-    int64_t nk = 0;
-    TBK_CHECK(tetra_check_mesh(dim, mesh, OCC_MESH, &nk));
-    TBK_ARG(E != nullptr, "E is NULL");
-    TBK_ARG(std::isfinite(mu), "the chemical potential is not finite");
-    TBK_CHECK(chi_check(T, n_q, q, chi_out, n_orb));
-    TBK_ARG(U != nullptr, "U is NULL: the orbital-resolved susceptibility needs the eigenvectors");
     TBK_ARG(part_bytes >= 0 && k_slice >= 0, "part_bytes / k_slice < 0");
-    ChiOrb ob;
-    ob.on = true;
-    ob.m = m;
-    ob.orbitals = orbitals;
-    std::vector<int32_t> h_lists;
-    TBK_CHECK(chi_orb_lists(ob, n_orb, &h_lists));
-    TBK_CHECK(tetra_check_device(device));
-    ChiOrbPlan L;
-    TBK_CHECK(chi_orb_plan(dim, mesh, nk, n_orb, m, n_q, (size_t)part_bytes, k_slice, &L));
-    const size_t out_bytes = (size_t)n_q * m * m * sizeof(double2);
-    std::vector<int32_t> h_Q;
-    TBK_CHECK(chi_reduce_q(dim, mesh, n_q, q, &h_Q));
-    const size_t e_bytes = (size_t)nk * n_orb * sizeof(double), u_bytes = (size_t)nk * n_orb * n_orb * sizeof(double2);
-    const size_t d_bytes = (size_t)n_q * n_orb * sizeof(double2), l_bytes = h_lists.size() * sizeof(int32_t);
-    DevBuf d_E, d_U, d_tab, d_Q, d_D, d_lists, d_part, d_chi;
-    TBK_CHECK(d_E.reserve(e_bytes));
-    TBK_CHECK(d_tab.reserve(2 * e_bytes));
-    TBK_CHECK(chi_reserve(d_U, u_bytes, "the eigenvectors of the whole mesh"));
-    TBK_CHECK(d_Q.reserve(h_Q.size() * sizeof(int32_t)));
-    TBK_CHECK(d_lists.reserve(l_bytes));
-    if (phases) TBK_CHECK(d_D.reserve(d_bytes));
-    TBK_CHECK(d_part.reserve(L.part_bytes()));
-    TBK_CHECK(d_chi.reserve(out_bytes));
-    TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
-    TBK_HIP(hipMemcpy(d_U.ptr, U, u_bytes, hipMemcpyHostToDevice));
-    TBK_HIP(hipMemcpy(d_Q.ptr, h_Q.data(), h_Q.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    TBK_HIP(hipMemcpy(d_lists.ptr, h_lists.data(), l_bytes, hipMemcpyHostToDevice));
-    if (phases) TBK_HIP(hipMemcpy(d_D.ptr, phases, d_bytes, hipMemcpyHostToDevice));
-    TBK_CHECK(chi_orb_launch_all(nullptr, L, nullptr, d_U.as<double>(), d_E.as<double>(), d_tab.as<double>(), d_Q.as<int32_t>(),
-                                 phases ? d_D.as<double>() : nullptr, d_lists.as<int32_t>(), n_q, mu, T, d_part.as<double>(), d_chi.as<double>()));
-    TBK_HIP(hipMemcpy(chi_out, d_chi.ptr, out_bytes, hipMemcpyDeviceToHost));
-    return TBK_OK;
+    return chi_from_eigensystem(device, dim, mesh, n_orb, E, U, mu, T, n_q, q, phases, ChiFreq(), ChiOrb{true, m, orbitals}, (size_t)part_bytes,
+                                k_slice, chi_out);
 }
 
 extern "C" int tbk_orbital_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
                                                 int64_t n_q, const int64_t* q, int m, const int32_t* orbitals, int convention, const double* pos,
                                                 double* mu_out, double* chi_out) {
-    ChiOrb ob;
-    ob.on = true;
-    ob.m = m;
-    ob.orbitals = orbitals;
-    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, ChiFreq(), ob, 1, convention, pos, mu_out, chi_out);
+    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, ChiFreq(), ChiOrb{true, m, orbitals}, 1, convention, pos, mu_out,
+                          chi_out);
 }
 
 extern "C" int tbk_orbital_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q,

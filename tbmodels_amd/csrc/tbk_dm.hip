@@ -356,16 +356,6 @@ int dm_check_R(int64_t n_r, const int64_t* R, const double* rho_out, int n_orb) 
     return TBK_OK;
 }
 
-// Waits for what a call has enqueued on its handles' streams when the call ends, however it ends: copies into host buffers that
-// the call owns (or the caller gets back) may be pending when an error of a later slab returns.
-struct DmDrain {
-    std::vector<OccSlab>& slabs;
-    ~DmDrain() {
-        for (OccSlab& s : slabs)
-            if (hipSetDevice(s.m->device) == hipSuccess) (void)hipStreamSynchronize(s.m->stream);
-    }
-};
-
 }  // namespace
 
 extern "C" int tbk_dm_plan(int64_t rows, int n_orb, int64_t n_r, int64_t* out) {
@@ -427,16 +417,17 @@ extern "C" int tbk_density_matrix_multi(tbk_model* const* handles, int n_handles
         TBK_CHECK(tbk_fermi_check_electrons(value, handles[0]->n_orb));
     else
         TBK_ARG(std::isfinite(value), "the energy is not finite");
+    // (the buffers the enqueued copies read and write, in front of the staged call: its MeshStreams waits before they go)
+    std::vector<int32_t> h_Rm;
+    std::vector<std::vector<double>> partial;  // of the slabs behind the first
     OccStaged staged;
     TBK_CHECK(staged.make(handles, n_handles, mesh));
     TBK_CHECK(staged.find_mu(mesh, mode, value, mu_out));
     TBK_CHECK(staged.weights(mu_out[0], nullptr, false));  // (not one of this family's three stages: not timed)
     const int n_orb = staged.n_orb, dim = staged.dim;
     const size_t rho_doubles = (size_t)n_r * n_orb * n_orb * 2;
-    std::vector<int32_t> h_Rm;
     TBK_CHECK(dm_reduce_R(dim, mesh, n_r, R, &h_Rm));
-    std::vector<std::vector<double>> partial(staged.slabs.size());  // of the slabs behind the first
-    DmDrain drain{staged.slabs};  // (declared behind the buffers: it waits before they go)
+    partial.resize(staged.slabs.size());
     for (size_t i = 0; i < staged.slabs.size(); ++i) {
         OccSlab& s = staged.slabs[i];
         tbk_model* m = s.m;
@@ -448,7 +439,7 @@ extern "C" int tbk_density_matrix_multi(tbk_model* const* handles, int n_handles
         TBK_CHECK(m->ws_dm_part.reserve(D.part_bytes()));
         if (D.slices > 1) TBK_CHECK(m->ws_dm_rho.reserve(D.rho_bytes()));
         TBK_CHECK(m->ws_dm_r.reserve(h_Rm.size() * sizeof(int32_t)));
-        const int64_t chunk = dm_cap_chunk(D, OccStaged::chunk_of(m, nk, 2));
+        const int64_t chunk = dm_cap_chunk(D, mesh_eigh_chunk(m, nk, 2));
         const size_t u_doubles = (size_t)chunk * n_orb * n_orb * 2;
         TBK_CHECK(m->ws_pdos_u.reserve((u_doubles + (size_t)chunk * n_orb) * sizeof(double)));
         TBK_CHECK(m->ws_dm_tab.reserve(D.tab_bytes(chunk)));
@@ -462,11 +453,11 @@ extern "C" int tbk_density_matrix_multi(tbk_model* const* handles, int n_handles
             const int64_t nkc = std::min(chunk, nk - c0);
             // (the chunk's eigenvalues are not used: the weights come from the eigenvalue path)
             TBK_CHECK(tbk_eigh_device(m, d_k_own + c0 * dim, nkc, 2, nullptr, d_U + u_doubles, d_U));
-            TBK_CHECK(dm_launch_chunk(m->stream, D, &s.ev, m->ws_dm_r.as<int32_t>(), d_U, d_w + (size_t)c0 * n_orb, c0, nkc,
+            TBK_CHECK(dm_launch_chunk(m->stream, D, s.ev, m->ws_dm_r.as<int32_t>(), d_U, d_w + (size_t)c0 * n_orb, c0, nkc,
                                       m->ws_dm_tab.as<double>(), m->ws_dm_p.as<double2>(), m->ws_dm_part.as<double2>()));
         }
         const double2* d_result = nullptr;
-        TBK_CHECK(dm_launch_reduce(m->stream, D, &s.ev, m->ws_dm_part.as<double2>(), m->ws_dm_rho.as<double2>(), &d_result));
+        TBK_CHECK(dm_launch_reduce(m->stream, D, s.ev, m->ws_dm_part.as<double2>(), m->ws_dm_rho.as<double2>(), &d_result));
         double* h_dst = rho_out;
         if (i > 0) {
             try {
@@ -480,14 +471,7 @@ extern "C" int tbk_density_matrix_multi(tbk_model* const* handles, int n_handles
         TBK_HIP(hipMemcpyAsync(h_dst, d_result, D.rho_bytes(), hipMemcpyDeviceToHost, m->stream));
     }
     // synchronises every handle (the eigenvector flags are reported as by tbk_eigh) and books the kernel times
-    for (OccSlab& s : staged.slabs) TBK_CHECK(tbk_eigenval_check(s.m));
-    for (size_t i = 0; i < staged.slabs.size(); ++i) {
-        tbk_model* m = staged.slabs[i].m;
-        TBK_HIP(hipSetDevice(m->device));
-        TBK_HIP(hipStreamSynchronize(m->stream));
-        staged.slabs[i].ev.collect(m->timed[TIMED_DM].ms);
-        m->timed[TIMED_DM].calls += 1;
-    }
+    TBK_CHECK(staged.finish(TIMED_DM));
     for (size_t i = 1; i < staged.slabs.size(); ++i)  // in handle order
         for (size_t x = 0; x < rho_doubles; ++x) rho_out[x] += partial[i][x];
     return TBK_OK;

@@ -343,13 +343,18 @@ struct tbk_model {
     DevBuf ws_dm_p;      // ... the projectors of one k chunk, [table columns][n_orb][n_orb] complex
     DevBuf ws_dm_part;   // ... the k slices' partial rho [slices][n_r padded to 16][n_orb][n_orb] complex, resident across the chunks
     DevBuf ws_dm_rho;    // ... their sum [n_r][n_orb][n_orb] complex (more than one slice)
-    DevBuf ws_chi_k;     // tbk_susceptibility (tbk_chi.hip): the k list of the whole mesh [NK][dim]
-    DevBuf ws_chi_e;     // ... the resident eigenvalues of the whole mesh [NK][n_orb], behind them the Fermi tables f, 1 - f [2][NK][n_orb]
-    DevBuf ws_chi_u;     // ... the resident eigenvectors of the whole mesh [NK][n_orb][n_orb] complex (with matrix elements)
-    DevBuf ws_chi_q;     // ... this handle's vectors: chi [n_q], 256-byte aligned the phases D [n_q][n_orb] complex (convention 1), the reduced q int32 [n_q][3]
-    DevBuf ws_chi_part;  // ... the partial sums of one batch of vectors [batch][NK][blocks]
-                         // (tbk_berry_flux, tbk_berry.hip, keeps its resident eigenvectors in the same k / e / u; q: its links, words,
-                         // |L| and phases; part: the plaquette kernel's outputs, the gathered words, the library path's batch)
+    // The calls on the resident eigensystem of a whole mesh (tbk_resident.h; the susceptibilities of tbk_chi.hip, tbk_berry_flux of
+    // tbk_berry.hip): k, E and U are ResidentMesh's, the other two each family lays out for itself
+    DevBuf ws_mesh_k;     // the k list of the whole mesh [NK][dim]
+    DevBuf ws_mesh_e;     // the eigenvalues of the whole mesh [NK][n_orb]; chi: behind them the Fermi tables f, 1 - f [2][NK][n_orb]
+    DevBuf ws_mesh_u;     // the eigenvectors of the whole mesh [NK][n_orb][n_orb] complex (chi: with matrix elements; berry: always)
+    DevBuf ws_mesh_io;    // the call's arguments and results on this handle.  chi: the results of its vectors (double [n_q], complex
+                          // [n_q][n_w] or [n_q][m][m]) and the frequencies [n_w], 256-byte aligned behind them the phases D [n_q][n_orb]
+                          // complex (convention 1), the reduced q int32 [n_q][3], the orbital selection int32 [2][m].  berry: the links
+                          // L [sets][dim][k share] complex, their words (u64) and |L|, each 256-byte aligned, then the phases D [dim][n_orb]
+    DevBuf ws_mesh_work;  // the call's partials or workspace.  chi: the partial sums of one batch of vectors, [batch][NK][blocks],
+                          // complex [batch][w_pass][NK][blocks] or [batch][slices][mp][mp].  berry: (handle 0) the plaquette kernel's
+                          // outputs and, with several handles, the words and |L| of the whole mesh; behind them the library path's batch
     std::vector<EventSpan> events;  // StageTimer's spans, read by tbk_get_timing (no synchronisation on the pipeline's path)
     double t_ms[TBK_T_COUNT] = {0, 0, 0, 0};
     int64_t t_n[TBK_T_COUNT] = {0, 0, 0, 0};

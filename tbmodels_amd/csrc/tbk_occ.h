@@ -1,12 +1,13 @@
 // tbk_occ.h -- what the calls that integrate with the point weights w[k][b] of a mesh share: tbk_occ.hip (weights, occupations) and
 // tbk_dm.hip (the real-space density matrix).  The plan of one slab, the launchers of tbk_occ.hip's kernels, and the staged call:
-// the handles with their slabs, the slabs' eigenvalues, mu and the weights, in that order.  The kernels are in tbk_occ.hip.
+// the handles with their slabs, the slabs' eigenvalues, mu and the weights, in that order.  The kernels are in tbk_occ.hip; the
+// check of every handle, the finish and the wait on every exit are MeshStreams' (tbk_resident.h).
 #pragma once
 
 #include <algorithm>
 #include <vector>
 
-#include "tbk_tetra.h"
+#include "tbk_resident.h"
 
 struct OccGeom {
     int n0_own;     // planes of axis 0 this launch writes weights for
@@ -40,13 +41,6 @@ int occ_clear_buf(hipStream_t s, const OccPlan& L, char* ws);
 int occ_launch_contract(hipStream_t s, const OccPlan& L, const double* d_U, const double* d_w, int64_t c0, int64_t nkc, double nk_total, char* ws);
 int occ_launch_reduce(hipStream_t s, const OccPlan& L, char* ws);
 
-// ---- what the calls on the resident eigensystem of a whole mesh share (tbk_chi.hip; tbk_berry.hip calls them too) ------------------
-// The eigensystem of the nk mesh points d_k (h_k: the same list on the host) on a handle whose device is current, enqueued on its
-// stream: with_u, tbk_eigh_device chunk by chunk (its own E, so that E and U belong together), else the eigenvalue path alone.
-int tbk_chi_fill_eigensystem(tbk_model* m, const double* d_k, const double* h_k, int64_t nk, bool with_u, double* d_E, double* d_U);
-// D[n_q][n_orb] (re, im) of convention 1: exp(-2 pi i sum_d q_d pos[i][d] / n_d), the unreduced q_d
-int tbk_chi_phase_table(int dim, const int32_t* mesh, int n_orb, int64_t n_q, const int64_t* q, const double* pos, std::vector<double>* out);
-
 inline constexpr const char* OCC_MESH ="the tetrahedron weights need a 2- or 3-dimensional mesh";
 
 // ---- the mesh on staged handles ------------------------------------------------------------------------------------------------
@@ -58,7 +52,9 @@ struct OccSlab {
     const double* d_E = nullptr;  // planes planes
     std::vector<double> h_k;
     std::vector<double> host;  // the off_host block
-    SpanRecorder ev;  // stages: 0 the weights kernel, 1 the band sums, 2 the contraction + its reduction (tbk_dm.hip: its own three)
+    // the handle's recorder in OccStaged::streams.  Stages: 0 the weights kernel, 1 the band sums, 2 the contraction + its reduction
+    // (tbk_dm.hip: its own three)
+    SpanRecorder* ev = nullptr;
 };
 
 // Handle i takes the slab of tbk_dos_multi.  Its eigenvalues: the planes [p_lo, p_lo + p_count] come from ONE call of the
@@ -66,6 +62,7 @@ struct OccSlab {
 // p_lo - 1 from a second call, in front of them in ws_out.  A handle that holds the whole axis needs neither neighbour.
 struct OccStaged : TetraHandles {
     std::vector<OccSlab> slabs;
+    MeshStreams streams;  // (behind the slabs: it waits before their host buffers go)
 
     // the handles and the mesh, checked and locked; then the eigenvalues of every slab, checked
     int make(tbk_model* const* handles, int n_handles, const int32_t* mesh) {
@@ -83,19 +80,16 @@ struct OccStaged : TetraHandles {
             s.off0 = p_count == n0 ? 0 : 1;
             const int64_t main_planes = p_count == n0 ? n0 : p_count + 1;
             s.planes = main_planes + s.off0;
-            TBK_CHECK(tbk_eig_check_option(m));
-            TBK_HIP(hipSetDevice(m->device));
+            TBK_CHECK(streams.add(m));
+            s.ev = &streams.used.back().ev;
             TBK_CHECK(occ_plan(dim, mesh, p_count, s.planes, s.off0, n_orb, &s.L));
             TBK_CHECK(m->ws_occ_w.reserve((size_t)s.L.rows * n_orb * sizeof(double)));
             TBK_CHECK(m->ws_occ.reserve(s.L.ws_bytes));
             // the neighbour plane below in front of the main planes
             TBK_CHECK(tbk_mesh_eigenvalues(m, mesh, p_lo, main_planes, s.off0 != 0, &s.h_k));
             s.d_E = m->ws_out.as<double>();
-            s.ev = SpanRecorder(m->timing, m->stream);
         }
-        // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigenval: the first failing slab's
-        for (OccSlab& s : slabs) TBK_CHECK(tbk_eigenval_check(s.m));
-        return TBK_OK;
+        return streams.check();
     }
 
     // mode 1: the Fermi search of tbk_fermi on the resident eigenvalues; mode 0: N(value) from the probe kernel
@@ -106,24 +100,18 @@ struct OccStaged : TetraHandles {
         return tbk_fermi_resident(f.data(), (int)f.size(), dim, mesh, n_orb, mode, value, mu_out);
     }
 
-    // timed: the kernel is booked on stage 0 of s.ev (not for a caller whose stages are others)
+    // timed: the kernel is booked on stage 0 of the slab's recorder (not for a caller whose stages are others)
     int weights(double mu, double* w_out, bool timed = true) {
         for (OccSlab& s : slabs) {
             TBK_HIP(hipSetDevice(s.m->device));
-            if (timed) s.ev.start(0);
+            if (timed) s.ev->start(0);
             TBK_CHECK(occ_launch_weights(s.m->stream, s.L, s.d_E, mu, (double)nk_total, s.m->ws_occ_w.as<double>()));
-            if (timed) s.ev.stop();
+            if (timed) s.ev->stop();
             if (w_out)
                 TBK_HIP(hipMemcpyAsync(w_out + (size_t)s.p_lo * plane_pts * n_orb, s.m->ws_occ_w.ptr, (size_t)s.L.rows * n_orb * sizeof(double),
                                        hipMemcpyDeviceToHost, s.m->stream));
         }
         return TBK_OK;
-    }
-
-    // k-points per chunk of a slab's eigenvector walk: TBK_OPT_K_CHUNK as given, else what the eigenvector call itself would take
-    // from the free memory, over `share` (the buffers a caller keeps beside the chunk's eigenvectors)
-    static int64_t chunk_of(tbk_model* m, int64_t nk, int share = 1) {
-        return std::max<int64_t>(1, std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : choose_chunk(m, nk, true) / share));
     }
 
     // f, eb and q of every slab (the weights are in ws_occ_w), left in s.host
@@ -134,13 +122,13 @@ struct OccStaged : TetraHandles {
             char* ws = m->ws_occ.as<char>();
             const double* d_w = m->ws_occ_w.as<double>();
             const double* d_E_own = s.d_E + (size_t)s.off0 * plane_pts * n_orb;
-            s.ev.start(1);
+            s.ev->start(1);
             TBK_CHECK(occ_launch_band(m->stream, s.L, d_w, d_E_own, (double)nk_total, ws));
-            s.ev.stop();
+            s.ev->stop();
             TBK_CHECK(occ_clear_buf(m->stream, s.L, ws));
             // the chunk's eigenvalues (not used: the weights come from the eigenvalue path) go behind its eigenvectors
             const int64_t nk = s.L.rows;
-            const int64_t chunk = chunk_of(m, nk);
+            const int64_t chunk = mesh_eigh_chunk(m, nk);
             const size_t u_doubles = (size_t)chunk * n_orb * n_orb * 2;
             TBK_CHECK(m->ws_pdos_u.reserve((u_doubles + (size_t)chunk * n_orb) * sizeof(double)));
             double* d_U = m->ws_pdos_u.as<double>();
@@ -148,13 +136,13 @@ struct OccStaged : TetraHandles {
             for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
                 const int64_t nkc = std::min(chunk, nk - c0);
                 TBK_CHECK(tbk_eigh_device(m, d_k_own + c0 * dim, nkc, 2, nullptr, d_U + u_doubles, d_U));
-                s.ev.start(2);
+                s.ev->start(2);
                 TBK_CHECK(occ_launch_contract(m->stream, s.L, d_U, d_w, c0, nkc, (double)nk_total, ws));
-                s.ev.stop();
+                s.ev->stop();
             }
-            s.ev.start(2);
+            s.ev->start(2);
             TBK_CHECK(occ_launch_reduce(m->stream, s.L, ws));
-            s.ev.stop();
+            s.ev->stop();
             try {
                 s.host.resize(5 * (size_t)n_orb);
             } catch (...) {
@@ -167,14 +155,5 @@ struct OccStaged : TetraHandles {
     }
 
     // synchronises every handle (the eigenvector flags are reported as by tbk_eigh) and books the kernel times
-    int finish() {
-        for (OccSlab& s : slabs) TBK_CHECK(tbk_eigenval_check(s.m));
-        for (OccSlab& s : slabs) {
-            TBK_HIP(hipSetDevice(s.m->device));
-            TBK_HIP(hipStreamSynchronize(s.m->stream));
-            s.ev.collect(s.m->timed[TIMED_OCC].ms);
-            s.m->timed[TIMED_OCC].calls += 1;
-        }
-        return TBK_OK;
-    }
+    int finish(TimedFamily family = TIMED_OCC) { return streams.finish(family); }
 };
