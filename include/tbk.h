@@ -407,6 +407,42 @@ int tbk_dm_plan(int64_t rows, int n_orb, int64_t n_r, int64_t* out);
  * weights kernel, a stage of tbk_occ_timing, is not timed in these calls.) */
 int tbk_dm_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
+/* ---- the lattice Green's function (the resolvent) of a uniform k mesh at complex energies (not in the reference) -----------------
+ * Mesh and mesh points k = (i_1 / n_1, ..., i_dim / n_dim) are those of tbk_occupations (dim 2 or 3), E and U those of
+ * tbk_eigh_device with convention 2, the phase is the integer-reduced one of tbk_density_matrix (R + n_d e_d gives the bits of R):
+ *
+ *     G(R, z)[i][j] = sum_k exp(-2 pi i k . R) sum_b (1 / (z - E[k][b]) / NK) U[k][i][b] conj(U[k][j][b])
+ *
+ * z: double [n_z][2] (re, im), 1 <= n_z <= 4096, every component finite and every Im z != 0 (either sign), else TBK_ERR_ARGUMENT
+ * before any device is touched.  R: int64 [n_r][dim], n_r as for tbk_density_matrix.  G_out: double [n_r][n_z][n_orb][n_orb][2].
+ * Per chunk of k-points the phase table is made once; per tile of at most 4 energies one projector launch (the eigenvectors of a
+ * block go through LDS once per tile) and one Fourier contraction into partial sums that stay resident across the chunks.  For a
+ * given eigensystem, chunk size and slab the bits of G(R, z) depend on (R, z) alone: not on the other energies, their order or
+ * the tile.  Error for a given eigensystem: 4 (NK n_orb + 32) 2^-53 / min |Im z| per component. */
+
+/* The kernels alone on an eigensystem the caller brings (E [NK][n_orb], U [NK][n_orb][n_orb][2]).  k_chunk, z_tile: 0 means
+ * tbk_green_plan's; a z_tile above 4 is 4. */
+int tbk_green_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, int64_t k_chunk,
+                               int64_t z_tile, int64_t n_z, const double* z, int64_t n_r, const int64_t* R, double* G_out);
+/* The whole call: the partial sums and G are reserved and cleared, then the k list is walked in chunks of at most TBK_OPT_K_CHUNK
+ * points (0: chosen from the memory left, shared between the chunk's eigenvectors and the projectors of one tile), per chunk
+ * tbk_eigh_device, the phase table and, per energy tile, projectors and contraction.  TBK_ERR_MEMORY when G, its partials (about
+ * slices x n_r x n_z x n_orb^2 complex numbers) or one chunk do not fit. */
+int tbk_green_function(tbk_model* m, const int32_t* mesh, int64_t n_z, const double* z, int64_t n_r, const int64_t* R, double* G_out);
+/* On several devices from one process: the slabs of tbk_dos_multi, added by the host in handle order.  The handles must be distinct. */
+int tbk_green_function_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int64_t n_z, const double* z, int64_t n_r,
+                             const int64_t* R, double* G_out);
+/* How a slab of `rows` mesh points is worked: out[0 .. 2] = tbk_dm_plan(rows, n_orb, n_r) (the k slices do not depend on the
+ * energies), out[3] = energies per tile (z_tile, 0: 4; at most n_z, and at most what keeps the projectors of one chunk of k_chunk
+ * points inside 1 GiB), out[4] = tiles, out[5] = k-points per chunk (k_chunk, 0: rows, capped so that the projectors of one tile
+ * stay inside 1 GiB; never more than the phase table's budget allows), out[6] = the projector template: 1 (n_orb <= 16: 16 x 16
+ * blocks of four k-points) or 4 (64 x 64 blocks).  A function of its arguments alone. */
+int tbk_green_plan(int64_t rows, int n_orb, int64_t n_r, int64_t n_z, int64_t z_tile, int64_t k_chunk, int64_t* out);
+/* ms[3] = the summed HIP-event time of the phase tables, the projectors, and the contractions + the sums of their slices in this
+ * handle's calls made while TBK_OPT_TIMING was on; calls = how many calls; reset = 1 clears.  (The eigensolver stages are in
+ * tbk_get_timing.) */
+int tbk_green_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
 /* ---- the bare (Lindhard) static susceptibility of a uniform k mesh (not in the reference) ----------------------------------------
  * Mesh and mesh points k = (i_1 / n_1, ..., i_dim / n_dim) are those of tbk_occupations (dim 2 or 3); k+q is the mesh point with the
  * indices (i_d + q_d) mod n_d.  With E, U the eigenvalues and eigenvectors of tbk_eigh (convention 2), T = k_B T > 0 in the model's

@@ -98,6 +98,11 @@ SIGNATURES = {
     "tbk_density_matrix_multi": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, _c_i64, _vp, _vp, _vp]),
     "tbk_dm_plan": (_c_int, [_c_i64, _c_int, _c_i64, ctypes.POINTER(_c_i64)]),
     "tbk_dm_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
+    "tbk_green_from_eigensystem": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, _vp, _c_i64, _c_i64, _c_i64, _vp, _c_i64, _vp, _vp]),
+    "tbk_green_function": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _vp, _vp]),
+    "tbk_green_function_multi": (_c_int, [_vp, _c_int, _vp, _c_i64, _vp, _c_i64, _vp, _vp]),
+    "tbk_green_plan": (_c_int, [_c_i64, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(_c_i64)]),
+    "tbk_green_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
     "tbk_chi_from_eigensystem": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, _vp, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _vp, _vp]),
     "tbk_susceptibility": (_c_int, [_vp, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _c_int, _c_int, _vp, _vp, _vp]),
     "tbk_susceptibility_multi": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _c_int, _c_int, _vp, _vp, _vp]),

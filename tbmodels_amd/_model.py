@@ -44,6 +44,7 @@ BandEdges = co.namedtuple("BandEdges", ("emin", "emax"))
 FermiLevel = co.namedtuple("FermiLevel", ("mu", "lower", "upper", "nos"))
 Occupations = co.namedtuple("Occupations", ("mu", "orbital_occ", "band_occ", "band_energy"))
 DensityMatrix = co.namedtuple("DensityMatrix", ("mu", "R", "rho"))
+GreenFunction = co.namedtuple("GreenFunction", ("z", "R", "G"))
 Susceptibility = co.namedtuple("Susceptibility", ("mu", "q", "chi"))
 DynamicSusceptibility = co.namedtuple("DynamicSusceptibility", ("mu", "q", "omega", "chi"))
 OrbitalSusceptibility = co.namedtuple("OrbitalSusceptibility", ("mu", "q", "orbitals", "chi"))
@@ -789,7 +790,7 @@ class Model:
         return (eig[0], vec[0]) if single else (eig, vec)
 
     def _mesh_argument(self, mesh, what="dos"):
-        """The mesh check ``dos``, ``pdos``, ``band_edges``, ``fermi_level``, ``tetra_weights``, ``occupations``, ``density_matrix``, ``susceptibility``, ``dynamic_susceptibility`` and ``berry_flux`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
+        """The mesh check ``dos``, ``pdos``, ``band_edges``, ``fermi_level``, ``tetra_weights``, ``occupations``, ``density_matrix``, ``green_function``, ``susceptibility``, ``dynamic_susceptibility`` and ``berry_flux`` share: ``mesh int32 (dim,)`` or ``ValueError``."""
         if self.dim not in (2, 3):
             raise ValueError("{} needs a 2- or 3-dimensional model, this one has dimension {}".format(what, self.dim))
         try:
@@ -1107,6 +1108,78 @@ class Model:
                                                     _lib.ptr(vectors), _lib.ptr(mu), _lib.ptr(rho))
             )
         return DensityMatrix(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, rho)
+
+    @staticmethod
+    def _complex_energies_argument(z):
+        """``z complex128 (NZ,)`` from a complex number or a sequence of 1 to 4096 of them, every one finite with ``Im z != 0``."""
+        if z is None or isinstance(z, (str, bytes)):
+            raise ValueError("z must be a complex number or a sequence of them, got {!r}".format(z))
+        try:
+            array = np.asarray(z)
+            if array.dtype.kind not in "iufc":
+                raise TypeError
+            array = array.astype(np.complex128)
+        except (TypeError, ValueError):
+            raise ValueError("z must be a complex number or a sequence of them") from None
+        if array.ndim == 0:
+            array = array.reshape(1)
+        if array.ndim != 1 or not 1 <= array.shape[0] <= 4096:
+            raise ValueError("z must be one energy or a sequence of 1 to 4096, got shape {}".format(array.shape))
+        if not (np.all(np.isfinite(array.real)) and np.all(np.isfinite(array.imag))):
+            raise ValueError("z must be finite")
+        if np.any(array.imag == 0.0):
+            raise ValueError("every z needs Im z != 0: the resolvent is evaluated off the real axis only")
+        return np.ascontiguousarray(array)
+
+    def green_function(self, mesh, z, *, R=None):
+        """
+        The lattice Green's function (the resolvent) ``G(R, z)`` of a uniform k mesh at complex energies, computed on the GPU from
+        eigenvalues and eigenvectors that never leave it.  Not in the reference.
+
+        ``mesh`` is that of :meth:`occupations`.  ``z`` is a complex number or a sequence of 1 to 4096 of them, every one finite
+        with ``Im z != 0`` of either sign (retarded, advanced, Matsubara or contour points), else ``ValueError``.  ``R`` is an
+        integer array-like of shape ``(NR, dim)`` or one vector; duplicates are allowed; ``None`` means the model's stored hopping
+        vectors in the order of ``self.hop``.  Returns the named tuple ``(z, R, G)``: ``z`` as ``complex128 (NZ,)``, ``R`` as
+        ``int64 (NR, dim)`` and ``G`` as ``complex128 (NR, NZ, size, size)``.
+
+        Definition.  With ``E, U`` of ``eigh(k, convention=2)`` at the mesh points ``k = (i_1 / n_1, ..., i_dim / n_dim)``::
+
+            P(k, z)[i, j] = sum_b (1 / (z - E[k, b])) U[k, i, b] conj(U[k, j, b]) / NK
+            G(R, z)[i, j] = sum_k exp(-2 pi i k . R) P(k, z)[i, j]
+
+        that is ``(1 / NK) sum_k exp(-2 pi i k . R) (z - H(k))^-1``.  The sign is that of :meth:`density_matrix`, the inverse of
+        ``hamilton``, and ``k . R`` is reduced in integers before any floating-point operation, so ``G(R + n_d e_d, z)`` has the
+        bits of ``G(R, z)``.  ``R`` is a lattice vector: convention 2 only.  No spin factor.
+
+        Properties.  (1) ``G(R, conj(z)) = G(-R, z)^H``.  (2) ``-Im tr G(0, w + i eta) / pi`` is the Lorentzian-broadened density
+        of states ``(1 / NK) sum_{k, b} (eta / pi) / ((w - E[k, b])^2 + eta^2)``, its diagonal the orbital-resolved one.  (3) Over
+        the dual cell of the mesh ``G`` solves the Dyson equation of the hoppings folded onto the mesh torus,
+        ``sum_R' (z delta(R') - H(R')) G(R - R', z) = delta(R)``.  (4) ``z G(R, z)`` tends to the identity for ``R = 0`` modulo
+        the mesh and to 0 otherwise as ``|z|`` grows.  (5) The bits of ``G(R, z)`` do not depend on the other entries of ``z`` and
+        ``R``, on their order or number; a duplicate has the bits of its original and a second call the bits of the first.
+
+        Error bound for a given eigensystem, with ``eta = min |Im z|``: every element is a sum of ``NK size`` terms whose moduli
+        add up to at most ``1 / eta``, so the rounding error is at most ``4 (NK size + 32) 2^-53 / eta`` per component.  Against
+        the exact resolvent the computed eigensystem adds ``(||U U^H - 1|| + ||H U - U E|| ||U|| / eta) / eta``.
+
+        Work: ``8 size^3`` flops per mesh point and energy for the projectors and ``8 NR size^2`` for the transform, both on the
+        FP64 matrix pipe, beside one eigensolve per mesh point whatever ``NZ``.  ``G`` and its partial sums (``NR NZ size^2``
+        complex numbers, times the k slices of the transform) stay in device memory, else ``MemoryError``.  One-dimensional models
+        raise ``ValueError``.  With several ``devices`` every device contracts a slab of the mesh along its first axis and the host
+        adds the slabs.
+        """
+        mesh_array = self._mesh_argument(mesh, "green_function")
+        energies = self._complex_energies_argument(z)
+        vectors = self._lattice_vectors_argument(R)
+        G = np.empty((vectors.shape[0], energies.shape[0], self.size, self.size), dtype=np.complex128)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_green_function_multi(handles, n_handles, _lib.ptr(mesh_array), energies.shape[0], _lib.ptr(energies),
+                                                    vectors.shape[0], _lib.ptr(vectors), _lib.ptr(G))
+            )
+        return GreenFunction(energies, vectors, G)
 
     def susceptibility(self, mesh, q, *, temperature, energy=None, n_electrons=None, matrix_elements=True, convention=2):
         """

@@ -31,6 +31,9 @@
 //                      slab's points are cut into `slices` ranges of kps points -- a function of the slab index, not of the chunk,
 //                      as in occ_contract_kernel -- one partial rho each, and dm_reduce_kernel adds them in index order.
 //
+// The plan, the launchers of dm_phase_kernel, dm_fourier_kernel and dm_reduce_kernel and the checks of R are declared in tbk_dm.h:
+// tbk_green.hip runs the same three kernels behind its own projector.
+//
 // For given (w, U), R, chunk size and slab the bits of rho depend on nothing else.  Another chunk size regroups the k-points of the
 // groups at the chunk boundaries: results differ within the rounding bound of DESIGN 14.
 
@@ -39,41 +42,13 @@
 #include <cstring>
 #include <vector>
 
-#include "tbk_occ.h"
+#include "tbk_dm.h"
 
 namespace {
+constexpr int64_t DM_TARGET_WAVES = 1024;  // Fourier tiles x slices the plan aims for (four waves on each of 256 CUs)
+constexpr int64_t DM_MIN_SLICE = 16;       // mesh points per slice, at least
+}  // namespace
 
-typedef double dm_d4 __attribute__((ext_vector_type(4)));
-
-constexpr int DM_THREADS = 256;
-constexpr int64_t DM_TARGET_WAVES = 1024;             // Fourier tiles x slices the plan aims for (four waves on each of 256 CUs)
-constexpr int64_t DM_MIN_SLICE = 16;                  // mesh points per slice, at least
-constexpr size_t DM_PART_BUDGET = size_t(256) << 20;  // the partials of all slices together; fewer slices beyond it
-constexpr size_t DM_TAB_BUDGET = size_t(256) << 20;   // the phase table of one chunk; a shorter chunk beyond it
-constexpr int64_t DM_MAX_R = int64_t(65535) * 16;     // one grid row per 16 R-vectors
-
-struct DmMesh {
-    int dim;
-    int n[3];       // (n[2] = 1 in two dimensions)
-    int64_t nk;     // points of the whole mesh
-    int64_t first;  // mesh index of the slab's first own point
-};
-
-struct DmPlan {
-    DmMesh mesh;
-    int n = 0;                       // orbitals
-    int64_t n2 = 0, nct = 0;         // elements of one matrix, column tiles of 16 of them
-    int64_t n_r = 0, nr_pad = 0;     // R-vectors, rounded up to the tile
-    int64_t rows = 0;                // own mesh points of the slab
-    int64_t slices = 1, kps = 4;     // k slices of the Fourier kernel, mesh points per slice (a multiple of 4)
-    size_t part_bytes() const { return (size_t)slices * nr_pad * n2 * sizeof(double2); }
-    size_t rho_bytes() const { return (size_t)n_r * n2 * sizeof(double2); }
-    int64_t groups(int64_t chunk) const { return chunk / 4 + 2; }  // table groups of a chunk, at most
-    size_t tab_bytes(int64_t chunk) const { return (size_t)nr_pad * groups(chunk) * 4 * 2 * sizeof(double); }
-    size_t p_bytes(int64_t chunk) const { return (size_t)groups(chunk) * 4 * n2 * sizeof(double2); }
-};
-
-// the slices: enough of them to fill the device with tiles, none shorter than DM_MIN_SLICE points, all partials inside the budget
 void dm_plan_slices(int64_t rows, int n_orb, int64_t n_r, int64_t* nr_pad, int64_t* slices, int64_t* kps) {
     const int64_t n2 = (int64_t)n_orb * n_orb;
     *nr_pad = (n_r + 15) / 16 * 16;
@@ -85,6 +60,10 @@ void dm_plan_slices(int64_t rows, int n_orb, int64_t n_r, int64_t* nr_pad, int64
     *kps = ((rows + want - 1) / want + 3) / 4 * 4;
     *slices = std::max<int64_t>(1, (rows + *kps - 1) / *kps);
 }
+
+namespace {
+
+typedef double dm_d4 __attribute__((ext_vector_type(4)));
 
 __global__ void __launch_bounds__(DM_THREADS) dm_phase_kernel(const int32_t* __restrict__ Rm, DmMesh g, int64_t n_r, int64_t nr_pad, int64_t c0,
                                                               int64_t nkc, int64_t ng, double* __restrict__ tab) {
@@ -264,6 +243,8 @@ __global__ void __launch_bounds__(DM_THREADS) dm_reduce_kernel(const double2* __
     rho[idx] = acc;
 }
 
+}  // namespace
+
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 int dm_plan(int dim, const int32_t* mesh, int64_t nk_total, int64_t first_pt, int64_t rows, int n_orb, int64_t n_r, DmPlan* out) {
     DmPlan L;
@@ -305,16 +286,36 @@ int64_t dm_cap_chunk(const DmPlan& L, int64_t chunk) {
     return std::max<int64_t>(1, std::min(chunk, std::max<int64_t>(4, by_tab - 8)));
 }
 
-// The slab's points [c0, c0 + nkc): d_U their eigenvectors, d_w_chunk their rows of w.  ev (may be NULL): stages 0, 1, 2
-int dm_launch_chunk(hipStream_t s, const DmPlan& L, SpanRecorder* ev, const int32_t* d_Rm, const double* d_U, const double* d_w_chunk, int64_t c0,
-                    int64_t nkc, double* d_tab, double2* d_P, double2* d_part) {
-    const int64_t pad = c0 & 3, g0 = c0 >> 2, ng = (pad + nkc + 3) / 4, g_end = g0 + ng, gps = L.kps / 4;
+int dm_launch_phase(hipStream_t s, const DmPlan& L, SpanRecorder* ev, const int32_t* d_Rm, int64_t c0, int64_t nkc, double* d_tab) {
+    const int64_t pad = c0 & 3, ng = (pad + nkc + 3) / 4;
     const int64_t tab_threads = L.nr_pad / 16 * ng * 64;
     if (ev) ev->start(0);
     hipLaunchKernelGGL(dm_phase_kernel, dim3((unsigned)((tab_threads + DM_THREADS - 1) / DM_THREADS)), dim3(DM_THREADS), 0, s, d_Rm, L.mesh, L.n_r,
                        L.nr_pad, c0, nkc, ng, d_tab);
     if (ev) ev->stop();
     TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+int dm_launch_fourier(hipStream_t s, const DmPlan& L, SpanRecorder* ev, int64_t c0, int64_t nkc, const double* d_tab, const double2* d_P,
+                      double2* d_part) {
+    const int64_t pad = c0 & 3, g0 = c0 >> 2, ng = (pad + nkc + 3) / 4, g_end = g0 + ng, gps = L.kps / 4;
+    const int64_t slice_lo = g0 / gps, slice_hi = (g_end - 1) / gps;
+    if (ev) ev->start(2);
+    hipLaunchKernelGGL(dm_fourier_kernel, dim3((unsigned)((L.nct + 3) / 4), (unsigned)(L.nr_pad / 16), (unsigned)(slice_hi - slice_lo + 1)),
+                       dim3(DM_THREADS), 0, s, d_tab, d_P, L.n2, L.nct, L.nr_pad, ng, g0, g_end, gps, slice_lo, d_part);
+    if (ev) ev->stop();
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+namespace {
+
+// The slab's points [c0, c0 + nkc): d_U their eigenvectors, d_w_chunk their rows of w.  ev (may be NULL): stages 0, 1, 2
+int dm_launch_chunk(hipStream_t s, const DmPlan& L, SpanRecorder* ev, const int32_t* d_Rm, const double* d_U, const double* d_w_chunk, int64_t c0,
+                    int64_t nkc, double* d_tab, double2* d_P, double2* d_part) {
+    const int64_t pad = c0 & 3, ng = (pad + nkc + 3) / 4;
+    TBK_CHECK(dm_launch_phase(s, L, ev, d_Rm, c0, nkc, d_tab));
     if (ev) ev->start(1);
     if (L.n <= 16) {
         hipLaunchKernelGGL(dm_project_kernel<1>, dim3((unsigned)ng, 1), dim3(DM_THREADS), 0, s, reinterpret_cast<const double2*>(d_U), d_w_chunk, L.n,
@@ -326,14 +327,10 @@ int dm_launch_chunk(hipStream_t s, const DmPlan& L, SpanRecorder* ev, const int3
     }
     if (ev) ev->stop();
     TBK_HIP(hipGetLastError());
-    const int64_t slice_lo = g0 / gps, slice_hi = (g_end - 1) / gps;
-    if (ev) ev->start(2);
-    hipLaunchKernelGGL(dm_fourier_kernel, dim3((unsigned)((L.nct + 3) / 4), (unsigned)(L.nr_pad / 16), (unsigned)(slice_hi - slice_lo + 1)),
-                       dim3(DM_THREADS), 0, s, d_tab, d_P, L.n2, L.nct, L.nr_pad, ng, g0, g_end, gps, slice_lo, d_part);
-    if (ev) ev->stop();
-    TBK_HIP(hipGetLastError());
-    return TBK_OK;
+    return dm_launch_fourier(s, L, ev, c0, nkc, d_tab, d_P, d_part);
 }
+
+}  // namespace
 
 // the result of the slab in device memory: d_part itself with one slice, else the slices summed into d_rho
 int dm_launch_reduce(hipStream_t s, const DmPlan& L, SpanRecorder* ev, const double2* d_part, double2* d_rho, const double2** result) {
@@ -355,8 +352,6 @@ int dm_check_R(int64_t n_r, const int64_t* R, const double* rho_out, int n_orb) 
     TBK_ARG(n_orb <= 16320, "more than 16320 orbitals");  // (255 x 255 blocks of the projector: one grid row each)
     return TBK_OK;
 }
-
-}  // namespace
 
 extern "C" int tbk_dm_plan(int64_t rows, int n_orb, int64_t n_r, int64_t* out) {
     TBK_ARG(rows >= 1 && n_orb >= 1 && n_r >= 1 && out != nullptr, "rows / n_orb / n_r < 1 or out is NULL");
