@@ -53,7 +53,8 @@ typedef enum tbk_status {
     TBK_ERR_DEVICE = 2,   /* no device, HIP / rocBLAS / RCCL failure              -> RuntimeError */
     TBK_ERR_MEMORY = 3,   /* device allocation failed                             -> MemoryError  */
     TBK_ERR_NOT_FINITE = 4, /* NaN / Inf in H(k): scipy check_finite=True         -> ValueError   */
-    TBK_ERR_NO_CONVERGENCE = 5 /* eigensolver did not converge                    -> LinAlgError  */
+    TBK_ERR_NO_CONVERGENCE = 5, /* eigensolver did not converge                   -> LinAlgError  */
+    TBK_ERR_SINGULAR = 6  /* tbk_green_dressed: z - H(k) - Sigma(z) is singular   -> LinAlgError  */
 } tbk_status;
 
 /* eigensolver selection for tbk_model_set_option(TBK_OPT_EIGENSOLVER, ...):
@@ -442,6 +443,37 @@ int tbk_green_plan(int64_t rows, int n_orb, int64_t n_r, int64_t n_z, int64_t z_
  * handle's calls made while TBK_OPT_TIMING was on; calls = how many calls; reset = 1 clears.  (The eigensolver stages are in
  * tbk_get_timing.) */
 int tbk_green_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
+/* ---- the dressed lattice Green's function: a local, energy-dependent self-energy by batched inversion (not in the reference) ------
+ * Mesh, mesh points, phase, R, G_out and the energy tiles are those of tbk_green_function; H(k) is that of tbk_hamilton_device with
+ * convention 2; Sigma: double [n_z][n_orb][n_orb][2], any finite complex matrices (not Hermitian, not causal if the caller says so):
+ *
+ *     G(R, z) = sum_k exp(-2 pi i k . R) (z 1 - H(k) - Sigma(z))^-1 / NK
+ *
+ * z: double [n_z][2], 1 <= n_z <= 4096, every component finite; Im z = 0 is allowed here (Sigma carries its own broadening).  No
+ * eigensolve: per chunk the FULL H(k), per energy tile one launch of the inversion kernel (Gauss-Jordan in place, partial pivoting on
+ * |re| + |im| with ties to the lowest row, panels of 16 pivots whose rank-16 update runs on the FP64 matrix pipe; up to 64 orbitals)
+ * and one Fourier contraction.  Above 64 orbitals, and for a handle with TBK_OPT_EIGENSOLVER = TBK_EIG_ROCSOLVER,
+ * rocsolver_zgetrf / zgetri_strided_batched take the inversions (booked on TBK_CNT_LIBRARY_CALLS).  A pivot that is exactly zero, a
+ * library status != 0 or a non-finite element of an inverse is TBK_ERR_SINGULAR; the message names the first such mesh point and
+ * energy, and G_out is not to be used.  The bits of G(R, z) depend on (R, z, Sigma(z)) alone for a given H, chunk size and slab.
+ * Error per component: max_k 8 n u rho kappa_2(A) ||A^-1||_2 + 4 (NK + 32) u max_k ||A^-1||_2. */
+
+/* The kernels alone on matrices the caller brings (H [NK][n_orb][n_orb][2] in mesh order).  k_chunk, z_tile: as for
+ * tbk_green_from_eigensystem.  Always the own kernel up to 64 orbitals, the library above. */
+int tbk_green_dressed_from_matrices(int device, int dim, const int32_t* mesh, int n_orb, const double* H, int64_t k_chunk, int64_t z_tile,
+                                    int64_t n_z, const double* z, const double* Sigma, int64_t n_r, const int64_t* R, double* G_out);
+/* The whole call: the loop of tbk_green_function with H(k) of the chunk and the inversions in the place of the eigensolve and the
+ * projectors.  The chunk (TBK_OPT_K_CHUNK, 0: from the memory left) is shared between H(k) of the chunk and the inverses of one tile. */
+int tbk_green_dressed(tbk_model* m, const int32_t* mesh, int64_t n_z, const double* z, const double* Sigma, int64_t n_r, const int64_t* R,
+                      double* G_out);
+/* On several devices from one process: the slabs of tbk_dos_multi, added by the host in handle order.  The handles must be distinct. */
+int tbk_green_dressed_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int64_t n_z, const double* z, const double* Sigma,
+                            int64_t n_r, const int64_t* R, double* G_out);
+/* ms[3] = the summed HIP-event time of the phase tables, the inversions (with the library route: forming, LU, inverse and scatter), and
+ * the contractions + the sums of their slices in this handle's dressed calls made while TBK_OPT_TIMING was on; calls, reset as above.
+ * (H(k) is in tbk_get_timing.) */
+int tbk_green_dressed_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
 /* ---- the bare (Lindhard) static susceptibility of a uniform k mesh (not in the reference) ----------------------------------------
  * Mesh and mesh points k = (i_1 / n_1, ..., i_dim / n_dim) are those of tbk_occupations (dim 2 or 3); k+q is the mesh point with the

@@ -23,6 +23,7 @@ TBK_ERR_DEVICE = 2
 TBK_ERR_MEMORY = 3
 TBK_ERR_NOT_FINITE = 4
 TBK_ERR_NO_CONVERGENCE = 5
+TBK_ERR_SINGULAR = 6
 
 TBK_EIG_AUTO, TBK_EIG_WAVE, TBK_EIG_ROCSOLVER = 0, 1, 2
 TBK_OPT_EIGENSOLVER, TBK_OPT_K_CHUNK, TBK_OPT_TIMING, TBK_OPT_FOLD, TBK_OPT_STRASSEN, TBK_OPT_STRASSEN_LEVELS = 1, 2, 3, 4, 5, 6
@@ -103,6 +104,10 @@ SIGNATURES = {
     "tbk_green_function_multi": (_c_int, [_vp, _c_int, _vp, _c_i64, _vp, _c_i64, _vp, _vp]),
     "tbk_green_plan": (_c_int, [_c_i64, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(_c_i64)]),
     "tbk_green_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
+    "tbk_green_dressed_from_matrices": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, _c_i64, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _vp]),
+    "tbk_green_dressed": (_c_int, [_vp, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _vp]),
+    "tbk_green_dressed_multi": (_c_int, [_vp, _c_int, _vp, _c_i64, _vp, _vp, _c_i64, _vp, _vp]),
+    "tbk_green_dressed_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
     "tbk_chi_from_eigensystem": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, _vp, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _vp, _vp]),
     "tbk_susceptibility": (_c_int, [_vp, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _c_int, _c_int, _vp, _vp, _vp]),
     "tbk_susceptibility_multi": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _c_int, _c_int, _vp, _vp, _vp]),
@@ -200,6 +205,8 @@ def check(status):
         raise MemoryError(msg)
     if status == TBK_ERR_NO_CONVERGENCE:
         raise np.linalg.LinAlgError(msg)  # what scipy.linalg.eigvalsh raises
+    if status == TBK_ERR_SINGULAR:
+        raise np.linalg.LinAlgError(msg)  # what numpy.linalg.inv raises
     raise RuntimeError(msg)
 
 

@@ -1110,8 +1110,9 @@ class Model:
         return DensityMatrix(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, rho)
 
     @staticmethod
-    def _complex_energies_argument(z):
-        """``z complex128 (NZ,)`` from a complex number or a sequence of 1 to 4096 of them, every one finite with ``Im z != 0``."""
+    def _complex_energies_argument(z, *, off_axis=True):
+        """``z complex128 (NZ,)`` from a complex number or a sequence of 1 to 4096 of them, every one finite and, unless
+        ``off_axis`` is false, with ``Im z != 0``."""
         if z is None or isinstance(z, (str, bytes)):
             raise ValueError("z must be a complex number or a sequence of them, got {!r}".format(z))
         try:
@@ -1127,11 +1128,33 @@ class Model:
             raise ValueError("z must be one energy or a sequence of 1 to 4096, got shape {}".format(array.shape))
         if not (np.all(np.isfinite(array.real)) and np.all(np.isfinite(array.imag))):
             raise ValueError("z must be finite")
-        if np.any(array.imag == 0.0):
+        if off_axis and np.any(array.imag == 0.0):
             raise ValueError("every z needs Im z != 0: the resolvent is evaluated off the real axis only")
         return np.ascontiguousarray(array)
 
-    def green_function(self, mesh, z, *, R=None):
+    def _self_energy_argument(self, self_energy, z, n_z):
+        """``Sigma complex128 (NZ, size, size)`` from an array-like of that shape (``(size, size)`` when ``z`` is one number), every
+        entry finite."""
+        if isinstance(self_energy, (str, bytes)):
+            raise ValueError("self_energy must be a complex array of shape (NZ, size, size), got {!r}".format(self_energy))
+        try:
+            array = np.asarray(self_energy)
+            if array.dtype.kind not in "iufc":
+                raise TypeError
+            array = array.astype(np.complex128)
+        except (TypeError, ValueError):
+            raise ValueError("self_energy must be a complex array of shape (NZ, size, size)") from None
+        if array.ndim == 2 and np.ndim(z) == 0:
+            array = array.reshape((1,) + array.shape)
+        if array.shape != (n_z, self.size, self.size):
+            raise ValueError(
+                "self_energy must have shape ({}, {}, {}): one matrix per energy, got {}".format(n_z, self.size, self.size, array.shape)
+            )
+        if not (np.all(np.isfinite(array.real)) and np.all(np.isfinite(array.imag))):
+            raise ValueError("self_energy must be finite")
+        return np.ascontiguousarray(array)
+
+    def green_function(self, mesh, z, *, R=None, self_energy=None):
         """
         The lattice Green's function (the resolvent) ``G(R, z)`` of a uniform k mesh at complex energies, computed on the GPU from
         eigenvalues and eigenvectors that never leave it.  Not in the reference.
@@ -1167,11 +1190,44 @@ class Model:
         complex numbers, times the k slices of the transform) stay in device memory, else ``MemoryError``.  One-dimensional models
         raise ``ValueError``.  With several ``devices`` every device contracts a slab of the mesh along its first axis and the host
         adds the slabs.
+
+        Dressed function.  ``self_energy`` is a local, energy-dependent self-energy ``Sigma``: a complex array-like of shape
+        ``(NZ, size, size)``, one matrix per energy (a single ``(size, size)`` matrix when ``z`` is one number), every entry finite,
+        else ``ValueError``.  It need not be Hermitian or causal.  With it ``z`` may be any finite complex number, real ones
+        included (``Sigma`` carries its own broadening), and no eigensystem is computed: with ``H(k)`` of
+        ``hamilton(k, convention=2)``::
+
+            A(k, z) = z 1 - H(k) - Sigma(z)
+            P(k, z) = A(k, z)^-1 / NK
+            G(R, z) = sum_k exp(-2 pi i k . R) P(k, z)
+
+        by one general inversion per mesh point and energy on the GPU -- Gauss-Jordan elimination with partial pivoting on
+        ``|re| + |im|`` up to 64 orbitals, the library's LU above -- and the transform above.  A singular ``A(k, z)`` (a pivot that
+        is exactly zero, or a non-finite element of the inverse) raises ``numpy.linalg.LinAlgError`` naming the first such mesh
+        point and energy; no NaN is returned.  Properties.  (1) ``Sigma = 0`` reproduces the undressed ``G`` within the sum of both
+        bounds.  (2) ``Sigma(z) = s(z) 1`` gives the undressed ``G`` at ``z - s(z)``.  (3) A constant Hermitian ``Sigma = S`` gives
+        the undressed ``G`` of the model with ``S`` added on site.  (4) ``G(R, conj(z); Sigma^H) = G(-R, z; Sigma)^H``.  (5) Over the
+        dual cell of the mesh ``sum_R' ((z - Sigma(z)) delta(R') - H(R')) G(R - R', z) = delta(R)``.  (6) The bits of ``G(R, z)``
+        depend on ``(R, z, Sigma(z))`` alone: not on the other energies, their order, the other vectors or duplicates, and
+        ``R + n_d e_d`` has the bits of ``R``.  Error bound per component, with ``u = 2^-53``, ``rho`` the growth factor of the
+        elimination and the 2-norm condition number ``kappa_2``: ``max_k 8 size u rho kappa_2(A) ||A^-1|| + 4 (NK + 32) u max_k
+        ||A^-1||``; for causal input ``||A^-1|| <= 1 / |Im z|``.  Work: ``8 size^3`` flops per mesh point and
+        energy, no eigensolve.
         """
         mesh_array = self._mesh_argument(mesh, "green_function")
-        energies = self._complex_energies_argument(z)
+        energies = self._complex_energies_argument(z, off_axis=self_energy is None)
         vectors = self._lattice_vectors_argument(R)
         G = np.empty((vectors.shape[0], energies.shape[0], self.size, self.size), dtype=np.complex128)
+        if self_energy is not None:
+            sigma = self._self_energy_argument(self_energy, z, energies.shape[0])
+            with self._call_lock:
+                # a singular z - H(k) - Sigma(z): TBK_ERR_SINGULAR -> numpy.linalg.LinAlgError, as numpy.linalg.inv
+                handles, n_handles = self._handle_array()
+                _lib.check(
+                    _lib.lib().tbk_green_dressed_multi(handles, n_handles, _lib.ptr(mesh_array), energies.shape[0], _lib.ptr(energies),
+                                                       _lib.ptr(sigma), vectors.shape[0], _lib.ptr(vectors), _lib.ptr(G))
+                )
+            return GreenFunction(energies, vectors, G)
         with self._call_lock:
             # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
             handles, n_handles = self._handle_array()

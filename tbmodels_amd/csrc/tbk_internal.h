@@ -178,11 +178,11 @@ struct SpanRecorder {
 };
 
 // The sums the mesh calls book their kernel times on, one row per family (tbk_dos_timing, tbk_pdos_timing, tbk_fermi_timing,
-// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing: what each counts differs and is listed in DESIGN.md
+// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing: what each counts differs and is listed in DESIGN.md
 // section 10)
-enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_COUNT };
+enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_COUNT };
 struct TimedSums {
-    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry and green three)
+    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green and the dressed green three)
     int64_t calls = 0;
     int64_t passes = 0;  // fermi: the passes of its searches
 };
@@ -346,7 +346,10 @@ struct tbk_model {
     DevBuf ws_dm_rho;    // ... their sum [n_r][n_orb][n_orb] complex (more than one slice)
                          // tbk_green_function (tbk_green.hip) goes through the same five: behind the vectors its energies, P and the partials
                          // per energy tile, ws_dm_rho G [n_r][n_z][n_orb][n_orb] and, behind it, the sum of one tile's slices; its k list is
-                         // in ws_mesh_k, the eigenvectors of one chunk and their eigenvalues in ws_pdos_u
+                         // in ws_mesh_k, the eigenvectors of one chunk and their eigenvalues in ws_pdos_u.  tbk_green_dressed: behind the
+                         // energies the self-energy [n_z][n_orb][n_orb] complex, ws_pdos_u the full H(k) of one chunk, ws_dm_p the inverses,
+                         // ws_mesh_work the library route's batch, pivots and status
+    DevBuf ws_green_flag;  // tbk_green_dressed: one 64-bit status word, all ones or the smallest (mesh index * 4096 + energy index) that was singular
     // The calls on the resident eigensystem of a whole mesh (tbk_resident.h; the susceptibilities of tbk_chi.hip, tbk_berry_flux of
     // tbk_berry.hip): k, E and U are ResidentMesh's, the other two each family lays out for itself
     DevBuf ws_mesh_k;     // the k list of the whole mesh [NK][dim]
