@@ -53,8 +53,8 @@ typedef enum tbk_status {
     TBK_ERR_DEVICE = 2,   /* no device, HIP / rocBLAS / RCCL failure              -> RuntimeError */
     TBK_ERR_MEMORY = 3,   /* device allocation failed                             -> MemoryError  */
     TBK_ERR_NOT_FINITE = 4, /* NaN / Inf in H(k): scipy check_finite=True         -> ValueError   */
-    TBK_ERR_NO_CONVERGENCE = 5, /* eigensolver did not converge                   -> LinAlgError  */
-    TBK_ERR_SINGULAR = 6  /* tbk_green_dressed: z - H(k) - Sigma(z) is singular   -> LinAlgError  */
+    TBK_ERR_NO_CONVERGENCE = 5, /* eigensolver / decimation did not converge      -> LinAlgError  */
+    TBK_ERR_SINGULAR = 6  /* tbk_green_dressed: z - H(k) - Sigma(z) is singular; tbk_surface_green: z - e is -> LinAlgError  */
 } tbk_status;
 
 /* eigensolver selection for tbk_model_set_option(TBK_OPT_EIGENSOLVER, ...):
@@ -474,6 +474,46 @@ int tbk_green_dressed_multi(tbk_model* const* handles, int n_handles, const int3
  * the contractions + the sums of their slices in this handle's dressed calls made while TBK_OPT_TIMING was on; calls, reset as above.
  * (H(k) is in tbk_get_timing.) */
 int tbk_green_dressed_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
+/* ---- surface and bulk Green's functions of a semi-infinite crystal by iterative decimation (not in the reference) -------------------
+ * Lopez Sancho, Lopez Sancho and Rubio, J. Phys. F 15, 851 (1985).  With a the stacking axis, hop_full[R] the full hopping matrices
+ * (tbk_hamilton with convention 2 is sum_R exp(2 pi i k.R) hop_full[R]) and kp an in-plane point (the reduced coordinates without
+ * component a):
+ *
+ *     H_m(kp)   = sum_{R : R_a = m} exp(2 pi i kp.Rp) hop_full[R]        m = -L ... L;  L = layers >= max |R_a|
+ *     H00[p][q] = H_{q-p},  H01[p][q] = H_{L+q-p} for q <= p, else 0     blocks of n_orb x n_orb, p, q = 0 ... L - 1;  N = n_orb max(L, 1)
+ *
+ *     es = et = e = H00, alpha = H01, beta = H01^H;  repeat  g = (z 1 - e)^-1,  T = g alpha:  alpha' = alpha T, et += beta T, e += beta T,
+ *     T = g beta:  es += alpha T, e += alpha T, beta' = beta T  until, after an update, max(|alpha|_inf, |beta|_inf) <= 2^-53 |H01|_inf
+ *     (row sums of |re| + |im|);   bottom = (z - es)^-1,  top = (z - et)^-1,  bulk = (z - e)^-1.
+ *
+ * bottom: the crystal on principal layers P >= 0 (its surface cell is block 0); top: on P <= 0 (surface cell: block L - 1); bulk: a
+ * principal layer deep inside.  L = 0: no iteration, all three are (z - H00)^-1.  z: double [n_z][2], 1 <= n_z <= 4096, finite,
+ * Im z != 0.  max_iterations: 1 ... 4096; a (kp, z) that reaches it is TBK_ERR_NO_CONVERGENCE, a zero pivot or a non-finite element of
+ * an inverse TBK_ERR_SINGULAR; the message names the first such k index and energy, and the results are not to be used.  Results:
+ * iterations int32 [nk][n_z]; bottom, top, bulk double [nk][n_z][N][N][2] or, spectral != 0, double [nk][n_z][N] holding -Im diag / pi
+ * (no matrix leaves the device).  The bits of one (kp, z) depend on nothing else.  N <= 64: one workgroup per (kp, z), Gauss-Jordan
+ * of tbk_green_dressed, six products per iteration on the FP64 matrix pipe.  65 <= N <= 1024, and for a handle with
+ * TBK_OPT_EIGENSOLVER = TBK_EIG_ROCSOLVER: the (kp, z) of a chunk in lockstep, in batches of a fixed number of members, on
+ * rocblas_zgemm_strided_batched and rocsolver_zgetrf / zgetri_strided_batched (booked on TBK_CNT_LIBRARY_CALLS); a member that has
+ * converged gets alpha = beta = 0 exactly.  N > 1024 is TBK_ERR_ARGUMENT.
+ * Error per component: 8 N u rho (|z| + |H00|_2 + 2 |H01|_2) / (Im z)^2 (iterations + 1). */
+
+/* The kernel alone on principal layers the caller brings: H00, H01 double [n_k][N][N][2] (H01 NULL: no hopping between the layers, no
+ * iteration).  k_chunk: points per launch (0: from the size of the results).  Always the own kernel up to 64 rows, the library above. */
+int tbk_surface_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int64_t n_z, const double* z,
+                              int max_iterations, int64_t k_chunk, int spectral, int32_t* iterations, double* bottom, double* top, double* bulk);
+/* The whole call: k double [nk][dim - 1] (dim = 1: ignored, nk = 1 is the one point there is).  Per chunk (TBK_OPT_K_CHUNK, 0: from the
+ * size of the results) the FULL H(k) of tbk_hamilton_device at k_a = j / (2 layers + 1), j = 0 ... 2 layers, H_m from them by a discrete
+ * Fourier sum, then the decimation.  layers below the reach of a stored hopping vector along axis is TBK_ERR_ARGUMENT. */
+int tbk_surface_green(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int64_t n_z, const double* z, int max_iterations,
+                      int spectral, int32_t* iterations, double* bottom, double* top, double* bulk);
+/* On several devices from one process: the slabs of tbk_hamilton_multi, every device writing its rows of the results. */
+int tbk_surface_green_multi(tbk_model* const* handles, int n_handles, int axis, int layers, const double* k, int64_t nk, int64_t n_z,
+                            const double* z, int max_iterations, int spectral, int32_t* iterations, double* bottom, double* top, double* bulk);
+/* ms[3] = the summed HIP-event time of H(k) with the principal layers, the decimation, and the copies of the results to the host in this
+ * handle's calls made while TBK_OPT_TIMING was on; calls, reset as above. */
+int tbk_surface_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
 /* ---- the bare (Lindhard) static susceptibility of a uniform k mesh (not in the reference) ----------------------------------------
  * Mesh and mesh points k = (i_1 / n_1, ..., i_dim / n_dim) are those of tbk_occupations (dim 2 or 3); k+q is the mesh point with the

@@ -178,11 +178,11 @@ struct SpanRecorder {
 };
 
 // The sums the mesh calls book their kernel times on, one row per family (tbk_dos_timing, tbk_pdos_timing, tbk_fermi_timing,
-// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing: what each counts differs and is listed in DESIGN.md
-// section 10)
-enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_COUNT };
+// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing, tbk_surface_timing: what each counts differs and is
+// listed in DESIGN.md section 10)
+enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_SURFACE, TIMED_COUNT };
 struct TimedSums {
-    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green and the dressed green three)
+    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green, the dressed green and surface three)
     int64_t calls = 0;
     int64_t passes = 0;  // fermi: the passes of its searches
 };
@@ -348,7 +348,9 @@ struct tbk_model {
                          // per energy tile, ws_dm_rho G [n_r][n_z][n_orb][n_orb] and, behind it, the sum of one tile's slices; its k list is
                          // in ws_mesh_k, the eigenvectors of one chunk and their eigenvalues in ws_pdos_u.  tbk_green_dressed: behind the
                          // energies the self-energy [n_z][n_orb][n_orb] complex, ws_pdos_u the full H(k) of one chunk, ws_dm_p the inverses,
-                         // ws_mesh_work the library route's batch, pivots and status
+                         // ws_mesh_work the library route's batch, pivots and status.  tbk_surface_green (tbk_surface.hip): ws_mesh_k the
+                         // k list with its samples along the stacking axis, ws_dm_r energies and twiddles, ws_pdos_u H(k) of one chunk,
+                         // ws_dm_p its principal layers, ws_dm_rho its results and status word, ws_mesh_work the workgroups' slots
     DevBuf ws_green_flag;  // tbk_green_dressed: one 64-bit status word, all ones or the smallest (mesh index * 4096 + energy index) that was singular
     // The calls on the resident eigensystem of a whole mesh (tbk_resident.h; the susceptibilities of tbk_chi.hip, tbk_berry_flux of
     // tbk_berry.hip): k, E and U are ResidentMesh's, the other two each family lays out for itself
@@ -378,6 +380,11 @@ struct tbk_kdotp {
 // what a tbk_*_timing getter does behind its argument checks: the family's row (its first `stages` times; passes may be NULL),
 // read and, if asked, reset under the handle's lock
 int tbk_timed_read(tbk_model* m, TimedFamily family, int stages, double* ms, int64_t* calls, int64_t* passes, int reset);
+
+// tbk_surface.hip: tbk_surface_green on one handle for the k-points [k_base, k_base + nk) of a longer list (the slabs of
+// tbk_surface_green_multi): the messages name k_base + the point's index
+int tbk_surface_green_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int64_t n_z, const double* z,
+                           int max_iterations, int spectral, int32_t* iterations, double* bottom, double* top, double* bulk);
 
 // roctx range around a stage (no-ops unless a roctx library can be loaded); tbk_api.hip
 void tbk_range_push(const char* name);

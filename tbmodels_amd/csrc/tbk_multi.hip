@@ -111,6 +111,27 @@ extern "C" int tbk_eigh_multi(tbk_model* const* handles, int n_handles, const do
     });
 }
 
+// The surface Green's function on several devices (tbk_surface.hip): the k list in the slabs of tbk_hamilton_multi, every device writing
+// its rows of the results
+extern "C" int tbk_surface_green_multi(tbk_model* const* handles, int n_handles, int axis, int layers, const double* k, int64_t nk, int64_t n_z,
+                                       const double* z, int max_iterations, int spectral, int32_t* iterations, double* bottom, double* top,
+                                       double* bulk) {
+    TBK_CHECK(check_handles(handles, n_handles));
+    TBK_ARG(nk >= 0, "nk < 0");
+    if (n_handles == 1 || nk == 0)
+        return tbk_surface_green(handles[0], axis, layers, k, nk, n_z, z, max_iterations, spectral, iterations, bottom, top, bulk);
+    TBK_ARG(n_z >= 1 && n_z <= 4096 && layers >= 0 && layers <= 1024, "n_z must be 1 to 4096, layers 0 ... 1024");
+    TBK_ARG(iterations != nullptr && bottom != nullptr && top != nullptr && bulk != nullptr, "iterations / bottom / top / bulk is NULL");
+    const int dim = handles[0]->dim;
+    TBK_ARG(k != nullptr || dim == 1, "k is NULL");
+    const int64_t N = (int64_t)handles[0]->n_orb * std::max(layers, 1);
+    const int64_t item = n_z * (spectral != 0 ? N : N * N * 2);  // doubles of one k-point in each of the three results
+    return run_slabs(n_handles, nk, [&](int i, int64_t lo, int64_t count) {
+        return tbk_surface_green_slab(handles[i], lo, axis, layers, k != nullptr ? k + lo * (dim - 1) : nullptr, count, n_z, z, max_iterations, spectral,
+                                      iterations + lo * n_z, bottom + lo * item, top + lo * item, bulk + lo * item);
+    });
+}
+
 // The density of states of a mesh on several devices (tbk_dos.hip): handle i takes a contiguous slab of ceil(n_1 / n) cells along
 // axis 0 and evaluates the planes of that slab plus the one periodic neighbour plane its last cells need.  Every handle returns
 // its share of nos; the host adds the shares in handle order (slabs that hold no cells are skipped).

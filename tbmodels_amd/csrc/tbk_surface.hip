@@ -1,0 +1,1064 @@
+// tbk_surface.hip -- surface and bulk Green's functions of a semi-infinite crystal by the iterative decimation of Lopez Sancho, Lopez
+// Sancho and Rubio (J. Phys. F 15, 851 (1985)).  Not in the reference; DESIGN.md section 21 has the quantity, the kernels and the
+// measurements, tools/surface_model.py is the statement the tests compare with.
+//
+//   H_m(kp)  = sum_{R : R_a = m} exp(2 pi i kp.Rp) hop_full[R]        a: the stacking axis, m = -L ... L, L = max |R_a|
+//   H00[p,q] = H_{q-p},  H01[p,q] = H_{L+q-p} (q <= p), else 0        principal layers of L cells: N = n L (n when L = 0)
+//
+//   es = et = e = H00, alpha = H01, beta = H01^H;  repeat
+//       g = (z 1 - e)^-1
+//       T = g alpha:  A' = alpha T,  et += beta T,  e += beta T
+//       T = g beta:   es += alpha T, e += alpha T,  B' = beta T
+//       alpha, beta = A', B'
+//   until max(|alpha|_inf, |beta|_inf) <= 2^-53 |H01|_inf  (row sums of |re| + |im|);
+//   G_bottom = (z - es)^-1, G_top = (z - et)^-1, G_bulk = (z - e)^-1.
+//
+//   surface_layers_kernel    H00, H01 of a chunk's in-plane points from the FULL H(k) at k_a = j / (2 L + 1), j = 0 ... 2 L (chunk_h,
+//                            convention 2): H_m = (1 / (2 L + 1)) sum_j exp(-2 pi i m j / (2 L + 1)) H(kp, j / (2 L + 1)), the twiddles
+//                            from a host table.  No line of the H(k) path knows about surfaces.
+//   surface_decimate_kernel  one workgroup owns one (kp, z) for the whole iteration: the inversion is green_invert_kernel's panelled
+//                            Gauss-Jordan (a second copy on LDS planes, surf_invert), the six products per iteration run on
+//                            v_mfma_f64_16x16x4_f64, four real MFMAs per complex tile and K step.  N <= 64.
+//   surf_lib_chunk           65 <= N <= 1024, and on request: the same iteration in lockstep batches of a fixed number of members on
+//                            rocblas_zgemm_strided_batched and rocsolver_zgetrf / zgetri_strided_batched, with five small kernels.
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include <rocsolver/rocsolver.h>
+
+#include "tbk_resident.h"
+
+namespace {
+
+typedef double surf_d4 __attribute__((ext_vector_type(4)));
+
+constexpr int64_t SURF_MAX_Z = 4096;  // energies per call (include/tbk.h)
+constexpr int SURF_OWN_MAX = 64;      // rows of a principal layer the decimation kernel takes
+constexpr int SURF_LIB_MAX = 1024;    // ... and the library route above it (or on request)
+constexpr int SURF_MAX_ITERATIONS = 4096;
+constexpr unsigned long long SURF_NO_FLAG = ~0ull;
+constexpr size_t SURF_CHUNK_BUDGET = size_t(256) << 20;  // the results of one chunk, and the H(k) samples of one chunk
+constexpr double SURF_DBL_MAX = 1.79769313486231570815e308;
+constexpr double SURF_PI = 3.14159265358979323846;
+constexpr const char* SURF_FAMILY = "the surface Green's function";
+
+inline size_t surf_align256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// What sits where, per template.  X, Y: two matrices in LDS, planes (re, im) of NP rows NP + 1 doubles apart -- the elimination runs
+// in X, its un-permuted result g goes to Y, X then holds T.  alpha, beta, e, es, et: in LDS behind them up to NP = 32 (seven
+// matrices), in the workgroup's slot of a global workspace at NP = 64 (pitch 64; the slot is reread by the workgroup that wrote
+// it; 256 slots are 80 MiB: more than L2, inside the Infinity Cache).
+template <int NP>
+struct SurfGeom {
+    static constexpr int THREADS = NP == 16 ? 64 : 256;
+    static constexpr int WAVES = THREADS / 64;
+    static constexpr int S = NP + 1;
+    static constexpr int TR = NP / 16;               // tile rows
+    static constexpr int NT = TR * TR / WAVES;       // 16 x 16 tiles of a product per wave: 1, 1, 4 (one tile row)
+    static constexpr bool GLOBAL = NP == 64;
+    static constexpr int SM = GLOBAL ? NP : S;       // pitch of alpha, beta, e, es, et
+    static constexpr int LDS_PLANES = GLOBAL ? 4 : 14;
+    static constexpr size_t lds_bytes = ((size_t)LDS_PLANES * NP * S + 2 * THREADS + 2 * NP + NP) * sizeof(double);
+    static constexpr size_t slot_doubles = GLOBAL ? (size_t)10 * NP * NP : 0;
+};
+
+// ---- the inversion: green_invert_kernel's elimination (tbk_green.hip) for ONE matrix per workgroup ------------------
+// Gauss-Jordan in place with implicit partial pivoting on |re| + |im| (ties: the lowest row; a NaN counts as +inf), in panels of 16
+// pivots; the panel's columns by rank-1 VALU updates, every other column tile by a rank-16 update on the matrix pipe.  jrow must be
+// -1 and the planes written before the call (its first barrier orders them); afterwards, behind a barrier of the caller's,
+// inverse[r][s] = storage[prow[r]][jrow[s]].  Returns whether a pivot was exactly zero (the same value on every thread).
+template <int NP, int THREADS>
+__device__ __forceinline__ bool surf_invert(double* ar, double* ai, int* prow, int* jrow, int n, int tid) {
+    constexpr int CG = THREADS / NP;  // column groups of a panel
+    constexpr int CPT = 16 / CG;      // panel columns per thread
+    constexpr int S = NP + 1;
+    constexpr int TR = NP / 16;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int row = tid & (NP - 1), cg = tid / NP;
+    bool used = row >= n, singular = false;
+    for (int j0 = 0; j0 < n; j0 += 16) {
+        const int jn = n - j0 < 16 ? n - j0 : 16;
+        for (int jj = 0; jj < jn; ++jj) {
+            const int jc = j0 + jj;
+            __syncthreads();  // column jc is up to date
+            const double fr = ar[row * S + jc], fi = ai[row * S + jc];
+            double best = fabs(fr) + fabs(fi);
+            if (!(best >= 0.0)) best = __builtin_inf();
+            if (used) best = -1.0;
+            int p = row;
+#pragma unroll
+            for (int off = NP / 2; off > 0; off >>= 1) {
+                const double ob = __shfl_xor(best, off, 64);
+                const int op = __shfl_xor(p, off, 64);
+                if (ob > best || (ob == best && op < p)) {
+                    best = ob;
+                    p = op;
+                }
+            }
+            // (p is a row below n that no step has taken: at least one is left, and taken rows and padding compare as -1)
+            const int src = (lane & ~(NP - 1)) | p;
+            const double pr = __shfl(fr, src, 64), pi = __shfl(fi, src, 64);
+            singular |= best == 0.0;
+            const double den = pr * pr + pi * pi;
+            const double ir = pr / den, ii = -pi / den;  // 1 / pivot
+            double xr[CPT], xi[CPT], yr[CPT], yi[CPT];
+#pragma unroll
+            for (int cc = 0; cc < CPT; ++cc) {
+                const int c = j0 + cg * CPT + cc;
+                xr[cc] = ar[p * S + c];
+                xi[cc] = ai[p * S + c];
+                yr[cc] = ar[row * S + c];
+                yi[cc] = ai[row * S + c];
+            }
+            __syncthreads();  // every wave has read column jc and row p
+#pragma unroll
+            for (int cc = 0; cc < CPT; ++cc) {
+                const int c = j0 + cg * CPT + cc;
+                double tr = ir, ti = ii;  // the new pivot row: a[p][c] / piv, 1 / piv in column jc
+                if (c != jc) {
+                    tr = xr[cc] * ir - xi[cc] * ii;
+                    ti = xr[cc] * ii + xi[cc] * ir;
+                }
+                double nr = tr, ni = ti;
+                if (row != p) {
+                    const double mr = fr * tr - fi * ti, mi = fr * ti + fi * tr;
+                    nr = c == jc ? -mr : yr[cc] - mr;
+                    ni = c == jc ? -mi : yi[cc] - mi;
+                }
+                ar[row * S + c] = nr;
+                ai[row * S + c] = ni;
+            }
+            if (row == p) {
+                used = true;
+                if (cg == 0) {
+                    prow[jc] = p;
+                    jrow[p] = jc;
+                }
+            }
+        }
+        if constexpr (TR > 1) {
+            // the rank-16 update of the other column tiles: T C = mask(C) + W C[pivot rows]
+            const int tp = j0 >> 4, q = lane >> 4, c16 = lane & 15;
+            const bool busy = wave < TR && wave * 16 < n;  // (wave-uniform)
+            double wr[4], wi[4], br[TR - 1][4], bi[TR - 1][4];
+            surf_d4 accr[TR - 1], acci[TR - 1];
+            __syncthreads();  // the panel's columns are W, its pivot rows are known
+            if (busy) {
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) {
+                    wr[ks] = ar[(wave * 16 + c16) * S + j0 + 4 * ks + q];
+                    wi[ks] = ai[(wave * 16 + c16) * S + j0 + 4 * ks + q];
+                }
+#pragma unroll
+                for (int t = 0; t < TR - 1; ++t) {
+                    const int tj = t < tp ? t : t + 1;  // (uniform)
+#pragma unroll
+                    for (int ks = 0; ks < 4; ++ks) {
+                        const int kk = 4 * ks + q;
+                        const int prw = kk < jn ? prow[j0 + kk] : 0;  // (steps beyond n: no pivot row, a zero operand)
+                        br[t][ks] = kk < jn ? ar[prw * S + tj * 16 + c16] : 0.0;
+                        bi[t][ks] = kk < jn ? ai[prw * S + tj * 16 + c16] : 0.0;
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ri = wave * 16 + q + 4 * r;
+                        const bool taken = jrow[ri] >= j0;  // a pivot row of this panel starts from zero
+                        accr[t][r] = taken ? 0.0 : ar[ri * S + tj * 16 + c16];
+                        acci[t][r] = taken ? 0.0 : ai[ri * S + tj * 16 + c16];
+                    }
+                }
+            }
+            __syncthreads();  // every operand is in registers
+            if (busy) {
+#pragma unroll
+                for (int t = 0; t < TR - 1; ++t) {
+                    const int tj = t < tp ? t : t + 1;
+                    if (tj * 16 < n) {  // (uniform: the columns beyond n are zero and stay zero)
+#pragma unroll
+                        for (int ks = 0; ks < 4; ++ks) {
+                            accr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[ks], br[t][ks], accr[t], 0, 0, 0);
+                            acci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[ks], bi[t][ks], acci[t], 0, 0, 0);
+                            accr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wi[ks], bi[t][ks], accr[t], 0, 0, 1);  // - w_i b_i
+                            acci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wi[ks], br[t][ks], acci[t], 0, 0, 0);
+                        }
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int ri = wave * 16 + q + 4 * r;
+                            ar[ri * S + tj * 16 + c16] = accr[t][r];
+                            ai[ri * S + tj * 16 + c16] = acci[t][r];
+                        }
+                    }
+                }
+            }
+        }
+    }
+    return singular;
+}
+
+// The same integer, opaque to the optimiser and not to be moved out of a loop: offsets derived from it are computed where they are
+// used.  Without it every address of the iteration's tiles -- 16 per plane, ten planes, 64 bits each at NP = 64 -- is hoisted in
+// front of the item loop and the kernel spills: 2 800 bytes of scratch per thread at NP = 64 in the first build, which
+// tests/test_dpp_hazards.py::test_no_product_kernel_spills reports.  If that test fails on this kernel after a
+// compiler change, look here first.
+__device__ __forceinline__ int surf_fresh(int x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+// ---- the products -------------------------------------------------------------------------------------------------------------------
+// C = A B of two NP x NP complex matrices in planes (pitches SA, SB), zero beyond n: the wave's NT tiles (tile row (wave NT) / TR,
+// tile columns from (wave NT) % TR on) into registers.  Lane (q = lane / 16, c = lane % 16) feeds A[16 tr + c][k + q], B[k + q][16 tc + c]
+// and holds C[16 tr + q + 4 r][16 tc + c], r = 0 ... 3.  Tiles and K blocks beyond n are skipped (wave-uniform): they are zero.
+template <int NP, int NT, int SA, int SB>
+__device__ __forceinline__ void surf_product(const double* ar, const double* ai, const double* br, const double* bi, int n, int wave, int lane,
+                                             surf_d4 (&cr)[NT], surf_d4 (&ci)[NT]) {
+    constexpr int TR = NP / 16;
+    lane = surf_fresh(lane);
+    const int q = lane >> 4, c16 = lane & 15;
+    const int tr = (wave * NT) / TR, tc0 = (wave * NT) % TR;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) cr[t] = ci[t] = surf_d4{0.0, 0.0, 0.0, 0.0};
+    if (tr * 16 >= n) return;
+#pragma unroll 1
+    for (int kb = 0; kb < TR; ++kb) {  // (not unrolled: the loads of every K block ahead of the first MFMA do not fit the registers)
+        if (kb * 16 < n) {
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const int kk = kb * 16 + 4 * ks + q;
+                const double a_r = ar[(tr * 16 + c16) * SA + kk], a_i = ai[(tr * 16 + c16) * SA + kk];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    if ((tc0 + t) * 16 < n) {
+                        const double b_r = br[kk * SB + (tc0 + t) * 16 + c16], b_i = bi[kk * SB + (tc0 + t) * 16 + c16];
+                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_r, b_r, cr[t], 0, 0, 0);
+                        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_r, b_i, ci[t], 0, 0, 0);
+                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_i, b_i, cr[t], 0, 0, 1);  // - a_i b_i
+                        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_i, b_r, ci[t], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// the wave's tiles of a product into a matrix (ADD: added to it); every element has one owner, whatever the matrix
+template <int NP, int NT, int SD, bool ADD>
+__device__ __forceinline__ void surf_tiles(double* dr, double* di, int n, int wave, int lane, const surf_d4 (&cr)[NT], const surf_d4 (&ci)[NT]) {
+    constexpr int TR = NP / 16;
+    lane = surf_fresh(lane);
+    const int q = lane >> 4, c16 = lane & 15;
+    const int tr = (wave * NT) / TR, tc0 = (wave * NT) % TR;
+    if (tr * 16 >= n) return;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        if ((tc0 + t) * 16 < n) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int at = (tr * 16 + q + 4 * r) * SD + (tc0 + t) * 16 + c16;
+                if (ADD) {
+                    dr[at] += cr[t][r];
+                    di[at] += ci[t][r];
+                } else {
+                    dr[at] = cr[t][r];
+                    di[at] = ci[t][r];
+                }
+            }
+        }
+    }
+}
+
+// |A|_inf and |B|_inf, row sums of |re| + |im| (the padding is zero): a thread sums NP / PARTS columns of its row, the first NP
+// threads add the parts in order, every thread takes the maximum over the rows.  A NaN counts as +inf.  Two barriers inside; the
+// matrices must be visible before the call.
+template <int NP, int THREADS, int SM>
+__device__ __forceinline__ void surf_norms(const double* ar, const double* ai, const double* br, const double* bi, int tid, double* red, double* rown,
+                                           double& na, double& nb) {
+    constexpr int PARTS = THREADS / NP, CPP = NP / PARTS;
+    tid = surf_fresh(tid);
+    const int row = tid & (NP - 1), part = tid / NP;
+    double sa = 0.0, sb = 0.0;
+#pragma unroll 4
+    for (int cc = 0; cc < CPP; ++cc) {
+        const int at = row * SM + part * CPP + cc;
+        sa += fabs(ar[at]) + fabs(ai[at]);
+        sb += fabs(br[at]) + fabs(bi[at]);
+    }
+    red[tid] = sa;
+    red[THREADS + tid] = sb;
+    __syncthreads();
+    if (tid < NP) {
+        double a = 0.0, b = 0.0;
+#pragma unroll
+        for (int p = 0; p < PARTS; ++p) {
+            a += red[p * NP + tid];
+            b += red[THREADS + p * NP + tid];
+        }
+        rown[tid] = a;
+        rown[NP + tid] = b;
+    }
+    __syncthreads();
+    na = 0.0;
+    nb = 0.0;
+#pragma unroll 4
+    for (int r = 0; r < NP; ++r) {
+        double a = rown[r], b = rown[NP + r];
+        if (!(a <= SURF_DBL_MAX)) a = __builtin_inf();
+        if (!(b <= SURF_DBL_MAX)) b = __builtin_inf();
+        na = a > na ? a : na;
+        nb = b > nb ? b : nb;
+    }
+}
+
+// X = z 1 - M, zeros beyond n; jrow cleared for the elimination
+template <int NP, int THREADS, int SM>
+__device__ __forceinline__ void surf_form(double* xr, double* xi, const double* mr, const double* mi, double2 zz, int n, int tid, int* jrow) {
+    constexpr int S = NP + 1;
+    tid = surf_fresh(tid);
+#pragma unroll 2
+    for (int e = tid; e < NP * NP; e += THREADS) {
+        const int i = e / NP, c = e - i * NP;
+        double vr = 0.0, vi = 0.0;
+        if (i < n && c < n) {
+            vr = (i == c ? zz.x : 0.0) - mr[i * SM + c];
+            vi = (i == c ? zz.y : 0.0) - mi[i * SM + c];
+        }
+        xr[i * S + c] = vr;
+        xi[i * S + c] = vi;
+    }
+    if (tid < NP) jrow[tid] = -1;
+}
+
+// H00, H01: [n_k][n][n] of the chunk's in-plane points (H01 NULL: no hopping between layers, no iteration); z: [n_z].  Item w = k n_z +
+// energy index; a workgroup takes the items blockIdx.x, blockIdx.x + gridDim.x, ...  Results per item: iterations, and bottom / top /
+// bulk as [n][n] complex or, spectral, [n] doubles -Im diag / pi.  key0: (index of the chunk's first point) * SURF_MAX_Z; the status
+// word takes the smallest ((point index * SURF_MAX_Z + energy index) * 2 + reason), reason 0 singular, 1 no convergence.  ws: the
+// workgroups' slots at NP = 64.  No index depends on a value but through the pivot tables, which are permutations of [0, n).
+template <int NP>
+__global__ void __launch_bounds__(SurfGeom<NP>::THREADS)
+    surface_decimate_kernel(const double2* __restrict__ H00, const double2* __restrict__ H01, const double2* __restrict__ z, int n_z, int n, int64_t items,
+                            int max_it, int spectral, unsigned long long key0, double* ws, int32_t* __restrict__ iters, double* __restrict__ out_b,
+                            double* __restrict__ out_t, double* __restrict__ out_m, unsigned long long* __restrict__ flag) {
+    using Geo = SurfGeom<NP>;
+    constexpr int THREADS = Geo::THREADS, S = Geo::S, SM = Geo::SM, NT = Geo::NT;
+    constexpr int PX = NP * S, PM = NP * SM;
+    extern __shared__ double surf_lds[];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double* xr = surf_lds;
+    double* xi = xr + PX;
+    double* yr = xi + PX;
+    double* yi = yr + PX;
+    double* mats;
+    double* red;
+    if constexpr (Geo::GLOBAL) {
+        mats = ws + (size_t)blockIdx.x * Geo::slot_doubles;
+        red = yi + PX;
+    } else {
+        mats = yi + PX;
+        red = mats + 10 * PM;
+    }
+    double* alr = mats;
+    double* ali = mats + PM;
+    double* ber = mats + 2 * PM;
+    double* bei = mats + 3 * PM;
+    double* er = mats + 4 * PM;
+    double* ei = mats + 5 * PM;
+    double* esr = mats + 6 * PM;
+    double* esi = mats + 7 * PM;
+    double* etr = mats + 8 * PM;
+    double* eti = mats + 9 * PM;
+    double* rown = red + 2 * THREADS;
+    int* prow = reinterpret_cast<int*>(rown + 2 * NP);
+    int* jrow = prow + NP;
+
+    for (int64_t w = blockIdx.x; w < items; w += gridDim.x) {
+        const int64_t k = w / n_z;
+        const int zi = (int)(w - k * n_z);
+        const double2 zz = z[zi];
+        const double2* h0 = H00 + (size_t)k * n * n;
+        const bool hops = H01 != nullptr;
+        const double2* h1 = hops ? H01 + (size_t)k * n * n : H00;
+#pragma unroll 2
+        for (int e = tid; e < NP * NP; e += THREADS) {
+            const int i = e / NP, c = e - i * NP;
+            double2 a = make_double2(0.0, 0.0), b = make_double2(0.0, 0.0);
+            if (i < n && c < n) {
+                a = h0[(size_t)i * n + c];
+                if (hops) b = h1[(size_t)i * n + c];
+            }
+            er[i * SM + c] = esr[i * SM + c] = etr[i * SM + c] = a.x;
+            ei[i * SM + c] = esi[i * SM + c] = eti[i * SM + c] = a.y;
+            alr[i * SM + c] = b.x;
+            ali[i * SM + c] = b.y;
+            ber[c * SM + i] = b.x;
+            bei[c * SM + i] = -b.y;
+        }
+        __syncthreads();
+        int it = 0, status = 0;  // status 1: singular, 2: the cap was reached (the same on every thread)
+        if (hops) {
+            double na, nb;
+            surf_norms<NP, THREADS, SM>(alr, ali, ber, bei, tid, red, rown, na, nb);
+            const double threshold = na * 0x1p-53;
+            for (;;) {
+                ++it;
+                surf_form<NP, THREADS, SM>(xr, xi, er, ei, zz, n, tid, jrow);
+                const bool zero_pivot = surf_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
+                __syncthreads();
+#pragma unroll 2
+                for (int e = tid; e < NP * NP; e += THREADS) {  // g into Y, the permutations undone
+                    const int i = e / NP, c = e - i * NP;
+                    double vr = 0.0, vi = 0.0;
+                    if (i < n && c < n) {
+                        const int at = prow[i] * S + jrow[c];
+                        vr = xr[at];
+                        vi = xi[at];
+                    }
+                    yr[i * S + c] = vr;
+                    yi[i * S + c] = vi;
+                }
+                __syncthreads();
+                surf_d4 tr[NT], ti[NT], p1r[NT], p1i[NT], p4r[NT], p4i[NT];
+                surf_product<NP, NT, S, SM>(yr, yi, alr, ali, n, wave, lane, tr, ti);  // T = g alpha
+                surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, tr, ti);
+                __syncthreads();
+                surf_product<NP, NT, SM, S>(alr, ali, xr, xi, n, wave, lane, p1r, p1i);  // alpha g alpha
+                surf_product<NP, NT, SM, S>(ber, bei, xr, xi, n, wave, lane, tr, ti);    // beta g alpha
+                surf_tiles<NP, NT, SM, true>(etr, eti, n, wave, lane, tr, ti);
+                surf_tiles<NP, NT, SM, true>(er, ei, n, wave, lane, tr, ti);
+                __syncthreads();  // T has been read
+                surf_product<NP, NT, S, SM>(yr, yi, ber, bei, n, wave, lane, tr, ti);  // T = g beta
+                surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, tr, ti);
+                __syncthreads();
+                surf_product<NP, NT, SM, S>(alr, ali, xr, xi, n, wave, lane, tr, ti);  // alpha g beta
+                surf_tiles<NP, NT, SM, true>(esr, esi, n, wave, lane, tr, ti);
+                surf_tiles<NP, NT, SM, true>(er, ei, n, wave, lane, tr, ti);
+                surf_product<NP, NT, SM, S>(ber, bei, xr, xi, n, wave, lane, p4r, p4i);  // beta g beta
+                __syncthreads();  // alpha and beta have been read
+                surf_tiles<NP, NT, SM, false>(alr, ali, n, wave, lane, p1r, p1i);
+                surf_tiles<NP, NT, SM, false>(ber, bei, n, wave, lane, p4r, p4i);
+                __syncthreads();
+                surf_norms<NP, THREADS, SM>(alr, ali, ber, bei, tid, red, rown, na, nb);
+                const double size = na > nb ? na : nb;
+                if (zero_pivot || !(size <= SURF_DBL_MAX)) {
+                    status = 1;
+                    break;
+                }
+                if (size <= threshold) break;
+                if (it >= max_it) {
+                    status = 2;
+                    break;
+                }
+            }
+        }
+        bool bad = status == 1;
+#pragma unroll 1
+        for (int which = 0; which < 3; ++which) {
+            const double* mr = which == 0 ? esr : which == 1 ? etr : er;
+            const double* mi = which == 0 ? esi : which == 1 ? eti : ei;
+            double* out = which == 0 ? out_b : which == 1 ? out_t : out_m;
+            surf_form<NP, THREADS, SM>(xr, xi, mr, mi, zz, n, tid, jrow);
+            bad |= surf_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
+            __syncthreads();
+            // (every element of the inverse is looked at in both modes: the same inputs are singular with and without spectral)
+            double2* o = reinterpret_cast<double2*>(out) + (size_t)w * n * n;
+            for (int e = tid; e < n * n; e += THREADS) {
+                const int r = e / n, s = e - r * n;
+                const int at = prow[r] * S + jrow[s];
+                const double2 v = make_double2(xr[at], xi[at]);
+                bad |= !(fabs(v.x) <= SURF_DBL_MAX && fabs(v.y) <= SURF_DBL_MAX);
+                if (!spectral)
+                    o[e] = v;
+                else if (r == s)
+                    out[(size_t)w * n + r] = -v.y / SURF_PI;
+            }
+            __syncthreads();  // X and the tables are free again
+        }
+        if (tid == 0) iters[w] = it;
+        const unsigned long long key = (key0 + (unsigned long long)k * (unsigned long long)SURF_MAX_Z + (unsigned long long)zi) * 2ull;
+        if (bad) atomicMin(flag, key);
+        if (status == 2 && tid == 0) atomicMin(flag, key + 1ull);
+    }
+}
+
+// Hs: [n_k][2 L + 1][n][n], the full H(k) at k_a = j / (2 L + 1); tw: [2 L + 1][2 L + 1][2] (cos, sin) of -2 pi ((m j) mod (2 L + 1)) /
+// (2 L + 1), row m + L.  One workgroup per in-plane point writes H00 and, L > 0, H01 [N][N], N = n max(L, 1): block (p, q) of H00 is
+// H_{q-p}, of H01 H_{L+q-p} for q <= p and zero above.  H_m = (sum_j tw[m][j] Hs[j]) / (2 L + 1), j ascending.
+__global__ void __launch_bounds__(256) surface_layers_kernel(const double2* __restrict__ Hs, const double* __restrict__ tw, int n, int L,
+                                                             double2* __restrict__ H00, double2* __restrict__ H01) {
+    const int M = 2 * L + 1, N = n * (L > 0 ? L : 1);
+    const double2* hs = Hs + (size_t)blockIdx.x * M * n * n;
+    double2* o0 = H00 + (size_t)blockIdx.x * N * N;
+    double2* o1 = L > 0 ? H01 + (size_t)blockIdx.x * N * N : nullptr;
+    for (int e = (int)threadIdx.x; e < N * N; e += 256) {
+        const int I = e / N, J = e - I * N;
+        const int p = I / n, i = I - p * n, q = J / n, j = J - q * n;
+        for (int part = 0; part < (L > 0 ? 2 : 1); ++part) {
+            const int m = part == 0 ? q - p : L + q - p;
+            double sr = 0.0, si = 0.0;
+            if (part == 0 || q <= p) {
+                for (int s = 0; s < M; ++s) {
+                    const double c = tw[((size_t)(m + L) * M + s) * 2], d = tw[((size_t)(m + L) * M + s) * 2 + 1];
+                    const double2 h = hs[((size_t)s * n + i) * n + j];
+                    sr += c * h.x - d * h.y;
+                    si += c * h.y + d * h.x;
+                }
+                sr /= (double)M;
+                si /= (double)M;
+            }
+            (part == 0 ? o0 : o1)[e] = make_double2(sr, si);
+        }
+    }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+tbk_flag_row surf_lds_done_32, surf_lds_done_64;  // more than 64 KiB of dynamic LDS
+
+struct SurfShape {
+    int n = 0;             // rows of a principal layer
+    int64_t n_z = 0;
+    bool spectral = false;
+    size_t item_doubles() const { return spectral ? (size_t)n : (size_t)n * n * 2; }  // of one of the three results
+    size_t out_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * item_doubles() * sizeof(double)); }
+    size_t it_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * sizeof(int32_t)); }
+    size_t result_bytes(int64_t nk) const { return 3 * out_bytes(nk) + it_bytes(nk); }  // bottom, top, bulk, iterations
+    int64_t auto_chunk(int64_t nk) const {
+        const size_t per_k = (size_t)n_z * (3 * item_doubles() * sizeof(double) + sizeof(int32_t));
+        return std::max<int64_t>(1, std::min<int64_t>(nk, (int64_t)(SURF_CHUNK_BUDGET / per_k)));
+    }
+};
+
+int64_t surf_grid(int n, int64_t items, int n_cu) {
+    if (n > 32) return std::min<int64_t>(items, std::max(1, n_cu));  // one resident workgroup per CU, each with a workspace slot
+    return std::min<int64_t>(items, int64_t(1) << 30);
+}
+
+size_t surf_workspace_bytes(int n, int64_t items, int n_cu) {
+    return n > 32 ? (size_t)surf_grid(n, items, n_cu) * SurfGeom<64>::slot_doubles * sizeof(double) : 0;
+}
+
+template <int NP>
+int surf_launch_np(hipStream_t s, int n_cu, tbk_flag_row* done, const SurfShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_z,
+                   int64_t nkc, int max_it, unsigned long long key0, double* d_ws, char* d_res) {
+    using Geo = SurfGeom<NP>;
+    const int64_t items = nkc * sh.n_z;
+    if (done != nullptr)
+        TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(surface_decimate_kernel<NP>), (int)Geo::lds_bytes, *done));
+    double* d_b = reinterpret_cast<double*>(d_res);
+    double* d_t = reinterpret_cast<double*>(d_res + sh.out_bytes(nkc));
+    double* d_m = reinterpret_cast<double*>(d_res + 2 * sh.out_bytes(nkc));
+    int32_t* d_it = reinterpret_cast<int32_t*>(d_res + 3 * sh.out_bytes(nkc));
+    hipLaunchKernelGGL(surface_decimate_kernel<NP>, dim3((unsigned)surf_grid(sh.n, items, n_cu)), dim3(Geo::THREADS), Geo::lds_bytes, s, d_H00, d_H01,
+                       d_z, (int)sh.n_z, sh.n, items, max_it, sh.spectral ? 1 : 0, key0, d_ws, d_it, d_b, d_t, d_m,
+                       reinterpret_cast<unsigned long long*>(d_res + sh.result_bytes(nkc)));
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// The decimation of the chunk's nkc points at every energy.  d_res: bottom, top, bulk, iterations of the chunk (SurfShape's
+// offsets for nkc points) and, behind them, the status word.
+int surf_launch(hipStream_t s, int n_cu, const SurfShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_z, int64_t nkc, int max_it,
+                int64_t k0, double* d_ws, char* d_res) {
+    const unsigned long long key0 = (unsigned long long)k0 * (unsigned long long)SURF_MAX_Z;
+    if (sh.n <= 16) return surf_launch_np<16>(s, n_cu, nullptr, sh, d_H00, d_H01, d_z, nkc, max_it, key0, d_ws, d_res);
+    if (sh.n <= 32) return surf_launch_np<32>(s, n_cu, &surf_lds_done_32, sh, d_H00, d_H01, d_z, nkc, max_it, key0, d_ws, d_res);
+    return surf_launch_np<64>(s, n_cu, &surf_lds_done_64, sh, d_H00, d_H01, d_z, nkc, max_it, key0, d_ws, d_res);
+}
+
+int surf_check_common(int N, int64_t n_z, const double* z, int max_iterations, const int32_t* iterations, const double* bottom, const double* top,
+                      const double* bulk) {
+    TBK_ARG(N >= 1, "a principal layer has no rows");
+    if (N > SURF_LIB_MAX) {
+        tbk_set_error("invalid argument: a principal layer of %d rows: the decimation takes at most %d", N, SURF_LIB_MAX);
+        return TBK_ERR_ARGUMENT;
+    }
+    TBK_ARG(n_z >= 1 && n_z <= SURF_MAX_Z, "n_z must be 1 to 4096");
+    TBK_ARG(z != nullptr, "z is NULL");
+    for (int64_t i = 0; i < n_z; ++i) {
+        TBK_ARG(std::isfinite(z[2 * i]) && std::isfinite(z[2 * i + 1]), "an energy z is not finite");
+        TBK_ARG(z[2 * i + 1] != 0.0, "every z needs Im z != 0");
+    }
+    TBK_ARG(max_iterations >= 1 && max_iterations <= SURF_MAX_ITERATIONS, "max_iterations must be 1 to 4096");
+    TBK_ARG(iterations != nullptr && bottom != nullptr && top != nullptr && bulk != nullptr, "iterations / bottom / top / bulk is NULL");
+    return TBK_OK;
+}
+
+// the status word as an error: the first (point, energy) of the call that failed
+int surf_status_error(unsigned long long word, const double* z, int max_iterations) {
+    if (word == SURF_NO_FLAG) return TBK_OK;
+    const int reason = (int)(word & 1ull);
+    const unsigned long long key = word >> 1;
+    const long long point = (long long)(key / (unsigned long long)SURF_MAX_Z), zi = (long long)(key % (unsigned long long)SURF_MAX_Z);
+    if (reason == 0) {
+        tbk_set_error("Singular matrix: z - e of the decimation at k index %lld and energy %lld (z = %.17g%+.17gj)", point, zi, z[2 * zi], z[2 * zi + 1]);
+        return TBK_ERR_SINGULAR;
+    }
+    tbk_set_error("the decimation did not converge in %d iterations at k index %lld and energy %lld (z = %.17g%+.17gj)", max_iterations, point, zi,
+                  z[2 * zi], z[2 * zi + 1]);
+    return TBK_ERR_NO_CONVERGENCE;
+}
+
+// ---- above 64 rows, and on request: the library route ---------------------------------------------------------------------------------
+// The (k, z) of a chunk in lockstep, in batches of a FIXED number of members (a function of N alone; the last batch is filled with
+// dummy members, zero matrices): rocblas_zgemm_strided_batched for the six products, rocsolver_zgetrf / zgetri_strided_batched for the
+// inversions, small kernels for z - e, the sums, the norms and the results.  The batch count never changes, so the library is asked the
+// same question whatever the chunk and the list; a member that has converged gets alpha = beta = 0 exactly and later iterations add
+// exact zeros to it.  Matrices are row-major: the library reads them as their transposes, so C = A B is the library's product of B
+// and A, and the in-place inverse of a transpose is the transpose of the inverse (20.2).
+constexpr size_t SURF_LIB_BUDGET = size_t(512) << 20;
+constexpr int SURF_LIB_MATRICES = 10;  // alpha, beta, their successors, e, es, et, A (g), T, one product
+
+int surf_lib_batch(int n) {
+    const size_t per = (size_t)SURF_LIB_MATRICES * n * n * sizeof(double2);
+    return (int)std::max<size_t>(1, std::min<size_t>(64, SURF_LIB_BUDGET / per));
+}
+
+struct SurfLib {
+    rocblas_handle blas = nullptr;
+    int n = 0, batch = 0;
+    double2* mat[SURF_LIB_MATRICES] = {};
+    int* ipiv = nullptr;    // [batch][n]
+    int* info = nullptr;    // [2][batch] of getrf and getri
+    int* done = nullptr;    // [batch]
+    int* active = nullptr;  // one word: members still iterating
+    double* thr = nullptr;  // [batch]
+    static size_t bytes(int n, int batch) {
+        return (size_t)SURF_LIB_MATRICES * surf_align256((size_t)batch * n * n * sizeof(double2)) + surf_align256((size_t)batch * n * sizeof(int)) +
+               surf_align256((size_t)(3 * batch + 1) * sizeof(int)) + surf_align256((size_t)batch * sizeof(double));
+    }
+    void place(char* base, int n_, int batch_, rocblas_handle h) {
+        n = n_;
+        batch = batch_;
+        blas = h;
+        const size_t mb = surf_align256((size_t)batch * n * n * sizeof(double2));
+        for (int i = 0; i < SURF_LIB_MATRICES; ++i) mat[i] = reinterpret_cast<double2*>(base + (size_t)i * mb);
+        char* at = base + (size_t)SURF_LIB_MATRICES * mb;
+        ipiv = reinterpret_cast<int*>(at);
+        at += surf_align256((size_t)batch * n * sizeof(int));
+        info = reinterpret_cast<int*>(at);
+        done = info + 2 * batch;
+        active = done + batch;
+        at += surf_align256((size_t)(3 * batch + 1) * sizeof(int));
+        thr = reinterpret_cast<double*>(at);
+    }
+};
+
+// member b of the batch is item w0 + b of the chunk (k = item / n_z), a dummy beyond `items`
+__global__ void __launch_bounds__(256) surf_lib_load_kernel(const double2* __restrict__ H00, const double2* __restrict__ H01, int n_z, int n, int64_t w0,
+                                                            int64_t items, double2* __restrict__ al, double2* __restrict__ be, double2* __restrict__ e,
+                                                            double2* __restrict__ es, double2* __restrict__ et, int32_t* __restrict__ iters) {
+    const int b = (int)blockIdx.x;
+    const int64_t w = w0 + b;
+    const bool valid = w < items;
+    const size_t nn = (size_t)n * n, k = valid ? (size_t)(w / n_z) : 0;
+    for (size_t x = (size_t)blockIdx.y * 256 + threadIdx.x; x < nn; x += (size_t)gridDim.y * 256) {
+        const size_t i = x / n, c = x - i * n;
+        double2 a = make_double2(0.0, 0.0), h = make_double2(0.0, 0.0);
+        if (valid) {
+            a = H00[k * nn + x];
+            if (H01 != nullptr) h = H01[k * nn + x];
+        }
+        e[b * nn + x] = es[b * nn + x] = et[b * nn + x] = a;
+        al[b * nn + x] = h;
+        be[b * nn + c * n + i] = make_double2(h.x, -h.y);
+    }
+    if (valid && blockIdx.y == 0 && threadIdx.x == 0) iters[w] = 0;
+}
+
+__global__ void __launch_bounds__(256) surf_lib_form_kernel(const double2* __restrict__ M, const double2* __restrict__ z, int n_z, int n, int64_t w0,
+                                                            double2* __restrict__ A) {
+    const int b = (int)blockIdx.x;
+    const double2 zz = z[(w0 + b) % n_z];  // (a dummy member takes some energy of the list: z 1 is invertible)
+    const size_t nn = (size_t)n * n;
+    for (size_t x = (size_t)blockIdx.y * 256 + threadIdx.x; x < nn; x += (size_t)gridDim.y * 256) {
+        const size_t i = x / n, c = x - i * n;
+        const double2 m = M[b * nn + x];
+        A[b * nn + x] = make_double2((i == c ? zz.x : 0.0) - m.x, (i == c ? zz.y : 0.0) - m.y);
+    }
+}
+
+__global__ void __launch_bounds__(256) surf_lib_add_kernel(const double2* __restrict__ src, size_t count, double2* __restrict__ d1, double2* __restrict__ d2) {
+    for (size_t x = (size_t)blockIdx.x * 256 + threadIdx.x; x < count; x += (size_t)gridDim.x * 256) {
+        const double2 v = src[x];
+        double2 a = d1[x], b = d2[x];
+        a.x += v.x;
+        a.y += v.y;
+        b.x += v.x;
+        b.y += v.y;
+        d1[x] = a;
+        d2[x] = b;
+    }
+}
+
+// One workgroup per member: |alpha|_inf, |beta|_inf (row sums of |re| + |im|, a thread per row, columns ascending).  it = 0: the
+// threshold 2^-53 |H01|_inf, done cleared.  it > 0, member not done: a failed library call or a non-finite norm raises the word
+// (singular), a norm at or below the threshold ends the member, the cap raises the word; an ended member records its count and gets
+// alpha = beta = 0; the others count themselves in *active.
+__global__ void __launch_bounds__(256) surf_lib_norms_kernel(double2* al, double2* be, int n, int batch, int64_t w0, int64_t items, int n_z, int it, int max_it,
+                                                             unsigned long long key0, const int* __restrict__ info, int* done, double* thr, int* active,
+                                                             int32_t* iters, unsigned long long* flag) {
+    __shared__ double red[2][256];
+    __shared__ int verdict;
+    const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int64_t w = w0 + b;
+    const bool valid = w < items;
+    const size_t nn = (size_t)n * n;
+    double2* a = al + b * nn;
+    double2* bb = be + b * nn;
+    if (it > 0 && done[b] != 0) return;  // (the same for every thread)
+    double ma = 0.0, mb = 0.0;
+    for (int r = tid; r < n; r += 256) {
+        double sa = 0.0, sb = 0.0;
+        for (int c = 0; c < n; ++c) {
+            const double2 x = a[(size_t)r * n + c], y = bb[(size_t)r * n + c];
+            sa += fabs(x.x) + fabs(x.y);
+            sb += fabs(y.x) + fabs(y.y);
+        }
+        if (!(sa <= SURF_DBL_MAX)) sa = __builtin_inf();
+        if (!(sb <= SURF_DBL_MAX)) sb = __builtin_inf();
+        ma = sa > ma ? sa : ma;
+        mb = sb > mb ? sb : mb;
+    }
+    red[0][tid] = ma;
+    red[1][tid] = mb;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (tid < off) {
+            red[0][tid] = red[0][tid + off] > red[0][tid] ? red[0][tid + off] : red[0][tid];
+            red[1][tid] = red[1][tid + off] > red[1][tid] ? red[1][tid + off] : red[1][tid];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        int v = 0;  // 0: goes on, 1: ended
+        if (it == 0) {
+            thr[b] = red[0][0] * 0x1p-53;
+            done[b] = 0;
+        } else {
+            const double size = red[0][0] > red[1][0] ? red[0][0] : red[1][0];
+            const unsigned long long key = (key0 + (unsigned long long)(w / n_z) * (unsigned long long)SURF_MAX_Z + (unsigned long long)(w % n_z)) * 2ull;
+            if (info[b] != 0 || info[batch + b] != 0 || !(size <= SURF_DBL_MAX)) {
+                v = 1;
+                if (valid) atomicMin(flag, key);
+            } else if (size <= thr[b]) {
+                v = 1;
+            } else if (it >= max_it) {
+                v = 1;
+                if (valid) atomicMin(flag, key + 1ull);
+            } else {
+                atomicAdd(active, 1);
+            }
+            if (v == 1) {
+                done[b] = 1;
+                if (valid) iters[w] = it;
+            }
+        }
+        verdict = v;
+    }
+    __syncthreads();
+    if (verdict == 1)
+        for (size_t x = tid; x < nn; x += 256) a[x] = bb[x] = make_double2(0.0, 0.0);
+}
+
+// the closing inverses of the batch into the chunk's results
+__global__ void __launch_bounds__(256) surf_lib_out_kernel(const double2* __restrict__ A, const int* __restrict__ info, int n, int batch, int64_t w0, int64_t items,
+                                                           int n_z, int spectral, unsigned long long key0, double* __restrict__ out,
+                                                           unsigned long long* __restrict__ flag) {
+    const int b = (int)blockIdx.x;
+    const int64_t w = w0 + b;
+    if (w >= items) return;
+    const size_t nn = (size_t)n * n;
+    const double2* g = A + b * nn;
+    bool bad = info[b] != 0 || info[batch + b] != 0;
+    for (size_t x = (size_t)blockIdx.y * 256 + threadIdx.x; x < nn; x += (size_t)gridDim.y * 256) {
+        const double2 v = g[x];
+        bad |= !(fabs(v.x) <= SURF_DBL_MAX && fabs(v.y) <= SURF_DBL_MAX);
+        const size_t i = x / n, c = x - i * n;
+        if (spectral) {
+            if (i == c) out[(size_t)w * n + i] = -v.y / SURF_PI;
+        } else {
+            reinterpret_cast<double2*>(out)[(size_t)w * nn + x] = v;
+        }
+    }
+    if (bad) atomicMin(flag, (key0 + (unsigned long long)(w / n_z) * (unsigned long long)SURF_MAX_Z + (unsigned long long)(w % n_z)) * 2ull);
+}
+
+// row-major C = A B for every member
+int surf_lib_gemm(const SurfLib& W, const double2* A, const double2* B, double2* C) {
+    const rocblas_double_complex one(1.0, 0.0), zero(0.0, 0.0);
+    const rocblas_stride st = (rocblas_stride)W.n * W.n;
+    TBK_ROCBLAS(rocblas_zgemm_strided_batched(W.blas, rocblas_operation_none, rocblas_operation_none, W.n, W.n, W.n, &one,
+                                              reinterpret_cast<const rocblas_double_complex*>(B), W.n, st,
+                                              reinterpret_cast<const rocblas_double_complex*>(A), W.n, st, &zero,
+                                              reinterpret_cast<rocblas_double_complex*>(C), W.n, st, W.batch));
+    return TBK_OK;
+}
+
+// A = (z 1 - M)^-1 for every member, in place; the two status rows in W.info
+int surf_lib_invert(hipStream_t s, const SurfLib& W, const double2* M, const double2* d_z, int n_z, int64_t w0, double2* A) {
+    const unsigned gy = (unsigned)std::min<size_t>(64, ((size_t)W.n * W.n + 255) / 256);
+    hipLaunchKernelGGL(surf_lib_form_kernel, dim3((unsigned)W.batch, gy), dim3(256), 0, s, M, d_z, n_z, W.n, w0, A);
+    TBK_HIP(hipGetLastError());
+    rocblas_double_complex* a = reinterpret_cast<rocblas_double_complex*>(A);
+    const rocblas_stride st = (rocblas_stride)W.n * W.n;
+    TBK_ROCBLAS(rocsolver_zgetrf_strided_batched(W.blas, W.n, W.n, a, W.n, st, W.ipiv, (rocblas_stride)W.n, W.info, W.batch));
+    TBK_ROCBLAS(rocsolver_zgetri_strided_batched(W.blas, W.n, a, W.n, st, W.ipiv, (rocblas_stride)W.n, W.info + W.batch, W.batch));
+    return TBK_OK;
+}
+
+// The chunk's nkc points at every energy on the library route (the arguments of surf_launch).  The host reads one word per iteration
+// and batch: how many members go on.
+int surf_lib_chunk(hipStream_t s, const SurfLib& W, const SurfShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_z, int64_t nkc,
+                   int max_it, int64_t k0, char* d_res) {
+    const int n = sh.n, n_z = (int)sh.n_z;
+    const int64_t items = nkc * sh.n_z;
+    const unsigned long long key0 = (unsigned long long)k0 * (unsigned long long)SURF_MAX_Z;
+    double* outs[3] = {reinterpret_cast<double*>(d_res), reinterpret_cast<double*>(d_res + sh.out_bytes(nkc)),
+                       reinterpret_cast<double*>(d_res + 2 * sh.out_bytes(nkc))};
+    int32_t* d_it = reinterpret_cast<int32_t*>(d_res + 3 * sh.out_bytes(nkc));
+    unsigned long long* d_flag = reinterpret_cast<unsigned long long*>(d_res + sh.result_bytes(nkc));
+    const size_t count = (size_t)W.batch * n * n;
+    const unsigned gy = (unsigned)std::min<size_t>(64, ((size_t)n * n + 255) / 256);
+    const unsigned ga = (unsigned)std::min<size_t>(4096, (count + 255) / 256);
+    for (int64_t w0 = 0; w0 < items; w0 += W.batch) {
+        double2 *al = W.mat[0], *be = W.mat[1], *al2 = W.mat[2], *be2 = W.mat[3];
+        double2 *e = W.mat[4], *es = W.mat[5], *et = W.mat[6], *A = W.mat[7], *T = W.mat[8], *V = W.mat[9];
+        hipLaunchKernelGGL(surf_lib_load_kernel, dim3((unsigned)W.batch, gy), dim3(256), 0, s, d_H00, d_H01, n_z, n, w0, items, al, be, e, es, et, d_it);
+        TBK_HIP(hipGetLastError());
+        if (d_H01 != nullptr) {
+            hipLaunchKernelGGL(surf_lib_norms_kernel, dim3((unsigned)W.batch), dim3(256), 0, s, al, be, n, W.batch, w0, items, n_z, 0, max_it, key0, W.info,
+                               W.done, W.thr, W.active, d_it, d_flag);
+            TBK_HIP(hipGetLastError());
+            for (int it = 1; it <= max_it; ++it) {
+                TBK_CHECK(surf_lib_invert(s, W, e, d_z, n_z, w0, A));
+                TBK_CHECK(surf_lib_gemm(W, A, al, T));    // T = g alpha
+                TBK_CHECK(surf_lib_gemm(W, al, T, al2));  // alpha g alpha
+                TBK_CHECK(surf_lib_gemm(W, be, T, V));    // beta g alpha
+                hipLaunchKernelGGL(surf_lib_add_kernel, dim3(ga), dim3(256), 0, s, V, count, et, e);
+                TBK_CHECK(surf_lib_gemm(W, A, be, T));    // T = g beta
+                TBK_CHECK(surf_lib_gemm(W, al, T, V));    // alpha g beta
+                hipLaunchKernelGGL(surf_lib_add_kernel, dim3(ga), dim3(256), 0, s, V, count, es, e);
+                TBK_CHECK(surf_lib_gemm(W, be, T, be2));  // beta g beta
+                std::swap(al, al2);
+                std::swap(be, be2);
+                TBK_HIP(hipMemsetAsync(W.active, 0, sizeof(int), s));
+                hipLaunchKernelGGL(surf_lib_norms_kernel, dim3((unsigned)W.batch), dim3(256), 0, s, al, be, n, W.batch, w0, items, n_z, it, max_it, key0,
+                                   W.info, W.done, W.thr, W.active, d_it, d_flag);
+                TBK_HIP(hipGetLastError());
+                int active = 0;
+                TBK_HIP(hipMemcpyAsync(&active, W.active, sizeof(int), hipMemcpyDeviceToHost, s));
+                TBK_HIP(hipStreamSynchronize(s));
+                if (active == 0) break;
+            }
+        }
+        const double2* closing[3] = {es, et, e};
+        for (int which = 0; which < 3; ++which) {
+            TBK_CHECK(surf_lib_invert(s, W, closing[which], d_z, n_z, w0, A));
+            hipLaunchKernelGGL(surf_lib_out_kernel, dim3((unsigned)W.batch, gy), dim3(256), 0, s, A, W.info, n, W.batch, w0, items, n_z, sh.spectral ? 1 : 0,
+                               key0, outs[which], d_flag);
+            TBK_HIP(hipGetLastError());
+        }
+    }
+    return TBK_OK;
+}
+
+bool surf_takes_library(int n, int eigensolver) { return n > SURF_OWN_MAX || eigensolver == TBK_EIG_ROCSOLVER; }
+
+int surf_device_cus(int device) {
+    int n_cu = 0;
+    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 1) n_cu = 256;
+    return n_cu;
+}
+
+}  // namespace
+
+extern "C" int tbk_surface_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int64_t n_z, const double* z,
+                                         int max_iterations, int64_t k_chunk, int spectral, int32_t* iterations, double* bottom, double* top,
+                                         double* bulk) {
+    TBK_CHECK(surf_check_common(N, n_z, z, max_iterations, iterations, bottom, top, bulk));
+    TBK_ARG(n_k >= 1 && n_k < (int64_t(1) << 40), "n_k < 1");
+    TBK_ARG(H00 != nullptr, "H00 is NULL");
+    TBK_ARG(k_chunk >= 0, "k_chunk < 0");
+    TBK_CHECK(tetra_check_device(device));
+    SurfShape sh;
+    sh.n = N;
+    sh.n_z = n_z;
+    sh.spectral = spectral != 0;
+    const int64_t chunk = std::min<int64_t>(n_k, k_chunk > 0 ? k_chunk : sh.auto_chunk(n_k));
+    const int n_cu = surf_device_cus(device);
+    const size_t nn = (size_t)N * N, h_bytes = (size_t)chunk * nn * sizeof(double2);
+    DevBuf d_H00, d_H01, d_z, d_res, d_ws;
+    TBK_CHECK(d_H00.reserve(h_bytes));
+    if (H01 != nullptr) TBK_CHECK(d_H01.reserve(h_bytes));
+    TBK_CHECK(d_z.reserve((size_t)n_z * sizeof(double2)));
+    TBK_CHECK(d_res.reserve(sh.result_bytes(chunk) + sizeof(unsigned long long)));
+    const bool library = surf_takes_library(N, TBK_EIG_AUTO);
+    const size_t ws_bytes = library ? SurfLib::bytes(N, surf_lib_batch(N)) : surf_workspace_bytes(N, chunk * n_z, n_cu);
+    if (ws_bytes > 0) TBK_CHECK(d_ws.reserve(ws_bytes));
+    Owned<rocblas_handle, rocblas_destroy_handle> blas;
+    SurfLib W;
+    if (library) {
+        TBK_ROCBLAS(rocblas_create_handle(blas.put()));
+        W.place(d_ws.as<char>(), N, surf_lib_batch(N), blas);
+    }
+    TBK_HIP(hipMemcpy(d_z.ptr, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice));
+    unsigned long long word = SURF_NO_FLAG;
+    for (int64_t c0 = 0; c0 < n_k; c0 += chunk) {
+        const int64_t nkc = std::min(chunk, n_k - c0);
+        const size_t items = (size_t)nkc * n_z;
+        char* res = d_res.as<char>();
+        TBK_HIP(hipMemcpy(d_H00.ptr, H00 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
+        if (H01 != nullptr) TBK_HIP(hipMemcpy(d_H01.ptr, H01 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
+        TBK_HIP(hipMemset(res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long)));
+        const double2* h01 = H01 != nullptr ? d_H01.as<double2>() : nullptr;
+        if (library)
+            TBK_CHECK(surf_lib_chunk(nullptr, W, sh, d_H00.as<double2>(), h01, d_z.as<double2>(), nkc, max_iterations, c0, res));
+        else
+            TBK_CHECK(surf_launch(nullptr, n_cu, sh, d_H00.as<double2>(), h01, d_z.as<double2>(), nkc, max_iterations, c0, d_ws.as<double>(), res));
+        const size_t o = (size_t)c0 * n_z * sh.item_doubles(), ob = items * sh.item_doubles() * sizeof(double);
+        unsigned long long chunk_word = SURF_NO_FLAG;
+        TBK_HIP(hipMemcpy(bottom + o, res, ob, hipMemcpyDeviceToHost));
+        TBK_HIP(hipMemcpy(top + o, res + sh.out_bytes(nkc), ob, hipMemcpyDeviceToHost));
+        TBK_HIP(hipMemcpy(bulk + o, res + 2 * sh.out_bytes(nkc), ob, hipMemcpyDeviceToHost));
+        TBK_HIP(hipMemcpy(iterations + (size_t)c0 * n_z, res + 3 * sh.out_bytes(nkc), items * sizeof(int32_t), hipMemcpyDeviceToHost));
+        TBK_HIP(hipMemcpy(&chunk_word, res + sh.result_bytes(nkc), sizeof(chunk_word), hipMemcpyDeviceToHost));
+        word = std::min(word, chunk_word);
+    }
+    return surf_status_error(word, z, max_iterations);
+}
+
+// The whole call on one handle; k_base: the index of k[0] in the caller's list (the slabs of tbk_surface_green_multi), for the messages.
+int tbk_surface_green_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int64_t n_z, const double* z,
+                           int max_iterations, int spectral, int32_t* iterations, double* bottom, double* top, double* bulk) {
+    TBK_ARG(m != nullptr, "model is NULL");
+    TBK_LOCK(m);
+    TBK_ARG(!m->kdotp, "the surface Green's function needs a tight-binding model");
+    const int dim = m->dim, n_orb = m->n_orb;
+    TBK_ARG(axis >= 0 && axis < dim, "axis must be 0 ... dim - 1");
+    TBK_ARG(layers >= 0 && layers <= 1024, "layers must be 0 ... 1024");
+    const int L = layers, M = 2 * L + 1;
+    for (size_t r = 0; r < m->h_R.size() / (size_t)dim; ++r) {
+        const int64_t reach = std::abs((int64_t)m->h_R[r * dim + axis]);
+        if (reach > L) {
+            tbk_set_error("invalid argument: layers = %d, but a stored hopping vector reaches %lld cells along axis %d", L, (long long)reach, axis);
+            return TBK_ERR_ARGUMENT;
+        }
+    }
+    const int64_t N64 = (int64_t)n_orb * std::max(L, 1);
+    TBK_CHECK(surf_check_common((int)std::min<int64_t>(N64, 1 << 20), n_z, z, max_iterations, iterations, bottom, top, bulk));
+    TBK_ARG(nk >= 0 && nk < (int64_t(1) << 40), "nk < 0");
+    if (nk == 0) return TBK_OK;
+    TBK_ARG(k != nullptr || dim == 1, "k is NULL");
+    SurfShape sh;
+    sh.n = (int)N64;
+    sh.n_z = n_z;
+    sh.spectral = spectral != 0;
+    const int N = sh.n;
+    const size_t nn2 = (size_t)n_orb * n_orb * 2;  // doubles of one H(k)
+    // k-points per chunk: the option, else what keeps the chunk's results and its H(k) samples inside the budget
+    const int64_t by_h = std::max<int64_t>(1, (int64_t)(SURF_CHUNK_BUDGET / ((size_t)M * nn2 * sizeof(double))));
+    const int64_t chunk = std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : std::min(sh.auto_chunk(nk), by_h));
+    // (the host buffers the enqueued copies read and write, in front of the streams: they wait before these go)
+    std::vector<double> h_k, h_tw;
+    unsigned long long word = SURF_NO_FLAG;
+    try {
+        h_k.resize((size_t)nk * M * dim);
+        h_tw.resize((size_t)M * M * 2);
+    } catch (...) {
+        tbk_set_error("cannot allocate the k list");
+        return TBK_ERR_MEMORY;
+    }
+    for (int64_t i = 0; i < nk; ++i)
+        for (int j = 0; j < M; ++j) {
+            double* dst = &h_k[((size_t)i * M + j) * dim];
+            for (int d = 0, s = 0; d < dim; ++d) dst[d] = d == axis ? (double)j / (double)M : k[(size_t)i * (dim - 1) + s++];
+        }
+    const double two_pi = 6.283185307179586476925286766559;
+    for (int mm = -L; mm <= L; ++mm)
+        for (int j = 0; j < M; ++j) {
+            const int num = ((mm * j) % M + M) % M;
+            const double angle = -two_pi * (double)num / (double)M;
+            h_tw[((size_t)(mm + L) * M + j) * 2] = std::cos(angle);
+            h_tw[((size_t)(mm + L) * M + j) * 2 + 1] = std::sin(angle);
+        }
+    std::vector<unsigned long long> words;
+    try {
+        words.assign((size_t)((nk + chunk - 1) / chunk), SURF_NO_FLAG);
+    } catch (...) {
+        tbk_set_error("cannot allocate the status words");
+        return TBK_ERR_MEMORY;
+    }
+    MeshStreams streams;
+    TBK_CHECK(streams.add(m));
+    SpanRecorder* ev = &streams.used.back().ev;
+    const size_t z_bytes = surf_align256((size_t)n_z * sizeof(double2)), tw_bytes = h_tw.size() * sizeof(double);
+    const size_t layer_bytes = surf_align256((size_t)chunk * N * N * sizeof(double2));
+    const bool library = surf_takes_library(N, m->eigensolver);
+    const size_t ws_bytes = library ? SurfLib::bytes(N, surf_lib_batch(N)) : surf_workspace_bytes(N, chunk * n_z, m->n_cu);
+    TBK_CHECK(mesh_reserve(m->ws_mesh_k, h_k.size() * sizeof(double), SURF_FAMILY, "the k list with its samples along the stacking axis"));
+    TBK_CHECK(mesh_reserve(m->ws_dm_r, z_bytes + tw_bytes, SURF_FAMILY, "the energies and the twiddles"));
+    TBK_CHECK(mesh_reserve(m->ws_dm_rho, sh.result_bytes(chunk) + sizeof(unsigned long long), SURF_FAMILY, "the results of one chunk"));
+    TBK_CHECK(mesh_reserve(m->ws_dm_p, 2 * layer_bytes, SURF_FAMILY, "the principal layers of one chunk"));
+    TBK_CHECK(mesh_reserve(m->ws_pdos_u, (size_t)chunk * M * nn2 * sizeof(double), SURF_FAMILY, "H(k) of one chunk"));
+    if (ws_bytes > 0) TBK_CHECK(mesh_reserve(m->ws_mesh_work, ws_bytes, SURF_FAMILY, library ? "the library's batch" : "the workgroups' matrices"));
+    SurfLib W;
+    if (library) {
+        W.place(m->ws_mesh_work.as<char>(), N, surf_lib_batch(N), m->blas);
+        m->counters[TBK_CNT_LIBRARY_CALLS] += 1;
+    }
+    double* d_k = m->ws_mesh_k.as<double>();
+    char* d_zt = m->ws_dm_r.as<char>();
+    double* d_H = m->ws_pdos_u.as<double>();
+    double2* d_H00 = m->ws_dm_p.as<double2>();
+    double2* d_H01 = L > 0 ? reinterpret_cast<double2*>(m->ws_dm_p.as<char>() + layer_bytes) : nullptr;
+    char* d_res = m->ws_dm_rho.as<char>();
+    TBK_HIP(hipMemcpyAsync(d_k, h_k.data(), h_k.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    TBK_HIP(hipMemcpyAsync(d_zt, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice, m->stream));
+    TBK_HIP(hipMemcpyAsync(d_zt + z_bytes, h_tw.data(), tw_bytes, hipMemcpyHostToDevice, m->stream));
+    for (int64_t c0 = 0, ci = 0; c0 < nk; c0 += chunk, ++ci) {
+        const int64_t nkc = std::min(chunk, nk - c0), npts = nkc * M;
+        const size_t items = (size_t)nkc * n_z;
+        // the FULL H(k) of the chunk's samples, by the routine tbk_eigh_device uses, in pieces of its own choice
+        if (ev) ev->start(0);
+        const int64_t piece = choose_chunk(m, npts, false);
+        for (int64_t p0 = 0; p0 < npts; p0 += piece) {
+            const int64_t np = std::min(piece, npts - p0);
+            const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), np, false);
+            TBK_CHECK(chunk_h(m, plan, HK_FULL, 2, d_k + ((size_t)c0 * M + p0) * dim, nullptr, tbk_one_k_t(), d_H + (size_t)p0 * nn2));
+        }
+        hipLaunchKernelGGL(surface_layers_kernel, dim3((unsigned)nkc), dim3(256), 0, m->stream, reinterpret_cast<const double2*>(d_H),
+                           reinterpret_cast<const double*>(d_zt + z_bytes), n_orb, L, d_H00, d_H01);
+        TBK_HIP(hipGetLastError());
+        if (ev) ev->stop();
+        TBK_HIP(hipMemsetAsync(d_res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long), m->stream));
+        if (ev) ev->start(1);
+        if (library)
+            TBK_CHECK(surf_lib_chunk(m->stream, W, sh, d_H00, d_H01, reinterpret_cast<const double2*>(d_zt), nkc, max_iterations, k_base + c0, d_res));
+        else
+            TBK_CHECK(surf_launch(m->stream, m->n_cu, sh, d_H00, d_H01, reinterpret_cast<const double2*>(d_zt), nkc, max_iterations, k_base + c0,
+                                  m->ws_mesh_work.as<double>(), d_res));
+        if (ev) ev->stop();
+        if (ev) ev->start(2);
+        const size_t o = (size_t)c0 * n_z * sh.item_doubles(), ob = items * sh.item_doubles() * sizeof(double);
+        TBK_HIP(hipMemcpyAsync(bottom + o, d_res, ob, hipMemcpyDeviceToHost, m->stream));
+        TBK_HIP(hipMemcpyAsync(top + o, d_res + sh.out_bytes(nkc), ob, hipMemcpyDeviceToHost, m->stream));
+        TBK_HIP(hipMemcpyAsync(bulk + o, d_res + 2 * sh.out_bytes(nkc), ob, hipMemcpyDeviceToHost, m->stream));
+        TBK_HIP(hipMemcpyAsync(iterations + (size_t)c0 * n_z, d_res + 3 * sh.out_bytes(nkc), items * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+        TBK_HIP(hipMemcpyAsync(&words[(size_t)ci], d_res + sh.result_bytes(nkc), sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
+        if (ev) ev->stop();
+    }
+    // synchronises the handle and books the kernel times; then the status words, the smallest (point, energy) first
+    TBK_CHECK(streams.finish(TIMED_SURFACE));
+    for (unsigned long long w : words) word = std::min(word, w);
+    return surf_status_error(word, z, max_iterations);
+}
+
+extern "C" int tbk_surface_green(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int64_t n_z, const double* z, int max_iterations,
+                                 int spectral, int32_t* iterations, double* bottom, double* top, double* bulk) {
+    return tbk_surface_green_slab(m, 0, axis, layers, k, nk, n_z, z, max_iterations, spectral, iterations, bottom, top, bulk);
+}
+
+extern "C" int tbk_surface_timing(tbk_model* m, double* ms, int64_t* calls, int reset) {
+    TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr, "model / ms / calls is NULL");
+    return tbk_timed_read(m, TIMED_SURFACE, 3, ms, calls, nullptr, reset);
+}
