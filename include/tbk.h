@@ -54,7 +54,7 @@ typedef enum tbk_status {
     TBK_ERR_MEMORY = 3,   /* device allocation failed                             -> MemoryError  */
     TBK_ERR_NOT_FINITE = 4, /* NaN / Inf in H(k): scipy check_finite=True         -> ValueError   */
     TBK_ERR_NO_CONVERGENCE = 5, /* eigensolver / decimation did not converge      -> LinAlgError  */
-    TBK_ERR_SINGULAR = 6  /* tbk_green_dressed: z - H(k) - Sigma(z) is singular; tbk_surface_green: z - e is -> LinAlgError  */
+    TBK_ERR_SINGULAR = 6  /* tbk_green_dressed: z - H(k) - Sigma(z) is singular; tbk_surface_green: z - e is; tbk_transmission: z - D_p is -> LinAlgError  */
 } tbk_status;
 
 /* eigensolver selection for tbk_model_set_option(TBK_OPT_EIGENSOLVER, ...):
@@ -514,6 +514,43 @@ int tbk_surface_green_multi(tbk_model* const* handles, int n_handles, int axis, 
 /* ms[3] = the summed HIP-event time of H(k) with the principal layers, the decimation, and the copies of the results to the host in this
  * handle's calls made while TBK_OPT_TIMING was on; calls, reset as above. */
 int tbk_surface_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
+/* ---- Landauer transmission through a device of M principal layers between two semi-infinite leads (not in the reference) ------------
+ * H00, H01, N, L and the decimation with its stopping rule are those of tbk_surface_green (layers >= 1: there must be hopping along the
+ * axis).  The device is the principal layers p = 1 ... M with on-site blocks H00(kp) + V_p, V_p a Hermitian N x N matrix independent
+ * of kp and ordered in blocks as H00; H01 between neighbouring layers and towards both leads; the left lead is the crystal on the
+ * layers P <= 0, the right lead on P >= M + 1.  Per (kp, z), Im z != 0:
+ *
+ *     es, et, iterations from the decimation (without its closing inversions);  Gamma_R = i (es - es^H),  Gamma_L = i (et - et^H)
+ *     D_1 = et + V_1;  for p = 1 ... M:  (p = M: D_p += es - H00)   g_p = (z - D_p)^-1
+ *                                        P_p = g_p (p = 1),  g_p (H01^H P_{p-1}) (p > 1);   D_{p+1} = (H00 + V_{p+1}) + H01^H (g_p H01)
+ *     T = Re tr[(Gamma_R P_M) (Gamma_L P_M^H)]
+ *
+ * P_M is block (M, 1) of the resolvent of the device with both lead self-energies attached.  V: double [M][N][N][2], 1 <= M <= 4096 and
+ * at most 256 MiB, staged once per call.  Results: iterations int32 [nk][n_z], T double [nk][n_z] and, G not NULL, P_M as double
+ * [nk][n_z][N][N][2]; without G one double per (kp, z) leaves the device.  The cap of the decimation is TBK_ERR_NO_CONVERGENCE; a zero
+ * pivot or a non-finite element of any g_p or of P_M is TBK_ERR_SINGULAR; the message names the first such k index and energy.  The bits
+ * of one (kp, z) depend on nothing else.  N <= 64: one workgroup owns a (kp, z) from the first decimation step to the trace.  65 <= N <=
+ * 1024, and for a handle with TBK_OPT_EIGENSOLVER = TBK_EIG_ROCSOLVER: the lead part of tbk_surface_green's library route, then M
+ * lockstep rounds of zgetrf / zgetri and four zgemm_strided_batched (booked on TBK_CNT_LIBRARY_CALLS).  H01 NULL, layers = 0, M outside
+ * [1, 4096], V above 256 MiB and N > 1024 are TBK_ERR_ARGUMENT.
+ * Error: |T - exact| <= 4 eps scale, eps = 8 N u rho (|z| + |H00|_2 + 2 |H01|_2 + max |V_p|_2) / |Im z| (iterations + M + 1), scale =
+ * N (2 |H01|^2 |G_bottom|) (2 |H01|^2 |G_top|) |P_M|^2. */
+
+/* The kernel alone on principal layers the caller brings: H00, H01 double [n_k][N][N][2].  k_chunk: points per launch (0: from the size
+ * of the results).  Always the own kernel up to 64 rows, the library above. */
+int tbk_transmission_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, const double* V, int64_t n_z,
+                                   const double* z, int max_iterations, int64_t k_chunk, int32_t* iterations, double* T, double* G);
+/* The whole call: k, layers, the chunks and H_m as in tbk_surface_green. */
+int tbk_transmission(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z, const double* z,
+                     int max_iterations, int32_t* iterations, double* T, double* G);
+/* On several devices from one process: the slabs of tbk_hamilton_multi, every device writing its rows of the results. */
+int tbk_transmission_multi(tbk_model* const* handles, int n_handles, int axis, int layers, const double* k, int64_t nk, int M, const double* V,
+                           int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T, double* G);
+/* ms[3] = the summed HIP-event time of H(k) with the principal layers, the decimation with the sweep (one launch on the own kernel's
+ * route, so the two are not separated), and the copies of the results to the host in this handle's calls made while TBK_OPT_TIMING was
+ * on; calls, reset as above. */
+int tbk_transmission_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
 /* ---- the bare (Lindhard) static susceptibility of a uniform k mesh (not in the reference) ----------------------------------------
  * Mesh and mesh points k = (i_1 / n_1, ..., i_dim / n_dim) are those of tbk_occupations (dim 2 or 3); k+q is the mesh point with the

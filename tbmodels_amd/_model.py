@@ -46,6 +46,8 @@ Occupations = co.namedtuple("Occupations", ("mu", "orbital_occ", "band_occ", "ba
 DensityMatrix = co.namedtuple("DensityMatrix", ("mu", "R", "rho"))
 GreenFunction = co.namedtuple("GreenFunction", ("z", "R", "G"))
 SurfaceGreenFunction = co.namedtuple("SurfaceGreenFunction", ("k", "z", "layers", "iterations", "bottom", "top", "bulk"))
+Transmission = co.namedtuple("Transmission", ("k", "z", "layers", "length", "iterations", "transmission"))
+TransmissionGreen = co.namedtuple("TransmissionGreen", Transmission._fields + ("green",))
 Susceptibility = co.namedtuple("Susceptibility", ("mu", "q", "chi"))
 DynamicSusceptibility = co.namedtuple("DynamicSusceptibility", ("mu", "q", "omega", "chi"))
 OrbitalSusceptibility = co.namedtuple("OrbitalSusceptibility", ("mu", "q", "orbitals", "chi"))
@@ -1238,6 +1240,41 @@ class Model:
             )
         return GreenFunction(energies, vectors, G)
 
+    def _stacking_arguments(self, k, z, axis, max_iterations):
+        """(energies, axis index, cap, in-plane k array, L) of `surface_green_function` and `transmission`."""
+        energies = self._complex_energies_argument(z, off_axis=True)
+        try:
+            axis_index = int(axis)
+        except (TypeError, ValueError):
+            raise ValueError("axis must be an integer, got {!r}".format(axis)) from None
+        if axis_index != axis or not -self.dim <= axis_index < self.dim:
+            raise ValueError("axis must be an integer in [-{0}, {0}), got {1!r}".format(self.dim, axis))
+        axis_index %= self.dim
+        try:
+            cap = int(max_iterations)
+        except (TypeError, ValueError):
+            raise ValueError("max_iterations must be an integer from 1 to 4096, got {!r}".format(max_iterations)) from None
+        if cap != max_iterations or not 1 <= cap <= 4096:
+            raise ValueError("max_iterations must be an integer from 1 to 4096, got {!r}".format(max_iterations))
+        if self.dim == 1 and (k is None or np.shape(k) == (0,)):
+            k_array = np.zeros((1, 0), dtype=np.float64)
+        else:
+            if k is None:
+                raise ValueError("k must be an array of shape (NK, {}), got None".format(self.dim - 1))
+            k_array = np.asarray(k, dtype=np.float64)
+            if k_array.ndim == 0 and self.dim == 2:
+                k_array = k_array.reshape(1, 1)
+            elif k_array.ndim == 1 and k_array.shape[0] == self.dim - 1:
+                k_array = k_array.reshape(1, -1)
+            if k_array.ndim != 2 or k_array.shape[1] != self.dim - 1:
+                raise ValueError("k must have shape (NK, {}): in-plane points without component {}, got {}".format(
+                    self.dim - 1, axis_index, np.shape(k)))
+            k_array = np.ascontiguousarray(k_array)
+        if not np.all(np.isfinite(k_array)):
+            raise ValueError("k must be finite")
+        layers = max([abs(int(R[axis_index])) for R in self.hop] or [0])
+        return energies, axis_index, cap, k_array, layers
+
     def surface_green_function(self, k, z, *, axis=-1, spectral=False, max_iterations=64):
         """
         Surface and bulk Green's functions of the semi-infinite crystal stacked along ``axis``, by the iterative decimation of
@@ -1298,37 +1335,7 @@ class Model:
         ``alpha = beta = 0`` exactly, so its bits do not depend on its neighbours.  With several ``devices`` the k list is split as
         for ``hamilton``.
         """
-        energies = self._complex_energies_argument(z, off_axis=True)
-        try:
-            axis_index = int(axis)
-        except (TypeError, ValueError):
-            raise ValueError("axis must be an integer, got {!r}".format(axis)) from None
-        if axis_index != axis or not -self.dim <= axis_index < self.dim:
-            raise ValueError("axis must be an integer in [-{0}, {0}), got {1!r}".format(self.dim, axis))
-        axis_index %= self.dim
-        try:
-            cap = int(max_iterations)
-        except (TypeError, ValueError):
-            raise ValueError("max_iterations must be an integer from 1 to 4096, got {!r}".format(max_iterations)) from None
-        if cap != max_iterations or not 1 <= cap <= 4096:
-            raise ValueError("max_iterations must be an integer from 1 to 4096, got {!r}".format(max_iterations))
-        if self.dim == 1 and (k is None or np.shape(k) == (0,)):
-            k_array = np.zeros((1, 0), dtype=np.float64)
-        else:
-            if k is None:
-                raise ValueError("k must be an array of shape (NK, {}), got None".format(self.dim - 1))
-            k_array = np.asarray(k, dtype=np.float64)
-            if k_array.ndim == 0 and self.dim == 2:
-                k_array = k_array.reshape(1, 1)
-            elif k_array.ndim == 1 and k_array.shape[0] == self.dim - 1:
-                k_array = k_array.reshape(1, -1)
-            if k_array.ndim != 2 or k_array.shape[1] != self.dim - 1:
-                raise ValueError("k must have shape (NK, {}): in-plane points without component {}, got {}".format(
-                    self.dim - 1, axis_index, np.shape(k)))
-            k_array = np.ascontiguousarray(k_array)
-        if not np.all(np.isfinite(k_array)):
-            raise ValueError("k must be finite")
-        layers = max([abs(int(R[axis_index])) for R in self.hop] or [0])
+        energies, axis_index, cap, k_array, layers = self._stacking_arguments(k, z, axis, max_iterations)
         n_rows = self.size * max(layers, 1)
         if n_rows > 1024:
             raise ValueError("a principal layer of {} cells has {} rows: surface_green_function takes at most 1024".format(layers, n_rows))
@@ -1346,6 +1353,106 @@ class Model:
                                                    _lib.ptr(top), _lib.ptr(bulk))
             )
         return SurfaceGreenFunction(k_array, energies, layers, iterations, bottom, top, bulk)
+
+    def transmission(self, k, z, *, axis=-1, device=None, length=1, max_iterations=64, green=False):
+        """
+        The two-terminal Landauer transmission ``T(kp, z)`` through a device of ``M`` principal layers between two semi-infinite
+        leads of the crystal, stacked along ``axis``, on the GPU.  Not in the reference.
+
+        ``k``, ``z``, ``axis``, ``max_iterations`` and the error messages are those of :meth:`surface_green_function`; ``H00``,
+        ``H01``, ``N = size * L`` and the decimation with its stopping rule are its as well.  ``device`` is ``None`` --
+        ``length`` pristine layers, ``V = 0`` -- or an array ``(M, N, N)`` of Hermitian matrices ``V_p``, ordered in blocks as
+        ``H00`` and independent of ``kp``, or an array ``(M, N)`` of real on-site energies (expanded to diagonal matrices on the
+        host); ``1 <= M <= 4096``.  A ``device`` with ``max|V - V^H| > 1e-12 max|V|`` raises ``ValueError``; otherwise it is
+        passed as given.  A model without hopping along ``axis`` raises ``ValueError``.  Returns the named tuple ``(k, z, layers,
+        length, iterations, transmission[, green])``: ``length`` is ``M``, ``transmission`` is ``float64 (NK, NZ)`` and, with
+        ``green=True``, ``green`` is ``P_M`` as ``complex128 (NK, NZ, N, N)``.  Without it one double per ``(kp, z)`` leaves the
+        GPU.
+
+        Definition.  The device is the principal layers ``p = 1 ... M`` with on-site blocks ``H00(kp) + V_p``, ``H01`` between
+        neighbouring layers and towards both leads; the left lead is the crystal on the layers ``P <= 0``, the right lead on
+        ``P >= M + 1``.  Per ``(kp, z)``::
+
+            es, et, iterations      the decimation, without its closing inversions
+            Gamma_R = i (es - es^H),    Gamma_L = i (et - et^H)         es - H00, et - H00: the leads' self-energies
+            D_1 = et + V_1
+            for p = 1 ... M:    if p = M:  D_p += es - H00
+                                g_p = (z - D_p)^-1
+                                P_p = g_p  (p = 1),   g_p (H01^H P_{p-1})  (p > 1)
+                                D_{p+1} = (H00 + V_{p+1}) + H01^H (g_p H01)   (p < M)
+            T = Re tr[(Gamma_R P_M) (Gamma_L P_M^H)]
+
+        ``P_M`` is block ``(M, 1)`` of the resolvent of the device with both self-energies attached.  The order of the operations
+        is part of the definition.  The cap of the decimation and a singular ``z - D_p`` (a zero pivot, or a non-finite element of
+        a ``g_p`` or of ``P_M``) raise ``numpy.linalg.LinAlgError`` naming the k index and the energy.
+
+        Properties.  (1) Without a device potential and for ``Im z -> 0``, ``T`` is the number of right-moving bands at ``Re z``,
+        whatever ``length``; it vanishes in a gap.  (2) ``T`` at ``conj(z)`` is the transmission from the other side: that of
+        the reversed stack at ``z``; the two directions agree for ``Im z -> 0``.  (3) A barrier of growing height drives ``T`` to 0.  (4) The bits of one ``(kp, z)`` depend on
+        nothing else: not on the other points or energies, their order, the chunking, or ``green``.  (5) The mean of ``T`` over
+        ``kp`` is the conductance per cell in units of ``e^2 / h``.
+
+        Error bound, with ``u = 2^-53``, ``rho`` the growth factor of the eliminations and ``eta = |Im z|``: ``|T - exact| <= 4 eps
+        scale``, ``eps = 8 N u rho (|z| + |H00| + 2 |H01| + max |V_p|) / eta (iterations + M + 1)`` and ``scale = N (2 |H01|^2
+        |G_bottom|) (2 |H01|^2 |G_top|) |P_M|^2`` in 2-norms.
+
+        Work: ``56 N^3`` flops per iteration of the decimation and ``40 N^3`` per layer.  Up to ``N = 64`` one workgroup owns a
+        ``(kp, z)`` from the first iteration to the trace; above, to 1024, and for a model with ``TBK_OPT_EIGENSOLVER =
+        TBK_EIG_ROCSOLVER``, the decimation and the sweep run in lockstep batches on rocBLAS and rocSOLVER.  With several
+        ``devices`` the k list is split as for ``hamilton``.
+        """
+        energies, axis_index, cap, k_array, layers = self._stacking_arguments(k, z, axis, max_iterations)
+        if layers == 0:
+            raise ValueError("the model has no hopping along axis {}: there is nothing to transmit".format(axis_index))
+        n_rows = self.size * layers
+        if n_rows > 1024:
+            raise ValueError("a principal layer of {} cells has {} rows: transmission takes at most 1024".format(layers, n_rows))
+        if device is None:
+            try:
+                count = int(length)
+            except (TypeError, ValueError):
+                raise ValueError("length must be an integer from 1 to 4096, got {!r}".format(length)) from None
+            if count != length or not 1 <= count <= 4096:
+                raise ValueError("length must be an integer from 1 to 4096, got {!r}".format(length))
+            if count * n_rows * n_rows * 16 > 256 << 20:
+                raise ValueError("a device of {} layers of {} rows takes more than 256 MiB".format(count, n_rows))
+            potential = np.zeros((count, n_rows, n_rows), dtype=np.complex128)
+        else:
+            given = np.asarray(device)
+            if given.ndim == 2 and given.shape[1] == n_rows and given.shape[0] >= 1:
+                if np.iscomplexobj(given):
+                    raise ValueError("on-site energies of shape (M, {}) must be real".format(n_rows))
+                onsite = np.asarray(given, dtype=np.float64)
+                potential = np.zeros((onsite.shape[0], n_rows, n_rows), dtype=np.complex128)
+                index = np.arange(n_rows)
+                potential[:, index, index] = onsite
+            elif given.ndim == 3 and given.shape[0] >= 1 and given.shape[1:] == (n_rows, n_rows):
+                potential = np.ascontiguousarray(given, dtype=np.complex128)
+            else:
+                raise ValueError("device must have shape (M, {0}, {0}) or (M, {0}) with M >= 1, got {1}".format(n_rows, given.shape))
+            if not np.all(np.isfinite(potential.view(np.float64))):
+                raise ValueError("device must be finite")
+            if potential.shape[0] > 4096 or potential.nbytes > 256 << 20:
+                raise ValueError("device has {} layers of {} rows: at most 4096 layers and 256 MiB".format(potential.shape[0], n_rows))
+            size = float(np.abs(potential).max())
+            skew = float(np.abs(potential - np.conj(np.transpose(potential, (0, 2, 1)))).max())
+            if skew > 1e-12 * size:
+                raise ValueError("device is not Hermitian: max|V - V^H| = {:.3e}".format(skew))
+        n_k, n_z, count = k_array.shape[0], energies.shape[0], potential.shape[0]
+        iterations = np.zeros((n_k, n_z), dtype=np.int32)
+        result = np.empty((n_k, n_z), dtype=np.float64)
+        matrices = np.empty((n_k, n_z, n_rows, n_rows), dtype=np.complex128) if green else None
+        with self._call_lock:
+            # the cap reached: TBK_ERR_NO_CONVERGENCE, a singular z - D: TBK_ERR_SINGULAR -> numpy.linalg.LinAlgError
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_transmission_multi(handles, n_handles, axis_index, layers, _lib.ptr(k_array) if k_array.size else None, n_k, count,
+                                                  _lib.ptr(potential), n_z, _lib.ptr(energies), cap, _lib.ptr(iterations), _lib.ptr(result),
+                                                  _lib.ptr(matrices))
+            )
+        if green:
+            return TransmissionGreen(k_array, energies, layers, count, iterations, result, matrices)
+        return Transmission(k_array, energies, layers, count, iterations, result)
 
     def susceptibility(self, mesh, q, *, temperature, energy=None, n_electrons=None, matrix_elements=True, convention=2):
         """

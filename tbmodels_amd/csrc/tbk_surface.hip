@@ -21,6 +21,14 @@
 //                            v_mfma_f64_16x16x4_f64, four real MFMAs per complex tile and K step.  N <= 64.
 //   surf_lib_chunk           65 <= N <= 1024, and on request: the same iteration in lockstep batches of a fixed number of members on
 //                            rocblas_zgemm_strided_batched and rocsolver_zgetrf / zgetri_strided_batched, with five small kernels.
+//
+// And the Landauer transmission through a device of M principal layers between two leads of the crystal (DESIGN.md section 22,
+// tools/transport_model.py): es and et of the decimation are H00 plus the leads' self-energies, a recursive sweep over the layers
+// gives P_M = G_{M,1}, and T = Re tr[(Gamma_R P_M) (Gamma_L P_M^H)].
+//
+//   transmission_kernel      one workgroup owns one (kp, z) from the first decimation step (surf_load, surf_iterate: the loop of
+//                            surface_decimate_kernel) through one inversion and four products per layer to the trace.  N <= 64.
+//   trans_lib_chunk          65 <= N <= 1024, and on request: the lead part is surf_lib_iterate, the sweep M lockstep rounds.
 
 #include <algorithm>
 #include <cmath>
@@ -330,6 +338,144 @@ __device__ __forceinline__ void surf_form(double* xr, double* xi, const double* 
     if (tid < NP) jrow[tid] = -1;
 }
 
+// The planes of one workgroup (pitches: X, Y NP + 1; the others SurfGeom<NP>::SM) and its small tables.
+struct SurfPlanes {
+    double *xr, *xi, *yr, *yi;
+    double *alr, *ali, *ber, *bei, *er, *ei, *esr, *esi, *etr, *eti;
+    double* more;  // the matrices behind the five (the transmission's P)
+    double *red, *rown;
+    int *prow, *jrow;
+};
+
+// The planes of this workgroup: X and Y in LDS; MATS matrices (alpha, beta, e, es, et first) behind them up to NP = 32, in the
+// workgroup's slot of ws at NP = 64; then the tables.
+template <int NP, int MATS>
+__device__ __forceinline__ SurfPlanes surf_planes(double* lds, double* ws) {
+    using Geo = SurfGeom<NP>;
+    constexpr int PX = NP * Geo::S, PM = NP * Geo::SM;
+    SurfPlanes P;
+    P.xr = lds;
+    P.xi = P.xr + PX;
+    P.yr = P.xi + PX;
+    P.yi = P.yr + PX;
+    double* mats;
+    if constexpr (Geo::GLOBAL) {
+        mats = ws + (size_t)blockIdx.x * ((size_t)2 * MATS * PM);
+        P.red = P.yi + PX;
+    } else {
+        mats = P.yi + PX;
+        P.red = mats + 2 * MATS * PM;
+    }
+    P.alr = mats;
+    P.ali = mats + PM;
+    P.ber = mats + 2 * PM;
+    P.bei = mats + 3 * PM;
+    P.er = mats + 4 * PM;
+    P.ei = mats + 5 * PM;
+    P.esr = mats + 6 * PM;
+    P.esi = mats + 7 * PM;
+    P.etr = mats + 8 * PM;
+    P.eti = mats + 9 * PM;
+    P.more = mats + 10 * PM;
+    P.rown = P.red + 2 * Geo::THREADS;
+    P.prow = reinterpret_cast<int*>(P.rown + 2 * NP);
+    P.jrow = P.prow + NP;
+    return P;
+}
+
+// es = et = e = H00, alpha = H01, beta = H01^H of one in-plane point into the planes, zeros beyond n (one barrier at the end)
+template <int NP>
+__device__ __forceinline__ void surf_load(const SurfPlanes& P, const double2* h0, const double2* h1, bool hops, int n, int tid) {
+    using Geo = SurfGeom<NP>;
+    constexpr int THREADS = Geo::THREADS, SM = Geo::SM;
+    double *alr = P.alr, *ali = P.ali, *ber = P.ber, *bei = P.bei, *er = P.er, *ei = P.ei, *esr = P.esr, *esi = P.esi, *etr = P.etr, *eti = P.eti;
+#pragma unroll 2
+    for (int e = tid; e < NP * NP; e += THREADS) {
+        const int i = e / NP, c = e - i * NP;
+        double2 a = make_double2(0.0, 0.0), b = make_double2(0.0, 0.0);
+        if (i < n && c < n) {
+            a = h0[(size_t)i * n + c];
+            if (hops) b = h1[(size_t)i * n + c];
+        }
+        er[i * SM + c] = esr[i * SM + c] = etr[i * SM + c] = a.x;
+        ei[i * SM + c] = esi[i * SM + c] = eti[i * SM + c] = a.y;
+        alr[i * SM + c] = b.x;
+        ali[i * SM + c] = b.y;
+        ber[c * SM + i] = b.x;
+        bei[c * SM + i] = -b.y;
+    }
+    __syncthreads();
+}
+
+// The iteration of the header on loaded planes: the count into `it`, returns 0, 1 (singular) or 2 (the cap was reached), the same
+// on every thread.  Afterwards es and et are final, alpha, beta, e, X and Y are free.
+template <int NP>
+__device__ __forceinline__ int surf_iterate(const SurfPlanes& P, double2 zz, int n, int max_it, int tid, int& it) {
+    using Geo = SurfGeom<NP>;
+    constexpr int THREADS = Geo::THREADS, S = Geo::S, SM = Geo::SM, NT = Geo::NT;
+    const int lane = tid & 63, wave = tid >> 6;
+    double *xr = P.xr, *xi = P.xi, *yr = P.yr, *yi = P.yi;
+    double *alr = P.alr, *ali = P.ali, *ber = P.ber, *bei = P.bei, *er = P.er, *ei = P.ei, *esr = P.esr, *esi = P.esi, *etr = P.etr, *eti = P.eti;
+    double *red = P.red, *rown = P.rown;
+    int *prow = P.prow, *jrow = P.jrow;
+    int status = 0;
+    it = 0;
+    double na, nb;
+    surf_norms<NP, THREADS, SM>(alr, ali, ber, bei, tid, red, rown, na, nb);
+    const double threshold = na * 0x1p-53;
+    for (;;) {
+        ++it;
+        surf_form<NP, THREADS, SM>(xr, xi, er, ei, zz, n, tid, jrow);
+        const bool zero_pivot = surf_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
+        __syncthreads();
+#pragma unroll 2
+        for (int e = tid; e < NP * NP; e += THREADS) {  // g into Y, the permutations undone
+            const int i = e / NP, c = e - i * NP;
+            double vr = 0.0, vi = 0.0;
+            if (i < n && c < n) {
+                const int at = prow[i] * S + jrow[c];
+                vr = xr[at];
+                vi = xi[at];
+            }
+            yr[i * S + c] = vr;
+            yi[i * S + c] = vi;
+        }
+        __syncthreads();
+        surf_d4 tr[NT], ti[NT], p1r[NT], p1i[NT], p4r[NT], p4i[NT];
+        surf_product<NP, NT, S, SM>(yr, yi, alr, ali, n, wave, lane, tr, ti);  // T = g alpha
+        surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, tr, ti);
+        __syncthreads();
+        surf_product<NP, NT, SM, S>(alr, ali, xr, xi, n, wave, lane, p1r, p1i);  // alpha g alpha
+        surf_product<NP, NT, SM, S>(ber, bei, xr, xi, n, wave, lane, tr, ti);    // beta g alpha
+        surf_tiles<NP, NT, SM, true>(etr, eti, n, wave, lane, tr, ti);
+        surf_tiles<NP, NT, SM, true>(er, ei, n, wave, lane, tr, ti);
+        __syncthreads();  // T has been read
+        surf_product<NP, NT, S, SM>(yr, yi, ber, bei, n, wave, lane, tr, ti);  // T = g beta
+        surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, tr, ti);
+        __syncthreads();
+        surf_product<NP, NT, SM, S>(alr, ali, xr, xi, n, wave, lane, tr, ti);  // alpha g beta
+        surf_tiles<NP, NT, SM, true>(esr, esi, n, wave, lane, tr, ti);
+        surf_tiles<NP, NT, SM, true>(er, ei, n, wave, lane, tr, ti);
+        surf_product<NP, NT, SM, S>(ber, bei, xr, xi, n, wave, lane, p4r, p4i);  // beta g beta
+        __syncthreads();  // alpha and beta have been read
+        surf_tiles<NP, NT, SM, false>(alr, ali, n, wave, lane, p1r, p1i);
+        surf_tiles<NP, NT, SM, false>(ber, bei, n, wave, lane, p4r, p4i);
+        __syncthreads();
+        surf_norms<NP, THREADS, SM>(alr, ali, ber, bei, tid, red, rown, na, nb);
+        const double size = na > nb ? na : nb;
+        if (zero_pivot || !(size <= SURF_DBL_MAX)) {
+            status = 1;
+            break;
+        }
+        if (size <= threshold) break;
+        if (it >= max_it) {
+            status = 2;
+            break;
+        }
+    }
+    return status;
+}
+
 // H00, H01: [n_k][n][n] of the chunk's in-plane points (H01 NULL: no hopping between layers, no iteration); z: [n_z].  Item w = k n_z +
 // energy index; a workgroup takes the items blockIdx.x, blockIdx.x + gridDim.x, ...  Results per item: iterations, and bottom / top /
 // bulk as [n][n] complex or, spectral, [n] doubles -Im diag / pi.  key0: (index of the chunk's first point) * SURF_MAX_Z; the status
@@ -341,36 +487,12 @@ __global__ void __launch_bounds__(SurfGeom<NP>::THREADS)
                             int max_it, int spectral, unsigned long long key0, double* ws, int32_t* __restrict__ iters, double* __restrict__ out_b,
                             double* __restrict__ out_t, double* __restrict__ out_m, unsigned long long* __restrict__ flag) {
     using Geo = SurfGeom<NP>;
-    constexpr int THREADS = Geo::THREADS, S = Geo::S, SM = Geo::SM, NT = Geo::NT;
-    constexpr int PX = NP * S, PM = NP * SM;
+    constexpr int THREADS = Geo::THREADS, S = Geo::S, SM = Geo::SM;
     extern __shared__ double surf_lds[];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double* xr = surf_lds;
-    double* xi = xr + PX;
-    double* yr = xi + PX;
-    double* yi = yr + PX;
-    double* mats;
-    double* red;
-    if constexpr (Geo::GLOBAL) {
-        mats = ws + (size_t)blockIdx.x * Geo::slot_doubles;
-        red = yi + PX;
-    } else {
-        mats = yi + PX;
-        red = mats + 10 * PM;
-    }
-    double* alr = mats;
-    double* ali = mats + PM;
-    double* ber = mats + 2 * PM;
-    double* bei = mats + 3 * PM;
-    double* er = mats + 4 * PM;
-    double* ei = mats + 5 * PM;
-    double* esr = mats + 6 * PM;
-    double* esi = mats + 7 * PM;
-    double* etr = mats + 8 * PM;
-    double* eti = mats + 9 * PM;
-    double* rown = red + 2 * THREADS;
-    int* prow = reinterpret_cast<int*>(rown + 2 * NP);
-    int* jrow = prow + NP;
+    const int tid = (int)threadIdx.x;
+    const SurfPlanes P = surf_planes<NP, 5>(surf_lds, ws);
+    double *xr = P.xr, *xi = P.xi, *er = P.er, *ei = P.ei, *esr = P.esr, *esi = P.esi, *etr = P.etr, *eti = P.eti;
+    int *prow = P.prow, *jrow = P.jrow;
 
     for (int64_t w = blockIdx.x; w < items; w += gridDim.x) {
         const int64_t k = w / n_z;
@@ -379,78 +501,9 @@ __global__ void __launch_bounds__(SurfGeom<NP>::THREADS)
         const double2* h0 = H00 + (size_t)k * n * n;
         const bool hops = H01 != nullptr;
         const double2* h1 = hops ? H01 + (size_t)k * n * n : H00;
-#pragma unroll 2
-        for (int e = tid; e < NP * NP; e += THREADS) {
-            const int i = e / NP, c = e - i * NP;
-            double2 a = make_double2(0.0, 0.0), b = make_double2(0.0, 0.0);
-            if (i < n && c < n) {
-                a = h0[(size_t)i * n + c];
-                if (hops) b = h1[(size_t)i * n + c];
-            }
-            er[i * SM + c] = esr[i * SM + c] = etr[i * SM + c] = a.x;
-            ei[i * SM + c] = esi[i * SM + c] = eti[i * SM + c] = a.y;
-            alr[i * SM + c] = b.x;
-            ali[i * SM + c] = b.y;
-            ber[c * SM + i] = b.x;
-            bei[c * SM + i] = -b.y;
-        }
-        __syncthreads();
+        surf_load<NP>(P, h0, h1, hops, n, tid);
         int it = 0, status = 0;  // status 1: singular, 2: the cap was reached (the same on every thread)
-        if (hops) {
-            double na, nb;
-            surf_norms<NP, THREADS, SM>(alr, ali, ber, bei, tid, red, rown, na, nb);
-            const double threshold = na * 0x1p-53;
-            for (;;) {
-                ++it;
-                surf_form<NP, THREADS, SM>(xr, xi, er, ei, zz, n, tid, jrow);
-                const bool zero_pivot = surf_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
-                __syncthreads();
-#pragma unroll 2
-                for (int e = tid; e < NP * NP; e += THREADS) {  // g into Y, the permutations undone
-                    const int i = e / NP, c = e - i * NP;
-                    double vr = 0.0, vi = 0.0;
-                    if (i < n && c < n) {
-                        const int at = prow[i] * S + jrow[c];
-                        vr = xr[at];
-                        vi = xi[at];
-                    }
-                    yr[i * S + c] = vr;
-                    yi[i * S + c] = vi;
-                }
-                __syncthreads();
-                surf_d4 tr[NT], ti[NT], p1r[NT], p1i[NT], p4r[NT], p4i[NT];
-                surf_product<NP, NT, S, SM>(yr, yi, alr, ali, n, wave, lane, tr, ti);  // T = g alpha
-                surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, tr, ti);
-                __syncthreads();
-                surf_product<NP, NT, SM, S>(alr, ali, xr, xi, n, wave, lane, p1r, p1i);  // alpha g alpha
-                surf_product<NP, NT, SM, S>(ber, bei, xr, xi, n, wave, lane, tr, ti);    // beta g alpha
-                surf_tiles<NP, NT, SM, true>(etr, eti, n, wave, lane, tr, ti);
-                surf_tiles<NP, NT, SM, true>(er, ei, n, wave, lane, tr, ti);
-                __syncthreads();  // T has been read
-                surf_product<NP, NT, S, SM>(yr, yi, ber, bei, n, wave, lane, tr, ti);  // T = g beta
-                surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, tr, ti);
-                __syncthreads();
-                surf_product<NP, NT, SM, S>(alr, ali, xr, xi, n, wave, lane, tr, ti);  // alpha g beta
-                surf_tiles<NP, NT, SM, true>(esr, esi, n, wave, lane, tr, ti);
-                surf_tiles<NP, NT, SM, true>(er, ei, n, wave, lane, tr, ti);
-                surf_product<NP, NT, SM, S>(ber, bei, xr, xi, n, wave, lane, p4r, p4i);  // beta g beta
-                __syncthreads();  // alpha and beta have been read
-                surf_tiles<NP, NT, SM, false>(alr, ali, n, wave, lane, p1r, p1i);
-                surf_tiles<NP, NT, SM, false>(ber, bei, n, wave, lane, p4r, p4i);
-                __syncthreads();
-                surf_norms<NP, THREADS, SM>(alr, ali, ber, bei, tid, red, rown, na, nb);
-                const double size = na > nb ? na : nb;
-                if (zero_pivot || !(size <= SURF_DBL_MAX)) {
-                    status = 1;
-                    break;
-                }
-                if (size <= threshold) break;
-                if (it >= max_it) {
-                    status = 2;
-                    break;
-                }
-            }
-        }
+        if (hops) status = surf_iterate<NP>(P, zz, n, max_it, tid, it);
         bool bad = status == 1;
 #pragma unroll 1
         for (int which = 0; which < 3; ++which) {
@@ -475,6 +528,224 @@ __global__ void __launch_bounds__(SurfGeom<NP>::THREADS)
             __syncthreads();  // X and the tables are free again
         }
         if (tid == 0) iters[w] = it;
+        const unsigned long long key = (key0 + (unsigned long long)k * (unsigned long long)SURF_MAX_Z + (unsigned long long)zi) * 2ull;
+        if (bad) atomicMin(flag, key);
+        if (status == 2 && tid == 0) atomicMin(flag, key + 1ull);
+    }
+}
+
+// ---- the transmission (tools/transport_model.py) ----------------------------------------------------------------
+//   D_1 = et + V_1;  for p = 1 ... M:  (p = M: D_p += es - H00)  g_p = (z - D_p)^-1,  P_p = g_p (p = 1), g_p (H01^H P_{p-1}) (p > 1),
+//   D_{p+1} = (H00 + V_{p+1}) + H01^H (g_p H01);   T = Re tr[(Gamma_R P_M) (Gamma_L P_M^H)],  Gamma = i (e - e^H) of es and et.
+// After the decimation alpha, beta and e are dead: their planes take H01, H01^H (the prologue's loads again) and D; P is a sixth
+// matrix behind et (LDS up to NP = 32: 140 032 bytes there; the slot of 12 planes at NP = 64).
+template <int NP>
+struct TransGeom {
+    using Geo = SurfGeom<NP>;
+    static constexpr int MATS = 6;
+    static constexpr size_t lds_bytes = Geo::lds_bytes + (Geo::GLOBAL ? 0 : (size_t)2 * NP * Geo::S * sizeof(double));
+    static constexpr size_t slot_doubles = Geo::GLOBAL ? (size_t)2 * MATS * NP * NP : 0;
+};
+
+// the wave's tiles of a product into D = (H00 + V) + product (zero beyond n); h0, v: [n][n] in global memory, read once
+template <int NP, int NT, int SD>
+__device__ __forceinline__ void trans_tiles_onsite(double* dr, double* di, const double2* __restrict__ h0, const double2* __restrict__ v, int n, int wave,
+                                                   int lane, const surf_d4 (&cr)[NT], const surf_d4 (&ci)[NT]) {
+    constexpr int TR = NP / 16;
+    lane = surf_fresh(lane);
+    const int q = lane >> 4, c16 = lane & 15;
+    const int tr = (wave * NT) / TR, tc0 = (wave * NT) % TR;
+    if (tr * 16 >= n) return;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        if ((tc0 + t) * 16 < n) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = tr * 16 + q + 4 * r, c = (tc0 + t) * 16 + c16;
+                double vr = 0.0, vi = 0.0;
+                if (i < n && c < n) {
+                    const double2 a = h0[(size_t)i * n + c], b = v[(size_t)i * n + c];
+                    vr = (a.x + b.x) + cr[t][r];
+                    vi = (a.y + b.y) + ci[t][r];
+                }
+                dr[i * SD + c] = vr;
+                di[i * SD + c] = vi;
+            }
+        }
+    }
+}
+
+// H00, H01, z, items, key0, ws, iters, flag: surface_decimate_kernel's (H01 is not NULL).  V: [m_layers][n][n], the same for every item.
+// One workgroup owns an item from the first decimation step to the trace: T_out[item], and P_M [n][n] into G_out unless it is NULL.
+// Status: a zero pivot or a non-finite element of a g_p or of P_M is reason 0, the cap of the decimation reason 1.  Every branch is
+// workgroup-uniform; no index depends on a value but through the pivot tables.
+template <int NP>
+__global__ void __launch_bounds__(SurfGeom<NP>::THREADS)
+    transmission_kernel(const double2* __restrict__ H00, const double2* __restrict__ H01, const double2* __restrict__ V, int m_layers,
+                        const double2* __restrict__ z, int n_z, int n, int64_t items, int max_it, unsigned long long key0, double* ws,
+                        int32_t* __restrict__ iters, double* __restrict__ T_out, double2* __restrict__ G_out, unsigned long long* __restrict__ flag) {
+    using Geo = SurfGeom<NP>;
+    constexpr int THREADS = Geo::THREADS, S = Geo::S, SM = Geo::SM, NT = Geo::NT;
+    constexpr int PM = NP * SM;
+    extern __shared__ double surf_lds[];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const SurfPlanes P = surf_planes<NP, TransGeom<NP>::MATS>(surf_lds, ws);
+    double *xr = P.xr, *xi = P.xi, *yr = P.yr, *yi = P.yi;
+    double *h01r = P.alr, *h01i = P.ali, *h10r = P.ber, *h10i = P.bei, *dr = P.er, *di = P.ei, *esr = P.esr, *esi = P.esi, *etr = P.etr, *eti = P.eti;
+    double *pr = P.more, *pi = P.more + PM;
+    double *red = P.red, *rown = P.rown;
+    int *prow = P.prow, *jrow = P.jrow;
+
+    for (int64_t w = blockIdx.x; w < items; w += gridDim.x) {
+        const int64_t k = w / n_z;
+        const int zi = (int)(w - k * n_z);
+        const double2 zz = z[zi];
+        const double2* h0 = H00 + (size_t)k * n * n;
+        const double2* h1 = H01 + (size_t)k * n * n;
+        surf_load<NP>(P, h0, h1, true, n, tid);
+        int it = 0;
+        const int status = surf_iterate<NP>(P, zz, n, max_it, tid, it);  // 1: singular, 2: the cap (the same on every thread)
+        bool bad = status == 1;
+#pragma unroll 2
+        for (int e = tid; e < NP * NP; e += THREADS) {  // H01 and H01^H again; D_1 = et + V_1
+            const int i = e / NP, c = e - i * NP;
+            double2 b = make_double2(0.0, 0.0), d = make_double2(0.0, 0.0);
+            if (i < n && c < n) {
+                b = h1[(size_t)i * n + c];
+                const double2 v = V[(size_t)i * n + c];
+                d = make_double2(etr[i * SM + c] + v.x, eti[i * SM + c] + v.y);
+            }
+            h01r[i * SM + c] = b.x;
+            h01i[i * SM + c] = b.y;
+            h10r[c * SM + i] = b.x;
+            h10i[c * SM + i] = -b.y;
+            dr[i * SM + c] = d.x;
+            di[i * SM + c] = d.y;
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int p = 0; p < m_layers; ++p) {
+            if (p == m_layers - 1) {  // the right lead: D_M += es - H00 (the elements surf_form gives this thread)
+#pragma unroll 2
+                for (int e = tid; e < NP * NP; e += THREADS) {
+                    const int i = e / NP, c = e - i * NP;
+                    if (i < n && c < n) {
+                        const double2 a = h0[(size_t)i * n + c];
+                        dr[i * SM + c] += esr[i * SM + c] - a.x;
+                        di[i * SM + c] += esi[i * SM + c] - a.y;
+                    }
+                }
+            }
+            surf_form<NP, THREADS, SM>(xr, xi, dr, di, zz, n, tid, jrow);
+            bad |= surf_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
+            __syncthreads();
+#pragma unroll 2
+            for (int e = tid; e < NP * NP; e += THREADS) {  // g_p into Y, the permutations undone
+                const int i = e / NP, c = e - i * NP;
+                double vr = 0.0, vi = 0.0;
+                if (i < n && c < n) {
+                    const int at = prow[i] * S + jrow[c];
+                    vr = xr[at];
+                    vi = xi[at];
+                    bad |= !(fabs(vr) <= SURF_DBL_MAX && fabs(vi) <= SURF_DBL_MAX);
+                }
+                yr[i * S + c] = vr;
+                yi[i * S + c] = vi;
+                if (p == 0) {  // P_1 = g_1
+                    pr[i * SM + c] = vr;
+                    pi[i * SM + c] = vi;
+                }
+            }
+            __syncthreads();
+            surf_d4 cr[NT], ci[NT];
+            if (p > 0) {
+                surf_product<NP, NT, SM, SM>(h10r, h10i, pr, pi, n, wave, lane, cr, ci);  // T = H01^H P_{p-1}
+                surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
+                __syncthreads();
+                surf_product<NP, NT, S, S>(yr, yi, xr, xi, n, wave, lane, cr, ci);  // P_p = g_p T
+                surf_tiles<NP, NT, SM, false>(pr, pi, n, wave, lane, cr, ci);
+                __syncthreads();  // T has been read
+            }
+            if (p + 1 < m_layers) {
+                surf_product<NP, NT, S, SM>(yr, yi, h01r, h01i, n, wave, lane, cr, ci);  // T = g_p H01
+                surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
+                __syncthreads();
+                surf_product<NP, NT, SM, S>(h10r, h10i, xr, xi, n, wave, lane, cr, ci);  // H01^H g_p H01
+                trans_tiles_onsite<NP, NT, SM>(dr, di, h0, V + (size_t)(p + 1) * n * n, n, wave, lane, cr, ci);
+                __syncthreads();
+            }
+        }
+        double2* g_out = G_out != nullptr ? G_out + (size_t)w * n * n : nullptr;
+#pragma unroll 2
+        for (int e = tid; e < NP * NP; e += THREADS) {  // Gamma_R into X, P_M^H into D's planes; P_M is looked at and leaves
+            const int i = e / NP, c = e - i * NP;
+            double gr = 0.0, gi = 0.0, ar = 0.0, ai = 0.0;
+            if (i < n && c < n) {
+                gr = -(esi[i * SM + c] + esi[c * SM + i]);
+                gi = esr[i * SM + c] - esr[c * SM + i];
+                ar = pr[c * SM + i];
+                ai = -pi[c * SM + i];
+                const double2 v = make_double2(pr[i * SM + c], pi[i * SM + c]);
+                bad |= !(fabs(v.x) <= SURF_DBL_MAX && fabs(v.y) <= SURF_DBL_MAX);
+                if (g_out != nullptr) g_out[(size_t)i * n + c] = v;
+            }
+            xr[i * S + c] = gr;
+            xi[i * S + c] = gi;
+            dr[i * SM + c] = ar;
+            di[i * SM + c] = ai;
+        }
+        __syncthreads();
+        {
+            surf_d4 cr[NT], ci[NT];
+            surf_product<NP, NT, S, SM>(xr, xi, pr, pi, n, wave, lane, cr, ci);  // Gamma_R P_M into Y
+            surf_tiles<NP, NT, S, false>(yr, yi, n, wave, lane, cr, ci);
+            __syncthreads();  // Gamma_R has been read
+#pragma unroll 2
+            for (int e = tid; e < NP * NP; e += THREADS) {  // Gamma_L into X
+                const int i = e / NP, c = e - i * NP;
+                double gr = 0.0, gi = 0.0;
+                if (i < n && c < n) {
+                    gr = -(eti[i * SM + c] + eti[c * SM + i]);
+                    gi = etr[i * SM + c] - etr[c * SM + i];
+                }
+                xr[i * S + c] = gr;
+                xi[i * S + c] = gi;
+            }
+            __syncthreads();
+            surf_product<NP, NT, S, SM>(xr, xi, dr, di, n, wave, lane, cr, ci);  // Gamma_L P_M^H into X
+            __syncthreads();  // Gamma_L has been read
+            surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
+            __syncthreads();
+        }
+        {
+            // Re sum_ij Y[i][j] X[j][i] in a fixed order: a thread sums NP / PARTS columns of its row, the first NP threads add the
+            // parts in order, thread 0 the rows
+            constexpr int PARTS = THREADS / NP, CPP = NP / PARTS;
+            const int row = tid & (NP - 1), part = tid / NP;
+            double sum = 0.0;
+#pragma unroll 4
+            for (int cc = 0; cc < CPP; ++cc) {
+                const int c = part * CPP + cc;
+                if (row < n && c < n) sum += yr[row * S + c] * xr[c * S + row] - yi[row * S + c] * xi[c * S + row];
+            }
+            red[tid] = sum;
+            __syncthreads();
+            if (tid < NP) {
+                double a = 0.0;
+#pragma unroll
+                for (int q = 0; q < PARTS; ++q) a += red[q * NP + tid];
+                rown[tid] = a;
+            }
+            __syncthreads();
+            if (tid == 0) {
+                double total = 0.0;
+#pragma unroll 4
+                for (int r = 0; r < NP; ++r) total += rown[r];
+                T_out[w] = total;
+                iters[w] = it;
+            }
+            __syncthreads();  // the tables are free again
+        }
         const unsigned long long key = (key0 + (unsigned long long)k * (unsigned long long)SURF_MAX_Z + (unsigned long long)zi) * 2ull;
         if (bad) atomicMin(flag, key);
         if (status == 2 && tid == 0) atomicMin(flag, key + 1ull);
@@ -565,8 +836,8 @@ int surf_launch(hipStream_t s, int n_cu, const SurfShape& sh, const double2* d_H
     return surf_launch_np<64>(s, n_cu, &surf_lds_done_64, sh, d_H00, d_H01, d_z, nkc, max_it, key0, d_ws, d_res);
 }
 
-int surf_check_common(int N, int64_t n_z, const double* z, int max_iterations, const int32_t* iterations, const double* bottom, const double* top,
-                      const double* bulk) {
+// what every call checks of its sizes, energies and cap
+int surf_check_energies(int N, int64_t n_z, const double* z, int max_iterations) {
     TBK_ARG(N >= 1, "a principal layer has no rows");
     if (N > SURF_LIB_MAX) {
         tbk_set_error("invalid argument: a principal layer of %d rows: the decimation takes at most %d", N, SURF_LIB_MAX);
@@ -579,18 +850,24 @@ int surf_check_common(int N, int64_t n_z, const double* z, int max_iterations, c
         TBK_ARG(z[2 * i + 1] != 0.0, "every z needs Im z != 0");
     }
     TBK_ARG(max_iterations >= 1 && max_iterations <= SURF_MAX_ITERATIONS, "max_iterations must be 1 to 4096");
+    return TBK_OK;
+}
+
+int surf_check_common(int N, int64_t n_z, const double* z, int max_iterations, const int32_t* iterations, const double* bottom, const double* top,
+                      const double* bulk) {
+    TBK_CHECK(surf_check_energies(N, n_z, z, max_iterations));
     TBK_ARG(iterations != nullptr && bottom != nullptr && top != nullptr && bulk != nullptr, "iterations / bottom / top / bulk is NULL");
     return TBK_OK;
 }
 
 // the status word as an error: the first (point, energy) of the call that failed
-int surf_status_error(unsigned long long word, const double* z, int max_iterations) {
+int surf_status_error(unsigned long long word, const double* z, int max_iterations, const char* what = "z - e of the decimation") {
     if (word == SURF_NO_FLAG) return TBK_OK;
     const int reason = (int)(word & 1ull);
     const unsigned long long key = word >> 1;
     const long long point = (long long)(key / (unsigned long long)SURF_MAX_Z), zi = (long long)(key % (unsigned long long)SURF_MAX_Z);
     if (reason == 0) {
-        tbk_set_error("Singular matrix: z - e of the decimation at k index %lld and energy %lld (z = %.17g%+.17gj)", point, zi, z[2 * zi], z[2 * zi + 1]);
+        tbk_set_error("Singular matrix: %s at k index %lld and energy %lld (z = %.17g%+.17gj)", what, point, zi, z[2 * zi], z[2 * zi + 1]);
         return TBK_ERR_SINGULAR;
     }
     tbk_set_error("the decimation did not converge in %d iterations at k index %lld and energy %lld (z = %.17g%+.17gj)", max_iterations, point, zi,
@@ -806,6 +1083,47 @@ int surf_lib_invert(hipStream_t s, const SurfLib& W, const double2* M, const dou
     return TBK_OK;
 }
 
+// The iteration of the batch that starts at item w0: afterwards es and et are in W.mat[5] and W.mat[6], e in W.mat[4]; the other
+// matrices are free.  The host reads one word per iteration: how many members go on.
+int surf_lib_iterate(hipStream_t s, const SurfLib& W, const double2* d_H00, const double2* d_H01, const double2* d_z, int n_z, int64_t items, int64_t w0,
+                     int max_it, unsigned long long key0, int32_t* d_it, unsigned long long* d_flag) {
+    const int n = W.n;
+    const size_t count = (size_t)W.batch * n * n;
+    const unsigned gy = (unsigned)std::min<size_t>(64, ((size_t)n * n + 255) / 256);
+    const unsigned ga = (unsigned)std::min<size_t>(4096, (count + 255) / 256);
+    double2 *al = W.mat[0], *be = W.mat[1], *al2 = W.mat[2], *be2 = W.mat[3];
+    double2 *e = W.mat[4], *es = W.mat[5], *et = W.mat[6], *A = W.mat[7], *T = W.mat[8], *V = W.mat[9];
+    hipLaunchKernelGGL(surf_lib_load_kernel, dim3((unsigned)W.batch, gy), dim3(256), 0, s, d_H00, d_H01, n_z, n, w0, items, al, be, e, es, et, d_it);
+    TBK_HIP(hipGetLastError());
+    if (d_H01 != nullptr) {
+        hipLaunchKernelGGL(surf_lib_norms_kernel, dim3((unsigned)W.batch), dim3(256), 0, s, al, be, n, W.batch, w0, items, n_z, 0, max_it, key0, W.info,
+                           W.done, W.thr, W.active, d_it, d_flag);
+        TBK_HIP(hipGetLastError());
+        for (int it = 1; it <= max_it; ++it) {
+            TBK_CHECK(surf_lib_invert(s, W, e, d_z, n_z, w0, A));
+            TBK_CHECK(surf_lib_gemm(W, A, al, T));    // T = g alpha
+            TBK_CHECK(surf_lib_gemm(W, al, T, al2));  // alpha g alpha
+            TBK_CHECK(surf_lib_gemm(W, be, T, V));    // beta g alpha
+            hipLaunchKernelGGL(surf_lib_add_kernel, dim3(ga), dim3(256), 0, s, V, count, et, e);
+            TBK_CHECK(surf_lib_gemm(W, A, be, T));    // T = g beta
+            TBK_CHECK(surf_lib_gemm(W, al, T, V));    // alpha g beta
+            hipLaunchKernelGGL(surf_lib_add_kernel, dim3(ga), dim3(256), 0, s, V, count, es, e);
+            TBK_CHECK(surf_lib_gemm(W, be, T, be2));  // beta g beta
+            std::swap(al, al2);
+            std::swap(be, be2);
+            TBK_HIP(hipMemsetAsync(W.active, 0, sizeof(int), s));
+            hipLaunchKernelGGL(surf_lib_norms_kernel, dim3((unsigned)W.batch), dim3(256), 0, s, al, be, n, W.batch, w0, items, n_z, it, max_it, key0,
+                               W.info, W.done, W.thr, W.active, d_it, d_flag);
+            TBK_HIP(hipGetLastError());
+            int active = 0;
+            TBK_HIP(hipMemcpyAsync(&active, W.active, sizeof(int), hipMemcpyDeviceToHost, s));
+            TBK_HIP(hipStreamSynchronize(s));
+            if (active == 0) break;
+        }
+    }
+    return TBK_OK;
+}
+
 // The chunk's nkc points at every energy on the library route (the arguments of surf_launch).  The host reads one word per iteration
 // and batch: how many members go on.
 int surf_lib_chunk(hipStream_t s, const SurfLib& W, const SurfShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_z, int64_t nkc,
@@ -817,40 +1135,10 @@ int surf_lib_chunk(hipStream_t s, const SurfLib& W, const SurfShape& sh, const d
                        reinterpret_cast<double*>(d_res + 2 * sh.out_bytes(nkc))};
     int32_t* d_it = reinterpret_cast<int32_t*>(d_res + 3 * sh.out_bytes(nkc));
     unsigned long long* d_flag = reinterpret_cast<unsigned long long*>(d_res + sh.result_bytes(nkc));
-    const size_t count = (size_t)W.batch * n * n;
     const unsigned gy = (unsigned)std::min<size_t>(64, ((size_t)n * n + 255) / 256);
-    const unsigned ga = (unsigned)std::min<size_t>(4096, (count + 255) / 256);
     for (int64_t w0 = 0; w0 < items; w0 += W.batch) {
-        double2 *al = W.mat[0], *be = W.mat[1], *al2 = W.mat[2], *be2 = W.mat[3];
-        double2 *e = W.mat[4], *es = W.mat[5], *et = W.mat[6], *A = W.mat[7], *T = W.mat[8], *V = W.mat[9];
-        hipLaunchKernelGGL(surf_lib_load_kernel, dim3((unsigned)W.batch, gy), dim3(256), 0, s, d_H00, d_H01, n_z, n, w0, items, al, be, e, es, et, d_it);
-        TBK_HIP(hipGetLastError());
-        if (d_H01 != nullptr) {
-            hipLaunchKernelGGL(surf_lib_norms_kernel, dim3((unsigned)W.batch), dim3(256), 0, s, al, be, n, W.batch, w0, items, n_z, 0, max_it, key0, W.info,
-                               W.done, W.thr, W.active, d_it, d_flag);
-            TBK_HIP(hipGetLastError());
-            for (int it = 1; it <= max_it; ++it) {
-                TBK_CHECK(surf_lib_invert(s, W, e, d_z, n_z, w0, A));
-                TBK_CHECK(surf_lib_gemm(W, A, al, T));    // T = g alpha
-                TBK_CHECK(surf_lib_gemm(W, al, T, al2));  // alpha g alpha
-                TBK_CHECK(surf_lib_gemm(W, be, T, V));    // beta g alpha
-                hipLaunchKernelGGL(surf_lib_add_kernel, dim3(ga), dim3(256), 0, s, V, count, et, e);
-                TBK_CHECK(surf_lib_gemm(W, A, be, T));    // T = g beta
-                TBK_CHECK(surf_lib_gemm(W, al, T, V));    // alpha g beta
-                hipLaunchKernelGGL(surf_lib_add_kernel, dim3(ga), dim3(256), 0, s, V, count, es, e);
-                TBK_CHECK(surf_lib_gemm(W, be, T, be2));  // beta g beta
-                std::swap(al, al2);
-                std::swap(be, be2);
-                TBK_HIP(hipMemsetAsync(W.active, 0, sizeof(int), s));
-                hipLaunchKernelGGL(surf_lib_norms_kernel, dim3((unsigned)W.batch), dim3(256), 0, s, al, be, n, W.batch, w0, items, n_z, it, max_it, key0,
-                                   W.info, W.done, W.thr, W.active, d_it, d_flag);
-                TBK_HIP(hipGetLastError());
-                int active = 0;
-                TBK_HIP(hipMemcpyAsync(&active, W.active, sizeof(int), hipMemcpyDeviceToHost, s));
-                TBK_HIP(hipStreamSynchronize(s));
-                if (active == 0) break;
-            }
-        }
+        double2 *e = W.mat[4], *es = W.mat[5], *et = W.mat[6], *A = W.mat[7];
+        TBK_CHECK(surf_lib_iterate(s, W, d_H00, d_H01, d_z, n_z, items, w0, max_it, key0, d_it, d_flag));
         const double2* closing[3] = {es, et, e};
         for (int which = 0; which < 3; ++which) {
             TBK_CHECK(surf_lib_invert(s, W, closing[which], d_z, n_z, w0, A));
@@ -870,7 +1158,440 @@ int surf_device_cus(int device) {
     return n_cu;
 }
 
+// The host lists of a whole call: per in-plane point the 2 L + 1 full k-points (k_a = j / (2 L + 1) inserted at `axis`), and the
+// twiddles of surface_layers_kernel.
+int surf_host_lists(int dim, int axis, int L, const double* k, int64_t nk, std::vector<double>& h_k, std::vector<double>& h_tw) {
+    const int M = 2 * L + 1;
+    try {
+        h_k.resize((size_t)nk * M * dim);
+        h_tw.resize((size_t)M * M * 2);
+    } catch (...) {
+        tbk_set_error("cannot allocate the k list");
+        return TBK_ERR_MEMORY;
+    }
+    for (int64_t i = 0; i < nk; ++i)
+        for (int j = 0; j < M; ++j) {
+            double* dst = &h_k[((size_t)i * M + j) * dim];
+            for (int d = 0, s = 0; d < dim; ++d) dst[d] = d == axis ? (double)j / (double)M : k[(size_t)i * (dim - 1) + s++];
+        }
+    const double two_pi = 6.283185307179586476925286766559;
+    for (int mm = -L; mm <= L; ++mm)
+        for (int j = 0; j < M; ++j) {
+            const int num = ((mm * j) % M + M) % M;
+            const double angle = -two_pi * (double)num / (double)M;
+            h_tw[((size_t)(mm + L) * M + j) * 2] = std::cos(angle);
+            h_tw[((size_t)(mm + L) * M + j) * 2 + 1] = std::sin(angle);
+        }
+    return TBK_OK;
+}
+
+// The chunk's principal layers: the FULL H(k) of its samples (d_k: the chunk's first), by the routine tbk_eigh_device uses, in pieces
+// of its own choice, then surface_layers_kernel.  Stage 0 of the call's timer.
+int surf_chunk_layers(tbk_model* m, SpanRecorder* ev, const double* d_k, int64_t nkc, int L, double* d_H, const double* d_tw, double2* d_H00,
+                      double2* d_H01) {
+    const int dim = m->dim, n_orb = m->n_orb, M = 2 * L + 1;
+    const size_t nn2 = (size_t)n_orb * n_orb * 2;
+    const int64_t npts = nkc * M;
+    if (ev) ev->start(0);
+    const int64_t piece = choose_chunk(m, npts, false);
+    for (int64_t p0 = 0; p0 < npts; p0 += piece) {
+        const int64_t np = std::min(piece, npts - p0);
+        const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), np, false);
+        TBK_CHECK(chunk_h(m, plan, HK_FULL, 2, d_k + (size_t)p0 * dim, nullptr, tbk_one_k_t(), d_H + (size_t)p0 * nn2));
+    }
+    hipLaunchKernelGGL(surface_layers_kernel, dim3((unsigned)nkc), dim3(256), 0, m->stream, reinterpret_cast<const double2*>(d_H), d_tw, n_orb, L, d_H00,
+                       d_H01);
+    TBK_HIP(hipGetLastError());
+    if (ev) ev->stop();
+    return TBK_OK;
+}
+
+// ---- the transmission: host ------------------------------------------------------------------------------------------------------------
+constexpr const char* TRANS_FAMILY = "the transmission";
+constexpr const char* TRANS_SINGULAR = "z - D of a device layer, or z - e of the decimation,";
+constexpr int TRANS_MAX_LAYERS = 4096;
+constexpr size_t TRANS_DEVICE_BUDGET = size_t(256) << 20;  // the device potential V [M][N][N] complex
+tbk_flag_row trans_lds_done_32, trans_lds_done_64;  // more than 64 KiB of dynamic LDS
+
+// The results of a chunk: T, iterations, P_M (green), and behind them the status word.
+struct TransShape {
+    int n = 0, m_layers = 0;
+    int64_t n_z = 0;
+    bool green = false;
+    size_t t_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * sizeof(double)); }
+    size_t it_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * sizeof(int32_t)); }
+    size_t g_bytes(int64_t nk) const { return green ? surf_align256((size_t)nk * n_z * n * n * sizeof(double2)) : 0; }
+    size_t result_bytes(int64_t nk) const { return t_bytes(nk) + it_bytes(nk) + g_bytes(nk); }
+    int64_t auto_chunk(int64_t nk) const {  // the chunk's results and its two layers inside the budget
+        const size_t nn = (size_t)n * n * sizeof(double2);
+        const size_t per_k = (size_t)n_z * (sizeof(double) + sizeof(int32_t) + (green ? nn : 0)) + 2 * nn;
+        return std::max<int64_t>(1, std::min<int64_t>(nk, (int64_t)(SURF_CHUNK_BUDGET / per_k)));
+    }
+};
+
+size_t trans_workspace_bytes(int n, int64_t items, int n_cu) {
+    return n > 32 ? (size_t)surf_grid(n, items, n_cu) * TransGeom<64>::slot_doubles * sizeof(double) : 0;
+}
+
+template <int NP>
+int trans_launch_np(hipStream_t s, int n_cu, tbk_flag_row* done, const TransShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_V,
+                    const double2* d_z, int64_t nkc, int max_it, unsigned long long key0, double* d_ws, char* d_res) {
+    using Geo = SurfGeom<NP>;
+    const int64_t items = nkc * sh.n_z;
+    if (done != nullptr)
+        TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(transmission_kernel<NP>), (int)TransGeom<NP>::lds_bytes, *done));
+    double* d_T = reinterpret_cast<double*>(d_res);
+    int32_t* d_it = reinterpret_cast<int32_t*>(d_res + sh.t_bytes(nkc));
+    double2* d_G = sh.green ? reinterpret_cast<double2*>(d_res + sh.t_bytes(nkc) + sh.it_bytes(nkc)) : nullptr;
+    hipLaunchKernelGGL(transmission_kernel<NP>, dim3((unsigned)surf_grid(sh.n, items, n_cu)), dim3(Geo::THREADS), TransGeom<NP>::lds_bytes, s, d_H00, d_H01,
+                       d_V, sh.m_layers, d_z, (int)sh.n_z, sh.n, items, max_it, key0, d_ws, d_it, d_T, d_G,
+                       reinterpret_cast<unsigned long long*>(d_res + sh.result_bytes(nkc)));
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// The transmission of the chunk's nkc points at every energy.  d_res: TransShape's layout for nkc points.
+int trans_launch(hipStream_t s, int n_cu, const TransShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_V, const double2* d_z,
+                 int64_t nkc, int max_it, int64_t k0, double* d_ws, char* d_res) {
+    const unsigned long long key0 = (unsigned long long)k0 * (unsigned long long)SURF_MAX_Z;
+    if (sh.n <= 16) return trans_launch_np<16>(s, n_cu, nullptr, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, d_ws, d_res);
+    if (sh.n <= 32) return trans_launch_np<32>(s, n_cu, &trans_lds_done_32, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, d_ws, d_res);
+    return trans_launch_np<64>(s, n_cu, &trans_lds_done_64, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, d_ws, d_res);
+}
+
+// ---- the library route of the transmission: the lead part is surf_lib_iterate, the sweep M lockstep rounds without convergence logic --
+// member b of the batch: H01 and H01^H again, D_1 = et + V_1 (a dummy member: zeros, so that z 1 - D is z 1)
+__global__ void __launch_bounds__(256) trans_lib_start_kernel(const double2* __restrict__ H01, const double2* __restrict__ V, const double2* __restrict__ et,
+                                                             int n_z, int n, int64_t w0, int64_t items, double2* __restrict__ h01,
+                                                             double2* __restrict__ h10, double2* __restrict__ D) {
+    const int b = (int)blockIdx.x;
+    const int64_t w = w0 + b;
+    const bool valid = w < items;
+    const size_t nn = (size_t)n * n, k = valid ? (size_t)(w / n_z) : 0;
+    for (size_t x = (size_t)blockIdx.y * 256 + threadIdx.x; x < nn; x += (size_t)gridDim.y * 256) {
+        const size_t i = x / n, c = x - i * n;
+        double2 h = make_double2(0.0, 0.0), d = make_double2(0.0, 0.0);
+        if (valid) {
+            h = H01[k * nn + x];
+            const double2 e = et[b * nn + x], v = V[x];
+            d = make_double2(e.x + v.x, e.y + v.y);
+        }
+        h01[b * nn + x] = h;
+        h10[b * nn + c * n + i] = make_double2(h.x, -h.y);
+        D[b * nn + x] = d;
+    }
+}
+
+// V NULL: D += es - H00 (the right lead, `other` is es); else D = (H00 + V) + other (`other` is H01^H g H01)
+__global__ void __launch_bounds__(256) trans_lib_onsite_kernel(const double2* __restrict__ H00, const double2* __restrict__ V, const double2* __restrict__ other,
+                                                              int n_z, int n, int64_t w0, int64_t items, double2* __restrict__ D) {
+    const int b = (int)blockIdx.x;
+    const int64_t w = w0 + b;
+    if (w >= items) return;  // (a dummy member keeps D = 0)
+    const size_t nn = (size_t)n * n, k = (size_t)(w / n_z);
+    for (size_t x = (size_t)blockIdx.y * 256 + threadIdx.x; x < nn; x += (size_t)gridDim.y * 256) {
+        const double2 a = H00[k * nn + x], o = other[b * nn + x];
+        double2 d;
+        if (V == nullptr) {
+            d = D[b * nn + x];
+            d.x += o.x - a.x;
+            d.y += o.y - a.y;
+        } else {
+            const double2 v = V[x];
+            d = make_double2((a.x + v.x) + o.x, (a.y + v.y) + o.y);
+        }
+        D[b * nn + x] = d;
+    }
+}
+
+// a failed library call (info not NULL) or a non-finite element of the member's matrix raises the word (singular)
+__global__ void __launch_bounds__(256) trans_lib_check_kernel(const double2* __restrict__ A, const int* __restrict__ info, int n, int batch, int64_t w0,
+                                                             int64_t items, int n_z, unsigned long long key0, unsigned long long* __restrict__ flag) {
+    const int b = (int)blockIdx.x;
+    const int64_t w = w0 + b;
+    if (w >= items) return;
+    const size_t nn = (size_t)n * n;
+    bool bad = info != nullptr && (info[b] != 0 || info[batch + b] != 0);
+    for (size_t x = (size_t)blockIdx.y * 256 + threadIdx.x; x < nn; x += (size_t)gridDim.y * 256) {
+        const double2 v = A[b * nn + x];
+        bad |= !(fabs(v.x) <= SURF_DBL_MAX && fabs(v.y) <= SURF_DBL_MAX);
+    }
+    if (bad) atomicMin(flag, (key0 + (unsigned long long)(w / n_z) * (unsigned long long)SURF_MAX_Z + (unsigned long long)(w % n_z)) * 2ull);
+}
+
+// gamma = i (e - e^H) and, P not NULL, adj = P^H, for every member
+__global__ void __launch_bounds__(256) trans_lib_gamma_kernel(const double2* __restrict__ e, int n, double2* __restrict__ gamma, const double2* __restrict__ P,
+                                                             double2* __restrict__ adj) {
+    const int b = (int)blockIdx.x;
+    const size_t nn = (size_t)n * n;
+    for (size_t x = (size_t)blockIdx.y * 256 + threadIdx.x; x < nn; x += (size_t)gridDim.y * 256) {
+        const size_t i = x / n, c = x - i * n;
+        const double2 u = e[b * nn + x], v = e[b * nn + c * n + i];
+        gamma[b * nn + x] = make_double2(-(u.y + v.y), u.x - v.x);
+        if (P != nullptr) {
+            const double2 q = P[b * nn + c * n + i];
+            adj[b * nn + x] = make_double2(q.x, -q.y);
+        }
+    }
+}
+
+// One workgroup per member: T = Re sum_ij A[i][j] B[j][i] in a fixed order (a thread per row, columns ascending; thread 0 adds the
+// rows in order), and P_M into G_out unless it is NULL.
+__global__ void __launch_bounds__(256) trans_lib_trace_kernel(const double2* __restrict__ A, const double2* __restrict__ B, const double2* __restrict__ P, int n,
+                                                             int64_t w0, int64_t items, double* __restrict__ T_out, double2* __restrict__ G_out) {
+    __shared__ double rows[SURF_LIB_MAX];
+    const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int64_t w = w0 + b;
+    if (w >= items) return;  // (the same for every thread)
+    const size_t nn = (size_t)n * n;
+    for (int r = tid; r < n; r += 256) {
+        double sum = 0.0;
+        for (int c = 0; c < n; ++c) {
+            const double2 x = A[b * nn + (size_t)r * n + c], y = B[b * nn + (size_t)c * n + r];
+            sum += x.x * y.x - x.y * y.y;
+        }
+        rows[r] = sum;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double total = 0.0;
+        for (int r = 0; r < n; ++r) total += rows[r];
+        T_out[w] = total;
+    }
+    if (G_out != nullptr)
+        for (size_t x = tid; x < nn; x += 256) G_out[(size_t)w * nn + x] = P[b * nn + x];
+}
+
+// The chunk's nkc points at every energy on the library route (the arguments of trans_launch)
+int trans_lib_chunk(hipStream_t s, const SurfLib& W, const TransShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_V,
+                    const double2* d_z, int64_t nkc, int max_it, int64_t k0, char* d_res) {
+    const int n = sh.n, n_z = (int)sh.n_z;
+    const int64_t items = nkc * sh.n_z;
+    const unsigned long long key0 = (unsigned long long)k0 * (unsigned long long)SURF_MAX_Z;
+    double* d_T = reinterpret_cast<double*>(d_res);
+    int32_t* d_it = reinterpret_cast<int32_t*>(d_res + sh.t_bytes(nkc));
+    double2* d_G = sh.green ? reinterpret_cast<double2*>(d_res + sh.t_bytes(nkc) + sh.it_bytes(nkc)) : nullptr;
+    unsigned long long* d_flag = reinterpret_cast<unsigned long long*>(d_res + sh.result_bytes(nkc));
+    const size_t nn = (size_t)n * n, count = (size_t)W.batch * nn;
+    const dim3 grid((unsigned)W.batch, (unsigned)std::min<size_t>(64, (nn + 255) / 256));
+    for (int64_t w0 = 0; w0 < items; w0 += W.batch) {
+        TBK_CHECK(surf_lib_iterate(s, W, d_H00, d_H01, d_z, n_z, items, w0, max_it, key0, d_it, d_flag));
+        double2 *h01 = W.mat[0], *h10 = W.mat[1], *P = W.mat[2], *Q = W.mat[3], *D = W.mat[4], *es = W.mat[5], *et = W.mat[6], *A = W.mat[7], *T = W.mat[8],
+                *R = W.mat[9];
+        hipLaunchKernelGGL(trans_lib_start_kernel, grid, dim3(256), 0, s, d_H01, d_V, et, n_z, n, w0, items, h01, h10, D);
+        TBK_HIP(hipGetLastError());
+        for (int p = 0; p < sh.m_layers; ++p) {
+            if (p == sh.m_layers - 1) hipLaunchKernelGGL(trans_lib_onsite_kernel, grid, dim3(256), 0, s, d_H00, nullptr, es, n_z, n, w0, items, D);
+            TBK_CHECK(surf_lib_invert(s, W, D, d_z, n_z, w0, A));  // g_p
+            hipLaunchKernelGGL(trans_lib_check_kernel, grid, dim3(256), 0, s, A, W.info, n, W.batch, w0, items, n_z, key0, d_flag);
+            TBK_HIP(hipGetLastError());
+            if (p == 0) {
+                TBK_HIP(hipMemcpyAsync(P, A, count * sizeof(double2), hipMemcpyDeviceToDevice, s));  // P_1 = g_1
+            } else {
+                TBK_CHECK(surf_lib_gemm(W, h10, P, T));  // T = H01^H P_{p-1}
+                TBK_CHECK(surf_lib_gemm(W, A, T, Q));    // P_p = g_p T
+                std::swap(P, Q);
+            }
+            if (p + 1 < sh.m_layers) {
+                TBK_CHECK(surf_lib_gemm(W, A, h01, T));  // T = g_p H01
+                TBK_CHECK(surf_lib_gemm(W, h10, T, R));  // H01^H g_p H01
+                hipLaunchKernelGGL(trans_lib_onsite_kernel, grid, dim3(256), 0, s, d_H00, d_V + (size_t)(p + 1) * nn, R, n_z, n, w0, items, D);
+                TBK_HIP(hipGetLastError());
+            }
+        }
+        hipLaunchKernelGGL(trans_lib_check_kernel, grid, dim3(256), 0, s, P, nullptr, n, W.batch, w0, items, n_z, key0, d_flag);
+        hipLaunchKernelGGL(trans_lib_gamma_kernel, grid, dim3(256), 0, s, es, n, T, P, Q);  // Gamma_R, P_M^H
+        TBK_HIP(hipGetLastError());
+        TBK_CHECK(surf_lib_gemm(W, T, P, R));  // Gamma_R P_M
+        hipLaunchKernelGGL(trans_lib_gamma_kernel, grid, dim3(256), 0, s, et, n, T, nullptr, nullptr);  // Gamma_L
+        TBK_HIP(hipGetLastError());
+        TBK_CHECK(surf_lib_gemm(W, T, Q, D));  // Gamma_L P_M^H
+        hipLaunchKernelGGL(trans_lib_trace_kernel, dim3((unsigned)W.batch), dim3(256), 0, s, R, D, P, n, w0, items, d_T, d_G);
+        TBK_HIP(hipGetLastError());
+    }
+    return TBK_OK;
+}
+
+// what the two entry points check of the device; M N^2 complex numbers are staged once per call
+int trans_check_device(int N, int M, const double* V, const int32_t* iterations, const double* T) {
+    TBK_ARG(M >= 1 && M <= TRANS_MAX_LAYERS, "the device must have 1 to 4096 principal layers");
+    if ((size_t)M * N * N * sizeof(double2) > TRANS_DEVICE_BUDGET) {
+        tbk_set_error("invalid argument: a device of %d layers of %d rows: V may take at most 256 MiB", M, N);
+        return TBK_ERR_ARGUMENT;
+    }
+    TBK_ARG(V != nullptr, "V is NULL");
+    TBK_ARG(iterations != nullptr && T != nullptr, "iterations / T is NULL");
+    return TBK_OK;
+}
+
 }  // namespace
+
+extern "C" int tbk_transmission_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, const double* V, int64_t n_z,
+                                              const double* z, int max_iterations, int64_t k_chunk, int32_t* iterations, double* T, double* G) {
+    TBK_CHECK(surf_check_energies(N, n_z, z, max_iterations));
+    TBK_ARG(H01 != nullptr, "H01 is NULL: the transmission needs hopping between the principal layers");
+    TBK_CHECK(trans_check_device(N, M, V, iterations, T));
+    TBK_ARG(n_k >= 1 && n_k < (int64_t(1) << 40), "n_k < 1");
+    TBK_ARG(H00 != nullptr, "H00 is NULL");
+    TBK_ARG(k_chunk >= 0, "k_chunk < 0");
+    TBK_CHECK(tetra_check_device(device));
+    TransShape sh;
+    sh.n = N;
+    sh.m_layers = M;
+    sh.n_z = n_z;
+    sh.green = G != nullptr;
+    const int64_t chunk = std::min<int64_t>(n_k, k_chunk > 0 ? k_chunk : sh.auto_chunk(n_k));
+    const int n_cu = surf_device_cus(device);
+    const size_t nn = (size_t)N * N, h_bytes = (size_t)chunk * nn * sizeof(double2), v_bytes = (size_t)M * nn * sizeof(double2);
+    DevBuf d_H00, d_H01, d_V, d_z, d_res, d_ws;
+    TBK_CHECK(d_H00.reserve(h_bytes));
+    TBK_CHECK(d_H01.reserve(h_bytes));
+    TBK_CHECK(d_V.reserve(v_bytes));
+    TBK_CHECK(d_z.reserve((size_t)n_z * sizeof(double2)));
+    TBK_CHECK(d_res.reserve(sh.result_bytes(chunk) + sizeof(unsigned long long)));
+    const bool library = surf_takes_library(N, TBK_EIG_AUTO);
+    const size_t ws_bytes = library ? SurfLib::bytes(N, surf_lib_batch(N)) : trans_workspace_bytes(N, chunk * n_z, n_cu);
+    if (ws_bytes > 0) TBK_CHECK(d_ws.reserve(ws_bytes));
+    Owned<rocblas_handle, rocblas_destroy_handle> blas;
+    SurfLib W;
+    if (library) {
+        TBK_ROCBLAS(rocblas_create_handle(blas.put()));
+        W.place(d_ws.as<char>(), N, surf_lib_batch(N), blas);
+    }
+    TBK_HIP(hipMemcpy(d_z.ptr, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice));
+    TBK_HIP(hipMemcpy(d_V.ptr, V, v_bytes, hipMemcpyHostToDevice));
+    unsigned long long word = SURF_NO_FLAG;
+    for (int64_t c0 = 0; c0 < n_k; c0 += chunk) {
+        const int64_t nkc = std::min(chunk, n_k - c0);
+        const size_t items = (size_t)nkc * n_z;
+        char* res = d_res.as<char>();
+        TBK_HIP(hipMemcpy(d_H00.ptr, H00 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
+        TBK_HIP(hipMemcpy(d_H01.ptr, H01 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
+        TBK_HIP(hipMemset(res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long)));
+        if (library)
+            TBK_CHECK(trans_lib_chunk(nullptr, W, sh, d_H00.as<double2>(), d_H01.as<double2>(), d_V.as<double2>(), d_z.as<double2>(), nkc, max_iterations, c0, res));
+        else
+            TBK_CHECK(trans_launch(nullptr, n_cu, sh, d_H00.as<double2>(), d_H01.as<double2>(), d_V.as<double2>(), d_z.as<double2>(), nkc, max_iterations, c0,
+                                   d_ws.as<double>(), res));
+        unsigned long long chunk_word = SURF_NO_FLAG;
+        TBK_HIP(hipMemcpy(T + (size_t)c0 * n_z, res, items * sizeof(double), hipMemcpyDeviceToHost));
+        TBK_HIP(hipMemcpy(iterations + (size_t)c0 * n_z, res + sh.t_bytes(nkc), items * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (sh.green)
+            TBK_HIP(hipMemcpy(G + (size_t)c0 * n_z * nn * 2, res + sh.t_bytes(nkc) + sh.it_bytes(nkc), items * nn * sizeof(double2), hipMemcpyDeviceToHost));
+        TBK_HIP(hipMemcpy(&chunk_word, res + sh.result_bytes(nkc), sizeof(chunk_word), hipMemcpyDeviceToHost));
+        word = std::min(word, chunk_word);
+    }
+    return surf_status_error(word, z, max_iterations, TRANS_SINGULAR);
+}
+
+// The whole call on one handle; k_base as in tbk_surface_green_slab.
+int tbk_transmission_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M_device, const double* V, int64_t n_z,
+                          const double* z, int max_iterations, int32_t* iterations, double* T, double* G) {
+    TBK_ARG(m != nullptr, "model is NULL");
+    TBK_LOCK(m);
+    TBK_ARG(!m->kdotp, "the transmission needs a tight-binding model");
+    const int dim = m->dim, n_orb = m->n_orb;
+    TBK_ARG(axis >= 0 && axis < dim, "axis must be 0 ... dim - 1");
+    TBK_ARG(layers >= 1 && layers <= 1024, "layers must be 1 ... 1024: the transmission needs hopping along the axis");
+    const int L = layers, M = 2 * L + 1;
+    for (size_t r = 0; r < m->h_R.size() / (size_t)dim; ++r) {
+        const int64_t reach = std::abs((int64_t)m->h_R[r * dim + axis]);
+        if (reach > L) {
+            tbk_set_error("invalid argument: layers = %d, but a stored hopping vector reaches %lld cells along axis %d", L, (long long)reach, axis);
+            return TBK_ERR_ARGUMENT;
+        }
+    }
+    const int64_t N64 = (int64_t)n_orb * L;
+    TBK_CHECK(surf_check_energies((int)std::min<int64_t>(N64, 1 << 20), n_z, z, max_iterations));
+    TransShape sh;
+    sh.n = (int)N64;
+    sh.m_layers = M_device;
+    sh.n_z = n_z;
+    sh.green = G != nullptr;
+    const int N = sh.n;
+    TBK_CHECK(trans_check_device(N, M_device, V, iterations, T));
+    TBK_ARG(nk >= 0 && nk < (int64_t(1) << 40), "nk < 0");
+    if (nk == 0) return TBK_OK;
+    TBK_ARG(k != nullptr || dim == 1, "k is NULL");
+    const size_t nn2 = (size_t)n_orb * n_orb * 2;  // doubles of one H(k)
+    const int64_t by_h = std::max<int64_t>(1, (int64_t)(SURF_CHUNK_BUDGET / ((size_t)M * nn2 * sizeof(double))));
+    const int64_t chunk = std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : std::min(sh.auto_chunk(nk), by_h));
+    // (the host buffers the enqueued copies read and write, in front of the streams: they wait before these go)
+    std::vector<double> h_k, h_tw;
+    std::vector<unsigned long long> words;
+    TBK_CHECK(surf_host_lists(dim, axis, L, k, nk, h_k, h_tw));
+    try {
+        words.assign((size_t)((nk + chunk - 1) / chunk), SURF_NO_FLAG);
+    } catch (...) {
+        tbk_set_error("cannot allocate the status words");
+        return TBK_ERR_MEMORY;
+    }
+    MeshStreams streams;
+    TBK_CHECK(streams.add(m));
+    SpanRecorder* ev = &streams.used.back().ev;
+    const size_t z_bytes = surf_align256((size_t)n_z * sizeof(double2)), tw_bytes = h_tw.size() * sizeof(double);
+    const size_t layer_bytes = surf_align256((size_t)chunk * N * N * sizeof(double2)), v_bytes = (size_t)M_device * N * N * sizeof(double2);
+    const bool library = surf_takes_library(N, m->eigensolver);
+    const size_t ws_bytes = library ? SurfLib::bytes(N, surf_lib_batch(N)) : trans_workspace_bytes(N, chunk * n_z, m->n_cu);
+    TBK_CHECK(mesh_reserve(m->ws_mesh_k, h_k.size() * sizeof(double), TRANS_FAMILY, "the k list with its samples along the stacking axis"));
+    TBK_CHECK(mesh_reserve(m->ws_dm_r, z_bytes + tw_bytes, TRANS_FAMILY, "the energies and the twiddles"));
+    TBK_CHECK(mesh_reserve(m->ws_dm_rho, sh.result_bytes(chunk) + sizeof(unsigned long long), TRANS_FAMILY, "the results of one chunk"));
+    TBK_CHECK(mesh_reserve(m->ws_dm_p, 2 * layer_bytes, TRANS_FAMILY, "the principal layers of one chunk"));
+    TBK_CHECK(mesh_reserve(m->ws_pdos_u, (size_t)chunk * M * nn2 * sizeof(double), TRANS_FAMILY, "H(k) of one chunk"));
+    TBK_CHECK(mesh_reserve(m->ws_mesh_io, v_bytes, TRANS_FAMILY, "the device potential"));
+    if (ws_bytes > 0) TBK_CHECK(mesh_reserve(m->ws_mesh_work, ws_bytes, TRANS_FAMILY, library ? "the library's batch" : "the workgroups' matrices"));
+    SurfLib W;
+    if (library) {
+        W.place(m->ws_mesh_work.as<char>(), N, surf_lib_batch(N), m->blas);
+        m->counters[TBK_CNT_LIBRARY_CALLS] += 1;
+    }
+    double* d_k = m->ws_mesh_k.as<double>();
+    char* d_zt = m->ws_dm_r.as<char>();
+    double* d_H = m->ws_pdos_u.as<double>();
+    double2* d_H00 = m->ws_dm_p.as<double2>();
+    double2* d_H01 = reinterpret_cast<double2*>(m->ws_dm_p.as<char>() + layer_bytes);
+    const double2* d_V = m->ws_mesh_io.as<double2>();
+    const double2* d_z = reinterpret_cast<const double2*>(d_zt);
+    char* d_res = m->ws_dm_rho.as<char>();
+    TBK_HIP(hipMemcpyAsync(d_k, h_k.data(), h_k.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    TBK_HIP(hipMemcpyAsync(d_zt, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice, m->stream));
+    TBK_HIP(hipMemcpyAsync(d_zt + z_bytes, h_tw.data(), tw_bytes, hipMemcpyHostToDevice, m->stream));
+    TBK_HIP(hipMemcpyAsync(m->ws_mesh_io.ptr, V, v_bytes, hipMemcpyHostToDevice, m->stream));  // once per call
+    for (int64_t c0 = 0, ci = 0; c0 < nk; c0 += chunk, ++ci) {
+        const int64_t nkc = std::min(chunk, nk - c0);
+        const size_t items = (size_t)nkc * n_z;
+        TBK_CHECK(surf_chunk_layers(m, ev, d_k + (size_t)c0 * M * dim, nkc, L, d_H, reinterpret_cast<const double*>(d_zt + z_bytes), d_H00, d_H01));
+        TBK_HIP(hipMemsetAsync(d_res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long), m->stream));
+        if (ev) ev->start(1);
+        if (library)
+            TBK_CHECK(trans_lib_chunk(m->stream, W, sh, d_H00, d_H01, d_V, d_z, nkc, max_iterations, k_base + c0, d_res));
+        else
+            TBK_CHECK(trans_launch(m->stream, m->n_cu, sh, d_H00, d_H01, d_V, d_z, nkc, max_iterations, k_base + c0, m->ws_mesh_work.as<double>(), d_res));
+        if (ev) ev->stop();
+        if (ev) ev->start(2);
+        TBK_HIP(hipMemcpyAsync(T + (size_t)c0 * n_z, d_res, items * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+        TBK_HIP(hipMemcpyAsync(iterations + (size_t)c0 * n_z, d_res + sh.t_bytes(nkc), items * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+        if (sh.green)
+            TBK_HIP(hipMemcpyAsync(G + (size_t)c0 * n_z * N * N * 2, d_res + sh.t_bytes(nkc) + sh.it_bytes(nkc), items * N * N * sizeof(double2),
+                                   hipMemcpyDeviceToHost, m->stream));
+        TBK_HIP(hipMemcpyAsync(&words[(size_t)ci], d_res + sh.result_bytes(nkc), sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
+        if (ev) ev->stop();
+    }
+    TBK_CHECK(streams.finish(TIMED_TRANSMISSION));
+    unsigned long long word = SURF_NO_FLAG;
+    for (unsigned long long w : words) word = std::min(word, w);
+    return surf_status_error(word, z, max_iterations, TRANS_SINGULAR);
+}
+
+extern "C" int tbk_transmission(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z, const double* z,
+                                int max_iterations, int32_t* iterations, double* T, double* G) {
+    return tbk_transmission_slab(m, 0, axis, layers, k, nk, M, V, n_z, z, max_iterations, iterations, T, G);
+}
+
+extern "C" int tbk_transmission_timing(tbk_model* m, double* ms, int64_t* calls, int reset) {
+    TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr, "model / ms / calls is NULL");
+    return tbk_timed_read(m, TIMED_TRANSMISSION, 3, ms, calls, nullptr, reset);
+}
 
 extern "C" int tbk_surface_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int64_t n_z, const double* z,
                                          int max_iterations, int64_t k_chunk, int spectral, int32_t* iterations, double* bottom, double* top,
@@ -961,26 +1682,7 @@ int tbk_surface_green_slab(tbk_model* m, int64_t k_base, int axis, int layers, c
     // (the host buffers the enqueued copies read and write, in front of the streams: they wait before these go)
     std::vector<double> h_k, h_tw;
     unsigned long long word = SURF_NO_FLAG;
-    try {
-        h_k.resize((size_t)nk * M * dim);
-        h_tw.resize((size_t)M * M * 2);
-    } catch (...) {
-        tbk_set_error("cannot allocate the k list");
-        return TBK_ERR_MEMORY;
-    }
-    for (int64_t i = 0; i < nk; ++i)
-        for (int j = 0; j < M; ++j) {
-            double* dst = &h_k[((size_t)i * M + j) * dim];
-            for (int d = 0, s = 0; d < dim; ++d) dst[d] = d == axis ? (double)j / (double)M : k[(size_t)i * (dim - 1) + s++];
-        }
-    const double two_pi = 6.283185307179586476925286766559;
-    for (int mm = -L; mm <= L; ++mm)
-        for (int j = 0; j < M; ++j) {
-            const int num = ((mm * j) % M + M) % M;
-            const double angle = -two_pi * (double)num / (double)M;
-            h_tw[((size_t)(mm + L) * M + j) * 2] = std::cos(angle);
-            h_tw[((size_t)(mm + L) * M + j) * 2 + 1] = std::sin(angle);
-        }
+    TBK_CHECK(surf_host_lists(dim, axis, L, k, nk, h_k, h_tw));
     std::vector<unsigned long long> words;
     try {
         words.assign((size_t)((nk + chunk - 1) / chunk), SURF_NO_FLAG);
@@ -1016,20 +1718,9 @@ int tbk_surface_green_slab(tbk_model* m, int64_t k_base, int axis, int layers, c
     TBK_HIP(hipMemcpyAsync(d_zt, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice, m->stream));
     TBK_HIP(hipMemcpyAsync(d_zt + z_bytes, h_tw.data(), tw_bytes, hipMemcpyHostToDevice, m->stream));
     for (int64_t c0 = 0, ci = 0; c0 < nk; c0 += chunk, ++ci) {
-        const int64_t nkc = std::min(chunk, nk - c0), npts = nkc * M;
+        const int64_t nkc = std::min(chunk, nk - c0);
         const size_t items = (size_t)nkc * n_z;
-        // the FULL H(k) of the chunk's samples, by the routine tbk_eigh_device uses, in pieces of its own choice
-        if (ev) ev->start(0);
-        const int64_t piece = choose_chunk(m, npts, false);
-        for (int64_t p0 = 0; p0 < npts; p0 += piece) {
-            const int64_t np = std::min(piece, npts - p0);
-            const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), np, false);
-            TBK_CHECK(chunk_h(m, plan, HK_FULL, 2, d_k + ((size_t)c0 * M + p0) * dim, nullptr, tbk_one_k_t(), d_H + (size_t)p0 * nn2));
-        }
-        hipLaunchKernelGGL(surface_layers_kernel, dim3((unsigned)nkc), dim3(256), 0, m->stream, reinterpret_cast<const double2*>(d_H),
-                           reinterpret_cast<const double*>(d_zt + z_bytes), n_orb, L, d_H00, d_H01);
-        TBK_HIP(hipGetLastError());
-        if (ev) ev->stop();
+        TBK_CHECK(surf_chunk_layers(m, ev, d_k + (size_t)c0 * M * dim, nkc, L, d_H, reinterpret_cast<const double*>(d_zt + z_bytes), d_H00, d_H01));
         TBK_HIP(hipMemsetAsync(d_res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long), m->stream));
         if (ev) ev->start(1);
         if (library)

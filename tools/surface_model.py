@@ -127,10 +127,9 @@ def _invert(a):
     return g, max(1.0, growth * scale / max(scale, float(np.abs(g).max())))
 
 
-def decimate(H00, H01, z, *, max_iterations=MAX_ITERATIONS, to_zero=False):
-    """(G_bottom, G_top, G_bulk, iterations, rho) of one (kpar, z).  rho: the largest growth factor of the inversions.  to_zero: run
-    alpha and beta down to exact zero instead of the stopping rule (the rule's test).  numpy.linalg.LinAlgError when the cap is
-    reached or an inversion is singular."""
+def decimate_terms(H00, H01, z, *, max_iterations=MAX_ITERATIONS, to_zero=False):
+    """(es, et, e, iterations, rho) of one (kpar, z): the loop of the decimation without its closing inversions -- what `decimate`
+    inverts, and what tools/transport_model.py takes the lead self-energies es - H00 and et - H00 from."""
     H00 = np.asarray(H00, dtype=np.complex128)
     N = H00.shape[0]
     one = np.eye(N)
@@ -163,6 +162,15 @@ def decimate(H00, H01, z, *, max_iterations=MAX_ITERATIONS, to_zero=False):
                 break
             if iterations >= max_iterations:
                 raise np.linalg.LinAlgError("no convergence in %d iterations" % max_iterations)
+    return es, et, e, iterations, rho
+
+
+def decimate(H00, H01, z, *, max_iterations=MAX_ITERATIONS, to_zero=False):
+    """(G_bottom, G_top, G_bulk, iterations, rho) of one (kpar, z).  rho: the largest growth factor of the inversions.  to_zero: run
+    alpha and beta down to exact zero instead of the stopping rule (the rule's test).  numpy.linalg.LinAlgError when the cap is
+    reached or an inversion is singular."""
+    es, et, e, iterations, rho = decimate_terms(H00, H01, z, max_iterations=max_iterations, to_zero=to_zero)
+    one = np.eye(es.shape[0])
     out = []
     for m in (es, et, e):
         g, growth = _invert(z * one - m)
