@@ -552,6 +552,44 @@ int tbk_transmission_multi(tbk_model* const* handles, int n_handles, int axis, i
  * on; calls, reset as above. */
 int tbk_transmission_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
+/* ---- the layer-resolved Green's functions of the device of tbk_transmission (not in the reference) -----------------------------------
+ * H00, H01, N, L, V, M, the decimation and the forward sweep with g_p, D_p, T are those of tbk_transmission, unchanged down to the order
+ * of the operations; Q_p below is its P_p.  Per (kp, z), after the forward sweep:
+ *
+ *     G_M = g_M,  C_M = g_M;   for p = M - 1 ... 1:  X = g_p H01,  Y = H01^H g_p,  G_p = g_p + (X G_{p+1}) Y,  C_p = X C_{p+1}
+ *     F_1 = G_1,  F_p = G_p (H01^H Q_{p-1}) (1 < p < M),  F_M = Q_M (M > 1)
+ *     ldos[p][i]  = -Im G_p[i][i] / pi
+ *     left[p][i]  = Re sum_j (F_p Gamma_L)[i][j] conj(F_p[i][j]) / (2 pi)        right[p][i]: C_p and Gamma_R
+ *
+ * G_p, F_p and C_p are the blocks (p, p), (p, 1) and (p, M) of the resolvent of the device with both lead self-energies attached; left
+ * and right are the parts of ldos injected from the two leads, and ldos - left - right = (Im z / pi) sum_q sum_j |G_pq[i][j]|^2.  Results:
+ * iterations int32 [nk][n_z], T double [nk][n_z] (the bits of tbk_transmission), ldos, left, right double [nk][n_z][M][N] and, G, F and C
+ * not NULL (all three or none), the blocks as double [nk][n_z][M][N][N][2].  The cap of the decimation is TBK_ERR_NO_CONVERGENCE; a zero
+ * pivot or a non-finite element of any g_p, G_p, F_p or C_p is TBK_ERR_SINGULAR; the message names the first such k index and energy.
+ * The bits of one (kp, z) depend on nothing else.  One workgroup owns a (kp, z) from the first decimation step to the last output; the
+ * forward sweep leaves g_p and H01^H Q_{p-1} on a stack of 2 M N^2 complex numbers per workgroup, as many stacks as fit 1 GiB.  N <= 64:
+ * there is no library route, and a handle with TBK_OPT_EIGENSOLVER = TBK_EIG_ROCSOLVER takes the own kernel as well.  H01 NULL,
+ * layers = 0, M outside [1, 4096], V above 256 MiB, N > 64 and a stack above 1 GiB are TBK_ERR_ARGUMENT.
+ * Error per component of a block B: eps c s, eps tbk_transmission's, c the number of error-carrying factors behind B and s the product of
+ * the 2-norms of the blocks B is formed from. */
+
+/* The kernel alone on principal layers the caller brings: H00, H01 double [n_k][N][N][2].  k_chunk: points per launch (0: from the size
+ * of the results).  slots: a cap on the workgroups and their stacks (0: as many as fit). */
+int tbk_device_green_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, const double* V, int64_t n_z,
+                                   const double* z, int max_iterations, int64_t k_chunk, int64_t slots, int32_t* iterations, double* T,
+                                   double* ldos, double* left, double* right, double* G, double* F, double* C);
+/* The whole call: k, layers, the chunks and H_m as in tbk_surface_green. */
+int tbk_device_green(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z, const double* z,
+                     int max_iterations, int32_t* iterations, double* T, double* ldos, double* left, double* right, double* G, double* F,
+                     double* C);
+/* On several devices from one process: the slabs of tbk_hamilton_multi, every device writing its rows of the results. */
+int tbk_device_green_multi(tbk_model* const* handles, int n_handles, int axis, int layers, const double* k, int64_t nk, int M, const double* V,
+                           int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T, double* ldos, double* left,
+                           double* right, double* G, double* F, double* C);
+/* ms[3] = the summed HIP-event time of H(k) with the principal layers, the decimation with both sweeps (one launch), and the copies of
+ * the results to the host in this handle's calls made while TBK_OPT_TIMING was on; calls, reset as above. */
+int tbk_device_green_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
 /* ---- the bare (Lindhard) static susceptibility of a uniform k mesh (not in the reference) ----------------------------------------
  * Mesh and mesh points k = (i_1 / n_1, ..., i_dim / n_dim) are those of tbk_occupations (dim 2 or 3); k+q is the mesh point with the
  * indices (i_d + q_d) mod n_d.  With E, U the eigenvalues and eigenvectors of tbk_eigh (convention 2), T = k_B T > 0 in the model's

@@ -48,6 +48,8 @@ GreenFunction = co.namedtuple("GreenFunction", ("z", "R", "G"))
 SurfaceGreenFunction = co.namedtuple("SurfaceGreenFunction", ("k", "z", "layers", "iterations", "bottom", "top", "bulk"))
 Transmission = co.namedtuple("Transmission", ("k", "z", "layers", "length", "iterations", "transmission"))
 TransmissionGreen = co.namedtuple("TransmissionGreen", Transmission._fields + ("green",))
+DeviceGreen = co.namedtuple("DeviceGreen", Transmission._fields + ("ldos", "left", "right"))
+DeviceGreenBlocks = co.namedtuple("DeviceGreenBlocks", DeviceGreen._fields + ("diagonal", "first", "last"))
 Susceptibility = co.namedtuple("Susceptibility", ("mu", "q", "chi"))
 DynamicSusceptibility = co.namedtuple("DynamicSusceptibility", ("mu", "q", "omega", "chi"))
 OrbitalSusceptibility = co.namedtuple("OrbitalSusceptibility", ("mu", "q", "orbitals", "chi"))
@@ -1401,12 +1403,33 @@ class Model:
         TBK_EIG_ROCSOLVER``, the decimation and the sweep run in lockstep batches on rocBLAS and rocSOLVER.  With several
         ``devices`` the k list is split as for ``hamilton``.
         """
+        energies, axis_index, cap, k_array, layers, potential = self._device_arguments(k, z, axis, max_iterations, device, length, "transmission", 1024)
+        n_rows = self.size * layers
+        n_k, n_z, count = k_array.shape[0], energies.shape[0], potential.shape[0]
+        iterations = np.zeros((n_k, n_z), dtype=np.int32)
+        result = np.empty((n_k, n_z), dtype=np.float64)
+        matrices = np.empty((n_k, n_z, n_rows, n_rows), dtype=np.complex128) if green else None
+        with self._call_lock:
+            # the cap reached: TBK_ERR_NO_CONVERGENCE, a singular z - D: TBK_ERR_SINGULAR -> numpy.linalg.LinAlgError
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_transmission_multi(handles, n_handles, axis_index, layers, _lib.ptr(k_array) if k_array.size else None, n_k, count,
+                                                  _lib.ptr(potential), n_z, _lib.ptr(energies), cap, _lib.ptr(iterations), _lib.ptr(result),
+                                                  _lib.ptr(matrices))
+            )
+        if green:
+            return TransmissionGreen(k_array, energies, layers, count, iterations, result, matrices)
+        return Transmission(k_array, energies, layers, count, iterations, result)
+
+    def _device_arguments(self, k, z, axis, max_iterations, device, length, name, max_rows):
+        """(energies, axis index, cap, in-plane k array, L, V as complex128 (M, N, N)) of `transmission` and `device_green_function`:
+        `_stacking_arguments` and the device, given as ``device`` or as ``length`` pristine layers."""
         energies, axis_index, cap, k_array, layers = self._stacking_arguments(k, z, axis, max_iterations)
         if layers == 0:
             raise ValueError("the model has no hopping along axis {}: there is nothing to transmit".format(axis_index))
         n_rows = self.size * layers
-        if n_rows > 1024:
-            raise ValueError("a principal layer of {} cells has {} rows: transmission takes at most 1024".format(layers, n_rows))
+        if n_rows > max_rows:
+            raise ValueError("a principal layer of {} cells has {} rows: {} takes at most {}".format(layers, n_rows, name, max_rows))
         if device is None:
             try:
                 count = int(length)
@@ -1438,21 +1461,74 @@ class Model:
             skew = float(np.abs(potential - np.conj(np.transpose(potential, (0, 2, 1)))).max())
             if skew > 1e-12 * size:
                 raise ValueError("device is not Hermitian: max|V - V^H| = {:.3e}".format(skew))
+        return energies, axis_index, cap, k_array, layers, potential
+
+    def device_green_function(self, k, z, *, axis=-1, device=None, length=1, max_iterations=64, green=False):
+        """
+        The layer-resolved Green's functions of the device of :meth:`transmission`: the local density of states per layer and
+        orbital, the parts of it injected from the left and from the right lead, and the diagonal blocks of the resolvent, on the
+        GPU.  Not in the reference.
+
+        ``k``, ``z``, ``axis``, ``device``, ``length``, ``max_iterations`` and the error messages are those of
+        :meth:`transmission`; ``H00``, ``H01``, ``N = size * L``, the decimation and the forward sweep with ``g_p``, ``D_p`` and
+        ``T`` are its as well, unchanged down to the order of the operations.  Returns the named tuple ``(k, z, layers, length,
+        iterations, transmission, ldos, left, right[, diagonal, first, last])``: ``ldos``, ``left`` and ``right`` are ``float64
+        (NK, NZ, M, N)``; with ``green=True``, ``diagonal``, ``first`` and ``last`` hold ``G_p``, ``F_p`` and ``C_p`` as
+        ``complex128 (NK, NZ, M, N, N)``.  Without it ``3 M N + 1`` doubles per ``(kp, z)`` leave the GPU.
+
+        Definition.  With ``Q_p`` the ``P_p`` of :meth:`transmission`, per ``(kp, z)`` after its forward sweep::
+
+            G_M = g_M,   C_M = g_M
+            for p = M - 1 ... 1:    X = g_p H01,   Y = H01^H g_p
+                                    G_p = g_p + (X G_{p+1}) Y          block (p, p) of the full resolvent
+                                    C_p = X C_{p+1}                    block (p, M)
+            F_1 = G_1;   F_p = G_p (H01^H Q_{p-1})  (1 < p < M);   F_M = Q_M  (M > 1)        block (p, 1)
+            ldos[p, i]  = -Im G_p[i, i] / pi
+            left[p, i]  = Re sum_j (F_p Gamma_L)[i, j] conj(F_p[i, j]) / (2 pi)
+            right[p, i] = Re sum_j (C_p Gamma_R)[i, j] conj(C_p[i, j]) / (2 pi)
+
+        Products are formed as bracketed; the order is part of the definition.  The cap of the decimation, a singular ``z - D_p``
+        and a non-finite element of a ``g_p``, ``G_p``, ``F_p`` or ``C_p`` raise ``numpy.linalg.LinAlgError`` naming the k index
+        and the energy.
+
+        Properties.  (1) ``ldos - left - right = (Im z / pi) sum_q sum_j |G_pq[i, j]|^2``: it has the sign of ``Im z`` and vanishes
+        as ``Im z -> 0``, where ``left + right`` is the whole density.  (2) With ``V = 0``, ``G_p`` is ``bulk`` of
+        :meth:`surface_green_function` for every ``p``.  (3) ``first[:, :, M - 1]`` and ``transmission`` have the bits of
+        ``transmission(..., green=True)``.  (4) The bits of one ``(kp, z)`` depend on nothing else: not on the other points or
+        energies, their order, the chunking, or ``green``.
+
+        Error bound per component of a block ``B`` of layer ``p``: ``E c(B) s(B)`` with ``E`` the ``eps`` of :meth:`transmission`,
+        ``c`` the number of error-carrying factors behind ``B`` (``3 (M - p) + 1`` for ``G_p``, ``M - p + 1`` for ``C_p``, ``c(G_p)
+        + p - 1`` for ``F_p``) and ``s`` the product of the 2-norms of the blocks ``B`` is formed from: ``s(G_p) = |g_p| + |X| |G_{p+1}|
+        |Y|``, ``s(C_p) = |X| |C_{p+1}|``, ``s(F_p) = |G_p| |H01^H Q_{p-1}|``.
+
+        Work: the decimation and ``40 N^3`` flops per layer of the forward sweep as for :meth:`transmission`, then eight products
+        per layer of the backward sweep, ``64 N^3`` flops, all on the FP64 matrix pipe.  One workgroup owns a ``(kp, z)`` from the
+        first iteration to the last output; the forward sweep leaves ``g_p`` and ``H01^H Q_{p-1}`` on a stack of ``2 M N^2`` complex
+        numbers per workgroup in device memory, as many stacks as fit 1 GiB.  ``N`` is at most 64, else ``ValueError``: there is no
+        library route, and a model with ``TBK_OPT_EIGENSOLVER = TBK_EIG_ROCSOLVER`` takes the own kernel too.  With several
+        ``devices`` the k list is split as for ``hamilton``.
+        """
+        energies, axis_index, cap, k_array, layers, potential = self._device_arguments(k, z, axis, max_iterations, device, length,
+                                                                                       "device_green_function", 64)
+        n_rows = self.size * layers
         n_k, n_z, count = k_array.shape[0], energies.shape[0], potential.shape[0]
         iterations = np.zeros((n_k, n_z), dtype=np.int32)
         result = np.empty((n_k, n_z), dtype=np.float64)
-        matrices = np.empty((n_k, n_z, n_rows, n_rows), dtype=np.complex128) if green else None
+        ldos, left, right = (np.empty((n_k, n_z, count, n_rows), dtype=np.float64) for _ in range(3))
+        blocks = [np.empty((n_k, n_z, count, n_rows, n_rows), dtype=np.complex128) if green else None for _ in range(3)]
         with self._call_lock:
-            # the cap reached: TBK_ERR_NO_CONVERGENCE, a singular z - D: TBK_ERR_SINGULAR -> numpy.linalg.LinAlgError
+            # the cap reached: TBK_ERR_NO_CONVERGENCE, a singular z - D or a non-finite block: TBK_ERR_SINGULAR -> numpy.linalg.LinAlgError
             handles, n_handles = self._handle_array()
             _lib.check(
-                _lib.lib().tbk_transmission_multi(handles, n_handles, axis_index, layers, _lib.ptr(k_array) if k_array.size else None, n_k, count,
+                _lib.lib().tbk_device_green_multi(handles, n_handles, axis_index, layers, _lib.ptr(k_array) if k_array.size else None, n_k, count,
                                                   _lib.ptr(potential), n_z, _lib.ptr(energies), cap, _lib.ptr(iterations), _lib.ptr(result),
-                                                  _lib.ptr(matrices))
+                                                  _lib.ptr(ldos), _lib.ptr(left), _lib.ptr(right), _lib.ptr(blocks[0]), _lib.ptr(blocks[1]),
+                                                  _lib.ptr(blocks[2]))
             )
         if green:
-            return TransmissionGreen(k_array, energies, layers, count, iterations, result, matrices)
-        return Transmission(k_array, energies, layers, count, iterations, result)
+            return DeviceGreenBlocks(k_array, energies, layers, count, iterations, result, ldos, left, right, blocks[0], blocks[1], blocks[2])
+        return DeviceGreen(k_array, energies, layers, count, iterations, result, ldos, left, right)
 
     def susceptibility(self, mesh, q, *, temperature, energy=None, n_electrons=None, matrix_elements=True, convention=2):
         """

@@ -1,0 +1,503 @@
+// tbk_device_green.hip -- the layer-resolved Green's functions of the device of tbk_transmission: the diagonal blocks G_pp of the
+// resolvent with both lead self-energies attached, the blocks (p, 1) and (p, M), the local density of states per layer and orbital and
+// its parts injected from each lead.  Not in the reference; DESIGN.md section 23 has the quantity, the kernel and the measurements,
+// tools/device_model.py is the statement the tests compare with.
+//
+//   the decimation and the forward sweep of the transmission (tbk_surface.h): g_p, Q_p = G_{p,1} of the left-connected
+//   system, T; then, with Gamma_R = i (es - es^H), Gamma_L = i (et - et^H),
+//
+//   G_M = g_M, C_M = g_M;  for p = M - 1 ... 1:  X = g_p H01, Y = H01^H g_p,  G_p = g_p + (X G_{p+1}) Y,  C_p = X C_{p+1}
+//   F_1 = G_1,  F_p = G_p (H01^H Q_{p-1}) (1 < p < M),  F_M = Q_M (M > 1)
+//   ldos[p][i] = -Im G_p[i][i] / pi,  left[p][i] = Re sum_j (F_p Gamma_L)[i][j] conj(F_p[i][j]) / (2 pi),  right: C_p and Gamma_R
+//
+//   device_green_kernel   one workgroup owns one (kp, z) from the first decimation step to the last output.  The forward sweep leaves
+//                         g_p and H01^H Q_{p-1} of every layer on a stack of 2 M N^2 complex numbers in global memory, one stack per
+//                         workgroup; the backward sweep reads it top down: eight products per layer on v_mfma_f64_16x16x4_f64.  The
+//                         planes are the transmission's (D's take G_p, P's take C_p): no LDS beyond it.  N <= 64; there is no library
+//                         route.
+
+#include "tbk_surface.h"
+
+namespace {
+
+constexpr const char* DEVG_FAMILY = "the device Green's function";
+constexpr const char* DEVG_SINGULAR = "z - D of a device layer, a block of the device's Green's function, or z - e of the decimation,";
+constexpr size_t DEVG_STACK_BUDGET = size_t(1) << 30;  // the workgroups' stacks of one launch: at M = 4096, N = 64 two still fit
+tbk_flag_row devg_lds_done_32, devg_lds_done_64;      // more than 64 KiB of dynamic LDS
+
+// Re sum_j A[row][j] conj(B[row][j]) / (2 pi) for every row below n into out[row], in a fixed order: a thread sums NP / PARTS columns
+// of its row, the first NP threads add the parts in order.  A: pitch NP + 1; B: pitch SB.  One barrier inside and one at the end.
+template <int NP, int THREADS, int SB>
+__device__ __forceinline__ void devg_row_sums(const double* ar, const double* ai, const double* br, const double* bi, int n, int tid, double* red,
+                                              double* __restrict__ out) {
+    constexpr int PARTS = THREADS / NP, CPP = NP / PARTS, S = NP + 1;
+    tid = surf_fresh(tid);
+    const int row = tid & (NP - 1), part = tid / NP;
+    double sum = 0.0;
+#pragma unroll 4
+    for (int cc = 0; cc < CPP; ++cc) {
+        const int c = part * CPP + cc;
+        if (row < n && c < n) sum += ar[row * S + c] * br[row * SB + c] + ai[row * S + c] * bi[row * SB + c];
+    }
+    red[tid] = sum;
+    __syncthreads();
+    if (tid < NP && tid < n) {
+        double a = 0.0;
+#pragma unroll
+        for (int q = 0; q < PARTS; ++q) a += red[q * NP + tid];
+        out[tid] = a / (2.0 * SURF_PI);
+    }
+    __syncthreads();  // red and A are free again
+}
+
+// i (e - e^H) of the first n rows and columns of e (pitch SM) into X, zeros beyond
+template <int NP, int THREADS, int SM>
+__device__ __forceinline__ void devg_broadening(double* xr, double* xi, const double* er, const double* ei, int n, int tid) {
+    constexpr int S = NP + 1;
+    tid = surf_fresh(tid);
+#pragma unroll 2
+    for (int e = tid; e < NP * NP; e += THREADS) {
+        const int i = e / NP, c = e - i * NP;
+        double gr = 0.0, gi = 0.0;
+        if (i < n && c < n) {
+            gr = -(ei[i * SM + c] + ei[c * SM + i]);
+            gi = er[i * SM + c] - er[c * SM + i];
+        }
+        xr[i * S + c] = gr;
+        xi[i * S + c] = gi;
+    }
+}
+
+// the wave's tiles of a product added to Y (pitch NP + 1) into D (pitch SD): D = Y + product
+template <int NP, int NT, int SD>
+__device__ __forceinline__ void devg_tiles_sum(double* dr, double* di, const double* yr, const double* yi, int n, int wave, int lane,
+                                               const surf_d4 (&cr)[NT], const surf_d4 (&ci)[NT]) {
+    constexpr int TR = NP / 16, S = NP + 1;
+    lane = surf_fresh(lane);
+    const int q = lane >> 4, c16 = lane & 15;
+    const int tr = (wave * NT) / TR, tc0 = (wave * NT) % TR;
+    if (tr * 16 >= n) return;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        if ((tc0 + t) * 16 < n) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = tr * 16 + q + 4 * r, c = (tc0 + t) * 16 + c16;
+                dr[i * SD + c] = yr[i * S + c] + cr[t][r];
+                di[i * SD + c] = yi[i * S + c] + ci[t][r];
+            }
+        }
+    }
+}
+
+// Layer p (from 0) of the backward sweep.  On entry (p < M - 1) D's planes hold G_{p+1} and P's C_{p+1}; at p = M - 1 P's hold Q_M as
+// the forward sweep left it.  Afterwards D's hold G_p, P's C_p and Y F_p, and the layer's outputs are written.  stack: the
+// workgroup's, as trans_layer wrote it.  Returns whether an element of G_p, F_p or C_p (this thread's share) is not finite.
+template <int NP>
+__device__ __forceinline__ bool devg_backward_layer(const SurfPlanes& P, const double2* stack, int p, int m_layers, int n, int tid,
+                                                    double* __restrict__ ldos, double* __restrict__ left, double* __restrict__ right,
+                                                    double2* __restrict__ g_out, double2* __restrict__ f_out, double2* __restrict__ c_out) {
+    using Geo = SurfGeom<NP>;
+    constexpr int THREADS = Geo::THREADS, S = Geo::S, SM = Geo::SM, NT = Geo::NT;
+    constexpr int PM = NP * SM;
+    const int lane = tid & 63, wave = tid >> 6;
+    double *xr = P.xr, *xi = P.xi, *yr = P.yr, *yi = P.yi;
+    double *h01r = P.alr, *h01i = P.ali, *h10r = P.ber, *h10i = P.bei, *dr = P.er, *di = P.ei, *esr = P.esr, *esi = P.esi, *etr = P.etr, *eti = P.eti;
+    double *pr = P.more, *pi = P.more + PM;
+    double* red = P.red;
+    const size_t nn = (size_t)n * n;
+    const double2* g = stack + (size_t)2 * p * nn;
+    const double2* hq = g + nn;  // H01^H Q_{p-1} (p > 0)
+    bool bad = false;
+    if (p == m_layers - 1) {
+#pragma unroll 2
+        for (int e = tid; e < NP * NP; e += THREADS) {  // F_M = Q_M into Y; G_M = C_M = g_M
+            const int i = e / NP, c = e - i * NP;
+            double2 v = make_double2(0.0, 0.0);
+            if (i < n && c < n) v = g[(size_t)i * n + c];
+            yr[i * S + c] = pr[i * SM + c];
+            yi[i * S + c] = pi[i * SM + c];
+            dr[i * SM + c] = pr[i * SM + c] = v.x;
+            di[i * SM + c] = pi[i * SM + c] = v.y;
+        }
+        __syncthreads();
+    } else {
+#pragma unroll 2
+        for (int e = tid; e < NP * NP; e += THREADS) {  // g_p into Y
+            const int i = e / NP, c = e - i * NP;
+            double2 v = make_double2(0.0, 0.0);
+            if (i < n && c < n) v = g[(size_t)i * n + c];
+            yr[i * S + c] = v.x;
+            yi[i * S + c] = v.y;
+        }
+        __syncthreads();
+        surf_d4 cr[NT], ci[NT], c2r[NT], c2i[NT];
+        surf_product<NP, NT, S, SM>(yr, yi, h01r, h01i, n, wave, lane, cr, ci);  // X = g_p H01
+        surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
+        __syncthreads();
+        surf_product<NP, NT, S, SM>(xr, xi, dr, di, n, wave, lane, cr, ci);    // X G_{p+1}
+        surf_product<NP, NT, S, SM>(xr, xi, pr, pi, n, wave, lane, c2r, c2i);  // C_p = X C_{p+1}
+        __syncthreads();  // X, G_{p+1} and C_{p+1} have been read
+        surf_tiles<NP, NT, SM, false>(dr, di, n, wave, lane, cr, ci);
+        surf_tiles<NP, NT, SM, false>(pr, pi, n, wave, lane, c2r, c2i);
+        surf_product<NP, NT, SM, S>(h10r, h10i, yr, yi, n, wave, lane, cr, ci);  // Y = H01^H g_p, into X's planes
+        surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
+        __syncthreads();
+        surf_product<NP, NT, SM, S>(dr, di, xr, xi, n, wave, lane, cr, ci);  // (X G_{p+1}) Y
+        __syncthreads();  // X G_{p+1} has been read
+        devg_tiles_sum<NP, NT, SM>(dr, di, yr, yi, n, wave, lane, cr, ci);  // G_p = g_p + (X G_{p+1}) Y
+        if (p > 0) {
+#pragma unroll 2
+            for (int e = tid; e < NP * NP; e += THREADS) {  // H01^H Q_{p-1} into X
+                const int i = e / NP, c = e - i * NP;
+                double2 v = make_double2(0.0, 0.0);
+                if (i < n && c < n) v = hq[(size_t)i * n + c];
+                xr[i * S + c] = v.x;
+                xi[i * S + c] = v.y;
+            }
+        }
+        __syncthreads();  // G_p is whole, g_p has been read
+        if (p > 0) {
+            surf_product<NP, NT, SM, S>(dr, di, xr, xi, n, wave, lane, cr, ci);  // F_p = G_p (H01^H Q_{p-1})
+            surf_tiles<NP, NT, S, false>(yr, yi, n, wave, lane, cr, ci);
+        } else {
+#pragma unroll 2
+            for (int e = tid; e < NP * NP; e += THREADS) {  // F_1 = G_1
+                const int i = e / NP, c = e - i * NP;
+                yr[i * S + c] = dr[i * SM + c];
+                yi[i * S + c] = di[i * SM + c];
+            }
+        }
+        __syncthreads();
+    }
+    // the layer's blocks are looked at and leave; Gamma_L into X
+    for (int e = tid; e < n * n; e += THREADS) {
+        const int i = e / n, c = e - i * n;
+        const double2 gv = make_double2(dr[i * SM + c], di[i * SM + c]), fv = make_double2(yr[i * S + c], yi[i * S + c]),
+                      cv = make_double2(pr[i * SM + c], pi[i * SM + c]);
+        bad |= !(fabs(gv.x) <= SURF_DBL_MAX && fabs(gv.y) <= SURF_DBL_MAX && fabs(fv.x) <= SURF_DBL_MAX && fabs(fv.y) <= SURF_DBL_MAX &&
+                 fabs(cv.x) <= SURF_DBL_MAX && fabs(cv.y) <= SURF_DBL_MAX);
+        if (g_out != nullptr) {
+            g_out[e] = gv;
+            f_out[e] = fv;
+            c_out[e] = cv;
+        }
+        if (i == c) ldos[i] = -gv.y / SURF_PI;
+    }
+    devg_broadening<NP, THREADS, SM>(xr, xi, etr, eti, n, tid);
+    __syncthreads();
+    {
+        surf_d4 cr[NT], ci[NT];
+        surf_product<NP, NT, S, S>(yr, yi, xr, xi, n, wave, lane, cr, ci);  // F_p Gamma_L
+        __syncthreads();  // Gamma_L has been read
+        surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
+        __syncthreads();
+        devg_row_sums<NP, THREADS, S>(xr, xi, yr, yi, n, tid, red, left);
+        devg_broadening<NP, THREADS, SM>(xr, xi, esr, esi, n, tid);
+        __syncthreads();
+        surf_product<NP, NT, SM, S>(pr, pi, xr, xi, n, wave, lane, cr, ci);  // C_p Gamma_R
+        __syncthreads();  // Gamma_R has been read
+        surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
+        __syncthreads();
+        devg_row_sums<NP, THREADS, SM>(xr, xi, pr, pi, n, tid, red, right);
+    }
+    return bad;
+}
+
+// H00, H01, V, z, items, key0, ws, iters, T_out, flag: transmission_kernel's.  stack: gridDim.x slots of slot_items = 2 m_layers n^2
+// complex numbers; a slot is written and read by its workgroup alone.  Per item: ldos, left, right [m_layers][n] and, G_out not NULL,
+// G_p, F_p, C_p [m_layers][n][n].  Status: a zero pivot or a non-finite element of a g_p, G_p, F_p or C_p is reason 0, the cap of
+// the decimation reason 1; the sweeps run on after either.  Every branch is workgroup-uniform; no index depends on a value but through
+// the pivot tables.
+template <int NP>
+__global__ void __launch_bounds__(SurfGeom<NP>::THREADS)
+    device_green_kernel(const double2* __restrict__ H00, const double2* __restrict__ H01, const double2* __restrict__ V, int m_layers,
+                        const double2* __restrict__ z, int n_z, int n, int64_t items, int max_it, unsigned long long key0, double* ws, double2* stack,
+                        size_t slot_items, int32_t* __restrict__ iters, double* __restrict__ T_out, double* __restrict__ ldos, double* __restrict__ left,
+                        double* __restrict__ right, double2* __restrict__ G_out, double2* __restrict__ F_out, double2* __restrict__ C_out,
+                        unsigned long long* __restrict__ flag) {
+    extern __shared__ double surf_lds[];
+    const int tid = (int)threadIdx.x;
+    const SurfPlanes P = surf_planes<NP, TransGeom<NP>::MATS>(surf_lds, ws);
+    double2* st = stack + (size_t)blockIdx.x * slot_items;
+
+    for (int64_t w = blockIdx.x; w < items; w += gridDim.x) {
+        const int64_t k = w / n_z;
+        const int zi = (int)(w - k * n_z);
+        const double2 zz = z[zi];
+        const double2* h0 = H00 + (size_t)k * n * n;
+        const double2* h1 = H01 + (size_t)k * n * n;
+        surf_load<NP>(P, h0, h1, true, n, tid);
+        int it = 0;
+        const int status = surf_iterate<NP>(P, zz, n, max_it, tid, it);  // 1: singular, 2: the cap (the same on every thread)
+        bool bad = status == 1;
+        trans_start<NP>(P, h1, V, n, tid);
+#pragma unroll 1
+        for (int p = 0; p < m_layers; ++p) bad |= trans_layer<NP, true>(P, h0, V, zz, p, m_layers, n, tid, st);
+        bad |= trans_closing<NP>(P, n, tid, nullptr, T_out + w, iters + w, it);
+        const size_t rows = ((size_t)w * m_layers) * n, mats = rows * n;
+#pragma unroll 1
+        for (int p = m_layers - 1; p >= 0; --p) {
+            const size_t ro = rows + (size_t)p * n, mo = mats + (size_t)p * n * n;
+            bad |= devg_backward_layer<NP>(P, st, p, m_layers, n, tid, ldos + ro, left + ro, right + ro, G_out != nullptr ? G_out + mo : nullptr,
+                                           G_out != nullptr ? F_out + mo : nullptr, G_out != nullptr ? C_out + mo : nullptr);
+        }
+        const unsigned long long key = (key0 + (unsigned long long)k * (unsigned long long)SURF_MAX_Z + (unsigned long long)zi) * 2ull;
+        if (bad) atomicMin(flag, key);
+        if (status == 2 && tid == 0) atomicMin(flag, key + 1ull);
+    }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+// The results of a chunk: T, iterations, ldos, left, right, (green) G, F, C, and behind them the status word.
+struct DevgShape {
+    int n = 0, m_layers = 0;
+    int64_t n_z = 0;
+    bool green = false;
+    size_t t_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * sizeof(double)); }
+    size_t it_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * sizeof(int32_t)); }
+    size_t row_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * m_layers * n * sizeof(double)); }
+    size_t mat_bytes(int64_t nk) const { return green ? surf_align256((size_t)nk * n_z * m_layers * n * n * sizeof(double2)) : 0; }
+    size_t result_bytes(int64_t nk) const { return t_bytes(nk) + it_bytes(nk) + 3 * row_bytes(nk) + 3 * mat_bytes(nk); }
+    size_t slot_items() const { return (size_t)2 * m_layers * n * n; }  // complex numbers of one stack
+    int64_t auto_chunk(int64_t nk) const {  // the chunk's results and its two layers inside the budget
+        const size_t nn = (size_t)n * n * sizeof(double2);
+        const size_t per_item = sizeof(double) + sizeof(int32_t) + (size_t)m_layers * (3 * n * sizeof(double) + (green ? 3 * nn : 0));
+        const size_t per_k = (size_t)n_z * per_item + 2 * nn;
+        return std::max<int64_t>(1, std::min<int64_t>(nk, (int64_t)(SURF_CHUNK_BUDGET / per_k)));
+    }
+};
+
+// workgroups and stacks of a launch: the slots the budget holds, at most the items, the usual grid and the caller's cap (0: none)
+int64_t devg_grid(const DevgShape& sh, int64_t items, int n_cu, int64_t slots) {
+    int64_t grid = std::min<int64_t>(surf_grid(sh.n, items, n_cu), (int64_t)(DEVG_STACK_BUDGET / (sh.slot_items() * sizeof(double2))));
+    if (slots > 0) grid = std::min(grid, slots);
+    return std::max<int64_t>(1, grid);
+}
+
+size_t devg_stack_bytes(const DevgShape& sh, int64_t items, int n_cu, int64_t slots) {
+    return (size_t)devg_grid(sh, items, n_cu, slots) * sh.slot_items() * sizeof(double2);
+}
+
+size_t devg_workspace_bytes(const DevgShape& sh, int64_t items, int n_cu, int64_t slots) {
+    return sh.n > 32 ? (size_t)devg_grid(sh, items, n_cu, slots) * TransGeom<64>::slot_doubles * sizeof(double) : 0;
+}
+
+template <int NP>
+int devg_launch_np(hipStream_t s, int n_cu, tbk_flag_row* done, const DevgShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_V,
+                   const double2* d_z, int64_t nkc, int max_it, unsigned long long key0, int64_t slots, double* d_ws, double2* d_stack, char* d_res) {
+    using Geo = SurfGeom<NP>;
+    const int64_t items = nkc * sh.n_z;
+    if (done != nullptr)
+        TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(device_green_kernel<NP>), (int)TransGeom<NP>::lds_bytes, *done));
+    char* at = d_res;
+    double* d_T = reinterpret_cast<double*>(at);
+    at += sh.t_bytes(nkc);
+    int32_t* d_it = reinterpret_cast<int32_t*>(at);
+    at += sh.it_bytes(nkc);
+    double* d_rows[3];
+    for (int i = 0; i < 3; ++i, at += sh.row_bytes(nkc)) d_rows[i] = reinterpret_cast<double*>(at);
+    double2* d_mats[3] = {nullptr, nullptr, nullptr};
+    if (sh.green)
+        for (int i = 0; i < 3; ++i, at += sh.mat_bytes(nkc)) d_mats[i] = reinterpret_cast<double2*>(at);
+    hipLaunchKernelGGL(device_green_kernel<NP>, dim3((unsigned)devg_grid(sh, items, n_cu, slots)), dim3(Geo::THREADS), TransGeom<NP>::lds_bytes, s, d_H00,
+                       d_H01, d_V, sh.m_layers, d_z, (int)sh.n_z, sh.n, items, max_it, key0, d_ws, d_stack, sh.slot_items(), d_it, d_T, d_rows[0], d_rows[1],
+                       d_rows[2], d_mats[0], d_mats[1], d_mats[2], reinterpret_cast<unsigned long long*>(d_res + sh.result_bytes(nkc)));
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// The chunk's nkc points at every energy.  d_res: DevgShape's layout for nkc points.
+int devg_launch(hipStream_t s, int n_cu, const DevgShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_V, const double2* d_z,
+                int64_t nkc, int max_it, int64_t k0, int64_t slots, double* d_ws, double2* d_stack, char* d_res) {
+    const unsigned long long key0 = (unsigned long long)k0 * (unsigned long long)SURF_MAX_Z;
+    if (sh.n <= 16) return devg_launch_np<16>(s, n_cu, nullptr, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, slots, d_ws, d_stack, d_res);
+    if (sh.n <= 32) return devg_launch_np<32>(s, n_cu, &devg_lds_done_32, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, slots, d_ws, d_stack, d_res);
+    return devg_launch_np<64>(s, n_cu, &devg_lds_done_64, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, slots, d_ws, d_stack, d_res);
+}
+
+// what the entry points check beyond the transmission's: the rows, the stack of one workgroup, the outputs
+int devg_check(int N, int M, const double* ldos, const double* left, const double* right, const double* G, const double* F, const double* C) {
+    if (N > SURF_OWN_MAX) {
+        tbk_set_error("invalid argument: a principal layer of %d rows: the device Green's function takes at most %d", N, SURF_OWN_MAX);
+        return TBK_ERR_ARGUMENT;
+    }
+    if ((size_t)2 * M * N * N * sizeof(double2) > DEVG_STACK_BUDGET) {
+        tbk_set_error("invalid argument: a device of %d layers of %d rows: the stack of one workgroup may take at most 1 GiB", M, N);
+        return TBK_ERR_ARGUMENT;
+    }
+    TBK_ARG(ldos != nullptr && left != nullptr && right != nullptr, "ldos / left / right is NULL");
+    TBK_ARG((G != nullptr) == (F != nullptr) && (G != nullptr) == (C != nullptr), "G, F and C must all be NULL or none of them");
+    return TBK_OK;
+}
+
+// the copies of a chunk's results to the host (s NULL: synchronous); *word receives the chunk's status word
+int devg_copy_out(hipStream_t s, bool async, const DevgShape& sh, const char* d_res, int64_t nkc, int64_t c0, int32_t* iterations, double* T, double* ldos,
+                  double* left, double* right, double* G, double* F, double* C, unsigned long long* word) {
+    const size_t items = (size_t)nkc * sh.n_z, first = (size_t)c0 * sh.n_z;
+    const size_t rows = (size_t)sh.m_layers * sh.n, mats = rows * sh.n * 2;
+    auto copy = [&](void* dst, const void* src, size_t bytes) {
+        return async ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+    };
+    const char* at = d_res;
+    TBK_HIP(copy(T + first, at, items * sizeof(double)));
+    at += sh.t_bytes(nkc);
+    TBK_HIP(copy(iterations + first, at, items * sizeof(int32_t)));
+    at += sh.it_bytes(nkc);
+    double* row_out[3] = {ldos, left, right};
+    for (int i = 0; i < 3; ++i, at += sh.row_bytes(nkc)) TBK_HIP(copy(row_out[i] + first * rows, at, items * rows * sizeof(double)));
+    double* mat_out[3] = {G, F, C};
+    if (sh.green)
+        for (int i = 0; i < 3; ++i, at += sh.mat_bytes(nkc)) TBK_HIP(copy(mat_out[i] + first * mats, at, items * mats * sizeof(double)));
+    TBK_HIP(copy(word, d_res + sh.result_bytes(nkc), sizeof(unsigned long long)));
+    return TBK_OK;
+}
+
+}  // namespace
+
+extern "C" int tbk_device_green_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, const double* V, int64_t n_z,
+                                              const double* z, int max_iterations, int64_t k_chunk, int64_t slots, int32_t* iterations, double* T,
+                                              double* ldos, double* left, double* right, double* G, double* F, double* C) {
+    TBK_CHECK(surf_check_energies(std::min(N, SURF_LIB_MAX), n_z, z, max_iterations));
+    TBK_ARG(H01 != nullptr, "H01 is NULL: the device Green's function needs hopping between the principal layers");
+    TBK_CHECK(trans_check_device(N, M, V, iterations, T));
+    TBK_CHECK(devg_check(N, M, ldos, left, right, G, F, C));
+    TBK_ARG(n_k >= 1 && n_k < (int64_t(1) << 40), "n_k < 1");
+    TBK_ARG(H00 != nullptr, "H00 is NULL");
+    TBK_ARG(k_chunk >= 0, "k_chunk < 0");
+    TBK_ARG(slots >= 0, "slots < 0");
+    TBK_CHECK(tetra_check_device(device));
+    DevgShape sh;
+    sh.n = N;
+    sh.m_layers = M;
+    sh.n_z = n_z;
+    sh.green = G != nullptr;
+    const int64_t chunk = std::min<int64_t>(n_k, k_chunk > 0 ? k_chunk : sh.auto_chunk(n_k));
+    const int n_cu = surf_device_cus(device);
+    const size_t nn = (size_t)N * N, h_bytes = (size_t)chunk * nn * sizeof(double2), v_bytes = (size_t)M * nn * sizeof(double2);
+    DevBuf d_H00, d_H01, d_V, d_z, d_res, d_ws, d_stack;
+    TBK_CHECK(d_H00.reserve(h_bytes));
+    TBK_CHECK(d_H01.reserve(h_bytes));
+    TBK_CHECK(d_V.reserve(v_bytes));
+    TBK_CHECK(d_z.reserve((size_t)n_z * sizeof(double2)));
+    TBK_CHECK(d_res.reserve(sh.result_bytes(chunk) + sizeof(unsigned long long)));
+    TBK_CHECK(d_stack.reserve(devg_stack_bytes(sh, chunk * n_z, n_cu, slots)));
+    const size_t ws_bytes = devg_workspace_bytes(sh, chunk * n_z, n_cu, slots);
+    if (ws_bytes > 0) TBK_CHECK(d_ws.reserve(ws_bytes));
+    TBK_HIP(hipMemcpy(d_z.ptr, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice));
+    TBK_HIP(hipMemcpy(d_V.ptr, V, v_bytes, hipMemcpyHostToDevice));
+    unsigned long long word = SURF_NO_FLAG;
+    for (int64_t c0 = 0; c0 < n_k; c0 += chunk) {
+        const int64_t nkc = std::min(chunk, n_k - c0);
+        char* res = d_res.as<char>();
+        TBK_HIP(hipMemcpy(d_H00.ptr, H00 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
+        TBK_HIP(hipMemcpy(d_H01.ptr, H01 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
+        TBK_HIP(hipMemset(res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long)));
+        TBK_CHECK(devg_launch(nullptr, n_cu, sh, d_H00.as<double2>(), d_H01.as<double2>(), d_V.as<double2>(), d_z.as<double2>(), nkc, max_iterations, c0,
+                              slots, d_ws.as<double>(), d_stack.as<double2>(), res));
+        unsigned long long chunk_word = SURF_NO_FLAG;
+        TBK_CHECK(devg_copy_out(nullptr, false, sh, res, nkc, c0, iterations, T, ldos, left, right, G, F, C, &chunk_word));
+        word = std::min(word, chunk_word);
+    }
+    return surf_status_error(word, z, max_iterations, DEVG_SINGULAR);
+}
+
+// The whole call on one handle; k_base as in tbk_surface_green_slab.  A handle with TBK_EIG_ROCSOLVER takes the own kernel too: there
+// is no library route.
+int tbk_device_green_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M_device, const double* V, int64_t n_z,
+                          const double* z, int max_iterations, int32_t* iterations, double* T, double* ldos, double* left, double* right, double* G,
+                          double* F, double* C) {
+    TBK_ARG(m != nullptr, "model is NULL");
+    TBK_LOCK(m);
+    TBK_ARG(!m->kdotp, "the device Green's function needs a tight-binding model");
+    const int dim = m->dim, n_orb = m->n_orb;
+    TBK_ARG(axis >= 0 && axis < dim, "axis must be 0 ... dim - 1");
+    TBK_ARG(layers >= 1 && layers <= 1024, "layers must be 1 ... 1024: the device Green's function needs hopping along the axis");
+    const int L = layers, S = 2 * L + 1;
+    for (size_t r = 0; r < m->h_R.size() / (size_t)dim; ++r) {
+        const int64_t reach = std::abs((int64_t)m->h_R[r * dim + axis]);
+        if (reach > L) {
+            tbk_set_error("invalid argument: layers = %d, but a stored hopping vector reaches %lld cells along axis %d", L, (long long)reach, axis);
+            return TBK_ERR_ARGUMENT;
+        }
+    }
+    const int64_t N64 = (int64_t)n_orb * L;
+    TBK_CHECK(surf_check_energies((int)std::min<int64_t>(N64, SURF_LIB_MAX), n_z, z, max_iterations));
+    DevgShape sh;
+    sh.n = (int)std::min<int64_t>(N64, 1 << 20);
+    sh.m_layers = M_device;
+    sh.n_z = n_z;
+    sh.green = G != nullptr;
+    const int N = sh.n;
+    TBK_CHECK(devg_check(N, std::max(M_device, 1), ldos, left, right, G, F, C));
+    TBK_CHECK(trans_check_device(N, M_device, V, iterations, T));
+    TBK_ARG(nk >= 0 && nk < (int64_t(1) << 40), "nk < 0");
+    if (nk == 0) return TBK_OK;
+    TBK_ARG(k != nullptr || dim == 1, "k is NULL");
+    const size_t nn2 = (size_t)n_orb * n_orb * 2;  // doubles of one H(k)
+    const int64_t by_h = std::max<int64_t>(1, (int64_t)(SURF_CHUNK_BUDGET / ((size_t)S * nn2 * sizeof(double))));
+    const int64_t chunk = std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : std::min(sh.auto_chunk(nk), by_h));
+    // (the host buffers the enqueued copies read and write, in front of the streams: they wait before these go)
+    std::vector<double> h_k, h_tw;
+    std::vector<unsigned long long> words;
+    TBK_CHECK(surf_host_lists(dim, axis, L, k, nk, h_k, h_tw));
+    try {
+        words.assign((size_t)((nk + chunk - 1) / chunk), SURF_NO_FLAG);
+    } catch (...) {
+        tbk_set_error("cannot allocate the status words");
+        return TBK_ERR_MEMORY;
+    }
+    MeshStreams streams;
+    TBK_CHECK(streams.add(m));
+    SpanRecorder* ev = &streams.used.back().ev;
+    const size_t z_bytes = surf_align256((size_t)n_z * sizeof(double2)), tw_bytes = h_tw.size() * sizeof(double);
+    const size_t layer_bytes = surf_align256((size_t)chunk * N * N * sizeof(double2)), v_bytes = (size_t)M_device * N * N * sizeof(double2);
+    const size_t ws_bytes = devg_workspace_bytes(sh, chunk * n_z, m->n_cu, 0);
+    TBK_CHECK(mesh_reserve(m->ws_mesh_k, h_k.size() * sizeof(double), DEVG_FAMILY, "the k list with its samples along the stacking axis"));
+    TBK_CHECK(mesh_reserve(m->ws_dm_r, z_bytes + tw_bytes, DEVG_FAMILY, "the energies and the twiddles"));
+    TBK_CHECK(mesh_reserve(m->ws_dm_rho, sh.result_bytes(chunk) + sizeof(unsigned long long), DEVG_FAMILY, "the results of one chunk"));
+    TBK_CHECK(mesh_reserve(m->ws_dm_p, 2 * layer_bytes, DEVG_FAMILY, "the principal layers of one chunk"));
+    TBK_CHECK(mesh_reserve(m->ws_pdos_u, (size_t)chunk * S * nn2 * sizeof(double), DEVG_FAMILY, "H(k) of one chunk"));
+    TBK_CHECK(mesh_reserve(m->ws_mesh_io, v_bytes, DEVG_FAMILY, "the device potential"));
+    TBK_CHECK(mesh_reserve(m->ws_mesh_u, devg_stack_bytes(sh, chunk * n_z, m->n_cu, 0), DEVG_FAMILY, "the workgroups' stacks"));
+    if (ws_bytes > 0) TBK_CHECK(mesh_reserve(m->ws_mesh_work, ws_bytes, DEVG_FAMILY, "the workgroups' matrices"));
+    double* d_k = m->ws_mesh_k.as<double>();
+    char* d_zt = m->ws_dm_r.as<char>();
+    double* d_H = m->ws_pdos_u.as<double>();
+    double2* d_H00 = m->ws_dm_p.as<double2>();
+    double2* d_H01 = reinterpret_cast<double2*>(m->ws_dm_p.as<char>() + layer_bytes);
+    const double2* d_V = m->ws_mesh_io.as<double2>();
+    const double2* d_z = reinterpret_cast<const double2*>(d_zt);
+    char* d_res = m->ws_dm_rho.as<char>();
+    TBK_HIP(hipMemcpyAsync(d_k, h_k.data(), h_k.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
+    TBK_HIP(hipMemcpyAsync(d_zt, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice, m->stream));
+    TBK_HIP(hipMemcpyAsync(d_zt + z_bytes, h_tw.data(), tw_bytes, hipMemcpyHostToDevice, m->stream));
+    TBK_HIP(hipMemcpyAsync(m->ws_mesh_io.ptr, V, v_bytes, hipMemcpyHostToDevice, m->stream));  // once per call
+    for (int64_t c0 = 0, ci = 0; c0 < nk; c0 += chunk, ++ci) {
+        const int64_t nkc = std::min(chunk, nk - c0);
+        TBK_CHECK(surf_chunk_layers(m, ev, d_k + (size_t)c0 * S * dim, nkc, L, d_H, reinterpret_cast<const double*>(d_zt + z_bytes), d_H00, d_H01));
+        TBK_HIP(hipMemsetAsync(d_res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long), m->stream));
+        if (ev) ev->start(1);
+        TBK_CHECK(devg_launch(m->stream, m->n_cu, sh, d_H00, d_H01, d_V, d_z, nkc, max_iterations, k_base + c0, 0, m->ws_mesh_work.as<double>(),
+                              m->ws_mesh_u.as<double2>(), d_res));
+        if (ev) ev->stop();
+        if (ev) ev->start(2);
+        TBK_CHECK(devg_copy_out(m->stream, true, sh, d_res, nkc, c0, iterations, T, ldos, left, right, G, F, C, &words[(size_t)ci]));
+        if (ev) ev->stop();
+    }
+    TBK_CHECK(streams.finish(TIMED_DEVICE_GREEN));
+    unsigned long long word = SURF_NO_FLAG;
+    for (unsigned long long w : words) word = std::min(word, w);
+    return surf_status_error(word, z, max_iterations, DEVG_SINGULAR);
+}
+
+extern "C" int tbk_device_green(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z, const double* z,
+                                int max_iterations, int32_t* iterations, double* T, double* ldos, double* left, double* right, double* G, double* F,
+                                double* C) {
+    return tbk_device_green_slab(m, 0, axis, layers, k, nk, M, V, n_z, z, max_iterations, iterations, T, ldos, left, right, G, F, C);
+}
+
+extern "C" int tbk_device_green_timing(tbk_model* m, double* ms, int64_t* calls, int reset) {
+    TBK_ARG(m != nullptr && ms != nullptr && calls != nullptr, "model / ms / calls is NULL");
+    return tbk_timed_read(m, TIMED_DEVICE_GREEN, 3, ms, calls, nullptr, reset);
+}

@@ -150,6 +150,28 @@ extern "C" int tbk_transmission_multi(tbk_model* const* handles, int n_handles, 
     });
 }
 
+// The device Green's function on several devices (tbk_device_green.hip): the slabs of tbk_transmission_multi; every handle stages the whole V
+extern "C" int tbk_device_green_multi(tbk_model* const* handles, int n_handles, int axis, int layers, const double* k, int64_t nk, int M, const double* V,
+                                      int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T, double* ldos, double* left,
+                                      double* right, double* G, double* F, double* C) {
+    TBK_CHECK(check_handles(handles, n_handles));
+    TBK_ARG(nk >= 0, "nk < 0");
+    if (n_handles == 1 || nk == 0)
+        return tbk_device_green(handles[0], axis, layers, k, nk, M, V, n_z, z, max_iterations, iterations, T, ldos, left, right, G, F, C);
+    TBK_ARG(n_z >= 1 && n_z <= 4096 && layers >= 1 && layers <= 1024 && M >= 1 && M <= 4096, "n_z and M must be 1 to 4096, layers 1 ... 1024");
+    TBK_ARG(iterations != nullptr && T != nullptr && ldos != nullptr && left != nullptr && right != nullptr, "iterations / T / ldos / left / right is NULL");
+    TBK_ARG((G != nullptr) == (F != nullptr) && (G != nullptr) == (C != nullptr), "G, F and C must all be NULL or none of them");
+    const int dim = handles[0]->dim;
+    TBK_ARG(k != nullptr || dim == 1, "k is NULL");
+    const int64_t N = (int64_t)handles[0]->n_orb * layers;
+    const int64_t rows = n_z * M * N, mats = rows * N * 2;  // doubles of one k-point in ldos, left, right and in G, F, C
+    return run_slabs(n_handles, nk, [&](int i, int64_t lo, int64_t count) {
+        return tbk_device_green_slab(handles[i], lo, axis, layers, k != nullptr ? k + lo * (dim - 1) : nullptr, count, M, V, n_z, z, max_iterations,
+                                     iterations + lo * n_z, T + lo * n_z, ldos + lo * rows, left + lo * rows, right + lo * rows,
+                                     G != nullptr ? G + lo * mats : nullptr, G != nullptr ? F + lo * mats : nullptr, G != nullptr ? C + lo * mats : nullptr);
+    });
+}
+
 // The density of states of a mesh on several devices (tbk_dos.hip): handle i takes a contiguous slab of ceil(n_1 / n) cells along
 // axis 0 and evaluates the planes of that slab plus the one periodic neighbour plane its last cells need.  Every handle returns
 // its share of nos; the host adds the shares in handle order (slabs that hold no cells are skipped).

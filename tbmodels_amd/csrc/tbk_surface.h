@@ -1,0 +1,836 @@
+// tbk_surface.h -- what the kernels and drivers of tbk_surface.hip (the decimation, the transmission) and tbk_device_green.hip (the
+// layer-resolved Green's functions of the device) share: the geometry of a workgroup's planes, the inversion, the products, the
+// iteration of the decimation, the layer body and the closing trace of the sweep, and the host helpers of the whole calls.  Everything
+// sits in an unnamed namespace: each translation unit has its own copy.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include <rocsolver/rocsolver.h>
+
+#include "tbk_resident.h"
+
+namespace {
+
+typedef double surf_d4 __attribute__((ext_vector_type(4)));
+
+constexpr int64_t SURF_MAX_Z = 4096;  // energies per call (include/tbk.h)
+constexpr int SURF_OWN_MAX = 64;      // rows of a principal layer the decimation kernel takes
+constexpr int SURF_LIB_MAX = 1024;    // ... and the library route above it (or on request)
+constexpr int SURF_MAX_ITERATIONS = 4096;
+constexpr unsigned long long SURF_NO_FLAG = ~0ull;
+constexpr size_t SURF_CHUNK_BUDGET = size_t(256) << 20;  // the results of one chunk, and the H(k) samples of one chunk
+constexpr double SURF_DBL_MAX = 1.79769313486231570815e308;
+constexpr double SURF_PI = 3.14159265358979323846;
+constexpr const char* SURF_FAMILY = "the surface Green's function";
+
+inline size_t surf_align256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// What sits where, per template.  X, Y: two matrices in LDS, planes (re, im) of NP rows NP + 1 doubles apart -- the elimination runs
+// in X, its un-permuted result g goes to Y, X then holds T.  alpha, beta, e, es, et: in LDS behind them up to NP = 32 (seven
+// matrices), in the workgroup's slot of a global workspace at NP = 64 (pitch 64; the slot is reread by the workgroup that wrote
+// it; 256 slots are 80 MiB: more than L2, inside the Infinity Cache).
+template <int NP>
+struct SurfGeom {
+    static constexpr int THREADS = NP == 16 ? 64 : 256;
+    static constexpr int WAVES = THREADS / 64;
+    static constexpr int S = NP + 1;
+    static constexpr int TR = NP / 16;               // tile rows
+    static constexpr int NT = TR * TR / WAVES;       // 16 x 16 tiles of a product per wave: 1, 1, 4 (one tile row)
+    static constexpr bool GLOBAL = NP == 64;
+    static constexpr int SM = GLOBAL ? NP : S;       // pitch of alpha, beta, e, es, et
+    static constexpr int LDS_PLANES = GLOBAL ? 4 : 14;
+    static constexpr size_t lds_bytes = ((size_t)LDS_PLANES * NP * S + 2 * THREADS + 2 * NP + NP) * sizeof(double);
+    static constexpr size_t slot_doubles = GLOBAL ? (size_t)10 * NP * NP : 0;
+};
+
+// ---- the inversion: green_invert_kernel's elimination (tbk_green.hip) for ONE matrix per workgroup ------------------
+// Gauss-Jordan in place with implicit partial pivoting on |re| + |im| (ties: the lowest row; a NaN counts as +inf), in panels of 16
+// pivots; the panel's columns by rank-1 VALU updates, every other column tile by a rank-16 update on the matrix pipe.  jrow must be
+// -1 and the planes written before the call (its first barrier orders them); afterwards, behind a barrier of the caller's,
+// inverse[r][s] = storage[prow[r]][jrow[s]].  Returns whether a pivot was exactly zero (the same value on every thread).
+template <int NP, int THREADS>
+__device__ __forceinline__ bool surf_invert(double* ar, double* ai, int* prow, int* jrow, int n, int tid) {
+    constexpr int CG = THREADS / NP;  // column groups of a panel
+    constexpr int CPT = 16 / CG;      // panel columns per thread
+    constexpr int S = NP + 1;
+    constexpr int TR = NP / 16;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int row = tid & (NP - 1), cg = tid / NP;
+    bool used = row >= n, singular = false;
+    for (int j0 = 0; j0 < n; j0 += 16) {
+        const int jn = n - j0 < 16 ? n - j0 : 16;
+        for (int jj = 0; jj < jn; ++jj) {
+            const int jc = j0 + jj;
+            __syncthreads();  // column jc is up to date
+            const double fr = ar[row * S + jc], fi = ai[row * S + jc];
+            double best = fabs(fr) + fabs(fi);
+            if (!(best >= 0.0)) best = __builtin_inf();
+            if (used) best = -1.0;
+            int p = row;
+#pragma unroll
+            for (int off = NP / 2; off > 0; off >>= 1) {
+                const double ob = __shfl_xor(best, off, 64);
+                const int op = __shfl_xor(p, off, 64);
+                if (ob > best || (ob == best && op < p)) {
+                    best = ob;
+                    p = op;
+                }
+            }
+            // (p is a row below n that no step has taken: at least one is left, and taken rows and padding compare as -1)
+            const int src = (lane & ~(NP - 1)) | p;
+            const double pr = __shfl(fr, src, 64), pi = __shfl(fi, src, 64);
+            singular |= best == 0.0;
+            const double den = pr * pr + pi * pi;
+            const double ir = pr / den, ii = -pi / den;  // 1 / pivot
+            double xr[CPT], xi[CPT], yr[CPT], yi[CPT];
+#pragma unroll
+            for (int cc = 0; cc < CPT; ++cc) {
+                const int c = j0 + cg * CPT + cc;
+                xr[cc] = ar[p * S + c];
+                xi[cc] = ai[p * S + c];
+                yr[cc] = ar[row * S + c];
+                yi[cc] = ai[row * S + c];
+            }
+            __syncthreads();  // every wave has read column jc and row p
+#pragma unroll
+            for (int cc = 0; cc < CPT; ++cc) {
+                const int c = j0 + cg * CPT + cc;
+                double tr = ir, ti = ii;  // the new pivot row: a[p][c] / piv, 1 / piv in column jc
+                if (c != jc) {
+                    tr = xr[cc] * ir - xi[cc] * ii;
+                    ti = xr[cc] * ii + xi[cc] * ir;
+                }
+                double nr = tr, ni = ti;
+                if (row != p) {
+                    const double mr = fr * tr - fi * ti, mi = fr * ti + fi * tr;
+                    nr = c == jc ? -mr : yr[cc] - mr;
+                    ni = c == jc ? -mi : yi[cc] - mi;
+                }
+                ar[row * S + c] = nr;
+                ai[row * S + c] = ni;
+            }
+            if (row == p) {
+                used = true;
+                if (cg == 0) {
+                    prow[jc] = p;
+                    jrow[p] = jc;
+                }
+            }
+        }
+        if constexpr (TR > 1) {
+            // the rank-16 update of the other column tiles: T C = mask(C) + W C[pivot rows]
+            const int tp = j0 >> 4, q = lane >> 4, c16 = lane & 15;
+            const bool busy = wave < TR && wave * 16 < n;  // (wave-uniform)
+            double wr[4], wi[4], br[TR - 1][4], bi[TR - 1][4];
+            surf_d4 accr[TR - 1], acci[TR - 1];
+            __syncthreads();  // the panel's columns are W, its pivot rows are known
+            if (busy) {
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) {
+                    wr[ks] = ar[(wave * 16 + c16) * S + j0 + 4 * ks + q];
+                    wi[ks] = ai[(wave * 16 + c16) * S + j0 + 4 * ks + q];
+                }
+#pragma unroll
+                for (int t = 0; t < TR - 1; ++t) {
+                    const int tj = t < tp ? t : t + 1;  // (uniform)
+#pragma unroll
+                    for (int ks = 0; ks < 4; ++ks) {
+                        const int kk = 4 * ks + q;
+                        const int prw = kk < jn ? prow[j0 + kk] : 0;  // (steps beyond n: no pivot row, a zero operand)
+                        br[t][ks] = kk < jn ? ar[prw * S + tj * 16 + c16] : 0.0;
+                        bi[t][ks] = kk < jn ? ai[prw * S + tj * 16 + c16] : 0.0;
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ri = wave * 16 + q + 4 * r;
+                        const bool taken = jrow[ri] >= j0;  // a pivot row of this panel starts from zero
+                        accr[t][r] = taken ? 0.0 : ar[ri * S + tj * 16 + c16];
+                        acci[t][r] = taken ? 0.0 : ai[ri * S + tj * 16 + c16];
+                    }
+                }
+            }
+            __syncthreads();  // every operand is in registers
+            if (busy) {
+#pragma unroll
+                for (int t = 0; t < TR - 1; ++t) {
+                    const int tj = t < tp ? t : t + 1;
+                    if (tj * 16 < n) {  // (uniform: the columns beyond n are zero and stay zero)
+#pragma unroll
+                        for (int ks = 0; ks < 4; ++ks) {
+                            accr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[ks], br[t][ks], accr[t], 0, 0, 0);
+                            acci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[ks], bi[t][ks], acci[t], 0, 0, 0);
+                            accr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wi[ks], bi[t][ks], accr[t], 0, 0, 1);  // - w_i b_i
+                            acci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wi[ks], br[t][ks], acci[t], 0, 0, 0);
+                        }
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int ri = wave * 16 + q + 4 * r;
+                            ar[ri * S + tj * 16 + c16] = accr[t][r];
+                            ai[ri * S + tj * 16 + c16] = acci[t][r];
+                        }
+                    }
+                }
+            }
+        }
+    }
+    return singular;
+}
+
+// The same integer, opaque to the optimiser and not to be moved out of a loop: offsets derived from it are computed where they are
+// used.  Without it every address of the iteration's tiles -- 16 per plane, ten planes, 64 bits each at NP = 64 -- is hoisted in
+// front of the item loop and the kernel spills: 2 800 bytes of scratch per thread at NP = 64 in the first build, which
+// tests/test_dpp_hazards.py::test_no_product_kernel_spills reports.  If that test fails on this kernel after a
+// compiler change, look here first.
+__device__ __forceinline__ int surf_fresh(int x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+// ---- the products -------------------------------------------------------------------------------------------------------------------
+// C = A B of two NP x NP complex matrices in planes (pitches SA, SB), zero beyond n: the wave's NT tiles (tile row (wave NT) / TR,
+// tile columns from (wave NT) % TR on) into registers.  Lane (q = lane / 16, c = lane % 16) feeds A[16 tr + c][k + q], B[k + q][16 tc + c]
+// and holds C[16 tr + q + 4 r][16 tc + c], r = 0 ... 3.  Tiles and K blocks beyond n are skipped (wave-uniform): they are zero.
+template <int NP, int NT, int SA, int SB>
+__device__ __forceinline__ void surf_product(const double* ar, const double* ai, const double* br, const double* bi, int n, int wave, int lane,
+                                             surf_d4 (&cr)[NT], surf_d4 (&ci)[NT]) {
+    constexpr int TR = NP / 16;
+    lane = surf_fresh(lane);
+    const int q = lane >> 4, c16 = lane & 15;
+    const int tr = (wave * NT) / TR, tc0 = (wave * NT) % TR;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) cr[t] = ci[t] = surf_d4{0.0, 0.0, 0.0, 0.0};
+    if (tr * 16 >= n) return;
+#pragma unroll 1
+    for (int kb = 0; kb < TR; ++kb) {  // (not unrolled: the loads of every K block ahead of the first MFMA do not fit the registers)
+        if (kb * 16 < n) {
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const int kk = kb * 16 + 4 * ks + q;
+                const double a_r = ar[(tr * 16 + c16) * SA + kk], a_i = ai[(tr * 16 + c16) * SA + kk];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    if ((tc0 + t) * 16 < n) {
+                        const double b_r = br[kk * SB + (tc0 + t) * 16 + c16], b_i = bi[kk * SB + (tc0 + t) * 16 + c16];
+                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_r, b_r, cr[t], 0, 0, 0);
+                        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_r, b_i, ci[t], 0, 0, 0);
+                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_i, b_i, cr[t], 0, 0, 1);  // - a_i b_i
+                        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_i, b_r, ci[t], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// the wave's tiles of a product into a matrix (ADD: added to it); every element has one owner, whatever the matrix
+template <int NP, int NT, int SD, bool ADD>
+__device__ __forceinline__ void surf_tiles(double* dr, double* di, int n, int wave, int lane, const surf_d4 (&cr)[NT], const surf_d4 (&ci)[NT]) {
+    constexpr int TR = NP / 16;
+    lane = surf_fresh(lane);
+    const int q = lane >> 4, c16 = lane & 15;
+    const int tr = (wave * NT) / TR, tc0 = (wave * NT) % TR;
+    if (tr * 16 >= n) return;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        if ((tc0 + t) * 16 < n) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int at = (tr * 16 + q + 4 * r) * SD + (tc0 + t) * 16 + c16;
+                if (ADD) {
+                    dr[at] += cr[t][r];
+                    di[at] += ci[t][r];
+                } else {
+                    dr[at] = cr[t][r];
+                    di[at] = ci[t][r];
+                }
+            }
+        }
+    }
+}
+
+// |A|_inf and |B|_inf, row sums of |re| + |im| (the padding is zero): a thread sums NP / PARTS columns of its row, the first NP
+// threads add the parts in order, every thread takes the maximum over the rows.  A NaN counts as +inf.  Two barriers inside; the
+// matrices must be visible before the call.
+template <int NP, int THREADS, int SM>
+__device__ __forceinline__ void surf_norms(const double* ar, const double* ai, const double* br, const double* bi, int tid, double* red, double* rown,
+                                           double& na, double& nb) {
+    constexpr int PARTS = THREADS / NP, CPP = NP / PARTS;
+    tid = surf_fresh(tid);
+    const int row = tid & (NP - 1), part = tid / NP;
+    double sa = 0.0, sb = 0.0;
+#pragma unroll 4
+    for (int cc = 0; cc < CPP; ++cc) {
+        const int at = row * SM + part * CPP + cc;
+        sa += fabs(ar[at]) + fabs(ai[at]);
+        sb += fabs(br[at]) + fabs(bi[at]);
+    }
+    red[tid] = sa;
+    red[THREADS + tid] = sb;
+    __syncthreads();
+    if (tid < NP) {
+        double a = 0.0, b = 0.0;
+#pragma unroll
+        for (int p = 0; p < PARTS; ++p) {
+            a += red[p * NP + tid];
+            b += red[THREADS + p * NP + tid];
+        }
+        rown[tid] = a;
+        rown[NP + tid] = b;
+    }
+    __syncthreads();
+    na = 0.0;
+    nb = 0.0;
+#pragma unroll 4
+    for (int r = 0; r < NP; ++r) {
+        double a = rown[r], b = rown[NP + r];
+        if (!(a <= SURF_DBL_MAX)) a = __builtin_inf();
+        if (!(b <= SURF_DBL_MAX)) b = __builtin_inf();
+        na = a > na ? a : na;
+        nb = b > nb ? b : nb;
+    }
+}
+
+// X = z 1 - M, zeros beyond n; jrow cleared for the elimination
+template <int NP, int THREADS, int SM>
+__device__ __forceinline__ void surf_form(double* xr, double* xi, const double* mr, const double* mi, double2 zz, int n, int tid, int* jrow) {
+    constexpr int S = NP + 1;
+    tid = surf_fresh(tid);
+#pragma unroll 2
+    for (int e = tid; e < NP * NP; e += THREADS) {
+        const int i = e / NP, c = e - i * NP;
+        double vr = 0.0, vi = 0.0;
+        if (i < n && c < n) {
+            vr = (i == c ? zz.x : 0.0) - mr[i * SM + c];
+            vi = (i == c ? zz.y : 0.0) - mi[i * SM + c];
+        }
+        xr[i * S + c] = vr;
+        xi[i * S + c] = vi;
+    }
+    if (tid < NP) jrow[tid] = -1;
+}
+
+// The planes of one workgroup (pitches: X, Y NP + 1; the others SurfGeom<NP>::SM) and its small tables.
+struct SurfPlanes {
+    double *xr, *xi, *yr, *yi;
+    double *alr, *ali, *ber, *bei, *er, *ei, *esr, *esi, *etr, *eti;
+    double* more;  // the matrices behind the five (the transmission's P)
+    double *red, *rown;
+    int *prow, *jrow;
+};
+
+// The planes of this workgroup: X and Y in LDS; MATS matrices (alpha, beta, e, es, et first) behind them up to NP = 32, in the
+// workgroup's slot of ws at NP = 64; then the tables.
+template <int NP, int MATS>
+__device__ __forceinline__ SurfPlanes surf_planes(double* lds, double* ws) {
+    using Geo = SurfGeom<NP>;
+    constexpr int PX = NP * Geo::S, PM = NP * Geo::SM;
+    SurfPlanes P;
+    P.xr = lds;
+    P.xi = P.xr + PX;
+    P.yr = P.xi + PX;
+    P.yi = P.yr + PX;
+    double* mats;
+    if constexpr (Geo::GLOBAL) {
+        mats = ws + (size_t)blockIdx.x * ((size_t)2 * MATS * PM);
+        P.red = P.yi + PX;
+    } else {
+        mats = P.yi + PX;
+        P.red = mats + 2 * MATS * PM;
+    }
+    P.alr = mats;
+    P.ali = mats + PM;
+    P.ber = mats + 2 * PM;
+    P.bei = mats + 3 * PM;
+    P.er = mats + 4 * PM;
+    P.ei = mats + 5 * PM;
+    P.esr = mats + 6 * PM;
+    P.esi = mats + 7 * PM;
+    P.etr = mats + 8 * PM;
+    P.eti = mats + 9 * PM;
+    P.more = mats + 10 * PM;
+    P.rown = P.red + 2 * Geo::THREADS;
+    P.prow = reinterpret_cast<int*>(P.rown + 2 * NP);
+    P.jrow = P.prow + NP;
+    return P;
+}
+
+// es = et = e = H00, alpha = H01, beta = H01^H of one in-plane point into the planes, zeros beyond n (one barrier at the end)
+template <int NP>
+__device__ __forceinline__ void surf_load(const SurfPlanes& P, const double2* h0, const double2* h1, bool hops, int n, int tid) {
+    using Geo = SurfGeom<NP>;
+    constexpr int THREADS = Geo::THREADS, SM = Geo::SM;
+    double *alr = P.alr, *ali = P.ali, *ber = P.ber, *bei = P.bei, *er = P.er, *ei = P.ei, *esr = P.esr, *esi = P.esi, *etr = P.etr, *eti = P.eti;
+#pragma unroll 2
+    for (int e = tid; e < NP * NP; e += THREADS) {
+        const int i = e / NP, c = e - i * NP;
+        double2 a = make_double2(0.0, 0.0), b = make_double2(0.0, 0.0);
+        if (i < n && c < n) {
+            a = h0[(size_t)i * n + c];
+            if (hops) b = h1[(size_t)i * n + c];
+        }
+        er[i * SM + c] = esr[i * SM + c] = etr[i * SM + c] = a.x;
+        ei[i * SM + c] = esi[i * SM + c] = eti[i * SM + c] = a.y;
+        alr[i * SM + c] = b.x;
+        ali[i * SM + c] = b.y;
+        ber[c * SM + i] = b.x;
+        bei[c * SM + i] = -b.y;
+    }
+    __syncthreads();
+}
+
+// The iteration of the header on loaded planes: the count into `it`, returns 0, 1 (singular) or 2 (the cap was reached), the same
+// on every thread.  Afterwards es and et are final, alpha, beta, e, X and Y are free.
+template <int NP>
+__device__ __forceinline__ int surf_iterate(const SurfPlanes& P, double2 zz, int n, int max_it, int tid, int& it) {
+    using Geo = SurfGeom<NP>;
+    constexpr int THREADS = Geo::THREADS, S = Geo::S, SM = Geo::SM, NT = Geo::NT;
+    const int lane = tid & 63, wave = tid >> 6;
+    double *xr = P.xr, *xi = P.xi, *yr = P.yr, *yi = P.yi;
+    double *alr = P.alr, *ali = P.ali, *ber = P.ber, *bei = P.bei, *er = P.er, *ei = P.ei, *esr = P.esr, *esi = P.esi, *etr = P.etr, *eti = P.eti;
+    double *red = P.red, *rown = P.rown;
+    int *prow = P.prow, *jrow = P.jrow;
+    int status = 0;
+    it = 0;
+    double na, nb;
+    surf_norms<NP, THREADS, SM>(alr, ali, ber, bei, tid, red, rown, na, nb);
+    const double threshold = na * 0x1p-53;
+    for (;;) {
+        ++it;
+        surf_form<NP, THREADS, SM>(xr, xi, er, ei, zz, n, tid, jrow);
+        const bool zero_pivot = surf_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
+        __syncthreads();
+#pragma unroll 2
+        for (int e = tid; e < NP * NP; e += THREADS) {  // g into Y, the permutations undone
+            const int i = e / NP, c = e - i * NP;
+            double vr = 0.0, vi = 0.0;
+            if (i < n && c < n) {
+                const int at = prow[i] * S + jrow[c];
+                vr = xr[at];
+                vi = xi[at];
+            }
+            yr[i * S + c] = vr;
+            yi[i * S + c] = vi;
+        }
+        __syncthreads();
+        surf_d4 tr[NT], ti[NT], p1r[NT], p1i[NT], p4r[NT], p4i[NT];
+        surf_product<NP, NT, S, SM>(yr, yi, alr, ali, n, wave, lane, tr, ti);  // T = g alpha
+        surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, tr, ti);
+        __syncthreads();
+        surf_product<NP, NT, SM, S>(alr, ali, xr, xi, n, wave, lane, p1r, p1i);  // alpha g alpha
+        surf_product<NP, NT, SM, S>(ber, bei, xr, xi, n, wave, lane, tr, ti);    // beta g alpha
+        surf_tiles<NP, NT, SM, true>(etr, eti, n, wave, lane, tr, ti);
+        surf_tiles<NP, NT, SM, true>(er, ei, n, wave, lane, tr, ti);
+        __syncthreads();  // T has been read
+        surf_product<NP, NT, S, SM>(yr, yi, ber, bei, n, wave, lane, tr, ti);  // T = g beta
+        surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, tr, ti);
+        __syncthreads();
+        surf_product<NP, NT, SM, S>(alr, ali, xr, xi, n, wave, lane, tr, ti);  // alpha g beta
+        surf_tiles<NP, NT, SM, true>(esr, esi, n, wave, lane, tr, ti);
+        surf_tiles<NP, NT, SM, true>(er, ei, n, wave, lane, tr, ti);
+        surf_product<NP, NT, SM, S>(ber, bei, xr, xi, n, wave, lane, p4r, p4i);  // beta g beta
+        __syncthreads();  // alpha and beta have been read
+        surf_tiles<NP, NT, SM, false>(alr, ali, n, wave, lane, p1r, p1i);
+        surf_tiles<NP, NT, SM, false>(ber, bei, n, wave, lane, p4r, p4i);
+        __syncthreads();
+        surf_norms<NP, THREADS, SM>(alr, ali, ber, bei, tid, red, rown, na, nb);
+        const double size = na > nb ? na : nb;
+        if (zero_pivot || !(size <= SURF_DBL_MAX)) {
+            status = 1;
+            break;
+        }
+        if (size <= threshold) break;
+        if (it >= max_it) {
+            status = 2;
+            break;
+        }
+    }
+    return status;
+}
+
+// ---- the transmission (tools/transport_model.py) ----------------------------------------------------------------
+//   D_1 = et + V_1;  for p = 1 ... M:  (p = M: D_p += es - H00)  g_p = (z - D_p)^-1,  P_p = g_p (p = 1), g_p (H01^H P_{p-1}) (p > 1),
+//   D_{p+1} = (H00 + V_{p+1}) + H01^H (g_p H01);   T = Re tr[(Gamma_R P_M) (Gamma_L P_M^H)],  Gamma = i (e - e^H) of es and et.
+// After the decimation alpha, beta and e are dead: their planes take H01, H01^H (the prologue's loads again) and D; P is a sixth
+// matrix behind et (LDS up to NP = 32: 140 032 bytes there; the slot of 12 planes at NP = 64).
+template <int NP>
+struct TransGeom {
+    using Geo = SurfGeom<NP>;
+    static constexpr int MATS = 6;
+    static constexpr size_t lds_bytes = Geo::lds_bytes + (Geo::GLOBAL ? 0 : (size_t)2 * NP * Geo::S * sizeof(double));
+    static constexpr size_t slot_doubles = Geo::GLOBAL ? (size_t)2 * MATS * NP * NP : 0;
+};
+
+// the wave's tiles of a product into D = (H00 + V) + product (zero beyond n); h0, v: [n][n] in global memory, read once
+template <int NP, int NT, int SD>
+__device__ __forceinline__ void trans_tiles_onsite(double* dr, double* di, const double2* __restrict__ h0, const double2* __restrict__ v, int n, int wave,
+                                                   int lane, const surf_d4 (&cr)[NT], const surf_d4 (&ci)[NT]) {
+    constexpr int TR = NP / 16;
+    lane = surf_fresh(lane);
+    const int q = lane >> 4, c16 = lane & 15;
+    const int tr = (wave * NT) / TR, tc0 = (wave * NT) % TR;
+    if (tr * 16 >= n) return;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        if ((tc0 + t) * 16 < n) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = tr * 16 + q + 4 * r, c = (tc0 + t) * 16 + c16;
+                double vr = 0.0, vi = 0.0;
+                if (i < n && c < n) {
+                    const double2 a = h0[(size_t)i * n + c], b = v[(size_t)i * n + c];
+                    vr = (a.x + b.x) + cr[t][r];
+                    vi = (a.y + b.y) + ci[t][r];
+                }
+                dr[i * SD + c] = vr;
+                di[i * SD + c] = vi;
+            }
+        }
+    }
+}
+
+// the wave's tiles of a product into g [n][n] complex in global memory (rows and columns below n); one owner per element
+template <int NP, int NT>
+__device__ __forceinline__ void trans_tiles_stack(double2* g, int n, int wave, int lane, const surf_d4 (&cr)[NT], const surf_d4 (&ci)[NT]) {
+    constexpr int TR = NP / 16;
+    lane = surf_fresh(lane);
+    const int q = lane >> 4, c16 = lane & 15;
+    const int tr = (wave * NT) / TR, tc0 = (wave * NT) % TR;
+    if (tr * 16 >= n) return;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        if ((tc0 + t) * 16 < n) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = tr * 16 + q + 4 * r, c = (tc0 + t) * 16 + c16;
+                if (i < n && c < n) g[(size_t)i * n + c] = make_double2(cr[t][r], ci[t][r]);
+            }
+        }
+    }
+}
+
+// The sweep on the planes surf_iterate leaves (es and et final), shared by transmission_kernel and device_green_kernel
+// (tbk_device_green.hip).  H01, H01^H and D live in the planes of alpha, beta and e, P in the sixth matrix.
+// trans_start: H01 and H01^H again; D_1 = et + V_1 (one barrier at the end)
+template <int NP>
+__device__ __forceinline__ void trans_start(const SurfPlanes& P, const double2* __restrict__ h1, const double2* __restrict__ V, int n, int tid) {
+    using Geo = SurfGeom<NP>;
+    constexpr int THREADS = Geo::THREADS, SM = Geo::SM;
+    double *h01r = P.alr, *h01i = P.ali, *h10r = P.ber, *h10i = P.bei, *dr = P.er, *di = P.ei, *etr = P.etr, *eti = P.eti;
+#pragma unroll 2
+    for (int e = tid; e < NP * NP; e += THREADS) {  // H01 and H01^H again; D_1 = et + V_1
+        const int i = e / NP, c = e - i * NP;
+        double2 b = make_double2(0.0, 0.0), d = make_double2(0.0, 0.0);
+        if (i < n && c < n) {
+            b = h1[(size_t)i * n + c];
+            const double2 v = V[(size_t)i * n + c];
+            d = make_double2(etr[i * SM + c] + v.x, eti[i * SM + c] + v.y);
+        }
+        h01r[i * SM + c] = b.x;
+        h01i[i * SM + c] = b.y;
+        h10r[c * SM + i] = b.x;
+        h10i[c * SM + i] = -b.y;
+        dr[i * SM + c] = d.x;
+        di[i * SM + c] = d.y;
+    }
+    __syncthreads();
+}
+
+// Layer p (from 0) of the sweep: g_p into Y, P_p into P's planes, D_{p+1} into D's.  Returns whether a pivot was zero or an element
+// of g_p not finite (this thread's share).  STACK: g_p goes to stack[2 p] and H01^H P_{p-1} (p > 0) to stack[2 p + 1], [n][n] complex
+// each, by the threads that own the elements; a barrier stands between these stores and whatever the workgroup reads of them later.
+template <int NP, bool STACK>
+__device__ __forceinline__ bool trans_layer(const SurfPlanes& P, const double2* __restrict__ h0, const double2* __restrict__ V, double2 zz, int p,
+                                            int m_layers, int n, int tid, double2* stack) {
+    using Geo = SurfGeom<NP>;
+    constexpr int THREADS = Geo::THREADS, S = Geo::S, SM = Geo::SM, NT = Geo::NT;
+    constexpr int PM = NP * SM;
+    const int lane = tid & 63, wave = tid >> 6;
+    double *xr = P.xr, *xi = P.xi, *yr = P.yr, *yi = P.yi;
+    double *h01r = P.alr, *h01i = P.ali, *h10r = P.ber, *h10i = P.bei, *dr = P.er, *di = P.ei, *esr = P.esr, *esi = P.esi;
+    double *pr = P.more, *pi = P.more + PM;
+    int *prow = P.prow, *jrow = P.jrow;
+    bool bad = false;
+    if (p == m_layers - 1) {  // the right lead: D_M += es - H00 (the elements surf_form gives this thread)
+#pragma unroll 2
+        for (int e = tid; e < NP * NP; e += THREADS) {
+            const int i = e / NP, c = e - i * NP;
+            if (i < n && c < n) {
+                const double2 a = h0[(size_t)i * n + c];
+                dr[i * SM + c] += esr[i * SM + c] - a.x;
+                di[i * SM + c] += esi[i * SM + c] - a.y;
+            }
+        }
+    }
+    surf_form<NP, THREADS, SM>(xr, xi, dr, di, zz, n, tid, jrow);
+    bad |= surf_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
+    __syncthreads();
+#pragma unroll 2
+    for (int e = tid; e < NP * NP; e += THREADS) {  // g_p into Y, the permutations undone
+        const int i = e / NP, c = e - i * NP;
+        double vr = 0.0, vi = 0.0;
+        if (i < n && c < n) {
+            const int at = prow[i] * S + jrow[c];
+            vr = xr[at];
+            vi = xi[at];
+            bad |= !(fabs(vr) <= SURF_DBL_MAX && fabs(vi) <= SURF_DBL_MAX);
+            if (STACK) stack[(size_t)2 * p * n * n + (size_t)i * n + c] = make_double2(vr, vi);
+        }
+        yr[i * S + c] = vr;
+        yi[i * S + c] = vi;
+        if (p == 0) {  // P_1 = g_1
+            pr[i * SM + c] = vr;
+            pi[i * SM + c] = vi;
+        }
+    }
+    __syncthreads();
+    surf_d4 cr[NT], ci[NT];
+    if (p > 0) {
+        surf_product<NP, NT, SM, SM>(h10r, h10i, pr, pi, n, wave, lane, cr, ci);  // T = H01^H P_{p-1}
+        surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
+        if (STACK) trans_tiles_stack<NP, NT>(stack + (size_t)(2 * p + 1) * n * n, n, wave, lane, cr, ci);
+        __syncthreads();
+        surf_product<NP, NT, S, S>(yr, yi, xr, xi, n, wave, lane, cr, ci);  // P_p = g_p T
+        surf_tiles<NP, NT, SM, false>(pr, pi, n, wave, lane, cr, ci);
+        __syncthreads();  // T has been read
+    }
+    if (p + 1 < m_layers) {
+        surf_product<NP, NT, S, SM>(yr, yi, h01r, h01i, n, wave, lane, cr, ci);  // T = g_p H01
+        surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
+        __syncthreads();
+        surf_product<NP, NT, SM, S>(h10r, h10i, xr, xi, n, wave, lane, cr, ci);  // H01^H g_p H01
+        trans_tiles_onsite<NP, NT, SM>(dr, di, h0, V + (size_t)(p + 1) * n * n, n, wave, lane, cr, ci);
+        __syncthreads();
+    }
+    return bad;
+}
+
+// The closing of the sweep: P_M is looked at (returns whether an element of this thread's share is not finite) and leaves to g_out
+// unless that is NULL; T = Re tr[(Gamma_R P_M) (Gamma_L P_M^H)] and the count of the decimation go to *T_at and *it_at.  X, Y and D's
+// planes are overwritten; P, es, et, H01 and H01^H stay.
+template <int NP>
+__device__ __forceinline__ bool trans_closing(const SurfPlanes& P, int n, int tid, double2* g_out, double* T_at, int32_t* it_at, int it) {
+    using Geo = SurfGeom<NP>;
+    constexpr int THREADS = Geo::THREADS, S = Geo::S, SM = Geo::SM, NT = Geo::NT;
+    constexpr int PM = NP * SM;
+    const int lane = tid & 63, wave = tid >> 6;
+    double *xr = P.xr, *xi = P.xi, *yr = P.yr, *yi = P.yi;
+    double *dr = P.er, *di = P.ei, *esr = P.esr, *esi = P.esi, *etr = P.etr, *eti = P.eti;
+    double *pr = P.more, *pi = P.more + PM;
+    double *red = P.red, *rown = P.rown;
+    bool bad = false;
+#pragma unroll 2
+    for (int e = tid; e < NP * NP; e += THREADS) {  // Gamma_R into X, P_M^H into D's planes; P_M is looked at and leaves
+        const int i = e / NP, c = e - i * NP;
+        double gr = 0.0, gi = 0.0, ar = 0.0, ai = 0.0;
+        if (i < n && c < n) {
+            gr = -(esi[i * SM + c] + esi[c * SM + i]);
+            gi = esr[i * SM + c] - esr[c * SM + i];
+            ar = pr[c * SM + i];
+            ai = -pi[c * SM + i];
+            const double2 v = make_double2(pr[i * SM + c], pi[i * SM + c]);
+            bad |= !(fabs(v.x) <= SURF_DBL_MAX && fabs(v.y) <= SURF_DBL_MAX);
+            if (g_out != nullptr) g_out[(size_t)i * n + c] = v;
+        }
+        xr[i * S + c] = gr;
+        xi[i * S + c] = gi;
+        dr[i * SM + c] = ar;
+        di[i * SM + c] = ai;
+    }
+    __syncthreads();
+    {
+        surf_d4 cr[NT], ci[NT];
+        surf_product<NP, NT, S, SM>(xr, xi, pr, pi, n, wave, lane, cr, ci);  // Gamma_R P_M into Y
+        surf_tiles<NP, NT, S, false>(yr, yi, n, wave, lane, cr, ci);
+        __syncthreads();  // Gamma_R has been read
+#pragma unroll 2
+        for (int e = tid; e < NP * NP; e += THREADS) {  // Gamma_L into X
+            const int i = e / NP, c = e - i * NP;
+            double gr = 0.0, gi = 0.0;
+            if (i < n && c < n) {
+                gr = -(eti[i * SM + c] + eti[c * SM + i]);
+                gi = etr[i * SM + c] - etr[c * SM + i];
+            }
+            xr[i * S + c] = gr;
+            xi[i * S + c] = gi;
+        }
+        __syncthreads();
+        surf_product<NP, NT, S, SM>(xr, xi, dr, di, n, wave, lane, cr, ci);  // Gamma_L P_M^H into X
+        __syncthreads();  // Gamma_L has been read
+        surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
+        __syncthreads();
+    }
+    {
+        // Re sum_ij Y[i][j] X[j][i] in a fixed order: a thread sums NP / PARTS columns of its row, the first NP threads add the
+        // parts in order, thread 0 the rows
+        constexpr int PARTS = THREADS / NP, CPP = NP / PARTS;
+        const int row = tid & (NP - 1), part = tid / NP;
+        double sum = 0.0;
+#pragma unroll 4
+        for (int cc = 0; cc < CPP; ++cc) {
+            const int c = part * CPP + cc;
+            if (row < n && c < n) sum += yr[row * S + c] * xr[c * S + row] - yi[row * S + c] * xi[c * S + row];
+        }
+        red[tid] = sum;
+        __syncthreads();
+        if (tid < NP) {
+            double a = 0.0;
+#pragma unroll
+            for (int q = 0; q < PARTS; ++q) a += red[q * NP + tid];
+            rown[tid] = a;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double total = 0.0;
+#pragma unroll 4
+            for (int r = 0; r < NP; ++r) total += rown[r];
+            *T_at = total;
+            *it_at = it;
+        }
+        __syncthreads();  // the tables are free again
+    }
+    return bad;
+}
+
+// Hs: [n_k][2 L + 1][n][n], the full H(k) at k_a = j / (2 L + 1); tw: [2 L + 1][2 L + 1][2] (cos, sin) of -2 pi ((m j) mod (2 L + 1)) /
+// (2 L + 1), row m + L.  One workgroup per in-plane point writes H00 and, L > 0, H01 [N][N], N = n max(L, 1): block (p, q) of H00 is
+// H_{q-p}, of H01 H_{L+q-p} for q <= p and zero above.  H_m = (sum_j tw[m][j] Hs[j]) / (2 L + 1), j ascending.
+__global__ void __launch_bounds__(256) surface_layers_kernel(const double2* __restrict__ Hs, const double* __restrict__ tw, int n, int L,
+                                                             double2* __restrict__ H00, double2* __restrict__ H01) {
+    const int M = 2 * L + 1, N = n * (L > 0 ? L : 1);
+    const double2* hs = Hs + (size_t)blockIdx.x * M * n * n;
+    double2* o0 = H00 + (size_t)blockIdx.x * N * N;
+    double2* o1 = L > 0 ? H01 + (size_t)blockIdx.x * N * N : nullptr;
+    for (int e = (int)threadIdx.x; e < N * N; e += 256) {
+        const int I = e / N, J = e - I * N;
+        const int p = I / n, i = I - p * n, q = J / n, j = J - q * n;
+        for (int part = 0; part < (L > 0 ? 2 : 1); ++part) {
+            const int m = part == 0 ? q - p : L + q - p;
+            double sr = 0.0, si = 0.0;
+            if (part == 0 || q <= p) {
+                for (int s = 0; s < M; ++s) {
+                    const double c = tw[((size_t)(m + L) * M + s) * 2], d = tw[((size_t)(m + L) * M + s) * 2 + 1];
+                    const double2 h = hs[((size_t)s * n + i) * n + j];
+                    sr += c * h.x - d * h.y;
+                    si += c * h.y + d * h.x;
+                }
+                sr /= (double)M;
+                si /= (double)M;
+            }
+            (part == 0 ? o0 : o1)[e] = make_double2(sr, si);
+        }
+    }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+int64_t surf_grid(int n, int64_t items, int n_cu) {
+    if (n > 32) return std::min<int64_t>(items, std::max(1, n_cu));  // one resident workgroup per CU, each with a workspace slot
+    return std::min<int64_t>(items, int64_t(1) << 30);
+}
+
+// what every call checks of its sizes, energies and cap
+int surf_check_energies(int N, int64_t n_z, const double* z, int max_iterations) {
+    TBK_ARG(N >= 1, "a principal layer has no rows");
+    if (N > SURF_LIB_MAX) {
+        tbk_set_error("invalid argument: a principal layer of %d rows: the decimation takes at most %d", N, SURF_LIB_MAX);
+        return TBK_ERR_ARGUMENT;
+    }
+    TBK_ARG(n_z >= 1 && n_z <= SURF_MAX_Z, "n_z must be 1 to 4096");
+    TBK_ARG(z != nullptr, "z is NULL");
+    for (int64_t i = 0; i < n_z; ++i) {
+        TBK_ARG(std::isfinite(z[2 * i]) && std::isfinite(z[2 * i + 1]), "an energy z is not finite");
+        TBK_ARG(z[2 * i + 1] != 0.0, "every z needs Im z != 0");
+    }
+    TBK_ARG(max_iterations >= 1 && max_iterations <= SURF_MAX_ITERATIONS, "max_iterations must be 1 to 4096");
+    return TBK_OK;
+}
+
+// the status word as an error: the first (point, energy) of the call that failed
+int surf_status_error(unsigned long long word, const double* z, int max_iterations, const char* what = "z - e of the decimation") {
+    if (word == SURF_NO_FLAG) return TBK_OK;
+    const int reason = (int)(word & 1ull);
+    const unsigned long long key = word >> 1;
+    const long long point = (long long)(key / (unsigned long long)SURF_MAX_Z), zi = (long long)(key % (unsigned long long)SURF_MAX_Z);
+    if (reason == 0) {
+        tbk_set_error("Singular matrix: %s at k index %lld and energy %lld (z = %.17g%+.17gj)", what, point, zi, z[2 * zi], z[2 * zi + 1]);
+        return TBK_ERR_SINGULAR;
+    }
+    tbk_set_error("the decimation did not converge in %d iterations at k index %lld and energy %lld (z = %.17g%+.17gj)", max_iterations, point, zi,
+                  z[2 * zi], z[2 * zi + 1]);
+    return TBK_ERR_NO_CONVERGENCE;
+}
+
+int surf_device_cus(int device) {
+    int n_cu = 0;
+    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 1) n_cu = 256;
+    return n_cu;
+}
+
+// The host lists of a whole call: per in-plane point the 2 L + 1 full k-points (k_a = j / (2 L + 1) inserted at `axis`), and the
+// twiddles of surface_layers_kernel.
+int surf_host_lists(int dim, int axis, int L, const double* k, int64_t nk, std::vector<double>& h_k, std::vector<double>& h_tw) {
+    const int M = 2 * L + 1;
+    try {
+        h_k.resize((size_t)nk * M * dim);
+        h_tw.resize((size_t)M * M * 2);
+    } catch (...) {
+        tbk_set_error("cannot allocate the k list");
+        return TBK_ERR_MEMORY;
+    }
+    for (int64_t i = 0; i < nk; ++i)
+        for (int j = 0; j < M; ++j) {
+            double* dst = &h_k[((size_t)i * M + j) * dim];
+            for (int d = 0, s = 0; d < dim; ++d) dst[d] = d == axis ? (double)j / (double)M : k[(size_t)i * (dim - 1) + s++];
+        }
+    const double two_pi = 6.283185307179586476925286766559;
+    for (int mm = -L; mm <= L; ++mm)
+        for (int j = 0; j < M; ++j) {
+            const int num = ((mm * j) % M + M) % M;
+            const double angle = -two_pi * (double)num / (double)M;
+            h_tw[((size_t)(mm + L) * M + j) * 2] = std::cos(angle);
+            h_tw[((size_t)(mm + L) * M + j) * 2 + 1] = std::sin(angle);
+        }
+    return TBK_OK;
+}
+
+// The chunk's principal layers: the FULL H(k) of its samples (d_k: the chunk's first), by the routine tbk_eigh_device uses, in pieces
+// of its own choice, then surface_layers_kernel.  Stage 0 of the call's timer.
+int surf_chunk_layers(tbk_model* m, SpanRecorder* ev, const double* d_k, int64_t nkc, int L, double* d_H, const double* d_tw, double2* d_H00,
+                      double2* d_H01) {
+    const int dim = m->dim, n_orb = m->n_orb, M = 2 * L + 1;
+    const size_t nn2 = (size_t)n_orb * n_orb * 2;
+    const int64_t npts = nkc * M;
+    if (ev) ev->start(0);
+    const int64_t piece = choose_chunk(m, npts, false);
+    for (int64_t p0 = 0; p0 < npts; p0 += piece) {
+        const int64_t np = std::min(piece, npts - p0);
+        const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), np, false);
+        TBK_CHECK(chunk_h(m, plan, HK_FULL, 2, d_k + (size_t)p0 * dim, nullptr, tbk_one_k_t(), d_H + (size_t)p0 * nn2));
+    }
+    hipLaunchKernelGGL(surface_layers_kernel, dim3((unsigned)nkc), dim3(256), 0, m->stream, reinterpret_cast<const double2*>(d_H), d_tw, n_orb, L, d_H00,
+                       d_H01);
+    TBK_HIP(hipGetLastError());
+    if (ev) ev->stop();
+    return TBK_OK;
+}
+
+// ---- the transmission: host ------------------------------------------------------------------------------------------------------------
+constexpr const char* TRANS_SINGULAR = "z - D of a device layer, or z - e of the decimation,";
+constexpr int TRANS_MAX_LAYERS = 4096;
+constexpr size_t TRANS_DEVICE_BUDGET = size_t(256) << 20;  // the device potential V [M][N][N] complex
+
+// what the two entry points check of the device; M N^2 complex numbers are staged once per call
+int trans_check_device(int N, int M, const double* V, const int32_t* iterations, const double* T) {
+    TBK_ARG(M >= 1 && M <= TRANS_MAX_LAYERS, "the device must have 1 to 4096 principal layers");
+    if ((size_t)M * N * N * sizeof(double2) > TRANS_DEVICE_BUDGET) {
+        tbk_set_error("invalid argument: a device of %d layers of %d rows: V may take at most 256 MiB", M, N);
+        return TBK_ERR_ARGUMENT;
+    }
+    TBK_ARG(V != nullptr, "V is NULL");
+    TBK_ARG(iterations != nullptr && T != nullptr, "iterations / T is NULL");
+    return TBK_OK;
+}
+
+}  // namespace
