@@ -590,6 +590,37 @@ int tbk_device_green_multi(tbk_model* const* handles, int n_handles, int axis, i
  * the results to the host in this handle's calls made while TBK_OPT_TIMING was on; calls, reset as above. */
 int tbk_device_green_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
+/* ---- the bond currents of the device of tbk_device_green (not in the reference) --------------------------------------------------------
+ * Everything of tbk_device_green, unchanged down to the order of the operations, and with H_pp = H00 + V_p, per (kp, z):
+ *
+ *     A^L_{p,q} = (F_p Gamma_L) F_q^H            A^R_{p,q} = (C_p Gamma_R) C_q^H
+ *     K^L_p[i][j] = 2 Im(conj(H01[i][j]) A^L_{p,p+1}[i][j])   p = 1 ... M - 1     from orbital i of layer p to orbital j of layer p + 1
+ *     J^L_p[i][j] = 2 Im(conj(H_pp[i][j]) A^L_{p,p}[i][j])    p = 1 ... M         from orbital i to orbital j inside layer p
+ *     K^R, J^R: the same with A^R;    current_left[p][i] = sum_j K^L_p[i][j],  current_right[p][i] = sum_j K^R_p[i][j]
+ *
+ * in e / h per unit energy: the currents of the states injected from the left and from the right lead.  sum_i current_left[p][i] tends
+ * to T at every interface as Im z -> 0 and differs from the next interface's by 4 pi Im z sum_i left[p + 1][i]; K and J are exactly zero
+ * where H01 and H_pp are.  Results: iterations, T, ldos, left, right as tbk_device_green, bit for bit; current_left, current_right double
+ * [nk][n_z][M - 1][N]; and, the four bond arrays not NULL (all four or none), inter_left, inter_right (K) double [nk][n_z][M - 1][N][N] and
+ * intra_left, intra_right (J) double [nk][n_z][M][N][N].  Without the bond arrays J is not formed.  A non-finite element of a K or J
+ * that is formed is TBK_ERR_SINGULAR like one of a block.  The bits of one (kp, z) depend on nothing else, the bond arrays included.
+ * The kernel is tbk_device_green's with four more products per layer (two without the bond arrays); F_p and C_p wait for the layer below
+ * in the stack's places of g_p and H01^H Q_{p-1}, which are dead by then.  N <= 64; the argument errors are tbk_device_green's.
+ * Error per component of K^L_p: 2 max|H01| (c(F_p) + c(F_{p+1}) + 1) eps s(F_p) s(F_{p+1}) 2 |H01|^2 |G_top|. */
+int tbk_device_current_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, const double* V, int64_t n_z,
+                                     const double* z, int max_iterations, int64_t k_chunk, int64_t slots, int32_t* iterations, double* T,
+                                     double* ldos, double* left, double* right, double* current_left, double* current_right, double* inter_left,
+                                     double* inter_right, double* intra_left, double* intra_right);
+int tbk_device_current(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z, const double* z,
+                       int max_iterations, int32_t* iterations, double* T, double* ldos, double* left, double* right, double* current_left,
+                       double* current_right, double* inter_left, double* inter_right, double* intra_left, double* intra_right);
+int tbk_device_current_multi(tbk_model* const* handles, int n_handles, int axis, int layers, const double* k, int64_t nk, int M, const double* V,
+                             int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T, double* ldos, double* left,
+                             double* right, double* current_left, double* current_right, double* inter_left, double* inter_right,
+                             double* intra_left, double* intra_right);
+/* ms[3] as tbk_device_green_timing, of this handle's tbk_device_current calls. */
+int tbk_device_current_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
 /* ---- the bare (Lindhard) static susceptibility of a uniform k mesh (not in the reference) ----------------------------------------
  * Mesh and mesh points k = (i_1 / n_1, ..., i_dim / n_dim) are those of tbk_occupations (dim 2 or 3); k+q is the mesh point with the
  * indices (i_d + q_d) mod n_d.  With E, U the eigenvalues and eigenvectors of tbk_eigh (convention 2), T = k_B T > 0 in the model's

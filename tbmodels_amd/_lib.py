@@ -121,6 +121,13 @@ SIGNATURES = {
     "tbk_device_green": (_c_int, [_vp, _c_int, _c_int, _vp, _c_i64, _c_int, _vp, _c_i64, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tbk_device_green_multi": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_i64, _c_int, _vp, _c_i64, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tbk_device_green_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
+    "tbk_device_current_from_matrices": (_c_int, [_c_int, _c_int, _c_i64, _vp, _vp, _c_int, _vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tbk_device_current": (_c_int, [_vp, _c_int, _c_int, _vp, _c_i64, _c_int, _vp, _c_i64, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp]),
+    "tbk_device_current_multi": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_i64, _c_int, _vp, _c_i64, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp]),
+    "tbk_device_current_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
     "tbk_chi_from_eigensystem": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, _vp, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _vp, _vp]),
     "tbk_susceptibility": (_c_int, [_vp, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _c_int, _c_int, _vp, _vp, _vp]),
     "tbk_susceptibility_multi": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _c_int, _c_int, _vp, _vp, _vp]),

@@ -50,6 +50,8 @@ Transmission = co.namedtuple("Transmission", ("k", "z", "layers", "length", "ite
 TransmissionGreen = co.namedtuple("TransmissionGreen", Transmission._fields + ("green",))
 DeviceGreen = co.namedtuple("DeviceGreen", Transmission._fields + ("ldos", "left", "right"))
 DeviceGreenBlocks = co.namedtuple("DeviceGreenBlocks", DeviceGreen._fields + ("diagonal", "first", "last"))
+DeviceCurrent = co.namedtuple("DeviceCurrent", DeviceGreen._fields + ("current_left", "current_right"))
+DeviceCurrentBonds = co.namedtuple("DeviceCurrentBonds", DeviceCurrent._fields + ("inter_left", "inter_right", "intra_left", "intra_right"))
 Susceptibility = co.namedtuple("Susceptibility", ("mu", "q", "chi"))
 DynamicSusceptibility = co.namedtuple("DynamicSusceptibility", ("mu", "q", "omega", "chi"))
 OrbitalSusceptibility = co.namedtuple("OrbitalSusceptibility", ("mu", "q", "orbitals", "chi"))
@@ -1529,6 +1531,73 @@ class Model:
         if green:
             return DeviceGreenBlocks(k_array, energies, layers, count, iterations, result, ldos, left, right, blocks[0], blocks[1], blocks[2])
         return DeviceGreen(k_array, energies, layers, count, iterations, result, ldos, left, right)
+
+    def device_current(self, k, z, *, axis=-1, device=None, length=1, max_iterations=64, bonds=False):
+        """
+        The bond currents of the device of :meth:`device_green_function`: per interface, orbital and, on request, bond, the current
+        of the states injected from the left and from the right lead, on the GPU.  Not in the reference.
+
+        ``k``, ``z``, ``axis``, ``device``, ``length``, ``max_iterations`` and the error messages are those of
+        :meth:`transmission`; everything in front of the new lines is :meth:`device_green_function`, unchanged down to the order of
+        the operations.  Returns the named tuple ``(k, z, layers, length, iterations, transmission, ldos, left, right, current_left,
+        current_right[, inter_left, inter_right, intra_left, intra_right])``: ``current_left`` and ``current_right`` are ``float64
+        (NK, NZ, M - 1, N)``, empty along that axis for ``M = 1``; with ``bonds=True``, ``inter_left`` and ``inter_right`` hold
+        ``K`` as ``float64 (NK, NZ, M - 1, N, N)`` and ``intra_left`` and ``intra_right`` hold ``J`` as ``(NK, NZ, M, N, N)``.
+
+        Definition.  With ``F_p``, ``C_p``, ``Gamma_L``, ``Gamma_R`` of :meth:`device_green_function` and ``H_pp = H00 + V_p``, per
+        ``(kp, z)``::
+
+            A^L_{p,q} = (F_p Gamma_L) F_q^H            A^R_{p,q} = (C_p Gamma_R) C_q^H
+            K^L_p[i, j] = 2 Im(conj(H01[i, j]) A^L_{p,p+1}[i, j])    p = 1 ... M - 1   orbital i of layer p -> orbital j of layer p + 1
+            J^L_p[i, j] = 2 Im(conj(H_pp[i, j]) A^L_{p,p}[i, j])     p = 1 ... M       orbital i -> orbital j inside layer p
+            K^R, J^R: the same with A^R
+            current_left[p, i] = sum_j K^L_p[i, j]     current_right[p, i] = sum_j K^R_p[i, j]
+
+        in ``e / h`` per unit energy.  Products are formed as bracketed.  ``K^L`` flows towards the right lead (positive totals),
+        ``K^R`` towards the left (negative totals); ``f_L K^L + f_R K^R`` is the kernel of a biased current.  A non-finite element of
+        a ``K`` or ``J`` raises ``numpy.linalg.LinAlgError`` like one of a block.
+
+        Properties, with the signed ``eta = Im z``.  (1) ``sum K^L_{p-1} - sum K^L_p = 4 pi eta sum_i left[p, i]`` for ``1 < p < M``
+        and ``sum K^L_{M-1} - transmission = 4 pi eta sum_i left[M, i]``: the current is conserved as ``eta -> 0``, and every
+        interface then carries ``transmission``.  (2) Per orbital ``j`` of an interior layer: ``sum_i K^L_{p-1}[i, j] - sum_k
+        K^L_p[j, k] - sum_k J^L_p[j, k] = 4 pi eta left[p, j]``; the same with ``R`` and ``right``.  (3) ``sum K^R_{p-1} - sum K^R_p =
+        4 pi eta sum_i right[p, i]``.  (4) ``K`` is exactly zero where ``H01`` is, ``J`` where ``H_pp`` is, and ``J`` is
+        antisymmetric up to rounding (``H01`` and ``H00`` as the call takes them from Fourier sums of ``H(k)``: an absent hopping
+        is zero there up to rounding).  (5) ``iterations``, ``transmission``, ``ldos``, ``left`` and ``right`` have the bits of
+        :meth:`device_green_function`.  (6) The bits of one ``(kp, z)`` depend on nothing else: not on the other points or energies,
+        their order, the chunking, ``bonds``, or the number of devices.
+
+        Error bound per component, with ``E``, ``c`` and ``s`` of :meth:`device_green_function` and ``gamma_L = 2 |H01|^2 |G_top|``:
+        ``2 max|H01| (c(F_p) + c(F_{p+1}) + 1) E s(F_p) s(F_{p+1}) gamma_L`` for ``K^L_p``, ``2 max|H_pp| (2 c(F_p) + 1) E s(F_p)^2
+        gamma_L`` for ``J^L_p``, ``C`` and ``gamma_R`` for the right, ``N`` times ``K``'s for ``current_*``.
+
+        Work: that of :meth:`device_green_function` and, per layer, two more products on the FP64 matrix pipe (four with
+        ``bonds=True``, which forms ``J``), ``16 N^3`` (``32 N^3``) flops; ``F_p`` and ``C_p`` wait for the layer below in the
+        stack's places of ``g_p`` and ``H01^H Q_{p-1}``, which are dead by then.  Without ``bonds``, ``2 (M - 1) N`` more doubles
+        per ``(kp, z)`` leave the GPU; with it ``2 (2 M - 1) N^2`` more.  ``N`` is at most 64, else ``ValueError``.
+        """
+        energies, axis_index, cap, k_array, layers, potential = self._device_arguments(k, z, axis, max_iterations, device, length,
+                                                                                       "device_current", 64)
+        n_rows = self.size * layers
+        n_k, n_z, count = k_array.shape[0], energies.shape[0], potential.shape[0]
+        iterations = np.zeros((n_k, n_z), dtype=np.int32)
+        result = np.empty((n_k, n_z), dtype=np.float64)
+        ldos, left, right = (np.empty((n_k, n_z, count, n_rows), dtype=np.float64) for _ in range(3))
+        rows = [np.empty((n_k, n_z, count - 1, n_rows), dtype=np.float64) for _ in range(2)]
+        inter = [np.empty((n_k, n_z, count - 1, n_rows, n_rows), dtype=np.float64) if bonds else None for _ in range(2)]
+        intra = [np.empty((n_k, n_z, count, n_rows, n_rows), dtype=np.float64) if bonds else None for _ in range(2)]
+        with self._call_lock:
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_device_current_multi(handles, n_handles, axis_index, layers, _lib.ptr(k_array) if k_array.size else None, n_k, count,
+                                                    _lib.ptr(potential), n_z, _lib.ptr(energies), cap, _lib.ptr(iterations), _lib.ptr(result),
+                                                    _lib.ptr(ldos), _lib.ptr(left), _lib.ptr(right), _lib.ptr(rows[0]), _lib.ptr(rows[1]),
+                                                    _lib.ptr(inter[0]), _lib.ptr(inter[1]), _lib.ptr(intra[0]), _lib.ptr(intra[1]))
+            )
+        plain = DeviceCurrent(k_array, energies, layers, count, iterations, result, ldos, left, right, rows[0], rows[1])
+        if bonds:
+            return DeviceCurrentBonds(*plain, inter[0], inter[1], intra[0], intra[1])
+        return plain
 
     def susceptibility(self, mesh, q, *, temperature, energy=None, n_electrons=None, matrix_elements=True, convention=2):
         """

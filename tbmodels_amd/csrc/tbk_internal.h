@@ -178,11 +178,11 @@ struct SpanRecorder {
 };
 
 // The sums the mesh calls book their kernel times on, one row per family (tbk_dos_timing, tbk_pdos_timing, tbk_fermi_timing,
-// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing, tbk_surface_timing, tbk_transmission_timing, tbk_device_green_timing: what each counts differs and is
+// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing, tbk_surface_timing, tbk_transmission_timing, tbk_device_green_timing, tbk_device_current_timing: what each counts differs and is
 // listed in DESIGN.md section 10)
-enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_SURFACE, TIMED_TRANSMISSION, TIMED_DEVICE_GREEN, TIMED_COUNT };
+enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_SURFACE, TIMED_TRANSMISSION, TIMED_DEVICE_GREEN, TIMED_DEVICE_CURRENT, TIMED_COUNT };
 struct TimedSums {
-    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green, the dressed green, surface, transmission and the device green three)
+    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green, the dressed green, surface, transmission, the device green and the device current three)
     int64_t calls = 0;
     int64_t passes = 0;  // fermi: the passes of its searches
 };
@@ -396,6 +396,12 @@ int tbk_transmission_slab(tbk_model* m, int64_t k_base, int axis, int layers, co
 int tbk_device_green_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z,
                           const double* z, int max_iterations, int32_t* iterations, double* T, double* ldos, double* left, double* right, double* G,
                           double* F, double* C);
+
+// ... and tbk_device_current (the slabs of tbk_device_current_multi)
+int tbk_device_current_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z,
+                            const double* z, int max_iterations, int32_t* iterations, double* T, double* ldos, double* left, double* right,
+                            double* current_left, double* current_right, double* inter_left, double* inter_right, double* intra_left,
+                            double* intra_right);
 
 // roctx range around a stage (no-ops unless a roctx library can be loaded); tbk_api.hip
 void tbk_range_push(const char* name);

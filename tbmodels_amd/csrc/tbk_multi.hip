@@ -172,6 +172,35 @@ extern "C" int tbk_device_green_multi(tbk_model* const* handles, int n_handles, 
     });
 }
 
+// The bond currents on several devices (tbk_device_green.hip): the slabs of tbk_device_green_multi
+extern "C" int tbk_device_current_multi(tbk_model* const* handles, int n_handles, int axis, int layers, const double* k, int64_t nk, int M, const double* V,
+                                        int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T, double* ldos, double* left,
+                                        double* right, double* current_left, double* current_right, double* inter_left, double* inter_right,
+                                        double* intra_left, double* intra_right) {
+    TBK_CHECK(check_handles(handles, n_handles));
+    TBK_ARG(nk >= 0, "nk < 0");
+    if (n_handles == 1 || nk == 0)
+        return tbk_device_current(handles[0], axis, layers, k, nk, M, V, n_z, z, max_iterations, iterations, T, ldos, left, right, current_left,
+                                  current_right, inter_left, inter_right, intra_left, intra_right);
+    TBK_ARG(n_z >= 1 && n_z <= 4096 && layers >= 1 && layers <= 1024 && M >= 1 && M <= 4096, "n_z and M must be 1 to 4096, layers 1 ... 1024");
+    TBK_ARG(iterations != nullptr && T != nullptr && ldos != nullptr && left != nullptr && right != nullptr, "iterations / T / ldos / left / right is NULL");
+    TBK_ARG(current_left != nullptr && current_right != nullptr, "current_left / current_right is NULL");
+    const bool bonds = inter_left != nullptr;
+    TBK_ARG((inter_right != nullptr) == bonds && (intra_left != nullptr) == bonds && (intra_right != nullptr) == bonds,
+            "inter_left, inter_right, intra_left and intra_right must all be NULL or none of them");
+    const int dim = handles[0]->dim;
+    TBK_ARG(k != nullptr || dim == 1, "k is NULL");
+    const int64_t N = (int64_t)handles[0]->n_orb * layers;
+    const int64_t rows = n_z * M * N, krows = n_z * (M - 1) * N;  // doubles of one k-point in ldos ... and in current_left, current_right
+    return run_slabs(n_handles, nk, [&](int i, int64_t lo, int64_t count) {
+        return tbk_device_current_slab(handles[i], lo, axis, layers, k != nullptr ? k + lo * (dim - 1) : nullptr, count, M, V, n_z, z, max_iterations,
+                                       iterations + lo * n_z, T + lo * n_z, ldos + lo * rows, left + lo * rows, right + lo * rows,
+                                       current_left + lo * krows, current_right + lo * krows, bonds ? inter_left + lo * krows * N : nullptr,
+                                       bonds ? inter_right + lo * krows * N : nullptr, bonds ? intra_left + lo * rows * N : nullptr,
+                                       bonds ? intra_right + lo * rows * N : nullptr);
+    });
+}
+
 // The density of states of a mesh on several devices (tbk_dos.hip): handle i takes a contiguous slab of ceil(n_1 / n) cells along
 // axis 0 and evaluates the planes of that slab plus the one periodic neighbour plane its last cells need.  Every handle returns
 // its share of nos; the host adds the shares in handle order (slabs that hold no cells are skipped).

@@ -225,6 +225,40 @@ __device__ __forceinline__ void surf_product(const double* ar, const double* ai,
     }
 }
 
+// C = A B^H: surf_product with the B fragment taken from B's rows and conjugated.  Lane (q, c) feeds A[16 tr + c][k + q] and
+// conj(B[16 tc + c][k + q]); the tiles, their owners and the skipped blocks are surf_product's.
+template <int NP, int NT, int SA, int SB>
+__device__ __forceinline__ void surf_product_h(const double* ar, const double* ai, const double* br, const double* bi, int n, int wave, int lane,
+                                               surf_d4 (&cr)[NT], surf_d4 (&ci)[NT]) {
+    constexpr int TR = NP / 16;
+    lane = surf_fresh(lane);
+    const int q = lane >> 4, c16 = lane & 15;
+    const int tr = (wave * NT) / TR, tc0 = (wave * NT) % TR;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) cr[t] = ci[t] = surf_d4{0.0, 0.0, 0.0, 0.0};
+    if (tr * 16 >= n) return;
+#pragma unroll 1
+    for (int kb = 0; kb < TR; ++kb) {
+        if (kb * 16 < n) {
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                const int kk = kb * 16 + 4 * ks + q;
+                const double a_r = ar[(tr * 16 + c16) * SA + kk], a_i = ai[(tr * 16 + c16) * SA + kk];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    if ((tc0 + t) * 16 < n) {
+                        const double b_r = br[((tc0 + t) * 16 + c16) * SB + kk], b_i = -bi[((tc0 + t) * 16 + c16) * SB + kk];
+                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_r, b_r, cr[t], 0, 0, 0);
+                        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_r, b_i, ci[t], 0, 0, 0);
+                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_i, b_i, cr[t], 0, 0, 1);  // - a_i b_i
+                        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_i, b_r, ci[t], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+}
+
 // the wave's tiles of a product into a matrix (ADD: added to it); every element has one owner, whatever the matrix
 template <int NP, int NT, int SD, bool ADD>
 __device__ __forceinline__ void surf_tiles(double* dr, double* di, int n, int wave, int lane, const surf_d4 (&cr)[NT], const surf_d4 (&ci)[NT]) {
