@@ -552,6 +552,42 @@ int tbk_transmission_multi(tbk_model* const* handles, int n_handles, int axis, i
  * on; calls, reset as above. */
 int tbk_transmission_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
+/* ---- the transmission of an ensemble of devices: disorder samples after one decimation (not in the reference) ------------------------
+ * T[k][z][s], s = 0 ... n_s - 1, is tbk_transmission's T of the device V_s, unchanged down to the order of the operations: up to
+ * N = 64 every T[k][z][s] and iterations[k][z] have the bits of tbk_transmission called with V_s alone.  The decimation of a (kp, z)
+ * does not depend on V: it is computed once for a group of samples, and the sweep with its closing once per sample.  Exactly one of
+ *     V       double [n_s][M][N][N][2]   Hermitian matrices, as tbk_transmission's
+ *     onsite  double [n_s][M][N]         real on-site energies: they stay diagonal into the kernel, which adds the energy on the
+ *                                        diagonal and 0.0 elsewhere in the expressions of the matrix form -- the bits are those of
+ *                                        the matrix form on the expanded diagonal
+ * is not NULL.  Results: iterations int32 [nk][n_z], T double [nk][n_z][n_s]; n_s doubles per (kp, z) leave the device.  A work item
+ * of the own kernel (N <= 64) is (kp, z, a group of consecutive samples); the group that holds sample 0 writes iterations.  The bits
+ * of a T[k][z][s] depend on nothing else: not on the groups, the chunks, the grid, the other samples or their order.  Above N = 64,
+ * and for a handle with TBK_OPT_EIGENSOLVER = TBK_EIG_ROCSOLVER, the library route of tbk_transmission runs its decimation once per
+ * lockstep batch and its sweep once per sample; there are no groups there.
+ * Errors: tbk_transmission's, and TBK_ERR_ARGUMENT for both or none of V and onsite, n_s outside [1, 4096], sample_chunk < 0 and more
+ * than 256 MiB of staged devices.  The message of TBK_ERR_SINGULAR names the k index, the energy and the sample (the smallest such
+ * triple in that order; a singular decimation names sample 0), that of TBK_ERR_NO_CONVERGENCE the k index and the energy.  Error
+ * bound per sample: tbk_transmission's. */
+
+/* The kernel alone on principal layers the caller brings: H00, H01 double [n_k][N][N][2], n_k < 2^36.  k_chunk: points per launch
+ * (0: from the size of the results, n_z (8 n_s + 4) bytes per point).  sample_chunk: samples per workgroup visit (0: chosen so that
+ * the groups of a chunk fill the workgroups resident at once and no further: every extra group repeats the decimation). */
+int tbk_transmission_ensemble_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, int64_t n_s, const double* V,
+                                            const double* onsite, int64_t n_z, const double* z, int max_iterations, int64_t k_chunk,
+                                            int64_t sample_chunk, int32_t* iterations, double* T);
+/* The whole call: k, layers, the chunks and H_m as in tbk_surface_green; the groups are chosen as for sample_chunk = 0. */
+int tbk_transmission_ensemble(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int M, int64_t n_s, const double* V, const double* onsite,
+                              int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T);
+/* On several devices from one process: the slabs of tbk_hamilton_multi; every handle stages all the samples. */
+int tbk_transmission_ensemble_multi(tbk_model* const* handles, int n_handles, int axis, int layers, const double* k, int64_t nk, int M, int64_t n_s,
+                                    const double* V, const double* onsite, int64_t n_z, const double* z, int max_iterations, int32_t* iterations,
+                                    double* T);
+/* ms[3] = the summed HIP-event time of H(k) with the principal layers, the decimation with the sweeps of every sample, and the copies
+ * of the results to the host in this handle's calls made while TBK_OPT_TIMING was on; calls, reset as above.  A row of its own:
+ * tbk_transmission_timing does not count these calls. */
+int tbk_transmission_ensemble_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
 /* ---- the layer-resolved Green's functions of the device of tbk_transmission (not in the reference) -----------------------------------
  * H00, H01, N, L, V, M, the decimation and the forward sweep with g_p, D_p, T are those of tbk_transmission, unchanged down to the order
  * of the operations; Q_p below is its P_p.  Per (kp, z), after the forward sweep:

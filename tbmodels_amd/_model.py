@@ -48,6 +48,7 @@ GreenFunction = co.namedtuple("GreenFunction", ("z", "R", "G"))
 SurfaceGreenFunction = co.namedtuple("SurfaceGreenFunction", ("k", "z", "layers", "iterations", "bottom", "top", "bulk"))
 Transmission = co.namedtuple("Transmission", ("k", "z", "layers", "length", "iterations", "transmission"))
 TransmissionGreen = co.namedtuple("TransmissionGreen", Transmission._fields + ("green",))
+TransmissionEnsemble = co.namedtuple("TransmissionEnsemble", ("k", "z", "layers", "length", "samples", "iterations", "transmission"))
 DeviceGreen = co.namedtuple("DeviceGreen", Transmission._fields + ("ldos", "left", "right"))
 DeviceGreenBlocks = co.namedtuple("DeviceGreenBlocks", DeviceGreen._fields + ("diagonal", "first", "last"))
 DeviceCurrent = co.namedtuple("DeviceCurrent", DeviceGreen._fields + ("current_left", "current_right"))
@@ -1422,6 +1423,89 @@ class Model:
         if green:
             return TransmissionGreen(k_array, energies, layers, count, iterations, result, matrices)
         return Transmission(k_array, energies, layers, count, iterations, result)
+
+    def transmission_ensemble(self, k, z, devices, *, axis=-1, max_iterations=64):
+        """
+        The transmission :meth:`transmission` of an ensemble of ``S`` devices between the same two leads -- the disorder samples of
+        one ``(kp, z)`` after ONE decimation -- on the GPU.  Not in the reference.
+
+        ``k``, ``z``, ``axis``, ``max_iterations`` and their error messages are those of :meth:`transmission`.  ``devices`` is an
+        array ``(S, M, N)`` of real on-site energies (Anderson disorder; a complex array raises ``ValueError``) or an array ``(S,
+        M, N, N)`` of Hermitian matrices under :meth:`transmission`'s rule, ``max|V - V^H| <= 1e-12 max|V|`` over the whole
+        array; the number of dimensions decides the form, and any other shape raises ``ValueError``.  ``1 <= S <= 4096``, ``1 <=
+        M <= 4096``, the array finite and at most 256 MiB as staged: on-site energies stay diagonal all the way into the kernel,
+        so ``S M N`` doubles are staged and not ``S M N^2`` complex numbers.  ``N = size * L <= 1024``; a model without hopping
+        along ``axis`` raises ``ValueError``.  Returns the named tuple ``(k, z, layers, length, samples, iterations,
+        transmission)``: ``length`` is ``M``, ``samples`` is ``S``, ``iterations`` is ``int32 (NK, NZ)`` and ``transmission`` is
+        ``float64 (NK, NZ, S)``.  ``S`` doubles per ``(kp, z)`` leave the GPU; ``<ln T>``, the variance and the rest are one NumPy
+        line on them.
+
+        Definition.  ``transmission[k, z, s]`` is ``transmission(k, z, device=devices[s])``, unchanged down to the order of the
+        operations.  The decimation does not depend on the device, so it is computed once for a group of samples; the sweep and
+        the trace run once per sample on what it left.  The cap of the decimation and a singular ``z - D_p`` raise
+        ``numpy.linalg.LinAlgError``; the message names the k index, the energy and, for a singular sweep, the sample -- the
+        first offender in that order of precedence.
+
+        Properties.  (1) Up to ``N = 64`` every ``transmission[k, z, s]`` and ``iterations[k, z]`` have the bits of
+        :meth:`transmission` called with ``devices[s]`` alone.  (2) The on-site form has the bits of the matrix form on the
+        expanded diagonal: the kernel adds the energy on the diagonal and ``0.0`` elsewhere in the same expressions.  (3) The
+        bits of one ``(kp, z, s)`` depend on nothing else: not on the other samples or their order, the points, the energies,
+        the chunking or the grouping of the samples.
+
+        Error bound per sample: that of :meth:`transmission`.
+
+        Work: ``56 N^3`` flops per iteration of the decimation, once per group of samples, and ``40 N^3`` per layer and sample; a
+        loop over :meth:`transmission` pays ``(iterations 56 + M 40) / (M 40)`` times the flops for many samples, and ``H(k)``,
+        the layers and a dense copy of ``V`` per call on top.  Up to ``N = 64`` a work item is ``(kp, z, group of samples)``: the
+        samples are split into just enough groups to fill the device's resident workgroups, because every group repeats the
+        decimation -- one ``(kp, z)`` with many samples still fills the GPU.  Above, to 1024, and for a model with
+        ``TBK_OPT_EIGENSOLVER = TBK_EIG_ROCSOLVER``, the library route of :meth:`transmission` runs its decimation once per
+        lockstep batch and its sweep per sample.  With several ``devices`` of the model the k list is split as for ``hamilton``.
+        """
+        energies, axis_index, cap, k_array, layers = self._stacking_arguments(k, z, axis, max_iterations)
+        if layers == 0:
+            raise ValueError("the model has no hopping along axis {}: there is nothing to transmit".format(axis_index))
+        n_rows = self.size * layers
+        if n_rows > 1024:
+            raise ValueError("a principal layer of {} cells has {} rows: transmission_ensemble takes at most 1024".format(layers, n_rows))
+        given = np.asarray(devices)
+        shapes = "devices must have shape (S, M, {0}) or (S, M, {0}, {0}) with S, M >= 1, got {1}".format(n_rows, given.shape)
+        if given.ndim == 3:
+            if given.shape[2] != n_rows or given.shape[0] < 1 or given.shape[1] < 1:
+                raise ValueError(shapes)
+            if np.iscomplexobj(given):
+                raise ValueError("on-site energies of shape (S, M, {}) must be real".format(n_rows))
+            staged = np.ascontiguousarray(given, dtype=np.float64)
+        elif given.ndim == 4:
+            if given.shape[2:] != (n_rows, n_rows) or given.shape[0] < 1 or given.shape[1] < 1:
+                raise ValueError(shapes)
+            staged = np.ascontiguousarray(given, dtype=np.complex128)
+        else:
+            raise ValueError(shapes)
+        samples, count = staged.shape[:2]
+        if samples > 4096 or count > 4096 or staged.nbytes > 256 << 20:
+            raise ValueError("devices has {} samples of {} layers of {} rows: at most 4096 samples, 4096 layers and 256 MiB".format(
+                samples, count, n_rows))
+        if not np.all(np.isfinite(staged.view(np.float64))):
+            raise ValueError("devices must be finite")
+        if staged.ndim == 4:
+            size = float(np.abs(staged).max())
+            skew = max(float(np.abs(sample - np.conj(np.transpose(sample, (0, 2, 1)))).max()) for sample in staged)
+            if skew > 1e-12 * size:
+                raise ValueError("devices is not Hermitian: max|V - V^H| = {:.3e}".format(skew))
+        n_k, n_z = k_array.shape[0], energies.shape[0]
+        iterations = np.zeros((n_k, n_z), dtype=np.int32)
+        result = np.empty((n_k, n_z, samples), dtype=np.float64)
+        with self._call_lock:
+            # the cap reached: TBK_ERR_NO_CONVERGENCE, a singular z - D: TBK_ERR_SINGULAR -> numpy.linalg.LinAlgError
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_transmission_ensemble_multi(handles, n_handles, axis_index, layers, _lib.ptr(k_array) if k_array.size else None, n_k,
+                                                           count, samples, _lib.ptr(staged) if staged.ndim == 4 else None,
+                                                           _lib.ptr(staged) if staged.ndim == 3 else None, n_z, _lib.ptr(energies), cap,
+                                                           _lib.ptr(iterations), _lib.ptr(result))
+            )
+        return TransmissionEnsemble(k_array, energies, layers, count, samples, iterations, result)
 
     def _device_arguments(self, k, z, axis, max_iterations, device, length, name, max_rows):
         """(energies, axis index, cap, in-plane k array, L, V as complex128 (M, N, N)) of `transmission` and `device_green_function`:

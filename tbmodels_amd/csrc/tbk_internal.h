@@ -178,11 +178,11 @@ struct SpanRecorder {
 };
 
 // The sums the mesh calls book their kernel times on, one row per family (tbk_dos_timing, tbk_pdos_timing, tbk_fermi_timing,
-// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing, tbk_surface_timing, tbk_transmission_timing, tbk_device_green_timing, tbk_device_current_timing: what each counts differs and is
+// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing, tbk_surface_timing, tbk_transmission_timing, tbk_device_green_timing, tbk_device_current_timing, tbk_transmission_ensemble_timing: what each counts differs and is
 // listed in DESIGN.md section 10)
-enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_SURFACE, TIMED_TRANSMISSION, TIMED_DEVICE_GREEN, TIMED_DEVICE_CURRENT, TIMED_COUNT };
+enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_SURFACE, TIMED_TRANSMISSION, TIMED_DEVICE_GREEN, TIMED_DEVICE_CURRENT, TIMED_TRANSMISSION_ENSEMBLE, TIMED_COUNT };
 struct TimedSums {
-    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green, the dressed green, surface, transmission, the device green and the device current three)
+    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green, the dressed green, surface, transmission, the device green, the device current and the ensemble three)
     int64_t calls = 0;
     int64_t passes = 0;  // fermi: the passes of its searches
 };
@@ -351,7 +351,8 @@ struct tbk_model {
                          // ws_mesh_work the library route's batch, pivots and status.  tbk_surface_green (tbk_surface.hip): ws_mesh_k the
                          // k list with its samples along the stacking axis, ws_dm_r energies and twiddles, ws_pdos_u H(k) of one chunk,
                          // ws_dm_p its principal layers, ws_dm_rho its results and status word, ws_mesh_work the workgroups' slots;
-                         // tbk_transmission the same, and ws_mesh_io the device potential V; tbk_device_green (tbk_device_green.hip) as
+                         // tbk_transmission the same, and ws_mesh_io the device potential V (tbk_transmission_ensemble, tbk_ensemble.hip:
+                         // the devices of all samples, in either form); tbk_device_green (tbk_device_green.hip) as
                          // tbk_transmission, and ws_mesh_u the workgroups' stacks
     DevBuf ws_green_flag;  // tbk_green_dressed: one 64-bit status word, all ones or the smallest (mesh index * 4096 + energy index) that was singular
     // The calls on the resident eigensystem of a whole mesh (tbk_resident.h; the susceptibilities of tbk_chi.hip, tbk_berry_flux of
@@ -391,6 +392,18 @@ int tbk_surface_green_slab(tbk_model* m, int64_t k_base, int axis, int layers, c
 // ... and tbk_transmission in the same way (the slabs of tbk_transmission_multi)
 int tbk_transmission_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z,
                           const double* z, int max_iterations, int32_t* iterations, double* T, double* G);
+
+// tbk_ensemble.hip: tbk_transmission_ensemble in the same way (the slabs of tbk_transmission_ensemble_multi)
+int tbk_transmission_ensemble_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M, int64_t n_s, const double* V,
+                                   const double* onsite, int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T);
+
+// tbk_surface.hip: the library route of the ensemble for tbk_ensemble.hip -- the bytes of its workspace d_ws, and one chunk of nkc
+// points on it.  Exactly one of d_V ([n_s][m_layers][n][n] complex) and d_onsite ([n_s][m_layers][n]) is not NULL; d_T: [nkc][n_z][n_s];
+// d_flag: two words, the sweeps' (keys with the sample) and the decimation's (the keys of tbk_transmission)
+size_t tbk_trans_ens_lib_bytes(int n);
+int tbk_trans_ens_lib_chunk(hipStream_t s, rocblas_handle blas, char* d_ws, int n, int m_layers, int64_t n_s, const double2* d_H00, const double2* d_H01,
+                            const double2* d_V, const double* d_onsite, const double2* d_z, int64_t n_z, int64_t nkc, int max_it, int64_t k0, int32_t* d_it,
+                            double* d_T, unsigned long long* d_flag);
 
 // tbk_device_green.hip: tbk_device_green in the same way (the slabs of tbk_device_green_multi)
 int tbk_device_green_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z,

@@ -1,5 +1,5 @@
-// tbk_surface.h -- what the kernels and drivers of tbk_surface.hip (the decimation, the transmission) and tbk_device_green.hip (the
-// layer-resolved Green's functions of the device) share: the geometry of a workgroup's planes, the inversion, the products, the
+// tbk_surface.h -- what the kernels and drivers of tbk_surface.hip (the decimation, the transmission), tbk_ensemble.hip (the
+// transmission of an ensemble of devices) and tbk_device_green.hip (the layer-resolved Green's functions of the device) share: the geometry of a workgroup's planes, the inversion, the products, the
 // iteration of the decimation, the layer body and the closing trace of the sweep, and the host helpers of the whole calls.  Everything
 // sits in an unnamed namespace: each translation unit has its own copy.
 #pragma once
@@ -497,9 +497,17 @@ struct TransGeom {
     static constexpr size_t slot_doubles = Geo::GLOBAL ? (size_t)2 * MATS * NP * NP : 0;
 };
 
-// the wave's tiles of a product into D = (H00 + V) + product (zero beyond n); h0, v: [n][n] in global memory, read once
-template <int NP, int NT, int SD>
-__device__ __forceinline__ void trans_tiles_onsite(double* dr, double* di, const double2* __restrict__ h0, const double2* __restrict__ v, int n, int wave,
+// Element (i, c) of the potential of one layer in its two forms: a matrix [n][n] complex, or real on-site energies [n] (the ensemble,
+// tbk_ensemble.hip) -- the energy on the diagonal and 0.0 elsewhere, so that the callers perform the additions of the matrix form on
+// the expanded diagonal and give its bits.  trans_v_layer: the elements of one layer in the array.
+__device__ __forceinline__ double2 trans_v(const double2* __restrict__ v, int i, int c, int n) { return v[(size_t)i * n + c]; }
+__device__ __forceinline__ double2 trans_v(const double* __restrict__ v, int i, int c, int n) { return make_double2(i == c ? v[i] : 0.0, 0.0); }
+__host__ __device__ __forceinline__ size_t trans_v_layer(const double2*, int n) { return (size_t)n * n; }
+__host__ __device__ __forceinline__ size_t trans_v_layer(const double*, int n) { return (size_t)n; }
+
+// the wave's tiles of a product into D = (H00 + V) + product (zero beyond n); h0, v: [n][n] in global memory (v: or [n]), read once
+template <int NP, int NT, int SD, typename VT>
+__device__ __forceinline__ void trans_tiles_onsite(double* dr, double* di, const double2* __restrict__ h0, const VT* __restrict__ v, int n, int wave,
                                                    int lane, const surf_d4 (&cr)[NT], const surf_d4 (&ci)[NT]) {
     constexpr int TR = NP / 16;
     lane = surf_fresh(lane);
@@ -514,7 +522,7 @@ __device__ __forceinline__ void trans_tiles_onsite(double* dr, double* di, const
                 const int i = tr * 16 + q + 4 * r, c = (tc0 + t) * 16 + c16;
                 double vr = 0.0, vi = 0.0;
                 if (i < n && c < n) {
-                    const double2 a = h0[(size_t)i * n + c], b = v[(size_t)i * n + c];
+                    const double2 a = h0[(size_t)i * n + c], b = trans_v(v, i, c, n);
                     vr = (a.x + b.x) + cr[t][r];
                     vi = (a.y + b.y) + ci[t][r];
                 }
@@ -547,9 +555,9 @@ __device__ __forceinline__ void trans_tiles_stack(double2* g, int n, int wave, i
 
 // The sweep on the planes surf_iterate leaves (es and et final), shared by transmission_kernel and device_green_kernel
 // (tbk_device_green.hip).  H01, H01^H and D live in the planes of alpha, beta and e, P in the sixth matrix.
-// trans_start: H01 and H01^H again; D_1 = et + V_1 (one barrier at the end)
-template <int NP>
-__device__ __forceinline__ void trans_start(const SurfPlanes& P, const double2* __restrict__ h1, const double2* __restrict__ V, int n, int tid) {
+// V: the potential in either form of trans_v.  trans_start: H01 and H01^H again; D_1 = et + V_1 (one barrier at the end)
+template <int NP, typename VT>
+__device__ __forceinline__ void trans_start(const SurfPlanes& P, const double2* __restrict__ h1, const VT* __restrict__ V, int n, int tid) {
     using Geo = SurfGeom<NP>;
     constexpr int THREADS = Geo::THREADS, SM = Geo::SM;
     double *h01r = P.alr, *h01i = P.ali, *h10r = P.ber, *h10i = P.bei, *dr = P.er, *di = P.ei, *etr = P.etr, *eti = P.eti;
@@ -559,7 +567,7 @@ __device__ __forceinline__ void trans_start(const SurfPlanes& P, const double2* 
         double2 b = make_double2(0.0, 0.0), d = make_double2(0.0, 0.0);
         if (i < n && c < n) {
             b = h1[(size_t)i * n + c];
-            const double2 v = V[(size_t)i * n + c];
+            const double2 v = trans_v(V, i, c, n);
             d = make_double2(etr[i * SM + c] + v.x, eti[i * SM + c] + v.y);
         }
         h01r[i * SM + c] = b.x;
@@ -575,8 +583,8 @@ __device__ __forceinline__ void trans_start(const SurfPlanes& P, const double2* 
 // Layer p (from 0) of the sweep: g_p into Y, P_p into P's planes, D_{p+1} into D's.  Returns whether a pivot was zero or an element
 // of g_p not finite (this thread's share).  STACK: g_p goes to stack[2 p] and H01^H P_{p-1} (p > 0) to stack[2 p + 1], [n][n] complex
 // each, by the threads that own the elements; a barrier stands between these stores and whatever the workgroup reads of them later.
-template <int NP, bool STACK>
-__device__ __forceinline__ bool trans_layer(const SurfPlanes& P, const double2* __restrict__ h0, const double2* __restrict__ V, double2 zz, int p,
+template <int NP, bool STACK, typename VT>
+__device__ __forceinline__ bool trans_layer(const SurfPlanes& P, const double2* __restrict__ h0, const VT* __restrict__ V, double2 zz, int p,
                                             int m_layers, int n, int tid, double2* stack) {
     using Geo = SurfGeom<NP>;
     constexpr int THREADS = Geo::THREADS, S = Geo::S, SM = Geo::SM, NT = Geo::NT;
@@ -635,15 +643,15 @@ __device__ __forceinline__ bool trans_layer(const SurfPlanes& P, const double2* 
         surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
         __syncthreads();
         surf_product<NP, NT, SM, S>(h10r, h10i, xr, xi, n, wave, lane, cr, ci);  // H01^H g_p H01
-        trans_tiles_onsite<NP, NT, SM>(dr, di, h0, V + (size_t)(p + 1) * n * n, n, wave, lane, cr, ci);
+        trans_tiles_onsite<NP, NT, SM>(dr, di, h0, V + (size_t)(p + 1) * trans_v_layer(V, n), n, wave, lane, cr, ci);
         __syncthreads();
     }
     return bad;
 }
 
 // The closing of the sweep: P_M is looked at (returns whether an element of this thread's share is not finite) and leaves to g_out
-// unless that is NULL; T = Re tr[(Gamma_R P_M) (Gamma_L P_M^H)] and the count of the decimation go to *T_at and *it_at.  X, Y and D's
-// planes are overwritten; P, es, et, H01 and H01^H stay.
+// unless that is NULL; T = Re tr[(Gamma_R P_M) (Gamma_L P_M^H)] and the count of the decimation go to *T_at and *it_at (it_at NULL:
+// the count has another owner).  X, Y and D's planes are overwritten; P, es, et, H01 and H01^H stay.
 template <int NP>
 __device__ __forceinline__ bool trans_closing(const SurfPlanes& P, int n, int tid, double2* g_out, double* T_at, int32_t* it_at, int it) {
     using Geo = SurfGeom<NP>;
@@ -721,7 +729,7 @@ __device__ __forceinline__ bool trans_closing(const SurfPlanes& P, int n, int ti
 #pragma unroll 4
             for (int r = 0; r < NP; ++r) total += rown[r];
             *T_at = total;
-            *it_at = it;
+            if (it_at != nullptr) *it_at = it;
         }
         __syncthreads();  // the tables are free again
     }

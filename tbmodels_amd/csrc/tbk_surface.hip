@@ -29,6 +29,8 @@
 //   transmission_kernel      one workgroup owns one (kp, z) from the first decimation step (surf_load, surf_iterate: the loop of
 //                            surface_decimate_kernel) through one inversion and four products per layer to the trace.  N <= 64.
 //   trans_lib_chunk          65 <= N <= 1024, and on request: the lead part is surf_lib_iterate, the sweep M lockstep rounds.
+//   trans_ens_lib_chunk      the same route for the ensemble of tbk_ensemble.hip: surf_lib_iterate once per
+//                            batch, the sweep (trans_lib_sweep, shared with trans_lib_chunk) once per sample.
 
 #include "tbk_surface.h"
 
@@ -512,8 +514,9 @@ int trans_launch(hipStream_t s, int n_cu, const TransShape& sh, const double2* d
 }
 
 // ---- the library route of the transmission: the lead part is surf_lib_iterate, the sweep M lockstep rounds without convergence logic --
-// member b of the batch: H01 and H01^H again, D_1 = et + V_1 (a dummy member: zeros, so that z 1 - D is z 1)
-__global__ void __launch_bounds__(256) trans_lib_start_kernel(const double2* __restrict__ H01, const double2* __restrict__ V, const double2* __restrict__ et,
+// member b of the batch: H01 and H01^H again, D_1 = et + V_1 (a dummy member: zeros, so that z 1 - D is z 1).  V: either form of trans_v
+template <typename VT>
+__global__ void __launch_bounds__(256) trans_lib_start_kernel(const double2* __restrict__ H01, const VT* __restrict__ V, const double2* __restrict__ et,
                                                              int n_z, int n, int64_t w0, int64_t items, double2* __restrict__ h01,
                                                              double2* __restrict__ h10, double2* __restrict__ D) {
     const int b = (int)blockIdx.x;
@@ -525,7 +528,7 @@ __global__ void __launch_bounds__(256) trans_lib_start_kernel(const double2* __r
         double2 h = make_double2(0.0, 0.0), d = make_double2(0.0, 0.0);
         if (valid) {
             h = H01[k * nn + x];
-            const double2 e = et[b * nn + x], v = V[x];
+            const double2 e = et[b * nn + x], v = trans_v(V, (int)i, (int)c, n);
             d = make_double2(e.x + v.x, e.y + v.y);
         }
         h01[b * nn + x] = h;
@@ -535,7 +538,8 @@ __global__ void __launch_bounds__(256) trans_lib_start_kernel(const double2* __r
 }
 
 // V NULL: D += es - H00 (the right lead, `other` is es); else D = (H00 + V) + other (`other` is H01^H g H01)
-__global__ void __launch_bounds__(256) trans_lib_onsite_kernel(const double2* __restrict__ H00, const double2* __restrict__ V, const double2* __restrict__ other,
+template <typename VT>
+__global__ void __launch_bounds__(256) trans_lib_onsite_kernel(const double2* __restrict__ H00, const VT* __restrict__ V, const double2* __restrict__ other,
                                                               int n_z, int n, int64_t w0, int64_t items, double2* __restrict__ D) {
     const int b = (int)blockIdx.x;
     const int64_t w = w0 + b;
@@ -549,16 +553,20 @@ __global__ void __launch_bounds__(256) trans_lib_onsite_kernel(const double2* __
             d.x += o.x - a.x;
             d.y += o.y - a.y;
         } else {
-            const double2 v = V[x];
+            const size_t i = x / n, c = x - i * n;
+            const double2 v = trans_v(V, (int)i, (int)c, n);
             d = make_double2((a.x + v.x) + o.x, (a.y + v.y) + o.y);
         }
         D[b * nn + x] = d;
     }
 }
 
-// a failed library call (info not NULL) or a non-finite element of the member's matrix raises the word (singular)
+// a failed library call (info not NULL) or a non-finite element of the member's matrix raises the word (singular).  The key of the
+// member is (key0 + point * SURF_MAX_Z + energy) * sub_n + sub: sub_n = 1, sub = 0 for the one device of the transmission, the
+// ensemble's SURF_MAX_Z and its sample
 __global__ void __launch_bounds__(256) trans_lib_check_kernel(const double2* __restrict__ A, const int* __restrict__ info, int n, int batch, int64_t w0,
-                                                             int64_t items, int n_z, unsigned long long key0, unsigned long long* __restrict__ flag) {
+                                                             int64_t items, int n_z, unsigned long long key0, unsigned long long sub_n,
+                                                             unsigned long long sub, unsigned long long* __restrict__ flag) {
     const int b = (int)blockIdx.x;
     const int64_t w = w0 + b;
     if (w >= items) return;
@@ -568,7 +576,8 @@ __global__ void __launch_bounds__(256) trans_lib_check_kernel(const double2* __r
         const double2 v = A[b * nn + x];
         bad |= !(fabs(v.x) <= SURF_DBL_MAX && fabs(v.y) <= SURF_DBL_MAX);
     }
-    if (bad) atomicMin(flag, (key0 + (unsigned long long)(w / n_z) * (unsigned long long)SURF_MAX_Z + (unsigned long long)(w % n_z)) * 2ull);
+    if (bad)
+        atomicMin(flag, ((key0 + (unsigned long long)(w / n_z) * (unsigned long long)SURF_MAX_Z + (unsigned long long)(w % n_z)) * sub_n + sub) * 2ull);
 }
 
 // gamma = i (e - e^H) and, P not NULL, adj = P^H, for every member
@@ -588,9 +597,10 @@ __global__ void __launch_bounds__(256) trans_lib_gamma_kernel(const double2* __r
 }
 
 // One workgroup per member: T = Re sum_ij A[i][j] B[j][i] in a fixed order (a thread per row, columns ascending; thread 0 adds the
-// rows in order), and P_M into G_out unless it is NULL.
+// rows in order) into T_out[item * t_stride + t_at], and P_M into G_out unless it is NULL.
 __global__ void __launch_bounds__(256) trans_lib_trace_kernel(const double2* __restrict__ A, const double2* __restrict__ B, const double2* __restrict__ P, int n,
-                                                             int64_t w0, int64_t items, double* __restrict__ T_out, double2* __restrict__ G_out) {
+                                                             int64_t w0, int64_t items, int64_t t_stride, int64_t t_at, double* __restrict__ T_out,
+                                                             double2* __restrict__ G_out) {
     __shared__ double rows[SURF_LIB_MAX];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
     const int64_t w = w0 + b;
@@ -608,64 +618,107 @@ __global__ void __launch_bounds__(256) trans_lib_trace_kernel(const double2* __r
     if (tid == 0) {
         double total = 0.0;
         for (int r = 0; r < n; ++r) total += rows[r];
-        T_out[w] = total;
+        T_out[w * t_stride + t_at] = total;
     }
     if (G_out != nullptr)
         for (size_t x = tid; x < nn; x += 256) G_out[(size_t)w * nn + x] = P[b * nn + x];
 }
 
+// The sweep and the closing of the batch that starts at item w0, on what surf_lib_iterate left: es and et (W.mat[5], W.mat[6]) are read
+// and stay, every other matrix of W is overwritten.  d_V: the device in either form of trans_v; the keys are trans_lib_check_kernel's;
+// T goes to d_T[item * t_stride + t_at].
+template <typename VT>
+int trans_lib_sweep(hipStream_t s, const SurfLib& W, int m_layers, const double2* d_H00, const double2* d_H01, const VT* d_V, const double2* d_z, int n_z,
+                    int64_t items, int64_t w0, unsigned long long key0, unsigned long long sub_n, unsigned long long sub, int64_t t_stride, int64_t t_at,
+                    double* d_T, double2* d_G, unsigned long long* d_flag) {
+    const int n = W.n;
+    const size_t nn = (size_t)n * n, count = (size_t)W.batch * nn;
+    const dim3 grid((unsigned)W.batch, (unsigned)std::min<size_t>(64, (nn + 255) / 256));
+    double2 *h01 = W.mat[0], *h10 = W.mat[1], *P = W.mat[2], *Q = W.mat[3], *D = W.mat[4], *es = W.mat[5], *et = W.mat[6], *A = W.mat[7], *T = W.mat[8],
+            *R = W.mat[9];
+    hipLaunchKernelGGL(trans_lib_start_kernel<VT>, grid, dim3(256), 0, s, d_H01, d_V, et, n_z, n, w0, items, h01, h10, D);
+    TBK_HIP(hipGetLastError());
+    for (int p = 0; p < m_layers; ++p) {
+        if (p == m_layers - 1)
+            hipLaunchKernelGGL(trans_lib_onsite_kernel<VT>, grid, dim3(256), 0, s, d_H00, static_cast<const VT*>(nullptr), es, n_z, n, w0, items, D);
+        TBK_CHECK(surf_lib_invert(s, W, D, d_z, n_z, w0, A));  // g_p
+        hipLaunchKernelGGL(trans_lib_check_kernel, grid, dim3(256), 0, s, A, W.info, n, W.batch, w0, items, n_z, key0, sub_n, sub, d_flag);
+        TBK_HIP(hipGetLastError());
+        if (p == 0) {
+            TBK_HIP(hipMemcpyAsync(P, A, count * sizeof(double2), hipMemcpyDeviceToDevice, s));  // P_1 = g_1
+        } else {
+            TBK_CHECK(surf_lib_gemm(W, h10, P, T));  // T = H01^H P_{p-1}
+            TBK_CHECK(surf_lib_gemm(W, A, T, Q));    // P_p = g_p T
+            std::swap(P, Q);
+        }
+        if (p + 1 < m_layers) {
+            TBK_CHECK(surf_lib_gemm(W, A, h01, T));  // T = g_p H01
+            TBK_CHECK(surf_lib_gemm(W, h10, T, R));  // H01^H g_p H01
+            hipLaunchKernelGGL(trans_lib_onsite_kernel<VT>, grid, dim3(256), 0, s, d_H00, d_V + (size_t)(p + 1) * trans_v_layer(d_V, n), R, n_z, n, w0, items,
+                               D);
+            TBK_HIP(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(trans_lib_check_kernel, grid, dim3(256), 0, s, P, nullptr, n, W.batch, w0, items, n_z, key0, sub_n, sub, d_flag);
+    hipLaunchKernelGGL(trans_lib_gamma_kernel, grid, dim3(256), 0, s, es, n, T, P, Q);  // Gamma_R, P_M^H
+    TBK_HIP(hipGetLastError());
+    TBK_CHECK(surf_lib_gemm(W, T, P, R));  // Gamma_R P_M
+    hipLaunchKernelGGL(trans_lib_gamma_kernel, grid, dim3(256), 0, s, et, n, T, nullptr, nullptr);  // Gamma_L
+    TBK_HIP(hipGetLastError());
+    TBK_CHECK(surf_lib_gemm(W, T, Q, D));  // Gamma_L P_M^H
+    hipLaunchKernelGGL(trans_lib_trace_kernel, dim3((unsigned)W.batch), dim3(256), 0, s, R, D, P, n, w0, items, t_stride, t_at, d_T, d_G);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
 // The chunk's nkc points at every energy on the library route (the arguments of trans_launch)
 int trans_lib_chunk(hipStream_t s, const SurfLib& W, const TransShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_V,
                     const double2* d_z, int64_t nkc, int max_it, int64_t k0, char* d_res) {
-    const int n = sh.n, n_z = (int)sh.n_z;
+    const int n_z = (int)sh.n_z;
     const int64_t items = nkc * sh.n_z;
     const unsigned long long key0 = (unsigned long long)k0 * (unsigned long long)SURF_MAX_Z;
     double* d_T = reinterpret_cast<double*>(d_res);
     int32_t* d_it = reinterpret_cast<int32_t*>(d_res + sh.t_bytes(nkc));
     double2* d_G = sh.green ? reinterpret_cast<double2*>(d_res + sh.t_bytes(nkc) + sh.it_bytes(nkc)) : nullptr;
     unsigned long long* d_flag = reinterpret_cast<unsigned long long*>(d_res + sh.result_bytes(nkc));
-    const size_t nn = (size_t)n * n, count = (size_t)W.batch * nn;
-    const dim3 grid((unsigned)W.batch, (unsigned)std::min<size_t>(64, (nn + 255) / 256));
     for (int64_t w0 = 0; w0 < items; w0 += W.batch) {
         TBK_CHECK(surf_lib_iterate(s, W, d_H00, d_H01, d_z, n_z, items, w0, max_it, key0, d_it, d_flag));
-        double2 *h01 = W.mat[0], *h10 = W.mat[1], *P = W.mat[2], *Q = W.mat[3], *D = W.mat[4], *es = W.mat[5], *et = W.mat[6], *A = W.mat[7], *T = W.mat[8],
-                *R = W.mat[9];
-        hipLaunchKernelGGL(trans_lib_start_kernel, grid, dim3(256), 0, s, d_H01, d_V, et, n_z, n, w0, items, h01, h10, D);
-        TBK_HIP(hipGetLastError());
-        for (int p = 0; p < sh.m_layers; ++p) {
-            if (p == sh.m_layers - 1) hipLaunchKernelGGL(trans_lib_onsite_kernel, grid, dim3(256), 0, s, d_H00, nullptr, es, n_z, n, w0, items, D);
-            TBK_CHECK(surf_lib_invert(s, W, D, d_z, n_z, w0, A));  // g_p
-            hipLaunchKernelGGL(trans_lib_check_kernel, grid, dim3(256), 0, s, A, W.info, n, W.batch, w0, items, n_z, key0, d_flag);
-            TBK_HIP(hipGetLastError());
-            if (p == 0) {
-                TBK_HIP(hipMemcpyAsync(P, A, count * sizeof(double2), hipMemcpyDeviceToDevice, s));  // P_1 = g_1
-            } else {
-                TBK_CHECK(surf_lib_gemm(W, h10, P, T));  // T = H01^H P_{p-1}
-                TBK_CHECK(surf_lib_gemm(W, A, T, Q));    // P_p = g_p T
-                std::swap(P, Q);
-            }
-            if (p + 1 < sh.m_layers) {
-                TBK_CHECK(surf_lib_gemm(W, A, h01, T));  // T = g_p H01
-                TBK_CHECK(surf_lib_gemm(W, h10, T, R));  // H01^H g_p H01
-                hipLaunchKernelGGL(trans_lib_onsite_kernel, grid, dim3(256), 0, s, d_H00, d_V + (size_t)(p + 1) * nn, R, n_z, n, w0, items, D);
-                TBK_HIP(hipGetLastError());
-            }
-        }
-        hipLaunchKernelGGL(trans_lib_check_kernel, grid, dim3(256), 0, s, P, nullptr, n, W.batch, w0, items, n_z, key0, d_flag);
-        hipLaunchKernelGGL(trans_lib_gamma_kernel, grid, dim3(256), 0, s, es, n, T, P, Q);  // Gamma_R, P_M^H
-        TBK_HIP(hipGetLastError());
-        TBK_CHECK(surf_lib_gemm(W, T, P, R));  // Gamma_R P_M
-        hipLaunchKernelGGL(trans_lib_gamma_kernel, grid, dim3(256), 0, s, et, n, T, nullptr, nullptr);  // Gamma_L
-        TBK_HIP(hipGetLastError());
-        TBK_CHECK(surf_lib_gemm(W, T, Q, D));  // Gamma_L P_M^H
-        hipLaunchKernelGGL(trans_lib_trace_kernel, dim3((unsigned)W.batch), dim3(256), 0, s, R, D, P, n, w0, items, d_T, d_G);
-        TBK_HIP(hipGetLastError());
+        TBK_CHECK(trans_lib_sweep(s, W, sh.m_layers, d_H00, d_H01, d_V, d_z, n_z, items, w0, key0, 1ull, 0ull, 1, 0, d_T, d_G, d_flag));
     }
     return TBK_OK;
 }
 
+// The ensemble's chunk on the library route (tbk_ensemble.hip has the call): per lockstep batch surf_lib_iterate once, then the sweep
+// and the closing per sample -- es and et survive them.  d_V: n_s devices [m_layers][n][n] complex or [m_layers][n] doubles; d_T:
+// [nkc][n_z][n_s]; d_flag: the sweeps' word (keys with the sample) and, behind it, the decimation's in surf_lib_norms_kernel's keys.
+template <typename VT>
+int trans_ens_lib_chunk(hipStream_t s, const SurfLib& W, int m_layers, int64_t n_s, const double2* d_H00, const double2* d_H01, const VT* d_V,
+                        const double2* d_z, int64_t n_z, int64_t nkc, int max_it, int64_t k0, int32_t* d_it, double* d_T, unsigned long long* d_flag) {
+    const int64_t items = nkc * n_z;
+    const unsigned long long key0 = (unsigned long long)k0 * (unsigned long long)SURF_MAX_Z;
+    const size_t per_sample = (size_t)m_layers * trans_v_layer(d_V, W.n);
+    for (int64_t w0 = 0; w0 < items; w0 += W.batch) {
+        TBK_CHECK(surf_lib_iterate(s, W, d_H00, d_H01, d_z, (int)n_z, items, w0, max_it, key0, d_it, d_flag + 1));
+        for (int64_t sample = 0; sample < n_s; ++sample)
+            TBK_CHECK(trans_lib_sweep(s, W, m_layers, d_H00, d_H01, d_V + (size_t)sample * per_sample, d_z, (int)n_z, items, w0, key0,
+                                      (unsigned long long)SURF_MAX_Z, (unsigned long long)sample, n_s, sample, d_T, nullptr, d_flag));
+    }
+    return TBK_OK;
+}
 
 }  // namespace
+
+// tbk_ensemble.hip's doors to the library route: the bytes of its workspace, and a chunk on a workspace of that size
+size_t tbk_trans_ens_lib_bytes(int n) { return SurfLib::bytes(n, surf_lib_batch(n)); }
+
+int tbk_trans_ens_lib_chunk(hipStream_t s, rocblas_handle blas, char* d_ws, int n, int m_layers, int64_t n_s, const double2* d_H00, const double2* d_H01,
+                            const double2* d_V, const double* d_onsite, const double2* d_z, int64_t n_z, int64_t nkc, int max_it, int64_t k0, int32_t* d_it,
+                            double* d_T, unsigned long long* d_flag) {
+    SurfLib W;
+    W.place(d_ws, n, surf_lib_batch(n), blas);
+    if (d_onsite != nullptr) return trans_ens_lib_chunk(s, W, m_layers, n_s, d_H00, d_H01, d_onsite, d_z, n_z, nkc, max_it, k0, d_it, d_T, d_flag);
+    return trans_ens_lib_chunk(s, W, m_layers, n_s, d_H00, d_H01, d_V, d_z, n_z, nkc, max_it, k0, d_it, d_T, d_flag);
+}
 
 extern "C" int tbk_transmission_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, const double* V, int64_t n_z,
                                               const double* z, int max_iterations, int64_t k_chunk, int32_t* iterations, double* T, double* G) {
