@@ -588,6 +588,50 @@ int tbk_transmission_ensemble_multi(tbk_model* const* handles, int n_handles, in
  * tbk_transmission_timing does not count these calls. */
 int tbk_transmission_ensemble_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
+/* ---- the transmission eigenvalues of an ensemble of devices: channels and shot noise (not in the reference) ---------------------------
+ * channels[k][z][s][0 ... N) are the transmission eigenvalues T_n of the device V_s in descending order: the eigenvalues of t^H t,
+ * t = L_R^H (P_M L_L), whose trace is tbk_transmission's T.  Per (kp, z, sample), behind the decimation and the sweep of
+ * tbk_transmission_ensemble, unchanged and in their order, with s = sign(Im z):
+ *
+ *     B_R = s i (es - es^H),  B_L = s i (et - et^H)     Hermitian, positive semidefinite up to rounding for either sign of Im z
+ *     B = L L^H        Cholesky with diagonal pivoting: the largest remaining diagonal first (ties: the lowest index, a NaN counts as
+ *                      +inf); it stops at rank r when that diagonal is <= N u d0, d0 the largest diagonal of B and u = 2^-53, and
+ *                      the other N - r columns of L are exactly zero -- a lead with fewer open directions than rows is no error
+ *     t = L_R^H (P_M L_L)                               two products on the FP64 matrix pipe, bracketed as written
+ *     one-sided (Hestenes) Jacobi on the columns of t (of t^H when r_R < r_L: the zero columns stay columns): sweeps of N' - 1 rounds
+ *     of N' / 2 disjoint pairs in the round-robin order, N' = 16, 32 or 64; a pair with a = |t_p|^2, b = |t_q|^2, c = t_p^H t_q is
+ *     skipped when a == 0, b == 0 or |c| <= N u sqrt(a) sqrt(b), else rotated to orthogonality; the first sweep without a rotation
+ *     is the last
+ *     T_n = the squared column norms, descending; the entries beyond min(r_R, r_L) are exactly 0.0
+ *
+ * One-sided Jacobi keeps small T_n relatively accurate where an eigensolve of t^H t would bury them under u T_max.  The arguments, the
+ * limits (n_s <= 4096, 256 MiB of staged devices), the groups and the errors are those of tbk_transmission_ensemble, with N <= 64
+ * only: more rows are TBK_ERR_ARGUMENT, there is no library route.  Results: iterations int32 [nk][n_z] and T double
+ * [nk][n_z][n_s], both with the bits of tbk_transmission_ensemble on the same input, and channels double [nk][n_z][n_s][N]; (N + 1)
+ * doubles per (kp, z, sample) leave the device.  The bits of a channels[k][z][s] depend on nothing else: not on the groups, the
+ * chunks, the grid, the other samples or their order.  A Jacobi that still rotates in its 48th sweep (the inputs of the tests need
+ * 20 at most) is TBK_ERR_NO_CONVERGENCE; the message says that it was the channel iteration and names the k index, the energy and
+ * the sample; a T_n that is not finite is TBK_ERR_SINGULAR with its sample, as a non-finite P_M is.  Error per T_n: (4 eps +
+ * (2 (N + 1)^2 + 8 N (sweeps + 2) + N^2) u) scale / N with tbk_transmission's eps and scale. */
+
+/* The kernel alone on principal layers the caller brings: tbk_transmission_ensemble_from_matrices' arguments.  k_chunk = 0: from the
+ * size of the results, n_z n_s (8 N + 8) + 4 n_z bytes per point. */
+int tbk_transmission_channels_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, int64_t n_s, const double* V,
+                                            const double* onsite, int64_t n_z, const double* z, int max_iterations, int64_t k_chunk,
+                                            int64_t sample_chunk, int32_t* iterations, double* T, double* channels);
+/* The whole call: k, layers, the chunks and H_m as in tbk_surface_green; the groups are chosen as for sample_chunk = 0.  Always the own
+ * kernel, whatever TBK_OPT_EIGENSOLVER. */
+int tbk_transmission_channels(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int M, int64_t n_s, const double* V, const double* onsite,
+                              int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T, double* channels);
+/* On several devices from one process: the slabs of tbk_hamilton_multi; every handle stages all the samples. */
+int tbk_transmission_channels_multi(tbk_model* const* handles, int n_handles, int axis, int layers, const double* k, int64_t nk, int M, int64_t n_s,
+                                    const double* V, const double* onsite, int64_t n_z, const double* z, int max_iterations, int32_t* iterations,
+                                    double* T, double* channels);
+/* ms[3] = the summed HIP-event time of H(k) with the principal layers, the decimation with the sweeps and the channels of every sample,
+ * and the copies of the results to the host in this handle's calls made while TBK_OPT_TIMING was on; calls, reset as above.  A row of
+ * its own: tbk_transmission_timing and tbk_transmission_ensemble_timing do not count these calls. */
+int tbk_transmission_channels_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
 /* ---- the layer-resolved Green's functions of the device of tbk_transmission (not in the reference) -----------------------------------
  * H00, H01, N, L, V, M, the decimation and the forward sweep with g_p, D_p, T are those of tbk_transmission, unchanged down to the order
  * of the operations; Q_p below is its P_p.  Per (kp, z), after the forward sweep:

@@ -121,6 +121,11 @@ SIGNATURES = {
     "tbk_transmission_ensemble": (_c_int, [_vp, _c_int, _c_int, _vp, _c_i64, _c_int, _c_i64, _vp, _vp, _c_i64, _vp, _c_int, _vp, _vp]),
     "tbk_transmission_ensemble_multi": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_i64, _c_int, _c_i64, _vp, _vp, _c_i64, _vp, _c_int, _vp, _vp]),
     "tbk_transmission_ensemble_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
+    "tbk_transmission_channels_from_matrices": (_c_int, [_c_int, _c_int, _c_i64, _vp, _vp, _c_int, _c_i64, _vp, _vp, _c_i64, _vp, _c_int, _c_i64, _c_i64,
+                                                         _vp, _vp, _vp]),
+    "tbk_transmission_channels": (_c_int, [_vp, _c_int, _c_int, _vp, _c_i64, _c_int, _c_i64, _vp, _vp, _c_i64, _vp, _c_int, _vp, _vp, _vp]),
+    "tbk_transmission_channels_multi": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_i64, _c_int, _c_i64, _vp, _vp, _c_i64, _vp, _c_int, _vp, _vp, _vp]),
+    "tbk_transmission_channels_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
     "tbk_device_green_from_matrices": (_c_int, [_c_int, _c_int, _c_i64, _vp, _vp, _c_int, _vp, _c_i64, _vp, _c_int, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _vp,
                                                 _vp, _vp, _vp]),
     "tbk_device_green": (_c_int, [_vp, _c_int, _c_int, _vp, _c_i64, _c_int, _vp, _c_i64, _vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

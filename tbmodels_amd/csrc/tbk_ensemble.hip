@@ -11,18 +11,14 @@
 //   tbk_trans_ens_lib_chunk  65 <= N <= 1024, and on request: tbk_surface.hip's library route, surf_lib_iterate once per lockstep
 //                            batch and the sweep per sample.
 //
-// The groups: with sample_chunk = 0 the host takes G = min(n_s, ceil(R / (nkc n_z))) groups per (kp, z), R the workgroups resident at
-// once (the CUs times the kernel's occupancy with its dynamic LDS; one per CU at NP = 64, as surf_grid assumes for the workspace
-// slots), and ceil(n_s / G) samples per group: enough groups to fill the device and no more, because every group repeats the
-// decimation.  The rule comes from the flop counts (25.3), not from a measurement.
+// The rule that splits the samples into groups, and the drivers tbk_channels.hip shares: tbk_ensemble.h.
 
 #include <type_traits>
 
-#include "tbk_surface.h"
+#include "tbk_ensemble.h"
 
 namespace {
 
-constexpr int64_t ENS_MAX_SAMPLES = 4096;  // samples per call (include/tbk.h); the status word gives the sample 12 bits
 constexpr const char* ENS_FAMILY = "the transmission of an ensemble";
 constexpr const char* ENS_SINGULAR = "z - D of a device layer, or z - e of the decimation,";
 
@@ -75,61 +71,18 @@ __global__ void __launch_bounds__(SurfGeom<NP>::THREADS)
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 tbk_flag_row ens_lds_done[2][2];  // [NP = 32, 64][DIAG]: more than 64 KiB of dynamic LDS
 
-// The call's sizes, and the results of a chunk: T, iterations, and behind them two status words -- the kernel's and the sweeps' of
-// the library route in the first, the decimation of the library route (tbk_transmission's keys) in the second.
-struct EnsShape {
-    int n = 0, m_layers = 0;
-    int64_t n_z = 0, n_s = 0;
-    bool diag = false;
-    size_t device_bytes() const { return (size_t)n_s * m_layers * n * (diag ? sizeof(double) : (size_t)n * sizeof(double2)); }
-    size_t t_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * n_s * sizeof(double)); }
-    size_t it_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * sizeof(int32_t)); }
-    size_t result_bytes(int64_t nk) const { return t_bytes(nk) + it_bytes(nk); }
-    static constexpr size_t flag_bytes = 2 * sizeof(unsigned long long);
-    int64_t auto_chunk(int64_t nk) const {  // the chunk's results and its two layers inside the budget
-        const size_t per_k = (size_t)n_z * ((size_t)n_s * sizeof(double) + sizeof(int32_t)) + (size_t)2 * n * n * sizeof(double2);
-        return std::max<int64_t>(1, std::min<int64_t>(nk, (int64_t)(SURF_CHUNK_BUDGET / per_k)));
-    }
-};
-
 // the slots of the workgroups' matrices at NP = 64 for any chunk of at most `chunk` points
 size_t ens_workspace_bytes(const EnsShape& sh, int64_t chunk, int n_cu) {
     return sh.n > 32 ? (size_t)surf_grid(sh.n, chunk * sh.n_z * sh.n_s, n_cu) * TransGeom<64>::slot_doubles * sizeof(double) : 0;
 }
-
-struct EnsLaunch {
-    hipStream_t s;
-    int n_cu;
-    const double2 *d_H00, *d_H01;
-    const void* d_V;
-    const double2* d_z;
-    int64_t nkc, sample_chunk;
-    int max_it;
-    unsigned long long key0;
-    double* d_ws;
-    int32_t* d_it;
-    double* d_T;
-    unsigned long long* d_flag;
-};
 
 template <int NP, bool DIAG>
 int ens_launch_np(tbk_flag_row* done, const EnsShape& sh, const EnsLaunch& a) {
     using Geo = SurfGeom<NP>;
     const void* kernel = reinterpret_cast<const void*>(transmission_ensemble_kernel<NP, DIAG>);
     if (done != nullptr) TBK_HIP(tbk_raise_lds_limit(kernel, (int)TransGeom<NP>::lds_bytes, *done));
-    int64_t spg = std::min<int64_t>(a.sample_chunk, sh.n_s);
-    if (a.sample_chunk == 0) {
-        // R: the workgroups resident at once; G groups fill them and no more; the samples of a group
-        int per_cu = 1;
-        if (!Geo::GLOBAL) {
-            TBK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, Geo::THREADS, TransGeom<NP>::lds_bytes));
-            per_cu = std::max(per_cu, 1);
-        }
-        const int64_t resident = (int64_t)std::max(a.n_cu, 1) * per_cu, kz = a.nkc * sh.n_z;
-        const int64_t want = std::min<int64_t>(sh.n_s, (resident + kz - 1) / kz);
-        spg = (sh.n_s + want - 1) / want;
-    }
-    const int64_t groups = (sh.n_s + spg - 1) / spg;  // (no group is empty)
+    int64_t spg = 0, groups = 0;
+    TBK_CHECK(ens_sample_groups<NP>(kernel, sh, a, spg, groups));
     const int64_t items = a.nkc * sh.n_z * groups;
     hipLaunchKernelGGL((transmission_ensemble_kernel<NP, DIAG>), dim3((unsigned)surf_grid(sh.n, items, a.n_cu)), dim3(Geo::THREADS), TransGeom<NP>::lds_bytes,
                        a.s, a.d_H00, a.d_H01, a.d_V, sh.m_layers, (int)sh.n_s, (int)spg, (int)groups, a.d_z, (int)sh.n_z, sh.n, items, a.max_it, a.key0,
@@ -146,7 +99,12 @@ int ens_launch(const EnsShape& sh, const EnsLaunch& a) {
 }
 
 // what the entry points check of the devices; the samples are staged once per call
-int ens_check_devices(const EnsShape& sh, const double* V, const double* onsite, const int32_t* iterations, const double* T) {
+int ens_check_devices(const EnsRoute& route, const EnsShape& sh, const double* V, const double* onsite, const int32_t* iterations, const double* T,
+                      const double* channels) {
+    if (route.channels && sh.n > SURF_OWN_MAX) {
+        tbk_set_error("invalid argument: a principal layer of %d rows: %s takes at most %d", sh.n, route.family, SURF_OWN_MAX);
+        return TBK_ERR_ARGUMENT;
+    }
     TBK_ARG(sh.m_layers >= 1 && sh.m_layers <= TRANS_MAX_LAYERS, "the device must have 1 to 4096 principal layers");
     TBK_ARG(sh.n_s >= 1 && sh.n_s <= ENS_MAX_SAMPLES, "n_s must be 1 to 4096");
     TBK_ARG((V != nullptr) != (onsite != nullptr), "exactly one of V and onsite must be given");
@@ -155,21 +113,22 @@ int ens_check_devices(const EnsShape& sh, const double* V, const double* onsite,
         return TBK_ERR_ARGUMENT;
     }
     TBK_ARG(iterations != nullptr && T != nullptr, "iterations / T is NULL");
+    TBK_ARG(!route.channels || channels != nullptr, "channels is NULL");
     return TBK_OK;
 }
 
 // The two status words of a chunk as one in the kernel's keys: the decimation of the library route names sample 0.
-unsigned long long ens_chunk_word(const unsigned long long* two) {
+unsigned long long ens_chunk_word(const EnsRoute& route, const unsigned long long* two) {
     unsigned long long word = two[0];
-    if (two[1] != SURF_NO_FLAG) word = std::min(word, (two[1] >> 1) * (unsigned long long)ENS_MAX_SAMPLES * 2ull + (two[1] & 1ull));
+    if (two[1] != SURF_NO_FLAG) word = std::min(word, (two[1] >> 1) * (unsigned long long)ENS_MAX_SAMPLES * route.radix + (two[1] & 1ull));
     return word;
 }
 
 // the status word as an error: the first (point, energy, sample) of the call that failed
-int ens_status_error(unsigned long long word, const double* z, int max_iterations) {
+int ens_status_error(const EnsRoute& route, unsigned long long word, const double* z, int max_iterations) {
     if (word == SURF_NO_FLAG) return TBK_OK;
-    const int reason = (int)(word & 1ull);
-    unsigned long long key = word >> 1;
+    const int reason = (int)(word % route.radix);
+    unsigned long long key = word / route.radix;
     const long long sample = (long long)(key % (unsigned long long)ENS_MAX_SAMPLES);
     key /= (unsigned long long)ENS_MAX_SAMPLES;
     const long long point = (long long)(key / (unsigned long long)SURF_MAX_Z), zi = (long long)(key % (unsigned long long)SURF_MAX_Z);
@@ -178,16 +137,26 @@ int ens_status_error(unsigned long long word, const double* z, int max_iteration
                       z[2 * zi + 1], sample);
         return TBK_ERR_SINGULAR;
     }
+    if (reason == 2) {
+        tbk_set_error("the channel iteration (the Jacobi sweeps of the transmission eigenvalues) did not converge at k index %lld, energy %lld "
+                      "(z = %.17g%+.17gj) and sample %lld",
+                      point, zi, z[2 * zi], z[2 * zi + 1], sample);
+        return TBK_ERR_NO_CONVERGENCE;
+    }
     tbk_set_error("the decimation did not converge in %d iterations at k index %lld and energy %lld (z = %.17g%+.17gj)", max_iterations, point, zi,
                   z[2 * zi], z[2 * zi + 1]);
     return TBK_ERR_NO_CONVERGENCE;
 }
 
+const EnsRoute ENS_ROUTE = {ens_launch, 2u, false, TIMED_TRANSMISSION_ENSEMBLE, ENS_FAMILY};
+
 }  // namespace
 
-extern "C" int tbk_transmission_ensemble_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, int64_t n_s,
-                                                       const double* V, const double* onsite, int64_t n_z, const double* z, int max_iterations,
-                                                       int64_t k_chunk, int64_t sample_chunk, int32_t* iterations, double* T) {
+// The kernel of `route` alone on principal layers the caller brings (tbk_transmission_ensemble_from_matrices and
+// tbk_transmission_channels_from_matrices)
+int tbk_ens_from_matrices(const EnsRoute& route, int device, int N, int64_t n_k, const double* H00, const double* H01, int M, int64_t n_s, const double* V,
+                          const double* onsite, int64_t n_z, const double* z, int max_iterations, int64_t k_chunk, int64_t sample_chunk,
+                          int32_t* iterations, double* T, double* channels) {
     TBK_CHECK(surf_check_energies(N, n_z, z, max_iterations));
     TBK_ARG(H01 != nullptr, "H01 is NULL: the transmission needs hopping between the principal layers");
     EnsShape sh;
@@ -196,8 +165,9 @@ extern "C" int tbk_transmission_ensemble_from_matrices(int device, int N, int64_
     sh.n_z = n_z;
     sh.n_s = n_s;
     sh.diag = onsite != nullptr;
-    TBK_CHECK(ens_check_devices(sh, V, onsite, iterations, T));
-    // ((n_k SURF_MAX_Z + n_z) ENS_MAX_SAMPLES + n_s) 2 + 1 < 2^64 needs n_k < 2^39; 2^36 leaves room)
+    sh.channels = route.channels;
+    TBK_CHECK(ens_check_devices(route, sh, V, onsite, iterations, T, channels));
+    // ((n_k SURF_MAX_Z + n_z) ENS_MAX_SAMPLES + n_s) 2 + 1 < 2^64 needs n_k < 2^39; 2^36 leaves room, radix 4 included)
     TBK_ARG(n_k >= 1 && n_k < (int64_t(1) << 36), "n_k must be 1 to 2^36 - 1");
     TBK_ARG(H00 != nullptr, "H00 is NULL");
     TBK_ARG(k_chunk >= 0, "k_chunk < 0");
@@ -212,7 +182,7 @@ extern "C" int tbk_transmission_ensemble_from_matrices(int device, int N, int64_
     TBK_CHECK(d_V.reserve(sh.device_bytes()));
     TBK_CHECK(d_z.reserve((size_t)n_z * sizeof(double2)));
     TBK_CHECK(d_res.reserve(sh.result_bytes(chunk) + EnsShape::flag_bytes));
-    const bool library = N > SURF_OWN_MAX;
+    const bool library = N > SURF_OWN_MAX;  // (never with channels: ens_check_devices)
     const size_t ws_bytes = library ? tbk_trans_ens_lib_bytes(N) : ens_workspace_bytes(sh, chunk, n_cu);
     if (ws_bytes > 0) TBK_CHECK(d_ws.reserve(ws_bytes));
     Owned<rocblas_handle, rocblas_destroy_handle> blas;
@@ -226,6 +196,7 @@ extern "C" int tbk_transmission_ensemble_from_matrices(int device, int N, int64_
         char* res = d_res.as<char>();
         double* d_T = reinterpret_cast<double*>(res);
         int32_t* d_it = reinterpret_cast<int32_t*>(res + sh.t_bytes(nkc));
+        double* d_ch = sh.channels ? reinterpret_cast<double*>(res + sh.t_bytes(nkc) + sh.it_bytes(nkc)) : nullptr;
         unsigned long long* d_flag = reinterpret_cast<unsigned long long*>(res + sh.result_bytes(nkc));
         TBK_HIP(hipMemcpy(d_H00.ptr, H00 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
         TBK_HIP(hipMemcpy(d_H01.ptr, H01 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
@@ -236,23 +207,31 @@ extern "C" int tbk_transmission_ensemble_from_matrices(int device, int N, int64_
                                               max_iterations, c0, d_it, d_T, d_flag));
         } else {
             const EnsLaunch a = {nullptr, n_cu, d_H00.as<double2>(), d_H01.as<double2>(), d_V.ptr, d_z.as<double2>(), nkc, sample_chunk, max_iterations,
-                                 (unsigned long long)c0 * (unsigned long long)SURF_MAX_Z, d_ws.as<double>(), d_it, d_T, d_flag};
-            TBK_CHECK(ens_launch(sh, a));
+                                 (unsigned long long)c0 * (unsigned long long)SURF_MAX_Z, d_ws.as<double>(), d_it, d_T, d_flag, d_ch};
+            TBK_CHECK(route.launch(sh, a));
         }
         unsigned long long two[2] = {SURF_NO_FLAG, SURF_NO_FLAG};
         TBK_HIP(hipMemcpy(T + (size_t)c0 * n_z * n_s, d_T, items * n_s * sizeof(double), hipMemcpyDeviceToHost));
         TBK_HIP(hipMemcpy(iterations + (size_t)c0 * n_z, d_it, items * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (sh.channels) TBK_HIP(hipMemcpy(channels + (size_t)c0 * n_z * n_s * N, d_ch, items * n_s * N * sizeof(double), hipMemcpyDeviceToHost));
         TBK_HIP(hipMemcpy(two, d_flag, EnsShape::flag_bytes, hipMemcpyDeviceToHost));
-        word = std::min(word, ens_chunk_word(two));
+        word = std::min(word, ens_chunk_word(route, two));
     }
-    return ens_status_error(word, z, max_iterations);
+    return ens_status_error(route, word, z, max_iterations);
+}
+
+extern "C" int tbk_transmission_ensemble_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, int64_t n_s,
+                                                       const double* V, const double* onsite, int64_t n_z, const double* z, int max_iterations,
+                                                       int64_t k_chunk, int64_t sample_chunk, int32_t* iterations, double* T) {
+    return tbk_ens_from_matrices(ENS_ROUTE, device, N, n_k, H00, H01, M, n_s, V, onsite, n_z, z, max_iterations, k_chunk, sample_chunk, iterations, T,
+                                 nullptr);
 }
 
 // The whole call on one handle; k_base as in tbk_surface_green_slab.  The buffers are tbk_transmission's (tbk_internal.h), ws_mesh_io
 // holding the samples.
-int tbk_transmission_ensemble_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M_device, int64_t n_s,
-                                   const double* V, const double* onsite, int64_t n_z, const double* z, int max_iterations, int32_t* iterations,
-                                   double* T) {
+int tbk_ens_slab(const EnsRoute& route, tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M_device, int64_t n_s,
+                 const double* V, const double* onsite, int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T,
+                 double* channels) {
     TBK_ARG(m != nullptr, "model is NULL");
     TBK_LOCK(m);
     TBK_ARG(!m->kdotp, "the transmission needs a tight-binding model");
@@ -275,8 +254,9 @@ int tbk_transmission_ensemble_slab(tbk_model* m, int64_t k_base, int axis, int l
     sh.n_z = n_z;
     sh.n_s = n_s;
     sh.diag = onsite != nullptr;
+    sh.channels = route.channels;
     const int N = sh.n;
-    TBK_CHECK(ens_check_devices(sh, V, onsite, iterations, T));
+    TBK_CHECK(ens_check_devices(route, sh, V, onsite, iterations, T, channels));
     TBK_ARG(nk >= 0 && k_base >= 0 && k_base + nk < (int64_t(1) << 36), "nk must be 0 to 2^36 - 1");
     if (nk == 0) return TBK_OK;
     TBK_ARG(k != nullptr || dim == 1, "k is NULL");
@@ -298,15 +278,15 @@ int tbk_transmission_ensemble_slab(tbk_model* m, int64_t k_base, int axis, int l
     SpanRecorder* ev = &streams.used.back().ev;
     const size_t z_bytes = surf_align256((size_t)n_z * sizeof(double2)), tw_bytes = h_tw.size() * sizeof(double);
     const size_t layer_bytes = surf_align256((size_t)chunk * N * N * sizeof(double2));
-    const bool library = N > SURF_OWN_MAX || m->eigensolver == TBK_EIG_ROCSOLVER;
+    const bool library = !route.channels && (N > SURF_OWN_MAX || m->eigensolver == TBK_EIG_ROCSOLVER);  // (channels: the own kernel only)
     const size_t ws_bytes = library ? tbk_trans_ens_lib_bytes(N) : ens_workspace_bytes(sh, chunk, m->n_cu);
-    TBK_CHECK(mesh_reserve(m->ws_mesh_k, h_k.size() * sizeof(double), ENS_FAMILY, "the k list with its samples along the stacking axis"));
-    TBK_CHECK(mesh_reserve(m->ws_dm_r, z_bytes + tw_bytes, ENS_FAMILY, "the energies and the twiddles"));
-    TBK_CHECK(mesh_reserve(m->ws_dm_rho, sh.result_bytes(chunk) + EnsShape::flag_bytes, ENS_FAMILY, "the results of one chunk"));
-    TBK_CHECK(mesh_reserve(m->ws_dm_p, 2 * layer_bytes, ENS_FAMILY, "the principal layers of one chunk"));
-    TBK_CHECK(mesh_reserve(m->ws_pdos_u, (size_t)chunk * M * nn2 * sizeof(double), ENS_FAMILY, "H(k) of one chunk"));
-    TBK_CHECK(mesh_reserve(m->ws_mesh_io, sh.device_bytes(), ENS_FAMILY, "the devices of the ensemble"));
-    if (ws_bytes > 0) TBK_CHECK(mesh_reserve(m->ws_mesh_work, ws_bytes, ENS_FAMILY, library ? "the library's batch" : "the workgroups' matrices"));
+    TBK_CHECK(mesh_reserve(m->ws_mesh_k, h_k.size() * sizeof(double), route.family, "the k list with its samples along the stacking axis"));
+    TBK_CHECK(mesh_reserve(m->ws_dm_r, z_bytes + tw_bytes, route.family, "the energies and the twiddles"));
+    TBK_CHECK(mesh_reserve(m->ws_dm_rho, sh.result_bytes(chunk) + EnsShape::flag_bytes, route.family, "the results of one chunk"));
+    TBK_CHECK(mesh_reserve(m->ws_dm_p, 2 * layer_bytes, route.family, "the principal layers of one chunk"));
+    TBK_CHECK(mesh_reserve(m->ws_pdos_u, (size_t)chunk * M * nn2 * sizeof(double), route.family, "H(k) of one chunk"));
+    TBK_CHECK(mesh_reserve(m->ws_mesh_io, sh.device_bytes(), route.family, "the devices of the ensemble"));
+    if (ws_bytes > 0) TBK_CHECK(mesh_reserve(m->ws_mesh_work, ws_bytes, route.family, library ? "the library's batch" : "the workgroups' matrices"));
     if (library) m->counters[TBK_CNT_LIBRARY_CALLS] += 1;
     double* d_k = m->ws_mesh_k.as<double>();
     char* d_zt = m->ws_dm_r.as<char>();
@@ -324,6 +304,7 @@ int tbk_transmission_ensemble_slab(tbk_model* m, int64_t k_base, int axis, int l
         const size_t items = (size_t)nkc * n_z;
         double* d_T = reinterpret_cast<double*>(d_res);
         int32_t* d_it = reinterpret_cast<int32_t*>(d_res + sh.t_bytes(nkc));
+        double* d_ch = sh.channels ? reinterpret_cast<double*>(d_res + sh.t_bytes(nkc) + sh.it_bytes(nkc)) : nullptr;
         unsigned long long* d_flag = reinterpret_cast<unsigned long long*>(d_res + sh.result_bytes(nkc));
         TBK_CHECK(surf_chunk_layers(m, ev, d_k + (size_t)c0 * M * dim, nkc, L, d_H, reinterpret_cast<const double*>(d_zt + z_bytes), d_H00, d_H01));
         TBK_HIP(hipMemsetAsync(d_flag, 0xff, EnsShape::flag_bytes, m->stream));
@@ -334,20 +315,28 @@ int tbk_transmission_ensemble_slab(tbk_model* m, int64_t k_base, int axis, int l
                                               nkc, max_iterations, k_base + c0, d_it, d_T, d_flag));
         } else {
             const EnsLaunch a = {m->stream, m->n_cu, d_H00, d_H01, m->ws_mesh_io.ptr, d_z, nkc, 0, max_iterations,
-                                 (unsigned long long)(k_base + c0) * (unsigned long long)SURF_MAX_Z, m->ws_mesh_work.as<double>(), d_it, d_T, d_flag};
-            TBK_CHECK(ens_launch(sh, a));
+                                 (unsigned long long)(k_base + c0) * (unsigned long long)SURF_MAX_Z, m->ws_mesh_work.as<double>(), d_it, d_T, d_flag, d_ch};
+            TBK_CHECK(route.launch(sh, a));
         }
         if (ev) ev->stop();
         if (ev) ev->start(2);
         TBK_HIP(hipMemcpyAsync(T + (size_t)c0 * n_z * n_s, d_T, items * n_s * sizeof(double), hipMemcpyDeviceToHost, m->stream));
         TBK_HIP(hipMemcpyAsync(iterations + (size_t)c0 * n_z, d_it, items * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
+        if (sh.channels)
+            TBK_HIP(hipMemcpyAsync(channels + (size_t)c0 * n_z * n_s * N, d_ch, items * n_s * N * sizeof(double), hipMemcpyDeviceToHost, m->stream));
         TBK_HIP(hipMemcpyAsync(&words[(size_t)ci * 2], d_flag, EnsShape::flag_bytes, hipMemcpyDeviceToHost, m->stream));
         if (ev) ev->stop();
     }
-    TBK_CHECK(streams.finish(TIMED_TRANSMISSION_ENSEMBLE));
+    TBK_CHECK(streams.finish((TimedFamily)route.timed));
     unsigned long long word = SURF_NO_FLAG;
-    for (size_t ci = 0; ci < words.size(); ci += 2) word = std::min(word, ens_chunk_word(&words[ci]));
-    return ens_status_error(word, z, max_iterations);
+    for (size_t ci = 0; ci < words.size(); ci += 2) word = std::min(word, ens_chunk_word(route, &words[ci]));
+    return ens_status_error(route, word, z, max_iterations);
+}
+
+int tbk_transmission_ensemble_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M_device, int64_t n_s,
+                                   const double* V, const double* onsite, int64_t n_z, const double* z, int max_iterations, int32_t* iterations,
+                                   double* T) {
+    return tbk_ens_slab(ENS_ROUTE, m, k_base, axis, layers, k, nk, M_device, n_s, V, onsite, n_z, z, max_iterations, iterations, T, nullptr);
 }
 
 extern "C" int tbk_transmission_ensemble(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int M, int64_t n_s, const double* V,

@@ -178,11 +178,11 @@ struct SpanRecorder {
 };
 
 // The sums the mesh calls book their kernel times on, one row per family (tbk_dos_timing, tbk_pdos_timing, tbk_fermi_timing,
-// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing, tbk_surface_timing, tbk_transmission_timing, tbk_device_green_timing, tbk_device_current_timing, tbk_transmission_ensemble_timing: what each counts differs and is
+// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing, tbk_surface_timing, tbk_transmission_timing, tbk_device_green_timing, tbk_device_current_timing, tbk_transmission_ensemble_timing, tbk_transmission_channels_timing: what each counts differs and is
 // listed in DESIGN.md section 10)
-enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_SURFACE, TIMED_TRANSMISSION, TIMED_DEVICE_GREEN, TIMED_DEVICE_CURRENT, TIMED_TRANSMISSION_ENSEMBLE, TIMED_COUNT };
+enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_SURFACE, TIMED_TRANSMISSION, TIMED_DEVICE_GREEN, TIMED_DEVICE_CURRENT, TIMED_TRANSMISSION_ENSEMBLE, TIMED_TRANSMISSION_CHANNELS, TIMED_COUNT };
 struct TimedSums {
-    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green, the dressed green, surface, transmission, the device green, the device current and the ensemble three)
+    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green, the dressed green, surface, transmission, the device green, the device current, the ensemble and the channels three)
     int64_t calls = 0;
     int64_t passes = 0;  // fermi: the passes of its searches
 };
@@ -396,6 +396,11 @@ int tbk_transmission_slab(tbk_model* m, int64_t k_base, int axis, int layers, co
 // tbk_ensemble.hip: tbk_transmission_ensemble in the same way (the slabs of tbk_transmission_ensemble_multi)
 int tbk_transmission_ensemble_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M, int64_t n_s, const double* V,
                                    const double* onsite, int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T);
+
+// tbk_channels.hip: tbk_transmission_channels in the same way (the slabs of tbk_transmission_channels_multi)
+int tbk_transmission_channels_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M, int64_t n_s, const double* V,
+                                   const double* onsite, int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T,
+                                   double* channels);
 
 // tbk_surface.hip: the library route of the ensemble for tbk_ensemble.hip -- the bytes of its workspace d_ws, and one chunk of nkc
 // points on it.  Exactly one of d_V ([n_s][m_layers][n][n] complex) and d_onsite ([n_s][m_layers][n]) is not NULL; d_T: [nkc][n_z][n_s];

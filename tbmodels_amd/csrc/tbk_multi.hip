@@ -168,6 +168,25 @@ extern "C" int tbk_transmission_ensemble_multi(tbk_model* const* handles, int n_
     });
 }
 
+// The transmission eigenvalues on several devices (tbk_channels.hip): the slabs of tbk_transmission_ensemble_multi
+extern "C" int tbk_transmission_channels_multi(tbk_model* const* handles, int n_handles, int axis, int layers, const double* k, int64_t nk, int M,
+                                               int64_t n_s, const double* V, const double* onsite, int64_t n_z, const double* z, int max_iterations,
+                                               int32_t* iterations, double* T, double* channels) {
+    TBK_CHECK(check_handles(handles, n_handles));
+    TBK_ARG(nk >= 0, "nk < 0");
+    if (n_handles == 1 || nk == 0)
+        return tbk_transmission_channels(handles[0], axis, layers, k, nk, M, n_s, V, onsite, n_z, z, max_iterations, iterations, T, channels);
+    TBK_ARG(n_z >= 1 && n_z <= 4096 && layers >= 1 && layers <= 1024 && n_s >= 1 && n_s <= 4096, "n_z and n_s must be 1 to 4096, layers 1 ... 1024");
+    TBK_ARG(iterations != nullptr && T != nullptr && channels != nullptr, "iterations / T / channels is NULL");
+    const int dim = handles[0]->dim;
+    TBK_ARG(k != nullptr || dim == 1, "k is NULL");
+    const int64_t N = (int64_t)handles[0]->n_orb * layers;
+    return run_slabs(n_handles, nk, [&](int i, int64_t lo, int64_t count) {
+        return tbk_transmission_channels_slab(handles[i], lo, axis, layers, k != nullptr ? k + lo * (dim - 1) : nullptr, count, M, n_s, V, onsite, n_z, z,
+                                              max_iterations, iterations + lo * n_z, T + lo * n_z * n_s, channels + lo * n_z * n_s * N);
+    });
+}
+
 // The device Green's function on several devices (tbk_device_green.hip): the slabs of tbk_transmission_multi; every handle stages the whole V
 extern "C" int tbk_device_green_multi(tbk_model* const* handles, int n_handles, int axis, int layers, const double* k, int64_t nk, int M, const double* V,
                                       int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T, double* ldos, double* left,
