@@ -12,7 +12,8 @@
 //                            Jacobi of chan_jacobi; the squared column norms, sorted by rank counting, to the output.  It consumes X, Y,
 //                            D and nothing else: P_M, es, et, H01 and H01^H stay for the next sample.
 //
-// The hosts are tbk_ensemble.hip's drivers (tbk_ensemble.h) with this kernel as their route: the same chunks, staging and groups.
+// The host is EnsFamily (tbk_ensemble.h) with this kernel as its route, behind the drivers of tbk_layered.h: the same chunks, staging
+// and groups.
 
 #include <type_traits>
 
@@ -376,13 +377,12 @@ __global__ void __launch_bounds__(SurfGeom<NP>::THREADS)
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-tbk_flag_row chan_lds_done[2][2];  // [NP = 32, 64][DIAG]: more than 64 KiB of dynamic LDS
-
 template <int NP, bool DIAG>
-int chan_launch_np(tbk_flag_row* done, const EnsShape& sh, const EnsLaunch& a) {
+int chan_launch_np(const EnsShape& sh, const EnsLaunch& a) {
     using Geo = SurfGeom<NP>;
+    static tbk_flag_row done;  // of this instantiation's kernel
     const void* kernel = reinterpret_cast<const void*>(transmission_channels_kernel<NP, DIAG>);
-    if (done != nullptr) TBK_HIP(tbk_raise_lds_limit(kernel, (int)TransGeom<NP>::lds_bytes, *done));
+    if (TransGeom<NP>::lds_bytes > SURF_LDS_DEFAULT) TBK_HIP(tbk_raise_lds_limit(kernel, (int)TransGeom<NP>::lds_bytes, done));
     int64_t spg = 0, groups = 0;
     TBK_CHECK(ens_sample_groups<NP>(kernel, sh, a, spg, groups));  // the ensemble's rule: the dynamic LDS, and so the occupancy, are its kernel's
     const int64_t items = a.nkc * sh.n_z * groups;
@@ -395,9 +395,9 @@ int chan_launch_np(tbk_flag_row* done, const EnsShape& sh, const EnsLaunch& a) {
 
 // The chunk's nkc points at every energy and sample (N <= 64: the drivers have checked it)
 int chan_launch(const EnsShape& sh, const EnsLaunch& a) {
-    if (sh.n <= 16) return sh.diag ? chan_launch_np<16, true>(nullptr, sh, a) : chan_launch_np<16, false>(nullptr, sh, a);
-    if (sh.n <= 32) return sh.diag ? chan_launch_np<32, true>(&chan_lds_done[0][1], sh, a) : chan_launch_np<32, false>(&chan_lds_done[0][0], sh, a);
-    return sh.diag ? chan_launch_np<64, true>(&chan_lds_done[1][1], sh, a) : chan_launch_np<64, false>(&chan_lds_done[1][0], sh, a);
+    return surf_with_np(sh.n, [&](auto np) {
+        return sh.diag ? chan_launch_np<decltype(np)::value, true>(sh, a) : chan_launch_np<decltype(np)::value, false>(sh, a);
+    });
 }
 
 const EnsRoute CHAN_ROUTE = {chan_launch, 4u, true, TIMED_TRANSMISSION_CHANNELS, CHAN_FAMILY};
@@ -407,15 +407,16 @@ const EnsRoute CHAN_ROUTE = {chan_launch, 4u, true, TIMED_TRANSMISSION_CHANNELS,
 extern "C" int tbk_transmission_channels_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, int64_t n_s,
                                                        const double* V, const double* onsite, int64_t n_z, const double* z, int max_iterations,
                                                        int64_t k_chunk, int64_t sample_chunk, int32_t* iterations, double* T, double* channels) {
-    return tbk_ens_from_matrices(CHAN_ROUTE, device, N, n_k, H00, H01, M, n_s, V, onsite, n_z, z, max_iterations, k_chunk, sample_chunk, iterations, T,
-                                 channels);
+    EnsFamily fam(CHAN_ROUTE, M, n_s, V, onsite, n_z, sample_chunk, iterations, T, channels);
+    return layered_from_matrices(fam, device, N, n_k, H00, H01, n_z, z, max_iterations, k_chunk);
 }
 
 // The whole call on one handle; k_base as in tbk_surface_green_slab
 int tbk_transmission_channels_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M_device, int64_t n_s,
                                    const double* V, const double* onsite, int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T,
                                    double* channels) {
-    return tbk_ens_slab(CHAN_ROUTE, m, k_base, axis, layers, k, nk, M_device, n_s, V, onsite, n_z, z, max_iterations, iterations, T, channels);
+    EnsFamily fam(CHAN_ROUTE, M_device, n_s, V, onsite, n_z, 0, iterations, T, channels);
+    return layered_slab(fam, m, k_base, axis, layers, k, nk, n_z, z, max_iterations);
 }
 
 extern "C" int tbk_transmission_channels(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int M, int64_t n_s, const double* V,

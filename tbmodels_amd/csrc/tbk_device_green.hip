@@ -25,7 +25,7 @@
 //                         the block of the layer above, which waits in the stack's dead place of g_{p+1} (H01^H Q_p), two more per layer
 //                         and four when J is returned.  The false instantiation is the kernel above, statement for statement.
 
-#include "tbk_surface.h"
+#include "tbk_layered.h"
 
 namespace {
 
@@ -34,8 +34,6 @@ constexpr const char* DEVG_SINGULAR = "z - D of a device layer, a block of the d
 constexpr const char* DEVC_SINGULAR =
     "z - D of a device layer, a block of the device's Green's function, a bond current, or z - e of the decimation,";
 constexpr size_t DEVG_STACK_BUDGET = size_t(1) << 30;  // the workgroups' stacks of one launch: at M = 4096, N = 64 two still fit
-tbk_flag_row devg_lds_done_32, devg_lds_done_64;      // more than 64 KiB of dynamic LDS
-tbk_flag_row devc_lds_done_32, devc_lds_done_64;      // ... of the CURRENT instantiations
 
 // Re sum_j A[row][j] conj(B[row][j]) / (2 pi) for every row below n into out[row], in a fixed order: a thread sums NP / PARTS columns
 // of its row, the first NP threads add the parts in order.  A: pitch NP + 1; B: pitch SB.  One barrier inside and one at the end.
@@ -449,12 +447,13 @@ size_t devg_workspace_bytes(const DevgShape& sh, int64_t items, int n_cu, int64_
 }
 
 template <int NP, bool CURRENT>
-int devg_launch_np(hipStream_t s, int n_cu, tbk_flag_row* done, const DevgShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_V,
-                   const double2* d_z, int64_t nkc, int max_it, unsigned long long key0, int64_t slots, double* d_ws, double2* d_stack, char* d_res) {
+int devg_launch_np(hipStream_t s, int n_cu, const DevgShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_V, const double2* d_z,
+                   int64_t nkc, int max_it, unsigned long long key0, int64_t slots, double* d_ws, double2* d_stack, char* d_res) {
     using Geo = SurfGeom<NP>;
+    static tbk_flag_row done;  // of this instantiation's kernel
     const int64_t items = nkc * sh.n_z;
-    if (done != nullptr)
-        TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(device_green_kernel<NP, CURRENT>), (int)TransGeom<NP>::lds_bytes, *done));
+    if (TransGeom<NP>::lds_bytes > SURF_LDS_DEFAULT)
+        TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(device_green_kernel<NP, CURRENT>), (int)TransGeom<NP>::lds_bytes, done));
     char* at = d_res;
     double* d_T = reinterpret_cast<double*>(at);
     at += sh.t_bytes(nkc);
@@ -484,16 +483,11 @@ int devg_launch_np(hipStream_t s, int n_cu, tbk_flag_row* done, const DevgShape&
 int devg_launch(hipStream_t s, int n_cu, const DevgShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_V, const double2* d_z,
                 int64_t nkc, int max_it, int64_t k0, int64_t slots, double* d_ws, double2* d_stack, char* d_res) {
     const unsigned long long key0 = (unsigned long long)k0 * (unsigned long long)SURF_MAX_Z;
-    if (sh.current) {
-        if (sh.n <= 16) return devg_launch_np<16, true>(s, n_cu, nullptr, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, slots, d_ws, d_stack, d_res);
-        if (sh.n <= 32)
-            return devg_launch_np<32, true>(s, n_cu, &devc_lds_done_32, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, slots, d_ws, d_stack, d_res);
-        return devg_launch_np<64, true>(s, n_cu, &devc_lds_done_64, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, slots, d_ws, d_stack, d_res);
-    }
-    if (sh.n <= 16) return devg_launch_np<16, false>(s, n_cu, nullptr, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, slots, d_ws, d_stack, d_res);
-    if (sh.n <= 32)
-        return devg_launch_np<32, false>(s, n_cu, &devg_lds_done_32, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, slots, d_ws, d_stack, d_res);
-    return devg_launch_np<64, false>(s, n_cu, &devg_lds_done_64, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, slots, d_ws, d_stack, d_res);
+    return surf_with_np(sh.n, [&](auto np) {
+        constexpr int NP = decltype(np)::value;
+        return sh.current ? devg_launch_np<NP, true>(s, n_cu, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, slots, d_ws, d_stack, d_res)
+                          : devg_launch_np<NP, false>(s, n_cu, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, slots, d_ws, d_stack, d_res);
+    });
 }
 
 // what the entry points check beyond the transmission's: the rows, the stack of one workgroup, the outputs
@@ -520,198 +514,102 @@ int devg_check_current(const DevgCurrentOut& cur) {
     return TBK_OK;
 }
 
-// the copies of a chunk's results to the host (s NULL: synchronous); *word receives the chunk's status word
-int devg_copy_out(hipStream_t s, bool async, const DevgShape& sh, const char* d_res, int64_t nkc, int64_t c0, int32_t* iterations, double* T, double* ldos,
-                  double* left, double* right, double* G, double* F, double* C, const DevgCurrentOut* cur, unsigned long long* word) {
-    const size_t items = (size_t)nkc * sh.n_z, first = (size_t)c0 * sh.n_z;
-    const size_t rows = (size_t)sh.m_layers * sh.n, mats = rows * sh.n * 2;
-    auto copy = [&](void* dst, const void* src, size_t bytes) {
-        return async ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) : hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
-    };
-    const char* at = d_res;
-    TBK_HIP(copy(T + first, at, items * sizeof(double)));
-    at += sh.t_bytes(nkc);
-    TBK_HIP(copy(iterations + first, at, items * sizeof(int32_t)));
-    at += sh.it_bytes(nkc);
-    double* row_out[3] = {ldos, left, right};
-    for (int i = 0; i < 3; ++i, at += sh.row_bytes(nkc)) TBK_HIP(copy(row_out[i] + first * rows, at, items * rows * sizeof(double)));
-    double* mat_out[3] = {G, F, C};
-    if (sh.green)
-        for (int i = 0; i < 3; ++i, at += sh.mat_bytes(nkc)) TBK_HIP(copy(mat_out[i] + first * mats, at, items * mats * sizeof(double)));
-    if (sh.current) {
-        const size_t krows = (size_t)(sh.m_layers - 1) * sh.n, kmats = krows * sh.n, jmats = rows * sh.n;
-        double* cur_out[2] = {cur->cur_l, cur->cur_r};
-        double* inter_out[2] = {cur->inter_l, cur->inter_r};
-        double* intra_out[2] = {cur->intra_l, cur->intra_r};
-        if (krows > 0)
-            for (int i = 0; i < 2; ++i) TBK_HIP(copy(cur_out[i] + first * krows, at + i * sh.cur_bytes(nkc), items * krows * sizeof(double)));
-        at += 2 * sh.cur_bytes(nkc);
-        if (sh.bonds) {
-            if (kmats > 0)
-                for (int i = 0; i < 2; ++i) TBK_HIP(copy(inter_out[i] + first * kmats, at + i * sh.inter_bytes(nkc), items * kmats * sizeof(double)));
-            at += 2 * sh.inter_bytes(nkc);
-            for (int i = 0; i < 2; ++i, at += sh.intra_bytes(nkc)) TBK_HIP(copy(intra_out[i] + first * jmats, at, items * jmats * sizeof(double)));
-        }
-    }
-    TBK_HIP(copy(word, d_res + sh.result_bytes(nkc), sizeof(unsigned long long)));
-    return TBK_OK;
-}
-
-// tbk_device_green_from_matrices (cur NULL) and tbk_device_current_from_matrices
-int devg_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, const double* V, int64_t n_z, const double* z,
-                       int max_iterations, int64_t k_chunk, int64_t slots, int32_t* iterations, double* T, double* ldos, double* left, double* right,
-                       double* G, double* F, double* C, const DevgCurrentOut* cur) {
-    TBK_CHECK(surf_check_energies(std::min(N, SURF_LIB_MAX), n_z, z, max_iterations));
-    TBK_ARG(H01 != nullptr, "H01 is NULL: the device Green's function needs hopping between the principal layers");
-    TBK_CHECK(trans_check_device(N, M, V, iterations, T));
-    TBK_CHECK(devg_check(N, M, ldos, left, right, G, F, C));
-    if (cur != nullptr) TBK_CHECK(devg_check_current(*cur));
-    TBK_ARG(n_k >= 1 && n_k < (int64_t(1) << 40), "n_k < 1");
-    TBK_ARG(H00 != nullptr, "H00 is NULL");
-    TBK_ARG(k_chunk >= 0, "k_chunk < 0");
-    TBK_ARG(slots >= 0, "slots < 0");
-    TBK_CHECK(tetra_check_device(device));
+// tbk_device_green* (cur NULL, timed on TIMED_DEVICE_GREEN) and tbk_device_current* (TIMED_DEVICE_CURRENT) behind the drivers of
+// tbk_layered.h.  There is no library route: a handle with TBK_EIG_ROCSOLVER takes the own kernel too.  on_handle: the whole call on
+// one handle looks at the outputs before the device, the kernel alone at the device first; slots: the option of *_from_matrices.
+struct DevgFamily : LayeredFamily {
     DevgShape sh;
-    sh.n = N;
-    sh.m_layers = M;
-    sh.n_z = n_z;
-    sh.green = G != nullptr;
-    sh.current = cur != nullptr;
-    sh.bonds = cur != nullptr && cur->inter_l != nullptr;
-    const int64_t chunk = std::min<int64_t>(n_k, k_chunk > 0 ? k_chunk : sh.auto_chunk(n_k));
-    const int n_cu = surf_device_cus(device);
-    const size_t nn = (size_t)N * N, h_bytes = (size_t)chunk * nn * sizeof(double2), v_bytes = (size_t)M * nn * sizeof(double2);
-    DevBuf d_H00, d_H01, d_V, d_z, d_res, d_ws, d_stack;
-    TBK_CHECK(d_H00.reserve(h_bytes));
-    TBK_CHECK(d_H01.reserve(h_bytes));
-    TBK_CHECK(d_V.reserve(v_bytes));
-    TBK_CHECK(d_z.reserve((size_t)n_z * sizeof(double2)));
-    TBK_CHECK(d_res.reserve(sh.result_bytes(chunk) + sizeof(unsigned long long)));
-    TBK_CHECK(d_stack.reserve(devg_stack_bytes(sh, chunk * n_z, n_cu, slots)));
-    const size_t ws_bytes = devg_workspace_bytes(sh, chunk * n_z, n_cu, slots);
-    if (ws_bytes > 0) TBK_CHECK(d_ws.reserve(ws_bytes));
-    TBK_HIP(hipMemcpy(d_z.ptr, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice));
-    TBK_HIP(hipMemcpy(d_V.ptr, V, v_bytes, hipMemcpyHostToDevice));
-    unsigned long long word = SURF_NO_FLAG;
-    for (int64_t c0 = 0; c0 < n_k; c0 += chunk) {
-        const int64_t nkc = std::min(chunk, n_k - c0);
-        char* res = d_res.as<char>();
-        TBK_HIP(hipMemcpy(d_H00.ptr, H00 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
-        TBK_HIP(hipMemcpy(d_H01.ptr, H01 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
-        TBK_HIP(hipMemset(res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long)));
-        TBK_CHECK(devg_launch(nullptr, n_cu, sh, d_H00.as<double2>(), d_H01.as<double2>(), d_V.as<double2>(), d_z.as<double2>(), nkc, max_iterations, c0,
-                              slots, d_ws.as<double>(), d_stack.as<double2>(), res));
-        unsigned long long chunk_word = SURF_NO_FLAG;
-        TBK_CHECK(devg_copy_out(nullptr, false, sh, res, nkc, c0, iterations, T, ldos, left, right, G, F, C, cur, &chunk_word));
-        word = std::min(word, chunk_word);
+    bool on_handle;
+    int64_t slots;
+    int32_t* iterations;
+    double *T, *ldos, *left, *right, *G, *F, *C;
+    const DevgCurrentOut* cur;
+    DevgFamily(bool on_handle_, int M, const double* V, int64_t n_z, int64_t slots_, int32_t* iterations_, double* T_, double* ldos_, double* left_,
+               double* right_, double* G_, double* F_, double* C_, const DevgCurrentOut* cur_)
+        : on_handle(on_handle_), slots(slots_), iterations(iterations_), T(T_), ldos(ldos_), left(left_), right(right_), G(G_), F(F_), C(C_), cur(cur_) {
+        family = needs = DEVG_FAMILY;
+        timed = cur != nullptr ? TIMED_DEVICE_CURRENT : TIMED_DEVICE_GREEN;
+        rows_clamp = SURF_LIB_MAX;  // N > 64 is devg_check's to report, whatever N
+        extra_what = "the workgroups' stacks";
+        h_V = V;
+        sh.m_layers = M;
+        sh.n_z = n_z;
+        sh.green = G != nullptr;
+        sh.current = cur != nullptr;
+        sh.bonds = cur != nullptr && cur->inter_l != nullptr;
     }
-    return surf_status_error(word, z, max_iterations, cur != nullptr ? DEVC_SINGULAR : DEVG_SINGULAR);
-}
-
-// The whole call on one handle; k_base as in tbk_surface_green_slab.  A handle with TBK_EIG_ROCSOLVER takes the own kernel too: there
-// is no library route.  cur NULL: tbk_device_green, timed on TIMED_DEVICE_GREEN; else tbk_device_current on TIMED_DEVICE_CURRENT.
-int devg_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M_device, const double* V, int64_t n_z, const double* z,
-              int max_iterations, int32_t* iterations, double* T, double* ldos, double* left, double* right, double* G, double* F, double* C,
-              const DevgCurrentOut* cur) {
-    TBK_ARG(m != nullptr, "model is NULL");
-    TBK_LOCK(m);
-    TBK_ARG(!m->kdotp, "the device Green's function needs a tight-binding model");
-    const int dim = m->dim, n_orb = m->n_orb;
-    TBK_ARG(axis >= 0 && axis < dim, "axis must be 0 ... dim - 1");
-    TBK_ARG(layers >= 1 && layers <= 1024, "layers must be 1 ... 1024: the device Green's function needs hopping along the axis");
-    const int L = layers, S = 2 * L + 1;
-    for (size_t r = 0; r < m->h_R.size() / (size_t)dim; ++r) {
-        const int64_t reach = std::abs((int64_t)m->h_R[r * dim + axis]);
-        if (reach > L) {
-            tbk_set_error("invalid argument: layers = %d, but a stored hopping vector reaches %lld cells along axis %d", L, (long long)reach, axis);
-            return TBK_ERR_ARGUMENT;
+    int check(int N) override {
+        sh.n = N;
+        const double* V = static_cast<const double*>(h_V);
+        if (!on_handle) TBK_CHECK(trans_check_device(N, sh.m_layers, V, iterations, T));
+        TBK_CHECK(devg_check(N, on_handle ? std::max(sh.m_layers, 1) : sh.m_layers, ldos, left, right, G, F, C));
+        if (cur != nullptr) TBK_CHECK(devg_check_current(*cur));
+        if (on_handle) TBK_CHECK(trans_check_device(N, sh.m_layers, V, iterations, T));
+        v_bytes = (size_t)sh.m_layers * N * N * sizeof(double2);
+        return TBK_OK;
+    }
+    int check_options() const override {
+        TBK_ARG(slots >= 0, "slots < 0");
+        return TBK_OK;
+    }
+    size_t result_bytes(int64_t nk) const override { return sh.result_bytes(nk); }
+    int64_t auto_chunk(int64_t nk) const override { return sh.auto_chunk(nk); }
+    bool library(int) const override { return false; }
+    size_t workspace_bytes(bool, int64_t chunk, int n_cu) const override { return devg_workspace_bytes(sh, chunk * sh.n_z, n_cu, slots); }
+    size_t extra_bytes(int64_t chunk, int n_cu) const override { return devg_stack_bytes(sh, chunk * sh.n_z, n_cu, slots); }
+    int run_chunk(bool, const LayeredChunk& c) const override {
+        return devg_launch(c.s, c.n_cu, sh, c.d_H00, c.d_H01, static_cast<const double2*>(c.d_V), c.d_z, c.nkc, c.max_it, c.k0, slots,
+                           reinterpret_cast<double*>(c.d_ws), reinterpret_cast<double2*>(c.d_extra), c.d_res);
+    }
+    int copy_out(const LayeredCopy& copy, const char* d_res, int64_t nkc, int64_t c0) const override {
+        const size_t items = (size_t)nkc * sh.n_z, first = (size_t)c0 * sh.n_z;
+        const size_t rows = (size_t)sh.m_layers * sh.n, mats = rows * sh.n * 2;
+        const char* at = d_res;
+        TBK_HIP(copy(T + first, at, items * sizeof(double)));
+        at += sh.t_bytes(nkc);
+        TBK_HIP(copy(iterations + first, at, items * sizeof(int32_t)));
+        at += sh.it_bytes(nkc);
+        double* row_out[3] = {ldos, left, right};
+        for (int i = 0; i < 3; ++i, at += sh.row_bytes(nkc)) TBK_HIP(copy(row_out[i] + first * rows, at, items * rows * sizeof(double)));
+        double* mat_out[3] = {G, F, C};
+        if (sh.green)
+            for (int i = 0; i < 3; ++i, at += sh.mat_bytes(nkc)) TBK_HIP(copy(mat_out[i] + first * mats, at, items * mats * sizeof(double)));
+        if (sh.current) {
+            const size_t krows = (size_t)(sh.m_layers - 1) * sh.n, kmats = krows * sh.n, jmats = rows * sh.n;
+            double* cur_out[2] = {cur->cur_l, cur->cur_r};
+            double* inter_out[2] = {cur->inter_l, cur->inter_r};
+            double* intra_out[2] = {cur->intra_l, cur->intra_r};
+            if (krows > 0)
+                for (int i = 0; i < 2; ++i) TBK_HIP(copy(cur_out[i] + first * krows, at + i * sh.cur_bytes(nkc), items * krows * sizeof(double)));
+            at += 2 * sh.cur_bytes(nkc);
+            if (sh.bonds) {
+                if (kmats > 0)
+                    for (int i = 0; i < 2; ++i) TBK_HIP(copy(inter_out[i] + first * kmats, at + i * sh.inter_bytes(nkc), items * kmats * sizeof(double)));
+                at += 2 * sh.inter_bytes(nkc);
+                for (int i = 0; i < 2; ++i, at += sh.intra_bytes(nkc)) TBK_HIP(copy(intra_out[i] + first * jmats, at, items * jmats * sizeof(double)));
+            }
         }
+        return TBK_OK;
     }
-    const int64_t N64 = (int64_t)n_orb * L;
-    TBK_CHECK(surf_check_energies((int)std::min<int64_t>(N64, SURF_LIB_MAX), n_z, z, max_iterations));
-    DevgShape sh;
-    sh.n = (int)std::min<int64_t>(N64, 1 << 20);
-    sh.m_layers = M_device;
-    sh.n_z = n_z;
-    sh.green = G != nullptr;
-    sh.current = cur != nullptr;
-    sh.bonds = cur != nullptr && cur->inter_l != nullptr;
-    const int N = sh.n;
-    TBK_CHECK(devg_check(N, std::max(M_device, 1), ldos, left, right, G, F, C));
-    if (cur != nullptr) TBK_CHECK(devg_check_current(*cur));
-    TBK_CHECK(trans_check_device(N, M_device, V, iterations, T));
-    TBK_ARG(nk >= 0 && nk < (int64_t(1) << 40), "nk < 0");
-    if (nk == 0) return TBK_OK;
-    TBK_ARG(k != nullptr || dim == 1, "k is NULL");
-    const size_t nn2 = (size_t)n_orb * n_orb * 2;  // doubles of one H(k)
-    const int64_t by_h = std::max<int64_t>(1, (int64_t)(SURF_CHUNK_BUDGET / ((size_t)S * nn2 * sizeof(double))));
-    const int64_t chunk = std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : std::min(sh.auto_chunk(nk), by_h));
-    // (the host buffers the enqueued copies read and write, in front of the streams: they wait before these go)
-    std::vector<double> h_k, h_tw;
-    std::vector<unsigned long long> words;
-    TBK_CHECK(surf_host_lists(dim, axis, L, k, nk, h_k, h_tw));
-    try {
-        words.assign((size_t)((nk + chunk - 1) / chunk), SURF_NO_FLAG);
-    } catch (...) {
-        tbk_set_error("cannot allocate the status words");
-        return TBK_ERR_MEMORY;
+    int status_error(unsigned long long word, const double* z, int max_iterations) const override {
+        return surf_status_error(word, z, max_iterations, cur != nullptr ? DEVC_SINGULAR : DEVG_SINGULAR);
     }
-    MeshStreams streams;
-    TBK_CHECK(streams.add(m));
-    SpanRecorder* ev = &streams.used.back().ev;
-    const size_t z_bytes = surf_align256((size_t)n_z * sizeof(double2)), tw_bytes = h_tw.size() * sizeof(double);
-    const size_t layer_bytes = surf_align256((size_t)chunk * N * N * sizeof(double2)), v_bytes = (size_t)M_device * N * N * sizeof(double2);
-    const size_t ws_bytes = devg_workspace_bytes(sh, chunk * n_z, m->n_cu, 0);
-    TBK_CHECK(mesh_reserve(m->ws_mesh_k, h_k.size() * sizeof(double), DEVG_FAMILY, "the k list with its samples along the stacking axis"));
-    TBK_CHECK(mesh_reserve(m->ws_dm_r, z_bytes + tw_bytes, DEVG_FAMILY, "the energies and the twiddles"));
-    TBK_CHECK(mesh_reserve(m->ws_dm_rho, sh.result_bytes(chunk) + sizeof(unsigned long long), DEVG_FAMILY, "the results of one chunk"));
-    TBK_CHECK(mesh_reserve(m->ws_dm_p, 2 * layer_bytes, DEVG_FAMILY, "the principal layers of one chunk"));
-    TBK_CHECK(mesh_reserve(m->ws_pdos_u, (size_t)chunk * S * nn2 * sizeof(double), DEVG_FAMILY, "H(k) of one chunk"));
-    TBK_CHECK(mesh_reserve(m->ws_mesh_io, v_bytes, DEVG_FAMILY, "the device potential"));
-    TBK_CHECK(mesh_reserve(m->ws_mesh_u, devg_stack_bytes(sh, chunk * n_z, m->n_cu, 0), DEVG_FAMILY, "the workgroups' stacks"));
-    if (ws_bytes > 0) TBK_CHECK(mesh_reserve(m->ws_mesh_work, ws_bytes, DEVG_FAMILY, "the workgroups' matrices"));
-    double* d_k = m->ws_mesh_k.as<double>();
-    char* d_zt = m->ws_dm_r.as<char>();
-    double* d_H = m->ws_pdos_u.as<double>();
-    double2* d_H00 = m->ws_dm_p.as<double2>();
-    double2* d_H01 = reinterpret_cast<double2*>(m->ws_dm_p.as<char>() + layer_bytes);
-    const double2* d_V = m->ws_mesh_io.as<double2>();
-    const double2* d_z = reinterpret_cast<const double2*>(d_zt);
-    char* d_res = m->ws_dm_rho.as<char>();
-    TBK_HIP(hipMemcpyAsync(d_k, h_k.data(), h_k.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
-    TBK_HIP(hipMemcpyAsync(d_zt, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice, m->stream));
-    TBK_HIP(hipMemcpyAsync(d_zt + z_bytes, h_tw.data(), tw_bytes, hipMemcpyHostToDevice, m->stream));
-    TBK_HIP(hipMemcpyAsync(m->ws_mesh_io.ptr, V, v_bytes, hipMemcpyHostToDevice, m->stream));  // once per call
-    for (int64_t c0 = 0, ci = 0; c0 < nk; c0 += chunk, ++ci) {
-        const int64_t nkc = std::min(chunk, nk - c0);
-        TBK_CHECK(surf_chunk_layers(m, ev, d_k + (size_t)c0 * S * dim, nkc, L, d_H, reinterpret_cast<const double*>(d_zt + z_bytes), d_H00, d_H01));
-        TBK_HIP(hipMemsetAsync(d_res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long), m->stream));
-        if (ev) ev->start(1);
-        TBK_CHECK(devg_launch(m->stream, m->n_cu, sh, d_H00, d_H01, d_V, d_z, nkc, max_iterations, k_base + c0, 0, m->ws_mesh_work.as<double>(),
-                              m->ws_mesh_u.as<double2>(), d_res));
-        if (ev) ev->stop();
-        if (ev) ev->start(2);
-        TBK_CHECK(devg_copy_out(m->stream, true, sh, d_res, nkc, c0, iterations, T, ldos, left, right, G, F, C, cur, &words[(size_t)ci]));
-        if (ev) ev->stop();
-    }
-    TBK_CHECK(streams.finish(cur != nullptr ? TIMED_DEVICE_CURRENT : TIMED_DEVICE_GREEN));
-    unsigned long long word = SURF_NO_FLAG;
-    for (unsigned long long w : words) word = std::min(word, w);
-    return surf_status_error(word, z, max_iterations, cur != nullptr ? DEVC_SINGULAR : DEVG_SINGULAR);
-}
+};
 
 }  // namespace
 
 extern "C" int tbk_device_green_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, const double* V, int64_t n_z,
                                               const double* z, int max_iterations, int64_t k_chunk, int64_t slots, int32_t* iterations, double* T,
                                               double* ldos, double* left, double* right, double* G, double* F, double* C) {
-    return devg_from_matrices(device, N, n_k, H00, H01, M, V, n_z, z, max_iterations, k_chunk, slots, iterations, T, ldos, left, right, G, F, C, nullptr);
+    DevgFamily fam(false, M, V, n_z, slots, iterations, T, ldos, left, right, G, F, C, nullptr);
+    return layered_from_matrices(fam, device, N, n_k, H00, H01, n_z, z, max_iterations, k_chunk);
 }
 
 int tbk_device_green_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z,
                           const double* z, int max_iterations, int32_t* iterations, double* T, double* ldos, double* left, double* right, double* G,
                           double* F, double* C) {
-    return devg_slab(m, k_base, axis, layers, k, nk, M, V, n_z, z, max_iterations, iterations, T, ldos, left, right, G, F, C, nullptr);
+    DevgFamily fam(true, M, V, n_z, 0, iterations, T, ldos, left, right, G, F, C, nullptr);
+    return layered_slab(fam, m, k_base, axis, layers, k, nk, n_z, z, max_iterations);
 }
 
 extern "C" int tbk_device_green(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z, const double* z,
@@ -731,8 +629,8 @@ extern "C" int tbk_device_current_from_matrices(int device, int N, int64_t n_k, 
                                                 double* ldos, double* left, double* right, double* current_left, double* current_right,
                                                 double* inter_left, double* inter_right, double* intra_left, double* intra_right) {
     const DevgCurrentOut cur = {current_left, current_right, inter_left, inter_right, intra_left, intra_right};
-    return devg_from_matrices(device, N, n_k, H00, H01, M, V, n_z, z, max_iterations, k_chunk, slots, iterations, T, ldos, left, right, nullptr, nullptr,
-                              nullptr, &cur);
+    DevgFamily fam(false, M, V, n_z, slots, iterations, T, ldos, left, right, nullptr, nullptr, nullptr, &cur);
+    return layered_from_matrices(fam, device, N, n_k, H00, H01, n_z, z, max_iterations, k_chunk);
 }
 
 int tbk_device_current_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z,
@@ -740,7 +638,8 @@ int tbk_device_current_slab(tbk_model* m, int64_t k_base, int axis, int layers, 
                             double* current_left, double* current_right, double* inter_left, double* inter_right, double* intra_left,
                             double* intra_right) {
     const DevgCurrentOut cur = {current_left, current_right, inter_left, inter_right, intra_left, intra_right};
-    return devg_slab(m, k_base, axis, layers, k, nk, M, V, n_z, z, max_iterations, iterations, T, ldos, left, right, nullptr, nullptr, nullptr, &cur);
+    DevgFamily fam(true, M, V, n_z, 0, iterations, T, ldos, left, right, nullptr, nullptr, nullptr, &cur);
+    return layered_slab(fam, m, k_base, axis, layers, k, nk, n_z, z, max_iterations);
 }
 
 extern "C" int tbk_device_current(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z, const double* z,

@@ -1,10 +1,9 @@
 // tbk_ensemble.h -- what tbk_ensemble.hip (the transmission of an ensemble of devices) and tbk_channels.hip (its transmission
 // eigenvalues) share on the host: the sizes of a call, the arguments of a launch, the rule that splits the samples into groups, and
-// the two drivers -- the kernel alone on the caller's layers, and the whole call on one handle.  The drivers live in
-// tbk_ensemble.hip and take the kernel as an EnsRoute, so that the chunks, the staging, the status words and the groups exist once.
+// EnsFamily, which describes either kernel to the drivers of tbk_layered.h (its members live in tbk_ensemble.hip).
 #pragma once
 
-#include "tbk_surface.h"
+#include "tbk_layered.h"
 
 constexpr int64_t ENS_MAX_SAMPLES = 4096;  // samples per call (include/tbk.h); the status word gives the sample 12 bits
 
@@ -45,23 +44,39 @@ struct EnsLaunch {
     double* d_ch;  // [nkc][n_z][n_s][n] of a route with channels, else NULL
 };
 
-// A kernel of the family behind the drivers.  launch: the chunk's nkc points at every energy and sample on the own kernel.  The
-// status word of the kernel is (key * radix + reason), key = (point index * 4096 + energy index) * 4096 + sample: radix 2 with the
-// reasons 0 (a singular sweep) and 1 (the cap of the decimation), radix 4 with reason 2 (the cap of the channel iteration) besides.
+// A kernel of the family.  launch: the chunk's nkc points at every energy and sample on the own kernel.  The status word of the
+// kernel is (key * radix + reason), key = (point index * 4096 + energy index) * 4096 + sample: radix 2 with the reasons 0 (a singular
+// sweep) and 1 (the cap of the decimation), radix 4 with reason 2 (the cap of the channel iteration) besides.
 struct EnsRoute {
     int (*launch)(const EnsShape&, const EnsLaunch&);
     unsigned radix;
     bool channels;  // the route writes channels; it takes N <= 64 only and has no library route
-    int timed;      // the TimedFamily row of the whole call
+    TimedFamily timed;
     const char* family;
 };
 
-int tbk_ens_from_matrices(const EnsRoute& route, int device, int N, int64_t n_k, const double* H00, const double* H01, int M, int64_t n_s, const double* V,
-                          const double* onsite, int64_t n_z, const double* z, int max_iterations, int64_t k_chunk, int64_t sample_chunk,
-                          int32_t* iterations, double* T, double* channels);
-int tbk_ens_slab(const EnsRoute& route, tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M_device, int64_t n_s,
-                 const double* V, const double* onsite, int64_t n_z, const double* z, int max_iterations, int32_t* iterations, double* T,
-                 double* channels);
+// The ensemble's calls as a LayeredFamily: the samples staged once per call in either form, two status words per chunk (EnsShape).
+// sample_chunk: the option of *_from_matrices, 0 on a handle.
+struct EnsFamily : LayeredFamily {
+    const EnsRoute& route;
+    EnsShape sh;
+    const double *V, *onsite;
+    int64_t sample_chunk;
+    int32_t* iterations;
+    double *T, *channels;
+    EnsFamily(const EnsRoute& route, int M, int64_t n_s, const double* V, const double* onsite, int64_t n_z, int64_t sample_chunk, int32_t* iterations,
+              double* T, double* channels);
+    int check(int N) override;
+    int check_options() const override;
+    size_t result_bytes(int64_t nk) const override { return sh.result_bytes(nk); }
+    int64_t auto_chunk(int64_t nk) const override { return sh.auto_chunk(nk); }
+    bool library(int eigensolver) const override { return !route.channels && surf_takes_library(sh.n, eigensolver); }
+    size_t workspace_bytes(bool library, int64_t chunk, int n_cu) const override;
+    int run_chunk(bool library, const LayeredChunk& c) const override;
+    int copy_out(const LayeredCopy& copy, const char* d_res, int64_t nkc, int64_t c0) const override;
+    unsigned long long chunk_word(const unsigned long long* words) const override;
+    int status_error(unsigned long long word, const double* z, int max_iterations) const override;
+};
 
 namespace {
 

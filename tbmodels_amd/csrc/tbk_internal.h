@@ -348,12 +348,12 @@ struct tbk_model {
                          // per energy tile, ws_dm_rho G [n_r][n_z][n_orb][n_orb] and, behind it, the sum of one tile's slices; its k list is
                          // in ws_mesh_k, the eigenvectors of one chunk and their eigenvalues in ws_pdos_u.  tbk_green_dressed: behind the
                          // energies the self-energy [n_z][n_orb][n_orb] complex, ws_pdos_u the full H(k) of one chunk, ws_dm_p the inverses,
-                         // ws_mesh_work the library route's batch, pivots and status.  tbk_surface_green (tbk_surface.hip): ws_mesh_k the
-                         // k list with its samples along the stacking axis, ws_dm_r energies and twiddles, ws_pdos_u H(k) of one chunk,
-                         // ws_dm_p its principal layers, ws_dm_rho its results and status word, ws_mesh_work the workgroups' slots;
-                         // tbk_transmission the same, and ws_mesh_io the device potential V (tbk_transmission_ensemble, tbk_ensemble.hip:
-                         // the devices of all samples, in either form); tbk_device_green (tbk_device_green.hip) as
-                         // tbk_transmission, and ws_mesh_u the workgroups' stacks
+                         // ws_mesh_work the library route's batch, pivots and status.  The layered calls (layered_slab, tbk_layered.hip):
+                         // ws_mesh_k the k list with its samples along the stacking axis, ws_dm_r energies and twiddles, ws_pdos_u H(k)
+                         // of one chunk, ws_dm_p its principal layers, ws_dm_rho its results and status words, ws_mesh_work the
+                         // workgroups' slots or the library route's batch; with a device, ws_mesh_io its potential V
+                         // (tbk_transmission_ensemble, tbk_transmission_channels: the devices of all samples, in either form);
+                         // tbk_device_green and tbk_device_current: ws_mesh_u the workgroups' stacks
     DevBuf ws_green_flag;  // tbk_green_dressed: one 64-bit status word, all ones or the smallest (mesh index * 4096 + energy index) that was singular
     // The calls on the resident eigensystem of a whole mesh (tbk_resident.h; the susceptibilities of tbk_chi.hip, tbk_berry_flux of
     // tbk_berry.hip): k, E and U are ResidentMesh's, the other two each family lays out for itself

@@ -1,11 +1,14 @@
-// tbk_surface.h -- what the kernels and drivers of tbk_surface.hip (the decimation, the transmission), tbk_ensemble.hip (the
-// transmission of an ensemble of devices) and tbk_device_green.hip (the layer-resolved Green's functions of the device) share: the geometry of a workgroup's planes, the inversion, the products, the
-// iteration of the decimation, the layer body and the closing trace of the sweep, and the host helpers of the whole calls.  Everything
-// sits in an unnamed namespace: each translation unit has its own copy.
+// tbk_surface.h -- what the kernels and launchers of tbk_surface.hip (the decimation, the transmission), tbk_ensemble.hip and
+// tbk_channels.hip (the transmission of an ensemble of devices, its eigenvalues) and tbk_device_green.hip (the layer-resolved Green's
+// functions of the device) share: the geometry of a workgroup's planes, the inversion, the products, the iteration of the decimation,
+// the layer body and the closing trace of the sweep, the constants, and the small inline helpers of the launchers.  The device
+// templates sit in an unnamed namespace: each translation unit instantiates its own.  The host drivers of the whole calls, their
+// helpers and surface_layers_kernel exist once, in tbk_layered.hip (tbk_layered.h).
 #pragma once
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include <rocsolver/rocsolver.h>
@@ -736,143 +739,26 @@ __device__ __forceinline__ bool trans_closing(const SurfPlanes& P, int n, int ti
     return bad;
 }
 
-// Hs: [n_k][2 L + 1][n][n], the full H(k) at k_a = j / (2 L + 1); tw: [2 L + 1][2 L + 1][2] (cos, sin) of -2 pi ((m j) mod (2 L + 1)) /
-// (2 L + 1), row m + L.  One workgroup per in-plane point writes H00 and, L > 0, H01 [N][N], N = n max(L, 1): block (p, q) of H00 is
-// H_{q-p}, of H01 H_{L+q-p} for q <= p and zero above.  H_m = (sum_j tw[m][j] Hs[j]) / (2 L + 1), j ascending.
-__global__ void __launch_bounds__(256) surface_layers_kernel(const double2* __restrict__ Hs, const double* __restrict__ tw, int n, int L,
-                                                             double2* __restrict__ H00, double2* __restrict__ H01) {
-    const int M = 2 * L + 1, N = n * (L > 0 ? L : 1);
-    const double2* hs = Hs + (size_t)blockIdx.x * M * n * n;
-    double2* o0 = H00 + (size_t)blockIdx.x * N * N;
-    double2* o1 = L > 0 ? H01 + (size_t)blockIdx.x * N * N : nullptr;
-    for (int e = (int)threadIdx.x; e < N * N; e += 256) {
-        const int I = e / N, J = e - I * N;
-        const int p = I / n, i = I - p * n, q = J / n, j = J - q * n;
-        for (int part = 0; part < (L > 0 ? 2 : 1); ++part) {
-            const int m = part == 0 ? q - p : L + q - p;
-            double sr = 0.0, si = 0.0;
-            if (part == 0 || q <= p) {
-                for (int s = 0; s < M; ++s) {
-                    const double c = tw[((size_t)(m + L) * M + s) * 2], d = tw[((size_t)(m + L) * M + s) * 2 + 1];
-                    const double2 h = hs[((size_t)s * n + i) * n + j];
-                    sr += c * h.x - d * h.y;
-                    si += c * h.y + d * h.x;
-                }
-                sr /= (double)M;
-                si /= (double)M;
-            }
-            (part == 0 ? o0 : o1)[e] = make_double2(sr, si);
-        }
-    }
-}
+// ---- host: what the launchers share (the drivers and their helpers: tbk_layered.h) ---------------------------------------------------
+constexpr const char* TRANS_SINGULAR = "z - D of a device layer, or z - e of the decimation,";
+constexpr int TRANS_MAX_LAYERS = 4096;
+constexpr size_t TRANS_DEVICE_BUDGET = size_t(256) << 20;  // the device potential V [M][N][N] complex
+constexpr size_t SURF_LDS_DEFAULT = size_t(64) << 10;      // dynamic LDS a kernel may ask for without tbk_raise_lds_limit
 
-// ---- host ---------------------------------------------------------------------------------------------------------------------------
-int64_t surf_grid(int n, int64_t items, int n_cu) {
+inline int64_t surf_grid(int n, int64_t items, int n_cu) {
     if (n > 32) return std::min<int64_t>(items, std::max(1, n_cu));  // one resident workgroup per CU, each with a workspace slot
     return std::min<int64_t>(items, int64_t(1) << 30);
 }
 
-// what every call checks of its sizes, energies and cap
-int surf_check_energies(int N, int64_t n_z, const double* z, int max_iterations) {
-    TBK_ARG(N >= 1, "a principal layer has no rows");
-    if (N > SURF_LIB_MAX) {
-        tbk_set_error("invalid argument: a principal layer of %d rows: the decimation takes at most %d", N, SURF_LIB_MAX);
-        return TBK_ERR_ARGUMENT;
-    }
-    TBK_ARG(n_z >= 1 && n_z <= SURF_MAX_Z, "n_z must be 1 to 4096");
-    TBK_ARG(z != nullptr, "z is NULL");
-    for (int64_t i = 0; i < n_z; ++i) {
-        TBK_ARG(std::isfinite(z[2 * i]) && std::isfinite(z[2 * i + 1]), "an energy z is not finite");
-        TBK_ARG(z[2 * i + 1] != 0.0, "every z needs Im z != 0");
-    }
-    TBK_ARG(max_iterations >= 1 && max_iterations <= SURF_MAX_ITERATIONS, "max_iterations must be 1 to 4096");
-    return TBK_OK;
-}
+inline bool surf_takes_library(int n, int eigensolver) { return n > SURF_OWN_MAX || eigensolver == TBK_EIG_ROCSOLVER; }
 
-// the status word as an error: the first (point, energy) of the call that failed
-int surf_status_error(unsigned long long word, const double* z, int max_iterations, const char* what = "z - e of the decimation") {
-    if (word == SURF_NO_FLAG) return TBK_OK;
-    const int reason = (int)(word & 1ull);
-    const unsigned long long key = word >> 1;
-    const long long point = (long long)(key / (unsigned long long)SURF_MAX_Z), zi = (long long)(key % (unsigned long long)SURF_MAX_Z);
-    if (reason == 0) {
-        tbk_set_error("Singular matrix: %s at k index %lld and energy %lld (z = %.17g%+.17gj)", what, point, zi, z[2 * zi], z[2 * zi + 1]);
-        return TBK_ERR_SINGULAR;
-    }
-    tbk_set_error("the decimation did not converge in %d iterations at k index %lld and energy %lld (z = %.17g%+.17gj)", max_iterations, point, zi,
-                  z[2 * zi], z[2 * zi + 1]);
-    return TBK_ERR_NO_CONVERGENCE;
-}
-
-int surf_device_cus(int device) {
-    int n_cu = 0;
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 1) n_cu = 256;
-    return n_cu;
-}
-
-// The host lists of a whole call: per in-plane point the 2 L + 1 full k-points (k_a = j / (2 L + 1) inserted at `axis`), and the
-// twiddles of surface_layers_kernel.
-int surf_host_lists(int dim, int axis, int L, const double* k, int64_t nk, std::vector<double>& h_k, std::vector<double>& h_tw) {
-    const int M = 2 * L + 1;
-    try {
-        h_k.resize((size_t)nk * M * dim);
-        h_tw.resize((size_t)M * M * 2);
-    } catch (...) {
-        tbk_set_error("cannot allocate the k list");
-        return TBK_ERR_MEMORY;
-    }
-    for (int64_t i = 0; i < nk; ++i)
-        for (int j = 0; j < M; ++j) {
-            double* dst = &h_k[((size_t)i * M + j) * dim];
-            for (int d = 0, s = 0; d < dim; ++d) dst[d] = d == axis ? (double)j / (double)M : k[(size_t)i * (dim - 1) + s++];
-        }
-    const double two_pi = 6.283185307179586476925286766559;
-    for (int mm = -L; mm <= L; ++mm)
-        for (int j = 0; j < M; ++j) {
-            const int num = ((mm * j) % M + M) % M;
-            const double angle = -two_pi * (double)num / (double)M;
-            h_tw[((size_t)(mm + L) * M + j) * 2] = std::cos(angle);
-            h_tw[((size_t)(mm + L) * M + j) * 2 + 1] = std::sin(angle);
-        }
-    return TBK_OK;
-}
-
-// The chunk's principal layers: the FULL H(k) of its samples (d_k: the chunk's first), by the routine tbk_eigh_device uses, in pieces
-// of its own choice, then surface_layers_kernel.  Stage 0 of the call's timer.
-int surf_chunk_layers(tbk_model* m, SpanRecorder* ev, const double* d_k, int64_t nkc, int L, double* d_H, const double* d_tw, double2* d_H00,
-                      double2* d_H01) {
-    const int dim = m->dim, n_orb = m->n_orb, M = 2 * L + 1;
-    const size_t nn2 = (size_t)n_orb * n_orb * 2;
-    const int64_t npts = nkc * M;
-    if (ev) ev->start(0);
-    const int64_t piece = choose_chunk(m, npts, false);
-    for (int64_t p0 = 0; p0 < npts; p0 += piece) {
-        const int64_t np = std::min(piece, npts - p0);
-        const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), np, false);
-        TBK_CHECK(chunk_h(m, plan, HK_FULL, 2, d_k + (size_t)p0 * dim, nullptr, tbk_one_k_t(), d_H + (size_t)p0 * nn2));
-    }
-    hipLaunchKernelGGL(surface_layers_kernel, dim3((unsigned)nkc), dim3(256), 0, m->stream, reinterpret_cast<const double2*>(d_H), d_tw, n_orb, L, d_H00,
-                       d_H01);
-    TBK_HIP(hipGetLastError());
-    if (ev) ev->stop();
-    return TBK_OK;
-}
-
-// ---- the transmission: host ------------------------------------------------------------------------------------------------------------
-constexpr const char* TRANS_SINGULAR = "z - D of a device layer, or z - e of the decimation,";
-constexpr int TRANS_MAX_LAYERS = 4096;
-constexpr size_t TRANS_DEVICE_BUDGET = size_t(256) << 20;  // the device potential V [M][N][N] complex
-
-// what the two entry points check of the device; M N^2 complex numbers are staged once per call
-int trans_check_device(int N, int M, const double* V, const int32_t* iterations, const double* T) {
-    TBK_ARG(M >= 1 && M <= TRANS_MAX_LAYERS, "the device must have 1 to 4096 principal layers");
-    if ((size_t)M * N * N * sizeof(double2) > TRANS_DEVICE_BUDGET) {
-        tbk_set_error("invalid argument: a device of %d layers of %d rows: V may take at most 256 MiB", M, N);
-        return TBK_ERR_ARGUMENT;
-    }
-    TBK_ARG(V != nullptr, "V is NULL");
-    TBK_ARG(iterations != nullptr && T != nullptr, "iterations / T is NULL");
-    return TBK_OK;
+// The kernels' three sizes: f(std::integral_constant<int, NP>()) with the smallest NP that holds n rows.  Every *_launch_np<NP, ...>
+// behind it keeps the flag row of its kernel as a local static and raises the LDS limit where its lds_bytes pass SURF_LDS_DEFAULT.
+template <class F>
+inline int surf_with_np(int n, F&& f) {
+    if (n <= 16) return f(std::integral_constant<int, 16>());
+    if (n <= 32) return f(std::integral_constant<int, 32>());
+    return f(std::integral_constant<int, 64>());
 }
 
 }  // namespace

@@ -32,7 +32,7 @@
 //   trans_ens_lib_chunk      the same route for the ensemble of tbk_ensemble.hip: surf_lib_iterate once per
 //                            batch, the sweep (trans_lib_sweep, shared with trans_lib_chunk) once per sample.
 
-#include "tbk_surface.h"
+#include "tbk_layered.h"
 
 namespace {
 
@@ -128,8 +128,6 @@ __global__ void __launch_bounds__(SurfGeom<NP>::THREADS)
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-tbk_flag_row surf_lds_done_32, surf_lds_done_64;  // more than 64 KiB of dynamic LDS
-
 struct SurfShape {
     int n = 0;             // rows of a principal layer
     int64_t n_z = 0;
@@ -144,18 +142,14 @@ struct SurfShape {
     }
 };
 
-
-size_t surf_workspace_bytes(int n, int64_t items, int n_cu) {
-    return n > 32 ? (size_t)surf_grid(n, items, n_cu) * SurfGeom<64>::slot_doubles * sizeof(double) : 0;
-}
-
 template <int NP>
-int surf_launch_np(hipStream_t s, int n_cu, tbk_flag_row* done, const SurfShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_z,
-                   int64_t nkc, int max_it, unsigned long long key0, double* d_ws, char* d_res) {
+int surf_launch_np(hipStream_t s, int n_cu, const SurfShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_z, int64_t nkc, int max_it,
+                   unsigned long long key0, double* d_ws, char* d_res) {
     using Geo = SurfGeom<NP>;
+    static tbk_flag_row done;  // of this instantiation's kernel
     const int64_t items = nkc * sh.n_z;
-    if (done != nullptr)
-        TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(surface_decimate_kernel<NP>), (int)Geo::lds_bytes, *done));
+    if (Geo::lds_bytes > SURF_LDS_DEFAULT)
+        TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(surface_decimate_kernel<NP>), (int)Geo::lds_bytes, done));
     double* d_b = reinterpret_cast<double*>(d_res);
     double* d_t = reinterpret_cast<double*>(d_res + sh.out_bytes(nkc));
     double* d_m = reinterpret_cast<double*>(d_res + 2 * sh.out_bytes(nkc));
@@ -172,19 +166,8 @@ int surf_launch_np(hipStream_t s, int n_cu, tbk_flag_row* done, const SurfShape&
 int surf_launch(hipStream_t s, int n_cu, const SurfShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_z, int64_t nkc, int max_it,
                 int64_t k0, double* d_ws, char* d_res) {
     const unsigned long long key0 = (unsigned long long)k0 * (unsigned long long)SURF_MAX_Z;
-    if (sh.n <= 16) return surf_launch_np<16>(s, n_cu, nullptr, sh, d_H00, d_H01, d_z, nkc, max_it, key0, d_ws, d_res);
-    if (sh.n <= 32) return surf_launch_np<32>(s, n_cu, &surf_lds_done_32, sh, d_H00, d_H01, d_z, nkc, max_it, key0, d_ws, d_res);
-    return surf_launch_np<64>(s, n_cu, &surf_lds_done_64, sh, d_H00, d_H01, d_z, nkc, max_it, key0, d_ws, d_res);
+    return surf_with_np(sh.n, [&](auto np) { return surf_launch_np<decltype(np)::value>(s, n_cu, sh, d_H00, d_H01, d_z, nkc, max_it, key0, d_ws, d_res); });
 }
-
-
-int surf_check_common(int N, int64_t n_z, const double* z, int max_iterations, const int32_t* iterations, const double* bottom, const double* top,
-                      const double* bulk) {
-    TBK_CHECK(surf_check_energies(N, n_z, z, max_iterations));
-    TBK_ARG(iterations != nullptr && bottom != nullptr && top != nullptr && bulk != nullptr, "iterations / bottom / top / bulk is NULL");
-    return TBK_OK;
-}
-
 
 // ---- above 64 rows, and on request: the library route ---------------------------------------------------------------------------------
 // The (k, z) of a chunk in lockstep, in batches of a FIXED number of members (a function of N alone; the last batch is filled with
@@ -461,11 +444,8 @@ int surf_lib_chunk(hipStream_t s, const SurfLib& W, const SurfShape& sh, const d
     return TBK_OK;
 }
 
-bool surf_takes_library(int n, int eigensolver) { return n > SURF_OWN_MAX || eigensolver == TBK_EIG_ROCSOLVER; }
-
 // ---- the transmission: host ------------------------------------------------------------------------------------------------------------
 constexpr const char* TRANS_FAMILY = "the transmission";
-tbk_flag_row trans_lds_done_32, trans_lds_done_64;  // more than 64 KiB of dynamic LDS
 
 // The results of a chunk: T, iterations, P_M (green), and behind them the status word.
 struct TransShape {
@@ -483,17 +463,14 @@ struct TransShape {
     }
 };
 
-size_t trans_workspace_bytes(int n, int64_t items, int n_cu) {
-    return n > 32 ? (size_t)surf_grid(n, items, n_cu) * TransGeom<64>::slot_doubles * sizeof(double) : 0;
-}
-
 template <int NP>
-int trans_launch_np(hipStream_t s, int n_cu, tbk_flag_row* done, const TransShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_V,
-                    const double2* d_z, int64_t nkc, int max_it, unsigned long long key0, double* d_ws, char* d_res) {
+int trans_launch_np(hipStream_t s, int n_cu, const TransShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_V, const double2* d_z,
+                    int64_t nkc, int max_it, unsigned long long key0, double* d_ws, char* d_res) {
     using Geo = SurfGeom<NP>;
+    static tbk_flag_row done;  // of this instantiation's kernel
     const int64_t items = nkc * sh.n_z;
-    if (done != nullptr)
-        TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(transmission_kernel<NP>), (int)TransGeom<NP>::lds_bytes, *done));
+    if (TransGeom<NP>::lds_bytes > SURF_LDS_DEFAULT)
+        TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(transmission_kernel<NP>), (int)TransGeom<NP>::lds_bytes, done));
     double* d_T = reinterpret_cast<double*>(d_res);
     int32_t* d_it = reinterpret_cast<int32_t*>(d_res + sh.t_bytes(nkc));
     double2* d_G = sh.green ? reinterpret_cast<double2*>(d_res + sh.t_bytes(nkc) + sh.it_bytes(nkc)) : nullptr;
@@ -508,9 +485,7 @@ int trans_launch_np(hipStream_t s, int n_cu, tbk_flag_row* done, const TransShap
 int trans_launch(hipStream_t s, int n_cu, const TransShape& sh, const double2* d_H00, const double2* d_H01, const double2* d_V, const double2* d_z,
                  int64_t nkc, int max_it, int64_t k0, double* d_ws, char* d_res) {
     const unsigned long long key0 = (unsigned long long)k0 * (unsigned long long)SURF_MAX_Z;
-    if (sh.n <= 16) return trans_launch_np<16>(s, n_cu, nullptr, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, d_ws, d_res);
-    if (sh.n <= 32) return trans_launch_np<32>(s, n_cu, &trans_lds_done_32, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, d_ws, d_res);
-    return trans_launch_np<64>(s, n_cu, &trans_lds_done_64, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, d_ws, d_res);
+    return surf_with_np(sh.n, [&](auto np) { return trans_launch_np<decltype(np)::value>(s, n_cu, sh, d_H00, d_H01, d_V, d_z, nkc, max_it, key0, d_ws, d_res); });
 }
 
 // ---- the library route of the transmission: the lead part is surf_lib_iterate, the sweep M lockstep rounds without convergence logic --
@@ -706,6 +681,100 @@ int trans_ens_lib_chunk(hipStream_t s, const SurfLib& W, int m_layers, int64_t n
     return TBK_OK;
 }
 
+// ---- the two families of this file behind the drivers of tbk_layered.h -----------------------------------------------------------------
+// what the library route and the own kernel share of a family: the route's rule and the bytes of either workspace
+struct SurfLibFamily : LayeredFamily {
+    int rows = 0;
+    size_t slot_doubles = 0;  // of a workgroup's slot at NP = 64
+    int64_t n_z = 0;
+    bool library(int eigensolver) const override { return surf_takes_library(rows, eigensolver); }
+    size_t workspace_bytes(bool library, int64_t chunk, int n_cu) const override {
+        if (library) return SurfLib::bytes(rows, surf_lib_batch(rows));
+        return rows > 32 ? (size_t)surf_grid(rows, chunk * n_z, n_cu) * slot_doubles * sizeof(double) : 0;
+    }
+    SurfLib placed(const LayeredChunk& c) const {
+        SurfLib W;
+        W.place(c.d_ws, rows, surf_lib_batch(rows), c.blas);
+        return W;
+    }
+};
+
+struct SurfFamily : SurfLibFamily {
+    SurfShape sh;
+    int32_t* iterations;
+    double *bottom, *top, *bulk;
+    SurfFamily(int64_t n_z_, int spectral, int32_t* iterations_, double* bottom_, double* top_, double* bulk_)
+        : iterations(iterations_), bottom(bottom_), top(top_), bulk(bulk_) {
+        family = needs = SURF_FAMILY;
+        timed = TIMED_SURFACE;
+        min_layers = 0;
+        slot_doubles = SurfGeom<64>::slot_doubles;
+        sh.n_z = n_z = n_z_;
+        sh.spectral = spectral != 0;
+    }
+    int check(int N) override {
+        sh.n = rows = N;
+        TBK_ARG(iterations != nullptr && bottom != nullptr && top != nullptr && bulk != nullptr, "iterations / bottom / top / bulk is NULL");
+        return TBK_OK;
+    }
+    size_t result_bytes(int64_t nk) const override { return sh.result_bytes(nk); }
+    int64_t auto_chunk(int64_t nk) const override { return sh.auto_chunk(nk); }
+    int run_chunk(bool library, const LayeredChunk& c) const override {
+        if (library) return surf_lib_chunk(c.s, placed(c), sh, c.d_H00, c.d_H01, c.d_z, c.nkc, c.max_it, c.k0, c.d_res);
+        return surf_launch(c.s, c.n_cu, sh, c.d_H00, c.d_H01, c.d_z, c.nkc, c.max_it, c.k0, reinterpret_cast<double*>(c.d_ws), c.d_res);
+    }
+    int copy_out(const LayeredCopy& copy, const char* d_res, int64_t nkc, int64_t c0) const override {
+        const size_t items = (size_t)nkc * sh.n_z;
+        const size_t o = (size_t)c0 * sh.n_z * sh.item_doubles(), ob = items * sh.item_doubles() * sizeof(double);
+        TBK_HIP(copy(bottom + o, d_res, ob));
+        TBK_HIP(copy(top + o, d_res + sh.out_bytes(nkc), ob));
+        TBK_HIP(copy(bulk + o, d_res + 2 * sh.out_bytes(nkc), ob));
+        TBK_HIP(copy(iterations + (size_t)c0 * sh.n_z, d_res + 3 * sh.out_bytes(nkc), items * sizeof(int32_t)));
+        return TBK_OK;
+    }
+    int status_error(unsigned long long word, const double* z, int max_iterations) const override {
+        return surf_status_error(word, z, max_iterations);
+    }
+};
+
+struct TransFamily : SurfLibFamily {
+    TransShape sh;
+    int32_t* iterations;
+    double *T, *G;
+    TransFamily(int M, const double* V, int64_t n_z_, int32_t* iterations_, double* T_, double* G_) : iterations(iterations_), T(T_), G(G_) {
+        family = needs = TRANS_FAMILY;
+        timed = TIMED_TRANSMISSION;
+        slot_doubles = TransGeom<64>::slot_doubles;
+        h_V = V;
+        sh.m_layers = M;
+        sh.n_z = n_z = n_z_;
+        sh.green = G != nullptr;
+    }
+    int check(int N) override {
+        sh.n = rows = N;
+        TBK_CHECK(trans_check_device(N, sh.m_layers, static_cast<const double*>(h_V), iterations, T));
+        v_bytes = (size_t)sh.m_layers * N * N * sizeof(double2);
+        return TBK_OK;
+    }
+    size_t result_bytes(int64_t nk) const override { return sh.result_bytes(nk); }
+    int64_t auto_chunk(int64_t nk) const override { return sh.auto_chunk(nk); }
+    int run_chunk(bool library, const LayeredChunk& c) const override {
+        const double2* d_V = static_cast<const double2*>(c.d_V);
+        if (library) return trans_lib_chunk(c.s, placed(c), sh, c.d_H00, c.d_H01, d_V, c.d_z, c.nkc, c.max_it, c.k0, c.d_res);
+        return trans_launch(c.s, c.n_cu, sh, c.d_H00, c.d_H01, d_V, c.d_z, c.nkc, c.max_it, c.k0, reinterpret_cast<double*>(c.d_ws), c.d_res);
+    }
+    int copy_out(const LayeredCopy& copy, const char* d_res, int64_t nkc, int64_t c0) const override {
+        const size_t items = (size_t)nkc * sh.n_z, first = (size_t)c0 * sh.n_z, nn = (size_t)sh.n * sh.n;
+        TBK_HIP(copy(T + first, d_res, items * sizeof(double)));
+        TBK_HIP(copy(iterations + first, d_res + sh.t_bytes(nkc), items * sizeof(int32_t)));
+        if (sh.green) TBK_HIP(copy(G + first * nn * 2, d_res + sh.t_bytes(nkc) + sh.it_bytes(nkc), items * nn * sizeof(double2)));
+        return TBK_OK;
+    }
+    int status_error(unsigned long long word, const double* z, int max_iterations) const override {
+        return surf_status_error(word, z, max_iterations, TRANS_SINGULAR);
+    }
+};
+
 }  // namespace
 
 // tbk_ensemble.hip's doors to the library route: the bytes of its workspace, and a chunk on a workspace of that size
@@ -722,159 +791,15 @@ int tbk_trans_ens_lib_chunk(hipStream_t s, rocblas_handle blas, char* d_ws, int 
 
 extern "C" int tbk_transmission_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int M, const double* V, int64_t n_z,
                                               const double* z, int max_iterations, int64_t k_chunk, int32_t* iterations, double* T, double* G) {
-    TBK_CHECK(surf_check_energies(N, n_z, z, max_iterations));
-    TBK_ARG(H01 != nullptr, "H01 is NULL: the transmission needs hopping between the principal layers");
-    TBK_CHECK(trans_check_device(N, M, V, iterations, T));
-    TBK_ARG(n_k >= 1 && n_k < (int64_t(1) << 40), "n_k < 1");
-    TBK_ARG(H00 != nullptr, "H00 is NULL");
-    TBK_ARG(k_chunk >= 0, "k_chunk < 0");
-    TBK_CHECK(tetra_check_device(device));
-    TransShape sh;
-    sh.n = N;
-    sh.m_layers = M;
-    sh.n_z = n_z;
-    sh.green = G != nullptr;
-    const int64_t chunk = std::min<int64_t>(n_k, k_chunk > 0 ? k_chunk : sh.auto_chunk(n_k));
-    const int n_cu = surf_device_cus(device);
-    const size_t nn = (size_t)N * N, h_bytes = (size_t)chunk * nn * sizeof(double2), v_bytes = (size_t)M * nn * sizeof(double2);
-    DevBuf d_H00, d_H01, d_V, d_z, d_res, d_ws;
-    TBK_CHECK(d_H00.reserve(h_bytes));
-    TBK_CHECK(d_H01.reserve(h_bytes));
-    TBK_CHECK(d_V.reserve(v_bytes));
-    TBK_CHECK(d_z.reserve((size_t)n_z * sizeof(double2)));
-    TBK_CHECK(d_res.reserve(sh.result_bytes(chunk) + sizeof(unsigned long long)));
-    const bool library = surf_takes_library(N, TBK_EIG_AUTO);
-    const size_t ws_bytes = library ? SurfLib::bytes(N, surf_lib_batch(N)) : trans_workspace_bytes(N, chunk * n_z, n_cu);
-    if (ws_bytes > 0) TBK_CHECK(d_ws.reserve(ws_bytes));
-    Owned<rocblas_handle, rocblas_destroy_handle> blas;
-    SurfLib W;
-    if (library) {
-        TBK_ROCBLAS(rocblas_create_handle(blas.put()));
-        W.place(d_ws.as<char>(), N, surf_lib_batch(N), blas);
-    }
-    TBK_HIP(hipMemcpy(d_z.ptr, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice));
-    TBK_HIP(hipMemcpy(d_V.ptr, V, v_bytes, hipMemcpyHostToDevice));
-    unsigned long long word = SURF_NO_FLAG;
-    for (int64_t c0 = 0; c0 < n_k; c0 += chunk) {
-        const int64_t nkc = std::min(chunk, n_k - c0);
-        const size_t items = (size_t)nkc * n_z;
-        char* res = d_res.as<char>();
-        TBK_HIP(hipMemcpy(d_H00.ptr, H00 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
-        TBK_HIP(hipMemcpy(d_H01.ptr, H01 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
-        TBK_HIP(hipMemset(res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long)));
-        if (library)
-            TBK_CHECK(trans_lib_chunk(nullptr, W, sh, d_H00.as<double2>(), d_H01.as<double2>(), d_V.as<double2>(), d_z.as<double2>(), nkc, max_iterations, c0, res));
-        else
-            TBK_CHECK(trans_launch(nullptr, n_cu, sh, d_H00.as<double2>(), d_H01.as<double2>(), d_V.as<double2>(), d_z.as<double2>(), nkc, max_iterations, c0,
-                                   d_ws.as<double>(), res));
-        unsigned long long chunk_word = SURF_NO_FLAG;
-        TBK_HIP(hipMemcpy(T + (size_t)c0 * n_z, res, items * sizeof(double), hipMemcpyDeviceToHost));
-        TBK_HIP(hipMemcpy(iterations + (size_t)c0 * n_z, res + sh.t_bytes(nkc), items * sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (sh.green)
-            TBK_HIP(hipMemcpy(G + (size_t)c0 * n_z * nn * 2, res + sh.t_bytes(nkc) + sh.it_bytes(nkc), items * nn * sizeof(double2), hipMemcpyDeviceToHost));
-        TBK_HIP(hipMemcpy(&chunk_word, res + sh.result_bytes(nkc), sizeof(chunk_word), hipMemcpyDeviceToHost));
-        word = std::min(word, chunk_word);
-    }
-    return surf_status_error(word, z, max_iterations, TRANS_SINGULAR);
+    TransFamily fam(M, V, n_z, iterations, T, G);
+    return layered_from_matrices(fam, device, N, n_k, H00, H01, n_z, z, max_iterations, k_chunk);
 }
 
 // The whole call on one handle; k_base as in tbk_surface_green_slab.
 int tbk_transmission_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int M_device, const double* V, int64_t n_z,
                           const double* z, int max_iterations, int32_t* iterations, double* T, double* G) {
-    TBK_ARG(m != nullptr, "model is NULL");
-    TBK_LOCK(m);
-    TBK_ARG(!m->kdotp, "the transmission needs a tight-binding model");
-    const int dim = m->dim, n_orb = m->n_orb;
-    TBK_ARG(axis >= 0 && axis < dim, "axis must be 0 ... dim - 1");
-    TBK_ARG(layers >= 1 && layers <= 1024, "layers must be 1 ... 1024: the transmission needs hopping along the axis");
-    const int L = layers, M = 2 * L + 1;
-    for (size_t r = 0; r < m->h_R.size() / (size_t)dim; ++r) {
-        const int64_t reach = std::abs((int64_t)m->h_R[r * dim + axis]);
-        if (reach > L) {
-            tbk_set_error("invalid argument: layers = %d, but a stored hopping vector reaches %lld cells along axis %d", L, (long long)reach, axis);
-            return TBK_ERR_ARGUMENT;
-        }
-    }
-    const int64_t N64 = (int64_t)n_orb * L;
-    TBK_CHECK(surf_check_energies((int)std::min<int64_t>(N64, 1 << 20), n_z, z, max_iterations));
-    TransShape sh;
-    sh.n = (int)N64;
-    sh.m_layers = M_device;
-    sh.n_z = n_z;
-    sh.green = G != nullptr;
-    const int N = sh.n;
-    TBK_CHECK(trans_check_device(N, M_device, V, iterations, T));
-    TBK_ARG(nk >= 0 && nk < (int64_t(1) << 40), "nk < 0");
-    if (nk == 0) return TBK_OK;
-    TBK_ARG(k != nullptr || dim == 1, "k is NULL");
-    const size_t nn2 = (size_t)n_orb * n_orb * 2;  // doubles of one H(k)
-    const int64_t by_h = std::max<int64_t>(1, (int64_t)(SURF_CHUNK_BUDGET / ((size_t)M * nn2 * sizeof(double))));
-    const int64_t chunk = std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : std::min(sh.auto_chunk(nk), by_h));
-    // (the host buffers the enqueued copies read and write, in front of the streams: they wait before these go)
-    std::vector<double> h_k, h_tw;
-    std::vector<unsigned long long> words;
-    TBK_CHECK(surf_host_lists(dim, axis, L, k, nk, h_k, h_tw));
-    try {
-        words.assign((size_t)((nk + chunk - 1) / chunk), SURF_NO_FLAG);
-    } catch (...) {
-        tbk_set_error("cannot allocate the status words");
-        return TBK_ERR_MEMORY;
-    }
-    MeshStreams streams;
-    TBK_CHECK(streams.add(m));
-    SpanRecorder* ev = &streams.used.back().ev;
-    const size_t z_bytes = surf_align256((size_t)n_z * sizeof(double2)), tw_bytes = h_tw.size() * sizeof(double);
-    const size_t layer_bytes = surf_align256((size_t)chunk * N * N * sizeof(double2)), v_bytes = (size_t)M_device * N * N * sizeof(double2);
-    const bool library = surf_takes_library(N, m->eigensolver);
-    const size_t ws_bytes = library ? SurfLib::bytes(N, surf_lib_batch(N)) : trans_workspace_bytes(N, chunk * n_z, m->n_cu);
-    TBK_CHECK(mesh_reserve(m->ws_mesh_k, h_k.size() * sizeof(double), TRANS_FAMILY, "the k list with its samples along the stacking axis"));
-    TBK_CHECK(mesh_reserve(m->ws_dm_r, z_bytes + tw_bytes, TRANS_FAMILY, "the energies and the twiddles"));
-    TBK_CHECK(mesh_reserve(m->ws_dm_rho, sh.result_bytes(chunk) + sizeof(unsigned long long), TRANS_FAMILY, "the results of one chunk"));
-    TBK_CHECK(mesh_reserve(m->ws_dm_p, 2 * layer_bytes, TRANS_FAMILY, "the principal layers of one chunk"));
-    TBK_CHECK(mesh_reserve(m->ws_pdos_u, (size_t)chunk * M * nn2 * sizeof(double), TRANS_FAMILY, "H(k) of one chunk"));
-    TBK_CHECK(mesh_reserve(m->ws_mesh_io, v_bytes, TRANS_FAMILY, "the device potential"));
-    if (ws_bytes > 0) TBK_CHECK(mesh_reserve(m->ws_mesh_work, ws_bytes, TRANS_FAMILY, library ? "the library's batch" : "the workgroups' matrices"));
-    SurfLib W;
-    if (library) {
-        W.place(m->ws_mesh_work.as<char>(), N, surf_lib_batch(N), m->blas);
-        m->counters[TBK_CNT_LIBRARY_CALLS] += 1;
-    }
-    double* d_k = m->ws_mesh_k.as<double>();
-    char* d_zt = m->ws_dm_r.as<char>();
-    double* d_H = m->ws_pdos_u.as<double>();
-    double2* d_H00 = m->ws_dm_p.as<double2>();
-    double2* d_H01 = reinterpret_cast<double2*>(m->ws_dm_p.as<char>() + layer_bytes);
-    const double2* d_V = m->ws_mesh_io.as<double2>();
-    const double2* d_z = reinterpret_cast<const double2*>(d_zt);
-    char* d_res = m->ws_dm_rho.as<char>();
-    TBK_HIP(hipMemcpyAsync(d_k, h_k.data(), h_k.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
-    TBK_HIP(hipMemcpyAsync(d_zt, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice, m->stream));
-    TBK_HIP(hipMemcpyAsync(d_zt + z_bytes, h_tw.data(), tw_bytes, hipMemcpyHostToDevice, m->stream));
-    TBK_HIP(hipMemcpyAsync(m->ws_mesh_io.ptr, V, v_bytes, hipMemcpyHostToDevice, m->stream));  // once per call
-    for (int64_t c0 = 0, ci = 0; c0 < nk; c0 += chunk, ++ci) {
-        const int64_t nkc = std::min(chunk, nk - c0);
-        const size_t items = (size_t)nkc * n_z;
-        TBK_CHECK(surf_chunk_layers(m, ev, d_k + (size_t)c0 * M * dim, nkc, L, d_H, reinterpret_cast<const double*>(d_zt + z_bytes), d_H00, d_H01));
-        TBK_HIP(hipMemsetAsync(d_res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long), m->stream));
-        if (ev) ev->start(1);
-        if (library)
-            TBK_CHECK(trans_lib_chunk(m->stream, W, sh, d_H00, d_H01, d_V, d_z, nkc, max_iterations, k_base + c0, d_res));
-        else
-            TBK_CHECK(trans_launch(m->stream, m->n_cu, sh, d_H00, d_H01, d_V, d_z, nkc, max_iterations, k_base + c0, m->ws_mesh_work.as<double>(), d_res));
-        if (ev) ev->stop();
-        if (ev) ev->start(2);
-        TBK_HIP(hipMemcpyAsync(T + (size_t)c0 * n_z, d_res, items * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-        TBK_HIP(hipMemcpyAsync(iterations + (size_t)c0 * n_z, d_res + sh.t_bytes(nkc), items * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-        if (sh.green)
-            TBK_HIP(hipMemcpyAsync(G + (size_t)c0 * n_z * N * N * 2, d_res + sh.t_bytes(nkc) + sh.it_bytes(nkc), items * N * N * sizeof(double2),
-                                   hipMemcpyDeviceToHost, m->stream));
-        TBK_HIP(hipMemcpyAsync(&words[(size_t)ci], d_res + sh.result_bytes(nkc), sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
-        if (ev) ev->stop();
-    }
-    TBK_CHECK(streams.finish(TIMED_TRANSMISSION));
-    unsigned long long word = SURF_NO_FLAG;
-    for (unsigned long long w : words) word = std::min(word, w);
-    return surf_status_error(word, z, max_iterations, TRANS_SINGULAR);
+    TransFamily fam(M_device, V, n_z, iterations, T, G);
+    return layered_slab(fam, m, k_base, axis, layers, k, nk, n_z, z, max_iterations);
 }
 
 extern "C" int tbk_transmission(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int M, const double* V, int64_t n_z, const double* z,
@@ -890,152 +815,15 @@ extern "C" int tbk_transmission_timing(tbk_model* m, double* ms, int64_t* calls,
 extern "C" int tbk_surface_from_matrices(int device, int N, int64_t n_k, const double* H00, const double* H01, int64_t n_z, const double* z,
                                          int max_iterations, int64_t k_chunk, int spectral, int32_t* iterations, double* bottom, double* top,
                                          double* bulk) {
-    TBK_CHECK(surf_check_common(N, n_z, z, max_iterations, iterations, bottom, top, bulk));
-    TBK_ARG(n_k >= 1 && n_k < (int64_t(1) << 40), "n_k < 1");
-    TBK_ARG(H00 != nullptr, "H00 is NULL");
-    TBK_ARG(k_chunk >= 0, "k_chunk < 0");
-    TBK_CHECK(tetra_check_device(device));
-    SurfShape sh;
-    sh.n = N;
-    sh.n_z = n_z;
-    sh.spectral = spectral != 0;
-    const int64_t chunk = std::min<int64_t>(n_k, k_chunk > 0 ? k_chunk : sh.auto_chunk(n_k));
-    const int n_cu = surf_device_cus(device);
-    const size_t nn = (size_t)N * N, h_bytes = (size_t)chunk * nn * sizeof(double2);
-    DevBuf d_H00, d_H01, d_z, d_res, d_ws;
-    TBK_CHECK(d_H00.reserve(h_bytes));
-    if (H01 != nullptr) TBK_CHECK(d_H01.reserve(h_bytes));
-    TBK_CHECK(d_z.reserve((size_t)n_z * sizeof(double2)));
-    TBK_CHECK(d_res.reserve(sh.result_bytes(chunk) + sizeof(unsigned long long)));
-    const bool library = surf_takes_library(N, TBK_EIG_AUTO);
-    const size_t ws_bytes = library ? SurfLib::bytes(N, surf_lib_batch(N)) : surf_workspace_bytes(N, chunk * n_z, n_cu);
-    if (ws_bytes > 0) TBK_CHECK(d_ws.reserve(ws_bytes));
-    Owned<rocblas_handle, rocblas_destroy_handle> blas;
-    SurfLib W;
-    if (library) {
-        TBK_ROCBLAS(rocblas_create_handle(blas.put()));
-        W.place(d_ws.as<char>(), N, surf_lib_batch(N), blas);
-    }
-    TBK_HIP(hipMemcpy(d_z.ptr, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice));
-    unsigned long long word = SURF_NO_FLAG;
-    for (int64_t c0 = 0; c0 < n_k; c0 += chunk) {
-        const int64_t nkc = std::min(chunk, n_k - c0);
-        const size_t items = (size_t)nkc * n_z;
-        char* res = d_res.as<char>();
-        TBK_HIP(hipMemcpy(d_H00.ptr, H00 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
-        if (H01 != nullptr) TBK_HIP(hipMemcpy(d_H01.ptr, H01 + (size_t)c0 * nn * 2, (size_t)nkc * nn * sizeof(double2), hipMemcpyHostToDevice));
-        TBK_HIP(hipMemset(res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long)));
-        const double2* h01 = H01 != nullptr ? d_H01.as<double2>() : nullptr;
-        if (library)
-            TBK_CHECK(surf_lib_chunk(nullptr, W, sh, d_H00.as<double2>(), h01, d_z.as<double2>(), nkc, max_iterations, c0, res));
-        else
-            TBK_CHECK(surf_launch(nullptr, n_cu, sh, d_H00.as<double2>(), h01, d_z.as<double2>(), nkc, max_iterations, c0, d_ws.as<double>(), res));
-        const size_t o = (size_t)c0 * n_z * sh.item_doubles(), ob = items * sh.item_doubles() * sizeof(double);
-        unsigned long long chunk_word = SURF_NO_FLAG;
-        TBK_HIP(hipMemcpy(bottom + o, res, ob, hipMemcpyDeviceToHost));
-        TBK_HIP(hipMemcpy(top + o, res + sh.out_bytes(nkc), ob, hipMemcpyDeviceToHost));
-        TBK_HIP(hipMemcpy(bulk + o, res + 2 * sh.out_bytes(nkc), ob, hipMemcpyDeviceToHost));
-        TBK_HIP(hipMemcpy(iterations + (size_t)c0 * n_z, res + 3 * sh.out_bytes(nkc), items * sizeof(int32_t), hipMemcpyDeviceToHost));
-        TBK_HIP(hipMemcpy(&chunk_word, res + sh.result_bytes(nkc), sizeof(chunk_word), hipMemcpyDeviceToHost));
-        word = std::min(word, chunk_word);
-    }
-    return surf_status_error(word, z, max_iterations);
+    SurfFamily fam(n_z, spectral, iterations, bottom, top, bulk);
+    return layered_from_matrices(fam, device, N, n_k, H00, H01, n_z, z, max_iterations, k_chunk);
 }
 
 // The whole call on one handle; k_base: the index of k[0] in the caller's list (the slabs of tbk_surface_green_multi), for the messages.
 int tbk_surface_green_slab(tbk_model* m, int64_t k_base, int axis, int layers, const double* k, int64_t nk, int64_t n_z, const double* z,
                            int max_iterations, int spectral, int32_t* iterations, double* bottom, double* top, double* bulk) {
-    TBK_ARG(m != nullptr, "model is NULL");
-    TBK_LOCK(m);
-    TBK_ARG(!m->kdotp, "the surface Green's function needs a tight-binding model");
-    const int dim = m->dim, n_orb = m->n_orb;
-    TBK_ARG(axis >= 0 && axis < dim, "axis must be 0 ... dim - 1");
-    TBK_ARG(layers >= 0 && layers <= 1024, "layers must be 0 ... 1024");
-    const int L = layers, M = 2 * L + 1;
-    for (size_t r = 0; r < m->h_R.size() / (size_t)dim; ++r) {
-        const int64_t reach = std::abs((int64_t)m->h_R[r * dim + axis]);
-        if (reach > L) {
-            tbk_set_error("invalid argument: layers = %d, but a stored hopping vector reaches %lld cells along axis %d", L, (long long)reach, axis);
-            return TBK_ERR_ARGUMENT;
-        }
-    }
-    const int64_t N64 = (int64_t)n_orb * std::max(L, 1);
-    TBK_CHECK(surf_check_common((int)std::min<int64_t>(N64, 1 << 20), n_z, z, max_iterations, iterations, bottom, top, bulk));
-    TBK_ARG(nk >= 0 && nk < (int64_t(1) << 40), "nk < 0");
-    if (nk == 0) return TBK_OK;
-    TBK_ARG(k != nullptr || dim == 1, "k is NULL");
-    SurfShape sh;
-    sh.n = (int)N64;
-    sh.n_z = n_z;
-    sh.spectral = spectral != 0;
-    const int N = sh.n;
-    const size_t nn2 = (size_t)n_orb * n_orb * 2;  // doubles of one H(k)
-    // k-points per chunk: the option, else what keeps the chunk's results and its H(k) samples inside the budget
-    const int64_t by_h = std::max<int64_t>(1, (int64_t)(SURF_CHUNK_BUDGET / ((size_t)M * nn2 * sizeof(double))));
-    const int64_t chunk = std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : std::min(sh.auto_chunk(nk), by_h));
-    // (the host buffers the enqueued copies read and write, in front of the streams: they wait before these go)
-    std::vector<double> h_k, h_tw;
-    unsigned long long word = SURF_NO_FLAG;
-    TBK_CHECK(surf_host_lists(dim, axis, L, k, nk, h_k, h_tw));
-    std::vector<unsigned long long> words;
-    try {
-        words.assign((size_t)((nk + chunk - 1) / chunk), SURF_NO_FLAG);
-    } catch (...) {
-        tbk_set_error("cannot allocate the status words");
-        return TBK_ERR_MEMORY;
-    }
-    MeshStreams streams;
-    TBK_CHECK(streams.add(m));
-    SpanRecorder* ev = &streams.used.back().ev;
-    const size_t z_bytes = surf_align256((size_t)n_z * sizeof(double2)), tw_bytes = h_tw.size() * sizeof(double);
-    const size_t layer_bytes = surf_align256((size_t)chunk * N * N * sizeof(double2));
-    const bool library = surf_takes_library(N, m->eigensolver);
-    const size_t ws_bytes = library ? SurfLib::bytes(N, surf_lib_batch(N)) : surf_workspace_bytes(N, chunk * n_z, m->n_cu);
-    TBK_CHECK(mesh_reserve(m->ws_mesh_k, h_k.size() * sizeof(double), SURF_FAMILY, "the k list with its samples along the stacking axis"));
-    TBK_CHECK(mesh_reserve(m->ws_dm_r, z_bytes + tw_bytes, SURF_FAMILY, "the energies and the twiddles"));
-    TBK_CHECK(mesh_reserve(m->ws_dm_rho, sh.result_bytes(chunk) + sizeof(unsigned long long), SURF_FAMILY, "the results of one chunk"));
-    TBK_CHECK(mesh_reserve(m->ws_dm_p, 2 * layer_bytes, SURF_FAMILY, "the principal layers of one chunk"));
-    TBK_CHECK(mesh_reserve(m->ws_pdos_u, (size_t)chunk * M * nn2 * sizeof(double), SURF_FAMILY, "H(k) of one chunk"));
-    if (ws_bytes > 0) TBK_CHECK(mesh_reserve(m->ws_mesh_work, ws_bytes, SURF_FAMILY, library ? "the library's batch" : "the workgroups' matrices"));
-    SurfLib W;
-    if (library) {
-        W.place(m->ws_mesh_work.as<char>(), N, surf_lib_batch(N), m->blas);
-        m->counters[TBK_CNT_LIBRARY_CALLS] += 1;
-    }
-    double* d_k = m->ws_mesh_k.as<double>();
-    char* d_zt = m->ws_dm_r.as<char>();
-    double* d_H = m->ws_pdos_u.as<double>();
-    double2* d_H00 = m->ws_dm_p.as<double2>();
-    double2* d_H01 = L > 0 ? reinterpret_cast<double2*>(m->ws_dm_p.as<char>() + layer_bytes) : nullptr;
-    char* d_res = m->ws_dm_rho.as<char>();
-    TBK_HIP(hipMemcpyAsync(d_k, h_k.data(), h_k.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
-    TBK_HIP(hipMemcpyAsync(d_zt, z, (size_t)n_z * sizeof(double2), hipMemcpyHostToDevice, m->stream));
-    TBK_HIP(hipMemcpyAsync(d_zt + z_bytes, h_tw.data(), tw_bytes, hipMemcpyHostToDevice, m->stream));
-    for (int64_t c0 = 0, ci = 0; c0 < nk; c0 += chunk, ++ci) {
-        const int64_t nkc = std::min(chunk, nk - c0);
-        const size_t items = (size_t)nkc * n_z;
-        TBK_CHECK(surf_chunk_layers(m, ev, d_k + (size_t)c0 * M * dim, nkc, L, d_H, reinterpret_cast<const double*>(d_zt + z_bytes), d_H00, d_H01));
-        TBK_HIP(hipMemsetAsync(d_res + sh.result_bytes(nkc), 0xff, sizeof(unsigned long long), m->stream));
-        if (ev) ev->start(1);
-        if (library)
-            TBK_CHECK(surf_lib_chunk(m->stream, W, sh, d_H00, d_H01, reinterpret_cast<const double2*>(d_zt), nkc, max_iterations, k_base + c0, d_res));
-        else
-            TBK_CHECK(surf_launch(m->stream, m->n_cu, sh, d_H00, d_H01, reinterpret_cast<const double2*>(d_zt), nkc, max_iterations, k_base + c0,
-                                  m->ws_mesh_work.as<double>(), d_res));
-        if (ev) ev->stop();
-        if (ev) ev->start(2);
-        const size_t o = (size_t)c0 * n_z * sh.item_doubles(), ob = items * sh.item_doubles() * sizeof(double);
-        TBK_HIP(hipMemcpyAsync(bottom + o, d_res, ob, hipMemcpyDeviceToHost, m->stream));
-        TBK_HIP(hipMemcpyAsync(top + o, d_res + sh.out_bytes(nkc), ob, hipMemcpyDeviceToHost, m->stream));
-        TBK_HIP(hipMemcpyAsync(bulk + o, d_res + 2 * sh.out_bytes(nkc), ob, hipMemcpyDeviceToHost, m->stream));
-        TBK_HIP(hipMemcpyAsync(iterations + (size_t)c0 * n_z, d_res + 3 * sh.out_bytes(nkc), items * sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
-        TBK_HIP(hipMemcpyAsync(&words[(size_t)ci], d_res + sh.result_bytes(nkc), sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
-        if (ev) ev->stop();
-    }
-    // synchronises the handle and books the kernel times; then the status words, the smallest (point, energy) first
-    TBK_CHECK(streams.finish(TIMED_SURFACE));
-    for (unsigned long long w : words) word = std::min(word, w);
-    return surf_status_error(word, z, max_iterations);
+    SurfFamily fam(n_z, spectral, iterations, bottom, top, bulk);
+    return layered_slab(fam, m, k_base, axis, layers, k, nk, n_z, z, max_iterations);
 }
 
 extern "C" int tbk_surface_green(tbk_model* m, int axis, int layers, const double* k, int64_t nk, int64_t n_z, const double* z, int max_iterations,
