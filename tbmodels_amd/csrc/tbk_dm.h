@@ -2,7 +2,8 @@
 // real weights) and tbk_green.hip (the lattice Green's function, complex weights at a list of energies).  The mesh and the plan of
 // one slab, the checks and the reduction of the lattice vectors, and the launchers of the three kernels both use: the phase table,
 // the Fourier contraction and the sum of its k slices.  The kernels are in tbk_dm.hip (its head describes them and the table
-// coordinates); each caller brings its own projector kernel, which writes the P operand of the contraction.
+// coordinates); the host drivers that launch them are tbk_lattice.hip's, and each family brings its own projector kernel, which
+// writes the P operand of the contraction.
 #pragma once
 
 #include <vector>
@@ -42,8 +43,6 @@ struct DmPlan {
     }
 };
 
-// the slices: enough of them to fill the device with tiles, none shorter than 16 points, all partials inside the budget
-void dm_plan_slices(int64_t rows, int n_orb, int64_t n_r, int64_t* nr_pad, int64_t* slices, int64_t* kps);
 int dm_plan(int dim, const int32_t* mesh, int64_t nk_total, int64_t first_pt, int64_t rows, int n_orb, int64_t n_r, DmPlan* out);
 // R[n_r][dim] reduced to [0, n_d) per axis
 int dm_reduce_R(int dim, const int32_t* mesh, int64_t n_r, const int64_t* R, std::vector<int32_t>* out);

@@ -32,7 +32,7 @@
 //                      as in occ_contract_kernel -- one partial rho each, and dm_reduce_kernel adds them in index order.
 //
 // The plan, the launchers of dm_phase_kernel, dm_fourier_kernel and dm_reduce_kernel and the checks of R are declared in tbk_dm.h:
-// tbk_green.hip runs the same three kernels behind its own projector.
+// the host drivers of tbk_lattice.hip run these three kernels around a family's own projector, this file's or tbk_green.hip's.
 //
 // For given (w, U), R, chunk size and slab the bits of rho depend on nothing else.  Another chunk size regroups the k-points of the
 // groups at the chunk boundaries: results differ within the rounding bound of DESIGN 14.
@@ -42,14 +42,15 @@
 #include <cstring>
 #include <vector>
 
-#include "tbk_dm.h"
+#include "tbk_lattice.h"
 
 namespace {
 constexpr int64_t DM_TARGET_WAVES = 1024;  // Fourier tiles x slices the plan aims for (four waves on each of 256 CUs)
 constexpr int64_t DM_MIN_SLICE = 16;       // mesh points per slice, at least
 }  // namespace
 
-void dm_plan_slices(int64_t rows, int n_orb, int64_t n_r, int64_t* nr_pad, int64_t* slices, int64_t* kps) {
+// the slices: enough of them to fill the device with tiles, none shorter than 16 points, all partials inside the budget
+static void dm_plan_slices(int64_t rows, int n_orb, int64_t n_r, int64_t* nr_pad, int64_t* slices, int64_t* kps) {
     const int64_t n2 = (int64_t)n_orb * n_orb;
     *nr_pad = (n_r + 15) / 16 * 16;
     const int64_t tiles = *nr_pad / 16 * ((n2 + 15) / 16);
@@ -309,29 +310,6 @@ int dm_launch_fourier(hipStream_t s, const DmPlan& L, SpanRecorder* ev, int64_t 
     return TBK_OK;
 }
 
-namespace {
-
-// The slab's points [c0, c0 + nkc): d_U their eigenvectors, d_w_chunk their rows of w.  ev (may be NULL): stages 0, 1, 2
-int dm_launch_chunk(hipStream_t s, const DmPlan& L, SpanRecorder* ev, const int32_t* d_Rm, const double* d_U, const double* d_w_chunk, int64_t c0,
-                    int64_t nkc, double* d_tab, double2* d_P, double2* d_part) {
-    const int64_t pad = c0 & 3, ng = (pad + nkc + 3) / 4;
-    TBK_CHECK(dm_launch_phase(s, L, ev, d_Rm, c0, nkc, d_tab));
-    if (ev) ev->start(1);
-    if (L.n <= 16) {
-        hipLaunchKernelGGL(dm_project_kernel<1>, dim3((unsigned)ng, 1), dim3(DM_THREADS), 0, s, reinterpret_cast<const double2*>(d_U), d_w_chunk, L.n,
-                           pad, nkc, d_P);
-    } else {
-        const int nb = (L.n + 63) / 64;
-        hipLaunchKernelGGL(dm_project_kernel<4>, dim3((unsigned)(ng * 4), (unsigned)(nb * nb)), dim3(DM_THREADS), 0, s,
-                           reinterpret_cast<const double2*>(d_U), d_w_chunk, L.n, pad, nkc, d_P);
-    }
-    if (ev) ev->stop();
-    TBK_HIP(hipGetLastError());
-    return dm_launch_fourier(s, L, ev, c0, nkc, d_tab, d_P, d_part);
-}
-
-}  // namespace
-
 // the result of the slab in device memory: d_part itself with one slice, else the slices summed into d_rho
 int dm_launch_reduce(hipStream_t s, const DmPlan& L, SpanRecorder* ev, const double2* d_part, double2* d_rho, const double2** result) {
     *result = d_part;
@@ -359,6 +337,37 @@ extern "C" int tbk_dm_plan(int64_t rows, int n_orb, int64_t n_r, int64_t* out) {
     return TBK_OK;
 }
 
+namespace {
+
+// The density matrix as the drivers of tbk_lattice.h see it: one energy in one tile, P = U diag(w) U^H from the chunk's eigenvectors
+// and its rows of the point weights w, which the entry point makes for the whole slab first.
+struct DmFamily : LatticeFamily {
+    const double* d_w = nullptr;  // the slab's weights [rows][n]
+    DmFamily() : LatticeFamily(TIMED_DM) {}
+    // no budget for P beside the phase table's: the chunk is the option, else the automatic one
+    GreenPlan plan(const DmPlan& D, int64_t, int64_t k_chunk, int64_t auto_chunk) const override {
+        GreenPlan G;
+        G.D = D;
+        G.bt = D.n <= 16 ? 1 : 4;
+        G.gather = false;
+        G.chunk = dm_cap_chunk(D, k_chunk > 0 ? std::min(k_chunk, D.rows) : auto_chunk);
+        return G;
+    }
+    int share(int, bool) const override { return 2; }  // the chunk is halved for the P buffer
+    int fill_p(const LatticeChunk& c, int64_t) const override {
+        const int n = c.G.D.n;
+        const double2* U = reinterpret_cast<const double2*>(c.d_in);
+        const double* w = d_w + (size_t)c.c0 * n;
+        if (c.G.bt == 1)
+            hipLaunchKernelGGL(dm_project_kernel<1>, c.project_grid(), dim3(DM_THREADS), 0, c.s, U, w, n, c.pad, c.nkc, c.d_P);
+        else
+            hipLaunchKernelGGL(dm_project_kernel<4>, c.project_grid(), dim3(DM_THREADS), 0, c.s, U, w, n, c.pad, c.nkc, c.d_P);
+        return TBK_OK;
+    }
+};
+
+}  // namespace
+
 extern "C" int tbk_density_matrix_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U,
                                                    double energy, int64_t k_chunk, int64_t n_r, const int64_t* R, double* rho_out) {
     int64_t nk = 0;
@@ -369,37 +378,18 @@ extern "C" int tbk_density_matrix_from_eigensystem(int device, int dim, const in
     TBK_ARG(k_chunk >= 0, "k_chunk < 0");
     TBK_CHECK(dm_check_R(n_r, R, rho_out, n_orb));
     TBK_CHECK(tetra_check_device(device));
+    // the weights of the whole mesh from its eigenvalues, once; the driver walks the eigenvectors
     OccPlan L;
     TBK_CHECK(occ_plan(dim, mesh, mesh[0], mesh[0], 0, n_orb, &L));
-    DmPlan D;
-    TBK_CHECK(dm_plan(dim, mesh, nk, 0, nk, n_orb, n_r, &D));
-    std::vector<int32_t> h_Rm;
-    TBK_CHECK(dm_reduce_R(dim, mesh, n_r, R, &h_Rm));
-    const int64_t chunk = dm_cap_chunk(D, k_chunk == 0 ? nk : std::min(k_chunk, nk));
-    const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double), u_per_k = (size_t)n_orb * (size_t)n_orb * 2;
-    DevBuf d_E, d_w, d_U, d_Rm, d_tab, d_P, d_part, d_rho;
+    const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double);
+    DevBuf d_E, d_w;
     TBK_CHECK(d_E.reserve(e_bytes));
     TBK_CHECK(d_w.reserve(e_bytes));
-    TBK_CHECK(d_part.reserve(D.part_bytes()));
-    if (D.slices > 1) TBK_CHECK(d_rho.reserve(D.rho_bytes()));
-    TBK_CHECK(d_Rm.reserve(h_Rm.size() * sizeof(int32_t)));
-    TBK_CHECK(d_U.reserve((size_t)chunk * u_per_k * sizeof(double)));
-    TBK_CHECK(d_tab.reserve(D.tab_bytes(chunk)));
-    TBK_CHECK(d_P.reserve(D.p_bytes(chunk)));
     TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
-    TBK_HIP(hipMemcpy(d_Rm.ptr, h_Rm.data(), h_Rm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    TBK_HIP(hipMemset(d_part.ptr, 0, D.part_bytes()));
     TBK_CHECK(occ_launch_weights(nullptr, L, d_E.as<double>(), energy, (double)nk, d_w.as<double>()));
-    for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
-        const int64_t nkc = std::min(chunk, nk - c0);
-        TBK_HIP(hipMemcpy(d_U.ptr, U + (size_t)c0 * u_per_k, (size_t)nkc * u_per_k * sizeof(double), hipMemcpyHostToDevice));
-        TBK_CHECK(dm_launch_chunk(nullptr, D, nullptr, d_Rm.as<int32_t>(), d_U.as<double>(), d_w.as<double>() + (size_t)c0 * n_orb, c0, nkc,
-                                  d_tab.as<double>(), d_P.as<double2>(), d_part.as<double2>()));
-    }
-    const double2* d_result = nullptr;
-    TBK_CHECK(dm_launch_reduce(nullptr, D, nullptr, d_part.as<double2>(), d_rho.as<double2>(), &d_result));
-    TBK_HIP(hipMemcpy(rho_out, d_result, D.rho_bytes(), hipMemcpyDeviceToHost));
-    return TBK_OK;
+    DmFamily fam;
+    fam.d_w = d_w.as<double>();
+    return lattice_from_arrays(fam, dim, mesh, nk, n_orb, nullptr, U, k_chunk, 0, n_r, R, rho_out);
 }
 
 extern "C" int tbk_density_matrix_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, int64_t n_r,
@@ -412,64 +402,22 @@ extern "C" int tbk_density_matrix_multi(tbk_model* const* handles, int n_handles
         TBK_CHECK(tbk_fermi_check_electrons(value, handles[0]->n_orb));
     else
         TBK_ARG(std::isfinite(value), "the energy is not finite");
-    // (the buffers the enqueued copies read and write, in front of the staged call: its MeshStreams waits before they go)
-    std::vector<int32_t> h_Rm;
-    std::vector<std::vector<double>> partial;  // of the slabs behind the first
+    DmFamily fam;
+    LatticeCall call;  // (in front of the staged call, which holds the streams)
     OccStaged staged;
     TBK_CHECK(staged.make(handles, n_handles, mesh));
     TBK_CHECK(staged.find_mu(mesh, mode, value, mu_out));
     TBK_CHECK(staged.weights(mu_out[0], nullptr, false));  // (not one of this family's three stages: not timed)
-    const int n_orb = staged.n_orb, dim = staged.dim;
-    const size_t rho_doubles = (size_t)n_r * n_orb * n_orb * 2;
-    TBK_CHECK(dm_reduce_R(dim, mesh, n_r, R, &h_Rm));
-    partial.resize(staged.slabs.size());
+    TBK_CHECK(call.open(fam, staged, mesh, n_r, R, rho_out, staged.slabs.size()));
     for (size_t i = 0; i < staged.slabs.size(); ++i) {
         OccSlab& s = staged.slabs[i];
-        tbk_model* m = s.m;
-        TBK_HIP(hipSetDevice(m->device));
-        const int64_t nk = s.L.rows;
-        DmPlan D;
-        TBK_CHECK(dm_plan(dim, mesh, staged.nk_total, s.p_lo * staged.plane_pts, nk, n_orb, n_r, &D));
-        // rho and its partials first: the chunk is chosen from the memory they leave, and halved for the P buffer
-        TBK_CHECK(m->ws_dm_part.reserve(D.part_bytes()));
-        if (D.slices > 1) TBK_CHECK(m->ws_dm_rho.reserve(D.rho_bytes()));
-        TBK_CHECK(m->ws_dm_r.reserve(h_Rm.size() * sizeof(int32_t)));
-        const int64_t chunk = dm_cap_chunk(D, mesh_eigh_chunk(m, nk, 2));
-        const size_t u_doubles = (size_t)chunk * n_orb * n_orb * 2;
-        TBK_CHECK(m->ws_pdos_u.reserve((u_doubles + (size_t)chunk * n_orb) * sizeof(double)));
-        TBK_CHECK(m->ws_dm_tab.reserve(D.tab_bytes(chunk)));
-        TBK_CHECK(m->ws_dm_p.reserve(D.p_bytes(chunk)));
-        TBK_HIP(hipMemcpyAsync(m->ws_dm_r.ptr, h_Rm.data(), h_Rm.size() * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
-        TBK_HIP(hipMemsetAsync(m->ws_dm_part.ptr, 0, D.part_bytes(), m->stream));
-        double* d_U = m->ws_pdos_u.as<double>();
-        const double* d_w = m->ws_occ_w.as<double>();
-        const double* d_k_own = m->ws_k.as<double>() + (size_t)s.off0 * staged.plane_pts * dim;
-        for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
-            const int64_t nkc = std::min(chunk, nk - c0);
-            // (the chunk's eigenvalues are not used: the weights come from the eigenvalue path)
-            TBK_CHECK(tbk_eigh_device(m, d_k_own + c0 * dim, nkc, 2, nullptr, d_U + u_doubles, d_U));
-            TBK_CHECK(dm_launch_chunk(m->stream, D, s.ev, m->ws_dm_r.as<int32_t>(), d_U, d_w + (size_t)c0 * n_orb, c0, nkc,
-                                      m->ws_dm_tab.as<double>(), m->ws_dm_p.as<double2>(), m->ws_dm_part.as<double2>()));
-        }
-        const double2* d_result = nullptr;
-        TBK_CHECK(dm_launch_reduce(m->stream, D, s.ev, m->ws_dm_part.as<double2>(), m->ws_dm_rho.as<double2>(), &d_result));
-        double* h_dst = rho_out;
-        if (i > 0) {
-            try {
-                partial[i].resize(rho_doubles);
-            } catch (...) {
-                tbk_set_error("cannot allocate the per-handle results");
-                return TBK_ERR_MEMORY;
-            }
-            h_dst = partial[i].data();
-        }
-        TBK_HIP(hipMemcpyAsync(h_dst, d_result, D.rho_bytes(), hipMemcpyDeviceToHost, m->stream));
+        TBK_HIP(hipSetDevice(s.m->device));
+        fam.d_w = s.m->ws_occ_w.as<double>();
+        // (the slab's own k list is the eigenvalue path's, behind the neighbour plane)
+        const double* d_k_own = s.m->ws_k.as<double>() + (size_t)s.off0 * staged.plane_pts * staged.dim;
+        TBK_CHECK(lattice_slab(fam, staged, call, i, s.m, s.ev, d_k_own, s.L.rows, s.p_lo * staged.plane_pts));
     }
-    // synchronises every handle (the eigenvector flags are reported as by tbk_eigh) and books the kernel times
-    TBK_CHECK(staged.finish(TIMED_DM));
-    for (size_t i = 1; i < staged.slabs.size(); ++i)  // in handle order
-        for (size_t x = 0; x < rho_doubles; ++x) rho_out[x] += partial[i][x];
-    return TBK_OK;
+    return lattice_finish(fam, call, staged.streams);
 }
 
 extern "C" int tbk_density_matrix(tbk_model* m, const int32_t* mesh, int mode, double value, int64_t n_r, const int64_t* R, double* mu_out,

@@ -36,16 +36,12 @@
 
 #include <rocsolver/rocsolver.h>
 
-#include "tbk_dm.h"
+#include "tbk_lattice.h"
 
 namespace {
 
 typedef double green_d4 __attribute__((ext_vector_type(4)));
 
-constexpr int GREEN_ZT = 4;                              // energies per tile, at most: their accumulators are register-resident
-constexpr int64_t GREEN_MAX_Z = 4096;                    // energies per call (include/tbk.h)
-constexpr size_t GREEN_P_BUDGET = size_t(1) << 30;       // the projectors of one chunk and one tile
-constexpr const char* GREEN_FAMILY = "the Green's function";
 
 // BT tiles of 16 along each side of the workgroup's block of P: 4 (one k-point per workgroup, wave t owns tile row t) or 1 (n <= 16:
 // four k-points per workgroup, one per wave).  U, E: of the chunk; z: the tile's zt energies.  Table column j is chunk point j - pad.
@@ -173,7 +169,6 @@ __global__ void __launch_bounds__(DM_THREADS) green_project_kernel(const double2
 // A pivot of modulus 0 or a non-finite element of the result raises the handle's status word (the smallest (mesh point, energy)
 // key wins); no index depends on a value, so a singular input ends like any other.
 constexpr int INVERT_PITCH_PAD = 1;  // pitch NP + 1 doubles: 32 consecutive rows of one column lie on 32 different bank pairs
-constexpr unsigned long long GREEN_NO_FLAG = ~0ull;
 
 template <int NP>
 constexpr size_t invert_lds_bytes() {
@@ -407,41 +402,6 @@ __global__ void __launch_bounds__(256) green_scatter_kernel(const double2* __res
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-// One slab: the density matrix's plan for n^2 elements (its slices are the Green's function's, whatever the energies), the k
-// chunk, the energy tile and the tiles of the call.
-struct GreenPlan {
-    DmPlan D;
-    int64_t n_z = 0, zt = 1, tiles = 1, chunk = 1;
-    int bt = 4;  // the projector template
-    int64_t tile_count(int64_t t) const { return std::min(zt, n_z - t * zt); }
-    size_t part_stride() const { return D.with_elements(zt * D.n2).part_bytes(); }  // between the partials of two tiles
-    size_t p_bytes() const { return D.with_elements(zt * D.n2).p_bytes(chunk); }
-    size_t g_bytes() const { return (size_t)D.n_r * n_z * D.n2 * sizeof(double2); }
-    size_t sum_bytes() const { return D.slices > 1 ? D.with_elements(zt * D.n2).rho_bytes() : 0; }  // the sum of one tile's slices
-};
-
-// k_chunk > 0: the caller's chunk, and the tile is what keeps its projectors inside the budget; 0: the tile is z_tile (0:
-// GREEN_ZT) and the chunk min(auto_chunk, what the budget allows that tile).  The tile does not depend on auto_chunk.
-GreenPlan green_plan(const DmPlan& D, int64_t n_z, int64_t z_tile, int64_t k_chunk, int64_t auto_chunk) {
-    GreenPlan G;
-    G.D = D;
-    G.n_z = n_z;
-    G.bt = D.n <= 16 ? 1 : 4;
-    const int64_t want = std::min<int64_t>(n_z, z_tile > 0 ? std::min<int64_t>(z_tile, GREEN_ZT) : GREEN_ZT);
-    const size_t per_point = (size_t)D.n2 * sizeof(double2);  // of one energy
-    if (k_chunk > 0) {
-        G.chunk = dm_cap_chunk(D, std::min(k_chunk, D.rows));
-        const int64_t by_budget = (int64_t)(GREEN_P_BUDGET / (per_point * (size_t)(D.groups(G.chunk) * 4)));
-        G.zt = std::max<int64_t>(1, std::min(want, by_budget));
-    } else {
-        G.zt = want;
-        const int64_t by_budget = (int64_t)(GREEN_P_BUDGET / (per_point * (size_t)want)) - 8;
-        G.chunk = dm_cap_chunk(D, std::max<int64_t>(4, std::min(std::min(auto_chunk, D.rows), by_budget)));
-    }
-    G.tiles = (n_z + G.zt - 1) / G.zt;
-    return G;
-}
-
 int green_check_z(int64_t n_z, const double* z) {
     TBK_ARG(n_z >= 1 && n_z <= GREEN_MAX_Z, "n_z must be 1 to 4096");
     TBK_ARG(z != nullptr, "z is NULL");
@@ -452,75 +412,35 @@ int green_check_z(int64_t n_z, const double* z) {
     return TBK_OK;
 }
 
-// The slab's points [c0, c0 + nkc): d_U their eigenvectors, d_E their eigenvalues.  The phase table once, then per tile of energies
-// the projectors and their contraction into the tile's partials.  ev (may be NULL): stages 0, 1, 2
-int green_launch_chunk(hipStream_t s, const GreenPlan& G, SpanRecorder* ev, const int32_t* d_Rm, const double2* d_z, const double* d_U,
-                       const double* d_E, int64_t c0, int64_t nkc, double* d_tab, double2* d_P, char* d_part) {
-    const DmPlan& D = G.D;
-    const int64_t pad = c0 & 3, ng = (pad + nkc + 3) / 4;
-    TBK_CHECK(dm_launch_phase(s, D, ev, d_Rm, c0, nkc, d_tab));
-    for (int64_t t = 0; t < G.tiles; ++t) {
+// The Green's function as the drivers of tbk_lattice.h see it: per tile of energies the projectors from the chunk's eigensystem.
+struct GreenFamily : LatticeFamily {
+    GreenFamily(int64_t n_z_, const double* z_) : LatticeFamily(TIMED_GREEN, n_z_, z_) {
+        family = "the Green's function";
+        part_what = "the partial sums of every energy";
+        result_what = "G(R, z) of the call";
+        in_what = "the eigenvectors of one chunk";
+        p_what = "the projectors of one chunk and one energy tile";
+    }
+    int share(int zt, bool) const override { return 1 + zt; }  // the chunk's eigenvectors and the projectors of one tile
+    int fill_p(const LatticeChunk& c, int64_t t) const override {
+        const GreenPlan& G = c.G;
+        const DmPlan& D = G.D;
         const int zt = (int)G.tile_count(t);
-        if (ev) ev->start(1);
-        if (G.bt == 1) {
-            hipLaunchKernelGGL(green_project_kernel<1>, dim3((unsigned)ng, 1), dim3(DM_THREADS), 0, s, reinterpret_cast<const double2*>(d_U), d_E,
-                               d_z + t * G.zt, zt, (double)D.mesh.nk, D.n, pad, nkc, d_P);
-        } else {
-            const int nb = (D.n + 63) / 64;
-            hipLaunchKernelGGL(green_project_kernel<4>, dim3((unsigned)(ng * 4), (unsigned)(nb * nb)), dim3(DM_THREADS), 0, s,
-                               reinterpret_cast<const double2*>(d_U), d_E, d_z + t * G.zt, zt, (double)D.mesh.nk, D.n, pad, nkc, d_P);
-        }
-        if (ev) ev->stop();
-        TBK_HIP(hipGetLastError());
-        TBK_CHECK(dm_launch_fourier(s, D.with_elements(zt * D.n2), ev, c0, nkc, d_tab, d_P, reinterpret_cast<double2*>(d_part + (size_t)t * G.part_stride())));
-    }
-    return TBK_OK;
-}
-
-// every tile's slices summed (d_sum: the scratch of one tile) and its block of energies put into d_G [n_r][n_z][n^2]
-int green_launch_gather(hipStream_t s, const GreenPlan& G, SpanRecorder* ev, const char* d_part, double2* d_sum, double2* d_G) {
-    const DmPlan& D = G.D;
-    for (int64_t t = 0; t < G.tiles; ++t) {
-        const int64_t zt = G.tile_count(t);
-        const double2* d_result = nullptr;
-        TBK_CHECK(dm_launch_reduce(s, D.with_elements(zt * D.n2), ev, reinterpret_cast<const double2*>(d_part + (size_t)t * G.part_stride()), d_sum,
-                                   &d_result));
-        const size_t width = (size_t)zt * D.n2 * sizeof(double2);
-        TBK_HIP(hipMemcpy2DAsync(d_G + (size_t)t * G.zt * D.n2, (size_t)G.n_z * D.n2 * sizeof(double2), d_result, width, width, (size_t)D.n_r,
-                                 hipMemcpyDeviceToDevice, s));
-    }
-    return TBK_OK;
-}
-
-// the vectors and, 256-byte aligned behind them, the energies: one small buffer
-size_t green_z_offset(size_t rm_bytes) { return dos_align256(rm_bytes); }
-
-// ---- the dressed function on the host ---------------------------------------------------------------------------------------------
-constexpr const char* DYSON_FAMILY = "the dressed Green's function";
-constexpr int GREEN_INVERT_MAX = 64;  // orbitals the own inversion kernel takes; above it (or on request) the library's LU
-
-tbk_flag_row green_invert_lds_done;  // green_invert_kernel<64>: more than 64 KiB of dynamic LDS
-
-// what the inversions of one slab read and write beside the plan's buffers
-struct DressedWork {
-    const double2* d_z = nullptr;       // [n_z]
-    const double2* d_sigma = nullptr;   // [n_z][n][n]
-    unsigned long long* d_flag = nullptr;
-    rocblas_handle blas = nullptr;      // the library route (NULL: the own kernel)
-    double2* d_batch = nullptr;         // ... its matrices [chunk][zt][n][n],
-    int* d_ipiv = nullptr;              // pivots [chunk][zt][n]
-    int* d_info = nullptr;              // and status [2][chunk zt]
-    static size_t batch_bytes(const GreenPlan& G) { return dos_align256((size_t)G.chunk * G.zt * G.D.n2 * sizeof(double2)); }
-    static size_t ipiv_bytes(const GreenPlan& G) { return dos_align256((size_t)G.chunk * G.zt * G.D.n * sizeof(int)); }
-    static size_t library_bytes(const GreenPlan& G) { return batch_bytes(G) + ipiv_bytes(G) + (size_t)2 * G.chunk * G.zt * sizeof(int); }
-    void place(const GreenPlan& G, char* base) {
-        d_batch = reinterpret_cast<double2*>(base);
-        d_ipiv = reinterpret_cast<int*>(base + batch_bytes(G));
-        d_info = reinterpret_cast<int*>(base + batch_bytes(G) + ipiv_bytes(G));
+        const double2* U = reinterpret_cast<const double2*>(c.d_in);
+        if (G.bt == 1)
+            hipLaunchKernelGGL(green_project_kernel<1>, c.project_grid(), dim3(DM_THREADS), 0, c.s, U, c.d_E(), c.d_z + t * G.zt, zt, (double)D.mesh.nk, D.n,
+                               c.pad, c.nkc, c.d_P);
+        else
+            hipLaunchKernelGGL(green_project_kernel<4>, c.project_grid(), dim3(DM_THREADS), 0, c.s, U, c.d_E(), c.d_z + t * G.zt, zt, (double)D.mesh.nk, D.n,
+                               c.pad, c.nkc, c.d_P);
+        return TBK_OK;
     }
 };
 
-bool dressed_takes_library(int n_orb, int eigensolver) { return n_orb > GREEN_INVERT_MAX || eigensolver == TBK_EIG_ROCSOLVER; }
+// ---- the dressed function on the host ---------------------------------------------------------------------------------------------
+constexpr int GREEN_INVERT_MAX = 64;  // orbitals the own inversion kernel takes; above it (or on request) the library's LU
+
+tbk_flag_row green_invert_lds_done;  // green_invert_kernel<64>: more than 64 KiB of dynamic LDS
 
 int green_check_dressed(int64_t n_z, const double* z, int n_orb, const double* sigma) {
     TBK_ARG(n_z >= 1 && n_z <= GREEN_MAX_Z, "n_z must be 1 to 4096");
@@ -531,57 +451,15 @@ int green_check_dressed(int64_t n_z, const double* z, int n_orb, const double* s
     return TBK_OK;
 }
 
+// key0: (mesh index of chunk point 0) * GREEN_MAX_Z + index of the tile's first energy t0
 template <int NP>
-int green_launch_invert_np(hipStream_t s, const DmPlan& D, const DressedWork& W, const double2* d_H, int64_t t0, int zt, int64_t pad, int64_t nkc,
-                           int64_t n_col, unsigned long long key0, double2* d_P) {
+int green_launch_invert_np(const LatticeChunk& c, int64_t t0, int zt, int64_t n_col, unsigned long long key0) {
+    const DmPlan& D = c.G.D;
     constexpr size_t lds = invert_lds_bytes<NP>();
     if (lds > (size_t(64) << 10)) TBK_HIP(tbk_raise_lds_limit(reinterpret_cast<const void*>(green_invert_kernel<NP>), (int)lds, green_invert_lds_done));
     const int64_t per = NP == 16 ? 4 : 1, blocks = (n_col * zt + per - 1) / per;
-    hipLaunchKernelGGL(green_invert_kernel<NP>, dim3((unsigned)blocks), dim3(DM_THREADS), lds, s, d_H, W.d_z + t0, W.d_sigma + (size_t)t0 * D.n2, zt,
-                       (double)D.mesh.nk, D.n, pad, nkc, n_col, key0, d_P, W.d_flag);
-    return TBK_OK;
-}
-
-// The slab's points [c0, c0 + nkc): d_H their H(k), full.  green_launch_chunk with the inversions in the projectors' place
-int green_launch_dressed_chunk(hipStream_t s, const GreenPlan& G, SpanRecorder* ev, const int32_t* d_Rm, const DressedWork& W, const double* d_H,
-                               int64_t c0, int64_t nkc, double* d_tab, double2* d_P, char* d_part) {
-    const DmPlan& D = G.D;
-    const int64_t pad = c0 & 3, n_col = (pad + nkc + 3) / 4 * 4;
-    const double2* H = reinterpret_cast<const double2*>(d_H);
-    TBK_CHECK(dm_launch_phase(s, D, ev, d_Rm, c0, nkc, d_tab));
-    for (int64_t t = 0; t < G.tiles; ++t) {
-        const int zt = (int)G.tile_count(t);
-        const int64_t t0 = t * G.zt;
-        const unsigned long long key0 = (unsigned long long)(D.mesh.first + c0) * (unsigned long long)GREEN_MAX_Z + (unsigned long long)t0;
-        if (ev) ev->start(1);
-        if (W.blas != nullptr) {
-            const unsigned gx = (unsigned)std::min<int64_t>(64, (D.n2 + 255) / 256);
-            hipLaunchKernelGGL(green_form_kernel, dim3((unsigned)nkc, gx, (unsigned)zt), dim3(256), 0, s, H, W.d_z + t0, W.d_sigma + (size_t)t0 * D.n2, zt,
-                               D.n, W.d_batch);
-            TBK_HIP(hipGetLastError());
-            // (calls stay below 2^29 elements, as those of tbk_eigh)
-            const int64_t batch = nkc * zt, step = std::max<int64_t>(1, (int64_t(1) << 29) / D.n2);
-            for (int64_t b0 = 0; b0 < batch; b0 += step) {
-                const rocblas_int nb = (rocblas_int)std::min(step, batch - b0);
-                rocblas_double_complex* A = reinterpret_cast<rocblas_double_complex*>(W.d_batch + (size_t)b0 * D.n2);
-                TBK_ROCBLAS(rocsolver_zgetrf_strided_batched(W.blas, D.n, D.n, A, D.n, (rocblas_stride)D.n2, W.d_ipiv + b0 * D.n, (rocblas_stride)D.n,
-                                                             W.d_info + b0, nb));
-                TBK_ROCBLAS(rocsolver_zgetri_strided_batched(W.blas, D.n, A, D.n, (rocblas_stride)D.n2, W.d_ipiv + b0 * D.n, (rocblas_stride)D.n,
-                                                             W.d_info + batch + b0, nb));
-            }
-            hipLaunchKernelGGL(green_scatter_kernel, dim3((unsigned)n_col, gx, (unsigned)zt), dim3(256), 0, s, W.d_batch, W.d_info, zt, (double)D.mesh.nk,
-                               D.n, pad, nkc, key0, d_P, W.d_flag);
-        } else if (D.n <= 16) {
-            TBK_CHECK(green_launch_invert_np<16>(s, D, W, H, t0, zt, pad, nkc, n_col, key0, d_P));
-        } else if (D.n <= 32) {
-            TBK_CHECK(green_launch_invert_np<32>(s, D, W, H, t0, zt, pad, nkc, n_col, key0, d_P));
-        } else {
-            TBK_CHECK(green_launch_invert_np<64>(s, D, W, H, t0, zt, pad, nkc, n_col, key0, d_P));
-        }
-        if (ev) ev->stop();
-        TBK_HIP(hipGetLastError());
-        TBK_CHECK(dm_launch_fourier(s, D.with_elements(zt * D.n2), ev, c0, nkc, d_tab, d_P, reinterpret_cast<double2*>(d_part + (size_t)t * G.part_stride())));
-    }
+    hipLaunchKernelGGL(green_invert_kernel<NP>, dim3((unsigned)blocks), dim3(DM_THREADS), lds, c.s, reinterpret_cast<const double2*>(c.d_in), c.d_z + t0,
+                       c.d_sigma + (size_t)t0 * D.n2, zt, (double)D.mesh.nk, D.n, c.pad, c.nkc, n_col, key0, c.d_P, c.d_flag);
     return TBK_OK;
 }
 
@@ -605,6 +483,82 @@ int green_singular_error(int dim, const int32_t* mesh, unsigned long long key, c
     return TBK_ERR_SINGULAR;
 }
 
+// The dressed function: per tile of energies the inverses from the chunk's full H(k), by the own kernel or the library's LU, whose
+// batch [chunk][zt][n][n], pivots [chunk][zt][n] and status [2][chunk zt] are the route's workspace.
+struct DressedFamily : LatticeFamily {
+    DressedFamily(int64_t n_z_, const double* z_, const double* sigma_) : LatticeFamily(TIMED_DYSON, n_z_, z_, sigma_) {
+        family = "the dressed Green's function";
+        part_what = "the partial sums of every energy";
+        result_what = "G(R, z) of the call";
+        const_what = "the self-energy of every energy";
+        in_what = "H(k) of one chunk";
+        p_what = "the inverses of one chunk and one energy tile";
+        work_what = "the library's batch of one chunk and one energy tile";
+        needs_h = true;
+        has_status = true;
+    }
+    static size_t batch_bytes(const GreenPlan& G) { return dos_align256((size_t)G.chunk * G.zt * G.D.n2 * sizeof(double2)); }
+    static size_t ipiv_bytes(const GreenPlan& G) { return dos_align256((size_t)G.chunk * G.zt * G.D.n * sizeof(int)); }
+    // the chunk's H(k), the inverses of one tile and, on the library route, its batch
+    int share(int zt, bool library) const override { return (library ? 2 : 1) * zt + 1; }
+    bool library(int n_orb, int eigensolver) const override { return n_orb > GREEN_INVERT_MAX || eigensolver == TBK_EIG_ROCSOLVER; }
+    size_t work_bytes(const GreenPlan& G) const override { return batch_bytes(G) + ipiv_bytes(G) + (size_t)2 * G.chunk * G.zt * sizeof(int); }
+    int status_error(unsigned long long word) const override { return green_singular_error(dim, mesh, word, z); }
+    int fill_p(const LatticeChunk& c, int64_t t) const override {
+        const GreenPlan& G = c.G;
+        const DmPlan& D = G.D;
+        const int zt = (int)G.tile_count(t);
+        const int64_t t0 = t * G.zt, n_col = c.ng * 4;
+        const unsigned long long key0 = (unsigned long long)(D.mesh.first + c.c0) * (unsigned long long)GREEN_MAX_Z + (unsigned long long)t0;
+        if (c.blas != nullptr) {
+            double2* d_batch = reinterpret_cast<double2*>(c.d_work);
+            int* d_ipiv = reinterpret_cast<int*>(c.d_work + batch_bytes(G));
+            int* d_info = reinterpret_cast<int*>(c.d_work + batch_bytes(G) + ipiv_bytes(G));
+            const unsigned gx = (unsigned)std::min<int64_t>(64, (D.n2 + 255) / 256);
+            hipLaunchKernelGGL(green_form_kernel, dim3((unsigned)c.nkc, gx, (unsigned)zt), dim3(256), 0, c.s, reinterpret_cast<const double2*>(c.d_in),
+                               c.d_z + t0, c.d_sigma + (size_t)t0 * D.n2, zt, D.n, d_batch);
+            TBK_HIP(hipGetLastError());
+            // (calls stay below 2^29 elements, as those of tbk_eigh)
+            const int64_t batch = c.nkc * zt, step = std::max<int64_t>(1, (int64_t(1) << 29) / D.n2);
+            for (int64_t b0 = 0; b0 < batch; b0 += step) {
+                const rocblas_int nb = (rocblas_int)std::min(step, batch - b0);
+                rocblas_double_complex* A = reinterpret_cast<rocblas_double_complex*>(d_batch + (size_t)b0 * D.n2);
+                TBK_ROCBLAS(rocsolver_zgetrf_strided_batched(c.blas, D.n, D.n, A, D.n, (rocblas_stride)D.n2, d_ipiv + b0 * D.n, (rocblas_stride)D.n,
+                                                             d_info + b0, nb));
+                TBK_ROCBLAS(rocsolver_zgetri_strided_batched(c.blas, D.n, A, D.n, (rocblas_stride)D.n2, d_ipiv + b0 * D.n, (rocblas_stride)D.n,
+                                                             d_info + batch + b0, nb));
+            }
+            hipLaunchKernelGGL(green_scatter_kernel, dim3((unsigned)n_col, gx, (unsigned)zt), dim3(256), 0, c.s, d_batch, d_info, zt, (double)D.mesh.nk, D.n,
+                               c.pad, c.nkc, key0, c.d_P, c.d_flag);
+            return TBK_OK;
+        }
+        if (D.n <= 16) return green_launch_invert_np<16>(c, t0, zt, n_col, key0);
+        if (D.n <= 32) return green_launch_invert_np<32>(c, t0, zt, n_col, key0);
+        return green_launch_invert_np<64>(c, t0, zt, n_col, key0);
+    }
+};
+
+// The front of both calls on staged handles, behind their checks: the handles opened, per busy handle its slab's k list made and
+// uploaded (ws_mesh_k), the slab, and the end of the call.
+int green_on_handles(LatticeFamily& fam, tbk_model* const* handles, int n_handles, const int32_t* mesh, int64_t n_r, const int64_t* R, double* G_out) {
+    TetraHandles th;
+    TBK_CHECK(th.open(handles, n_handles, mesh, OCC_MESH));
+    LatticeCall call;  // (in front of the streams)
+    MeshStreams streams;
+    TBK_CHECK(call.open(fam, th, mesh, n_r, R, G_out, (size_t)th.cut.busy()));
+    for (int i = 0; i < th.cut.busy(); ++i) {  // handles whose slab is empty are skipped
+        tbk_model* m = handles[i];  // (locked by th)
+        std::vector<double>& h_k = call.h_k[(size_t)i];
+        TBK_CHECK(streams.add(m));
+        TBK_CHECK(tbk_dos_mesh_klist(th.dim, mesh, th.cut.lo(i), th.cut.count(i), &h_k));
+        TBK_CHECK(m->ws_mesh_k.reserve(h_k.size() * sizeof(double)));
+        TBK_HIP(hipMemcpyAsync(m->ws_mesh_k.ptr, h_k.data(), h_k.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
+        TBK_CHECK(lattice_slab(fam, th, call, (size_t)i, m, &streams.used.back().ev, m->ws_mesh_k.as<double>(), th.cut.count(i) * th.plane_pts,
+                               th.cut.lo(i) * th.plane_pts));
+    }
+    return lattice_finish(fam, call, streams);
+}
+
 }  // namespace
 
 extern "C" int tbk_green_dressed_from_matrices(int device, int dim, const int32_t* mesh, int n_orb, const double* H, int64_t k_chunk, int64_t z_tile,
@@ -617,52 +571,8 @@ extern "C" int tbk_green_dressed_from_matrices(int device, int dim, const int32_
     TBK_CHECK(green_check_dressed(n_z, z, n_orb, Sigma));
     TBK_CHECK(dm_check_R(n_r, R, G_out, n_orb));
     TBK_CHECK(tetra_check_device(device));
-    DmPlan D;
-    TBK_CHECK(dm_plan(dim, mesh, nk, 0, nk, n_orb, n_r, &D));
-    const GreenPlan G = green_plan(D, n_z, z_tile, k_chunk, nk);
-    std::vector<int32_t> h_Rm;
-    TBK_CHECK(dm_reduce_R(dim, mesh, n_r, R, &h_Rm));
-    const size_t rm_bytes = h_Rm.size() * sizeof(int32_t), z_bytes = (size_t)n_z * sizeof(double2), s_bytes = (size_t)n_z * D.n2 * sizeof(double2);
-    const size_t h_per_k = (size_t)D.n2 * 2;
-    DevBuf d_H, d_Rz, d_sigma, d_tab, d_P, d_part, d_G, d_flag, d_lib;
-    Owned<rocblas_handle, rocblas_destroy_handle> blas;
-    DressedWork W;
-    TBK_CHECK(d_part.reserve((size_t)G.tiles * G.part_stride()));
-    TBK_CHECK(d_G.reserve(dos_align256(G.g_bytes()) + G.sum_bytes()));
-    TBK_CHECK(d_Rz.reserve(green_z_offset(rm_bytes) + z_bytes));
-    TBK_CHECK(d_sigma.reserve(s_bytes));
-    TBK_CHECK(d_flag.reserve(sizeof(unsigned long long)));
-    TBK_CHECK(d_H.reserve((size_t)G.chunk * h_per_k * sizeof(double)));
-    TBK_CHECK(d_tab.reserve(D.tab_bytes(G.chunk)));
-    TBK_CHECK(d_P.reserve(G.p_bytes()));
-    if (dressed_takes_library(n_orb, TBK_EIG_AUTO)) {
-        TBK_CHECK(d_lib.reserve(DressedWork::library_bytes(G)));
-        TBK_ROCBLAS(rocblas_create_handle(blas.put()));
-        W.blas = blas;
-        W.place(G, d_lib.as<char>());
-    }
-    W.d_z = reinterpret_cast<const double2*>(d_Rz.as<char>() + green_z_offset(rm_bytes));
-    W.d_sigma = d_sigma.as<double2>();
-    W.d_flag = d_flag.as<unsigned long long>();
-    double2* d_sum = reinterpret_cast<double2*>(d_G.as<char>() + dos_align256(G.g_bytes()));
-    TBK_HIP(hipMemcpy(d_Rz.ptr, h_Rm.data(), rm_bytes, hipMemcpyHostToDevice));
-    TBK_HIP(hipMemcpy(d_Rz.as<char>() + green_z_offset(rm_bytes), z, z_bytes, hipMemcpyHostToDevice));
-    TBK_HIP(hipMemcpy(d_sigma.ptr, Sigma, s_bytes, hipMemcpyHostToDevice));
-    TBK_HIP(hipMemset(d_flag.ptr, 0xff, sizeof(unsigned long long)));
-    TBK_HIP(hipMemset(d_part.ptr, 0, (size_t)G.tiles * G.part_stride()));
-    for (int64_t c0 = 0; c0 < nk; c0 += G.chunk) {
-        const int64_t nkc = std::min(G.chunk, nk - c0);
-        TBK_HIP(hipMemcpy(d_H.ptr, H + (size_t)c0 * h_per_k, (size_t)nkc * h_per_k * sizeof(double), hipMemcpyHostToDevice));
-        TBK_CHECK(green_launch_dressed_chunk(nullptr, G, nullptr, d_Rz.as<int32_t>(), W, d_H.as<double>(), c0, nkc, d_tab.as<double>(), d_P.as<double2>(),
-                                             d_part.as<char>()));
-        // (the next chunk's upload overwrites d_H: the null stream orders it behind the kernels)
-    }
-    TBK_CHECK(green_launch_gather(nullptr, G, nullptr, d_part.as<char>(), d_sum, d_G.as<double2>()));
-    unsigned long long key = GREEN_NO_FLAG;
-    TBK_HIP(hipMemcpy(&key, d_flag.ptr, sizeof(key), hipMemcpyDeviceToHost));
-    TBK_CHECK(green_singular_error(dim, mesh, key, z));
-    TBK_HIP(hipMemcpy(G_out, d_G.ptr, G.g_bytes(), hipMemcpyDeviceToHost));
-    return TBK_OK;
+    DressedFamily fam(n_z, z, Sigma);
+    return lattice_from_arrays(fam, dim, mesh, nk, n_orb, nullptr, H, k_chunk, z_tile, n_r, R, G_out);
 }
 
 extern "C" int tbk_green_dressed_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int64_t n_z, const double* z, const double* Sigma,
@@ -670,99 +580,8 @@ extern "C" int tbk_green_dressed_multi(tbk_model* const* handles, int n_handles,
     TBK_ARG(handles != nullptr && n_handles >= 1 && handles[0] != nullptr, "no handles");
     TBK_CHECK(green_check_dressed(n_z, z, handles[0]->n_orb, Sigma));
     TBK_CHECK(dm_check_R(n_r, R, G_out, handles[0]->n_orb));
-    TetraHandles th;
-    TBK_CHECK(th.open(handles, n_handles, mesh, OCC_MESH));
-    const int dim = th.dim, n_orb = th.n_orb;
-    // (the host buffers the enqueued copies read and write, in front of the streams: they wait before these go)
-    std::vector<int32_t> h_Rm;
-    std::vector<std::vector<double>> h_k((size_t)th.cut.busy()), partial((size_t)th.cut.busy());  // the slabs' k lists; G of the slabs behind the first
-    std::vector<unsigned long long> h_flag((size_t)th.cut.busy(), GREEN_NO_FLAG);                 // the handles' status words
-    MeshStreams streams;
-    TBK_CHECK(dm_reduce_R(dim, mesh, n_r, R, &h_Rm));
-    const size_t rm_bytes = h_Rm.size() * sizeof(int32_t), z_bytes = (size_t)n_z * sizeof(double2);
-    const size_t s_off = dos_align256(green_z_offset(rm_bytes) + z_bytes), s_bytes = (size_t)n_z * n_orb * n_orb * sizeof(double2);
-    const size_t g_doubles = (size_t)n_r * n_z * n_orb * n_orb * 2;
-    for (int i = 0; i < th.cut.busy(); ++i) {  // handles whose slab is empty are skipped
-        tbk_model* m = handles[i];  // (locked by th: chunk_h below needs the lock)
-        const int64_t nk = th.cut.count(i) * th.plane_pts;
-        TBK_CHECK(streams.add(m));
-        SpanRecorder* ev = &streams.used.back().ev;
-        TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, th.cut.lo(i), th.cut.count(i), &h_k[(size_t)i]));
-        DmPlan D;
-        TBK_CHECK(dm_plan(dim, mesh, th.nk_total, th.cut.lo(i) * th.plane_pts, nk, n_orb, n_r, &D));
-        // G and its partials first: the chunk is chosen from the memory they leave, shared between the chunk's H(k), the inverses of
-        // one tile and, on the library route, its batch
-        const bool library = dressed_takes_library(n_orb, m->eigensolver);
-        GreenPlan G = green_plan(D, n_z, 0, m->k_chunk, nk);
-        const size_t part_bytes = (size_t)G.tiles * G.part_stride();
-        TBK_CHECK(mesh_reserve(m->ws_dm_part, part_bytes, DYSON_FAMILY, "the partial sums of every energy"));
-        TBK_CHECK(mesh_reserve(m->ws_dm_rho, dos_align256(G.g_bytes()) + G.sum_bytes(), DYSON_FAMILY, "G(R, z) of the call"));
-        TBK_CHECK(mesh_reserve(m->ws_dm_r, s_off + s_bytes, DYSON_FAMILY, "the self-energy of every energy"));
-        TBK_CHECK(m->ws_mesh_k.reserve(h_k[(size_t)i].size() * sizeof(double)));
-        TBK_CHECK(m->ws_green_flag.reserve(sizeof(unsigned long long)));
-        TBK_HIP(hipMemsetAsync(m->ws_green_flag.ptr, 0xff, sizeof(unsigned long long), m->stream));  // (a call that ended early may have left it raised)
-        G = green_plan(D, n_z, 0, m->k_chunk, mesh_eigh_chunk(m, nk, (library ? 2 : 1) * (int)G.zt + 1));
-        const int64_t chunk = G.chunk;
-        TBK_CHECK(mesh_reserve(m->ws_pdos_u, (size_t)chunk * n_orb * n_orb * sizeof(double2), DYSON_FAMILY, "H(k) of one chunk"));
-        TBK_CHECK(m->ws_dm_tab.reserve(D.tab_bytes(chunk)));
-        TBK_CHECK(mesh_reserve(m->ws_dm_p, G.p_bytes(), DYSON_FAMILY, "the inverses of one chunk and one energy tile"));
-        char* d_rz = m->ws_dm_r.as<char>();
-        DressedWork W;
-        W.d_z = reinterpret_cast<const double2*>(d_rz + green_z_offset(rm_bytes));
-        W.d_sigma = reinterpret_cast<const double2*>(d_rz + s_off);
-        W.d_flag = m->ws_green_flag.as<unsigned long long>();
-        if (library) {
-            TBK_CHECK(mesh_reserve(m->ws_mesh_work, DressedWork::library_bytes(G), DYSON_FAMILY, "the library's batch of one chunk and one energy tile"));
-            W.blas = m->blas;
-            W.place(G, m->ws_mesh_work.as<char>());
-            m->counters[TBK_CNT_LIBRARY_CALLS] += 1;
-        }
-        double* d_k = m->ws_mesh_k.as<double>();
-        TBK_HIP(hipMemcpyAsync(d_k, h_k[(size_t)i].data(), h_k[(size_t)i].size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
-        TBK_HIP(hipMemcpyAsync(d_rz, h_Rm.data(), rm_bytes, hipMemcpyHostToDevice, m->stream));
-        TBK_HIP(hipMemcpyAsync(d_rz + green_z_offset(rm_bytes), z, z_bytes, hipMemcpyHostToDevice, m->stream));
-        TBK_HIP(hipMemcpyAsync(d_rz + s_off, Sigma, s_bytes, hipMemcpyHostToDevice, m->stream));
-        TBK_HIP(hipMemsetAsync(m->ws_dm_part.ptr, 0, part_bytes, m->stream));
-        double* d_H = m->ws_pdos_u.as<double>();
-        const size_t nn2 = (size_t)n_orb * n_orb * 2;
-        for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
-            const int64_t nkc = std::min(chunk, nk - c0);
-            // the FULL H(k) of the chunk, by the routine tbk_eigh_device uses, in pieces of its own choice
-            const int64_t piece = choose_chunk(m, nkc, false);
-            for (int64_t p0 = 0; p0 < nkc; p0 += piece) {
-                const int64_t np = std::min(piece, nkc - p0);
-                const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), np, false);
-                TBK_CHECK(chunk_h(m, plan, HK_FULL, 2, d_k + (c0 + p0) * dim, nullptr, tbk_one_k_t(), d_H + (size_t)p0 * nn2));
-            }
-            TBK_CHECK(green_launch_dressed_chunk(m->stream, G, ev, reinterpret_cast<const int32_t*>(d_rz), W, d_H, c0, nkc, m->ws_dm_tab.as<double>(),
-                                                 m->ws_dm_p.as<double2>(), m->ws_dm_part.as<char>()));
-        }
-        double2* d_G = m->ws_dm_rho.as<double2>();
-        double2* d_sum = reinterpret_cast<double2*>(m->ws_dm_rho.as<char>() + dos_align256(G.g_bytes()));
-        TBK_CHECK(green_launch_gather(m->stream, G, ev, m->ws_dm_part.as<char>(), d_sum, d_G));
-        double* h_dst = G_out;
-        if (i > 0) {
-            try {
-                partial[(size_t)i].resize(g_doubles);
-            } catch (...) {
-                tbk_set_error("cannot allocate the per-handle results");
-                return TBK_ERR_MEMORY;
-            }
-            h_dst = partial[(size_t)i].data();
-        }
-        TBK_HIP(hipMemcpyAsync(h_dst, d_G, G.g_bytes(), hipMemcpyDeviceToHost, m->stream));
-        // the status word comes down with the result and is cleared for the next call
-        TBK_HIP(hipMemcpyAsync(&h_flag[(size_t)i], m->ws_green_flag.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
-        TBK_HIP(hipMemsetAsync(m->ws_green_flag.ptr, 0xff, sizeof(unsigned long long), m->stream));
-    }
-    // synchronises every handle and books the kernel times; then the status words, the smallest (mesh point, energy) first
-    TBK_CHECK(streams.finish(TIMED_DYSON));
-    unsigned long long key = GREEN_NO_FLAG;
-    for (unsigned long long word : h_flag) key = std::min(key, word);
-    TBK_CHECK(green_singular_error(dim, mesh, key, z));
-    for (size_t i = 1; i < partial.size(); ++i)  // in handle order
-        for (size_t x = 0; x < g_doubles; ++x) G_out[x] += partial[i][x];
-    return TBK_OK;
+    DressedFamily fam(n_z, z, Sigma);
+    return green_on_handles(fam, handles, n_handles, mesh, n_r, R, G_out);
 }
 
 extern "C" int tbk_green_dressed(tbk_model* m, const int32_t* mesh, int64_t n_z, const double* z, const double* Sigma, int64_t n_r, const int64_t* R,
@@ -803,36 +622,8 @@ extern "C" int tbk_green_from_eigensystem(int device, int dim, const int32_t* me
     TBK_CHECK(green_check_z(n_z, z));
     TBK_CHECK(dm_check_R(n_r, R, G_out, n_orb));
     TBK_CHECK(tetra_check_device(device));
-    DmPlan D;
-    TBK_CHECK(dm_plan(dim, mesh, nk, 0, nk, n_orb, n_r, &D));
-    const GreenPlan G = green_plan(D, n_z, z_tile, k_chunk, nk);
-    std::vector<int32_t> h_Rm;
-    TBK_CHECK(dm_reduce_R(dim, mesh, n_r, R, &h_Rm));
-    const size_t rm_bytes = h_Rm.size() * sizeof(int32_t), z_bytes = (size_t)n_z * sizeof(double2);
-    const size_t e_per_k = (size_t)n_orb, u_per_k = (size_t)n_orb * (size_t)n_orb * 2;
-    DevBuf d_E, d_U, d_Rz, d_tab, d_P, d_part, d_G;
-    TBK_CHECK(d_part.reserve((size_t)G.tiles * G.part_stride()));
-    TBK_CHECK(d_G.reserve(dos_align256(G.g_bytes()) + G.sum_bytes()));
-    TBK_CHECK(d_Rz.reserve(green_z_offset(rm_bytes) + z_bytes));
-    TBK_CHECK(d_E.reserve((size_t)G.chunk * e_per_k * sizeof(double)));
-    TBK_CHECK(d_U.reserve((size_t)G.chunk * u_per_k * sizeof(double)));
-    TBK_CHECK(d_tab.reserve(D.tab_bytes(G.chunk)));
-    TBK_CHECK(d_P.reserve(G.p_bytes()));
-    const double2* d_z = reinterpret_cast<const double2*>(d_Rz.as<char>() + green_z_offset(rm_bytes));
-    double2* d_sum = reinterpret_cast<double2*>(d_G.as<char>() + dos_align256(G.g_bytes()));
-    TBK_HIP(hipMemcpy(d_Rz.ptr, h_Rm.data(), rm_bytes, hipMemcpyHostToDevice));
-    TBK_HIP(hipMemcpy(d_Rz.as<char>() + green_z_offset(rm_bytes), z, z_bytes, hipMemcpyHostToDevice));
-    TBK_HIP(hipMemset(d_part.ptr, 0, (size_t)G.tiles * G.part_stride()));
-    for (int64_t c0 = 0; c0 < nk; c0 += G.chunk) {
-        const int64_t nkc = std::min(G.chunk, nk - c0);
-        TBK_HIP(hipMemcpy(d_E.ptr, E + (size_t)c0 * e_per_k, (size_t)nkc * e_per_k * sizeof(double), hipMemcpyHostToDevice));
-        TBK_HIP(hipMemcpy(d_U.ptr, U + (size_t)c0 * u_per_k, (size_t)nkc * u_per_k * sizeof(double), hipMemcpyHostToDevice));
-        TBK_CHECK(green_launch_chunk(nullptr, G, nullptr, d_Rz.as<int32_t>(), d_z, d_U.as<double>(), d_E.as<double>(), c0, nkc, d_tab.as<double>(),
-                                     d_P.as<double2>(), d_part.as<char>()));
-    }
-    TBK_CHECK(green_launch_gather(nullptr, G, nullptr, d_part.as<char>(), d_sum, d_G.as<double2>()));
-    TBK_HIP(hipMemcpy(G_out, d_G.ptr, G.g_bytes(), hipMemcpyDeviceToHost));
-    return TBK_OK;
+    GreenFamily fam(n_z, z);
+    return lattice_from_arrays(fam, dim, mesh, nk, n_orb, E, U, k_chunk, z_tile, n_r, R, G_out);
 }
 
 extern "C" int tbk_green_function_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int64_t n_z, const double* z, int64_t n_r,
@@ -840,73 +631,8 @@ extern "C" int tbk_green_function_multi(tbk_model* const* handles, int n_handles
     TBK_CHECK(green_check_z(n_z, z));
     TBK_ARG(handles != nullptr && n_handles >= 1 && handles[0] != nullptr, "no handles");
     TBK_CHECK(dm_check_R(n_r, R, G_out, handles[0]->n_orb));
-    TetraHandles th;
-    TBK_CHECK(th.open(handles, n_handles, mesh, OCC_MESH));
-    const int dim = th.dim, n_orb = th.n_orb;
-    // (the host buffers the enqueued copies read and write, in front of the streams: they wait before these go)
-    std::vector<int32_t> h_Rm;
-    std::vector<std::vector<double>> h_k((size_t)th.cut.busy()), partial((size_t)th.cut.busy());  // the slabs' k lists; G of the slabs behind the first
-    MeshStreams streams;
-    TBK_CHECK(dm_reduce_R(dim, mesh, n_r, R, &h_Rm));
-    const size_t rm_bytes = h_Rm.size() * sizeof(int32_t), z_bytes = (size_t)n_z * sizeof(double2);
-    const size_t g_doubles = (size_t)n_r * n_z * n_orb * n_orb * 2;
-    for (int i = 0; i < th.cut.busy(); ++i) {  // handles whose slab is empty are skipped
-        tbk_model* m = handles[i];
-        const int64_t nk = th.cut.count(i) * th.plane_pts;
-        TBK_CHECK(streams.add(m));
-        SpanRecorder* ev = &streams.used.back().ev;
-        TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, th.cut.lo(i), th.cut.count(i), &h_k[(size_t)i]));
-        DmPlan D;
-        TBK_CHECK(dm_plan(dim, mesh, th.nk_total, th.cut.lo(i) * th.plane_pts, nk, n_orb, n_r, &D));
-        // G and its partials first (the tile does not depend on the automatic chunk): the chunk is chosen from the memory they leave,
-        // shared between the chunk's eigenvectors and the projectors of one tile
-        GreenPlan G = green_plan(D, n_z, 0, m->k_chunk, nk);
-        const size_t part_bytes = (size_t)G.tiles * G.part_stride();
-        TBK_CHECK(mesh_reserve(m->ws_dm_part, part_bytes, GREEN_FAMILY, "the partial sums of every energy"));
-        TBK_CHECK(mesh_reserve(m->ws_dm_rho, dos_align256(G.g_bytes()) + G.sum_bytes(), GREEN_FAMILY, "G(R, z) of the call"));
-        TBK_CHECK(m->ws_dm_r.reserve(green_z_offset(rm_bytes) + z_bytes));
-        TBK_CHECK(m->ws_mesh_k.reserve(h_k[(size_t)i].size() * sizeof(double)));
-        G = green_plan(D, n_z, 0, m->k_chunk, mesh_eigh_chunk(m, nk, 1 + (int)G.zt));
-        const int64_t chunk = G.chunk;
-        const size_t u_doubles = (size_t)chunk * n_orb * n_orb * 2;
-        TBK_CHECK(mesh_reserve(m->ws_pdos_u, (u_doubles + (size_t)chunk * n_orb) * sizeof(double), GREEN_FAMILY, "the eigenvectors of one chunk"));
-        TBK_CHECK(m->ws_dm_tab.reserve(D.tab_bytes(chunk)));
-        TBK_CHECK(mesh_reserve(m->ws_dm_p, G.p_bytes(), GREEN_FAMILY, "the projectors of one chunk and one energy tile"));
-        char* d_rz = m->ws_dm_r.as<char>();
-        const double2* d_z = reinterpret_cast<const double2*>(d_rz + green_z_offset(rm_bytes));
-        double* d_k = m->ws_mesh_k.as<double>();
-        TBK_HIP(hipMemcpyAsync(d_k, h_k[(size_t)i].data(), h_k[(size_t)i].size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
-        TBK_HIP(hipMemcpyAsync(d_rz, h_Rm.data(), rm_bytes, hipMemcpyHostToDevice, m->stream));
-        TBK_HIP(hipMemcpyAsync(d_rz + green_z_offset(rm_bytes), z, z_bytes, hipMemcpyHostToDevice, m->stream));
-        TBK_HIP(hipMemsetAsync(m->ws_dm_part.ptr, 0, part_bytes, m->stream));
-        double* d_U = m->ws_pdos_u.as<double>();
-        double* d_E = d_U + u_doubles;
-        for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
-            const int64_t nkc = std::min(chunk, nk - c0);
-            TBK_CHECK(tbk_eigh_device(m, d_k + c0 * dim, nkc, 2, nullptr, d_E, d_U));
-            TBK_CHECK(green_launch_chunk(m->stream, G, ev, reinterpret_cast<const int32_t*>(d_rz), d_z, d_U, d_E, c0, nkc, m->ws_dm_tab.as<double>(),
-                                         m->ws_dm_p.as<double2>(), m->ws_dm_part.as<char>()));
-        }
-        double2* d_G = m->ws_dm_rho.as<double2>();
-        double2* d_sum = reinterpret_cast<double2*>(m->ws_dm_rho.as<char>() + dos_align256(G.g_bytes()));
-        TBK_CHECK(green_launch_gather(m->stream, G, ev, m->ws_dm_part.as<char>(), d_sum, d_G));
-        double* h_dst = G_out;
-        if (i > 0) {
-            try {
-                partial[(size_t)i].resize(g_doubles);
-            } catch (...) {
-                tbk_set_error("cannot allocate the per-handle results");
-                return TBK_ERR_MEMORY;
-            }
-            h_dst = partial[(size_t)i].data();
-        }
-        TBK_HIP(hipMemcpyAsync(h_dst, d_G, G.g_bytes(), hipMemcpyDeviceToHost, m->stream));
-    }
-    // synchronises every handle (the eigenvector flags are reported as by tbk_eigh) and books the kernel times
-    TBK_CHECK(streams.finish(TIMED_GREEN));
-    for (size_t i = 1; i < partial.size(); ++i)  // in handle order
-        for (size_t x = 0; x < g_doubles; ++x) G_out[x] += partial[i][x];
-    return TBK_OK;
+    GreenFamily fam(n_z, z);
+    return green_on_handles(fam, handles, n_handles, mesh, n_r, R, G_out);
 }
 
 extern "C" int tbk_green_function(tbk_model* m, const int32_t* mesh, int64_t n_z, const double* z, int64_t n_r, const int64_t* R, double* G_out) {

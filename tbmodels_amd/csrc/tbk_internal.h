@@ -339,21 +339,22 @@ struct tbk_model {
     DevBuf ws_occ_w;     // tbk_tetra_weights / tbk_occupations: the point weights of the slab's own mesh points w[rows][n_orb] (tbk_occ.hip)
     DevBuf ws_occ;       // ... the block partials of the band sums, the workgroups' rows of the contraction and the combined words
                          // (the eigenvectors of one k chunk go through ws_pdos_u, the Fermi search through ws_dos)
-    DevBuf ws_dm_r;      // tbk_density_matrix (tbk_dm.hip): the lattice vectors reduced modulo the mesh, int32 [n_r][dim]
-    DevBuf ws_dm_tab;    // ... the phase table of one k chunk, [R tiles][groups of 4 k][cos | sin][64]
-    DevBuf ws_dm_p;      // ... the projectors of one k chunk, [table columns][n_orb][n_orb] complex
-    DevBuf ws_dm_part;   // ... the k slices' partial rho [slices][n_r padded to 16][n_orb][n_orb] complex, resident across the chunks
-    DevBuf ws_dm_rho;    // ... their sum [n_r][n_orb][n_orb] complex (more than one slice)
-                         // tbk_green_function (tbk_green.hip) goes through the same five: behind the vectors its energies, P and the partials
-                         // per energy tile, ws_dm_rho G [n_r][n_z][n_orb][n_orb] and, behind it, the sum of one tile's slices; its k list is
-                         // in ws_mesh_k, the eigenvectors of one chunk and their eigenvalues in ws_pdos_u.  tbk_green_dressed: behind the
-                         // energies the self-energy [n_z][n_orb][n_orb] complex, ws_pdos_u the full H(k) of one chunk, ws_dm_p the inverses,
-                         // ws_mesh_work the library route's batch, pivots and status.  The layered calls (layered_slab, tbk_layered.hip):
-                         // ws_mesh_k the k list with its samples along the stacking axis, ws_dm_r energies and twiddles, ws_pdos_u H(k)
-                         // of one chunk, ws_dm_p its principal layers, ws_dm_rho its results and status words, ws_mesh_work the
-                         // workgroups' slots or the library route's batch; with a device, ws_mesh_io its potential V
-                         // (tbk_transmission_ensemble, tbk_transmission_channels: the devices of all samples, in either form);
-                         // tbk_device_green and tbk_device_current: ws_mesh_u the workgroups' stacks
+    // The calls that Fourier-sum a matrix of the mesh into lattice vectors (lattice_slab, tbk_lattice.hip): tbk_density_matrix,
+    // tbk_green_function, tbk_green_dressed.  The chunk's eigenvectors, with their eigenvalues behind them, or its full H(k) go
+    // through ws_pdos_u, the Green's functions' k list through ws_mesh_k, the dressed one's library batch, pivots and status
+    // through ws_mesh_work.
+    DevBuf ws_dm_r;      // the lattice vectors reduced modulo the mesh, int32 [n_r][dim]; 256-byte aligned behind them the energies [n_z]
+                         // and the self-energy [n_z][n_orb][n_orb], both complex
+    DevBuf ws_dm_tab;    // the phase table of one k chunk, [R tiles][groups of 4 k][cos | sin][64]
+    DevBuf ws_dm_p;      // P of one k chunk and one tile of energies, [table columns][energy in tile][n_orb][n_orb] complex
+    DevBuf ws_dm_part;   // per tile the k slices' partial sums [slices][n_r padded to 16][energy in tile][n_orb][n_orb] complex, across the chunks
+    DevBuf ws_dm_rho;    // rho: their sum [n_r][n_orb][n_orb] complex (more than one slice); G [n_r][n_z][n_orb][n_orb], behind it one tile's sum
+                         // The layered calls (layered_slab, tbk_layered.hip) use the same buffers: ws_mesh_k the k list with its
+                         // samples along the stacking axis, ws_dm_r energies and twiddles, ws_pdos_u H(k) of one chunk, ws_dm_p its
+                         // principal layers, ws_dm_rho its results and status words, ws_mesh_work the workgroups' slots or the library
+                         // route's batch; with a device, ws_mesh_io its potential V (tbk_transmission_ensemble,
+                         // tbk_transmission_channels: the devices of all samples, in either form); tbk_device_green and
+                         // tbk_device_current: ws_mesh_u the workgroups' stacks
     DevBuf ws_green_flag;  // tbk_green_dressed: one 64-bit status word, all ones or the smallest (mesh index * 4096 + energy index) that was singular
     // The calls on the resident eigensystem of a whole mesh (tbk_resident.h; the susceptibilities of tbk_chi.hip, tbk_berry_flux of
     // tbk_berry.hip): k, E and U are ResidentMesh's, the other two each family lays out for itself

@@ -21,10 +21,10 @@ inline int64_t mesh_eigh_chunk(tbk_model* m, int64_t nk, int share = 1) {
     return std::max<int64_t>(1, std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : choose_chunk(m, nk, true) / share));
 }
 
-// a reservation whose failure names the family ("the susceptibility"), what it keeps and the bytes
+// a reservation whose failure names the family ("the susceptibility"), what it keeps (NULL: the plain message) and the bytes
 inline int mesh_reserve(DevBuf& buf, size_t bytes, const char* family, const char* what) {
     const int r = buf.reserve(bytes);
-    if (r == TBK_ERR_MEMORY) tbk_set_error("%s keeps %s in device memory: %zu bytes do not fit", family, what, bytes);
+    if (r == TBK_ERR_MEMORY && what) tbk_set_error("%s keeps %s in device memory: %zu bytes do not fit", family, what, bytes);
     return r;
 }
 
