@@ -410,12 +410,12 @@ extern "C" int tbk_density_matrix_multi(tbk_model* const* handles, int n_handles
     TBK_CHECK(staged.weights(mu_out[0], nullptr, false));  // (not one of this family's three stages: not timed)
     TBK_CHECK(call.open(fam, staged, mesh, n_r, R, rho_out, staged.slabs.size()));
     for (size_t i = 0; i < staged.slabs.size(); ++i) {
-        OccSlab& s = staged.slabs[i];
+        TetraSlab& s = staged.slabs[i];
         TBK_HIP(hipSetDevice(s.m->device));
         fam.d_w = s.m->ws_occ_w.as<double>();
         // (the slab's own k list is the eigenvalue path's, behind the neighbour plane)
-        const double* d_k_own = s.m->ws_k.as<double>() + (size_t)s.off0 * staged.plane_pts * staged.dim;
-        TBK_CHECK(lattice_slab(fam, staged, call, i, s.m, s.ev, d_k_own, s.L.rows, s.p_lo * staged.plane_pts));
+        const double* d_k_own = s.m->ws_k.as<double>() + (size_t)s.head * staged.dim;
+        TBK_CHECK(lattice_slab(fam, staged, call, i, s.m, s.ev, d_k_own, staged.occ[i].L.rows, s.p_lo * staged.plane_pts));
     }
     return lattice_finish(fam, call, staged.streams);
 }

@@ -22,7 +22,7 @@
 #include <cmath>
 #include <vector>
 
-#include "tbk_tetra.h"
+#include "tbk_tetra_staged.h"
 
 namespace {
 
@@ -208,7 +208,7 @@ int tetra_check_mesh(int dim, const int32_t* mesh, const char* what, int64_t* nk
 
 int tbk_dos_check(int dim, const int32_t* mesh, double e_step, int64_t n_e, const void* nos_out, int64_t* nk_total) {
     if (dim == 2 || dim == 3) TBK_ARG(mesh != nullptr && nos_out != nullptr, "mesh / nos is NULL");  // (a wrong dim is reported first)
-    TBK_CHECK(tetra_check_mesh(dim, mesh, "the density of states needs a 2- or 3-dimensional mesh", nk_total));
+    TBK_CHECK(tetra_check_mesh(dim, mesh, DOS_MESH, nk_total));
     TBK_ARG(n_e >= 2, "the energy grid needs at least two points");
     TBK_ARG(n_e <= DOS_MAX_NE, "the energy grid has more than 2^20 points");
     TBK_ARG(std::isfinite(e_step) && e_step > 0.0, "the energy step must be positive and finite");
@@ -328,57 +328,49 @@ extern "C" int tbk_dos_from_eigenvalues(int device, int dim, const int32_t* mesh
     TBK_CHECK(tetra_check_device(device));
     DosLaunch L;
     TBK_CHECK(dos_plan(dim, mesh, mesh[0], mesh[0], n_orb, n_e, &L));
-    const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double);
-    DevBuf d_E, d_ws, d_nos;
-    TBK_CHECK(d_E.reserve(e_bytes));
+    TetraOwnedE d_E;
+    DevBuf d_ws, d_nos;
+    TBK_CHECK(d_E.upload(E, nk, n_orb));
     TBK_CHECK(d_ws.reserve(L.ws_bytes));
     TBK_CHECK(d_nos.reserve((size_t)n_e * sizeof(double)));
-    TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
-    TBK_CHECK(dos_launch(nullptr, dim, L, d_E.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk, d_ws.ptr, d_nos.as<double>()));
+    TBK_CHECK(dos_launch(nullptr, dim, L, d_E.d(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk, d_ws.ptr, d_nos.as<double>()));
     TBK_HIP(hipMemcpy(nos_out, d_nos.ptr, (size_t)n_e * sizeof(double), hipMemcpyDeviceToHost));
     return TBK_OK;
 }
 
-// Cells [p_lo, p_lo + p_count) along axis 0 of the mesh on one handle: the eigenvalues of those planes and of the one periodic
-// neighbour plane the last cells need (none when the slab is the whole axis) stay in HBM; nos_out receives this slab's share of
-// nos, already divided by S * NK of the whole mesh.
+// Cells [p_lo, p_lo + p_count) along axis 0 of the mesh on one handle, a one-slab case of the scaffold (tbk_tetra_staged.h): the
+// eigenvalues of those planes and of the one periodic neighbour plane the last cells need (none when the slab is the whole axis)
+// stay in HBM; nos_out -- the caller's, it outlives the wait -- receives this slab's share of nos, already divided by S * NK of
+// the whole mesh.
 int tbk_dos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_count, double e_min, double e_step, int64_t n_e, double* nos_out) {
     TBK_ARG(m != nullptr, "model is NULL");
-    TBK_LOCK(m);
     TBK_ARG(!m->kdotp, "a k.p model has no Brillouin zone");
     int64_t nk_total = 0;
     TBK_CHECK(tbk_dos_check(m->dim, mesh, e_step, n_e, nos_out, &nk_total));
     TBK_ARG(std::isfinite(e_min), "e_min is not finite");
-    const int dim = m->dim, n_orb = m->n_orb;
-    const int64_t n0 = mesh[0];
-    TBK_ARG(p_lo >= 0 && p_count >= 1 && p_lo + p_count <= n0, "slab outside the mesh");
-    TBK_HIP(hipSetDevice(m->device));
-    const int64_t planes = p_count == n0 ? n0 : p_count + 1;
+    TBK_ARG(p_lo >= 0 && p_count >= 1 && p_lo + p_count <= mesh[0], "slab outside the mesh");
     DosLaunch L;
-    TBK_CHECK(dos_plan(dim, mesh, p_count, planes, n_orb, n_e, &L));
-
-    TBK_CHECK(m->ws_dos.reserve(L.ws_bytes + dos_align256((size_t)n_e * sizeof(double))));
-    std::vector<double> h_k;
-    TBK_CHECK(tbk_mesh_eigenvalues(m, mesh, p_lo, planes, false, &h_k));
-    TBK_CHECK(tbk_eigenval_check(m));  // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigenval
-
+    TetraStaged staged;
+    TBK_CHECK(staged.make_slab(
+        m, mesh, DOS_MESH, p_lo, p_count,
+        [&](TetraSlab& s, size_t) -> int {
+            TBK_CHECK(dos_plan(staged.dim, mesh, s.p_count, s.planes, staged.n_orb, n_e, &L));
+            return m->ws_dos.reserve(L.ws_bytes + dos_align256((size_t)n_e * sizeof(double)));
+        },
+        false));
+    const TetraSlab& s = staged.slabs[0];
     double* d_nos = reinterpret_cast<double*>(m->ws_dos.as<char>() + L.ws_bytes);
-    SpanRecorder timer(m->timing, m->stream);
-    timer.start();
-    TBK_CHECK(dos_launch(m->stream, dim, L, m->ws_out.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk_total, m->ws_dos.ptr, d_nos));
-    timer.stop();
+    s.ev->start();
+    TBK_CHECK(dos_launch(m->stream, staged.dim, L, s.d_E, e_min, e_step, (double)(staged.dim == 3 ? 6 : 2) * (double)nk_total, m->ws_dos.ptr, d_nos));
+    s.ev->stop();
     TBK_HIP(hipMemcpyAsync(nos_out, d_nos, (size_t)n_e * sizeof(double), hipMemcpyDeviceToHost, m->stream));
-    TBK_HIP(hipStreamSynchronize(m->stream));
-    TimedSums& sums = m->timed[TIMED_DOS];
-    timer.collect(sums.ms);
-    if (timer.on) sums.calls += 1;
-    return TBK_OK;
+    return staged.streams.book(TIMED_DOS, true);
 }
 
 extern "C" int tbk_dos(tbk_model* m, const int32_t* mesh, double e_min, double e_step, int64_t n_e, double* nos_out) {
     TBK_ARG(m != nullptr, "model is NULL");
     TBK_ARG(mesh != nullptr, "mesh / nos is NULL");
-    TBK_ARG(m->dim == 2 || m->dim == 3, "the density of states needs a 2- or 3-dimensional mesh");
+    TBK_ARG(m->dim == 2 || m->dim == 3, DOS_MESH);
     TBK_ARG(mesh[0] >= 1, "a mesh entry is < 1");
     return tbk_dos_slab(m, mesh, 0, mesh[0], e_min, e_step, n_e, nos_out);
 }

@@ -29,12 +29,11 @@
 #include <cstring>
 #include <vector>
 
-#include "tbk_tetra.h"
+#include "tbk_tetra_staged.h"
 
 namespace {
 
 constexpr int FERMI_THREADS = 256;
-constexpr int FERMI_PROBES = 16;      // probe energies per launch
 constexpr int FERMI_SEARCH_M = 15;    // probes per pass of the search: 16 sub-intervals, 4 bits of the ordered image per pass
 constexpr int FERMI_EDGE_WG = 256;    // row workgroups of the band-edge kernel, at most
 
@@ -201,13 +200,7 @@ __global__ void __launch_bounds__(FERMI_THREADS) band_edges_reduce_kernel(const 
     emax[band] = hi;
 }
 
-// ---- host: one slab of the mesh on one device ----------------------------------------------------------------------------------
-struct FermiLaunch {
-    DosGeom g;
-    int n_wg = 0, edge_wg = 0;
-    int64_t rows = 0;  // mesh rows of this slab's own cells (without the periodic neighbour plane)
-    size_t off_count = 0, off_sums = 0, off_pmin = 0, off_pmax = 0, off_emin = 0, off_emax = 0, ws_bytes = 0;
-};
+// ---- host: one slab of the mesh on one device (FermiLaunch, FermiSlab: tbk_tetra_staged.h) --------------------------------------
 
 // dim in {2, 3}; cells0 cells along axis 0 out of planes0 planes held in E
 int fermi_plan(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb, FermiLaunch* out) {
@@ -275,19 +268,6 @@ FermiCount fermi_target(double n_electrons, int64_t simplices) {
     return q;
 }
 
-struct FermiSlab {
-    tbk_model* m = nullptr;  // NULL: eigenvalues the caller brought
-    int device = 0, dim = 0;
-    hipStream_t stream = nullptr;
-    FermiLaunch L;
-    const double* d_E = nullptr;
-    char* d_ws = nullptr;
-    std::vector<double> h_k;  // the mesh's k list until the eigenvalues are checked
-    SpanRecorder timer;       // off unless the slab is a staged handle's with TBK_OPT_TIMING on
-    double ms = 0.0;          // the kernels of every pass of the call
-    unsigned long long h_sums[FERMI_PROBES * 3];
-};
-
 // enqueue: N at n probes (1 .. 16) of this slab's cells -> h_sums, behind the stream
 int fermi_probe_enqueue(FermiSlab& s, const double* energies, int n) {
     FermiProbes p;
@@ -296,7 +276,7 @@ int fermi_probe_enqueue(FermiSlab& s, const double* energies, int n) {
     auto* part_g = reinterpret_cast<unsigned long long*>(s.d_ws);
     auto* count_g = reinterpret_cast<unsigned*>(s.d_ws + s.L.off_count);
     auto* sums = reinterpret_cast<unsigned long long*>(s.d_ws + s.L.off_sums);
-    s.timer.start();
+    if (s.ev) s.ev->start();
     if (s.dim == 3)
         hipLaunchKernelGGL(nos_probe_kernel<3>, dim3((unsigned)s.L.n_wg), dim3(FERMI_THREADS), 0, s.stream, s.d_E, s.L.g, p, part_g, count_g);
     else
@@ -304,7 +284,7 @@ int fermi_probe_enqueue(FermiSlab& s, const double* energies, int n) {
     TBK_HIP(hipGetLastError());
     hipLaunchKernelGGL(nos_probe_reduce_kernel, dim3(1), dim3(FERMI_THREADS), 0, s.stream, part_g, count_g, s.L.n_wg, sums);
     TBK_HIP(hipGetLastError());
-    s.timer.stop();
+    if (s.ev) s.ev->stop();
     TBK_HIP(hipMemcpyAsync(s.h_sums, sums, sizeof(s.h_sums), hipMemcpyDeviceToHost, s.stream));
     return TBK_OK;
 }
@@ -316,30 +296,27 @@ int fermi_probe(std::vector<FermiSlab>& slabs, const double* energies, int n, Fe
     for (FermiSlab& s : slabs) {
         TBK_HIP(hipSetDevice(s.device));
         TBK_HIP(hipStreamSynchronize(s.stream));
-        s.timer.collect(&s.ms);
         for (int m = 0; m < n; ++m) q[m].add(fermi_count(s.h_sums + 3 * m));
     }
     return TBK_OK;
 }
 
-// emin / emax [n_orb] over all slabs
+// emin / emax [n_orb] over all slabs, through every slab's h_edges
 int fermi_edges(std::vector<FermiSlab>& slabs, int n_orb, double* emin, double* emax) {
-    std::vector<double> share((size_t)slabs.size() * 2 * (size_t)n_orb);
-    for (size_t i = 0; i < slabs.size(); ++i) {
-        FermiSlab& s = slabs[i];
+    for (FermiSlab& s : slabs) {
         TBK_HIP(hipSetDevice(s.device));
         auto* pmin = reinterpret_cast<double*>(s.d_ws + s.L.off_pmin);
         auto* pmax = reinterpret_cast<double*>(s.d_ws + s.L.off_pmax);
         auto* d_min = reinterpret_cast<double*>(s.d_ws + s.L.off_emin);
         auto* d_max = reinterpret_cast<double*>(s.d_ws + s.L.off_emax);
         const dim3 grid((unsigned)s.L.edge_wg, (unsigned)((n_orb + FERMI_THREADS - 1) / FERMI_THREADS));
-        s.timer.start();
+        if (s.ev) s.ev->start();
         hipLaunchKernelGGL(band_edges_kernel, grid, dim3(FERMI_THREADS), 0, s.stream, s.d_E, s.L.rows, n_orb, pmin, pmax);
         TBK_HIP(hipGetLastError());
         hipLaunchKernelGGL(band_edges_reduce_kernel, dim3(grid.y), dim3(FERMI_THREADS), 0, s.stream, pmin, pmax, s.L.edge_wg, n_orb, d_min, d_max);
         TBK_HIP(hipGetLastError());
-        s.timer.stop();
-        double* h = share.data() + i * 2 * (size_t)n_orb;
+        if (s.ev) s.ev->stop();
+        double* h = s.h_edges.data();
         TBK_HIP(hipMemcpyAsync(h, d_min, (size_t)n_orb * sizeof(double), hipMemcpyDeviceToHost, s.stream));
         TBK_HIP(hipMemcpyAsync(h + n_orb, d_max, (size_t)n_orb * sizeof(double), hipMemcpyDeviceToHost, s.stream));
     }
@@ -347,8 +324,7 @@ int fermi_edges(std::vector<FermiSlab>& slabs, int n_orb, double* emin, double* 
         FermiSlab& s = slabs[i];
         TBK_HIP(hipSetDevice(s.device));
         TBK_HIP(hipStreamSynchronize(s.stream));
-        s.timer.collect(&s.ms);
-        const double* h = share.data() + i * 2 * (size_t)n_orb;
+        const double* h = s.h_edges.data();
         for (int b = 0; b < n_orb; ++b) {
             emin[b] = i == 0 ? h[b] : std::fmin(emin[b], h[b]);
             emax[b] = i == 0 ? h[n_orb + b] : std::fmax(emax[b], h[n_orb + b]);
@@ -438,115 +414,96 @@ int fermi_search(std::vector<FermiSlab>& slabs, int n_orb, int64_t simplices, do
     return TBK_OK;
 }
 
-const char* const FERMI_MESH = "the density of states needs a 2- or 3-dimensional mesh";
-
 int fermi_check_electrons(double n_electrons, int n_orb) {
     TBK_ARG(std::isfinite(n_electrons) && n_electrons > 0.0 && n_electrons < (double)n_orb, "n_electrons must lie inside (0, n_orb)");
     return TBK_OK;
 }
 
-// eigenvalues the caller brought, on one device: the slab is the whole mesh
+// eigenvalues the caller brought, on the device just checked: one slab that is the whole mesh, on the null stream, not timed
 struct FermiOwned {
-    DevBuf d_E, d_ws;
+    TetraOwnedE d_E;
+    DevBuf d_ws;
     std::vector<FermiSlab> slabs;
     int make(int device, int dim, const int32_t* mesh, int n_orb, const double* E, int64_t nk) {
-        slabs.emplace_back();
-        FermiSlab& s = slabs.back();
+        slabs.resize(1);
+        FermiSlab& s = slabs[0];
         s.device = device;
         s.dim = dim;
+        s.h_edges.resize(2 * (size_t)n_orb);
         TBK_CHECK(fermi_plan(dim, mesh, mesh[0], mesh[0], n_orb, &s.L));
-        const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double);
-        TBK_CHECK(d_E.reserve(e_bytes));
+        TBK_CHECK(d_E.upload(E, nk, n_orb));
         TBK_CHECK(d_ws.reserve(s.L.ws_bytes));
-        TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
-        s.d_E = d_E.as<double>();
+        s.d_E = d_E.d();
         s.d_ws = d_ws.as<char>();
         return TBK_OK;
     }
 };
 
-// The mesh on staged handles: handle i takes the slab of tbk_dos_multi.  The caller's thread holds every handle's lock for the
-// whole call (the eigenvalues stay in the handles' ws_out across all passes), taken in address order; the eigenvalue calls are
-// enqueued handle after handle and checked afterwards, the probes of a pass likewise.
-struct FermiStaged : TetraHandles {
-    std::vector<FermiSlab> slabs;
-    int64_t simplices = 0;
-    int make(tbk_model* const* handles, int n_handles, const int32_t* mesh) {
-        TBK_CHECK(open(handles, n_handles, mesh, FERMI_MESH));
-        simplices = (int64_t)(dim == 3 ? 6 : 2) * nk_total;
-        const int64_t n0 = mesh[0];
-        slabs.reserve((size_t)cut.busy());
-        for (int i = 0; i < cut.busy(); ++i) {  // handles whose slab is empty are skipped
-            const int64_t p_lo = cut.lo(i), p_count = cut.count(i);
-            tbk_model* m = handles[i];
-            slabs.emplace_back();
-            FermiSlab& s = slabs.back();
-            s.m = m;
-            s.device = m->device;
-            s.dim = dim;
-            s.stream = m->stream;
-            TBK_HIP(hipSetDevice(m->device));
-            const int64_t planes = p_count == n0 ? n0 : p_count + 1;
-            TBK_CHECK(fermi_plan(dim, mesh, p_count, planes, n_orb, &s.L));
-            TBK_CHECK(m->ws_dos.reserve(s.L.ws_bytes));
-            TBK_CHECK(tbk_mesh_eigenvalues(m, mesh, p_lo, planes, false, &s.h_k));
-            s.d_E = m->ws_out.as<double>();
-            s.d_ws = m->ws_dos.as<char>();
-            s.timer = SpanRecorder(m->timing, m->stream);
-        }
-        // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigenval: the first failing slab's
-        for (FermiSlab& s : slabs) {
-            TBK_CHECK(tbk_eigenval_check(s.m));
-            std::vector<double>().swap(s.h_k);
-        }
-        return TBK_OK;
+// The Fermi state of a staged slab, on its handle's device: the plan and the probe rows in ws_dos -- in front of the slab's
+// eigenvalues (TetraStaged::make) or, for a family that finds its mu on eigenvalues it keeps, behind them
+int fermi_reserve(const TetraStaged& t, const TetraSlab& s, const int32_t* mesh, FermiSlab* f) {
+    f->device = s.m->device;
+    f->dim = t.dim;
+    f->stream = s.m->stream;
+    f->h_edges.resize(2 * (size_t)t.n_orb);
+    TBK_CHECK(fermi_plan(t.dim, mesh, s.p_count, s.upper_planes(), t.n_orb, &f->L));
+    return s.m->ws_dos.reserve(f->L.ws_bytes);
+}
+
+void fermi_attach(const TetraStaged& t, std::vector<FermiSlab>& state) {
+    for (size_t i = 0; i < state.size(); ++i) {
+        state[i].d_E = t.slabs[i].own_E(t.n_orb);
+        state[i].d_ws = t.slabs[i].m->ws_dos.as<char>();
     }
-    void book(int passes, bool searched) {
-        for (FermiSlab& s : slabs) {
-            TimedSums& sums = s.m->timed[TIMED_FERMI];
-            if (s.timer.on) sums.ms[0] += s.ms;
-            sums.calls += 1;
-            if (searched) sums.passes += passes;
-        }
-    }
-};
+}
+
+int64_t fermi_simplices(const TetraStaged& t) { return (int64_t)(t.dim == 3 ? 6 : 2) * t.nk_total; }
+
+// The mesh on staged handles: handle i takes the slab of tbk_dos_multi, and its eigenvalues stay in its ws_out across all passes.
+// `state` is the caller's, declared in front of `staged`.  The kernels of every pass are booked on the handles' recorders.
+int fermi_make(TetraStaged& staged, std::vector<FermiSlab>& state, tbk_model* const* handles, int n_handles, const int32_t* mesh) {
+    TBK_CHECK(staged.make(handles, n_handles, mesh, DOS_MESH, false, [&](TetraSlab& s, size_t i) {
+        state.resize(i + 1);  // (nothing is enqueued into the state before the first pass)
+        state[i].ev = s.ev;
+        return fermi_reserve(staged, s, mesh, &state[i]);
+    }));
+    fermi_attach(staged, state);
+    return TBK_OK;
+}
+
+// every call counts, and the passes of a search
+int fermi_book(TetraStaged& staged, int passes) {
+    TBK_CHECK(staged.streams.book(TIMED_FERMI));
+    for (TetraSlab& s : staged.slabs) s.m->timed[TIMED_FERMI].passes += passes;
+    return TBK_OK;
+}
 
 }  // namespace
 
 int tbk_fermi_check_electrons(double n_electrons, int n_orb) { return fermi_check_electrons(n_electrons, n_orb); }
 
-int tbk_fermi_resident(const tbk_fermi_slab_t* slabs, int n_slabs, int dim, const int32_t* mesh, int n_orb, int mode, double value, double* out4) {
-    int64_t nk_total = 0;
-    TBK_CHECK(tetra_check_mesh(dim, mesh, FERMI_MESH, &nk_total));
-    std::vector<FermiSlab> v((size_t)n_slabs);
-    for (int i = 0; i < n_slabs; ++i) {
-        FermiSlab& s = v[(size_t)i];
-        s.m = slabs[i].m;
-        s.device = s.m->device;
-        s.dim = dim;
-        s.stream = s.m->stream;
-        TBK_CHECK(fermi_plan(dim, mesh, slabs[i].cells0, slabs[i].planes0, n_orb, &s.L));
-        TBK_HIP(hipSetDevice(s.device));
-        TBK_CHECK(s.m->ws_dos.reserve(s.L.ws_bytes));
-        s.d_E = slabs[i].d_E;
-        s.d_ws = s.m->ws_dos.as<char>();
+int tbk_fermi_resident(TetraStaged& staged, std::vector<FermiSlab>& state, const int32_t* mesh, int mode, double value, double* out4) {
+    state.resize(staged.slabs.size());
+    for (size_t i = 0; i < state.size(); ++i) {
+        TBK_HIP(hipSetDevice(staged.slabs[i].m->device));
+        TBK_CHECK(fermi_reserve(staged, staged.slabs[i], mesh, &state[i]));
     }
-    const int64_t simplices = (int64_t)(dim == 3 ? 6 : 2) * nk_total;
+    fermi_attach(staged, state);
     if (mode == 1) {
         int passes = 0;
-        return fermi_search(v, n_orb, simplices, value, out4, &passes);
+        return fermi_search(state, staged.n_orb, fermi_simplices(staged), value, out4, &passes);
     }
     FermiCount q[FERMI_PROBES];
-    TBK_CHECK(fermi_probe(v, &value, 1, q));
+    TBK_CHECK(fermi_probe(state, &value, 1, q));
     out4[0] = out4[1] = out4[2] = value;
-    out4[3] = fermi_nos(q[0], simplices);
+    out4[3] = fermi_nos(q[0], fermi_simplices(staged));
     return TBK_OK;
 }
 
 extern "C" int tbk_nos_at_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* energies,
                                            int64_t n_p, double* nos_out) {
     int64_t nk = 0;
-    TBK_CHECK(tetra_check_mesh(dim, mesh, FERMI_MESH, &nk));
+    TBK_CHECK(tetra_check_mesh(dim, mesh, DOS_MESH, &nk));
     TBK_ARG(E != nullptr && energies != nullptr && nos_out != nullptr, "E / energies / nos is NULL");
     TBK_ARG(n_orb >= 1, "n_orb < 1");
     TBK_ARG(n_p >= 1, "no probe energies");
@@ -567,7 +524,7 @@ extern "C" int tbk_nos_at_from_eigenvalues(int device, int dim, const int32_t* m
 extern "C" int tbk_band_edges_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double* emin_out,
                                                double* emax_out) {
     int64_t nk = 0;
-    TBK_CHECK(tetra_check_mesh(dim, mesh, FERMI_MESH, &nk));
+    TBK_CHECK(tetra_check_mesh(dim, mesh, DOS_MESH, &nk));
     TBK_ARG(E != nullptr && emin_out != nullptr && emax_out != nullptr, "E / emin / emax is NULL");
     TBK_ARG(n_orb >= 1, "n_orb < 1");
     TBK_CHECK(tetra_check_device(device));
@@ -579,7 +536,7 @@ extern "C" int tbk_band_edges_from_eigenvalues(int device, int dim, const int32_
 extern "C" int tbk_fermi_from_eigenvalues(int device, int dim, const int32_t* mesh, int n_orb, const double* E, double n_electrons, double* out,
                                           int32_t* passes_out) {
     int64_t nk = 0;
-    TBK_CHECK(tetra_check_mesh(dim, mesh, FERMI_MESH, &nk));
+    TBK_CHECK(tetra_check_mesh(dim, mesh, DOS_MESH, &nk));
     TBK_ARG(E != nullptr && out != nullptr, "E / out is NULL");
     TBK_ARG(n_orb >= 1, "n_orb < 1");
     TBK_CHECK(fermi_check_electrons(n_electrons, n_orb));
@@ -594,11 +551,11 @@ extern "C" int tbk_fermi_from_eigenvalues(int device, int dim, const int32_t* me
 
 extern "C" int tbk_band_edges_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, double* emin_out, double* emax_out) {
     TBK_ARG(emin_out != nullptr && emax_out != nullptr, "emin / emax is NULL");
-    FermiStaged staged;
-    TBK_CHECK(staged.make(handles, n_handles, mesh));
-    TBK_CHECK(fermi_edges(staged.slabs, handles[0]->n_orb, emin_out, emax_out));
-    staged.book(0, false);
-    return TBK_OK;
+    std::vector<FermiSlab> state;  // (in front of `staged`: its streams wait before the state goes)
+    TetraStaged staged;
+    TBK_CHECK(fermi_make(staged, state, handles, n_handles, mesh));
+    TBK_CHECK(fermi_edges(state, staged.n_orb, emin_out, emax_out));
+    return fermi_book(staged, 0);
 }
 
 extern "C" int tbk_band_edges(tbk_model* m, const int32_t* mesh, double* emin_out, double* emax_out) {
@@ -609,12 +566,12 @@ extern "C" int tbk_fermi_multi(tbk_model* const* handles, int n_handles, const i
     TBK_ARG(out != nullptr, "out is NULL");
     TBK_ARG(handles != nullptr && n_handles >= 1 && handles[0] != nullptr, "no handles");
     TBK_CHECK(fermi_check_electrons(n_electrons, handles[0]->n_orb));
-    FermiStaged staged;
-    TBK_CHECK(staged.make(handles, n_handles, mesh));
+    std::vector<FermiSlab> state;  // (in front of `staged`: its streams wait before the state goes)
+    TetraStaged staged;
+    TBK_CHECK(fermi_make(staged, state, handles, n_handles, mesh));
     int passes = 0;
-    TBK_CHECK(fermi_search(staged.slabs, handles[0]->n_orb, staged.simplices, n_electrons, out, &passes));
-    staged.book(passes, true);
-    return TBK_OK;
+    TBK_CHECK(fermi_search(state, staged.n_orb, fermi_simplices(staged), n_electrons, out, &passes));
+    return fermi_book(staged, passes);
 }
 
 extern "C" int tbk_fermi(tbk_model* m, const int32_t* mesh, double n_electrons, double* out) { return tbk_fermi_multi(&m, 1, mesh, n_electrons, out); }

@@ -332,13 +332,17 @@ struct tbk_model {
     std::vector<double> pos_cache;  // host copy of what ws_posraw holds
     DevBuf ws_posraw;
     DevBuf ws_xl;     // the launch chain of band_xl_*: the second matrix buffer (the sweep of a panel reads one, writes the other)
-    DevBuf ws_dos;    // tbk_dos / tbk_pdos: the workgroups' fixed-point bins [n_wg][NE], the combined bins and nos (tbk_dos.hip, tbk_pdos.hip); tbk_fermi: its rows and partials
-    DevBuf ws_pdos_u;    // tbk_pdos: the eigenvectors of one k chunk [chunk][n_orb][n_orb] complex
-    DevBuf ws_pdos_w;    // ... the weights of the whole slab W[NK][G][n_orb]
+    // The tetrahedron calls on staged handles (TetraStaged, tbk_tetra_staged.h): a slab's k list goes through ws_k and its eigenvalues
+    // stay in ws_out, for every family
+    DevBuf ws_dos;    // tbk_dos / tbk_pdos: the workgroups' fixed-point bins [n_wg][NE], the combined bins and nos (tbk_dos.hip, tbk_pdos.hip);
+                      // tbk_fermi and every search for mu (tbk_fermi_resident: occupations, density matrix, susceptibilities): its rows and partials
+    DevBuf ws_pdos_u;    // the eigenvectors of one k chunk [chunk][n_orb][n_orb] complex: tbk_pdos; tbk_occupations, with the chunk's
+                         // eigenvalues behind them (the R-space calls of tbk_lattice.hip: below)
+    DevBuf ws_pdos_w;    // tbk_pdos: the weights of the whole slab W[NK][G][n_orb]
     DevBuf ws_pdos_grp;  // ... the groups: offsets [G + 1] and, 256-byte aligned behind them, the orbital list
-    DevBuf ws_occ_w;     // tbk_tetra_weights / tbk_occupations: the point weights of the slab's own mesh points w[rows][n_orb] (tbk_occ.hip)
-    DevBuf ws_occ;       // ... the block partials of the band sums, the workgroups' rows of the contraction and the combined words
-                         // (the eigenvectors of one k chunk go through ws_pdos_u, the Fermi search through ws_dos)
+    DevBuf ws_occ_w;     // the point weights of the slab's own mesh points w[rows][n_orb] (tbk_occ.hip): tbk_tetra_weights, tbk_occupations,
+                         // tbk_density_matrix
+    DevBuf ws_occ;       // tbk_occupations: the block partials of the band sums, the workgroups' rows of the contraction and the combined words
     // The calls that Fourier-sum a matrix of the mesh into lattice vectors (lattice_slab, tbk_lattice.hip): tbk_density_matrix,
     // tbk_green_function, tbk_green_dressed.  The chunk's eigenvectors, with their eigenvalues behind them, or its full H(k) go
     // through ws_pdos_u, the Green's functions' k list through ws_mesh_k, the dressed one's library batch, pivots and status
@@ -681,18 +685,6 @@ int tbk_dos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_coun
 int tbk_pdos_check_groups(int n_orb, const int32_t* group_offsets, const int32_t* group_orbitals, int n_groups);
 int tbk_pdos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_count, const int32_t* group_offsets, const int32_t* group_orbitals,
                   int n_groups, double e_min, double e_step, int64_t n_e, double* nos_out);
-
-// tbk_fermi.hip: the Fermi search (mode 1, value = n_electrons: mu, lower, upper, N(mu) of tbk_fermi) or N at one energy (mode 0,
-// value = the energy: mu = lower = upper = value) on eigenvalues that are resident on the handles -- slab i holds planes0 planes of
-// axis 0 at d_E, its own cells0 cells first (the layout of tbk_fermi_multi).  The caller holds the handles' locks and has checked
-// the eigenvalues; the probe rows go through every handle's ws_dos.  tbk_occupations (tbk_occ.hip) finds its mu here.
-struct tbk_fermi_slab_t {
-    tbk_model* m;
-    const double* d_E;
-    int64_t cells0, planes0;
-};
-int tbk_fermi_resident(const tbk_fermi_slab_t* slabs, int n_slabs, int dim, const int32_t* mesh, int n_orb, int mode, double value, double* out4);
-int tbk_fermi_check_electrons(double n_electrons, int n_orb);
 
 // tbk_peak.hip
 int tbk_run_mfma_f64_peak(double* tflops);

@@ -15,7 +15,7 @@
 #include <thread>
 #include <vector>
 
-#include "tbk_tetra.h"
+#include "tbk_tetra_staged.h"
 
 namespace {
 
@@ -252,20 +252,11 @@ extern "C" int tbk_dos_multi(tbk_model* const* handles, int n_handles, const int
     const int64_t n0 = mesh[0];
     const int busy = TetraSlabs(n0, n_handles).busy();
     std::vector<double> share;
-    try {
-        share.assign((size_t)busy * (size_t)n_e, 0.0);
-    } catch (...) {
-        tbk_set_error("cannot allocate the per-handle results");
-        return TBK_ERR_MEMORY;
-    }
+    TBK_CHECK(tetra_shares(&share, (size_t)busy * (size_t)n_e));
     TBK_CHECK(run_slabs(n_handles, n0, [&](int i, int64_t lo, int64_t count) {
         return tbk_dos_slab(handles[i], mesh, lo, count, e_min, e_step, n_e, share.data() + (size_t)i * (size_t)n_e);
     }));
-    for (int64_t j = 0; j < n_e; ++j) {
-        double sum = share[(size_t)j];
-        for (int i = 1; i < busy; ++i) sum += share[(size_t)i * (size_t)n_e + (size_t)j];
-        nos_out[j] = sum;
-    }
+    tetra_add_shares(share, (size_t)busy, (size_t)n_e, nos_out);
     return TBK_OK;
 }
 
@@ -284,21 +275,12 @@ extern "C" int tbk_pdos_multi(tbk_model* const* handles, int n_handles, const in
     const int busy = TetraSlabs(n0, n_handles).busy();
     const size_t n_out = (size_t)n_groups * (size_t)n_e;
     std::vector<double> share;
-    try {
-        share.assign((size_t)busy * n_out, 0.0);
-    } catch (...) {
-        tbk_set_error("cannot allocate the per-handle results");
-        return TBK_ERR_MEMORY;
-    }
+    TBK_CHECK(tetra_shares(&share, (size_t)busy * n_out));
     TBK_CHECK(run_slabs(n_handles, n0, [&](int i, int64_t lo, int64_t count) {
         return tbk_pdos_slab(handles[i], mesh, lo, count, group_offsets, group_orbitals, n_groups, e_min, e_step, n_e,
                              share.data() + (size_t)i * n_out);
     }));
-    for (size_t j = 0; j < n_out; ++j) {
-        double sum = share[j];
-        for (int i = 1; i < busy; ++i) sum += share[(size_t)i * n_out + j];
-        nos_out[j] = sum;
-    }
+    tetra_add_shares(share, (size_t)busy, n_out, nos_out);
     return TBK_OK;
 }
 

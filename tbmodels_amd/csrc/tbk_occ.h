@@ -1,13 +1,13 @@
 // tbk_occ.h -- what the calls that integrate with the point weights w[k][b] of a mesh share: tbk_occ.hip (weights, occupations) and
 // tbk_dm.hip (the real-space density matrix).  The plan of one slab, the launchers of tbk_occ.hip's kernels, and the staged call:
-// the handles with their slabs, the slabs' eigenvalues, mu and the weights, in that order.  The kernels are in tbk_occ.hip; the
-// check of every handle, the finish and the wait on every exit are MeshStreams' (tbk_resident.h).
+// TetraStaged (tbk_tetra_staged.h: the handles with their slabs and the slabs' eigenvalues), then mu and the weights.  The kernels
+// are in tbk_occ.hip; the check of every handle, the finish and the wait on every exit are MeshStreams' (tbk_resident.h).
 #pragma once
 
 #include <algorithm>
 #include <vector>
 
-#include "tbk_resident.h"
+#include "tbk_tetra_staged.h"
 
 struct OccGeom {
     int n0_own;     // planes of axis 0 this launch writes weights for
@@ -44,112 +44,90 @@ int occ_launch_reduce(hipStream_t s, const OccPlan& L, char* ws);
 inline constexpr const char* OCC_MESH ="the tetrahedron weights need a 2- or 3-dimensional mesh";
 
 // ---- the mesh on staged handles ------------------------------------------------------------------------------------------------
+// what a slab keeps beside TetraSlab.  The stages of its recorder: 0 the weights kernel, 1 the band sums, 2 the contraction + its
+// reduction (tbk_dm.hip: its own three)
 struct OccSlab {
-    tbk_model* m = nullptr;
-    int64_t p_lo = 0, p_count = 0, planes = 0;
-    int off0 = 0;
     OccPlan L;
-    const double* d_E = nullptr;  // planes planes
-    std::vector<double> h_k;
     std::vector<double> host;  // the off_host block
-    // the handle's recorder in OccStaged::streams.  Stages: 0 the weights kernel, 1 the band sums, 2 the contraction + its reduction
-    // (tbk_dm.hip: its own three)
-    SpanRecorder* ev = nullptr;
+};
+
+// the host side of what the call enqueues: a base in front of TetraStaged, so that it goes after the streams have waited
+struct OccHost {
+    std::vector<OccSlab> occ;      // beside TetraStaged::slabs
+    std::vector<FermiSlab> fermi;  // find_mu's passes
 };
 
 // Handle i takes the slab of tbk_dos_multi.  Its eigenvalues: the planes [p_lo, p_lo + p_count] come from ONE call of the
 // eigenvalue path on the k list tbk_fermi_multi gives it (the same call, so the same bits: mu is tbk_fermi's), the neighbour plane
 // p_lo - 1 from a second call, in front of them in ws_out.  A handle that holds the whole axis needs neither neighbour.
-struct OccStaged : TetraHandles {
-    std::vector<OccSlab> slabs;
-    MeshStreams streams;  // (behind the slabs: it waits before their host buffers go)
-
+struct OccStaged : OccHost, TetraStaged {
     // the handles and the mesh, checked and locked; then the eigenvalues of every slab, checked
     int make(tbk_model* const* handles, int n_handles, const int32_t* mesh) {
-        TBK_CHECK(open(handles, n_handles, mesh, OCC_MESH));
-        const int64_t n0 = mesh[0];
-        slabs.reserve((size_t)cut.busy());
-        for (int i = 0; i < cut.busy(); ++i) {  // handles whose slab is empty are skipped
-            const int64_t p_lo = cut.lo(i), p_count = cut.count(i);
-            tbk_model* m = handles[i];
-            slabs.emplace_back();
-            OccSlab& s = slabs.back();
-            s.m = m;
-            s.p_lo = p_lo;
-            s.p_count = p_count;
-            s.off0 = p_count == n0 ? 0 : 1;
-            const int64_t main_planes = p_count == n0 ? n0 : p_count + 1;
-            s.planes = main_planes + s.off0;
-            TBK_CHECK(streams.add(m));
-            s.ev = &streams.used.back().ev;
-            TBK_CHECK(occ_plan(dim, mesh, p_count, s.planes, s.off0, n_orb, &s.L));
-            TBK_CHECK(m->ws_occ_w.reserve((size_t)s.L.rows * n_orb * sizeof(double)));
-            TBK_CHECK(m->ws_occ.reserve(s.L.ws_bytes));
-            // the neighbour plane below in front of the main planes
-            TBK_CHECK(tbk_mesh_eigenvalues(m, mesh, p_lo, main_planes, s.off0 != 0, &s.h_k));
-            s.d_E = m->ws_out.as<double>();
-        }
-        return streams.check();
+        return TetraStaged::make(handles, n_handles, mesh, OCC_MESH, true, [&](TetraSlab& s, size_t i) -> int {
+            occ.resize(i + 1);  // (nothing is enqueued into these before the eigenvalues are checked)
+            OccPlan& L = occ[i].L;
+            TBK_CHECK(occ_plan(dim, mesh, s.p_count, s.planes, s.off0, n_orb, &L));
+            TBK_CHECK(s.m->ws_occ_w.reserve((size_t)L.rows * n_orb * sizeof(double)));
+            return s.m->ws_occ.reserve(L.ws_bytes);
+        });
     }
 
     // mode 1: the Fermi search of tbk_fermi on the resident eigenvalues; mode 0: N(value) from the probe kernel
-    int find_mu(const int32_t* mesh, int mode, double value, double* mu_out) {
-        std::vector<tbk_fermi_slab_t> f;
-        for (OccSlab& s : slabs)
-            f.push_back({s.m, s.d_E + (size_t)s.off0 * plane_pts * n_orb, s.p_count, s.p_count == mesh[0] ? s.p_count : s.p_count + 1});
-        return tbk_fermi_resident(f.data(), (int)f.size(), dim, mesh, n_orb, mode, value, mu_out);
-    }
+    int find_mu(const int32_t* mesh, int mode, double value, double* mu_out) { return tbk_fermi_resident(*this, fermi, mesh, mode, value, mu_out); }
 
     // timed: the kernel is booked on stage 0 of the slab's recorder (not for a caller whose stages are others)
     int weights(double mu, double* w_out, bool timed = true) {
-        for (OccSlab& s : slabs) {
+        for (size_t i = 0; i < slabs.size(); ++i) {
+            TetraSlab& s = slabs[i];
+            const OccPlan& L = occ[i].L;
             TBK_HIP(hipSetDevice(s.m->device));
             if (timed) s.ev->start(0);
-            TBK_CHECK(occ_launch_weights(s.m->stream, s.L, s.d_E, mu, (double)nk_total, s.m->ws_occ_w.as<double>()));
+            TBK_CHECK(occ_launch_weights(s.m->stream, L, s.d_E, mu, (double)nk_total, s.m->ws_occ_w.as<double>()));
             if (timed) s.ev->stop();
             if (w_out)
-                TBK_HIP(hipMemcpyAsync(w_out + (size_t)s.p_lo * plane_pts * n_orb, s.m->ws_occ_w.ptr, (size_t)s.L.rows * n_orb * sizeof(double),
+                TBK_HIP(hipMemcpyAsync(w_out + (size_t)s.p_lo * plane_pts * n_orb, s.m->ws_occ_w.ptr, (size_t)L.rows * n_orb * sizeof(double),
                                        hipMemcpyDeviceToHost, s.m->stream));
         }
         return TBK_OK;
     }
 
-    // f, eb and q of every slab (the weights are in ws_occ_w), left in s.host
+    // f, eb and q of every slab (the weights are in ws_occ_w), left in occ[i].host
     int sums() {
-        for (OccSlab& s : slabs) {
+        for (size_t i = 0; i < slabs.size(); ++i) {
+            TetraSlab& s = slabs[i];
+            const OccPlan& L = occ[i].L;
             tbk_model* m = s.m;
             TBK_HIP(hipSetDevice(m->device));
             char* ws = m->ws_occ.as<char>();
             const double* d_w = m->ws_occ_w.as<double>();
-            const double* d_E_own = s.d_E + (size_t)s.off0 * plane_pts * n_orb;
             s.ev->start(1);
-            TBK_CHECK(occ_launch_band(m->stream, s.L, d_w, d_E_own, (double)nk_total, ws));
+            TBK_CHECK(occ_launch_band(m->stream, L, d_w, s.own_E(n_orb), (double)nk_total, ws));
             s.ev->stop();
-            TBK_CHECK(occ_clear_buf(m->stream, s.L, ws));
+            TBK_CHECK(occ_clear_buf(m->stream, L, ws));
             // the chunk's eigenvalues (not used: the weights come from the eigenvalue path) go behind its eigenvectors
-            const int64_t nk = s.L.rows;
+            const int64_t nk = L.rows;
             const int64_t chunk = mesh_eigh_chunk(m, nk);
             const size_t u_doubles = (size_t)chunk * n_orb * n_orb * 2;
             TBK_CHECK(m->ws_pdos_u.reserve((u_doubles + (size_t)chunk * n_orb) * sizeof(double)));
             double* d_U = m->ws_pdos_u.as<double>();
-            const double* d_k_own = m->ws_k.as<double>() + (size_t)s.off0 * plane_pts * dim;
+            const double* d_k_own = m->ws_k.as<double>() + (size_t)s.head * dim;
             for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
                 const int64_t nkc = std::min(chunk, nk - c0);
                 TBK_CHECK(tbk_eigh_device(m, d_k_own + c0 * dim, nkc, 2, nullptr, d_U + u_doubles, d_U));
                 s.ev->start(2);
-                TBK_CHECK(occ_launch_contract(m->stream, s.L, d_U, d_w, c0, nkc, (double)nk_total, ws));
+                TBK_CHECK(occ_launch_contract(m->stream, L, d_U, d_w, c0, nkc, (double)nk_total, ws));
                 s.ev->stop();
             }
             s.ev->start(2);
-            TBK_CHECK(occ_launch_reduce(m->stream, s.L, ws));
+            TBK_CHECK(occ_launch_reduce(m->stream, L, ws));
             s.ev->stop();
             try {
-                s.host.resize(5 * (size_t)n_orb);
+                occ[i].host.resize(5 * (size_t)n_orb);
             } catch (...) {
                 tbk_set_error("cannot allocate the per-handle results");
                 return TBK_ERR_MEMORY;
             }
-            TBK_HIP(hipMemcpyAsync(s.host.data(), ws + s.L.off_host, s.L.host_bytes, hipMemcpyDeviceToHost, m->stream));
+            TBK_HIP(hipMemcpyAsync(occ[i].host.data(), ws + L.off_host, L.host_bytes, hipMemcpyDeviceToHost, m->stream));
         }
         return TBK_OK;
     }

@@ -377,13 +377,12 @@ extern "C" int tbk_tetra_weights_from_eigenvalues(int device, int dim, const int
     TBK_CHECK(tetra_check_device(device));
     OccPlan L;
     TBK_CHECK(occ_plan(dim, mesh, mesh[0], mesh[0], 0, n_orb, &L));
-    const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double);
-    DevBuf d_E, d_w;
-    TBK_CHECK(d_E.reserve(e_bytes));
-    TBK_CHECK(d_w.reserve(e_bytes));
-    TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
-    TBK_CHECK(occ_launch_weights(nullptr, L, d_E.as<double>(), energy, (double)nk, d_w.as<double>()));
-    TBK_HIP(hipMemcpy(w_out, d_w.ptr, e_bytes, hipMemcpyDeviceToHost));
+    TetraOwnedE d_E;
+    DevBuf d_w;
+    TBK_CHECK(d_E.upload(E, nk, n_orb));
+    TBK_CHECK(d_w.reserve(d_E.bytes));
+    TBK_CHECK(occ_launch_weights(nullptr, L, d_E.d(), energy, (double)nk, d_w.as<double>()));
+    TBK_HIP(hipMemcpy(w_out, d_w.ptr, d_E.bytes, hipMemcpyDeviceToHost));
     return TBK_OK;
 }
 
@@ -400,16 +399,16 @@ extern "C" int tbk_occupations_from_eigensystem(int device, int dim, const int32
     OccPlan L;
     TBK_CHECK(occ_plan(dim, mesh, mesh[0], mesh[0], 0, n_orb, &L));
     const int64_t chunk = k_chunk == 0 ? nk : std::min(k_chunk, nk);
-    const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double), u_per_k = (size_t)n_orb * (size_t)n_orb * 2;
-    DevBuf d_E, d_w, d_ws, d_U;
-    TBK_CHECK(d_E.reserve(e_bytes));
-    TBK_CHECK(d_w.reserve(e_bytes));
+    const size_t u_per_k = (size_t)n_orb * (size_t)n_orb * 2;
+    TetraOwnedE d_E;
+    DevBuf d_w, d_ws, d_U;
+    TBK_CHECK(d_E.upload(E, nk, n_orb));
+    TBK_CHECK(d_w.reserve(d_E.bytes));
     TBK_CHECK(d_ws.reserve(L.ws_bytes));
     TBK_CHECK(d_U.reserve((size_t)chunk * u_per_k * sizeof(double)));
     char* ws = d_ws.as<char>();
-    TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
-    TBK_CHECK(occ_launch_weights(nullptr, L, d_E.as<double>(), energy, (double)nk, d_w.as<double>()));
-    TBK_CHECK(occ_launch_band(nullptr, L, d_w.as<double>(), d_E.as<double>(), (double)nk, ws));
+    TBK_CHECK(occ_launch_weights(nullptr, L, d_E.d(), energy, (double)nk, d_w.as<double>()));
+    TBK_CHECK(occ_launch_band(nullptr, L, d_w.as<double>(), d_E.d(), (double)nk, ws));
     TBK_CHECK(occ_clear_buf(nullptr, L, ws));
     for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
         const int64_t nkc = std::min(chunk, nk - c0);
@@ -454,7 +453,7 @@ extern "C" int tbk_occupations_multi(tbk_model* const* handles, int n_handles, c
     TBK_CHECK(staged.sums());
     TBK_CHECK(staged.finish());
     OccTotals totals(staged.n_orb);
-    for (size_t i = 0; i < staged.slabs.size(); ++i) totals.add(staged.slabs[i].host, staged.n_orb, i == 0);
+    for (size_t i = 0; i < staged.occ.size(); ++i) totals.add(staged.occ[i].host, staged.n_orb, i == 0);
     totals.finish(staged.n_orb, (double)staged.nk_total, q_out, f_out, eb_out);
     return TBK_OK;
 }

@@ -32,7 +32,7 @@
 #include <cstring>
 #include <vector>
 
-#include "tbk_tetra.h"
+#include "tbk_tetra_staged.h"
 
 namespace {
 
@@ -357,47 +357,41 @@ extern "C" int tbk_pdos_from_eigensystem(int device, int dim, const int32_t* mes
     TBK_CHECK(tetra_check_device(device));
     PdosLaunch L;
     TBK_CHECK(pdos_plan(dim, mesh, mesh[0], mesh[0], n_orb, n_groups, n_e, &L));
-    const size_t e_bytes = (size_t)nk * (size_t)n_orb * sizeof(double), w_bytes = e_bytes * (size_t)n_groups;
     const size_t nos_bytes = (size_t)n_groups * (size_t)n_e * sizeof(double);
-    DevBuf d_E, d_W, d_ws, d_nos;
-    TBK_CHECK(d_E.reserve(e_bytes));
+    TetraOwnedE d_E;
+    DevBuf d_W, d_ws, d_nos;
+    TBK_CHECK(d_E.upload(E, nk, n_orb));
+    const size_t w_bytes = d_E.bytes * (size_t)n_groups;
     TBK_CHECK(d_W.reserve(w_bytes));
     TBK_CHECK(d_ws.reserve(L.ws_bytes));
     TBK_CHECK(d_nos.reserve(nos_bytes));
-    TBK_HIP(hipMemcpy(d_E.ptr, E, e_bytes, hipMemcpyHostToDevice));
     TBK_HIP(hipMemcpy(d_W.ptr, W, w_bytes, hipMemcpyHostToDevice));
     SpanRecorder untimed;
-    TBK_CHECK(pdos_launch(nullptr, dim, L, d_E.as<double>(), d_W.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk, d_ws.ptr,
+    TBK_CHECK(pdos_launch(nullptr, dim, L, d_E.d(), d_W.as<double>(), e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk, d_ws.ptr,
                           d_nos.as<double>(), untimed));
     TBK_HIP(hipMemcpy(nos_out, d_nos.ptr, nos_bytes, hipMemcpyDeviceToHost));
     return TBK_OK;
 }
 
-// Cells [p_lo, p_lo + p_count) along axis 0 of the mesh on one handle: E and W of those planes and of the one periodic neighbour
-// plane the last cells need stay in HBM (NK n_orb (1 + G) doubles); the eigenvectors exist one k chunk at a time.  nos_out[G][n_e]
-// receives this slab's share, already divided by S * NK of the whole mesh.
-int tbk_pdos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_count, const int32_t* group_offsets, const int32_t* group_orbitals,
-                  int n_groups, double e_min, double e_step, int64_t n_e, double* nos_out) {
-    TBK_ARG(m != nullptr, "model is NULL");
-    TBK_LOCK(m);
-    TBK_ARG(!m->kdotp, "a k.p model has no Brillouin zone");
-    int64_t nk_total = 0;
-    TBK_CHECK(tbk_dos_check(m->dim, mesh, e_step, n_e, nos_out, &nk_total));
-    TBK_ARG(std::isfinite(e_min), "e_min is not finite");
-    TBK_CHECK(tbk_pdos_check_groups(m->n_orb, group_offsets, group_orbitals, n_groups));
-    const int dim = m->dim, n_orb = m->n_orb;
-    const int64_t n0 = mesh[0];
-    TBK_ARG(p_lo >= 0 && p_count >= 1 && p_lo + p_count <= n0, "slab outside the mesh");
-    TBK_CHECK(tbk_eig_check_option(m));
-    TBK_HIP(hipSetDevice(m->device));
-    const int64_t planes = p_count == n0 ? n0 : p_count + 1;
-    const int64_t plane_pts = nk_total / n0, nk = planes * plane_pts;
-    PdosLaunch L;
-    TBK_CHECK(pdos_plan(dim, mesh, p_count, planes, n_orb, n_groups, n_e, &L));
+namespace {
 
-    std::vector<double> h_k;
-    TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, p_lo, planes, &h_k));
-    const size_t k_bytes = h_k.size() * sizeof(double);
+// what one slab keeps between its reservations and its launches
+struct PdosSlab {
+    PdosLaunch L;
+    double* d_W = nullptr;
+};
+
+// The reservations of one slab and, enqueued, E and W of its planes: the k list goes through ws_k, E stays in ws_out and W in
+// ws_pdos_w (NK n_orb (1 + G) doubles for the planes of the slab and the one periodic neighbour plane its last cells need); the
+// eigenvectors exist one k chunk at a time.  E comes from the eigenvector call, so that E and U belong together.
+int pdos_fill(const TetraStaged& t, TetraSlab& s, const int32_t* mesh, const int32_t* group_offsets, const int32_t* group_orbitals, int n_groups,
+              int64_t n_e, PdosSlab* out) {
+    tbk_model* m = s.m;
+    const int dim = t.dim, n_orb = t.n_orb;
+    const int64_t nk = s.planes * t.plane_pts;
+    TBK_CHECK(pdos_plan(dim, mesh, s.p_count, s.planes, n_orb, n_groups, n_e, &out->L));
+    TBK_CHECK(tbk_dos_mesh_klist(dim, mesh, s.p_lo, s.planes, &s.h_k));
+    const size_t k_bytes = s.h_k.size() * sizeof(double);
     const size_t off_bytes = dos_align256((size_t)(n_groups + 1) * sizeof(int32_t)), orb_bytes = (size_t)group_offsets[n_groups] * sizeof(int32_t);
     const size_t nos_bytes = (size_t)n_groups * (size_t)n_e * sizeof(double);
     // what stays for the whole call first, so that the chunk is chosen from what is left
@@ -405,49 +399,67 @@ int tbk_pdos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_cou
     TBK_CHECK(m->ws_out.reserve((size_t)nk * n_orb * sizeof(double)));
     TBK_CHECK(m->ws_pdos_w.reserve((size_t)nk * n_groups * n_orb * sizeof(double)));
     TBK_CHECK(m->ws_pdos_grp.reserve(off_bytes + orb_bytes));
-    TBK_CHECK(m->ws_dos.reserve(L.ws_bytes + dos_align256(nos_bytes)));
+    TBK_CHECK(m->ws_dos.reserve(out->L.ws_bytes + dos_align256(nos_bytes)));
     // k-points per chunk: TBK_OPT_K_CHUNK as given (chunks need not be whole planes nor whole k tiles), else what the eigenvector
     // call itself would take from the free memory -- its U chunk, chunk * n_orb^2 * 16 bytes, is the large term there
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nk, m->k_chunk > 0 ? m->k_chunk : choose_chunk(m, nk, true)));
+    const int64_t chunk = mesh_eigh_chunk(m, nk);
     TBK_CHECK(m->ws_pdos_u.reserve((size_t)chunk * n_orb * n_orb * 2 * sizeof(double)));
     const auto* d_off = m->ws_pdos_grp.as<int32_t>();
     const auto* d_orb = reinterpret_cast<const int32_t*>(m->ws_pdos_grp.as<char>() + off_bytes);
-    TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, h_k.data(), k_bytes, hipMemcpyHostToDevice, m->stream));
+    TBK_HIP(hipMemcpyAsync(m->ws_k.ptr, s.h_k.data(), k_bytes, hipMemcpyHostToDevice, m->stream));
     TBK_HIP(hipMemcpyAsync(m->ws_pdos_grp.ptr, group_offsets, (size_t)(n_groups + 1) * sizeof(int32_t), hipMemcpyHostToDevice, m->stream));
     TBK_HIP(hipMemcpyAsync(m->ws_pdos_grp.as<char>() + off_bytes, group_orbitals, orb_bytes, hipMemcpyHostToDevice, m->stream));
 
-    const int64_t n_chunks = (nk + chunk - 1) / chunk;
-    SpanRecorder timer(m->timing, m->stream);  // stages: 0 the weights kernel, 1 the accumulate kernel, 2 reduction + scan
     double* d_E = m->ws_out.as<double>();
-    double* d_W = m->ws_pdos_w.as<double>();
     double* d_U = m->ws_pdos_u.as<double>();
-    for (int64_t c = 0; c < n_chunks; ++c) {
-        const int64_t c0 = c * chunk, nkc = std::min(chunk, nk - c0);
+    out->d_W = m->ws_pdos_w.as<double>();
+    for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
+        const int64_t nkc = std::min(chunk, nk - c0);
         TBK_CHECK(tbk_eigh_device(m, m->ws_k.as<double>() + c0 * dim, nkc, 2, nullptr, d_E + c0 * n_orb, d_U));
-        timer.start(0);
+        s.ev->start(0);
         const int64_t threads = nkc * n_orb;
         hipLaunchKernelGGL(pdos_weights_kernel, dim3((unsigned)((threads + PDOS_THREADS - 1) / PDOS_THREADS)), dim3(PDOS_THREADS), 0, m->stream,
-                           reinterpret_cast<const double2*>(d_U), n_orb, nkc, n_groups, d_off, d_orb, d_W + (size_t)c0 * n_groups * n_orb);
+                           reinterpret_cast<const double2*>(d_U), n_orb, nkc, n_groups, d_off, d_orb, out->d_W + (size_t)c0 * n_groups * n_orb);
         TBK_HIP(hipGetLastError());
-        timer.stop();
+        s.ev->stop();
     }
-    TBK_CHECK(tbk_eigenval_check(m));  // synchronises; non-finite eigenvalues / no convergence end the call here, as in tbk_eigh
-
-    double* d_nos = reinterpret_cast<double*>(m->ws_dos.as<char>() + L.ws_bytes);
-    TBK_CHECK(pdos_launch(m->stream, dim, L, d_E, d_W, e_min, e_step, (double)(dim == 3 ? 6 : 2) * (double)nk_total, m->ws_dos.ptr, d_nos, timer));
-    TBK_HIP(hipMemcpyAsync(nos_out, d_nos, nos_bytes, hipMemcpyDeviceToHost, m->stream));
-    TBK_HIP(hipStreamSynchronize(m->stream));
-    TimedSums& sums = m->timed[TIMED_PDOS];
-    timer.collect(sums.ms);
-    if (timer.on) sums.calls += 1;
+    s.d_E = d_E;
     return TBK_OK;
+}
+
+}  // namespace
+
+// Cells [p_lo, p_lo + p_count) along axis 0 of the mesh on one handle, a one-slab case of the scaffold (tbk_tetra_staged.h) with
+// pdos_fill as its reservation step.  nos_out[G][n_e] -- the caller's, it outlives the wait -- receives this slab's share, already
+// divided by S * NK of the whole mesh.  The recorder's stages: 0 the weights kernel, 1 the accumulate kernel, 2 reduction + scan.
+int tbk_pdos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_count, const int32_t* group_offsets, const int32_t* group_orbitals,
+                  int n_groups, double e_min, double e_step, int64_t n_e, double* nos_out) {
+    TBK_ARG(m != nullptr, "model is NULL");
+    TBK_ARG(!m->kdotp, "a k.p model has no Brillouin zone");
+    int64_t nk_total = 0;
+    TBK_CHECK(tbk_dos_check(m->dim, mesh, e_step, n_e, nos_out, &nk_total));
+    TBK_ARG(std::isfinite(e_min), "e_min is not finite");
+    TBK_CHECK(tbk_pdos_check_groups(m->n_orb, group_offsets, group_orbitals, n_groups));
+    TBK_ARG(p_lo >= 0 && p_count >= 1 && p_lo + p_count <= mesh[0], "slab outside the mesh");
+    PdosSlab own;
+    TetraStaged staged;
+    TBK_CHECK(staged.make_slab(
+        m, mesh, DOS_MESH, p_lo, p_count,
+        [&](TetraSlab& s, size_t) { return pdos_fill(staged, s, mesh, group_offsets, group_orbitals, n_groups, n_e, &own); }, true));
+    const TetraSlab& s = staged.slabs[0];
+    const size_t nos_bytes = (size_t)n_groups * (size_t)n_e * sizeof(double);
+    double* d_nos = reinterpret_cast<double*>(m->ws_dos.as<char>() + own.L.ws_bytes);
+    TBK_CHECK(pdos_launch(m->stream, staged.dim, own.L, s.d_E, own.d_W, e_min, e_step, (double)(staged.dim == 3 ? 6 : 2) * (double)nk_total,
+                          m->ws_dos.ptr, d_nos, *s.ev));
+    TBK_HIP(hipMemcpyAsync(nos_out, d_nos, nos_bytes, hipMemcpyDeviceToHost, m->stream));
+    return staged.streams.book(TIMED_PDOS, true);
 }
 
 extern "C" int tbk_pdos(tbk_model* m, const int32_t* mesh, const int32_t* group_offsets, const int32_t* group_orbitals, int n_groups, double e_min,
                         double e_step, int64_t n_e, double* nos_out) {
     TBK_ARG(m != nullptr, "model is NULL");
     TBK_ARG(mesh != nullptr, "mesh / nos is NULL");
-    TBK_ARG(m->dim == 2 || m->dim == 3, "the density of states needs a 2- or 3-dimensional mesh");
+    TBK_ARG(m->dim == 2 || m->dim == 3, DOS_MESH);
     TBK_ARG(mesh[0] >= 1, "a mesh entry is < 1");
     return tbk_pdos_slab(m, mesh, 0, mesh[0], group_offsets, group_orbitals, n_groups, e_min, e_step, n_e, nos_out);
 }

@@ -3,7 +3,8 @@
 // susceptibilities) and tbk_berry.hip (the Berry flux).  Two objects, no kernels:
 //
 //   MeshStreams   the busy handles of one call with their span recorders: the mid-call check, the finish, the wait on every exit.
-//                 OccStaged (tbk_occ.h: weights, occupations, and through it tbk_dm.hip) holds one, ResidentMesh holds one.
+//                 TetraStaged (tbk_tetra_staged.h: every tetrahedron call, and through OccStaged tbk_dm.hip) holds one, ResidentMesh
+//                 holds one.
 //   ResidentMesh  the k list of the mesh and, per handle, the steps in the order a caller takes them: stage (the reservations of
 //                 k, E and U), the caller's own reservations, upload, the caller's own copies, fill, the caller's launches.
 #pragma once
@@ -78,16 +79,22 @@ struct MeshStreams {
         return TBK_OK;
     }
 
-    // check, then the kernel times of every handle booked on the family's row
-    int finish(TimedFamily family) {
-        TBK_CHECK(check());
+    // every handle waited for and its kernel times booked on the family's row: for a call that has enqueued no eigensystem since its
+    // last check().  timed_only: the row counts the calls made under TBK_OPT_TIMING alone (dos, pdos)
+    int book(TimedFamily family, bool timed_only = false) {
         for (Use& u : used) {
             TBK_HIP(hipSetDevice(u.m->device));
             TBK_HIP(hipStreamSynchronize(u.m->stream));
             u.ev.collect(u.m->timed[family].ms);
-            u.m->timed[family].calls += 1;
+            if (u.ev.on || !timed_only) u.m->timed[family].calls += 1;
         }
         return TBK_OK;
+    }
+
+    // check, then book
+    int finish(TimedFamily family) {
+        TBK_CHECK(check());
+        return book(family);
     }
 };
 

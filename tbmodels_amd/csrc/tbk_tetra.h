@@ -5,8 +5,8 @@
 // contribution and the split of its 64-bit sums; the two sorts of a simplex's corners; the scaled gaps of a simplex with the
 // number-of-states fraction n_T(E) and Bloechl's corner weights; the step from a work item to its cell's corner rows; and, on the
 // host (tbk_dos.hip), the mesh and device checks, the geometry, the cut of the items into workgroups and the handles of a call on
-// several devices with their slabs.  A kernel keeps what is its own: its loop over bins or probes, its loop over the simplices of
-// a cell, its accumulators.
+// several devices with their slabs (the call itself, slab by slab: tbk_tetra_staged.h).  A kernel keeps what is its own: its loop
+// over bins or probes, its loop over the simplices of a cell, its accumulators.
 #pragma once
 
 #include <algorithm>
@@ -304,6 +304,8 @@ __device__ __forceinline__ int64_t tetra_row(const DosGeom& g, int a0, int a1, i
 // ---- host (tbk_dos.hip) ------------------------------------------------------------------------------------------------------------
 inline size_t dos_align256(size_t x) { return (x + 255) / 256 * 256; }
 
+// the text of dos, pdos and the Fermi level for a wrong dim
+inline constexpr const char* DOS_MESH = "the density of states needs a 2- or 3-dimensional mesh";
 // dim in {2, 3} (`what`: the caller's text for a wrong one), mesh not NULL, every entry >= 1, *nk_total = points of the mesh < 2^31
 int tetra_check_mesh(int dim, const int32_t* mesh, const char* what, int64_t* nk_total);
 // ... and the grid checks every density-of-states entry point shares

@@ -3,7 +3,10 @@
 the tool for "does this build give the same bits as that one".  The inputs are the smallest that reach every kernel instantiation
 and every tile edge (two and three dimensions, every group tile of the projected kernel, grids that cross a bin tile, two probe
 launches, the second band block above 256 orbitals, tied corners and energies on corners), then the Model methods on silicon with
-one handle and with two.
+one handle and with two, and the smallest shapes that reach every edge of the cut of a mesh into slabs: meshes (2, 3, 2), (3, 4) and
+(1, 4, 3) on the caller's arrays, silicon on (3, 4, 4) with the device lists [0], [0, 0] (slabs of 2 + 1 planes, with neighbour planes)
+and [0, 0, 0, 0] (a short slab and an empty one), on (1, 4, 3) with [0, 0] (one busy handle that holds the whole axis), TBK_OPT_K_CHUNK
+0 and 5 for the calls that walk eigenvectors, and the density matrix and the susceptibility once on two handles.
 
     python tools/tetra_dump.py OUT.npz                  (TBK_LIBTBK=/path/to/libtbk.so selects another build of the library)
     python tools/tetra_dump.py --compare A.npz B.npz    exit status 1 unless every array agrees bit for bit (NaN == NaN)
@@ -75,6 +78,48 @@ def library_calls(out):
             out["occ_n%d_chunk%d" % (n, k_chunk)] = np.concatenate([q, f, eb])
 
 
+def occupation_calls(out, tag, mesh, eig, vec, chunks):
+    mesh_a, n = np.array(mesh, dtype=np.int32), eig.shape[-1]
+    for k_chunk in chunks:
+        q, f, eb = np.empty(n), np.empty(n), np.empty(n)
+        c_call("tbk_occupations_from_eigensystem", 0, len(mesh), mesh_a, n, eig, vec.view(np.float64), 0.125, k_chunk, q, f, eb)
+        out["%s/occ_chunk%d" % (tag, k_chunk)] = np.concatenate([q, f, eb])
+
+
+def slab_calls(out):
+    rng = np.random.default_rng(20261021)
+    for mesh in ((2, 3, 2), (3, 4), (1, 4, 3)):
+        for n in (2, 9):
+            nk, tag = int(np.prod(mesh)), "slab_" + "x".join(map(str, mesh)) + "_n%d" % n
+            eig = np.sort(rng.uniform(-1.0, 1.0, (nk, n)), axis=-1)
+            eigenvalue_calls(out, tag, mesh, eig, rng)
+            vec = np.ascontiguousarray(np.linalg.qr(rng.normal(size=(nk, n, n)) + 1j * rng.normal(size=(nk, n, n)))[0])
+            occupation_calls(out, tag, mesh, eig, vec, (0, 5))
+    g = np.load(os.path.join(ROOT, "tests", "golden", "silicon.npz"))
+    grid, groups = np.linspace(-8.0, 14.0, 65), [[0, 1], [2, 3, 4], [5, 6, 7]]
+    for mesh, lists in (((3, 4, 4), ([0], [0, 0], [0, 0, 0, 0])), ((1, 4, 3), ([0, 0],))):
+        for devices in lists:
+            model = tbmodels_amd.Model.from_packed(g["R"], g["hop"], pos=g["pos"], uc=g["uc"])
+            model.devices = devices
+            tag = "si_%s_on%d" % ("x".join(map(str, mesh)), len(devices))
+            out[tag + "/dos"] = model.dos(mesh, grid).nos
+            out[tag + "/edges"] = np.concatenate(model.band_edges(mesh))
+            out[tag + "/weights"] = model.tetra_weights(mesh, 3.0)
+            for filling in (4, 4.5):
+                out["%s/fermi%s" % (tag, filling)] = np.array(model.fermi_level(mesh, filling))
+            for k_chunk in (0, 5):
+                model.set_option(_lib.TBK_OPT_K_CHUNK, k_chunk)
+                out["%s/pdos_chunk%d" % (tag, k_chunk)] = model.pdos(mesh, grid, groups).nos
+                for key, how in (("energy", {"energy": 3.0}), ("electrons4", {"n_electrons": 4}), ("electrons4.5", {"n_electrons": 4.5})):
+                    occ = model.occupations(mesh, **how)
+                    out["%s/occ_%s_chunk%d" % (tag, key, k_chunk)] = np.concatenate([np.array(occ.mu), occ.orbital_occ, occ.band_occ, occ.band_energy])
+            if mesh == (3, 4, 4) and len(devices) == 2:  # (the two other callers of the staged occupations)
+                rho = model.density_matrix(mesh, n_electrons=4.5)
+                out[tag + "/dm"], out[tag + "/dm_mu"] = rho.rho, np.array(rho.mu, dtype=np.float64)
+                chi = model.susceptibility(mesh, [[1, 0, 0], [1, 2, 1]], temperature=0.1, n_electrons=4.5)
+                out[tag + "/chi"], out[tag + "/chi_mu"] = chi.chi, np.array(chi.mu, dtype=np.float64)
+
+
 def model_calls(out):
     g = np.load(os.path.join(ROOT, "tests", "golden", "silicon.npz"))
     single = tbmodels_amd.Model.from_packed(g["R"], g["hop"], pos=g["pos"], uc=g["uc"])
@@ -105,6 +150,7 @@ def main(argv):
     out = {}
     library_calls(out)
     model_calls(out)
+    slab_calls(out)
     np.savez(argv[0], **out)
     print("%s: %d arrays from %s" % (argv[0], len(out), _lib.LIB_PATH))
     return 0
