@@ -865,6 +865,49 @@ int tbk_berry_plan(int64_t nk, int n_orb, int n_sets, const int32_t* ranges, int
  * reset = 1 clears.  (The eigensolver stages are in tbk_get_timing.) */
 int tbk_berry_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
 
+/* ---- the Kubo optical conductivity sigma[a][c](omega + i eta) of a uniform k mesh (not in the reference) --------------------------
+ * Mesh, mu (mode, value), T, the frequencies omega[n_w] and eta are those of tbk_dynamic_susceptibility; dim is 2 or 3.  With E, U of
+ * tbk_eigh (convention 2) at the mesh points, D^a(k) = (1 / 2 pi) dH/dk_a = sum_R i R_a exp(2 pi i k.R) hop[R] + h.c. and
+ * V^a = U^H D^a U -- for convention 1 plus i (E_b - E_b') (U^H diag(pos[:, a]) U)[b][b'], pos[n_orb][dim] --
+ *
+ *     sigma[a][c](omega) = (i / NK) sum_k sum_{b b'} w V^a[b][b'] conj(V^c[b][b']) / (omega + i eta + E_b - E_b'),
+ *     w = -(f(E_b) - f(E_b')) / (E_b - E_b') >= 0, -f' on equal energies, evaluated as T F of tbk_susceptibility is.
+ *
+ * sigma_out: complex [n_w][dim][dim] in reduced coordinates, e = hbar = 1, per unit cell, no spin factor; mu_out: double [4] as for
+ * tbk_susceptibility.  The mesh is walked in chunks of eigenvectors; the velocity matrices never leave the device.  The bits of
+ * sigma(omega_j) do not depend on the other frequencies, their order or part_bytes: per-k partial sums are added in groups of 256
+ * consecutive mesh points in index order, the groups in index order, and handles take whole groups.  They do not depend on
+ * TBK_OPT_K_CHUNK or the number of handles either for sparse models and for dense models on the matrix-vector H(k) kernel (at most
+ * 256 padded packed slots, i.e. up to 22 orbitals, and fewer than 128 lattice vectors): their walk stays in chunks of at most 4096
+ * points, which all run one arithmetic.  For a larger dense model the eigensystem and D^a of a k-point are those of the H(k) kernel
+ * its chunk takes (matrix-vector up to 32 points, tiles split along K by the number of tiles above), which differ in the last bit
+ * with the chunk's length, as tbk_eigh's do; the sums add nothing to that.  part_bytes: the bytes the partial sums of one pass over
+ * the mesh may take (0: the library's budget, 1 GiB or a quarter of the device's free memory if that is less); tbk_optics_plan. */
+int tbk_optical_conductivity(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_w, const double* omega,
+                             double eta, int convention, const double* pos, int64_t part_bytes, double* mu_out, double* sigma_out);
+int tbk_optical_conductivity_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
+                                   int64_t n_w, const double* omega, double eta, int convention, const double* pos,
+                                   int64_t part_bytes, double* mu_out, double* sigma_out);
+/* The kernels on the caller's arrays (tests): E[nk][n_orb], U[nk][n_orb][n_orb] complex, D[nk][dim][n_orb][n_orb] complex (Hermitian),
+ * pos NULL or [n_orb][dim]; all nk points are one chunk. */
+int tbk_optics_from_eigensystem(int device, int dim, int n_orb, int64_t nk, const double* E, const double* U, const double* D,
+                                const double* pos, double mu, double T, int64_t n_w, const double* omega, double eta,
+                                int64_t part_bytes, double* sigma_out);
+/* How a call on nk mesh points and n_w frequencies is run: out[0] = the fused kernel's template (the orbitals padded to 16, 32 or 64;
+ * 0: above 64 orbitals, the products go through rocBLAS), out[1] = the frequencies per register chunk of the epilogue, out[2] = the
+ * frequencies per pass when the partial sums (16 dim^2 nk bytes per frequency) may take part_bytes (0: 1 GiB -- a call on a device
+ * with less than 4 GiB free takes a quarter of the free memory instead, so pass that figure to see its passes; whole register chunks
+ * when one fits; 0: not one frequency fits, the call returns TBK_ERR_MEMORY), out[3] = passes, every one of which walks the mesh
+ * again, out[4] = summation groups of 256 mesh points.  out: int64 [5]. */
+int tbk_optics_plan(int64_t nk, int n_orb, int dim, int64_t n_w, int64_t part_bytes, int64_t* out);
+/* ms[3] = the summed HIP-event time of the derivative H(k) contractions, the rotation into the band basis with its epilogue (the
+ * Fermi tables and the library route's products included), and the reductions in this handle's calls made while TBK_OPT_TIMING was
+ * on; calls = how many calls; reset = 1 clears.  (The eigensolver stages are in tbk_get_timing.) */
+int tbk_optics_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+/* D^a = (1 / 2 pi) dH/dk_a of nk k-points on device buffers, FULL, convention 2, axis in [0, dim): d_D [nk][n_orb][n_orb] complex.
+ * The H(k) kernels on derivative phase rows (-R_a sin, +R_a cos) with the staged operand; a test hook, enqueued only. */
+int tbk_hamilton_derivative_device(tbk_model* m, const double* d_k, int64_t nk, int axis, double* d_D);
+
 /* ---- k.p models (kdotp.py:51-100): H(k) = sum_p prod_d k_d^powers[p][d] * coeffs[p] ------- */
 int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, const int32_t* powers,
                      const double* coeffs, tbk_kdotp** out);

@@ -162,6 +162,15 @@ SIGNATURES = {
     "tbk_berry_flux_multi": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _vp]),
     "tbk_berry_plan": (_c_int, [_c_i64, _c_int, _c_int, _vp, ctypes.POINTER(_c_i64)]),
     "tbk_berry_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
+    "tbk_optical_conductivity": (_c_int, [_vp, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, ctypes.c_double, _c_int, _vp, _c_i64, _vp,
+                                          _vp]),
+    "tbk_optical_conductivity_multi": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, ctypes.c_double, _c_int, _vp,
+                                                _c_i64, _vp, _vp]),
+    "tbk_optics_from_eigensystem": (_c_int, [_c_int, _c_int, _c_int, _c_i64, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _c_i64, _vp,
+                                             ctypes.c_double, _c_i64, _vp]),
+    "tbk_optics_plan": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _c_i64, ctypes.POINTER(_c_i64)]),
+    "tbk_optics_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
+    "tbk_hamilton_derivative_device": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp]),
     "tbk_kdotp_create": (_c_int, [_c_int, _c_int, _c_int, _c_i64, _vp, _vp, _pp]),
     "tbk_kdotp_destroy": (None, [_vp]),
     "tbk_kdotp_hamilton": (_c_int, [_vp, _vp, _c_i64, _vp]),

@@ -58,6 +58,7 @@ Susceptibility = co.namedtuple("Susceptibility", ("mu", "q", "chi"))
 DynamicSusceptibility = co.namedtuple("DynamicSusceptibility", ("mu", "q", "omega", "chi"))
 OrbitalSusceptibility = co.namedtuple("OrbitalSusceptibility", ("mu", "q", "orbitals", "chi"))
 BerryFlux = co.namedtuple("BerryFlux", ("bands", "planes", "flux", "chern", "link_min"))
+OpticalConductivity = co.namedtuple("OpticalConductivity", ("mu", "omega", "sigma"))
 
 
 def _devices_from_env():
@@ -1856,14 +1857,47 @@ class Model:
         if q is None:
             raise ValueError("q must be an integer array of shape (NQ, {}), got None".format(self.dim))
         vectors = self._integer_vectors_argument(q, "q", "NQ")
-        t_value = self._positive_number_argument(temperature, "temperature")
-        mode, value = self._occupation_argument(name, energy, n_electrons)
-        if convention not in [1, 2]:
-            raise ValueError("Invalid value '{}' for 'convention': must be either '1' or '2'".format(convention))
+        t_value, mode, value = self._thermal_arguments(name, temperature, energy, n_electrons)
+        pos = self._convention_argument(convention)
         if not isinstance(matrix_elements, (bool, np.bool_)):
             raise ValueError("matrix_elements must be True or False, got {!r}".format(matrix_elements))
-        pos = np.ascontiguousarray(self.pos, dtype=np.float64) if convention == 1 else None
         return mesh_array, vectors, t_value, mode, value, pos
+
+    def _thermal_arguments(self, name, temperature, energy, n_electrons):
+        """``(temperature, mode, value)`` of the calls that weigh states with the Fermi function at one chemical potential."""
+        t_value = self._positive_number_argument(temperature, "temperature")
+        mode, value = self._occupation_argument(name, energy, n_electrons)
+        return t_value, mode, value
+
+    def _convention_argument(self, convention):
+        """The positions the kernels take for ``convention=1``, ``None`` for ``convention=2``, else ``ValueError``."""
+        if convention not in [1, 2]:
+            raise ValueError("Invalid value '{}' for 'convention': must be either '1' or '2'".format(convention))
+        return np.ascontiguousarray(self.pos, dtype=np.float64) if convention == 1 else None
+
+    @staticmethod
+    def _frequency_arguments(omega, eta):
+        """The checks of ``omega`` and ``eta`` that ``dynamic_susceptibility`` and ``optical_conductivity`` share: ``(omega float64
+        (NW,), eta)`` or ``ValueError``."""
+        if omega is None or isinstance(omega, (str, bytes)):
+            raise ValueError("omega must be a real number or a real array of shape (NW,), got {!r}".format(omega))
+        try:
+            frequencies = np.asarray(omega)
+        except (TypeError, ValueError):
+            raise ValueError("omega must be a real number or a real array of shape (NW,)") from None
+        if frequencies.dtype.kind not in "iuf":
+            raise ValueError("omega must hold real numbers, got dtype {}".format(frequencies.dtype))
+        if frequencies.ndim == 0:
+            frequencies = frequencies.reshape(1)
+        if frequencies.ndim != 1 or frequencies.shape[0] < 1:
+            raise ValueError("omega must have shape (NW,) with NW >= 1, got {}".format(frequencies.shape))
+        frequencies = np.ascontiguousarray(frequencies, dtype=np.float64)
+        if not np.all(np.isfinite(frequencies)):
+            raise ValueError("omega must be finite")
+        eta_value = Model._positive_number_argument(eta, "eta")
+        if not eta_value * eta_value > 0.0:
+            raise ValueError("eta must be finite and positive, got {!r} (its square underflows)".format(eta))
+        return frequencies, eta_value
 
     def dynamic_susceptibility(self, mesh, q, omega, *, eta, temperature, energy=None, n_electrons=None, matrix_elements=True, convention=2):
         """
@@ -1915,24 +1949,7 @@ class Model:
         """
         mesh_array, vectors, t_value, mode, value, pos = self._susceptibility_arguments("dynamic_susceptibility", mesh, q, temperature, energy,
                                                                                         n_electrons, matrix_elements, convention)
-        if omega is None or isinstance(omega, (str, bytes)):
-            raise ValueError("omega must be a real number or a real array of shape (NW,), got {!r}".format(omega))
-        try:
-            frequencies = np.asarray(omega)
-        except (TypeError, ValueError):
-            raise ValueError("omega must be a real number or a real array of shape (NW,)") from None
-        if frequencies.dtype.kind not in "iuf":
-            raise ValueError("omega must hold real numbers, got dtype {}".format(frequencies.dtype))
-        if frequencies.ndim == 0:
-            frequencies = frequencies.reshape(1)
-        if frequencies.ndim != 1 or frequencies.shape[0] < 1:
-            raise ValueError("omega must have shape (NW,) with NW >= 1, got {}".format(frequencies.shape))
-        frequencies = np.ascontiguousarray(frequencies, dtype=np.float64)
-        if not np.all(np.isfinite(frequencies)):
-            raise ValueError("omega must be finite")
-        eta_value = self._positive_number_argument(eta, "eta")
-        if not eta_value * eta_value > 0.0:
-            raise ValueError("eta must be finite and positive, got {!r} (its square underflows)".format(eta))
+        frequencies, eta_value = self._frequency_arguments(omega, eta)
         mu = np.empty(4, dtype=np.float64)
         chi = np.empty((vectors.shape[0], frequencies.shape[0]), dtype=np.complex128)
         with self._call_lock:
@@ -1945,6 +1962,79 @@ class Model:
                                                             _lib.ptr(chi))
             )
         return DynamicSusceptibility(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, frequencies, chi)
+
+    def optical_conductivity(self, mesh, omega, *, eta, temperature, energy=None, n_electrons=None, convention=2, cartesian=False):
+        """
+        The Kubo optical (current-current) conductivity ``sigma[a, c](omega + i eta)`` of a uniform k mesh, computed on the GPU
+        from the eigensystem and the derivative ``dH/dk`` of one chunk of the mesh at a time: the velocity matrices never leave
+        the device.  Not in the reference.
+
+        ``mesh``, ``temperature``, ``energy`` and ``n_electrons`` are those of :meth:`susceptibility`, ``omega`` and ``eta`` those
+        of :meth:`dynamic_susceptibility`, all with the same errors.  Returns the named tuple ``(mu, omega, sigma)``: ``mu`` is the
+        :class:`FermiLevel` tuple as in the susceptibilities (for ``n_electrons`` that of :meth:`fermi_level`, bit for bit),
+        ``omega`` is ``float64 (NW,)`` and ``sigma`` is ``complex128 (NW, dim, dim)``.
+
+        Definition.  Mesh points ``k = (i_1 / n_1, ..., i_dim / n_dim)``, ``E, U`` of ``eigh(k, convention=2)``; reduced
+        coordinates, ``e = hbar = 1``, per unit cell, no spin factor::
+
+            D^a(k)      = sum_R  i R_a exp(2 pi i k.R) hop[R]  +  h.c.          = (1 / 2 pi) dH/dk_a   (Hermitian, R = 0 drops out)
+            V^a(k)      = U^H D^a U                                             convention 2
+            V^a[b, b'] += i (E_b - E_b') (U^H diag(pos[:, a]) U)[b, b']         convention 1 only: the positions inside the cell
+            w[b, b']    = -(f(E_b) - f(E_b')) / (E_b - E_b')  >= 0              equal energies give -f'(E): the Drude term is included
+            sigma[a, c](omega) = (i / NK) sum_k sum_{b, b'} w[b, b'] V^a[b, b'] conj(V^c[b, b']) / (omega + i eta + E_b - E_b')
+
+        ``w`` is evaluated as :meth:`susceptibility` evaluates ``-F``: from the two Fermi tables and one ``expm1``, nothing cancels.
+        The convention-1 term is what differentiating the convention-1 Hamiltonian gives, rotated to the band basis.
+
+        ``cartesian=True`` needs ``uc`` (else ``ValueError``) and returns ``uc^T sigma uc / |det uc|`` per frequency: the tensor
+        along the Cartesian axes, per unit volume.  It is a host transform of the ``(NW, dim, dim)`` result.
+
+        Properties, pair by pair and therefore up to the rounding of ``V``.  (1) ``sigma[a, c](-omega) = conj sigma[a, c](omega)``.
+        (2) The Hermitian part ``(sigma + sigma^H) / 2`` over ``(a, c)`` is positive semidefinite at every ``omega``; in particular
+        ``Re sigma[a, a] >= 0``.  (3) With ``mu`` 746 ``T`` or more outside the spectrum every entry is ``+0``.  (4) The bits of
+        ``sigma(omega_j)`` do not depend on the other frequencies, their order or duplicates, on ``TBK_OPT_K_CHUNK``, on a second
+        call or on the number of ``devices``: per-k partial sums are added in fixed groups of 256 consecutive mesh points in index
+        order and the groups in index order, and devices take whole groups.  The chunk and the devices leave every bit alone for
+        sparse models and for dense models on the matrix-vector H(k) kernel (up to 22 orbitals and fewer than 128 lattice vectors),
+        whose walk stays in chunks of at most 4096 points; for a larger dense model chunks of up to 32 points and longer ones take
+        different H(k) kernels, which differ in the last bit as :meth:`eigh`'s do.  (5) For a gapped 2-D model at low ``T`` and small
+        ``eta``, ``2 pi sigma[0, 1](0)`` tends to the Chern number of the occupied bands as :meth:`berry_flux` returns it (QWZ model,
+        12 x 12 mesh, ``eta = 0.05``, ``T = 0.02``: within 4.1e-4).
+
+        Error bound of either component of an element for a given eigensystem and ``D^a``, with ``u = 2^-53``, ``G`` the largest
+        Frobenius norm of a ``V^a(k)``, ``W`` the bandwidth and ``P`` = 2 (3 for ``convention=1``) matrix products (DESIGN.md 27.4;
+        ``tools/optics_model.py`` ``tolerance``)::
+
+            |error| <= [ NK size^2 + 58 + (2 W + |omega|) / eta + 2 P (2 size + 3) sqrt(size) ] G^2 u / (2 T eta)
+
+        One-dimensional models raise ``ValueError``.  Dense and sparse models of every size :meth:`eigh` accepts; up to 64 orbitals
+        one fused kernel rotates and contracts, above the products go through rocBLAS.  The partial sums take
+        ``16 dim^2 NW NK`` bytes; when they do not fit 1 GiB (or a quarter of the free memory, if that is less) the frequencies go in passes and every
+        pass computes the eigensystem and the derivatives of the mesh again.  With several ``devices`` each takes a contiguous share
+        of the groups of mesh points with all frequencies.
+        """
+        mesh_array = self._mesh_argument(mesh, "optical_conductivity")
+        frequencies, eta_value = self._frequency_arguments(omega, eta)
+        t_value, mode, value = self._thermal_arguments("optical_conductivity", temperature, energy, n_electrons)
+        pos = self._convention_argument(convention)
+        if not isinstance(cartesian, (bool, np.bool_)):
+            raise ValueError("cartesian must be True or False, got {!r}".format(cartesian))
+        if cartesian and self.uc is None:
+            raise ValueError("cartesian=True needs the unit cell: the model has no uc")
+        mu = np.empty(4, dtype=np.float64)
+        sigma = np.empty((frequencies.shape[0], self.dim, self.dim), dtype=np.complex128)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_optical_conductivity_multi(handles, n_handles, _lib.ptr(mesh_array), mode, value, t_value, frequencies.shape[0],
+                                                          _lib.ptr(frequencies), eta_value, int(convention), _lib.ptr(pos), 0, _lib.ptr(mu),
+                                                          _lib.ptr(sigma))
+            )
+        if cartesian:
+            cell = np.asarray(self.uc, dtype=np.float64)
+            sigma = np.einsum("ia,wij,jc->wac", cell, sigma, cell) / abs(np.linalg.det(cell))
+        return OpticalConductivity(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), frequencies, sigma)
 
     def orbital_susceptibility(self, mesh, q, *, temperature, energy=None, n_electrons=None, orbitals=None, convention=2):
         """

@@ -528,6 +528,31 @@ int chunk_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, c
     return build_h(m, plan, mode, convention, d_k, d_pos_raw, one_k, d_H);
 }
 
+int tbk_chunk_dh(tbk_model* m, int axis, const double* d_k, int64_t nk, double* d_D) {
+    const int64_t chunk = choose_chunk(m, nk, false);
+    const size_t nn2 = (size_t)m->n_orb * m->n_orb * 2;
+    for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
+        const int64_t nkc = std::min(chunk, nk - c0);
+        const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), nkc, true, true);
+        TBK_CHECK(m->ws_phase.reserve((size_t)plan.row_doubles * sizeof(double)));
+        TBK_CHECK(tbk_launch_phase_derivative(m, plan.op, d_k + c0 * m->dim, nkc, plan.nk_pad, axis, m->ws_phase.as<double>()));
+        TBK_CHECK(build_h(m, plan, HK_FULL, 2, d_k + c0 * m->dim, nullptr, tbk_one_k_t(), d_D + (size_t)c0 * nn2));
+    }
+    return TBK_OK;
+}
+
+extern "C" int tbk_hamilton_derivative_device(tbk_model* m, const double* d_k, int64_t nk, int axis, double* d_D) {
+    TBK_ARG(m != nullptr, "model is NULL");
+    TBK_LOCK(m);
+    TBK_ARG(!m->kdotp, "k.p models have no lattice vectors to differentiate");
+    TBK_ARG(axis >= 0 && axis < m->dim, "axis must be 0 ... dim - 1");
+    TBK_ARG(nk >= 0, "nk < 0");
+    if (nk == 0) return TBK_OK;
+    TBK_ARG(d_k && d_D, "k / D is NULL");
+    TBK_HIP(hipSetDevice(m->device));
+    return tbk_chunk_dh(m, axis, d_k, nk, d_D);
+}
+
 // FULL H(k) of nk k-points on the device, chunk by chunk (the caller holds the lock and has checked the arguments)
 static int hamilton_chunks(tbk_model* m, const double* d_k, int64_t nk, int convention, const double* d_pos, const tbk_one_k_t& one_k, double* d_H) {
     const int64_t chunk = choose_chunk(m, nk, false);

@@ -65,12 +65,13 @@
 #include <vector>
 
 #include "tbk_occ.h"
+#include "tbk_pair.h"
 
 namespace {
 
 typedef double chi_d4 __attribute__((ext_vector_type(4)));
 
-constexpr int CHI_THREADS = 256;
+constexpr int CHI_THREADS = PAIR_THREADS;
 constexpr int64_t CHI_MAX_BATCH = 4096;                 // vectors per launch (grid z), at most
 constexpr size_t CHI_PART_BUDGET = size_t(256) << 20;   // the partials of one batch, at most
 constexpr int64_t CHI_MAX_NK = int64_t(1) << 23;          // one grid column per k-point, 256 threads each
@@ -155,23 +156,6 @@ __device__ __forceinline__ int64_t chi_shifted(const ChiMesh& g, int64_t k, cons
     return (j0 * g.n[1] + j1) * g.n[2] + j2;
 }
 
-// f(lo) (1 - f(hi)) h((lo - hi) / T) >= 0 of one pair of states: -T F
-__device__ __forceinline__ double chi_pair_weight(double ea, double fa, double ga, double eb, double fb, double gb, double inv_t) {
-    const bool a_low = ea <= eb;
-    const double lo = a_low ? ea : eb, hi = a_low ? eb : ea;
-    const double y = (lo - hi) * inv_t;
-    const double h = y < 0.0 ? expm1(y) / y : 1.0;  // (-inf: 0)
-    return (a_low ? fa : fb) * (a_low ? gb : ga) * h;
-}
-
-// g = f(a) - f(b) of one pair of states, |g| <= 1: +-f(lo) (1 - f(hi)) (-expm1((lo - hi) / T)), + where a <= b; a zero for a == b
-__device__ __forceinline__ double chi_pair_difference(double ea, double fa, double ga, double eb, double fb, double gb, double inv_t) {
-    const bool a_low = ea <= eb;
-    const double lo = a_low ? ea : eb, hi = a_low ? eb : ea;
-    const double v = (a_low ? fa : fb) * (a_low ? gb : ga) * (-expm1((lo - hi) * inv_t));
-    return a_low ? v : -v;
-}
-
 // one pair of states at one frequency: re += t x, im -= t eta with t = p / (x^2 + eta^2), the multiply-adds fused as written
 __device__ __forceinline__ void chi_dyn_term(double p, double delta, double omega, double eta, double eta2, double& re, double& im) {
     const double x = delta + omega;
@@ -179,26 +163,6 @@ __device__ __forceinline__ void chi_dyn_term(double p, double delta, double omeg
     const double t = p * r;
     re = fma(t, x, re);
     im = fma(-t, eta, im);
-}
-
-// all 64 lanes, the same tree whatever the values
-__device__ __forceinline__ double chi_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// f and 1 - f of one state from ONE exponential, t = exp(-|E - mu| / T): (t, 1) / (1 + t) above mu, (1, t) / (1 + t) at and below
-// it -- 1 - f(x) = f(2 mu - x) at the mirrored distance, which is -(E - mu) without a rounding
-__global__ void __launch_bounds__(CHI_THREADS) chi_fermi_kernel(const double* __restrict__ E, int64_t items, double mu, double T,
-                                                                double* __restrict__ tab) {
-    const int64_t i = (int64_t)blockIdx.x * CHI_THREADS + threadIdx.x;
-    if (i >= items) return;
-    const double d = E[i] - mu;
-    const double t = exp(-fabs(d) / T);
-    const double small = t / (1.0 + t), big = 1.0 / (1.0 + t);
-    tab[i] = d > 0.0 ? small : big;
-    tab[items + i] = d < 0.0 ? small : big;
 }
 
 // BT tiles of 16 along each side of the workgroup's block of M: 4 (one k-point per workgroup, wave t owns tile row t) or 1 (n <= 16:
@@ -988,12 +952,7 @@ int chi_check(double T, int64_t n_q, const int64_t* q, const double* chi_out, in
 }
 
 int chi_check_frequencies(int64_t n_w, const double* omega, double eta) {
-    TBK_ARG(n_w >= 1, "n_w < 1");
-    TBK_ARG(n_w <= CHI_MAX_NW, "the dynamic susceptibility takes up to 2^23 frequencies per call");
-    TBK_ARG(omega != nullptr, "omega is NULL");
-    for (int64_t j = 0; j < n_w; ++j) TBK_ARG(std::isfinite(omega[j]), "a frequency is not finite");
-    TBK_ARG(std::isfinite(eta) && eta > 0.0 && eta * eta > 0.0, "eta is not finite or not positive (or its square underflows)");
-    return TBK_OK;
+    return pair_check_frequencies(n_w, CHI_MAX_NW, omega, eta, "the dynamic susceptibility takes up to 2^23 frequencies per call");
 }
 
 constexpr const char* CHI_FAMILY = "the susceptibility";

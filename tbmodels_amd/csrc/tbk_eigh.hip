@@ -358,8 +358,10 @@ int tbk_eigh_check_arguments(int64_t nk, int convention, const double* pos) {
     return TBK_OK;
 }
 
-extern "C" int tbk_eigh_device(tbk_model* m, const double* d_k, int64_t nk, int convention, const double* d_pos, double* d_E,
-                               double* d_U) {
+// tbk_eigh_device; caller_rows: H(k) of every chunk from finished phase rows on the classical paths (tbk_hk_plan), so that a k-point's
+// bits do not depend on the chunk being one point long (which otherwise takes the one-launch kernel)
+int tbk_eigh_device_rows(tbk_model* m, const double* d_k, int64_t nk, int convention, const double* d_pos, double* d_E, double* d_U,
+                         bool caller_rows) {
     TBK_CHECK(tbk_eigh_check_arguments(nk, convention, d_pos));
     TBK_ARG(m != nullptr, "model is NULL");
     TBK_LOCK(m);
@@ -378,13 +380,18 @@ extern "C" int tbk_eigh_device(tbk_model* m, const double* d_k, int64_t nk, int 
     }
     for (int64_t c0 = 0; c0 < nk; c0 += chunk) {
         const int64_t nkc = std::min(chunk, nk - c0);
-        const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), nkc, false);
+        const tbk_hk_plan_t plan = tbk_hk_plan(m, tbk_staged_operand(m), nkc, caller_rows, caller_rows);
         double* Uc = d_U + (size_t)c0 * nn2;
         double* Ec = d_E + (size_t)c0 * n;
         TBK_CHECK(chunk_h(m, plan, HK_FULL, convention, d_k + c0 * m->dim, d_pos, tbk_one_k_t(), Uc));
         TBK_CHECK(own ? eigh_jacobi(m, Uc, nkc, Ec) : eigh_rocsolver(m, Uc, nkc, Ec));
     }
     return TBK_OK;
+}
+
+extern "C" int tbk_eigh_device(tbk_model* m, const double* d_k, int64_t nk, int convention, const double* d_pos, double* d_E,
+                               double* d_U) {
+    return tbk_eigh_device_rows(m, d_k, nk, convention, d_pos, d_E, d_U, false);
 }
 
 // Host buffers: k (and pos) go up through the pinned staging buffer when they fit, E and U come down in pieces of at most

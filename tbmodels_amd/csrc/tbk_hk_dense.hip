@@ -1245,7 +1245,23 @@ void gemv_plan(const tbk_model* m, int64_t k2, int64_t nk, int* slices_out, size
 //   workspace, hk_finish_kernel adds them in fixed order.  Measured at N_orb = 64, N_R = 4096: one k-point 1056 -> 163 us
 //   (before the matrix-vector path), 1000 k-points 2137 -> 1264 us.  (Just enough splits for ONE full round plus a
 //   sub-split tail was slower up to 500 k-points: three more launches on a 0.2 ms kernel.)
-tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, const tbk_operand_t& op, int64_t nk, bool caller_rows) {
+// classical (with caller_rows): a caller whose rows are not the phases themselves (the derivative rows of tbk_chunk_dh) keeps to the
+// paths that read plain rows A[K2][nk_pad] -- CSR, GEMV, TILES -- whatever the chunk's length: the Strassen row blocks are sums of
+// phases of different k-points and lattice vectors, which such a caller does not make.
+// a SMALL model: the matrix-vector path takes its chunks of up to GEMV_SMALL_MAX_NK k-points
+constexpr int64_t GEMV_SMALL_MAX_NK = 4096;
+static bool gemv_small_model(const tbk_model* m, const tbk_operand_t& op) { return m->ncol_pad <= 256 && op.k2 < 16 * TBK_BK; }
+
+// The longest chunk up to which a classical caller-rows plan of the staged operand runs the same arithmetic per k-point whatever the
+// chunk's length: any length for sparse models (the CSR kernel walks an element's records in one order), GEMV_SMALL_MAX_NK for a small
+// dense model (the matrix-vector kernel: its K slices are a function of the model alone), 0 for a larger dense model -- there chunks
+// of up to 32 points take the matrix-vector kernel and longer ones the tiles, whose K splits follow the number of tiles.
+int64_t tbk_hk_stable_chunk(const tbk_model* m) {
+    if (m->sparse) return INT64_MAX;
+    return !m->kdotp && gemv_small_model(m, tbk_staged_operand(m)) ? GEMV_SMALL_MAX_NK : 0;
+}
+
+tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, const tbk_operand_t& op, int64_t nk, bool caller_rows, bool classical) {
     tbk_hk_plan_t p;
     p.op = op;
     p.nk = nk;
@@ -1256,7 +1272,7 @@ tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, const tbk_operand_t& op, int64_t n
         p.path = HK_PATH_CSR;
         return p;
     }
-    if (nk >= 1 && op.k2 > 0 && (nk <= 32 || (nk <= 4096 && m->ncol_pad <= 256 && op.k2 < 16 * TBK_BK))) {
+    if (nk >= 1 && op.k2 > 0 && (nk <= 32 || (nk <= GEMV_SMALL_MAX_NK && gemv_small_model(m, op)))) {
         gemv_plan(m, op.k2, nk, &p.splits, &p.lds);
         if (!caller_rows && !m->kdotp && op.d_R != nullptr && gemv_strip_rows(op.k2, p.splits) * gemv_nkv(nk) <= (int64_t)(p.lds / 32))
             p.rows = HK_ROWS_NONE;
@@ -1265,7 +1281,7 @@ tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, const tbk_operand_t& op, int64_t n
         return p;
     }
     const int64_t tiles = (nk + TBK_BM - 1) / TBK_BM * (m->ncol_pad / TBK_BNP);
-    if (m->strassen && m->d_Bs != nullptr && op.d_B == m->d_B && !m->kdotp && op.n_r_pad >= TBK_STRASSEN_MIN_NR &&
+    if (!classical && m->strassen && m->d_Bs != nullptr && op.d_B == m->d_B && !m->kdotp && op.n_r_pad >= TBK_STRASSEN_MIN_NR &&
         nk >= TBK_STRASSEN_MIN_NK && tiles >= 2 * m->n_cu) {
         if (m->strassen_levels >= 2 && !m->bs2_skipped && nk >= TBK_STRASSEN2_MIN_NK && op.k2 % (4 * TBK_BK) == 0 &&
             m->ncol_pad % (4 * TBK_BNP) == 0) {

@@ -178,11 +178,11 @@ struct SpanRecorder {
 };
 
 // The sums the mesh calls book their kernel times on, one row per family (tbk_dos_timing, tbk_pdos_timing, tbk_fermi_timing,
-// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing, tbk_surface_timing, tbk_transmission_timing, tbk_device_green_timing, tbk_device_current_timing, tbk_transmission_ensemble_timing, tbk_transmission_channels_timing: what each counts differs and is
+// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing, tbk_surface_timing, tbk_transmission_timing, tbk_device_green_timing, tbk_device_current_timing, tbk_transmission_ensemble_timing, tbk_transmission_channels_timing, tbk_optics_timing: what each counts differs and is
 // listed in DESIGN.md section 10)
-enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_SURFACE, TIMED_TRANSMISSION, TIMED_DEVICE_GREEN, TIMED_DEVICE_CURRENT, TIMED_TRANSMISSION_ENSEMBLE, TIMED_TRANSMISSION_CHANNELS, TIMED_COUNT };
+enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_SURFACE, TIMED_TRANSMISSION, TIMED_DEVICE_GREEN, TIMED_DEVICE_CURRENT, TIMED_TRANSMISSION_ENSEMBLE, TIMED_TRANSMISSION_CHANNELS, TIMED_OPTICS, TIMED_COUNT };
 struct TimedSums {
-    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green, the dressed green, surface, transmission, the device green, the device current, the ensemble and the channels three)
+    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green, the dressed green, surface, transmission, the device green, the device current, the ensemble, the channels and the optical conductivity three)
     int64_t calls = 0;
     int64_t passes = 0;  // fermi: the passes of its searches
 };
@@ -489,7 +489,11 @@ struct tbk_hk_plan_t {
 };
 // A function of the model's options and packed columns, the operand (the staged one, or a folded one: only the staged one
 // has Strassen blocks) and nk.  caller_rows: the caller makes the phase rows whatever the path (never HK_ROWS_NONE).
-tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, const tbk_operand_t& op, int64_t nk, bool caller_rows);
+// classical (only with caller_rows): never a Strassen path, so that the rows are A[K2][nk_pad] whatever nk (tbk_hk_dense.hip).
+tbk_hk_plan_t tbk_hk_plan(const tbk_model* m, const tbk_operand_t& op, int64_t nk, bool caller_rows, bool classical = false);
+// tbk_hk_dense.hip: chunks of up to this many k-points give a k-point the same bits under a classical caller-rows plan whatever their
+// length (INT64_MAX: any; 0: the model is too large for that -- tbk_optics.hip caps its walk with it)
+int64_t tbk_hk_stable_chunk(const tbk_model* m);
 
 // ONE k-point on host buffers (tbk_hamilton / tbk_eigenval) whose plan is HK_ROWS_NONE: k goes into the kernel arguments (no
 // upload) and the H(k) kernel forms the convention-1 phases itself from the raw positions.  Those two entry points decide
@@ -506,6 +510,9 @@ int64_t choose_chunk(tbk_model* m, int64_t nk, bool with_eig);
 int fill_rows(tbk_model* m, const tbk_hk_plan_t& plan, const double* d_k);
 int chunk_h(tbk_model* m, const tbk_hk_plan_t& plan, int mode, int convention, const double* d_k, const double* d_pos_raw,
             const tbk_one_k_t& one_k, double* d_H);
+// D^a = (1 / 2 pi) dH/dk_a of nk k-points, FULL, convention 2, in pieces of choose_chunk: the derivative rows (tbk_phase.hip) in
+// ws_phase, then the contraction of a classical caller-rows plan with the staged operand (tbk_optics.hip; tbk_hamilton_derivative_device)
+int tbk_chunk_dh(tbk_model* m, int axis, const double* d_k, int64_t nk, double* d_D);
 
 // tbk_api.hip: tbk_eigenval_device_hint with a hook (NULL: none).  The chunk pipeline calls it whenever the eigenvalues of rows
 // [c0, c0 + nkc) of the call have been enqueued, with an event recorded behind them (tbk_comm.hip); the rocSOLVER path never does.
@@ -516,6 +523,7 @@ int tbk_eigenval_device_hooked(tbk_model* m, const double* d_k, const double* h_
 int tbk_launch_phase_strassen(tbk_model* m, const tbk_operand_t& op, const double* d_k, int64_t nk, double* d_As);
 int tbk_launch_phase_strassen2(tbk_model* m, const tbk_operand_t& op, const double* d_k, int64_t nk, double* d_As2);
 int tbk_launch_phase(tbk_model* m, const tbk_operand_t& op, const double* d_k, int64_t nk, int64_t nk_pad, double* d_A);
+int tbk_launch_phase_derivative(tbk_model* m, const tbk_operand_t& op, const double* d_k, int64_t nk, int64_t nk_pad, int axis, double* d_A);
 int tbk_launch_orbital_phases(tbk_model* m, const double* d_k, const double* d_pos, int64_t nk, double* d_orb);
 int tbk_launch_monomials(hipStream_t s, const int32_t* d_powers, int dim, int64_t n_p,
                          int64_t n_p_pad, const double* d_k, int64_t nk, int64_t nk_pad,
@@ -551,6 +559,10 @@ int tbk_eig_batched(tbk_model* m, double* d_H, int64_t nk, double* d_E);    // f
 
 // tbk_eigh.hip: the checks of the eigh entry points that need no model (convention, pos, nk)
 int tbk_eigh_check_arguments(int64_t nk, int convention, const double* pos);
+// tbk_eigh_device with the choice of how H(k) is built: caller_rows = true keeps every chunk on the paths that read finished phase
+// rows (tbk_hk_plan's caller_rows and classical), whatever its length -- tbk_optics.hip, whose sums must not know the chunk
+int tbk_eigh_device_rows(tbk_model* m, const double* d_k, int64_t nk, int convention, const double* d_pos, double* d_E, double* d_U,
+                         bool caller_rows);
 
 // ------------------------------------------------------------------------------------------------
 // The eigensolver's plan (tbk_eig_plan.hip).  How the matrices of one eigenvalue CALL are reduced and solved: tbk_eig_plan is

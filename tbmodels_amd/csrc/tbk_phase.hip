@@ -36,6 +36,30 @@ phase_rows_kernel(const double* __restrict__ k, const int32_t* __restrict__ R, i
     A[(2 * r + 1) * nk_pad + kidx] = s;
 }
 
+// The rows of D^a = (1 / 2 pi) dH/dk_a (tbk_optics.hip): H = A B is real-linear in the phase rows, so the derivative is A' B with the same
+// operand and A'[2r][k] = -R_a sin(2 pi k.R_r), A'[2r + 1][k] = +R_a cos(2 pi k.R_r) -- the arithmetic and the argument reduction of
+// phase_rows_kernel, one more multiply.  Rows of R_a = 0 (R = 0 among them) and the padding are zeros.
+__global__ void __launch_bounds__(256)
+phase_rows_derivative_kernel(const double* __restrict__ k, const int32_t* __restrict__ R, int dim, int axis, int64_t nk,
+                             int64_t nk_pad, int64_t n_r, double* __restrict__ A) {
+    const int64_t kidx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t r = blockIdx.y;
+    if (kidx >= nk_pad) return;
+    double c = 0.0, s = 0.0;
+    if (kidx < nk && r < n_r) {
+        double dot = 0.0;
+        for (int d = 0; d < dim; ++d)
+            dot = fma(k[kidx * dim + d], (double)R[r * dim + d], dot);
+        sincospi(2.0 * dot, &s, &c);
+        const double ra = (double)R[r * dim + axis];
+        const double ds = -(ra * s), dc = ra * c;
+        c = ds;
+        s = dc;
+    }
+    A[(2 * r) * nk_pad + kidx] = c;
+    A[(2 * r + 1) * nk_pad + kidx] = s;
+}
+
 // The table of the left operands of one Strassen level (below), applied to quadrants v[k half][K half]
 __device__ __forceinline__ void strassen_left(const double (&v)[2][2], double (&out)[7]) {
     out[0] = v[0][0] + v[1][1];
@@ -187,6 +211,15 @@ int tbk_launch_phase(tbk_model* m, const tbk_operand_t& op, const double* d_k, i
     dim3 grid((unsigned)((nk_pad + 255) / 256), (unsigned)op.n_r_pad);
     hipLaunchKernelGGL(phase_rows_kernel, grid, dim3(256), 0, m->stream, d_k, op.d_R, op.dim, nk,
                        nk_pad, op.n_r, d_A);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+int tbk_launch_phase_derivative(tbk_model* m, const tbk_operand_t& op, const double* d_k, int64_t nk, int64_t nk_pad, int axis, double* d_A) {
+    if (op.n_r_pad == 0 || nk_pad == 0) return TBK_OK;
+    StageTimer t(m, TBK_T_PHASE);
+    dim3 grid((unsigned)((nk_pad + 255) / 256), (unsigned)op.n_r_pad);
+    hipLaunchKernelGGL(phase_rows_derivative_kernel, grid, dim3(256), 0, m->stream, d_k, op.d_R, op.dim, axis, nk, nk_pad, op.n_r, d_A);
     TBK_HIP(hipGetLastError());
     return TBK_OK;
 }
