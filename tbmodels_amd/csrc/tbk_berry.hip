@@ -8,7 +8,7 @@
 //   F_ab(k)    = a_a(k) + a_b(k+e_a) - a_a(k+e_b) - a_b(k)             wrapping 64-bit arithmetic, read as int64
 //   flux_ab(k) = (double)F_ab(k) 2 pi 2^-64,   C_ab(i_c) = (sum of F_ab over the plane) / 2^64, an integer
 //
-//   berry_link_kernel<BT, false>  M as four real products on v_mfma_f64_16x16x4_f64 with chi_overlap_kernel's staging: panels of 16
+//   berry_link_kernel<BT, false>  M as four real products on v_mfma_f64_16x16x4_f64 by zpanel_overlap (tbk_zmfma.h): panels of 16
 //                       orbitals through LDS, orbital-major planes Ur, Ui (bands of the set at k) and Re, Im of D U' (at k+e_d),
 //                       padded with zeros to the tile; a panel row of the set is the contiguous segment U[k][i][lo:hi], D is applied
 //                       while staging.  M is never stored to global memory: the accumulators go to an LDS tile (over the planes,
@@ -39,10 +39,9 @@
 
 #include "tbk_occ.h"  // OCC_MESH
 #include "tbk_resident.h"
+#include "tbk_zmfma.h"
 
 namespace {
-
-typedef double berry_d4 __attribute__((ext_vector_type(4)));
 
 constexpr int BERRY_THREADS = 256;
 constexpr int BERRY_MAX_SETS = 16;
@@ -82,7 +81,7 @@ BerrySet berry_plan_set(int64_t nk, int lo, int hi) {
 }
 
 // LDS of one workgroup of berry_link_kernel: the planes, and over them the tile(s)
-constexpr int berry_plane_stride(int bt) { return bt == 1 ? 18 : 82; }
+constexpr int berry_plane_stride(int bt) { return bt == 1 ? ZPanel<1>::S : ZPanel<4>::S; }
 constexpr int berry_tile_stride(int bt) { return 16 * bt + 1; }
 constexpr size_t berry_lds_bytes(int bt, bool store) {
     const size_t kpw = bt == 1 ? 4 : 1;
@@ -137,10 +136,9 @@ __global__ void __launch_bounds__(BERRY_THREADS) berry_link_kernel(const double2
                                                                    const double2* __restrict__ D, int64_t k0, int64_t nkc, int64_t l0,
                                                                    int64_t n_links, double2* __restrict__ Mws, double2* __restrict__ L_out,
                                                                    uint64_t* __restrict__ words, double* __restrict__ absL) {
-    constexpr int RB = 16 * BT;               // rows (and columns) of the block
-    constexpr int KPW = BT == 1 ? 4 : 1;      // links per workgroup
-    constexpr int TEAM = BERRY_THREADS / KPW; // threads that work on one link
-    constexpr int S = berry_plane_stride(BT); // doubles between the orbital rows of a plane (chi_overlap_kernel's)
+    using Geo = ZPanel<BT>;  // (tbk_zmfma.h; an item is a link)
+    constexpr int RB = Geo::RB, KPW = Geo::KPW, TEAM = Geo::TEAM;
+    static_assert(BERRY_THREADS == Geo::THREADS, "the panel's workgroup");
     constexpr int TS = berry_tile_stride(BT); // complex numbers between the rows of the tile: a wave walks along a row
     extern __shared__ double2 berry_lds[];
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -155,68 +153,15 @@ __global__ void __launch_bounds__(BERRY_THREADS) berry_link_kernel(const double2
     const double2* Uk = U + (size_t)k * n * n + lo;
     const double2* Up = U + (size_t)kp * n * n + lo;
     const double2* Dd = D ? D + (size_t)d * n : nullptr;
-    double(*pl)[16][S] = reinterpret_cast<double(*)[16][S]>(reinterpret_cast<double*>(berry_lds) + (size_t)team * 4 * 16 * S);
+    double* pl = reinterpret_cast<double*>(berry_lds) + (size_t)team * 4 * 16 * Geo::S;  // the team's four planes
     const int ti = BT == 1 ? 0 : wave;                      // the wave's tile row
     const bool row_live = valid && bi * RB + ti * 16 < m;   // (wave-uniform)
-    berry_d4 accr[BT], acci[BT];
-#pragma unroll
-    for (int tj = 0; tj < BT; ++tj) accr[tj] = acci[tj] = berry_d4{0.0, 0.0, 0.0, 0.0};
-    const int sc = tt % RB, so0 = tt / RB;  // the band (column of the panel) and the first orbital row this thread stages
-    const int col_a = bi * RB + sc, col_b = bj * RB + sc;
-    for (int i0 = 0; i0 < n; i0 += 16) {
-        __syncthreads();  // the previous panel has been read
-#pragma unroll
-        for (int o = so0; o < 16; o += TEAM / RB) {
-            const int i = i0 + o;
-            const bool i_in = valid && i < n;
-            double2 ua = make_double2(0.0, 0.0), ub = ua;
-            if (i_in && col_a < m) ua = Uk[(size_t)i * n + col_a];
-            if (i_in && col_b < m) {
-                ub = Up[(size_t)i * n + col_b];
-                if (Dd) {
-                    const double2 dv = Dd[i];
-                    ub = make_double2(dv.x * ub.x - dv.y * ub.y, dv.x * ub.y + dv.y * ub.x);
-                }
-            }
-            pl[0][o][sc] = ua.x;
-            pl[1][o][sc] = ua.y;
-            pl[2][o][sc] = ub.x;
-            pl[3][o][sc] = ub.y;
-        }
-        __syncthreads();
-        if (row_live) {
-#pragma unroll 1
-            for (int q4 = 0; q4 < 4; ++q4) {  // (not unrolled: dm_project_kernel's note on registers)
-                const int oq = 4 * q4 + (lane >> 4);
-                const double ar = pl[0][oq][ti * 16 + (lane & 15)], ai = pl[1][oq][ti * 16 + (lane & 15)];
-#pragma unroll
-                for (int tj = 0; tj < BT; ++tj) {
-                    if (bj * RB + tj * 16 < m) {  // (uniform)
-                        const double br = pl[2][oq][tj * 16 + (lane & 15)], bim = pl[3][oq][tj * 16 + (lane & 15)];
-                        accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, accr[tj], 0, 0, 0);
-                        accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, bim, accr[tj], 0, 0, 0);
-                        acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bim, acci[tj], 0, 0, 0);
-                        acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, acci[tj], 0, 0, 1);  // - Ui^T U'r
-                    }
-                }
-            }
-        }
-    }
+    zd4 accr[BT], acci[BT];
+    zpanel_overlap<BT>(Uk, Up, Dd, valid, n, m, bi, bj, pl, tt, ti, lane, row_live, accr, acci);  // M = U(k)^H D U(k+e_d) of the set
     // lane (q, c), register r: row q + 4 r, column c of the tile
     if constexpr (STORE) {
         if (!row_live) return;
-        double2* out = Mws + (size_t)(li - l0) * m * m;
-#pragma unroll
-        for (int tj = 0; tj < BT; ++tj) {
-            const int col = bj * RB + tj * 16 + (lane & 15);
-            if (col < m) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = bi * RB + ti * 16 + (lane >> 4) + 4 * r;
-                    if (row < m) out[(size_t)row * m + col] = make_double2(accr[tj][r], acci[tj][r]);
-                }
-            }
-        }
+        ztiles_store<BT>(Mws + (size_t)(li - l0) * m * m, m, bi * RB + ti * 16, bj * RB, lane, accr, acci);
         return;
     } else {
         double2* T = berry_lds + (size_t)team * RB * TS;

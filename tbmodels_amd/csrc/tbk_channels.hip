@@ -43,40 +43,6 @@ struct ChanGeom {
     static_assert(2 * Geo::WAVES * (int)sizeof(int) <= 2 * THREADS * (int)sizeof(double), "the sweeps' flags fit red");
 };
 
-// C = A^H B: surf_product with the A fragment taken from A's columns and conjugated.  Lane (q, c) feeds conj(A[k + q][16 tr + c]) and
-// B[k + q][16 tc + c]; the tiles, their owners and the skipped blocks are surf_product's.
-template <int NP, int NT, int SA, int SB>
-__device__ __forceinline__ void chan_product_ah(const double* ar, const double* ai, const double* br, const double* bi, int n, int wave, int lane,
-                                                surf_d4 (&cr)[NT], surf_d4 (&ci)[NT]) {
-    constexpr int TR = NP / 16;
-    lane = surf_fresh(lane);
-    const int q = lane >> 4, c16 = lane & 15;
-    const int tr = (wave * NT) / TR, tc0 = (wave * NT) % TR;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) cr[t] = ci[t] = surf_d4{0.0, 0.0, 0.0, 0.0};
-    if (tr * 16 >= n) return;
-#pragma unroll 1
-    for (int kb = 0; kb < TR; ++kb) {
-        if (kb * 16 < n) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int kk = kb * 16 + 4 * ks + q;
-                const double a_r = ar[kk * SA + tr * 16 + c16], a_i = -ai[kk * SA + tr * 16 + c16];
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    if ((tc0 + t) * 16 < n) {
-                        const double b_r = br[kk * SB + (tc0 + t) * 16 + c16], b_i = bi[kk * SB + (tc0 + t) * 16 + c16];
-                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_r, b_r, cr[t], 0, 0, 0);
-                        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_r, b_i, ci[t], 0, 0, 0);
-                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_i, b_i, cr[t], 0, 0, 1);  // - a_i b_i
-                        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_i, b_r, ci[t], 0, 0, 0);
-                    }
-                }
-            }
-        }
-    }
-}
-
 // B = sign i (e - e^H) of the planes e (pitch SM) into the planes b (pitch S), element by element as trans_closing forms Gamma; zeros
 // beyond n.  taken[i] = -1 for the rows below n, NP beyond: the table of chan_cholesky.  No barrier inside.
 template <int NP, int THREADS, int S, int SM>
@@ -283,11 +249,11 @@ __device__ __forceinline__ bool chan_closing(const SurfPlanes& P, double sign, i
     const int rank_l = chan_cholesky<NP, THREADS, S>(yr, yi, P.jrow, n, tid);  // L_L in Y
     __syncthreads();
     {
-        surf_d4 cr[NT], ci[NT];
+        zd4 cr[NT], ci[NT];
         surf_product<NP, NT, SM, S>(pr, pi, yr, yi, n, wave, lane, cr, ci);  // P_M L_L into D
         surf_tiles<NP, NT, SM, false>(dr, di, n, wave, lane, cr, ci);
         __syncthreads();
-        chan_product_ah<NP, NT, S, SM>(xr, xi, dr, di, n, wave, lane, cr, ci);  // t = L_R^H (P_M L_L)
+        surf_product<NP, NT, S, SM, true, false>(xr, xi, dr, di, n, wave, lane, cr, ci);  // t = L_R^H (P_M L_L)
         __syncthreads();  // L_R and L_L have been read
         // every tile of t, the zero ones beyond n included, into the Jacobi's columns: t as it is when r_L <= r_R, else t^H
         const bool flip = rank_l > rank_r;  // (uniform)
@@ -312,7 +278,7 @@ __device__ __forceinline__ bool chan_closing(const SurfPlanes& P, double sign, i
 #pragma unroll 4
         for (int i = 0; i < NP; ++i) v += tr[tid * PT + i] * tr[tid * PT + i] + ti[tid * PT + i] * ti[tid * PT + i];
         P.rown[tid] = v;
-        bad |= !(v <= SURF_DBL_MAX);
+        bad |= !(v <= DBL_MAX);
     }
     __syncthreads();
     if (tid < NP) {

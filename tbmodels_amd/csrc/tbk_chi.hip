@@ -66,10 +66,9 @@
 
 #include "tbk_occ.h"
 #include "tbk_pair.h"
+#include "tbk_zmfma.h"
 
 namespace {
-
-typedef double chi_d4 __attribute__((ext_vector_type(4)));
 
 constexpr int CHI_THREADS = PAIR_THREADS;
 constexpr int64_t CHI_MAX_BATCH = 4096;                 // vectors per launch (grid z), at most
@@ -173,12 +172,10 @@ __global__ void __launch_bounds__(CHI_THREADS) chi_overlap_kernel(const double2*
                                                                   const double* __restrict__ tab, ChiMesh g, int n,
                                                                   const int32_t* __restrict__ Q, const double2* __restrict__ D, double inv_t,
                                                                   int64_t blocks, double* __restrict__ part, ChiDyn dyn) {
-    constexpr int RB = 16 * BT;               // rows (and columns) of the block
-    constexpr int KPW = BT == 1 ? 4 : 1;      // k-points per workgroup
-    constexpr int TEAM = CHI_THREADS / KPW;   // threads that stage one k-point's panel
-    constexpr int S = BT == 1 ? 18 : 82;      // doubles between the orbital rows of a plane (dm_project_kernel's: the four rows a wave reads at once
-                                              // land in different bank pairs); a wave stores along a row
-    __shared__ double planes[KPW][4][16][S];  // Ur, Ui of the block's rows (k); Re, Im of D U' of its columns (k+q)
+    using Geo = ZPanel<BT>;  // (tbk_zmfma.h; an item is a k-point)
+    constexpr int RB = Geo::RB, KPW = Geo::KPW, TEAM = Geo::TEAM, S = Geo::S;
+    static_assert(CHI_THREADS == Geo::THREADS, "the panel's workgroup");
+    __shared__ double planes[KPW][4 * 16 * S];  // per k-point four planes [16][S]: Ur, Ui of the block's rows (k); Re, Im of D U' of its columns (k+q)
     __shared__ double wave_part[4];
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int team = BT == 1 ? wave : 0, tt = tid - team * TEAM;
@@ -191,53 +188,10 @@ __global__ void __launch_bounds__(CHI_THREADS) chi_overlap_kernel(const double2*
     const double2* Uk = U + (valid ? (size_t)k * n * n : 0);
     const double2* Up = U + (size_t)kp * n * n;
     const double2* Dq = D ? D + (size_t)ql * n : nullptr;
-    double(*pl)[16][S] = planes[team];
     const int ti = BT == 1 ? 0 : wave;                      // the wave's tile row
     const bool row_live = valid && bi * RB + ti * 16 < n;   // (wave-uniform)
-    chi_d4 accr[BT], acci[BT];
-#pragma unroll
-    for (int tj = 0; tj < BT; ++tj) accr[tj] = acci[tj] = chi_d4{0.0, 0.0, 0.0, 0.0};
-    const int sc = tt % RB, so0 = tt / RB;  // the band (column of the panel) and the first orbital row this thread stages
-    const int col_a = bi * RB + sc, col_b = bj * RB + sc;
-    for (int i0 = 0; i0 < n; i0 += 16) {
-        __syncthreads();  // the previous panel has been read
-#pragma unroll
-        for (int o = so0; o < 16; o += TEAM / RB) {
-            const int i = i0 + o;
-            const bool i_in = valid && i < n;
-            double2 ua = make_double2(0.0, 0.0), ub = ua;
-            if (i_in && col_a < n) ua = Uk[(size_t)i * n + col_a];
-            if (i_in && col_b < n) {
-                ub = Up[(size_t)i * n + col_b];
-                if (Dq) {
-                    const double2 d = Dq[i];
-                    ub = make_double2(d.x * ub.x - d.y * ub.y, d.x * ub.y + d.y * ub.x);
-                }
-            }
-            pl[0][o][sc] = ua.x;
-            pl[1][o][sc] = ua.y;
-            pl[2][o][sc] = ub.x;
-            pl[3][o][sc] = ub.y;
-        }
-        __syncthreads();
-        if (row_live) {
-#pragma unroll 1
-            for (int q4 = 0; q4 < 4; ++q4) {  // (not unrolled: dm_project_kernel's note on registers)
-                const int oq = 4 * q4 + (lane >> 4);
-                const double ar = pl[0][oq][ti * 16 + (lane & 15)], ai = pl[1][oq][ti * 16 + (lane & 15)];
-#pragma unroll
-                for (int tj = 0; tj < BT; ++tj) {
-                    if (bj * RB + tj * 16 < n) {  // (uniform)
-                        const double br = pl[2][oq][tj * 16 + (lane & 15)], bim = pl[3][oq][tj * 16 + (lane & 15)];
-                        accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, accr[tj], 0, 0, 0);
-                        accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, bim, accr[tj], 0, 0, 0);
-                        acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bim, acci[tj], 0, 0, 0);
-                        acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, acci[tj], 0, 0, 1);  // - Ui^T U'r
-                    }
-                }
-            }
-        }
-    }
+    zd4 accr[BT], acci[BT];
+    zpanel_overlap<BT>(Uk, Up, Dq, valid, n, n, bi, bj, planes[team], tt, ti, lane, row_live, accr, acci);  // M = U(k)^H D U(k+q)
     // the epilogue.  lane (q, c), register r: row q + 4 r, column c of the tile
     if constexpr (DYN) {
         __shared__ double wave_dyn[4][CHI_WC][2];
@@ -497,23 +451,20 @@ __device__ __forceinline__ double2 chi_cmul(double2 a, double2 b) {
 }
 
 // The MFMAs of one staged panel of 16 b' on the wave's tile row ti and all BT tiles of the block: four steps of four b', the X pair
-// read once per step, per tile the Y pair and the four real products (the last with the negate bit: - Xr Yi^T).  No tile is guarded:
+// read once per step, per tile the Y pair and the four real products of zmfma_abh.  No tile is guarded:
 // a branch around an MFMA makes its accumulator a phi of two values, which the compiler keeps in VGPRs and copies to and from the
 // AGPRs around every group of MFMAs (32 v_accvgpr moves and a drain of the pipe per four).  So the loop holds ds_read_b64 and MFMA
 // only, and a tile that is never written (padding: zeros; below the diagonal of a diagonal block) is multiplied like any other.
 template <int S, int BT>
-__device__ __forceinline__ void chi_orb_tiles(const double (*pl)[16][S], int ti, int lane, chi_d4 (&accr)[BT], chi_d4 (&acci)[BT]) {
+__device__ __forceinline__ void chi_orb_tiles(const double (*pl)[16][S], int ti, int lane, zd4 (&accr)[BT], zd4 (&acci)[BT]) {
 #pragma unroll 1
-    for (int q4 = 0; q4 < 4; ++q4) {  // (not unrolled: dm_project_kernel's note on registers)
+    for (int q4 = 0; q4 < 4; ++q4) {  // (not unrolled: ZPanel's note on registers)
         const int kq = 4 * q4 + (lane >> 4);
         const double xr = pl[0][kq][ti * 16 + (lane & 15)], xi = pl[1][kq][ti * 16 + (lane & 15)];
 #pragma unroll
         for (int tj = 0; tj < BT; ++tj) {
             const double yr = pl[2][kq][tj * 16 + (lane & 15)], yi = pl[3][kq][tj * 16 + (lane & 15)];
-            accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, yr, accr[tj], 0, 0, 0);
-            accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, yi, accr[tj], 0, 0, 0);
-            acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, yr, acci[tj], 0, 0, 0);
-            acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, yi, acci[tj], 0, 0, 1);  // - Xr Yi^T
+            zmfma_abh(xr, xi, yr, yi, accr[tj], acci[tj]);
         }
     }
 }
@@ -532,11 +483,10 @@ __global__ void __launch_bounds__(CHI_THREADS) chi_orbital_kernel(const double2*
                                                                   const int32_t* __restrict__ Q, const double2* __restrict__ D, double inv_t,
                                                                   const int32_t* __restrict__ orb, int m, int mp, int64_t ks, int64_t slices,
                                                                   double2* __restrict__ part) {
-    constexpr int RB = 16 * BT;               // rows (and columns) of the block
-    constexpr int KPW = BT == 1 ? 4 : 1;      // slices per workgroup
-    constexpr int TEAM = CHI_THREADS / KPW;   // threads that stage one slice's panels
+    using Geo = ZPanel<BT>;  // (tbk_zmfma.h; an item is a slice)
+    constexpr int RB = Geo::RB, KPW = Geo::KPW, TEAM = Geo::TEAM, S = Geo::S;
+    static_assert(CHI_THREADS == Geo::THREADS, "the panel's workgroup");
     constexpr int STEP = TEAM / 16;           // rows between the four a thread stages
-    constexpr int S = BT == 1 ? 18 : 82;      // doubles between the b' rows of a plane (dm_project_kernel's)
     __shared__ double planes[KPW][4][16][S];  // Xr, Xi of the block's rows i; Yr, Yi of its columns j
     __shared__ double tw[KPW][TEAM];          // t[b][b'] of TEAM b' at once: one chi_pair_weight per (k, b, b')
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -558,9 +508,9 @@ __global__ void __launch_bounds__(CHI_THREADS) chi_orbital_kernel(const double2*
     const int ti = BT == 1 ? 0 : wave;               // the wave's tile row
     const bool row_live = bi * RB + ti * 16 < m;     // (wave-uniform)
     const bool diag = bi == bj;
-    chi_d4 accr[BT], acci[BT];
+    zd4 accr[BT], acci[BT];
 #pragma unroll
-    for (int tj = 0; tj < BT; ++tj) accr[tj] = acci[tj] = chi_d4{0.0, 0.0, 0.0, 0.0};
+    for (int tj = 0; tj < BT; ++tj) accr[tj] = acci[tj] = zd4{0.0, 0.0, 0.0, 0.0};
     // The accumulators' home is the AGPRs over all the loops below: an empty statement (no instruction) that reads them as AGPRs
     // stands behind the loops, and in <1> another ahead of them.  Without these the compiler keeps them in VGPRs and moves them in
     // and out around every group of MFMAs; where the statements must stand was read off the built code of each template

@@ -21,7 +21,7 @@
 //   K^L_p = 2 Im(conj(H01) o ((F_p Gamma_L) F_{p+1}^H)),  J^L_p = 2 Im(conj(H00 + V_p) o ((F_p Gamma_L) F_p^H)),  K^R, J^R: C_p and Gamma_R
 //   current_left[p][i] = sum_j K^L_p[i][j],  current_right[p][i] = sum_j K^R_p[i][j]
 //
-//                         after each lead's row sums, when X still holds F_p Gamma_L (C_p Gamma_R): products A B^H (surf_product_h) with
+//                         after each lead's row sums, when X still holds F_p Gamma_L (C_p Gamma_R): products A B^H (surf_product, BH) with
 //                         the block of the layer above, which waits in the stack's dead place of g_{p+1} (H01^H Q_p), two more per layer
 //                         and four when J is returned.  The false instantiation is the kernel above, statement for statement.
 
@@ -81,7 +81,7 @@ __device__ __forceinline__ void devg_broadening(double* xr, double* xi, const do
 // the wave's tiles of a product added to Y (pitch NP + 1) into D (pitch SD): D = Y + product
 template <int NP, int NT, int SD>
 __device__ __forceinline__ void devg_tiles_sum(double* dr, double* di, const double* yr, const double* yi, int n, int wave, int lane,
-                                               const surf_d4 (&cr)[NT], const surf_d4 (&ci)[NT]) {
+                                               const zd4 (&cr)[NT], const zd4 (&ci)[NT]) {
     constexpr int TR = NP / 16, S = NP + 1;
     lane = surf_fresh(lane);
     const int q = lane >> 4, c16 = lane & 15;
@@ -136,8 +136,8 @@ __device__ __forceinline__ void devg_row_totals(const double* a, int n, int tid,
 // this thread's share is not finite.
 template <int NP, int NT, int SH, bool ONSITE, bool PLANE>
 __device__ __forceinline__ bool devg_tiles_bond(const double* hr, const double* hi, const double2* __restrict__ h0, const double2* __restrict__ v,
-                                                double* kr, double* __restrict__ out, int n, int wave, int lane, const surf_d4 (&cr)[NT],
-                                                const surf_d4 (&ci)[NT]) {
+                                                double* kr, double* __restrict__ out, int n, int wave, int lane, const zd4 (&cr)[NT],
+                                                const zd4 (&ci)[NT]) {
     constexpr int TR = NP / 16, S = NP + 1;
     lane = surf_fresh(lane);
     const int q = lane >> 4, c16 = lane & 15;
@@ -162,7 +162,7 @@ __device__ __forceinline__ bool devg_tiles_bond(const double* hr, const double* 
                         h_i = hi[i * SH + c];
                     }
                     b = 2.0 * (h_r * ci[t][r] - h_i * cr[t][r]);
-                    bad |= !(fabs(b) <= SURF_DBL_MAX);
+                    bad |= !(fabs(b) <= DBL_MAX);
                     if (out != nullptr) out[(size_t)i * n + c] = b;
                 }
                 if (PLANE) kr[i * S + c] = b;
@@ -185,7 +185,7 @@ __device__ __forceinline__ bool devg_current_side(const SurfPlanes& P, const dou
     const int lane = tid & 63, wave = tid >> 6;
     double *xr = P.xr, *xi = P.xi, *yr = P.yr, *yi = P.yi;
     bool bad = false;
-    surf_d4 cr[NT], ci[NT];
+    zd4 cr[NT], ci[NT];
     if (intra != nullptr) {
         if (own_r != nullptr) {
 #pragma unroll 2
@@ -196,7 +196,7 @@ __device__ __forceinline__ bool devg_current_side(const SurfPlanes& P, const dou
             }
             __syncthreads();
         }
-        surf_product_h<NP, NT, S, S>(xr, xi, yr, yi, n, wave, lane, cr, ci);  // (B_p Gamma) B_p^H
+        surf_product<NP, NT, S, S, false, true>(xr, xi, yr, yi, n, wave, lane, cr, ci);  // (B_p Gamma) B_p^H
         bad |= devg_tiles_bond<NP, NT, SM, true, false>(nullptr, nullptr, h0, vp, nullptr, intra, n, wave, lane, cr, ci);
         __syncthreads();  // Y has been read
     }
@@ -210,7 +210,7 @@ __device__ __forceinline__ bool devg_current_side(const SurfPlanes& P, const dou
             yi[i * S + c] = v.y;
         }
         __syncthreads();
-        surf_product_h<NP, NT, S, S>(xr, xi, yr, yi, n, wave, lane, cr, ci);  // (B_p Gamma) B_{p+1}^H
+        surf_product<NP, NT, S, S, false, true>(xr, xi, yr, yi, n, wave, lane, cr, ci);  // (B_p Gamma) B_{p+1}^H
         __syncthreads();  // X has been read
         bad |= devg_tiles_bond<NP, NT, SM, false, true>(P.alr, P.ali, nullptr, nullptr, xr, inter, n, wave, lane, cr, ci);
         __syncthreads();
@@ -264,7 +264,7 @@ __device__ __forceinline__ bool devg_backward_layer(const SurfPlanes& P, double2
             yi[i * S + c] = v.y;
         }
         __syncthreads();
-        surf_d4 cr[NT], ci[NT], c2r[NT], c2i[NT];
+        zd4 cr[NT], ci[NT], c2r[NT], c2i[NT];
         surf_product<NP, NT, S, SM>(yr, yi, h01r, h01i, n, wave, lane, cr, ci);  // X = g_p H01
         surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
         __syncthreads();
@@ -308,8 +308,8 @@ __device__ __forceinline__ bool devg_backward_layer(const SurfPlanes& P, double2
         const int i = e / n, c = e - i * n;
         const double2 gv = make_double2(dr[i * SM + c], di[i * SM + c]), fv = make_double2(yr[i * S + c], yi[i * S + c]),
                       cv = make_double2(pr[i * SM + c], pi[i * SM + c]);
-        bad |= !(fabs(gv.x) <= SURF_DBL_MAX && fabs(gv.y) <= SURF_DBL_MAX && fabs(fv.x) <= SURF_DBL_MAX && fabs(fv.y) <= SURF_DBL_MAX &&
-                 fabs(cv.x) <= SURF_DBL_MAX && fabs(cv.y) <= SURF_DBL_MAX);
+        bad |= !(fabs(gv.x) <= DBL_MAX && fabs(gv.y) <= DBL_MAX && fabs(fv.x) <= DBL_MAX && fabs(fv.y) <= DBL_MAX &&
+                 fabs(cv.x) <= DBL_MAX && fabs(cv.y) <= DBL_MAX);
         if (g_out != nullptr) {
             g_out[e] = gv;
             f_out[e] = fv;
@@ -324,7 +324,7 @@ __device__ __forceinline__ bool devg_backward_layer(const SurfPlanes& P, double2
     devg_broadening<NP, THREADS, SM>(xr, xi, etr, eti, n, tid);
     __syncthreads();
     {
-        surf_d4 cr[NT], ci[NT];
+        zd4 cr[NT], ci[NT];
         surf_product<NP, NT, S, S>(yr, yi, xr, xi, n, wave, lane, cr, ci);  // F_p Gamma_L
         __syncthreads();  // Gamma_L has been read
         surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
@@ -410,13 +410,13 @@ struct DevgShape {
     int64_t n_z = 0;
     bool green = false;
     bool current = false, bonds = false;  // tbk_device_current*: the kernel's CURRENT instantiation; bonds needs current
-    size_t t_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * sizeof(double)); }
-    size_t it_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * sizeof(int32_t)); }
-    size_t row_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * m_layers * n * sizeof(double)); }
-    size_t mat_bytes(int64_t nk) const { return green ? surf_align256((size_t)nk * n_z * m_layers * n * n * sizeof(double2)) : 0; }
-    size_t cur_bytes(int64_t nk) const { return current ? surf_align256((size_t)nk * n_z * (m_layers - 1) * n * sizeof(double)) : 0; }
-    size_t inter_bytes(int64_t nk) const { return bonds ? surf_align256((size_t)nk * n_z * (m_layers - 1) * n * n * sizeof(double)) : 0; }
-    size_t intra_bytes(int64_t nk) const { return bonds ? surf_align256((size_t)nk * n_z * m_layers * n * n * sizeof(double)) : 0; }
+    size_t t_bytes(int64_t nk) const { return dos_align256((size_t)nk * n_z * sizeof(double)); }
+    size_t it_bytes(int64_t nk) const { return dos_align256((size_t)nk * n_z * sizeof(int32_t)); }
+    size_t row_bytes(int64_t nk) const { return dos_align256((size_t)nk * n_z * m_layers * n * sizeof(double)); }
+    size_t mat_bytes(int64_t nk) const { return green ? dos_align256((size_t)nk * n_z * m_layers * n * n * sizeof(double2)) : 0; }
+    size_t cur_bytes(int64_t nk) const { return current ? dos_align256((size_t)nk * n_z * (m_layers - 1) * n * sizeof(double)) : 0; }
+    size_t inter_bytes(int64_t nk) const { return bonds ? dos_align256((size_t)nk * n_z * (m_layers - 1) * n * n * sizeof(double)) : 0; }
+    size_t intra_bytes(int64_t nk) const { return bonds ? dos_align256((size_t)nk * n_z * m_layers * n * n * sizeof(double)) : 0; }
     size_t result_bytes(int64_t nk) const {
         return t_bytes(nk) + it_bytes(nk) + 3 * row_bytes(nk) + 3 * mat_bytes(nk) + 2 * (cur_bytes(nk) + inter_bytes(nk) + intra_bytes(nk));
     }

@@ -18,7 +18,7 @@
 //   dm_phase_kernel    tab[R tile][group][cos | sin][64]: the A operand of the Fourier product in the order its lanes load it --
 //                      lane (q, r) of a group holds R row 16 tile + r at column 4 group + q.  VALU work, once per chunk.
 //   dm_project_kernel  P = (U diag w) U^H as two real products on v_mfma_f64_16x16x4_f64, contraction over the bands:
-//                      Pr = wUr Ur^T + wUi Ui^T, Pi = wUi Ur^T - wUr Ui^T (the minus is the instruction's negate-A bit).  A workgroup
+//                      Pr = wUr Ur^T + wUi Ui^T, Pi = wUi Ur^T - wUr Ui^T (zmfma_abh of tbk_zmfma.h).  A workgroup
 //                      owns a 64 x 64 block of one P(k) (16 x 16 of four k-points up to 16 orbitals): panels of 16 bands of the
 //                      block's rows of U go through LDS once, band-major planes wUr, wUi (rows of the block) and Ur, Ui (its
 //                      columns), padded with zeros to the tile, so an operand is one ds_read_b64 per lane.  Every tile is computed
@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "tbk_lattice.h"
+#include "tbk_zmfma.h"
 
 namespace {
 constexpr int64_t DM_TARGET_WAVES = 1024;  // Fourier tiles x slices the plan aims for (four waves on each of 256 CUs)
@@ -63,8 +64,6 @@ static void dm_plan_slices(int64_t rows, int n_orb, int64_t n_r, int64_t* nr_pad
 }
 
 namespace {
-
-typedef double dm_d4 __attribute__((ext_vector_type(4)));
 
 __global__ void __launch_bounds__(DM_THREADS) dm_phase_kernel(const int32_t* __restrict__ Rm, DmMesh g, int64_t n_r, int64_t nr_pad, int64_t c0,
                                                               int64_t nkc, int64_t ng, double* __restrict__ tab) {
@@ -98,11 +97,9 @@ __global__ void __launch_bounds__(DM_THREADS) dm_phase_kernel(const int32_t* __r
 template <int BT>
 __global__ void __launch_bounds__(DM_THREADS) dm_project_kernel(const double2* __restrict__ U, const double* __restrict__ w, int n, int64_t pad,
                                                                 int64_t nkc, double2* __restrict__ P) {
-    constexpr int RB = 16 * BT;                   // rows (and columns) of the block
-    constexpr int KPW = BT == 1 ? 4 : 1;          // k-points per workgroup
-    constexpr int TEAM = DM_THREADS / KPW;        // threads that stage one k-point's panel
-    constexpr int S = BT == 1 ? 18 : 82;          // doubles between the band rows of a plane: the 16 bands a wave stores at once land
-                                                  // in 16 different bank pairs, the four a wave reads at once (nearly) so
+    using Geo = ZPanel<BT>;  // (tbk_zmfma.h; an item is a k-point)
+    constexpr int RB = Geo::RB, KPW = Geo::KPW, TEAM = Geo::TEAM, S = Geo::S;
+    static_assert(DM_THREADS == Geo::THREADS, "the panel's workgroup");
     __shared__ double planes[KPW][4][16][S];      // wUr, wUi of the block's rows; Ur, Ui of its columns
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int team = BT == 1 ? wave : 0, tt = tid - team * TEAM;
@@ -116,9 +113,9 @@ __global__ void __launch_bounds__(DM_THREADS) dm_project_kernel(const double2* _
     double(*pl)[16][S] = planes[team];
     const int ti = BT == 1 ? 0 : wave;  // the wave's tile row
     const bool row_live = bi * RB + ti * 16 < n;  // (wave-uniform)
-    dm_d4 accr[BT], acci[BT];
+    zd4 accr[BT], acci[BT];
 #pragma unroll
-    for (int tj = 0; tj < BT; ++tj) accr[tj] = acci[tj] = dm_d4{0.0, 0.0, 0.0, 0.0};
+    for (int tj = 0; tj < BT; ++tj) accr[tj] = acci[tj] = zd4{0.0, 0.0, 0.0, 0.0};
     const int sb = tt & 15, srow0 = tt >> 4;
     for (int b0 = 0; b0 < n; b0 += 16) {
         __syncthreads();  // the previous panel has been read
@@ -141,41 +138,25 @@ __global__ void __launch_bounds__(DM_THREADS) dm_project_kernel(const double2* _
         __syncthreads();
         if (row_live) {
 #pragma unroll 1
-            for (int q = 0; q < 4; ++q) {  // (not unrolled: with the operands of all four steps at once the kernel takes 344 registers, 96 of them accumulation registers)
+            for (int q = 0; q < 4; ++q) {  // (not unrolled: ZPanel's note on registers)
                 const int bq = 4 * q + (lane >> 4);
                 const double ar = pl[0][bq][ti * 16 + (lane & 15)], ai = pl[1][bq][ti * 16 + (lane & 15)];
 #pragma unroll
                 for (int tj = 0; tj < BT; ++tj) {
                     if (bj * RB + tj * 16 < n) {  // (uniform)
                         const double br = pl[2][bq][tj * 16 + (lane & 15)], bim = pl[3][bq][tj * 16 + (lane & 15)];
-                        accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, accr[tj], 0, 0, 0);
-                        accr[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, bim, accr[tj], 0, 0, 0);
-                        acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, acci[tj], 0, 0, 0);
-                        acci[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bim, acci[tj], 0, 0, 1);  // - wUr Ui^T
+                        zmfma_abh(ar, ai, br, bim, accr[tj], acci[tj]);
                     }
                 }
             }
         }
     }
     if (!row_live) return;
-    // lane (q, c), register r: row q + 4 r, column c of the tile
-    double2* Pj = P + (size_t)j * n * n;
-#pragma unroll
-    for (int tj = 0; tj < BT; ++tj) {
-        const int gj = bj * RB + tj * 16 + (lane & 15);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int gi = bi * RB + ti * 16 + (lane >> 4) + 4 * r;
-            if (gi < n && gj < n) Pj[(size_t)gi * n + gj] = make_double2(accr[tj][r], acci[tj][r]);
-        }
-    }
+    ztiles_store<BT>(P + (size_t)j * n * n, n, bi * RB + ti * 16, bj * RB, lane, accr, acci);
 }
 
-__device__ __forceinline__ void dm_fourier_step(double c, double s, double2 p, dm_d4& ar, dm_d4& ai) {
-    ar = __builtin_amdgcn_mfma_f64_16x16x4f64(c, p.x, ar, 0, 0, 0);
-    ar = __builtin_amdgcn_mfma_f64_16x16x4f64(s, p.y, ar, 0, 0, 0);
-    ai = __builtin_amdgcn_mfma_f64_16x16x4f64(c, p.y, ai, 0, 0, 0);
-    ai = __builtin_amdgcn_mfma_f64_16x16x4f64(s, p.x, ai, 0, 0, 1);  // - s Pr
+__device__ __forceinline__ void dm_fourier_step(double c, double s, double2 p, zd4& ar, zd4& ai) {
+    zmfma_ahb(c, s, p.x, p.y, ar, ai);  // (c + i s)^H (Pr + i Pi)
 }
 
 // grid: (column tiles / 4, R tiles, slices the chunk touches from slice_lo on); a wave owns one tile of one slice.  The chunk's table
@@ -195,7 +176,7 @@ __global__ void __launch_bounds__(DM_THREADS) dm_fourier_kernel(const double* __
     const double2* pb = P + ((ga - g0) * 4 + (lane >> 4)) * n2 + (e_in ? e : n2 - 1);
     double2* out = part + ((sl * nr_pad + rt * 16 + (lane >> 4)) * n2 + e);  // register r: 4 r rows further
     const int64_t out_step = 4 * n2, p_step = 4 * n2;
-    dm_d4 ar = {0.0, 0.0, 0.0, 0.0}, ai = ar;
+    zd4 ar = {0.0, 0.0, 0.0, 0.0}, ai = ar;
     if (e_in) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {

@@ -16,9 +16,9 @@ struct EnsShape {
     bool diag = false;
     bool channels = false;
     size_t device_bytes() const { return (size_t)n_s * m_layers * n * (diag ? sizeof(double) : (size_t)n * sizeof(double2)); }
-    size_t t_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * n_s * sizeof(double)); }
-    size_t it_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * sizeof(int32_t)); }
-    size_t ch_bytes(int64_t nk) const { return channels ? surf_align256((size_t)nk * n_z * n_s * n * sizeof(double)) : 0; }
+    size_t t_bytes(int64_t nk) const { return dos_align256((size_t)nk * n_z * n_s * sizeof(double)); }
+    size_t it_bytes(int64_t nk) const { return dos_align256((size_t)nk * n_z * sizeof(int32_t)); }
+    size_t ch_bytes(int64_t nk) const { return channels ? dos_align256((size_t)nk * n_z * n_s * n * sizeof(double)) : 0; }
     size_t result_bytes(int64_t nk) const { return t_bytes(nk) + it_bytes(nk) + ch_bytes(nk); }
     static constexpr size_t flag_bytes = 2 * sizeof(unsigned long long);
     int64_t auto_chunk(int64_t nk) const {  // the chunk's results and its two layers inside the budget

@@ -37,10 +37,9 @@
 #include <rocsolver/rocsolver.h>
 
 #include "tbk_lattice.h"
+#include "tbk_zmfma.h"
 
 namespace {
-
-typedef double green_d4 __attribute__((ext_vector_type(4)));
 
 
 // BT tiles of 16 along each side of the workgroup's block of P: 4 (one k-point per workgroup, wave t owns tile row t) or 1 (n <= 16:
@@ -49,10 +48,9 @@ template <int BT>
 __global__ void __launch_bounds__(DM_THREADS) green_project_kernel(const double2* __restrict__ U, const double* __restrict__ E,
                                                                    const double2* __restrict__ z, int zt, double nk_total, int n, int64_t pad,
                                                                    int64_t nkc, double2* __restrict__ P) {
-    constexpr int RB = 16 * BT;                   // rows (and columns) of the block
-    constexpr int KPW = BT == 1 ? 4 : 1;          // k-points per workgroup
-    constexpr int TEAM = DM_THREADS / KPW;        // threads that stage one k-point's panel
-    constexpr int S = BT == 1 ? 18 : 82;          // doubles between the band rows of a plane (tbk_dm.hip)
+    using Geo = ZPanel<BT>;  // (tbk_zmfma.h; an item is a k-point)
+    constexpr int RB = Geo::RB, KPW = Geo::KPW, TEAM = Geo::TEAM, S = Geo::S;
+    static_assert(DM_THREADS == Geo::THREADS, "the panel's workgroup");
     __shared__ double planes[KPW][4][16][S];      // Ur, Ui of the block's rows; Ur, Ui of its columns
     __shared__ double2 gtab[KPW][GREEN_ZT][16];   // g / NK of the panel's bands at the tile's energies
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -68,11 +66,11 @@ __global__ void __launch_bounds__(DM_THREADS) green_project_kernel(const double2
     double2(*gt)[16] = gtab[team];
     const int ti = BT == 1 ? 0 : wave;  // the wave's tile row
     const bool row_live = bi * RB + ti * 16 < n;  // (wave-uniform)
-    green_d4 accr[GREEN_ZT][BT], acci[GREEN_ZT][BT];
+    zd4 accr[GREEN_ZT][BT], acci[GREEN_ZT][BT];
 #pragma unroll
     for (int zi = 0; zi < GREEN_ZT; ++zi)
 #pragma unroll
-        for (int tj = 0; tj < BT; ++tj) accr[zi][tj] = acci[zi][tj] = green_d4{0.0, 0.0, 0.0, 0.0};
+        for (int tj = 0; tj < BT; ++tj) accr[zi][tj] = acci[zi][tj] = zd4{0.0, 0.0, 0.0, 0.0};
     const int sb = tt & 15, srow0 = tt >> 4;
     for (int b0 = 0; b0 < n; b0 += 16) {
         __syncthreads();  // the previous panel has been read
@@ -104,7 +102,7 @@ __global__ void __launch_bounds__(DM_THREADS) green_project_kernel(const double2
         __syncthreads();
         if (row_live) {
 #pragma unroll 1
-            for (int q = 0; q < 4; ++q) {  // (not unrolled, as in dm_project_kernel: the accumulators take the registers)
+            for (int q = 0; q < 4; ++q) {  // (not unrolled: ZPanel's note on registers)
                 const int bq = 4 * q + (lane >> 4);
                 const double ur = pl[0][bq][ti * 16 + (lane & 15)], ui = pl[1][bq][ti * 16 + (lane & 15)];
                 double br[BT], bim[BT];
@@ -123,6 +121,10 @@ __global__ void __launch_bounds__(DM_THREADS) green_project_kernel(const double2
 #pragma unroll
                         for (int tj = 0; tj < BT; ++tj) {
                             if (bj * RB + tj * 16 < n) {  // (uniform)
+                                // zmfma_abh's four products with the two accumulators taken in turn, Gr Gi Gr Gi: this site's own
+                                // copy.  With GREEN_ZT x BT accumulator pairs in flight the shared step's order (Gr Gr Gi Gi)
+                                // measured 0.2 - 0.4 % slower at 64 energies (DESIGN_LOG R29.1); each accumulator's own order,
+                                // and so the bits, are the step's
                                 accr[zi][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br[tj], accr[zi][tj], 0, 0, 0);
                                 acci[zi][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br[tj], acci[zi][tj], 0, 0, 0);
                                 accr[zi][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, bim[tj], accr[zi][tj], 0, 0, 0);
@@ -135,7 +137,8 @@ __global__ void __launch_bounds__(DM_THREADS) green_project_kernel(const double2
         }
     }
     if (!row_live) return;
-    // lane (q, c), register r: row q + 4 r, column c of the tile
+    // lane (q, c), register r: row q + 4 r, column c of the tile (ztiles_store's loop, kept here with the kernel's own MFMA order:
+    // the kernel's built code is then what it was measured as)
 #pragma unroll
     for (int zi = 0; zi < GREEN_ZT; ++zi) {
         if (zi >= zt) break;
@@ -153,26 +156,13 @@ __global__ void __launch_bounds__(DM_THREADS) green_project_kernel(const double2
 }
 
 // ---- the dressed function: P(k, z) = (z - H(k) - Sigma(z))^-1 / NK by batched inversion ------------------
-// Gauss-Jordan in place with implicit partial pivoting, in panels of 16 pivots (tools/dyson_model.py states the same elimination).
-// The matrix A = (z 1 - H) - Sigma of one (k, z) is formed in LDS -- two planes (re, im) of NP rows, NP + 1 doubles apart
-// -- and stays there; rows never move.  Step j of a panel [j0, j0 + 16):
-//     pivot   the row p among those not yet taken with the largest |re| + |im| in column j (ties: the lowest row index; a NaN counts
-//             as +inf so that every lane reaches the same row).  Lane = row: every wave of the team finds p by itself.
-//     update  of the panel's 16 columns alone (VALU, rank 1): row p becomes a[p][c] / piv (column j: 1 / piv), every other row i
-//             a[i][c] - a[i][j] (a[p][c] / piv) (column j: -a[i][j] / piv).
-// After its 16 steps the panel's columns hold W = T E, where T is the product of the 16 elementary transformations and E the unit
-// columns of the pivot rows: T differs from 1 in those columns alone, so for every OTHER column tile C (the earlier panels, which
-// hold columns of the inverse, and the later ones)  T C = mask(C) + W C[pivot rows], mask zeroing the panel's pivot rows: a rank-16
-// update, a complex product on v_mfma_f64_16x16x4_f64 (four real MFMAs per complex tile and K step), wave t owning tile row t.  Its
-// operands -- W of the tile row, the 16 pivot rows, the tile itself as the accumulator -- go from LDS into registers once, in front
-// of a barrier, and the results back behind it.  In the end storage[p_j][c] = inverse[j][p_c]; the store undoes both permutations.
-// A pivot of modulus 0 or a non-finite element of the result raises the handle's status word (the smallest (mesh point, energy)
-// key wins); no index depends on a value, so a singular input ends like any other.
-constexpr int INVERT_PITCH_PAD = 1;  // pitch NP + 1 doubles: 32 consecutive rows of one column lie on 32 different bank pairs
-
+// The matrix A = (z 1 - H) - Sigma of one (k, z) is formed in LDS -- two planes (re, im) of NP rows, NP + 1 doubles apart -- and
+// inverted there by zgj_invert (tbk_zmfma.h: Gauss-Jordan with implicit partial pivoting, panels of 16 pivots, the rank-16 updates on
+// the matrix pipe), which leaves storage[p_j][c] = inverse[j][p_c]; the store undoes both permutations.  A pivot of modulus 0 or a
+// non-finite element of the result raises the handle's status word (the smallest (mesh point, energy) key wins).
 template <int NP>
 constexpr size_t invert_lds_bytes() {
-    return (size_t)(NP == 16 ? 4 : 1) * ((size_t)2 * NP * (NP + INVERT_PITCH_PAD) * sizeof(double) + (size_t)2 * NP * sizeof(int));
+    return (size_t)(NP == 16 ? 4 : 1) * ((size_t)2 * NP * (NP + 1) * sizeof(double) + (size_t)2 * NP * sizeof(int));
 }
 
 // H: [nkc][n][n] of the chunk; z, Sigma: of the tile's zt energies ([zt], [zt][n][n]); table column j is chunk point j - pad, columns
@@ -184,12 +174,9 @@ __global__ void __launch_bounds__(DM_THREADS) green_invert_kernel(const double2*
                                                                   unsigned long long* __restrict__ flag) {
     constexpr int MPW = NP == 16 ? 4 : 1;     // matrices per workgroup
     constexpr int TEAM = DM_THREADS / MPW;    // threads of one matrix
-    constexpr int CG = TEAM / NP;             // column groups of a panel
-    constexpr int CPT = 16 / CG;              // panel columns per thread
-    constexpr int S = NP + INVERT_PITCH_PAD;  // doubles between two rows of a plane
-    constexpr int TR = NP / 16;               // tile rows
+    constexpr int S = NP + 1;                 // doubles between two rows of a plane (zgj_invert's)
     extern __shared__ double invert_lds[];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = (int)threadIdx.x, wave = tid >> 6;
     const int team = MPW == 1 ? 0 : wave, tt = tid - team * TEAM;
     double* ar = invert_lds + (size_t)team * (2 * NP * S + NP);  // (2 NP ints = NP doubles)
     double* ai = ar + NP * S;
@@ -223,124 +210,7 @@ __global__ void __launch_bounds__(DM_THREADS) green_invert_kernel(const double2*
         }
         if (tt < NP) jrow[tt] = -1;
     }
-    const int row = tt & (NP - 1), cg = tt / NP;
-    bool used = row >= n, singular = false;
-    for (int j0 = 0; j0 < n; j0 += 16) {
-        const int jn = n - j0 < 16 ? n - j0 : 16;
-        for (int jj = 0; jj < jn; ++jj) {
-            const int jc = j0 + jj;
-            __syncthreads();  // column jc is up to date
-            const double fr = ar[row * S + jc], fi = ai[row * S + jc];
-            double best = fabs(fr) + fabs(fi);
-            if (!(best >= 0.0)) best = __builtin_inf();
-            if (used) best = -1.0;
-            int p = row;
-#pragma unroll
-            for (int off = NP / 2; off > 0; off >>= 1) {
-                const double ob = __shfl_xor(best, off, 64);
-                const int op = __shfl_xor(p, off, 64);
-                if (ob > best || (ob == best && op < p)) {
-                    best = ob;
-                    p = op;
-                }
-            }
-            // (p is a row below n that no step has taken: at least one is left, and taken rows and padding compare as -1)
-            const int src = (lane & ~(NP - 1)) | p;
-            const double pr = __shfl(fr, src, 64), pi = __shfl(fi, src, 64);
-            singular |= best == 0.0;
-            const double den = pr * pr + pi * pi;
-            const double ir = pr / den, ii = -pi / den;  // 1 / pivot
-            double xr[CPT], xi[CPT], yr[CPT], yi[CPT];
-#pragma unroll
-            for (int cc = 0; cc < CPT; ++cc) {
-                const int c = j0 + cg * CPT + cc;
-                xr[cc] = ar[p * S + c];  // (one address per column group: a broadcast)
-                xi[cc] = ai[p * S + c];
-                yr[cc] = ar[row * S + c];
-                yi[cc] = ai[row * S + c];
-            }
-            __syncthreads();  // every wave has read column jc and row p
-#pragma unroll
-            for (int cc = 0; cc < CPT; ++cc) {
-                const int c = j0 + cg * CPT + cc;
-                double tr = ir, ti = ii;  // the new pivot row: a[p][c] / piv, 1 / piv in column jc
-                if (c != jc) {
-                    tr = xr[cc] * ir - xi[cc] * ii;
-                    ti = xr[cc] * ii + xi[cc] * ir;
-                }
-                double nr = tr, ni = ti;
-                if (row != p) {
-                    const double mr = fr * tr - fi * ti, mi = fr * ti + fi * tr;
-                    nr = c == jc ? -mr : yr[cc] - mr;
-                    ni = c == jc ? -mi : yi[cc] - mi;
-                }
-                ar[row * S + c] = nr;
-                ai[row * S + c] = ni;
-            }
-            if (row == p) {
-                used = true;
-                if (cg == 0) {
-                    prow[jc] = p;
-                    jrow[p] = jc;
-                }
-            }
-        }
-        if constexpr (TR > 1) {
-            // the rank-16 update of the other column tiles
-            const int tp = j0 >> 4, q = lane >> 4, c16 = lane & 15;
-            const bool busy = wave < TR && wave * 16 < n;  // (wave-uniform; TR <= 4 waves)
-            double wr[4], wi[4], br[TR > 1 ? TR - 1 : 1][4], bi[TR > 1 ? TR - 1 : 1][4];
-            green_d4 accr[TR > 1 ? TR - 1 : 1], acci[TR > 1 ? TR - 1 : 1];
-            __syncthreads();  // the panel's columns are W, its pivot rows are known
-            if (busy) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    wr[ks] = ar[(wave * 16 + c16) * S + j0 + 4 * ks + q];
-                    wi[ks] = ai[(wave * 16 + c16) * S + j0 + 4 * ks + q];
-                }
-#pragma unroll
-                for (int t = 0; t < TR - 1; ++t) {
-                    const int tj = t < tp ? t : t + 1;  // (uniform)
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) {
-                        const int kk = 4 * ks + q;
-                        const int prw = kk < jn ? prow[j0 + kk] : 0;  // (steps beyond n: no pivot row, a zero operand)
-                        br[t][ks] = kk < jn ? ar[prw * S + tj * 16 + c16] : 0.0;
-                        bi[t][ks] = kk < jn ? ai[prw * S + tj * 16 + c16] : 0.0;
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int ri = wave * 16 + q + 4 * r;
-                        const bool taken = jrow[ri] >= j0;  // a pivot row of this panel starts from zero
-                        accr[t][r] = taken ? 0.0 : ar[ri * S + tj * 16 + c16];
-                        acci[t][r] = taken ? 0.0 : ai[ri * S + tj * 16 + c16];
-                    }
-                }
-            }
-            __syncthreads();  // every operand is in registers
-            if (busy) {
-#pragma unroll
-                for (int t = 0; t < TR - 1; ++t) {
-                    const int tj = t < tp ? t : t + 1;
-                    if (tj * 16 < n) {  // (uniform: the columns beyond n are zero and stay zero)
-#pragma unroll
-                        for (int ks = 0; ks < 4; ++ks) {
-                            accr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[ks], br[t][ks], accr[t], 0, 0, 0);
-                            acci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[ks], bi[t][ks], acci[t], 0, 0, 0);
-                            accr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wi[ks], bi[t][ks], accr[t], 0, 0, 1);  // - w_i b_i
-                            acci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wi[ks], br[t][ks], acci[t], 0, 0, 0);
-                        }
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int ri = wave * 16 + q + 4 * r;
-                            ar[ri * S + tj * 16 + c16] = accr[t][r];
-                            ai[ri * S + tj * 16 + c16] = acci[t][r];
-                        }
-                    }
-                }
-            }
-        }
-    }
+    bool singular = zgj_invert<NP, TEAM>(ar, ai, prow, jrow, n, tt);
     __syncthreads();
     // inverse[r][s] = storage[prow[r]][jrow[s]], over NK
     if (live) {
@@ -351,7 +221,7 @@ __global__ void __launch_bounds__(DM_THREADS) green_invert_kernel(const double2*
             if (valid) {
                 const int at = prow[r] * S + jrow[s];
                 v = make_double2(ar[at] / nk_total, ai[at] / nk_total);
-                singular |= !(fabs(v.x) <= 1.79769313486231570815e308 && fabs(v.y) <= 1.79769313486231570815e308);
+                singular |= !(fabs(v.x) <= DBL_MAX && fabs(v.y) <= DBL_MAX);
             }
             Pj[e] = v;
         }
@@ -394,7 +264,7 @@ __global__ void __launch_bounds__(256) green_scatter_kernel(const double2* __res
         if (valid) {
             const double2 a = A[((size_t)k * zt + zi) * nn + e];
             v = make_double2(a.x / nk_total, a.y / nk_total);
-            singular |= !(fabs(v.x) <= 1.79769313486231570815e308 && fabs(v.y) <= 1.79769313486231570815e308);
+            singular |= !(fabs(v.x) <= DBL_MAX && fabs(v.y) <= DBL_MAX);
         }
         P[((size_t)j * zt + zi) * nn + e] = v;
     }

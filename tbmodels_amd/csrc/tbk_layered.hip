@@ -236,8 +236,8 @@ int layered_slab(LayeredFamily& fam, tbk_model* m, int64_t k_base, int axis, int
     MeshStreams streams;
     TBK_CHECK(streams.add(m));
     SpanRecorder* ev = &streams.used.back().ev;
-    const size_t z_bytes = surf_align256((size_t)n_z * sizeof(double2)), tw_bytes = h_tw.size() * sizeof(double);
-    const size_t layer_bytes = surf_align256((size_t)chunk * N * N * sizeof(double2)), flag_bytes = (size_t)fam.n_words * sizeof(unsigned long long);
+    const size_t z_bytes = dos_align256((size_t)n_z * sizeof(double2)), tw_bytes = h_tw.size() * sizeof(double);
+    const size_t layer_bytes = dos_align256((size_t)chunk * N * N * sizeof(double2)), flag_bytes = (size_t)fam.n_words * sizeof(unsigned long long);
     const bool library = fam.library(m->eigensolver);
     const size_t extra_bytes = fam.extra_bytes(chunk, m->n_cu), ws_bytes = fam.workspace_bytes(library, chunk, m->n_cu);
     TBK_CHECK(mesh_reserve(m->ws_mesh_k, h_k.size() * sizeof(double), fam.family, "the k list with its samples along the stacking axis"));

@@ -39,10 +39,9 @@
 
 #include "tbk_occ.h"
 #include "tbk_pair.h"
+#include "tbk_zmfma.h"
 
 namespace {
-
-typedef double opt_d4 __attribute__((ext_vector_type(4)));
 
 constexpr int OPT_THREADS = PAIR_THREADS;
 constexpr int OPT_GROUP = 256;                          // mesh points per summation group
@@ -123,7 +122,7 @@ __device__ __forceinline__ int opt_at(int o, int c) {
 // (cr, ci) += X^H Y for the wave's tile row ti and tiles tj0 ... tj0 + TPW - 1: `steps` MFMA steps of four rows of the planes
 template <int NP, int TPW>
 __device__ __forceinline__ void opt_product(const double* __restrict__ xr, const double* __restrict__ xi, const double* __restrict__ yr,
-                                            const double* __restrict__ yi, int steps, int ti, int tj0, int lane, opt_d4 (&cr)[TPW], opt_d4 (&ci)[TPW]) {
+                                            const double* __restrict__ yi, int steps, int ti, int tj0, int lane, zd4 (&cr)[TPW], zd4 (&ci)[TPW]) {
     const int l15 = lane & 15, lq = lane >> 4;
 #pragma unroll 1
     for (int s = 0; s < steps; ++s) {
@@ -134,10 +133,7 @@ __device__ __forceinline__ void opt_product(const double* __restrict__ xr, const
         for (int t = 0; t < TPW; ++t) {
             const int ib = opt_at<NP>(o, (tj0 + t) * 16 + l15);
             const double br = yr[ib], bi = yi[ib];
-            cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br, cr[t], 0, 0, 0);
-            cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, bi, cr[t], 0, 0, 0);
-            ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi, ci[t], 0, 0, 0);
-            ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br, ci[t], 0, 0, 1);  // - Xi^T Yr
+            zmfma_ahb(ar, ai, br, bi, cr[t], ci[t]);
         }
     }
 }
@@ -239,7 +235,7 @@ __global__ void __launch_bounds__(OPT_THREADS, NP == 64 ? 1 : 2) opt_fused_kerne
             gb[t] = gk[cs];
         }
     }
-    opt_d4 vr[DIM][TPW], vi[DIM][TPW];
+    zd4 vr[DIM][TPW], vi[DIM][TPW];
 #pragma unroll
     for (int a = 0; a < DIM; ++a) {
         const double2* Da = g.D + (size_t)ks * g.d_sk + (size_t)a * g.d_sa;
@@ -253,9 +249,9 @@ __global__ void __launch_bounds__(OPT_THREADS, NP == 64 ? 1 : 2) opt_fused_kerne
         }
         __syncthreads();
         // W = (D^a)^H U = D^a U
-        opt_d4 wr[TPW], wi[TPW];
+        zd4 wr[TPW], wi[TPW];
 #pragma unroll
-        for (int t = 0; t < TPW; ++t) wr[t] = wi[t] = opt_d4{0.0, 0.0, 0.0, 0.0};
+        for (int t = 0; t < TPW; ++t) wr[t] = wi[t] = zd4{0.0, 0.0, 0.0, 0.0};
         opt_product<NP, TPW>(br, bi, ur, ui, steps, ti, tj0, lane, wr, wi);
         __syncthreads();  // every wave has read D^a
 #pragma unroll
@@ -269,7 +265,7 @@ __global__ void __launch_bounds__(OPT_THREADS, NP == 64 ? 1 : 2) opt_fused_kerne
         __syncthreads();
         // V^a = U^H W
 #pragma unroll
-        for (int t = 0; t < TPW; ++t) vr[a][t] = vi[a][t] = opt_d4{0.0, 0.0, 0.0, 0.0};
+        for (int t = 0; t < TPW; ++t) vr[a][t] = vi[a][t] = zd4{0.0, 0.0, 0.0, 0.0};
         opt_product<NP, TPW>(ur, ui, br, bi, steps, ti, tj0, lane, vr[a], vi[a]);
         if (g.pos != nullptr) {
             // convention 1: V^a += i (E_b - E_b') (U^H (pos_a o U))[b][b'], the rows of U scaled while staging
@@ -287,7 +283,7 @@ __global__ void __launch_bounds__(OPT_THREADS, NP == 64 ? 1 : 2) opt_fused_kerne
             }
             __syncthreads();
 #pragma unroll
-            for (int t = 0; t < TPW; ++t) wr[t] = wi[t] = opt_d4{0.0, 0.0, 0.0, 0.0};
+            for (int t = 0; t < TPW; ++t) wr[t] = wi[t] = zd4{0.0, 0.0, 0.0, 0.0};
             opt_product<NP, TPW>(ur, ui, br, bi, steps, ti, tj0, lane, wr, wi);
 #pragma unroll
             for (int t = 0; t < TPW; ++t)

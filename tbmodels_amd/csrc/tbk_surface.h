@@ -1,6 +1,6 @@
 // tbk_surface.h -- what the kernels and launchers of tbk_surface.hip (the decimation, the transmission), tbk_ensemble.hip and
 // tbk_channels.hip (the transmission of an ensemble of devices, its eigenvalues) and tbk_device_green.hip (the layer-resolved Green's
-// functions of the device) share: the geometry of a workgroup's planes, the inversion, the products, the iteration of the decimation,
+// functions of the device) share: the geometry of a workgroup's planes, the products, the iteration of the decimation,
 // the layer body and the closing trace of the sweep, the constants, and the small inline helpers of the launchers.  The device
 // templates sit in an unnamed namespace: each translation unit instantiates its own.  The host drivers of the whole calls, their
 // helpers and surface_layers_kernel exist once, in tbk_layered.hip (tbk_layered.h).
@@ -14,10 +14,9 @@
 #include <rocsolver/rocsolver.h>
 
 #include "tbk_resident.h"
+#include "tbk_zmfma.h"
 
 namespace {
-
-typedef double surf_d4 __attribute__((ext_vector_type(4)));
 
 constexpr int64_t SURF_MAX_Z = 4096;  // energies per call (include/tbk.h)
 constexpr int SURF_OWN_MAX = 64;      // rows of a principal layer the decimation kernel takes
@@ -25,11 +24,8 @@ constexpr int SURF_LIB_MAX = 1024;    // ... and the library route above it (or 
 constexpr int SURF_MAX_ITERATIONS = 4096;
 constexpr unsigned long long SURF_NO_FLAG = ~0ull;
 constexpr size_t SURF_CHUNK_BUDGET = size_t(256) << 20;  // the results of one chunk, and the H(k) samples of one chunk
-constexpr double SURF_DBL_MAX = 1.79769313486231570815e308;
 constexpr double SURF_PI = 3.14159265358979323846;
 constexpr const char* SURF_FAMILY = "the surface Green's function";
-
-inline size_t surf_align256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 
 // What sits where, per template.  X, Y: two matrices in LDS, planes (re, im) of NP rows NP + 1 doubles apart -- the elimination runs
 // in X, its un-permuted result g goes to Y, X then holds T.  alpha, beta, e, es, et: in LDS behind them up to NP = 32 (seven
@@ -49,139 +45,6 @@ struct SurfGeom {
     static constexpr size_t slot_doubles = GLOBAL ? (size_t)10 * NP * NP : 0;
 };
 
-// ---- the inversion: green_invert_kernel's elimination (tbk_green.hip) for ONE matrix per workgroup ------------------
-// Gauss-Jordan in place with implicit partial pivoting on |re| + |im| (ties: the lowest row; a NaN counts as +inf), in panels of 16
-// pivots; the panel's columns by rank-1 VALU updates, every other column tile by a rank-16 update on the matrix pipe.  jrow must be
-// -1 and the planes written before the call (its first barrier orders them); afterwards, behind a barrier of the caller's,
-// inverse[r][s] = storage[prow[r]][jrow[s]].  Returns whether a pivot was exactly zero (the same value on every thread).
-template <int NP, int THREADS>
-__device__ __forceinline__ bool surf_invert(double* ar, double* ai, int* prow, int* jrow, int n, int tid) {
-    constexpr int CG = THREADS / NP;  // column groups of a panel
-    constexpr int CPT = 16 / CG;      // panel columns per thread
-    constexpr int S = NP + 1;
-    constexpr int TR = NP / 16;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int row = tid & (NP - 1), cg = tid / NP;
-    bool used = row >= n, singular = false;
-    for (int j0 = 0; j0 < n; j0 += 16) {
-        const int jn = n - j0 < 16 ? n - j0 : 16;
-        for (int jj = 0; jj < jn; ++jj) {
-            const int jc = j0 + jj;
-            __syncthreads();  // column jc is up to date
-            const double fr = ar[row * S + jc], fi = ai[row * S + jc];
-            double best = fabs(fr) + fabs(fi);
-            if (!(best >= 0.0)) best = __builtin_inf();
-            if (used) best = -1.0;
-            int p = row;
-#pragma unroll
-            for (int off = NP / 2; off > 0; off >>= 1) {
-                const double ob = __shfl_xor(best, off, 64);
-                const int op = __shfl_xor(p, off, 64);
-                if (ob > best || (ob == best && op < p)) {
-                    best = ob;
-                    p = op;
-                }
-            }
-            // (p is a row below n that no step has taken: at least one is left, and taken rows and padding compare as -1)
-            const int src = (lane & ~(NP - 1)) | p;
-            const double pr = __shfl(fr, src, 64), pi = __shfl(fi, src, 64);
-            singular |= best == 0.0;
-            const double den = pr * pr + pi * pi;
-            const double ir = pr / den, ii = -pi / den;  // 1 / pivot
-            double xr[CPT], xi[CPT], yr[CPT], yi[CPT];
-#pragma unroll
-            for (int cc = 0; cc < CPT; ++cc) {
-                const int c = j0 + cg * CPT + cc;
-                xr[cc] = ar[p * S + c];
-                xi[cc] = ai[p * S + c];
-                yr[cc] = ar[row * S + c];
-                yi[cc] = ai[row * S + c];
-            }
-            __syncthreads();  // every wave has read column jc and row p
-#pragma unroll
-            for (int cc = 0; cc < CPT; ++cc) {
-                const int c = j0 + cg * CPT + cc;
-                double tr = ir, ti = ii;  // the new pivot row: a[p][c] / piv, 1 / piv in column jc
-                if (c != jc) {
-                    tr = xr[cc] * ir - xi[cc] * ii;
-                    ti = xr[cc] * ii + xi[cc] * ir;
-                }
-                double nr = tr, ni = ti;
-                if (row != p) {
-                    const double mr = fr * tr - fi * ti, mi = fr * ti + fi * tr;
-                    nr = c == jc ? -mr : yr[cc] - mr;
-                    ni = c == jc ? -mi : yi[cc] - mi;
-                }
-                ar[row * S + c] = nr;
-                ai[row * S + c] = ni;
-            }
-            if (row == p) {
-                used = true;
-                if (cg == 0) {
-                    prow[jc] = p;
-                    jrow[p] = jc;
-                }
-            }
-        }
-        if constexpr (TR > 1) {
-            // the rank-16 update of the other column tiles: T C = mask(C) + W C[pivot rows]
-            const int tp = j0 >> 4, q = lane >> 4, c16 = lane & 15;
-            const bool busy = wave < TR && wave * 16 < n;  // (wave-uniform)
-            double wr[4], wi[4], br[TR - 1][4], bi[TR - 1][4];
-            surf_d4 accr[TR - 1], acci[TR - 1];
-            __syncthreads();  // the panel's columns are W, its pivot rows are known
-            if (busy) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    wr[ks] = ar[(wave * 16 + c16) * S + j0 + 4 * ks + q];
-                    wi[ks] = ai[(wave * 16 + c16) * S + j0 + 4 * ks + q];
-                }
-#pragma unroll
-                for (int t = 0; t < TR - 1; ++t) {
-                    const int tj = t < tp ? t : t + 1;  // (uniform)
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) {
-                        const int kk = 4 * ks + q;
-                        const int prw = kk < jn ? prow[j0 + kk] : 0;  // (steps beyond n: no pivot row, a zero operand)
-                        br[t][ks] = kk < jn ? ar[prw * S + tj * 16 + c16] : 0.0;
-                        bi[t][ks] = kk < jn ? ai[prw * S + tj * 16 + c16] : 0.0;
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int ri = wave * 16 + q + 4 * r;
-                        const bool taken = jrow[ri] >= j0;  // a pivot row of this panel starts from zero
-                        accr[t][r] = taken ? 0.0 : ar[ri * S + tj * 16 + c16];
-                        acci[t][r] = taken ? 0.0 : ai[ri * S + tj * 16 + c16];
-                    }
-                }
-            }
-            __syncthreads();  // every operand is in registers
-            if (busy) {
-#pragma unroll
-                for (int t = 0; t < TR - 1; ++t) {
-                    const int tj = t < tp ? t : t + 1;
-                    if (tj * 16 < n) {  // (uniform: the columns beyond n are zero and stay zero)
-#pragma unroll
-                        for (int ks = 0; ks < 4; ++ks) {
-                            accr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[ks], br[t][ks], accr[t], 0, 0, 0);
-                            acci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wr[ks], bi[t][ks], acci[t], 0, 0, 0);
-                            accr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wi[ks], bi[t][ks], accr[t], 0, 0, 1);  // - w_i b_i
-                            acci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wi[ks], br[t][ks], acci[t], 0, 0, 0);
-                        }
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int ri = wave * 16 + q + 4 * r;
-                            ar[ri * S + tj * 16 + c16] = accr[t][r];
-                            ai[ri * S + tj * 16 + c16] = acci[t][r];
-                        }
-                    }
-                }
-            }
-        }
-    }
-    return singular;
-}
-
 // The same integer, opaque to the optimiser and not to be moved out of a loop: offsets derived from it are computed where they are
 // used.  Without it every address of the iteration's tiles -- 16 per plane, ten planes, 64 bits each at NP = 64 -- is hoisted in
 // front of the item loop and the kernel spills: 2 800 bytes of scratch per thread at NP = 64 in the first build, which
@@ -193,18 +56,20 @@ __device__ __forceinline__ int surf_fresh(int x) {
 }
 
 // ---- the products -------------------------------------------------------------------------------------------------------------------
-// C = A B of two NP x NP complex matrices in planes (pitches SA, SB), zero beyond n: the wave's NT tiles (tile row (wave NT) / TR,
-// tile columns from (wave NT) % TR on) into registers.  Lane (q = lane / 16, c = lane % 16) feeds A[16 tr + c][k + q], B[k + q][16 tc + c]
-// and holds C[16 tr + q + 4 r][16 tc + c], r = 0 ... 3.  Tiles and K blocks beyond n are skipped (wave-uniform): they are zero.
-template <int NP, int NT, int SA, int SB>
+// C = op(A) op(B) of two NP x NP complex matrices in planes (pitches SA, SB), zero beyond n: the wave's NT tiles (tile row
+// (wave NT) / TR, tile columns from (wave NT) % TR on) into registers.  Lane (q = lane / 16, c = lane % 16) feeds A[16 tr + c][k + q],
+// B[k + q][16 tc + c] and holds C[16 tr + q + 4 r][16 tc + c], r = 0 ... 3.  AH: A^H in place of A, the fragment taken from A's
+// columns and conjugated, conj(A[k + q][16 tr + c]); BH: B^H likewise, conj(B[16 tc + c][k + q]).  Tiles and K blocks beyond n are
+// skipped (wave-uniform): they are zero.
+template <int NP, int NT, int SA, int SB, bool AH = false, bool BH = false>
 __device__ __forceinline__ void surf_product(const double* ar, const double* ai, const double* br, const double* bi, int n, int wave, int lane,
-                                             surf_d4 (&cr)[NT], surf_d4 (&ci)[NT]) {
+                                             zd4 (&cr)[NT], zd4 (&ci)[NT]) {
     constexpr int TR = NP / 16;
     lane = surf_fresh(lane);
     const int q = lane >> 4, c16 = lane & 15;
     const int tr = (wave * NT) / TR, tc0 = (wave * NT) % TR;
 #pragma unroll
-    for (int t = 0; t < NT; ++t) cr[t] = ci[t] = surf_d4{0.0, 0.0, 0.0, 0.0};
+    for (int t = 0; t < NT; ++t) cr[t] = ci[t] = zd4{0.0, 0.0, 0.0, 0.0};
     if (tr * 16 >= n) return;
 #pragma unroll 1
     for (int kb = 0; kb < TR; ++kb) {  // (not unrolled: the loads of every K block ahead of the first MFMA do not fit the registers)
@@ -212,49 +77,14 @@ __device__ __forceinline__ void surf_product(const double* ar, const double* ai,
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const int kk = kb * 16 + 4 * ks + q;
-                const double a_r = ar[(tr * 16 + c16) * SA + kk], a_i = ai[(tr * 16 + c16) * SA + kk];
+                const int ia = AH ? kk * SA + tr * 16 + c16 : (tr * 16 + c16) * SA + kk;
+                const double a_r = ar[ia], a_i = AH ? -ai[ia] : ai[ia];
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     if ((tc0 + t) * 16 < n) {
-                        const double b_r = br[kk * SB + (tc0 + t) * 16 + c16], b_i = bi[kk * SB + (tc0 + t) * 16 + c16];
-                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_r, b_r, cr[t], 0, 0, 0);
-                        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_r, b_i, ci[t], 0, 0, 0);
-                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_i, b_i, cr[t], 0, 0, 1);  // - a_i b_i
-                        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_i, b_r, ci[t], 0, 0, 0);
-                    }
-                }
-            }
-        }
-    }
-}
-
-// C = A B^H: surf_product with the B fragment taken from B's rows and conjugated.  Lane (q, c) feeds A[16 tr + c][k + q] and
-// conj(B[16 tc + c][k + q]); the tiles, their owners and the skipped blocks are surf_product's.
-template <int NP, int NT, int SA, int SB>
-__device__ __forceinline__ void surf_product_h(const double* ar, const double* ai, const double* br, const double* bi, int n, int wave, int lane,
-                                               surf_d4 (&cr)[NT], surf_d4 (&ci)[NT]) {
-    constexpr int TR = NP / 16;
-    lane = surf_fresh(lane);
-    const int q = lane >> 4, c16 = lane & 15;
-    const int tr = (wave * NT) / TR, tc0 = (wave * NT) % TR;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) cr[t] = ci[t] = surf_d4{0.0, 0.0, 0.0, 0.0};
-    if (tr * 16 >= n) return;
-#pragma unroll 1
-    for (int kb = 0; kb < TR; ++kb) {
-        if (kb * 16 < n) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int kk = kb * 16 + 4 * ks + q;
-                const double a_r = ar[(tr * 16 + c16) * SA + kk], a_i = ai[(tr * 16 + c16) * SA + kk];
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    if ((tc0 + t) * 16 < n) {
-                        const double b_r = br[((tc0 + t) * 16 + c16) * SB + kk], b_i = -bi[((tc0 + t) * 16 + c16) * SB + kk];
-                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_r, b_r, cr[t], 0, 0, 0);
-                        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_r, b_i, ci[t], 0, 0, 0);
-                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_i, b_i, cr[t], 0, 0, 1);  // - a_i b_i
-                        ci[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_i, b_r, ci[t], 0, 0, 0);
+                        const int ib = BH ? ((tc0 + t) * 16 + c16) * SB + kk : kk * SB + (tc0 + t) * 16 + c16;
+                        const double b_r = br[ib], b_i = BH ? -bi[ib] : bi[ib];
+                        zmfma_ab(a_r, a_i, b_r, b_i, cr[t], ci[t]);
                     }
                 }
             }
@@ -264,7 +94,7 @@ __device__ __forceinline__ void surf_product_h(const double* ar, const double* a
 
 // the wave's tiles of a product into a matrix (ADD: added to it); every element has one owner, whatever the matrix
 template <int NP, int NT, int SD, bool ADD>
-__device__ __forceinline__ void surf_tiles(double* dr, double* di, int n, int wave, int lane, const surf_d4 (&cr)[NT], const surf_d4 (&ci)[NT]) {
+__device__ __forceinline__ void surf_tiles(double* dr, double* di, int n, int wave, int lane, const zd4 (&cr)[NT], const zd4 (&ci)[NT]) {
     constexpr int TR = NP / 16;
     lane = surf_fresh(lane);
     const int q = lane >> 4, c16 = lane & 15;
@@ -323,8 +153,8 @@ __device__ __forceinline__ void surf_norms(const double* ar, const double* ai, c
 #pragma unroll 4
     for (int r = 0; r < NP; ++r) {
         double a = rown[r], b = rown[NP + r];
-        if (!(a <= SURF_DBL_MAX)) a = __builtin_inf();
-        if (!(b <= SURF_DBL_MAX)) b = __builtin_inf();
+        if (!(a <= DBL_MAX)) a = __builtin_inf();
+        if (!(b <= DBL_MAX)) b = __builtin_inf();
         na = a > na ? a : na;
         nb = b > nb ? b : nb;
     }
@@ -437,7 +267,7 @@ __device__ __forceinline__ int surf_iterate(const SurfPlanes& P, double2 zz, int
     for (;;) {
         ++it;
         surf_form<NP, THREADS, SM>(xr, xi, er, ei, zz, n, tid, jrow);
-        const bool zero_pivot = surf_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
+        const bool zero_pivot = zgj_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
         __syncthreads();
 #pragma unroll 2
         for (int e = tid; e < NP * NP; e += THREADS) {  // g into Y, the permutations undone
@@ -452,7 +282,7 @@ __device__ __forceinline__ int surf_iterate(const SurfPlanes& P, double2 zz, int
             yi[i * S + c] = vi;
         }
         __syncthreads();
-        surf_d4 tr[NT], ti[NT], p1r[NT], p1i[NT], p4r[NT], p4i[NT];
+        zd4 tr[NT], ti[NT], p1r[NT], p1i[NT], p4r[NT], p4i[NT];
         surf_product<NP, NT, S, SM>(yr, yi, alr, ali, n, wave, lane, tr, ti);  // T = g alpha
         surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, tr, ti);
         __syncthreads();
@@ -474,7 +304,7 @@ __device__ __forceinline__ int surf_iterate(const SurfPlanes& P, double2 zz, int
         __syncthreads();
         surf_norms<NP, THREADS, SM>(alr, ali, ber, bei, tid, red, rown, na, nb);
         const double size = na > nb ? na : nb;
-        if (zero_pivot || !(size <= SURF_DBL_MAX)) {
+        if (zero_pivot || !(size <= DBL_MAX)) {
             status = 1;
             break;
         }
@@ -511,7 +341,7 @@ __host__ __device__ __forceinline__ size_t trans_v_layer(const double*, int n) {
 // the wave's tiles of a product into D = (H00 + V) + product (zero beyond n); h0, v: [n][n] in global memory (v: or [n]), read once
 template <int NP, int NT, int SD, typename VT>
 __device__ __forceinline__ void trans_tiles_onsite(double* dr, double* di, const double2* __restrict__ h0, const VT* __restrict__ v, int n, int wave,
-                                                   int lane, const surf_d4 (&cr)[NT], const surf_d4 (&ci)[NT]) {
+                                                   int lane, const zd4 (&cr)[NT], const zd4 (&ci)[NT]) {
     constexpr int TR = NP / 16;
     lane = surf_fresh(lane);
     const int q = lane >> 4, c16 = lane & 15;
@@ -538,7 +368,7 @@ __device__ __forceinline__ void trans_tiles_onsite(double* dr, double* di, const
 
 // the wave's tiles of a product into g [n][n] complex in global memory (rows and columns below n); one owner per element
 template <int NP, int NT>
-__device__ __forceinline__ void trans_tiles_stack(double2* g, int n, int wave, int lane, const surf_d4 (&cr)[NT], const surf_d4 (&ci)[NT]) {
+__device__ __forceinline__ void trans_tiles_stack(double2* g, int n, int wave, int lane, const zd4 (&cr)[NT], const zd4 (&ci)[NT]) {
     constexpr int TR = NP / 16;
     lane = surf_fresh(lane);
     const int q = lane >> 4, c16 = lane & 15;
@@ -610,7 +440,7 @@ __device__ __forceinline__ bool trans_layer(const SurfPlanes& P, const double2* 
         }
     }
     surf_form<NP, THREADS, SM>(xr, xi, dr, di, zz, n, tid, jrow);
-    bad |= surf_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
+    bad |= zgj_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
     __syncthreads();
 #pragma unroll 2
     for (int e = tid; e < NP * NP; e += THREADS) {  // g_p into Y, the permutations undone
@@ -620,7 +450,7 @@ __device__ __forceinline__ bool trans_layer(const SurfPlanes& P, const double2* 
             const int at = prow[i] * S + jrow[c];
             vr = xr[at];
             vi = xi[at];
-            bad |= !(fabs(vr) <= SURF_DBL_MAX && fabs(vi) <= SURF_DBL_MAX);
+            bad |= !(fabs(vr) <= DBL_MAX && fabs(vi) <= DBL_MAX);
             if (STACK) stack[(size_t)2 * p * n * n + (size_t)i * n + c] = make_double2(vr, vi);
         }
         yr[i * S + c] = vr;
@@ -631,7 +461,7 @@ __device__ __forceinline__ bool trans_layer(const SurfPlanes& P, const double2* 
         }
     }
     __syncthreads();
-    surf_d4 cr[NT], ci[NT];
+    zd4 cr[NT], ci[NT];
     if (p > 0) {
         surf_product<NP, NT, SM, SM>(h10r, h10i, pr, pi, n, wave, lane, cr, ci);  // T = H01^H P_{p-1}
         surf_tiles<NP, NT, S, false>(xr, xi, n, wave, lane, cr, ci);
@@ -676,7 +506,7 @@ __device__ __forceinline__ bool trans_closing(const SurfPlanes& P, int n, int ti
             ar = pr[c * SM + i];
             ai = -pi[c * SM + i];
             const double2 v = make_double2(pr[i * SM + c], pi[i * SM + c]);
-            bad |= !(fabs(v.x) <= SURF_DBL_MAX && fabs(v.y) <= SURF_DBL_MAX);
+            bad |= !(fabs(v.x) <= DBL_MAX && fabs(v.y) <= DBL_MAX);
             if (g_out != nullptr) g_out[(size_t)i * n + c] = v;
         }
         xr[i * S + c] = gr;
@@ -686,7 +516,7 @@ __device__ __forceinline__ bool trans_closing(const SurfPlanes& P, int n, int ti
     }
     __syncthreads();
     {
-        surf_d4 cr[NT], ci[NT];
+        zd4 cr[NT], ci[NT];
         surf_product<NP, NT, S, SM>(xr, xi, pr, pi, n, wave, lane, cr, ci);  // Gamma_R P_M into Y
         surf_tiles<NP, NT, S, false>(yr, yi, n, wave, lane, cr, ci);
         __syncthreads();  // Gamma_R has been read

@@ -17,7 +17,7 @@
 //                            convention 2): H_m = (1 / (2 L + 1)) sum_j exp(-2 pi i m j / (2 L + 1)) H(kp, j / (2 L + 1)), the twiddles
 //                            from a host table.  No line of the H(k) path knows about surfaces.
 //   surface_decimate_kernel  one workgroup owns one (kp, z) for the whole iteration: the inversion is green_invert_kernel's panelled
-//                            Gauss-Jordan (a second copy on LDS planes, surf_invert), the six products per iteration run on
+//                            Gauss-Jordan (zgj_invert of tbk_zmfma.h on the X planes), the six products per iteration run on
 //                            v_mfma_f64_16x16x4_f64, four real MFMAs per complex tile and K step.  N <= 64.
 //   surf_lib_chunk           65 <= N <= 1024, and on request: the same iteration in lockstep batches of a fixed number of members on
 //                            rocblas_zgemm_strided_batched and rocsolver_zgetrf / zgetri_strided_batched, with five small kernels.
@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(SurfGeom<NP>::THREADS)
             const double* mi = which == 0 ? esi : which == 1 ? eti : ei;
             double* out = which == 0 ? out_b : which == 1 ? out_t : out_m;
             surf_form<NP, THREADS, SM>(xr, xi, mr, mi, zz, n, tid, jrow);
-            bad |= surf_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
+            bad |= zgj_invert<NP, THREADS>(xr, xi, prow, jrow, n, tid);
             __syncthreads();
             // (every element of the inverse is looked at in both modes: the same inputs are singular with and without spectral)
             double2* o = reinterpret_cast<double2*>(out) + (size_t)w * n * n;
@@ -79,7 +79,7 @@ __global__ void __launch_bounds__(SurfGeom<NP>::THREADS)
                 const int r = e / n, s = e - r * n;
                 const int at = prow[r] * S + jrow[s];
                 const double2 v = make_double2(xr[at], xi[at]);
-                bad |= !(fabs(v.x) <= SURF_DBL_MAX && fabs(v.y) <= SURF_DBL_MAX);
+                bad |= !(fabs(v.x) <= DBL_MAX && fabs(v.y) <= DBL_MAX);
                 if (!spectral)
                     o[e] = v;
                 else if (r == s)
@@ -133,8 +133,8 @@ struct SurfShape {
     int64_t n_z = 0;
     bool spectral = false;
     size_t item_doubles() const { return spectral ? (size_t)n : (size_t)n * n * 2; }  // of one of the three results
-    size_t out_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * item_doubles() * sizeof(double)); }
-    size_t it_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * sizeof(int32_t)); }
+    size_t out_bytes(int64_t nk) const { return dos_align256((size_t)nk * n_z * item_doubles() * sizeof(double)); }
+    size_t it_bytes(int64_t nk) const { return dos_align256((size_t)nk * n_z * sizeof(int32_t)); }
     size_t result_bytes(int64_t nk) const { return 3 * out_bytes(nk) + it_bytes(nk); }  // bottom, top, bulk, iterations
     int64_t auto_chunk(int64_t nk) const {
         const size_t per_k = (size_t)n_z * (3 * item_doubles() * sizeof(double) + sizeof(int32_t));
@@ -194,22 +194,22 @@ struct SurfLib {
     int* active = nullptr;  // one word: members still iterating
     double* thr = nullptr;  // [batch]
     static size_t bytes(int n, int batch) {
-        return (size_t)SURF_LIB_MATRICES * surf_align256((size_t)batch * n * n * sizeof(double2)) + surf_align256((size_t)batch * n * sizeof(int)) +
-               surf_align256((size_t)(3 * batch + 1) * sizeof(int)) + surf_align256((size_t)batch * sizeof(double));
+        return (size_t)SURF_LIB_MATRICES * dos_align256((size_t)batch * n * n * sizeof(double2)) + dos_align256((size_t)batch * n * sizeof(int)) +
+               dos_align256((size_t)(3 * batch + 1) * sizeof(int)) + dos_align256((size_t)batch * sizeof(double));
     }
     void place(char* base, int n_, int batch_, rocblas_handle h) {
         n = n_;
         batch = batch_;
         blas = h;
-        const size_t mb = surf_align256((size_t)batch * n * n * sizeof(double2));
+        const size_t mb = dos_align256((size_t)batch * n * n * sizeof(double2));
         for (int i = 0; i < SURF_LIB_MATRICES; ++i) mat[i] = reinterpret_cast<double2*>(base + (size_t)i * mb);
         char* at = base + (size_t)SURF_LIB_MATRICES * mb;
         ipiv = reinterpret_cast<int*>(at);
-        at += surf_align256((size_t)batch * n * sizeof(int));
+        at += dos_align256((size_t)batch * n * sizeof(int));
         info = reinterpret_cast<int*>(at);
         done = info + 2 * batch;
         active = done + batch;
-        at += surf_align256((size_t)(3 * batch + 1) * sizeof(int));
+        at += dos_align256((size_t)(3 * batch + 1) * sizeof(int));
         thr = reinterpret_cast<double*>(at);
     }
 };
@@ -285,8 +285,8 @@ __global__ void __launch_bounds__(256) surf_lib_norms_kernel(double2* al, double
             sa += fabs(x.x) + fabs(x.y);
             sb += fabs(y.x) + fabs(y.y);
         }
-        if (!(sa <= SURF_DBL_MAX)) sa = __builtin_inf();
-        if (!(sb <= SURF_DBL_MAX)) sb = __builtin_inf();
+        if (!(sa <= DBL_MAX)) sa = __builtin_inf();
+        if (!(sb <= DBL_MAX)) sb = __builtin_inf();
         ma = sa > ma ? sa : ma;
         mb = sb > mb ? sb : mb;
     }
@@ -308,7 +308,7 @@ __global__ void __launch_bounds__(256) surf_lib_norms_kernel(double2* al, double
         } else {
             const double size = red[0][0] > red[1][0] ? red[0][0] : red[1][0];
             const unsigned long long key = (key0 + (unsigned long long)(w / n_z) * (unsigned long long)SURF_MAX_Z + (unsigned long long)(w % n_z)) * 2ull;
-            if (info[b] != 0 || info[batch + b] != 0 || !(size <= SURF_DBL_MAX)) {
+            if (info[b] != 0 || info[batch + b] != 0 || !(size <= DBL_MAX)) {
                 v = 1;
                 if (valid) atomicMin(flag, key);
             } else if (size <= thr[b]) {
@@ -343,7 +343,7 @@ __global__ void __launch_bounds__(256) surf_lib_out_kernel(const double2* __rest
     bool bad = info[b] != 0 || info[batch + b] != 0;
     for (size_t x = (size_t)blockIdx.y * 256 + threadIdx.x; x < nn; x += (size_t)gridDim.y * 256) {
         const double2 v = g[x];
-        bad |= !(fabs(v.x) <= SURF_DBL_MAX && fabs(v.y) <= SURF_DBL_MAX);
+        bad |= !(fabs(v.x) <= DBL_MAX && fabs(v.y) <= DBL_MAX);
         const size_t i = x / n, c = x - i * n;
         if (spectral) {
             if (i == c) out[(size_t)w * n + i] = -v.y / SURF_PI;
@@ -452,9 +452,9 @@ struct TransShape {
     int n = 0, m_layers = 0;
     int64_t n_z = 0;
     bool green = false;
-    size_t t_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * sizeof(double)); }
-    size_t it_bytes(int64_t nk) const { return surf_align256((size_t)nk * n_z * sizeof(int32_t)); }
-    size_t g_bytes(int64_t nk) const { return green ? surf_align256((size_t)nk * n_z * n * n * sizeof(double2)) : 0; }
+    size_t t_bytes(int64_t nk) const { return dos_align256((size_t)nk * n_z * sizeof(double)); }
+    size_t it_bytes(int64_t nk) const { return dos_align256((size_t)nk * n_z * sizeof(int32_t)); }
+    size_t g_bytes(int64_t nk) const { return green ? dos_align256((size_t)nk * n_z * n * n * sizeof(double2)) : 0; }
     size_t result_bytes(int64_t nk) const { return t_bytes(nk) + it_bytes(nk) + g_bytes(nk); }
     int64_t auto_chunk(int64_t nk) const {  // the chunk's results and its two layers inside the budget
         const size_t nn = (size_t)n * n * sizeof(double2);
@@ -549,7 +549,7 @@ __global__ void __launch_bounds__(256) trans_lib_check_kernel(const double2* __r
     bool bad = info != nullptr && (info[b] != 0 || info[batch + b] != 0);
     for (size_t x = (size_t)blockIdx.y * 256 + threadIdx.x; x < nn; x += (size_t)gridDim.y * 256) {
         const double2 v = A[b * nn + x];
-        bad |= !(fabs(v.x) <= SURF_DBL_MAX && fabs(v.y) <= SURF_DBL_MAX);
+        bad |= !(fabs(v.x) <= DBL_MAX && fabs(v.y) <= DBL_MAX);
     }
     if (bad)
         atomicMin(flag, ((key0 + (unsigned long long)(w / n_z) * (unsigned long long)SURF_MAX_Z + (unsigned long long)(w % n_z)) * sub_n + sub) * 2ull);
