@@ -818,6 +818,40 @@ int tbk_chi_orbital_plan(int64_t nk, int n_orb, int m, int64_t n_q, int64_t part
 /* (Kernel times of these calls are booked into tbk_chi_timing's three stages: the Fermi tables, the rank-K update, the reduction of the
  * slices; its call count includes them.) */
 
+/* ---- the four-index bare static susceptibility chi_0[i][l][j][m](q) of a uniform k mesh (not in the reference) ------------------
+ * Mesh, k+q, q, E, U, mu (mode, value), T and t are those of tbk_orbital_susceptibility; convention 2 only: there is no phase table
+ * (csrc/tbk_chi.hip):
+ *     chi_0[i][l][j][m](q) = (1 / (T NK)) sum_k sum_{b b'} t(E[k][b], E[k+q][b'])
+ *                            conj(U[k][i][b]) U[k+q][l][b'] U[k][j][b] conj(U[k+q][m][b'])
+ * No spin factor; static only; the sign is tbk_susceptibility's.  chi_0[i][i][j][j] is tbk_orbital_susceptibility's chi_0[i][j].  As an
+ * m^2 x m^2 matrix with rows (i, l) and columns (j, m) chi_0(q) is Hermitian and positive semidefinite, and the output is exactly
+ * Hermitian: entries with (i, l) <= (j, m) (ascending orbital order, row-major pairs) are computed, the others are their conjugates
+ * with the imaginary part formed as 0 - x, the diagonal's imaginary part is +0.  1 <= m <= 16 distinct orbitals are selected by
+ * orbitals (int32 [m], any order; NULL with m = n_orb: all of them): chi_out is [n_q][m][m][m][m] complex (Re, Im interleaved) in
+ * the caller's order, and every entry has the bits of the same entry of any other selection that holds its four orbitals.  For given
+ * (E, U, mu, T) the bits of an entry depend on q modulo the mesh and its four orbitals alone.  |error| per component <=
+ * chi_model.tensor_tolerance.
+ * Argument errors (TBK_ERR_ARGUMENT), before any device is touched: those of tbk_orbital_susceptibility, and m > 16. */
+/* The kernels alone on an eigensystem the caller brings (E, U as for tbk_chi_orbital_from_eigensystem; U is required).  part_bytes,
+ * k_slice: as in tbk_chi_tensor_plan. */
+int tbk_chi_tensor_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu, double T,
+                                    int64_t n_q, const int64_t* q, int m, const int32_t* orbitals, int64_t part_bytes, int64_t k_slice,
+                                    double* chi_out);
+/* The whole call: tbk_susceptibility's driver -- the same mu, the same resident eigensystem, the same wait on every exit. */
+int tbk_susceptibility_tensor(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q, int n_sel,
+                              const int32_t* orbitals, double* mu_out, double* chi_out);
+/* On several devices from one process: tbk_susceptibility_multi's split, a contiguous share of the vectors per handle. */
+int tbk_susceptibility_tensor_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
+                                    int64_t n_q, const int64_t* q, int m, const int32_t* orbitals, double* mu_out, double* chi_out);
+/* How a call on nk mesh points, m <= 16 of n_orb orbitals and n_q vectors is run.  The kernel works on X[(i, j)][(l, m)] with the
+ * m (m + 1) / 2 rows i <= j and the m^2 columns, in blocks of 64 x 64: out[0] = row blocks, out[1] = blocks per vector, out[2] =
+ * k-points per slice -- k_slice, or for 0 the library's own, a function of (nk, n_orb) alone -- out[3] = slices, out[4] = vectors per
+ * batch (at most 4096; the partial sums take 16 out[3] rows' cols' bytes per vector, rows and columns padded to 64, and may take
+ * part_bytes, 0: 256 MiB; 0: not one vector fits, the call returns TBK_ERR_MEMORY), out[5] = batches.  out: int64 [6]. */
+int tbk_chi_tensor_plan(int64_t nk, int n_orb, int m, int64_t n_q, int64_t part_bytes, int64_t k_slice, int64_t* out);
+/* (Kernel times of these calls are booked into tbk_chi_timing's three stages: the Fermi tables, the two-stage kernel, the reduction of
+ * the slices; its call count includes them.) */
+
 /* ---- the lattice Berry flux and the Chern numbers of a uniform k mesh (not in the reference) -----------------------------------------
  * The Fukui-Hatsugai-Suzuki field strength (csrc/tbk_berry.hip, DESIGN.md section 18, tools/berry_model.py).  Mesh and mesh points are
  * those of tbk_occupations (dim 2 or 3), k+e_d is the mesh point with index (i_d + 1) mod n_d on axis d.  U is that of tbk_eigh

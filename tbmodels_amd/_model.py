@@ -57,6 +57,7 @@ DeviceCurrentBonds = co.namedtuple("DeviceCurrentBonds", DeviceCurrent._fields +
 Susceptibility = co.namedtuple("Susceptibility", ("mu", "q", "chi"))
 DynamicSusceptibility = co.namedtuple("DynamicSusceptibility", ("mu", "q", "omega", "chi"))
 OrbitalSusceptibility = co.namedtuple("OrbitalSusceptibility", ("mu", "q", "orbitals", "chi"))
+SusceptibilityTensor = co.namedtuple("SusceptibilityTensor", ("mu", "q", "orbitals", "chi"))
 BerryFlux = co.namedtuple("BerryFlux", ("bands", "planes", "flux", "chern", "link_min"))
 OpticalConductivity = co.namedtuple("OpticalConductivity", ("mu", "omega", "sigma"))
 
@@ -2036,6 +2037,31 @@ class Model:
             sigma = np.einsum("ia,wij,jc->wac", cell, sigma, cell) / abs(np.linalg.det(cell))
         return OpticalConductivity(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), frequencies, sigma)
 
+    def _orbital_selection_argument(self, orbitals):
+        """The checks of ``orbitals`` that ``orbital_susceptibility`` and ``susceptibility_tensor`` share: ``int64 (m,)`` distinct
+        indices in ``[0, size)`` in the caller's order (``None``: all of them in order) or ``ValueError``."""
+        if orbitals is None:
+            selected = np.arange(self.size, dtype=np.int64)
+        else:
+            if isinstance(orbitals, (str, bytes)):
+                raise ValueError("orbitals must be an integer array of shape (m,), got {!r}".format(orbitals))
+            try:
+                selected = np.asarray(orbitals)
+            except (TypeError, ValueError):
+                raise ValueError("orbitals must be an integer array of shape (m,)") from None
+            if selected.dtype.kind not in "iu" or selected.dtype == np.uint64:
+                raise ValueError("orbitals must hold (64-bit signed) integers, got dtype {}".format(selected.dtype))
+            if selected.ndim == 0:
+                selected = selected.reshape(1)
+            if selected.ndim != 1 or selected.shape[0] < 1:
+                raise ValueError("orbitals must have shape (m,) with m >= 1, got {}".format(selected.shape))
+            selected = np.ascontiguousarray(selected, dtype=np.int64)
+            if selected.min() < 0 or selected.max() >= self.size:
+                raise ValueError("orbitals must lie in [0, {}), got {}".format(self.size, selected.tolist()))
+            if np.unique(selected).shape[0] != selected.shape[0]:
+                raise ValueError("orbitals must be distinct, got {}".format(selected.tolist()))
+        return selected
+
     def orbital_susceptibility(self, mesh, q, *, temperature, energy=None, n_electrons=None, orbitals=None, convention=2):
         """
         The orbital-resolved bare static susceptibility ``chi_0[i, j](q)`` of a uniform k mesh -- the response of the density on
@@ -2077,26 +2103,7 @@ class Model:
         """
         mesh_array, vectors, t_value, mode, value, pos = self._susceptibility_arguments("orbital_susceptibility", mesh, q, temperature, energy,
                                                                                         n_electrons, True, convention)
-        if orbitals is None:
-            selected = np.arange(self.size, dtype=np.int64)
-        else:
-            if isinstance(orbitals, (str, bytes)):
-                raise ValueError("orbitals must be an integer array of shape (m,), got {!r}".format(orbitals))
-            try:
-                selected = np.asarray(orbitals)
-            except (TypeError, ValueError):
-                raise ValueError("orbitals must be an integer array of shape (m,)") from None
-            if selected.dtype.kind not in "iu" or selected.dtype == np.uint64:
-                raise ValueError("orbitals must hold (64-bit signed) integers, got dtype {}".format(selected.dtype))
-            if selected.ndim == 0:
-                selected = selected.reshape(1)
-            if selected.ndim != 1 or selected.shape[0] < 1:
-                raise ValueError("orbitals must have shape (m,) with m >= 1, got {}".format(selected.shape))
-            selected = np.ascontiguousarray(selected, dtype=np.int64)
-            if selected.min() < 0 or selected.max() >= self.size:
-                raise ValueError("orbitals must lie in [0, {}), got {}".format(self.size, selected.tolist()))
-            if np.unique(selected).shape[0] != selected.shape[0]:
-                raise ValueError("orbitals must be distinct, got {}".format(selected.tolist()))
+        selected = self._orbital_selection_argument(orbitals)
         chosen = np.ascontiguousarray(selected, dtype=np.int32)
         mu = np.empty(4, dtype=np.float64)
         chi = np.empty((vectors.shape[0], chosen.shape[0], chosen.shape[0]), dtype=np.complex128)
@@ -2109,6 +2116,79 @@ class Model:
                                                             _lib.ptr(mu), _lib.ptr(chi))
             )
         return OrbitalSusceptibility(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, selected, chi)
+
+    def susceptibility_tensor(self, mesh, q, *, temperature, energy=None, n_electrons=None, orbitals=None):
+        """
+        The four-index bare static susceptibility ``chi_0[i, l; j, m](q)`` of a uniform k mesh -- the full particle-hole bubble a
+        multi-orbital RPA with Hund's coupling and pair hopping (the Kanamori ``U, U', J, J'`` vertices) starts from, of which
+        :meth:`orbital_susceptibility` returns the density-density block ``i = l, j = m`` -- computed on the GPU from the
+        eigensystem of the whole mesh, which never leaves it.  Not in the reference.
+
+        ``mesh``, ``q``, ``temperature``, ``energy`` and ``n_electrons`` are those of :meth:`susceptibility`, ``orbitals`` that of
+        :meth:`orbital_susceptibility` with ``1 <= m <= 16``, all with the same errors; more than 16 selected orbitals (or a model
+        of more than 16 with ``orbitals=None``) raise ``ValueError``.  Returns the named tuple ``(mu, q, orbitals, chi)``: ``mu``
+        and ``q`` as for :meth:`susceptibility`, ``orbitals`` as ``int64 (m,)`` and ``chi`` as ``complex128 (NQ, m, m, m, m)``
+        indexed ``[q, i, l, j, m]`` in the order of ``orbitals``.
+
+        Definition.  With ``E``, ``U`` (``eigh(k, convention=2)``), ``k+q`` and the pair weight ``t = f(lo) (1 - f(hi)) h(y) >= 0``
+        (``-T F``) of :meth:`orbital_susceptibility`::
+
+            chi_0[i, l; j, m](q) = (1 / (T NK)) sum_k sum_{b, b'} t(E[k, b], E[k+q, b'])
+                                   conj(U[k, i, b]) U[k+q, l, b'] U[k, j, b] conj(U[k+q, m, b'])
+
+        No spin factor; static only; the sign is that of :meth:`susceptibility`.  In the notation of Graser, Maier, Hirschfeld and
+        Scalapino (New J. Phys. 11, 025016 (2009), eq. 5), whose numerator is ``a_mu^{l4}(k) a_mu^{l2*}(k) a_nu^{l1}(k+q)
+        a_nu^{l3*}(k+q)``, this is ``chi_{l1 l2 l3 l4}`` with ``l2 = i, l1 = l, l4 = j, l3 = m``:
+        ``chi_{l1 l2 l3 l4}(q) = chi[q, l2, l1, l4, l3]``, or ``numpy.transpose(chi, (0, 2, 1, 4, 3))`` indexed ``[q, l1, l2,
+        l3, l4]``.
+
+        Convention.  There is no ``convention`` argument: the tensor is that of the lattice-periodic gauge (convention 2), in which
+        RPA codes work.  In convention 1 the pair amplitude ``conj(U[k, i, b]) U[k+q, l, b']`` carries ``exp(2 pi i k.(pos_i -
+        pos_l))``, which depends on ``k`` whenever ``i != l`` and does not leave the k sum as a table ``D(q)``: that tensor is another
+        operator (bond densities at the true positions).  On the block ``i = l, j = m`` the k dependence cancels and
+        ``orbital_susceptibility(convention=1).chi[q, i, j] = D(q)[i] conj(D(q)[j]) chi[q, i, i, j, j]`` with ``D(q)[i] =
+        exp(-2 pi i sum_d q_d pos[i, d] / n_d)``.
+
+        Properties.  (1) As an ``m^2 x m^2`` matrix with rows ``(i, l)`` and columns ``(j, m)`` ``chi_0(q)`` is Hermitian and
+        positive semidefinite; the output is exactly Hermitian: entries with ``(i, l) <= (j, m)`` (ascending orbital order) are
+        computed, the others are their conjugates with the imaginary part formed as ``0 - x`` (no ``-0``), and the diagonal's
+        imaginary part is ``+0``.  (2) ``chi_0[i, i; j, j](q)`` is ``chi_0[i, j](q)`` of :meth:`orbital_susceptibility` and (3)
+        ``sum_ij chi_0[i, i; j, j](q)`` is ``chi_0(q)`` of :meth:`susceptibility`, each within the sum of the two bounds (the
+        summation orders differ).  (4) ``chi_0(-q)[i, l; j, m] = chi_0(q)[m, j; l, i]``.  (5) ``4 T chi_0[i, l; j, m](q) ->
+        delta_ij delta_lm`` as ``T -> inf``.  (6) With ``mu`` 746 ``T`` or more outside the spectrum every entry is ``+0`` in both
+        components.  (7) ``q + n_d e_d`` has the bits of ``q``.  (8) ``chi_0`` does not depend on the phases of the eigenvectors
+        or on the basis inside degenerate clusters.  (9) The bits of an entry do not depend on the other entries of ``q``, on
+        their order or on the number of ``devices``; a second call gives the bits of the first.  (10) A selection returns the
+        bits of the same entries of any other selection that holds their orbitals, in whatever order.
+
+        Error bound of either component of an entry for a given eigensystem, with ``u = 2^-53`` and 2 ulps allowed for ``exp`` and
+        ``expm1`` (DESIGN.md 29.5; ``tools/chi_model.py`` ``tensor_tolerance``)::
+
+            |error| <= [ NK size^2 / 2 + 25.5 ] u / T
+
+        The kernels use the factorised form: per ``(k, b)`` ``P[i, j] = conj(U[k, i, b]) U[k, j, b]`` and ``Q[l, m] = sum_b' t
+        U[k+q, l, b'] conj(U[k+q, m, b'])``, ``chi_0 = sum P Q / (T NK)``: about ``4 size m^4`` flops per ``(k, q)`` on the FP64
+        matrix pipe instead of the ``8 size^2 m^4`` of the definition.  One-dimensional models raise ``ValueError``.  The
+        eigenvectors of the whole mesh must fit the device, else ``MemoryError``.  With several ``devices`` every device holds the
+        whole mesh's eigensystem and takes a contiguous share of ``q``.  Sparse models go through the same call.
+        """
+        mesh_array, vectors, t_value, mode, value, _ = self._susceptibility_arguments("susceptibility_tensor", mesh, q, temperature, energy,
+                                                                                      n_electrons, True, 2)
+        selected = self._orbital_selection_argument(orbitals)
+        if selected.shape[0] > 16:
+            raise ValueError("susceptibility_tensor takes up to 16 selected orbitals, got {}".format(selected.shape[0]))
+        chosen = np.ascontiguousarray(selected, dtype=np.int32)
+        m = chosen.shape[0]
+        mu = np.empty(4, dtype=np.float64)
+        chi = np.empty((vectors.shape[0], m, m, m, m), dtype=np.complex128)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_susceptibility_tensor_multi(handles, n_handles, _lib.ptr(mesh_array), mode, value, t_value, vectors.shape[0],
+                                                           _lib.ptr(vectors), m, _lib.ptr(chosen), _lib.ptr(mu), _lib.ptr(chi))
+            )
+        return SusceptibilityTensor(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, selected, chi)
 
     def _band_sets_argument(self, bands):
         """``int32 (S, 2)`` half-open band ranges from an int ``n_occ`` (``[(0, n_occ)]``) or a sequence of ``(lo, hi)`` pairs, or

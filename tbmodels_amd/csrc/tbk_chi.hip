@@ -58,6 +58,20 @@
 //   chi_reduce_orb_kernel  the slices in index order, / T / NK, the entry and its mirror (the conjugate) at the caller's places.
 //
 // tbk_chi_orbital_plan chooses template, slice length (a function of NK and n_orb alone), slices and batch.
+//
+// The four-index chi_0[i][l][j][m](q) (chi_model.susceptibility_tensor; convention 2 only) keeps both orbital
+// indices of each vertex and factorises per (k, b):
+//
+//   P[i][j] = conj(U[k][i][b]) U[k][j][b]         Q[l][m] = sum_b' t[b][b'] U[k+q][l][b'] conj(U[k+q][m][b'])
+//   chi_0[i][l][j][m](q) = (1 / (T NK)) sum_k sum_b P[i][j] Q[l][m]
+//
+//   chi_tensor_kernel   a workgroup owns a 64 x 64 block of X[(i, j)][(l, m)] (rows: the pairs i <= j of the ascending selection, the
+//                       others are conjugates) over a slice of k-points.  Per k and panel of 16 b: stage A, Q[(l, m)][b] = W t with
+//                       W[(l, m)][b'] = U'[l][b'] conj(U'[m][b']) over panels of 16 b' (complex by real: two MFMAs per step), whose tile
+//                       goes to LDS beside P; stage B, the plain transposed rank-16 update X += P Q^T (zmfma_ab) on the block in registers.
+//   chi_reduce_ten_kernel  the slices in index order, / T / NK, the entry and its mirror at the caller's [i][l][j][m].
+//
+// tbk_chi_tensor_plan chooses blocks, slice length (a function of NK and n_orb alone), slices and batch.
 
 #include <algorithm>
 #include <cmath>
@@ -83,7 +97,7 @@ struct ChiMesh {
     int64_t nk;  // points of the mesh
 };
 
-// the plan of a call of one of the three kinds: static (n_w = 0, m = 0), dynamic (n_w > 0), orbital-resolved (m > 0)
+// the plan of a call of one of the four kinds: static (n_w = 0, m = 0), dynamic (n_w > 0), orbital-resolved (m > 0), four-index (tr > 0)
 struct ChiPlan {
     ChiMesh mesh;
     int n = 0;            // orbitals
@@ -99,8 +113,11 @@ struct ChiPlan {
     int mp = 0;           // ... padded to the block
     int64_t ks = 1;       // ... k-points per slice
     int64_t slices = 1;
+    int64_t tr = 0;       // four-index: rows (pairs i <= j) and columns (pairs (l, m)) of one vector's partial matrix, padded to the
+    int64_t tc = 0;       // block (0: not a four-index call)
     // the partials of one vector (dynamic: at one frequency), and of one batch
     size_t per_q() const {
+        if (tr > 0) return (size_t)slices * (size_t)tr * (size_t)tc * sizeof(double2);
         return m > 0 ? (size_t)slices * mp * mp * sizeof(double2) : (size_t)mesh.nk * (size_t)blocks * (n_w == 0 ? sizeof(double) : sizeof(double2));
     }
     size_t part_bytes() const { return (size_t)batch * (n_w == 0 ? 1 : (size_t)w_pass) * per_q(); }
@@ -652,6 +669,203 @@ __global__ void __launch_bounds__(CHI_THREADS) chi_reduce_orb_kernel(const doubl
     if (i != j) out[(size_t)cj * m + ci] = make_double2(re, 0.0 - im);
 }
 
+// ---- the four-index chi_0[i][l][j][m](q) ---------------------------------------------------------------------
+constexpr int CHI_TEN_MAX = 16;  // selected orbitals, at most: X is 136 x 256 then
+constexpr int CHI_TEN_RB = 64;   // rows and columns of a workgroup's block of X
+
+// The MFMAs of stage B on one staged panel of 16 b: four steps of four b, the P pair of the wave's tile row read once per step, per
+// tile the Q pair and the four real products of zmfma_ab (plain transpose, nothing conjugated).  As in chi_orb_tiles no tile is
+// guarded: the loop holds ds_read_b64 and MFMA only, the padding is zeros.  pl: plane 0, the planes (Pr, Pi, Qr, Qi) are PLANE apart.
+template <int S>
+__device__ __forceinline__ void chi_ten_tiles(const double* pl, int ti, int lane, zd4 (&accr)[4], zd4 (&acci)[4]) {
+    constexpr int PLANE = 16 * S;
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+        const double* at = pl + (4 * q4 + (lane >> 4)) * S + (lane & 15);
+        const double pr = at[ti * 16], pi = at[PLANE + ti * 16];
+#pragma unroll
+        for (int tj = 0; tj < 4; ++tj) {
+            const double qr = at[2 * PLANE + tj * 16], qi = at[3 * PLANE + tj * 16];
+            zmfma_ab(pr, pi, qr, qi, accr[tj], acci[tj]);
+        }
+    }
+}
+
+// X[(i, j)][(l, m)] += sum over (k, b) of a slice of P[(i, j)][k b] Q[(l, m)][k b]: the factorised four-index bubble.  Rows of X: the
+// pairs i <= j of the ascending selection in lexicographic order, m (m + 1) / 2 of them; columns: all pairs (l, m), l m + m.  A workgroup
+// owns block (bi, bj) of 64 x 64, wave t its tile row t (ZPanel<4>'s geometry), over one slice of k-points.  Per k-point and panel of
+// 16 bands b of U[k]:
+//   stage A  wave t forms tile t of Q[(l, m)][b] = sum_b' W[(l, m)][b'] t[b'][b] for the block's 64 columns: b' in panels of 16 through
+//            LDS (W = U'[l][b'] conj(U'[m][b']) made while staging with explicit fma, t one chi_pair_weight per thread), four steps of two
+//            MFMAs (Re, Im: complex by real) per panel.  The Q of the other row blocks of the same columns is computed again there:
+//            n / 128 of stage B's MFMAs per block (DESIGN.md 29.2 has the choice).
+//   stage B  the tile goes to the Q planes [b][64], P = conj(U[k][i][b]) U[k][j][b] of the block's rows to the P planes, one barrier,
+//            then chi_ten_tiles on the accumulators, which stay in registers over the slice.
+// Every element walks k ascending, b ascending in panels of 16 from 0 (four per MFMA step), and inside Q the b' ascending likewise: a
+// function of n alone.  Zeros stand beyond n, beyond the rows and beyond the columns.  One complex partial block goes to
+// part[q][slice][tr][tc], padding included (tr, tc are multiples of 64: every store is inside).
+// grid: (slices, blocks, vectors of the batch).  orb: the selected orbitals [m], ascending.
+__global__ void __launch_bounds__(CHI_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) chi_tensor_kernel(const double2* __restrict__ U, const double* __restrict__ E,
+                                                                 const double* __restrict__ tab, ChiMesh g, int n,
+                                                                 const int32_t* __restrict__ Q, double inv_t, const int32_t* __restrict__ orb,
+                                                                 int m, int64_t tr, int64_t tc, int64_t ks, int64_t slices,
+                                                                 double2* __restrict__ part) {
+    constexpr int S = ZPanel<4>::S, PLANE = 16 * S, TS = 18;
+    static_assert(CHI_THREADS == ZPanel<4>::THREADS && CHI_TEN_RB == ZPanel<4>::RB, "the panel's workgroup");
+    __shared__ double planes[4 * PLANE];  // Pr, Pi [b][rows of the block]; Qr, Qi [b][columns of the block]
+    __shared__ double wpl[2 * PLANE];     // Wr, Wi [b'][columns of the block]
+    __shared__ double tw[16 * TS];        // t[b'][b] of the two panels
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int cbk = (int)(tc / CHI_TEN_RB);
+    const int bi = (int)blockIdx.y / cbk, bj = (int)blockIdx.y - bi * cbk;
+    const int64_t sl = blockIdx.x, ql = blockIdx.z;
+    const int64_t k0 = sl * ks, k1 = k0 + ks < g.nk ? k0 + ks : g.nk;
+    const int mr = m * (m + 1) / 2, mc = m * m;
+    const int sb = tid & 15, srow0 = tid >> 4;  // the band (row of a panel) and the first of the four rows / columns this thread stages
+    int oi[4], oj[4], ol[4], om[4];             // the orbitals of its rows (i, j) and columns (l, m); -1: padding
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        int row = bi * CHI_TEN_RB + srow0 + 16 * r;
+        oi[r] = oj[r] = ol[r] = om[r] = -1;
+        if (row < mr) {
+            int i = 0;
+            while (row >= m - i) {
+                row -= m - i;
+                ++i;
+            }
+            oi[r] = orb[i];
+            oj[r] = orb[i + row];
+        }
+        const int col = bj * CHI_TEN_RB + srow0 + 16 * r;
+        if (col < mc) {
+            ol[r] = orb[col / m];
+            om[r] = orb[col % m];
+        }
+    }
+    zd4 accr[4], acci[4];
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj) accr[tj] = acci[tj] = zd4{0.0, 0.0, 0.0, 0.0};
+    const int64_t items = g.nk * n;
+    const int tbp = tid >> 4, tb = tid & 15;  // the (b', b) of the panel pair whose weight this thread makes
+    // The accumulators' home.  chi_orbital_kernel's empty "+a" statements did not hold here: with the second set of MFMAs (stage A)
+    // in the loop nest the compiler kept six of the eight accumulators in VGPRs and copied 48 words to and 48 from the AGPRs around
+    // the 64 MFMAs of every panel, wherever the statements stood and with the loops nested or flat.  The kernel is
+    // therefore bounded to two waves per SIMD (what its LDS allows anyway): 256 registers, no AGPRs, and the compiler selects the
+    // MFMA that reads and writes its accumulator in VGPRs -- gfx950's register file is one, so the accumulators stay in place from
+    // the first MFMA to the store and the built code has no v_accvgpr_* at all.  The k-points of the slice and the panels of b run
+    // as ONE counter (k slow, b fast) and the four K steps are unrolled: one loop level carries the accumulators.
+    const int panels = (n + 15) >> 4;
+    const int64_t walks = (k1 - k0) * panels;
+    int64_t k = k0;
+    int b0 = 0;
+    for (int64_t it = 0; it < walks; ++it) {
+        const int64_t kp = chi_shifted(g, k, Q + ql * 3);
+        const double2* Uk = U + (size_t)k * n * n;
+        const double2* Up = U + (size_t)kp * n * n;
+        const double *Ea = E + (size_t)k * n, *Eb = E + (size_t)kp * n;
+        const double *fa = tab + (size_t)k * n, *ga = fa + items, *fb = tab + (size_t)kp * n, *gb = fb + items;
+        // ---- stage A: the wave's tile of Q[(l, m)][b0 ... b0 + 16)
+        zd4 qr = zd4{0.0, 0.0, 0.0, 0.0}, qi = qr;
+        const int bw = b0 + tb;
+        const bool bw_in = bw < n;
+        const double ea = bw_in ? Ea[bw] : 0.0, fav = bw_in ? fa[bw] : 0.0, gav = bw_in ? ga[bw] : 0.0;
+        for (int p0 = 0; p0 < n; p0 += 16) {
+            __syncthreads();  // the previous panels have been read (W, t by stage A; P, Q by stage B of the panel before)
+            const int bp = p0 + sb;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                double wr = 0.0, wi = 0.0;
+                if (bp < n && ol[r] >= 0) {
+                    const double2 ul = Up[(size_t)ol[r] * n + bp], um = Up[(size_t)om[r] * n + bp];
+                    wr = fma(ul.x, um.x, ul.y * um.y);     // U'[l] conj(U'[m])
+                    wi = fma(ul.y, um.x, -(ul.x * um.y));
+                }
+                wpl[sb * S + srow0 + 16 * r] = wr;
+                wpl[PLANE + sb * S + srow0 + 16 * r] = wi;
+            }
+            {
+                const int bq = p0 + tbp;
+                tw[tbp * TS + tb] = (bw_in && bq < n) ? chi_pair_weight(ea, fav, gav, Eb[bq], fb[bq], gb[bq], inv_t) : 0.0;
+            }
+            __syncthreads();
+#pragma unroll 1
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const int kq = 4 * q4 + (lane >> 4);
+                const double wr = wpl[kq * S + wave * 16 + (lane & 15)], wi = wpl[PLANE + kq * S + wave * 16 + (lane & 15)];
+                const double t = tw[kq * TS + (lane & 15)];
+                qr = __builtin_amdgcn_mfma_f64_16x16x4f64(wr, t, qr, 0, 0, 0);
+                qi = __builtin_amdgcn_mfma_f64_16x16x4f64(wi, t, qi, 0, 0, 0);
+            }
+        }
+        // ---- stage B: lane (q, c), register r of the tile: column (l, m) = 16 wave + q + 4 r of the block, band c of the panel
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double* st = planes + 2 * PLANE + (lane & 15) * S + wave * 16 + (lane >> 4) + 4 * r;
+            st[0] = qr[r];
+            st[PLANE] = qi[r];
+        }
+        const int b = b0 + sb;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double pr = 0.0, pi = 0.0;
+            if (b < n && oi[r] >= 0) {
+                const double2 ui = Uk[(size_t)oi[r] * n + b], uj = Uk[(size_t)oj[r] * n + b];
+                pr = fma(ui.x, uj.x, ui.y * uj.y);     // conj(U[i]) U[j]
+                pi = fma(ui.x, uj.y, -(ui.y * uj.x));
+            }
+            planes[sb * S + srow0 + 16 * r] = pr;
+            planes[PLANE + sb * S + srow0 + 16 * r] = pi;
+        }
+        __syncthreads();
+        chi_ten_tiles<S>(planes, wave, lane, accr, acci);
+        b0 += 16;
+        if (b0 >= n) {
+            b0 = 0;
+            ++k;
+        }
+    }
+    double2* out = part + ((size_t)ql * slices + sl) * (size_t)tr * (size_t)tc;
+#pragma unroll
+    for (int tj = 0; tj < 4; ++tj) {
+        const int gj = bj * CHI_TEN_RB + tj * 16 + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int gi = bi * CHI_TEN_RB + wave * 16 + (lane >> 4) + 4 * r;
+            out[(size_t)gi * tc + gj] = make_double2(accr[tj][r], acci[tj][r]);
+        }
+    }
+}
+
+// chi[q][perm[i]][perm[l]][perm[j]][perm[m]] = (the slices of part[q][.][(i, j)][(l, m)] in index order) / T / NK and its mirror, the
+// conjugate at [j][m][i][l]: one thread per (q, (i, l) <= (j, m)) of the ascending list, as rows and columns i m + l of the
+// m^2 x m^2 matrix -- which has i <= j, the rows the kernel computes.  The mirror's imaginary part is the difference from +0 and the
+// diagonal's is +0.  grid: (elements / 256, vectors of the batch)
+__global__ void __launch_bounds__(CHI_THREADS) chi_reduce_ten_kernel(const double2* __restrict__ part, int m, int64_t tr, int64_t tc,
+                                                                     int64_t slices, double T, double nk, const int32_t* __restrict__ perm,
+                                                                     double2* __restrict__ chi) {
+    const int64_t m2 = (int64_t)m * m;
+    const int64_t e = (int64_t)blockIdx.x * CHI_THREADS + threadIdx.x;
+    if (e >= m2 * m2) return;
+    const int rr = (int)(e / m2), cc = (int)(e - (int64_t)rr * m2);
+    if (rr > cc) return;
+    const int i = rr / m, l = rr - i * m, j = cc / m, mm = cc - j * m;
+    const int64_t row = (int64_t)i * m - (int64_t)i * (i - 1) / 2 + (j - i), col = (int64_t)l * m + mm;
+    const size_t plane = (size_t)tr * (size_t)tc;
+    const double2* p = part + (size_t)blockIdx.y * slices * plane + (size_t)row * tc + col;
+    double re = 0.0, im = 0.0;
+    for (int64_t s = 0; s < slices; ++s) {
+        const double2 v = p[(size_t)s * plane];
+        re += v.x;
+        im += v.y;
+    }
+    re = re / T / nk;
+    im = rr == cc ? 0.0 : im / T / nk;
+    double2* out = chi + (size_t)blockIdx.y * m2 * m2;
+    const int64_t ci = perm[i], cl = perm[l], cj = perm[j], cm = perm[mm];
+    out[((ci * m + cl) * m + cj) * m + cm] = make_double2(re, im);
+    if (rr != cc) out[((cj * m + cm) * m + ci) * m + cl] = make_double2(re, 0.0 - im);
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 // the frequencies of a dynamic call (n_w = 0: the static call)
 struct ChiFreq {
@@ -783,10 +997,38 @@ void chi_orb_plan_sizes(int64_t nk, int n_orb, int m, int64_t n_q, size_t mem, i
     L->batches = L->batch == 0 ? 0 : (n_q + L->batch - 1) / L->batch;
 }
 
+constexpr int64_t CHI_TEN_AMORTISE = 8;   // panels of 16 b a slice walks at least per register-resident block (64 KiB of partials)
+constexpr int64_t CHI_TEN_SLICES = 256;   // slices of one vector, about: with up to 12 blocks each, workgroups for every compute unit
+
+// the four-index call's slice length, a function of (NK, n_orb) alone as chi_orb_slice is and for its reason: long enough to walk
+// CHI_TEN_AMORTISE panels per block, short enough for about CHI_TEN_SLICES slices, and long enough that two vectors' partials of the
+// largest selection (16 orbitals: 192 x 256 padded) fit the budget
+int64_t chi_ten_slice(int64_t nk, int n_orb) {
+    const int64_t panels = ((int64_t)n_orb + 15) / 16;
+    const int64_t amortise = (CHI_TEN_AMORTISE + panels - 1) / panels, fill = (nk + CHI_TEN_SLICES - 1) / CHI_TEN_SLICES;
+    const int64_t most = (int64_t)(CHI_PART_BUDGET / 2 / (sizeof(double2) * 192 * 256));
+    return std::min(nk, std::max(std::max(amortise, fill), (nk + most - 1) / most));
+}
+
+// the one place that chooses for the four-index call: blocks, slice length (k_slice = 0: the library's), slices, batch
+void chi_ten_plan_sizes(int64_t nk, int n_orb, int m, int64_t n_q, size_t mem, int64_t k_slice, ChiPlan* L) {
+    L->n = n_orb;
+    L->m = m;
+    L->bt = 4;
+    L->tr = ((int64_t)m * (m + 1) / 2 + CHI_TEN_RB - 1) / CHI_TEN_RB * CHI_TEN_RB;
+    L->tc = ((int64_t)m * m + CHI_TEN_RB - 1) / CHI_TEN_RB * CHI_TEN_RB;
+    L->blocks = (L->tr / CHI_TEN_RB) * (L->tc / CHI_TEN_RB);
+    L->ks = k_slice > 0 ? std::min(k_slice, nk) : chi_ten_slice(nk, n_orb);
+    L->slices = (nk + L->ks - 1) / L->ks;
+    const size_t room = mem == 0 ? CHI_PART_BUDGET : mem;
+    L->batch = std::max<int64_t>(0, std::min<int64_t>(std::min(n_q, CHI_MAX_BATCH), (int64_t)(room / L->per_q())));
+    L->batches = L->batch == 0 ? 0 : (n_q + L->batch - 1) / L->batch;
+}
+
 // The plan of n_q vectors on a mesh of nk points: n_w frequencies (0: static), m selected orbitals (0: the scalar calls; k_slice
-// is theirs); mem: the bytes the partials may take (0: the budget)
-int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, int64_t n_w, int m, bool matrix_elements, size_t mem,
-             int64_t k_slice, ChiPlan* out) {
+// is theirs) of the orbital-resolved or, with `tensor`, the four-index call; mem: the bytes the partials may take (0: the budget)
+int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, int64_t n_w, int m, bool tensor, bool matrix_elements,
+             size_t mem, int64_t k_slice, ChiPlan* out) {
     ChiPlan L;
     L.mesh.n[0] = mesh[0];
     L.mesh.n[1] = mesh[1];
@@ -795,7 +1037,9 @@ int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, i
     L.n = n_orb;
     TBK_ARG(nk <= CHI_MAX_NK, "the susceptibility takes meshes of up to 2^23 points");
     L.n_w = n_w;
-    if (m > 0)
+    if (m > 0 && tensor)
+        chi_ten_plan_sizes(nk, n_orb, m, n_q, mem, k_slice, &L);
+    else if (m > 0)
         chi_orb_plan_sizes(nk, n_orb, m, n_q, mem, k_slice, &L);
     else if (n_w == 0)
         chi_plan_sizes(nk, n_orb, n_q, matrix_elements, mem, &L.bt, &L.blocks, &L.batch, &L.batches);
@@ -803,7 +1047,8 @@ int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, i
         chi_dyn_plan_sizes(nk, n_orb, n_q, n_w, matrix_elements, mem, &L.bt, &L.blocks, &L.batch, &L.batches, &L.w_pass, &L.passes);
     if (L.batch < 1) {
         if (m > 0)
-            tbk_set_error("the partial sums of one orbital-resolved susceptibility vector need %zu bytes of device memory", L.per_q());
+            tbk_set_error("the partial sums of one %s susceptibility vector need %zu bytes of device memory", tensor ? "four-index" : "orbital-resolved",
+                          L.per_q());
         else
             tbk_set_error("the partial sums of one susceptibility vector%s need %zu bytes of device memory", n_w == 0 ? "" : " at one frequency",
                           L.per_q());
@@ -813,11 +1058,12 @@ int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, i
     return TBK_OK;
 }
 
-// the selection of an orbital-resolved call (off: the scalar calls)
+// the selection of an orbital-resolved or four-index call (off: the scalar calls)
 struct ChiOrb {
     bool on = false;
     int m = 0;
     const int32_t* orbitals = nullptr;  // host [m] or NULL: all of them in order (m = n_orb)
+    bool tensor = false;                // the four-index call: m <= CHI_TEN_MAX, [m][m][m][m] per vector
 };
 
 // lists[0 .. m): the selection in ascending order; lists[m .. 2 m): the place of each in the caller's order
@@ -825,6 +1071,7 @@ struct ChiOrb {
 int chi_orb_lists(const ChiOrb& ob, int n_orb, std::vector<int32_t>* lists) {
     if (!ob.on) return TBK_OK;
     TBK_ARG(ob.m >= 1 && ob.m <= n_orb, "m < 1 or more selected orbitals than the model has");
+    TBK_ARG(!ob.tensor || ob.m <= CHI_TEN_MAX, "the four-index susceptibility takes up to 16 selected orbitals");
     TBK_ARG(ob.orbitals != nullptr || ob.m == n_orb, "orbitals is NULL and m is not n_orb");
     try {
         lists->assign((size_t)ob.m * 2, 0);
@@ -872,9 +1119,28 @@ int chi_launch_orb_batch(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, cons
     return TBK_OK;
 }
 
+// the four-index call's: nq vectors (at most L.batch); d_lists: chi_orb_lists' on the device; d_chi: their [.][m][m][m][m] complex
+int chi_launch_ten_batch(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, const double* d_tab,
+                         const int32_t* d_Q, const int32_t* d_lists, int64_t nq, double T, double* d_part, double* d_chi) {
+    const int64_t elements = (int64_t)L.m * L.m * L.m * L.m;
+    if (ev) ev->start(1);
+    hipLaunchKernelGGL(chi_tensor_kernel, dim3((unsigned)L.slices, (unsigned)L.blocks, (unsigned)nq), dim3(CHI_THREADS), 0, s,
+                       reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q, 1.0 / T, d_lists, L.m, L.tr, L.tc, L.ks, L.slices,
+                       reinterpret_cast<double2*>(d_part));
+    if (ev) ev->stop();
+    TBK_HIP(hipGetLastError());
+    if (ev) ev->start(2);
+    hipLaunchKernelGGL(chi_reduce_ten_kernel, dim3((unsigned)((elements + CHI_THREADS - 1) / CHI_THREADS), (unsigned)nq), dim3(CHI_THREADS), 0, s,
+                       reinterpret_cast<const double2*>(d_part), L.m, L.tr, L.tc, L.slices, T, (double)L.mesh.nk, d_lists + L.m,
+                       reinterpret_cast<double2*>(d_chi));
+    if (ev) ev->stop();
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
 // The Fermi tables once, then all batches of n_q vectors whose reduced entries (and phases) are on the device, by the plan's kind:
 // d_chi [n_q], [n_q][L.n_w] complex with the frequencies d_W of a dynamic call, or [n_q][m][m] complex with the orbital-resolved
-// call's d_lists
+// call's d_lists, or [n_q][m][m][m][m] complex with the four-index call's
 int chi_launch_all(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, double* d_tab, const int32_t* d_Q,
                    const double* d_D, const int32_t* d_lists, int64_t n_q, double mu, double T, const double* d_W, double eta, double* d_part,
                    double* d_chi) {
@@ -883,7 +1149,10 @@ int chi_launch_all(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const doub
         const int64_t nq = std::min(L.batch, n_q - q0);
         const int32_t* Q = d_Q + q0 * 3;
         const double* D = d_D ? d_D + (size_t)q0 * L.n * 2 : nullptr;
-        if (L.m > 0)
+        if (L.tr > 0)
+            TBK_CHECK(chi_launch_ten_batch(s, L, ev, d_U, d_E, d_tab, Q, d_lists, nq, T, d_part,
+                                           d_chi + (size_t)q0 * L.m * L.m * L.m * L.m * 2));
+        else if (L.m > 0)
             TBK_CHECK(chi_launch_orb_batch(s, L, ev, d_U, d_E, d_tab, Q, D, d_lists, nq, T, d_part, d_chi + (size_t)q0 * L.m * L.m * 2));
         else if (L.n_w > 0)
             TBK_CHECK(chi_launch_dyn_batch(s, L, ev, d_U, d_E, d_tab, Q, D, nq, T, d_W, eta, d_part, d_chi + (size_t)q0 * L.n_w * 2));
@@ -907,8 +1176,9 @@ int chi_check_frequencies(int64_t n_w, const double* omega, double eta) {
 
 constexpr const char* CHI_FAMILY = "the susceptibility";
 
-// the bytes of one vector's result: a double, n_w complex numbers, or the m x m complex matrix
+// the bytes of one vector's result: a double, n_w complex numbers, the m x m complex matrix or the m x m x m x m complex tensor
 size_t chi_out_per_q(const ChiFreq& fr, const ChiOrb& ob) {
+    if (ob.on && ob.tensor) return (size_t)ob.m * ob.m * ob.m * ob.m * sizeof(double2);
     return ob.on ? (size_t)ob.m * ob.m * sizeof(double2) : fr.n_w == 0 ? sizeof(double) : (size_t)fr.n_w * sizeof(double2);
 }
 
@@ -940,7 +1210,7 @@ static int chi_from_eigensystem(int device, int dim, const int32_t* mesh, int n_
     TBK_CHECK(chi_orb_lists(ob, n_orb, &h_lists));
     TBK_CHECK(tetra_check_device(device));
     ChiPlan L;
-    TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, n_q, fr.n_w, ob.m, U != nullptr, mem, k_slice, &L));
+    TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, n_q, fr.n_w, ob.m, ob.tensor, U != nullptr, mem, k_slice, &L));
     const size_t out_bytes = (size_t)n_q * chi_out_per_q(fr, ob);
     std::vector<int32_t> h_Q;
     TBK_CHECK(chi_reduce_q(dim, mesh, n_q, q, &h_Q));
@@ -1022,7 +1292,7 @@ static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_
         TBK_HIP(hipMemGetInfo(&free_b, &total_b));
         const size_t room = std::max<size_t>(1, std::min(CHI_PART_BUDGET, std::max(m->ws_mesh_work.bytes, free_b / 4)));
         ChiPlan L;
-        TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, q_n, fr.n_w, ob.m, with_u, room, 0, &L));
+        TBK_CHECK(chi_plan(dim, mesh, nk, n_orb, q_n, fr.n_w, ob.m, ob.tensor, with_u, room, 0, &L));
         TBK_CHECK(m->ws_mesh_work.reserve(L.part_bytes()));
         double* d_E = m->ws_mesh_e.as<double>();
         // ws_mesh_io: the results (and the frequencies of a dynamic call), 256-byte aligned behind them the phases, then the reduced
@@ -1137,4 +1407,39 @@ extern "C" int tbk_orbital_susceptibility_multi(tbk_model* const* handles, int n
 extern "C" int tbk_orbital_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q,
                                           int n_sel, const int32_t* orbitals, int convention, const double* pos, double* mu_out, double* chi_out) {
     return tbk_orbital_susceptibility_multi(&m, 1, mesh, mode, value, T, n_q, q, n_sel, orbitals, convention, pos, mu_out, chi_out);
+}
+
+// ---- the four-index chi_0[i][l][j][m](q) -----------------------------------------------------------------------------------------
+extern "C" int tbk_chi_tensor_plan(int64_t nk, int n_orb, int m, int64_t n_q, int64_t part_bytes, int64_t k_slice, int64_t* out) {
+    TBK_ARG(nk >= 1 && n_orb >= 1 && n_orb <= CHI_MAX_ORB && m >= 1 && m <= n_orb && m <= CHI_TEN_MAX && n_q >= 1 && part_bytes >= 0 &&
+                k_slice >= 0 && out != nullptr,
+            "nk / n_orb / m / n_q < 1, more than 16320 orbitals, m > n_orb or m > 16, part_bytes / k_slice < 0 or out is NULL");
+    ChiPlan L;
+    chi_ten_plan_sizes(nk, n_orb, m, n_q, (size_t)part_bytes, k_slice, &L);
+    out[0] = L.tr / CHI_TEN_RB;
+    out[1] = L.blocks;
+    out[2] = L.ks;
+    out[3] = L.slices;
+    out[4] = L.batch;
+    out[5] = L.batches;
+    return TBK_OK;
+}
+
+extern "C" int tbk_chi_tensor_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu,
+                                               double T, int64_t n_q, const int64_t* q, int m, const int32_t* orbitals, int64_t part_bytes,
+                                               int64_t k_slice, double* chi_out) {
+    TBK_ARG(part_bytes >= 0 && k_slice >= 0, "part_bytes / k_slice < 0");
+    return chi_from_eigensystem(device, dim, mesh, n_orb, E, U, mu, T, n_q, q, nullptr, ChiFreq(), ChiOrb{true, m, orbitals, true},
+                                (size_t)part_bytes, k_slice, chi_out);
+}
+
+extern "C" int tbk_susceptibility_tensor_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
+                                               int64_t n_q, const int64_t* q, int m, const int32_t* orbitals, double* mu_out, double* chi_out) {
+    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, ChiFreq(), ChiOrb{true, m, orbitals, true}, 1, 2, nullptr, mu_out,
+                          chi_out);
+}
+
+extern "C" int tbk_susceptibility_tensor(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q,
+                                         int n_sel, const int32_t* orbitals, double* mu_out, double* chi_out) {
+    return tbk_susceptibility_tensor_multi(&m, 1, mesh, mode, value, T, n_q, q, n_sel, orbitals, mu_out, chi_out);
 }

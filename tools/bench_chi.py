@@ -28,7 +28,15 @@ the selection, which are the ones written, and for all the tiles the kernel mult
 64 x 64 blocks, the tiles of the padding and those below the diagonal of a diagonal block included); and the host route at one
 vector, Model.eigh + chi_model.orbital_susceptibility, timed on two planes and scaled.
 
-    python tools/bench_chi.py [--reps 3] [--filling 0.3] [--temperature 0.05] [--quick] [--omegas 1,16,128 [--eta 0.05]] [--orbital [--orbitals m]]
+With --tensor it prints the table of Model.susceptibility_tensor instead for synthetic dense models: 10 of 10
+orbitals on 32 x 32 and on 16^3, 16 of 64 on 16^3 and 3 of 8 on 64 x 64, NQ = 1 and 8: ms per vector (best, median and worst of --reps
+calls after a warm-up), the three stages of the best call, the executed flops of stage A (Q = W t) and stage B (X += P Q^T) per
+(k, q) as the kernel issues them -- whole blocks of 64 x 64, padding included -- stage B's rate over the kernel's whole time against
+tbk_mfma_f64_peak, the same selection the direct way AS AN ESTIMATE (the rank-K update stage of Model.orbital_susceptibility times the
+flop ratio 8 n^2 m^4 / 8 n^2 m^2 = m^2), and for the first shape the host route at one vector, Model.eigh + chi_model.susceptibility_tensor,
+timed on two rows of the mesh and scaled.
+
+    python tools/bench_chi.py [--reps 3] [--filling 0.3] [--temperature 0.05] [--quick] [--omegas 1,16,128 [--eta 0.05]] [--orbital [--orbitals m]] [--tensor]
 """
 
 import argparse
@@ -196,6 +204,69 @@ def measure_orbital(name, model, mesh, counts, m, filling, T, reps, peak_tflops)
         sys.stdout.flush()
 
 
+def measure_tensor(name, model, mesh, counts, m, filling, T, reps, peak_tflops, host_route):
+    lib = _lib.lib()
+    n, n_k = model.size, int(np.prod(mesh))
+    n_el = filling * n
+    chosen = None if m == n else np.arange(m)
+    handle = model._staged()
+    ms, calls, plan = (ctypes.c_double * 3)(), ctypes.c_int64(0), (ctypes.c_int64 * 6)()
+    panels = (n + 15) // 16
+    for n_q in counts:
+        q = np.zeros((n_q, len(mesh)), dtype=np.int64)
+        q[:, 0] = np.arange(1, n_q + 1)
+        call = lambda: model.susceptibility_tensor(mesh, q, temperature=T, n_electrons=n_el, orbitals=chosen)  # noqa: E731
+        call()  # warm-up
+        times = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            result = call()
+            times.append(time.perf_counter() - t0)
+        _lib.check(lib.tbk_model_set_option(handle, _lib.TBK_OPT_TIMING, 1))
+        _lib.check(lib.tbk_chi_timing(handle, ms, ctypes.byref(calls), 1))
+        runs = []
+        for _ in range(reps):
+            call()
+            _lib.check(lib.tbk_chi_timing(handle, ms, ctypes.byref(calls), 1))
+            runs.append(list(ms))
+        kernel = sorted(r[1] for r in runs)
+        best = min(runs, key=lambda r: r[1])
+        # the same selection through the orbital-resolved call: its update stage, for the estimate of the direct form
+        direct = lambda: model.orbital_susceptibility(mesh, q, temperature=T, n_electrons=n_el, orbitals=chosen)  # noqa: E731
+        direct()
+        _lib.check(lib.tbk_chi_timing(handle, ms, ctypes.byref(calls), 1))
+        update = []
+        for _ in range(reps):
+            direct()
+            _lib.check(lib.tbk_chi_timing(handle, ms, ctypes.byref(calls), 1))
+            update.append(ms[1])
+        model.timing(reset=True)
+        _lib.check(lib.tbk_model_set_option(handle, _lib.TBK_OPT_TIMING, 0))
+        _lib.check(lib.tbk_chi_tensor_plan(n_k, n, m, n_q, 0, 0, plan))
+        blocks = plan[1]
+        flops_b = 2048.0 * 256 * panels * blocks          # per (k, q): 64 MFMAs per wave and panel of b, four waves
+        flops_a = 2048.0 * 32 * panels * panels * blocks  # ... 8 MFMAs per wave and pair of panels (b, b')
+        rate_b = flops_b * n_k * n_q / (best[1] * 1e-3) / 1e12 if best[1] > 0 else float("nan")
+        host = ""
+        if host_route and n_q == counts[0]:
+            kpts = np.ascontiguousarray(dos_model.mesh_kpoints(mesh))
+            row = int(np.prod(mesh[1:]))
+            sub_mesh = (2,) + tuple(mesh[1:])
+            model.eigh(kpts[:row])
+            t_eigh, (eig2, vec2) = _best(lambda: model.eigh(kpts[:2 * row]), max(1, reps - 1))
+            t_model, _ = _best(lambda: chi_model.susceptibility_tensor(eig2, vec2, sub_mesh, q[:1], result.mu.mu, T, chosen), 1)
+            host = "%.1f" % ((t_eigh + t_model) / 2 * mesh[0] * 1e3)
+        times.sort()
+        print("| %s | %s | %d | %d | %d | %d x %d, %d blocks | %.2f / %.2f / %.2f | %.3f | %.3f / %.3f / %.3f | %.3f | %.3g | %.3g | %.2f | %.3f | %.1f | %s |"
+              % (name, "x".join(str(x) for x in mesh), n, m, n_q, plan[3], plan[2], blocks, times[0] * 1e3 / n_q, times[len(times) // 2] * 1e3 / n_q,
+                 times[-1] * 1e3 / n_q, best[0], kernel[0], kernel[len(kernel) // 2], kernel[-1], best[2], flops_a, flops_b, rate_b, rate_b / peak_tflops,
+                 min(update) * m * m, host))
+        matrix = result.chi[0].reshape(m * m, m * m)
+        print("  (%s NQ = %d: mu = %.12g, largest eigenvalue of chi(q_1) = %.12g, trace = %.12g)"
+              % (name, n_q, result.mu.mu, np.linalg.eigvalsh(matrix).max(), matrix.trace().real))
+        sys.stdout.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -208,7 +279,25 @@ def main():
                     "of vector FP64 is one fused multiply-add per lane and cycle, 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz")
     ap.add_argument("--orbital", action="store_true", help="the table of Model.orbital_susceptibility instead")
     ap.add_argument("--orbitals", type=int, default=0, help="with --orbital: the first m orbitals only (0: all)")
+    ap.add_argument("--tensor", action="store_true", help="the table of Model.susceptibility_tensor instead")
     args = ap.parse_args()
+    if args.tensor:
+        tf = ctypes.c_double(0.0)
+        _lib.check(_lib.lib().tbk_mfma_f64_peak(0, ctypes.byref(tf)))
+        print("FP64 MFMA peak: %.1f TFLOP/s" % tf.value)
+        print("| model | mesh | orbitals | selected | NQ | slices x k-points, blocks | Model.susceptibility_tensor ms per vector (best / median / worst) | "
+              "Fermi tables ms | two-stage kernel ms (best / median / worst) | reduction ms | stage A flops per (k, q) | stage B flops per (k, q) | "
+              "stage B TFLOP/s over the kernel's time | of the MFMA peak | ESTIMATE of the direct form: orbital update stage x m^2, ms | today, one "
+              "vector: Model.eigh to the host + tools/chi_model.py ms (two rows, scaled) |")
+        print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+        counts = (1, 2) if args.quick else (1, 8)
+        shapes = [(10, 10, (8, 8), 2), (8, 3, (8, 8), 2)] if args.quick else [(10, 10, (32, 32), 2), (10, 10, (16,) * 3, 3), (64, 16, (16,) * 3, 3),
+                                                                             (8, 3, (64, 64), 2)]
+        for index, (n, m, mesh, dim) in enumerate(shapes):
+            r_vec, hop, _ = synthetic.dense_model_arrays(n, 16, synthetic.MODEL_SEED + 40 + index, dim=dim)
+            model = tbmodels_amd.Model.from_packed(r_vec, hop)
+            measure_tensor("dense %d" % n, model, mesh, counts, m, args.filling, args.temperature, args.reps, tf.value, index == 0)
+        return
     if args.orbital:
         tf = ctypes.c_double(0.0)
         _lib.check(_lib.lib().tbk_mfma_f64_peak(0, ctypes.byref(tf)))

@@ -20,7 +20,9 @@ exactly): every factor is non-negative, nothing overflows, a = b is the same bra
 
 The dynamic chi_0(q, omega + i eta) of DESIGN.md section 16 is `dynamic_susceptibility`, with the occupation difference in the stable
 form of `pair_difference` and the bound `dynamic_tolerance`.  The orbital-resolved chi_0[i][j](q) of section 17 is `orbital_susceptibility`
-(`orbital_susceptibility_naive`: F as the quotient), with the bound `orbital_tolerance`.
+(`orbital_susceptibility_naive`: F as the quotient), with the bound `orbital_tolerance`.  The four-index chi_0[i, l; j, m](q) of section
+29 is `susceptibility_tensor` (the definition), `susceptibility_tensor_factored` (the kernels' P Q form) and
+`susceptibility_tensor_naive` (F as the quotient), with the bound `tensor_tolerance`.
 
 `python tools/chi_model.py` prints one small case by the stable and by the naive F.  Design tooling: nothing in the product imports it.
 """
@@ -356,6 +358,129 @@ def orbital_tolerance(n_k, n, T):
     the unbounded part of the exponential's argument error, absolute, 4 u per unit of sum |A_i| |A_j|: 4 u."""
     u = 2.0 ** -53
     side = (n_k * n * n + 4 * ULP_EXP + ULP_EXPM1 + 15 + ROUNDINGS_AMPLITUDES) / 4.0 + 4.0
+    return 2.0 * side * u / T
+
+
+def _tensor_arguments(E, U, mesh, q, orbitals):
+    E = np.asarray(E, dtype=float)
+    n = E.shape[-1]
+    flat_e = E.reshape(-1, n)
+    q = np.asarray(q)
+    if q.dtype.kind not in "iu":
+        raise ValueError("q must be integers")
+    q = q.astype(np.int64).reshape(-1, len(mesh))
+    chosen = _orbital_selection(orbitals, n)
+    return flat_e, np.asarray(U).reshape(-1, n, n), q, chosen
+
+
+def _tensor_hermitian(total):
+    """The (m, m, m, m) sum as the kernels write it: as an m^2 x m^2 matrix with rows (i, l) and columns (j, m) the upper triangle is
+    kept, the lower is its conjugate, the diagonal's imaginary part is +0 and no -0 stays."""
+    m = total.shape[0]
+    matrix = total.reshape(m * m, m * m)
+    upper = np.triu(matrix, 1)
+    matrix = upper + upper.conj().T + np.diag(matrix.diagonal().real)
+    return matrix.reshape(m, m, m, m) + (0.0 + 0.0j)
+
+
+def _per_reduced_vector(mesh, q, one):
+    """[one(vector) for vector in q], computed once per vector modulo the mesh: q and q + n_d e_d are the same sum."""
+    sizes = np.array([int(s) for s in mesh], dtype=np.int64)
+    done = {}
+    rows = []
+    for vector in q:
+        key = tuple(int(x) for x in np.mod(vector, sizes))
+        if key not in done:
+            done[key] = one(vector)
+        rows.append(done[key])
+    return np.array(rows)
+
+
+def susceptibility_tensor(E, U, mesh, q, mu, T, orbitals=None):
+    """chi_0[NQ][m][m][m][m], complex, indexed [q, i, l, j, m], of DESIGN.md section 29 (convention 2 only: no phases), for the integer
+    vectors ``q`` of shape (NQ, dim):
+
+        chi_0[i, l; j, m](q) = (1 / (T NK)) sum_k sum_{b b'} t(E[k][b], E[k+q][b'])
+                               conj(U[k][i][b]) U[k+q][l][b'] U[k][j][b] conj(U[k+q][m][b'])
+
+    with t = `pair_weight` >= 0 (-T F).  The definition as it stands: with the pair amplitude a[(i, l); b, b'] = conj(U[k][i][b])
+    U[k+q][l][b'] the k-point's term is the contraction ``einsum("c,pc,rc->pr", t, a, conj(a))`` over c = (b, b') all at once, as one
+    matrix product so that BLAS does the n^2 m^4 part.  The sum over b' is NOT taken first: the kernels' factorisation
+    (`susceptibility_tensor_factored`) does not enter, the two are held together by the tests.  ``E``, ``U``, ``orbitals`` as for
+    `orbital_susceptibility`.  The output is made Hermitian as the kernels make it (`_tensor_hermitian`)."""
+    flat_e, flat_u, q, chosen = _tensor_arguments(E, U, mesh, q, orbitals)
+    n_k, n = flat_e.shape
+    m = chosen.size
+    f, g = fermi_tables(flat_e, mu, T)
+
+    def one(vector):
+        to = shifted_points(mesh, vector)
+        a, b = flat_e[:, :, None], flat_e[to][:, None, :]
+        weight = pair_weight(a, b, f[:, :, None], g[:, :, None], f[to][:, None, :], g[to][:, None, :], T)
+        total = np.zeros((m * m, m * m), dtype=complex)
+        for k in range(n_k):  # (the amplitudes of one k-point at a time: m^2 n^2 numbers)
+            left, right = flat_u[k][chosen].conj(), flat_u[to[k]][chosen]
+            amp = (left[:, None, :, None] * right[None, :, None, :]).reshape(m * m, n * n)
+            total += (weight[k].reshape(1, n * n) * amp) @ amp.conj().T
+        return _tensor_hermitian((total / T / n_k).reshape(m, m, m, m))
+
+    return _per_reduced_vector(mesh, q, one)
+
+
+def susceptibility_tensor_factored(E, U, mesh, q, mu, T, orbitals=None):
+    """The same tensor in the kernels' algebra: per k-point and band b, P[i, j] = conj(U[k][i][b]) U[k][j][b] and Q[l, m] = sum_b'
+    t[b, b'] U[k+q][l][b'] conj(U[k+q][m][b']), chi_0[i, l; j, m] = (1 / (T NK)) sum_{k b} P[i, j] Q[l, m].  n times fewer
+    multiplications than the definition; held to `susceptibility_tensor` within `tensor_tolerance`."""
+    flat_e, flat_u, q, chosen = _tensor_arguments(E, U, mesh, q, orbitals)
+    n_k = flat_e.shape[0]
+    m = chosen.size
+    f, g = fermi_tables(flat_e, mu, T)
+
+    def one(vector):
+        to = shifted_points(mesh, vector)
+        a, b = flat_e[:, :, None], flat_e[to][:, None, :]
+        weight = pair_weight(a, b, f[:, :, None], g[:, :, None], f[to][:, None, :], g[to][:, None, :], T)
+        total = np.zeros((m, m, m, m), dtype=complex)
+        for k in range(n_k):
+            here, there = flat_u[k][chosen], flat_u[to[k]][chosen]
+            p = np.einsum("ib,jb->bij", here.conj(), here)
+            w = np.einsum("lc,mc->clm", there, there.conj())
+            big_q = np.einsum("bc,clm->blm", weight[k], w)
+            total += np.einsum("bij,blm->iljm", p, big_q)
+        return _tensor_hermitian(total / T / n_k)
+
+    return _per_reduced_vector(mesh, q, one)
+
+
+def susceptibility_tensor_naive(E, U, mesh, q, mu, T, orbitals=None):
+    """The formula with F as the quotient (`pair_factor_naive`) in one einsum over (k, b, b'), nothing made Hermitian: for comparison
+    where the quotient is well conditioned."""
+    flat_e, flat_u, q, chosen = _tensor_arguments(E, U, mesh, q, orbitals)
+    out = []
+    for vector in q:
+        to = shifted_points(mesh, vector)
+        factor = pair_factor_naive(flat_e[:, :, None], flat_e[to][:, None, :], mu, T)
+        here, there = flat_u[:, chosen, :], flat_u[to][:, chosen, :]
+        out.append(-np.einsum("kbc,kib,klc,kjb,kmc->iljm", factor, here.conj(), there, here, there.conj(), optimize=True) / flat_e.shape[0])
+    return np.array(out)
+
+
+ROUNDINGS_TENSOR = 10.0  # c_T of DESIGN.md 29.5: a term t conj(U_i) U_j U'_l conj(U'_m) as the unfused model forms it holds two complex
+#                          products of two eigenvector factors (three roundings per component each), the scale by t (one) and the
+#                          complex product of the two pairs (three)
+
+
+def tensor_tolerance(n_k, n, T):
+    """tol of DESIGN.md 29.5: the bound on either component of one entry of chi - chi' of two evaluations (the kernels, this model) of
+    the SAME (E, U, mu, T), derived as `orbital_tolerance` is.  Per k the moduli of an entry's terms add up to at most s = 1 / 4 in
+    units of 1 / T: sum_b |U[k][i][b]| |U[k][j][b]| <= 1 and sum_b' |U[k+q][l][b']| |U[k+q][m][b']| <= 1 by Cauchy-Schwarz on unit
+    rows, t <= 1 / 4.  Per side: the sum of NK n^2 terms in any order, NK n^2 s u -- which covers the two-level sum of the factorised
+    form, n - 1 additions over b' inside and NK n - 1 over (k, b) outside, fewer than NK n^2 for every n, its products being those
+    counted in ROUNDINGS_TENSOR with the sum over b' between them;  the factors of a term, relative,
+    (4 ULP_EXP + ULP_EXPM1 + 15 + ROUNDINGS_TENSOR) s u;  the unbounded part of the exponential's argument error, absolute, 4 u.
+    Together [NK n^2 / 2 + 25.5] u / T."""
+    u = 2.0 ** -53
+    side = (n_k * n * n + 4 * ULP_EXP + ULP_EXPM1 + 15 + ROUNDINGS_TENSOR) / 4.0 + 4.0
     return 2.0 * side * u / T
 
 
