@@ -942,6 +942,37 @@ int tbk_optics_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
  * The H(k) kernels on derivative phase rows (-R_a sin, +R_a cos) with the staged operand; a test hook, enqueued only. */
 int tbk_hamilton_derivative_device(tbk_model* m, const double* d_k, int64_t nk, int axis, double* d_D);
 
+/* ---- the transport distribution Sigma[a][c](E) of a uniform k mesh by the tetrahedron method (not in the reference) ---------------
+ * mesh, the energy grid (e_min, e_step, n_e), the simplices, the half-open ranges and the stable sort are those of tbk_dos /
+ * tbk_pdos; dim is 2 or 3.  With E, U of tbk_eigh (convention 2) at the mesh points, D^a = (1 / 2 pi) dH/dk_a and V^a = U^H D^a U,
+ *
+ *     w[a][c](k, b) = Re sum_{b' : fabs(E_b - E_b') <= degeneracy} V^a[b][b'] conj(V^c[b][b'])       (v_a v_c of an isolated band)
+ *
+ * is integrated by Bloechl's corner weights as tbk_pdos integrates A_g, through G = dim (dim + 1) / 2 non-negative channels: channel
+ * a < dim is sum |V^a|^2, channel dim + p is sum |V^a + V^c|^2 for the pairs a < c in the order (0, 1), (0, 2), (1, 2).
+ * cumulative_out: double [G][n_e], channel g integrated up to every grid energy, per unit cell, reduced coordinates, e = hbar = 1, no
+ * spin factor; N[a][c] = (N+[a][c] - N[a][a] - N[c][c]) / 2 is the caller's step.  scale: double [G], positive and finite: the
+ * kernels divide channel g by scale[g] so that the fixed point of tbk_pdos receives weights in [0, 1], and the result is multiplied
+ * back -- exactly, and with bits that do not depend on the handles, when the scales are powers of two.  scale[g] must bound the
+ * channel's weights: the next power of two above 1.0000001 B_a^2, or (B_a + B_c)^2, B_a = sum_R |R_a| ||hop[R]||_F over both halves
+ * of the lattice, does.  A weight above scale[g] is counted, never clamped: the call fails with TBK_ERR_ARGUMENT and names the channel.
+ * For given scales the bits depend neither on a second call nor, for sparse models and dense models on the matrix-vector H(k)
+ * kernel, on TBK_OPT_K_CHUNK or the number of handles (the walk is tbk_optical_conductivity's).  Argument errors
+ * (TBK_ERR_ARGUMENT), before any device is touched: those of tbk_dos, degeneracy negative or not finite, a scale that is not positive
+ * and finite, a k.p handle, a handle given twice. */
+int tbk_transport_distribution(tbk_model* m, const int32_t* mesh, double e_min, double e_step, int64_t n_e, double degeneracy,
+                               const double* scale, double* cumulative_out);
+int tbk_transport_distribution_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, double e_min, double e_step,
+                                     int64_t n_e, double degeneracy, const double* scale, double* cumulative_out);
+/* The weights kernels on the caller's arrays (tests): E[nk][n_orb], U[nk][n_orb][n_orb] complex, D[nk][dim][n_orb][n_orb] complex; all
+ * nk points are one chunk.  W_out: double [nk][G][n_orb], the channels divided by their scales. */
+int tbk_tdf_weights_from_eigensystem(int device, int dim, int n_orb, int64_t nk, const double* E, const double* U, const double* D,
+                                     double degeneracy, const double* scale, double* W_out);
+/* ms[3] = the summed HIP-event time of the derivative H(k) contractions, the weights kernel (the library route's products included),
+ * and accumulate + reduction + scan in this handle's calls made while TBK_OPT_TIMING was on; calls = how many calls; reset = 1
+ * clears.  (The eigensolver stages are in tbk_get_timing.) */
+int tbk_tdf_timing(tbk_model* m, double* ms, int64_t* calls, int reset);
+
 /* ---- k.p models (kdotp.py:51-100): H(k) = sum_p prod_d k_d^powers[p][d] * coeffs[p] ------- */
 int tbk_kdotp_create(int device, int dim, int n_orb, int64_t n_p, const int32_t* powers,
                      const double* coeffs, tbk_kdotp** out);

@@ -176,6 +176,10 @@ SIGNATURES = {
     "tbk_optics_plan": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _c_i64, ctypes.POINTER(_c_i64)]),
     "tbk_optics_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
     "tbk_hamilton_derivative_device": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp]),
+    "tbk_transport_distribution": (_c_int, [_vp, _vp, ctypes.c_double, ctypes.c_double, _c_i64, ctypes.c_double, _vp, _vp]),
+    "tbk_transport_distribution_multi": (_c_int, [_vp, _c_int, _vp, ctypes.c_double, ctypes.c_double, _c_i64, ctypes.c_double, _vp, _vp]),
+    "tbk_tdf_weights_from_eigensystem": (_c_int, [_c_int, _c_int, _c_int, _c_i64, _vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
+    "tbk_tdf_timing": (_c_int, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_c_i64), _c_int]),
     "tbk_kdotp_create": (_c_int, [_c_int, _c_int, _c_int, _c_i64, _vp, _vp, _pp]),
     "tbk_kdotp_destroy": (None, [_vp]),
     "tbk_kdotp_hamilton": (_c_int, [_vp, _vp, _c_i64, _vp]),

@@ -60,6 +60,8 @@ OrbitalSusceptibility = co.namedtuple("OrbitalSusceptibility", ("mu", "q", "orbi
 SusceptibilityTensor = co.namedtuple("SusceptibilityTensor", ("mu", "q", "orbitals", "chi"))
 BerryFlux = co.namedtuple("BerryFlux", ("bands", "planes", "flux", "chern", "link_min"))
 OpticalConductivity = co.namedtuple("OpticalConductivity", ("mu", "omega", "sigma"))
+#: what ``Model.transport_distribution`` returns: the grid (NE,), int^E Sigma (dim, dim, NE) and Sigma at the bin midpoints (dim, dim, NE - 1)
+TransportDistribution = co.namedtuple("TransportDistribution", ("energies", "cumulative", "tdf"))
 
 
 def _devices_from_env():
@@ -2036,6 +2038,91 @@ class Model:
             cell = np.asarray(self.uc, dtype=np.float64)
             sigma = np.einsum("ia,wij,jc->wac", cell, sigma, cell) / abs(np.linalg.det(cell))
         return OpticalConductivity(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), frequencies, sigma)
+
+    def _transport_scales(self):
+        """The power-of-two scales ``s_g`` of the ``dim (dim + 1) / 2`` channels of :meth:`transport_distribution`, from the model
+        alone: ``B_a = sum_R |R_a| ||hop[R]||_F`` over both halves of the lattice bounds ``||D^a(k)||_2``, so every row sum of
+        ``|V^a|^2`` is at most ``B_a^2`` and every one of ``|V^a + V^c|^2`` at most ``(B_a + B_c)^2``; ``s_g`` is the power of two
+        above 1.0000001 times that bound (1 when it is 0)."""
+        bound = np.zeros(self.dim, dtype=np.float64)
+        for key, mat in self._hop_items():
+            norm = float(np.sqrt((np.abs(mat.data if self._sparse else mat) ** 2).sum()))
+            bound += 2.0 * np.abs(np.array(key, dtype=np.float64)) * norm  # (the stored half and its conjugate)
+        channel = [bound[a] ** 2 for a in range(self.dim)]
+        channel += [(bound[a] + bound[c]) ** 2 for a in range(self.dim) for c in range(a + 1, self.dim)]
+        return np.array([1.0 if b == 0.0 else float(np.ldexp(1.0, np.frexp(1.0000001 * b)[1])) for b in channel], dtype=np.float64)
+
+    def transport_distribution(self, mesh, energies, *, degeneracy=1e-8, cartesian=False):
+        """
+        The transport distribution ``Sigma[a, c](E) = (1 / NK) sum_k sum_b v_a(k, b) v_c(k, b) delta(E - E_kb)`` of a uniform k mesh
+        by the linear tetrahedron method, computed on the GPU from the eigensystem and ``dH/dk`` of one chunk of the mesh at a time:
+        neither eigenvectors nor velocity matrices leave the device, ``dim (dim + 1) / 2 * NE`` doubles come back.  It is what
+        Boltzmann transport in the relaxation-time approximation starts from (``tbmodels_amd.transport_coefficients``).  Not in
+        the reference.
+
+        ``mesh`` and ``energies`` are those of :meth:`dos`, with the same checks; the simplices, the half-open ranges and the stable
+        sort are those of :meth:`dos` / :meth:`pdos`.  Returns the named tuple ``(energies, cumulative, tdf)``: ``cumulative`` is
+        ``float64 (dim, dim, NE)``, ``int^E Sigma[a, c]`` at the grid energies, and ``tdf = diff(cumulative) / step`` (shape
+        ``(dim, dim, NE - 1)``) belongs to the bin midpoints, like ``dos``.  Both are exactly symmetric in ``(a, c)``: ``a <= c`` is
+        computed and the other half mirrored.
+
+        Definition.  ``E, U`` of ``eigh(k, convention=2)``, ``D^a`` and ``V^a = U^H D^a U`` as in :meth:`optical_conductivity`;
+        reduced coordinates, ``e = hbar = 1``, per unit cell, no spin factor::
+
+            w[a, c](k, b) = Re sum_{b' : |E_kb - E_kb'| <= degeneracy}  V^a[b, b'] conj(V^c[b, b'])
+            N[a, c](E)    = (1 / (S NK)) sum_simplices sum_b sum_corners  w_corner(E) w[a, c](corner, b)       = cumulative
+            Sigma[a, c]   = diff(N[a, c]) / step
+
+        For an isolated band ``w = v_a v_c``.  Inside a degenerate set the diagonal of ``V`` depends on the basis the eigensolver
+        returns (see :meth:`eigh`); the sum of ``w`` over the set, ``Re tr(P V^a P V^c)``, does not -- the statement :meth:`pdos`
+        makes about ``A_g``.  The pair criterion is the plain comparison of the doubles, not chained into clusters;
+        ``degeneracy`` (energy units, ``>= 0`` and finite) is its threshold.  There is no ``convention`` argument: the term that
+        convention 1 adds to ``V^a[b, b']`` carries the factor ``(E_b - E_b')``, which vanishes on the pairs that enter (up to
+        ``degeneracy`` times a position, far below the rounding of ``V``), so both conventions give the same ``w``.
+
+        ``cartesian=True`` needs ``uc`` (else ``ValueError``) and returns ``uc^T N uc / |det uc|`` per energy, a host transform, as
+        in :meth:`optical_conductivity`.
+
+        The device integrates ``dim (dim + 1) / 2`` non-negative channels -- ``sum |V^a|^2`` and, for ``a < c``,
+        ``sum |V^a + V^c|^2`` -- each divided by a power of two derived from the hoppings alone, in the 64-bit fixed point of
+        :meth:`pdos`; ``N[a, c] = (N+[a, c] - N[a, a] - N[c, c]) / 2`` is formed on the host.  The bits do not depend on a second call
+        nor, for sparse models and dense models on the matrix-vector H(k) kernel, on ``TBK_OPT_K_CHUNK`` or the ``devices``.
+        Error bound: DESIGN.md section 30 (``tools/tdf_model.py`` ``tolerance``).  One-dimensional models raise ``ValueError``;
+        :class:`KdotpModel` has no Brillouin zone and no such method.
+        """
+        mesh_array, grid, step = self._dos_arguments(mesh, energies)
+        if isinstance(degeneracy, (bool, np.bool_)) or not isinstance(degeneracy, (int, float, np.integer, np.floating)):
+            raise ValueError("degeneracy must be a real number, got {!r}".format(degeneracy))
+        threshold = float(degeneracy)
+        if not np.isfinite(threshold) or threshold < 0.0:
+            raise ValueError("degeneracy must be finite and >= 0, got {!r}".format(degeneracy))
+        if not isinstance(cartesian, (bool, np.bool_)):
+            raise ValueError("cartesian must be True or False, got {!r}".format(cartesian))
+        if cartesian and self.uc is None:
+            raise ValueError("cartesian=True needs the unit cell: the model has no uc")
+        dim = self.dim
+        scale = self._transport_scales()
+        channels = np.empty((scale.shape[0], grid.shape[0]), dtype=np.float64)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_transport_distribution_multi(handles, n_handles, _lib.ptr(mesh_array), float(grid[0]), step, grid.shape[0],
+                                                            threshold, _lib.ptr(scale), _lib.ptr(channels))
+            )
+        total = np.empty((dim, dim, grid.shape[0]), dtype=np.float64)
+        pair = dim
+        for a in range(dim):
+            total[a, a] = channels[a]
+            for c in range(a + 1, dim):
+                total[a, c] = (channels[pair] - channels[a] - channels[c]) / 2.0
+                total[c, a] = total[a, c]
+                pair += 1
+        if cartesian:
+            cell = np.asarray(self.uc, dtype=np.float64)
+            total = np.einsum("ia,ijw,jc->acw", cell, total, cell) / abs(np.linalg.det(cell))
+            total = (total + total.transpose(1, 0, 2)) / 2.0  # (the transform of a symmetric tensor, symmetric to the bit again)
+        return TransportDistribution(grid, total, np.diff(total, axis=2) / step)
 
     def _orbital_selection_argument(self, orbitals):
         """The checks of ``orbitals`` that ``orbital_susceptibility`` and ``susceptibility_tensor`` share: ``int64 (m,)`` distinct

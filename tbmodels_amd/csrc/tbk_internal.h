@@ -178,11 +178,11 @@ struct SpanRecorder {
 };
 
 // The sums the mesh calls book their kernel times on, one row per family (tbk_dos_timing, tbk_pdos_timing, tbk_fermi_timing,
-// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing, tbk_surface_timing, tbk_transmission_timing, tbk_device_green_timing, tbk_device_current_timing, tbk_transmission_ensemble_timing, tbk_transmission_channels_timing, tbk_optics_timing: what each counts differs and is
+// tbk_occ_timing, tbk_dm_timing, tbk_chi_timing, tbk_berry_timing, tbk_green_timing, tbk_green_dressed_timing, tbk_surface_timing, tbk_transmission_timing, tbk_device_green_timing, tbk_device_current_timing, tbk_transmission_ensemble_timing, tbk_transmission_channels_timing, tbk_optics_timing, tbk_tdf_timing: what each counts differs and is
 // listed in DESIGN.md section 10)
-enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_SURFACE, TIMED_TRANSMISSION, TIMED_DEVICE_GREEN, TIMED_DEVICE_CURRENT, TIMED_TRANSMISSION_ENSEMBLE, TIMED_TRANSMISSION_CHANNELS, TIMED_OPTICS, TIMED_COUNT };
+enum TimedFamily { TIMED_DOS, TIMED_PDOS, TIMED_FERMI, TIMED_OCC, TIMED_DM, TIMED_CHI, TIMED_BERRY, TIMED_GREEN, TIMED_DYSON, TIMED_SURFACE, TIMED_TRANSMISSION, TIMED_DEVICE_GREEN, TIMED_DEVICE_CURRENT, TIMED_TRANSMISSION_ENSEMBLE, TIMED_TRANSMISSION_CHANNELS, TIMED_OPTICS, TIMED_TDF, TIMED_COUNT };
 struct TimedSums {
-    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green, the dressed green, surface, transmission, the device green, the device current, the ensemble, the channels and the optical conductivity three)
+    double ms[3] = {0.0, 0.0, 0.0};  // per stage of the family (dos and fermi have one, occ, dm, chi, berry, green, the dressed green, surface, transmission, the device green, the device current, the ensemble, the channels, the optical conductivity and the transport distribution three)
     int64_t calls = 0;
     int64_t passes = 0;  // fermi: the passes of its searches
 };
@@ -697,6 +697,18 @@ int tbk_dos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_coun
 int tbk_pdos_check_groups(int n_orb, const int32_t* group_offsets, const int32_t* group_orbitals, int n_groups);
 int tbk_pdos_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_count, const int32_t* group_offsets, const int32_t* group_orbitals,
                   int n_groups, double e_min, double e_step, int64_t n_e, double* nos_out);
+// ... its plan and launch for weights the caller made itself (tbk_tdf.hip): W[nk][n_groups][n_orb] in [0, 1]
+int tbk_pdos_weighted_bytes(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb, int n_groups, int64_t n_e, size_t* ws_bytes);
+int tbk_pdos_weighted_launch(hipStream_t s, int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb, int n_groups, int64_t n_e,
+                             const double* d_E, const double* d_W, double e_min, double e_step, double denom, void* d_ws, double* d_nos,
+                             SpanRecorder& timer);
+
+// tbk_tdf.hip: the checks that need no device, and one handle's part of a call: the whole call (cumulative_out[G][n_e]), or for a call
+// on several handles E and W of the planes [p_lo, p_lo + p_count) of axis 0 to the host, or the accumulation of the whole mesh from there
+enum { TBK_TDF_WHOLE = 0, TBK_TDF_WEIGHTS = 1, TBK_TDF_ACCUMULATE = 2 };
+int tbk_tdf_check_arguments(int dim, double degeneracy, const double* scale);
+int tbk_tdf_slab(tbk_model* m, const int32_t* mesh, int64_t p_lo, int64_t p_count, double e_min, double e_step, int64_t n_e, double degeneracy,
+                 const double* scale, int mode, double* h_E, double* h_W, double* cumulative_out);
 
 // tbk_peak.hip
 int tbk_run_mfma_f64_peak(double* tflops);

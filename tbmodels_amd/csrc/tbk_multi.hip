@@ -284,6 +284,37 @@ extern "C" int tbk_pdos_multi(tbk_model* const* handles, int n_handles, const in
     return TBK_OK;
 }
 
+// The transport distribution on several devices (tbk_tdf.hip): the slabs of tbk_pdos_multi for the expensive half -- every handle
+// walks the eigensystem of its own planes and leaves E and the channel weights W at their place in two host arrays of the whole
+// mesh -- and then ONE accumulation of the whole mesh on the first handle.  Shares of the channels, each divided and rounded by its
+// handle, would add up to other bits than the one launch of a single handle; E and W of a k-point do not know their handle.
+extern "C" int tbk_transport_distribution_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, double e_min, double e_step,
+                                                int64_t n_e, double degeneracy, const double* scale, double* cumulative_out) {
+    TBK_CHECK(check_handles(handles, n_handles));
+    for (int i = 0; i < n_handles; ++i) {
+        TBK_ARG(!handles[i]->kdotp, "a k.p model has no Brillouin zone");
+        for (int j = 0; j < i; ++j) TBK_ARG(handles[j] != handles[i], "a handle appears twice");
+    }
+    TBK_ARG(mesh != nullptr && cumulative_out != nullptr, "mesh / cumulative is NULL");
+    if (n_handles == 1) return tbk_transport_distribution(handles[0], mesh, e_min, e_step, n_e, degeneracy, scale, cumulative_out);
+    const int dim = handles[0]->dim, n = handles[0]->n_orb;
+    TBK_CHECK(tbk_tdf_check_arguments(dim, degeneracy, scale));
+    int64_t nk_total = 0;
+    TBK_CHECK(tbk_dos_check(dim, mesh, e_step, n_e, cumulative_out, &nk_total));
+    TBK_ARG(std::isfinite(e_min), "e_min is not finite");
+    const int64_t n0 = mesh[0], plane = nk_total / n0;
+    const size_t G = (size_t)(dim * (dim + 1) / 2);
+    std::vector<double> h_E, h_W;
+    TBK_CHECK(tetra_shares(&h_E, (size_t)nk_total * n));
+    TBK_CHECK(tetra_shares(&h_W, (size_t)nk_total * n * G));
+    TBK_CHECK(run_slabs(n_handles, n0, [&](int i, int64_t lo, int64_t count) {
+        const size_t at = (size_t)(lo * plane) * n;
+        return tbk_tdf_slab(handles[i], mesh, lo, count, e_min, e_step, n_e, degeneracy, scale, TBK_TDF_WEIGHTS, h_E.data() + at, h_W.data() + at * G,
+                            cumulative_out);
+    }));
+    return tbk_tdf_slab(handles[0], mesh, 0, n0, e_min, e_step, n_e, degeneracy, scale, TBK_TDF_ACCUMULATE, h_E.data(), h_W.data(), cumulative_out);
+}
+
 // k.p models on several devices (kdotp.py:51-100 has the same two methods as Model): the same slabs, through the k.p
 // entry points of every staged copy
 extern "C" int tbk_kdotp_eigenval_multi(tbk_kdotp* const* handles, int n_handles, const double* k, int64_t nk, double* E_out) {

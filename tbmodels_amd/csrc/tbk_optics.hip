@@ -39,13 +39,12 @@
 
 #include "tbk_occ.h"
 #include "tbk_pair.h"
-#include "tbk_zmfma.h"
+#include "tbk_velocity.h"
 
 namespace {
 
 constexpr int OPT_THREADS = PAIR_THREADS;
 constexpr int OPT_GROUP = 256;                          // mesh points per summation group
-constexpr int OPT_FUSED_MAX = 64;                       // orbitals of the fused kernel, at most
 constexpr size_t OPT_PART_BUDGET = size_t(1) << 30;     // the partials of one pass, at most
 constexpr int64_t OPT_MAX_NW = int64_t(1) << 23;
 constexpr int64_t OPT_MAX_NK = int64_t(1) << 23;
@@ -113,30 +112,8 @@ struct OptArgs {
     int64_t k_off = 0;             // the chunk's first point in part
 };
 
-// the place of element (row o, column c) in a plane of NP x NP doubles
-template <int NP>
-__device__ __forceinline__ int opt_at(int o, int c) {
-    return o * NP + (NP == 16 ? c : c ^ ((o & 1) << 4));
-}
-
-// (cr, ci) += X^H Y for the wave's tile row ti and tiles tj0 ... tj0 + TPW - 1: `steps` MFMA steps of four rows of the planes
-template <int NP, int TPW>
-__device__ __forceinline__ void opt_product(const double* __restrict__ xr, const double* __restrict__ xi, const double* __restrict__ yr,
-                                            const double* __restrict__ yi, int steps, int ti, int tj0, int lane, zd4 (&cr)[TPW], zd4 (&ci)[TPW]) {
-    const int l15 = lane & 15, lq = lane >> 4;
-#pragma unroll 1
-    for (int s = 0; s < steps; ++s) {
-        const int o = 4 * s + lq;
-        const int ia = opt_at<NP>(o, ti * 16 + l15);
-        const double ar = xr[ia], ai = xi[ia];
-#pragma unroll
-        for (int t = 0; t < TPW; ++t) {
-            const int ib = opt_at<NP>(o, (tj0 + t) * 16 + l15);
-            const double br = yr[ib], bi = yi[ib];
-            zmfma_ahb(ar, ai, br, bi, cr[t], ci[t]);
-        }
-    }
-}
+// (opt_at and opt_product -- the planes and the product of two staged matrices -- are tbk_velocity.h's.  The staging loops below stay
+// written out: through the header's opt_stage the fused kernels compile to other instruction streams)
 
 // the wave's sums of one chunk of frequencies into part: KPW == 4, a wave per k-point, lane 0 writes; else the block's four waves are
 // added in order through LDS
@@ -483,8 +460,7 @@ struct OptChunk {
     double* d_P = nullptr;          // library, convention 1: U^H diag(pos_a) U with the strides of d_D
 };
 
-// The library route's products on row-major matrices, which the library reads as their transposes: V^T = U^T D^T conj(U), so with
-// Uc, Dc the library's views T = Dc Uc^H and Vc = Uc T; V^a takes D^a's place.  Convention 1: T = diag(pos_a) Uc^H from
+// The library route's products: V^a takes D^a's place (opt_library_rotate, tbk_velocity.h).  Convention 1: T = diag(pos_a) Uc^H from
 // opt_scale_kernel, Pc = Uc T.  Calls stay below 2^29 elements, as those of tbk_eigh.
 int opt_library_products(const OptPlan& L, const OptChunk& c) {
     const int n = L.n;
@@ -497,10 +473,7 @@ int opt_library_products(const OptPlan& L, const OptChunk& c) {
             const Z* Uc = reinterpret_cast<const Z*>(c.d_U) + (size_t)b0 * nn;
             Z* Da = reinterpret_cast<Z*>(c.d_D) + (size_t)b0 * c.d_sk + (size_t)a * c.d_sa;
             Z* Tc = reinterpret_cast<Z*>(c.d_T) + (size_t)b0 * nn;
-            TBK_ROCBLAS(rocblas_zgemm_strided_batched(c.blas, rocblas_operation_none, rocblas_operation_conjugate_transpose, n, n, n, &one, Da, n,
-                                                      (rocblas_stride)c.d_sk, Uc, n, (rocblas_stride)nn, &zero, Tc, n, (rocblas_stride)nn, nb));
-            TBK_ROCBLAS(rocblas_zgemm_strided_batched(c.blas, rocblas_operation_none, rocblas_operation_none, n, n, n, &one, Uc, n, (rocblas_stride)nn, Tc,
-                                                      n, (rocblas_stride)nn, &zero, Da, n, (rocblas_stride)c.d_sk, nb));
+            TBK_CHECK(opt_library_rotate(c.blas, n, nb, Uc, Da, c.d_sk, Tc));
             if (c.d_pos != nullptr) {
                 Z* Pa = reinterpret_cast<Z*>(c.d_P) + (size_t)b0 * c.d_sk + (size_t)a * c.d_sa;
                 const int64_t total = (int64_t)nb * nn;

@@ -346,6 +346,23 @@ int tbk_pdos_check_groups(int n_orb, const int32_t* group_offsets, const int32_t
     return TBK_OK;
 }
 
+// pdos_plan and pdos_launch for a caller that brings weights of its own in [0, 1] (tbk_tdf.hip): the bytes of the workspace, and the
+// launch of `cells0` cells out of `planes0` planes on it.  The recorder's stages are pdos_launch's: 1 accumulate, 2 reduction + scan.
+int tbk_pdos_weighted_bytes(int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb, int n_groups, int64_t n_e, size_t* ws_bytes) {
+    PdosLaunch L;
+    TBK_CHECK(pdos_plan(dim, mesh, cells0, planes0, n_orb, n_groups, n_e, &L));
+    *ws_bytes = L.ws_bytes;
+    return TBK_OK;
+}
+
+int tbk_pdos_weighted_launch(hipStream_t s, int dim, const int32_t* mesh, int64_t cells0, int64_t planes0, int n_orb, int n_groups, int64_t n_e,
+                             const double* d_E, const double* d_W, double e_min, double e_step, double denom, void* d_ws, double* d_nos,
+                             SpanRecorder& timer) {
+    PdosLaunch L;
+    TBK_CHECK(pdos_plan(dim, mesh, cells0, planes0, n_orb, n_groups, n_e, &L));
+    return pdos_launch(s, dim, L, d_E, d_W, e_min, e_step, denom, d_ws, d_nos, timer);
+}
+
 extern "C" int tbk_pdos_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, int n_groups, const double* E, const double* W,
                                          double e_min, double e_step, int64_t n_e, double* nos_out) {
     int64_t nk = 0;
