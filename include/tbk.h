@@ -818,6 +818,47 @@ int tbk_chi_orbital_plan(int64_t nk, int n_orb, int m, int64_t n_q, int64_t part
 /* (Kernel times of these calls are booked into tbk_chi_timing's three stages: the Fermi tables, the rank-K update, the reduction of the
  * slices; its call count includes them.) */
 
+/* ---- the orbital-resolved bare dynamic susceptibility chi_0[i][j](q, omega + i eta) of a uniform k mesh (not in the reference) ----
+ * Mesh, k+q, q, E, U, D(q), convention, mu (mode, value) and T are those of tbk_susceptibility, omega, eta and z = omega + i eta those
+ * of tbk_dynamic_susceptibility, A and the selection those of tbk_orbital_susceptibility (csrc/tbk_chi.hip):
+ *     chi_0[i][j](q, z) = -(1 / NK) sum_k sum_{b b'} g(E[k][b], E[k+q][b']) / (E[k][b] - E[k+q][b'] + z) A[i; b, b'] conj(A[j; b, b'])
+ * No spin factor; the sign is that of the other susceptibilities; the sum over (i, j) is tbk_dynamic_susceptibility's chi_0(q, z) with
+ * matrix elements.  g and Delta = E[k][b] - E[k+q][b'] once per pair as there; per frequency x = Delta + omega, r = 1 / (x^2 + eta^2),
+ * c = (g r x, -(g r eta)), X = c A, and chi = (0 - sum X conj(A)) / NK per component.  The matrix is NOT Hermitian: all m^2 entries are
+ * computed.  chi_0[i][j](-q, -omega + i eta) = conj chi_0[i][j](q, omega + i eta).  For given (E, U, mu, T, eta) the bits of an entry
+ * depend on q modulo the mesh, D(q), omega_j, i and j alone -- not on the other vectors, frequencies or selected orbitals, their order,
+ * the batches, the frequency passes, the register chunk or the number of handles.  |error| per component <=
+ * chi_model.dynamic_orbital_tolerance.
+ * chi_out: [n_q][n_w][m][m] complex (Re, Im interleaved) in the caller's order of orbitals.  Argument errors (TBK_ERR_ARGUMENT), before
+ * any device is touched: those of tbk_orbital_susceptibility and of tbk_dynamic_susceptibility, with at most 65535 frequencies per call
+ * (one grid row of the reduction each). */
+/* The kernels alone on an eigensystem the caller brings (E, U, phases as for tbk_chi_from_eigensystem; U is required).  part_bytes,
+ * k_slice: as in tbk_chi_orbital_dynamic_plan. */
+int tbk_chi_orbital_dynamic_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U, double mu,
+                                             double T, int64_t n_q, const int64_t* q, const double* phases, int m, const int32_t* orbitals,
+                                             int64_t n_w, const double* omega, double eta, int64_t part_bytes, int64_t k_slice,
+                                             double* chi_out);
+/* The whole call: tbk_susceptibility's driver -- the same mu, the same resident eigensystem, the same wait on every exit. */
+int tbk_dynamic_orbital_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q,
+                                       int64_t n_w, const double* omega, double eta, int n_sel, const int32_t* orbitals, int convention,
+                                       const double* pos, double* mu_out, double* chi_out);
+/* On several devices from one process: tbk_susceptibility_multi's split, a contiguous share of the vectors (with all frequencies) per
+ * handle. */
+int tbk_dynamic_orbital_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value, double T,
+                                             int64_t n_q, const int64_t* q, int64_t n_w, const double* omega, double eta, int m,
+                                             const int32_t* orbitals, int convention, const double* pos, double* mu_out, double* chi_out);
+/* How a call on nk mesh points, m of n_orb orbitals, n_q vectors and n_w <= 65535 frequencies is run: out[0] = the kernel's template
+ * (as for tbk_chi_orbital_plan), out[1] = blocks per (q, omega): all nb^2 ordered ones, out[2] = k-points per slice -- k_slice, or for 0
+ * the library's own, a function of (nk, n_orb) alone -- out[3] = slices, out[4] = frequencies per register chunk of the kernel.  The
+ * partial sums take 16 out[3] m'^2 bytes per (q, omega), m' = m padded to the block, and may take part_bytes (0: 256 MiB).  When all
+ * frequencies of one vector fit, out[7] = n_w, out[8] = 1, out[5] = vectors per batch (at most 4096, and as many as the grid takes with
+ * their chunks) and out[6] = batches; else out[5] = 1, out[6] = n_q and the frequencies go in out[8] passes of out[7] (whole register
+ * chunks when one fits), the update computed again in each.  out[5] = 0: not one (q, omega) fits, the call returns TBK_ERR_MEMORY.
+ * out[9] = out[5] out[7], the (q, omega) per launch.  out: int64 [10]. */
+int tbk_chi_orbital_dynamic_plan(int64_t nk, int n_orb, int m, int64_t n_q, int64_t n_w, int64_t part_bytes, int64_t k_slice, int64_t* out);
+/* (Kernel times of these calls are booked into tbk_chi_timing's three stages: the Fermi tables, the complex-weighted rank-K update, the
+ * reduction of the slices; its call count includes them.) */
+
 /* ---- the four-index bare static susceptibility chi_0[i][l][j][m](q) of a uniform k mesh (not in the reference) ------------------
  * Mesh, k+q, q, E, U, mu (mode, value), T and t are those of tbk_orbital_susceptibility; convention 2 only: there is no phase table
  * (csrc/tbk_chi.hip):

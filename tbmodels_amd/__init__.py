@@ -7,7 +7,7 @@ C ABI of ``include/tbk.h``.  See DESIGN.md for the path and its kernels, INTEGRA
 binding a TBmodels maintainer would add.
 """
 
-from ._model import BerryFlux, DensityMatrix, DynamicSusceptibility, GreenFunction, Model, OpticalConductivity, OrbitalSusceptibility, Susceptibility, SusceptibilityTensor, TransportDistribution
+from ._model import BerryFlux, DensityMatrix, DynamicOrbitalSusceptibility, DynamicSusceptibility, GreenFunction, Model, OpticalConductivity, OrbitalSusceptibility, Susceptibility, SusceptibilityTensor, TransportDistribution
 from .transport import TransportCoefficients, transport_coefficients
 from .kdotp import KdotpModel
 from . import synthetic
@@ -15,5 +15,5 @@ from . import io
 
 __version__ = "0.1.0"
 
-__all__ = ("Model", "KdotpModel", "DensityMatrix", "GreenFunction", "Susceptibility", "DynamicSusceptibility", "OrbitalSusceptibility", "SusceptibilityTensor", "BerryFlux", "OpticalConductivity", "TransportDistribution", "TransportCoefficients",
+__all__ = ("Model", "KdotpModel", "DensityMatrix", "GreenFunction", "Susceptibility", "DynamicSusceptibility", "OrbitalSusceptibility", "DynamicOrbitalSusceptibility", "SusceptibilityTensor", "BerryFlux", "OpticalConductivity", "TransportDistribution", "TransportCoefficients",
            "transport_coefficients", "synthetic", "io")

@@ -156,6 +156,13 @@ SIGNATURES = {
     "tbk_orbital_susceptibility_multi": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _c_int, _vp, _c_int, _vp,
                                                   _vp, _vp]),
     "tbk_chi_orbital_plan": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _c_i64, _c_i64, ctypes.POINTER(_c_i64)]),
+    "tbk_chi_orbital_dynamic_from_eigensystem": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, _vp, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _vp,
+                                                          _c_int, _vp, _c_i64, _vp, ctypes.c_double, _c_i64, _c_i64, _vp]),
+    "tbk_dynamic_orbital_susceptibility": (_c_int, [_vp, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _c_i64, _vp, ctypes.c_double,
+                                                    _c_int, _vp, _c_int, _vp, _vp, _vp]),
+    "tbk_dynamic_orbital_susceptibility_multi": (_c_int, [_vp, _c_int, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _c_i64, _vp,
+                                                          ctypes.c_double, _c_int, _vp, _c_int, _vp, _vp, _vp]),
+    "tbk_chi_orbital_dynamic_plan": (_c_int, [_c_i64, _c_int, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(_c_i64)]),
     "tbk_chi_tensor_from_eigensystem": (_c_int, [_c_int, _c_int, _vp, _c_int, _vp, _vp, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _c_int, _vp,
                                                  _c_i64, _c_i64, _vp]),
     "tbk_susceptibility_tensor": (_c_int, [_vp, _vp, _c_int, ctypes.c_double, ctypes.c_double, _c_i64, _vp, _c_int, _vp, _vp, _vp]),

@@ -57,6 +57,7 @@ DeviceCurrentBonds = co.namedtuple("DeviceCurrentBonds", DeviceCurrent._fields +
 Susceptibility = co.namedtuple("Susceptibility", ("mu", "q", "chi"))
 DynamicSusceptibility = co.namedtuple("DynamicSusceptibility", ("mu", "q", "omega", "chi"))
 OrbitalSusceptibility = co.namedtuple("OrbitalSusceptibility", ("mu", "q", "orbitals", "chi"))
+DynamicOrbitalSusceptibility = co.namedtuple("DynamicOrbitalSusceptibility", ("mu", "q", "omega", "orbitals", "chi"))
 SusceptibilityTensor = co.namedtuple("SusceptibilityTensor", ("mu", "q", "orbitals", "chi"))
 BerryFlux = co.namedtuple("BerryFlux", ("bands", "planes", "flux", "chern", "link_min"))
 OpticalConductivity = co.namedtuple("OpticalConductivity", ("mu", "omega", "sigma"))
@@ -1880,7 +1881,7 @@ class Model:
 
     @staticmethod
     def _frequency_arguments(omega, eta):
-        """The checks of ``omega`` and ``eta`` that ``dynamic_susceptibility`` and ``optical_conductivity`` share: ``(omega float64
+        """The checks of ``omega`` and ``eta`` that ``dynamic_susceptibility``, ``dynamic_orbital_susceptibility`` and ``optical_conductivity`` share: ``(omega float64
         (NW,), eta)`` or ``ValueError``."""
         if omega is None or isinstance(omega, (str, bytes)):
             raise ValueError("omega must be a real number or a real array of shape (NW,), got {!r}".format(omega))
@@ -2125,7 +2126,7 @@ class Model:
         return TransportDistribution(grid, total, np.diff(total, axis=2) / step)
 
     def _orbital_selection_argument(self, orbitals):
-        """The checks of ``orbitals`` that ``orbital_susceptibility`` and ``susceptibility_tensor`` share: ``int64 (m,)`` distinct
+        """The checks of ``orbitals`` that ``orbital_susceptibility``, ``dynamic_orbital_susceptibility`` and ``susceptibility_tensor`` share: ``int64 (m,)`` distinct
         indices in ``[0, size)`` in the caller's order (``None``: all of them in order) or ``ValueError``."""
         if orbitals is None:
             selected = np.arange(self.size, dtype=np.int64)
@@ -2203,6 +2204,75 @@ class Model:
                                                             _lib.ptr(mu), _lib.ptr(chi))
             )
         return OrbitalSusceptibility(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, selected, chi)
+
+    def dynamic_orbital_susceptibility(self, mesh, q, omega, *, eta, temperature, energy=None, n_electrons=None, orbitals=None, convention=2):
+        """
+        The orbital-resolved bare dynamic susceptibility ``chi_0[i, j](q, omega + i eta)`` of a uniform k mesh -- what a
+        multi-orbital RPA needs once it leaves ``omega = 0``: spin-excitation spectra, orbital-resolved loss functions, the dynamic
+        vertex ``(1 - chi_0 U)^-1 chi_0`` -- computed on the GPU from the eigensystem of the whole mesh, which never leaves it.  Not
+        in the reference.
+
+        ``mesh``, ``q``, ``temperature``, ``energy``, ``n_electrons`` and ``convention`` are those of :meth:`susceptibility`,
+        ``omega`` and ``eta`` those of :meth:`dynamic_susceptibility`, ``orbitals`` that of :meth:`orbital_susceptibility`, all with
+        the same errors; at most 65535 frequencies per call.  Returns the named tuple ``(mu, q, omega, orbitals, chi)``: ``mu``,
+        ``q``, ``omega`` and ``orbitals`` as for those calls and ``chi`` as ``complex128 (NQ, NW, m, m)`` in the order of
+        ``orbitals``.
+
+        Definition.  With ``A`` of :meth:`orbital_susceptibility`, ``g = f(E[k, b]) - f(E[k+q, b'])`` and ``z = omega + i eta`` of
+        :meth:`dynamic_susceptibility`::
+
+            A(k, q)[i; b, b']  = conj(U[k, i, b]) D(q)[i] U[k+q, i, b']
+            chi_0[i, j](q, z)  = -(1 / NK) sum_k sum_{b, b'} g / (E[k, b] - E[k+q, b'] + z) A[i; b, b'] conj(A[j; b, b'])
+
+        No spin factor; the sign is that of the other susceptibilities.  ``g`` is evaluated without cancellation as in
+        :meth:`dynamic_susceptibility`; per pair ``g`` and ``Delta = E[k, b] - E[k+q, b']`` are computed once, per frequency
+        ``x = Delta + omega``, ``r = 1 / (x^2 + eta^2)``, ``c = (g r x, -(g r eta))``, and ``chi = (0 - sum c A conj(A)) / NK`` per
+        component.  A frequency that hits a transition exactly (``x = 0``) is finite.  The matrix is not Hermitian --
+        ``chi_0 = -(H_r + i H_i) / NK`` with two different Hermitian parts -- so all ``m^2`` entries are computed, as one
+        complex-weighted product on the FP64 matrix pipe.
+
+        Properties, with ``Herm(M) = (M + M^H) / 2`` and ``B(M) = (M - M^H) / (2i)``.  (1) ``chi_0[i, j](-q, -omega + i eta) = conj
+        chi_0[i, j](q, omega + i eta)``.  (2) ``sum_ij chi_0[i, j](q, z)`` is ``chi_0(q, z)`` of :meth:`dynamic_susceptibility` with
+        matrix elements.  (3) ``Herm chi_0(q, i eta)`` and ``orbital_susceptibility(q) - Herm chi_0(q, i eta)`` are positive
+        semidefinite.  (4) ``omega [B(chi_0(q, omega + i eta)) + B(chi_0(-q, omega + i eta))^T]`` is positive semidefinite and
+        exactly 0 at ``omega = 0``.  (5) With ``mu`` 746 ``T`` or more outside the spectrum every entry is ``+0`` in both
+        components.  (6) For ``convention=2`` ``q + n_d e_d`` has the bits of ``q``.  (7) ``chi_0`` does not depend on the phases of
+        the eigenvectors or on the basis inside degenerate clusters.  (8) The bits of ``chi_0[i, j](q, omega_j)`` do not depend on
+        the other vectors or frequencies, on their order or on the number of ``devices``; duplicates have equal bits and a second
+        call the bits of the first.  (9) A selection returns the bits of the same entries of the full matrix, whatever else is
+        selected and in whatever order.
+
+        Error bound of either component of an entry for a given eigensystem, with ``u = 2^-53``, ``W`` the bandwidth and allowances
+        of 2 for ``exp``, ``expm1`` and the quotient (DESIGN.md 31.5; ``tools/chi_model.py`` ``dynamic_orbital_tolerance``)::
+
+            |error| <= 2 [ NK size^2 + 51 + (2 W + |omega|) / eta ] u / eta
+
+        The work is ``8 size^2 m^2`` flops per ``(k, q, omega)``.  One-dimensional models raise ``ValueError``.  The eigenvectors of
+        the whole mesh must fit the device, else ``MemoryError``.  The partial sums take ``16 slices m'^2`` bytes per ``(q,
+        omega)`` (``m'``: ``m`` padded to 16, above 16 to 64); when one vector's do not fit 256 MiB the frequencies go in passes and
+        the update is computed again in each.  With several ``devices`` every device holds the whole mesh's eigensystem and takes a
+        contiguous share of ``q`` with all frequencies.
+        """
+        mesh_array, vectors, t_value, mode, value, pos = self._susceptibility_arguments("dynamic_orbital_susceptibility", mesh, q, temperature,
+                                                                                        energy, n_electrons, True, convention)
+        frequencies, eta_value = self._frequency_arguments(omega, eta)
+        selected = self._orbital_selection_argument(orbitals)
+        if frequencies.shape[0] > 65535:
+            raise ValueError("dynamic_orbital_susceptibility takes up to 65535 frequencies per call, got {}".format(frequencies.shape[0]))
+        chosen = np.ascontiguousarray(selected, dtype=np.int32)
+        mu = np.empty(4, dtype=np.float64)
+        chi = np.empty((vectors.shape[0], frequencies.shape[0], chosen.shape[0], chosen.shape[0]), dtype=np.complex128)
+        with self._call_lock:
+            # NaN / Inf in the hoppings: TBK_ERR_NOT_FINITE -> ValueError, as for eigh
+            handles, n_handles = self._handle_array()
+            _lib.check(
+                _lib.lib().tbk_dynamic_orbital_susceptibility_multi(handles, n_handles, _lib.ptr(mesh_array), mode, value, t_value,
+                                                                    vectors.shape[0], _lib.ptr(vectors), frequencies.shape[0],
+                                                                    _lib.ptr(frequencies), eta_value, chosen.shape[0], _lib.ptr(chosen),
+                                                                    int(convention), _lib.ptr(pos), _lib.ptr(mu), _lib.ptr(chi))
+            )
+        return DynamicOrbitalSusceptibility(FermiLevel(float(mu[0]), float(mu[1]), float(mu[2]), float(mu[3])), vectors, frequencies, selected,
+                                            chi)
 
     def susceptibility_tensor(self, mesh, q, *, temperature, energy=None, n_electrons=None, orbitals=None):
         """

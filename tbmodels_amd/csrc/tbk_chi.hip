@@ -59,6 +59,19 @@
 //
 // tbk_chi_orbital_plan chooses template, slice length (a function of NK and n_orb alone), slices and batch.
 //
+// The orbital-resolved dynamic chi_0[i][j](q, omega + i eta) (chi_model.dynamic_orbital_susceptibility) puts the
+// dynamic call's complex weight into the orbital call's update; the sum is not Hermitian, so every block and tile is computed and written:
+//
+//   chi_0[i][j](q, z) = -(1 / NK) sum_k sum_{b b'} g / (Delta + z) A[i; b, b'] conj(A[j; b, b'])      g, Delta as in the dynamic call
+//
+//   chi_orbital_dyn_kernel<BT, CHI_OWC>  one complex-weighted rank-K product X(omega) A^H per (vector, frequency), X = c A with
+//                       c = (g r x, -(g r eta)), x = Delta + omega, r = 1 / (x^2 + eta^2): chi_orbital_kernel's geometry and walk, all
+//                       nb^2 ordered blocks, frequencies in register chunks of CHI_OWC that share the staging of A, one complex partial
+//                       block in part[q][omega][slice][i][j].
+//   chi_reduce_orb_dyn_kernel  chi[q][omega][i][j] = (0 - the slices in index order) / NK per component, all m^2 entries.
+//
+// tbk_chi_orbital_dynamic_plan chooses template, blocks, slice length, slices, the vectors per batch and the frequency passes.
+//
 // The four-index chi_0[i][l][j][m](q) (chi_model.susceptibility_tensor; convention 2 only) keeps both orbital
 // indices of each vertex and factorises per (k, b):
 //
@@ -91,19 +104,22 @@ constexpr int64_t CHI_MAX_NK = int64_t(1) << 23;          // one grid column per
 constexpr int CHI_MAX_ORB = 16320;                      // 255 x 255 blocks of one M: one grid row each
 constexpr int CHI_WC = 8;                               // frequencies per chunk of the dynamic epilogue: 2 CHI_WC accumulators per lane
 constexpr int64_t CHI_MAX_NW = int64_t(1) << 23;          // one grid column of the dynamic reduction per frequency, 256 threads each
+constexpr int64_t CHI_GRID_YZ = 65535;                  // blocks along y or z of a grid, at most
+constexpr int64_t CHI_ORB_MAX_NW = CHI_GRID_YZ;         // orbital-resolved dynamic: one grid row of its reduction per frequency of a pass
 
 struct ChiMesh {
     int n[3];    // (n[2] = 1 in two dimensions)
     int64_t nk;  // points of the mesh
 };
 
-// the plan of a call of one of the four kinds: static (n_w = 0, m = 0), dynamic (n_w > 0), orbital-resolved (m > 0), four-index (tr > 0)
+// the plan of a call of one of the five kinds: static (n_w = 0, m = 0), dynamic (n_w > 0), orbital-resolved (m > 0), orbital-resolved
+// dynamic (m > 0 and n_w > 0), four-index (tr > 0)
 struct ChiPlan {
     ChiMesh mesh;
     int n = 0;            // orbitals
     int bt = 0;           // template of the overlap kernel: 4, 1 (up to 16 orbitals), 0: no matrix elements (chi_pair_kernel);
                           // orbital-resolved: of chi_orbital_kernel, 4, 1 (m <= 16)
-    int64_t blocks = 1;   // partials per (k, q); orbital-resolved: blocks with bi <= bj of one vector
+    int64_t blocks = 1;   // partials per (k, q); orbital-resolved: blocks with bi <= bj of one vector (dynamic: all nb^2 ordered blocks)
     int64_t batch = 1;    // vectors per launch
     int64_t batches = 1;
     int64_t n_w = 0;      // dynamic: frequencies
@@ -669,6 +685,245 @@ __global__ void __launch_bounds__(CHI_THREADS) chi_reduce_orb_kernel(const doubl
     if (i != j) out[(size_t)cj * m + ci] = make_double2(re, 0.0 - im);
 }
 
+// ---- the orbital-resolved dynamic chi_0[i][j](q, omega + i eta) ----------------------------------------------
+constexpr int CHI_OWC = 2;  // frequencies per register chunk of chi_orbital_dyn_kernel: 2 CHI_OWC BT accumulators and 2 CHI_OWC planes
+                            // of X per item (DESIGN.md 31.2 has the compiler's report of 1, 2 and 4)
+
+// chi_orb_tiles with one Y pair per tile and WC X pairs: the Y pairs of all BT tiles are read once per step of four b', then per
+// frequency of the chunk its X pair and the four real products of zmfma_abh on its own accumulators.  pl: planes 0, 1 are Yr, Yi of the
+// block's columns j, planes 2 + 2 w, 3 + 2 w are Xr, Xi of its rows i at frequency w of the chunk.  Nothing is guarded (chi_orb_tiles).
+template <int S, int BT, int WC>
+__device__ __forceinline__ void chi_orb_dyn_tiles(const double (*pl)[16][S], int ti, int lane, zd4 (&accr)[WC][BT], zd4 (&acci)[WC][BT]) {
+#pragma unroll 1
+    for (int q4 = 0; q4 < 4; ++q4) {  // (not unrolled: ZPanel's note on registers)
+        const int kq = 4 * q4 + (lane >> 4);
+        double yr[BT], yi[BT];
+#pragma unroll
+        for (int tj = 0; tj < BT; ++tj) {
+            yr[tj] = pl[0][kq][tj * 16 + (lane & 15)];
+            yi[tj] = pl[1][kq][tj * 16 + (lane & 15)];
+        }
+#pragma unroll
+        for (int w = 0; w < WC; ++w) {
+            const double xr = pl[2 + 2 * w][kq][ti * 16 + (lane & 15)], xi = pl[3 + 2 * w][kq][ti * 16 + (lane & 15)];
+#pragma unroll
+            for (int tj = 0; tj < BT; ++tj) zmfma_abh(xr, xi, yr[tj], yi[tj], accr[w][tj], acci[w][tj]);
+        }
+    }
+}
+
+// One complex-weighted rank-K update per (vector, frequency), K = (k, b, b') of a slice of k-points: sum X(omega) Y^H with Y = A,
+// X = c A, c = g / (Delta + omega + i eta) = (g r x, -(g r eta)), x = Delta + omega, r = 1 / (x^2 + eta^2), g = chi_pair_difference and
+// Delta = E[k][b] - E[k+q][b'] (one rounding).  The geometry, the staging and the walk of K are chi_orbital_kernel's; the sum is not
+// Hermitian, so all nb^2 ordered blocks (bi, bj) = (blockIdx.y / nb, blockIdx.y % nb) and all tiles of a block are computed and
+// written (tiles of the padding are multiplied and not written).  Frequencies go in register chunks of WC: per panel A is formed once
+// (the Y planes), per frequency of the chunk X = c A goes to its own two planes and its own accumulators; a short last chunk is filled
+// with copies of its last frequency, which are computed and not stored, so every frequency runs the same instructions.  g and Delta are
+// made once per (k, b, b') and chunk where chi_orbital_kernel makes t, the WC complex weights from them go to LDS ahead of the panels
+// that read them.  grid: (slices / KPW, nb^2, vectors of the batch x chunks of the pass); W: the nw frequencies of the pass, device
+// memory.  One complex partial block per (q, omega, slice) goes to part[q][omega][slice][mp][mp].
+template <int BT, int WC>
+__global__ void __launch_bounds__(CHI_THREADS) chi_orbital_dyn_kernel(const double2* __restrict__ U, const double* __restrict__ E,
+                                                                      const double* __restrict__ tab, ChiMesh g, int n,
+                                                                      const int32_t* __restrict__ Q, const double2* __restrict__ D, double inv_t,
+                                                                      const int32_t* __restrict__ orb, int m, int mp, int64_t ks, int64_t slices,
+                                                                      const double* __restrict__ W, int nw, double eta,
+                                                                      double2* __restrict__ part) {
+    using Geo = ZPanel<BT>;  // (tbk_zmfma.h; an item is a slice)
+    constexpr int RB = Geo::RB, KPW = Geo::KPW, TEAM = Geo::TEAM, S = Geo::S;
+    static_assert(CHI_THREADS == Geo::THREADS, "the panel's workgroup");
+    constexpr int STEP = TEAM / 16;                    // rows between the four a thread stages
+    __shared__ double planes[KPW][2 + 2 * WC][16][S];  // Yr, Yi of the block's columns j; per frequency Xr, Xi of its rows i
+    __shared__ double cw[KPW][WC][2][TEAM];            // c[omega][b'] of TEAM b' at once: one chi_pair_difference per (k, b, b')
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int team = BT == 1 ? wave : 0, tt = tid - team * TEAM;
+    const int nb = mp / RB;
+    const int bi = (int)blockIdx.y / nb, bj = (int)blockIdx.y - bi * nb;
+    const int64_t sl = (int64_t)blockIdx.x * KPW + team;
+    const int chunks = (nw + WC - 1) / WC;
+    const int64_t ql = blockIdx.z / chunks;
+    const int w0 = (int)(blockIdx.z - ql * chunks) * WC;
+    const bool live = sl < slices;
+    const int64_t k0 = live ? sl * ks : 0, k1 = live ? (k0 + ks < g.nk ? k0 + ks : g.nk) : 0;
+    const double2* Dq = D ? D + (size_t)ql * n : nullptr;
+    double(*pl)[16][S] = planes[team];
+    double(*cwt)[2][TEAM] = cw[team];
+    const int ti = BT == 1 ? 0 : wave;               // the wave's tile row
+    const bool row_live = bi * RB + ti * 16 < m;     // (wave-uniform)
+    const bool diag = bi == bj;
+    const double eta2 = eta * eta;
+    double om[WC];
+#pragma unroll
+    for (int w = 0; w < WC; ++w) om[w] = W[w0 + w < nw ? w0 + w : nw - 1];
+    zd4 accr[WC][BT], acci[WC][BT];
+#pragma unroll
+    for (int w = 0; w < WC; ++w)
+#pragma unroll
+        for (int tj = 0; tj < BT; ++tj) accr[w][tj] = acci[w][tj] = zd4{0.0, 0.0, 0.0, 0.0};
+    // (the accumulators' home is the AGPRs, as in chi_orbital_kernel: the empty statements behind the loops)
+    const int sb = tt & 15, srow0 = tt >> 4;  // the b' (row of the panel) and the first orbital row this thread stages
+    int oi[4], oj[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int pi = bi * RB + srow0 + r * STEP, pj = bj * RB + srow0 + r * STEP;
+        oi[r] = pi < m ? orb[pi] : -1;
+        oj[r] = pj < m ? orb[pj] : -1;
+    }
+    const int64_t items = g.nk * n;
+    const int64_t kn = BT == 1 ? ks : k1 - k0;  // (<1>: a team past its slice keeps the barriers; <4>: one slice, its own length)
+    for (int64_t kk = 0; kk < kn; ++kk) {
+        const int64_t k = k0 + kk;
+        const bool valid = BT != 1 || k < k1;  // (uniform in the team)
+        const int64_t kp = valid ? chi_shifted(g, k, Q + ql * 3) : 0;
+        const double2* Uk = U + (valid ? (size_t)k * n * n : 0);
+        const double2* Up = U + (size_t)kp * n * n;
+        const double *Ea = E + (valid ? (size_t)k * n : 0), *Eb = E + (size_t)kp * n;
+        const double *fa = tab + (valid ? (size_t)k * n : 0), *ga = fa + items, *fb = tab + (size_t)kp * n, *gb = fb + items;
+        // (<4> loads the thread's entries of U[k+q] one panel ahead, <1> where it stages: chi_orbital_kernel's note)
+        double2 ui[4], uj[4];
+        auto fetch = [&](int p0) {
+            const int bp = p0 + sb;
+            const bool in = valid && bp < n;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                ui[r] = uj[r] = make_double2(0.0, 0.0);
+                if (in && oi[r] >= 0) ui[r] = Up[(size_t)oi[r] * n + bp];
+                if (!diag && in && oj[r] >= 0) uj[r] = Up[(size_t)oj[r] * n + bp];
+            }
+        };
+        if constexpr (BT != 1) fetch(0);
+        for (int b = 0; b < n; ++b) {
+            // conj(U[k][i][b]) D[i] of the thread's rows: one value per i and b
+            double2 ci[4], cj[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                ci[r] = cj[r] = make_double2(0.0, 0.0);
+                if (valid && oi[r] >= 0) {
+                    const double2 u = Uk[(size_t)oi[r] * n + b];
+                    ci[r] = make_double2(u.x, -u.y);
+                    if (Dq) ci[r] = chi_cmul(ci[r], Dq[oi[r]]);
+                }
+                if (!diag && valid && oj[r] >= 0) {
+                    const double2 u = Uk[(size_t)oj[r] * n + b];
+                    cj[r] = make_double2(u.x, -u.y);
+                    if (Dq) cj[r] = chi_cmul(cj[r], Dq[oj[r]]);
+                }
+            }
+            const double ea = Ea[b], fav = fa[b], gav = ga[b];
+            for (int s0 = 0; s0 < n; s0 += TEAM) {
+                {
+                    // (the panels that read the previous weights are behind their second barrier)
+                    const int bp = s0 + tt;
+                    const bool in = valid && bp < n;
+                    const double gd = in ? chi_pair_difference(ea, fav, gav, Eb[bp], fb[bp], gb[bp], inv_t) : 0.0;
+                    const double delta = in ? ea - Eb[bp] : 0.0;
+#pragma unroll
+                    for (int w = 0; w < WC; ++w) {
+                        const double x = delta + om[w];
+                        const double r = 1.0 / fma(x, x, eta2);
+                        const double gr = gd * r;
+                        cwt[w][0][tt] = gr * x;
+                        cwt[w][1][tt] = -(gr * eta);
+                    }
+                }
+                const int s1 = s0 + TEAM < n ? s0 + TEAM : n;
+                for (int p0 = s0; p0 < s1; p0 += 16) {
+                    __syncthreads();  // the previous panel has been read, the weights are written
+                    const int bp = p0 + sb;
+                    const bool in = valid && bp < n;
+                    double2 c[WC];
+#pragma unroll
+                    for (int w = 0; w < WC; ++w) c[w] = make_double2(cwt[w][0][bp - s0], cwt[w][1][bp - s0]);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = srow0 + r * STEP;
+                        double2 vi = make_double2(0.0, 0.0), vj = vi;
+                        if constexpr (BT == 1) {
+                            if (in && oi[r] >= 0) vi = Up[(size_t)oi[r] * n + bp];
+                            if (!diag && in && oj[r] >= 0) vj = Up[(size_t)oj[r] * n + bp];
+                        } else {
+                            vi = ui[r];
+                            vj = uj[r];
+                        }
+                        const double2 ai = chi_cmul(ci[r], vi);
+                        const double2 aj = diag ? ai : chi_cmul(cj[r], vj);
+                        pl[0][sb][row] = aj.x;
+                        pl[1][sb][row] = aj.y;
+#pragma unroll
+                        for (int w = 0; w < WC; ++w) {
+                            const double2 xw = chi_cmul(c[w], ai);
+                            pl[2 + 2 * w][sb][row] = xw.x;
+                            pl[3 + 2 * w][sb][row] = xw.y;
+                        }
+                    }
+                    if constexpr (BT != 1) fetch(p0 + 16 < n ? p0 + 16 : 0);
+                    __syncthreads();
+                    // No branch around the MFMAs in either template (chi_orb_tiles' note; with two frequencies chi_orbital_kernel<1>'s
+                    // guard costs 16 v_accvgpr moves per step here): a dead row and a team past its slice have staged zeros, which
+                    // leave every sum as it is up to the sign of a zero, and the reduction adds the partials to +0
+                    chi_orb_dyn_tiles<S, BT, WC>(pl, ti, lane, accr, acci);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int w = 0; w < WC; ++w)
+#pragma unroll
+        for (int tj = 0; tj < BT; ++tj) asm volatile("" : "+a"(accr[w][tj]), "+a"(acci[w][tj]));  // (see at the accumulators' declaration)
+    if (!live || !row_live) return;
+    // lane (q, c), register r: row q + 4 r, column c of the tile
+#pragma unroll
+    for (int w = 0; w < WC; ++w) {
+        if (w0 + w >= nw) continue;  // (a copy of the chunk's last frequency)
+        double2* out = part + (((size_t)ql * nw + (w0 + w)) * slices + sl) * mp * mp;
+#pragma unroll
+        for (int tj = 0; tj < BT; ++tj) {
+            if (bj * RB + tj * 16 < m) {
+                const int gj = bj * RB + tj * 16 + (lane & 15);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int gi = bi * RB + ti * 16 + (lane >> 4) + 4 * r;
+                    out[(size_t)gi * mp + gj] = make_double2(accr[w][tj][r], acci[w][tj][r]);
+                }
+            }
+        }
+    }
+}
+
+// chi[q][w_first + omega][perm[i]][perm[j]] = (0 - the slices of part[q][omega][.][i][j] in index order) / NK per component: one
+// thread per (q, omega, i, j) of the ascending list over all m^2 entries, perm its places in the caller's order.  Four loads are in
+// flight ahead of the ordered adds.  grid: (elements / 256, frequencies of the pass, vectors of the batch); chi: the batch's rows of
+// [n_q][n_w][m][m]
+__global__ void __launch_bounds__(CHI_THREADS) chi_reduce_orb_dyn_kernel(const double2* __restrict__ part, int m, int mp, int64_t slices,
+                                                                         double nk, int64_t n_w, int64_t w_first,
+                                                                         const int32_t* __restrict__ perm, double2* __restrict__ chi) {
+    const int64_t e = (int64_t)blockIdx.x * CHI_THREADS + threadIdx.x;
+    if (e >= (int64_t)m * m) return;
+    const int i = (int)(e / m), j = (int)(e - (int64_t)i * m);
+    const size_t block = (size_t)mp * mp;
+    const double2* p = part + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * slices * block + (size_t)i * mp + j;
+    double re = 0.0, im = 0.0;
+    int64_t s = 0;
+    for (; s + 4 <= slices; s += 4) {
+        const double2 v0 = p[(size_t)s * block], v1 = p[(size_t)(s + 1) * block], v2 = p[(size_t)(s + 2) * block], v3 = p[(size_t)(s + 3) * block];
+        re += v0.x;
+        im += v0.y;
+        re += v1.x;
+        im += v1.y;
+        re += v2.x;
+        im += v2.y;
+        re += v3.x;
+        im += v3.y;
+    }
+    for (; s < slices; ++s) {
+        const double2 v = p[(size_t)s * block];
+        re += v.x;
+        im += v.y;
+    }
+    double2* out = chi + ((size_t)blockIdx.z * n_w + w_first + blockIdx.y) * m * m;
+    out[(size_t)perm[i] * m + perm[j]] = make_double2((0.0 - re) / nk, (0.0 - im) / nk);
+}
+
 // ---- the four-index chi_0[i][l][j][m](q) ---------------------------------------------------------------------
 constexpr int CHI_TEN_MAX = 16;  // selected orbitals, at most: X is 136 x 256 then
 constexpr int CHI_TEN_RB = 64;   // rows and columns of a workgroup's block of X
@@ -997,6 +1252,36 @@ void chi_orb_plan_sizes(int64_t nk, int n_orb, int m, int64_t n_q, size_t mem, i
     L->batches = L->batch == 0 ? 0 : (n_q + L->batch - 1) / L->batch;
 }
 
+// the orbital-resolved dynamic call's: template, all nb^2 blocks, chi_orb_slice's slice length (a function of (NK, n_orb) alone; k_slice =
+// 0: the library's), and chi_dyn_plan_sizes' split with 16 slices mp^2 bytes per (q, omega): all frequencies of a vector in one launch
+// when they fit (then as many vectors as fit, and as the grid's z takes with their register chunks), else one vector per batch and the
+// frequencies in passes, whole chunks of CHI_OWC when one fits
+void chi_orb_dyn_plan_sizes(int64_t nk, int n_orb, int m, int64_t n_q, int64_t n_w, size_t mem, int64_t k_slice, ChiPlan* L) {
+    L->n = n_orb;
+    L->m = m;
+    L->bt = m <= 16 ? 1 : 4;
+    const int rb = 16 * L->bt;
+    const int64_t nb = (m + rb - 1) / rb;
+    L->mp = (int)(nb * rb);
+    L->blocks = nb * nb;
+    L->ks = k_slice > 0 ? std::min(k_slice, nk) : chi_orb_slice(nk, n_orb);
+    L->slices = (nk + L->ks - 1) / L->ks;
+    L->n_w = n_w;
+    const size_t per_qw = (size_t)L->slices * L->mp * L->mp * sizeof(double2);
+    const size_t room = mem == 0 ? CHI_PART_BUDGET : mem;
+    const int64_t fit = (int64_t)std::min<size_t>(room / per_qw, (size_t)1 << 62);  // (q, omega) pairs whose partials fit
+    if (fit >= n_w) {
+        const int64_t chunks = (n_w + CHI_OWC - 1) / CHI_OWC;
+        L->w_pass = n_w;
+        L->batch = std::min(std::min<int64_t>(std::min(n_q, CHI_MAX_BATCH), fit / n_w), CHI_GRID_YZ / chunks);
+    } else {
+        L->w_pass = fit >= CHI_OWC ? fit / CHI_OWC * CHI_OWC : fit;
+        L->batch = fit >= 1 ? 1 : 0;
+    }
+    L->passes = L->w_pass == 0 ? 0 : (n_w + L->w_pass - 1) / L->w_pass;
+    L->batches = L->batch == 0 ? 0 : (n_q + L->batch - 1) / L->batch;
+}
+
 constexpr int64_t CHI_TEN_AMORTISE = 8;   // panels of 16 b a slice walks at least per register-resident block (64 KiB of partials)
 constexpr int64_t CHI_TEN_SLICES = 256;   // slices of one vector, about: with up to 12 blocks each, workgroups for every compute unit
 
@@ -1039,6 +1324,8 @@ int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, i
     L.n_w = n_w;
     if (m > 0 && tensor)
         chi_ten_plan_sizes(nk, n_orb, m, n_q, mem, k_slice, &L);
+    else if (m > 0 && n_w > 0)
+        chi_orb_dyn_plan_sizes(nk, n_orb, m, n_q, n_w, mem, k_slice, &L);
     else if (m > 0)
         chi_orb_plan_sizes(nk, n_orb, m, n_q, mem, k_slice, &L);
     else if (n_w == 0)
@@ -1047,8 +1334,8 @@ int chi_plan(int dim, const int32_t* mesh, int64_t nk, int n_orb, int64_t n_q, i
         chi_dyn_plan_sizes(nk, n_orb, n_q, n_w, matrix_elements, mem, &L.bt, &L.blocks, &L.batch, &L.batches, &L.w_pass, &L.passes);
     if (L.batch < 1) {
         if (m > 0)
-            tbk_set_error("the partial sums of one %s susceptibility vector need %zu bytes of device memory", tensor ? "four-index" : "orbital-resolved",
-                          L.per_q());
+            tbk_set_error("the partial sums of one %s susceptibility vector%s need %zu bytes of device memory",
+                          tensor ? "four-index" : "orbital-resolved", n_w == 0 ? "" : " at one frequency", L.per_q());
         else
             tbk_set_error("the partial sums of one susceptibility vector%s need %zu bytes of device memory", n_w == 0 ? "" : " at one frequency",
                           L.per_q());
@@ -1119,6 +1406,39 @@ int chi_launch_orb_batch(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, cons
     return TBK_OK;
 }
 
+// the orbital-resolved dynamic call's: nq vectors (at most L.batch), every pass of the frequencies d_W[L.n_w]; d_chi: their
+// [.][L.n_w][m][m] complex.  The spans are the static call's: 1 = the rank-K update, 2 = the reduction.
+int chi_launch_orb_dyn_batch(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, const double* d_tab,
+                             const int32_t* d_Q, const double* d_D, const int32_t* d_lists, int64_t nq, double T, const double* d_W, double eta,
+                             double* d_part, double* d_chi) {
+    const double inv_t = 1.0 / T;
+    const int64_t elements = (int64_t)L.m * L.m;
+    const double2* D = reinterpret_cast<const double2*>(d_D);
+    for (int64_t w0 = 0; w0 < L.n_w; w0 += L.w_pass) {
+        const int nw = (int)std::min(L.w_pass, L.n_w - w0);
+        const int64_t chunks = (nw + CHI_OWC - 1) / CHI_OWC;
+        if (ev) ev->start(1);
+        if (L.bt == 1) {
+            hipLaunchKernelGGL((chi_orbital_dyn_kernel<1, CHI_OWC>), dim3((unsigned)((L.slices + 3) / 4), 1, (unsigned)(nq * chunks)),
+                               dim3(CHI_THREADS), 0, s, reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q, D, inv_t, d_lists, L.m,
+                               L.mp, L.ks, L.slices, d_W + w0, nw, eta, reinterpret_cast<double2*>(d_part));
+        } else {
+            hipLaunchKernelGGL((chi_orbital_dyn_kernel<4, CHI_OWC>), dim3((unsigned)L.slices, (unsigned)L.blocks, (unsigned)(nq * chunks)),
+                               dim3(CHI_THREADS), 0, s, reinterpret_cast<const double2*>(d_U), d_E, d_tab, L.mesh, L.n, d_Q, D, inv_t, d_lists, L.m,
+                               L.mp, L.ks, L.slices, d_W + w0, nw, eta, reinterpret_cast<double2*>(d_part));
+        }
+        if (ev) ev->stop();
+        TBK_HIP(hipGetLastError());
+        if (ev) ev->start(2);
+        hipLaunchKernelGGL(chi_reduce_orb_dyn_kernel, dim3((unsigned)((elements + CHI_THREADS - 1) / CHI_THREADS), (unsigned)nw, (unsigned)nq),
+                           dim3(CHI_THREADS), 0, s, reinterpret_cast<const double2*>(d_part), L.m, L.mp, L.slices, (double)L.mesh.nk, L.n_w, w0,
+                           d_lists + L.m, reinterpret_cast<double2*>(d_chi));
+        if (ev) ev->stop();
+        TBK_HIP(hipGetLastError());
+    }
+    return TBK_OK;
+}
+
 // the four-index call's: nq vectors (at most L.batch); d_lists: chi_orb_lists' on the device; d_chi: their [.][m][m][m][m] complex
 int chi_launch_ten_batch(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, const double* d_tab,
                          const int32_t* d_Q, const int32_t* d_lists, int64_t nq, double T, double* d_part, double* d_chi) {
@@ -1140,7 +1460,7 @@ int chi_launch_ten_batch(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, cons
 
 // The Fermi tables once, then all batches of n_q vectors whose reduced entries (and phases) are on the device, by the plan's kind:
 // d_chi [n_q], [n_q][L.n_w] complex with the frequencies d_W of a dynamic call, or [n_q][m][m] complex with the orbital-resolved
-// call's d_lists, or [n_q][m][m][m][m] complex with the four-index call's
+// call's d_lists (with both [n_q][L.n_w][m][m] complex), or [n_q][m][m][m][m] complex with the four-index call's
 int chi_launch_all(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const double* d_U, const double* d_E, double* d_tab, const int32_t* d_Q,
                    const double* d_D, const int32_t* d_lists, int64_t n_q, double mu, double T, const double* d_W, double eta, double* d_part,
                    double* d_chi) {
@@ -1152,6 +1472,9 @@ int chi_launch_all(hipStream_t s, const ChiPlan& L, SpanRecorder* ev, const doub
         if (L.tr > 0)
             TBK_CHECK(chi_launch_ten_batch(s, L, ev, d_U, d_E, d_tab, Q, d_lists, nq, T, d_part,
                                            d_chi + (size_t)q0 * L.m * L.m * L.m * L.m * 2));
+        else if (L.m > 0 && L.n_w > 0)
+            TBK_CHECK(chi_launch_orb_dyn_batch(s, L, ev, d_U, d_E, d_tab, Q, D, d_lists, nq, T, d_W, eta, d_part,
+                                               d_chi + (size_t)q0 * L.n_w * L.m * L.m * 2));
         else if (L.m > 0)
             TBK_CHECK(chi_launch_orb_batch(s, L, ev, d_U, d_E, d_tab, Q, D, d_lists, nq, T, d_part, d_chi + (size_t)q0 * L.m * L.m * 2));
         else if (L.n_w > 0)
@@ -1170,15 +1493,20 @@ int chi_check(double T, int64_t n_q, const int64_t* q, const double* chi_out, in
     return TBK_OK;
 }
 
-int chi_check_frequencies(int64_t n_w, const double* omega, double eta) {
+int chi_check_frequencies(int64_t n_w, const double* omega, double eta, bool orbital) {
+    if (orbital)
+        return pair_check_frequencies(n_w, CHI_ORB_MAX_NW, omega, eta,
+                                      "the orbital-resolved dynamic susceptibility takes up to 65535 frequencies per call");
     return pair_check_frequencies(n_w, CHI_MAX_NW, omega, eta, "the dynamic susceptibility takes up to 2^23 frequencies per call");
 }
 
 constexpr const char* CHI_FAMILY = "the susceptibility";
 
-// the bytes of one vector's result: a double, n_w complex numbers, the m x m complex matrix or the m x m x m x m complex tensor
+// the bytes of one vector's result: a double, n_w complex numbers, the m x m complex matrix (one per frequency of an orbital-resolved
+// dynamic call) or the m x m x m x m complex tensor
 size_t chi_out_per_q(const ChiFreq& fr, const ChiOrb& ob) {
     if (ob.on && ob.tensor) return (size_t)ob.m * ob.m * ob.m * ob.m * sizeof(double2);
+    if (ob.on && fr.n_w != 0) return (size_t)fr.n_w * ob.m * ob.m * sizeof(double2);
     return ob.on ? (size_t)ob.m * ob.m * sizeof(double2) : fr.n_w == 0 ? sizeof(double) : (size_t)fr.n_w * sizeof(double2);
 }
 
@@ -1203,7 +1531,7 @@ static int chi_from_eigensystem(int device, int dim, const int32_t* mesh, int n_
     TBK_ARG(E != nullptr, "E is NULL");
     TBK_ARG(std::isfinite(mu), "the chemical potential is not finite");
     TBK_CHECK(chi_check(T, n_q, q, chi_out, n_orb));
-    if (fr.n_w != 0) TBK_CHECK(chi_check_frequencies(fr.n_w, fr.omega, fr.eta));
+    if (fr.n_w != 0) TBK_CHECK(chi_check_frequencies(fr.n_w, fr.omega, fr.eta, ob.on));
     TBK_ARG(U != nullptr || !ob.on, "U is NULL: the orbital-resolved susceptibility needs the eigenvectors");
     TBK_ARG(U != nullptr || phases == nullptr, "phases without eigenvectors");
     std::vector<int32_t> h_lists;
@@ -1249,7 +1577,7 @@ static int chi_whole_call(tbk_model* const* handles, int n_handles, const int32_
     TBK_ARG(mode == 0 || mode == 1, "mode must be 0 (value = energy) or 1 (value = n_electrons)");
     TBK_ARG(handles != nullptr && n_handles >= 1 && handles[0] != nullptr, "no handles");
     TBK_CHECK(chi_check(T, n_q, q, chi_out, handles[0]->n_orb));
-    if (fr.n_w != 0) TBK_CHECK(chi_check_frequencies(fr.n_w, fr.omega, fr.eta));
+    if (fr.n_w != 0) TBK_CHECK(chi_check_frequencies(fr.n_w, fr.omega, fr.eta, ob.on));
     TBK_CHECK(tbk_eigh_check_arguments(0, convention, pos));
     if (mode == 1)
         TBK_CHECK(tbk_fermi_check_electrons(value, handles[0]->n_orb));
@@ -1442,4 +1770,51 @@ extern "C" int tbk_susceptibility_tensor_multi(tbk_model* const* handles, int n_
 extern "C" int tbk_susceptibility_tensor(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q, const int64_t* q,
                                          int n_sel, const int32_t* orbitals, double* mu_out, double* chi_out) {
     return tbk_susceptibility_tensor_multi(&m, 1, mesh, mode, value, T, n_q, q, n_sel, orbitals, mu_out, chi_out);
+}
+
+// ---- the orbital-resolved dynamic chi_0[i][j](q, omega + i eta) -------------------------------------------------------------------
+extern "C" int tbk_chi_orbital_dynamic_plan(int64_t nk, int n_orb, int m, int64_t n_q, int64_t n_w, int64_t part_bytes, int64_t k_slice,
+                                            int64_t* out) {
+    TBK_ARG(nk >= 1 && n_orb >= 1 && n_orb <= CHI_MAX_ORB && m >= 1 && m <= n_orb && n_q >= 1 && n_w >= 1 && n_w <= CHI_ORB_MAX_NW &&
+                part_bytes >= 0 && k_slice >= 0 && out != nullptr,
+            "nk / n_orb / m / n_q / n_w < 1, more than 16320 orbitals or 65535 frequencies, m > n_orb, part_bytes / k_slice < 0 or out is NULL");
+    ChiPlan L;
+    chi_orb_dyn_plan_sizes(nk, n_orb, m, n_q, n_w, (size_t)part_bytes, k_slice, &L);
+    out[0] = L.bt;
+    out[1] = L.blocks;
+    out[2] = L.ks;
+    out[3] = L.slices;
+    out[4] = CHI_OWC;
+    out[5] = L.batch;
+    out[6] = L.batches;
+    out[7] = L.w_pass;
+    out[8] = L.passes;
+    out[9] = L.batch * L.w_pass;
+    return TBK_OK;
+}
+
+extern "C" int tbk_chi_orbital_dynamic_from_eigensystem(int device, int dim, const int32_t* mesh, int n_orb, const double* E, const double* U,
+                                                        double mu, double T, int64_t n_q, const int64_t* q, const double* phases, int m,
+                                                        const int32_t* orbitals, int64_t n_w, const double* omega, double eta,
+                                                        int64_t part_bytes, int64_t k_slice, double* chi_out) {
+    TBK_ARG(part_bytes >= 0 && k_slice >= 0, "part_bytes / k_slice < 0");
+    TBK_ARG(n_w >= 1, "n_w < 1");
+    return chi_from_eigensystem(device, dim, mesh, n_orb, E, U, mu, T, n_q, q, phases, ChiFreq{n_w, omega, eta}, ChiOrb{true, m, orbitals},
+                                (size_t)part_bytes, k_slice, chi_out);
+}
+
+extern "C" int tbk_dynamic_orbital_susceptibility_multi(tbk_model* const* handles, int n_handles, const int32_t* mesh, int mode, double value,
+                                                        double T, int64_t n_q, const int64_t* q, int64_t n_w, const double* omega, double eta,
+                                                        int m, const int32_t* orbitals, int convention, const double* pos, double* mu_out,
+                                                        double* chi_out) {
+    TBK_ARG(n_w >= 1, "n_w < 1");
+    return chi_whole_call(handles, n_handles, mesh, mode, value, T, n_q, q, ChiFreq{n_w, omega, eta}, ChiOrb{true, m, orbitals}, 1, convention, pos,
+                          mu_out, chi_out);
+}
+
+extern "C" int tbk_dynamic_orbital_susceptibility(tbk_model* m, const int32_t* mesh, int mode, double value, double T, int64_t n_q,
+                                                  const int64_t* q, int64_t n_w, const double* omega, double eta, int n_sel,
+                                                  const int32_t* orbitals, int convention, const double* pos, double* mu_out, double* chi_out) {
+    return tbk_dynamic_orbital_susceptibility_multi(&m, 1, mesh, mode, value, T, n_q, q, n_w, omega, eta, n_sel, orbitals, convention, pos, mu_out,
+                                                    chi_out);
 }

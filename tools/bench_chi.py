@@ -21,6 +21,11 @@ vectors, measured in the same run; its f64 VALU rate, EPILOGUE_VALU instructions
 fraction of --valu-peak (lane-instructions per second of the whole chip); and the host route, Model.eigh + chi_model.dynamic_susceptibility,
 timed on two planes, at most two vectors and at most four frequencies and scaled.
 
+With --orbital --omegas N[,N...] it prints the table of Model.dynamic_orbital_susceptibility: silicon on 32^3 and
+the dense 64-orbital model on 24^3 with 64 of 64 and 16 of 64 orbitals, NQ = 1 and 8, NW from the list; the call and its three stages,
+the update per (q, omega), its executed and written flops over tbk_mfma_f64_peak, the STATIC orbital call's update stage per vector
+from the same session as the yardstick, and the host route timed on two planes at one (q, omega) and scaled (marked so).
+
 With --orbital it prints the table of Model.orbital_susceptibility instead, NQ = 1 and 8 (--orbitals m: the
 first m orbitals only): the same stages (the overlap stage is the rank-K update), the update's flops -- 2048 n n_pad per (k, q) and
 tile of 16 x 16, n_pad = n rounded up to 16 -- over its time as a fraction of tbk_mfma_f64_peak, twice: for the tiles with i <= j of
@@ -204,6 +209,71 @@ def measure_orbital(name, model, mesh, counts, m, filling, T, reps, peak_tflops)
         sys.stdout.flush()
 
 
+def measure_orbital_dynamic(name, model, mesh, counts, n_ws, m, filling, T, eta, reps, peak_tflops):
+    """The table of Model.dynamic_orbital_susceptibility: per (NQ, NW) the call, its three stages, the time per
+    (q, omega), the update's executed and written flops over the MFMA peak, and the static orbital call's update stage per vector from
+    the same session as the yardstick."""
+    lib = _lib.lib()
+    n, n_k = model.size, int(np.prod(mesh))
+    n_el = filling * n
+    m = n if m <= 0 else min(m, n)
+    chosen = None if m == n else np.arange(m)
+    n_pad, tiles = (n + 15) // 16 * 16, (m + 15) // 16
+    handle = model._staged()
+    ms, calls, plan = (ctypes.c_double * 3)(), ctypes.c_int64(0), (ctypes.c_int64 * 10)()
+    kpts = np.ascontiguousarray(dos_model.mesh_kpoints(mesh))
+    plane = int(np.prod(mesh[1:]))
+    sub_mesh = (2,) + tuple(mesh[1:])
+    model.eigh(kpts[:plane])
+    t_eigh, (eig2, vec2) = _best(lambda: model.eigh(kpts[:2 * plane]), max(1, reps - 1))
+    edges = model.band_edges(mesh)
+    width = float(edges.emax.max() - edges.emin.min())
+
+    def stages_of(call):
+        call()  # warm-up
+        t_call, result = _best(call, reps)
+        _lib.check(lib.tbk_model_set_option(handle, _lib.TBK_OPT_TIMING, 1))
+        _lib.check(lib.tbk_chi_timing(handle, ms, ctypes.byref(calls), 1))
+        best = None
+        for _ in range(reps):  # the stages of the call with the shortest update
+            call()
+            _lib.check(lib.tbk_chi_timing(handle, ms, ctypes.byref(calls), 1))
+            if best is None or ms[1] < best[1]:
+                best = list(ms)
+        model.timing(reset=True)
+        _lib.check(lib.tbk_model_set_option(handle, _lib.TBK_OPT_TIMING, 0))
+        return t_call, result, best
+
+    host_done = False
+    for n_q in counts:
+        q = np.zeros((n_q, len(mesh)), dtype=np.int64)
+        q[:, 0] = np.arange(1, n_q + 1)
+        _, _, static = stages_of(lambda: model.orbital_susceptibility(mesh, q, temperature=T, n_electrons=n_el, orbitals=chosen))
+        for n_w in n_ws:
+            omega = np.arange(n_w) * (2.0 * width / n_w)
+            t_call, result, best = stages_of(lambda: model.dynamic_orbital_susceptibility(mesh, q, omega, eta=eta, temperature=T, n_electrons=n_el,
+                                                                                        orbitals=chosen))
+            _lib.check(lib.tbk_chi_orbital_dynamic_plan(n_k, n, m, n_q, n_w, 0, 0, plan))
+            chunk, w_pass, passes = plan[4], plan[7], plan[8]
+            computed_w = sum(-(-min(w_pass, n_w - p * w_pass) // chunk) * chunk for p in range(passes))  # with the copies of short chunks
+            per_tile = 2048.0 * n * n_pad * n_k * n_q
+            issued_tiles = 16 * plan[1] if plan[0] == 4 else 1
+            executed = per_tile * issued_tiles * computed_w / (best[1] * 1e-3) / (peak_tflops * 1e12) if best[1] > 0 else float("nan")
+            written = per_tile * tiles * tiles * n_w / (best[1] * 1e-3) / (peak_tflops * 1e12) if best[1] > 0 else float("nan")
+            host = ""
+            if not host_done:
+                t_model, _ = _best(lambda: chi_model.dynamic_orbital_susceptibility(eig2, vec2, sub_mesh, q[:1], result.mu.mu, T, omega[:1], eta, None,
+                                                                                    chosen), 1)
+                host = "%.1f (scaled)" % ((t_eigh + t_model * n_q * n_w) / 2 * mesh[0] * 1e3)
+                host_done = True
+            print("| %s | %s | %d | %d | %d | %d | %d x %d, passes of %d | %.1f | %.1f | %.3f | %.3f | %.3f | %.3f | %.3f | %.3f | %.3f | %s |"
+                  % (name, "x".join(str(x) for x in mesh), n, m, n_q, n_w, plan[3], plan[2], w_pass, t_call * 1e3, t_call * 1e3 - sum(best), best[0], best[1],
+                     best[2], best[1] / (n_q * n_w), executed, written, static[1] / n_q, host))
+            print("  (%s NQ = %d NW = %d: mu = %.12g, sum of chi(q_1, omega_0) = %.12g%+.12gj)"
+                  % (name, n_q, n_w, result.mu.mu, result.chi[0, 0].sum().real, result.chi[0, 0].sum().imag))
+            sys.stdout.flush()
+
+
 def measure_tensor(name, model, mesh, counts, m, filling, T, reps, peak_tflops, host_route):
     lib = _lib.lib()
     n, n_k = model.size, int(np.prod(mesh))
@@ -306,6 +376,24 @@ def main():
               "eigensystem) ms | Fermi tables ms | rank-K update ms | reduction ms | update / MFMA peak (tiles with i <= j) | update / MFMA peak (all tiles multiplied) | today, one vector: Model.eigh "
               "to the host + tools/chi_model.py ms (two planes, scaled) |")
         print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+        if args.omegas:
+            n_ws = [int(x) for x in args.omegas.split(",")]
+            print("| model | mesh | orbitals | selected | NQ | NW | slices x k-points, frequencies per pass | Model.dynamic_orbital_susceptibility ms | of it "
+                  "outside the chi kernels ms | Fermi tables ms | complex rank-K update ms | reduction ms | update ms per (q, omega) | update / MFMA peak "
+                  "(tiles executed) | update / MFMA peak (tiles written) | STATIC Model.orbital_susceptibility update ms per vector, same session | "
+                  "today: Model.eigh to the host + tools/chi_model.py ms (two planes, one (q, omega), scaled) |")
+            print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+            counts = (1, 2) if args.quick else (1, 8)
+            data = np.load(os.path.join(ROOT, "tests", "golden", "silicon.npz"))
+            silicon = tbmodels_amd.Model.from_packed(data["R"], data["hop"], pos=data["pos"])
+            measure_orbital_dynamic("silicon", silicon, (8,) * 3 if args.quick else (32,) * 3, counts, n_ws, 0, args.filling, args.temperature, args.eta,
+                                    args.reps, tf.value)
+            r_vec, hop, _ = synthetic.dense_model_arrays(64, 64, synthetic.MODEL_SEED + 2)
+            dense = tbmodels_amd.Model.from_packed(r_vec, hop)
+            for chosen in ((0,) if args.orbitals else (0, 16)):  # 64 of 64 and 16 of 64
+                measure_orbital_dynamic("dense 64", dense, (6,) * 3 if args.quick else (24,) * 3, counts, n_ws, args.orbitals or chosen, args.filling,
+                                        args.temperature, args.eta, args.reps, tf.value)
+            return
         counts = (1, 2) if args.quick else (1, 8)
         data = np.load(os.path.join(ROOT, "tests", "golden", "silicon.npz"))
         silicon = tbmodels_amd.Model.from_packed(data["R"], data["hop"], pos=data["pos"])

@@ -22,7 +22,9 @@ The dynamic chi_0(q, omega + i eta) of DESIGN.md section 16 is `dynamic_suscepti
 form of `pair_difference` and the bound `dynamic_tolerance`.  The orbital-resolved chi_0[i][j](q) of section 17 is `orbital_susceptibility`
 (`orbital_susceptibility_naive`: F as the quotient), with the bound `orbital_tolerance`.  The four-index chi_0[i, l; j, m](q) of section
 29 is `susceptibility_tensor` (the definition), `susceptibility_tensor_factored` (the kernels' P Q form) and
-`susceptibility_tensor_naive` (F as the quotient), with the bound `tensor_tolerance`.
+`susceptibility_tensor_naive` (F as the quotient), with the bound `tensor_tolerance`.  The orbital-resolved dynamic
+chi_0[i][j](q, omega + i eta) of section 31 is `dynamic_orbital_susceptibility` (`dynamic_orbital_susceptibility_naive`: f - f' as a
+difference), with the bound `dynamic_orbital_tolerance`.
 
 `python tools/chi_model.py` prints one small case by the stable and by the naive F.  Design tooling: nothing in the product imports it.
 """
@@ -359,6 +361,95 @@ def orbital_tolerance(n_k, n, T):
     u = 2.0 ** -53
     side = (n_k * n * n + 4 * ULP_EXP + ULP_EXPM1 + 15 + ROUNDINGS_AMPLITUDES) / 4.0 + 4.0
     return 2.0 * side * u / T
+
+
+def dynamic_orbital_susceptibility(E, U, mesh, q, mu, T, omega, eta, phases=None, orbitals=None):
+    """chi_0[NQ][NW][m][m], complex, of DESIGN.md section 31, for the integer vectors ``q`` of shape (NQ, dim):
+
+        A(k, q)[i; b, b']  = conj(U[k][i][b]) D(q)[i] U[k+q][i][b']
+        chi_0[i][j](q, z)  = -(1 / NK) sum_k sum_{b b'} g(E[k][b], E[k+q][b']) / (E[k][b] - E[k+q][b'] + z) A[i; b, b'] conj(A[j; b, b'])
+
+    with z = omega + i eta and g = `pair_difference`.  ``E``, ``U``, ``phases``, ``orbitals`` as for `orbital_susceptibility`, ``omega``
+    and ``eta`` as for `dynamic_susceptibility`.  Per pair of states g and Delta = E[k][b] - E[k+q][b'] (one rounding) once; per
+    frequency, unfused and in this order, x = Delta + omega, r = 1 / (x^2 + eta^2), gr = g r, c = (gr x, -(gr eta)); X = c A, and per
+    k-point one matrix product X A^H (reshaped to (m, n^2)) so that BLAS does the n^4 part.  The sum is taken away from +0 and divided by
+    NK per component, so that a sum of zeros of either sign gives +0.  The matrix is not Hermitian: nothing is mirrored."""
+    E = np.asarray(E, dtype=float)
+    n = E.shape[-1]
+    flat_e = E.reshape(-1, n)
+    n_k = flat_e.shape[0]
+    q = np.asarray(q)
+    if q.dtype.kind not in "iu":
+        raise ValueError("q must be integers")
+    q = q.astype(np.int64).reshape(-1, len(mesh))
+    omega, eta = _frequencies(omega, eta)
+    chosen = _orbital_selection(orbitals, n)
+    m = chosen.size
+    flat_u = np.asarray(U).reshape(-1, n, n)
+    f, g = fermi_tables(flat_e, mu, T)
+    out = np.zeros((q.shape[0], omega.size, m, m), dtype=complex)
+    for index, vector in enumerate(q):
+        to = shifted_points(mesh, vector)
+        a, b = flat_e[:, :, None], flat_e[to][:, None, :]
+        gd = pair_difference(a, b, f[:, :, None], g[:, :, None], f[to][:, None, :], g[to][:, None, :], T)
+        delta = a - b
+        left = flat_u[:, chosen, :].conj()
+        if phases is not None:
+            left = left * np.asarray(phases)[index][None, chosen, None]
+        total = np.zeros((omega.size, m, m), dtype=complex)
+        for k in range(n_k):  # (A of one k-point at a time: m n^2 numbers)
+            y = (left[k][:, :, None] * flat_u[to[k]][chosen][:, None, :]).reshape(m, n * n)
+            yh = y.conj().T
+            for j, w in enumerate(omega):
+                x = delta[k] + w
+                gr = gd[k] * (1.0 / (x * x + eta * eta))
+                c = (gr * x + 1j * (-(gr * eta))).reshape(1, n * n)
+                total[j] += (c * y) @ yh
+        out[index] = ((0.0 - total.real) / n_k) + 1j * ((0.0 - total.imag) / n_k)
+    return out
+
+
+def dynamic_orbital_susceptibility_naive(E, U, mesh, q, mu, T, omega, eta, phases=None, orbitals=None):
+    """The formula as written, in complex arithmetic with f(a) - f(b) as the difference of two Fermi functions and one einsum over
+    (k, b, b'): for comparison where that difference is well conditioned."""
+    E = np.asarray(E, dtype=float)
+    n = E.shape[-1]
+    flat_e = E.reshape(-1, n)
+    q = np.asarray(q).astype(np.int64).reshape(-1, len(mesh))
+    omega, eta = _frequencies(omega, eta)
+    chosen = _orbital_selection(orbitals, n)
+    with np.errstate(over="ignore"):
+        occ = 1.0 / (1.0 + np.exp((flat_e - mu) / T))
+    out = np.zeros((q.shape[0], omega.size, chosen.size, chosen.size), dtype=complex)
+    for index, vector in enumerate(q):
+        to = shifted_points(mesh, vector)
+        weight = occ[:, :, None] - occ[to][:, None, :]
+        delta = flat_e[:, :, None] - flat_e[to][:, None, :]
+        amp = orbital_amplitudes(U, mesh, vector, None if phases is None else np.asarray(phases)[index], chosen)
+        for j, w in enumerate(omega):
+            out[index, j] = -np.einsum("kbc,kibc,kjbc->ij", weight / (delta + complex(w, eta)), amp, amp.conj()) / flat_e.shape[0]
+    return out
+
+
+ROUNDINGS_COMPLEX_SCALE = 3.0  # X = c A is a complex product, three roundings per component (two unfused), where ROUNDINGS_AMPLITUDES
+#                                counts one for the real scale by t: taken in full, on top
+
+
+def dynamic_orbital_tolerance(n_k, n, T, eta, spread):
+    """tol of DESIGN.md 31.5: the bound on either component of one element of chi - chi' of two evaluations (the kernels, this model)
+    of the SAME (E, U, mu, T, omega, eta), derived as `dynamic_tolerance` and `orbital_tolerance` are.  ``spread`` = 2 bandwidth +
+    |omega| (a number, or an array per frequency).  Per k the moduli of an element's terms add up to at most S = 1 in units of 1 / eta:
+    sum_{b b'} |A_i| |A_j| <= 1 by Cauchy-Schwarz on the unit rows of U(k) and U(k+q), |g| <= 1 and |1 / (x + i eta)| <= 1 / eta; an
+    error of a complex term's modulus bounds that of either component.  Per side:  the sum of NK n^2 terms in any order, NK n^2 u;  the
+    factors of a term, relative: 16.4's (4 ULP_EXP + ULP_EXPM1 + ULP_DIV + 18) for g, x and the Lorentzian, 17.5's
+    ROUNDINGS_AMPLITUDES for the two amplitudes and ROUNDINGS_COMPLEX_SCALE for the complex weight;  the unbounded part of the
+    exponential's argument error, absolute: 4 u;  the rounding of Delta + omega under the Lorentzian's slope, 16.4's: spread / eta u.
+    T does not enter (kept in the signature as in `dynamic_tolerance`); no number from the kernels does."""
+    del T
+    u = 2.0 ** -53
+    factors = 4 * ULP_EXP + ULP_EXPM1 + ULP_DIV + 18 + ROUNDINGS_AMPLITUDES + ROUNDINGS_COMPLEX_SCALE
+    side = n_k * n * n + factors + 4.0 + np.asarray(spread, dtype=float) / eta
+    return 2.0 * side * u / eta
 
 
 def _tensor_arguments(E, U, mesh, q, orbitals):
